@@ -89,6 +89,10 @@ def parse():
     ap.add_argument("--from-host", action="store_true",
                     help="measurement aid, never the headline: the volumes start in pinned HOST memory and every group's "
                          "host-to-device copy is inside the timed region (on the lane's stream): the PCIe-inclusive rate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (rank 0: the last timed volume's final "
+                         "logits, per-step losses, mask counts, Dice and IoU) as DIR/<name>.npy, for output-by-output "
+                         "comparison of two builds (the inputs and weights are seeded; bench_outputs/ is git-ignored)")
     return ap.parse_args()
 
 
@@ -225,6 +229,32 @@ def post_dice_from_table(table: torch.Tensor, R: int) -> float:
     return float((dvals * vmask).sum().item() / max(1.0, float(vmask.sum().item())))
 
 
+DUMP_LIMIT_BYTES = 48 << 20     # logits above this are dumped as a fixed, seeded sample of voxels (all files < 64 MB)
+
+
+def dump_outputs(dirname, plug, res, b, counts_row):
+    """What a caller of the timed path received for item `b` of the last timed group: its final logits [R,D,H,W] (or, past
+    DUMP_LIMIT_BYTES, `logits_sample`: the values at a seeded sorted sample of flat indices, the same for every run of the
+    same shape), its per-step losses [S], and the mask counts [R,3] (intersection, predicted, ground truth) with the Dice
+    and IoU they give."""
+    import numpy as np
+    from multimodal_tta_amd.evaluation import dice_iou_from_counts
+    os.makedirs(dirname, exist_ok=True)
+    logits = plug.logits(res)[b].float().cpu().numpy()
+    losses = res["losses"]
+    losses = (losses[:, b] if losses.dim() == 2 else losses).float().cpu().numpy()
+    dice, iou, _ = dice_iou_from_counts(counts_row.view(1, -1, 3).cpu())
+    arrays = {"losses": losses, "mask_counts": counts_row.cpu().numpy().astype(np.float64),
+              "dice": dice[0].numpy(), "iou": iou[0].numpy()}
+    if logits.nbytes <= DUMP_LIMIT_BYTES:
+        arrays["logits"] = logits
+    else:
+        pick = np.sort(np.random.default_rng(0).choice(logits.size, DUMP_LIMIT_BYTES // 4, replace=False))
+        arrays["logits_sample"] = logits.reshape(-1)[pick]
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", 0))
@@ -327,7 +357,9 @@ def main():
         return _host[key]
 
     def run_volumes(plugs_, streams_, first, last, counts_, group_=None):
+        """Adapts the volumes [first, last); returns (plugin, result, volume indices) of the last group launched."""
         group_ = group if group_ is None else group_
+        done = None
         for k, idx in schedule(first, last, group_, len(plugs_)):
             lane = k % len(plugs_)
             x, y = group_tensors(idx)
@@ -337,6 +369,8 @@ def main():
                     x, y = hx.to(device, non_blocking=True), hy.to(device, non_blocking=True)
                 res = plugs_[lane].adapt_volume(x)
                 ops.mask_dice_counts(res["logits_cl"], y, thr, counts_[idx[0] % nvol:idx[0] % nvol + len(idx)], None)
+            done = (plugs_[lane], res, idx)
+        return done
 
     plugs, streams = make_lanes(cfg, lanes, streams_=lane_streams)
     plug = plugs[0]
@@ -351,7 +385,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_volumes(plugs, streams, args.warmup, nvol, counts)
+    last = run_volumes(plugs, streams, args.warmup, nvol, counts)
     torch.cuda.synchronize()
     t_local = time.perf_counter() - t0
     rows = bench_rows(counts[args.warmup:].cpu(), rank, world)
@@ -369,6 +403,10 @@ def main():
     elapsed, t_local_max, t_local_min, t_gather = float(t[0]), float(t[1]), -float(t[2]), float(t[3])
     assert table.shape == (args.steps * world, table_width(R))
     post_dice = post_dice_from_table(table, R)
+    if rank == 0 and args.dump_outputs:
+        # before anything else runs on the lanes' buffers (the profile pass and the variants reuse them)
+        plug_last, res_last, idx_last = last
+        dump_outputs(args.dump_outputs, plug_last, res_last, len(idx_last) - 1, counts[idx_last[-1] % nvol])
 
     out = {
         "metric": "adapted volumes/sec", "value": args.steps * world / elapsed, "unit": "volumes/s",

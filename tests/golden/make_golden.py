@@ -1,11 +1,11 @@
 #!/usr/bin/env python
 """Generate the committed golden fixtures under tests/golden/.
 
-Run in the build container (needs /root/reference for the registry capture; everything else comes
-from the oracle, which restates the reference path with torch CPU - see oracle/__init__.py for why
-parity is otherwise unpinned).  Outputs are DATA only (JSON / npz): inputs and expected outputs.
+Needs a checkout of the reference for the registry capture (its root, the directory holding src/registry.py, is the
+first argument); everything else comes from the oracle, which restates the reference path with torch CPU - see
+oracle/__init__.py for why parity is otherwise unpinned.  Outputs are DATA only (JSON / npz): inputs and expected outputs.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py /path/to/reference
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
+REF = None          # the reference checkout (command line)
 
 
 def registry_behaviour():
@@ -104,6 +104,25 @@ def model_fixture(name, cfg, shape, seed=42):
                     "state_dict_keys": list(sd0.keys()), "state_dict_shapes": [list(v.shape) for v in sd0.values()]}
 
 
+# Fixtures whose float32 `adapted_logits` carry the generating CPU's rounding beyond tests/test_oracle.py's tolerance.
+# Adam's first step moves a parameter by ~lr * g / (|g| + eps), so a parameter whose gradient is rounding noise (a conv bias
+# ahead of an InstanceNorm, a weight with a near-zero gradient) moves in the noise's direction.  For unet_hecktor_small
+# that reaches 6 voxels of the float32 result (2.1x the tolerance against the float64 result); the other fixtures stay
+# within 0.2x of it.  Their float64 results go to adapted_logits_f64.npz, which the oracle test checks against instead.
+F64_ADAPTED = ("unet_hecktor_small",)
+
+
+def adapted_logits_f64(arrays, meta):
+    """A fixture's adapted logits recomputed in float64 from its float32 weights and input (stored as float32)."""
+    import oracle
+
+    model = oracle.MODELS[meta["name"]](meta["cfg"])
+    model.load_state_dict({k: torch.from_numpy(arrays["w/" + k]) for k in meta["state_dict_keys"]})
+    model.double().train()
+    res = oracle.adapt_volume(model, torch.from_numpy(arrays["x"]).double(), meta["train_cfg"], steps=1, episodic=True)
+    return res["logits"].float().numpy()
+
+
 def default_key_lists():
     """state_dict keys + shapes of both models at the shipped default configuration."""
     import oracle
@@ -128,15 +147,17 @@ def main():
     small = dict(in_channels=4, num_classes=3, spatial_dims=3, channels=[4, 8, 16, 32, 64], strides=[2, 2, 2, 2],
                  num_res_units=2, norm="INSTANCE", act="RELU", dropout=0.0)
     metas = {}
-    arrays, metas["unet_small"] = model_fixture("unet", small, (1, 4, 32, 32, 32))
-    np.savez_compressed(os.path.join(HERE, "unet_small.npz"), **arrays)
+    fixtures = {}
+    fixtures["unet_small"], metas["unet_small"] = model_fixture("unet", small, (1, 4, 32, 32, 32))
     hk = dict(small, in_channels=2, num_classes=1)
-    arrays, metas["unet_hecktor_small"] = model_fixture("unet", hk, (1, 2, 16, 48, 48))
-    np.savez_compressed(os.path.join(HERE, "unet_hecktor_small.npz"), **arrays)
+    fixtures["unet_hecktor_small"], metas["unet_hecktor_small"] = model_fixture("unet", hk, (1, 2, 16, 48, 48))
     df = dict(small, num_modalities=4, channels=[2, 4, 8, 16, 32])
     df.pop("in_channels")
-    arrays, metas["deepfusion_small"] = model_fixture("unet_multimodal_deepfusion", df, (1, 4, 32, 32, 32))
-    np.savez_compressed(os.path.join(HERE, "deepfusion_small.npz"), **arrays)
+    fixtures["deepfusion_small"], metas["deepfusion_small"] = model_fixture("unet_multimodal_deepfusion", df, (1, 4, 32, 32, 32))
+    for name, arrays in fixtures.items():
+        np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrays)
+    np.savez_compressed(os.path.join(HERE, "adapted_logits_f64.npz"),
+                        **{name: adapted_logits_f64(fixtures[name], metas[name]) for name in F64_ADAPTED})
     with open(os.path.join(HERE, "model_fixtures.json"), "w") as fh:
         json.dump(metas, fh, indent=1)
     for f in sorted(os.listdir(HERE)):
@@ -144,4 +165,7 @@ def main():
 
 
 if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.path.exists(os.path.join(sys.argv[1], "src", "registry.py")):
+        raise SystemExit("usage: make_golden.py REFERENCE_ROOT  (the directory holding src/registry.py)")
+    REF = os.path.abspath(sys.argv[1])
     main()
