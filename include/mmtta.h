@@ -54,7 +54,8 @@ typedef struct {
 #define MMTTA_TENSOR_OWNS_PAD 1
 
 /* Per-(n,c) normalisation applied to a tensor WHEN IT IS READ ("norm on load"):
- *   v = (x - mean[n*C+c]) * rstd[n*C+c] * (gamma ? gamma[c] : 1) + (beta ? beta[c] : 0);
+ *   v = (x - mean[n*C+c]) * rstd[n*C+c] * (gamma ? gamma[a+c] : 1) + (beta ? beta[a+c] : 0),
+ *   a = per_item ? n*C : 0;
  *   if (relu) v = max(v, 0);
  * mean == NULL means "no transform".  This is MONAI's ADN (Norm -> Dropout(p=0) -> ReLU) of the
  * producing Convolution, folded into the consumer (reference:
@@ -62,10 +63,15 @@ typedef struct {
 typedef struct {
   const float* mean;  /* [N*C] or NULL */
   const float* rstd;  /* [N*C] */
-  const float* gamma; /* [C] or NULL */
-  const float* beta;  /* [C] or NULL */
+  const float* gamma; /* [C] (per_item: [N*C]) or NULL */
+  const float* beta;  /* [C] (per_item: [N*C]) or NULL */
   int32_t relu;
-  int32_t _pad;
+  /* 0: gamma / beta are one [C] vector for the whole batch.  1: they hold one [C] vector PER BATCH ITEM ([N*C], the
+   * gamma_items / beta_items of mmtta_norm_stats_finalize_sets: a group of volumes, each with its own norm affines).
+   * Every entry point that reads a norm-on-load honours it; the convolution entry points (mmtta_conv_run*, the epilogue's
+   * add_norm, mmtta_conv_wgrad*) read such a descriptor through scale / shift only and refuse one without them
+   * (MMTTA_ERR_INVALID). */
+  int32_t per_item;
   /* optional precombined form written by mmtta_norm_stats_finalize: v = x*scale[n*C+c] + shift[n*C+c].
    * When given, consumers read ONLY these two arrays (one branch-free vector load per thread instead of four
    * dependent ones); mean / rstd / gamma / beta are still what the backward kernels use. */
@@ -324,6 +330,34 @@ int mmtta_norm_stats_finalize(int kind, int groups, const float* part, int rows_
                               const float* gamma, const float* beta, float* scale, float* shift,
                               double* scratch, void* stream);
 
+/* ---- per-volume norm parameter sets: the norm layers of a group of volumes adapted side by side (mmtta_param_sets), each
+ * volume with its own norm affines and - BatchNorm - its own running statistics.  Batch item n belongs to set
+ * q = n / items_per_set; set q's gamma / beta (and dgamma / dbeta) live q * affine_stride elements behind the base pointers
+ * (the arena replica stride), its running_mean / running_var q * stats_stride elements behind theirs.  BatchNorm statistics
+ * (and the backward's m1 / m2, dgamma / dbeta) pool over THAT set's items only, in the order the plain entry point uses for
+ * a batch of items_per_set: every set computes bit for bit what the plain call computes for its items alone.  Strides must
+ * keep 16-byte alignment (multiples of 4 elements); with more than one set, affine_stride must be >= C where affine
+ * gradients are written and stats_stride >= C where running statistics are given (sets may share read-only affines with
+ * affine_stride 0, never written vectors). */
+typedef struct {
+  int32_t items_per_set; /* consecutive batch items that share a set (>= 1; must divide N) */
+  int32_t _pad;
+  int64_t affine_stride; /* ELEMENTS between the gamma / beta / dgamma / dbeta of consecutive sets */
+  int64_t stats_stride;  /* ELEMENTS between the running_mean / running_var of consecutive sets */
+} mmtta_norm_sets;
+
+/* mmtta_norm_stats_finalize over norm parameter sets: `gamma`, `beta`, `running_mean`, `running_var` are the base pointers of
+ * set 0.  training != 0 applies the EMA update to every set's running statistics (BatchNorm; once per set, from the set's
+ * batch statistics); training == 0 reads them.  gamma_items / beta_items (fp32 [N*C] or NULL; NULL when gamma / beta is
+ * NULL): each item's copy of its set's gamma / beta, the per_item arrays a mmtta_norm_on_load with per_item = 1 points at
+ * (the consumers, mmtta_norm_bwd_reduce and mmtta_norm_bwd_apply read them).  Arguments are checked before any launch. */
+int mmtta_norm_stats_finalize_sets(int kind, int groups, const float* part, int rows_per_n, int n, int c,
+                                   int64_t count, float eps, int training, float* running_mean,
+                                   float* running_var, float momentum, float* mean, float* rstd,
+                                   const float* gamma, const float* beta, float* scale, float* shift,
+                                   float* gamma_items, float* beta_items, double* scratch,
+                                   const mmtta_norm_sets* sets, void* stream);
+
 /* Rows per batch item of the partial slabs written by mmtta_channel_stats and
  * mmtta_norm_bwd_reduce for a tensor of this shape (deterministic two-stage reductions). */
 int mmtta_reduce_rows_per_n(const mmtta_tensor* t);
@@ -351,6 +385,14 @@ int mmtta_norm_bwd_reduce(const mmtta_tensor* dout, const mmtta_tensor* y, const
 int mmtta_norm_bwd_finalize(int kind, int groups, const float* part, int rows_per_n, int n, int c, int64_t count,
                             const float* gamma, int training, float* m1, float* m2, float* dgamma,
                             float* dbeta, int accumulate, double* scratch /* fp64 [N*C*2] */, void* stream);
+
+/* mmtta_norm_bwd_finalize over norm parameter sets (mmtta_norm_sets): `gamma`, `dgamma`, `dbeta` are the base pointers of
+ * set 0; m1 / m2 pool over each set's items (BatchNorm), set q's dgamma / dbeta are the sums over ITS items, written (or,
+ * accumulate != 0, added) q * affine_stride elements behind the base pointers. */
+int mmtta_norm_bwd_finalize_sets(int kind, int groups, const float* part, int rows_per_n, int n, int c, int64_t count,
+                                 const float* gamma, int training, float* m1, float* m2, float* dgamma,
+                                 float* dbeta, int accumulate, double* scratch /* fp64 [N*C*2] */,
+                                 const mmtta_norm_sets* sets, void* stream);
 
 /* Pass 3: dy = rstd * (gamma*dz - m1 - xhat*m2); dy may alias dout. */
 int mmtta_norm_bwd_apply(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,

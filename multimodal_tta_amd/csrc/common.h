@@ -221,6 +221,14 @@ inline NL nl(const mmtta_norm_on_load* t) {
   r.scale = t->scale; r.shift = t->scale ? t->shift : nullptr;
   return r;
 }
+// Per-item affines (mmtta_norm_on_load.per_item): the convolution kernels read a norm-on-load through its precombined
+// scale / shift, which are [N*C] - per item - by construction, so they honour the flag as they are; a per-item descriptor
+// without them is rejected on the host (the [C] gamma / beta indexing of nl_coeff / nl_coeff_vec stays as it is)
+inline int nl_per_item_check(const mmtta_norm_on_load* t, const char* what) {
+  MMTTA_CHECK(t == nullptr || t->per_item == 0 || t->mean == nullptr || t->scale != nullptr, MMTTA_ERR_INVALID,
+              "%s: a norm-on-load with per-item gamma / beta needs its precombined scale / shift", what);
+  return MMTTA_OK;
+}
 
 // Per-volume parameter sets (mmtta_param_sets): which set batch item n reads / writes.  Items [q * ips, (q + 1) * ips)
 // share set q; set q lives (q / inner) outer strides + (q % inner) inner strides behind the base pointer.  All-zero

@@ -2078,6 +2078,12 @@ extern "C" int mmtta_conv_run_sets(const mmtta_conv_desc* d, const mmtta_tensor*
                                    const void* packed, const float* bias, const mmtta_conv_epilogue* epi,
                                    const mmtta_tensor* y, int accumulate, float* stats, void* workspace,
                                    int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
+  {
+    const int pst = nl_per_item_check(x_norm, "conv_run (x_norm)");
+    if (pst) return pst;
+    const int ast = nl_per_item_check(epi ? &epi->add_norm : nullptr, "conv_run (epilogue add_norm)");
+    if (ast) return ast;
+  }
   Geometry g;
   int st = geometry(d, x, y, g);
   if (st) return st;

@@ -2143,11 +2143,17 @@ static int conv_wgrad_impl(const mmtta_conv_desc* d, const mmtta_tensor* x, cons
 extern "C" int mmtta_conv_wgrad(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                 const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
+  const int pst = nl_per_item_check(x_norm, "conv_wgrad (x_norm)");
+  if (pst) return pst;
   return conv_wgrad_impl(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, nullptr, stream);
 }
 
 extern "C" int mmtta_conv_wgrad_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                      const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
                                      int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
+  {
+    const int pst = nl_per_item_check(x_norm, "conv_wgrad (x_norm)");
+    if (pst) return pst;
+  }
   return conv_wgrad_impl(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream);
 }

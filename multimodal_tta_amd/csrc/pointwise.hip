@@ -41,6 +41,7 @@ struct RedArgs {
   TV x;        // MODE 0: tensor ; MODE 1: y (pre-norm)
   TV dout;     // MODE 1
   NL t;        // MODE 1
+  int per_item; // MODE 1: t's gamma / beta are [N*C] (mmtta_norm_on_load.per_item)
   float* part; // [N*rows_per_n][2][C]
   int rows_per_n;
   long long vox_per_row;
@@ -71,13 +72,14 @@ __global__ __launch_bounds__(256) void channel_reduce_kernel(RedArgs a) {
     for (int j = 0; j < VEC; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
     if (c0 < C) {
       float mu[VEC], rs[VEC], g[VEC], b[VEC];
+      const int ab = a.per_item ? n * C : 0;
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         mu[j] = 0.f; rs[j] = 1.f; g[j] = 1.f; b[j] = 0.f;
         if (MODE == 1 && a.t.mean && c0 + j < C) {
           mu[j] = a.t.mean[n * C + c0 + j]; rs[j] = a.t.rstd[n * C + c0 + j];
-          if (a.t.gamma) g[j] = a.t.gamma[c0 + j];
-          if (a.t.beta) b[j] = a.t.beta[c0 + j];
+          if (a.t.gamma) g[j] = a.t.gamma[ab + c0 + j];
+          if (a.t.beta) b[j] = a.t.beta[ab + c0 + j];
         }
       }
       for (long long v = v0 + vl; v < v1; v += nvl) {
@@ -155,12 +157,24 @@ __global__ __launch_bounds__(64) void rows_reduce_kernel(const float* part, int 
   }
 }
 
+// Norm parameter sets (mmtta_norm_sets) on the device: item n reads set q = n / ips, whose affines sit q * astride and
+// whose running statistics sit q * sstride elements behind set 0's.  The plain entry points run the same kernels with ONE
+// set spanning the batch (ips = N, strides 0), so both forms share every summation order.
+struct NSets {
+  int ips;
+  long long astride, sstride;
+};
+inline NSets nsets_plain(int n) { NSets r; r.ips = n; r.astride = 0; r.sstride = 0; return r; }
+
 // InstanceNorm fast path: one wave per (n,c) reduces the partial rows AND finishes the statistics
-// (no cross-(n,c) coupling), one launch instead of two.
+// (no cross-(n,c) coupling), one launch instead of two.  gi / bi (optional): item n's copy of its set's gamma / beta.
 __global__ __launch_bounds__(64) void instance_stats_kernel(const float* part, int rows_per_n, int C, double count, float eps,
                                                             float* mean, float* rstd, const float* gamma, const float* beta,
-                                                            float* scale, float* shift) {
+                                                            float* scale, float* shift, NSets ns, float* gi, float* bi) {
   const int n = blockIdx.x / C, c = blockIdx.x % C;
+  const long long ab = (long long)(n / ns.ips) * ns.astride;
+  if (gamma) gamma += ab;
+  if (beta) beta += ab;
   double s0 = 0.0, s1 = 0.0;
   for (int r = threadIdx.x; r < rows_per_n; r += 64) {
     const long long row = (long long)n * rows_per_n + r;
@@ -181,12 +195,15 @@ __global__ __launch_bounds__(64) void instance_stats_kernel(const float* part, i
       scale[blockIdx.x] = sc;
       shift[blockIdx.x] = (beta ? beta[c] : 0.f) - (float)mu * sc;
     }
+    if (gi != nullptr) gi[blockIdx.x] = gamma[c];
+    if (bi != nullptr) bi[blockIdx.x] = beta[c];
   }
 }
 
 __global__ __launch_bounds__(64) void instance_bwd_kernel(const float* part, int rows_per_n, int C, double count,
-                                                          const float* gamma, float* m1, float* m2) {
+                                                          const float* gamma, float* m1, float* m2, NSets ns) {
   const int n = blockIdx.x / C, c = blockIdx.x % C;
+  if (gamma) gamma += (long long)(n / ns.ips) * ns.astride;
   double s0 = 0.0, s1 = 0.0;
   for (int r = threadIdx.x; r < rows_per_n; r += 64) {
     const long long row = (long long)n * rows_per_n + r;
@@ -211,28 +228,37 @@ struct StatFinArgs {
   float* mean; float* rstd;
   const float* gamma; const float* beta; float* scale; float* shift;
   const double* tot;
+  NSets ns;
+  float* gi; float* bi;   // optional per-item copies of the set's gamma / beta
 };
 
 __global__ void stats_finalize_kernel(StatFinArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.N * a.C) return;
   const int n = i / a.C, c = i % a.C;
+  const int q = n / a.ns.ips, m0 = q * a.ns.ips;          // this item's set and its first item
+  const float* gamma = a.gamma ? a.gamma + q * a.ns.astride : nullptr;
+  const float* beta = a.beta ? a.beta + q * a.ns.astride : nullptr;
+  float* running_mean = a.running_mean ? a.running_mean + q * a.ns.sstride : nullptr;
+  float* running_var = a.running_var ? a.running_var + q * a.ns.sstride : nullptr;
+  if (a.gi != nullptr) a.gi[i] = gamma[c];
+  if (a.bi != nullptr) a.bi[i] = beta[c];
   double S = 0.0, Q = 0.0, cnt = 0.0;
   if (a.kind == MMTTA_NORM_INSTANCE) {
     S = a.tot[(long long)i * 2]; Q = a.tot[(long long)i * 2 + 1]; cnt = a.count;
   } else if (a.kind == MMTTA_NORM_BATCH) {
     if (!a.training) {
-      a.mean[i] = a.running_mean[c];
-      a.rstd[i] = (float)(1.0 / sqrt((double)a.running_var[c] + (double)a.eps));
+      a.mean[i] = running_mean[c];
+      a.rstd[i] = (float)(1.0 / sqrt((double)running_var[c] + (double)a.eps));
       if (a.scale != nullptr) {
-        const float sc = a.rstd[i] * (a.gamma ? a.gamma[c] : 1.f);
+        const float sc = a.rstd[i] * (gamma ? gamma[c] : 1.f);
         a.scale[i] = sc;
-        a.shift[i] = (a.beta ? a.beta[c] : 0.f) - a.mean[i] * sc;
+        a.shift[i] = (beta ? beta[c] : 0.f) - a.mean[i] * sc;
       }
       return;
     }
-    for (int m = 0; m < a.N; ++m) { S += a.tot[((long long)m * a.C + c) * 2]; Q += a.tot[((long long)m * a.C + c) * 2 + 1]; }
-    cnt = a.count * a.N;
+    for (int m = m0; m < m0 + a.ns.ips; ++m) { S += a.tot[((long long)m * a.C + c) * 2]; Q += a.tot[((long long)m * a.C + c) * 2 + 1]; }
+    cnt = a.count * a.ns.ips;
   } else {
     const int cg = a.C / a.groups, g0 = (c / cg) * cg;
     for (int k = g0; k < g0 + cg; ++k) { S += a.tot[((long long)n * a.C + k) * 2]; Q += a.tot[((long long)n * a.C + k) * 2 + 1]; }
@@ -244,14 +270,14 @@ __global__ void stats_finalize_kernel(StatFinArgs a) {
   a.mean[i] = (float)mu;
   a.rstd[i] = (float)(1.0 / sqrt(var + (double)a.eps));
   if (a.scale != nullptr) {
-    const float sc = a.rstd[i] * (a.gamma ? a.gamma[c] : 1.f);
+    const float sc = a.rstd[i] * (gamma ? gamma[c] : 1.f);
     a.scale[i] = sc;
-    a.shift[i] = (a.beta ? a.beta[c] : 0.f) - a.mean[i] * sc;
+    a.shift[i] = (beta ? beta[c] : 0.f) - a.mean[i] * sc;
   }
-  if (a.kind == MMTTA_NORM_BATCH && a.training && n == 0 && a.running_mean != nullptr) {
+  if (a.kind == MMTTA_NORM_BATCH && a.training && n == m0 && running_mean != nullptr) {
     const double unb = cnt > 1.0 ? var * cnt / (cnt - 1.0) : var;
-    a.running_mean[c] = (float)((1.0 - a.momentum) * a.running_mean[c] + a.momentum * mu);
-    a.running_var[c] = (float)((1.0 - a.momentum) * a.running_var[c] + a.momentum * unb);
+    running_mean[c] = (float)((1.0 - a.momentum) * running_mean[c] + a.momentum * mu);
+    running_var[c] = (float)((1.0 - a.momentum) * running_var[c] + a.momentum * unb);
   }
 }
 
@@ -262,24 +288,27 @@ struct BwdFinArgs {
   int training;
   float* m1; float* m2; float* dgamma; float* dbeta; int accumulate;
   const double* tot;
+  NSets ns;
 };
 
 __global__ void bwd_finalize_kernel(BwdFinArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.N * a.C) return;
   const int n = i / a.C, c = i % a.C;
+  const int q = n / a.ns.ips, m0 = q * a.ns.ips;          // this item's set and its first item
+  const float* gamma = a.gamma ? a.gamma + q * a.ns.astride : nullptr;
   double A = 0.0, B = 0.0, cnt = 1.0;
   if (a.kind == MMTTA_NORM_INSTANCE) {
-    const double g = a.gamma ? (double)a.gamma[c] : 1.0;
+    const double g = gamma ? (double)gamma[c] : 1.0;
     A = g * a.tot[(long long)i * 2]; B = g * a.tot[(long long)i * 2 + 1]; cnt = a.count;
   } else if (a.kind == MMTTA_NORM_BATCH) {
-    const double g = a.gamma ? (double)a.gamma[c] : 1.0;
-    for (int m = 0; m < a.N; ++m) { A += g * a.tot[((long long)m * a.C + c) * 2]; B += g * a.tot[((long long)m * a.C + c) * 2 + 1]; }
-    cnt = a.count * a.N;
+    const double g = gamma ? (double)gamma[c] : 1.0;
+    for (int m = m0; m < m0 + a.ns.ips; ++m) { A += g * a.tot[((long long)m * a.C + c) * 2]; B += g * a.tot[((long long)m * a.C + c) * 2 + 1]; }
+    cnt = a.count * a.ns.ips;
   } else {
     const int cg = a.C / a.groups, g0 = (c / cg) * cg;
     for (int k = g0; k < g0 + cg; ++k) {
-      const double g = a.gamma ? (double)a.gamma[k] : 1.0;
+      const double g = gamma ? (double)gamma[k] : 1.0;
       A += g * a.tot[((long long)n * a.C + k) * 2]; B += g * a.tot[((long long)n * a.C + k) * 2 + 1];
     }
     cnt = a.count * cg;
@@ -287,11 +316,15 @@ __global__ void bwd_finalize_kernel(BwdFinArgs a) {
   const bool frozen = (a.kind == MMTTA_NORM_BATCH && !a.training);
   a.m1[i] = frozen ? 0.f : (float)(A / cnt);
   a.m2[i] = frozen ? 0.f : (float)(B / cnt);
-  if (n == 0 && a.dgamma != nullptr) {
+  if (n == m0 && a.dgamma != nullptr) {
     double dg = 0.0, db = 0.0;
-    for (int m = 0; m < a.N; ++m) { db += a.tot[((long long)m * a.C + c) * 2]; dg += a.tot[((long long)m * a.C + c) * 2 + 1]; }
-    a.dgamma[c] = a.accumulate ? a.dgamma[c] + (float)dg : (float)dg;
-    if (a.dbeta) a.dbeta[c] = a.accumulate ? a.dbeta[c] + (float)db : (float)db;
+    for (int m = m0; m < m0 + a.ns.ips; ++m) { db += a.tot[((long long)m * a.C + c) * 2]; dg += a.tot[((long long)m * a.C + c) * 2 + 1]; }
+    float* dgamma = a.dgamma + q * a.ns.astride;
+    dgamma[c] = a.accumulate ? dgamma[c] + (float)dg : (float)dg;
+    if (a.dbeta) {
+      float* dbeta = a.dbeta + q * a.ns.astride;
+      dbeta[c] = a.accumulate ? dbeta[c] + (float)db : (float)db;
+    }
   }
 }
 
@@ -301,7 +334,17 @@ struct EwArgs {
   NL ta, tb;
   const float* m1; const float* m2;
   int hasb;
+  int pa, pb;   // ta / tb carry per-item gamma / beta [N*C] (mmtta_norm_on_load.per_item)
 };
+
+// item n's view of a norm-on-load whose gamma / beta are per item ([N*C]): the [C] vectors of that item
+__device__ __forceinline__ NL nl_item(NL t, int per_item, int n, int C) {
+  if (per_item) {
+    if (t.gamma) t.gamma += (long long)n * C;
+    if (t.beta) t.beta += (long long)n * C;
+  }
+  return t;
+}
 
 // MODE 0: combine  out = Ta(a) + Tb(b)
 // MODE 1: norm bwd apply: a = dout, b = y, T = ta(on y)   out = rstd*(g*dz - m1 - xhat*m2)
@@ -334,19 +377,20 @@ __global__ __launch_bounds__(256) void elementwise_kernel(EwArgs e) {
       const int c = c0 + j;
       if (MODE == 0) {
         float sa, ha;
-        nl_coeff(e.ta, n, C, min(c, C - 1), sa, ha);
+        nl_coeff(nl_item(e.ta, e.pa, n, C), n, C, min(c, C - 1), sa, ha);
         float r = nl_apply(av[j], sa, ha, e.ta.relu);
         if (bp) {
           float sb, hb;
-          nl_coeff(e.tb, n, C, min(c, C - 1), sb, hb);
+          nl_coeff(nl_item(e.tb, e.pb, n, C), n, C, min(c, C - 1), sb, hb);
           r += nl_apply(bv[j], sb, hb, e.tb.relu);
         }
         ov[j] = r;
       } else {
         const int cc = min(c, C - 1);                 // pad lanes of a padded row compute on channel C-1's values
         const float mu = e.ta.mean[n * C + cc], rs = e.ta.rstd[n * C + cc];
-        const float g = e.ta.gamma ? e.ta.gamma[cc] : 1.f;
-        const float bt = e.ta.beta ? e.ta.beta[cc] : 0.f;
+        const int ab = e.pa ? n * C : 0;
+        const float g = e.ta.gamma ? e.ta.gamma[ab + cc] : 1.f;
+        const float bt = e.ta.beta ? e.ta.beta[ab + cc] : 0.f;
         const float xhat = (bv[j] - mu) * rs;
         float dz = av[j];
         if (e.ta.relu && !(fmaf(g, xhat, bt) > 0.f)) dz = 0.f;
@@ -370,6 +414,7 @@ struct Nb8Args {
   int C, relu;
   unsigned dhw;
   const float* mean; const float* rstd; const float* gamma; const float* beta; const float* m1; const float* m2;
+  int per_item;   // gamma / beta [N*C] (mmtta_norm_on_load.per_item)
 };
 
 template <bool YBF, int IT, bool DBF = false>
@@ -398,12 +443,13 @@ __global__ __launch_bounds__(256) void norm_bwd_apply8_kernel(Nb8Args a) {
       r[0] = lo.x; r[1] = lo.y; r[2] = lo.z; r[3] = lo.w; r[4] = hi.x; r[5] = hi.y; r[6] = hi.z; r[7] = hi.w;
     };
     ld8(a.mean, pc, mu); ld8(a.rstd, pc, rs); ld8(a.m1, pc, m1); ld8(a.m2, pc, m2);
-    if (a.gamma) ld8(a.gamma, c0, g);
+    const unsigned ac = a.per_item ? pc : c0;
+    if (a.gamma) ld8(a.gamma, ac, g);
     else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) g[j] = 1.f;
     }
-    if (a.beta) ld8(a.beta, c0, bt);
+    if (a.beta) ld8(a.beta, ac, bt);
     else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) bt[j] = 0.f;
@@ -439,6 +485,7 @@ struct NbsArgs {
   unsigned dhw;
   double count;
   const float* mean; const float* rstd; const float* gamma; const float* beta;
+  int per_item;   // gamma / beta [N*C] (mmtta_norm_on_load.per_item)
 };
 
 template <bool YBF, bool DBF = false>
@@ -459,12 +506,13 @@ __global__ __launch_bounds__(256) void norm_bwd_small_kernel(NbsArgs a) {
       r[0] = lo.x; r[1] = lo.y; r[2] = lo.z; r[3] = lo.w; r[4] = hi.x; r[5] = hi.y; r[6] = hi.z; r[7] = hi.w;
     };
     ld8(a.mean, pc, mu); ld8(a.rstd, pc, rs);
-    if (a.gamma) ld8(a.gamma, c0, g);
+    const unsigned ac = a.per_item ? pc : c0;
+    if (a.gamma) ld8(a.gamma, ac, g);
     else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) g[j] = 1.f;
     }
-    if (a.beta) ld8(a.beta, c0, bt);
+    if (a.beta) ld8(a.beta, ac, bt);
     else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) bt[j] = 0.f;
@@ -507,7 +555,7 @@ __global__ __launch_bounds__(256) void norm_bwd_small_kernel(NbsArgs a) {
     double t = 0.0;
     for (int l = 0; l < 64; ++l) t += (double)part[k][j][l * 4 + q];
     const int c = blockIdx.x * 32 + q * 8 + j;
-    const double gm = a.gamma ? (double)a.gamma[c] : 1.0;
+    const double gm = a.gamma ? (double)a.gamma[(a.per_item ? n * a.C : 0) + c] : 1.0;
     mm[k][q * 8 + j] = (float)(gm * t / a.count);
   }
   __syncthreads();
@@ -551,6 +599,7 @@ struct Cb8Args {
   int C;
   unsigned dhw;
   NL ta, tb;
+  int pa, pb;   // per-item gamma / beta of ta / tb
 };
 
 template <bool BF, bool HASB, int IT>
@@ -574,8 +623,8 @@ __global__ __launch_bounds__(256) void combine8_kernel(Cb8Args e) {
     if (HASB) br[i] = oct8_ld<BF>(bp, v * e.bsw + c0, v * e.bsw + c0 + 4);
   }
   float sa[8], ha[8], sb[8], hb[8];
-  nl_coeff_vec<8>(e.ta, n, e.C, (int)c0, sa, ha);
-  if (HASB) nl_coeff_vec<8>(e.tb, n, e.C, (int)c0, sb, hb);
+  nl_coeff_vec<8>(nl_item(e.ta, e.pa, n, e.C), n, e.C, (int)c0, sa, ha);
+  if (HASB) nl_coeff_vec<8>(nl_item(e.tb, e.pb, n, e.C), n, e.C, (int)c0, sb, hb);
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     float av[8], bv[8], ov[8];
@@ -822,7 +871,7 @@ int channel_partial_rows(const mmtta_tensor* t) {
 
 int launch_channel_sums(const mmtta_tensor* x, float* part, hipStream_t s) {
   RedArgs a;
-  a.x = tv(x); a.dout = tv(x); a.t = nl(nullptr); a.part = part;
+  a.x = tv(x); a.dout = tv(x); a.t = nl(nullptr); a.per_item = 0; a.part = part;
   rows_geometry(x, a.rows_per_n, a.vox_per_row);
   const dim3 grid(x->n * a.rows_per_n);
   if (is_bf16(x)) {
@@ -863,11 +912,33 @@ extern "C" int mmtta_channel_stats(const mmtta_tensor* x, float* part, void* str
   return launch_channel_sums(x, part, (hipStream_t)stream);
 }
 
-extern "C" int mmtta_norm_stats_finalize(int kind, int groups, const float* part, int rows_per_n, int n, int c,
-                                         int64_t count, float eps, int training, float* running_mean,
-                                         float* running_var, float momentum, float* mean, float* rstd,
-                                         const float* gamma, const float* beta, float* scale, float* shift,
-                                         double* scratch, void* stream) {
+// host-side check of a norm-sets descriptor against a batch of n items (mmtta_norm_sets)
+// (with several sets, written affine gradients / running statistics must not overlap: each set's first item writes its own
+// [C] vectors, a stride below C would make the writers of two sets race on one element)
+static int nsets_validate(const mmtta_norm_sets* g, int n, int c, bool writes_affine, bool has_stats, const char* what) {
+  MMTTA_CHECK(g != nullptr, MMTTA_ERR_INVALID, "%s: null norm-sets descriptor", what);
+  MMTTA_CHECK(g->items_per_set >= 1, MMTTA_ERR_INVALID, "%s: items_per_set %d (>= 1)", what, g->items_per_set);
+  MMTTA_CHECK(n > 0 && n % g->items_per_set == 0, MMTTA_ERR_INVALID, "%s: batch %d is no multiple of items_per_set %d", what, n,
+              g->items_per_set);
+  MMTTA_CHECK(g->affine_stride >= 0 && g->stats_stride >= 0 && g->affine_stride % 4 == 0 && g->stats_stride % 4 == 0,
+              MMTTA_ERR_INVALID, "%s: strides must be non-negative and keep 16-byte alignment (affine %lld, stats %lld)", what,
+              (long long)g->affine_stride, (long long)g->stats_stride);
+  if (n / g->items_per_set > 1) {
+    MMTTA_CHECK(!writes_affine || g->affine_stride >= c, MMTTA_ERR_INVALID,
+                "%s: affine_stride %lld < C %d: the affine gradients of the sets would overlap", what, (long long)g->affine_stride, c);
+    MMTTA_CHECK(!has_stats || g->stats_stride >= c, MMTTA_ERR_INVALID,
+                "%s: stats_stride %lld < C %d: the running statistics of the sets would overlap", what, (long long)g->stats_stride, c);
+  }
+  return MMTTA_OK;
+}
+static NSets nsets(const mmtta_norm_sets* g) {
+  NSets r; r.ips = g->items_per_set; r.astride = g->affine_stride; r.sstride = g->stats_stride; return r;
+}
+
+static int stats_finalize(int kind, int groups, const float* part, int rows_per_n, int n, int c, int64_t count, float eps,
+                          int training, float* running_mean, float* running_var, float momentum, float* mean, float* rstd,
+                          const float* gamma, const float* beta, float* scale, float* shift, float* gi, float* bi,
+                          double* scratch, NSets ns, void* stream) {
   MMTTA_CHECK(kind >= 0 && kind <= 2, MMTTA_ERR_INVALID, "norm: bad kind %d", kind);
   MMTTA_CHECK(mean && rstd && n > 0 && c > 0 && count > 0, MMTTA_ERR_INVALID, "norm finalize: bad argument");
   MMTTA_CHECK((scale == nullptr) == (shift == nullptr), MMTTA_ERR_INVALID, "norm finalize: scale and shift go together");
@@ -879,7 +950,7 @@ extern "C" int mmtta_norm_stats_finalize(int kind, int groups, const float* part
   if (kind == MMTTA_NORM_INSTANCE) {
     MMTTA_CHECK(part != nullptr && rows_per_n > 0, MMTTA_ERR_INVALID, "norm finalize: null partials");
     hipLaunchKernelGGL(instance_stats_kernel, dim3(n * c), dim3(64), 0, s, part, rows_per_n, c, (double)count, eps, mean, rstd,
-                       gamma, beta, scale, shift);
+                       gamma, beta, scale, shift, ns, gi, bi);
     return launch_status("instance norm stats");
   }
   const bool need_rows = !(kind == MMTTA_NORM_BATCH && !training);
@@ -894,8 +965,34 @@ extern "C" int mmtta_norm_stats_finalize(int kind, int groups, const float* part
   a.running_mean = running_mean; a.running_var = running_var; a.momentum = momentum; a.mean = mean; a.rstd = rstd;
   a.gamma = gamma; a.beta = beta; a.scale = scale; a.shift = shift;
   a.tot = g_tot;
+  a.ns = ns; a.gi = gi; a.bi = bi;
   hipLaunchKernelGGL(stats_finalize_kernel, dim3((n * c + 63) / 64), dim3(64), 0, s, a);
   return launch_status("norm stats finalize");
+}
+
+extern "C" int mmtta_norm_stats_finalize(int kind, int groups, const float* part, int rows_per_n, int n, int c,
+                                         int64_t count, float eps, int training, float* running_mean,
+                                         float* running_var, float momentum, float* mean, float* rstd,
+                                         const float* gamma, const float* beta, float* scale, float* shift,
+                                         double* scratch, void* stream) {
+  return stats_finalize(kind, groups, part, rows_per_n, n, c, count, eps, training, running_mean, running_var, momentum, mean,
+                        rstd, gamma, beta, scale, shift, nullptr, nullptr, scratch, nsets_plain(n > 0 ? n : 1), stream);
+}
+
+extern "C" int mmtta_norm_stats_finalize_sets(int kind, int groups, const float* part, int rows_per_n, int n, int c,
+                                              int64_t count, float eps, int training, float* running_mean,
+                                              float* running_var, float momentum, float* mean, float* rstd,
+                                              const float* gamma, const float* beta, float* scale, float* shift,
+                                              float* gamma_items, float* beta_items, double* scratch,
+                                              const mmtta_norm_sets* sets, void* stream) {
+  const int st = nsets_validate(sets, n, c, false, running_mean != nullptr, "norm finalize (sets)");
+  if (st) return st;
+  MMTTA_CHECK((gamma_items == nullptr || gamma != nullptr) && (beta_items == nullptr || beta != nullptr), MMTTA_ERR_INVALID,
+              "norm finalize (sets): gamma_items / beta_items need gamma / beta");
+  MMTTA_CHECK((running_mean == nullptr) == (running_var == nullptr), MMTTA_ERR_INVALID,
+              "norm finalize (sets): running_mean and running_var go together");
+  return stats_finalize(kind, groups, part, rows_per_n, n, c, count, eps, training, running_mean, running_var, momentum, mean,
+                        rstd, gamma, beta, scale, shift, gamma_items, beta_items, scratch, nsets(sets), stream);
 }
 
 extern "C" int mmtta_combine(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtta_tensor* b,
@@ -905,6 +1002,8 @@ extern "C" int mmtta_combine(const mmtta_tensor* a, const mmtta_norm_on_load* ta
   MMTTA_CHECK(is_cl(a) && is_cl(out) && (!b || is_cl(b)), MMTTA_ERR_UNSUPPORTED, "combine: channels-last only");
   EwArgs e;
   e.a = tv(a); e.b = b ? tv(b) : tv(a); e.o = tv(out); e.ta = nl(ta); e.tb = nl(tb); e.m1 = e.m2 = nullptr; e.hasb = b ? 1 : 0;
+  e.pa = ta && ta->per_item ? 1 : 0;
+  e.pb = b && tb && tb->per_item ? 1 : 0;
   const bool v4 = vec4_rd(a) && vec4_wr(out) && (!b || vec4_rd(b));
   const long long total = (long long)out->n * out->d * out->h * out->w * (v4 ? (out->c + 3) / 4 : out->c);
   // storage: all fp32, or all bf16 (the wide forward activations of bf16 precision)
@@ -927,7 +1026,7 @@ extern "C" int mmtta_combine(const mmtta_tensor* a, const mmtta_norm_on_load* ta
       q.a = (const float*)a->ptr; q.b = b ? (const float*)b->ptr : nullptr; q.o = (float*)out->ptr;
       q.asn = a->sn; q.bsn = b ? b->sn : 0; q.osn = out->sn;
       q.asw = (unsigned)a->sw; q.bsw = b ? (unsigned)b->sw : 0u; q.osw = (unsigned)out->sw;
-      q.C = C; q.dhw = (unsigned)dhw; q.ta = e.ta; q.tb = e.tb;
+      q.C = C; q.dhw = (unsigned)dhw; q.ta = e.ta; q.tb = e.tb; q.pa = e.pa; q.pb = e.pb;
       if (abf) { if (b) launch_combine8<true, true>(q, out->n, s); else launch_combine8<true, false>(q, out->n, s); }
       else { if (b) launch_combine8<false, true>(q, out->n, s); else launch_combine8<false, false>(q, out->n, s); }
       return launch_status("combine");
@@ -951,7 +1050,7 @@ extern "C" int mmtta_norm_bwd_reduce(const mmtta_tensor* dout, const mmtta_tenso
   MMTTA_CHECK(!is_bf16(dout) || is_bf16(y) || y->c <= 4, MMTTA_ERR_UNSUPPORTED, "norm bwd reduce: a bf16-stored gradient needs a bf16-stored activation");
   MMTTA_CHECK(same_shape(dout, y) && is_cl(dout) && is_cl(y), MMTTA_ERR_INVALID, "norm bwd reduce: shape/layout mismatch");
   RedArgs a;
-  a.x = tv(y); a.dout = tv(dout); a.t = nl(t); a.part = part;
+  a.x = tv(y); a.dout = tv(dout); a.t = nl(t); a.per_item = t->per_item != 0 ? 1 : 0; a.part = part;
   rows_geometry(y, a.rows_per_n, a.vox_per_row);
   const dim3 grid(y->n * a.rows_per_n);
   hipStream_t s = (hipStream_t)stream;
@@ -972,9 +1071,9 @@ extern "C" int mmtta_norm_bwd_reduce(const mmtta_tensor* dout, const mmtta_tenso
   return launch_status("norm bwd reduce");
 }
 
-extern "C" int mmtta_norm_bwd_finalize(int kind, int groups, const float* part, int rows_per_n, int n, int c,
-                                       int64_t count, const float* gamma, int training, float* m1, float* m2,
-                                       float* dgamma, float* dbeta, int accumulate, double* scratch, void* stream) {
+static int bwd_finalize(int kind, int groups, const float* part, int rows_per_n, int n, int c, int64_t count,
+                        const float* gamma, int training, float* m1, float* m2, float* dgamma, float* dbeta, int accumulate,
+                        double* scratch, NSets ns, void* stream) {
   MMTTA_CHECK(kind >= 0 && kind <= 2, MMTTA_ERR_INVALID, "norm: bad kind %d", kind);
   MMTTA_CHECK(part && m1 && m2 && n > 0 && c > 0 && count > 0 && rows_per_n > 0, MMTTA_ERR_INVALID, "norm bwd finalize: bad argument");
   MMTTA_CHECK(scratch != nullptr, MMTTA_ERR_INVALID, "norm bwd finalize: null scratch");
@@ -982,7 +1081,7 @@ extern "C" int mmtta_norm_bwd_finalize(int kind, int groups, const float* part, 
   if (kind == MMTTA_NORM_GROUP) MMTTA_CHECK(groups > 0 && c % groups == 0, MMTTA_ERR_INVALID, "group norm: C %% groups != 0");
   hipStream_t s = (hipStream_t)stream;
   if (kind == MMTTA_NORM_INSTANCE && dgamma == nullptr) {
-    hipLaunchKernelGGL(instance_bwd_kernel, dim3(n * c), dim3(64), 0, s, part, rows_per_n, c, (double)count, gamma, m1, m2);
+    hipLaunchKernelGGL(instance_bwd_kernel, dim3(n * c), dim3(64), 0, s, part, rows_per_n, c, (double)count, gamma, m1, m2, ns);
     return launch_status("instance norm bwd finalize");
   }
   hipLaunchKernelGGL(rows_reduce_kernel, dim3(n * c), dim3(64), 0, s, part, rows_per_n, c, g_tot);
@@ -991,8 +1090,27 @@ extern "C" int mmtta_norm_bwd_finalize(int kind, int groups, const float* part, 
   BwdFinArgs a;
   a.kind = kind; a.groups = groups; a.N = n; a.C = c; a.count = (double)count; a.gamma = gamma; a.training = training;
   a.m1 = m1; a.m2 = m2; a.dgamma = dgamma; a.dbeta = dbeta; a.accumulate = accumulate; a.tot = g_tot;
+  a.ns = ns;
   hipLaunchKernelGGL(bwd_finalize_kernel, dim3((n * c + 63) / 64), dim3(64), 0, s, a);
   return launch_status("norm bwd finalize");
+}
+
+extern "C" int mmtta_norm_bwd_finalize(int kind, int groups, const float* part, int rows_per_n, int n, int c,
+                                       int64_t count, const float* gamma, int training, float* m1, float* m2,
+                                       float* dgamma, float* dbeta, int accumulate, double* scratch, void* stream) {
+  return bwd_finalize(kind, groups, part, rows_per_n, n, c, count, gamma, training, m1, m2, dgamma, dbeta, accumulate, scratch,
+                      nsets_plain(n > 0 ? n : 1), stream);
+}
+
+extern "C" int mmtta_norm_bwd_finalize_sets(int kind, int groups, const float* part, int rows_per_n, int n, int c,
+                                            int64_t count, const float* gamma, int training, float* m1, float* m2,
+                                            float* dgamma, float* dbeta, int accumulate, double* scratch,
+                                            const mmtta_norm_sets* sets, void* stream) {
+  const int st = nsets_validate(sets, n, c, dgamma != nullptr || dbeta != nullptr, false, "norm bwd finalize (sets)");
+  if (st) return st;
+  MMTTA_CHECK(dbeta == nullptr || dgamma != nullptr, MMTTA_ERR_INVALID, "norm bwd finalize (sets): dbeta needs dgamma");
+  return bwd_finalize(kind, groups, part, rows_per_n, n, c, count, gamma, training, m1, m2, dgamma, dbeta, accumulate, scratch,
+                      nsets(sets), stream);
 }
 
 extern "C" int mmtta_norm_bwd_apply(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
@@ -1005,6 +1123,7 @@ extern "C" int mmtta_norm_bwd_apply(const mmtta_tensor* dout, const mmtta_tensor
   MMTTA_CHECK(is_cl(dout) && is_cl(y) && is_cl(dy), MMTTA_ERR_UNSUPPORTED, "norm bwd apply: channels-last only");
   EwArgs e;
   e.a = tv(dout); e.b = tv(y); e.o = tv(dy); e.ta = nl(t); e.tb = nl(nullptr); e.m1 = m1; e.m2 = m2; e.hasb = 1;
+  e.pa = t->per_item ? 1 : 0; e.pb = 0;
   const bool v4 = vec4_rd(dout) && vec4_rd(y) && vec4_wr(dy);
   const long long total = (long long)y->n * y->d * y->h * y->w * (v4 ? (y->c + 3) / 4 : y->c);
   const dim3 grid(grid_for(total));
@@ -1030,6 +1149,7 @@ extern "C" int mmtta_norm_bwd_apply(const mmtta_tensor* dout, const mmtta_tensor
       q.dsw = (unsigned)dout->sw; q.ysw = (unsigned)y->sw; q.osw = (unsigned)dy->sw;
       q.C = C; q.relu = t->relu; q.dhw = (unsigned)dhw;
       q.mean = t->mean; q.rstd = t->rstd; q.gamma = t->gamma; q.beta = t->beta; q.m1 = m1; q.m2 = m2;
+      q.per_item = t->per_item != 0 ? 1 : 0;
       const long long nvl = 256 / (C / 8);
       const bool four = dhw / (nvl * 4) >= 1024;
       const long long per = nvl * (four ? 4 : 2);
@@ -1092,6 +1212,7 @@ extern "C" int mmtta_norm_bwd_small(const mmtta_tensor* dout, const mmtta_tensor
   q.dsw = (unsigned)dout->sw; q.ysw = (unsigned)y->sw; q.osw = (unsigned)dy->sw;
   q.C = y->c; q.relu = t->relu; q.dhw = (unsigned)((long long)y->d * y->h * y->w); q.count = (double)count;
   q.mean = t->mean; q.rstd = t->rstd; q.gamma = t->gamma; q.beta = t->beta;
+  q.per_item = t->per_item != 0 ? 1 : 0;
   const dim3 grid((unsigned)(y->c / 32), (unsigned)y->n);
   if (is_bf16(dout)) hipLaunchKernelGGL((norm_bwd_small_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, q);
   else if (is_bf16(y)) hipLaunchKernelGGL(norm_bwd_small_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, q);

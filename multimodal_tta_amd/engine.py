@@ -161,8 +161,24 @@ class NormLayer:
         self.C, self.groups, self.eps, self.momentum = channels, groups, eps, momentum
         self.gamma, self.beta = gamma, beta
         self.bn = bn_module        # owns running_mean / running_var / num_batches_tracked (BatchNorm only)
+        self.rt: Optional["Runtime"] = None       # set by build_norm
+        self.stats_off = 0         # running_mean / running_var offsets in the runtime's statistics replicas (BatchNorm)
+        self.bn_index = 0
+
+    def grouped(self) -> bool:
+        """True inside the launches of a volume group (``Runtime.use_sets``) for a norm with per-volume state - affines or
+        running statistics: every batch item then reads / writes its own replica (mmtta_norm_sets).  A parameter-free norm
+        has none and keeps the plain entry points."""
+        rt = self.rt
+        return (rt is not None and rt.use_sets and rt.group > 1 and rt.arena is not None
+                and (self.gamma is not None or self.beta is not None or self.bn is not None))
+
+    def _sets(self) -> "ops._lib.NormSets":
+        return ops.norm_sets(1, self.rt.arena.total, self.rt.bn_stats_total)
 
     def finalize(self, pool: Pool, key, part, rows_per_n: int, n: int, count: int, training: bool) -> NL:
+        if self.grouped():
+            return self._finalize_sets(pool, key, part, rows_per_n, n, count, training)
         mean = pool.flat((key, "mean"), n * self.C)
         rstd = pool.flat((key, "rstd"), n * self.C)
         scale = pool.flat((key, "scale"), n * self.C)
@@ -178,6 +194,28 @@ class NormLayer:
         if self.bn is not None and training and self.bn.num_batches_tracked is not None:
             self.bn.num_batches_tracked.add_(1)
         return NL(mean, rstd, g, b, True, scale, shift)
+
+    def _finalize_sets(self, pool: Pool, key, part, rows_per_n: int, n: int, count: int, training: bool) -> NL:
+        """Batch item v = volume v of the group: its statistics (BatchNorm: over its own voxels only), its replica's affines
+        and running statistics; consumers get per-item copies of the affines (NL.per_item)."""
+        C = self.C
+        mean = pool.flat((key, "mean"), n * C)
+        rstd = pool.flat((key, "rstd"), n * C)
+        scale = pool.flat((key, "scale"), n * C)
+        shift = pool.flat((key, "shift"), n * C)
+        scratch = pool.flat((key, "tot"), n * C * 2, dtype=torch.float64)
+        g = self.gamma.data if self.gamma else None
+        b = self.beta.data if self.beta else None
+        gi = pool.flat((key, "gamma_items"), n * C) if g is not None else None
+        bi = pool.flat((key, "beta_items"), n * C) if b is not None else None
+        use_batch = training or self.kind != ops.NORM_BATCH
+        rm = self.bn.running_mean if self.bn is not None else None
+        rv = self.bn.running_var if self.bn is not None else None
+        ops.norm_stats_finalize_sets(self.kind, self.groups, part, rows_per_n, n, C, count, self.eps, use_batch, rm, rv,
+                                     self.momentum, mean, rstd, scratch, self._sets(), g, b, scale, shift, gi, bi)
+        if self.bn is not None and training and self.bn.num_batches_tracked is not None:
+            self.rt.bn_nbt_all[:n, self.bn_index].add_(1)
+        return NL(mean, rstd, gi, bi, True, scale, shift, per_item=True)
 
     def backward(self, pool: Pool, key, dT: torch.Tensor, y: torch.Tensor, nl: NL, dy: torch.Tensor,
                  training: bool, accumulate: bool = False) -> None:
@@ -195,10 +233,13 @@ class NormLayer:
         scratch = pool.flat((key, "tot"), n * c * 2, dtype=torch.float64)
         ops.norm_bwd_reduce(dT, y, nl, part)
         use_batch = training or self.kind != ops.NORM_BATCH
-        ops.norm_bwd_finalize(self.kind, self.groups, part, rows, n, c, d * h * w,
-                              self.gamma.data if self.gamma else None, use_batch, m1, m2,
-                              self.gamma.grad if train_g else None,
-                              self.beta.grad if (train_g and self.beta is not None) else None, accumulate, scratch)
+        fin_args = (self.kind, self.groups, part, rows, n, c, d * h * w, self.gamma.data if self.gamma else None, use_batch,
+                    m1, m2, self.gamma.grad if train_g else None,
+                    self.beta.grad if (train_g and self.beta is not None) else None, accumulate, scratch)
+        if self.grouped():
+            ops.norm_bwd_finalize_sets(*fin_args, self._sets())      # set v's gradients land in arena replica v
+        else:
+            ops.norm_bwd_finalize(*fin_args)
         ops.norm_bwd_apply(dT, y, nl, m1, m2, dy)
 
 
@@ -212,6 +253,11 @@ class ConvLayer:
         self.members = members if members is not None else [(weight, bias)]      # member 0 = (weight, bias)
         self.items_per_set = int(items_per_set)      # consecutive batch items sharing a set (the fusion layer: M)
         self.side_index = 0          # which side stream takes this layer's weight gradient (Runtime.make_conv)
+
+    @property
+    def frozen(self) -> bool:
+        """No member's weight or bias adapts: every replica holds the source values, ONE packed image serves them all."""
+        return all(not w.trainable and not (b is not None and b.trainable) for w, b in self.members)
 
     def pack(self) -> None:
         for m, (w, _) in enumerate(self.members):
@@ -231,7 +277,8 @@ class ConvLayer:
             if len(wd) != 1 or len(bd) != 1:
                 raise MmttaError("the members of a layer family must sit at a uniform stride in the arena")
             wi, bi = wd.pop(), bd.pop()
-        self.op.set_param_sets(self.items_per_set, inner, arena.total, wi, arena.total, bi, self.rt)
+        # a frozen layer reads replica 0 for every volume (zero outer strides): its weights are the same in every replica
+        self.op.set_param_sets(self.items_per_set, inner, arena.total, wi, arena.total, bi, self.rt, shared=self.frozen)
 
     def bias_data(self):
         return self.bias.data if self.bias is not None else None
@@ -390,7 +437,15 @@ class Runtime:
         self.convs: List[ConvLayer] = []
         self.refs: List[ParamRef] = []
         self.buffers: List[torch.nn.Module] = []     # modules owning running statistics (BatchNorm)
+        self.norms: List[NormLayer] = []
         self.arena: Optional[Arena] = None
+        # per-volume norm parameter sets (method.norm_sets): a group of volumes may adapt norm affines and BatchNorm running
+        # statistics, each volume on its own replica.  The statistics replicas: [group, bn_stats_total] fp32 (running_mean,
+        # running_var of every BatchNorm) and [group, modules] int64 (num_batches_tracked); replica 0 backs the modules' buffers
+        self.norm_sets = False
+        self.bn_stats_all: Optional[torch.Tensor] = None
+        self.bn_nbt_all: Optional[torch.Tensor] = None
+        self.bn_stats_total = 0
 
     def act_dtype(self, channels: int) -> torch.dtype:
         """Storage type of a forward activation with `channels` channels."""
@@ -475,14 +530,15 @@ class Runtime:
                 r.group = GROUP_DECAY
 
     def build_arena(self) -> Arena:
-        if self.group > 1:
+        if self.group > 1 and not self.norm_sets:
             # a volume group needs every parameter to be per-item: convolution weights and biases are (mmtta_param_sets);
-            # norm affines and BatchNorm's cross-item statistics are not
+            # norm affines and BatchNorm's cross-item statistics are only with the norm parameter sets (method.norm_sets)
             bad = [r.name for r in self.refs if ".adn.N." in r.name]
             if bad or self.buffers:
                 raise NotImplementedError(
                     f"method.group = {self.group} needs per-volume norms without parameters (INSTANCE, the shipped configs); "
-                    f"this model has {bad[:2] or 'BatchNorm running statistics'}: use method.lanes with method.group = 1")
+                    f"this model has {bad[:2] or 'BatchNorm running statistics'}: use method.lanes with method.group = 1 "
+                    f"or method.norm_sets: true")
         self.arena = Arena(self.refs, self.device, replicas=self.group)
         for c in self.convs:
             c.bind_sets(self.arena)
@@ -490,34 +546,118 @@ class Runtime:
             for name, buf in list(mod.named_buffers(recurse=False)):
                 if buf is not None and buf.device != self.device:
                     setattr(mod, name, buf.to(self.device))
+        if self.group > 1 and self.buffers:
+            self._replicate_running_stats()
         return self.arena
 
+    def _replicate_running_stats(self) -> None:
+        """One replica of every BatchNorm's running statistics per volume of the group (mmtta_norm_sets.stats_stride); the
+        modules' buffers become views of replica 0, the way the nn.Parameters view the arena."""
+        layers, seen = [], set()
+        for nl in self.norms:
+            if nl.bn is not None and id(nl.bn) not in seen:
+                seen.add(id(nl.bn))
+                layers.append(nl)
+        off = 0
+        for j, nl in enumerate(layers):
+            nl.stats_off, nl.bn_index = off, j
+            off += 2 * ((nl.C + 3) // 4 * 4)        # running_mean, running_var: 16-byte aligned each
+        self.bn_stats_total = max(off, 4)
+        self.bn_stats_all = torch.zeros((self.group, self.bn_stats_total), dtype=torch.float32, device=self.device)
+        self.bn_nbt_all = torch.zeros((self.group, max(len(layers), 1)), dtype=torch.int64, device=self.device)
+        for nl in layers:
+            mod, cp = nl.bn, (nl.C + 3) // 4 * 4
+            rm = self.bn_stats_all[0, nl.stats_off:nl.stats_off + nl.C]
+            rv = self.bn_stats_all[0, nl.stats_off + cp:nl.stats_off + cp + nl.C]
+            with torch.no_grad():
+                rm.copy_(mod.running_mean)
+                rv.copy_(mod.running_var)
+                mod.running_mean, mod.running_var = rm, rv
+                if mod.num_batches_tracked is not None:
+                    nb = self.bn_nbt_all[0, nl.bn_index]
+                    nb.copy_(mod.num_batches_tracked)
+                    mod.num_batches_tracked = nb
+        self.bn_stats_all.copy_(self.bn_stats_all[:1].expand_as(self.bn_stats_all))
+        self.bn_nbt_all.copy_(self.bn_nbt_all[:1].expand_as(self.bn_nbt_all))
+
+    def replica_buffers(self, g: int) -> List[Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]]:
+        """(running_mean, running_var, num_batches_tracked) of every BatchNorm module as volume ``g`` of the group sees them
+        (views; a runtime without statistics replicas has only the modules' own buffers)."""
+        out = []
+        for mod in self.buffers:
+            nl = next((x for x in self.norms if x.bn is mod), None)
+            if self.bn_stats_all is None or nl is None:
+                out.append((mod.running_mean, mod.running_var, mod.num_batches_tracked))
+                continue
+            cp = (nl.C + 3) // 4 * 4
+            row = self.bn_stats_all[g]
+            out.append((row[nl.stats_off:nl.stats_off + nl.C], row[nl.stats_off + cp:nl.stats_off + cp + nl.C],
+                        self.bn_nbt_all[g, nl.bn_index] if mod.num_batches_tracked is not None else None))
+        return out
+
     def pack_all(self) -> None:
-        """Refresh every packed weight image from the arena (one launch)."""
-        if getattr(self, "_packer", None) is None or self._packer_base != self.arena.params.data_ptr():
-            items = []
+        """Refresh every packed weight image from the arena (one launch).  A frozen convolution (weight and bias both frozen)
+        has ONE image per member for every replica; it is packed when the packers are built and again only when its weights
+        were written since (``refresh_frozen``), not on every step."""
+        if getattr(self, "_packer_base", None) != self.arena.params.data_ptr():
+            step_items, frozen_items = [], []
+            self._frozen_params = []
             seen = set()
             for c in self.convs:
                 if id(c.op) in seen:
                     continue
                 seen.add(id(c.op))
                 inner = len(c.members)
-                for g in range(self.arena.replicas if c.op.n_sets == self.arena.replicas * inner else 1):
+                frozen = c.frozen
+                per_replica = c.op.n_sets == self.arena.replicas * inner and not frozen
+                items = frozen_items if frozen else step_items
+                if frozen:
+                    self._frozen_params += [r.param for wb in c.members for r in wb if r is not None]
+                for g in range(self.arena.replicas if per_replica else 1):
                     for m, (w, _) in enumerate(c.members):
                         wd = self.arena.replica_data(w, g)
                         items.append((c.op.d_fwd, wd, c.op.packed_image(False, g * inner + m)))
                         if c.op.need_dgrad:
                             items.append((c.op.d_dgrad, wd, c.op.packed_image(True, g * inner + m)))
-            self._packer = ops.BatchedPacker(items, self.device)
+            self._packer = ops.BatchedPacker(step_items, self.device) if step_items else None
+            self._packer_frozen = ops.BatchedPacker(frozen_items, self.device) if frozen_items else None
+            self._frozen_version = None
             self._packer_base = self.arena.params.data_ptr()
-        self._packer.run()
+        self.refresh_frozen()
+        if self._packer is not None:
+            self._packer.run()
+
+    def _frozen_key(self) -> Tuple:
+        # writes through the arena's tensors (the episodic reset, replica views) bump the arena's version counter; writes
+        # through an nn.Parameter (load_state_dict, an external optimizer, p.copy_) bump the Parameter's own counter, which
+        # its `.data = arena view` adoption leaves separate.  Writes through `p.data` bypass both, as they bypass autograd.
+        return (self.arena.params_all._version,) + tuple(p._version for p in self._frozen_params)
+
+    def refresh_frozen(self) -> None:
+        """Repack the frozen convolutions' images if their weights were written since they were packed (one launch, on the
+        current stream; nothing when they are current).  Callers replaying a captured step call it first: the step itself
+        packs only the trainable layers."""
+        if getattr(self, "_packer_frozen", None) is None:
+            return
+        key = self._frozen_key()
+        if key != self._frozen_version:
+            self._packer_frozen.run()
+            self._frozen_version = key
 
     def snapshot_buffers(self) -> None:
         """Source values of the running statistics (BatchNorm), restored with the weights per volume."""
         self._buf_src = [(mod, name, buf.clone()) for mod in self.buffers
                          for name, buf in mod.named_buffers(recurse=False) if buf is not None]
+        if self.bn_stats_all is not None:
+            self._buf_src_all = (self.bn_stats_all[0].clone(), self.bn_nbt_all[0].clone())
 
     def restore_buffers(self) -> None:
+        if self.bn_stats_all is not None and getattr(self, "_buf_src_all", None) is not None:
+            # the source values into every replica (replica 0 backs the modules' buffers)
+            stats, nbt = self._buf_src_all
+            self.bn_stats_all.copy_(stats.unsqueeze(0).expand_as(self.bn_stats_all))
+            self.bn_nbt_all.copy_(nbt.unsqueeze(0).expand_as(self.bn_nbt_all))
+            return
         for mod, name, src in getattr(self, "_buf_src", []):
             getattr(mod, name).copy_(src)
 
@@ -564,7 +704,7 @@ def build_norm(rt: Runtime, prefix: str, adn: Optional[torch.nn.Module], channel
             raise NotImplementedError("InstanceNorm3d(track_running_stats=True)")
         g = rt.make_ref(prefix + ".N.weight", nmod.weight) if nmod.affine else None
         b = rt.make_ref(prefix + ".N.bias", nmod.bias) if nmod.affine else None
-        return NormLayer("INSTANCE", channels, 1, nmod.eps, 0.1, g, b)
+        return _adopt_norm(rt, NormLayer("INSTANCE", channels, 1, nmod.eps, 0.1, g, b))
     if isinstance(nmod, torch.nn.BatchNorm3d):
         if not (nmod.affine and nmod.track_running_stats):
             raise NotImplementedError("BatchNorm3d without affine / running statistics")
@@ -572,12 +712,18 @@ def build_norm(rt: Runtime, prefix: str, adn: Optional[torch.nn.Module], channel
         b = rt.make_ref(prefix + ".N.bias", nmod.bias)
         rt.buffers.append(nmod)
         mom = 0.1 if nmod.momentum is None else float(nmod.momentum)
-        return NormLayer("BATCH", channels, 1, nmod.eps, mom, g, b, bn_module=nmod)
+        return _adopt_norm(rt, NormLayer("BATCH", channels, 1, nmod.eps, mom, g, b, bn_module=nmod))
     if isinstance(nmod, torch.nn.GroupNorm):
         g = rt.make_ref(prefix + ".N.weight", nmod.weight) if nmod.affine else None
         b = rt.make_ref(prefix + ".N.bias", nmod.bias) if nmod.affine else None
-        return NormLayer("GROUP", channels, nmod.num_groups, nmod.eps, 0.1, g, b)
+        return _adopt_norm(rt, NormLayer("GROUP", channels, nmod.num_groups, nmod.eps, 0.1, g, b))
     raise NotImplementedError(f"norm module {type(nmod).__name__}")
+
+
+def _adopt_norm(rt: Runtime, layer: NormLayer) -> NormLayer:
+    layer.rt = rt
+    rt.norms.append(layer)
+    return layer
 
 
 def build_convolution(rt: Runtime, prefix: str, cont: torch.nn.Module) -> ConvolutionBlock:

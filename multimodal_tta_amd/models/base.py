@@ -55,6 +55,7 @@ class HipSegModel(nn.Module):
         self._treat_1d = True
         self.conv_dtype = ops.F32
         self.group = 1
+        self.norm_sets = False
 
     def set_group(self, group: int) -> None:
         """``group`` volumes adapt side by side through one launch sequence, each with its own parameter replica
@@ -62,6 +63,14 @@ class HipSegModel(nn.Module):
         group = max(1, int(group))
         if group != self.group:
             self.group = group
+            self._rt = None
+
+    def set_norm_sets(self, enabled: bool) -> None:
+        """Norm layers with parameters (affines, BatchNorm running statistics) get one replica per volume of a group
+        (``method.norm_sets``; takes effect at the next runtime build).  Off: such a model cannot take ``group`` > 1."""
+        enabled = bool(enabled)
+        if enabled != self.norm_sets:
+            self.norm_sets = enabled
             self._rt = None
 
     # ---- engine binding
@@ -107,6 +116,7 @@ class HipSegModel(nn.Module):
         if rt is not None and rt.device == device and rt.arena is not None and rt.arena.owns():
             return rt
         rt = self.runtime_cls(self, device)
+        rt.norm_sets = bool(getattr(self, "norm_sets", False))
         rt.assign_groups(self._trainable, self._no_decay_keys, self._treat_1d)
         rt.build_arena()
         self._rt = rt

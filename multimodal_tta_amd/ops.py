@@ -195,9 +195,11 @@ class NL:
     relu: bool = True
     scale: Optional[torch.Tensor] = None     # precombined rstd*gamma and beta - mean*rstd*gamma (fast consumer path)
     shift: Optional[torch.Tensor] = None
+    per_item: bool = False                   # gamma / beta are [N*C], one copy per batch item (norm_stats_finalize_sets)
 
     def struct(self) -> _lib.NormOnLoad:
-        return _lib.norm_on_load(self.mean, self.rstd, self.gamma, self.beta, self.relu, self.scale, self.shift)
+        return _lib.norm_on_load(self.mean, self.rstd, self.gamma, self.beta, self.relu, self.scale, self.shift,
+                                 self.per_item)
 
 
 def _nl_ref(nl: Optional[NL]):
@@ -353,16 +355,24 @@ class ConvOp:
         self.sets_grouped: Optional[Tuple[ParamSets, ParamSets]] = None      # (forward image, input-gradient image)
         self.sets_plain: Optional[Tuple[ParamSets, ParamSets]] = None        # a family of modules inside ONE weight set
         self.sets_ctl = None
+        self.shared_sets = False
 
     def set_param_sets(self, items_per_set: int, inner: int, weight_outer: int, weight_inner: int, bias_outer: int,
-                       bias_inner: int, ctl) -> None:
+                       bias_inner: int, ctl, shared: bool = False) -> None:
         """Batch item n uses set q = n // items_per_set, stored (q // inner) outer + (q % inner) inner strides behind set 0;
-        the packed images of the op are laid out [outer][inner]."""
+        the packed images of the op are laid out [outer][inner].  ``shared``: the outer sets are all alike (a frozen layer:
+        every volume of a group reads the images and bias of set 0, outer strides 0)."""
         if self.n_sets % inner:
             raise MmttaError(f"{self.n_sets} packed images cannot hold families of {inner} sets")
         mk = lambda nb, outer: ParamSets(int(items_per_set), int(inner), nb * int(inner) * outer, nb, int(weight_outer) * outer,
                                          int(weight_inner), int(bias_outer) * outer, int(bias_inner))
-        self.sets_grouped = (mk(self.nb_fwd, 1), mk(self.nb_dgrad, 1))
+        o = 0 if shared else 1
+        self.sets_grouped = (mk(self.nb_fwd, o), mk(self.nb_dgrad, o))
+        self.shared_sets = bool(shared)
+        if shared and self.n_sets > inner:
+            # only the images of set 0's members are packed and read: the others are not kept
+            self.packed_fwd = torch.zeros(self.nb_fwd * int(inner), dtype=torch.uint8, device=self.device)
+            self.packed_dgrad = torch.zeros(self.nb_dgrad * int(inner), dtype=torch.uint8, device=self.device)
         # without a volume group (the nn.Module facade: one weight set for the whole batch) a family of modules - the M
         # modality encoders as the batch items of one launch - still selects its member's weights: outer strides 0
         self.sets_plain = (mk(self.nb_fwd, 0), mk(self.nb_dgrad, 0)) if inner > 1 else None
@@ -546,6 +556,7 @@ class BatchedPacker:
         self.table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device)
         self.count, self.total = n, int(total.value)
         self._keep = [t for it in items for t in it[1:]]
+        self.items = list(items)
 
     def run(self) -> None:
         check(_lib.load().mmtta_conv_pack_batched(ptr(self.table), self.count, self.total, stream_ptr()),
@@ -574,6 +585,27 @@ def norm_stats_finalize(kind: int, groups: int, part: Optional[torch.Tensor], ro
           "norm_stats_finalize")
 
 
+def norm_sets(items_per_set: int, affine_stride: int, stats_stride: int = 0) -> _lib.NormSets:
+    """mmtta_norm_sets: batch item n uses norm set n // items_per_set; set q's gamma / beta (and their gradients) sit
+    q * affine_stride, its running statistics q * stats_stride elements behind set 0's."""
+    return _lib.NormSets(int(items_per_set), 0, int(affine_stride), int(stats_stride))
+
+
+def norm_stats_finalize_sets(kind: int, groups: int, part: Optional[torch.Tensor], rows_per_n: int, n: int, c: int,
+                             count: int, eps: float, training: bool, running_mean, running_var, momentum: float,
+                             mean: torch.Tensor, rstd: torch.Tensor, scratch: torch.Tensor, sets: _lib.NormSets,
+                             gamma=None, beta=None, scale: Optional[torch.Tensor] = None,
+                             shift: Optional[torch.Tensor] = None, gamma_items: Optional[torch.Tensor] = None,
+                             beta_items: Optional[torch.Tensor] = None) -> None:
+    """norm_stats_finalize per norm set (``sets``: norm_sets); gamma / beta / running statistics are set 0's."""
+    check(_lib.load().mmtta_norm_stats_finalize_sets(kind, groups, ptr(part), rows_per_n, n, c, count, eps,
+                                                     1 if training else 0, ptr(running_mean), ptr(running_var),
+                                                     momentum, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(scale),
+                                                     ptr(shift), ptr(gamma_items), ptr(beta_items), ptr(scratch),
+                                                     C.byref(sets), stream_ptr()),
+          "norm_stats_finalize_sets")
+
+
 def combine(a: torch.Tensor, a_nl: Optional[NL], b: Optional[torch.Tensor], b_nl: Optional[NL], out: torch.Tensor) -> None:
     ta, to = desc_cl(a), desc_cl(out)
     tb = desc_cl(b) if b is not None else None
@@ -596,6 +628,16 @@ def norm_bwd_finalize(kind: int, groups: int, part: torch.Tensor, rows_per_n: in
                                               1 if training else 0, ptr(m1), ptr(m2), ptr(dgamma), ptr(dbeta),
                                               1 if accumulate else 0, ptr(scratch), stream_ptr()),
           "norm_bwd_finalize")
+
+
+def norm_bwd_finalize_sets(kind: int, groups: int, part: torch.Tensor, rows_per_n: int, n: int, c: int, count: int,
+                           gamma, training: bool, m1: torch.Tensor, m2: torch.Tensor, dgamma, dbeta, accumulate: bool,
+                           scratch: torch.Tensor, sets: _lib.NormSets) -> None:
+    """norm_bwd_finalize per norm set: gamma / dgamma / dbeta are set 0's, set q's sit q * sets.affine_stride behind."""
+    check(_lib.load().mmtta_norm_bwd_finalize_sets(kind, groups, ptr(part), rows_per_n, n, c, count, ptr(gamma),
+                                                   1 if training else 0, ptr(m1), ptr(m2), ptr(dgamma), ptr(dbeta),
+                                                   1 if accumulate else 0, ptr(scratch), C.byref(sets), stream_ptr()),
+          "norm_bwd_finalize_sets")
 
 
 def norm_bwd_apply(dout: torch.Tensor, y: torch.Tensor, nl: NL, m1: torch.Tensor, m2: torch.Tensor,

@@ -87,6 +87,9 @@ class EntropyMinimizationTTA:
         # and optimizer state (mmtta_param_sets): a volume alone fills a quarter of the chip or less at the lower levels
         self.group = max(1, int(get_config(m, "group", 1)))
         self.lanes = max(1, int(get_config(m, "lanes", 1)))      # the evaluator's lanes: volumes in flight = lanes x group
+        # norm layers with parameters (BatchNorm, GroupNorm, affine InstanceNorm) per volume of a group: own affines, own Adam
+        # state, own running statistics (mmtta_norm_sets).  Off: such models fall back to group 1
+        self.norm_sets = bool(get_config(m, "norm_sets", False))
         # launch geometry (split-K, weight-gradient slabs) is chosen for this many volumes in flight; `auto` = lanes x group.
         # Two runs agree BIT FOR BIT when they use the same figure (the geometry fixes the summation order), whatever their
         # lanes / group are - which is how the grouped arrangement is checked against one volume at a time
@@ -143,6 +146,7 @@ class EntropyMinimizationTTA:
         names = select_params(model, self.params_spec)
         model.set_precision(self.precision, self.storage, self.grad_storage)
         model.set_group(self.group)
+        model.set_norm_sets(self.norm_sets)
         model.configure_training(set(names), self.no_decay_keys, self.treat_1d)
         model.to(device)
         try:
@@ -156,6 +160,11 @@ class EntropyMinimizationTTA:
             self.group = 1
             model.set_group(1)
             self.rt = model.runtime(device)
+        if self.norm_sets and int(self.rt.group) < self.group:
+            # (the deep-fusion network with such norms runs its modality encoders one after another, without volume groups)
+            warnings.warn(f"method.group = {self.group} -> {int(self.rt.group)}: {type(self.rt).__name__} has no per-volume "
+                          "parameter sets for this model (a family of modality encoders in one launch needs parameter-free "
+                          "per-item norms, INSTANCE); method.norm_sets does not apply to it")
         self.group = int(self.rt.group)          # what the runtime supports (a runtime without per-volume sets reports 1)
         self.rt.overlap_wgrad = self.side_streams > 0
         self.rt.n_side = max(1, self.side_streams)
@@ -244,6 +253,7 @@ class EntropyMinimizationTTA:
                 ops.Workspace.frozen = False
             self._graphs[key] = g
             return  # the warm-up already performed this step
+        self.rt.refresh_frozen()          # frozen layers' images are not repacked inside the step (engine.Runtime.pack_all)
         g.replay()
 
     # ------------------------------------------------------------------ per volume
