@@ -56,16 +56,30 @@ typedef struct {
 /* Per-(n,c) normalisation applied to a tensor WHEN IT IS READ ("norm on load"):
  *   v = (x - mean[n*C+c]) * rstd[n*C+c] * (gamma ? gamma[a+c] : 1) + (beta ? beta[a+c] : 0),
  *   a = per_item ? n*C : 0;
- *   if (relu) v = max(v, 0);
- * mean == NULL means "no transform".  This is MONAI's ADN (Norm -> Dropout(p=0) -> ReLU) of the
+ *   then the activation `relu` (an mmtta_act code):
+ *     MMTTA_ACT_NONE        v
+ *     MMTTA_ACT_RELU        max(v, 0)
+ *     MMTTA_ACT_LEAKY_RELU  v > 0 ? v : negative_slope * v   (torch leaky_relu, any finite slope)
+ *   and the backward kernels (mmtta_norm_bwd_*, mmtta_combine's adjoint) scale the incoming gradient by the derivative at
+ *   `post` (the activation's input): RELU [post > 0], LEAKY_RELU post > 0 ? 1 : negative_slope (torch leaky_relu_backward).
+ * mean == NULL means "no transform".  This is MONAI's ADN (Norm -> Dropout(p=0) -> Act) of the
  * producing Convolution, folded into the consumer (reference:
- * src/models/unet_multimodal_midfusion.py:45-55 via monai Convolution/ADN). */
+ * src/models/unet_multimodal_midfusion.py:45-55 via monai Convolution/ADN).
+ *
+ * Layout: `negative_slope` and `_pad2` were appended in ABI version 2 without a version bump.  The library reads
+ * `negative_slope` ONLY when relu == MMTTA_ACT_LEAKY_RELU, so a 56-byte descriptor built against the earlier layout (code
+ * 0 or 1) is never read past its end; mmtta_conv_epilogue holds this struct as its last member, so the same holds there.
+ * A code outside 0..2, or a LEAKY_RELU descriptor with a non-finite slope, is MMTTA_ERR_INVALID in every entry point that
+ * takes a descriptor, before anything is launched. */
+#define MMTTA_ACT_NONE 0
+#define MMTTA_ACT_RELU 1
+#define MMTTA_ACT_LEAKY_RELU 2
 typedef struct {
   const float* mean;  /* [N*C] or NULL */
   const float* rstd;  /* [N*C] */
   const float* gamma; /* [C] (per_item: [N*C]) or NULL */
   const float* beta;  /* [C] (per_item: [N*C]) or NULL */
-  int32_t relu;
+  int32_t relu;       /* activation code MMTTA_ACT_* (the name is kept from when ReLU was the only one: 0 / 1 unchanged) */
   /* 0: gamma / beta are one [C] vector for the whole batch.  1: they hold one [C] vector PER BATCH ITEM ([N*C], the
    * gamma_items / beta_items of mmtta_norm_stats_finalize_sets: a group of volumes, each with its own norm affines).
    * Every entry point that reads a norm-on-load honours it; the convolution entry points (mmtta_conv_run*, the epilogue's
@@ -77,6 +91,8 @@ typedef struct {
    * dependent ones); mean / rstd / gamma / beta are still what the backward kernels use. */
   const float* scale; /* [N*C] or NULL */
   const float* shift; /* [N*C] or NULL */
+  float negative_slope; /* MMTTA_ACT_LEAKY_RELU only (read for no other code) */
+  int32_t _pad2;
 } mmtta_norm_on_load;
 
 const char* mmtta_last_error(void);   /* thread-local text for the last non-zero status */
@@ -367,12 +383,12 @@ int mmtta_reduce_rows_per_n(const mmtta_tensor* t);
 int mmtta_channel_stats(const mmtta_tensor* x, float* part, void* stream);
 
 /* out = Ta(a) + Tb(b)  (b may be NULL), Ta/Tb = norm-on-load.  Materialises
- * relu(norm(y)) [+ residual]: monai ResidualUnit.forward's add with an Identity residual. */
+ * act(norm(y)) [+ residual]: monai ResidualUnit.forward's add with an Identity residual. */
 int mmtta_combine(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtta_tensor* b,
                   const mmtta_norm_on_load* tb, const mmtta_tensor* out, void* stream);
 
-/* Backward of norm(+ReLU), pass 1: per-(n,c) reductions
- *   s1[n,c] = sum dz, s2[n,c] = sum dz * xhat,  dz = dout * [post > 0] (relu) or dout,
+/* Backward of norm(+activation), pass 1: per-(n,c) reductions
+ *   s1[n,c] = sum dz, s2[n,c] = sum dz * xhat,  dz = dout * act'(post) (see mmtta_norm_on_load),
  *   xhat = (y - mean) * rstd,  post = gamma*xhat + beta.
  *   part: fp32 [N * mmtta_reduce_rows_per_n(y)][2][C].  Replaces the reduction half of
  *   native_*_norm_backward. */

@@ -38,6 +38,12 @@ class NormOnLoad(C.Structure):
     ]
 
 
+class NormOnLoadAct(NormOnLoad):
+    """The whole mmtta_norm_on_load: the 56-byte layout above (all the library reads for ACT_NONE / ACT_RELU) with the
+    appended LeakyReLU slope.  norm_on_load() builds this one, so a LEAKY_RELU descriptor is never read past its end."""
+    _fields_ = [("negative_slope", C.c_float), ("_pad2", C.c_int32)]
+
+
 class NormSets(C.Structure):           # mmtta_norm_sets
     _fields_ = [("items_per_set", C.c_int32), ("_pad", C.c_int32), ("affine_stride", C.c_int64), ("stats_stride", C.c_int64)]
 
@@ -74,7 +80,7 @@ OPTIM_ADAM, OPTIM_ADAMW, OPTIM_SGD = 0, 1, 2
 
 
 class ConvEpilogue(C.Structure):
-    _fields_ = [("add", C.POINTER(Tensor)), ("add_norm", NormOnLoad)]
+    _fields_ = [("add", C.POINTER(Tensor)), ("add_norm", NormOnLoadAct)]
 
 
 class IntensityRule(C.Structure):      # mmtta_intensity_rule
@@ -232,7 +238,12 @@ def desc_ncdhw(t: torch.Tensor) -> Tensor:
     return Tensor(t.data_ptr(), n, c, d, h, w, sn, sc, sd, sh, sw, F32, 0)
 
 
+ACT_NONE, ACT_RELU, ACT_LEAKY_RELU = 0, 1, 2       # mmtta_norm_on_load.relu: the activation code (mmtta.h MMTTA_ACT_*)
+
+
 def norm_on_load(mean=None, rstd=None, gamma=None, beta=None, relu=False, scale=None, shift=None,
-                 per_item=False) -> NormOnLoad:
-    return NormOnLoad(ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), 1 if relu else 0, 1 if per_item else 0, ptr(scale),
-                      ptr(shift))
+                 per_item=False, act=None, negative_slope=0.0) -> NormOnLoadAct:
+    """`act` (an ACT_* code) takes precedence over the older `relu` flag; `negative_slope` is read for ACT_LEAKY_RELU."""
+    code = (ACT_RELU if relu else ACT_NONE) if act is None else int(act)
+    return NormOnLoadAct(ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), code, 1 if per_item else 0, ptr(scale),
+                      ptr(shift), float(negative_slope) if code == ACT_LEAKY_RELU else 0.0, 0)

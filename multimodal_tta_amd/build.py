@@ -19,6 +19,10 @@ SOURCES = ["api.hip", "conv_igemm.hip", "conv_direct.hip", "conv_wgrad.hip", "po
            "surface.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-variable",
          "-Wno-unused-but-set-variable"]
+# Sources that read a norm-on-load are compiled a second time as the LeakyReLU instantiation (common.h: namespace
+# mmtta::leaky, entry bodies only); the plain objects keep the ReLU / no-activation kernels exactly as they are.
+ACT_SOURCES = ["conv_igemm.hip", "conv_direct.hip", "conv_wgrad.hip", "pointwise.hip"]
+ACT_FLAGS = ["-DMMTTA_ACT_LEAKY_TU"]
 
 
 def _hipcc() -> str:
@@ -37,7 +41,7 @@ def _digest() -> str:
                 h.update(fh.read())
     with open(os.path.join(os.path.dirname(HERE), "include", "mmtta.h"), "rb") as fh:
         h.update(fh.read())
-    h.update(" ".join(FLAGS).encode())
+    h.update(" ".join(FLAGS + ACT_SOURCES + ACT_FLAGS).encode())
     return h.hexdigest()
 
 
@@ -49,12 +53,14 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     hipcc = _hipcc()
     objs: List[str] = []
     procs = []
-    for src in SOURCES:
-        obj = os.path.join(CSRC, src.replace(".hip", ".o"))
-        cmd = [hipcc, *FLAGS, "-c", os.path.join(CSRC, src), "-o", obj]
+    units = [(src, src.replace(".hip", ".o"), []) for src in SOURCES]
+    units += [(src, src.replace(".hip", "_leaky.o"), ACT_FLAGS) for src in ACT_SOURCES]
+    for src, oname, extra in units:
+        obj = os.path.join(CSRC, oname)
+        cmd = [hipcc, *FLAGS, *extra, "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
-        procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+        procs.append((oname, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
         objs.append(obj)
     failed = False
     for src, p in procs:

@@ -30,6 +30,63 @@ inline int launch_status(const char* what) {
   return MMTTA_OK;
 }
 
+// launch knobs (api.hip): one copy for the whole library
+extern int g_profile_main_only;     // api.hip: mmtta_set_option(MMTTA_OPT_PROFILE_MAIN_KERNEL_ONLY)
+extern int g_igemm_pipeline;        // api.hip: MMTTA_OPT_IGEMM_PIPELINE
+extern int g_wgrad_vec;             // api.hip: MMTTA_OPT_WGRAD_VECTOR_STAGING
+extern int g_igemm_lean;            // api.hip: MMTTA_OPT_IGEMM_LEAN
+extern int g_cls_fused_min;         // api.hip: MMTTA_OPT_CLASS_FUSED_MIN_WORKGROUPS
+extern int g_thin_mfma;             // api.hip: MMTTA_OPT_THIN_MFMA
+extern int g_epilogue_vec;          // api.hip: MMTTA_OPT_EPILOGUE_VEC16
+extern int g_tune[4];               // api.hip: launch-geometry knobs (MMTTA_OPT_SPLITK_BELOW ... MMTTA_OPT_WGRAD_THIN_SLABS)
+
+// ---- activation of a norm-on-load (mmtta_norm_on_load.relu: MMTTA_ACT_*).
+// The four sources that read a norm-on-load (conv_igemm, conv_direct, conv_wgrad, pointwise) are compiled TWICE:
+//   - as they are: `NL::relu` is today's int ReLU flag (MMTTA_ACT_NONE / MMTTA_ACT_RELU), the kernels and their register
+//     figures are exactly those of the ReLU-only library;
+//   - with MMTTA_ACT_LEAKY_TU defined (build.py): everything below lives in namespace mmtta::leaky, `NL::relu` is a float
+//     slope k and every staging / epilogue / backward site computes v > 0 ? v : k*v (NONE = slope 1, RELU = slope 0, so a
+//     launch may mix descriptors).  Only the entry bodies of that copy are reachable: the C entry points of the plain
+//     copy validate the descriptors and hand a call with any LEAKY_RELU descriptor to mmtta::leaky::*_body.
+// So the activation is a compile-time property of the instantiation, picked on the host, as the storage type is.
+inline bool nl_leaky(const mmtta_norm_on_load* t) { return t != nullptr && t->relu == MMTTA_ACT_LEAKY_RELU; }
+inline int nl_act_check(const mmtta_norm_on_load* t, const char* what) {
+  MMTTA_CHECK(t == nullptr || (t->relu >= MMTTA_ACT_NONE && t->relu <= MMTTA_ACT_LEAKY_RELU), MMTTA_ERR_INVALID,
+              "%s: activation code %d (MMTTA_ACT_NONE, _RELU or _LEAKY_RELU)", what, t ? t->relu : 0);
+  MMTTA_CHECK(t == nullptr || t->relu != MMTTA_ACT_LEAKY_RELU || __builtin_isfinite(t->negative_slope), MMTTA_ERR_INVALID,
+              "%s: LeakyReLU negative_slope must be finite", what);
+  return MMTTA_OK;
+}
+
+// entry bodies of one activation instantiation (descriptors already validated by the C entry point)
+#define MMTTA_ACT_BODIES                                                                                                    \
+  int conv_run_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,  \
+                    const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats, \
+                    void* workspace, int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);                \
+  int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,                    \
+                      const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,                        \
+                      int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);                                 \
+  int combine_body(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtta_tensor* b,                              \
+                   const mmtta_norm_on_load* tb, const mmtta_tensor* out, void* stream);                                    \
+  int norm_bwd_reduce_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t, float* part,      \
+                           void* stream);                                                                                   \
+  int norm_bwd_apply_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t, const float* m1,   \
+                          const float* m2, const mmtta_tensor* dy, void* stream);                                           \
+  int norm_bwd_small_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t, int64_t count,     \
+                          const mmtta_tensor* dy, void* stream);
+namespace leaky { MMTTA_ACT_BODIES }
+
+#ifdef MMTTA_ACT_LEAKY_TU
+#define MMTTA_ACT_NS_OPEN namespace leaky {
+#define MMTTA_ACT_NS_CLOSE }
+#else
+#define MMTTA_ACT_NS_OPEN
+#define MMTTA_ACT_NS_CLOSE
+#endif
+
+MMTTA_ACT_NS_OPEN
+MMTTA_ACT_BODIES
+
 inline bool is_cl(const mmtta_tensor* t) { return t->sc == 1 || t->c == 1; }
 
 inline bool is_f32(const mmtta_tensor* t) { return t->dtype == MMTTA_F32; }
@@ -203,21 +260,38 @@ __device__ __forceinline__ long long vox_addr(const TV& t, int n, int z, int y, 
   return (long long)n * t.sn + (long long)z * t.sd + (long long)y * t.sh + (long long)x * t.sw;
 }
 
+// Activation argument of a norm-on-load in this instantiation (see the top of this file): the ReLU flag, or the slope k.
+#ifdef MMTTA_ACT_LEAKY_TU
+typedef float act_t;
+#define MMTTA_ACT_ID 1.f
+#else
+typedef int act_t;
+#define MMTTA_ACT_ID 0
+#endif
+inline act_t act_arg(const mmtta_norm_on_load* t) {
+#ifdef MMTTA_ACT_LEAKY_TU
+  if (t == nullptr) return 1.f;
+  return t->relu == MMTTA_ACT_LEAKY_RELU ? t->negative_slope : (t->relu == MMTTA_ACT_RELU ? 0.f : 1.f);
+#else
+  return t == nullptr ? 0 : t->relu;
+#endif
+}
+
 // Device-side norm-on-load descriptor.
 struct NL {
   const float* mean;
   const float* rstd;
   const float* gamma;
   const float* beta;
-  int relu;
+  act_t relu;      // activation argument (act_t above)
   const float* scale;
   const float* shift;
 };
 
 inline NL nl(const mmtta_norm_on_load* t) {
   NL r;
-  if (t == nullptr) { r.mean = r.rstd = r.gamma = r.beta = r.scale = r.shift = nullptr; r.relu = 0; return r; }
-  r.mean = t->mean; r.rstd = t->rstd; r.gamma = t->gamma; r.beta = t->beta; r.relu = t->relu;
+  if (t == nullptr) { r.mean = r.rstd = r.gamma = r.beta = r.scale = r.shift = nullptr; r.relu = MMTTA_ACT_ID; return r; }
+  r.mean = t->mean; r.rstd = t->rstd; r.gamma = t->gamma; r.beta = t->beta; r.relu = act_arg(t);
   r.scale = t->scale; r.shift = t->scale ? t->shift : nullptr;
   return r;
 }
@@ -332,10 +406,31 @@ __device__ __forceinline__ void nl_coeff_vec(const NL& t, int n, int C, int c0, 
     if (c0 + j >= C) { sc[j] = 0.f; sh[j] = 0.f; }
 }
 
+// The activation after the affine, in three forms:
+//   nl_apply(x, sc, sh, t.relu)            one element
+//   lo = act_lo(t.relu); act_max(v, lo)    the hoisted form of the staging loops (ReLU: max with 0 or -inf)
+//   MMTTA_ACT_BWD(dz, t.relu, post)        the gradient through it: dz *= act'(post)
+#ifdef MMTTA_ACT_LEAKY_TU
+// torch leaky_relu / leaky_relu_backward: a select, not max(v, k*v), which holds for 0 <= k <= 1 only
+__device__ __forceinline__ float act_max(float v, float k) { return v > 0.f ? v : k * v; }
+__device__ __forceinline__ float act_lo(float k) { return k; }
+__device__ __forceinline__ float nl_apply(float x, float sc, float sh, float k) { return act_max(fmaf(x, sc, sh), k); }
+#define MMTTA_ACT_BWD(dz, k, post) \
+  do {                             \
+    if (!((post) > 0.f)) (dz) *= (k); \
+  } while (0)
+#else
 __device__ __forceinline__ float nl_apply(float x, float sc, float sh, int relu) {
   float v = fmaf(x, sc, sh);
   return relu ? fmaxf(v, 0.f) : v;
 }
+__device__ __forceinline__ float act_max(float v, float lo) { return fmaxf(v, lo); }
+__device__ __forceinline__ float act_lo(int relu) { return relu ? 0.f : -__builtin_inff(); }
+#define MMTTA_ACT_BWD(dz, relu, post) \
+  do {                                \
+    if ((relu) && !((post) > 0.f)) (dz) = 0.f; \
+  } while (0)
+#endif
 
 // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2 (observed placement: a speed matter only).
 // Give the workgroups that share an XCD one CONTIGUOUS range of logical ids, so that neighbours in the logical order
@@ -423,14 +518,6 @@ int channel_partial_rows(const mmtta_tensor* t);                        // parti
 int launch_channel_sums(const mmtta_tensor* x, float* part, hipStream_t s);  // part: [N*rows][2][C] (sum, sumsq)
 
 // direct path for layers producing <= 4 channels (conv_direct.hip)
-extern int g_profile_main_only;     // api.hip: mmtta_set_option(MMTTA_OPT_PROFILE_MAIN_KERNEL_ONLY)
-extern int g_igemm_pipeline;        // api.hip: MMTTA_OPT_IGEMM_PIPELINE
-extern int g_wgrad_vec;             // api.hip: MMTTA_OPT_WGRAD_VECTOR_STAGING
-extern int g_igemm_lean;            // api.hip: MMTTA_OPT_IGEMM_LEAN
-extern int g_cls_fused_min;         // api.hip: MMTTA_OPT_CLASS_FUSED_MIN_WORKGROUPS
-extern int g_thin_mfma;             // api.hip: MMTTA_OPT_THIN_MFMA
-extern int g_epilogue_vec;          // api.hip: MMTTA_OPT_EPILOGUE_VEC16
-extern int g_tune[4];               // api.hip: launch-geometry knobs (MMTTA_OPT_SPLITK_BELOW ... MMTTA_OPT_WGRAD_THIN_SLABS)
 bool direct_applicable(const mmtta_conv_desc* d);
 // bytes of the fragment-ordered bf16 weight image W' of the 2x2x2 gather-GEMM up-convolution (conv_direct.hip,
 // upconv8_kernel), stored behind the fp32 tap image of the packed buffer; 0 for every other layer
@@ -451,4 +538,5 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
                     const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
                     const PSets& sets, hipStream_t stream);
 
+MMTTA_ACT_NS_CLOSE
 }  // namespace mmtta

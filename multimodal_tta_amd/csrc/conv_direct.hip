@@ -15,6 +15,7 @@
 #include "common.h"
 
 namespace mmtta {
+MMTTA_ACT_NS_OPEN
 
 typedef float float2_t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -528,7 +529,7 @@ __global__ __launch_bounds__(256) void conv3_mfma4_kernel(DArgs a) {
 #pragma unroll
     for (int k = 0; k < 4; ++k)
       if (k >= a.K) { sc[k] = 0.f; sh[k] = 0.f; }                   // pad lanes of the voxel row may hold anything
-    const float relu_lo = (HAS_T && a.tin.relu) ? 0.f : -__builtin_inff();
+    const float relu_lo = act_lo(HAS_T ? a.tin.relu : MMTTA_ACT_ID);
     const float* inb = GBF ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(a.in.p) + (long long)n * a.in.sn)
                            : a.in.p + (long long)n * a.in.sn;
     const unsigned isw = (unsigned)a.in.sw;
@@ -568,7 +569,7 @@ __global__ __launch_bounds__(256) void conv3_mfma4_kernel(DArgs a) {
           const float xs[4] = {raw[j][q].x, raw[j][q].y, raw[j][q].z, raw[j][q].w};
           float v4[4];
 #pragma unroll
-          for (int k = 0; k < 4; ++k) v4[k] = fmaxf(fmaf(xs[k], sc[k], sh[k]), relu_lo);
+          for (int k = 0; k < 4; ++k) v4[k] = act_max(fmaf(xs[k], sc[k], sh[k]), relu_lo);
           const unsigned m = ((okm >> (4 * j + q)) & 1u) ? 0xffffffffu : 0u;
           pk[q].x = f32x2_to_bf16x2(v4[0], v4[1]) & m; pk[q].y = f32x2_to_bf16x2(v4[2], v4[3]) & m;
         }
@@ -1716,7 +1717,7 @@ __global__ __launch_bounds__(256, 2) void upconv8_kernel(DArgs a, int tiles_per_
   static_assert(256 % KC8 == 0, "items of a thread must share their channel octet");
   float sc[8], sh[8];
   if (HAS_T) nl_coeff_vec<8>(a.tin, n, K, (tid % KC8) * 8, sc, sh);
-  const float relu_lo = (HAS_T && a.tin.relu) ? 0.f : -__builtin_inff();
+  const float relu_lo = act_lo(HAS_T ? a.tin.relu : MMTTA_ACT_ID);
   const float* inb = item_base<INBF>(a.in.p, n, a.in.sn);
   const unsigned isd = (unsigned)a.in.sd, ish = (unsigned)a.in.sh, isw = (unsigned)a.in.sw;
   long long tfirst, tlast;
@@ -1763,7 +1764,7 @@ __global__ __launch_bounds__(256, 2) void upconv8_kernel(DArgs a, int tiles_per_
       oct8_f8(raw[j], v);
       if (HAS_T) {
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = fmaxf(fmaf(v[q], sc[q], sh[q]), relu_lo);
+        for (int q = 0; q < 8; ++q) v[q] = act_max(fmaf(v[q], sc[q], sh[q]), relu_lo);
       }
       const unsigned m = ((okm >> j) & 1u) ? 0xffffffffu : 0u;
       uint4 pk;
@@ -2015,4 +2016,5 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   return launch_status("direct conv");
 }
 
+MMTTA_ACT_NS_CLOSE
 }  // namespace mmtta

@@ -27,6 +27,7 @@
 #include "common.h"
 
 namespace mmtta {
+MMTTA_ACT_NS_OPEN
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -479,13 +480,13 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(GArgs a) {
           sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w; sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w;
           sh[0] = h0.x; sh[1] = h0.y; sh[2] = h0.z; sh[3] = h0.w; sh[4] = h1.x; sh[5] = h1.y; sh[6] = h1.z; sh[7] = h1.w;
         }
-        const float relu_lo = a.tin.relu ? 0.f : -__builtin_inff();
+        const float relu_lo = act_lo(a.tin.relu);
         auto commit_item = [&](auto pc) {
           constexpr int P = decltype(pc)::value;
           float v[8];
           oct8_f8(gv[P], v);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = fmaxf(fmaf(v[j], sc[j], sh[j]), relu_lo);
+          for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
           const unsigned okm = ((pok >> P) & 1u) ? 0xffffffffu : 0u;
           uint4 pk;
           pk.x = pack_bf16x2(v[0], v[1]) & okm; pk.y = pack_bf16x2(v[2], v[3]) & okm;
@@ -775,6 +776,10 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(GArgs a) {
             }
           }
         }
+      } else if (pipe && stage + 1 < ks1) {
+        // a wave without live columns (Np no multiple of 32 * NB) still stages its share of the next box: its prefetch
+        // is due all the same, or the next stage commits the registers of this one
+        issue(stage + 1);
       }
     } else {
     // ---------------- MFMA over taps x channel pairs ----------------
@@ -1026,7 +1031,7 @@ __global__ __launch_bounds__(256, 2) void igemm_cls8_kernel(GArgs a) {
   const int cmax = ABF ? ((a.Ci - 1) & ~7) : ((a.Ci - 1) & ~3);
   constexpr int AIT = (BZ * BY * BX * KC8 + 255) / 256;      // box items per thread
   constexpr int BIT = (WIMG + 255) / 256;                    // weight entries per thread
-  const float relu_lo = a.tin.relu ? 0.f : -__builtin_inff();
+  const float relu_lo = act_lo(a.tin.relu);
 
   for (int ks = 0; ks < a.nstages; ++ks) {
     const int c0 = ks * KCI;
@@ -1071,7 +1076,7 @@ __global__ __launch_bounds__(256, 2) void igemm_cls8_kernel(GArgs a) {
       float v[8];
       oct8_f8(av[j], v);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = fmaxf(fmaf(v[q], sc[j][q], sh[j][q]), relu_lo);
+      for (int q = 0; q < 8; ++q) v[q] = act_max(fmaf(v[q], sc[j][q], sh[j][q]), relu_lo);
       const unsigned okm = ((aok >> j) & 1u) ? 0xffffffffu : 0u;
       uint4 pk;
       pk.x = pack_bf16x2(v[0], v[1]) & okm; pk.y = pack_bf16x2(v[2], v[3]) & okm;
@@ -1541,7 +1546,7 @@ __global__ __launch_bounds__(256) void pointwise_mfma_kernel(PWArgs a) {
   const float* inn = item_base<BF>(a.in, n, a.isn);
   float* outn = const_cast<float*>(item_base<BF>(a.out, n, a.osn));
   const float* addn = a.add == nullptr ? nullptr : item_base<BF>(a.add, n, a.asn);
-  const float relu_lo = a.tadd.relu ? 0.f : -__builtin_inff();
+  const float relu_lo = act_lo(a.tadd.relu);
   // every wave makes the same number of trips (a wave past the end works on clamped voxels and stores nothing): the tile
   // hand-over below needs no more than the wave's own program order
   for (long long base = (long long)blockIdx.x * 128; base < a.dhw; base += (long long)gridDim.x * 128) {
@@ -1609,7 +1614,7 @@ __global__ __launch_bounds__(256) void pointwise_mfma_kernel(PWArgs a) {
             for (int e = 0; e < 8; ++e) ad[e] = c0 + e < a.Co ? ld1_t<BF>(addn, (unsigned)vv * a.asw + c0 + e) : 0.f;
           }
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] += fmaxf(fmaf(ad[e], coef[1][c0 + e], coef[2][c0 + e]), relu_lo);
+          for (int e = 0; e < 8; ++e) v[e] += act_max(fmaf(ad[e], coef[1][c0 + e], coef[2][c0 + e]), relu_lo);
         }
         if (full) {
           if (a.accumulate) {
@@ -1935,8 +1940,135 @@ static int launch_any(const Config& c, const GArgs& a, const Taps* ht, int tiles
   }
 }
 
+// mmtta_conv_run_sets past the checks of its norm-on-load descriptors
+int conv_run_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
+                  const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
+                  void* workspace, int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
+  Geometry g;
+  int st = geometry(d, x, y, g);
+  if (st) return st;
+  MMTTA_CHECK(packed != nullptr, MMTTA_ERR_INVALID, "conv: null packed weights");
+  st = psets_validate(sets, x->n);
+  if (st) return st;
+  const PSets ps = psets(sets);
+  if (direct_applicable(d)) return direct_conv_run(d, x, x_norm, packed, bias, epi, y, accumulate, stats, ps, (hipStream_t)stream);
+  if (pointwise_small_applicable(d, x, y, stats, epi, x_norm) && !use_bf16(d, g.K) && is_f32(x))      // (y: fp32- or bf16-stored)
+    return pointwise_small_run(x, packed, g.Kp, g.Np, bias, y, accumulate, ps, (hipStream_t)stream);
+  if (chan_applicable(d, x, y) && !use_bf16(d, g.K))
+    return chan_conv_run(d, x, x_norm, packed, g.Kp, g.Np, bias, epi, y, accumulate, stats, ps, (hipStream_t)stream);
+  {  // 1x1x1 over many voxels with bf16 operands, nothing but bias / add / accumulate around it: the streaming kernel
+    static const bool pw_on = !(getenv("MMTTA_POINTWISE_MFMA") && atoi(getenv("MMTTA_POINTWISE_MFMA")) == 0);      // (A/B switch)
+    auto dense = [](const mmtta_tensor* t) { return t->sc == 1 && t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
+    const mmtta_tensor* ad = (epi && epi->add) ? epi->add : nullptr;
+    const bool bfs = is_bf16(x);
+    const long long dhw = (long long)y->d * y->h * y->w;
+    const int kb = (g.K + 15) / 16;
+    auto rows_ok = [&](const mmtta_tensor* t) {
+      return dense(t) && is_bf16(t) == bfs && ((uintptr_t)t->ptr) % 16 == 0 && t->sw % (bfs ? 8 : 4) == 0 && t->sn % (bfs ? 8 : 4) == 0 &&
+             dhw * t->sw < (1LL << 31);
+    };
+    const bool pw = pw_on && d->ksize == 1 && (d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONV_DGRAD) && use_bf16(d, g.K) &&
+                    (kb <= 4 || kb == 6 || kb == 8) && g.Np <= 64 && stats == nullptr && !(x_norm && (x_norm->mean || x_norm->scale)) &&
+                    dhw >= 4096 && rows_ok(x) && rows_ok(y) && (ad == nullptr || (rows_ok(ad) && ad->n == y->n && ad->c == y->c && ad->d == y->d && ad->h == y->h && ad->w == y->w));
+    if (pw) {
+      PWArgs q;
+      q.in = (const float*)x->ptr; q.isn = x->sn; q.isw = (unsigned)x->sw; q.Ci = x->c;
+      q.out = (float*)y->ptr; q.osn = y->sn; q.osw = (unsigned)y->sw; q.Co = y->c;
+      q.add = ad ? (const float*)ad->ptr : nullptr; q.asn = ad ? ad->sn : 0; q.asw = ad ? (unsigned)ad->sw : 0u;
+      q.tadd = ad ? nl(&epi->add_norm) : nl(nullptr);
+      q.wp = (const float*)packed; q.bias = bias; q.Np = g.Np; q.ps = ps; q.accumulate = accumulate; q.dhw = dhw;
+      long long blocks = (dhw + 127) / 128;
+      if (blocks > 2048) blocks = 2048;
+      const dim3 grid((unsigned)blocks, y->n);
+      if (bfs) launch_pointwise_mfma<true>(q, kb, g.Np / 32, grid, (hipStream_t)stream);
+      else launch_pointwise_mfma<false>(q, kb, g.Np / 32, grid, (hipStream_t)stream);
+      return launch_status("1x1 conv (streaming MFMA)");
+    }
+  }
+  const int64_t need = g.ksplit > 1 ? (int64_t)g.ksplit * g.tiles * g.cfg.TZ * g.cfg.TY * g.cfg.TX * g.Np * 4 : 0;
+  MMTTA_CHECK(need == 0 || (workspace != nullptr && workspace_bytes >= need), MMTTA_ERR_WORKSPACE,
+              "conv: workspace %lld bytes, need %lld", (long long)workspace_bytes, (long long)need);
+  GArgs a;
+  a.in = (const float*)x->ptr; a.isn = x->sn; a.isd = x->sd; a.ish = x->sh; a.isw = x->sw;
+  a.Ci = x->c; a.Di = x->d; a.Hi = x->h; a.Wi = x->w;
+  a.tin = nl(x_norm);
+  a.out = (float*)y->ptr; a.osn = y->sn; a.osd = y->sd; a.osh = y->sh; a.osw = y->sw;
+  a.Co = y->c; a.Do = y->d; a.Ho = y->h; a.Wo = y->w;
+  a.si = g.si;
+  a.wp = (const float*)packed; a.Kp = g.Kp; a.Np = g.Np;
+  a.bias = bias;
+  a.ps = ps;
+  a.add = nullptr; a.asn = a.asd = a.ash = a.asw = 0; a.tadd = nl(nullptr);
+  if (epi && epi->add) {
+    const mmtta_tensor* ad = epi->add;
+    MMTTA_CHECK(ad->ptr && is_cl(ad) && ad->n == y->n && ad->c == y->c && ad->d == y->d && ad->h == y->h && ad->w == y->w,
+                MMTTA_ERR_INVALID, "conv: epilogue `add` must be channels-last with the shape of y");
+    a.add = (const float*)ad->ptr; a.asn = ad->sn; a.asd = ad->sd; a.ash = ad->sh; a.asw = ad->sw;
+    a.tadd = nl(&epi->add_norm);
+  }
+  a.accumulate = accumulate;
+  a.in_bf = is_bf16(x) ? 1 : 0;
+  a.out_bf = is_bf16(y) ? 1 : 0;
+  a.add_bf = (epi && epi->add && is_bf16(epi->add)) ? 1 : 0;
+  {
+    auto al16 = [](const void* p, long long sn, long long sd, long long sh, long long sw, int bf) {      // 4-channel accesses
+      return ((uintptr_t)p) % (bf ? 8 : 16) == 0 && sn % 4 == 0 && sd % 4 == 0 && sh % 4 == 0 && sw % 4 == 0;
+    };
+    const bool oal = al16(y->ptr, y->sn, y->sd, y->sh, y->sw, a.out_bf) && y->c % 4 == 0 &&
+                     (a.add == nullptr || al16(a.add, a.asn, a.asd, a.ash, a.asw, a.add_bf)) &&
+                     (bias == nullptr || ((uintptr_t)bias) % 16 == 0);
+    a.ovec = (oal && g_epilogue_vec) ? 1 : 0;
+  }
+  const int srt = stats_rows_per_tile(g);
+  a.stats = stats; a.stats_rows_per_n = g.ncls * g.tiles_per_n * srt;
+  a.ws = (float*)workspace; a.ksplit = g.ksplit; a.stages_per_split = g.sps; a.nstages = g.nstages;
+  a.tz = g.tz; a.ty = g.ty; a.tx = g.tx;
+  MMTTA_CHECK(g.cfg.bf || (!a.in_bf && !a.out_bf && !a.add_bf), MMTTA_ERR_UNSUPPORTED,
+              "conv: bf16-stored tensors need a bf16-operand layer (K >= 16 in bf16 precision)");
+  // 8-channel items: 32 bytes of fp32 (two 16-byte loads) or 16 bytes of bf16 (one): strides must keep them aligned
+  const int am = a.in_bf ? 8 : 4;
+  const bool al = (((uintptr_t)x->ptr) % 16 == 0) && x->sw % am == 0 && x->sh % am == 0 && x->sd % am == 0 && x->sn % am == 0;
+  a.vec4 = al ? 1 : 0;
+  a.flip27 = 0;
+  {  // row-structured loader of the 3x3x3 stride-1 stages: 32-bit element offsets from 24-bit multiply-adds
+    const int64_t lim24 = (int64_t)1 << 24;
+    const int64_t last = (int64_t)(x->d - 1) * x->sd + (int64_t)(x->h - 1) * x->sh + (int64_t)(x->w - 1) * x->sw + x->c + 16;
+    a.rowload = (al && x->sd < lim24 && x->sh < lim24 && x->sw < lim24 && x->d < lim24 && x->h < lim24 && x->w < lim24 &&
+                 last < ((int64_t)1 << 31) && g_igemm_pipeline) ? 1 : 0;
+  }
+  Taps ht[8];
+  a.ncls = g.classes ? 8 : 1;
+  a.so = g.classes ? 2 : 1;
+  int tap0 = 0;
+  for (int cls = 0; cls < a.ncls; ++cls) {
+    const int pz = (cls >> 2) & 1, py = (cls >> 1) & 1, px = cls & 1;
+    build_taps(d, pz, py, px, ht[cls]);
+    ClassInfo& ci = a.cls[cls];
+    ci.tap0 = tap0; ci.ntaps = ht[cls].n; tap0 += ht[cls].n;
+    ci.zmin = ht[cls].zmin; ci.ymin = ht[cls].ymin; ci.xmin = ht[cls].xmin;
+    ci.zext = ht[cls].zext; ci.yext = ht[cls].yext; ci.xext = ht[cls].xext;
+    if (g.classes) {
+      ci.oz = pz; ci.oy = py; ci.ox = px;
+      ci.Dg = (y->d - pz + 1) / 2; ci.Hg = (y->h - py + 1) / 2; ci.Wg = (y->w - px + 1) / 2;
+    } else {
+      ci.oz = ci.oy = ci.ox = 0;
+      ci.Dg = y->d; ci.Hg = y->h; ci.Wg = y->w;
+    }
+  }
+  if (g.fused) {
+    MMTTA_CHECK(a.ovec && a.vec4, MMTTA_ERR_UNSUPPORTED,
+                "conv (class-fused stride-2 form): the epilogue operands must admit 16-byte accesses");
+    MMTTA_CHECK(a.in_bf == a.out_bf && (a.add == nullptr || a.add_bf == a.out_bf), MMTTA_ERR_UNSUPPORTED,
+                "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf, a.add_bf);
+    return a.in_bf ? launch_cls8_t<16, true>(a, g.tiles, (hipStream_t)stream) : launch_cls8_t<16, false>(a, g.tiles, (hipStream_t)stream);
+  }
+  return launch_any(g.cfg, a, ht, g.tiles, (hipStream_t)stream);
+}
+
+MMTTA_ACT_NS_CLOSE
 }  // namespace mmtta
 
+#ifndef MMTTA_ACT_LEAKY_TU
 using namespace mmtta;
 
 extern "C" int64_t mmtta_conv_packed_bytes(const mmtta_conv_desc* d) {
@@ -2078,129 +2210,19 @@ extern "C" int mmtta_conv_run_sets(const mmtta_conv_desc* d, const mmtta_tensor*
                                    const void* packed, const float* bias, const mmtta_conv_epilogue* epi,
                                    const mmtta_tensor* y, int accumulate, float* stats, void* workspace,
                                    int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
+  const mmtta_norm_on_load* add_norm = (epi && epi->add) ? &epi->add_norm : nullptr;
   {
-    const int pst = nl_per_item_check(x_norm, "conv_run (x_norm)");
-    if (pst) return pst;
-    const int ast = nl_per_item_check(epi ? &epi->add_norm : nullptr, "conv_run (epilogue add_norm)");
-    if (ast) return ast;
+    int st = nl_act_check(x_norm, "conv_run (x_norm)");
+    if (st) return st;
+    st = nl_act_check(add_norm, "conv_run (epilogue add_norm)");
+    if (st) return st;
+    st = nl_per_item_check(x_norm, "conv_run (x_norm)");
+    if (st) return st;
+    st = nl_per_item_check(epi ? &epi->add_norm : nullptr, "conv_run (epilogue add_norm)");
+    if (st) return st;
   }
-  Geometry g;
-  int st = geometry(d, x, y, g);
-  if (st) return st;
-  MMTTA_CHECK(packed != nullptr, MMTTA_ERR_INVALID, "conv: null packed weights");
-  st = psets_validate(sets, x->n);
-  if (st) return st;
-  const PSets ps = psets(sets);
-  if (direct_applicable(d)) return direct_conv_run(d, x, x_norm, packed, bias, epi, y, accumulate, stats, ps, (hipStream_t)stream);
-  if (pointwise_small_applicable(d, x, y, stats, epi, x_norm) && !use_bf16(d, g.K) && is_f32(x))      // (y: fp32- or bf16-stored)
-    return pointwise_small_run(x, packed, g.Kp, g.Np, bias, y, accumulate, ps, (hipStream_t)stream);
-  if (chan_applicable(d, x, y) && !use_bf16(d, g.K))
-    return chan_conv_run(d, x, x_norm, packed, g.Kp, g.Np, bias, epi, y, accumulate, stats, ps, (hipStream_t)stream);
-  {  // 1x1x1 over many voxels with bf16 operands, nothing but bias / add / accumulate around it: the streaming kernel
-    static const bool pw_on = !(getenv("MMTTA_POINTWISE_MFMA") && atoi(getenv("MMTTA_POINTWISE_MFMA")) == 0);      // (A/B switch)
-    auto dense = [](const mmtta_tensor* t) { return t->sc == 1 && t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
-    const mmtta_tensor* ad = (epi && epi->add) ? epi->add : nullptr;
-    const bool bfs = is_bf16(x);
-    const long long dhw = (long long)y->d * y->h * y->w;
-    const int kb = (g.K + 15) / 16;
-    auto rows_ok = [&](const mmtta_tensor* t) {
-      return dense(t) && is_bf16(t) == bfs && ((uintptr_t)t->ptr) % 16 == 0 && t->sw % (bfs ? 8 : 4) == 0 && t->sn % (bfs ? 8 : 4) == 0 &&
-             dhw * t->sw < (1LL << 31);
-    };
-    const bool pw = pw_on && d->ksize == 1 && (d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONV_DGRAD) && use_bf16(d, g.K) &&
-                    (kb <= 4 || kb == 6 || kb == 8) && g.Np <= 64 && stats == nullptr && !(x_norm && (x_norm->mean || x_norm->scale)) &&
-                    dhw >= 4096 && rows_ok(x) && rows_ok(y) && (ad == nullptr || (rows_ok(ad) && ad->n == y->n && ad->c == y->c && ad->d == y->d && ad->h == y->h && ad->w == y->w));
-    if (pw) {
-      PWArgs q;
-      q.in = (const float*)x->ptr; q.isn = x->sn; q.isw = (unsigned)x->sw; q.Ci = x->c;
-      q.out = (float*)y->ptr; q.osn = y->sn; q.osw = (unsigned)y->sw; q.Co = y->c;
-      q.add = ad ? (const float*)ad->ptr : nullptr; q.asn = ad ? ad->sn : 0; q.asw = ad ? (unsigned)ad->sw : 0u;
-      q.tadd = ad ? nl(&epi->add_norm) : nl(nullptr);
-      q.wp = (const float*)packed; q.bias = bias; q.Np = g.Np; q.ps = ps; q.accumulate = accumulate; q.dhw = dhw;
-      long long blocks = (dhw + 127) / 128;
-      if (blocks > 2048) blocks = 2048;
-      const dim3 grid((unsigned)blocks, y->n);
-      if (bfs) launch_pointwise_mfma<true>(q, kb, g.Np / 32, grid, (hipStream_t)stream);
-      else launch_pointwise_mfma<false>(q, kb, g.Np / 32, grid, (hipStream_t)stream);
-      return launch_status("1x1 conv (streaming MFMA)");
-    }
-  }
-  const int64_t need = g.ksplit > 1 ? (int64_t)g.ksplit * g.tiles * g.cfg.TZ * g.cfg.TY * g.cfg.TX * g.Np * 4 : 0;
-  MMTTA_CHECK(need == 0 || (workspace != nullptr && workspace_bytes >= need), MMTTA_ERR_WORKSPACE,
-              "conv: workspace %lld bytes, need %lld", (long long)workspace_bytes, (long long)need);
-  GArgs a;
-  a.in = (const float*)x->ptr; a.isn = x->sn; a.isd = x->sd; a.ish = x->sh; a.isw = x->sw;
-  a.Ci = x->c; a.Di = x->d; a.Hi = x->h; a.Wi = x->w;
-  a.tin = nl(x_norm);
-  a.out = (float*)y->ptr; a.osn = y->sn; a.osd = y->sd; a.osh = y->sh; a.osw = y->sw;
-  a.Co = y->c; a.Do = y->d; a.Ho = y->h; a.Wo = y->w;
-  a.si = g.si;
-  a.wp = (const float*)packed; a.Kp = g.Kp; a.Np = g.Np;
-  a.bias = bias;
-  a.ps = ps;
-  a.add = nullptr; a.asn = a.asd = a.ash = a.asw = 0; a.tadd = nl(nullptr);
-  if (epi && epi->add) {
-    const mmtta_tensor* ad = epi->add;
-    MMTTA_CHECK(ad->ptr && is_cl(ad) && ad->n == y->n && ad->c == y->c && ad->d == y->d && ad->h == y->h && ad->w == y->w,
-                MMTTA_ERR_INVALID, "conv: epilogue `add` must be channels-last with the shape of y");
-    a.add = (const float*)ad->ptr; a.asn = ad->sn; a.asd = ad->sd; a.ash = ad->sh; a.asw = ad->sw;
-    a.tadd = nl(&epi->add_norm);
-  }
-  a.accumulate = accumulate;
-  a.in_bf = is_bf16(x) ? 1 : 0;
-  a.out_bf = is_bf16(y) ? 1 : 0;
-  a.add_bf = (epi && epi->add && is_bf16(epi->add)) ? 1 : 0;
-  {
-    auto al16 = [](const void* p, long long sn, long long sd, long long sh, long long sw, int bf) {      // 4-channel accesses
-      return ((uintptr_t)p) % (bf ? 8 : 16) == 0 && sn % 4 == 0 && sd % 4 == 0 && sh % 4 == 0 && sw % 4 == 0;
-    };
-    const bool oal = al16(y->ptr, y->sn, y->sd, y->sh, y->sw, a.out_bf) && y->c % 4 == 0 &&
-                     (a.add == nullptr || al16(a.add, a.asn, a.asd, a.ash, a.asw, a.add_bf)) &&
-                     (bias == nullptr || ((uintptr_t)bias) % 16 == 0);
-    a.ovec = (oal && g_epilogue_vec) ? 1 : 0;
-  }
-  const int srt = stats_rows_per_tile(g);
-  a.stats = stats; a.stats_rows_per_n = g.ncls * g.tiles_per_n * srt;
-  a.ws = (float*)workspace; a.ksplit = g.ksplit; a.stages_per_split = g.sps; a.nstages = g.nstages;
-  a.tz = g.tz; a.ty = g.ty; a.tx = g.tx;
-  MMTTA_CHECK(g.cfg.bf || (!a.in_bf && !a.out_bf && !a.add_bf), MMTTA_ERR_UNSUPPORTED,
-              "conv: bf16-stored tensors need a bf16-operand layer (K >= 16 in bf16 precision)");
-  // 8-channel items: 32 bytes of fp32 (two 16-byte loads) or 16 bytes of bf16 (one): strides must keep them aligned
-  const int am = a.in_bf ? 8 : 4;
-  const bool al = (((uintptr_t)x->ptr) % 16 == 0) && x->sw % am == 0 && x->sh % am == 0 && x->sd % am == 0 && x->sn % am == 0;
-  a.vec4 = al ? 1 : 0;
-  a.flip27 = 0;
-  {  // row-structured loader of the 3x3x3 stride-1 stages: 32-bit element offsets from 24-bit multiply-adds
-    const int64_t lim24 = (int64_t)1 << 24;
-    const int64_t last = (int64_t)(x->d - 1) * x->sd + (int64_t)(x->h - 1) * x->sh + (int64_t)(x->w - 1) * x->sw + x->c + 16;
-    a.rowload = (al && x->sd < lim24 && x->sh < lim24 && x->sw < lim24 && x->d < lim24 && x->h < lim24 && x->w < lim24 &&
-                 last < ((int64_t)1 << 31) && g_igemm_pipeline) ? 1 : 0;
-  }
-  Taps ht[8];
-  a.ncls = g.classes ? 8 : 1;
-  a.so = g.classes ? 2 : 1;
-  int tap0 = 0;
-  for (int cls = 0; cls < a.ncls; ++cls) {
-    const int pz = (cls >> 2) & 1, py = (cls >> 1) & 1, px = cls & 1;
-    build_taps(d, pz, py, px, ht[cls]);
-    ClassInfo& ci = a.cls[cls];
-    ci.tap0 = tap0; ci.ntaps = ht[cls].n; tap0 += ht[cls].n;
-    ci.zmin = ht[cls].zmin; ci.ymin = ht[cls].ymin; ci.xmin = ht[cls].xmin;
-    ci.zext = ht[cls].zext; ci.yext = ht[cls].yext; ci.xext = ht[cls].xext;
-    if (g.classes) {
-      ci.oz = pz; ci.oy = py; ci.ox = px;
-      ci.Dg = (y->d - pz + 1) / 2; ci.Hg = (y->h - py + 1) / 2; ci.Wg = (y->w - px + 1) / 2;
-    } else {
-      ci.oz = ci.oy = ci.ox = 0;
-      ci.Dg = y->d; ci.Hg = y->h; ci.Wg = y->w;
-    }
-  }
-  if (g.fused) {
-    MMTTA_CHECK(a.ovec && a.vec4, MMTTA_ERR_UNSUPPORTED,
-                "conv (class-fused stride-2 form): the epilogue operands must admit 16-byte accesses");
-    MMTTA_CHECK(a.in_bf == a.out_bf && (a.add == nullptr || a.add_bf == a.out_bf), MMTTA_ERR_UNSUPPORTED,
-                "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf, a.add_bf);
-    return a.in_bf ? launch_cls8_t<16, true>(a, g.tiles, (hipStream_t)stream) : launch_cls8_t<16, false>(a, g.tiles, (hipStream_t)stream);
-  }
-  return launch_any(g.cfg, a, ht, g.tiles, (hipStream_t)stream);
+  if (nl_leaky(x_norm) || nl_leaky(add_norm))
+    return leaky::conv_run_body(d, x, x_norm, packed, bias, epi, y, accumulate, stats, workspace, workspace_bytes, sets, stream);
+  return conv_run_body(d, x, x_norm, packed, bias, epi, y, accumulate, stats, workspace, workspace_bytes, sets, stream);
 }
+#endif  // MMTTA_ACT_LEAKY_TU

@@ -19,6 +19,7 @@
 #include "common.h"
 
 namespace mmtta {
+MMTTA_ACT_NS_OPEN
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 static inline int roundup(int v, int m) { return (v + m - 1) / m * m; }
@@ -515,7 +516,7 @@ __global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_ke
   int pn = -1, poz0 = 0, poy0 = 0, pox0 = 0;     // tile whose loads are in gv[0..PG) / dq
   int cn = -1;                                   // batch item the transform coefficients belong to
   float* coefl = reinterpret_cast<float*>(dl + NB * G::D_BYTES);     // [NB][2][32]: scale, shift of the module-input channels
-  const float relu_lo = (TD ? a.td.relu : a.tg.relu) ? 0.f : -__builtin_inff();
+  const float relu_lo = act_lo(TD ? a.td.relu : a.tg.relu);
   unsigned gxoff = 0u;                           // per tile: x / channel part of the box offsets, x in bounds
   bool gxok = false;
 
@@ -551,7 +552,7 @@ __global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_ke
     oct8_f8(gv[P], v);
     if constexpr (!TD) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = fmaxf(fmaf(v[j], sc[j], sh[j]), relu_lo);
+      for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
     }
     const unsigned okm = ((pok >> P) & 1u) ? 0xffffffffu : 0u;
     uint4 pk;
@@ -637,7 +638,7 @@ __global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_ke
       oct8_f8(dq[p], v);
       if constexpr (TD) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = fmaxf(fmaf(v[j], sc[j], sh[j]), relu_lo);
+        for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
       }
       const unsigned okm = ((dok >> p) & 1u) ? 0xffffffffu : 0u;
       if (want_db) {                                                  // bias gradient: fp32 sums of what is staged
@@ -674,7 +675,7 @@ __global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_ke
       oct8_f8(dq[nb * DP + p], v);
       if constexpr (TD) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = fmaxf(fmaf(v[j], sc[j], sh[j]), relu_lo);
+        for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
       }
       const unsigned okm = ((dok >> p) & 1u) ? 0xffffffffu : 0u;
       if (want_db) {                                                  // bias gradient: fp32 sums of what is staged
@@ -872,7 +873,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_tr1_kernel(WArgs a) {
       sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w; sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w;
       sh[0] = h0.x; sh[1] = h0.y; sh[2] = h0.z; sh[3] = h0.w; sh[4] = h1.x; sh[5] = h1.y; sh[6] = h1.z; sh[7] = h1.w;
     }
-    const float relu_lo = (td ? a.td.relu : a.tg.relu) ? 0.f : -__builtin_inff();
+    const float relu_lo = act_lo(td ? a.td.relu : a.tg.relu);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const unsigned okm = ((okbits >> p) & 1u) ? 0xffffffffu : 0u;
@@ -881,10 +882,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_tr1_kernel(WArgs a) {
       oct8_f8(dq[p], u);
       if (td) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) u[j] = fmaxf(fmaf(u[j], sc[j], sh[j]), relu_lo);
+        for (int j = 0; j < 8; ++j) u[j] = act_max(fmaf(u[j], sc[j], sh[j]), relu_lo);
       } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = fmaxf(fmaf(v[j], sc[j], sh[j]), relu_lo);
+        for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
       }
       if (want_db) {
 #pragma unroll
@@ -1330,7 +1331,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_thin_tr_kernel(W2Args a) {
   }
   const unsigned qsd = (unsigned)a.qsd, qsh = (unsigned)a.qsh, qsw = (unsigned)a.qsw;
   const unsigned psd = (unsigned)a.psd, psh = (unsigned)a.psh, psw = (unsigned)a.psw;
-  const float qlo = a.tq.relu ? 0.f : -__builtin_inff(), plo = a.tp.relu ? 0.f : -__builtin_inff();
+  const float qlo = act_lo(a.tq.relu), plo = act_lo(a.tp.relu);
 
   const int sx = (int)xcd_contiguous_id(blockIdx.x, gridDim.x);
   const int qset = sx / a.S, sls = sx - qset * a.S;
@@ -1407,10 +1408,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_thin_tr_kernel(W2Args a) {
           raw[q] = make_float4(bf16_bits_to_f32(ux & 0xffffu), __uint_as_float(ux & 0xffff0000u),
                                bf16_bits_to_f32(uy & 0xffffu), __uint_as_float(uy & 0xffff0000u));
         }
-        const float v0 = fmaxf(fmaf(raw[q].x, qsc[0], qsf[0]), qlo);
-        const float v1 = a.Cs > 1 ? fmaxf(fmaf(raw[q].y, qsc[1], qsf[1]), qlo) : 0.f;
-        const float v2 = a.Cs > 2 ? fmaxf(fmaf(raw[q].z, qsc[2], qsf[2]), qlo) : 0.f;
-        const float v3 = a.Cs > 3 ? fmaxf(fmaf(raw[q].w, qsc[3], qsf[3]), qlo) : 0.f;
+        const float v0 = act_max(fmaf(raw[q].x, qsc[0], qsf[0]), qlo);
+        const float v1 = a.Cs > 1 ? act_max(fmaf(raw[q].y, qsc[1], qsf[1]), qlo) : 0.f;
+        const float v2 = a.Cs > 2 ? act_max(fmaf(raw[q].z, qsc[2], qsf[2]), qlo) : 0.f;
+        const float v3 = a.Cs > 3 ? act_max(fmaf(raw[q].w, qsc[3], qsf[3]), qlo) : 0.f;
         uint2 pk;
         pk.x = wpack2(v0, v1) & okm; pk.y = wpack2(v2, v3) & okm;
         *reinterpret_cast<uint2*>(ql + (tid + 256 * q) * 8) = pk;
@@ -1428,7 +1429,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_thin_tr_kernel(W2Args a) {
         float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          v[j] = __uint_as_float(__float_as_uint(fmaxf(fmaf(raw4[j], psc[j], psf[j]), plo)) & (j < a.Cb ? okm : 0u));
+          v[j] = __uint_as_float(__float_as_uint(act_max(fmaf(raw4[j], psc[j], psf[j]), plo)) & (j < a.Cb ? okm : 0u));
           dbs[j] += v[j];
         }
         *reinterpret_cast<uint2*>(pst) = make_uint2(wpack2(v[0], v[1]), wpack2(v[2], v[3]));
@@ -1439,7 +1440,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_thin_tr_kernel(W2Args a) {
       float v[8];
       oct8_f8(pit[p], v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = fmaxf(fmaf(v[j], psc[j], psf[j]), plo);
+      for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], psc[j], psf[j]), plo);
       const unsigned okm = ((pok >> p) & 1u) ? 0xffffffffu : 0u;
       if (want_db) {
 #pragma unroll
@@ -1945,37 +1946,10 @@ static int launch_wgrad(const WArgs& a, int S, hipStream_t s) {
   return launch_wgrad_t<TZ, TY, TX, NTW, false, false>(a, S, s);
 }
 
-}  // namespace mmtta
-
-using namespace mmtta;
-
-extern "C" int64_t mmtta_conv_wgrad_workspace_bytes_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy,
-                                                         const mmtta_param_sets* sets) {
-  WGeo w;
-  if (wgeometry(d, x, dy, sets, w)) return -1;
-  return (w.slab_floats + w.db_floats + w.pre_floats) * w.nsets * (int64_t)sizeof(float);
-}
-
-extern "C" int64_t mmtta_conv_wgrad_workspace_bytes(const mmtta_conv_desc* d, const mmtta_tensor* x,
-                                                    const mmtta_tensor* dy) {
-  return mmtta_conv_wgrad_workspace_bytes_sets(d, x, dy, nullptr);
-}
-
-extern "C" int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy) {
-  WGeo w;
-  const int st = wgeometry(d, x, dy, nullptr, w);
-  if (st) return st < 0 ? st : -st;
-  if (w.tiny) return 6;
-  if (w.small) return w.thin_tr ? 10 : 3;
-  if (w.tr1) return 9;
-  if (w.tr) return w.si == 1 ? 7 : 8;
-  if (w.ntaps == 1) return 2;
-  return w.si == 1 ? 0 : 1;
-}
-
-static int conv_wgrad_impl(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                           const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
-                           int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
+// mmtta_conv_wgrad_sets past the checks of its norm-on-load descriptor
+int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                    const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
+                    int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
   WGeo w;
   int st = wgeometry(d, x, dy, sets, w);
   if (st) return st;
@@ -2140,20 +2114,53 @@ static int conv_wgrad_impl(const mmtta_conv_desc* d, const mmtta_tensor* x, cons
   return st;
 }
 
+MMTTA_ACT_NS_CLOSE
+}  // namespace mmtta
+
+#ifndef MMTTA_ACT_LEAKY_TU
+using namespace mmtta;
+
+extern "C" int64_t mmtta_conv_wgrad_workspace_bytes_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy,
+                                                         const mmtta_param_sets* sets) {
+  WGeo w;
+  if (wgeometry(d, x, dy, sets, w)) return -1;
+  return (w.slab_floats + w.db_floats + w.pre_floats) * w.nsets * (int64_t)sizeof(float);
+}
+
+extern "C" int64_t mmtta_conv_wgrad_workspace_bytes(const mmtta_conv_desc* d, const mmtta_tensor* x,
+                                                    const mmtta_tensor* dy) {
+  return mmtta_conv_wgrad_workspace_bytes_sets(d, x, dy, nullptr);
+}
+
+extern "C" int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy) {
+  WGeo w;
+  const int st = wgeometry(d, x, dy, nullptr, w);
+  if (st) return st < 0 ? st : -st;
+  if (w.tiny) return 6;
+  if (w.small) return w.thin_tr ? 10 : 3;
+  if (w.tr1) return 9;
+  if (w.tr) return w.si == 1 ? 7 : 8;
+  if (w.ntaps == 1) return 2;
+  return w.si == 1 ? 0 : 1;
+}
+
 extern "C" int mmtta_conv_wgrad(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                 const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
-  const int pst = nl_per_item_check(x_norm, "conv_wgrad (x_norm)");
-  if (pst) return pst;
-  return conv_wgrad_impl(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, nullptr, stream);
+  return mmtta_conv_wgrad_sets(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, nullptr, stream);
 }
 
 extern "C" int mmtta_conv_wgrad_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                      const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
                                      int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
   {
-    const int pst = nl_per_item_check(x_norm, "conv_wgrad (x_norm)");
-    if (pst) return pst;
+    int st = nl_act_check(x_norm, "conv_wgrad (x_norm)");
+    if (st) return st;
+    st = nl_per_item_check(x_norm, "conv_wgrad (x_norm)");
+    if (st) return st;
   }
-  return conv_wgrad_impl(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream);
+  if (nl_leaky(x_norm))
+    return leaky::conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream);
+  return conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream);
 }
+#endif  // MMTTA_ACT_LEAKY_TU

@@ -7,6 +7,7 @@
 #include "common.h"
 
 namespace mmtta {
+MMTTA_ACT_NS_OPEN
 
 
 // ------------------------------------------------------------------ strided copy
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(256) void channel_reduce_kernel(RedArgs a) {
           } else {
             const float xhat = (xv[j] - mu[j]) * rs[j];
             float dz = dv[j];
-            if (a.t.relu && !(fmaf(g[j], xhat, b[j]) > 0.f)) dz = 0.f;
+            MMTTA_ACT_BWD(dz, a.t.relu, fmaf(g[j], xhat, b[j]));
             s0[j] += dz;
             s1[j] += dz * xhat;
           }
@@ -393,7 +394,7 @@ __global__ __launch_bounds__(256) void elementwise_kernel(EwArgs e) {
         const float bt = e.ta.beta ? e.ta.beta[ab + cc] : 0.f;
         const float xhat = (bv[j] - mu) * rs;
         float dz = av[j];
-        if (e.ta.relu && !(fmaf(g, xhat, bt) > 0.f)) dz = 0.f;
+        MMTTA_ACT_BWD(dz, e.ta.relu, fmaf(g, xhat, bt));
         ov[j] = rs * (g * dz - e.m1[n * C + cc] - xhat * e.m2[n * C + cc]);
       }
     }
@@ -411,7 +412,8 @@ struct Nb8Args {
   const float* dout; const float* y; float* o;
   long long dsn, ysn, osn;
   unsigned dsw, ysw, osw;
-  int C, relu;
+  int C;
+  act_t relu;
   unsigned dhw;
   const float* mean; const float* rstd; const float* gamma; const float* beta; const float* m1; const float* m2;
   int per_item;   // gamma / beta [N*C] (mmtta_norm_on_load.per_item)
@@ -464,7 +466,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply8_kernel(Nb8Args a) {
     for (int j = 0; j < 8; ++j) {
       const float xhat = (yv[j] - mu[j]) * rs[j];
       float dz = dv[j];
-      if (a.relu && !(fmaf(g[j], xhat, bt[j]) > 0.f)) dz = 0.f;
+      MMTTA_ACT_BWD(dz, a.relu, fmaf(g[j], xhat, bt[j]));
       ov[j] = rs[j] * (g[j] * dz - m1[j] - xhat * m2[j]);
     }
     const unsigned v = v0 + i * nvl;
@@ -481,7 +483,8 @@ struct NbsArgs {
   const float* dout; const float* y; float* o;
   long long dsn, ysn, osn;
   unsigned dsw, ysw, osw;
-  int C, relu;
+  int C;
+  act_t relu;
   unsigned dhw;
   double count;
   const float* mean; const float* rstd; const float* gamma; const float* beta;
@@ -541,7 +544,7 @@ __global__ __launch_bounds__(256) void norm_bwd_small_kernel(NbsArgs a) {
       for (int j = 0; j < 8; ++j) {
         const float xhat = (yv[j] - mu[j]) * rs[j];
         float dz = live ? dv[j] : 0.f;
-        if (a.relu && !(fmaf(g[j], xhat, bt[j]) > 0.f)) dz = 0.f;
+        MMTTA_ACT_BWD(dz, a.relu, fmaf(g[j], xhat, bt[j]));
         s0[j] += dz;
         s1[j] += dz * xhat;
       }
@@ -580,7 +583,7 @@ __global__ __launch_bounds__(256) void norm_bwd_small_kernel(NbsArgs a) {
       for (int j = 0; j < 8; ++j) {
         const float xhat = (yv[j] - mu[j]) * rs[j];
         float dz = dv[j];
-        if (a.relu && !(fmaf(g[j], xhat, bt[j]) > 0.f)) dz = 0.f;
+        MMTTA_ACT_BWD(dz, a.relu, fmaf(g[j], xhat, bt[j]));
         ov[j] = rs[j] * (g[j] * dz - m1[j] - xhat * m2[j]);
       }
       const unsigned v = vb + 64 * i;
@@ -884,8 +887,189 @@ int launch_channel_sums(const mmtta_tensor* x, float* part, hipStream_t s) {
   return launch_status("channel sums");
 }
 
+// ---- entry bodies (the C entry points below check the norm-on-load descriptors and pick the activation instantiation)
+int combine_body(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtta_tensor* b,
+                 const mmtta_norm_on_load* tb, const mmtta_tensor* out, void* stream) {
+  MMTTA_CHECK(a && out && a->ptr && out->ptr, MMTTA_ERR_INVALID, "combine: null tensor");
+  MMTTA_CHECK(same_shape(a, out) && (!b || same_shape(b, out)), MMTTA_ERR_INVALID, "combine: shape mismatch");
+  MMTTA_CHECK(is_cl(a) && is_cl(out) && (!b || is_cl(b)), MMTTA_ERR_UNSUPPORTED, "combine: channels-last only");
+  EwArgs e;
+  e.a = tv(a); e.b = b ? tv(b) : tv(a); e.o = tv(out); e.ta = nl(ta); e.tb = nl(tb); e.m1 = e.m2 = nullptr; e.hasb = b ? 1 : 0;
+  e.pa = ta && ta->per_item ? 1 : 0;
+  e.pb = b && tb && tb->per_item ? 1 : 0;
+  const bool v4 = vec4_rd(a) && vec4_wr(out) && (!b || vec4_rd(b));
+  const long long total = (long long)out->n * out->d * out->h * out->w * (v4 ? (out->c + 3) / 4 : out->c);
+  // storage: all fp32, or all bf16 (the wide forward activations of bf16 precision)
+  const bool abf = is_bf16(a), bbf = b ? is_bf16(b) : abf, obf = is_bf16(out);
+  MMTTA_CHECK((abf == bbf && bbf == obf), MMTTA_ERR_UNSUPPORTED, "combine: operands must share one storage type");
+  const dim3 grid(grid_for(total));
+  hipStream_t s = (hipStream_t)stream;
+  {
+    // octet form: C a power of two in [8, 2048], voxel-dense tensors, 16-byte aligned octets, 32-bit offsets inside an item
+    const int C = out->c;
+    const long long dhw = (long long)out->d * out->h * out->w;
+    auto dense = [](const mmtta_tensor* t) { return t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
+    const int per = abf ? 8 : 4;
+    auto al = [per](const mmtta_tensor* t) { return ((uintptr_t)t->ptr) % 16 == 0 && t->sw % per == 0 && t->sn % per == 0; };
+    const bool pow2 = C >= 8 && C <= 2048 && (C & (C - 1)) == 0;
+    const bool ok8 = v4 && pow2 && dense(a) && dense(out) && al(a) && al(out) && (!b || (dense(b) && al(b))) &&
+                     dhw * std::max(std::max(a->sw, out->sw), b ? b->sw : (int64_t)0) < (1LL << 31);
+    if (ok8) {
+      Cb8Args q;
+      q.a = (const float*)a->ptr; q.b = b ? (const float*)b->ptr : nullptr; q.o = (float*)out->ptr;
+      q.asn = a->sn; q.bsn = b ? b->sn : 0; q.osn = out->sn;
+      q.asw = (unsigned)a->sw; q.bsw = b ? (unsigned)b->sw : 0u; q.osw = (unsigned)out->sw;
+      q.C = C; q.dhw = (unsigned)dhw; q.ta = e.ta; q.tb = e.tb; q.pa = e.pa; q.pb = e.pb;
+      if (abf) { if (b) launch_combine8<true, true>(q, out->n, s); else launch_combine8<true, false>(q, out->n, s); }
+      else { if (b) launch_combine8<false, true>(q, out->n, s); else launch_combine8<false, false>(q, out->n, s); }
+      return launch_status("combine");
+    }
+  }
+  if (abf) {
+    if (v4) hipLaunchKernelGGL((elementwise_kernel<0, 4, true, true, true>), grid, dim3(256), 0, s, e);
+    else hipLaunchKernelGGL((elementwise_kernel<0, 1, true, true, true>), grid, dim3(256), 0, s, e);
+  } else {
+    if (v4) hipLaunchKernelGGL((elementwise_kernel<0, 4>), grid, dim3(256), 0, s, e);
+    else hipLaunchKernelGGL((elementwise_kernel<0, 1>), grid, dim3(256), 0, s, e);
+  }
+  return launch_status("combine");
+}
+
+int norm_bwd_reduce_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
+                         float* part, void* stream) {
+  MMTTA_CHECK(dout && y && t && part && dout->ptr && y->ptr && t->mean && t->rstd, MMTTA_ERR_INVALID, "norm bwd reduce: null argument");
+  // (a bf16-stored gradient sits next to a bf16-stored activation - or, <= 4 channels, next to an fp32-stored one: the thin
+  // full-resolution tensors keep their activations fp32, round 3)
+  MMTTA_CHECK(!is_bf16(dout) || is_bf16(y) || y->c <= 4, MMTTA_ERR_UNSUPPORTED, "norm bwd reduce: a bf16-stored gradient needs a bf16-stored activation");
+  MMTTA_CHECK(same_shape(dout, y) && is_cl(dout) && is_cl(y), MMTTA_ERR_INVALID, "norm bwd reduce: shape/layout mismatch");
+  RedArgs a;
+  a.x = tv(y); a.dout = tv(dout); a.t = nl(t); a.per_item = t->per_item != 0 ? 1 : 0; a.part = part;
+  rows_geometry(y, a.rows_per_n, a.vox_per_row);
+  const dim3 grid(y->n * a.rows_per_n);
+  hipStream_t s = (hipStream_t)stream;
+  const bool v4 = vec4_rd(y) && vec4_rd(dout);
+  if (is_bf16(dout) && !is_bf16(y)) {
+    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4, false, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((channel_reduce_kernel<1, 1, false, true>), grid, dim3(256), 0, s, a);
+  } else if (is_bf16(dout)) {
+    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4, true, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((channel_reduce_kernel<1, 1, true, true>), grid, dim3(256), 0, s, a);
+  } else if (is_bf16(y)) {
+    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((channel_reduce_kernel<1, 1, true>), grid, dim3(256), 0, s, a);
+  } else {
+    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((channel_reduce_kernel<1, 1>), grid, dim3(256), 0, s, a);
+  }
+  return launch_status("norm bwd reduce");
+}
+
+int norm_bwd_apply_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
+                        const float* m1, const float* m2, const mmtta_tensor* dy, void* stream) {
+  MMTTA_CHECK(dout && y && t && dy && m1 && m2 && t->mean && t->rstd, MMTTA_ERR_INVALID, "norm bwd apply: null argument");
+  MMTTA_CHECK(dout->dtype == dy->dtype && (!is_bf16(dout) || is_bf16(y) || y->c <= 4), MMTTA_ERR_UNSUPPORTED,
+              "norm bwd apply: `dout` and `dy` share one storage type (bf16 only next to a bf16-stored activation)");
+  const bool dbf = is_bf16(dout);
+  MMTTA_CHECK(same_shape(dout, y) && same_shape(dy, y), MMTTA_ERR_INVALID, "norm bwd apply: shape mismatch");
+  MMTTA_CHECK(is_cl(dout) && is_cl(y) && is_cl(dy), MMTTA_ERR_UNSUPPORTED, "norm bwd apply: channels-last only");
+  EwArgs e;
+  e.a = tv(dout); e.b = tv(y); e.o = tv(dy); e.ta = nl(t); e.tb = nl(nullptr); e.m1 = m1; e.m2 = m2; e.hasb = 1;
+  e.pa = t->per_item ? 1 : 0; e.pb = 0;
+  const bool v4 = vec4_rd(dout) && vec4_rd(y) && vec4_wr(dy);
+  const long long total = (long long)y->n * y->d * y->h * y->w * (v4 ? (y->c + 3) / 4 : y->c);
+  const dim3 grid(grid_for(total));
+  hipStream_t s = (hipStream_t)stream;
+  {
+    // octet form: C a power of two in [8, 2048], voxel-dense tensors, 16-byte aligned octets, 32-bit offsets inside an item
+    const int C = y->c;
+    const long long dhw = (long long)y->d * y->h * y->w;
+    auto dense = [](const mmtta_tensor* t) { return t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
+    auto al = [](const mmtta_tensor* t, int per) {
+      return ((uintptr_t)t->ptr) % 16 == 0 && t->sw % per == 0 && t->sn % per == 0;
+    };
+    const bool pow2 = C >= 8 && C <= 2048 && (C & (C - 1)) == 0;
+    const bool ok8 = v4 && pow2 && dense(dout) && dense(y) && dense(dy) && al(dout, dbf ? 8 : 4) && al(dy, dbf ? 8 : 4) &&
+                     al(y, is_bf16(y) ? 8 : 4) &&
+                     ((uintptr_t)t->mean % 16 == 0) && ((uintptr_t)t->rstd % 16 == 0) && ((uintptr_t)m1 % 16 == 0) &&
+                     ((uintptr_t)m2 % 16 == 0) && (!t->gamma || (uintptr_t)t->gamma % 16 == 0) &&
+                     (!t->beta || (uintptr_t)t->beta % 16 == 0) && dhw * std::max(std::max(dout->sw, y->sw), dy->sw) < (1LL << 31);
+    if (ok8) {
+      Nb8Args q;
+      q.dout = (const float*)dout->ptr; q.y = (const float*)y->ptr; q.o = (float*)dy->ptr;
+      q.dsn = dout->sn; q.ysn = y->sn; q.osn = dy->sn;
+      q.dsw = (unsigned)dout->sw; q.ysw = (unsigned)y->sw; q.osw = (unsigned)dy->sw;
+      q.C = C; q.relu = act_arg(t); q.dhw = (unsigned)dhw;
+      q.mean = t->mean; q.rstd = t->rstd; q.gamma = t->gamma; q.beta = t->beta; q.m1 = m1; q.m2 = m2;
+      q.per_item = t->per_item != 0 ? 1 : 0;
+      const long long nvl = 256 / (C / 8);
+      const bool four = dhw / (nvl * 4) >= 1024;
+      const long long per = nvl * (four ? 4 : 2);
+      const dim3 g8((unsigned)((dhw + per - 1) / per), (unsigned)y->n);
+      if (dbf) {
+        if (four) hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 4, true>), g8, dim3(256), 0, s, q);
+        else hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 2, true>), g8, dim3(256), 0, s, q);
+      } else if (is_bf16(y)) {
+        if (four) hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 4>), g8, dim3(256), 0, s, q);
+        else hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 2>), g8, dim3(256), 0, s, q);
+      } else {
+        if (four) hipLaunchKernelGGL((norm_bwd_apply8_kernel<false, 4>), g8, dim3(256), 0, s, q);
+        else hipLaunchKernelGGL((norm_bwd_apply8_kernel<false, 2>), g8, dim3(256), 0, s, q);
+      }
+      return launch_status("norm bwd apply");
+    }
+  }
+  if (dbf && !is_bf16(y)) {          // thin tensors: bf16-stored gradients next to an fp32-stored activation
+    if (v4) hipLaunchKernelGGL((elementwise_kernel<1, 4, true, false, true>), grid, dim3(256), 0, s, e);
+    else hipLaunchKernelGGL((elementwise_kernel<1, 1, true, false, true>), grid, dim3(256), 0, s, e);
+  } else if (dbf) {
+    if (v4) hipLaunchKernelGGL((elementwise_kernel<1, 4, true, true, true>), grid, dim3(256), 0, s, e);
+    else hipLaunchKernelGGL((elementwise_kernel<1, 1, true, true, true>), grid, dim3(256), 0, s, e);
+  } else if (is_bf16(y)) {
+    if (v4) hipLaunchKernelGGL((elementwise_kernel<1, 4, false, true, false>), grid, dim3(256), 0, s, e);
+    else hipLaunchKernelGGL((elementwise_kernel<1, 1, false, true, false>), grid, dim3(256), 0, s, e);
+  } else {
+    if (v4) hipLaunchKernelGGL((elementwise_kernel<1, 4>), grid, dim3(256), 0, s, e);
+    else hipLaunchKernelGGL((elementwise_kernel<1, 1>), grid, dim3(256), 0, s, e);
+  }
+  return launch_status("norm bwd apply");
+}
+
+// eligibility of the one-launch backward (host-only): instance statistics of a small voxel-dense tensor, channels in whole
+// groups of 32, 16-byte aligned octets
+bool nbs_ok(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t, const mmtta_tensor* dy) {
+  if (!dout || !y || !t || !dy || !t->mean || !t->rstd) return false;
+  if (dout->dtype != dy->dtype || (is_bf16(dout) && !is_bf16(y))) return false;
+  if (!same_shape(dout, y) || !same_shape(dy, y) || !is_cl(dout) || !is_cl(y) || !is_cl(dy)) return false;
+  const long long dhw = (long long)y->d * y->h * y->w;
+  auto dense = [](const mmtta_tensor* x) { return x->sh == (int64_t)x->w * x->sw && x->sd == (int64_t)x->h * x->sh; };
+  auto al = [](const mmtta_tensor* x, int per) { return ((uintptr_t)x->ptr) % 16 == 0 && x->sw % per == 0 && x->sn % per == 0; };
+  auto a16 = [](const void* p) { return p == nullptr || ((uintptr_t)p) % 16 == 0; };
+  return y->c % 32 == 0 && dhw >= 1 && dhw <= 4096 && dense(dout) && dense(y) && dense(dy) && al(dout, is_bf16(dout) ? 8 : 4) &&
+         al(dy, is_bf16(dy) ? 8 : 4) && al(y, is_bf16(y) ? 8 : 4) && a16(t->mean) && a16(t->rstd) && a16(t->gamma) && a16(t->beta);
+}
+
+int norm_bwd_small_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
+                        int64_t count, const mmtta_tensor* dy, void* stream) {
+  MMTTA_CHECK(nbs_ok(dout, y, t, dy), MMTTA_ERR_UNSUPPORTED, "norm bwd (one launch): tensors not eligible (mmtta_norm_bwd_small_ok)");
+  MMTTA_CHECK(count > 0, MMTTA_ERR_INVALID, "norm bwd (one launch): count must be positive");
+  NbsArgs q;
+  q.dout = (const float*)dout->ptr; q.y = (const float*)y->ptr; q.o = (float*)dy->ptr;
+  q.dsn = dout->sn; q.ysn = y->sn; q.osn = dy->sn;
+  q.dsw = (unsigned)dout->sw; q.ysw = (unsigned)y->sw; q.osw = (unsigned)dy->sw;
+  q.C = y->c; q.relu = act_arg(t); q.dhw = (unsigned)((long long)y->d * y->h * y->w); q.count = (double)count;
+  q.mean = t->mean; q.rstd = t->rstd; q.gamma = t->gamma; q.beta = t->beta;
+  q.per_item = t->per_item != 0 ? 1 : 0;
+  const dim3 grid((unsigned)(y->c / 32), (unsigned)y->n);
+  if (is_bf16(dout)) hipLaunchKernelGGL((norm_bwd_small_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, q);
+  else if (is_bf16(y)) hipLaunchKernelGGL(norm_bwd_small_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, q);
+  else hipLaunchKernelGGL(norm_bwd_small_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, q);
+  return launch_status("norm bwd (one launch)");
+}
+
+MMTTA_ACT_NS_CLOSE
 }  // namespace mmtta
 
+#ifndef MMTTA_ACT_LEAKY_TU
 using namespace mmtta;
 
 extern "C" int mmtta_copy_strided(const mmtta_tensor* src, const mmtta_tensor* dst, void* stream) {
@@ -995,82 +1179,6 @@ extern "C" int mmtta_norm_stats_finalize_sets(int kind, int groups, const float*
                         rstd, gamma, beta, scale, shift, gamma_items, beta_items, scratch, nsets(sets), stream);
 }
 
-extern "C" int mmtta_combine(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtta_tensor* b,
-                             const mmtta_norm_on_load* tb, const mmtta_tensor* out, void* stream) {
-  MMTTA_CHECK(a && out && a->ptr && out->ptr, MMTTA_ERR_INVALID, "combine: null tensor");
-  MMTTA_CHECK(same_shape(a, out) && (!b || same_shape(b, out)), MMTTA_ERR_INVALID, "combine: shape mismatch");
-  MMTTA_CHECK(is_cl(a) && is_cl(out) && (!b || is_cl(b)), MMTTA_ERR_UNSUPPORTED, "combine: channels-last only");
-  EwArgs e;
-  e.a = tv(a); e.b = b ? tv(b) : tv(a); e.o = tv(out); e.ta = nl(ta); e.tb = nl(tb); e.m1 = e.m2 = nullptr; e.hasb = b ? 1 : 0;
-  e.pa = ta && ta->per_item ? 1 : 0;
-  e.pb = b && tb && tb->per_item ? 1 : 0;
-  const bool v4 = vec4_rd(a) && vec4_wr(out) && (!b || vec4_rd(b));
-  const long long total = (long long)out->n * out->d * out->h * out->w * (v4 ? (out->c + 3) / 4 : out->c);
-  // storage: all fp32, or all bf16 (the wide forward activations of bf16 precision)
-  const bool abf = is_bf16(a), bbf = b ? is_bf16(b) : abf, obf = is_bf16(out);
-  MMTTA_CHECK((abf == bbf && bbf == obf), MMTTA_ERR_UNSUPPORTED, "combine: operands must share one storage type");
-  const dim3 grid(grid_for(total));
-  hipStream_t s = (hipStream_t)stream;
-  {
-    // octet form: C a power of two in [8, 2048], voxel-dense tensors, 16-byte aligned octets, 32-bit offsets inside an item
-    const int C = out->c;
-    const long long dhw = (long long)out->d * out->h * out->w;
-    auto dense = [](const mmtta_tensor* t) { return t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
-    const int per = abf ? 8 : 4;
-    auto al = [per](const mmtta_tensor* t) { return ((uintptr_t)t->ptr) % 16 == 0 && t->sw % per == 0 && t->sn % per == 0; };
-    const bool pow2 = C >= 8 && C <= 2048 && (C & (C - 1)) == 0;
-    const bool ok8 = v4 && pow2 && dense(a) && dense(out) && al(a) && al(out) && (!b || (dense(b) && al(b))) &&
-                     dhw * std::max(std::max(a->sw, out->sw), b ? b->sw : (int64_t)0) < (1LL << 31);
-    if (ok8) {
-      Cb8Args q;
-      q.a = (const float*)a->ptr; q.b = b ? (const float*)b->ptr : nullptr; q.o = (float*)out->ptr;
-      q.asn = a->sn; q.bsn = b ? b->sn : 0; q.osn = out->sn;
-      q.asw = (unsigned)a->sw; q.bsw = b ? (unsigned)b->sw : 0u; q.osw = (unsigned)out->sw;
-      q.C = C; q.dhw = (unsigned)dhw; q.ta = e.ta; q.tb = e.tb; q.pa = e.pa; q.pb = e.pb;
-      if (abf) { if (b) launch_combine8<true, true>(q, out->n, s); else launch_combine8<true, false>(q, out->n, s); }
-      else { if (b) launch_combine8<false, true>(q, out->n, s); else launch_combine8<false, false>(q, out->n, s); }
-      return launch_status("combine");
-    }
-  }
-  if (abf) {
-    if (v4) hipLaunchKernelGGL((elementwise_kernel<0, 4, true, true, true>), grid, dim3(256), 0, s, e);
-    else hipLaunchKernelGGL((elementwise_kernel<0, 1, true, true, true>), grid, dim3(256), 0, s, e);
-  } else {
-    if (v4) hipLaunchKernelGGL((elementwise_kernel<0, 4>), grid, dim3(256), 0, s, e);
-    else hipLaunchKernelGGL((elementwise_kernel<0, 1>), grid, dim3(256), 0, s, e);
-  }
-  return launch_status("combine");
-}
-
-extern "C" int mmtta_norm_bwd_reduce(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
-                                     float* part, void* stream) {
-  MMTTA_CHECK(dout && y && t && part && dout->ptr && y->ptr && t->mean && t->rstd, MMTTA_ERR_INVALID, "norm bwd reduce: null argument");
-  // (a bf16-stored gradient sits next to a bf16-stored activation - or, <= 4 channels, next to an fp32-stored one: the thin
-  // full-resolution tensors keep their activations fp32, round 3)
-  MMTTA_CHECK(!is_bf16(dout) || is_bf16(y) || y->c <= 4, MMTTA_ERR_UNSUPPORTED, "norm bwd reduce: a bf16-stored gradient needs a bf16-stored activation");
-  MMTTA_CHECK(same_shape(dout, y) && is_cl(dout) && is_cl(y), MMTTA_ERR_INVALID, "norm bwd reduce: shape/layout mismatch");
-  RedArgs a;
-  a.x = tv(y); a.dout = tv(dout); a.t = nl(t); a.per_item = t->per_item != 0 ? 1 : 0; a.part = part;
-  rows_geometry(y, a.rows_per_n, a.vox_per_row);
-  const dim3 grid(y->n * a.rows_per_n);
-  hipStream_t s = (hipStream_t)stream;
-  const bool v4 = vec4_rd(y) && vec4_rd(dout);
-  if (is_bf16(dout) && !is_bf16(y)) {
-    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4, false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((channel_reduce_kernel<1, 1, false, true>), grid, dim3(256), 0, s, a);
-  } else if (is_bf16(dout)) {
-    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4, true, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((channel_reduce_kernel<1, 1, true, true>), grid, dim3(256), 0, s, a);
-  } else if (is_bf16(y)) {
-    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((channel_reduce_kernel<1, 1, true>), grid, dim3(256), 0, s, a);
-  } else {
-    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((channel_reduce_kernel<1, 1>), grid, dim3(256), 0, s, a);
-  }
-  return launch_status("norm bwd reduce");
-}
-
 static int bwd_finalize(int kind, int groups, const float* part, int rows_per_n, int n, int c, int64_t count,
                         const float* gamma, int training, float* m1, float* m2, float* dgamma, float* dbeta, int accumulate,
                         double* scratch, NSets ns, void* stream) {
@@ -1113,88 +1221,30 @@ extern "C" int mmtta_norm_bwd_finalize_sets(int kind, int groups, const float* p
                       nsets(sets), stream);
 }
 
-extern "C" int mmtta_norm_bwd_apply(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
-                                    const float* m1, const float* m2, const mmtta_tensor* dy, void* stream) {
-  MMTTA_CHECK(dout && y && t && dy && m1 && m2 && t->mean && t->rstd, MMTTA_ERR_INVALID, "norm bwd apply: null argument");
-  MMTTA_CHECK(dout->dtype == dy->dtype && (!is_bf16(dout) || is_bf16(y) || y->c <= 4), MMTTA_ERR_UNSUPPORTED,
-              "norm bwd apply: `dout` and `dy` share one storage type (bf16 only next to a bf16-stored activation)");
-  const bool dbf = is_bf16(dout);
-  MMTTA_CHECK(same_shape(dout, y) && same_shape(dy, y), MMTTA_ERR_INVALID, "norm bwd apply: shape mismatch");
-  MMTTA_CHECK(is_cl(dout) && is_cl(y) && is_cl(dy), MMTTA_ERR_UNSUPPORTED, "norm bwd apply: channels-last only");
-  EwArgs e;
-  e.a = tv(dout); e.b = tv(y); e.o = tv(dy); e.ta = nl(t); e.tb = nl(nullptr); e.m1 = m1; e.m2 = m2; e.hasb = 1;
-  e.pa = t->per_item ? 1 : 0; e.pb = 0;
-  const bool v4 = vec4_rd(dout) && vec4_rd(y) && vec4_wr(dy);
-  const long long total = (long long)y->n * y->d * y->h * y->w * (v4 ? (y->c + 3) / 4 : y->c);
-  const dim3 grid(grid_for(total));
-  hipStream_t s = (hipStream_t)stream;
-  {
-    // octet form: C a power of two in [8, 2048], voxel-dense tensors, 16-byte aligned octets, 32-bit offsets inside an item
-    const int C = y->c;
-    const long long dhw = (long long)y->d * y->h * y->w;
-    auto dense = [](const mmtta_tensor* t) { return t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
-    auto al = [](const mmtta_tensor* t, int per) {
-      return ((uintptr_t)t->ptr) % 16 == 0 && t->sw % per == 0 && t->sn % per == 0;
-    };
-    const bool pow2 = C >= 8 && C <= 2048 && (C & (C - 1)) == 0;
-    const bool ok8 = v4 && pow2 && dense(dout) && dense(y) && dense(dy) && al(dout, dbf ? 8 : 4) && al(dy, dbf ? 8 : 4) &&
-                     al(y, is_bf16(y) ? 8 : 4) &&
-                     ((uintptr_t)t->mean % 16 == 0) && ((uintptr_t)t->rstd % 16 == 0) && ((uintptr_t)m1 % 16 == 0) &&
-                     ((uintptr_t)m2 % 16 == 0) && (!t->gamma || (uintptr_t)t->gamma % 16 == 0) &&
-                     (!t->beta || (uintptr_t)t->beta % 16 == 0) && dhw * std::max(std::max(dout->sw, y->sw), dy->sw) < (1LL << 31);
-    if (ok8) {
-      Nb8Args q;
-      q.dout = (const float*)dout->ptr; q.y = (const float*)y->ptr; q.o = (float*)dy->ptr;
-      q.dsn = dout->sn; q.ysn = y->sn; q.osn = dy->sn;
-      q.dsw = (unsigned)dout->sw; q.ysw = (unsigned)y->sw; q.osw = (unsigned)dy->sw;
-      q.C = C; q.relu = t->relu; q.dhw = (unsigned)dhw;
-      q.mean = t->mean; q.rstd = t->rstd; q.gamma = t->gamma; q.beta = t->beta; q.m1 = m1; q.m2 = m2;
-      q.per_item = t->per_item != 0 ? 1 : 0;
-      const long long nvl = 256 / (C / 8);
-      const bool four = dhw / (nvl * 4) >= 1024;
-      const long long per = nvl * (four ? 4 : 2);
-      const dim3 g8((unsigned)((dhw + per - 1) / per), (unsigned)y->n);
-      if (dbf) {
-        if (four) hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 4, true>), g8, dim3(256), 0, s, q);
-        else hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 2, true>), g8, dim3(256), 0, s, q);
-      } else if (is_bf16(y)) {
-        if (four) hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 4>), g8, dim3(256), 0, s, q);
-        else hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 2>), g8, dim3(256), 0, s, q);
-      } else {
-        if (four) hipLaunchKernelGGL((norm_bwd_apply8_kernel<false, 4>), g8, dim3(256), 0, s, q);
-        else hipLaunchKernelGGL((norm_bwd_apply8_kernel<false, 2>), g8, dim3(256), 0, s, q);
-      }
-      return launch_status("norm bwd apply");
-    }
+extern "C" int mmtta_combine(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtta_tensor* b,
+                             const mmtta_norm_on_load* tb, const mmtta_tensor* out, void* stream) {
+  int st = nl_act_check(ta, "combine (ta)");
+  if (st) return st;
+  if (b) {
+    st = nl_act_check(tb, "combine (tb)");
+    if (st) return st;
   }
-  if (dbf && !is_bf16(y)) {          // thin tensors: bf16-stored gradients next to an fp32-stored activation
-    if (v4) hipLaunchKernelGGL((elementwise_kernel<1, 4, true, false, true>), grid, dim3(256), 0, s, e);
-    else hipLaunchKernelGGL((elementwise_kernel<1, 1, true, false, true>), grid, dim3(256), 0, s, e);
-  } else if (dbf) {
-    if (v4) hipLaunchKernelGGL((elementwise_kernel<1, 4, true, true, true>), grid, dim3(256), 0, s, e);
-    else hipLaunchKernelGGL((elementwise_kernel<1, 1, true, true, true>), grid, dim3(256), 0, s, e);
-  } else if (is_bf16(y)) {
-    if (v4) hipLaunchKernelGGL((elementwise_kernel<1, 4, false, true, false>), grid, dim3(256), 0, s, e);
-    else hipLaunchKernelGGL((elementwise_kernel<1, 1, false, true, false>), grid, dim3(256), 0, s, e);
-  } else {
-    if (v4) hipLaunchKernelGGL((elementwise_kernel<1, 4>), grid, dim3(256), 0, s, e);
-    else hipLaunchKernelGGL((elementwise_kernel<1, 1>), grid, dim3(256), 0, s, e);
-  }
-  return launch_status("norm bwd apply");
+  if (nl_leaky(ta) || (b && nl_leaky(tb))) return leaky::combine_body(a, ta, b, tb, out, stream);
+  return combine_body(a, ta, b, tb, out, stream);
 }
 
-// eligibility of the one-launch backward (host-only): instance statistics of a small voxel-dense tensor, channels in whole
-// groups of 32, 16-byte aligned octets
-static bool nbs_ok(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t, const mmtta_tensor* dy) {
-  if (!dout || !y || !t || !dy || !t->mean || !t->rstd) return false;
-  if (dout->dtype != dy->dtype || (is_bf16(dout) && !is_bf16(y))) return false;
-  if (!same_shape(dout, y) || !same_shape(dy, y) || !is_cl(dout) || !is_cl(y) || !is_cl(dy)) return false;
-  const long long dhw = (long long)y->d * y->h * y->w;
-  auto dense = [](const mmtta_tensor* x) { return x->sh == (int64_t)x->w * x->sw && x->sd == (int64_t)x->h * x->sh; };
-  auto al = [](const mmtta_tensor* x, int per) { return ((uintptr_t)x->ptr) % 16 == 0 && x->sw % per == 0 && x->sn % per == 0; };
-  auto a16 = [](const void* p) { return p == nullptr || ((uintptr_t)p) % 16 == 0; };
-  return y->c % 32 == 0 && dhw >= 1 && dhw <= 4096 && dense(dout) && dense(y) && dense(dy) && al(dout, is_bf16(dout) ? 8 : 4) &&
-         al(dy, is_bf16(dy) ? 8 : 4) && al(y, is_bf16(y) ? 8 : 4) && a16(t->mean) && a16(t->rstd) && a16(t->gamma) && a16(t->beta);
+extern "C" int mmtta_norm_bwd_reduce(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
+                                     float* part, void* stream) {
+  const int st = nl_act_check(t, "norm bwd reduce");
+  if (st) return st;
+  return nl_leaky(t) ? leaky::norm_bwd_reduce_body(dout, y, t, part, stream) : norm_bwd_reduce_body(dout, y, t, part, stream);
+}
+
+extern "C" int mmtta_norm_bwd_apply(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
+                                    const float* m1, const float* m2, const mmtta_tensor* dy, void* stream) {
+  const int st = nl_act_check(t, "norm bwd apply");
+  if (st) return st;
+  return nl_leaky(t) ? leaky::norm_bwd_apply_body(dout, y, t, m1, m2, dy, stream) : norm_bwd_apply_body(dout, y, t, m1, m2, dy, stream);
 }
 
 extern "C" int mmtta_norm_bwd_small_ok(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
@@ -1204,20 +1254,9 @@ extern "C" int mmtta_norm_bwd_small_ok(const mmtta_tensor* dout, const mmtta_ten
 
 extern "C" int mmtta_norm_bwd_small(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
                                     int64_t count, const mmtta_tensor* dy, void* stream) {
-  MMTTA_CHECK(nbs_ok(dout, y, t, dy), MMTTA_ERR_UNSUPPORTED, "norm bwd (one launch): tensors not eligible (mmtta_norm_bwd_small_ok)");
-  MMTTA_CHECK(count > 0, MMTTA_ERR_INVALID, "norm bwd (one launch): count must be positive");
-  NbsArgs q;
-  q.dout = (const float*)dout->ptr; q.y = (const float*)y->ptr; q.o = (float*)dy->ptr;
-  q.dsn = dout->sn; q.ysn = y->sn; q.osn = dy->sn;
-  q.dsw = (unsigned)dout->sw; q.ysw = (unsigned)y->sw; q.osw = (unsigned)dy->sw;
-  q.C = y->c; q.relu = t->relu; q.dhw = (unsigned)((long long)y->d * y->h * y->w); q.count = (double)count;
-  q.mean = t->mean; q.rstd = t->rstd; q.gamma = t->gamma; q.beta = t->beta;
-  q.per_item = t->per_item != 0 ? 1 : 0;
-  const dim3 grid((unsigned)(y->c / 32), (unsigned)y->n);
-  if (is_bf16(dout)) hipLaunchKernelGGL((norm_bwd_small_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, q);
-  else if (is_bf16(y)) hipLaunchKernelGGL(norm_bwd_small_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, q);
-  else hipLaunchKernelGGL(norm_bwd_small_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, q);
-  return launch_status("norm bwd (one launch)");
+  const int st = nl_act_check(t, "norm bwd (one launch)");
+  if (st) return st;
+  return nl_leaky(t) ? leaky::norm_bwd_small_body(dout, y, t, count, dy, stream) : norm_bwd_small_body(dout, y, t, count, dy, stream);
 }
 
 extern "C" int mmtta_upsample2x_fwd(const mmtta_tensor* x, const mmtta_tensor* y, void* stream) {
@@ -1292,3 +1331,4 @@ extern "C" int mmtta_lincomb(int count, const mmtta_tensor* const* in, const flo
 #undef MMTTA_LINCOMB_S
   return launch_status("lincomb");
 }
+#endif  // MMTTA_ACT_LEAKY_TU

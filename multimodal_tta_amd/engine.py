@@ -164,6 +164,8 @@ class NormLayer:
         self.rt: Optional["Runtime"] = None       # set by build_norm
         self.stats_off = 0         # running_mean / running_var offsets in the runtime's statistics replicas (BatchNorm)
         self.bn_index = 0
+        self.act = ops.ACT_RELU    # MONAI ADN's "A" (set by build_norm): carried into every NL this layer returns
+        self.negative_slope = 0.0
 
     def grouped(self) -> bool:
         """True inside the launches of a volume group (``Runtime.use_sets``) for a norm with per-volume state - affines or
@@ -193,7 +195,7 @@ class NormLayer:
                                 use_batch, rm, rv, self.momentum, mean, rstd, scratch, g, b, scale, shift)
         if self.bn is not None and training and self.bn.num_batches_tracked is not None:
             self.bn.num_batches_tracked.add_(1)
-        return NL(mean, rstd, g, b, True, scale, shift)
+        return NL(mean, rstd, g, b, True, scale, shift, act=self.act, negative_slope=self.negative_slope)
 
     def _finalize_sets(self, pool: Pool, key, part, rows_per_n: int, n: int, count: int, training: bool) -> NL:
         """Batch item v = volume v of the group: its statistics (BatchNorm: over its own voxels only), its replica's affines
@@ -215,7 +217,8 @@ class NormLayer:
                                      self.momentum, mean, rstd, scratch, self._sets(), g, b, scale, shift, gi, bi)
         if self.bn is not None and training and self.bn.num_batches_tracked is not None:
             self.rt.bn_nbt_all[:n, self.bn_index].add_(1)
-        return NL(mean, rstd, gi, bi, True, scale, shift, per_item=True)
+        return NL(mean, rstd, gi, bi, True, scale, shift, per_item=True, act=self.act,
+                  negative_slope=self.negative_slope)
 
     def backward(self, pool: Pool, key, dT: torch.Tensor, y: torch.Tensor, nl: NL, dy: torch.Tensor,
                  training: bool, accumulate: bool = False) -> None:
@@ -687,7 +690,7 @@ class Runtime:
 
 # ----------------------------------------------------------------------------- container -> block builders
 def build_norm(rt: Runtime, prefix: str, adn: Optional[torch.nn.Module], channels: int) -> Optional[NormLayer]:
-    """ADN container -> NormLayer.  Dropout must be p=0 (every shipped config), activation ReLU."""
+    """ADN container -> NormLayer.  Dropout must be p=0 (every shipped config); activation ReLU, LeakyReLU or none."""
     if adn is None:
         return None
     mods = dict(adn.named_children())
@@ -697,14 +700,27 @@ def build_norm(rt: Runtime, prefix: str, adn: Optional[torch.nn.Module], channel
     nmod = mods.get("N")
     if nmod is None:
         raise NotImplementedError("an ADN without a norm layer is not supported by the fused norm-on-load path")
-    if "A" not in mods:
-        raise NotImplementedError("an ADN without an activation is not supported")
+    amod = mods.get("A")
+    if amod is None:
+        act, slope = ops.ACT_NONE, 0.0
+    elif type(amod) is torch.nn.ReLU:
+        act, slope = ops.ACT_RELU, 0.0
+    elif type(amod) is torch.nn.LeakyReLU:
+        act, slope = ops.ACT_LEAKY_RELU, float(amod.negative_slope)
+    else:
+        raise NotImplementedError(f"activation {type(amod).__name__}: the norm-on-load path fuses ReLU, LeakyReLU or none")
+    layer = _build_norm_layer(rt, prefix, nmod, channels)
+    layer.act, layer.negative_slope = act, slope
+    return _adopt_norm(rt, layer)
+
+
+def _build_norm_layer(rt: Runtime, prefix: str, nmod: torch.nn.Module, channels: int) -> NormLayer:
     if isinstance(nmod, torch.nn.InstanceNorm3d):
         if nmod.track_running_stats:
             raise NotImplementedError("InstanceNorm3d(track_running_stats=True)")
         g = rt.make_ref(prefix + ".N.weight", nmod.weight) if nmod.affine else None
         b = rt.make_ref(prefix + ".N.bias", nmod.bias) if nmod.affine else None
-        return _adopt_norm(rt, NormLayer("INSTANCE", channels, 1, nmod.eps, 0.1, g, b))
+        return NormLayer("INSTANCE", channels, 1, nmod.eps, 0.1, g, b)
     if isinstance(nmod, torch.nn.BatchNorm3d):
         if not (nmod.affine and nmod.track_running_stats):
             raise NotImplementedError("BatchNorm3d without affine / running statistics")
@@ -712,11 +728,11 @@ def build_norm(rt: Runtime, prefix: str, adn: Optional[torch.nn.Module], channel
         b = rt.make_ref(prefix + ".N.bias", nmod.bias)
         rt.buffers.append(nmod)
         mom = 0.1 if nmod.momentum is None else float(nmod.momentum)
-        return _adopt_norm(rt, NormLayer("BATCH", channels, 1, nmod.eps, mom, g, b, bn_module=nmod))
+        return NormLayer("BATCH", channels, 1, nmod.eps, mom, g, b, bn_module=nmod)
     if isinstance(nmod, torch.nn.GroupNorm):
         g = rt.make_ref(prefix + ".N.weight", nmod.weight) if nmod.affine else None
         b = rt.make_ref(prefix + ".N.bias", nmod.bias) if nmod.affine else None
-        return _adopt_norm(rt, NormLayer("GROUP", channels, nmod.num_groups, nmod.eps, 0.1, g, b))
+        return NormLayer("GROUP", channels, nmod.num_groups, nmod.eps, 0.1, g, b)
     raise NotImplementedError(f"norm module {type(nmod).__name__}")
 
 

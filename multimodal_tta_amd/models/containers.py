@@ -36,6 +36,13 @@ def parse_act(act) -> Optional[str]:
     return (act if isinstance(act, str) else str(act[0])).upper()
 
 
+def act_kwargs(act) -> dict:
+    """Keyword arguments of a MONAI activation spec: ("NAME", {...}) or ["NAME", {...}]; none for a bare name."""
+    if act is None or isinstance(act, str) or len(act) < 2 or act[1] is None:
+        return {}
+    return dict(act[1])
+
+
 class ADN(Holder):
     def __init__(self, channels: int, ordering: str, act, norm: NormSpec, dropout):
         super().__init__()
@@ -55,12 +62,16 @@ class ADN(Holder):
                 self.add_module("D", nn.Dropout(float(dropout)))
             elif item == "A" and act is not None:
                 a = parse_act(act)
-                if a != "RELU":
+                if a == "RELU":
+                    self.add_module("A", nn.ReLU())
+                elif a == "LEAKYRELU":       # MONAI's ("LEAKYRELU", {"negative_slope": k, "inplace": ...}); torch default 0.01
+                    kw = act_kwargs(act)
+                    self.add_module("A", nn.LeakyReLU(negative_slope=float(kw.get("negative_slope", 0.01))))
+                else:
                     raise NotImplementedError(
-                        f"activation {act!r}: the gfx950 kernels fuse ReLU only (every shipped config uses RELU: "
-                        "reference configs/_global_patches/brats.yaml:18)"
+                        f"activation {act!r}: the gfx950 kernels fuse RELU, LEAKYRELU or no activation (act=None) "
+                        "(every shipped config uses RELU: reference configs/_global_patches/brats.yaml:18)"
                     )
-                self.add_module("A", nn.ReLU())
 
 
 class Convolution(Holder):

@@ -363,7 +363,7 @@ class DeepFusionRuntime(Runtime):
             ops.lincomb([shared], [1.0], mem(catf, m)[..., :c[-1]])
         y, nl = self.fusion.fwd(catf, None)                               # shared weights: one set per volume, M items each
         fused = pool.cl("fused", n * M, *bd, c[-1], dtype=act(c[-1]))
-        ops.combine(y, nl, catf[..., :c[-1]], None, fused)                # shared + relu(norm(conv(cat[shared, feat_m])))
+        ops.combine(y, nl, catf[..., :c[-1]], None, fused)                # shared + act(norm(conv(cat[shared, feat_m])))
         bcat = pool.cl("bcat", n, *bd, M * c[-1], dtype=act(M * c[-1]))
         for m in range(M):
             src = mem(fused, m) if m in keep else shared                  # an absent branch feeds the shared mean

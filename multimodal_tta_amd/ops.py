@@ -184,10 +184,14 @@ def tune_for_volumes_in_flight(volumes: int) -> Dict[int, int]:
     return vals
 
 
+ACT_NONE, ACT_RELU, ACT_LEAKY_RELU = _lib.ACT_NONE, _lib.ACT_RELU, _lib.ACT_LEAKY_RELU
+
+
 # ----------------------------------------------------------------------------- norm on load
 @dataclass
 class NL:
-    """Pending normalisation(+ReLU) of a raw conv output; consumers apply it when they read."""
+    """Pending normalisation(+activation) of a raw conv output; consumers apply it when they read.  The activation is
+    `act` (ACT_NONE / ACT_RELU / ACT_LEAKY_RELU with `negative_slope`) or, when `act` is None, ReLU if `relu`."""
     mean: torch.Tensor
     rstd: torch.Tensor
     gamma: Optional[torch.Tensor] = None
@@ -196,10 +200,12 @@ class NL:
     scale: Optional[torch.Tensor] = None     # precombined rstd*gamma and beta - mean*rstd*gamma (fast consumer path)
     shift: Optional[torch.Tensor] = None
     per_item: bool = False                   # gamma / beta are [N*C], one copy per batch item (norm_stats_finalize_sets)
+    act: Optional[int] = None                # ACT_* code; None: ACT_RELU if relu else ACT_NONE
+    negative_slope: float = 0.0              # ACT_LEAKY_RELU: v > 0 ? v : negative_slope * v
 
     def struct(self) -> _lib.NormOnLoad:
         return _lib.norm_on_load(self.mean, self.rstd, self.gamma, self.beta, self.relu, self.scale, self.shift,
-                                 self.per_item)
+                                 self.per_item, self.act, self.negative_slope)
 
 
 def _nl_ref(nl: Optional[NL]):
