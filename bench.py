@@ -11,7 +11,12 @@ BraTS-shaped 4x128^3 fp32 volume, S=10 entropy-minimisation steps of the registe
 the mask/Dice tail.  Inputs are resident in HBM before the timed region.  Ranks adapt their own
 volumes (weak scaling); the only collective is the all_gather of the per-volume Dice table.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+Prints ONE JSON line (rank 0): the driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step),
+post_tta_dice, config, repeatability and
+  ranks        - per-rank volumes/s (min / max over ranks) and the time of the gather.
+A plain run does only that: it sets up, warms up, times the steps, writes --dump-outputs and prints.  With --full (off by
+default; each part can be dropped with its --no-* switch) rank 0 then measures and checks beyond the headline, on the
+same lanes and volumes, and adds to the line:
   roofline     - the dominant conv kernel (by measured time; events on the launch stream).  bf16 mode is HBM-bound
                  (model AI ~ 109 flop/B < ridge ~ 310): `achieved` = that kernel's ALGORITHMIC
                  bytes per launch (input + weight image + output, each once) / its measured launch duration against
@@ -19,11 +24,12 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
                  `mfma` carries the same kernel's FLOP/s against the dense MFMA peak of its operand type and
                  `whole_volume` the algorithmic bytes and FLOPs of a whole adapted volume over its wall time.
                  fp32 mode (--precision fp32) is MFMA-bound: the two blocks swap places.
-  cpu_baseline - the oracle (torch CPU restatement of the reference path) timed on this host on a
+                 (config.algorithmic_conv_tflop_per_volume comes from the same pass.)
+  cpu_baseline - (1 GPU) the oracle (torch CPU restatement of the reference path) timed on this host on a
                  bounded sample of the same workload.
   parity_full_size - the GPU path against that same CPU step on volume 0 (loss, logits, masks, Dice).
-  variants     - (1 GPU) the same workload with one volume in flight, and in fp32 mode (the reference's arithmetic).
-  ranks        - per-rank volumes/s (min / max over ranks) and the time of the gather.
+  variants     - (1 GPU) the same workload with one volume in flight, and in fp32 mode (the reference's arithmetic),
+                 and `lanes_equal`: the grouped, multi-lane timed volumes give the same Dice counts one at a time.
 """
 from __future__ import annotations
 
@@ -53,7 +59,7 @@ def mfma_peak(kernel_name: str) -> float:
     return PEAK_BF16_MFMA_TFLOPS if bf else PEAK_FP32_MFMA_TFLOPS
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=48, help="timed adapted volumes per rank (default: two rounds of 3 lanes x 8)")
@@ -82,9 +88,13 @@ def parse():
                     help="bf16 precision: storage of the wide activation GRADIENTS (default: the method config, bf16)")
     ap.add_argument("--storage", default=None, choices=["bf16", "fp32"],
                     help="bf16 precision: storage of the wide forward activations (default: the method config, bf16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile-pass", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the one-lane and fp32-mode runs of the same workload")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the roofline profile pass, the variants (one volume / one lane / fp32 "
+                         "mode, lanes_equal) and, on one GPU, the CPU baseline with its full-size parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity check")
+    ap.add_argument("--no-profile-pass", action="store_true", help="--full without the roofline profile pass")
+    ap.add_argument("--no-variants", action="store_true",
+                    help="--full without the one-lane and fp32-mode runs of the same workload")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--from-host", action="store_true",
                     help="measurement aid, never the headline: the volumes start in pinned HOST memory and every group's "
@@ -93,7 +103,7 @@ def parse():
                     help="after the timed steps, write what the last of them computed (rank 0: the last timed volume's final "
                          "logits, per-step losses, mask counts, Dice and IoU) as DIR/<name>.npy, for output-by-output "
                          "comparison of two builds (the inputs and weights are seeded; bench_outputs/ is git-ignored)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def build_cfg(args):
@@ -404,7 +414,7 @@ def main():
     assert table.shape == (args.steps * world, table_width(R))
     post_dice = post_dice_from_table(table, R)
     if rank == 0 and args.dump_outputs:
-        # before anything else runs on the lanes' buffers (the profile pass and the variants reuse them)
+        # before anything else runs on the lanes' buffers (the profile pass and the variants of --full reuse them)
         plug_last, res_last, idx_last = last
         dump_outputs(args.dump_outputs, plug_last, res_last, len(idx_last) - 1, counts[idx_last[-1] % nvol])
 
@@ -441,11 +451,11 @@ def main():
                   "gather_ms": 1000.0 * t_gather},
     }
 
-    if rank == 0 and not args.no_profile_pass:
+    if args.full and rank == 0 and not args.no_profile_pass:
         first_group = schedule(args.warmup, nvol, group)[0][1]
         out["roofline"] = roofline_block(args, cfg, plug, group_tensors(first_group)[0], elapsed / args.steps)
         out["config"]["algorithmic_conv_tflop_per_volume"] = out["roofline"]["whole_volume"]["algorithmic_tflop"]
-    if rank == 0 and world == 1 and not args.no_variants:
+    if args.full and rank == 0 and world == 1 and not args.no_variants:
         # the same workload (a) one volume at a time (one lane, group 1: the single-volume latency - and the check that the
         # grouped, multi-lane headline run produced the SAME results for the same volumes), (b) in fp32 mode: the reference's
         # own arithmetic
@@ -480,7 +490,7 @@ def main():
                 variants[name]["latency_ms"] = 1000.0 * tv / nv
             del pl2, st2
         out["variants"] = variants
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.method == "tta_entmin":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.method == "tta_entmin":
         out["cpu_baseline"], ref = cpu_baseline(cfg, shape, args.tta_steps)
         out["parity_full_size"] = parity_full_size(cfg, ref, device, args.precision)
     if rank == 0:

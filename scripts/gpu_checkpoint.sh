@@ -5,10 +5,10 @@ TAG=${1:-ckpt}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 if [ "$2" != "notests" ]; then
   python -m pytest tests -m gpu -x -q > $O/tests.log 2>&1; echo "rc=$?" >> $O/tests.log; tail -3 $O/tests.log
 fi
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 # the headline arrangement (lanes x group volumes per round) needs a whole round of volumes: 24 warm-up + 24 dry-run + 24 timed
-rocprofv3 --kernel-trace --stats --output-format rocpd csv -d $O/prof -o run -- python3 $R/bench.py --steps 24 --warmup 24 --no-cpu-baseline --no-variants > $O/bench_traced.json 2> $O/trace.err
+rocprofv3 --kernel-trace --stats --output-format rocpd csv -d $O/prof -o run -- python3 $R/bench.py --steps 24 --warmup 24 --full --no-cpu-baseline --no-variants > $O/bench_traced.json 2> $O/trace.err
 cd $R
 python scripts/trace_summary.py $O/prof/run_results.db > $O/kernels.md 2>> $O/trace.err
 python scripts/trace_summary.py $O/prof/run_results.db --json > $O/trace_avg_us.json 2>> $O/trace.err

@@ -7,7 +7,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smok
 tail -1 $out/smoke.log
 run() {   # name, bench arguments...
   local name=$1; shift
-  timeout -k 10 500 python bench.py "$@" --no-variants > $out/bench_$name.json 2> $out/bench_$name.err || { tail -20 $out/bench_$name.err; exit 1; }
+  timeout -k 10 500 python bench.py "$@" --full --no-variants > $out/bench_$name.json 2> $out/bench_$name.err || { tail -20 $out/bench_$name.err; exit 1; }
   python -c "import json;d=json.load(open('$out/bench_$name.json'));r=d['roofline'];print('$name', round(d['value'],2), 'vol/s', round(d['ms_per_step'],2), 'ms;', r['kernel'], 'frac', round(r['frac'],3), '| whole volume', {k: round(v,3) for k,v in r['whole_volume'].items() if k.startswith('frac') or k.startswith('eff')})"
 }
 # (whole rounds of lanes x group volumes: a partial round runs smaller groups)

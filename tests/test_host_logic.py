@@ -295,3 +295,13 @@ def test_workspace_selectors_are_per_thread():
         assert (ops.Workspace.lane, ops.Workspace.slot, ops.Workspace.frozen) == (3, 1, False)
     finally:
         ops.Workspace.lane, ops.Workspace.slot = 0, 0
+
+
+def test_bench_extras_are_opt_in():
+    """`bench.py` without `--full` runs the headline alone; the roofline pass, the variants and the CPU baseline are opt-in,
+    and their --no-* switches still drop parts of a --full run."""
+    import bench
+    plain = bench.parse(["--gpus", "1", "--steps", "4", "--warmup", "2"])
+    assert not plain.full and (plain.steps, plain.warmup) == (4, 2)
+    full = bench.parse(["--full", "--no-cpu-baseline"])
+    assert full.full and full.no_cpu_baseline and not full.no_variants and not full.no_profile_pass
