@@ -461,6 +461,21 @@ int64_t mmtta_entropy_partials_items(const mmtta_tensor* logits);
 int mmtta_entropy_loss_items(const mmtta_tensor* logits, int softmax, const mmtta_tensor* dlogits,
                              double* partial, float* loss, void* stream);
 
+/* SAR's reliable-entropy objective (Niu et al., ICLR 2023) for N INDEPENDENT volumes: only the elements whose entropy lies
+ * below `margin` enter the loss (elements: (voxel, region) for softmax == 0, voxel for softmax != 0; H as above).
+ *   keep_out[n][voxel][c]  uint8, dense channels-last (c < R for softmax == 0, one byte per voxel otherwise):
+ *                          H < margin, ANDed with keep_in when keep_in != NULL (SAR's second pass: keep1 & (H2 < margin))
+ *   loss[n]   = sum_{keep} H / |keep| of item n (NaN when nothing is kept);  kept[n] = |keep| (int64)
+ *   dlogits   = keep * dH/dz / |keep| (zero when nothing is kept); the scale is read on the device (capturable).
+ * Three launches: a pass that writes the mask and fp64 block partials, a per-item finish, a gradient pass that reads the
+ * logits and the mask again.  Storages as mmtta_entropy_loss_items (bf16 thin gradients included); with every element kept
+ * the gradient is bitwise that of mmtta_entropy_loss_items.  `margin` must be finite and positive; keep_out may be keep_in.
+ *   partial  fp64 [mmtta_entropy_filtered_partials(logits)] scratch */
+int64_t mmtta_entropy_filtered_partials(const mmtta_tensor* logits);
+int mmtta_entropy_filtered_items(const mmtta_tensor* logits, int softmax, float margin, const uint8_t* keep_in,
+                                 uint8_t* keep_out, const mmtta_tensor* dlogits, double* partial, float* loss,
+                                 int64_t* kept, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of
@@ -496,6 +511,18 @@ int mmtta_optim_step(const mmtta_optim_desc* desc, float* p, const float* g, flo
  * step counter, advanced once.  set_stride a multiple of 4. */
 int mmtta_optim_step_sets(const mmtta_optim_desc* desc, float* p, const float* g, float* m, float* v, int64_t n,
                           int64_t n_decay, int sets, int64_t set_stride, int32_t* step, void* stream);
+
+/* The ascent of a sharpness-aware step (SAM, as SAR uses it) over the first `sets` of `replicas` arena replicas
+ * ([replica][set_stride]): per replica r, over [0, n),
+ *   saved = p;  p += g * (rho / (||g||_2 + 1e-12))
+ * with ||g||_2 from a deterministic two-stage fp64 sum of g^2 and fp32 scale / product / sum as torch computes them.
+ * Replica r of `saved` starts at r * saved_stride (saved_stride >= n: [sets][n] holds only what the ascent rewrites).
+ * Restoring the weights is a plain copy of `saved` back.  n, set_stride and saved_stride multiples of 4, n <= set_stride,
+ * 1 <= sets <= replicas, rho finite and >= 0, buffers 16-byte aligned.
+ *   partial  fp64 [mmtta_sam_ascent_partials(n, sets)] scratch */
+int64_t mmtta_sam_ascent_partials(int64_t n, int sets);
+int mmtta_sam_ascent_sets(float* p, const float* g, float* saved, int64_t saved_stride, double* partial, int64_t n, int sets,
+                          int replicas, int64_t set_stride, float rho, void* stream);
 
 /* ------------------------------------------------------------------ evaluation tail ------ */
 /* sigmoid -> (>= threshold) -> uint8 mask; GT (> 0.5); per (n,r) integer counts

@@ -143,12 +143,18 @@ _SIGNATURES = {
     "mmtta_entropy_loss": (C.c_int, [_P(Tensor), C.c_int, _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_entropy_partials_items": (C.c_int64, [_P(Tensor)]),
     "mmtta_entropy_loss_items": (C.c_int, [_P(Tensor), C.c_int, _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_entropy_filtered_partials": (C.c_int64, [_P(Tensor)]),
+    "mmtta_entropy_filtered_items": (C.c_int, [_P(Tensor), C.c_int, C.c_float, C.c_void_p, C.c_void_p, _P(Tensor), C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mmtta_optim_step": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                    C.c_void_p, C.c_void_p]),
     "mmtta_optim_step_sets": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                         C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mmtta_sam_ascent_partials": (C.c_int64, [C.c_int64, C.c_int]),
+    "mmtta_sam_ascent_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                        C.c_int64, C.c_float, C.c_void_p]),
     "mmtta_mask_dice_counts": (C.c_int, [_P(Tensor), _P(Tensor), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_dice_ce_scratch_bytes": (C.c_int64, [_P(Tensor)]),
     "mmtta_dice_ce_sums": (C.c_int, [_P(Tensor), _P(Tensor), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -426,6 +426,220 @@ __global__ __launch_bounds__(256) void dice_ce_grad_kernel(DceGradArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ filtered entropy (SAR's reliable-entropy loss)
+// Per independent item (gridDim.y), the same launch geometry as entropy_launch(per_item).  Pass 1 computes H per element with
+// the per-logit arithmetic of the three kernels above, writes keep = H < margin (ANDed with an incoming mask) as one byte per
+// element (dense channels-last: (voxel, region) for the Bernoulli heads, voxel for the categorical one) and leaves fp64 block
+// partials of the kept sum of H and of the kept count: partial[item][0][block], partial[item][1][block].  The finish kernel
+// writes loss[item] and kept[item]; pass 2 writes dlogits = keep * dH/dz / kept[item], the scale read on the device.  With
+// every element kept the block partials, the loss arithmetic and the gradient scale are those of mmtta_entropy_loss_items.
+__device__ __forceinline__ void fent_store_partials(double acc, int cnt, double* partial, double* sh) {
+  const double s = block_sum_d(acc, sh);
+  __syncthreads();
+  const double c = block_sum_d((double)cnt, sh);
+  if (threadIdx.x == 0) {
+    double* p = partial + (long long)blockIdx.y * 2 * gridDim.x;
+    p[blockIdx.x] = s;
+    p[gridDim.x + blockIdx.x] = c;
+  }
+}
+
+__device__ __forceinline__ float fent_scale(const long long* kept) {
+  const long long k = kept[blockIdx.y];
+  return k > 0 ? (float)(1.0 / (double)k) : 0.f;
+}
+
+__global__ __launch_bounds__(256) void fent_bernoulli_kernel(TV z, TV dz, float margin, const unsigned char* kin,
+                                                             unsigned char* kout, double* partial, const long long* kept) {
+  __shared__ double sh[4];
+  const int C = z.c;
+  const long long total = (long long)z.d * z.h * z.w * C;
+  z.p += (long long)blockIdx.y * z.sn;
+  kout += (long long)blockIdx.y * total;
+  if (kin) kin += (long long)blockIdx.y * total;
+  const bool grad = kept != nullptr;      // pass 2: kout is the mask pass 1 wrote
+  if (grad) dz.p += (long long)blockIdx.y * dz.sn;
+  const float scale = grad ? fent_scale(kept) : 0.f;
+  double acc = 0.0;
+  int cnt = 0;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    long long v = i / C;
+    const int x = (int)(v % z.w); v /= z.w;
+    const int y = (int)(v % z.h); v /= z.h;
+    const int zz = (int)v;
+    const float t = z.p[zz * z.sd + y * z.sh + x * z.sw + c];
+    const float e = expf(-fabsf(t));
+    const float sig = t >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    if (grad) {
+      dz.p[zz * dz.sd + y * dz.sh + x * dz.sw + c] = kout[i] ? -t * sig * (1.f - sig) * scale : 0.f;
+      continue;
+    }
+    const float softplus = fmaxf(t, 0.f) + log1pf(e);
+    const float h = softplus - t * sig;
+    const bool keep = h < margin && (kin == nullptr || kin[i] != 0);
+    kout[i] = keep ? 1 : 0;
+    if (keep) { acc += (double)h; ++cnt; }
+  }
+  if (!grad) fent_store_partials(acc, cnt, partial, sh);
+}
+
+template <bool OBF>
+__global__ __launch_bounds__(256) void fent_bernoulli_vec_kernel(TV z, TV dz, float margin, const unsigned char* kin,
+                                                                 unsigned char* kout, double* partial, const long long* kept) {
+  __shared__ double sh[4];
+  const int C = z.c;
+  const long long total = (long long)z.d * z.h * z.w;
+  z.p += (long long)blockIdx.y * z.sn;
+  kout += (long long)blockIdx.y * total * C;
+  if (kin) kin += (long long)blockIdx.y * total * C;
+  const bool grad = kept != nullptr;
+  if (grad)
+    dz.p = OBF ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(dz.p) + (long long)blockIdx.y * dz.sn)
+               : dz.p + (long long)blockIdx.y * dz.sn;
+  const float scale = grad ? fent_scale(kept) : 0.f;
+  double acc = 0.0;
+  int cnt = 0;
+  for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < total;
+       v += (long long)gridDim.x * blockDim.x) {
+    const float4 t4 = *reinterpret_cast<const float4*>(z.p + v * 4);
+    const float ts[4] = {t4.x, t4.y, t4.z, t4.w};
+    float g[4] = {0.f, 0.f, 0.f, 0.f};
+    float h = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (c < C) {
+        float hc, gc;
+        bernoulli_entropy_terms(ts[c], hc, gc);
+        if (grad) {
+          g[c] = kout[v * C + c] ? gc * scale : 0.f;
+        } else {
+          const bool keep = hc < margin && (kin == nullptr || kin[v * C + c] != 0);
+          kout[v * C + c] = keep ? 1 : 0;
+          if (keep) { h += hc; ++cnt; }
+        }
+      }
+    }
+    if (grad) st4_any(dz.p, v * 4, make_float4(g[0], g[1], g[2], g[3]), OBF);
+    else acc += (double)h;
+  }
+  if (!grad) fent_store_partials(acc, cnt, partial, sh);
+}
+
+__global__ __launch_bounds__(256) void fent_categorical_kernel(TV z, TV dz, float margin, const unsigned char* kin,
+                                                               unsigned char* kout, double* partial, const long long* kept) {
+  __shared__ double sh[4];
+  const int R = z.c;
+  const long long total = (long long)z.d * z.h * z.w;
+  z.p += (long long)blockIdx.y * z.sn;
+  kout += (long long)blockIdx.y * total;
+  if (kin) kin += (long long)blockIdx.y * total;
+  const bool grad = kept != nullptr;
+  if (grad) dz.p += (long long)blockIdx.y * dz.sn;
+  const float scale = grad ? fent_scale(kept) : 0.f;
+  double acc = 0.0;
+  int cnt = 0;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    long long v = i;
+    const int x = (int)(v % z.w); v /= z.w;
+    const int y = (int)(v % z.h); v /= z.h;
+    const int zz = (int)v;
+    const float* zp = z.p + zz * z.sd + y * z.sh + x * z.sw;
+    float t[ENT_MAX_R];
+    float m = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < ENT_MAX_R; ++r)
+      if (r < R) { t[r] = zp[r]; m = fmaxf(m, t[r]); }
+    float se = 0.f;
+#pragma unroll
+    for (int r = 0; r < ENT_MAX_R; ++r)
+      if (r < R) se += expf(t[r] - m);
+    const float lse = m + logf(se);
+    float pz = 0.f;
+#pragma unroll
+    for (int r = 0; r < ENT_MAX_R; ++r)
+      if (r < R) pz += expf(t[r] - lse) * t[r];
+    const float H = lse - pz;
+    if (grad) {
+      float* gp = dz.p + zz * dz.sd + y * dz.sh + x * dz.sw;
+      const bool keep = kout[i] != 0;
+#pragma unroll
+      for (int r = 0; r < ENT_MAX_R; ++r)
+        if (r < R) {
+          const float logp = t[r] - lse;
+          gp[r] = keep ? -expf(logp) * (logp + H) * scale : 0.f;
+        }
+      continue;
+    }
+    const bool keep = H < margin && (kin == nullptr || kin[i] != 0);
+    kout[i] = keep ? 1 : 0;
+    if (keep) { acc += (double)H; ++cnt; }
+  }
+  if (!grad) fent_store_partials(acc, cnt, partial, sh);
+}
+
+__global__ __launch_bounds__(64) void fent_finish_kernel(const double* partial, int nblocks, float* loss, long long* kept) {
+  partial += (long long)blockIdx.x * 2 * nblocks;
+  double s = 0.0, c = 0.0;
+  for (int i = threadIdx.x; i < nblocks; i += 64) { s += partial[i]; c += partial[nblocks + i]; }
+  s = wave_sum_d(s);
+  c = wave_sum_d(c);
+  if (threadIdx.x == 0) {
+    kept[blockIdx.x] = (long long)c;
+    loss[blockIdx.x] = c > 0.0 ? (float)(s * (1.0 / c)) : __builtin_nanf("");
+  }
+}
+
+// ------------------------------------------------------------------ SAM ascent over arena replicas
+// eps = rho * g / (||g||_2 + 1e-12) over [0, n) of each of the first `sets` replicas; w_saved = w, w += eps.  Stage 1: fp64
+// block partials of g^2 per replica [set][SAM_BLOCKS]; stage 2: every workgroup sums its replica's partials in the same
+// fixed order (deterministic, identical in every workgroup), then rewrites its slice.  The scale and the update are fp32 with
+// separate roundings, as torch's p.add_(p.grad * scale) computes them.
+constexpr int SAM_BLOCKS = 256;
+
+__global__ __launch_bounds__(256) void sam_sumsq_kernel(const float* __restrict__ g, long long n, long long stride,
+                                                        double* partial) {
+  __shared__ double sh[4];
+  g += (long long)blockIdx.y * stride;
+  const long long n4 = n >> 2;
+  double acc = 0.0;
+  for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < n4; q += (long long)gridDim.x * blockDim.x) {
+    const float4 v = *reinterpret_cast<const float4*>(g + (q << 2));
+    acc += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+  }
+  const double t = block_sum_d(acc, sh);
+  if (threadIdx.x == 0) partial[(long long)blockIdx.y * gridDim.x + blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(256) void sam_ascent_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                         float* __restrict__ saved, long long n, long long stride,
+                                                         long long saved_stride, const double* partial, int nblocks,
+                                                         float rho) {
+  __shared__ float s_scale;
+  const long long o = (long long)blockIdx.y * stride;
+  p += o; g += o; saved += (long long)blockIdx.y * saved_stride;
+  if (threadIdx.x < 64) {
+    const double* pp = partial + (long long)blockIdx.y * nblocks;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 64) s += pp[i];
+    s = wave_sum_d(s);
+    if (threadIdx.x == 0) s_scale = rho / ((float)sqrt(s) + 1e-12f);
+  }
+  __syncthreads();
+  const float scale = s_scale;
+  const long long n4 = n >> 2;
+  for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < n4; q += (long long)gridDim.x * blockDim.x) {
+    const long long i = q << 2;
+    const float4 w = *reinterpret_cast<const float4*>(p + i);
+    const float4 gq = *reinterpret_cast<const float4*>(g + i);
+    *reinterpret_cast<float4*>(saved + i) = w;
+    *reinterpret_cast<float4*>(p + i) = make_float4(__fadd_rn(w.x, __fmul_rn(gq.x, scale)), __fadd_rn(w.y, __fmul_rn(gq.y, scale)),
+                                                    __fadd_rn(w.z, __fmul_rn(gq.z, scale)), __fadd_rn(w.w, __fmul_rn(gq.w, scale)));
+  }
+}
+
 }  // namespace mmtta
 
 using namespace mmtta;
@@ -625,4 +839,111 @@ extern "C" int mmtta_dice_ce_grad(const mmtta_tensor* logits, const mmtta_tensor
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(dice_ce_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   return launch_status("dice_ce grad");
+}
+
+extern "C" int64_t mmtta_entropy_filtered_partials(const mmtta_tensor* logits) {
+  if (logits == nullptr) return -1;
+  mmtta_tensor one = *logits;
+  one.n = 1;
+  return 2 * (int64_t)entropy_blocks(&one) * logits->n;
+}
+
+extern "C" int mmtta_entropy_filtered_items(const mmtta_tensor* logits, int softmax, float margin, const uint8_t* keep_in,
+                                            uint8_t* keep_out, const mmtta_tensor* dlogits, double* partial, float* loss,
+                                            int64_t* kept, void* stream) {
+  MMTTA_CHECK(__builtin_isfinite(margin) && margin > 0.f, MMTTA_ERR_INVALID,
+              "entropy filtered: margin must be finite and positive, got %g", (double)margin);
+  MMTTA_CHECK(keep_out != nullptr, MMTTA_ERR_INVALID, "entropy filtered: null mask output");
+  MMTTA_CHECK(logits && dlogits && partial && loss && kept && logits->ptr && dlogits->ptr, MMTTA_ERR_INVALID,
+              "entropy filtered: null argument");
+  MMTTA_CHECK(logits->n == dlogits->n && logits->c == dlogits->c && logits->d == dlogits->d && logits->h == dlogits->h &&
+                  logits->w == dlogits->w && logits->n >= 1 && logits->c >= 1,
+              MMTTA_ERR_INVALID, "entropy filtered: shape mismatch");
+  MMTTA_CHECK(logits->dtype == MMTTA_F32, MMTTA_ERR_UNSUPPORTED, "entropy filtered: `logits` must be fp32-stored");
+  MMTTA_CHECK(is_cl(logits) && is_cl(dlogits), MMTTA_ERR_UNSUPPORTED, "entropy filtered: channels-last only");
+  hipStream_t s = (hipStream_t)stream;
+  mmtta_tensor one = *logits;
+  one.n = 1;
+  const int items = logits->n;
+  const int blocks = entropy_blocks(&one);
+  const dim3 grid(blocks, items);
+  const long long* kd = (const long long*)kept;
+  if (!softmax) {
+    auto dense16 = [](const mmtta_tensor* t) {
+      return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
+             ((uintptr_t)t->ptr) % 16 == 0;
+    };
+    const bool vec = logits->c <= 4 && dense16(logits) && dense16(dlogits) && ((dlogits->flags & MMTTA_TENSOR_OWNS_PAD) || dlogits->c == 4);
+    MMTTA_CHECK(is_f32(dlogits) || vec, MMTTA_ERR_UNSUPPORTED,
+                "entropy filtered: a bf16-stored `dlogits` needs dense 4-channel voxel rows that own their pad");
+    auto run = [&](const unsigned char* kin, unsigned char* kout, double* part, const long long* kk) {
+      if (vec && is_bf16(dlogits))
+        hipLaunchKernelGGL(fent_bernoulli_vec_kernel<true>, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin, kin, kout, part, kk);
+      else if (vec)
+        hipLaunchKernelGGL(fent_bernoulli_vec_kernel<false>, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin, kin, kout, part, kk);
+      else
+        hipLaunchKernelGGL(fent_bernoulli_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin, kin, kout, part, kk);
+    };
+    run(keep_in, keep_out, partial, nullptr);
+    int st = launch_status("entropy filtered bernoulli");
+    if (st) return st;
+    hipLaunchKernelGGL(fent_finish_kernel, dim3(items), dim3(64), 0, s, partial, blocks, loss, (long long*)kept);
+    st = launch_status("entropy filtered finish");
+    if (st) return st;
+    run(nullptr, keep_out, nullptr, kd);
+    return launch_status("entropy filtered bernoulli gradient");
+  }
+  MMTTA_CHECK(logits->c <= ENT_MAX_R, MMTTA_ERR_UNSUPPORTED, "entropy filtered softmax: more than %d classes", ENT_MAX_R);
+  MMTTA_CHECK(is_f32(dlogits), MMTTA_ERR_UNSUPPORTED, "entropy filtered softmax: `dlogits` must be fp32-stored");
+  hipLaunchKernelGGL(fent_categorical_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin, keep_in, keep_out, partial,
+                     (const long long*)nullptr);
+  int st = launch_status("entropy filtered categorical");
+  if (st) return st;
+  hipLaunchKernelGGL(fent_finish_kernel, dim3(items), dim3(64), 0, s, partial, blocks, loss, (long long*)kept);
+  st = launch_status("entropy filtered finish");
+  if (st) return st;
+  hipLaunchKernelGGL(fent_categorical_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin,
+                     (const unsigned char*)nullptr, keep_out, (double*)nullptr, kd);
+  return launch_status("entropy filtered categorical gradient");
+}
+
+static long long sam_blocks(int64_t n) {
+  long long b = ((n + 3) / 4 + 255) / 256;
+  if (b < 1) b = 1;
+  if (b > SAM_BLOCKS) b = SAM_BLOCKS;
+  return b;
+}
+
+extern "C" int64_t mmtta_sam_ascent_partials(int64_t n, int sets) {
+  if (n < 0 || sets < 1) return -1;
+  return sam_blocks(n) * sets;
+}
+
+extern "C" int mmtta_sam_ascent_sets(float* p, const float* g, float* saved, int64_t saved_stride, double* partial, int64_t n,
+                                     int sets, int replicas, int64_t set_stride, float rho, void* stream) {
+  MMTTA_CHECK(__builtin_isfinite(rho) && rho >= 0.f, MMTTA_ERR_INVALID, "sam ascent: rho must be finite and >= 0, got %g",
+              (double)rho);
+  MMTTA_CHECK(p && g && saved && partial, MMTTA_ERR_INVALID, "sam ascent: null argument");
+  MMTTA_CHECK(n >= 0 && n % 4 == 0 && set_stride >= 0 && set_stride % 4 == 0, MMTTA_ERR_INVALID,
+              "sam ascent: n = %lld and set_stride = %lld must be multiples of 4", (long long)n, (long long)set_stride);
+  MMTTA_CHECK(saved_stride >= n && saved_stride % 4 == 0, MMTTA_ERR_INVALID,
+              "sam ascent: saved_stride = %lld must be a multiple of 4 and at least n = %lld", (long long)saved_stride,
+              (long long)n);
+  MMTTA_CHECK(sets >= 1 && sets <= replicas && n <= set_stride, MMTTA_ERR_INVALID,
+              "sam ascent: %d sets of %lld elements do not fit %d replicas of stride %lld", sets, (long long)n, replicas,
+              (long long)set_stride);
+  MMTTA_CHECK(((uintptr_t)p | (uintptr_t)g | (uintptr_t)saved) % 16 == 0, MMTTA_ERR_INVALID,
+              "sam ascent: buffers must be 16-byte aligned");
+  if (n == 0) return MMTTA_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const long long nb = sam_blocks(n);
+  hipLaunchKernelGGL(sam_sumsq_kernel, dim3((unsigned)nb, (unsigned)sets), dim3(256), 0, s, g, (long long)n, (long long)set_stride,
+                     partial);
+  int st = launch_status("sam sum of squares");
+  if (st) return st;
+  long long ub = ((n + 3) / 4 + 255) / 256;
+  if (ub > 4096) ub = 4096;
+  hipLaunchKernelGGL(sam_ascent_kernel, dim3((unsigned)ub, (unsigned)sets), dim3(256), 0, s, p, g, saved, (long long)n,
+                     (long long)set_stride, (long long)saved_stride, (const double*)partial, (int)nb, rho);
+  return launch_status("sam ascent");
 }

@@ -723,6 +723,52 @@ def entropy_loss_items(logits: torch.Tensor, dlogits: torch.Tensor, partial: tor
                                                stream_ptr()), "entropy_loss_items")
 
 
+def entropy_filtered_partials(logits: torch.Tensor) -> int:
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_entropy_filtered_partials(C.byref(t)))
+
+
+def entropy_filtered_items(logits: torch.Tensor, dlogits: torch.Tensor, margin: float, keep_in: Optional[torch.Tensor],
+                           keep_out: torch.Tensor, partial: torch.Tensor, loss: torch.Tensor, kept: torch.Tensor,
+                           softmax: bool = False) -> None:
+    """SAR's reliable-entropy objective of every batch item on its own: elements with H < margin (and keep_in) enter the
+    loss.  keep_in / keep_out: uint8, one byte per element (N*D*H*W*R, or N*D*H*W for softmax heads); loss fp32 [N], kept
+    int64 [N]; dlogits = keep * dH/dz / kept."""
+    n, d, h, w, r = logits.shape
+    elems = n * d * h * w * (1 if softmax else r)
+    for name, t in (("keep_in", keep_in), ("keep_out", keep_out)):
+        if t is not None and (t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() < elems):
+            raise MmttaError(f"entropy_filtered_items: {name} must be contiguous uint8 of at least {elems} elements")
+    if loss.numel() < n or kept.numel() < n or kept.dtype != torch.int64:
+        raise MmttaError("entropy_filtered_items: one loss slot and one int64 count per batch item")
+    if partial.dtype != torch.float64 or partial.numel() < entropy_filtered_partials(logits):
+        raise MmttaError("entropy_filtered_items: partial must be fp64 of entropy_filtered_partials(logits) elements")
+    tz, tg = desc_cl(logits), desc_cl(dlogits)
+    check(_lib.load().mmtta_entropy_filtered_items(C.byref(tz), 1 if softmax else 0, float(margin), ptr(keep_in), ptr(keep_out),
+                                                   C.byref(tg), ptr(partial), ptr(loss), ptr(kept), stream_ptr()),
+          "entropy_filtered_items")
+
+
+def sam_ascent_partials(n: int, sets: int) -> int:
+    return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
+
+
+def sam_ascent_sets(p: torch.Tensor, g: torch.Tensor, saved: torch.Tensor, partial: torch.Tensor, n: int, sets: int,
+                    rho: float) -> None:
+    """SAM's ascent over the first ``sets`` replicas of the arena ([replicas, total]; the first ``n`` elements of a replica
+    train): saved[r, :n] = p[r, :n], p += rho * g / (||g|| + 1e-12), the norm per replica.  ``saved``: [>= sets, >= n]."""
+    for t in (p, g):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape != p.shape:
+            raise MmttaError("sam_ascent_sets: p and g must be contiguous fp32 [replicas, total] of equal shape")
+    if saved.dtype != torch.float32 or not saved.is_contiguous() or saved.dim() != 2 or saved.shape[0] < sets \
+            or saved.shape[1] < n:
+        raise MmttaError(f"sam_ascent_sets: saved must be contiguous fp32 [>= {sets}, >= {n}], got {tuple(saved.shape)}")
+    if partial.dtype != torch.float64 or partial.numel() < sam_ascent_partials(n, sets):
+        raise MmttaError("sam_ascent_sets: partial must be fp64 of sam_ascent_partials(n, sets) elements")
+    check(_lib.load().mmtta_sam_ascent_sets(ptr(p), ptr(g), ptr(saved), int(saved.shape[1]), ptr(partial), int(n), int(sets),
+                                            int(p.shape[0]), int(p.shape[1]), float(rho), stream_ptr()), "sam_ascent_sets")
+
+
 def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n_decay: int, lr: float,
               beta1: float, beta2: float, eps: float, weight_decay: float, step: torch.Tensor) -> None:
     n = p.numel()

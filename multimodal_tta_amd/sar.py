@@ -1,0 +1,127 @@
+"""``sar_tta``: SAR (Niu et al., ICLR 2023, "Towards Stable Test-Time Adaptation in Dynamic Wild World") on the
+native engine, next to ``entmin_tta`` (Tent).
+
+Per volume and step (each volume of a group on its own weight replica):
+
+    z1 = f(x; w);  keep1 = H(z1) < m;  L1 = mean of H over keep1;  g1 = dL1/dw
+    w_saved = w;  w += rho * g1 / (||g1|| + 1e-12)          (the norm over every trainable parameter of the replica)
+    z2 = f(x; w);  keep2 = keep1 & (H(z2) < m);  L2 = mean of H over keep2;  g2 = dL2/dw
+    w = w_saved;  base-optimizer step with g2
+
+with m = e_margin * ln K (K = 2 for the sigmoid head's Bernoulli elements (voxel, region), K = R for the softmax head's
+voxels).  An empty filter gives L = NaN and a zero gradient, as torch's mean over an empty selection does.  Where this
+differs from the classification paper: the elements are voxels (or voxel x region pairs), not images; the margin is a
+fraction of ln K so that one default serves both heads; SAR's model-recovery reset is not built (it targets continual runs,
+this package resets every volume).
+
+Everything else - episodic reset, groups, lanes, the captured step, the final forward - is ``entmin_tta``'s.
+"""
+from __future__ import annotations
+
+import math
+from typing import Any, Dict, Optional, Sequence
+
+import torch
+
+from . import ops
+from .config import as_cfg, get_config
+from .registry import register_plugin
+from .tta import EntropyMinimizationTTA, select_params
+
+
+@register_plugin("sar_tta")
+class SharpnessAwareReliableTTA(EntropyMinimizationTTA):
+    """``method.sar.e_margin`` (fraction of ln K, default 0.4) and ``method.sar.rho`` (SAM radius, default 0.05), the SAR
+    paper's defaults; the base optimizer is ``training.optimizer`` exactly as for ``entmin_tta``."""
+
+    def __init__(self, config: Any = None):
+        super().__init__(config)
+        s = get_config(get_config(as_cfg(config), "method", {}) or {}, "sar", {}) or {}
+        self.e_margin = float(get_config(s, "e_margin", 0.4))
+        self.rho = float(get_config(s, "rho", 0.05))
+        if not (math.isfinite(self.e_margin) and self.e_margin > 0.0):
+            raise ValueError(f"method.sar.e_margin = {self.e_margin}: expected a finite positive fraction of ln K")
+        if not (math.isfinite(self.rho) and self.rho >= 0.0):
+            raise ValueError(f"method.sar.rho = {self.rho}: expected a finite radius >= 0")
+        self._kept_hist: Optional[torch.Tensor] = None
+        self._t = 0
+
+    def setup(self, model, device) -> "SharpnessAwareReliableTTA":
+        if not select_params(model, self.params_spec):
+            # torch SAR has no gradient to take the ascent along either
+            raise ValueError(f"sar_tta: method.params = {self.params_spec!r} selects no trainable parameter")
+        return super().setup(model, device)
+
+    def margin(self, regions: int) -> float:
+        """The entropy margin in nats: e_margin * ln K."""
+        return self.e_margin * math.log(float(regions) if self.softmax else 2.0)
+
+    # ------------------------------------------------------------------ one step
+    def _step_launches(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+        rt, ar = self.rt, self.rt.arena
+        ops.Workspace.lane = self.lane
+        rt.training = True
+        rt.use_sets = rt.group > 1          # batch item g reads / writes parameter replica g
+        try:
+            def forward() -> torch.Tensor:
+                return rt.forward_cl(x_cl) if present is None else rt.forward_cl(x_cl, present=present)
+
+            rt.pack_all()
+            logits = forward()
+            n, d, h, w, r = logits.shape
+            gdt = rt.thin_grad_dtype() if (not self.softmax and r <= 4) else torch.float32
+            dlogits = rt.pool.cl("dlogits", n, d, h, w, r, ldc=(r + 3) // 4 * 4, dtype=gdt)
+            slots = rt.group if rt.group > 1 else 1
+            elems = n * d * h * w * (1 if self.softmax else r)
+            margin = self.margin(r)
+            partial = rt.pool.flat("sar_partial", ops.entropy_filtered_partials(logits), dtype=torch.float64)
+            loss1 = rt.pool.flat("ent_loss", slots)          # adapt_volume records L1 from here
+            loss2 = rt.pool.flat("sar_loss2", slots)
+            kept1 = rt.pool.flat("sar_kept", slots, dtype=torch.int64)
+            kept2 = rt.pool.flat("sar_kept2", slots, dtype=torch.int64)
+            keep1 = rt.pool.flat("sar_keep1", elems, dtype=torch.uint8)
+            keep2 = rt.pool.flat("sar_keep2", elems, dtype=torch.uint8)
+            ops.entropy_filtered_items(logits, dlogits, margin, None, keep1, partial, loss1, kept1, softmax=self.softmax)
+            rt.run_backward(dlogits)
+            # ascent: w_saved = w, w += rho g1 / ||g1|| per replica in use; the packed images follow the arena
+            sets = min(n, ar.replicas)
+            saved = rt.pool.flat("sar_saved", ar.replicas * ar.n_train).view(ar.replicas, ar.n_train)
+            sam_partial = rt.pool.flat("sar_sam_partial", ops.sam_ascent_partials(ar.n_train, sets), dtype=torch.float64)
+            ops.sam_ascent_sets(ar.params_all, ar.grads_all, saved, sam_partial, ar.n_train, sets, self.rho)
+            rt.pack_all()
+            logits = forward()
+            ops.entropy_filtered_items(logits, dlogits, margin, keep1, keep2, partial, loss2, kept2, softmax=self.softmax)
+            rt.run_backward(dlogits)
+            # exact restore (SAR's SAM copies old_p back), then the base optimizer with the gradient taken at w + eps
+            ar.params_all[:sets, :ar.n_train].copy_(saved[:sets])
+            self.optimizer_step(n)
+        finally:
+            rt.use_sets = False
+
+    def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+        super()._step(x_cl, present)
+        if self._kept_hist is not None:
+            B = int(x_cl.shape[0])
+            self._kept_hist[self._t].copy_(self.rt.pool.flat("sar_kept", self.rt.group if self.rt.group > 1 else 1,
+                                                             dtype=torch.int64)[:B])
+            self._t += 1
+
+    # ------------------------------------------------------------------ per volume
+    @torch.no_grad()
+    def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
+        """As ``entmin_tta.adapt_volume``; ``losses`` holds L1 per step, ``kept`` the number of elements that passed the
+        first filter per step ([steps], or [steps, B] for a group of B > 1 volumes)."""
+        if self.rt is None:
+            return super().adapt_volume(x, steps)          # raises
+        steps = self.steps if steps is None else int(steps)
+        B = int(x.shape[0])
+        grouped = self.rt.group > 1
+        hist = self.rt.pool.flat("sar_kept_hist", max(steps, 1) * B, dtype=torch.int64).view(max(steps, 1), B)
+        self._kept_hist, self._t = hist, 0
+        try:
+            out = super().adapt_volume(x, steps)
+        finally:
+            self._kept_hist = None
+        kept = hist[:steps]
+        out["kept"] = kept[:, 0] if (not grouped or B == 1) else kept
+        return out

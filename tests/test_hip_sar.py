@@ -1,0 +1,610 @@
+"""SAR adaptation (``sar_tta``) on the GPU: the filtered entropy and the SAM ascent against float64 torch restatements, the
+plugin against a SAR restatement with torch autograd on the oracle networks, and the bitwise properties (keep-all = Tent,
+grouped = one volume at a time, graph replay = eager).
+
+Inputs of the kernel tests are seeded so that no element's entropy lies within 1e-5 of the margin (the rule DESIGN.md
+section 6 applies to the ReLU threshold): the keep masks must then agree exactly."""
+import copy
+import math
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from test_hip_tta import SMALL, build_pair, root_cfg, volume
+
+pytestmark = pytest.mark.gpu
+
+
+# ----------------------------------------------------------------------------- float64 restatements
+def entropy_elements(z: torch.Tensor, softmax: bool) -> torch.Tensor:
+    """H per element of logits [N,R,D,H,W]: [N,R,D,H,W] (Bernoulli) or [N,D,H,W] (categorical)."""
+    if softmax:
+        logp = F.log_softmax(z, dim=1)
+        return -(logp.exp() * logp).sum(1)
+    return F.softplus(z) - z * torch.sigmoid(z)
+
+
+def filtered_reference(z: torch.Tensor, margin: float, softmax: bool, keep_in=None):
+    """Per item: loss, kept count, keep mask (channels-last element order) and d(loss)/dz in float64."""
+    z = z.double().detach().requires_grad_(True)
+    H = entropy_elements(z, softmax)
+    keep = H < margin
+    if keep_in is not None:
+        keep = keep & keep_in
+    losses, kept = [], []
+    total = 0.0
+    for n in range(z.shape[0]):
+        k = keep[n]
+        c = int(k.sum())
+        kept.append(c)
+        if c:
+            ln = H[n][k].sum() / c
+            total = total + ln
+            losses.append(float(ln))
+        else:
+            losses.append(float("nan"))
+    if torch.is_tensor(total):
+        total.backward()
+        grad = z.grad
+    else:
+        grad = torch.zeros_like(z)
+    return losses, kept, keep, grad
+
+
+def away_from_margin(z: torch.Tensor, margin: float, softmax: bool, gen) -> torch.Tensor:
+    """Resample the logits of the elements whose entropy lies within 1e-5 of the margin."""
+    for _ in range(20):
+        H = entropy_elements(z.double(), softmax)
+        near = (H - margin).abs() < 1e-5
+        if not near.any():
+            return z
+        if softmax:
+            near = near.unsqueeze(1).expand_as(z)
+        z = torch.where(near, torch.randn(z.shape, generator=gen) * 3.0, z)
+    raise AssertionError("could not seed the logits away from the margin")
+
+
+def keep_cl(keep: torch.Tensor, softmax: bool) -> torch.Tensor:
+    """A [N,R,D,H,W] / [N,D,H,W] mask in the kernels' element order (dense channels-last), flat uint8."""
+    k = keep if softmax else keep.permute(0, 2, 3, 4, 1)
+    return k.contiguous().reshape(-1).to(torch.uint8)
+
+
+def stage(z: torch.Tensor, generic: bool) -> torch.Tensor:
+    """Logits [N,R,D,H,W] -> a channels-last device view: 16-byte voxel rows (the Bernoulli fast path for R <= 4) or an
+    odd row pitch (the generic kernel)."""
+    from multimodal_tta_amd import ops
+    n, r, d, h, w = z.shape
+    ldc = (r + 3) // 4 * 4 if not generic else (r if r % 4 else r + 1)
+    return ops.to_cl(z.cuda(), ldc=ldc)
+
+
+def grad_buffer(z_cl: torch.Tensor, dtype) -> torch.Tensor:
+    from multimodal_tta_amd import ops
+    n, d, h, w, r = z_cl.shape
+    ldc = z_cl.stride(3)
+    g = ops.new_cl(n, d, h, w, r, "cuda", ldc=ldc if dtype == torch.float32 else 4, dtype=dtype)
+    (g if g._base is None else g._base).fill_(float("nan"))
+    return g
+
+
+def run_filtered(z_cl, margin, softmax, keep_in=None, dtype=torch.float32):
+    from multimodal_tta_amd import ops
+    n, d, h, w, r = z_cl.shape
+    elems = n * d * h * w * (1 if softmax else r)
+    g = grad_buffer(z_cl, dtype)
+    keep = torch.full((elems,), 7, dtype=torch.uint8, device="cuda")
+    partial = torch.empty(ops.entropy_filtered_partials(z_cl), dtype=torch.float64, device="cuda")
+    loss = torch.full((n,), 123.0, device="cuda")
+    kept = torch.full((n,), -1, dtype=torch.int64, device="cuda")
+    ops.entropy_filtered_items(z_cl, g, margin, None if keep_in is None else keep_in.cuda(), keep, partial, loss, kept,
+                               softmax=softmax)
+    torch.cuda.synchronize()
+    return loss.cpu(), kept.cpu(), keep.cpu(), ops.from_cl(g.float()).cpu()
+
+
+HEADS = [(False, 1, False), (False, 3, False), (False, 4, False), (False, 3, True), (False, 4, True), (False, 1, True),
+         (True, 3, False), (True, 5, False)]
+
+
+@pytest.mark.parametrize("softmax,R,generic", HEADS)
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("with_mask", [False, True])
+def test_filtered_entropy_matches_float64(softmax, R, generic, N, with_mask):
+    gen = torch.Generator().manual_seed(100 + 7 * R + N)
+    margin = 0.5 * math.log(R if softmax else 2.0)
+    z = away_from_margin(torch.randn((N, R, 6, 7, 9), generator=gen) * 3.0, margin, softmax, gen)
+    keep_in = None
+    if with_mask:
+        shape = (N, 6, 7, 9) if softmax else (N, R, 6, 7, 9)
+        keep_in = torch.rand(shape, generator=gen) < 0.7
+    l_ref, k_ref, m_ref, g_ref = filtered_reference(z, margin, softmax, keep_in)
+    z_cl = stage(z, generic)
+    for dtype in ((torch.float32, torch.bfloat16) if (not softmax and not generic) else (torch.float32,)):
+        loss, kept, keep, g = run_filtered(z_cl, margin, softmax, None if keep_in is None else keep_cl(keep_in, softmax),
+                                           dtype=dtype)
+        assert torch.equal(keep, keep_cl(m_ref, softmax)), "keep masks differ"
+        assert kept.tolist() == k_ref
+        for a, b in zip(loss.tolist(), l_ref):
+            assert abs(a - b) <= 1e-5 * abs(b), (a, b)
+        want = g_ref.float() if dtype == torch.float32 else g_ref.float().to(torch.bfloat16).float()
+        tol = 2e-5 * g_ref.abs().max().item() + (0.0 if dtype == torch.float32 else 1e-2 * want.abs().max().item())
+        assert (g.double() - want.double()).abs().max().item() <= tol
+        assert torch.all(g[~(m_ref.unsqueeze(1).expand_as(g) if softmax else m_ref)] == 0)
+
+
+# bf16 gradients exist for the Bernoulli fast path only
+KEEP_ALL = [h + (torch.float32,) for h in HEADS] + [h + (torch.bfloat16,) for h in HEADS if not h[0] and not h[2]]
+
+
+@pytest.mark.parametrize("softmax,R,generic,dtype", KEEP_ALL)
+def test_keep_all_is_bitwise_the_entropy_objective(softmax, R, generic, dtype):
+    from multimodal_tta_amd import ops
+    gen = torch.Generator().manual_seed(11 + R)
+    N = 3
+    z = torch.randn((N, R, 5, 6, 7), generator=gen) * 3.0
+    z_cl = stage(z, generic)
+    loss, kept, keep, g = run_filtered(z_cl, 2.0 * math.log(R if softmax else 2.0), softmax, dtype=dtype)
+    g0 = grad_buffer(z_cl, dtype)
+    partial = torch.empty(ops.entropy_partials_items(z_cl), dtype=torch.float64, device="cuda")
+    loss0 = torch.empty(N, device="cuda")
+    ops.entropy_loss_items(z_cl, g0, partial, loss0, softmax=softmax)
+    torch.cuda.synchronize()
+    assert torch.equal(g, ops.from_cl(g0.float()).cpu()), "dlogits differ from mmtta_entropy_loss_items"
+    assert torch.all(keep == 1) and kept.tolist() == [5 * 6 * 7 * (1 if softmax else R)] * N
+    assert ((loss - loss0.cpu()).abs() <= 1e-6 * loss0.cpu().abs()).all()
+
+
+@pytest.mark.parametrize("softmax,R,generic", [(False, 3, False), (False, 3, True), (True, 4, False)])
+def test_n_items_equal_n_single_item_calls(softmax, R, generic):
+    gen = torch.Generator().manual_seed(5)
+    N = 3
+    margin = 0.6 * math.log(R if softmax else 2.0)
+    z = torch.randn((N, R, 9, 8, 7), generator=gen) * 3.0
+    together = run_filtered(stage(z, generic), margin, softmax)
+    for n in range(N):
+        one = run_filtered(stage(z[n:n + 1], generic), margin, softmax)
+        per = z[0:1].numel() // R * (1 if softmax else R)
+        assert torch.equal(one[0], together[0][n:n + 1]) and torch.equal(one[1], together[1][n:n + 1])
+        assert torch.equal(one[2], together[2][n * per:(n + 1) * per])
+        assert torch.equal(one[3], together[3][n:n + 1])
+
+
+@pytest.mark.parametrize("softmax", [False, True])
+def test_empty_filter_gives_nan_loss_and_zero_gradient(softmax):
+    gen = torch.Generator().manual_seed(9)
+    z = torch.randn((2, 3, 4, 5, 6), generator=gen) * 3.0
+    loss, kept, keep, g = run_filtered(stage(z, False), 1e-30, softmax)
+    assert torch.isnan(loss).all() and kept.tolist() == [0, 0]
+    assert torch.all(keep == 0) and torch.all(g == 0)
+
+
+def test_sam_ascent_matches_torch():
+    from multimodal_tta_amd import ops
+    gen = torch.Generator().manual_seed(3)
+    replicas, stride, n, sets = 3, 1032, 1000, 2
+    p0 = torch.randn((replicas, stride), generator=gen)
+    g = torch.randn((replicas, stride), generator=gen) * torch.tensor([1.0, 1e-3, 5.0]).view(3, 1)
+    for rho in (0.05, 0.0):
+        p = p0.clone().cuda()
+        saved = torch.full((replicas, n), float("nan"), device="cuda")          # only [0, n) of a replica is saved
+        partial = torch.empty(ops.sam_ascent_partials(n, sets), dtype=torch.float64, device="cuda")
+        ops.sam_ascent_sets(p, g.cuda(), saved, partial, n, sets, rho)
+        torch.cuda.synchronize()
+        p, saved = p.cpu(), saved.cpu()
+        assert torch.equal(saved[:sets], p0[:sets, :n]), "w_saved is not the input"
+        assert torch.equal(p[sets:], p0[sets:]), "a replica at or above `sets` moved"
+        assert torch.equal(p[:, n:], p0[:, n:]), "elements past n moved"
+        assert torch.isnan(saved[sets:]).all()
+        if rho == 0.0:
+            assert torch.equal(p, p0)
+            continue
+        for r in range(sets):
+            gr = g[r, :n]
+            scale = rho / (gr.norm(p=2) + 1e-12)          # torch SAR's first_step, fp32
+            want = p0[r, :n] + gr * scale
+            assert ((p[r, :n] - want).abs() <= 1e-6 * want.abs() + 1e-7).all()
+
+
+# ----------------------------------------------------------------------------- the plugin against a SAR restatement
+def sar_reference(model, x, train_cfg, steps, e_margin, rho, params="all", softmax=False):
+    """SAR (Niu et al. 2023, the reference algorithm with SAM's exact restore) with torch autograd, one volume."""
+    import oracle
+    from oracle.tta import select_params
+    named = select_params(model, params)
+    chosen = {id(p) for _, p in named}
+    for p in model.parameters():
+        p.requires_grad_(id(p) in chosen)
+    opt = oracle.adam.build_optimizer(named, train_cfg)
+    plist = [p for _, p in named]
+    losses, kept = [], []
+    model.train()
+    for _ in range(steps):
+        opt.zero_grad()
+        z = model(x)
+        margin = e_margin * math.log(z.shape[1] if softmax else 2.0)
+        H = entropy_elements(z, softmax)
+        keep1 = H < margin
+        l1 = H[keep1].mean()
+        l1.backward()
+        losses.append(float(l1))
+        kept.append(int(keep1.sum()))
+        with torch.no_grad():
+            norm = torch.norm(torch.stack([p.grad.norm(p=2) for p in plist if p.grad is not None]), p=2)
+            scale = rho / (norm + 1e-12)
+            old = [p.detach().clone() for p in plist]
+            for p in plist:
+                if p.grad is not None:
+                    p.add_(p.grad * scale.to(p))
+        opt.zero_grad()
+        H2 = entropy_elements(model(x), softmax)
+        keep2 = keep1 & (H2 < margin)
+        H2[keep2].mean().backward()
+        with torch.no_grad():
+            for p, o in zip(plist, old):
+                p.copy_(o)
+        opt.step()
+    model.eval()
+    with torch.no_grad():
+        logits = model(x)
+    for p in model.parameters():
+        p.requires_grad_(True)
+    return {"logits": logits, "losses": losses, "kept": kept}
+
+
+def sar_cfg(model_cfg, steps=3, lr=1e-3, e_margin=0.8, rho=0.05, **method):
+    """``lr=None``: the configured learning rate (the reference's)."""
+    from multimodal_tta_amd.config import compose
+    cfg = root_cfg(model_cfg, steps=steps, lr=1e-3 if lr is None else lr, **method)
+    if lr is None:
+        cfg["training"]["optimizers"]["adam"]["lr"] = compose(overrides=["task=brats", "model=unet"])["training"]["optimizers"]["adam"]["lr"]
+    cfg["method"]["name"] = "sar_tta"
+    cfg["method"]["sar"] = {"e_margin": e_margin, "rho": rho}
+    return cfg
+
+
+def check_against_reference(z_hip, res, out_ref, ref0, x, y, cfg, e_margin, rho, params="all", softmax=False, bf16=False,
+                            elements=None):
+    """fp32, at the reference's learning rate: per-step L1 within 1e-4 relative and kept counts within 1e-4 of the element
+    count of a float64 run of the restatement (or 3x as far as the fp32 restatement sits from it); final logits within
+    5e-3 of max|logits| (or 3x the fp32 restatement's distance), mask voxels differing only where the float64 logit is
+    within that bound of the threshold, Dice 2e-3.  The logit bound is wider than
+    Tent's 2e-3: the filtered gradient comes from a tenth of the elements, so a single ReLU input that two fp32 evaluations
+    put on different sides of zero weighs ten times more, and Adam's sign-like first steps pass that
+    on (measured 3.5e-3 on the small U-Net; one SAR step on its own matches torch to fp32 rounding).  At lr = 1e-3 the
+    filtered trajectory is chaotic for torch itself (fp32 vs float64: 8.5e-2 of max|logits| after 3 steps), so it is not
+    compared there.  bf16, at the reference's learning rate: L1 1e-2 relative, kept 1e-2 of the element count, logits 3e-2 of
+    max|logits|, masks 1e-2, Dice 2e-2 against the fp32 restatement (Tent's bf16 bounds)."""
+    import oracle
+    steps = len(out_ref["losses"])
+    losses, kept = res["losses"].cpu().reshape(-1).tolist(), res["kept"].cpu().reshape(-1).tolist()
+
+    def masks(z):
+        if softmax:
+            return F.one_hot(z.argmax(1), z.shape[1]).permute(0, 4, 1, 2, 3)
+        return torch.sigmoid(z) >= 0.5
+
+    def dice(m):
+        return oracle.binary_dice_iou(m.to(torch.uint8), (y > 0.5).to(torch.uint8))[0]
+
+    z_ref = out_ref["logits"]
+    if bf16:
+        for t, (a, b) in enumerate(zip(losses, out_ref["losses"])):
+            assert (math.isnan(a) and math.isnan(b)) or abs(a - b) <= 1e-2 * abs(b), f"step {t}: L1 {a} vs reference {b}"
+        for t, (a, b) in enumerate(zip(kept, out_ref["kept"])):
+            assert abs(a - b) <= 1e-2 * elements, f"step {t}: kept {a} vs reference {b}"
+        err = (z_hip - z_ref).abs().max().item() / z_ref.abs().max().item()
+        mism = (masks(z_hip) != masks(z_ref)).float().mean().item()
+        ddice = (dice(masks(z_hip)) - dice(masks(z_ref))).abs().max().item()
+        print(f"bf16: L1 {losses} kept {kept}; logits {err:.2e}, masks {mism:.2e}, Dice {ddice:.2e}")
+        assert err > 1e-6, "bf16 path not taken"
+        assert err <= 3e-2 and mism <= 1e-2 and ddice <= 2e-2, (err, mism, ddice)
+        return
+    o64 = sar_reference(copy.deepcopy(ref0).double(), x.double(), cfg["training"], steps, e_margin, rho, params=params,
+                        softmax=softmax)
+    for t in range(steps):
+        a, b, c = losses[t], out_ref["losses"][t], o64["losses"][t]
+        if math.isnan(c):
+            assert math.isnan(a), f"step {t}: L1 {a}, the reference kept nothing"
+            continue
+        assert abs(a - c) <= max(1e-4 * abs(c) + 1e-6, 3.0 * abs(b - c)), f"step {t}: L1 {a}, fp32 {b}, fp64 {c}"
+        a, b, c = kept[t], out_ref["kept"][t], o64["kept"][t]
+        assert abs(a - c) <= max(1e-4 * elements, 3.0 * abs(b - c)), f"step {t}: kept {a}, fp32 {b}, fp64 {c}"
+    z64 = o64["logits"]
+    scale = z64.abs().max().item()
+    e_ref = (z_ref.double() - z64).abs().max().item() / scale
+    e_hip = (z_hip.double() - z64).abs().max().item() / scale
+    assert e_hip <= max(5e-3, 3.0 * e_ref), f"HIP vs fp64 SAR {e_hip:.3e}; fp32 SAR vs fp64 SAR {e_ref:.3e}"
+    m_hip, m_ref, m64 = masks(z_hip), masks(z_ref), masks(z64)
+    mism_hip = (m_hip != m64).float().mean().item()
+    if not softmax:
+        # a voxel may differ only where the float64 logit lies within the logit bound of the threshold (logit 0)
+        near = z64.abs() <= max(5e-3, 3.0 * e_ref) * scale
+        assert not torch.any((m_hip != m64) & ~near), "a mask voxel differs away from the threshold"
+    d64 = dice(m64)
+    dd_hip, dd_ref = (dice(m_hip) - d64).abs().max().item(), (dice(m_ref) - d64).abs().max().item()
+    assert dd_hip <= max(2e-3, 3.0 * dd_ref), (dd_hip, dd_ref)
+    print(f"L1 {losses} kept {kept}; logits {e_hip:.2e} (fp32 {e_ref:.2e}), masks {mism_hip:.2e}, Dice {dd_hip:.2e}")
+
+
+BATCH = dict(SMALL, norm="BATCH")
+# running statistics after 2 x S updates: measured up to 1.6e-5 from the restatement in the grouped run (the filtered
+# trajectories carry the single-ReLU-flip differences described in check_against_reference), so 5e-5
+RUNNING_TOL = 5e-5
+
+
+def bn_twins(plug, hip, ref):
+    """The oracle's BatchNorm modules in the order of the runtime's running-statistics list (matched by module name)."""
+    names = {id(m): n for n, m in hip.named_modules()}
+    return [ref.get_submodule(names[id(mod)]) for mod in plug.rt.buffers]
+
+
+@pytest.mark.parametrize("model_cfg,e_margin,lr", [(SMALL, 0.8, None), (SMALL, 0.4, None), (BATCH, 0.8, None)])
+def test_sar_matches_the_restatement(model_cfg, e_margin, lr):
+    from multimodal_tta_amd.registry import get_plugin
+    cfg = sar_cfg(model_cfg, steps=3, lr=lr, e_margin=e_margin, rho=0.05, group=1)
+    ref, hip = build_pair(model_cfg)
+    ref0 = copy.deepcopy(ref)
+    x, y = volume(0)
+    out_ref = sar_reference(ref, x, cfg["training"], 3, e_margin, 0.05)
+    plug = get_plugin("sar_tta")(cfg).setup(hip, "cuda")
+    res = plug.adapt_volume(x.cuda())
+    assert res["losses"].shape == (3,) and res["kept"].shape == (3,)
+    check_against_reference(plug.logits(res).cpu(), res, out_ref, ref0, x, y, cfg, e_margin, 0.05, elements=x[0, :3].numel())
+    if model_cfg is BATCH:          # running statistics after 2 x S forwards
+        for (rm, rv, nb), mod in zip(plug.rt.replica_buffers(0), bn_twins(plug, hip, ref)):
+            print("running statistics", (rm.cpu() - mod.running_mean).abs().max().item(),
+                  (rv.cpu() - mod.running_var).abs().max().item())
+            assert (rm.cpu() - mod.running_mean).abs().max().item() <= RUNNING_TOL
+            assert (rv.cpu() - mod.running_var).abs().max().item() <= RUNNING_TOL * max(1.0, mod.running_var.abs().max().item())
+            assert nb is None or int(nb) == int(mod.num_batches_tracked) == 6
+
+
+def test_sar_batchnorm_norm_sets_group_matches_the_restatement():
+    from multimodal_tta_amd.registry import get_plugin
+    G, e_margin = 3, 0.8
+    cfg = sar_cfg(BATCH, steps=3, lr=None, e_margin=e_margin, rho=0.05, group=G, norm_sets=True)
+    ref, hip = build_pair(BATCH)
+    plug = get_plugin("sar_tta")(cfg).setup(hip, "cuda")
+    assert plug.group == G
+    vols = [volume(i) for i in range(G)]
+    res = plug.adapt_volume(torch.cat([v[0] for v in vols]).cuda())
+    assert res["losses"].shape == (3, G) and res["kept"].shape == (3, G)
+    z = plug.logits(res).cpu()
+    for g in range(G):
+        x, y = vols[g]
+        m = copy.deepcopy(ref)
+        out_ref = sar_reference(m, x, cfg["training"], 3, e_margin, 0.05)
+        one = {"losses": res["losses"][:, g], "kept": res["kept"][:, g]}
+        check_against_reference(z[g:g + 1], one, out_ref, ref, x, y, cfg, e_margin, 0.05, elements=x[0, :3].numel())
+        for (rm, rv, nb), mod in zip(plug.rt.replica_buffers(g), bn_twins(plug, hip, m)):
+            print("running statistics", (rm.cpu() - mod.running_mean).abs().max().item(),
+                  (rv.cpu() - mod.running_var).abs().max().item())
+            assert (rm.cpu() - mod.running_mean).abs().max().item() <= RUNNING_TOL
+            assert (rv.cpu() - mod.running_var).abs().max().item() <= RUNNING_TOL * max(1.0, mod.running_var.abs().max().item())
+
+
+def test_sar_softmax_head_matches_the_restatement():
+    from multimodal_tta_amd.registry import get_plugin
+    e_margin = 0.8
+    mcfg = dict(SMALL, num_classes=4)
+    cfg = sar_cfg(mcfg, steps=3, lr=None, e_margin=e_margin, rho=0.05, group=1)
+    cfg["training"]["criterion"]["softmax"] = True
+    cfg["training"]["criterion"]["sigmoid"] = False
+    ref, hip = build_pair(mcfg)
+    ref0 = copy.deepcopy(ref)
+    x, y = volume(1, R=4)
+    out_ref = sar_reference(ref, x, cfg["training"], 3, e_margin, 0.05, softmax=True)
+    plug = get_plugin("sar_tta")(cfg).setup(hip, "cuda")
+    assert plug.softmax
+    res = plug.adapt_volume(x.cuda())
+    check_against_reference(plug.logits(res).cpu(), res, out_ref, ref0, x, y, cfg, e_margin, 0.05, softmax=True,
+                            elements=x[0, 0].numel())
+
+
+def test_sar_deepfusion_matches_the_restatement():
+    import oracle
+    from multimodal_tta_amd.models import MultimodalUNetDeepFusion
+    from multimodal_tta_amd.registry import get_plugin
+    e_margin = 0.8
+    mcfg = dict(name="unet_multimodal_deepfusion", num_modalities=4, num_classes=3, spatial_dims=3,
+                channels=[4, 8, 16, 32, 64], strides=[2, 2, 2, 2], num_res_units=2, norm="INSTANCE", act="RELU", dropout=0.0)
+    cfg = sar_cfg(mcfg, steps=3, lr=None, e_margin=e_margin, rho=0.05, group=1)
+    torch.manual_seed(42)
+    ref = oracle.MultimodalUNetDeepFusion(mcfg)
+    hip = MultimodalUNetDeepFusion(mcfg)
+    hip.load_state_dict(ref.state_dict())
+    ref0 = copy.deepcopy(ref)
+    x, y = volume(2)
+    out_ref = sar_reference(ref, x, cfg["training"], 3, e_margin, 0.05)
+    plug = get_plugin("sar_tta")(cfg).setup(hip, "cuda")
+    res = plug.adapt_volume(x.cuda())
+    check_against_reference(plug.logits(res).cpu(), res, out_ref, ref0, x, y, cfg, e_margin, 0.05, elements=x[0, :3].numel())
+
+
+def test_sar_bf16_tracks_the_restatement():
+    from multimodal_tta_amd.registry import get_plugin
+    e_margin = 0.8
+    cfg = sar_cfg(SMALL, steps=3, lr=None, e_margin=e_margin, rho=0.05, group=1, precision="bf16")
+    ref, hip = build_pair(SMALL)
+    ref0 = copy.deepcopy(ref)
+    x, y = volume(5)
+    out_ref = sar_reference(ref, x, cfg["training"], 3, e_margin, 0.05)
+    plug = get_plugin("sar_tta")(cfg).setup(hip, "cuda")
+    res = plug.adapt_volume(x.cuda())
+    check_against_reference(plug.logits(res).cpu(), res, out_ref, ref0, x, y, cfg, e_margin, 0.05, bf16=True,
+                            elements=x[0, :3].numel())
+
+
+@pytest.mark.parametrize("e_margin", [2.0, 0.8])
+def test_one_sar_step_matches_torch_stage_by_stage(monkeypatch, e_margin):
+    """One eager step of the plugin, read at every stage against torch on the same weights: g1, w + eps (the ascent runs on
+    the plugin's own replica and moves it), the keep masks, g2 (taken at w + eps: it differs from g1), the exact restore
+    and the optimizer's result.  With the filter on (e_margin 0.8) g2 is not compared: one ReLU input of this network lies
+    2.1e-6 from zero at w + eps, the two fp32 evaluations put it on different sides, and that single flip moves g2 by
+    3.7e-4 of its 0.13 maximum (reproduced in float64 by flipping that activation alone)."""
+    import oracle
+    from multimodal_tta_amd import ops
+    from multimodal_tta_amd.registry import get_plugin
+    rho = 0.05
+    cfg = sar_cfg(SMALL, steps=1, lr=1e-3, e_margin=e_margin, rho=rho, group=1, use_graph=False)
+    ref, hip = build_pair(SMALL)
+    x, _ = volume(0)
+    plug = get_plugin("sar_tta")(cfg).setup(hip, "cuda")
+    rec = {}
+    ascent = ops.sam_ascent_sets
+
+    def spy_ascent(p, g, saved, partial, n, sets, r):
+        rec["g1"], rec["w0"] = g[0, :n].cpu(), p[0, :n].cpu()
+        ascent(p, g, saved, partial, n, sets, r)
+        rec["w1"] = p[0, :n].cpu()
+
+    step = plug.optimizer_step
+
+    def spy_step(volumes=1):
+        ar = plug.rt.arena
+        rec["g2"], rec["wr"] = ar.grads_all[0, :ar.n_train].cpu(), ar.params_all[0, :ar.n_train].cpu()
+        step(volumes)
+
+    monkeypatch.setattr(ops, "sam_ascent_sets", spy_ascent)
+    monkeypatch.setattr(plug, "optimizer_step", spy_step)
+    plug.adapt_volume(x.cuda())
+    ar = plug.rt.arena
+    w_final = ar.params_all[0, :ar.n_train].cpu()
+    keep1_hip = plug.rt.pool.flat("sar_keep1", x[0, :3].numel(), dtype=torch.uint8).cpu()
+    keep2_hip = plug.rt.pool.flat("sar_keep2", x[0, :3].numel(), dtype=torch.uint8).cpu()
+
+    def flat(values):
+        out = torch.zeros(ar.n_train)
+        for r in ar.refs:
+            if r.trainable:
+                out[r.offset:r.offset + r.numel] = values[r.name].reshape(-1)
+        return out
+
+    named = list(ref.named_parameters())
+    opt = oracle.adam.build_optimizer(named, cfg["training"])
+    ref.train()
+    m = e_margin * math.log(2.0)
+    H = entropy_elements(ref(x), False)
+    keep1 = H < m
+    H[keep1].mean().backward()
+    g1 = flat({n: p.grad for n, p in named})
+    with torch.no_grad():
+        norm = torch.norm(torch.stack([p.grad.norm(p=2) for _, p in named]), p=2)
+        w0 = flat({n: p for n, p in named})
+        old = [p.detach().clone() for _, p in named]
+        for _, p in named:
+            p.add_(p.grad * (rho / (norm + 1e-12)))
+        w1 = flat({n: p for n, p in named})
+    opt.zero_grad()
+    H2 = entropy_elements(ref(x), False)
+    keep2 = keep1 & (H2 < m)
+    H2[keep2].mean().backward()
+    g2 = flat({n: p.grad for n, p in named})
+    with torch.no_grad():
+        for (_, p), o in zip(named, old):
+            p.copy_(o)
+    opt.step()
+    w2 = flat({n: p.detach() for n, p in named})
+
+    assert torch.equal(rec["w0"], w0), "the ascent did not start from the source weights"
+    assert (rec["g1"] - g1).abs().max().item() <= 2e-5 * g1.abs().max().item()
+    assert not torch.equal(rec["w1"], rec["w0"]), "the ascent did not move the plugin's replica"
+    assert ((rec["w1"] - w1).abs() <= 1e-6 * w1.abs() + 1e-7).all()
+    assert torch.equal(keep1_hip, keep_cl(keep1, False)) and torch.equal(keep2_hip, keep_cl(keep2, False))
+    assert torch.equal(rec["wr"], rec["w0"]), "the restore is not exact"
+    if e_margin >= 1.0:
+        assert (rec["g2"] - g2).abs().max().item() <= 2e-5 * g2.abs().max().item()
+        assert (g2 - g1).abs().max().item() > 1e-2 * g1.abs().max().item(), "g2 was not taken at a different point"
+        # Adam's first step: lr * sign-like update; parameters whose gradient is rounding noise may move either way
+        moved = (w_final - w2).abs()
+        assert (moved <= 1e-6 * w2.abs() + 1e-7).float().mean().item() >= 0.99
+
+
+def test_rho0_keep_all_is_bitwise_entmin():
+    """rho = 0 and e_margin = 2 (every element kept): each SAR step is a Tent step computed twice - bit for bit."""
+    from multimodal_tta_amd.registry import get_plugin
+    G = 3
+    xs = torch.cat([volume(i)[0] for i in range(G)]).cuda()
+    out = {}
+    for name in ("entmin_tta", "sar_tta"):
+        cfg = sar_cfg(SMALL, steps=3, e_margin=2.0, rho=0.0, group=G, tune_volumes=4)
+        cfg["method"]["name"] = name
+        _, hip = build_pair(SMALL)
+        plug = get_plugin(name)(cfg).setup(hip, "cuda")
+        res = plug.adapt_volume(xs)
+        z = plug.logits(res)
+        counts = torch.stack([(torch.sigmoid(z[g]) >= 0.5).sum((1, 2, 3)) for g in range(G)])
+        out[name] = (z.cpu(), res["losses"].cpu(), counts.cpu())
+        if name == "sar_tta":
+            assert torch.all(res["kept"].cpu() == 32 ** 3 * 3)
+    for a, b in zip(out["entmin_tta"], out["sar_tta"]):
+        assert torch.equal(a, b)
+
+
+def test_sar_group_equals_one_volume_at_a_time_and_graph_equals_eager():
+    from multimodal_tta_amd.registry import get_plugin
+    G = 3
+    vols = [volume(i)[0] for i in range(G)]
+    runs = {}
+    for group, use_graph in ((G, True), (1, True), (G, False)):
+        cfg = sar_cfg(SMALL, steps=3, e_margin=0.6, rho=0.05, group=group, tune_volumes=4, use_graph=use_graph)
+        _, hip = build_pair(SMALL)
+        plug = get_plugin("sar_tta")(cfg).setup(hip, "cuda")
+        if group == G:
+            r = plug.adapt_volume(torch.cat(vols).cuda())
+            runs[(group, use_graph)] = (plug.logits(r).cpu(), r["losses"].cpu(), r["kept"].cpu())
+        else:
+            zs, ls, ks = [], [], []
+            for v in vols:
+                r = plug.adapt_volume(v.cuda())
+                zs.append(plug.logits(r).cpu())
+                ls.append(r["losses"].cpu())
+                ks.append(r["kept"].cpu())
+            runs[(group, use_graph)] = (torch.cat(zs), torch.stack(ls, 1), torch.stack(ks, 1))
+    for a, b in zip(runs[(G, True)], runs[(1, True)]):
+        assert torch.equal(a, b), "grouped run differs from one volume at a time"
+    for a, b in zip(runs[(G, True)], runs[(G, False)]):
+        assert torch.equal(a, b), "graph replay differs from eager launches"
+
+
+def test_seg_tta_eval_with_tta_sar():
+    from multimodal_tta_amd.config import compose
+    from multimodal_tta_amd.registry import get_dataset_builder, get_evaluation_strategy
+    cfg = compose(overrides=["task=brats", "model=unet", "method=tta_sar", "method.steps=2"])
+    cfg["model"] = dict(SMALL)
+    cfg["dataset"]["synthetic"]["num_volumes"] = 2
+    cfg["dataset"]["synthetic"]["shape"] = [32, 32, 32]
+    _, hip = build_pair(SMALL)
+    loader = get_dataset_builder("brats")(cfg).get_loader("test")
+    strat = get_evaluation_strategy("seg_tta_eval")(cfg)
+    m = strat.evaluate_epoch(hip, loader, torch.device("cuda"))
+    assert type(strat.plugin).__name__ == "SharpnessAwareReliableTTA"
+    assert {"et_dc", "tc_dc", "wt_dc", "avg_dc", "loss"} <= set(m)
+    assert 0.0 <= m["avg_dc"] <= 1.0
+
+
+FULL = dict(name="unet", in_channels=4, num_classes=3, spatial_dims=3, channels=[32, 64, 128, 256, 512],
+            strides=[2, 2, 2, 2], num_res_units=2, norm="INSTANCE", act="RELU", dropout=0.0)
+
+
+def test_sar_full_width_bf16_tracks_the_restatement():
+    """unet 4x128^3 at the width the bench runs, bf16, S = 2, against the restatement on the host cores."""
+    import oracle
+    from multimodal_tta_amd.models import UNet
+    from multimodal_tta_amd.registry import get_plugin
+    from multimodal_tta_amd.synth import synth_volume
+    e_margin = 0.4
+    cfg = sar_cfg(FULL, steps=2, lr=None, e_margin=e_margin, rho=0.05, group=1, lanes=1, precision="bf16")
+    torch.manual_seed(42)
+    ref = oracle.UNet(FULL)
+    hip = UNet(FULL)
+    hip.load_state_dict(ref.state_dict())
+    v = synth_volume(0, 4, (128, 128, 128), 3)
+    x, y = v["image"].unsqueeze(0), v["label"].unsqueeze(0)
+    out_ref = sar_reference(ref, x, cfg["training"], 2, e_margin, 0.05)
+    plug = get_plugin("sar_tta")(cfg).setup(hip, "cuda")
+    res = plug.adapt_volume(x.cuda())
+    check_against_reference(plug.logits(res).cpu(), res, out_ref, None, x, y, cfg, e_margin, 0.05, bf16=True,
+                            elements=x[0, :3].numel())
