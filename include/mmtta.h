@@ -512,6 +512,34 @@ int mmtta_optim_step(const mmtta_optim_desc* desc, float* p, const float* g, flo
 int mmtta_optim_step_sets(const mmtta_optim_desc* desc, float* p, const float* g, float* m, float* v, int64_t n,
                           int64_t n_decay, int sets, int64_t set_stride, int32_t* step, void* stream);
 
+/* Weight gradient, optimizer step and repack of a 27-tap layer in one pass (per parameter set).  The weight-gradient
+ * kernel writes its slabs as mmtta_conv_wgrad_sets does; the reduction of the slabs then feeds the optimizer of the layer's
+ * weight (and bias) directly and writes the new weights into both bf16 packed images - bit for bit what
+ * mmtta_conv_wgrad_sets + mmtta_optim_step_sets + mmtta_conv_pack_batched give.  The step counter is read, not advanced.
+ * Layers whose gradient does not end in the 27-tap reduction, and non-bf16 images, are MMTTA_ERR_UNSUPPORTED.
+ * Switched off (MMTTA_ERR_UNSUPPORTED) by MMTTA_FUSED_UPDATE=0 in the environment; mmtta_fused_update_enabled says which. */
+typedef struct mmtta_update_target {
+  mmtta_optim_desc optim;
+  float* w_p; float* w_m; float* w_v;  /* weight, its moments: set 0, set strides of mmtta_param_sets.weight_* */
+  float* b_p; float* b_m; float* b_v;  /* bias and its moments (Conv3d only; NULL: no bias, or not updated here) */
+  float* b_grad;                       /* ConvTranspose3d: its bias gradient lands here, for the arena optimizer */
+  void* image[2];                      /* forward and input-gradient images of set 0 (image[1] may be NULL) */
+  int64_t image_outer[2], image_inner[2]; /* BYTES between the images of sets, as mmtta_param_sets.packed_* */
+  const int32_t* step;                 /* device step counter (read) */
+  int32_t w_decay, b_decay;            /* the parameter group decays (weight_decay applies) */
+} mmtta_update_target;
+int mmtta_fused_update_enabled(void);
+int mmtta_conv_wgrad_update_sets(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                 const mmtta_tensor* dy, const mmtta_update_target* target, void* workspace,
+                                 int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);
+
+/* mmtta_optim_step_sets over a table of segments of every replica (the parameters a fused weight-gradient update does not
+ * cover).  `segments` is a DEVICE int64 table: `count` rows (start, length, decay) relative to a replica, start and length
+ * multiples of 4, followed by the `count` running starts of the rows (0, length0, length0 + length1, ...).  `total` = sum
+ * of the lengths.  Same arithmetic as mmtta_optim_step_sets; the shared step counter is advanced once, after the launch. */
+int mmtta_optim_step_segments(const mmtta_optim_desc* desc, float* p, const float* g, float* m, float* v, const int64_t* segments,
+                              int count, int64_t total, int sets, int64_t set_stride, int32_t* step, void* stream);
+
 /* The ascent of a sharpness-aware step (SAM, as SAR uses it) over the first `sets` of `replicas` arena replicas
  * ([replica][set_stride]): per replica r, over [0, n),
  *   saved = p;  p += g * (rho / (||g||_2 + 1e-12))

@@ -76,6 +76,13 @@ class OptimDesc(C.Structure):          # mmtta_optim_desc
                 ("weight_decay", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int32)]
 
 
+class UpdateTarget(C.Structure):       # mmtta_update_target
+    _fields_ = [("optim", OptimDesc), ("w_p", C.c_void_p), ("w_m", C.c_void_p), ("w_v", C.c_void_p), ("b_p", C.c_void_p),
+                ("b_m", C.c_void_p), ("b_v", C.c_void_p), ("b_grad", C.c_void_p), ("image", C.c_void_p * 2),
+                ("image_outer", C.c_int64 * 2), ("image_inner", C.c_int64 * 2), ("step", C.c_void_p),
+                ("w_decay", C.c_int32), ("b_decay", C.c_int32)]
+
+
 OPTIM_ADAM, OPTIM_ADAMW, OPTIM_SGD = 0, 1, 2
 
 
@@ -152,6 +159,11 @@ _SIGNATURES = {
                                    C.c_void_p, C.c_void_p]),
     "mmtta_optim_step_sets": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                         C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mmtta_optim_step_segments": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                            C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mmtta_fused_update_enabled": (C.c_int, []),
+    "mmtta_conv_wgrad_update_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(Tensor), _P(UpdateTarget),
+                                               C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
     "mmtta_sam_ascent_partials": (C.c_int64, [C.c_int64, C.c_int]),
     "mmtta_sam_ascent_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                         C.c_int64, C.c_float, C.c_void_p]),

@@ -58,6 +58,14 @@ inline int nl_act_check(const mmtta_norm_on_load* t, const char* what) {
   return MMTTA_OK;
 }
 
+// Geometry of a packed weight image (conv_igemm.hip: fill_pack_entry): torch weight [A][B][T], image [T][Kp][Np] with
+// K = B, N = A when kn_is_ba, else K = A, N = B.  `plain_bf16`: a bf16 [T][Kp/8][Np][8] image and nothing else in the buffer
+// (not direct, no gather-GEMM or thin-K fragment image behind it).
+struct PackImageGeo {
+  int A, B, T, Kp, Np, kn_is_ba, plain_bf16;
+};
+int pack_image_geometry(const mmtta_conv_desc* d, PackImageGeo& g);
+
 // entry bodies of one activation instantiation (descriptors already validated by the C entry point)
 #define MMTTA_ACT_BODIES                                                                                                    \
   int conv_run_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,  \
@@ -65,7 +73,8 @@ inline int nl_act_check(const mmtta_norm_on_load* t, const char* what) {
                     void* workspace, int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);                \
   int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,                    \
                       const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,                        \
-                      int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);                                 \
+                      int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream,                                  \
+                      const mmtta_update_target* upd);                                                                      \
   int combine_body(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtta_tensor* b,                              \
                    const mmtta_norm_on_load* tb, const mmtta_tensor* out, void* stream);                                    \
   int norm_bwd_reduce_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t, float* part,      \
@@ -103,6 +112,15 @@ __device__ __forceinline__ unsigned int f32x2_to_bf16x2(float lo, float hi) {
   v[0] = (__bf16)lo;   // v_cvt_pk_bf16_f32: round to nearest even, NaN preserved
   v[1] = (__bf16)hi;
   return __builtin_bit_cast(unsigned int, v);
+}
+// fp32 -> bf16 bits, round to nearest even (the packed weight images: pack_tile and the fused weight update)
+__device__ __forceinline__ unsigned short f32_to_bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
+// 8 consecutive k of one column of a bf16 image [T][Kp/8][Np][8]: one 16-byte store
+__device__ __forceinline__ uint4 bf16x8_pack(const unsigned short* h) {
+  uint4 q;
+  q.x = h[0] | ((unsigned)h[1] << 16); q.y = h[2] | ((unsigned)h[3] << 16);
+  q.z = h[4] | ((unsigned)h[5] << 16); q.w = h[6] | ((unsigned)h[7] << 16);
+  return q;
 }
 __device__ __forceinline__ float4 ld4_any(const float* base, long long eoff, int bf) {
   if (bf) {

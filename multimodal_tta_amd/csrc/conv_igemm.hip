@@ -1430,12 +1430,9 @@ __device__ __forceinline__ void pack_tile(const PackEntry& e, int lb, float* til
 #pragma unroll
       for (int kk = 0; kk < PK; ++kk) {
         const float v = e.kn_is_ba ? tile[nn * RS + kk * T + tp] : tile[kk * (PN * T) + nn * T + tp];
-        h[kk] = __builtin_bit_cast(unsigned short, (__bf16)v);
+        h[kk] = f32_to_bf16_bits(v);
       }
-      uint4 q;
-      q.x = h[0] | ((unsigned)h[1] << 16); q.y = h[2] | ((unsigned)h[3] << 16);
-      q.z = h[4] | ((unsigned)h[5] << 16); q.w = h[6] | ((unsigned)h[7] << 16);
-      *reinterpret_cast<uint4*>((unsigned short*)e.p + tp * slab + ((long long)(k0 >> 3) * e.Np + n0 + nn) * 8) = q;
+      *reinterpret_cast<uint4*>((unsigned short*)e.p + tp * slab + ((long long)(k0 >> 3) * e.Np + n0 + nn) * 8) = bf16x8_pack(h);
     }
   } else {
     for (int o = threadIdx.x; o < T * PK * PN; o += 256) {
@@ -2111,27 +2108,50 @@ extern "C" int mmtta_conv_pack_weights(const mmtta_conv_desc* d, const float* w,
   return launch_status("pack weights");
 }
 
-static int fill_pack_entry(const mmtta_conv_desc* d, const float* w, void* packed, PackEntry& e) {
+// the geometry of an entry (every field but the pointers); up8 / chfr: whether those images follow the tap image
+static int pack_entry_geometry(const mmtta_conv_desc* d, PackEntry& e, bool& up8, bool& chfr) {
   int st = validate_desc(d);
   if (st) return st;
-  MMTTA_CHECK(w && packed, MMTTA_ERR_INVALID, "pack: null pointer");
   int K, N, si; bool cl;
   op_dims(d, K, N, si, cl);
   const bool convt = d->op == MMTTA_CONVT_FWD || d->op == MMTTA_CONVT_DGRAD;
   const bool direct = direct_applicable(d);
-  e.w = w; e.p = packed;
+  e.w = nullptr; e.p = nullptr; e.up8 = nullptr; e.chfr = nullptr;
   e.A = convt ? d->cin : d->cout; e.B = convt ? d->cout : d->cin;
   e.T = d->ksize * d->ksize * d->ksize;
   e.Kp = direct ? K : roundup(K, 32); e.Np = direct ? 4 : roundup(N, 32);
   e.kn_is_ba = (d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONVT_DGRAD) ? 1 : 0;
   e.bf16 = use_bf16(d, K) ? 1 : 0; e.direct = direct ? 1 : 0;
-  e.up8 = (direct && upconv8_image_bytes(d) > 0) ? (unsigned short*)((char*)packed + (size_t)e.T * e.Kp * e.Np * 4) : nullptr;
-  e.chfr = (!direct && chan_frag_bytes(d) > 0) ? (uint4*)((char*)packed + (size_t)e.T * e.Kp * e.Np * 4) : nullptr;
+  up8 = direct && upconv8_image_bytes(d) > 0;
+  chfr = !direct && chan_frag_bytes(d) > 0;
   e.KI = K; e.NO = N;
   MMTTA_CHECK(e.T == 1 || e.T == 27, MMTTA_ERR_UNSUPPORTED, "pack: ksize %d", d->ksize);
   e.start = 0;
   return MMTTA_OK;
 }
+
+static int fill_pack_entry(const mmtta_conv_desc* d, const float* w, void* packed, PackEntry& e) {
+  bool up8, chfr;
+  int st = pack_entry_geometry(d, e, up8, chfr);
+  if (st) return st;
+  MMTTA_CHECK(w && packed, MMTTA_ERR_INVALID, "pack: null pointer");
+  e.w = w; e.p = packed;
+  e.up8 = up8 ? (unsigned short*)((char*)packed + (size_t)e.T * e.Kp * e.Np * 4) : nullptr;
+  e.chfr = chfr ? (uint4*)((char*)packed + (size_t)e.T * e.Kp * e.Np * 4) : nullptr;
+  return MMTTA_OK;
+}
+
+namespace mmtta {
+int pack_image_geometry(const mmtta_conv_desc* d, PackImageGeo& g) {
+  PackEntry e;
+  bool up8, chfr;
+  const int st = pack_entry_geometry(d, e, up8, chfr);
+  if (st) return st;
+  g.A = e.A; g.B = e.B; g.T = e.T; g.Kp = e.Kp; g.Np = e.Np; g.kn_is_ba = e.kn_is_ba;
+  g.plain_bf16 = (e.bf16 && !e.direct && !up8 && !chfr) ? 1 : 0;
+  return MMTTA_OK;
+}
+}  // namespace mmtta
 
 extern "C" int64_t mmtta_conv_pack_table_bytes(int count) { return count < 0 ? -1 : (int64_t)count * (int64_t)sizeof(PackEntry); }
 

@@ -237,6 +237,48 @@ __global__ __launch_bounds__(256) void wgrad_f32_kernel(WArgs a) {
   }
 }
 
+// The sums of the 27-tap reduction, shared by wgrad_reduce27_kernel and wgrad_update27_kernel (the two must agree bit for
+// bit).  slab_sums: NI elements per thread, element it = sum over sl of pit[it][sl * st] in slab order, 4 slabs per trip.
+template <int NI>
+__device__ __forceinline__ void slab_sums(const float* const* pit, int nsl, long long st, float* acc) {
+#pragma unroll
+  for (int it = 0; it < NI; ++it) acc[it] = 0.f;
+  for (int sl = 0; sl < nsl; sl += 4) {
+    float v[NI][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int it = 0; it < NI; ++it) v[it][u] = pit[it][(long long)min(sl + u, nsl - 1) * st];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int it = 0; it < NI; ++it) acc[it] += sl + u < nsl ? v[it][u] : 0.f;
+  }
+}
+// bias_rows_sum: db[cd0 + t] for thread t < 32 = sum_sl dbpart[sl][cd] (8 threads per channel, then 8 partials in order);
+// every thread of the block calls it (one barrier), `red` holds 256 floats of LDS
+__device__ __forceinline__ float bias_rows_sum(const float* __restrict__ dbpart, int db_nsl, int Cd, int CDp, int cd0, float* red) {
+  const int cdl = threadIdx.x & 31, part = threadIdx.x >> 5;
+  const int cd = min(cd0 + cdl, Cd - 1);
+  float s4[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int sl = part; sl < db_nsl; sl += 32) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int q = sl + 8 * u;
+      const float v = dbpart[(long long)min(q, db_nsl - 1) * CDp + cd];
+      s4[u] += q < db_nsl ? v : 0.f;
+    }
+  }
+  red[threadIdx.x] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+  __syncthreads();
+  float t = 0.f;
+  if (threadIdx.x < 32) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) t += red[q * 32 + threadIdx.x];
+  }
+  return t;
+}
+
 // dw[cd][cg][tap] (+)= sum_sl slab[sl][tap][cg][cd]   (torch weight layout out of the [tap][cg][cd] slabs)
 // The transpose goes through LDS so that both sides stay coalesced: reads run along cd, writes are runs of
 // `ntaps` consecutive floats per (cd, cg).  27 taps: one block = one cg x 64 cd;  1 tap: 32 cg x 32 cd.
@@ -254,24 +296,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce27_kernel(const float* __rest
   const int cd0 = blockIdx.y * 32;
   if ((int)blockIdx.x == Cg) {
     // bias gradient rows ride in the same launch: db[cd] (+)= sum_sl dbpart[sl][cd]; 8 threads per channel
-    const int cdl = threadIdx.x & 31, part = threadIdx.x >> 5;
-    const int cd = min(cd0 + cdl, Cd - 1);
-    float s4[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int sl = part; sl < db_nsl; sl += 32) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int q = sl + 8 * u;
-        const float v = dbpart[(long long)min(q, db_nsl - 1) * CDp + cd];
-        s4[u] += q < db_nsl ? v : 0.f;
-      }
-    }
-    float* red = &tile[0][0];
-    red[threadIdx.x] = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    __syncthreads();
+    const float t = bias_rows_sum(dbpart, db_nsl, Cd, CDp, cd0, &tile[0][0]);
     if (threadIdx.x < 32 && cd0 + (int)threadIdx.x < Cd) {
-      float t = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t += red[q * 32 + threadIdx.x];
       float* o = db + cd0 + threadIdx.x;
       *o = accumulate ? (*o + t) : t;
     }
@@ -290,18 +316,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce27_kernel(const float* __rest
     live[it] = i < 27 * 32 && cd0 + cdl < Cd;
     pit[it] = slab + ((long long)tap * CGp + cg) * CDp + min(cd0 + cdl, CDp - 1);
   }
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int sl = 0; sl < nsl; sl += 4) {
-    float v[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int it = 0; it < 4; ++it) v[it][u] = pit[it][(long long)min(sl + u, nsl - 1) * st];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int it = 0; it < 4; ++it) acc[it] += sl + u < nsl ? v[it][u] : 0.f;
-  }
+  float acc[4];
+  slab_sums<4>(pit, nsl, st, acc);
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     const int i = threadIdx.x + 256 * it;
@@ -315,6 +331,142 @@ __global__ __launch_bounds__(256) void wgrad_reduce27_kernel(const float* __rest
       const long long idx = ((long long)cd * Cg + cg) * 27 + tap;
       const float v = tile[cdl][tap];
       dw[idx] = accumulate ? (dw[idx] + v) : v;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ fused weight update (27 taps)
+// wgrad_reduce27_kernel + the arena optimizer + the repack of both bf16 images in one pass over a layer's weights.  One
+// block = one parameter set (blockIdx.z) x 8 cg x 32 cd x 27 taps of the layer: the tile pack_tile<27> moves (PK x PN), so
+// both images are written as whole 16-byte runs.  Per element: the slab sum of wgrad_reduce27_kernel (slab_sums), then
+// optim_update on the torch-layout p / m / v of the set, then fp32 -> bf16 into the images.  The extra column of blocks
+// (blockIdx.x == cg tiles) reduces and updates the bias rows.  Nothing else reads the gradient: it never reaches memory.
+struct UpdImage {
+  unsigned short* p;                  // set 0's image (null: none)
+  long long outer, inner;             // bytes between the images of sets
+  int Kp, Np, kn_is_ba;
+};
+struct UpdArgs {
+  OptimArgs a;
+  float *wp, *wm, *wv, *bp, *bm, *bv;
+  UpdImage img[2];
+  const int* step;
+  int w_decay, b_decay;
+};
+
+constexpr int UPD_CG = 8, UPD_CD = 32, UPD_RS = UPD_CG * 27 + 1;      // LDS row = one cd: [cg][tap] (odd stride)
+
+template <int KIND>
+__global__ __launch_bounds__(256) void wgrad_update27_kernel(const float* __restrict__ slab, int nsl, int Cg, int Cd, int CGp,
+                                                             int CDp, const float* __restrict__ dbpart, int db_nsl, PSets ps,
+                                                             UpdArgs u) {
+  __shared__ float tile[UPD_CD * UPD_RS];
+  __shared__ float s_step_size, s_bc2_sqrt;
+  const int q = blockIdx.z;
+  slab += (long long)q * nsl * 27 * CGp * CDp;
+  const int t0 = *u.step;
+  if (threadIdx.x == 0) optim_scalars(KIND, u.a, t0, s_step_size, s_bc2_sqrt);
+  const bool first = t0 == 0;
+  const bool wd_on = u.a.wd != 0.f;
+  const bool keep_m = KIND != 2 || u.a.momentum != 0.f;
+  const int cd0 = blockIdx.y * UPD_CD;
+  const int cg_tiles = (Cg + UPD_CG - 1) / UPD_CG;
+  if ((int)blockIdx.x == cg_tiles) {
+    // bias rows: the reduction of wgrad_reduce27_kernel's extra column, then the optimizer
+    const float t = bias_rows_sum(dbpart + (long long)q * db_nsl * CDp, db_nsl, Cd, CDp, cd0, tile);
+    const float step_size = s_step_size, bc2_sqrt = s_bc2_sqrt;       // (written before bias_rows_sum's barrier)
+    const int cd = cd0 + (int)threadIdx.x;
+    if (threadIdx.x < 32 && cd < Cd) {
+      const long long o = pset_bias_elems(ps, q) + cd;
+      float pi = u.bp[o], mi = 0.f, vi = 0.f;
+      if (!first) {
+        if (keep_m) mi = u.bm[o];
+        if (KIND != 2) vi = u.bv[o];
+      }
+      optim_update<KIND>(pi, t, mi, vi, wd_on && u.b_decay, u.a, step_size, bc2_sqrt, first);
+      u.bp[o] = pi;
+      if (keep_m) u.bm[o] = mi;
+      if (KIND != 2) u.bv[o] = vi;
+    }
+    return;
+  }
+  const int cg0 = blockIdx.x * UPD_CG;
+  const long long st = (long long)27 * CGp * CDp;
+  // ---- reduce: element e = tid + 256 j (j < 27) is (cgl, tap, cdl) = (e / 864, (e % 864) >> 5, e & 31), as in reduce27
+  constexpr int NI = 9;
+#pragma unroll 1
+  for (int j0 = 0; j0 < 27; j0 += NI) {
+    const float* pit[NI];
+    bool live[NI];
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+      const int e = threadIdx.x + 256 * (j0 + it);
+      const int cgl = e / 864, i = e % 864, cdl = i & 31, tap = i >> 5;
+      const int cg = cg0 + cgl, cd = cd0 + cdl;
+      live[it] = cg < Cg && cd < Cd;
+      pit[it] = slab + ((long long)tap * CGp + min(cg, Cg - 1)) * CDp + min(cd, CDp - 1);
+    }
+    float acc[NI];
+    slab_sums<NI>(pit, nsl, st, acc);
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+      const int e = threadIdx.x + 256 * (j0 + it);
+      const int cgl = e / 864, i = e % 864, cdl = i & 31, tap = i >> 5;
+      tile[cdl * UPD_RS + cgl * 27 + tap] = live[it] ? acc[it] : 0.f;
+    }
+  }
+  __syncthreads();
+  // ---- optimizer on the torch-layout rows: per cd a run of 8 cg x 27 taps = 216 consecutive floats
+  {
+    const float step_size = s_step_size, bc2_sqrt = s_bc2_sqrt;
+    const bool decay = wd_on && u.w_decay;
+    const long long wo = pset_weight_elems(ps, q);
+    const int ncg = min(UPD_CG, Cg - cg0);
+    for (int e = threadIdx.x; e < UPD_CD * UPD_CG * 27; e += 256) {
+      const int cdl = e / (UPD_CG * 27), r = e % (UPD_CG * 27);
+      const int cd = cd0 + cdl;
+      if (cd < Cd && r < ncg * 27) {
+        const long long o = wo + ((long long)cd * Cg + cg0) * 27 + r;
+        float pi = u.wp[o], mi = 0.f, vi = 0.f;
+        if (!first) {
+          if (keep_m) mi = u.wm[o];
+          if (KIND != 2) vi = u.wv[o];
+        }
+        optim_update<KIND>(pi, tile[cdl * UPD_RS + r], mi, vi, decay, u.a, step_size, bc2_sqrt, first);
+        u.wp[o] = pi;
+        if (keep_m) u.wm[o] = mi;
+        if (KIND != 2) u.wv[o] = vi;
+        tile[cdl * UPD_RS + r] = pi;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- repack: both images, pack_tile's index map and rounding (positions outside the weight hold 0, as there)
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const UpdImage im = u.img[m];
+    if (im.p == nullptr) continue;
+    unsigned short* img = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(im.p) + (ps.inner == 1
+        ? q * im.outer : (q / ps.inner) * im.outer + (q % ps.inner) * im.inner));
+    const long long tslab = (long long)im.Kp * im.Np;
+    if (im.kn_is_ba) {
+      // k = cg (one group of 8), n = cd (32 columns): 27 x 32 runs of 16 bytes
+      for (int o = threadIdx.x; o < 27 * UPD_CD; o += 256) {
+        const int nn = o % UPD_CD, tp = o / UPD_CD;
+        unsigned short h[8];
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) h[kk] = f32_to_bf16_bits(tile[nn * UPD_RS + kk * 27 + tp]);
+        *reinterpret_cast<uint4*>(img + tp * tslab + ((long long)(cg0 >> 3) * im.Np + cd0 + nn) * 8) = bf16x8_pack(h);
+      }
+    } else {
+      // k = cd (four groups of 8), n = cg (8 columns)
+      for (int o = threadIdx.x; o < 27 * 4 * UPD_CG; o += 256) {
+        const int c = o % UPD_CG, k8 = (o / UPD_CG) % 4, tp = o / (UPD_CG * 4);
+        unsigned short h[8];
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) h[kk] = f32_to_bf16_bits(tile[(k8 * 8 + kk) * UPD_RS + c * 27 + tp]);
+        *reinterpret_cast<uint4*>(img + tp * tslab + ((long long)((cd0 >> 3) + k8) * im.Np + cg0 + c) * 8) = bf16x8_pack(h);
+      }
     }
   }
 }
@@ -1949,12 +2101,50 @@ static int launch_wgrad(const WArgs& a, int S, hipStream_t s) {
 // mmtta_conv_wgrad_sets past the checks of its norm-on-load descriptor
 int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                     const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
-                    int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
+                    int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream, const mmtta_update_target* upd) {
   WGeo w;
   int st = wgeometry(d, x, dy, sets, w);
   if (st) return st;
   const PSets ps = psets(sets);
   const int Q = w.nsets;                 // the workspace regions below hold Q sets back to back (set-major)
+  UpdArgs ua;
+  if (upd != nullptr) {
+    // the fused update (mmtta_conv_wgrad_update_sets): checked before anything is launched
+    MMTTA_CHECK(!w.tiny && !w.small && w.ntaps == 27, MMTTA_ERR_UNSUPPORTED,
+                "wgrad update: the layer's weight gradient does not end in the 27-tap reduction");
+    MMTTA_CHECK(upd->w_p && upd->w_m && upd->step && upd->image[0] && (upd->optim.kind == MMTTA_OPTIM_SGD || upd->w_v),
+                MMTTA_ERR_INVALID, "wgrad update: null weight, moment, image or step pointer");
+    const bool convt = d->op == MMTTA_CONVT_FWD;
+    MMTTA_CHECK(upd->b_p == nullptr || (!convt && upd->b_m && (upd->optim.kind == MMTTA_OPTIM_SGD || upd->b_v)),
+                MMTTA_ERR_UNSUPPORTED, "wgrad update: the bias is updated here for Conv3d only (ConvTranspose3d: b_grad)");
+    MMTTA_CHECK(upd->optim.kind >= MMTTA_OPTIM_ADAM && upd->optim.kind <= MMTTA_OPTIM_SGD, MMTTA_ERR_INVALID,
+                "wgrad update: optimizer kind %d", upd->optim.kind);
+    const mmtta_optim_desc& o = upd->optim;
+    MMTTA_CHECK(!(o.kind == MMTTA_OPTIM_SGD && o.nesterov && (o.momentum <= 0.f || o.dampening != 0.f)), MMTTA_ERR_INVALID,
+                "wgrad update: nesterov needs momentum > 0 and zero dampening");
+    ua.a = OptimArgs{o.lr, o.beta1, o.beta2, o.eps, o.weight_decay, o.momentum, o.dampening, o.nesterov};
+    ua.wp = upd->w_p; ua.wm = upd->w_m; ua.wv = upd->w_v;
+    ua.bp = upd->b_p; ua.bm = upd->b_m; ua.bv = upd->b_v;
+    ua.step = upd->step; ua.w_decay = upd->w_decay ? 1 : 0; ua.b_decay = upd->b_decay ? 1 : 0;
+    for (int m = 0; m < 2; ++m) {
+      ua.img[m].p = (unsigned short*)upd->image[m];
+      ua.img[m].outer = upd->image_outer[m]; ua.img[m].inner = upd->image_inner[m];
+      ua.img[m].Kp = ua.img[m].Np = ua.img[m].kn_is_ba = 0;
+      if (upd->image[m] == nullptr) continue;
+      mmtta_conv_desc dd = *d;
+      if (m == 1) dd.op = convt ? MMTTA_CONVT_DGRAD : MMTTA_CONV_DGRAD;
+      PackImageGeo g;
+      st = pack_image_geometry(&dd, g);
+      if (st) return st;
+      MMTTA_CHECK(g.plain_bf16 && g.T == 27, MMTTA_ERR_UNSUPPORTED, "wgrad update: image %d is not a 27-tap bf16 image", m);
+      MMTTA_CHECK(g.A == w.dn->c && g.B == w.g->c, MMTTA_ERR_INVALID, "wgrad update: image %d does not match the gradient", m);
+      MMTTA_CHECK(((uintptr_t)upd->image[m]) % 16 == 0 && upd->image_outer[m] % 16 == 0 && upd->image_inner[m] % 16 == 0,
+                  MMTTA_ERR_INVALID, "wgrad update: images must keep 16-byte alignment");
+      ua.img[m].Kp = g.Kp; ua.img[m].Np = g.Np; ua.img[m].kn_is_ba = g.kn_is_ba;
+    }
+    dw = upd->w_p;                       // (not written: the gradient stays in the workspace)
+    db = convt ? upd->b_grad : upd->b_p;
+  }
   MMTTA_CHECK(dw != nullptr, MMTTA_ERR_INVALID, "wgrad: null dw");
   const int64_t need = (w.slab_floats + w.db_floats + w.pre_floats) * Q * 4;
   MMTTA_CHECK(workspace != nullptr && workspace_bytes >= need, MMTTA_ERR_WORKSPACE, "wgrad: workspace %lld bytes, need %lld",
@@ -2077,7 +2267,7 @@ int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   else if (w.tr) st = (w.si == 1) ? launch_wgrad_tr<4, 8, 1>(a, SQ, s, w.ncb) : launch_wgrad_tr<2, 4, 2>(a, SQ, s, w.ncb);
   else if (w.ntaps == 1) st = launch_wgrad<4, 4, 8, 1>(a, SQ, s);
   else st = (w.si == 1) ? launch_wgrad<4, 4, 8, 7>(a, SQ, s) : launch_wgrad<2, 2, 8, 7>(a, SQ, s);
-  if (st || g_profile_main_only) return st;
+  if (st || (g_profile_main_only && upd == nullptr)) return st;
   const float* rsrc = a.slab;
   int rn = w.nsl;
   if (w.pre_chunks > 0) {
@@ -2090,7 +2280,18 @@ int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
     rsrc = pre; rn = w.pre_chunks;
   }
   const bool db_here = db != nullptr && !w.convt;      // bias partials written by the main kernel: [nsl][CDp]
-  if (w.ntaps == 27)
+  if (upd != nullptr) {
+    const dim3 grid((a.Cg + UPD_CG - 1) / UPD_CG + (db_here ? 1 : 0), (a.Cd + UPD_CD - 1) / UPD_CD, Q);
+    if (upd->optim.kind == MMTTA_OPTIM_ADAM)
+      hipLaunchKernelGGL(wgrad_update27_kernel<0>, grid, dim3(256), 0, s, rsrc, rn, a.Cg, a.Cd, w.CGp, w.CDp, dbws, w.nsl, ps, ua);
+    else if (upd->optim.kind == MMTTA_OPTIM_ADAMW)
+      hipLaunchKernelGGL(wgrad_update27_kernel<1>, grid, dim3(256), 0, s, rsrc, rn, a.Cg, a.Cd, w.CGp, w.CDp, dbws, w.nsl, ps, ua);
+    else
+      hipLaunchKernelGGL(wgrad_update27_kernel<2>, grid, dim3(256), 0, s, rsrc, rn, a.Cg, a.Cd, w.CGp, w.CDp, dbws, w.nsl, ps, ua);
+    st = launch_status("wgrad update");
+    if (st) return st;
+    if (db != nullptr && !w.convt) db = nullptr;       // the bias rows rode in the launch above
+  } else if (w.ntaps == 27)
     hipLaunchKernelGGL(wgrad_reduce27_kernel, dim3(a.Cg + (db_here ? 1 : 0), (a.Cd + 31) / 32, Q), dim3(256), 0, s, rsrc, dw, rn,
                        a.Cg, a.Cd, w.CGp, w.CDp, accumulate, dbws, db_here ? db : nullptr, w.nsl, ps);
   else
@@ -2160,7 +2361,28 @@ extern "C" int mmtta_conv_wgrad_sets(const mmtta_conv_desc* d, const mmtta_tenso
     if (st) return st;
   }
   if (nl_leaky(x_norm))
-    return leaky::conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream);
-  return conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream);
+    return leaky::conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
+  return conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
+}
+
+// (A/B switch: MMTTA_FUSED_UPDATE=0 turns the fused weight update off; the host then takes the separate passes)
+static const int g_fused_update = getenv("MMTTA_FUSED_UPDATE") ? atoi(getenv("MMTTA_FUSED_UPDATE")) : 1;
+
+extern "C" int mmtta_fused_update_enabled(void) { return g_fused_update != 0 ? 1 : 0; }
+
+extern "C" int mmtta_conv_wgrad_update_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                            const mmtta_tensor* dy, const mmtta_update_target* target, void* workspace,
+                                            int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
+  MMTTA_CHECK(g_fused_update != 0, MMTTA_ERR_UNSUPPORTED, "wgrad update: switched off (MMTTA_FUSED_UPDATE=0)");
+  MMTTA_CHECK(target != nullptr, MMTTA_ERR_INVALID, "wgrad update: null target");
+  {
+    int st = nl_act_check(x_norm, "conv_wgrad_update (x_norm)");
+    if (st) return st;
+    st = nl_per_item_check(x_norm, "conv_wgrad_update (x_norm)");
+    if (st) return st;
+  }
+  if (nl_leaky(x_norm))
+    return leaky::conv_wgrad_body(d, x, x_norm, dy, nullptr, nullptr, 0, workspace, workspace_bytes, sets, stream, target);
+  return conv_wgrad_body(d, x, x_norm, dy, nullptr, nullptr, 0, workspace, workspace_bytes, sets, stream, target);
 }
 #endif  // MMTTA_ACT_LEAKY_TU

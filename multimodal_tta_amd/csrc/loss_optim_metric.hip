@@ -226,6 +226,54 @@ __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const
   }
 }
 
+// optim_kernel over a table of segments of each replica (the parameters the fused weight updates of conv_wgrad.hip do not
+// cover): seg[3 i .. 3 i + 2] = (start, length, decay), multiples of 4; a thread owns 4 consecutive parameters of the
+// concatenation of the segments and finds its segment by binary search over their running starts (prefix[i]).
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_segments_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                             float* __restrict__ m, float* __restrict__ v,
+                                                             const long long* __restrict__ seg, const long long* __restrict__ prefix,
+                                                             int count, long long total, OptimArgs a, const int* __restrict__ step,
+                                                             long long set_stride) {
+  __shared__ float s_step_size, s_bc2_sqrt;
+  {
+    const long long o = (long long)blockIdx.y * set_stride;
+    p += o; g += o; m += o;
+    if (v != nullptr) v += o;
+  }
+  const int t0 = *step;
+  if (threadIdx.x == 0) optim_scalars(KIND, a, t0, s_step_size, s_bc2_sqrt);
+  __syncthreads();
+  const float step_size = s_step_size, bc2_sqrt = s_bc2_sqrt;
+  const bool first = t0 == 0;
+  const bool wd_on = a.wd != 0.f;
+  const long long n4 = total >> 2;
+  for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < n4; q += (long long)gridDim.x * blockDim.x) {
+    const long long j = q << 2;
+    int lo = 0, hi = count - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (prefix[mid] <= j) lo = mid; else hi = mid - 1;
+    }
+    const long long i = seg[3 * lo] + (j - prefix[lo]);
+    float4 pq = *reinterpret_cast<const float4*>(p + i);
+    const float4 gq = *reinterpret_cast<const float4*>(g + i);
+    float4 mq = make_float4(0.f, 0.f, 0.f, 0.f), vq = mq;
+    if (!first) {
+      if (KIND != 2 || a.momentum != 0.f) mq = *reinterpret_cast<const float4*>(m + i);
+      if (KIND != 2) vq = *reinterpret_cast<const float4*>(v + i);
+    }
+    const bool decay = wd_on && seg[3 * lo + 2] != 0;
+    optim_update<KIND>(pq.x, gq.x, mq.x, vq.x, decay, a, step_size, bc2_sqrt, first);
+    optim_update<KIND>(pq.y, gq.y, mq.y, vq.y, decay, a, step_size, bc2_sqrt, first);
+    optim_update<KIND>(pq.z, gq.z, mq.z, vq.z, decay, a, step_size, bc2_sqrt, first);
+    optim_update<KIND>(pq.w, gq.w, mq.w, vq.w, decay, a, step_size, bc2_sqrt, first);
+    *reinterpret_cast<float4*>(p + i) = pq;
+    if (KIND != 2 || a.momentum != 0.f) *reinterpret_cast<float4*>(m + i) = mq;
+    if (KIND != 2) *reinterpret_cast<float4*>(v + i) = vq;
+  }
+}
+
 __global__ void step_inc_kernel(int* step) { *step += 1; }
 
 // ------------------------------------------------------------------ mask + Dice counts
@@ -761,6 +809,45 @@ extern "C" int mmtta_optim_step_sets(const mmtta_optim_desc* d, float* p, const 
     MMTTA_CHECK(!(d->nesterov && (d->momentum <= 0.f || d->dampening != 0.f)), MMTTA_ERR_INVALID,
                 "optimizer: nesterov needs momentum > 0 and zero dampening (torch.optim.SGD raises the same)");
   return optim_launch(d->kind, p, g, m, v, n, n_decay, a, step, (hipStream_t)stream, sets, set_stride);
+}
+
+extern "C" int mmtta_optim_step_segments(const mmtta_optim_desc* d, float* p, const float* g, float* m, float* v,
+                                         const int64_t* segments, int count, int64_t total, int sets, int64_t set_stride,
+                                         int32_t* step, void* stream) {
+  MMTTA_CHECK(d != nullptr, MMTTA_ERR_INVALID, "optimizer: null desc");
+  OptimArgs a{d->lr, d->beta1, d->beta2, d->eps, d->weight_decay, d->momentum, d->dampening, d->nesterov};
+  const int kind = d->kind;
+  if (kind == MMTTA_OPTIM_SGD)
+    MMTTA_CHECK(!(d->nesterov && (d->momentum <= 0.f || d->dampening != 0.f)), MMTTA_ERR_INVALID,
+                "optimizer: nesterov needs momentum > 0 and zero dampening (torch.optim.SGD raises the same)");
+  MMTTA_CHECK(kind >= MMTTA_OPTIM_ADAM && kind <= MMTTA_OPTIM_SGD, MMTTA_ERR_INVALID, "optimizer: kind %d", kind);
+  MMTTA_CHECK(p && g && m && step && (kind == MMTTA_OPTIM_SGD || v != nullptr), MMTTA_ERR_INVALID, "optimizer: bad argument");
+  MMTTA_CHECK(sets >= 1 && set_stride >= 0 && set_stride % 4 == 0 && total >= 0 && total % 4 == 0 && count >= 0,
+              MMTTA_ERR_INVALID, "optimizer segments: %d sets, stride %lld, %lld elements", sets, (long long)set_stride,
+              (long long)total);
+  const bool al = ((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0;
+  MMTTA_CHECK(al, MMTTA_ERR_UNSUPPORTED, "optimizer: buffers must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (total > 0) {
+    MMTTA_CHECK(segments != nullptr && count > 0, MMTTA_ERR_INVALID, "optimizer segments: no table");
+    // the table is [count][3] followed by the [count] running starts (mmtta.h: the caller builds both)
+    const long long* seg = (const long long*)segments;
+    const long long* prefix = seg + 3 * (long long)count;
+    long long blocks = (total / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const dim3 grid((unsigned)blocks, (unsigned)sets), blk(256);
+    const long long ss = (long long)set_stride;
+    if (kind == MMTTA_OPTIM_ADAM)
+      hipLaunchKernelGGL(optim_segments_kernel<0>, grid, blk, 0, s, p, g, m, v, seg, prefix, count, (long long)total, a, step, ss);
+    else if (kind == MMTTA_OPTIM_ADAMW)
+      hipLaunchKernelGGL(optim_segments_kernel<1>, grid, blk, 0, s, p, g, m, v, seg, prefix, count, (long long)total, a, step, ss);
+    else
+      hipLaunchKernelGGL(optim_segments_kernel<2>, grid, blk, 0, s, p, g, m, v, seg, prefix, count, (long long)total, a, step, ss);
+    int st = launch_status("optimizer segments");
+    if (st) return st;
+  }
+  hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step);
+  return launch_status("optimizer step counter");
 }
 
 extern "C" int mmtta_mask_dice_counts(const mmtta_tensor* logits, const mmtta_tensor* label, float threshold, int64_t* counts,

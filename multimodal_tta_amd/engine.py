@@ -256,6 +256,16 @@ class ConvLayer:
         self.members = members if members is not None else [(weight, bias)]      # member 0 = (weight, bias)
         self.items_per_set = int(items_per_set)      # consecutive batch items sharing a set (the fusion layer: M)
         self.side_index = 0          # which side stream takes this layer's weight gradient (Runtime.make_conv)
+        # mmtta_update_target while the fused weight update owns this layer (Runtime.enable_fused_update): inside the
+        # adaptation step (Runtime.fused_active) its weight gradient then also steps the optimizer on its weight (and bias)
+        # and rewrites both packed images
+        self.upd_target = None
+
+    @property
+    def fused(self) -> bool:
+        """This backward's weight gradient of the layer is the fused update (only inside the adaptation plugin's step: any
+        other backward - the nn.Module facade, a trainer - computes plain gradients into the arena)."""
+        return self.upd_target is not None and self.rt is not None and self.rt.fused_active
 
     @property
     def frozen(self) -> bool:
@@ -287,6 +297,11 @@ class ConvLayer:
         return self.bias.data if self.bias is not None else None
 
     def _wgrad_launch(self, x, x_nl, dy, db, accumulate) -> None:
+        if self.fused:
+            if accumulate:
+                raise MmttaError("the fused weight update needs the whole weight gradient in one call")
+            self.op.wgrad_update(x, x_nl, dy, self.upd_target)
+            return
         self.op.wgrad(x, x_nl, dy, self.weight.grad, db, accumulate)
 
     def wgrad(self, x, x_nl, dy, accumulate=False) -> None:
@@ -353,6 +368,12 @@ class ConvolutionBlock(Block):
         if self.norm is not None:
             dy = self.rt.pool.cl((self.key, "dy"), *y.shape, dtype=dT.dtype)      # gradients keep their storage type
             self.norm.backward(self.rt.pool, self.key, dT, y, nl, dy, self.rt.training, grad_accumulate)
+        if self.conv.fused:
+            # the fused update rewrites the images this input gradient reads: it goes first
+            if need_dx:
+                self.conv.op.dgrad(dy, dx, accumulate, add=add)
+            self.conv.wgrad(x, x_nl, dy, grad_accumulate)
+            return
         self.conv.wgrad(x, x_nl, dy, grad_accumulate)
         if need_dx:
             self.conv.op.dgrad(dy, dx, accumulate, add=add)
@@ -407,6 +428,11 @@ class ResidualUnitBlock(Block):
                 unit.bwd(d, dx, accumulate=accumulate, need_dx=need_dx, grad_accumulate=grad_accumulate,
                          add=dout if (self.residual is None and need_dx) else None)
         if self.residual is not None:
+            if self.residual.fused:
+                if need_dx:
+                    self.residual.op.dgrad(dout, dx, accumulate=True)
+                self.residual.wgrad(x, x_nl, dout, grad_accumulate)
+                return
             self.residual.wgrad(x, x_nl, dout, grad_accumulate)
             if need_dx:
                 self.residual.op.dgrad(dout, dx, accumulate=True)
@@ -415,6 +441,9 @@ class ResidualUnitBlock(Block):
 # ----------------------------------------------------------------------------- runtime base
 class Runtime:
     """Owns the arena, the buffer pool and the conv layers of one model instance on one device."""
+    # every weight gradient of the runtime's backward goes through the blocks above (ConvolutionBlock / ResidualUnitBlock),
+    # which order a fused layer's input gradient before its update: runtimes that say so may use the fused weight update
+    supports_fused_update = False
 
     def __init__(self, device: torch.device, conv_dtype: int = ops.F32, group: int = 1):
         self.device = device
@@ -449,6 +478,10 @@ class Runtime:
         self.bn_stats_all: Optional[torch.Tensor] = None
         self.bn_nbt_all: Optional[torch.Tensor] = None
         self.bn_stats_total = 0
+        # the fused weight update (enable_fused_update): its layers, and the optimizer segments of everything else
+        self.fused_layers: List[ConvLayer] = []
+        self.fused_active = False      # set by the adaptation step around its backward: the fused layers update in place
+        self.leftover: Optional[Tuple[torch.Tensor, int, int]] = None      # (device table, count, total)
 
     def act_dtype(self, channels: int) -> torch.dtype:
         """Storage type of a forward activation with `channels` channels."""
@@ -598,13 +631,16 @@ class Runtime:
                         self.bn_nbt_all[g, nl.bn_index] if mod.num_batches_tracked is not None else None))
         return out
 
-    def pack_all(self) -> None:
+    def pack_all(self, fused_current: bool = False) -> None:
         """Refresh every packed weight image from the arena (one launch).  A frozen convolution (weight and bias both frozen)
         has ONE image per member for every replica; it is packed when the packers are built and again only when its weights
-        were written since (``refresh_frozen``), not on every step."""
+        were written since (``refresh_frozen``), not on every step.  ``fused_current``: the caller is the adaptation step
+        (or its final forward), whose fused layers' images were rewritten by their own update - they are repacked only when
+        their weights were written from outside; any other caller gets them repacked as every trainable layer is."""
         if getattr(self, "_packer_base", None) != self.arena.params.data_ptr():
-            step_items, frozen_items = [], []
+            step_items, frozen_items, fused_items = [], [], []
             self._frozen_params = []
+            self._fused_params = []
             seen = set()
             for c in self.convs:
                 if id(c.op) in seen:
@@ -613,9 +649,12 @@ class Runtime:
                 inner = len(c.members)
                 frozen = c.frozen
                 per_replica = c.op.n_sets == self.arena.replicas * inner and not frozen
-                items = frozen_items if frozen else step_items
+                owned = c.upd_target is not None
+                items = frozen_items if frozen else (fused_items if owned else step_items)
                 if frozen:
                     self._frozen_params += [r.param for wb in c.members for r in wb if r is not None]
+                if owned:
+                    self._fused_params += [r.param for wb in c.members for r in wb if r is not None]
                 for g in range(self.arena.replicas if per_replica else 1):
                     for m, (w, _) in enumerate(c.members):
                         wd = self.arena.replica_data(w, g)
@@ -624,28 +663,84 @@ class Runtime:
                             items.append((c.op.d_dgrad, wd, c.op.packed_image(True, g * inner + m)))
             self._packer = ops.BatchedPacker(step_items, self.device) if step_items else None
             self._packer_frozen = ops.BatchedPacker(frozen_items, self.device) if frozen_items else None
+            self._packer_fused = ops.BatchedPacker(fused_items, self.device) if fused_items else None
             self._frozen_version = None
+            self._fused_version = None
             self._packer_base = self.arena.params.data_ptr()
+        if not fused_current and self._packer_fused is not None:
+            self._packer_fused.run()
+            self._fused_version = self._frozen_key(self._fused_params)
         self.refresh_frozen()
         if self._packer is not None:
             self._packer.run()
 
-    def _frozen_key(self) -> Tuple:
+    def _frozen_key(self, params=None) -> Tuple:
         # writes through the arena's tensors (the episodic reset, replica views) bump the arena's version counter; writes
         # through an nn.Parameter (load_state_dict, an external optimizer, p.copy_) bump the Parameter's own counter, which
         # its `.data = arena view` adoption leaves separate.  Writes through `p.data` bypass both, as they bypass autograd.
-        return (self.arena.params_all._version,) + tuple(p._version for p in self._frozen_params)
+        # (The kernels of a step - the arena optimizer, the fused weight update - write through raw pointers: no bump.)
+        return (self.arena.params_all._version,) + tuple(p._version for p in (self._frozen_params if params is None else params))
 
     def refresh_frozen(self) -> None:
         """Repack the frozen convolutions' images if their weights were written since they were packed (one launch, on the
         current stream; nothing when they are current).  Callers replaying a captured step call it first: the step itself
         packs only the trainable layers."""
+        if getattr(self, "_packer_fused", None) is not None:
+            # the fused layers' images are rewritten by their update inside the step: repacked here only when their weights
+            # were written from outside (episodic reset, load_state_dict, a checkpoint, an external optimizer)
+            key = self._frozen_key(self._fused_params)
+            if key != self._fused_version:
+                self._packer_fused.run()
+                self._fused_version = key
         if getattr(self, "_packer_frozen", None) is None:
             return
         key = self._frozen_key()
         if key != self._frozen_version:
             self._packer_frozen.run()
             self._frozen_version = key
+
+    def enable_fused_update(self, spec: Optional["ops.OptimSpec"]) -> None:
+        """Hand the weight update of the wide 27-tap layers to their weight-gradient launch (mmtta_conv_wgrad_update_sets):
+        the slab reduction steps the optimizer (``spec``: Adam, AdamW or SGD) and rewrites both bf16 images in one pass, and
+        the arena optimizer keeps only the leftover segments (``leftover``).  ``None`` (or MMTTA_FUSED_UPDATE=0): every layer
+        takes the separate passes.  Taken by a layer with one member, one set per volume, a trainable weight (and bias)
+        and bare 27-tap bf16 images; its weight gradient must come in one call per step."""
+        ar = self.arena
+        for c in self.convs:
+            c.upd_target = None
+        self.fused_layers, self.leftover = [], None
+        self._packer_base = None                       # the packers are rebuilt with / without the fused layers
+        if (spec is None or ar is None or ar.n_train == 0 or not self.supports_fused_update
+                or not ops.fused_update_enabled()):
+            return
+        covered = []
+        row = lambda buf, r: buf[0, r.offset:r.offset + r.numel] if r is not None else None
+        for c in self.convs:
+            w, b = c.weight, c.bias
+            if (len(c.members) != 1 or c.items_per_set != 1 or not w.trainable or (b is not None and not b.trainable)
+                    or c.op.n_sets != ar.replicas or not c.op.plain_bf16_images()):
+                continue
+            bias_here = b is not None and not c.op.transposed        # ConvTranspose3d: bias gradient -> arena optimizer
+            c.upd_target = c.op.update_target(
+                spec, row(ar.params_all, w), row(ar.exp_avg_all, w), row(ar.exp_avg_sq_all, w),
+                row(ar.params_all, b) if bias_here else None, row(ar.exp_avg_all, b) if bias_here else None,
+                row(ar.exp_avg_sq_all, b) if bias_here else None, row(ar.grads_all, b) if not bias_here else None,
+                w.group == GROUP_DECAY, b is not None and b.group == GROUP_DECAY, ar.step)
+            self.fused_layers.append(c)
+            covered.append((w.offset, w.offset + (w.numel + 3) // 4 * 4))
+            if bias_here:
+                covered.append((b.offset, b.offset + (b.numel + 3) // 4 * 4))
+        if not self.fused_layers:
+            return
+        segs, pos = [], 0
+        for a, e in sorted(covered) + [(ar.n_train, ar.n_train)]:
+            for lo, hi in ((pos, min(a, ar.n_decay)), (max(pos, ar.n_decay), a)):
+                if hi > lo:
+                    segs.append((lo, hi - lo, lo < ar.n_decay))
+            pos = max(pos, e)
+        table, total = ops.optim_segments_table(segs, self.device) if segs else (torch.zeros(1, dtype=torch.int64,
+                                                                                              device=self.device), 0)
+        self.leftover = (table, len(segs), total)
 
     def snapshot_buffers(self) -> None:
         """Source values of the running statistics (BatchNorm), restored with the weights per volume."""

@@ -26,6 +26,7 @@ from .containers import Convolution, ResidualUnit, Seq, SkipConnection
 
 class UNetRuntime(Runtime):
     """Flat execution plan of the recursive ``down / skip(sub) / up`` structure."""
+    supports_fused_update = True         # every weight gradient goes through the blocks (engine.Runtime.enable_fused_update)
 
     def __init__(self, model: "UNet", device: torch.device):
         super().__init__(device, model.conv_dtype, group=getattr(model, "group", 1))

@@ -541,6 +541,50 @@ class ConvOp:
                          (self.io_bytes(x, dy, dw) + (nsets - 1) * dw.numel() * 4.0) * PROFILER.reps)
 
 
+    def plain_bf16_images(self) -> bool:
+        """Both images are bare 27-tap bf16 images (what the fused weight update writes): bf16 operands, K >= 16 each way."""
+        if self.k != 3 or int(self.d_fwd.dtype) != BF16 or min(self.cin, self.cout) < 16:
+            return False
+        img = 27 * ((self.cin + 31) // 32 * 32) * ((self.cout + 31) // 32 * 32) * 2
+        return self.nb_fwd == img and self.nb_dgrad == img
+
+    def update_target(self, spec: "OptimSpec", w_p, w_m, w_v, b_p, b_m, b_v, b_grad, w_decay: bool, b_decay: bool,
+                      step: torch.Tensor) -> _lib.UpdateTarget:
+        """mmtta_update_target of this op's parameter set 0 (tensors: the first element of set 0's slices)."""
+        t = _lib.UpdateTarget()
+        t.optim = spec.struct()
+        t.w_p, t.w_m, t.w_v = ptr(w_p), ptr(w_m), ptr(w_v)
+        t.b_p, t.b_m, t.b_v, t.b_grad = ptr(b_p), ptr(b_m), ptr(b_v), ptr(b_grad)
+        t.image[0] = ptr(self.packed_image(False, 0))
+        t.image[1] = ptr(self.packed_image(True, 0)) if self.need_dgrad else None
+        pair = self.sets_grouped
+        for i in range(2):
+            t.image_outer[i] = int(pair[i].packed_outer) if pair is not None else 0
+            t.image_inner[i] = int(pair[i].packed_inner) if pair is not None else 0
+        t.step = ptr(step)
+        t.w_decay, t.b_decay = int(bool(w_decay)), int(bool(b_decay))
+        return t
+
+    def wgrad_update(self, x: torch.Tensor, x_nl: Optional[NL], dy: torch.Tensor, target: _lib.UpdateTarget) -> None:
+        """Weight gradient + optimizer step + repack of both images (mmtta_conv_wgrad_update_sets): the layer's parameters,
+        moments and images of every set in the batch are updated in place; the step counter is read, not advanced."""
+        lib = _lib.load()
+        tx, tdy = desc_cl(x), desc_cl(dy)
+        sets = self._sets(self.d_fwd)
+        sref = C.byref(sets) if sets is not None else None
+        need = lib.mmtta_conv_wgrad_workspace_bytes_sets(C.byref(self.d_fwd), C.byref(tx), C.byref(tdy), sref)
+        if need < 0:
+            check(-1, "conv_wgrad_workspace_bytes")
+        ws = Workspace.get(int(need), x.device)
+        nls, nlr = _nl_ref(x_nl)
+        check(lib.mmtta_conv_wgrad_update_sets(C.byref(self.d_fwd), C.byref(tx), nlr, C.byref(tdy), C.byref(target), ptr(ws),
+                                               int(need), sref, stream_ptr()), "conv_wgrad_update")
+
+
+def fused_update_enabled() -> bool:
+    """The fused weight update is on (MMTTA_FUSED_UPDATE=0 in the environment switches it off)."""
+    return bool(_lib.load().mmtta_fused_update_enabled())
+
 
 class BatchedPacker:
     """Every packed weight image of a model refreshed by ONE kernel launch (the table is built once: parameter
@@ -832,6 +876,32 @@ def optim_step_sets(spec: OptimSpec, p: torch.Tensor, g: torch.Tensor, m: torch.
     d = spec.struct()
     check(_lib.load().mmtta_optim_step_sets(C.byref(d), ptr(p), ptr(g), ptr(m), ptr(v), int(n), int(n_decay), int(sets),
                                             int(p.shape[1]), ptr(step), stream_ptr()), "optim_step_sets")
+
+
+def optim_segments_table(segments: Sequence[Tuple[int, int, bool]], device) -> Tuple[torch.Tensor, int]:
+    """Device table of mmtta_optim_step_segments: [count][3] (start, length, decay) then the [count] running starts."""
+    rows, starts, run = [], [], 0
+    for a, n, dec in segments:
+        if a % 4 or n % 4 or n <= 0:
+            raise MmttaError(f"optimizer segment ({a}, {n}) is not a positive run of whole 16-byte groups")
+        rows += [int(a), int(n), 1 if dec else 0]
+        starts.append(run)
+        run += int(n)
+    return torch.tensor(rows + starts, dtype=torch.int64).to(device), run
+
+
+def optim_step_segments(spec: OptimSpec, p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: Optional[torch.Tensor],
+                        table: torch.Tensor, count: int, total: int, sets: int, step: torch.Tensor) -> None:
+    """optim_step_sets over the segments of ``table`` (optim_segments_table) of the first ``sets`` replicas, then the step
+    counter advances once."""
+    for t in (p, g, m) + ((v,) if v is not None else ()):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape != p.shape:
+            raise MmttaError("optimizer: p, g, m, v must be contiguous fp32 [replicas, total] of equal shape")
+    if not 1 <= sets <= p.shape[0]:
+        raise MmttaError(f"optimizer: {sets} sets do not fit {tuple(p.shape)}")
+    d = spec.struct()
+    check(_lib.load().mmtta_optim_step_segments(C.byref(d), ptr(p), ptr(g), ptr(m), ptr(v), ptr(table), int(count), int(total),
+                                                int(sets), int(p.shape[1]), ptr(step), stream_ptr()), "optim_step_segments")
 
 
 def _desc_any(t: torch.Tensor, channels_last: bool):

@@ -33,6 +33,7 @@ from .tta import EntropyMinimizationTTA, select_params
 class SharpnessAwareReliableTTA(EntropyMinimizationTTA):
     """``method.sar.e_margin`` (fraction of ln K, default 0.4) and ``method.sar.rho`` (SAM radius, default 0.05), the SAR
     paper's defaults; the base optimizer is ``training.optimizer`` exactly as for ``entmin_tta``."""
+    fused_update = False     # the ascent needs the whole gradient (its norm) before any weight moves
 
     def __init__(self, config: Any = None):
         super().__init__(config)

@@ -29,6 +29,7 @@ from .tta import EntropyMinimizationTTA, select_params
 class SupervisedSegStep(EntropyMinimizationTTA):
     """Shares construction (optimizer hyper-parameters, parameter groups, precision) with the adaptation plugin;
     only the objective differs."""
+    fused_update = False     # the supervised step keeps the separate weight-gradient, optimizer and repack passes
 
     def __init__(self, config: Any = None):
         super().__init__(config)

@@ -67,6 +67,9 @@ class EntropyMinimizationTTA:
     """Construct with the ROOT config (like the reference's evaluation strategies,
     src/core/experiment_manager.py:369-370), then ``setup(model, device)`` once and
     ``adapt_volume(x)`` per test volume."""
+    # the wide 27-tap layers update inside their weight-gradient launch (engine.Runtime.enable_fused_update); a subclass whose
+    # step needs the whole gradient before any weight moves (SAR: the global gradient norm) switches it off
+    fused_update = True
 
     def __init__(self, config: Any = None):
         cfg = as_cfg(config)
@@ -170,6 +173,8 @@ class EntropyMinimizationTTA:
         self.rt.n_side = max(1, self.side_streams)
         self.rt.arena.snapshot_source()
         self.rt.snapshot_buffers()
+        # the wide 27-tap layers step their optimizer and repack their images inside their weight-gradient launch
+        self.rt.enable_fused_update(self.optim if self.fused_update else None)
         self._graphs.clear()
         return self
 
@@ -180,7 +185,7 @@ class EntropyMinimizationTTA:
         rt.training = True
         rt.use_sets = rt.group > 1          # batch item g reads / writes parameter replica g
         try:
-            rt.pack_all()
+            rt.pack_all(fused_current=True)
             logits = rt.forward_cl(x_cl) if present is None else rt.forward_cl(x_cl, present=present)
             n, d, h, w, r = logits.shape
             # (the categorical objective writes fp32 only)
@@ -196,14 +201,26 @@ class EntropyMinimizationTTA:
                 loss = rt.pool.flat("ent_loss", 1)
                 ops.entropy_loss(logits, dlogits, partial, loss, softmax=self.softmax)
             if ar.n_train > 0:
-                rt.run_backward(dlogits)
-                self.optimizer_step(n)
+                fused = bool(rt.fused_layers)
+                rt.fused_active = fused         # only this backward updates the fused layers in place
+                try:
+                    rt.run_backward(dlogits)
+                finally:
+                    rt.fused_active = False
+                self.optimizer_step(n, fused=fused)
         finally:
             rt.use_sets = False
 
-    def optimizer_step(self, volumes: int = 1) -> None:
-        """The arena optimizer: ONE launch over [decay | no-decay] of every replica in use (+ the device step counter)."""
+    def optimizer_step(self, volumes: int = 1, fused: bool = False) -> None:
+        """The arena optimizer: ONE launch over [decay | no-decay] of every replica in use (+ the device step counter).
+        ``fused``: the backward before it was the fused update of ``rt.fused_layers``; only the leftover segments remain."""
         ar = self.rt.arena
+        if fused:
+            # the fused layers were updated by their weight-gradient launches: the segments of everything else
+            table, count, total = self.rt.leftover
+            ops.optim_step_segments(self.optim, ar.params_all, ar.grads_all, ar.exp_avg_all, ar.exp_avg_sq_all, table, count,
+                                    total, min(volumes, ar.replicas), ar.step)
+            return
         if ar.replicas > 1:
             ops.optim_step_sets(self.optim, ar.params_all, ar.grads_all, ar.exp_avg_all, ar.exp_avg_sq_all, ar.n_train, ar.n_decay,
                                 min(volumes, ar.replicas), ar.step)
@@ -305,7 +322,7 @@ class EntropyMinimizationTTA:
         ops.Workspace.lane = self.lane
         rt.use_sets = grouped
         try:
-            rt.pack_all()
+            rt.pack_all(fused_current=True)
             logits_cl = (rt.forward_cl(x_cl, present=base_present) if wants_present else rt.forward_cl(x_cl))
         finally:
             rt.use_sets = False
