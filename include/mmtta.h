@@ -476,6 +476,42 @@ int mmtta_entropy_filtered_items(const mmtta_tensor* logits, int softmax, float 
                                  uint8_t* keep_out, const mmtta_tensor* dlogits, double* partial, float* loss,
                                  int64_t* kept, void* stream);
 
+/* ---- MEMO (Zhang, Levine, Finn, NeurIPS 2022) over the mirrored views of a volume.  A batch of G volumes x V views is
+ * [G * V, D, H, W, C], item g * V + v = view v of volume g = the volume mirrored along the axes of mask view_axes[v]
+ * (bit 0 = W, bit 1 = H, bit 2 = D; view_axes[0] must be 0: view 0 is the volume itself).  `views` is 1, 2, 4 or 8;
+ * `view_axes` is a HOST array of `views` masks, read at launch.  Mirroring is exact on the voxel grid and its own inverse,
+ * so every kernel below addresses a voxel of the volume's own frame and its image in each view directly.
+ *
+ * mmtta_mirror_views: y[g * V + v] = x[g] mirrored along view v's axes.  x [G, D, H, W, C] and y [G * V, D, H, W, C]
+ *   channels-last with dense rows of one width, fp32 or bf16 (the 8-byte voxel rows of the network input included); a
+ *   voxel's whole row moves intact, pad lanes included (y must own them).  Bit-exact.
+ *
+ * mmtta_memo_loss_items: every volume g is its own objective (as in mmtta_entropy_loss_items).  With u_v = view v's logits
+ *   brought back to the volume's frame:
+ *     softmax == 0:  pbar = 1/V sum_v sigmoid(u_v);   loss[g] = mean over (voxel, region) of H_bern(pbar)
+ *     softmax != 0:  pbar = 1/V sum_v softmax_r(u_v); loss[g] = mean over voxel of -sum_r pbar_r log pbar_r
+ *   dlogits of view v = dloss[g]/dlogits, written in view v's own frame.  One streaming pass (a thread owns a voxel of
+ *   the volume's frame, reads its V rows and writes its V gradient rows) and the per-volume finish.  Loss and gradient
+ *   are finite for every finite fp32 logit: 1 - pbar is never formed by subtraction and x log x is taken at
+ *   max(x, smallest normal) (softmax != 0: log pbar is a log-sum-exp over the views' log-softmaxes).  Storages as mmtta_entropy_loss_items: fp32 logits; fp32 gradients, or - softmax == 0, <= 4
+ *   channels in dense 4-channel voxel rows - bf16.  G volumes in one call are bit for bit G calls on one volume each.
+ *   views == 1 (nothing to mirror, the marginal is the one prediction) IS mmtta_entropy_loss_items: the same kernels, the
+ *   same bits, and mmtta_memo_partials(logits, 1) == mmtta_entropy_partials_items(logits).
+ *   partial  fp64 [mmtta_memo_partials(logits, views)] scratch; loss  fp32 [G]
+ *
+ * mmtta_memo_ensemble: out [G, D, H, W, C] fp32 = logit(pbar) (softmax == 0; +-87.3365 = -ln(smallest normal) where pbar
+ *   or 1 - pbar underflows; views == 1 returns the logits) or log pbar (softmax != 0), in the volume's frame.
+ *
+ * Bad arguments (null pointers, views outside {1, 2, 4, 8}, N no multiple of views, a bad mask, shape mismatches) are
+ * MMTTA_ERR_INVALID, storages without a kernel (and more than 65535 volumes in one call) MMTTA_ERR_UNSUPPORTED, both before
+ * anything is launched. */
+int mmtta_mirror_views(const mmtta_tensor* x, const mmtta_tensor* y, int views, const int32_t* view_axes, void* stream);
+int64_t mmtta_memo_partials(const mmtta_tensor* logits, int views);
+int mmtta_memo_loss_items(const mmtta_tensor* logits, int softmax, int views, const int32_t* view_axes,
+                          const mmtta_tensor* dlogits, double* partial, float* loss, void* stream);
+int mmtta_memo_ensemble(const mmtta_tensor* logits, int softmax, int views, const int32_t* view_axes,
+                        const mmtta_tensor* out, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

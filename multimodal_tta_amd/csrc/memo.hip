@@ -1,0 +1,493 @@
+// MEMO objective (Zhang, Levine, Finn, NeurIPS 2022) over the mirrored views of a volume (gfx950): the entropy of the
+// MARGINAL prediction of V views, its gradient for every view, the view layout of the staged input and the ensemble of
+// the views' predictions.  See include/mmtta.h for the contract of the four entry points.
+//
+// Batch layout everywhere: [G * V, D, H, W, R], item g * V + v = view v of volume g.  View v is the volume mirrored along
+// the axes of mask view_axes[v] (bit 0 = W, 1 = H, 2 = D); mirroring is an involution on the voxel grid, so voxel
+// (z, y, x) of the volume's own frame is voxel (z', y', x') of view v with x' = W-1-x where the mask says so.  A thread owns
+// a voxel of the volume's frame and visits its V images.  Inside a row of W the order of voxels reverses, but the 64 voxels
+// of a wavefront still cover one contiguous segment of every view: the accesses stay coalesced.
+#include "common.h"
+
+namespace mmtta {
+
+constexpr int MEMO_MAX_BLOCKS = 2048;      // block partials per volume (the entropy objective's figure)
+constexpr int MEMO_MAX_R = 16;             // classes of the categorical path (ENT_MAX_R of loss_optim_metric.hip)
+constexpr int MEMO_MAX_V = 8;
+constexpr int MEMO_MAX_GRID_Y = 65535;     // gridDim.y carries the volume (the output item of the view layout)
+constexpr float MEMO_TINY = 1.17549435e-38f;   // smallest normal fp32: v_log_f32 and x log x stay finite from here up
+
+struct MemoViews {
+  int v;
+  int axes[MEMO_MAX_V];
+};
+
+__device__ __forceinline__ double memo_block_sum(double v, double* sh) {
+  v = wave_sum_d(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
+  return t;  // valid on thread 0
+}
+
+// coordinates of linear voxel i (32-bit: the host checks D*H*W*ldc < 2^31) and of its mirror image
+struct MemoVox {
+  unsigned x, y, z, xm, ym, zm;
+};
+__device__ __forceinline__ MemoVox memo_vox(unsigned i, unsigned D, unsigned H, unsigned W) {
+  MemoVox p;
+  const unsigned t = i / W;
+  p.x = i - t * W;
+  p.z = t / H;
+  p.y = t - p.z * H;
+  p.xm = W - 1 - p.x; p.ym = H - 1 - p.y; p.zm = D - 1 - p.z;
+  return p;
+}
+// linear voxel index of the image of `p` in a view with mirror mask `m` (wave-uniform selects)
+__device__ __forceinline__ unsigned memo_image(const MemoVox& p, int m, unsigned H, unsigned W) {
+  const unsigned xx = (m & 1) ? p.xm : p.x, yy = (m & 2) ? p.ym : p.y, zz = (m & 4) ? p.zm : p.z;
+  return (zz * H + yy) * W + xx;
+}
+
+// sigmoid(t), sigmoid(-t) and their product, none formed by subtraction: v_exp_f32 / v_rcp_f32 as the entropy fast path
+__device__ __forceinline__ void memo_sigmoid_terms(float t, float& p, float& q, float& pq) {
+  const float e = __builtin_amdgcn_exp2f(-fabsf(t) * 1.4426950408889634f);   // exp(-|t|)
+  const float r = __builtin_amdgcn_rcpf(1.f + e);
+  const float er = e * r;
+  p = t >= 0.f ? r : er;
+  q = t >= 0.f ? er : r;
+  pq = er * r;
+}
+__device__ __forceinline__ float memo_ln(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }   // x normal
+// log p and log q of a complementary pair (p + q = 1 up to rounding), finite for p or q = 0: the log of the smaller one is
+// taken at max(s, smallest normal) - s log s is below 1e-35 there - and the log of the larger one is log1p(-s), the 4-term
+// series below 2^-6 (relative error < 2e-8) and log(1 - s) above, as the entropy fast path takes its log1p
+__device__ __forceinline__ void memo_pair_logs(float p, float q, float& lp, float& lq) {
+  const float s = fminf(p, q);
+  const float ls = memo_ln(fmaxf(s, MEMO_TINY));
+  const float series = -s * fmaf(s, fmaf(s, fmaf(s, 0.25f, 0.33333334f), 0.5f), 1.f);
+  const float lb = s < 0.015625f ? series : memo_ln(1.f - s);
+  const bool pbig = p >= q;
+  lp = pbig ? lb : ls;
+  lq = pbig ? ls : lb;
+}
+
+// ------------------------------------------------------------------ marginal entropy, Bernoulli head
+// Fast path: <= 4 regions in dense 16-byte voxel rows.  Per view and voxel one 16-byte load and one 16- / 8-byte store
+// (the gradient tensor owns its pad lane), two 32-bit divisions per voxel, ~2 logs per (voxel, region) and one exp per
+// view.  gridDim.y = volume; the block partials and the scale of a volume are those of a call on that volume alone.
+template <int V, bool OBF>
+__global__ __launch_bounds__(256) void memo_bernoulli_vec_kernel(const float* __restrict__ z, float* __restrict__ dz,
+                                                                 long long zsn, long long dzsn, int C, unsigned D, unsigned H,
+                                                                 unsigned W, MemoViews mv, double* partial, float inv_count) {
+  __shared__ double sh[4];
+  const long long item0 = (long long)blockIdx.y * V;
+  partial += (long long)blockIdx.y * gridDim.x;
+  const unsigned dhw = D * H * W;
+  const float inv_v = 1.f / (float)V;
+  double acc = 0.0;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < dhw; i += gridDim.x * 256u) {
+    const MemoVox pos = memo_vox(i, D, H, W);
+    unsigned off[V];
+    float4 t4[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      off[v] = memo_image(pos, mv.axes[v], H, W) * 4u;
+      t4[v] = *reinterpret_cast<const float4*>(z + (item0 + v) * zsn + off[v]);
+    }
+    float pq[V][4];
+    float f[4] = {0.f, 0.f, 0.f, 0.f};
+    float h = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (c < C) {
+        float ps = 0.f, qs = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+          const float t = c == 0 ? t4[v].x : (c == 1 ? t4[v].y : (c == 2 ? t4[v].z : t4[v].w));
+          float p, q;
+          memo_sigmoid_terms(t, p, q, pq[v][c]);
+          ps += p; qs += q;
+        }
+        const float pbar = ps * inv_v, qbar = qs * inv_v;
+        float lp, lq;
+        memo_pair_logs(pbar, qbar, lp, lq);
+        h -= fmaf(pbar, lp, qbar * lq);
+        f[c] = (lq - lp) * inv_count;
+      } else {
+#pragma unroll
+        for (int v = 0; v < V; ++v) pq[v][c] = 0.f;
+      }
+    }
+    acc += (double)h;
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      float* gb = OBF ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(dz) + (item0 + v) * dzsn)
+                      : dz + (item0 + v) * dzsn;
+      st4_any(gb, off[v], make_float4(f[0] * pq[v][0], f[1] * pq[v][1], f[2] * pq[v][2], f[3] * pq[v][3]), OBF);
+    }
+  }
+  const double t = memo_block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+// Generic path: any R, any row stride, fp32 gradients; a thread owns a (voxel, region) pair.
+__global__ __launch_bounds__(256) void memo_bernoulli_kernel(TV z, TV dz, MemoViews mv, double* partial, float inv_count) {
+  __shared__ double sh[4];
+  const int V = mv.v;
+  const long long item0 = (long long)blockIdx.y * V;
+  partial += (long long)blockIdx.y * gridDim.x;
+  const unsigned C = z.c, D = z.d, H = z.h, W = z.w;
+  const unsigned total = D * H * W * C;
+  const float inv_v = 1.f / (float)V;
+  double acc = 0.0;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const unsigned vox = i / C, c = i - vox * C;
+    const MemoVox pos = memo_vox(vox, D, H, W);
+    float pq[MEMO_MAX_V];
+    float ps = 0.f, qs = 0.f;
+#pragma unroll
+    for (int v = 0; v < MEMO_MAX_V; ++v) {
+      if (v < V) {
+        const int m = mv.axes[v];
+        const long long a = vox_addr(z, (int)(item0 + v), (m & 4) ? pos.zm : pos.z, (m & 2) ? pos.ym : pos.y, (m & 1) ? pos.xm : pos.x);
+        float p, q;
+        memo_sigmoid_terms(z.p[a + c], p, q, pq[v]);
+        ps += p; qs += q;
+      }
+    }
+    const float pbar = ps * inv_v, qbar = qs * inv_v;
+    float lp, lq;
+    memo_pair_logs(pbar, qbar, lp, lq);
+    acc += (double)(-fmaf(pbar, lp, qbar * lq));
+    const float f = (lq - lp) * inv_count;
+#pragma unroll
+    for (int v = 0; v < MEMO_MAX_V; ++v) {
+      if (v < V) {
+        const int m = mv.axes[v];
+        const long long a = vox_addr(dz, (int)(item0 + v), (m & 4) ? pos.zm : pos.z, (m & 2) ? pos.ym : pos.y, (m & 1) ? pos.xm : pos.x);
+        dz.p[a + c] = f * pq[v];
+      }
+    }
+  }
+  const double t = memo_block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+// ------------------------------------------------------------------ marginal entropy, categorical head
+// log softmax of one voxel row into lp[0..R), finite for every finite row (a difference that overflows is held at -3e38)
+__device__ __forceinline__ void memo_log_softmax_row(const float* zp, int R, float (&lp)[MEMO_MAX_R]) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < MEMO_MAX_R; ++r)
+    if (r < R) { lp[r] = zp[r]; m = fmaxf(m, lp[r]); }
+  float se = 0.f;
+#pragma unroll
+  for (int r = 0; r < MEMO_MAX_R; ++r)
+    if (r < R) se += expf(lp[r] - m);
+  // (t - m) - log(se), not t - (m + log(se)): at logits of 1e4 the sum m + log(se) would round log(se) to 1e-3
+  const float lg = logf(se);             // se >= 1: the maximum contributes exp(0)
+#pragma unroll
+  for (int r = 0; r < MEMO_MAX_R; ++r)
+    if (r < R) lp[r] = fmaxf((lp[r] - m) - lg, -3e38f);
+}
+// log pbar_r = logsumexp_v(log softmax_r(u_v)) - log V, accumulated view by view (running maximum mx, scaled sum sm):
+// the log-domain form keeps the relative accuracy of small probabilities, and one view gives its log softmax back exactly
+__device__ __forceinline__ void memo_lse_add(float lp, bool first, float& mx, float& sm) {
+  if (first) { mx = lp; sm = 1.f; return; }
+  const float nm = fmaxf(mx, lp);
+  sm = sm * expf(mx - nm) + expf(lp - nm);
+  mx = nm;
+}
+__device__ __forceinline__ const float* memo_row(const TV& z, long long item, const MemoVox& pos, int m) {
+  return z.p + vox_addr(z, (int)item, (m & 4) ? pos.zm : pos.z, (m & 2) ? pos.ym : pos.y, (m & 1) ? pos.xm : pos.x);
+}
+
+// A thread owns a voxel.  Two sweeps over the views (the second one re-reads the rows through the cache): the marginal
+// needs every view before any gradient can be written, and V x R probabilities do not fit the register file.
+__global__ __launch_bounds__(256) void memo_categorical_kernel(TV z, TV dz, MemoViews mv, double* partial, float inv_count) {
+  __shared__ double sh[4];
+  const int V = mv.v, R = z.c;
+  const long long item0 = (long long)blockIdx.y * V;
+  partial += (long long)blockIdx.y * gridDim.x;
+  const unsigned D = z.d, H = z.h, W = z.w;
+  const unsigned total = D * H * W;
+  const float log_v = logf((float)V);
+  double acc = 0.0;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const MemoVox pos = memo_vox(i, D, H, W);
+    float lpb[MEMO_MAX_R], sm[MEMO_MAX_R], lp[MEMO_MAX_R];
+    for (int v = 0; v < V; ++v) {
+      memo_log_softmax_row(memo_row(z, item0 + v, pos, mv.axes[v]), R, lp);
+#pragma unroll
+      for (int r = 0; r < MEMO_MAX_R; ++r)
+        if (r < R) memo_lse_add(lp[r], v == 0, lpb[r], sm[r]);
+    }
+    float h = 0.f;
+#pragma unroll
+    for (int r = 0; r < MEMO_MAX_R; ++r)
+      if (r < R) {
+        lpb[r] = lpb[r] + logf(sm[r]) - log_v;
+        h -= expf(lpb[r]) * lpb[r];
+      }
+    acc += (double)h;
+    for (int v = 0; v < V; ++v) {
+      memo_log_softmax_row(memo_row(z, item0 + v, pos, mv.axes[v]), R, lp);
+      float s = 0.f;
+#pragma unroll
+      for (int r = 0; r < MEMO_MAX_R; ++r)
+        if (r < R) { lp[r] = expf(lp[r]); s = fmaf(lp[r], lpb[r], s); }
+      float* gp = const_cast<float*>(memo_row(dz, item0 + v, pos, mv.axes[v]));
+#pragma unroll
+      for (int r = 0; r < MEMO_MAX_R; ++r)
+        if (r < R) gp[r] = lp[r] * (s - lpb[r]) * inv_count;
+    }
+  }
+  const double t = memo_block_sum(acc, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+__global__ __launch_bounds__(64) void memo_finish_kernel(const double* partial, int nblocks, double inv_count, float* loss) {
+  partial += (long long)blockIdx.x * nblocks;      // one workgroup per volume
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nblocks; i += 64) s += partial[i];
+  s = wave_sum_d(s);
+  if (threadIdx.x == 0) loss[blockIdx.x] = (float)(s * inv_count);
+}
+
+// ------------------------------------------------------------------ ensemble of the views' predictions
+// out[g] = logit(pbar) (Bernoulli; a thread per (voxel, region)) or log pbar (categorical; a thread per voxel; log-sum-exp over the views) in the
+// volume's frame.  Where pbar or qbar underflows the logit is +-87.3365 (-ln of the smallest normal: as far as the fp32
+// sigmoid inverts).  V = 1: the Bernoulli ensemble is the logits themselves.
+__global__ __launch_bounds__(256) void memo_ensemble_bernoulli_kernel(TV z, TV out, MemoViews mv) {
+  const int V = mv.v;
+  const long long item0 = (long long)blockIdx.y * V;
+  const unsigned C = z.c, D = z.d, H = z.h, W = z.w;
+  const unsigned total = D * H * W * C;
+  const float inv_v = 1.f / (float)V;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const unsigned vox = i / C, c = i - vox * C;
+    const MemoVox pos = memo_vox(vox, D, H, W);
+    float ps = 0.f, qs = 0.f, t0 = 0.f;
+#pragma unroll
+    for (int v = 0; v < MEMO_MAX_V; ++v) {
+      if (v < V) {
+        const int m = mv.axes[v];
+        const float t = z.p[vox_addr(z, (int)(item0 + v), (m & 4) ? pos.zm : pos.z, (m & 2) ? pos.ym : pos.y, (m & 1) ? pos.xm : pos.x) + c];
+        if (v == 0) t0 = t;
+        float p, q, pq;
+        memo_sigmoid_terms(t, p, q, pq);
+        ps += p; qs += q;
+      }
+    }
+    float lp, lq;
+    memo_pair_logs(ps * inv_v, qs * inv_v, lp, lq);
+    out.p[vox_addr(out, (int)blockIdx.y, pos.z, pos.y, pos.x) + c] = V == 1 ? t0 : lp - lq;
+  }
+}
+
+__global__ __launch_bounds__(256) void memo_ensemble_categorical_kernel(TV z, TV out, MemoViews mv) {
+  const int V = mv.v, R = z.c;
+  const long long item0 = (long long)blockIdx.y * V;
+  const unsigned D = z.d, H = z.h, W = z.w;
+  const unsigned total = D * H * W;
+  const float log_v = logf((float)V);
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const MemoVox pos = memo_vox(i, D, H, W);
+    float lpb[MEMO_MAX_R], sm[MEMO_MAX_R], lp[MEMO_MAX_R];
+    for (int v = 0; v < V; ++v) {
+      memo_log_softmax_row(memo_row(z, item0 + v, pos, mv.axes[v]), R, lp);
+#pragma unroll
+      for (int r = 0; r < MEMO_MAX_R; ++r)
+        if (r < R) memo_lse_add(lp[r], v == 0, lpb[r], sm[r]);
+    }
+    float* op = out.p + vox_addr(out, (int)blockIdx.y, pos.z, pos.y, pos.x);
+#pragma unroll
+    for (int r = 0; r < MEMO_MAX_R; ++r)
+      if (r < R) op[r] = lpb[r] + logf(sm[r]) - log_v;
+  }
+}
+
+// ------------------------------------------------------------------ the mirrored views of the staged input
+// y[g * V + v] = x[g] mirrored along the axes of view v; a voxel's whole row (pad lanes included) moves as `upr` units of
+// type T.  A thread owns a unit of the OUTPUT; gridDim.y = output item.  Once per volume: index arithmetic is not tuned.
+template <class T>
+__global__ __launch_bounds__(256) void memo_mirror_kernel(const T* __restrict__ x, T* __restrict__ y, long long xsn, long long ysn,
+                                                          unsigned upr, unsigned D, unsigned H, unsigned W, MemoViews mv) {
+  const int item = blockIdx.y, g = item / mv.v, m = mv.axes[item - g * mv.v];
+  const unsigned total = D * H * W * upr;
+  const T* xb = x + (long long)g * xsn;
+  T* yb = y + (long long)item * ysn;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const unsigned vox = i / upr, u = i - vox * upr;
+    const MemoVox pos = memo_vox(vox, D, H, W);
+    yb[i] = xb[memo_image(pos, m, H, W) * upr + u];
+  }
+}
+
+static int memo_blocks(const mmtta_tensor* z) {
+  // the figure of mmtta_entropy_partials for ONE item, for every head: it counts (voxel, region) pairs, so the kernels that
+  // give a thread a whole voxel get up to c times the workgroups they have voxels for below the cap - those write a zero
+  // partial - and mmtta_memo_partials is one formula
+  const long long total = (long long)z->d * z->h * z->w * z->c;
+  long long b = (total + 255) / 256;
+  if (b < 1) b = 1;
+  if (b > MEMO_MAX_BLOCKS) b = MEMO_MAX_BLOCKS;
+  return (int)b;
+}
+
+static int memo_views_check(const char* what, int views, const int32_t* view_axes, int n, MemoViews& mv) {
+  MMTTA_CHECK(views == 1 || views == 2 || views == 4 || views == 8, MMTTA_ERR_INVALID, "%s: views = %d (1, 2, 4 or 8)", what, views);
+  MMTTA_CHECK(view_axes != nullptr, MMTTA_ERR_INVALID, "%s: null argument (view_axes)", what);
+  MMTTA_CHECK(view_axes[0] == 0, MMTTA_ERR_INVALID, "%s: view_axes[0] = %d, view 0 is the unmirrored volume", what, view_axes[0]);
+  mv.v = views;
+  for (int v = 0; v < MEMO_MAX_V; ++v) {
+    mv.axes[v] = v < views ? view_axes[v] : 0;
+    MMTTA_CHECK(mv.axes[v] >= 0 && mv.axes[v] <= 7, MMTTA_ERR_INVALID, "%s: view_axes[%d] = %d (bit 0 = W, 1 = H, 2 = D)", what, v, mv.axes[v]);
+  }
+  MMTTA_CHECK(n >= views && n % views == 0, MMTTA_ERR_INVALID, "%s: batch %d is no multiple of views %d", what, n, views);
+  return MMTTA_OK;
+}
+
+static bool memo_dense16(const mmtta_tensor* t) {
+  return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
+         ((uintptr_t)t->ptr) % 16 == 0;
+}
+
+// every offset inside one item fits 31 bits (the kernels index voxels with 32-bit arithmetic)
+static bool memo_small_item(const mmtta_tensor* t) {
+  const long long ld = t->sw > t->c ? t->sw : t->c;
+  return t->d > 0 && t->h > 0 && t->w > 0 && t->c > 0 && (long long)t->d * t->h * t->w * (ld > 4 ? ld : 4) < (1ll << 31);
+}
+
+}  // namespace mmtta
+
+using namespace mmtta;
+
+extern "C" int64_t mmtta_memo_partials(const mmtta_tensor* logits, int views) {
+  if (logits == nullptr || !(views == 1 || views == 2 || views == 4 || views == 8) || logits->n < views || logits->n % views) return -1;
+  return (int64_t)memo_blocks(logits) * (logits->n / views);
+}
+
+extern "C" int mmtta_memo_loss_items(const mmtta_tensor* logits, int softmax, int views, const int32_t* view_axes,
+                                     const mmtta_tensor* dlogits, double* partial, float* loss, void* stream) {
+  MMTTA_CHECK(logits && dlogits && partial && loss && logits->ptr && dlogits->ptr, MMTTA_ERR_INVALID, "memo loss: null argument");
+  MemoViews mv;
+  int st = memo_views_check("memo loss", views, view_axes, logits->n, mv);
+  if (st) return st;
+  MMTTA_CHECK(logits->n == dlogits->n && logits->c == dlogits->c && logits->d == dlogits->d && logits->h == dlogits->h &&
+                  logits->w == dlogits->w, MMTTA_ERR_INVALID, "memo loss: shape mismatch");
+  // one view: nothing is mirrored and the marginal is that view's prediction - the entropy objective itself, same kernels
+  // and same bits (mmtta_memo_partials(logits, 1) is mmtta_entropy_partials_items(logits))
+  if (views == 1) return mmtta_entropy_loss_items(logits, softmax, dlogits, partial, loss, stream);
+  MMTTA_CHECK(logits->dtype == MMTTA_F32, MMTTA_ERR_UNSUPPORTED, "memo loss: `logits` must be fp32-stored");
+  MMTTA_CHECK(is_cl(logits) && is_cl(dlogits), MMTTA_ERR_UNSUPPORTED, "memo loss: channels-last only");
+  MMTTA_CHECK(memo_small_item(logits) && memo_small_item(dlogits), MMTTA_ERR_UNSUPPORTED, "memo loss: an item of 2^31 elements or more");
+  hipStream_t s = (hipStream_t)stream;
+  const int volumes = logits->n / views;
+  MMTTA_CHECK(volumes <= MEMO_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "memo loss: more than %d volumes in one call", MEMO_MAX_GRID_Y);
+  const int blocks = memo_blocks(logits);
+  const long long nvox = (long long)logits->d * logits->h * logits->w;
+  const dim3 grid(blocks, volumes);
+  const double cnt = softmax ? (double)nvox : (double)nvox * logits->c;
+  const float inv = (float)(1.0 / (cnt * views));
+  if (!softmax) {
+    const bool vec = logits->c <= 4 && memo_dense16(logits) && memo_dense16(dlogits) &&
+                     ((dlogits->flags & MMTTA_TENSOR_OWNS_PAD) || dlogits->c == 4);
+    MMTTA_CHECK(is_f32(dlogits) || vec, MMTTA_ERR_UNSUPPORTED, "memo loss: a bf16-stored `dlogits` needs dense 4-channel voxel rows that own their pad");
+    if (vec) {
+      const float* zp = (const float*)logits->ptr;
+      float* gp = (float*)dlogits->ptr;
+#define MEMO_VEC(VV)                                                                                                          \
+  do {                                                                                                                        \
+    if (is_bf16(dlogits))                                                                                                     \
+      hipLaunchKernelGGL((memo_bernoulli_vec_kernel<VV, true>), grid, dim3(256), 0, s, zp, gp, (long long)logits->sn,          \
+                         (long long)dlogits->sn, (int)logits->c, (unsigned)logits->d, (unsigned)logits->h, (unsigned)logits->w, \
+                         mv, partial, inv);                                                                                   \
+    else                                                                                                                      \
+      hipLaunchKernelGGL((memo_bernoulli_vec_kernel<VV, false>), grid, dim3(256), 0, s, zp, gp, (long long)logits->sn,         \
+                         (long long)dlogits->sn, (int)logits->c, (unsigned)logits->d, (unsigned)logits->h, (unsigned)logits->w, \
+                         mv, partial, inv);                                                                                   \
+  } while (0)
+      if (views == 2) MEMO_VEC(2);
+      else if (views == 4) MEMO_VEC(4);
+      else MEMO_VEC(8);
+#undef MEMO_VEC
+    } else {
+      hipLaunchKernelGGL(memo_bernoulli_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), mv, partial, inv);
+    }
+    st = launch_status("memo bernoulli");
+  } else {
+    MMTTA_CHECK(logits->c <= MEMO_MAX_R, MMTTA_ERR_UNSUPPORTED, "memo loss softmax: more than %d classes", MEMO_MAX_R);
+    MMTTA_CHECK(is_f32(dlogits), MMTTA_ERR_UNSUPPORTED, "memo loss softmax: `dlogits` must be fp32-stored");
+    hipLaunchKernelGGL(memo_categorical_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), mv, partial, inv);
+    st = launch_status("memo categorical");
+  }
+  if (st) return st;
+  hipLaunchKernelGGL(memo_finish_kernel, dim3(volumes), dim3(64), 0, s, partial, blocks, 1.0 / cnt, loss);
+  return launch_status("memo finish");
+}
+
+extern "C" int mmtta_memo_ensemble(const mmtta_tensor* logits, int softmax, int views, const int32_t* view_axes,
+                                   const mmtta_tensor* out, void* stream) {
+  MMTTA_CHECK(logits && out && logits->ptr && out->ptr, MMTTA_ERR_INVALID, "memo ensemble: null argument");
+  MemoViews mv;
+  int st = memo_views_check("memo ensemble", views, view_axes, logits->n, mv);
+  if (st) return st;
+  MMTTA_CHECK(logits->n == out->n * views && logits->c == out->c && logits->d == out->d && logits->h == out->h &&
+                  logits->w == out->w, MMTTA_ERR_INVALID, "memo ensemble: shape mismatch");
+  MMTTA_CHECK(logits->dtype == MMTTA_F32 && out->dtype == MMTTA_F32, MMTTA_ERR_UNSUPPORTED, "memo ensemble: fp32-stored tensors only");
+  MMTTA_CHECK(is_cl(logits) && is_cl(out), MMTTA_ERR_UNSUPPORTED, "memo ensemble: channels-last only");
+  MMTTA_CHECK(memo_small_item(logits) && memo_small_item(out), MMTTA_ERR_UNSUPPORTED, "memo ensemble: an item of 2^31 elements or more");
+  MMTTA_CHECK(!softmax || logits->c <= MEMO_MAX_R, MMTTA_ERR_UNSUPPORTED, "memo ensemble softmax: more than %d classes", MEMO_MAX_R);
+  MMTTA_CHECK(out->n <= MEMO_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "memo ensemble: more than %d volumes in one call", MEMO_MAX_GRID_Y);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(memo_blocks(logits), out->n);
+  if (softmax)
+    hipLaunchKernelGGL(memo_ensemble_categorical_kernel, grid, dim3(256), 0, s, tv(logits), tv(out), mv);
+  else
+    hipLaunchKernelGGL(memo_ensemble_bernoulli_kernel, grid, dim3(256), 0, s, tv(logits), tv(out), mv);
+  return launch_status("memo ensemble");
+}
+
+extern "C" int mmtta_mirror_views(const mmtta_tensor* x, const mmtta_tensor* y, int views, const int32_t* view_axes, void* stream) {
+  MMTTA_CHECK(x && y && x->ptr && y->ptr, MMTTA_ERR_INVALID, "mirror views: null argument");
+  MemoViews mv;
+  int st = memo_views_check("mirror views", views, view_axes, y->n, mv);
+  if (st) return st;
+  MMTTA_CHECK(y->n == x->n * views && x->c == y->c && x->d == y->d && x->h == y->h && x->w == y->w && x->dtype == y->dtype,
+              MMTTA_ERR_INVALID, "mirror views: shape mismatch");
+  MMTTA_CHECK(x->dtype == MMTTA_F32 || x->dtype == MMTTA_BF16, MMTTA_ERR_UNSUPPORTED, "mirror views: fp32 or bf16 rows");
+  auto dense = [](const mmtta_tensor* t) {
+    return t->sc == 1 && t->sw >= t->c && t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh;
+  };
+  MMTTA_CHECK(dense(x) && dense(y) && x->sw == y->sw, MMTTA_ERR_UNSUPPORTED, "mirror views: dense channels-last rows of one width");
+  MMTTA_CHECK(y->sw == y->c || (y->flags & MMTTA_TENSOR_OWNS_PAD), MMTTA_ERR_UNSUPPORTED, "mirror views: `y` must own the pad lanes of its rows");
+  MMTTA_CHECK(memo_small_item(x), MMTTA_ERR_UNSUPPORTED, "mirror views: an item of 2^31 elements or more");
+  MMTTA_CHECK(y->n <= MEMO_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "mirror views: more than %d output items in one call", MEMO_MAX_GRID_Y);
+  const long long esz = x->dtype == MMTTA_BF16 ? 2 : 4;
+  const long long row = x->sw * esz;
+  const uintptr_t both = (uintptr_t)x->ptr | (uintptr_t)y->ptr | (uintptr_t)(x->sn * esz) | (uintptr_t)(y->sn * esz) | (uintptr_t)row;
+  const int unit = both % 16 == 0 ? 16 : (both % 8 == 0 ? 8 : (both % 4 == 0 ? 4 : 2));
+  MMTTA_CHECK(unit >= esz && both % esz == 0, MMTTA_ERR_UNSUPPORTED, "mirror views: misaligned tensor");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned upr = (unsigned)(row / unit);
+  const long long units = (long long)x->d * x->h * x->w * upr;
+  long long b = (units + 255) / 256;
+  if (b > 4096) b = 4096;
+  const dim3 grid((unsigned)b, y->n);
+  const long long xsn = x->sn * esz / unit, ysn = y->sn * esz / unit;
+  const unsigned D = x->d, H = x->h, W = x->w;
+  if (unit == 16)
+    hipLaunchKernelGGL(memo_mirror_kernel<uint4>, grid, dim3(256), 0, s, (const uint4*)x->ptr, (uint4*)y->ptr, xsn, ysn, upr, D, H, W, mv);
+  else if (unit == 8)
+    hipLaunchKernelGGL(memo_mirror_kernel<uint2>, grid, dim3(256), 0, s, (const uint2*)x->ptr, (uint2*)y->ptr, xsn, ysn, upr, D, H, W, mv);
+  else if (unit == 4)
+    hipLaunchKernelGGL(memo_mirror_kernel<unsigned>, grid, dim3(256), 0, s, (const unsigned*)x->ptr, (unsigned*)y->ptr, xsn, ysn, upr, D, H, W, mv);
+  else
+    hipLaunchKernelGGL(memo_mirror_kernel<unsigned short>, grid, dim3(256), 0, s, (const unsigned short*)x->ptr, (unsigned short*)y->ptr, xsn, ysn, upr, D, H, W, mv);
+  return launch_status("mirror views");
+}

@@ -176,7 +176,8 @@ class NormLayer:
                 and (self.gamma is not None or self.beta is not None or self.bn is not None))
 
     def _sets(self) -> "ops._lib.NormSets":
-        return ops.norm_sets(1, self.rt.arena.total, self.rt.bn_stats_total)
+        # (the views of a volume are consecutive batch items on its set: BatchNorm pools over them, as torch does over a batch)
+        return ops.norm_sets(self.rt.views, self.rt.arena.total, self.rt.bn_stats_total)
 
     def finalize(self, pool: Pool, key, part, rows_per_n: int, n: int, count: int, training: bool) -> NL:
         if self.grouped():
@@ -216,7 +217,7 @@ class NormLayer:
         ops.norm_stats_finalize_sets(self.kind, self.groups, part, rows_per_n, n, C, count, self.eps, use_batch, rm, rv,
                                      self.momentum, mean, rstd, scratch, self._sets(), g, b, scale, shift, gi, bi)
         if self.bn is not None and training and self.bn.num_batches_tracked is not None:
-            self.rt.bn_nbt_all[:n, self.bn_index].add_(1)
+            self.rt.bn_nbt_all[:n // self.rt.views, self.bn_index].add_(1)
         return NL(mean, rstd, gi, bi, True, scale, shift, per_item=True, act=self.act,
                   negative_slope=self.negative_slope)
 
@@ -453,6 +454,12 @@ class Runtime:
         # launches; the nn.Module facade (plain batched forward, one weight set) leaves it off
         self.group = max(1, int(group))
         self.use_sets = False
+        # `views` consecutive batch items belong to one volume (memo_tta: the mirrored views of a volume, HipSegModel.set_views):
+        # inside the launches of a volume group they share the volume's parameter set - mmtta_param_sets.items_per_set and
+        # mmtta_norm_sets.items_per_set are multiplied by it - so the batch is group x views items on `group` replicas.
+        # Without a group the views are a plain batch on the one weight set.  1 except inside the launches of a plugin
+        # that works on views (memo_tta switches it on around them)
+        self.views = 1
         self.pool = Pool(device)
         # forward activations of more than 4 channels stored as bf16 (torch-autocast style): set by runtimes whose every
         # layer kind has storage-agnostic kernels (models/unet.py); gradients, logits, statistics, weights stay fp32
@@ -767,6 +774,14 @@ class Runtime:
         x_cl = self.pool.cl("x", n, d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=self.input_dtype())
         ops.to_cl(x, out=x_cl)
         return x_cl
+
+    def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int]) -> torch.Tensor:
+        """The staged input [G,D,H,W,C] -> its mirrored views as batch items [G * V,D,H,W,C] (item g * V + v = volume g
+        mirrored along the axes of mask view_axes[v]; ops.mirror_views), in the storage of the staged input."""
+        n, d, h, w, c = x_cl.shape
+        xv = self.pool.cl("x_views", n * len(view_axes), d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=x_cl.dtype)
+        ops.mirror_views(x_cl, xv, view_axes)
+        return xv
 
     def input_dtype(self) -> torch.dtype:
         """Storage of the staged network input.  Runtimes whose every reader of the input rounds it to bf16 while staging

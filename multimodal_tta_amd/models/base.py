@@ -56,6 +56,7 @@ class HipSegModel(nn.Module):
         self.conv_dtype = ops.F32
         self.group = 1
         self.norm_sets = False
+        self.views = 1
 
     def set_group(self, group: int) -> None:
         """``group`` volumes adapt side by side through one launch sequence, each with its own parameter replica
@@ -63,6 +64,16 @@ class HipSegModel(nn.Module):
         group = max(1, int(group))
         if group != self.group:
             self.group = group
+            self._rt = None
+
+    def set_views(self, views: int) -> None:
+        """Every volume enters the adaptation launches as ``views`` consecutive batch items on its parameter replica
+        (``memo_tta``: the mirrored views of a volume; takes effect at the next runtime build, which may refuse the
+        combination with ``group``).  The plugin switches ``Runtime.views`` on around its own launches; the facade's
+        batched forward is not affected."""
+        views = max(1, int(views))
+        if views != self.views:
+            self.views = views
             self._rt = None
 
     def set_norm_sets(self, enabled: bool) -> None:

@@ -279,6 +279,11 @@ class DeepFusionRuntime(Runtime):
 
     def __init__(self, model: "MultimodalUNetDeepFusion", device: torch.device):
         super().__init__(device, model.conv_dtype, group=getattr(model, "group", 1))
+        if self.group > 1 and int(getattr(model, "views", 1)) > 1:
+            # the encoder families spend the set index on the modality: (volume, view, modality) items with the views of a
+            # volume on one set have no layout in mmtta_param_sets
+            raise NotImplementedError(f"method.group = {self.group} with {model.views} views per volume: the deep-fusion "
+                                      "network takes views at group 1 only")
         self.M = model.num_modalities
         self.in_channels = self.M
         self.channels = list(model.channels)
@@ -317,9 +322,22 @@ class DeepFusionRuntime(Runtime):
         ops.to_cl(x.contiguous().view(n * M, 1, D, H, W), out=xm)
         return x_cl
 
-    @staticmethod
-    def _member(t: torch.Tensor, M: int, m: int) -> torch.Tensor:
-        """[n * M, ...] family batch -> the [n, ...] view of member m (batch stride M items)."""
+    def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int]) -> torch.Tensor:
+        """The mirrored views of the staged volume, and the family batch [n * V * M, D, H, W, 1] of those views."""
+        xv = super().stage_views(x_cl, view_axes)
+        n, D, H, W, M = xv.shape
+        xm = self.pool.cl("xm", n * M, D, H, W, 1, ldc=4, zero=True)
+        for m in range(M):
+            ops.lincomb([xv[..., m:m + 1]], [1.0], self._member(xm, M, m))
+        return xv
+
+    def _member(self, t: torch.Tensor, M: int, m: int) -> torch.Tensor:
+        """[n * M, ...] family batch -> the [n, ...] view of member m (batch stride M items).  With views (group 1 only) the
+        family batch is member-major, [M * V, ...] with item m * V + v: the V views of a member's input are consecutive items
+        on the member's weights (mmtta_param_sets.items_per_set = V), so its weight gradient sums over them."""
+        if self.views > 1:
+            V = t.shape[0] // M
+            return t[m * V:(m + 1) * V]
         return t.view(t.shape[0] // M, M, *t.shape[1:])[:, m]
 
     # ---------------------------------------------------------------- forward

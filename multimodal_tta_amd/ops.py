@@ -362,6 +362,7 @@ class ConvOp:
         self.sets_plain: Optional[Tuple[ParamSets, ParamSets]] = None        # a family of modules inside ONE weight set
         self.sets_ctl = None
         self.shared_sets = False
+        self._sets_views: Dict[Tuple, ParamSets] = {}      # sets_grouped with items_per_set x views (filled by _sets)
 
     def set_param_sets(self, items_per_set: int, inner: int, weight_outer: int, weight_inner: int, bias_outer: int,
                        bias_inner: int, ctl, shared: bool = False) -> None:
@@ -374,6 +375,7 @@ class ConvOp:
                                          int(weight_inner), int(bias_outer) * outer, int(bias_inner))
         o = 0 if shared else 1
         self.sets_grouped = (mk(self.nb_fwd, o), mk(self.nb_dgrad, o))
+        self._sets_views = {}
         self.shared_sets = bool(shared)
         if shared and self.n_sets > inner:
             # only the images of set 0's members are packed and read: the others are not kept
@@ -389,7 +391,20 @@ class ConvOp:
         pair = self.sets_grouped if grouped else self.sets_plain
         if pair is None:
             return None
-        return pair[1] if int(desc.op) in (CONV_DGRAD, CONVT_DGRAD) else pair[0]
+        dgrad = int(desc.op) in (CONV_DGRAD, CONVT_DGRAD)
+        sets = pair[1] if dgrad else pair[0]
+        views = int(getattr(self.sets_ctl, "views", 1))
+        if views == 1:
+            return sets
+        # every set brings `views` consecutive batch items (engine.Runtime.views: the views of a volume - or, in a family of
+        # modules, of one member's input) that share it; its weight gradient sums over them
+        key = (grouped, dgrad, views)
+        scaled = self._sets_views.get(key)
+        if scaled is None:
+            scaled = ParamSets.from_buffer_copy(sets)
+            scaled.items_per_set = int(sets.items_per_set) * views
+            self._sets_views[key] = scaled
+        return scaled
 
     def packed_image(self, dgrad: bool, index: int) -> torch.Tensor:
         """The packed image of parameter set ``index`` (a view)."""
@@ -791,6 +806,47 @@ def entropy_filtered_items(logits: torch.Tensor, dlogits: torch.Tensor, margin: 
     check(_lib.load().mmtta_entropy_filtered_items(C.byref(tz), 1 if softmax else 0, float(margin), ptr(keep_in), ptr(keep_out),
                                                    C.byref(tg), ptr(partial), ptr(loss), ptr(kept), stream_ptr()),
           "entropy_filtered_items")
+
+
+def _view_axes(view_axes: Sequence[int]):
+    """The host array of mirror masks the MEMO entry points read at launch (bit 0 = W, 1 = H, 2 = D)."""
+    return (C.c_int32 * len(view_axes))(*[int(a) for a in view_axes])
+
+
+def mirror_views(x: torch.Tensor, y: torch.Tensor, view_axes: Sequence[int]) -> None:
+    """y[g * V + v] = x[g] mirrored along the axes of mask view_axes[v]: channels-last [G,D,H,W,C] -> [G*V,D,H,W,C], whole
+    voxel rows (pad lanes included), fp32 or bf16, bit-exact."""
+    tx, ty = desc_cl(x), desc_cl(y)
+    check(_lib.load().mmtta_mirror_views(C.byref(tx), C.byref(ty), len(view_axes), _view_axes(view_axes), stream_ptr()),
+          "mirror_views")
+
+
+def memo_partials(logits: torch.Tensor, views: int) -> int:
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_memo_partials(C.byref(t), int(views)))
+
+
+def memo_loss_items(logits: torch.Tensor, dlogits: torch.Tensor, view_axes: Sequence[int], partial: torch.Tensor,
+                    loss: torch.Tensor, softmax: bool = False) -> None:
+    """MEMO's marginal entropy of every volume on its own: logits / dlogits [G*V,D,H,W,R] (item g*V+v = view v of volume g,
+    each in its own mirrored frame), loss fp32 [G]."""
+    views = len(view_axes)
+    need = memo_partials(logits, views)          # -1 for a bad view count: the entry point below says which
+    if loss.numel() < logits.shape[0] // max(views, 1):
+        raise MmttaError("memo_loss_items: one loss slot per volume")
+    if partial.dtype != torch.float64 or partial.numel() < need:
+        raise MmttaError("memo_loss_items: partial must be fp64 of memo_partials(logits, views) elements")
+    tz, tg = desc_cl(logits), desc_cl(dlogits)
+    check(_lib.load().mmtta_memo_loss_items(C.byref(tz), 1 if softmax else 0, views, _view_axes(view_axes), C.byref(tg),
+                                            ptr(partial), ptr(loss), stream_ptr()), "memo_loss_items")
+
+
+def memo_ensemble(logits: torch.Tensor, out: torch.Tensor, view_axes: Sequence[int], softmax: bool = False) -> None:
+    """out [G,D,H,W,R] = logit (sigmoid head) or log (softmax head) of the mean over the views of the predicted
+    probabilities, in the volume's own frame."""
+    tz, to = desc_cl(logits), desc_cl(out)
+    check(_lib.load().mmtta_memo_ensemble(C.byref(tz), 1 if softmax else 0, len(view_axes), _view_axes(view_axes), C.byref(to),
+                                          stream_ptr()), "memo_ensemble")
 
 
 def sam_ascent_partials(n: int, sets: int) -> int:

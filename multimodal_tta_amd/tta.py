@@ -70,6 +70,9 @@ class EntropyMinimizationTTA:
     # the wide 27-tap layers update inside their weight-gradient launch (engine.Runtime.enable_fused_update); a subclass whose
     # step needs the whole gradient before any weight moves (SAR: the global gradient norm) switches it off
     fused_update = True
+    # batch items a volume brings into the adaptation launches (memo_tta: its mirrored views); told to the model at every
+    # setup, so a model that another plugin set up with views is built for this plugin's figure again
+    views = 1
 
     def __init__(self, config: Any = None):
         cfg = as_cfg(config)
@@ -149,6 +152,7 @@ class EntropyMinimizationTTA:
         names = select_params(model, self.params_spec)
         model.set_precision(self.precision, self.storage, self.grad_storage)
         model.set_group(self.group)
+        model.set_views(self.views)
         model.set_norm_sets(self.norm_sets)
         model.configure_training(set(names), self.no_decay_keys, self.treat_1d)
         model.to(device)
