@@ -512,6 +512,48 @@ int mmtta_memo_loss_items(const mmtta_tensor* logits, int softmax, int views, co
 int mmtta_memo_ensemble(const mmtta_tensor* logits, int softmax, int views, const int32_t* view_axes,
                         const mmtta_tensor* out, void* stream);
 
+/* ---- CoTTA (Wang et al., CVPR 2022): the student's consistency loss against the teacher's soft target, and the pass after
+ * the student's optimizer step (teacher EMA + stochastic restore).
+ *
+ * mmtta_consistency_loss_items: every batch item is its own objective (as in mmtta_entropy_loss_items).  `logits` z and
+ *   `target` t are [N, D, H, W, C] fp32 in one frame; t is what mmtta_memo_ensemble writes - logit(pbar) (softmax == 0) or
+ *   log pbar (softmax != 0) - and takes no gradient:
+ *     softmax == 0:  q = sigmoid(t);  loss[n] = mean over (voxel, region) of -q log sigmoid(z) - (1 - q) log sigmoid(-z)
+ *                    dlogits = (sigmoid(z) - q) / count
+ *     softmax != 0:  loss[n] = mean over voxel of -sum_r exp(t_r) log softmax(z)_r;  dlogits = (softmax(z) - exp(t)) / count
+ *   One streaming pass and the per-item finish (fixed-order fp64 sums, no atomics).  Loss and gradient are finite for every
+ *   finite fp32 input: log sigmoid(z) = min(z, 0) - log1p(exp(-|z|)), 1 - q is never formed by subtraction, and both
+ *   sigmoids are taken at the logit held inside +-87.3365 (the ensemble's bound; t_r is held at -3e38 from below) by the
+ *   same instructions, so target == logits gives a gradient of exactly zero - as does, for the softmax head, the target
+ *   mmtta_memo_ensemble makes from the same logits with one view.  Storages as mmtta_entropy_loss_items: fp32 gradients, or
+ *   - softmax == 0, <= 4 channels, all three tensors in dense 4-channel voxel rows - bf16 (the fp32 value rounded).  N
+ *   items in one call are bit for bit N calls on one item each.
+ *   partial  fp64 [mmtta_consistency_partials(logits)] scratch; loss  fp32 [N]
+ *
+ * mmtta_cotta_update_sets: ONE pass over the first n elements of each of `sets` parameter sets (set s of w at
+ *   s * w_stride, of teacher at s * teacher_stride; `source` [n] is shared):
+ *     teacher <- a teacher + b w      a = (float)alpha, b = (float)(1 - alpha) (the difference taken in double), fp32
+ *                                     products and sum with separate roundings; alpha == 1 leaves the teacher's bits
+ *     w_i <- source_i where u_i < restore_p (the source BITS), else unchanged
+ *   u_i = (word >> 8) * 2^-24, compared in fp32, where word is number i & 3 of the four outputs of Philox4x32-10 (Salmon
+ *   et al., SC 2011; Random123's and curand's generator, written out in the kernel) with key (seed & 0xffffffff, seed >> 32)
+ *   and counter (i >> 2, *step, ordinals[s], 0).  `step` is the arena's DEVICE step counter, read after the optimizer
+ *   advanced it (1 for the first step), so a replayed graph draws fresh numbers; `ordinals` is a DEVICE int32 [sets] array
+ *   with one number per volume (not the set index: a group of volumes then equals the same volumes one at a time).
+ *   restored[s] (int64) = the number of restored elements of set s, summed from int64 block partials in a fixed order.
+ *   12 B read and 8 B written per parameter.  n need not be a multiple of 4; strides are, buffers are 16-byte aligned.
+ *   partial  int64 [mmtta_cotta_update_partials(n, sets)] scratch
+ *
+ * Bad arguments (null pointers, shape mismatches, alpha outside [0, 1], restore_p outside [0, 1), bad strides) are
+ * MMTTA_ERR_INVALID, storages without a kernel MMTTA_ERR_UNSUPPORTED, both before anything is launched. */
+int64_t mmtta_consistency_partials(const mmtta_tensor* logits);
+int mmtta_consistency_loss_items(const mmtta_tensor* logits, const mmtta_tensor* target, int softmax,
+                                 const mmtta_tensor* dlogits, double* partial, float* loss, void* stream);
+int64_t mmtta_cotta_update_partials(int64_t n, int sets);
+int mmtta_cotta_update_sets(float* w, float* teacher, const float* source, int64_t n, int sets, int64_t w_stride,
+                            int64_t teacher_stride, double alpha, float restore_p, uint64_t seed, const int32_t* step,
+                            const int32_t* ordinals, int64_t* partial, int64_t* restored, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

@@ -158,6 +158,12 @@ _SIGNATURES = {
     "mmtta_memo_loss_items": (C.c_int, [_P(Tensor), C.c_int, C.c_int, _P(C.c_int32), _P(Tensor), C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     "mmtta_memo_ensemble": (C.c_int, [_P(Tensor), C.c_int, C.c_int, _P(C.c_int32), _P(Tensor), C.c_void_p]),
+    "mmtta_consistency_partials": (C.c_int64, [_P(Tensor)]),
+    "mmtta_consistency_loss_items": (C.c_int, [_P(Tensor), _P(Tensor), C.c_int, _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_cotta_update_partials": (C.c_int64, [C.c_int64, C.c_int]),
+    "mmtta_cotta_update_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64,
+                                          C.c_double, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "mmtta_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mmtta_optim_step": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,

@@ -849,6 +849,53 @@ def memo_ensemble(logits: torch.Tensor, out: torch.Tensor, view_axes: Sequence[i
                                           stream_ptr()), "memo_ensemble")
 
 
+def consistency_partials(logits: torch.Tensor) -> int:
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_consistency_partials(C.byref(t)))
+
+
+def consistency_loss_items(logits: torch.Tensor, target: torch.Tensor, dlogits: torch.Tensor, partial: torch.Tensor,
+                           loss: torch.Tensor, softmax: bool = False) -> None:
+    """CoTTA's consistency loss of every batch item on its own: the student's logits against the teacher's target (logit of
+    its mean probability, softmax head: log of it - ``memo_ensemble``'s output), all [N,D,H,W,R]; loss fp32 [N]; dlogits =
+    (sigmoid(z) - sigmoid(t)) / count, softmax head (softmax(z) - exp(t)) / count."""
+    if loss.numel() < logits.shape[0]:
+        raise MmttaError("consistency_loss_items: one loss slot per batch item")
+    if partial.dtype != torch.float64 or partial.numel() < consistency_partials(logits):
+        raise MmttaError("consistency_loss_items: partial must be fp64 of consistency_partials(logits) elements")
+    tz, tt, tg = desc_cl(logits), desc_cl(target), desc_cl(dlogits)
+    check(_lib.load().mmtta_consistency_loss_items(C.byref(tz), C.byref(tt), 1 if softmax else 0, C.byref(tg), ptr(partial),
+                                                   ptr(loss), stream_ptr()), "consistency_loss_items")
+
+
+def cotta_update_partials(n: int, sets: int) -> int:
+    return int(_lib.load().mmtta_cotta_update_partials(int(n), int(sets)))
+
+
+def cotta_update_sets(w: torch.Tensor, teacher: torch.Tensor, source: torch.Tensor, n: int, sets: int, alpha: float,
+                      restore_p: float, seed: int, step: torch.Tensor, ordinals: torch.Tensor, partial: torch.Tensor,
+                      restored: torch.Tensor) -> None:
+    """CoTTA's pass after the student's optimizer step over the first ``sets`` rows of ``w`` / ``teacher`` ([rows, >= n]
+    fp32) and the shared ``source`` ([>= n]): teacher = alpha teacher + (1 - alpha) w, then w[i] = source[i] where the
+    Philox4x32-10 draw of (seed; i >> 2, step, ordinal) is below ``restore_p``.  ``step``: the device int32 step counter;
+    ``ordinals``: device int32 [>= sets]; ``restored``: int64 [>= sets], the restored elements per row."""
+    for name, t in (("w", w), ("teacher", teacher)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[0] < sets or t.shape[1] < n:
+            raise MmttaError(f"cotta_update_sets: {name} must be contiguous fp32 [>= {sets}, >= {n}], got {tuple(t.shape)}")
+    if source.dtype != torch.float32 or not source.is_contiguous() or source.numel() < n:
+        raise MmttaError(f"cotta_update_sets: source must be contiguous fp32 of at least {n} elements")
+    if step.dtype != torch.int32 or ordinals.dtype != torch.int32 or ordinals.numel() < sets:
+        raise MmttaError("cotta_update_sets: step must be a device int32 scalar, ordinals device int32 [>= sets]")
+    if restored.dtype != torch.int64 or restored.numel() < sets:
+        raise MmttaError("cotta_update_sets: one int64 count per set")
+    if partial.dtype != torch.int64 or partial.numel() < cotta_update_partials(n, sets):
+        raise MmttaError("cotta_update_sets: partial must be int64 of cotta_update_partials(n, sets) elements")
+    check(_lib.load().mmtta_cotta_update_sets(ptr(w), ptr(teacher), ptr(source), int(n), int(sets), int(w.shape[1]),
+                                              int(teacher.shape[1]), float(alpha), float(restore_p),
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), ptr(ordinals), ptr(partial),
+                                              ptr(restored), stream_ptr()), "cotta_update_sets")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 
