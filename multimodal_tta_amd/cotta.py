@@ -37,12 +37,13 @@ Scope: the fused weight-gradient update is off (the step's gradient is taken wit
 resident packed images (two repacks per step); BatchNorm models raise ``NotImplementedError`` (the teacher's train-mode
 forward would move the running statistics the student owns) - parameter-free and affine Instance / Group norms work;
 ``moddrop.enabled: true`` raises as in ``memo_tta`` while ``missing_modalities`` works (mask, then mirror); the deep-fusion
-network takes views at ``group`` 1 only.  Everything else - groups, lanes, precisions, heads, the captured step - is
-``entmin_tta``'s.
+network takes views at ``group`` 1 only.  The class is its step (``_update``), the teacher's reset with the episodic one
+(``_reset``), the staging of the views (``_stage``), one more per-step record and the ordinals; the per-volume loop - groups,
+lanes, the captured step, the final forward - is ``EntropyMinimizationTTA``'s.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, Optional, Sequence
+from typing import Any, Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -51,7 +52,7 @@ from . import ops
 from .config import as_cfg, get_config
 from .memo import parse_mirror_axes, view_masks
 from .registry import register_plugin
-from .tta import EntropyMinimizationTTA, drop_modality, modality_mask
+from .tta import EntropyMinimizationTTA
 
 
 @register_plugin("cotta_tta")
@@ -65,10 +66,7 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         super().__init__(config)
         m = get_config(as_cfg(config), "method", {}) or {}
         s = get_config(m, "cotta", {}) or {}
-        try:
-            self.mirror_axes = parse_mirror_axes(get_config(s, "mirror_axes", ["h", "w"]))
-        except ValueError as exc:
-            raise ValueError(str(exc).replace("method.memo.", "method.cotta.")) from None
+        self.mirror_axes = parse_mirror_axes(get_config(s, "mirror_axes", ["h", "w"]), "method.cotta.mirror_axes")
         self.view_axes = view_masks(self.mirror_axes)
         self.views = len(self.view_axes)
         alpha, p, seed = get_config(s, "alpha", 0.999), get_config(s, "restore_p", 0.01), get_config(s, "seed", 0)
@@ -85,9 +83,6 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         self.teacher: Optional[torch.Tensor] = None          # [replicas, n_train] fp32
         self._ordinals: Optional[torch.Tensor] = None        # device int32 [replicas]: the draw's per-volume number
         self._served = 0
-        self._xv: Optional[torch.Tensor] = None
-        self._restored_hist: Optional[torch.Tensor] = None
-        self._t = 0
 
     def setup(self, model, device) -> "MeanTeacherTTA":
         super().setup(model, device)          # (tells the model its views: EntropyMinimizationTTA.setup)
@@ -97,9 +92,6 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
                 f"cotta_tta: model.norm = {get_config(get_config(self.cfg, 'model', {}) or {}, 'norm', 'BATCH')!r} keeps running "
                 "statistics, which the teacher's train-mode forward would move (running_mean, running_var, "
                 "num_batches_tracked belong to the student); use a model.norm without them (INSTANCE, GROUP)")
-        if self.tune_volumes is None and self.views > 1:
-            # `auto`: launch geometry for the items of the widest launches - lanes x group x views (memo_tta's rule)
-            ops.tune_for_volumes_in_flight(self.lanes * self.group * self.views)
         self.teacher = torch.empty((ar.replicas, ar.n_train), dtype=torch.float32, device=ar.device)
         self._ordinals = torch.zeros(ar.replicas, dtype=torch.int32, device=ar.device)
         self._served = int(self.lane) << 24
@@ -112,123 +104,71 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         self.teacher.copy_(ar.source[:ar.n_train].unsqueeze(0).expand_as(self.teacher))
 
     # ------------------------------------------------------------------ one step
-    def _step_launches(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+    # ``restored``: the number of elements the step returned to their source values
+    records = EntropyMinimizationTTA.records + (("restored", "cotta_restored", torch.int64),)
+
+    def _update(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]], xv: torch.Tensor) -> None:
         rt, ar = self.rt, self.rt.arena
-        V, xv, nt = self.views, self._xv, ar.n_train
-        ops.Workspace.lane = self.lane
-        rt.training = True
-        rt.use_sets = rt.group > 1          # batch items [g * V, (g + 1) * V) resp. item g read / write parameter replica g
-        try:
-            def forward(x: torch.Tensor) -> torch.Tensor:
-                return rt.forward_cl(x) if present is None else rt.forward_cl(x, present=present)
-
-            B = int(x_cl.shape[0])
-            sets = min(B, ar.replicas)
-            # 1. targets: the teacher in the student's place, its V views, their ensemble in the volume's frame
-            saved = rt.pool.flat("cotta_saved", ar.replicas * nt).view(ar.replicas, nt)
-            if nt > 0:
-                saved[:sets].copy_(ar.params_all[:sets, :nt])
-                ar.params_all[:sets, :nt].copy_(self.teacher[:sets])
-            rt.views = V
-            rt.pack_all()
-            zv = forward(xv)
-            n, d, h, w, r = zv.shape
-            target = rt.pool.cl("cotta_target", B, d, h, w, r, ldc=(r + 3) // 4 * 4)
-            ops.memo_ensemble(zv, target, self.view_axes, softmax=self.softmax)
-            # 2. the student on the volume alone
-            if nt > 0:
-                ar.params_all[:sets, :nt].copy_(saved[:sets])
-            rt.views = 1
-            rt.pack_all()
-            logits = forward(x_cl)
-            # 3. consistency loss (the categorical form writes fp32 only)
-            gdt = rt.thin_grad_dtype() if (not self.softmax and r <= 4) else torch.float32
-            dlogits = rt.pool.cl("dlogits", B, d, h, w, r, ldc=(r + 3) // 4 * 4, dtype=gdt)
-            partial = rt.pool.flat("cotta_partial", ops.consistency_partials(logits), dtype=torch.float64)
-            loss = rt.pool.flat("ent_loss", rt.group if rt.group > 1 else 1)
-            ops.consistency_loss_items(logits, target, dlogits, partial, loss, softmax=self.softmax)
-            restored = rt.pool.flat("cotta_restored", ar.replicas, dtype=torch.int64, zero=True)
-            if nt > 0:
-                # 4. - 6. backward, the optimizer (it advances the step counter), teacher EMA + stochastic restore
-                rt.run_backward(dlogits)
-                self.optimizer_step(B)
-                upd = rt.pool.flat("cotta_upd_partial", ops.cotta_update_partials(nt, sets), dtype=torch.int64)
-                ops.cotta_update_sets(ar.params_all, self.teacher, ar.source, nt, sets, self.alpha, self.restore_p, self.seed,
-                                      ar.step, self._ordinals, upd, restored)
-        finally:
-            rt.use_sets = False
-            rt.views = 1
-
-    def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
-        super()._step(x_cl, present)
-        if self._restored_hist is not None:
-            B = int(x_cl.shape[0])
-            self._restored_hist[self._t].copy_(self.rt.pool.flat("cotta_restored", self.rt.arena.replicas, dtype=torch.int64,
-                                                                 zero=True)[:B])
-            self._t += 1
+        nt = ar.n_train
+        B = int(x_cl.shape[0])
+        sets = min(B, ar.replicas)
+        # 1. targets: the teacher in the student's place, its V views (batch items [g * V, (g + 1) * V) on replica g), their
+        # ensemble in the volume's frame
+        saved = rt.pool.flat("cotta_saved", ar.replicas * nt).view(ar.replicas, nt)
+        if nt > 0:
+            saved[:sets].copy_(ar.params_all[:sets, :nt])
+            ar.params_all[:sets, :nt].copy_(self.teacher[:sets])
+        rt.views = self.views
+        rt.pack_all()
+        zv = self._forward(xv, present)
+        n, d, h, w, r = zv.shape
+        target = rt.pool.cl("cotta_target", B, d, h, w, r, ldc=(r + 3) // 4 * 4)
+        ops.memo_ensemble(zv, target, self.view_axes, softmax=self.softmax)
+        # 2. the student on the volume alone
+        if nt > 0:
+            ar.params_all[:sets, :nt].copy_(saved[:sets])
+        rt.views = 1
+        rt.pack_all()
+        logits = self._forward(x_cl, present)
+        # 3. consistency loss
+        dlogits = self._dlogits(logits)
+        partial = rt.pool.flat("cotta_partial", ops.consistency_partials(logits), dtype=torch.float64)
+        loss = rt.pool.flat("ent_loss", rt.group)
+        ops.consistency_loss_items(logits, target, dlogits, partial, loss, softmax=self.softmax)
+        restored = rt.pool.flat("cotta_restored", ar.replicas, dtype=torch.int64, zero=True)
+        if nt > 0:
+            # 4. - 6. backward, the optimizer (it advances the step counter), teacher EMA + stochastic restore
+            rt.run_backward(dlogits)
+            self.optimizer_step(B)
+            upd = rt.pool.flat("cotta_upd_partial", ops.cotta_update_partials(nt, sets), dtype=torch.int64)
+            ops.cotta_update_sets(ar.params_all, self.teacher, ar.source, nt, sets, self.alpha, self.restore_p, self.seed,
+                                  ar.step, self._ordinals, upd, restored)
 
     # ------------------------------------------------------------------ per volume
-    @torch.no_grad()
+    def _reset(self) -> None:
+        super()._reset()
+        self.reset_teacher()
+
+    def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
+        self.rt.views = self.views
+        xv = self.rt.stage_views(x_cl, self.view_axes)
+        self.rt.views = 1          # the loop runs on the volumes; the step switches to the views for the teacher
+        return x_cl, (xv,)
+
     def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None,
                      ordinals: Optional[Sequence[int]] = None) -> Dict[str, Any]:
         """As ``entmin_tta.adapt_volume``: x [B,C,D,H,W] (B <= ``method.group`` volumes), the student's final logits and the
         per-step losses, plus ``restored``: the number of restored elements per step ([steps], or [steps, B] for a group of
         B > 1 volumes).  ``ordinals``: one number per volume for the restore draw (default: the volumes served so far)."""
-        if self.rt is None:
-            return super().adapt_volume(x, steps)          # raises
-        rt, ar = self.rt, self.rt.arena
-        steps = self.steps if steps is None else int(steps)
-        B = int(x.shape[0])
-        if B > rt.group:
-            raise ValueError(f"method.group = {rt.group}: at most {rt.group} volumes per call, got {B}")
-        if ordinals is None:
-            ordinals = [self._served + b for b in range(B)]
-            self._served += B
-        ordinals = [int(o) for o in ordinals]
-        if len(ordinals) != B or any(not (0 <= o < 1 << 32) for o in ordinals):
-            raise ValueError(f"ordinals = {ordinals!r}: expected {B} numbers (one per volume) with 0 <= ordinal < 2^32")
-        self._ordinals[:B].copy_(torch.from_numpy(np.array(ordinals, dtype=np.uint32).view(np.int32)))
-        if self.episodic:
-            ar.restore_source()
-            rt.restore_buffers()
-            self.reset_teacher()
-        C = x.shape[1]
-        masked = bool(self.missing)
-        base_present = modality_mask(C, self.missing, 0.0, None)
-        x = x.float()
-        wants_present = masked and getattr(rt, "supports_present", False)
-        restage = masked and not getattr(rt, "input_mask_on_load", False)
-        # mask, then mirror: the views are views of the volume the network is given
-        x_cl = rt.stage_input(drop_modality(x, base_present) if restage else x)
-        present = base_present if wants_present else None
-        grouped = rt.group > 1
-        loss_hist = rt.pool.flat("loss_hist", max(steps, 1) * (B if grouped else 1))
-        loss_buf = rt.pool.flat("ent_loss", rt.group if grouped else 1)
-        if grouped:
-            loss_hist = loss_hist.view(max(steps, 1), B)
-        hist = rt.pool.flat("cotta_restored_hist", max(steps, 1) * B, dtype=torch.int64).view(max(steps, 1), B)
-        self._restored_hist, self._t = hist, 0
-        try:
-            rt.views = self.views
-            try:
-                self._xv = rt.stage_views(x_cl, self.view_axes)
-            finally:
-                rt.views = 1
-            for t in range(steps):
-                self._step(x_cl, present)
-                if grouped:
-                    loss_hist[t].copy_(loss_buf[:B])
-                else:
-                    loss_hist[t:t + 1].copy_(loss_buf)
-            rt.training = False
-            ops.Workspace.lane = self.lane
-            rt.use_sets = grouped
-            rt.pack_all()
-            logits_cl = rt.forward_cl(x_cl, present=present) if wants_present else rt.forward_cl(x_cl)
-        finally:
-            rt.use_sets = False
-            rt.views = 1
-            self._restored_hist = None
-        losses, restored = loss_hist[:steps], hist[:steps]
-        return {"logits_cl": logits_cl, "losses": losses[:, 0] if (grouped and B == 1) else losses,
-                "restored": restored[:, 0] if (not grouped or B == 1) else restored}
+        if self.rt is not None:
+            B = int(x.shape[0])
+            if B > self.rt.group:          # (one ordinal per replica)
+                raise ValueError(f"method.group = {self.rt.group}: at most {self.rt.group} volumes per call, got {B}")
+            if ordinals is None:
+                ordinals = [self._served + b for b in range(B)]
+                self._served += B
+            ordinals = [int(o) for o in ordinals]
+            if len(ordinals) != B or any(not (0 <= o < 1 << 32) for o in ordinals):
+                raise ValueError(f"ordinals = {ordinals!r}: expected {B} numbers (one per volume) with 0 <= ordinal < 2^32")
+            self._ordinals[:B].copy_(torch.from_numpy(np.array(ordinals, dtype=np.uint32).view(np.int32)))
+        return super().adapt_volume(x, steps)

@@ -19,33 +19,33 @@ inverse is exact on the voxel grid, so the views' predictions meet in one frame 
 voxels (or voxel x region pairs), not images; the step count is ``method.steps``, shared with Tent.
 
 With ``mirror_axes: []`` (V = 1) the method IS ``entmin_tta``: the same launches, bit for bit.  With V > 1 the fused
-weight-gradient update is off (its reduction covers one batch item per set).  Everything else - episodic reset, groups,
-lanes, the captured step - is ``entmin_tta``'s.
+weight-gradient update is off (its reduction covers one batch item per set).  The class is its step (``_update``), the
+staging of the views (``_stage``) and the ensemble (``_final_logits``); the per-volume loop is ``EntropyMinimizationTTA``'s.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
 from .config import as_cfg, get_config
 from .registry import register_plugin
-from .tta import EntropyMinimizationTTA, drop_modality, modality_mask
+from .tta import EntropyMinimizationTTA
 
 AXIS_BITS = {"w": 1, "h": 2, "d": 4}          # the kernels' mirror masks: bit 0 = W, bit 1 = H, bit 2 = D (torch D, H, W)
 
 
-def parse_mirror_axes(value: Any) -> List[str]:
-    """``method.memo.mirror_axes``: a list of distinct axes out of d, h, w."""
+def parse_mirror_axes(value: Any, key: str = "method.memo.mirror_axes") -> List[str]:
+    """A list of distinct axes out of d, h, w; ``key``: the config key it came from, for the messages."""
     if isinstance(value, (str, bytes)) or not hasattr(value, "__iter__"):
-        raise ValueError(f"method.memo.mirror_axes = {value!r}: expected a list of axes out of d, h, w")
+        raise ValueError(f"{key} = {value!r}: expected a list of axes out of d, h, w")
     axes = [str(a).lower() for a in value]
     for a in axes:
         if a not in AXIS_BITS:
-            raise ValueError(f"method.memo.mirror_axes = {list(value)!r}: unknown axis {a!r} (d, h or w)")
+            raise ValueError(f"{key} = {list(value)!r}: unknown axis {a!r} (d, h or w)")
     if len(set(axes)) != len(axes):
-        raise ValueError(f"method.memo.mirror_axes = {list(value)!r}: an axis is repeated")
+        raise ValueError(f"{key} = {list(value)!r}: an axis is repeated")
     return axes
 
 
@@ -76,92 +76,35 @@ class MarginalEntropyTTA(EntropyMinimizationTTA):
         # the fused weight update reduces one batch item per parameter set; V views per set take the separate passes
         self.fused_update = self.views == 1
 
-    def setup(self, model, device) -> "MarginalEntropyTTA":
-        super().setup(model, device)          # (tells the model its views: EntropyMinimizationTTA.setup)
-        if self.tune_volumes is None and self.views > 1:
-            # `auto`: launch geometry for the items actually in flight - lanes x group x views, with the group the runtime
-            # settled on (models that fall back to group 1 are tuned for group 1)
-            ops.tune_for_volumes_in_flight(self.lanes * self.group * self.views)
-        return self
-
     # ------------------------------------------------------------------ one step
-    def _step_launches(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+    def _update(self, xv: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
         if self.views == 1:
-            super()._step_launches(x_cl, present)          # entmin_tta's own step: its loss kernel, its fused update
+            super()._update(xv, present)          # entmin_tta's own step: its loss kernel, its fused update
             return
-        rt, ar = self.rt, self.rt.arena
-        V = self.views
-        ops.Workspace.lane = self.lane
-        rt.training = True
-        rt.use_sets = rt.group > 1          # batch items [g * V, (g + 1) * V) read / write parameter replica g
-        try:
-            rt.pack_all()
-            logits = rt.forward_cl(x_cl) if present is None else rt.forward_cl(x_cl, present=present)
-            n, d, h, w, r = logits.shape
-            gdt = rt.thin_grad_dtype() if (not self.softmax and r <= 4) else torch.float32
-            dlogits = rt.pool.cl("dlogits", n, d, h, w, r, ldc=(r + 3) // 4 * 4, dtype=gdt)
-            partial = rt.pool.flat("memo_partial", ops.memo_partials(logits, V), dtype=torch.float64)
-            loss = rt.pool.flat("ent_loss", rt.group if rt.group > 1 else 1)
-            ops.memo_loss_items(logits, dlogits, self.view_axes, partial, loss, softmax=self.softmax)
-            if ar.n_train > 0:
-                rt.run_backward(dlogits)
-                self.optimizer_step(n // V)
-        finally:
-            rt.use_sets = False
+        rt = self.rt          # (batch items [g * V, (g + 1) * V) read / write parameter replica g)
+        rt.pack_all()
+        logits = self._forward(xv, present)
+        dlogits = self._dlogits(logits)
+        partial = rt.pool.flat("memo_partial", ops.memo_partials(logits, self.views), dtype=torch.float64)
+        loss = rt.pool.flat("ent_loss", rt.group)
+        ops.memo_loss_items(logits, dlogits, self.view_axes, partial, loss, softmax=self.softmax)
+        if rt.arena.n_train > 0:
+            rt.run_backward(dlogits)
+            self.optimizer_step(int(logits.shape[0]) // self.views)
 
     # ------------------------------------------------------------------ per volume
-    @torch.no_grad()
-    def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
-        """As ``entmin_tta.adapt_volume``: x [B,C,D,H,W] (B <= ``method.group`` volumes), the final logits of the volumes
-        ([B,D,H,W,R] channels-last, in the volumes' own frame) and the per-step losses."""
-        if self.rt is None or self.views == 1:
-            return super().adapt_volume(x, steps)
-        rt, ar = self.rt, self.rt.arena
-        V = self.views
-        steps = self.steps if steps is None else int(steps)
-        B = int(x.shape[0])
-        if B > rt.group:
-            raise ValueError(f"method.group = {rt.group}: at most {rt.group} volumes per call, got {B}")
-        if self.episodic:
-            ar.restore_source()
-            rt.restore_buffers()
-        C = x.shape[1]
-        masked = bool(self.missing)
-        base_present = modality_mask(C, self.missing, 0.0, None)
-        x = x.float()
-        wants_present = masked and getattr(rt, "supports_present", False)
-        restage = masked and not getattr(rt, "input_mask_on_load", False)
-        # mask, then mirror: the views are views of the volume the network is given
-        x_cl = rt.stage_input(drop_modality(x, base_present) if restage else x)
-        present = base_present if wants_present else None
-        grouped = rt.group > 1
-        loss_hist = rt.pool.flat("loss_hist", max(steps, 1) * (B if grouped else 1))
-        loss_buf = rt.pool.flat("ent_loss", rt.group if grouped else 1)
-        if grouped:
-            loss_hist = loss_hist.view(max(steps, 1), B)
-        rt.views = V          # every launch below carries V consecutive batch items per volume
-        try:
-            xv = rt.stage_views(x_cl, self.view_axes)
-            for t in range(steps):
-                self._step(xv, present)
-                if grouped:
-                    loss_hist[t].copy_(loss_buf[:B])
-                else:
-                    loss_hist[t:t + 1].copy_(loss_buf)
-            rt.training = False
-            ops.Workspace.lane = self.lane
-            rt.use_sets = grouped
-            rt.pack_all()
-            if self.ensemble:
-                zv = rt.forward_cl(xv, present=present) if wants_present else rt.forward_cl(xv)
-                n, d, h, w, r = zv.shape
-                logits_cl = rt.pool.cl("memo_ensemble", B, d, h, w, r, ldc=(r + 3) // 4 * 4)
-                ops.memo_ensemble(zv, logits_cl, self.view_axes, softmax=self.softmax)
-            else:
-                rt.views = 1          # the volumes alone: one batch item per replica again
-                logits_cl = rt.forward_cl(x_cl, present=present) if wants_present else rt.forward_cl(x_cl)
-        finally:
-            rt.use_sets = False
-            rt.views = 1
-        losses = loss_hist[:steps]
-        return {"logits_cl": logits_cl, "losses": losses[:, 0] if (grouped and B == 1) else losses}
+    def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
+        if self.views == 1:
+            return super()._stage(x_cl)
+        self.rt.views = self.views          # every launch of the loop carries V consecutive batch items per volume
+        return self.rt.stage_views(x_cl, self.view_axes), ()
+
+    def _final_logits(self, x_cl: torch.Tensor, xv: torch.Tensor, present: Optional[Sequence[bool]]) -> torch.Tensor:
+        if self.views == 1 or not self.ensemble:
+            self.rt.views = 1          # the volumes alone: one batch item per replica again
+            return super()._final_logits(x_cl, xv, present)
+        zv = self._forward(xv, present)
+        n, d, h, w, r = zv.shape
+        logits_cl = self.rt.pool.cl("memo_ensemble", int(x_cl.shape[0]), d, h, w, r, ldc=(r + 3) // 4 * 4)
+        ops.memo_ensemble(zv, logits_cl, self.view_axes, softmax=self.softmax)
+        return logits_cl

@@ -14,12 +14,13 @@ differs from the classification paper: the elements are voxels (or voxel x regio
 fraction of ln K so that one default serves both heads; SAR's model-recovery reset is not built (it targets continual runs,
 this package resets every volume).
 
-Everything else - episodic reset, groups, lanes, the captured step, the final forward - is ``entmin_tta``'s.
+The class is its step (``_update``) and one more per-step record; the per-volume loop, the captured step and the final
+forward are ``EntropyMinimizationTTA``'s.
 """
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, Optional, Sequence
+from typing import Any, Optional, Sequence
 
 import torch
 
@@ -44,8 +45,6 @@ class SharpnessAwareReliableTTA(EntropyMinimizationTTA):
             raise ValueError(f"method.sar.e_margin = {self.e_margin}: expected a finite positive fraction of ln K")
         if not (math.isfinite(self.rho) and self.rho >= 0.0):
             raise ValueError(f"method.sar.rho = {self.rho}: expected a finite radius >= 0")
-        self._kept_hist: Optional[torch.Tensor] = None
-        self._t = 0
 
     def setup(self, model, device) -> "SharpnessAwareReliableTTA":
         if not select_params(model, self.params_spec):
@@ -58,71 +57,36 @@ class SharpnessAwareReliableTTA(EntropyMinimizationTTA):
         return self.e_margin * math.log(float(regions) if self.softmax else 2.0)
 
     # ------------------------------------------------------------------ one step
-    def _step_launches(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+    # ``losses`` holds L1 per step, ``kept`` the number of elements that passed the first filter
+    records = EntropyMinimizationTTA.records + (("kept", "sar_kept", torch.int64),)
+
+    def _update(self, x: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
         rt, ar = self.rt, self.rt.arena
-        ops.Workspace.lane = self.lane
-        rt.training = True
-        rt.use_sets = rt.group > 1          # batch item g reads / writes parameter replica g
-        try:
-            def forward() -> torch.Tensor:
-                return rt.forward_cl(x_cl) if present is None else rt.forward_cl(x_cl, present=present)
-
-            rt.pack_all()
-            logits = forward()
-            n, d, h, w, r = logits.shape
-            gdt = rt.thin_grad_dtype() if (not self.softmax and r <= 4) else torch.float32
-            dlogits = rt.pool.cl("dlogits", n, d, h, w, r, ldc=(r + 3) // 4 * 4, dtype=gdt)
-            slots = rt.group if rt.group > 1 else 1
-            elems = n * d * h * w * (1 if self.softmax else r)
-            margin = self.margin(r)
-            partial = rt.pool.flat("sar_partial", ops.entropy_filtered_partials(logits), dtype=torch.float64)
-            loss1 = rt.pool.flat("ent_loss", slots)          # adapt_volume records L1 from here
-            loss2 = rt.pool.flat("sar_loss2", slots)
-            kept1 = rt.pool.flat("sar_kept", slots, dtype=torch.int64)
-            kept2 = rt.pool.flat("sar_kept2", slots, dtype=torch.int64)
-            keep1 = rt.pool.flat("sar_keep1", elems, dtype=torch.uint8)
-            keep2 = rt.pool.flat("sar_keep2", elems, dtype=torch.uint8)
-            ops.entropy_filtered_items(logits, dlogits, margin, None, keep1, partial, loss1, kept1, softmax=self.softmax)
-            rt.run_backward(dlogits)
-            # ascent: w_saved = w, w += rho g1 / ||g1|| per replica in use; the packed images follow the arena
-            sets = min(n, ar.replicas)
-            saved = rt.pool.flat("sar_saved", ar.replicas * ar.n_train).view(ar.replicas, ar.n_train)
-            sam_partial = rt.pool.flat("sar_sam_partial", ops.sam_ascent_partials(ar.n_train, sets), dtype=torch.float64)
-            ops.sam_ascent_sets(ar.params_all, ar.grads_all, saved, sam_partial, ar.n_train, sets, self.rho)
-            rt.pack_all()
-            logits = forward()
-            ops.entropy_filtered_items(logits, dlogits, margin, keep1, keep2, partial, loss2, kept2, softmax=self.softmax)
-            rt.run_backward(dlogits)
-            # exact restore (SAR's SAM copies old_p back), then the base optimizer with the gradient taken at w + eps
-            ar.params_all[:sets, :ar.n_train].copy_(saved[:sets])
-            self.optimizer_step(n)
-        finally:
-            rt.use_sets = False
-
-    def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
-        super()._step(x_cl, present)
-        if self._kept_hist is not None:
-            B = int(x_cl.shape[0])
-            self._kept_hist[self._t].copy_(self.rt.pool.flat("sar_kept", self.rt.group if self.rt.group > 1 else 1,
-                                                             dtype=torch.int64)[:B])
-            self._t += 1
-
-    # ------------------------------------------------------------------ per volume
-    @torch.no_grad()
-    def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
-        """As ``entmin_tta.adapt_volume``; ``losses`` holds L1 per step, ``kept`` the number of elements that passed the
-        first filter per step ([steps], or [steps, B] for a group of B > 1 volumes)."""
-        if self.rt is None:
-            return super().adapt_volume(x, steps)          # raises
-        steps = self.steps if steps is None else int(steps)
-        B = int(x.shape[0])
-        grouped = self.rt.group > 1
-        hist = self.rt.pool.flat("sar_kept_hist", max(steps, 1) * B, dtype=torch.int64).view(max(steps, 1), B)
-        self._kept_hist, self._t = hist, 0
-        try:
-            out = super().adapt_volume(x, steps)
-        finally:
-            self._kept_hist = None
-        kept = hist[:steps]
-        out["kept"] = kept[:, 0] if (not grouped or B == 1) else kept
-        return out
+        rt.pack_all()
+        logits = self._forward(x, present)
+        dlogits = self._dlogits(logits)
+        n, d, h, w, r = logits.shape
+        slots = rt.group
+        elems = n * d * h * w * (1 if self.softmax else r)
+        margin = self.margin(r)
+        partial = rt.pool.flat("sar_partial", ops.entropy_filtered_partials(logits), dtype=torch.float64)
+        loss1 = rt.pool.flat("ent_loss", slots)          # the recorded loss is L1
+        loss2 = rt.pool.flat("sar_loss2", slots)
+        kept1 = rt.pool.flat("sar_kept", slots, dtype=torch.int64)
+        kept2 = rt.pool.flat("sar_kept2", slots, dtype=torch.int64)
+        keep1 = rt.pool.flat("sar_keep1", elems, dtype=torch.uint8)
+        keep2 = rt.pool.flat("sar_keep2", elems, dtype=torch.uint8)
+        ops.entropy_filtered_items(logits, dlogits, margin, None, keep1, partial, loss1, kept1, softmax=self.softmax)
+        rt.run_backward(dlogits)
+        # ascent: w_saved = w, w += rho g1 / ||g1|| per replica in use; the packed images follow the arena
+        sets = min(n, ar.replicas)
+        saved = rt.pool.flat("sar_saved", ar.replicas * ar.n_train).view(ar.replicas, ar.n_train)
+        sam_partial = rt.pool.flat("sar_sam_partial", ops.sam_ascent_partials(ar.n_train, sets), dtype=torch.float64)
+        ops.sam_ascent_sets(ar.params_all, ar.grads_all, saved, sam_partial, ar.n_train, sets, self.rho)
+        rt.pack_all()
+        logits = self._forward(x, present)
+        ops.entropy_filtered_items(logits, dlogits, margin, keep1, keep2, partial, loss2, kept2, softmax=self.softmax)
+        rt.run_backward(dlogits)
+        # exact restore (SAR's SAM copies old_p back), then the base optimizer with the gradient taken at w + eps
+        ar.params_all[:sets, :ar.n_train].copy_(saved[:sets])
+        self.optimizer_step(n)

@@ -180,40 +180,58 @@ class EntropyMinimizationTTA:
         # the wide 27-tap layers step their optimizer and repack their images inside their weight-gradient launch
         self.rt.enable_fused_update(self.optim if self.fused_update else None)
         self._graphs.clear()
+        if self.tune_volumes is None and self.views > 1:
+            # `auto`: launch geometry for the items of the widest launches - lanes x group x views, with the group the runtime
+            # settled on (models that fall back to group 1 are tuned for group 1)
+            ops.tune_for_volumes_in_flight(self.lanes * self.group * self.views)
         return self
 
     # ------------------------------------------------------------------ one step
-    def _step_launches(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
-        rt, ar = self.rt, self.rt.arena
+    def _step_launches(self, x: torch.Tensor, present: Optional[Sequence[bool]], *views: torch.Tensor) -> None:
+        """The launches of one step (what the graph captures): the method's ``_update`` between the runtime's switches."""
+        rt = self.rt
         ops.Workspace.lane = self.lane
         rt.training = True
-        rt.use_sets = rt.group > 1          # batch item g reads / writes parameter replica g
+        rt.use_sets = rt.group > 1          # the batch items of volume g read / write parameter replica g
+        loop_views = rt.views
         try:
-            rt.pack_all(fused_current=True)
-            logits = rt.forward_cl(x_cl) if present is None else rt.forward_cl(x_cl, present=present)
-            n, d, h, w, r = logits.shape
-            # (the categorical objective writes fp32 only)
-            gdt = rt.thin_grad_dtype() if (not self.softmax and r <= 4) else torch.float32
-            dlogits = rt.pool.cl("dlogits", n, d, h, w, r, ldc=(r + 3) // 4 * 4, dtype=gdt)
-            if rt.group > 1:
-                # every volume of the group is its own objective (own mean, own gradient scale): loss [group]
-                partial = rt.pool.flat("ent_partial", ops.entropy_partials_items(logits), dtype=torch.float64)
-                loss = rt.pool.flat("ent_loss", rt.group)
-                ops.entropy_loss_items(logits, dlogits, partial, loss, softmax=self.softmax)
-            else:
-                partial = rt.pool.flat("ent_partial", ops.entropy_partials(logits), dtype=torch.float64)
-                loss = rt.pool.flat("ent_loss", 1)
-                ops.entropy_loss(logits, dlogits, partial, loss, softmax=self.softmax)
-            if ar.n_train > 0:
-                fused = bool(rt.fused_layers)
-                rt.fused_active = fused         # only this backward updates the fused layers in place
-                try:
-                    rt.run_backward(dlogits)
-                finally:
-                    rt.fused_active = False
-                self.optimizer_step(n, fused=fused)
+            self._update(x, present, *views)
         finally:
             rt.use_sets = False
+            rt.views = loop_views
+
+    def _forward(self, x: torch.Tensor, present: Optional[Sequence[bool]]) -> torch.Tensor:
+        return self.rt.forward_cl(x) if present is None else self.rt.forward_cl(x, present=present)
+
+    def _dlogits(self, logits: torch.Tensor) -> torch.Tensor:
+        """The step's gradient buffer for ``logits`` (the categorical objectives write fp32 only)."""
+        n, d, h, w, r = logits.shape
+        gdt = self.rt.thin_grad_dtype() if (not self.softmax and r <= 4) else torch.float32
+        return self.rt.pool.cl("dlogits", n, d, h, w, r, ldc=(r + 3) // 4 * 4, dtype=gdt)
+
+    def _update(self, x: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+        """The method's own launch sequence: pack, forward, objective, backward, optimizer.  It leaves every per-step record
+        (``records``) in its pool buffer, one slot per replica."""
+        rt, ar = self.rt, self.rt.arena
+        rt.pack_all(fused_current=True)
+        logits = self._forward(x, present)
+        dlogits = self._dlogits(logits)
+        loss = rt.pool.flat("ent_loss", rt.group)
+        if rt.group > 1:
+            # every volume of the group is its own objective (own mean, own gradient scale): loss [group]
+            partial = rt.pool.flat("ent_partial", ops.entropy_partials_items(logits), dtype=torch.float64)
+            ops.entropy_loss_items(logits, dlogits, partial, loss, softmax=self.softmax)
+        else:
+            partial = rt.pool.flat("ent_partial", ops.entropy_partials(logits), dtype=torch.float64)
+            ops.entropy_loss(logits, dlogits, partial, loss, softmax=self.softmax)
+        if ar.n_train > 0:
+            fused = bool(rt.fused_layers)
+            rt.fused_active = fused         # only this backward updates the fused layers in place
+            try:
+                rt.run_backward(dlogits)
+            finally:
+                rt.fused_active = False
+            self.optimizer_step(int(logits.shape[0]), fused=fused)
 
     def optimizer_step(self, volumes: int = 1, fused: bool = False) -> None:
         """The arena optimizer: ONE launch over [decay | no-decay] of every replica in use (+ the device step counter).
@@ -232,16 +250,9 @@ class EntropyMinimizationTTA:
         ops.optim_step(self.optim, ar.params[:ar.n_train], ar.grads[:ar.n_train], ar.exp_avg[:ar.n_train],
                        ar.exp_avg_sq[:ar.n_train], ar.n_decay, ar.step)
 
-    # hyper-parameters under their old attribute names (tests, scripts)
-    lr = property(lambda self: self.optim.lr)
-    beta1 = property(lambda self: self.optim.beta1)
-    beta2 = property(lambda self: self.optim.beta2)
-    eps = property(lambda self: self.optim.eps)
-    weight_decay = property(lambda self: self.optim.weight_decay)
-
-    def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+    def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]], *views: torch.Tensor) -> None:
         if not self.use_graph:
-            self._step_launches(x_cl, present)
+            self._step_launches(x_cl, present, *views)
             return
         key = (tuple(x_cl.shape), x_cl.data_ptr(), None if present is None else tuple(present))
         g = self._graphs.get(key)
@@ -255,7 +266,7 @@ class EntropyMinimizationTTA:
             if on_default:
                 work.wait_stream(cur)
             with torch.cuda.stream(work):
-                self._step_launches(x_cl, present)
+                self._step_launches(x_cl, present, *views)
             if on_default:
                 cur.wait_stream(work)
             torch.cuda.synchronize()
@@ -265,7 +276,7 @@ class EntropyMinimizationTTA:
                                             self.lane))
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=work):
-                    self._step_launches(x_cl, present)
+                    self._step_launches(x_cl, present, *views)
             except Exception as exc:  # capture is an optimisation: the eager launches are the same kernels
                 warnings.warn(f"hipGraph capture failed ({exc}); running the step eagerly")
                 self.use_graph = False
@@ -278,21 +289,39 @@ class EntropyMinimizationTTA:
         g.replay()
 
     # ------------------------------------------------------------------ per volume
+    # what is read after every step: (result key, pool buffer with one slot per replica, dtype).  The loop keeps the history
+    # and returns it under the result key, [steps] - or [steps, B] for B > 1 volumes of a group
+    records: Tuple[Tuple[str, str, torch.dtype], ...] = (("losses", "ent_loss", torch.float32),)
+
+    def _reset(self) -> None:
+        """The episodic reset at the start of a volume: weights, optimizer state and running statistics of the source."""
+        self.rt.arena.restore_source()
+        self.rt.restore_buffers()
+
+    def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
+        """What ``_update`` is given every step: its input and any further tensors, from the staged volumes ``x_cl``.  A
+        method whose step input is views sets ``rt.views`` here; the loop keeps it until ``_final_logits`` and resets it."""
+        return x_cl, ()
+
+    def _final_logits(self, x_cl: torch.Tensor, x_step: torch.Tensor, present: Optional[Sequence[bool]]) -> torch.Tensor:
+        """The returned logits: the eval-mode forward of the staged volumes (the images are packed)."""
+        return self._forward(x_cl, present)
+
     @torch.no_grad()
     def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
         """x: [1,C,D,H,W] fp32 on the plugin's device - or, with ``method.group`` = G > 1, up to G volumes [B,C,D,H,W]
         that adapt independently (volume b on parameter replica b).  Returns the final logits (channels-last view
-        [B,D,H,W,R]) and the per-step losses ([steps], or [steps, B] for a group)."""
+        [B,D,H,W,R]) and the per-step ``records``: the losses ([steps], or [steps, B] for a group)."""
         if self.rt is None:
             raise MmttaError("call setup(model, device) first")
-        rt, ar = self.rt, self.rt.arena
+        rt = self.rt
         steps = self.steps if steps is None else int(steps)
         B = int(x.shape[0])
-        if rt.group > 1 and B > rt.group:
+        # (without a group the batch items share the one weight set: any number of them - unless they are a volume's views)
+        if B > rt.group and (rt.group > 1 or self.views > 1):
             raise ValueError(f"method.group = {rt.group}: at most {rt.group} volumes per call, got {B}")
         if self.episodic:
-            ar.restore_source()
-            rt.restore_buffers()
+            self._reset()
         C = x.shape[1]
         masked = bool(self.missing) or self.moddrop_p > 0.0
         gen = torch.Generator().manual_seed(self.moddrop_seed) if self.moddrop_p > 0.0 else None
@@ -300,38 +329,39 @@ class EntropyMinimizationTTA:
         x = x.float()
         wants_present = masked and getattr(rt, "supports_present", False)
         # a runtime that applies the mask while its first level stages the input (models/unet.py) reads the volume as it is;
-        # the others get the masked volume re-staged whenever the mask changes
+        # the others get the masked volume re-staged whenever the mask changes (mask, then mirror: views are staged from it)
         restage = masked and not getattr(rt, "input_mask_on_load", False)
         x_cl = rt.stage_input(drop_modality(x, base_present) if restage else x)
         grouped = rt.group > 1
-        loss_hist = rt.pool.flat("loss_hist", max(steps, 1) * (B if grouped else 1))
-        loss_buf = rt.pool.flat("ent_loss", rt.group if grouped else 1)
-        if grouped:
-            loss_hist = loss_hist.view(max(steps, 1), B)
-        for t in range(steps):
-            present = None
-            if masked:
-                p = modality_mask(C, self.missing, self.moddrop_p, gen)
-                if self.moddrop_p > 0.0 and restage:
-                    rt.stage_input(drop_modality(x, p))
-                present = p if wants_present else None
-            self._step(x_cl, present)
-            if grouped:
-                loss_hist[t].copy_(loss_buf[:B])
-            else:
-                loss_hist[t:t + 1].copy_(loss_buf)
-        if masked and self.moddrop_p > 0.0 and restage:
-            rt.stage_input(drop_modality(x, base_present))
-        rt.training = False
-        ops.Workspace.lane = self.lane
-        rt.use_sets = grouped
+        rows, width = max(steps, 1), B if grouped else 1
+        recs = [(key, rt.pool.flat(buf, rt.group, dtype=dt, zero=True),
+                 rt.pool.flat(buf + "_hist", rows * width, dtype=dt).view(rows, width)) for key, buf, dt in self.records]
         try:
+            x_step, views = self._stage(x_cl)
+            for t in range(steps):
+                present = None
+                if masked:
+                    p = modality_mask(C, self.missing, self.moddrop_p, gen)
+                    if self.moddrop_p > 0.0 and restage:
+                        rt.stage_input(drop_modality(x, p))
+                    present = p if wants_present else None
+                self._step(x_step, present, *views)
+                for _, buf, hist in recs:
+                    hist[t].copy_(buf[:width])
+            if masked and self.moddrop_p > 0.0 and restage:
+                rt.stage_input(drop_modality(x, base_present))
+            rt.training = False
+            ops.Workspace.lane = self.lane
+            rt.use_sets = grouped
             rt.pack_all(fused_current=True)
-            logits_cl = (rt.forward_cl(x_cl, present=base_present) if wants_present else rt.forward_cl(x_cl))
+            logits_cl = self._final_logits(x_cl, x_step, base_present if wants_present else None)
         finally:
             rt.use_sets = False
-        losses = loss_hist[:steps]
-        return {"logits_cl": logits_cl, "losses": losses[:, 0] if (grouped and B == 1) else losses}
+            rt.views = 1
+        out = {"logits_cl": logits_cl}
+        for key, _, hist in recs:
+            out[key] = hist[:steps, 0] if width == 1 else hist[:steps]
+        return out
 
     def logits(self, result: Dict[str, Any]) -> torch.Tensor:
         return ops.from_cl(result["logits_cl"])

@@ -51,15 +51,15 @@ def run(arm, lanes, volumes):
     if arm == "no_pack":
         orig_pack = engine.Runtime.pack_all
         done = set()
-        def pack(self):
+        def pack(self, fused_current=False):
             if id(self) not in done or len(done) < 0:
                 done.add(id(self))
-                return orig_pack(self)
+                return orig_pack(self, fused_current)
             if not hasattr(self, "_npack"):
                 self._npack = 0
             self._npack += 1
             if self._npack < 3:
-                return orig_pack(self)
+                return orig_pack(self, fused_current)
         patch(engine.Runtime, "pack_all", pack)
     if arm == "no_wgrad":
         patch(engine.ConvLayer, "wgrad", lambda self, x, x_nl, dy, accumulate=False: None)
@@ -67,7 +67,7 @@ def run(arm, lanes, volumes):
         patch(ops.ConvOp, "dgrad", lambda self, dy, dx, accumulate=False: None)
     if arm == "no_optimizer":
         from multimodal_tta_amd import tta
-        patch(tta.EntropyMinimizationTTA, "optimizer_step", lambda self: None)
+        patch(tta.EntropyMinimizationTTA, "optimizer_step", lambda self, volumes=1, fused=False: None)
 
     device = torch.device("cuda", 0)
     cfg = compose(overrides=["task=brats", "dataset=brats", "model=unet", "method=tta_entmin", "method.steps=10",

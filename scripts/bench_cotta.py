@@ -12,68 +12,15 @@ file.
 usage: python scripts/bench_cotta.py [--lanes 3] [--group 8] [--cotta-group 2] [--views 1 2 4] [--volumes 48] [--out FILE]
 """
 import argparse
-import gc
 import json
 import os
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from multimodal_tta_amd import _lib  # noqa: E402
-
-MODEL = dict(name="unet", in_channels=4, num_classes=3, spatial_dims=3, channels=[32, 64, 128, 256, 512],
-             strides=[2, 2, 2, 2], num_res_units=2, norm="INSTANCE", act="RELU", dropout=0.0)
-AXES = {1: [], 2: ["w"], 4: ["h", "w"], 8: ["d", "h", "w"]}
-
-
-class Method:
-    """`lanes` plugins (own model replica, stream and graph each) adapting `group` volumes per launch sequence."""
-
-    def __init__(self, method, lanes, group, streams, device, steps, views=None):
-        from multimodal_tta_amd.config import compose
-        from multimodal_tta_amd.models import UNet
-        from multimodal_tta_amd.registry import get_plugin
-
-        self.lanes, self.group = lanes, group
-        cfg = compose(overrides=["task=brats", "model=unet", f"method={method}"])
-        cfg["model"] = dict(MODEL)
-        cfg["method"].update(steps=steps, precision="bf16", group=group, lanes=lanes)
-        if views is not None:
-            cfg["method"]["cotta"]["mirror_axes"] = AXES[views]
-        self.streams = streams[:lanes]
-        self.plugs = []
-        for lane in range(lanes):
-            torch.manual_seed(42)
-            p = get_plugin(str(cfg["method"]["name"]))(cfg)
-            p.lane = lane
-            self.plugs.append(p.setup(UNet(dict(MODEL)), device))
-
-    def round(self, xs):
-        for lane in range(self.lanes):
-            lo = lane * self.group
-            with torch.cuda.stream(self.streams[lane]):
-                self.plugs[lane].adapt_volume(xs[lo:lo + self.group])
-        return self.lanes * self.group
-
-
-def measure(make, xs, volumes, device):
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats(device)
-    m = make()
-    m.round(xs)                                         # warm-up: capture
-    torch.cuda.synchronize()
-    n, t0 = 0, time.perf_counter()
-    while n < volumes:
-        n += m.round(xs)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    peak = torch.cuda.max_memory_allocated(device) / 2 ** 30
-    del m
-    gc.collect()
-    torch.cuda.empty_cache()
-    return round(n / dt, 2), round(peak, 2), n
+from method_bench import AXES, Method, measure  # noqa: E402
 
 
 def main():
@@ -98,7 +45,8 @@ def main():
     out = {"workload": f"unet INSTANCE {a.shape[0]}x{a.shape[1]}x{a.shape[2]} S={a.steps} bf16", "lanes": a.lanes,
            "entmin": {"group": a.group, "volumes_per_s": rate, "peak_memory_gb": peak, "timed_volumes": n}, "cotta": {}}
     for v in a.views:
-        r, p, n = measure(lambda: Method("tta_cotta", a.lanes, a.cotta_group, streams, device, a.steps, views=v), xs,
+        cotta = ("cotta", {"mirror_axes": AXES[v]})
+        r, p, n = measure(lambda: Method("tta_cotta", a.lanes, a.cotta_group, streams, device, a.steps, cotta), xs,
                           a.volumes, device)
         out["cotta"][f"V{v}"] = {"group": a.cotta_group, "volumes_per_s": r, "peak_memory_gb": p, "timed_volumes": n,
                                  "over_entmin": round(r / rate, 3), "over_expected": round(r / (rate * 3.0 / (3.0 + v)), 3)}

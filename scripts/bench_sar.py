@@ -18,42 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from multimodal_tta_amd import _lib  # noqa: E402
-
-MODEL = dict(name="unet", in_channels=4, num_classes=3, spatial_dims=3, channels=[32, 64, 128, 256, 512],
-             strides=[2, 2, 2, 2], num_res_units=2, norm="INSTANCE", act="RELU", dropout=0.0)
-
-
-class Method:
-    """`lanes` plugins (own model replica, stream and graph each) adapting `group` volumes per launch sequence."""
-
-    def __init__(self, name, method, lanes, group, streams, device, steps, sar):
-        from multimodal_tta_amd.config import compose
-        from multimodal_tta_amd.models import UNet
-        from multimodal_tta_amd.registry import get_plugin
-
-        self.name, self.lanes, self.group = name, lanes, group
-        cfg = compose(overrides=["task=brats", "model=unet", f"method={method}"])
-        cfg["model"] = dict(MODEL)
-        cfg["method"].update(steps=steps, precision="bf16", group=group, lanes=lanes)
-        if "sar" in cfg["method"]:
-            cfg["method"]["sar"] = dict(sar)
-        self.streams = streams[:lanes]
-        self.plugs = []
-        self.kept = None
-        for lane in range(lanes):
-            torch.manual_seed(42)
-            p = get_plugin(str(cfg["method"]["name"]))(cfg)
-            p.lane = lane
-            self.plugs.append(p.setup(UNet(dict(MODEL)), device))
-
-    def round(self, xs):
-        for lane in range(self.lanes):
-            lo = lane * self.group
-            with torch.cuda.stream(self.streams[lane]):
-                r = self.plugs[lane].adapt_volume(xs[lo:lo + self.group])
-            if lane == 0 and "kept" in r:
-                self.kept = r["kept"]
-        return self.lanes * self.group
+from method_bench import Method  # noqa: E402
 
 
 def main():
@@ -73,24 +38,24 @@ def main():
     streams = ops.lane_streams(a.lanes, device)
     n_in = a.lanes * a.group
     xs = torch.stack([synth_volume(i, 4, tuple(a.shape), 3)["image"] for i in range(n_in)]).to(device)
-    sar = {"e_margin": a.e_margin, "rho": a.rho}
-    methods = [Method("entmin_tta", "tta_entmin", a.lanes, a.group, streams, device, a.steps, sar),
-               Method("sar_tta", "tta_sar", a.lanes, a.group, streams, device, a.steps, sar)]
-    for m in methods:                                   # warm-up: capture
+    sar = ("sar", {"e_margin": a.e_margin, "rho": a.rho})
+    methods = {"entmin_tta": Method("tta_entmin", a.lanes, a.group, streams, device, a.steps),
+               "sar_tta": Method("tta_sar", a.lanes, a.group, streams, device, a.steps, sar)}
+    for m in methods.values():                          # warm-up: capture
         m.round(xs)
     torch.cuda.synchronize()
-    t = {m.name: 0.0 for m in methods}
-    n = {m.name: 0 for m in methods}
+    t = {name: 0.0 for name in methods}
+    n = {name: 0 for name in methods}
     while min(n.values()) < a.volumes:                  # alternated, one round per method and turn
-        for m in methods:
+        for name, m in methods.items():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            n[m.name] += m.round(xs)
+            n[name] += m.round(xs)
             torch.cuda.synchronize()
-            t[m.name] += time.perf_counter() - t0
+            t[name] += time.perf_counter() - t0
     rate = {k: round(n[k] / t[k], 2) for k in n}
     elems = a.shape[0] * a.shape[1] * a.shape[2] * 3
-    kept = methods[1].kept.float() / elems
+    kept = methods["sar_tta"].result["kept"].float() / elems
     print(json.dumps({"workload": f"unet INSTANCE {a.shape[0]}x{a.shape[1]}x{a.shape[2]} S={a.steps} bf16",
                       "lanes": a.lanes, "group": a.group, "e_margin": a.e_margin, "rho": a.rho, "timed_volumes": n,
                       "entmin_volumes_per_s": rate["entmin_tta"], "sar_volumes_per_s": rate["sar_tta"],
