@@ -554,6 +554,53 @@ int mmtta_cotta_update_sets(float* w, float* teacher, const float* source, int64
                             int64_t teacher_stride, double alpha, float restore_p, uint64_t seed, const int32_t* step,
                             const int32_t* ordinals, int64_t* partial, int64_t* restored, void* stream);
 
+/* ------------------------------------------------------------------ EATA ----------------- */
+/* EATA (Niu et al., ICML 2022) - csrc/eata.hip.
+ *
+ * mmtta_entropy_weighted_items: the weighted reliable entropy of N independent items.  Elements, margin, mask layout, partial
+ *   layout, storages (fp32 logits; fp32 or - on the <= 4-region fast path - bf16 thin gradients) and the three launches are
+ *   those of mmtta_entropy_filtered_items without `keep_in`; the entropy arithmetic is that entry point's, so keep_out and
+ *   kept equal its results bit for bit.  Per item, with c = exp(margin - H) (a constant of the gradient, 1 < c <= e^margin):
+ *     keep = H < margin;  loss = sum_keep c H / |keep|;  dlogits = keep * c * dH/dz / |keep|
+ *   An empty filter gives loss NaN, kept 0 and a zero gradient.  N items in one call equal N calls bit for bit.
+ *   Softmax head: `keep` is decided with the filtered entry point's H = lse(z) - sum p z (hence the equal masks), while c,
+ *   the loss and the gradient use H in the shifted form log sum exp(z - max) - sum p (z - max), which does not carry the
+ *   largest logit's rounding.  The two differ at fp32 rounding level; an element they put on different sides of the margin
+ *   is kept with c = 1 (c is held to exp(margin - min(H, margin))), so there 1 <= c.
+ *     partial  fp64 [mmtta_entropy_weighted_partials(logits)] scratch
+ *
+ * mmtta_pseudo_label_loss_items: the loss the Fisher estimate differentiates, per item, one pass + finish, the storages of
+ *   mmtta_consistency_loss_items.  Sigmoid head: y = 1[z >= 0], loss = mean over (voxel, region) of BCE(z, y) =
+ *   log1p(exp(-|z|)), dlogits = (sigmoid(z) - y) / count.  Softmax head: y = one-hot of the first arg max, loss = mean over
+ *   voxels of lse(z) - max z, dlogits = (softmax(z) - y) / count.
+ *     partial  fp64 [mmtta_pseudo_label_partials(logits)] scratch
+ *
+ * mmtta_fisher_accumulate_sets: F_i <- F_i + g_{s,i}^2 for s = 0 .. sets-1 in that order over [0, n) of `grads` (set s starts
+ *   at s * set_stride); fp32, the product and the sum rounded separately.  mmtta_fisher_scale: F_i <- F_i / count (IEEE fp32
+ *   division; count >= 1), the end of an estimate.  n need not be a multiple of 4; set_stride is, buffers are 16-byte aligned.
+ *
+ * mmtta_fisher_penalty_sets: over [0, n) of the first `sets` of `replicas` arena replicas ([replica][set_stride]), with the
+ *   shared `fisher` and `source` spans ([n]):
+ *     g += 2 lambda F (w - source);  penalty[s] = lambda sum_i F_i (w_i - source_i)^2
+ *   fp32 elementwise arithmetic with separate roundings, fp64 block partials summed per set in a fixed order.  16 B read and
+ *   4 B written per parameter and set.  n and set_stride multiples of 4, n <= set_stride, 1 <= sets <= replicas, lambda
+ *   finite and >= 0, buffers 16-byte aligned.
+ *     partial  fp64 [mmtta_fisher_penalty_partials(n, sets)] scratch;  penalty  fp32 [sets]
+ *
+ * Bad arguments (null pointers, shape mismatches, a margin that is not finite and positive, a bad lambda, count or stride)
+ * are MMTTA_ERR_INVALID, storages without a kernel MMTTA_ERR_UNSUPPORTED, both before anything is launched. */
+int64_t mmtta_entropy_weighted_partials(const mmtta_tensor* logits);
+int mmtta_entropy_weighted_items(const mmtta_tensor* logits, int softmax, float margin, uint8_t* keep_out,
+                                 const mmtta_tensor* dlogits, double* partial, float* loss, int64_t* kept, void* stream);
+int64_t mmtta_pseudo_label_partials(const mmtta_tensor* logits);
+int mmtta_pseudo_label_loss_items(const mmtta_tensor* logits, int softmax, const mmtta_tensor* dlogits, double* partial,
+                                  float* loss, void* stream);
+int mmtta_fisher_accumulate_sets(float* fisher, const float* grads, int64_t n, int sets, int64_t set_stride, void* stream);
+int mmtta_fisher_scale(float* fisher, int64_t n, float count, void* stream);
+int64_t mmtta_fisher_penalty_partials(int64_t n, int sets);
+int mmtta_fisher_penalty_sets(const float* w, float* g, const float* fisher, const float* source, int64_t n, int sets,
+                              int replicas, int64_t set_stride, float lambda, double* partial, float* penalty, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

@@ -164,6 +164,16 @@ _SIGNATURES = {
     "mmtta_cotta_update_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64,
                                           C.c_double, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "mmtta_entropy_weighted_partials": (C.c_int64, [_P(Tensor)]),
+    "mmtta_entropy_weighted_items": (C.c_int, [_P(Tensor), C.c_int, C.c_float, C.c_void_p, _P(Tensor), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "mmtta_pseudo_label_partials": (C.c_int64, [_P(Tensor)]),
+    "mmtta_pseudo_label_loss_items": (C.c_int, [_P(Tensor), C.c_int, _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_fisher_accumulate_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p]),
+    "mmtta_fisher_scale": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "mmtta_fisher_penalty_partials": (C.c_int64, [C.c_int64, C.c_int]),
+    "mmtta_fisher_penalty_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                            C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mmtta_optim_step": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,

@@ -9,16 +9,7 @@ namespace mmtta {
 constexpr int ENT_MAX_BLOCKS = 2048;
 constexpr int ENT_MAX_R = 16;
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  return t;  // valid on thread 0
-}
+// block_sum_d: common.h
 
 __global__ __launch_bounds__(256) void entropy_bernoulli_kernel(TV z, TV dz, double* partial, float inv_count, int per_item) {
   __shared__ double sh[4];
@@ -58,17 +49,7 @@ __global__ __launch_bounds__(256) void entropy_bernoulli_kernel(TV z, TV dz, dou
 // error < 2e-8) and log(1 + e) above (absolute rounding 6e-8 against a value >= 0.0155); the voxel's <= 4 terms are summed
 // in fp32 and enter the double accumulator once.  Against the libm form: loss within 1e-6 relative, gradient within 2e-6
 // of its maximum (tests/test_hip_pointwise.py::test_entropy_loss holds both to the torch reference at 2e-5).
-__device__ __forceinline__ void bernoulli_entropy_terms(float t, float& h, float& g) {
-  const float a = fabsf(t);
-  const float e = __builtin_amdgcn_exp2f(-a * 1.4426950408889634f);          // exp(-|t|)
-  const float r = __builtin_amdgcn_rcpf(1.f + e);
-  const float sig = t >= 0.f ? r : e * r;
-  const float series = e * fmaf(e, fmaf(e, fmaf(e, -0.25f, 0.33333334f), -0.5f), 1.f);
-  const float lg = __builtin_amdgcn_logf(1.f + e) * 0.6931471805599453f;     // v_log_f32 is log2
-  const float l1p = e < 0.015625f ? series : lg;
-  h = fmaxf(t, 0.f) + l1p - t * sig;
-  g = -t * (e * r * r);            // sig (1 - sig) = sig(|t|) (1 - sig(|t|)) = r * (e r): even in t
-}
+// bernoulli_entropy_terms: common.h (shared with csrc/eata.hip, whose masks must equal the filtered kernel's bit for bit)
 // OBF: the gradient is bf16-stored (8-byte voxels; method.grad_storage - its readers round it to bf16 while staging)
 template <bool OBF>
 __global__ __launch_bounds__(256) void entropy_bernoulli_vec_kernel(TV z, TV dz, double* partial, float inv_count, int per_item) {
@@ -481,22 +462,7 @@ __global__ __launch_bounds__(256) void dice_ce_grad_kernel(DceGradArgs a) {
 // partials of the kept sum of H and of the kept count: partial[item][0][block], partial[item][1][block].  The finish kernel
 // writes loss[item] and kept[item]; pass 2 writes dlogits = keep * dH/dz / kept[item], the scale read on the device.  With
 // every element kept the block partials, the loss arithmetic and the gradient scale are those of mmtta_entropy_loss_items.
-__device__ __forceinline__ void fent_store_partials(double acc, int cnt, double* partial, double* sh) {
-  const double s = block_sum_d(acc, sh);
-  __syncthreads();
-  const double c = block_sum_d((double)cnt, sh);
-  if (threadIdx.x == 0) {
-    double* p = partial + (long long)blockIdx.y * 2 * gridDim.x;
-    p[blockIdx.x] = s;
-    p[gridDim.x + blockIdx.x] = c;
-  }
-}
-
-__device__ __forceinline__ float fent_scale(const long long* kept) {
-  const long long k = kept[blockIdx.y];
-  return k > 0 ? (float)(1.0 / (double)k) : 0.f;
-}
-
+// fent_store_partials / fent_scale: common.h
 __global__ __launch_bounds__(256) void fent_bernoulli_kernel(TV z, TV dz, float margin, const unsigned char* kin,
                                                              unsigned char* kout, double* partial, const long long* kept) {
   __shared__ double sh[4];

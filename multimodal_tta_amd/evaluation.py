@@ -501,6 +501,35 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
                 self.plugins.append(p.setup(twin, device))
                 self.streams.append(pool[lane])
 
+    def _provide_fisher(self, data_loader: Iterable, device) -> Iterable:
+        """A Fisher estimate for a plugin that asks for one (``needs_fisher``), before the first volume adapts: the file
+        ``method.eata.fisher.path`` names, else an estimate on lane 0's plugin from the first ``fisher.volumes`` volumes of the
+        loader (this rank's shard).  One span serves every lane.  Returns the loader to evaluate: the batches drawn for the
+        estimate come first again, so every volume is still evaluated once and in order."""
+        import itertools
+
+        plugin = self.plugin
+        buffered: List[Any] = []
+        it = iter(data_loader)
+        if getattr(plugin, "fisher_path", None):
+            plugin.load_fisher(plugin.fisher_path)
+        else:
+            want, vols = int(plugin.fisher_volumes), []
+            while len(vols) < want:
+                batch = next(it, None)
+                if batch is None:
+                    break
+                buffered.append(batch)
+                x = self.prepare_image(batch["image"].to(device))
+                vols += [x[i:i + 1] for i in range(x.size(0))]
+            vols = vols[:want]
+            if vols:
+                plugin.estimate_fisher(torch.cat(vols[i:i + self.group]) for i in range(0, len(vols), self.group))
+        if plugin.fisher is not None:
+            for other in self.plugins[1:]:
+                other.set_fisher(plugin.fisher, plugin.fisher_count)
+        return itertools.chain(buffered, it)
+
     def _submit(self, lane: int, xb: torch.Tensor, yb: torch.Tensor) -> Dict[str, Any]:
         """Queue adaptation + scoring of one volume - or of one GROUP of volumes (``method.group``, batch items that adapt
         independently) - on the lane's stream; nothing here waits for the GPU."""
@@ -547,6 +576,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         if self.plugin is None:
             self._setup_lanes(model, device)
+        if getattr(self.plugin, "needs_fisher", False):      # (eata_tta with its regulariser on and no estimate yet)
+            data_loader = self._provide_fisher(data_loader, device)
         R = len(self.region_order)
         done: List[Tuple[int, torch.Tensor]] = []          # (submission order, row)
         pending: List[Optional[Dict[str, Any]]] = [None] * self.lanes

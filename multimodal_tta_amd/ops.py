@@ -896,6 +896,90 @@ def cotta_update_sets(w: torch.Tensor, teacher: torch.Tensor, source: torch.Tens
                                               ptr(restored), stream_ptr()), "cotta_update_sets")
 
 
+def entropy_weighted_partials(logits: torch.Tensor) -> int:
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_entropy_weighted_partials(C.byref(t)))
+
+
+def entropy_weighted_items(logits: torch.Tensor, dlogits: torch.Tensor, margin: float, keep_out: torch.Tensor,
+                           partial: torch.Tensor, loss: torch.Tensor, kept: torch.Tensor, softmax: bool = False) -> None:
+    """EATA's weighted reliable entropy of every batch item on its own: elements with H < margin enter the loss with the
+    weight c = exp(margin - H) (no gradient through c).  keep_out: uint8, one byte per element (N*D*H*W*R, or N*D*H*W for
+    softmax heads) - the mask of ``entropy_filtered_items`` bit for bit; loss fp32 [N] = sum c H / kept, kept int64 [N];
+    dlogits = keep * c * dH/dz / kept."""
+    n, d, h, w, r = logits.shape
+    elems = n * d * h * w * (1 if softmax else r)
+    if keep_out.dtype != torch.uint8 or not keep_out.is_contiguous() or keep_out.numel() < elems:
+        raise MmttaError(f"entropy_weighted_items: keep_out must be contiguous uint8 of at least {elems} elements")
+    if loss.numel() < n or kept.numel() < n or kept.dtype != torch.int64:
+        raise MmttaError("entropy_weighted_items: one loss slot and one int64 count per batch item")
+    if partial.dtype != torch.float64 or partial.numel() < entropy_weighted_partials(logits):
+        raise MmttaError("entropy_weighted_items: partial must be fp64 of entropy_weighted_partials(logits) elements")
+    tz, tg = desc_cl(logits), desc_cl(dlogits)
+    check(_lib.load().mmtta_entropy_weighted_items(C.byref(tz), 1 if softmax else 0, float(margin), ptr(keep_out), C.byref(tg),
+                                                   ptr(partial), ptr(loss), ptr(kept), stream_ptr()), "entropy_weighted_items")
+
+
+def pseudo_label_partials(logits: torch.Tensor) -> int:
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_pseudo_label_partials(C.byref(t)))
+
+
+def pseudo_label_loss_items(logits: torch.Tensor, dlogits: torch.Tensor, partial: torch.Tensor, loss: torch.Tensor,
+                            softmax: bool = False) -> None:
+    """The loss of EATA's Fisher estimate for every batch item on its own: cross entropy against the model's own hard
+    prediction (sigmoid head: y = 1[z >= 0], softmax head: the first arg max); loss fp32 [N], dlogits = (p - y) / count."""
+    if loss.numel() < logits.shape[0]:
+        raise MmttaError("pseudo_label_loss_items: one loss slot per batch item")
+    if partial.dtype != torch.float64 or partial.numel() < pseudo_label_partials(logits):
+        raise MmttaError("pseudo_label_loss_items: partial must be fp64 of pseudo_label_partials(logits) elements")
+    tz, tg = desc_cl(logits), desc_cl(dlogits)
+    check(_lib.load().mmtta_pseudo_label_loss_items(C.byref(tz), 1 if softmax else 0, C.byref(tg), ptr(partial), ptr(loss),
+                                                    stream_ptr()), "pseudo_label_loss_items")
+
+
+def fisher_accumulate_sets(fisher: torch.Tensor, grads: torch.Tensor, n: int, sets: int) -> None:
+    """fisher[:n] += grads[s, :n] ** 2 for s = 0 .. sets-1 in that order (fp32, torch's ``F + g * g``).  ``grads``:
+    contiguous fp32 [>= sets, >= n] with a row length that is a multiple of 4."""
+    if fisher.dtype != torch.float32 or not fisher.is_contiguous() or fisher.numel() < n:
+        raise MmttaError(f"fisher_accumulate_sets: fisher must be contiguous fp32 of at least {n} elements")
+    if grads.dtype != torch.float32 or not grads.is_contiguous() or grads.dim() != 2 or grads.shape[0] < sets or grads.shape[1] < n:
+        raise MmttaError(f"fisher_accumulate_sets: grads must be contiguous fp32 [>= {sets}, >= {n}], got {tuple(grads.shape)}")
+    check(_lib.load().mmtta_fisher_accumulate_sets(ptr(fisher), ptr(grads), int(n), int(sets), int(grads.shape[1]), stream_ptr()),
+          "fisher_accumulate_sets")
+
+
+def fisher_scale(fisher: torch.Tensor, n: int, count: int) -> None:
+    """fisher[:n] /= float(count): the end of a Fisher estimate over ``count`` volumes."""
+    if fisher.dtype != torch.float32 or not fisher.is_contiguous() or fisher.numel() < n:
+        raise MmttaError(f"fisher_scale: fisher must be contiguous fp32 of at least {n} elements")
+    check(_lib.load().mmtta_fisher_scale(ptr(fisher), int(n), float(count), stream_ptr()), "fisher_scale")
+
+
+def fisher_penalty_partials(n: int, sets: int) -> int:
+    return int(_lib.load().mmtta_fisher_penalty_partials(int(n), int(sets)))
+
+
+def fisher_penalty_sets(w: torch.Tensor, g: torch.Tensor, fisher: torch.Tensor, source: torch.Tensor, n: int, sets: int,
+                        lam: float, partial: torch.Tensor, penalty: torch.Tensor) -> None:
+    """EATA's regulariser over the first ``sets`` replicas of the arena ([replicas, total]; the first ``n`` elements of a
+    replica train): g += 2 lam F (w - source), penalty[s] = lam sum F (w - source)^2, with ``fisher`` and ``source`` ([>= n])
+    shared by the replicas."""
+    for t in (w, g):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape != w.shape:
+            raise MmttaError("fisher_penalty_sets: w and g must be contiguous fp32 [replicas, total] of equal shape")
+    for name, t in (("fisher", fisher), ("source", source)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+            raise MmttaError(f"fisher_penalty_sets: {name} must be contiguous fp32 of at least {n} elements")
+    if penalty.dtype != torch.float32 or penalty.numel() < sets:
+        raise MmttaError("fisher_penalty_sets: one fp32 penalty slot per set")
+    if partial.dtype != torch.float64 or partial.numel() < fisher_penalty_partials(n, sets):
+        raise MmttaError("fisher_penalty_sets: partial must be fp64 of fisher_penalty_partials(n, sets) elements")
+    check(_lib.load().mmtta_fisher_penalty_sets(ptr(w), ptr(g), ptr(fisher), ptr(source), int(n), int(sets), int(w.shape[0]),
+                                                int(w.shape[1]), float(lam), ptr(partial), ptr(penalty), stream_ptr()),
+          "fisher_penalty_sets")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 
