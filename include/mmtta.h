@@ -554,6 +554,44 @@ int mmtta_cotta_update_sets(float* w, float* teacher, const float* source, int64
                             int64_t teacher_stride, double alpha, float restore_p, uint64_t seed, const int32_t* step,
                             const int32_t* ordinals, int64_t* partial, int64_t* restored, void* stream);
 
+/* ---- Intensity-augmented views of the staged input - csrc/augment.hip.  The views of MEMO and CoTTA above, each with a
+ * pointwise intensity transform on top of its mirror: a batch of G volumes x V views is [G * V, D, H, W, C] as for
+ * mmtta_mirror_views (`views`, `view_axes` and their rules are that entry point's; masks may repeat and may all be 0).
+ * Both entry points take channels-last tensors of <= 4 channels in dense 4-channel voxel rows, fp32 (16-byte rows) or bf16
+ * (the 8-byte voxel rows of the network input), base pointers aligned to a row.
+ *
+ * mmtta_intensity_range: range[g][c] = (min, max) of channel c over the voxels of volume g, fp32 [G][C][2] on the device,
+ *   exact; the pad lanes of the rows never enter.  Block partials and a fixed per-volume finish, no atomics.
+ *   partial  fp32 [mmtta_intensity_range_partials(x)] scratch, 16-byte aligned
+ *
+ * mmtta_augment_views: y[g * V + v] = x[g] mirrored along view v's axes and transformed, in one pass: a thread owns a voxel
+ *   row of the volume's frame, loads it once and stores it V times.  `table` is a DEVICE array fp32 [G * V][C][4], 16-byte
+ *   aligned, with the row (g, a, b, sigma) of every (volume, view, channel); `table_host` is the HOST copy of the same
+ *   array, read at launch for the one check that needs its values: the rows of view 0 must be the identity (1, 1, 0, 0).
+ *   `range` is what mmtta_intensity_range wrote for x, `ordinals` a DEVICE int32 [G] array with one number per volume (as
+ *   in mmtta_cotta_update_sets: the number, not the batch slot, enters the draw, so G volumes in one call are bit for bit G
+ *   calls on one volume each).  On a value x of channel c, with (lo, hi) = range[g][c], in this order, every operation in
+ *   fp32 and rounded on its own (no fused multiply-add):
+ *     g != 1:     x <- ((x - lo) / (hi - lo))^g * (hi - lo) + lo     (the power as exp2(g * log2(t)), t = 0 gives 0)
+ *                 x <- x * a;  x <- x + b
+ *     sigma > 0:  x <- x + sigma * n
+ *   and a bf16 row takes the result rounded to nearest even once.  n is the standard normal of (voxel, channel, view,
+ *   volume): Philox4x32-10 (as in mmtta_cotta_update_sets) with key (seed & 0xffffffff, seed >> 32) at the counter
+ *   (i, (q << 8) | v, ordinals[g], 1), i = the voxel's linear index in the volume's own (unmirrored) frame, q = c / 4 (0
+ *   here); words (0, 1) give R = sqrt(-2 ln(((w0 >> 8) + 1) 2^-24)), theta = 2 pi (w1 >> 8) 2^-24 and channel 4q takes
+ *   R cos theta, channel 4q + 1 R sin theta; words (2, 3) give channels 4q + 2 and 4q + 3 the same way.  A channel whose row
+ *   is the identity, a channel with hi == lo, every channel of view 0 and the pad lanes move their BITS (y must own its pad
+ *   lanes); a call whose table is all identity is mmtta_mirror_views bit for bit.
+ *
+ * Bad arguments (null pointers, views outside {1, 2, 4, 8}, N no multiple of views, a bad mask, shape mismatches, a view 0
+ * row that is not the identity) are MMTTA_ERR_INVALID, layouts without a kernel (and more than 65535 volumes in one call)
+ * MMTTA_ERR_UNSUPPORTED, both before anything is launched. */
+int64_t mmtta_intensity_range_partials(const mmtta_tensor* x);
+int mmtta_intensity_range(const mmtta_tensor* x, float* partial, float* range, void* stream);
+int mmtta_augment_views(const mmtta_tensor* x, const mmtta_tensor* y, int views, const int32_t* view_axes,
+                        const float* table_host, const float* table, const float* range, uint64_t seed,
+                        const int32_t* ordinals, void* stream);
+
 /* ------------------------------------------------------------------ EATA ----------------- */
 /* EATA (Niu et al., ICML 2022) - csrc/eata.hip.
  *

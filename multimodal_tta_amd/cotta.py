@@ -45,14 +45,14 @@ from __future__ import annotations
 
 from typing import Any, Dict, Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 
 from . import ops
 from .config import as_cfg, get_config
-from .memo import parse_mirror_axes, view_masks
+from .intensity import parse_intensity
+from .memo import parse_mirror_axes
 from .registry import register_plugin
-from .tta import EntropyMinimizationTTA
+from .tta import EntropyMinimizationTTA, modality_mask
 
 
 @register_plugin("cotta_tta")
@@ -67,7 +67,8 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         m = get_config(as_cfg(config), "method", {}) or {}
         s = get_config(m, "cotta", {}) or {}
         self.mirror_axes = parse_mirror_axes(get_config(s, "mirror_axes", ["h", "w"]), "method.cotta.mirror_axes")
-        self.view_axes = view_masks(self.mirror_axes)
+        self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, "method.cotta.intensity")
+        self.view_axes = self.intensity.view_axes          # the mirror group, ``intensity.copies`` times over
         self.views = len(self.view_axes)
         alpha, p, seed = get_config(s, "alpha", 0.999), get_config(s, "restore_p", 0.01), get_config(s, "seed", 0)
         if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not (0.0 <= float(alpha) <= 1.0):
@@ -81,8 +82,6 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
             raise NotImplementedError("method.moddrop.enabled: true is not supported by cotta_tta (one modality mask per step "
                                       "for the teacher's views and the student is not defined yet)")
         self.teacher: Optional[torch.Tensor] = None          # [replicas, n_train] fp32
-        self._ordinals: Optional[torch.Tensor] = None        # device int32 [replicas]: the draw's per-volume number
-        self._served = 0
 
     def setup(self, model, device) -> "MeanTeacherTTA":
         super().setup(model, device)          # (tells the model its views: EntropyMinimizationTTA.setup)
@@ -93,8 +92,7 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
                 "statistics, which the teacher's train-mode forward would move (running_mean, running_var, "
                 "num_batches_tracked belong to the student); use a model.norm without them (INSTANCE, GROUP)")
         self.teacher = torch.empty((ar.replicas, ar.n_train), dtype=torch.float32, device=ar.device)
-        self._ordinals = torch.zeros(ar.replicas, dtype=torch.int32, device=ar.device)
-        self._served = int(self.lane) << 24
+        self._setup_ordinals()          # the restore draw's (and the intensity views') per-volume numbers
         self.reset_teacher()
         return self
 
@@ -151,7 +149,11 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
 
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
         self.rt.views = self.views
-        xv = self.rt.stage_views(x_cl, self.view_axes)
+        if self.intensity.active and self.views > 1:
+            present = modality_mask(int(x_cl.shape[-1]), self.missing, 0.0, None)
+            xv = self.rt.stage_views(x_cl, self.view_axes, self.intensity, self._ordinals_host, present)
+        else:
+            xv = self.rt.stage_views(x_cl, self.view_axes)
         self.rt.views = 1          # the loop runs on the volumes; the step switches to the views for the teacher
         return x_cl, (xv,)
 
@@ -159,16 +161,8 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
                      ordinals: Optional[Sequence[int]] = None) -> Dict[str, Any]:
         """As ``entmin_tta.adapt_volume``: x [B,C,D,H,W] (B <= ``method.group`` volumes), the student's final logits and the
         per-step losses, plus ``restored``: the number of restored elements per step ([steps], or [steps, B] for a group of
-        B > 1 volumes).  ``ordinals``: one number per volume for the restore draw (default: the volumes served so far)."""
+        B > 1 volumes).  ``ordinals``: one number per volume for the restore draw and the intensity views (default: the
+        volumes served so far)."""
         if self.rt is not None:
-            B = int(x.shape[0])
-            if B > self.rt.group:          # (one ordinal per replica)
-                raise ValueError(f"method.group = {self.rt.group}: at most {self.rt.group} volumes per call, got {B}")
-            if ordinals is None:
-                ordinals = [self._served + b for b in range(B)]
-                self._served += B
-            ordinals = [int(o) for o in ordinals]
-            if len(ordinals) != B or any(not (0 <= o < 1 << 32) for o in ordinals):
-                raise ValueError(f"ordinals = {ordinals!r}: expected {B} numbers (one per volume) with 0 <= ordinal < 2^32")
-            self._ordinals[:B].copy_(torch.from_numpy(np.array(ordinals, dtype=np.uint32).view(np.int32)))
+            self._take_ordinals(int(x.shape[0]), ordinals)
         return super().adapt_volume(x, steps)

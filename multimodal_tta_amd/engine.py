@@ -22,6 +22,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -775,12 +776,32 @@ class Runtime:
         ops.to_cl(x, out=x_cl)
         return x_cl
 
-    def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int]) -> torch.Tensor:
+    def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int], intensity=None,
+                    ordinals: Optional[Sequence[int]] = None, present: Optional[Sequence[bool]] = None) -> torch.Tensor:
         """The staged input [G,D,H,W,C] -> its mirrored views as batch items [G * V,D,H,W,C] (item g * V + v = volume g
-        mirrored along the axes of mask view_axes[v]; ops.mirror_views), in the storage of the staged input."""
+        mirrored along the axes of mask view_axes[v]; ops.mirror_views), in the storage of the staged input.  ``intensity``
+        (an active ``intensity.IntensitySpec``): every view v >= 1 also takes its intensity transform, drawn for the
+        per-volume numbers ``ordinals`` (one per volume) with the channels ``present`` marks absent left alone - the
+        channels' ranges, the parameter table's upload, then ops.augment_views in place of the mirror pass."""
         n, d, h, w, c = x_cl.shape
         xv = self.pool.cl("x_views", n * len(view_axes), d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=x_cl.dtype)
-        ops.mirror_views(x_cl, xv, view_axes)
+        if intensity is None or not intensity.active:
+            ops.mirror_views(x_cl, xv, view_axes)
+            return xv
+        from .intensity import view_parameters
+        if ordinals is None or len(ordinals) != n:
+            raise ValueError(f"stage_views: intensity views need one ordinal per volume, got {ordinals!r} for {n} volumes")
+        if list(view_axes) != list(intensity.view_axes):
+            raise ValueError(f"stage_views: view_axes {list(view_axes)} are not the intensity block's {intensity.view_axes}")
+        value_range = self.pool.flat("aug_range", n * c * 2)
+        partial = self.pool.flat("aug_range_partial", ops.intensity_range_partials(x_cl))
+        ops.intensity_range(x_cl, partial, value_range)
+        table_host = torch.from_numpy(view_parameters(intensity, ordinals, c, present))
+        table = self.pool.flat("aug_table", table_host.numel())
+        table.copy_(table_host.reshape(-1))
+        ords = self.pool.flat("aug_ordinals", n, dtype=torch.int32)
+        ords.copy_(torch.from_numpy(np.array([int(o) for o in ordinals], dtype=np.uint32).view(np.int32)))
+        ops.augment_views(x_cl, xv, view_axes, table_host, table, value_range, intensity.seed, ords)
         return xv
 
     def input_dtype(self) -> torch.dtype:

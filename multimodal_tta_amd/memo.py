@@ -24,14 +24,15 @@ staging of the views (``_stage``) and the ensemble (``_final_logits``); the per-
 """
 from __future__ import annotations
 
-from typing import Any, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
 from .config import as_cfg, get_config
+from .intensity import parse_intensity
 from .registry import register_plugin
-from .tta import EntropyMinimizationTTA
+from .tta import EntropyMinimizationTTA, modality_mask
 
 AXIS_BITS = {"w": 1, "h": 2, "d": 4}          # the kernels' mirror masks: bit 0 = W, bit 1 = H, bit 2 = D (torch D, H, W)
 
@@ -68,13 +69,19 @@ class MarginalEntropyTTA(EntropyMinimizationTTA):
         if not isinstance(ens, bool):
             raise ValueError(f"method.memo.ensemble = {ens!r}: expected true or false")
         self.ensemble = ens
-        self.view_axes = view_masks(self.mirror_axes)
+        self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, "method.memo.intensity")
+        self.view_axes = self.intensity.view_axes          # the mirror group, ``intensity.copies`` times over
         self.views = len(self.view_axes)
         if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
             raise NotImplementedError("method.moddrop.enabled: true is not supported by memo_tta (one modality mask per step "
                                       "for all views is not defined yet)")
         # the fused weight update reduces one batch item per parameter set; V views per set take the separate passes
         self.fused_update = self.views == 1
+
+    def setup(self, model, device) -> "MarginalEntropyTTA":
+        super().setup(model, device)
+        self._setup_ordinals()          # the intensity views' per-volume numbers
+        return self
 
     # ------------------------------------------------------------------ one step
     def _update(self, xv: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
@@ -97,7 +104,20 @@ class MarginalEntropyTTA(EntropyMinimizationTTA):
         if self.views == 1:
             return super()._stage(x_cl)
         self.rt.views = self.views          # every launch of the loop carries V consecutive batch items per volume
-        return self.rt.stage_views(x_cl, self.view_axes), ()
+        if not self.intensity.active:
+            return self.rt.stage_views(x_cl, self.view_axes), ()
+        present = modality_mask(int(x_cl.shape[-1]), self.missing, 0.0, None)
+        return self.rt.stage_views(x_cl, self.view_axes, self.intensity, self._ordinals_host, present), ()
+
+    def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None,
+                     ordinals: Optional[Sequence[int]] = None) -> Dict[str, Any]:
+        """As ``entmin_tta.adapt_volume``.  ``ordinals``: one number per volume for the draws of the intensity views
+        (default: the volumes served so far), as for ``cotta_tta``; without intensity views they are counted and unused."""
+        if self.rt is not None and ((self.views > 1 and self.intensity.active) or ordinals is not None):
+            self._take_ordinals(int(x.shape[0]), ordinals)
+        elif self.rt is not None:
+            self._served += int(x.shape[0])
+        return super().adapt_volume(x, steps)
 
     def _final_logits(self, x_cl: torch.Tensor, xv: torch.Tensor, present: Optional[Sequence[bool]]) -> torch.Tensor:
         if self.views == 1 or not self.ensemble:

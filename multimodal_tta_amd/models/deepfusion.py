@@ -322,9 +322,11 @@ class DeepFusionRuntime(Runtime):
         ops.to_cl(x.contiguous().view(n * M, 1, D, H, W), out=xm)
         return x_cl
 
-    def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int]) -> torch.Tensor:
-        """The mirrored views of the staged volume, and the family batch [n * V * M, D, H, W, 1] of those views."""
-        xv = super().stage_views(x_cl, view_axes)
+    def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int], intensity=None,
+                    ordinals: Optional[Sequence[int]] = None, present: Optional[Sequence[bool]] = None) -> torch.Tensor:
+        """The mirrored (and, with ``intensity``, intensity-augmented) views of the staged volume, and the family batch
+        [n * V * M, D, H, W, 1] of those views."""
+        xv = super().stage_views(x_cl, view_axes, intensity, ordinals, present)
         n, D, H, W, M = xv.shape
         xm = self.pool.cl("xm", n * M, D, H, W, 1, ldc=4, zero=True)
         for m in range(M):

@@ -821,6 +821,45 @@ def mirror_views(x: torch.Tensor, y: torch.Tensor, view_axes: Sequence[int]) -> 
           "mirror_views")
 
 
+def intensity_range_partials(x: torch.Tensor) -> int:
+    t = desc_cl(x)
+    return int(_lib.load().mmtta_intensity_range_partials(C.byref(t)))
+
+
+def intensity_range(x: torch.Tensor, partial: torch.Tensor, out: torch.Tensor) -> None:
+    """out [G, C, 2] fp32 = (min, max) of every channel of every volume of the staged input x [G,D,H,W,C] (fp32 or bf16
+    4-channel voxel rows; the pad lanes do not enter)."""
+    g, c = int(x.shape[0]), int(x.shape[4])
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < g * c * 2:
+        raise MmttaError(f"intensity_range: out must be contiguous fp32 of at least {g * c * 2} elements")
+    if partial.dtype != torch.float32 or partial.numel() < intensity_range_partials(x):
+        raise MmttaError("intensity_range: partial must be fp32 of intensity_range_partials(x) elements")
+    tx = desc_cl(x)
+    check(_lib.load().mmtta_intensity_range(C.byref(tx), ptr(partial), ptr(out), stream_ptr()), "intensity_range")
+
+
+def augment_views(x: torch.Tensor, y: torch.Tensor, view_axes: Sequence[int], table_host: torch.Tensor, table: torch.Tensor,
+                  value_range: torch.Tensor, seed: int, ordinals: torch.Tensor) -> None:
+    """y[g * V + v] = x[g] mirrored along the axes of mask view_axes[v] and put through view v's intensity transform
+    (``intensity.py``): ``table`` device fp32 [G, V, C, 4] with the rows (g, a, b, sigma), ``table_host`` its host copy (the
+    entry point checks view 0's rows on it), ``value_range`` what ``intensity_range`` wrote for x, ``ordinals`` device int32
+    [>= G].  An all-identity table gives ``mirror_views``' bits."""
+    g, c, v = int(x.shape[0]), int(x.shape[4]), len(view_axes)
+    n = g * v * c * 4
+    for name, t, cuda in (("table", table, True), ("table_host", table_host, False)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.is_cuda != cuda:
+            raise MmttaError(f"augment_views: {name} must be contiguous fp32 [{g}, {v}, {c}, 4] on the "
+                             f"{'device' if cuda else 'host'}, got {tuple(t.shape)} {t.dtype} {t.device}")
+    if value_range.dtype != torch.float32 or not value_range.is_contiguous() or value_range.numel() < g * c * 2 or not value_range.is_cuda:
+        raise MmttaError(f"augment_views: value_range must be contiguous device fp32 of at least {g * c * 2} elements")
+    if ordinals.dtype != torch.int32 or ordinals.numel() < g or not ordinals.is_cuda:
+        raise MmttaError("augment_views: ordinals must be device int32 [>= volumes]")
+    tx, ty = desc_cl(x), desc_cl(y)
+    check(_lib.load().mmtta_augment_views(C.byref(tx), C.byref(ty), v, _view_axes(view_axes), ptr(table_host), ptr(table),
+                                          ptr(value_range), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(ordinals), stream_ptr()),
+          "augment_views")
+
+
 def memo_partials(logits: torch.Tensor, views: int) -> int:
     t = desc_cl(logits)
     return int(_lib.load().mmtta_memo_partials(C.byref(t), int(views)))

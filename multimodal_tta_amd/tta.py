@@ -18,6 +18,7 @@ from __future__ import annotations
 import warnings
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -140,6 +141,11 @@ class EntropyMinimizationTTA:
         self._graphs: Dict[Tuple, torch.cuda.CUDAGraph] = {}
         self._gen: Optional[torch.Generator] = None
         self.lane = 0      # plugins that adapt different volumes concurrently (own stream each) take distinct lanes
+        # the per-volume number of the methods that draw random numbers per volume (cotta_tta's restore, the intensity views
+        # of memo_tta and cotta_tta): see ``_setup_ordinals`` / ``_take_ordinals``
+        self._ordinals: Optional[torch.Tensor] = None        # device int32 [replicas]
+        self._ordinals_host: List[int] = []                  # the same numbers for the host-side draws, one per volume
+        self._served = 0
 
     # ------------------------------------------------------------------ setup
     def setup(self, model: HipSegModel, device) -> "EntropyMinimizationTTA":
@@ -185,6 +191,31 @@ class EntropyMinimizationTTA:
             # settled on (models that fall back to group 1 are tuned for group 1)
             ops.tune_for_volumes_in_flight(self.lanes * self.group * self.views)
         return self
+
+    # ------------------------------------------------------------------ per-volume ordinals
+    def _setup_ordinals(self) -> None:
+        """Called from the ``setup`` of a method that draws per volume: one device slot per replica, and the count of volumes
+        served starts at ``lane * 2^24`` (the lanes of an evaluator draw apart)."""
+        ar = self.rt.arena
+        self._ordinals = torch.zeros(ar.replicas, dtype=torch.int32, device=ar.device)
+        self._ordinals_host = []
+        self._served = int(self.lane) << 24
+
+    def _take_ordinals(self, B: int, ordinals: Optional[Sequence[int]]) -> List[int]:
+        """The ordinals of the ``B`` volumes of one ``adapt_volume`` call, on the host and in ``self._ordinals[:B]``: the
+        caller's, or by default the volumes served so far.  The ordinal, never the replica slot, enters a draw - which is
+        what keeps a group of volumes equal to the same volumes served one at a time."""
+        if B > self.rt.group:          # (one ordinal per replica)
+            raise ValueError(f"method.group = {self.rt.group}: at most {self.rt.group} volumes per call, got {B}")
+        if ordinals is None:
+            ordinals = [self._served + b for b in range(B)]
+            self._served += B
+        ordinals = [int(o) for o in ordinals]
+        if len(ordinals) != B or any(not (0 <= o < 1 << 32) for o in ordinals):
+            raise ValueError(f"ordinals = {ordinals!r}: expected {B} numbers (one per volume) with 0 <= ordinal < 2^32")
+        self._ordinals[:B].copy_(torch.from_numpy(np.array(ordinals, dtype=np.uint32).view(np.int32)))
+        self._ordinals_host = ordinals
+        return ordinals
 
     # ------------------------------------------------------------------ one step
     def _step_launches(self, x: torch.Tensor, present: Optional[Sequence[bool]], *views: torch.Tensor) -> None:
