@@ -482,7 +482,21 @@ int mmtta_entropy_filtered_items(const mmtta_tensor* logits, int softmax, float 
  * `view_axes` is a HOST array of `views` masks, read at launch.  Mirroring is exact on the voxel grid and its own inverse,
  * so every kernel below addresses a voxel of the volume's own frame and its image in each view directly.
  *
- * mmtta_mirror_views: y[g * V + v] = x[g] mirrored along view v's axes.  x [G, D, H, W, C] and y [G * V, D, H, W, C]
+ * Bit 4 (value 16) of a code transposes H and W BEFORE the mirrors of bits 0-2; bit 4 stays unused (a code with it is
+ * invalid, as before), so the valid codes are 0..7 and 16..23.  For a volume x and
+ * a view y, both [D, H, W, C]:  y = flip(x.transpose(H, W) if code & 16 else x, dims of code & 7), and bringing a view back
+ * to the frame is the inverse, flip then transpose (such a view is not its own inverse).  In coordinates, frame voxel
+ * (d, h, w) sits at view voxel (fd(d), fh(w), fw(h)) with bit 4 and at (fd(d), fh(h), fw(w)) without, f* = the mirror of
+ * that VIEW axis where its bit is set.  A quarter turn of the (H, W) plane (torch.rot90(x, k, dims = (H, W))) is code 18
+ * (k = 1), 3 (k = 2) or 17 (k = 3).  A code with bit 4 needs h == w on every tensor of the call (MMTTA_ERR_INVALID, the
+ * message names both extents).  A call in which no code has bit 4 launches the mirror group's kernels with their
+ * arguments, bit for bit; with one, mmtta_memo_loss_items (sigmoid head, <= 4 regions in dense 16-byte rows) and
+ * mmtta_memo_ensemble (sigmoid head, dense 16-byte rows, `out` owning its pad lanes, which then take 0) run tiled kernels
+ * that load a transposed view along the view's W and turn the tile through LDS; every other path (generic Bernoulli,
+ * categorical, generic ensemble, mmtta_mirror_views, mmtta_augment_views) follows the coordinate map alone and is
+ * uncoalesced for transposed views.  mmtta_memo_partials is one formula for both.
+ *
+ * mmtta_mirror_views: y[g * V + v] = x[g] under view v's code (transposed where bit 4 is set, then mirrored).  x [G, D, H, W, C] and y [G * V, D, H, W, C]
  *   channels-last with dense rows of one width, fp32 or bf16 (the 8-byte voxel rows of the network input included); a
  *   voxel's whole row moves intact, pad lanes included (y must own them).  Bit-exact.
  *
@@ -490,7 +504,9 @@ int mmtta_entropy_filtered_items(const mmtta_tensor* logits, int softmax, float 
  *   brought back to the volume's frame:
  *     softmax == 0:  pbar = 1/V sum_v sigmoid(u_v);   loss[g] = mean over (voxel, region) of H_bern(pbar)
  *     softmax != 0:  pbar = 1/V sum_v softmax_r(u_v); loss[g] = mean over voxel of -sum_r pbar_r log pbar_r
- *   dlogits of view v = dloss[g]/dlogits, written in view v's own frame.  One streaming pass (a thread owns a voxel of
+ *   dlogits of view v = dloss[g]/dlogits, written in view v's own frame (u_v = view v's logits flipped, then - bit 4 -
+ *   transposed).  With transposed views the fast path gives, for equal frame-aligned rows, the gradient bits of the
+ *   mirror kernel.  One streaming pass (a thread owns a voxel of
  *   the volume's frame, reads its V rows and writes its V gradient rows) and the per-volume finish.  Loss and gradient
  *   are finite for every finite fp32 logit: 1 - pbar is never formed by subtraction and x log x is taken at
  *   max(x, smallest normal) (softmax != 0: log pbar is a log-sum-exp over the views' log-softmaxes).  Storages as mmtta_entropy_loss_items: fp32 logits; fp32 gradients, or - softmax == 0, <= 4
@@ -500,10 +516,11 @@ int mmtta_entropy_filtered_items(const mmtta_tensor* logits, int softmax, float 
  *   partial  fp64 [mmtta_memo_partials(logits, views)] scratch; loss  fp32 [G]
  *
  * mmtta_memo_ensemble: out [G, D, H, W, C] fp32 = logit(pbar) (softmax == 0; +-87.3365 = -ln(smallest normal) where pbar
- *   or 1 - pbar underflows; views == 1 returns the logits) or log pbar (softmax != 0), in the volume's frame.
+ *   or 1 - pbar underflows; views == 1 returns the logits) or log pbar (softmax != 0), in the volume's frame (every view
+ *   brought back by its inverse: flip, then - bit 4 - transpose).
  *
- * Bad arguments (null pointers, views outside {1, 2, 4, 8}, N no multiple of views, a bad mask, shape mismatches) are
- * MMTTA_ERR_INVALID, storages without a kernel (and more than 65535 volumes in one call) MMTTA_ERR_UNSUPPORTED, both before
+ * Bad arguments (null pointers, views outside {1, 2, 4, 8}, N no multiple of views, a code outside 0..7 and 16..23, a code with bit
+ * 4 on tensors with h != w, shape mismatches) are MMTTA_ERR_INVALID, storages without a kernel (and more than 65535 volumes in one call) MMTTA_ERR_UNSUPPORTED, both before
  * anything is launched. */
 int mmtta_mirror_views(const mmtta_tensor* x, const mmtta_tensor* y, int views, const int32_t* view_axes, void* stream);
 int64_t mmtta_memo_partials(const mmtta_tensor* logits, int views);
@@ -564,8 +581,9 @@ int mmtta_cotta_update_sets(float* w, float* teacher, const float* source, int64
  *   exact; the pad lanes of the rows never enter.  Block partials and a fixed per-volume finish, no atomics.
  *   partial  fp32 [mmtta_intensity_range_partials(x)] scratch, 16-byte aligned
  *
- * mmtta_augment_views: y[g * V + v] = x[g] mirrored along view v's axes and transformed, in one pass: a thread owns a voxel
- *   row of the volume's frame, loads it once and stores it V times.  `table` is a DEVICE array fp32 [G * V][C][4], 16-byte
+ * mmtta_augment_views: y[g * V + v] = x[g] under view v's code (mmtta_mirror_views' codes, bit 4 = H and W transposed
+ *   first, h == w, included) and transformed, in one pass: a thread owns a voxel
+ *   row of the volume's frame, loads it once and stores it V times (W rows apart for a transposed view: uncoalesced).  `table` is a DEVICE array fp32 [G * V][C][4], 16-byte
  *   aligned, with the row (g, a, b, sigma) of every (volume, view, channel); `table_host` is the HOST copy of the same
  *   array, read at launch for the one check that needs its values: the rows of view 0 must be the identity (1, 1, 0, 0).
  *   `range` is what mmtta_intensity_range wrote for x, `ordinals` a DEVICE int32 [G] array with one number per volume (as
@@ -577,14 +595,14 @@ int mmtta_cotta_update_sets(float* w, float* teacher, const float* source, int64
  *     sigma > 0:  x <- x + sigma * n
  *   and a bf16 row takes the result rounded to nearest even once.  n is the standard normal of (voxel, channel, view,
  *   volume): Philox4x32-10 (as in mmtta_cotta_update_sets) with key (seed & 0xffffffff, seed >> 32) at the counter
- *   (i, (q << 8) | v, ordinals[g], 1), i = the voxel's linear index in the volume's own (unmirrored) frame, q = c / 4 (0
+ *   (i, (q << 8) | v, ordinals[g], 1), i = the voxel's linear index in the volume's own (unmirrored, unturned) frame, q = c / 4 (0
  *   here); words (0, 1) give R = sqrt(-2 ln(((w0 >> 8) + 1) 2^-24)), theta = 2 pi (w1 >> 8) 2^-24 and channel 4q takes
  *   R cos theta, channel 4q + 1 R sin theta; words (2, 3) give channels 4q + 2 and 4q + 3 the same way.  A channel whose row
  *   is the identity, a channel with hi == lo, every channel of view 0 and the pad lanes move their BITS (y must own its pad
  *   lanes); a call whose table is all identity is mmtta_mirror_views bit for bit.
  *
- * Bad arguments (null pointers, views outside {1, 2, 4, 8}, N no multiple of views, a bad mask, shape mismatches, a view 0
- * row that is not the identity) are MMTTA_ERR_INVALID, layouts without a kernel (and more than 65535 volumes in one call)
+ * Bad arguments (null pointers, views outside {1, 2, 4, 8}, N no multiple of views, a code outside 0..7 and 16..23 or with bit 4 on
+ * h != w, shape mismatches, a view 0 row that is not the identity) are MMTTA_ERR_INVALID, layouts without a kernel (and more than 65535 volumes in one call)
  * MMTTA_ERR_UNSUPPORTED, both before anything is launched. */
 int64_t mmtta_intensity_range_partials(const mmtta_tensor* x);
 int mmtta_intensity_range(const mmtta_tensor* x, float* partial, float* range, void* stream);

@@ -3,10 +3,10 @@
 ``episodic: false``: the student learns from the augmentation-averaged prediction of a teacher that is an exponential moving
 average of the student, and after every step a random small share of the student's weights returns to the source values.
 
-Per volume and step (each volume of a group on its own weight replica), with F_v = mirror along view v's axes, w the
-student, w' the teacher and w0 the source weights:
+Per volume and step (each volume of a group on its own weight replica), with F_v = view v's map (mirrors, and the quarter
+turns of ``method.cotta.rot90.k``, as ``memo_tta``), w the student, w' the teacher and w0 the source weights:
 
-    t  = logit( 1/V sum_v sigmoid(F_v f(F_v x; w')) )         (softmax head: log of the mean softmax)   no gradient
+    t  = logit( 1/V sum_v sigmoid(F_v^-1 f(F_v x; w')) )         (softmax head: log of the mean softmax)   no gradient
     z  = f(x; w)
     L  = mean over (voxel, region) of -q log sigmoid(z) - (1 - q) log sigmoid(-z),  q = sigmoid(t)        (sigmoid head)
     L  = mean over voxels of -sum_r exp(t_r) log softmax(z)_r                                             (softmax head)
@@ -28,8 +28,9 @@ by default the count of volumes this plugin has served since ``setup`` (lane ``l
 or ``adapt_volume(..., ordinals=[...])``.  The ordinal, not the replica slot, enters the draw: a group of volumes equals the
 same volumes served one at a time.
 
-Where this differs from the paper: the views are the mirror group (``method.cotta.mirror_axes``, ``memo_tta``'s views: the
-one augmentation whose inverse is exact on the voxel grid), not colour / affine augmentations; the teacher always averages
+Where this differs from the paper: the views are the mirror group and quarter turns in the (H, W) plane
+(``method.cotta.mirror_axes``, ``method.cotta.rot90``, ``memo_tta``'s views: the augmentations whose inverse is exact on the
+voxel grid), not colour / affine augmentations; the teacher always averages
 its views (the paper's confidence-gated switch between one and 32 views is not built); the elements are voxels (or voxel x
 region pairs), not images; the restore draw is per element of the flat trainable span, not per tensor.
 
@@ -50,14 +51,14 @@ import torch
 from . import ops
 from .config import as_cfg, get_config
 from .intensity import parse_intensity
-from .memo import parse_mirror_axes
+from .memo import check_square, parse_mirror_axes, parse_rot90
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA, modality_mask
 
 
 @register_plugin("cotta_tta")
 class MeanTeacherTTA(EntropyMinimizationTTA):
-    """``method.cotta.mirror_axes`` (default [h, w]: 4 teacher views), ``alpha`` (teacher momentum, default 0.999),
+    """``method.cotta.mirror_axes`` (default [h, w]: 4 teacher views), ``rot90`` (default {k: []}), ``alpha`` (teacher momentum, default 0.999),
     ``restore_p`` (default 0.01) and ``seed`` (default 0); the optimizer is ``training.optimizer`` exactly as for
     ``entmin_tta``."""
     fused_update = False     # one gradient for the whole span, then the teacher / restore pass over it
@@ -67,8 +68,10 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         m = get_config(as_cfg(config), "method", {}) or {}
         s = get_config(m, "cotta", {}) or {}
         self.mirror_axes = parse_mirror_axes(get_config(s, "mirror_axes", ["h", "w"]), "method.cotta.mirror_axes")
-        self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, "method.cotta.intensity")
-        self.view_axes = self.intensity.view_axes          # the mirror group, ``intensity.copies`` times over
+        self.rot90 = parse_rot90(get_config(s, "rot90", None), "method.cotta.rot90")
+        self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, "method.cotta.intensity", self.rot90)
+        # ({identity} + the quarter turns) x the mirror group, ``intensity.copies`` times over
+        self.view_axes = self.intensity.view_axes
         self.views = len(self.view_axes)
         alpha, p, seed = get_config(s, "alpha", 0.999), get_config(s, "restore_p", 0.01), get_config(s, "seed", 0)
         if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not (0.0 <= float(alpha) <= 1.0):
@@ -148,6 +151,7 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         self.reset_teacher()
 
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
+        check_square(self.view_axes, int(x_cl.shape[2]), int(x_cl.shape[3]), "method.cotta.rot90")
         self.rt.views = self.views
         if self.intensity.active and self.views > 1:
             present = modality_mask(int(x_cl.shape[-1]), self.missing, 0.0, None)

@@ -13,6 +13,7 @@ namespace mmtta {
 
 constexpr int AUG_MAX_BLOCKS = 2048;       // block partials per volume (the entropy objective's figure)
 constexpr int AUG_MAX_V = 8;
+constexpr int AUG_TURN = 16;               // bit 4 of a view's code: H and W transposed before the mirrors (memo.hip's MEMO_TURN)
 constexpr int AUG_MAX_GRID_Y = 65535;      // gridDim.y carries the volume
 constexpr int AUG_ROW = 4;                 // channels of a voxel row: one 16-byte (fp32) or 8-byte (bf16) access
 
@@ -149,7 +150,10 @@ constexpr unsigned AUG_ANY = 0xfu, AUG_GAMMA = 0xf0u, AUG_NOISE = 0xf00u;
 // contiguous segment of every view).  The table rows of the volume's views, made identity for constant channels and pad
 // lanes, and the ranges sit in LDS; what a view needs (nothing / arithmetic / gamma / noise) is one flag word per view, read
 // through readfirstlane: every branch below is on a wavefront-uniform value and holds no global load.
-template <bool BF>
+// TR (a view of the call has bit 4: H and W transposed before the mirrors, H == W): frame voxel (z, y, x) goes to
+// (fd(z), fh(x), fw(y)) of such a view - stores W rows apart, uncoalesced, once per volume.  The noise counter stays the
+// voxel's index in the volume's own frame: a transposed view draws the field a mirror view would at the same frame voxel.
+template <bool BF, bool TR>
 __global__ __launch_bounds__(256) void augment_views_kernel(const typename AugRow<BF>::raw_t* __restrict__ x,
                                                             typename AugRow<BF>::raw_t* __restrict__ y, long long xsn,
                                                             long long ysn, int C, unsigned D, unsigned H, unsigned W, AugViews mv,
@@ -195,7 +199,8 @@ __global__ __launch_bounds__(256) void augment_views_kernel(const typename AugRo
     AugRow<BF>::unpack(raw, f, b);
     for (int v = 0; v < V; ++v) {
       const int m = mv.axes[v];
-      const unsigned xx = (m & 1) ? W - 1 - px : px, yy = (m & 2) ? H - 1 - py : py, zz = (m & 4) ? D - 1 - pz : pz;
+      const unsigned qx = (TR && (m & AUG_TURN)) ? py : px, qy = (TR && (m & AUG_TURN)) ? px : py;
+      const unsigned xx = (m & 1) ? W - 1 - qx : qx, yy = (m & 2) ? H - 1 - qy : qy, zz = (m & 4) ? D - 1 - pz : pz;
       raw_t* yb = y + ((long long)g * V + v) * ysn;
       const unsigned o = (zz * H + yy) * W + xx;
       const unsigned fl = __builtin_amdgcn_readfirstlane(flags[v]);
@@ -301,8 +306,16 @@ extern "C" int mmtta_augment_views(const mmtta_tensor* x, const mmtta_tensor* y,
   mv.v = views;
   for (int v = 0; v < AUG_MAX_V; ++v) {
     mv.axes[v] = v < views ? view_axes[v] : 0;
-    MMTTA_CHECK(mv.axes[v] >= 0 && mv.axes[v] <= 7, MMTTA_ERR_INVALID, "augment views: view_axes[%d] = %d (bit 0 = W, 1 = H, 2 = D)", v, mv.axes[v]);
+    MMTTA_CHECK((mv.axes[v] & ~(7 | AUG_TURN)) == 0, MMTTA_ERR_INVALID,
+                "augment views: view_axes[%d] = %d (bit 0 = W, 1 = H, 2 = D mirrored, bit 4 = H and W transposed first)", v, mv.axes[v]);
   }
+  bool turned = false;
+  for (int v = 0; v < views; ++v)
+    if (mv.axes[v] & AUG_TURN) {
+      turned = true;
+      MMTTA_CHECK(y->h == y->w, MMTTA_ERR_INVALID,
+                  "augment views: view_axes[%d] = %d transposes H and W, which needs h == w: h = %d, w = %d", v, mv.axes[v], y->h, y->w);
+    }
   MMTTA_CHECK(y->n >= views && y->n % views == 0, MMTTA_ERR_INVALID, "augment views: batch %d is no multiple of views %d", y->n, views);
   MMTTA_CHECK(y->n == x->n * views && x->c == y->c && x->d == y->d && x->h == y->h && x->w == y->w && x->dtype == y->dtype,
               MMTTA_ERR_INVALID, "augment views: shape mismatch");
@@ -324,11 +337,16 @@ extern "C" int mmtta_augment_views(const mmtta_tensor* x, const mmtta_tensor* y,
   const dim3 grid(aug_blocks(x), x->n);
   const unsigned k0 = (unsigned)(seed & 0xffffffffu), k1 = (unsigned)(seed >> 32);
   const long long xsn = x->sn / AUG_ROW, ysn = y->sn / AUG_ROW;
-  if (is_bf16(x))
-    hipLaunchKernelGGL(augment_views_kernel<true>, grid, dim3(256), 0, s, (const uint2*)x->ptr, (uint2*)y->ptr, xsn, ysn, (int)x->c,
-                       (unsigned)x->d, (unsigned)x->h, (unsigned)x->w, mv, table, range, (const int*)ordinals, k0, k1);
-  else
-    hipLaunchKernelGGL(augment_views_kernel<false>, grid, dim3(256), 0, s, (const uint4*)x->ptr, (uint4*)y->ptr, xsn, ysn, (int)x->c,
-                       (unsigned)x->d, (unsigned)x->h, (unsigned)x->w, mv, table, range, (const int*)ordinals, k0, k1);
+#define AUG_VIEWS(BF, TR, RAW)                                                                                                  \
+  hipLaunchKernelGGL((augment_views_kernel<BF, TR>), grid, dim3(256), 0, s, (const RAW*)x->ptr, (RAW*)y->ptr, xsn, ysn, (int)x->c, \
+                     (unsigned)x->d, (unsigned)x->h, (unsigned)x->w, mv, table, range, (const int*)ordinals, k0, k1)
+  if (!turned) {
+    if (is_bf16(x)) AUG_VIEWS(true, false, uint2);
+    else AUG_VIEWS(false, false, uint4);
+  } else {
+    if (is_bf16(x)) AUG_VIEWS(true, true, uint2);
+    else AUG_VIEWS(false, true, uint4);
+  }
+#undef AUG_VIEWS
   return launch_status("augment views");
 }

@@ -778,12 +778,16 @@ class Runtime:
 
     def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int], intensity=None,
                     ordinals: Optional[Sequence[int]] = None, present: Optional[Sequence[bool]] = None) -> torch.Tensor:
-        """The staged input [G,D,H,W,C] -> its mirrored views as batch items [G * V,D,H,W,C] (item g * V + v = volume g
-        mirrored along the axes of mask view_axes[v]; ops.mirror_views), in the storage of the staged input.  ``intensity``
+        """The staged input [G,D,H,W,C] -> its views as batch items [G * V,D,H,W,C] (item g * V + v = volume g under the
+        code view_axes[v]: bit 4 = H and W transposed, then mirrored along the axes of bits 0-2; ops.mirror_views), in the
+        storage of the staged input.  A code with bit 4 needs H == W (ValueError before any launch).  ``intensity``
         (an active ``intensity.IntensitySpec``): every view v >= 1 also takes its intensity transform, drawn for the
         per-volume numbers ``ordinals`` (one per volume) with the channels ``present`` marks absent left alone - the
         channels' ranges, the parameter table's upload, then ops.augment_views in place of the mirror pass."""
         n, d, h, w, c = x_cl.shape
+        if h != w and any(int(a) & 16 for a in view_axes):
+            raise ValueError(f"stage_views: view_axes {list(view_axes)} transpose H and W (bit 4, an odd quarter turn), which "
+                             f"needs H == W; the volume has H = {h}, W = {w}")
         xv = self.pool.cl("x_views", n * len(view_axes), d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=x_cl.dtype)
         if intensity is None or not intensity.active:
             ops.mirror_views(x_cl, xv, view_axes)

@@ -2,7 +2,9 @@
 (``method.memo.intensity`` / ``method.cotta.intensity``), the layout of the views, and the per-view parameter draws.
 
 The views of a volume are the mirror group of ``mirror_axes`` times ``copies`` intensity copies: V = 2^k * copies <= 8,
-view v has the mirror mask ``view_masks(mirror_axes)[v % 2^k]`` and the copy index ``v // 2^k``.  View 0 is the volume
+view v has the mirror mask ``view_masks(mirror_axes)[v % 2^k]`` and the copy index ``v // 2^k``.  With the quarter turns of
+the methods' ``rot90`` block the geometric views are ({identity} + the turns) x the mirror group, G of them, and view v has
+the code ``view_layout(...)[v % G]`` and the copy index ``v // G``.  View 0 is the volume
 itself; every view v >= 1 takes its own draw (g, a, b) and, per voxel, its own noise.  On a value, in this order:
 
     gamma      x <- ((x - lo) / (hi - lo))^g * (hi - lo) + lo     g = exp(gamma * (2u - 1)); lo / hi: the channel's range
@@ -49,16 +51,34 @@ def philox4x32_10(counter: Sequence[Any], key: Sequence[int]) -> List[np.ndarray
     return [v.astype(np.uint32) for v in c]
 
 
-def view_layout(mirror_axes: Sequence[str], copies: int = 1, key: str = "intensity") -> List[int]:
-    """The mirror mask of every view: the masks of the mirror group, ``copies`` times over."""
-    from .memo import view_masks
+def view_layout(mirror_axes: Sequence[str], copies: int = 1, key: str = "intensity", rot90: Sequence[int] = ()) -> List[int]:
+    """The code of every view: the masks of the mirror group - with quarter turns ``rot90`` (counts out of 1, 2, 3 in the
+    (H, W) plane): ({identity} + the turns, in the listed order) x the mirror group, mirror index fastest - ``copies`` times
+    over.  A code is a mirror mask (bit 0 = W, 1 = H, 2 = D) plus bit 4 = H and W transposed first."""
+    from .memo import ROT90_CODES, rotated_code, view_masks
     base = view_masks(mirror_axes)
     if isinstance(copies, bool) or not isinstance(copies, int) or copies not in COPIES:
         raise ValueError(f"{key}.copies = {copies!r}: expected 1, 2, 4 or 8")
     if len(base) * copies > MAX_VIEWS:
         raise ValueError(f"{key}.copies = {copies} with {len(base)} mirrored views: V = {len(base) * copies} views, at most "
                          f"{MAX_VIEWS}")
-    return list(base) * copies
+    turns = list(rot90)
+    if not turns:
+        return list(base) * copies
+    rkey = key.rsplit(".", 1)[0] + ".rot90" if "." in key else "rot90"
+    views = len(base) * (1 + len(turns)) * copies
+    if views not in (1, 2, 4, 8):
+        raise ValueError(f"{rkey}.k = {turns!r} with {len(base)} mirrored views and {copies} copies: V = {len(base)} * "
+                         f"{1 + len(turns)} * {copies} = {views} views, expected 1, 2, 4 or 8 (one turn or all three)")
+    codes: List[int] = []
+    for t in [0] + turns:
+        for m in base:
+            code = rotated_code(ROT90_CODES[t] if t else 0, m)
+            if code in codes:
+                raise ValueError(f"{rkey}.k = {turns!r} with mirror_axes = {list(mirror_axes)!r}: views {codes.index(code)} and "
+                                 f"{len(codes)} are the same view (code {code}) in every copy")
+            codes.append(code)
+    return codes * copies
 
 
 @dataclass
@@ -83,9 +103,10 @@ class IntensitySpec:
         return any(getattr(self, k) > 0.0 for k in MAGNITUDES)
 
 
-def parse_intensity(value: Any, mirror_axes: Sequence[str], key: str = "method.memo.intensity") -> IntensitySpec:
-    """The ``intensity`` block (a mapping, or None for the defaults) of a method whose views mirror ``mirror_axes``;
-    ``key``: the config key it came from, for the messages."""
+def parse_intensity(value: Any, mirror_axes: Sequence[str], key: str = "method.memo.intensity",
+                    rot90: Sequence[int] = ()) -> IntensitySpec:
+    """The ``intensity`` block (a mapping, or None for the defaults) of a method whose views mirror ``mirror_axes`` and
+    turn by the quarter turns ``rot90`` (``memo.parse_rot90``); ``key``: the config key it came from, for the messages."""
     value = {} if value is None else value
     if not hasattr(value, "keys"):
         raise ValueError(f"{key} = {value!r}: expected a mapping with the keys copies, scale, shift, gamma, noise_std, "
@@ -95,7 +116,7 @@ def parse_intensity(value: Any, mirror_axes: Sequence[str], key: str = "method.m
         if k not in known:
             raise ValueError(f"{key}.{k}: unknown key (expected one of {', '.join(known)})")
     copies = get_config(value, "copies", 1)
-    view_axes = view_layout(mirror_axes, copies, key)
+    view_axes = view_layout(mirror_axes, copies, key, rot90)
     mags = {}
     for k in MAGNITUDES:
         v = get_config(value, k, 0.0)

@@ -2,20 +2,24 @@
 the native engine, next to ``entmin_tta`` (Tent) and ``sar_tta`` (SAR) - the method that was designed for one test point
 adapted episodically: minimise the entropy of the prediction AVERAGED over several augmented views of the one input.
 
-Per volume and step, with F_v = mirror along view v's axes (its own inverse) and the weights w shared by the views:
+Per volume and step, with F_v = view v's map (mirrors, quarter turns: exact on the voxel grid, with an exact inverse) and the
+weights w shared by the views:
 
     z_v  = f(F_v x; w)                      v = 0..V-1   (V consecutive batch items on the volume's replica, train-mode norms)
-    u_v  = F_v z_v                                       (back in the volume's own frame)
+    u_v  = F_v^-1 z_v                                    (back in the volume's own frame)
     pbar = 1/V sum_v sigmoid(u_v)           L = mean over (region, voxel) of H_bern(pbar)            (sigmoid head)
     pbar = 1/V sum_v softmax_r(u_v)         L = mean over voxel of -sum_r pbar_r log pbar_r            (softmax head)
     one step of training.optimizer with dL/dw summed over the V views
 
 The views are every subset of ``method.memo.mirror_axes`` (nnU-Net's test-time mirroring): V = 2^k, view v mirrors
-``mirror_axes[i]`` iff bit i of v is set, view 0 is the volume itself.  After the last step: the eval-mode forward of the
+``mirror_axes[i]`` iff bit i of v is set, view 0 is the volume itself.  ``method.memo.rot90.k`` (default []) adds quarter turns
+in the (H, W) plane - the one geometric augmentation the upstream trainer applies (``RandRotate90d(max_k=3)``): the views are
+then ({identity} + the turns of k) x the mirror group, mirror index fastest, V = 2^len(mirror_axes) * (1 + len(k)); an odd turn
+needs H == W.  After the last step: the eval-mode forward of the
 unmirrored volume (``ensemble: false``), or of all views, combined as logit(pbar) / log pbar (``ensemble: true``).
 
-Where this differs from the paper: the views are the mirror group instead of AugMix samples (the one augmentation whose
-inverse is exact on the voxel grid, so the views' predictions meet in one frame without resampling); the elements are
+Where this differs from the paper: the views are the mirror group and the quarter turns instead of AugMix samples (the
+augmentations whose inverse is exact on the voxel grid, so the views' predictions meet in one frame without resampling); the elements are
 voxels (or voxel x region pairs), not images; the step count is ``method.steps``, shared with Tent.
 
 With ``mirror_axes: []`` (V = 1) the method IS ``entmin_tta``: the same launches, bit for bit.  With V > 1 the fused
@@ -50,6 +54,45 @@ def parse_mirror_axes(value: Any, key: str = "method.memo.mirror_axes") -> List[
     return axes
 
 
+# a quarter turn in the (H, W) plane as a view code: bit 4 = transpose H and W, THEN the mirrors of bits 0-2.  On a
+# channels-last item [D, H, W, C], torch.rot90(x, k, dims=(H, W)) is code ROT90_CODES[k] (tests/test_rot90_host.py derives it)
+ROT90_CODES = {1: 18, 2: 3, 3: 17}
+TRANSPOSE = 16
+
+
+def parse_rot90(value: Any, key: str = "method.memo.rot90") -> List[int]:
+    """The ``rot90`` block ``{k: [...]}`` (or None for the default, no turns): a list of distinct quarter-turn counts out of
+    1, 2, 3; ``key``: the config key it came from, for the messages."""
+    value = {} if value is None else value
+    if not hasattr(value, "keys"):
+        raise ValueError(f"{key} = {value!r}: expected a mapping with the key k (a list of quarter turns out of 1, 2, 3)")
+    for name in value.keys():
+        if name != "k":
+            raise ValueError(f"{key}.{name}: unknown key (expected k)")
+    k = get_config(value, "k", [])
+    if isinstance(k, (str, bytes)) or not hasattr(k, "__iter__") or hasattr(k, "keys"):
+        raise ValueError(f"{key}.k = {k!r}: expected a list of quarter turns out of 1, 2, 3")
+    turns = list(k)
+    for t in turns:
+        if isinstance(t, bool) or not isinstance(t, int) or t not in ROT90_CODES:
+            raise ValueError(f"{key}.k = {turns!r}: {t!r} is no quarter-turn count (1, 2 or 3)")
+    if len(set(turns)) != len(turns):
+        raise ValueError(f"{key}.k = {turns!r}: a turn is repeated")
+    return [int(t) for t in turns]
+
+
+def rotated_code(turn_code: int, mask: int) -> int:
+    """The code of "mirror ``mask`` after the view ``turn_code``": the mirrors act on the view's own axes."""
+    return (turn_code & TRANSPOSE) | ((turn_code & 7) ^ mask)
+
+
+def check_square(view_axes: Sequence[int], h: int, w: int, key: str = "method.memo.rot90") -> None:
+    """An odd quarter turn (a code with bit 4) needs H == W: raise before anything is staged or launched."""
+    if h != w and any(int(a) & TRANSPOSE for a in view_axes):
+        raise ValueError(f"{key}.k: an odd quarter turn needs square (H, W) planes, the volume has H = {h}, W = {w} "
+                         "(k: [2] is the only turn of a non-square plane)")
+
+
 def view_masks(axes: Sequence[str]) -> List[int]:
     """The mirror mask of every view: view v mirrors axes[i] iff bit i of v is set (view 0 = the volume itself)."""
     return [sum(AXIS_BITS[a] for i, a in enumerate(axes) if (v >> i) & 1) for v in range(1 << len(axes))]
@@ -57,7 +100,8 @@ def view_masks(axes: Sequence[str]) -> List[int]:
 
 @register_plugin("memo_tta")
 class MarginalEntropyTTA(EntropyMinimizationTTA):
-    """``method.memo.mirror_axes`` (default [h, w]: 4 views) and ``method.memo.ensemble`` (default false); the optimizer is
+    """``method.memo.mirror_axes`` (default [h, w]: 4 views), ``method.memo.rot90`` (default {k: []}) and
+    ``method.memo.ensemble`` (default false); the optimizer is
     ``training.optimizer`` exactly as for ``entmin_tta``."""
 
     def __init__(self, config: Any = None):
@@ -69,8 +113,10 @@ class MarginalEntropyTTA(EntropyMinimizationTTA):
         if not isinstance(ens, bool):
             raise ValueError(f"method.memo.ensemble = {ens!r}: expected true or false")
         self.ensemble = ens
-        self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, "method.memo.intensity")
-        self.view_axes = self.intensity.view_axes          # the mirror group, ``intensity.copies`` times over
+        self.rot90 = parse_rot90(get_config(s, "rot90", None), "method.memo.rot90")
+        self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, "method.memo.intensity", self.rot90)
+        # ({identity} + the quarter turns) x the mirror group, ``intensity.copies`` times over
+        self.view_axes = self.intensity.view_axes
         self.views = len(self.view_axes)
         if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
             raise NotImplementedError("method.moddrop.enabled: true is not supported by memo_tta (one modality mask per step "
@@ -103,6 +149,7 @@ class MarginalEntropyTTA(EntropyMinimizationTTA):
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
         if self.views == 1:
             return super()._stage(x_cl)
+        check_square(self.view_axes, int(x_cl.shape[2]), int(x_cl.shape[3]), "method.memo.rot90")
         self.rt.views = self.views          # every launch of the loop carries V consecutive batch items per volume
         if not self.intensity.active:
             return self.rt.stage_views(x_cl, self.view_axes), ()

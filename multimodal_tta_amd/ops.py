@@ -809,13 +809,14 @@ def entropy_filtered_items(logits: torch.Tensor, dlogits: torch.Tensor, margin: 
 
 
 def _view_axes(view_axes: Sequence[int]):
-    """The host array of mirror masks the MEMO entry points read at launch (bit 0 = W, 1 = H, 2 = D)."""
+    """The host array of view codes the MEMO entry points read at launch (bit 0 = W, 1 = H, 2 = D mirrored; bit 4 = H and W
+    transposed before the mirrors, H == W only: a quarter turn in the (H, W) plane is code 18, 3 or 17 for k = 1, 2, 3)."""
     return (C.c_int32 * len(view_axes))(*[int(a) for a in view_axes])
 
 
 def mirror_views(x: torch.Tensor, y: torch.Tensor, view_axes: Sequence[int]) -> None:
-    """y[g * V + v] = x[g] mirrored along the axes of mask view_axes[v]: channels-last [G,D,H,W,C] -> [G*V,D,H,W,C], whole
-    voxel rows (pad lanes included), fp32 or bf16, bit-exact."""
+    """y[g * V + v] = x[g] under the code view_axes[v] (transposed in (H, W) where bit 4 is set, then mirrored along the axes
+    of bits 0-2): channels-last [G,D,H,W,C] -> [G*V,D,H,W,C], whole voxel rows (pad lanes included), fp32 or bf16, bit-exact."""
     tx, ty = desc_cl(x), desc_cl(y)
     check(_lib.load().mmtta_mirror_views(C.byref(tx), C.byref(ty), len(view_axes), _view_axes(view_axes), stream_ptr()),
           "mirror_views")
@@ -840,7 +841,7 @@ def intensity_range(x: torch.Tensor, partial: torch.Tensor, out: torch.Tensor) -
 
 def augment_views(x: torch.Tensor, y: torch.Tensor, view_axes: Sequence[int], table_host: torch.Tensor, table: torch.Tensor,
                   value_range: torch.Tensor, seed: int, ordinals: torch.Tensor) -> None:
-    """y[g * V + v] = x[g] mirrored along the axes of mask view_axes[v] and put through view v's intensity transform
+    """y[g * V + v] = x[g] under the code view_axes[v] (as ``mirror_views``) and put through view v's intensity transform
     (``intensity.py``): ``table`` device fp32 [G, V, C, 4] with the rows (g, a, b, sigma), ``table_host`` its host copy (the
     entry point checks view 0's rows on it), ``value_range`` what ``intensity_range`` wrote for x, ``ordinals`` device int32
     [>= G].  An all-identity table gives ``mirror_views``' bits."""
@@ -868,7 +869,7 @@ def memo_partials(logits: torch.Tensor, views: int) -> int:
 def memo_loss_items(logits: torch.Tensor, dlogits: torch.Tensor, view_axes: Sequence[int], partial: torch.Tensor,
                     loss: torch.Tensor, softmax: bool = False) -> None:
     """MEMO's marginal entropy of every volume on its own: logits / dlogits [G*V,D,H,W,R] (item g*V+v = view v of volume g,
-    each in its own mirrored frame), loss fp32 [G]."""
+    each in its own mirrored / turned frame), loss fp32 [G]."""
     views = len(view_axes)
     need = memo_partials(logits, views)          # -1 for a bad view count: the entry point below says which
     if loss.numel() < logits.shape[0] // max(views, 1):
