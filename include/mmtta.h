@@ -304,6 +304,11 @@ int64_t mmtta_conv_wgrad_workspace_bytes_sets(const mmtta_conv_desc* desc, const
 int mmtta_conv_wgrad_sets(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                           const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
                           int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);
+/* The reduction plan of that launch sequence (bookkeeping for profiles and tests; nothing is launched):
+ *   plan[0] partial slabs per set   plan[1] chunks of the pre-reduce stage (0: none; else the last stage reads these)
+ *   plan[2], plan[3] the padded channel counts CGp, CDp of a slab's [tap][CGp][CDp] rows */
+int mmtta_conv_wgrad_plan_sets(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_tensor* dy,
+                               const mmtta_param_sets* sets, int32_t plan[4]);
 
 /* ------------------------------------------------------------------ input pre-pass -------- */
 /* Per-channel intensity rule of one image [C,D,H,W] (reference src/datasets/transforms.py:129-223).

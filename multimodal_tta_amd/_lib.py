@@ -116,6 +116,7 @@ _SIGNATURES = {
                                       _P(Tensor), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
     "mmtta_conv_wgrad_workspace_bytes": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor)]),
     "mmtta_conv_wgrad_workspace_bytes_sets": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor), _P(ParamSets)]),
+    "mmtta_conv_wgrad_plan_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(Tensor), _P(ParamSets), _P(C.c_int32)]),
     "mmtta_conv_wgrad_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(Tensor), C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
     "mmtta_conv_wgrad_kernel": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(Tensor)]),

@@ -355,6 +355,115 @@ struct UpdArgs {
 };
 
 constexpr int UPD_CG = 8, UPD_CD = 32, UPD_RS = UPD_CG * 27 + 1;      // LDS row = one cd: [cg][tap] (odd stride)
+constexpr int UPD_NV = 27 * UPD_CG * UPD_CD / 4;                      // float4 items of a tile: 1728 = 6.75 per thread
+
+__device__ __forceinline__ void add4(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+
+// slab_sums for a thread that owns 4 consecutive cd of a (tap, cg) row: each lane of the float4 is slab_sums' value, the
+// sum over the slabs in slab order.  (The tail trip loads only the slabs that exist instead of clamped copies plus 0: the
+// accumulator starts at +0 and can never become -0, so the dropped `+ 0.f` terms change no bit.)
+template <int NI>
+__device__ __forceinline__ void slab_sums4(const float4* const* pit, int nsl, long long st4, float4* acc) {
+#pragma unroll
+  for (int it = 0; it < NI; ++it) acc[it] = make_float4(0.f, 0.f, 0.f, 0.f);
+  int sl = 0;
+  for (; sl + 4 <= nsl; sl += 4) {
+    float4 v[NI][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int it = 0; it < NI; ++it) v[it][u] = pit[it][(long long)(sl + u) * st4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int it = 0; it < NI; ++it) add4(acc[it], v[it][u]);
+  }
+  const int rem = nsl - sl;                                           // 0 .. 3, the same for the whole launch
+  if (rem > 0) {
+    float4 v[NI][3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+      if (u < rem) {
+#pragma unroll
+        for (int it = 0; it < NI; ++it) v[it][u] = pit[it][(long long)(sl + u) * st4];
+      }
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+      if (u < rem) {
+#pragma unroll
+        for (int it = 0; it < NI; ++it) add4(acc[it], v[it][u]);
+      }
+  }
+}
+
+// reduce phase, 16-byte form: item f = tid + 256 j (j < 7) is row f / 8 = cgl * 27 + tap of the tile and cd 4 (f % 8) ..+3
+template <int NI>
+__device__ __forceinline__ void upd_reduce4(const float* __restrict__ slab, int nsl, long long st, int j0, int cg0, int cd0, int Cg,
+                                            int Cd, int CGp, int CDp, float* tile) {
+  const float4* pit[NI];
+#pragma unroll
+  for (int it = 0; it < NI; ++it) {
+    const int f = min((int)threadIdx.x + 256 * (j0 + it), UPD_NV - 1);
+    const int row = f >> 3, c4 = f & 7, cgl = row / 27, tap = row % 27;
+    pit[it] = reinterpret_cast<const float4*>(slab + ((long long)tap * CGp + min(cg0 + cgl, Cg - 1)) * CDp + cd0 + 4 * c4);
+  }
+  float4 acc[NI];
+  slab_sums4<NI>(pit, nsl, st / 4, acc);
+#pragma unroll
+  for (int it = 0; it < NI; ++it) {
+    const int f = threadIdx.x + 256 * (j0 + it);
+    if (f < UPD_NV) {
+      const int row = f >> 3, c4 = f & 7, cgl = row / 27;              // row = cgl * 27 + tap: the offset inside an LDS row
+      const bool lg = cg0 + cgl < Cg;
+      const int cd = cd0 + 4 * c4;
+      float* t = tile + (4 * c4) * UPD_RS + row;
+      t[0] = lg && cd < Cd ? acc[it].x : 0.f;
+      t[UPD_RS] = lg && cd + 1 < Cd ? acc[it].y : 0.f;
+      t[2 * UPD_RS] = lg && cd + 2 < Cd ? acc[it].z : 0.f;
+      t[3 * UPD_RS] = lg && cd + 3 < Cd ? acc[it].w : 0.f;
+    }
+  }
+}
+
+// optimizer phase, 16-byte form: a cd's run of 8 cg x 27 taps is 54 float4; item g = tid + 256 k is (cdl, r4) = (g / 54,
+// g % 54).  All of a batch's p / m / v loads are issued before the first use (clamped addresses, stores predicated).
+template <int KIND, int NB>
+__device__ __forceinline__ void upd_optim4(const UpdArgs& u, long long ob, long long rowst, int k0, int cd0, int Cd, bool first,
+                                           bool keep_m, bool decay, float step_size, float bc2_sqrt, float* tile) {
+  float4 p[NB], m[NB], v[NB];
+  long long off[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    const int g = min((int)threadIdx.x + 256 * (k0 + k), UPD_NV - 1);
+    const int cdl = min(g / 54, Cd - 1 - cd0), r4 = g % 54;
+    off[k] = ob + cdl * rowst + 4 * r4;
+    p[k] = *reinterpret_cast<const float4*>(u.wp + off[k]);
+    m[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    v[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!first) {
+      if (keep_m) m[k] = *reinterpret_cast<const float4*>(u.wm + off[k]);
+      if (KIND != 2) v[k] = *reinterpret_cast<const float4*>(u.wv + off[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    const int g = threadIdx.x + 256 * (k0 + k);
+    const int cdl = g / 54, r4 = g % 54;
+    if (g < UPD_NV && cd0 + cdl < Cd) {
+      float* t = tile + cdl * UPD_RS + 4 * r4;
+      optim_update<KIND>(p[k].x, t[0], m[k].x, v[k].x, decay, u.a, step_size, bc2_sqrt, first);
+      optim_update<KIND>(p[k].y, t[1], m[k].y, v[k].y, decay, u.a, step_size, bc2_sqrt, first);
+      optim_update<KIND>(p[k].z, t[2], m[k].z, v[k].z, decay, u.a, step_size, bc2_sqrt, first);
+      optim_update<KIND>(p[k].w, t[3], m[k].w, v[k].w, decay, u.a, step_size, bc2_sqrt, first);
+      *reinterpret_cast<float4*>(u.wp + off[k]) = p[k];
+      if (keep_m) *reinterpret_cast<float4*>(u.wm + off[k]) = m[k];
+      if (KIND != 2) *reinterpret_cast<float4*>(u.wv + off[k]) = v[k];
+      t[0] = p[k].x; t[1] = p[k].y; t[2] = p[k].z; t[3] = p[k].w;
+    }
+  }
+}
+
+__device__ __forceinline__ bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int KIND>
 __global__ __launch_bounds__(256) void wgrad_update27_kernel(const float* __restrict__ slab, int nsl, int Cg, int Cd, int CGp,
@@ -392,27 +501,34 @@ __global__ __launch_bounds__(256) void wgrad_update27_kernel(const float* __rest
   }
   const int cg0 = blockIdx.x * UPD_CG;
   const long long st = (long long)27 * CGp * CDp;
-  // ---- reduce: element e = tid + 256 j (j < 27) is (cgl, tap, cdl) = (e / 864, (e % 864) >> 5, e & 31), as in reduce27
-  constexpr int NI = 9;
+  // ---- reduce.  16-byte form when the slab rows allow it (the padded [tap][CGp][CDp] slabs of the planner always do): a
+  // thread owns 4 consecutive cd of a row, 4 + 3 rows in two chunks, 4 slabs in flight per row
+  if (ptr16(slab) && CDp % 4 == 0) {
+    upd_reduce4<4>(slab, nsl, st, 0, cg0, cd0, Cg, Cd, CGp, CDp, tile);
+    upd_reduce4<3>(slab, nsl, st, 4, cg0, cd0, Cg, Cd, CGp, CDp, tile);
+  } else {
+    // 4-byte form: element e = tid + 256 j (j < 27) is (cgl, tap, cdl) = (e / 864, (e % 864) >> 5, e & 31), as in reduce27
+    constexpr int NI = 9;
 #pragma unroll 1
-  for (int j0 = 0; j0 < 27; j0 += NI) {
-    const float* pit[NI];
-    bool live[NI];
+    for (int j0 = 0; j0 < 27; j0 += NI) {
+      const float* pit[NI];
+      bool live[NI];
 #pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const int e = threadIdx.x + 256 * (j0 + it);
-      const int cgl = e / 864, i = e % 864, cdl = i & 31, tap = i >> 5;
-      const int cg = cg0 + cgl, cd = cd0 + cdl;
-      live[it] = cg < Cg && cd < Cd;
-      pit[it] = slab + ((long long)tap * CGp + min(cg, Cg - 1)) * CDp + min(cd, CDp - 1);
-    }
-    float acc[NI];
-    slab_sums<NI>(pit, nsl, st, acc);
+      for (int it = 0; it < NI; ++it) {
+        const int e = threadIdx.x + 256 * (j0 + it);
+        const int cgl = e / 864, i = e % 864, cdl = i & 31, tap = i >> 5;
+        const int cg = cg0 + cgl, cd = cd0 + cdl;
+        live[it] = cg < Cg && cd < Cd;
+        pit[it] = slab + ((long long)tap * CGp + min(cg, Cg - 1)) * CDp + min(cd, CDp - 1);
+      }
+      float acc[NI];
+      slab_sums<NI>(pit, nsl, st, acc);
 #pragma unroll
-    for (int it = 0; it < NI; ++it) {
-      const int e = threadIdx.x + 256 * (j0 + it);
-      const int cgl = e / 864, i = e % 864, cdl = i & 31, tap = i >> 5;
-      tile[cdl * UPD_RS + cgl * 27 + tap] = live[it] ? acc[it] : 0.f;
+      for (int it = 0; it < NI; ++it) {
+        const int e = threadIdx.x + 256 * (j0 + it);
+        const int cgl = e / 864, i = e % 864, cdl = i & 31, tap = i >> 5;
+        tile[cdl * UPD_RS + cgl * 27 + tap] = live[it] ? acc[it] : 0.f;
+      }
     }
   }
   __syncthreads();
@@ -422,21 +538,31 @@ __global__ __launch_bounds__(256) void wgrad_update27_kernel(const float* __rest
     const bool decay = wd_on && u.w_decay;
     const long long wo = pset_weight_elems(ps, q);
     const int ncg = min(UPD_CG, Cg - cg0);
-    for (int e = threadIdx.x; e < UPD_CD * UPD_CG * 27; e += 256) {
-      const int cdl = e / (UPD_CG * 27), r = e % (UPD_CG * 27);
-      const int cd = cd0 + cdl;
-      if (cd < Cd && r < ncg * 27) {
-        const long long o = wo + ((long long)cd * Cg + cg0) * 27 + r;
-        float pi = u.wp[o], mi = 0.f, vi = 0.f;
-        if (!first) {
-          if (keep_m) mi = u.wm[o];
-          if (KIND != 2) vi = u.wv[o];
+    const long long ob = wo + ((long long)cd0 * Cg + cg0) * 27, rowst = (long long)Cg * 27;
+    // 16-byte form: whole runs (a full cg tile) that start on 16 bytes in every row, for every array the step touches
+    bool vec = ncg == UPD_CG && rowst % 4 == 0 && ptr16(u.wp + ob);
+    if (keep_m) vec = vec && ptr16(u.wm + ob);
+    if (KIND != 2) vec = vec && ptr16(u.wv + ob);
+    if (vec) {
+      upd_optim4<KIND, 4>(u, ob, rowst, 0, cd0, Cd, first, keep_m, decay, step_size, bc2_sqrt, tile);
+      upd_optim4<KIND, 3>(u, ob, rowst, 4, cd0, Cd, first, keep_m, decay, step_size, bc2_sqrt, tile);
+    } else {
+      for (int e = threadIdx.x; e < UPD_CD * UPD_CG * 27; e += 256) {
+        const int cdl = e / (UPD_CG * 27), r = e % (UPD_CG * 27);
+        const int cd = cd0 + cdl;
+        if (cd < Cd && r < ncg * 27) {
+          const long long o = ob + cdl * rowst + r;
+          float pi = u.wp[o], mi = 0.f, vi = 0.f;
+          if (!first) {
+            if (keep_m) mi = u.wm[o];
+            if (KIND != 2) vi = u.wv[o];
+          }
+          optim_update<KIND>(pi, tile[cdl * UPD_RS + r], mi, vi, decay, u.a, step_size, bc2_sqrt, first);
+          u.wp[o] = pi;
+          if (keep_m) u.wm[o] = mi;
+          if (KIND != 2) u.wv[o] = vi;
+          tile[cdl * UPD_RS + r] = pi;
         }
-        optim_update<KIND>(pi, tile[cdl * UPD_RS + r], mi, vi, decay, u.a, step_size, bc2_sqrt, first);
-        u.wp[o] = pi;
-        if (keep_m) u.wm[o] = mi;
-        if (KIND != 2) u.wv[o] = vi;
-        tile[cdl * UPD_RS + r] = pi;
       }
     }
   }
@@ -2331,6 +2457,16 @@ extern "C" int64_t mmtta_conv_wgrad_workspace_bytes_sets(const mmtta_conv_desc* 
 extern "C" int64_t mmtta_conv_wgrad_workspace_bytes(const mmtta_conv_desc* d, const mmtta_tensor* x,
                                                     const mmtta_tensor* dy) {
   return mmtta_conv_wgrad_workspace_bytes_sets(d, x, dy, nullptr);
+}
+
+extern "C" int mmtta_conv_wgrad_plan_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy,
+                                          const mmtta_param_sets* sets, int32_t plan[4]) {
+  MMTTA_CHECK(plan != nullptr, MMTTA_ERR_INVALID, "wgrad plan: null output");
+  WGeo w;
+  const int st = wgeometry(d, x, dy, sets, w);
+  if (st) return st;
+  plan[0] = w.nsl; plan[1] = w.pre_chunks; plan[2] = w.CGp; plan[3] = w.CDp;
+  return MMTTA_OK;
 }
 
 extern "C" int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy) {

@@ -556,6 +556,17 @@ class ConvOp:
                          (self.io_bytes(x, dy, dw) + (nsets - 1) * dw.numel() * 4.0) * PROFILER.reps)
 
 
+    def wgrad_plan(self, x: torch.Tensor, dy: torch.Tensor) -> dict:
+        """The weight gradient's reduction plan for this problem (mmtta_conv_wgrad_plan_sets): partial slabs per set, chunks
+        of the pre-reduce stage (0: none) and the padded channel counts of a slab.  Launches nothing."""
+        lib = _lib.load()
+        tx, tdy = desc_cl(x), desc_cl(dy)
+        sets = self._sets(self.d_fwd)
+        out = (C.c_int32 * 4)()
+        check(lib.mmtta_conv_wgrad_plan_sets(C.byref(self.d_fwd), C.byref(tx), C.byref(tdy),
+                                             C.byref(sets) if sets is not None else None, out), "conv_wgrad_plan")
+        return {"nsl": int(out[0]), "pre_chunks": int(out[1]), "CGp": int(out[2]), "CDp": int(out[3])}
+
     def plain_bf16_images(self) -> bool:
         """Both images are bare 27-tap bf16 images (what the fused weight update writes): bf16 operands, K >= 16 each way."""
         if self.k != 3 or int(self.d_fwd.dtype) != BF16 or min(self.cin, self.cout) < 16:

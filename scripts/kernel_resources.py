@@ -22,16 +22,26 @@ KEYS = {".vgpr_count": "vgpr", ".agpr_count": "agpr", ".sgpr_count": "sgpr", ".g
         ".private_segment_fixed_size": "scratch", ".vgpr_spill_count": "vgpr_spill", ".sgpr_spill_count": "sgpr_spill"}
 
 
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
 def figures(obj: str) -> dict:
+    """Figures of every gfx950 kernel in an object, or in a linked library (whose fatbin section holds one bundle per object)."""
+    notes = ""
     with tempfile.TemporaryDirectory() as td:
-        co, fb = os.path.join(td, "k.co"), os.path.join(td, "fatbin")
+        co, fb, one = os.path.join(td, "k.co"), os.path.join(td, "fatbin"), os.path.join(td, "bundle")
         if subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fb}", obj, os.path.join(td, "o")],
                           capture_output=True).returncode != 0:
             return {}                                 # host-only object (no device code)
-        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--unbundle", f"--input={fb}",
-                        f"--output={co}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True)
-        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
-                               text=True).stdout
+        blob = open(fb, "rb").read()
+        starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)] or [0]
+        for a, b in zip(starts, starts[1:] + [len(blob)]):
+            with open(one, "wb") as fh:
+                fh.write(blob[a:b])
+            subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--type=o", "--unbundle", f"--input={one}",
+                            f"--output={co}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950"], check=True)
+            notes += subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
+                                    text=True).stdout
     out, cur = {}, None
     for line in notes.splitlines():
         if line.startswith("  - "):            # a kernel's record starts (keys of the record sit at column 4)
