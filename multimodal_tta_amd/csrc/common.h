@@ -101,6 +101,20 @@ inline bool is_cl(const mmtta_tensor* t) { return t->sc == 1 || t->c == 1; }
 inline bool is_f32(const mmtta_tensor* t) { return t->dtype == MMTTA_F32; }
 inline bool is_bf16(const mmtta_tensor* t) { return t->dtype == MMTTA_BF16; }
 
+// ---- operand predicates of the host-side planners
+// 4-channel vector accesses of a tensor are legal: the base sits on `base_bytes` and the n/d/h/w strides keep a group of
+// `elems` elements (a quad) aligned.  quad_bytes: one quad of the tensor's storage type.
+inline bool quad_aligned(const mmtta_tensor* t, int base_bytes, int elems = 4) {
+  return ((uintptr_t)t->ptr) % base_bytes == 0 && t->sw % elems == 0 && t->sh % elems == 0 && t->sd % elems == 0 &&
+         t->sn % elems == 0;
+}
+inline int quad_bytes(const mmtta_tensor* t) { return is_bf16(t) ? 8 : 16; }
+// 32-bit element offsets inside a batch item: the last voxel's offset plus `pad` elements fits 31 bits
+inline bool item_fits_31(const mmtta_tensor* t, int64_t pad) {
+  const int64_t last = (int64_t)(t->d - 1) * t->sd + (int64_t)(t->h - 1) * t->sh + (int64_t)(t->w - 1) * t->sw + pad;
+  return last < ((int64_t)1 << 31);
+}
+
 // ---- storage-type helpers.  In `bf16` precision the forward activations (raw conv outputs, residual-unit outputs,
 // concat buffers) are STORED as bf16 (what torch autocast does); gradients, logits, statistics and weights stay fp32.
 // A tensor's base pointer is carried as `float*` either way; `bf` says the elements are 2 bytes wide, offsets are in

@@ -843,7 +843,7 @@ long long upconv8_image_bytes(const mmtta_conv_desc* d) {
 }
 
 static bool aligned16(const mmtta_tensor* x) {
-  return x->sc == 1 && x->sw % 4 == 0 && x->sh % 4 == 0 && x->sd % 4 == 0 && x->sn % 4 == 0 && ((uintptr_t)x->ptr) % 16 == 0;
+  return x->sc == 1 && quad_aligned(x, 16);
 }
 
 // ------------------------------------------------------------------ lanes along N (K <= 4 gathered, N = 32 / 64)
@@ -1187,14 +1187,12 @@ bool chan_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtt
   // N = 64 only on the matrix cores (bf16 mode): the input gradient of the 64->R up-convolution
   // a one-channel slice of a wider tensor (modality m of the network input) need not start on a 16-byte group: the kernels
   // load the group it sits in and pick its float (CArgs::koff)
-  const bool slice1 = K == 1 && x->sc == 1 && x->sw % 4 == 0 && x->sh % 4 == 0 && x->sd % 4 == 0 && x->sn % 4 == 0 &&
-                      ((uintptr_t)x->ptr) % 4 == 0;
+  const bool slice1 = K == 1 && x->sc == 1 && quad_aligned(x, 4);
   // the kernels address with 32-bit element offsets inside a batch item (input) / a z-slice (output)
   const bool small = (long long)x->d * x->sd < (1LL << 31) && (long long)(y->h + 4) * y->sh < (1LL << 31);
   // bf16-stored gathered tensor (8-byte voxels): the matrix-core kernel
   if (is_bf16(x))
-    return d->dtype == MMTTA_BF16 && K <= 4 && ((N == 32 && K >= 2) || N == 64) && x->sc == 1 && x->sw % 4 == 0 && x->sh % 4 == 0 &&
-           x->sd % 4 == 0 && x->sn % 4 == 0 && ((uintptr_t)x->ptr) % 8 == 0 && small;
+    return d->dtype == MMTTA_BF16 && K <= 4 && ((N == 32 && K >= 2) || N == 64) && x->sc == 1 && quad_aligned(x, 8) && small;
   return K <= 4 && (N == 32 || (N == 64 && d->dtype == MMTTA_BF16)) && (aligned16(x) || slice1) && x->sw >= 4 && small;
 }
 
@@ -1387,8 +1385,7 @@ bool pointwise_small_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x,
   if (x_norm && (x_norm->mean || x_norm->scale)) return false;
   if (!(d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONV_DGRAD)) return false;
   return x->c <= 4 && is_f32(x) && y->c % 4 == 0 && y->c >= 4 && aligned16(x) && x->sw >= 4 &&
-         (is_bf16(y) ? (y->sc == 1 && y->sw % 4 == 0 && y->sh % 4 == 0 && y->sd % 4 == 0 && y->sn % 4 == 0 && ((uintptr_t)y->ptr) % 8 == 0)
-                     : aligned16(y));
+         (is_bf16(y) ? (y->sc == 1 && quad_aligned(y, 8)) : aligned16(y));
 }
 
 int pointwise_small_run(const mmtta_tensor* x, const void* packed, int Kp, int Np, const float* bias, const mmtta_tensor* y,

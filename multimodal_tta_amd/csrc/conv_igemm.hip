@@ -2008,11 +2008,8 @@ int conv_run_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
   a.out_bf = is_bf16(y) ? 1 : 0;
   a.add_bf = (epi && epi->add && is_bf16(epi->add)) ? 1 : 0;
   {
-    auto al16 = [](const void* p, long long sn, long long sd, long long sh, long long sw, int bf) {      // 4-channel accesses
-      return ((uintptr_t)p) % (bf ? 8 : 16) == 0 && sn % 4 == 0 && sd % 4 == 0 && sh % 4 == 0 && sw % 4 == 0;
-    };
-    const bool oal = al16(y->ptr, y->sn, y->sd, y->sh, y->sw, a.out_bf) && y->c % 4 == 0 &&
-                     (a.add == nullptr || al16(a.add, a.asn, a.asd, a.ash, a.asw, a.add_bf)) &&
+    const bool oal = quad_aligned(y, quad_bytes(y)) && y->c % 4 == 0 &&                                    // 4-channel accesses
+                     (!(epi && epi->add) || quad_aligned(epi->add, quad_bytes(epi->add))) &&
                      (bias == nullptr || ((uintptr_t)bias) % 16 == 0);
     a.ovec = (oal && g_epilogue_vec) ? 1 : 0;
   }

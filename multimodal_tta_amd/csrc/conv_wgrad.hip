@@ -2002,39 +2002,80 @@ static void launch_tiny(const WTArgs& a, int cs, int cb, int blocks, hipStream_t
   }
 }
 
-// 4-channel vector loads of a tensor are legal: base and every stride keep a quad aligned (16 bytes fp32, 8 bytes bf16)
-static bool wvec_ok(const mmtta_tensor* t) {
-  return ((uintptr_t)t->ptr) % (is_bf16(t) ? 8 : 16) == 0 && t->sw % 4 == 0 && t->sh % 4 == 0 && t->sd % 4 == 0 && t->sn % 4 == 0;
-}
-
-// the transposed-read kernel's loader: 16-byte items of 8 channels (fp32: two quads), 32-bit element offsets built
+// ------------------------------------------------------------------ host side: plan (wgeometry), then launch
+// The transposed-read kernel's loader: 16-byte items of 8 channels (fp32: two quads), 32-bit element offsets built
 // from 24-bit multiply-adds
 static bool wtr_ok(const mmtta_tensor* t) {
-  const int64_t q = is_bf16(t) ? 8 : 4;
-  if (((uintptr_t)t->ptr) % 16 != 0 || t->sw % q != 0 || t->sh % q != 0 || t->sd % q != 0 || t->sn % q != 0) return false;
+  if (!quad_aligned(t, 16, is_bf16(t) ? 8 : 4)) return false;
   const int64_t lim24 = (int64_t)1 << 24;
   if (t->sw >= lim24 || t->sh >= lim24 || t->sd >= lim24 || t->d >= lim24 || t->h >= lim24 || t->w >= lim24) return false;
-  const int64_t last = (int64_t)(t->d - 1) * t->sd + (int64_t)(t->h - 1) * t->sh + (int64_t)(t->w - 1) * t->sw + roundup(t->c, 8) + 8;
-  return last < ((int64_t)1 << 31);
+  return item_fits_31(t, roundup(t->c, 8) + 8);
 }
 
+// Which main kernel a call runs: the values are the public ids of mmtta_conv_wgrad_kernel (4 and 5 are retired)
+enum WRoute : int {
+  W_F32_S1 = 0,     // wgrad_f32_kernel, 27 taps, stride 1
+  W_F32_S2 = 1,     //                   27 taps, stride 2 (ConvTranspose3d included)
+  W_F32_1X1 = 2,    //                   1 tap
+  W_SMALL = 3,      // wgrad_small_kernel: <= 4 channels on one side
+  W_TINY = 6,       // wgrad_tiny_kernel: <= 4 channels on both sides, fp32 VALU
+  W_TR_S1 = 7,      // wgrad_tr_kernel (bf16 operands, transposed reads), stride 1
+  W_TR_S2 = 8,      //                                                    stride 2
+  W_TR_1X1 = 9,     // wgrad_tr1_kernel: the 1x1x1 streaming kernel of bf16 precision
+  W_THIN_TR = 10,   // wgrad_thin_tr_kernel: the thin 27-tap layers of bf16 precision
+};
+static inline bool route_thin(WRoute r) { return r == W_SMALL || r == W_THIN_TR; }        // W2Args, [128][CDp] slabs
+static inline bool route_reduce27(WRoute r) { return r == W_F32_S1 || r == W_F32_S2 || r == W_TR_S1 || r == W_TR_S2; }
+
+// Where the bias gradient comes from
+enum WBias {
+  WB_MAIN_PARTIALS,     // rows [nsl][CDp] written by the main kernel (its dense operand is dy)
+  WB_COLSUMS,           // column sums of dy (launch_channel_sums): dy is the gathered operand
+  WB_TINY_PARTIALS,     // the tiny kernel's rows [blocks][4]
+};
+
 struct WGeo {
-  bool tiny; int tiny_blocks;
-  bool bf16; bool small; int small_is_cd; const mmtta_tensor *q, *pb; bool q_is_x;
+  WRoute route; WBias bias;
+  int tiny_blocks;
+  int small_is_cd; const mmtta_tensor *q, *pb; bool q_is_x;       // thin family: gathered thin tensor Q, dense tensor P
   const mmtta_tensor *g, *dn;
-  int si, ntaps, TZ, TY, TX;
+  int si, ntaps;
   int tz, ty, tx, tiles, S, tps, nsl, CGp, CDp;
-  int64_t slab_floats, db_floats, colsum_blocks, pre_floats; int pre_chunks;
+  int64_t slab_elems, slab_floats, db_floats, colsum_blocks, pre_floats; int pre_chunks;
   bool convt;
-  bool tr;        // bf16 27-tap layer on the transposed-read kernel (its own tile shape)
-  bool tr1;       // 1x1x1 layer of bf16 precision on the transposed-read streaming kernel
-  bool thin_tr;   // thin 27-tap layer of bf16 precision on the transposed-read kernel (wgrad_thin_tr_kernel)
-  int ncb;        // its 32-column blocks per workgroup
-  bool p_thin;    // ... with <= 4 channels on the dense side as well
+  int ncb = 1;    // 32-column blocks per workgroup (wgrad_tr_kernel NB, wgrad_thin_tr_kernel NCB)
+  bool p_thin;    // W_THIN_TR with <= 4 channels on the dense side as well
   int ips, nsets; // batch items per parameter set, sets per launch: tiles / S / nsl / *_floats / colsum_blocks are PER SET
 };
 
-static const int g_wgrad_pair = getenv("MMTTA_WGRAD_PAIR") ? atoi(getenv("MMTTA_WGRAD_PAIR")) : 1;      // (A/B switch: 0 off, 2: every stride-1 layer too)
+// A/B switches read from the environment once.  MMTTA_WGRAD_PAIR: 0 no paired column blocks, 2: every stride-1 layer too.
+// MMTTA_FUSED_UPDATE=0 turns the fused weight update off; the host then takes the separate passes.
+static const int g_wgrad_pair = getenv("MMTTA_WGRAD_PAIR") ? atoi(getenv("MMTTA_WGRAD_PAIR")) : 1;
+static const int g_fused_update = getenv("MMTTA_FUSED_UPDATE") ? atoi(getenv("MMTTA_FUSED_UPDATE")) : 1;
+
+// `want` slabs of `elems` floats over w.tiles tiles: tiles per slab, the slabs that leaves, and the pre-reduce stage past
+// 32 of them.  A split writes `mult` slabs (the four waves of a 1-tap kernel write one each).
+static void plan_slabs(WGeo& w, int want, int64_t elems, int mult) {
+  const int S = std::min(std::max(want, 1), w.tiles);
+  w.tps = (w.tiles + S - 1) / S;
+  w.S = (w.tiles + w.tps - 1) / w.tps;
+  w.nsl = w.S * mult;
+  w.slab_elems = elems;
+  w.slab_floats = (int64_t)w.nsl * elems;
+  w.pre_chunks = w.nsl > 32 ? (w.nsl + 31) / 32 : 0;
+  w.pre_floats = (int64_t)w.pre_chunks * elems;
+}
+
+// the bias source and its workspace rows (after the slabs are planned)
+static void plan_bias(WGeo& w, WBias src, const mmtta_tensor* dy) {
+  w.bias = src;
+  if (src == WB_COLSUMS) {
+    w.colsum_blocks = (int64_t)w.ips * channel_partial_rows(dy);
+    w.db_floats = w.colsum_blocks * 2 * dy->c;
+  } else {
+    w.db_floats = src == WB_TINY_PARTIALS ? (int64_t)w.tiny_blocks * 4 : (int64_t)w.nsl * w.CDp;
+  }
+}
 
 static int wgeometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy, const mmtta_param_sets* sets, WGeo& w) {
   MMTTA_CHECK(d && x && dy && x->ptr && dy->ptr, MMTTA_ERR_INVALID, "wgrad: null argument");
@@ -2055,11 +2096,6 @@ static int wgeometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtt
   MMTTA_CHECK(is_cl(x) && is_cl(dy), MMTTA_ERR_UNSUPPORTED, "wgrad: tensors must be channels-last");
   MMTTA_CHECK(x->c == d->cin && dy->c == d->cout && x->n == dy->n, MMTTA_ERR_INVALID, "wgrad: channel/batch mismatch");
   w.convt = d->op == MMTTA_CONVT_FWD;
-  w.tr = false;
-  w.tr1 = false;
-  w.thin_tr = false;
-  w.ncb = 1;
-  w.p_thin = false;
   if (w.convt) MMTTA_CHECK(d->ksize == 3 && d->stride == 2, MMTTA_ERR_UNSUPPORTED, "wgrad: conv_transpose is k3 s2 only");
   w.g = w.convt ? dy : x;
   w.dn = w.convt ? x : dy;
@@ -2071,61 +2107,46 @@ static int wgeometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtt
     MMTTA_CHECK(dd[i] == want && (!w.convt || gd[i] % 2 == 0), MMTTA_ERR_INVALID,
                 "wgrad: spatial mismatch on axis %d (fine %d, coarse %d)", i, gd[i], dd[i]);
   }
+  const bool bf16 = d->dtype == MMTTA_BF16;
   // both sides <= 4 channels, k3 s1, 16-byte voxel rows: VALU kernel, partials in dw layout
-  auto al16 = [](const mmtta_tensor* t) {
-    return ((uintptr_t)t->ptr) % 16 == 0 && t->sc == 1 && t->sw % 4 == 0 && t->sh % 4 == 0 && t->sd % 4 == 0 && t->sn % 4 == 0 &&
-           (long long)t->w * t->sw * 4 < (1LL << 31);
-  };
+  auto al16 = [](const mmtta_tensor* t) { return t->sc == 1 && quad_aligned(t, 16) && (long long)t->w * t->sw * 4 < (1LL << 31); };
   // fp32 voxels of 16 bytes addressed by 32-bit element offsets inside a batch item (wgrad_thin_tr_kernel's thin operands)
-  auto q_ok = [](const mmtta_tensor* t) {
-    const int64_t last = (int64_t)(t->d - 1) * t->sd + (int64_t)(t->h - 1) * t->sh + (int64_t)(t->w - 1) * t->sw + 8;
-    return is_f32(t) && ((uintptr_t)t->ptr) % 16 == 0 && t->sw % 4 == 0 && t->sh % 4 == 0 && t->sd % 4 == 0 && t->sn % 4 == 0 &&
-           last < ((int64_t)1 << 31);
-  };
-  auto q_ok16 = [](const mmtta_tensor* t) {          // ... or bf16 voxels of 8 bytes
-    const int64_t last = (int64_t)(t->d - 1) * t->sd + (int64_t)(t->h - 1) * t->sh + (int64_t)(t->w - 1) * t->sw + 8;
-    return is_bf16(t) && ((uintptr_t)t->ptr) % 8 == 0 && t->sw % 4 == 0 && t->sh % 4 == 0 && t->sd % 4 == 0 && t->sn % 4 == 0 &&
-           last < ((int64_t)1 << 31);
-  };
-  w.tiny = !w.convt && d->cin <= 4 && d->cout <= 4 && d->ksize == 3 && d->stride == 1 && al16(x) && al16(dy);
+  auto q_ok = [](const mmtta_tensor* t) { return is_f32(t) && quad_aligned(t, 16) && item_fits_31(t, 8); };
+  auto q_ok16 = [](const mmtta_tensor* t) { return is_bf16(t) && quad_aligned(t, 8) && item_fits_31(t, 8); };   // ... or bf16 voxels of 8 bytes
   // bf16 precision with the thin layers on the matrix cores (MMTTA_OPT_THIN_MFMA, like their forward / input gradient):
   // the transposed-read kernel below instead of the fp32 vector-ALU kernel
-  if (w.tiny && d->dtype == MMTTA_BF16 && g_thin_mfma && g_wgrad_vec && q_ok(x) && (q_ok(dy) || q_ok16(dy))) w.tiny = false;
-  if (w.tiny) {
+  if (!w.convt && d->cin <= 4 && d->cout <= 4 && d->ksize == 3 && d->stride == 1 && al16(x) && al16(dy) &&
+      !(bf16 && g_thin_mfma && g_wgrad_vec && q_ok(x) && (q_ok(dy) || q_ok16(dy)))) {
+    w.route = W_TINY;
     const long long units = (long long)w.ips * dy->d * ((dy->h + 1) / 2) * ((dy->w + 63) / 64);
-    long long blocks = (units + 3) / 4;
-    if (blocks > 512) blocks = 512;
-    w.tiny_blocks = (int)blocks;
-    w.small = false; w.bf16 = false; w.small_is_cd = 0; w.q = w.pb = nullptr; w.q_is_x = false;
-    w.TZ = w.TY = w.TX = 0; w.tz = w.ty = w.tx = w.tiles = w.S = w.tps = w.nsl = 0; w.CGp = w.CDp = 0;
-    w.slab_floats = (int64_t)blocks * (27 * d->cin * d->cout);
-    w.db_floats = (int64_t)blocks * 4;
-    w.pre_floats = 0; w.pre_chunks = 0; w.colsum_blocks = 0;
+    w.tiny_blocks = (int)std::min((units + 3) / 4, 512LL);
+    w.slab_floats = (int64_t)w.tiny_blocks * (27 * d->cin * d->cout);
+    plan_bias(w, WB_TINY_PARTIALS, dy);
     return MMTTA_OK;
   }
   // small-channel path: which tensor is the small gathered one (Q) and which the dense one (P)
-  w.small = false; w.bf16 = false; w.small_is_cd = 0; w.q = w.pb = nullptr; w.q_is_x = false;
-  if (!w.convt && d->cin <= 4) { w.small = true; w.q = x; w.pb = dy; w.q_is_x = true; }
+  if (!w.convt && d->cin <= 4) { w.q = x; w.pb = dy; w.q_is_x = true; }
   else if (!w.convt && d->cout <= 4 && d->ksize == 1 &&
-           !(d->dtype == MMTTA_BF16 && d->cin >= 16 && wtr_ok(x) && wtr_ok(dy) && (!is_bf16(dy) || is_bf16(x)) && g_wgrad_vec)) {
+           !(bf16 && d->cin >= 16 && wtr_ok(x) && wtr_ok(dy) && (!is_bf16(dy) || is_bf16(x)) && g_wgrad_vec)) {
     // (in bf16 precision the 1x1x1 streaming kernel below takes these heads too: N padded to 32 costs nothing there)
-    w.small = true; w.q = dy; w.pb = x; w.small_is_cd = 1;
+    w.q = dy; w.pb = x; w.small_is_cd = 1;
   }
-  else if (w.convt && d->cout <= 4) { w.small = true; w.q = dy; w.pb = x; }
-  if (w.small) {
+  else if (w.convt && d->cout <= 4) { w.q = dy; w.pb = x; }
+  if (w.q != nullptr) {
     w.CGp = 128;
     w.CDp = roundup(w.pb->c, 32);
     // bf16 precision, 27 taps: the transposed-read kernel when the operands admit its staging (Q: fp32 voxels of 16 bytes;
     // P: 16-byte items of 8 channels; 32-bit element offsets inside a batch item)
     w.p_thin = w.pb->c <= 4 && w.si == 1 && g_thin_mfma;
     // (a bf16-stored thin tensor - the network input of bf16 precision, a thin gradient - has 8-byte voxels: this kernel only)
-    w.thin_tr = d->dtype == MMTTA_BF16 && w.ntaps == 27 && g_wgrad_vec &&
-                (q_ok(w.q) || (q_ok16(w.q) && !w.p_thin)) &&
-                (w.p_thin ? (q_ok(w.pb) || q_ok16(w.pb)) : (wtr_ok(w.pb) && w.pb->c % 8 == 0));
-    if (!w.thin_tr) w.p_thin = false;
-    w.ncb = (w.thin_tr && (w.CDp / 32) % 2 == 0) ? 2 : 1;
-    w.TZ = 4; w.TY = (w.thin_tr && w.si == 1) ? 8 : 4; w.TX = 8;
-    w.tz = (w.pb->d + 3) / 4; w.ty = (w.pb->h + w.TY - 1) / w.TY; w.tx = (w.pb->w + 7) / 8;
+    const bool thin_tr = bf16 && w.ntaps == 27 && g_wgrad_vec &&
+                         (q_ok(w.q) || (q_ok16(w.q) && !w.p_thin)) &&
+                         (w.p_thin ? (q_ok(w.pb) || q_ok16(w.pb)) : (wtr_ok(w.pb) && w.pb->c % 8 == 0));
+    w.route = thin_tr ? W_THIN_TR : W_SMALL;
+    if (!thin_tr) w.p_thin = false;
+    w.ncb = (thin_tr && (w.CDp / 32) % 2 == 0) ? 2 : 1;
+    const int TY = (thin_tr && w.si == 1) ? 8 : 4;
+    w.tz = (w.pb->d + 3) / 4; w.ty = (w.pb->h + TY - 1) / TY; w.tx = (w.pb->w + 7) / 8;
     w.tiles = w.tz * w.ty * w.tx * w.ips;
     // slabs: one volume in flight 256 / 512 / 768 / 1024 -> 56 / 46 / 57 / 57 us per launch at 128^3; two in flight
     // (method.lanes: 2, the default) 256 edges out 512 for the whole step (41.9 vs 41.5 volumes/s): less slab traffic
@@ -2134,37 +2155,25 @@ static int wgeometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtt
     // with workgroups per CU (86 - 172 registers: 3 - 5 per SIMD), so it wants 4x the slabs, down to 8 tiles each
     // (24 volumes in flight, per group of 8, 42 -> 168 slabs per volume: 3 -> 3 at 128^3 475 -> 265 us, 4 -> 32 145 -> 123, the
     // up-convolution 262 -> 239; 336: 238 / 128 / 241; 672 slabs: 249 / 142 / 272)
-    if (w.thin_tr) S = std::min(4 * S, std::max(1, w.tiles / 8));
-    if (S < 1) S = 1;
-    if (S > w.tiles) S = w.tiles;
-    w.tps = (w.tiles + S - 1) / S;
-    w.S = (w.tiles + w.tps - 1) / w.tps;
-    w.nsl = w.S;
-    w.slab_floats = (int64_t)w.nsl * 128 * w.CDp;
-    w.pre_chunks = w.nsl > 32 ? (w.nsl + 31) / 32 : 0;
-    w.pre_floats = (int64_t)w.pre_chunks * 128 * w.CDp;
-    w.colsum_blocks = 0;
-    const bool bias_from_p = (w.pb == dy);           // P carries the output channels
-    if (bias_from_p) w.db_floats = (int64_t)w.nsl * w.CDp;
-    else { w.colsum_blocks = (int64_t)w.ips * channel_partial_rows(dy); w.db_floats = w.colsum_blocks * 2 * dy->c; }
+    if (thin_tr) S = std::min(4 * S, std::max(1, w.tiles / 8));
+    plan_slabs(w, S, (int64_t)128 * w.CDp, 1);
+    plan_bias(w, w.pb == dy ? WB_MAIN_PARTIALS : WB_COLSUMS, dy);        // P carries the output channels, or Q does
     return MMTTA_OK;
   }
   // bf16 operands: the transposed-read kernel, for operand pairs that admit its 16-byte items; anything else (ragged
   // channel slices, MMTTA_OPT_WGRAD_VECTOR_STAGING = 0) computes on the fp32-operand kernel
   // (a gradient may be bf16-stored only next to a bf16-stored module input: x is the gathered operand of a convolution, the
   // dense one of a transposed convolution)
-  const bool grad_bf_ok = !is_bf16(dy) || is_bf16(x);
-  w.tr = d->dtype == MMTTA_BF16 && w.ntaps == 27 && wtr_ok(w.g) && wtr_ok(w.dn) && grad_bf_ok && g_wgrad_vec;
-  w.bf16 = w.tr;
-  w.tr1 = !w.convt && d->dtype == MMTTA_BF16 && w.ntaps == 1 && w.si == 1 && wtr_ok(w.g) && wtr_ok(w.dn) && grad_bf_ok &&
-          g_wgrad_vec;
-  if ((w.tr && w.si == 1) || w.tr1) { w.TZ = 4; w.TY = 8; w.TX = 8; }
-  else if (w.si == 1) { w.TZ = 4; w.TY = 4; w.TX = 8; }
-  else if (w.tr) { w.TZ = 2; w.TY = 4; w.TX = 8; }
-  else { w.TZ = 2; w.TY = 2; w.TX = 8; }
-  w.tz = (w.dn->d + w.TZ - 1) / w.TZ;
-  w.ty = (w.dn->h + w.TY - 1) / w.TY;
-  w.tx = (w.dn->w + w.TX - 1) / w.TX;
+  const bool tr_ok = bf16 && wtr_ok(w.g) && wtr_ok(w.dn) && (!is_bf16(dy) || is_bf16(x)) && g_wgrad_vec;
+  const bool tr = tr_ok && w.ntaps == 27, tr1 = tr_ok && !w.convt && w.ntaps == 1 && w.si == 1;
+  w.route = tr1 ? W_TR_1X1 : tr ? (w.si == 1 ? W_TR_S1 : W_TR_S2) : w.ntaps == 1 ? W_F32_1X1 : w.si == 1 ? W_F32_S1 : W_F32_S2;
+  int TZ = 2, TY = 2;                                                  // tiles are TZ x TY x 8 voxels of the dense operand
+  if ((tr && w.si == 1) || tr1) { TZ = 4; TY = 8; }
+  else if (w.si == 1) { TZ = 4; TY = 4; }
+  else if (tr) { TZ = 2; TY = 4; }
+  w.tz = (w.dn->d + TZ - 1) / TZ;
+  w.ty = (w.dn->h + TY - 1) / TY;
+  w.tx = (w.dn->w + 7) / 8;
   w.tiles = w.tz * w.ty * w.tx * w.ips;
   w.CGp = roundup(w.g->c, 32);
   w.CDp = roundup(w.dn->c, 32);
@@ -2172,7 +2181,7 @@ static int wgeometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtt
   // stride-2 layer, and the stride-1 layers of <= 128 dense channels (per group of 8 volumes: conv 32->64 s2 162 -> 112 us,
   // convT 128->32 307 -> 210, convT 256->64 200 -> 144, 64->128 s2 102 -> 64; 64->64 s1 120 -> 98, 128->128 83 -> 73; the
   // 256- and 512-channel stride-1 layers have hundreds of workgroups and want two of them per CU: 512->512 218 -> 224)
-  if (w.tr && g_wgrad_pair && (w.si == 2 || w.CDp <= 128 || g_wgrad_pair >= 2) && is_bf16(w.g) && is_bf16(w.dn) && (w.CDp / 32) % 2 == 0)
+  if (tr && g_wgrad_pair && (w.si == 2 || w.CDp <= 128 || g_wgrad_pair >= 2) && is_bf16(w.g) && is_bf16(w.dn) && (w.CDp / 32) % 2 == 0)
     w.ncb = 2;
   // (a pair counts as one block: the launch keeps its workgroup count and takes twice the slabs - measured against the same
   // slabs with half the workgroups, three runs each on one box: 96.5 / 96.1 volumes/s, 94.7 without pairs)
@@ -2181,22 +2190,9 @@ static int wgeometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtt
   // time; two in flight (method.lanes: 2, the default) the other lane fills the CUs and halving the slab traffic wins:
   // 512 / 256 / 128 -> 40.1 / 41.5 / 40.6 volumes/s
   int S = g_tune[2] / blocks_cc;
-  if (w.tr1) S = 1024 / blocks_cc;       // a streaming kernel: enough workgroups to keep HBM busy (slabs are 4 KB each)
-  if (S < 1) S = 1;
-  if (S > w.tiles) S = w.tiles;
-  w.tps = (w.tiles + S - 1) / S;
-  w.S = (w.tiles + w.tps - 1) / w.tps;
-  w.nsl = w.S * (w.ntaps == 1 ? 4 : 1);
-  w.slab_floats = (int64_t)w.nsl * w.ntaps * w.CGp * w.CDp;
-  w.pre_chunks = w.nsl > 32 ? (w.nsl + 31) / 32 : 0;
-  w.pre_floats = (int64_t)w.pre_chunks * w.ntaps * w.CGp * w.CDp;
-  w.colsum_blocks = 0;
-  if (w.convt) {
-    w.colsum_blocks = (int64_t)w.ips * channel_partial_rows(dy);
-    w.db_floats = w.colsum_blocks * 2 * dy->c;
-  } else {
-    w.db_floats = (int64_t)w.nsl * w.CDp;
-  }
+  if (tr1) S = 1024 / blocks_cc;         // a streaming kernel: enough workgroups to keep HBM busy (slabs are 4 KB each)
+  plan_slabs(w, S, (int64_t)w.ntaps * w.CGp * w.CDp, w.ntaps == 1 ? 4 : 1);
+  plan_bias(w, w.convt ? WB_COLSUMS : WB_MAIN_PARTIALS, dy);
   return MMTTA_OK;
 }
 
@@ -2218,155 +2214,108 @@ static int launch_wgrad_t(const WArgs& a, int S, hipStream_t s) {
 
 template <int TZ, int TY, int TX, int NTW>
 static int launch_wgrad(const WArgs& a, int S, hipStream_t s) {
-  if (a.g_bf && a.d_bf) return launch_wgrad_t<TZ, TY, TX, NTW, true, true>(a, S, s);
-  if (a.g_bf) return launch_wgrad_t<TZ, TY, TX, NTW, true, false>(a, S, s);
-  if (a.d_bf) return launch_wgrad_t<TZ, TY, TX, NTW, false, true>(a, S, s);
-  return launch_wgrad_t<TZ, TY, TX, NTW, false, false>(a, S, s);
+  static constexpr int (*by_storage[2][2])(const WArgs&, int, hipStream_t) = {      // [g_bf][d_bf]
+      {launch_wgrad_t<TZ, TY, TX, NTW, false, false>, launch_wgrad_t<TZ, TY, TX, NTW, false, true>},
+      {launch_wgrad_t<TZ, TY, TX, NTW, true, false>, launch_wgrad_t<TZ, TY, TX, NTW, true, true>}};
+  return by_storage[a.g_bf][a.d_bf](a, S, s);
 }
 
-// mmtta_conv_wgrad_sets past the checks of its norm-on-load descriptor
-int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                    const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
-                    int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream, const mmtta_update_target* upd) {
-  WGeo w;
-  int st = wgeometry(d, x, dy, sets, w);
-  if (st) return st;
-  const PSets ps = psets(sets);
-  const int Q = w.nsets;                 // the workspace regions below hold Q sets back to back (set-major)
-  UpdArgs ua;
-  if (upd != nullptr) {
-    // the fused update (mmtta_conv_wgrad_update_sets): checked before anything is launched
-    MMTTA_CHECK(!w.tiny && !w.small && w.ntaps == 27, MMTTA_ERR_UNSUPPORTED,
-                "wgrad update: the layer's weight gradient does not end in the 27-tap reduction");
-    MMTTA_CHECK(upd->w_p && upd->w_m && upd->step && upd->image[0] && (upd->optim.kind == MMTTA_OPTIM_SGD || upd->w_v),
-                MMTTA_ERR_INVALID, "wgrad update: null weight, moment, image or step pointer");
-    const bool convt = d->op == MMTTA_CONVT_FWD;
-    MMTTA_CHECK(upd->b_p == nullptr || (!convt && upd->b_m && (upd->optim.kind == MMTTA_OPTIM_SGD || upd->b_v)),
-                MMTTA_ERR_UNSUPPORTED, "wgrad update: the bias is updated here for Conv3d only (ConvTranspose3d: b_grad)");
-    MMTTA_CHECK(upd->optim.kind >= MMTTA_OPTIM_ADAM && upd->optim.kind <= MMTTA_OPTIM_SGD, MMTTA_ERR_INVALID,
-                "wgrad update: optimizer kind %d", upd->optim.kind);
-    const mmtta_optim_desc& o = upd->optim;
-    MMTTA_CHECK(!(o.kind == MMTTA_OPTIM_SGD && o.nesterov && (o.momentum <= 0.f || o.dampening != 0.f)), MMTTA_ERR_INVALID,
-                "wgrad update: nesterov needs momentum > 0 and zero dampening");
-    ua.a = OptimArgs{o.lr, o.beta1, o.beta2, o.eps, o.weight_decay, o.momentum, o.dampening, o.nesterov};
-    ua.wp = upd->w_p; ua.wm = upd->w_m; ua.wv = upd->w_v;
-    ua.bp = upd->b_p; ua.bm = upd->b_m; ua.bv = upd->b_v;
-    ua.step = upd->step; ua.w_decay = upd->w_decay ? 1 : 0; ua.b_decay = upd->b_decay ? 1 : 0;
-    for (int m = 0; m < 2; ++m) {
-      ua.img[m].p = (unsigned short*)upd->image[m];
-      ua.img[m].outer = upd->image_outer[m]; ua.img[m].inner = upd->image_inner[m];
-      ua.img[m].Kp = ua.img[m].Np = ua.img[m].kn_is_ba = 0;
-      if (upd->image[m] == nullptr) continue;
-      mmtta_conv_desc dd = *d;
-      if (m == 1) dd.op = convt ? MMTTA_CONVT_DGRAD : MMTTA_CONV_DGRAD;
-      PackImageGeo g;
-      st = pack_image_geometry(&dd, g);
-      if (st) return st;
-      MMTTA_CHECK(g.plain_bf16 && g.T == 27, MMTTA_ERR_UNSUPPORTED, "wgrad update: image %d is not a 27-tap bf16 image", m);
-      MMTTA_CHECK(g.A == w.dn->c && g.B == w.g->c, MMTTA_ERR_INVALID, "wgrad update: image %d does not match the gradient", m);
-      MMTTA_CHECK(((uintptr_t)upd->image[m]) % 16 == 0 && upd->image_outer[m] % 16 == 0 && upd->image_inner[m] % 16 == 0,
-                  MMTTA_ERR_INVALID, "wgrad update: images must keep 16-byte alignment");
-      ua.img[m].Kp = g.Kp; ua.img[m].Np = g.Np; ua.img[m].kn_is_ba = g.kn_is_ba;
-    }
-    dw = upd->w_p;                       // (not written: the gradient stays in the workspace)
-    db = convt ? upd->b_grad : upd->b_p;
-  }
-  MMTTA_CHECK(dw != nullptr, MMTTA_ERR_INVALID, "wgrad: null dw");
-  const int64_t need = (w.slab_floats + w.db_floats + w.pre_floats) * Q * 4;
-  MMTTA_CHECK(workspace != nullptr && workspace_bytes >= need, MMTTA_ERR_WORKSPACE, "wgrad: workspace %lld bytes, need %lld",
-              (long long)workspace_bytes, (long long)need);
-  hipStream_t s = (hipStream_t)stream;
-  if (w.tiny) {
-    MMTTA_CHECK(is_f32(x) && is_f32(dy), MMTTA_ERR_UNSUPPORTED, "wgrad (tiny layer): fp32-stored tensors only");
-    WTArgs t;
-    t.x = tv(x); t.tx = nl(x_norm); t.dy = tv(dy);
-    t.part = (float*)workspace; t.ld = 27 * d->cin * d->cout;
-    t.dbpart = db != nullptr ? (float*)workspace + w.slab_floats * Q : nullptr;
-    t.B = w.tiny_blocks; t.ips = w.ips; t.BT = w.tiny_blocks * Q;
-    if (t.tx.mean != nullptr || t.tx.scale != nullptr) launch_tiny<true>(t, d->cin, d->cout, w.tiny_blocks * Q, s);
-    else launch_tiny<false>(t, d->cin, d->cout, w.tiny_blocks * Q, s);
-    st = launch_status("wgrad tiny");
-    if (st || g_profile_main_only) return st;
-    hipLaunchKernelGGL(db_reduce_kernel, dim3(t.ld, Q), dim3(64), 0, s, t.part, dw, w.tiny_blocks, t.ld, t.ld, accumulate, ps, 1);
-    if (db != nullptr)
-      hipLaunchKernelGGL(db_reduce_kernel, dim3(d->cout, Q), dim3(64), 0, s, t.dbpart, db, w.tiny_blocks, d->cout, 4, accumulate, ps, 0);
-    return launch_status("wgrad tiny reduce");
-  }
-  if (w.small) {
-    W2Args b;
-    b.q = (const float*)w.q->ptr; b.qsn = w.q->sn; b.qsd = w.q->sd; b.qsh = w.q->sh; b.qsw = w.q->sw;
-    b.Cs = w.q->c; b.Dq = w.q->d; b.Hq = w.q->h; b.Wq = w.q->w;
-    b.p = (const float*)w.pb->ptr; b.psn = w.pb->sn; b.psd = w.pb->sd; b.psh = w.pb->sh; b.psw = w.pb->sw;
-    b.Cb = w.pb->c; b.Dp = w.pb->d; b.Hp = w.pb->h; b.Wp = w.pb->w;
-    b.tq = w.q_is_x ? nl(x_norm) : nl(nullptr);
-    b.tp = w.q_is_x ? nl(nullptr) : nl(x_norm);
-    b.si = w.si; b.ntaps = w.ntaps;
-    b.slab = (float*)workspace;
-    float* dbws2 = (float*)workspace + w.slab_floats * Q;
-    const bool bias_from_p = (w.pb == dy);
-    b.dbpart = (db != nullptr && bias_from_p) ? dbws2 : nullptr;
-    b.tz = w.tz; b.ty = w.ty; b.tx = w.tx; b.tiles = w.tiles * Q; b.tiles_per_split = w.tps; b.CBp = w.CDp;
-    b.S = w.S; b.tiles_set = w.tiles;
-    auto al4 = [](const mmtta_tensor* t) {
-      return ((((uintptr_t)t->ptr) % 16 == 0) && t->sw % 4 == 0 && t->sh % 4 == 0 && t->sd % 4 == 0 && t->sn % 4 == 0) ? 1 : 0;
-    };
-    b.qvec4 = al4(w.q); b.pvec4 = al4(w.pb);
-    MMTTA_CHECK(is_f32(w.q) || w.thin_tr, MMTTA_ERR_UNSUPPORTED, "wgrad (thin layer): the <= 4-channel tensor must be fp32-stored");
-    b.p_bf = is_bf16(w.pb) ? 1 : 0;
-    if (b.p_bf) b.pvec4 = (((uintptr_t)w.pb->ptr) % 8 == 0 && w.pb->sw % 4 == 0 && w.pb->sh % 4 == 0 && w.pb->sd % 4 == 0 && w.pb->sn % 4 == 0) ? 1 : 0;
-    b.bf = (d->dtype == MMTTA_BF16 && w.ntaps == 27) ? 1 : 0;
-    b.p_thin = w.p_thin ? 1 : 0;
-    b.q_bf = is_bf16(w.q) ? 1 : 0;
-    MMTTA_CHECK(!b.q_bf || w.thin_tr, MMTTA_ERR_UNSUPPORTED, "wgrad (thin layer): a bf16-stored <= 4-channel tensor needs the transposed-read kernel");
-    const int ext = w.ntaps == 1 ? 0 : 2;
-    const int BZ = 3 * w.si + ext + 1, BY = 3 * w.si + ext + 1, BX = 7 * w.si + ext + 1;
-    const size_t lds = ((size_t)BZ * BY * BX * 4 + 128 * 32) * sizeof(float);
-    MMTTA_CHECK((w.ntaps == 27 && (w.si == 1 || w.si == 2)) || (w.ntaps == 1 && w.si == 1), MMTTA_ERR_UNSUPPORTED,
-                "wgrad (thin layer): %d taps with stride %d", w.ntaps, w.si);
-    const dim3 sg(w.S * Q, w.CDp / 32);
-    if (w.thin_tr) {
-      launch_thin_tr(b, w.si, w.ncb, dim3(w.S * Q, w.CDp / 32 / w.ncb), s);
-    } else if (w.ntaps == 1) {
-      if (b.p_bf) hipLaunchKernelGGL((wgrad_small_kernel<true, 1, false>), sg, dim3(256), lds, s, b);
-      else hipLaunchKernelGGL((wgrad_small_kernel<false, 1, false>), sg, dim3(256), lds, s, b);
-    } else if (w.si == 1) {
-      if (b.p_bf) hipLaunchKernelGGL((wgrad_small_kernel<true, 1, true>), sg, dim3(256), lds, s, b);
-      else hipLaunchKernelGGL((wgrad_small_kernel<false, 1, true>), sg, dim3(256), lds, s, b);
-    } else {
-      if (b.p_bf) hipLaunchKernelGGL((wgrad_small_kernel<true, 2, true>), sg, dim3(256), lds, s, b);
-      else hipLaunchKernelGGL((wgrad_small_kernel<false, 2, true>), sg, dim3(256), lds, s, b);
-    }
-    st = launch_status("wgrad small");
-    if (st || g_profile_main_only) return st;
-    const int total = w.ntaps * b.Cs * b.Cb;
-    const float* rsrc = b.slab;
-    int rn = w.nsl;
-    if (w.pre_chunks > 0) {
-      float* pre = (float*)workspace + (w.slab_floats + w.db_floats) * Q;
-      const long long elems = (long long)128 * w.CDp;
-      hipLaunchKernelGGL(slab_prereduce_kernel, dim3((unsigned)((elems + 255) / 256), w.pre_chunks, Q), dim3(256), 0, s, b.slab,
-                         pre, w.nsl, elems);
-      st = launch_status("wgrad small prereduce");
-      if (st) return st;
-      rsrc = pre; rn = w.pre_chunks;
-    }
-    hipLaunchKernelGGL(wgrad_small_reduce_kernel, dim3((total + 255) / 256, Q), dim3(256), 0, s, rsrc, dw, rn, w.ntaps, b.Cs,
-                       b.Cb, w.CDp, w.small_is_cd, accumulate, ps);
-    st = launch_status("wgrad small reduce");
+// The fused update (mmtta_conv_wgrad_update_sets): validates the target and fills the kernel's arguments before anything
+// is launched
+static int check_update_target(const mmtta_conv_desc* d, const WGeo& w, const mmtta_update_target* upd, UpdArgs& ua) {
+  MMTTA_CHECK(route_reduce27(w.route), MMTTA_ERR_UNSUPPORTED,
+              "wgrad update: the layer's weight gradient does not end in the 27-tap reduction");
+  MMTTA_CHECK(upd->w_p && upd->w_m && upd->step && upd->image[0] && (upd->optim.kind == MMTTA_OPTIM_SGD || upd->w_v),
+              MMTTA_ERR_INVALID, "wgrad update: null weight, moment, image or step pointer");
+  MMTTA_CHECK(upd->b_p == nullptr || (!w.convt && upd->b_m && (upd->optim.kind == MMTTA_OPTIM_SGD || upd->b_v)),
+              MMTTA_ERR_UNSUPPORTED, "wgrad update: the bias is updated here for Conv3d only (ConvTranspose3d: b_grad)");
+  MMTTA_CHECK(upd->optim.kind >= MMTTA_OPTIM_ADAM && upd->optim.kind <= MMTTA_OPTIM_SGD, MMTTA_ERR_INVALID,
+              "wgrad update: optimizer kind %d", upd->optim.kind);
+  const mmtta_optim_desc& o = upd->optim;
+  MMTTA_CHECK(!(o.kind == MMTTA_OPTIM_SGD && o.nesterov && (o.momentum <= 0.f || o.dampening != 0.f)), MMTTA_ERR_INVALID,
+              "wgrad update: nesterov needs momentum > 0 and zero dampening");
+  ua.a = OptimArgs{o.lr, o.beta1, o.beta2, o.eps, o.weight_decay, o.momentum, o.dampening, o.nesterov};
+  ua.wp = upd->w_p; ua.wm = upd->w_m; ua.wv = upd->w_v;
+  ua.bp = upd->b_p; ua.bm = upd->b_m; ua.bv = upd->b_v;
+  ua.step = upd->step; ua.w_decay = upd->w_decay ? 1 : 0; ua.b_decay = upd->b_decay ? 1 : 0;
+  for (int m = 0; m < 2; ++m) {
+    ua.img[m].p = (unsigned short*)upd->image[m];
+    ua.img[m].outer = upd->image_outer[m]; ua.img[m].inner = upd->image_inner[m];
+    ua.img[m].Kp = ua.img[m].Np = ua.img[m].kn_is_ba = 0;
+    if (upd->image[m] == nullptr) continue;
+    mmtta_conv_desc dd = *d;
+    if (m == 1) dd.op = w.convt ? MMTTA_CONVT_DGRAD : MMTTA_CONV_DGRAD;
+    PackImageGeo g;
+    const int st = pack_image_geometry(&dd, g);
     if (st) return st;
-    if (db != nullptr) {
-      if (bias_from_p) {
-        hipLaunchKernelGGL(db_reduce_kernel, dim3(b.Cb, Q), dim3(64), 0, s, dbws2, db, w.nsl, b.Cb, w.CDp, accumulate, ps, 0);
-      } else {
-        st = launch_channel_sums(dy, dbws2, s);          // rows are n-major: a set's rows are contiguous
-        if (st) return st;
-        hipLaunchKernelGGL(db_reduce_kernel, dim3(dy->c, Q), dim3(64), 0, s, dbws2, db, (int)w.colsum_blocks, dy->c, 2 * dy->c,
-                           accumulate, ps, 0);
-      }
-      st = launch_status("bias reduce");
-    }
-    return st;
+    MMTTA_CHECK(g.plain_bf16 && g.T == 27, MMTTA_ERR_UNSUPPORTED, "wgrad update: image %d is not a 27-tap bf16 image", m);
+    MMTTA_CHECK(g.A == w.dn->c && g.B == w.g->c, MMTTA_ERR_INVALID, "wgrad update: image %d does not match the gradient", m);
+    MMTTA_CHECK(((uintptr_t)upd->image[m]) % 16 == 0 && upd->image_outer[m] % 16 == 0 && upd->image_inner[m] % 16 == 0,
+                MMTTA_ERR_INVALID, "wgrad update: images must keep 16-byte alignment");
+    ua.img[m].Kp = g.Kp; ua.img[m].Np = g.Np; ua.img[m].kn_is_ba = g.kn_is_ba;
   }
+  return MMTTA_OK;
+}
+
+// ---- the main kernel of each family.  Workspace of a launch, Q = w.nsets sets back to back (set-major) in each region:
+// slabs [Q][slab_floats], bias rows [Q][db_floats], pre-reduced slabs [Q][pre_floats]; `dbws` is the second region, or
+// null when the main kernel has no bias rows to write
+static int launch_tiny_family(const mmtta_conv_desc* d, const WGeo& w, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                              const mmtta_tensor* dy, float* ws, float* dbws, hipStream_t s) {
+  MMTTA_CHECK(is_f32(x) && is_f32(dy), MMTTA_ERR_UNSUPPORTED, "wgrad (tiny layer): fp32-stored tensors only");
+  WTArgs t;
+  t.x = tv(x); t.tx = nl(x_norm); t.dy = tv(dy);
+  t.part = ws; t.ld = 27 * d->cin * d->cout;
+  t.dbpart = dbws;
+  t.B = w.tiny_blocks; t.ips = w.ips; t.BT = w.tiny_blocks * w.nsets;
+  if (t.tx.mean != nullptr || t.tx.scale != nullptr) launch_tiny<true>(t, d->cin, d->cout, t.BT, s);
+  else launch_tiny<false>(t, d->cin, d->cout, t.BT, s);
+  return launch_status("wgrad tiny");
+}
+
+static int launch_thin_family(const mmtta_conv_desc* d, const WGeo& w, const mmtta_norm_on_load* x_norm, float* ws, float* dbws,
+                              hipStream_t s) {
+  const int Q = w.nsets;
+  const bool thin_tr = w.route == W_THIN_TR;
+  W2Args b;
+  b.q = (const float*)w.q->ptr; b.qsn = w.q->sn; b.qsd = w.q->sd; b.qsh = w.q->sh; b.qsw = w.q->sw;
+  b.Cs = w.q->c; b.Dq = w.q->d; b.Hq = w.q->h; b.Wq = w.q->w;
+  b.p = (const float*)w.pb->ptr; b.psn = w.pb->sn; b.psd = w.pb->sd; b.psh = w.pb->sh; b.psw = w.pb->sw;
+  b.Cb = w.pb->c; b.Dp = w.pb->d; b.Hp = w.pb->h; b.Wp = w.pb->w;
+  b.tq = w.q_is_x ? nl(x_norm) : nl(nullptr);
+  b.tp = w.q_is_x ? nl(nullptr) : nl(x_norm);
+  b.si = w.si; b.ntaps = w.ntaps;
+  b.slab = ws;
+  b.dbpart = dbws;
+  b.tz = w.tz; b.ty = w.ty; b.tx = w.tx; b.tiles = w.tiles * Q; b.tiles_per_split = w.tps; b.CBp = w.CDp;
+  b.S = w.S; b.tiles_set = w.tiles;
+  b.qvec4 = quad_aligned(w.q, 16) ? 1 : 0;
+  b.pvec4 = quad_aligned(w.pb, quad_bytes(w.pb)) ? 1 : 0;
+  MMTTA_CHECK(is_f32(w.q) || thin_tr, MMTTA_ERR_UNSUPPORTED, "wgrad (thin layer): the <= 4-channel tensor must be fp32-stored");
+  b.p_bf = is_bf16(w.pb) ? 1 : 0;
+  b.bf = (d->dtype == MMTTA_BF16 && w.ntaps == 27) ? 1 : 0;
+  b.p_thin = w.p_thin ? 1 : 0;
+  b.q_bf = is_bf16(w.q) ? 1 : 0;
+  MMTTA_CHECK(!b.q_bf || thin_tr, MMTTA_ERR_UNSUPPORTED, "wgrad (thin layer): a bf16-stored <= 4-channel tensor needs the transposed-read kernel");
+  const int ext = w.ntaps == 1 ? 0 : 2;
+  const int BZ = 3 * w.si + ext + 1, BY = 3 * w.si + ext + 1, BX = 7 * w.si + ext + 1;
+  const size_t lds = ((size_t)BZ * BY * BX * 4 + 128 * 32) * sizeof(float);
+  MMTTA_CHECK((w.ntaps == 27 && (w.si == 1 || w.si == 2)) || (w.ntaps == 1 && w.si == 1), MMTTA_ERR_UNSUPPORTED,
+              "wgrad (thin layer): %d taps with stride %d", w.ntaps, w.si);
+  if (thin_tr) {
+    launch_thin_tr(b, w.si, w.ncb, dim3(w.S * Q, w.CDp / 32 / w.ncb), s);
+  } else {
+    static constexpr decltype(&wgrad_small_kernel<false, 1, false>) forms[2][3] = {      // [p_bf][1 tap | 27 taps s1 | 27 taps s2]
+        {wgrad_small_kernel<false, 1, false>, wgrad_small_kernel<false, 1, true>, wgrad_small_kernel<false, 2, true>},
+        {wgrad_small_kernel<true, 1, false>, wgrad_small_kernel<true, 1, true>, wgrad_small_kernel<true, 2, true>}};
+    const auto kern = forms[b.p_bf][w.ntaps == 1 ? 0 : w.si];
+    hipLaunchKernelGGL(kern, dim3(w.S * Q, w.CDp / 32), dim3(256), lds, s, b);
+  }
+  return launch_status("wgrad small");
+}
+
+static int launch_main_family(const WGeo& w, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, float* ws, float* dbws,
+                              hipStream_t s) {
   WArgs a;
   a.g = (const float*)w.g->ptr; a.gsn = w.g->sn; a.gsd = w.g->sd; a.gsh = w.g->sh; a.gsw = w.g->sw;
   a.Cg = w.g->c; a.Dgg = w.g->d; a.Hgg = w.g->h; a.Wgg = w.g->w;
@@ -2377,68 +2326,119 @@ int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   a.td = w.convt ? nl(x_norm) : nl(nullptr);
   a.N = x->n;
   a.si = w.si; a.ntaps = w.ntaps;
-  a.slab = (float*)workspace;
-  float* dbws = (float*)workspace + w.slab_floats * Q;
-  a.dbpart = (db != nullptr && !w.convt) ? dbws : nullptr;
-  a.tz = w.tz; a.ty = w.ty; a.tx = w.tx; a.tiles = w.tiles * Q; a.tiles_per_split = w.tps;
+  a.slab = ws;
+  a.dbpart = dbws;
+  a.tz = w.tz; a.ty = w.ty; a.tx = w.tx; a.tiles = w.tiles * w.nsets; a.tiles_per_split = w.tps;
   a.S = w.S; a.tiles_set = w.tiles;
   a.CGp = w.CGp; a.CDp = w.CDp;
   a.g_bf = is_bf16(w.g) ? 1 : 0;
   a.d_bf = is_bf16(w.dn) ? 1 : 0;
   a.convt = w.convt ? 1 : 0;
-  a.gvec4 = wvec_ok(w.g) ? 1 : 0;
-  a.dvec4 = wvec_ok(w.dn) ? 1 : 0;
-  const int SQ = w.S * Q;                // slabs of the launch
-  if (w.tr1) st = launch_wgrad_tr1(a, SQ, s);
-  else if (w.tr) st = (w.si == 1) ? launch_wgrad_tr<4, 8, 1>(a, SQ, s, w.ncb) : launch_wgrad_tr<2, 4, 2>(a, SQ, s, w.ncb);
-  else if (w.ntaps == 1) st = launch_wgrad<4, 4, 8, 1>(a, SQ, s);
-  else st = (w.si == 1) ? launch_wgrad<4, 4, 8, 7>(a, SQ, s) : launch_wgrad<2, 2, 8, 7>(a, SQ, s);
-  if (st || (g_profile_main_only && upd == nullptr)) return st;
-  const float* rsrc = a.slab;
-  int rn = w.nsl;
+  a.gvec4 = quad_aligned(w.g, quad_bytes(w.g)) ? 1 : 0;
+  a.dvec4 = quad_aligned(w.dn, quad_bytes(w.dn)) ? 1 : 0;
+  const int SQ = w.S * w.nsets;          // slabs of the launch
+  switch (w.route) {
+    case W_TR_1X1: return launch_wgrad_tr1(a, SQ, s);
+    case W_TR_S1: return launch_wgrad_tr<4, 8, 1>(a, SQ, s, w.ncb);
+    case W_TR_S2: return launch_wgrad_tr<2, 4, 2>(a, SQ, s, w.ncb);
+    case W_F32_1X1: return launch_wgrad<4, 4, 8, 1>(a, SQ, s);
+    case W_F32_S1: return launch_wgrad<4, 4, 8, 7>(a, SQ, s);
+    default: return launch_wgrad<2, 2, 8, 7>(a, SQ, s);
+  }
+}
+
+// Everything behind the main kernel: slabs -> (pre-reduce past 32 slabs) -> the route's reduce kernel -> bias gradient.
+// With `upd` the 27-tap reduce is the fused update (optimizer step and both bf16 images in the same pass).
+static int reduce_tail(const WGeo& w, const mmtta_tensor* dy, float* ws, float* dw, float* db, int accumulate,
+                       const mmtta_param_sets* sets, const mmtta_update_target* upd, const UpdArgs& ua, hipStream_t s) {
+  const PSets ps = psets(sets);
+  const int Q = w.nsets;
+  const bool tiny = w.route == W_TINY, thin = route_thin(w.route);
+  float* dbws = ws + w.slab_floats * Q;
+  const float* rsrc = ws;
+  int rn = w.nsl, st;
   if (w.pre_chunks > 0) {
-    float* pre = (float*)workspace + (w.slab_floats + w.db_floats) * Q;
-    const long long elems = (long long)w.ntaps * w.CGp * w.CDp;
-    hipLaunchKernelGGL(slab_prereduce_kernel, dim3((unsigned)((elems + 255) / 256), w.pre_chunks, Q), dim3(256), 0, s, a.slab, pre,
+    float* pre = ws + (w.slab_floats + w.db_floats) * Q;
+    const long long elems = w.slab_elems;
+    hipLaunchKernelGGL(slab_prereduce_kernel, dim3((unsigned)((elems + 255) / 256), w.pre_chunks, Q), dim3(256), 0, s, ws, pre,
                        w.nsl, elems);
-    st = launch_status("wgrad prereduce");
+    st = launch_status(thin ? "wgrad small prereduce" : "wgrad prereduce");
     if (st) return st;
     rsrc = pre; rn = w.pre_chunks;
   }
-  const bool db_here = db != nullptr && !w.convt;      // bias partials written by the main kernel: [nsl][CDp]
-  if (upd != nullptr) {
-    const dim3 grid((a.Cg + UPD_CG - 1) / UPD_CG + (db_here ? 1 : 0), (a.Cd + UPD_CD - 1) / UPD_CD, Q);
-    if (upd->optim.kind == MMTTA_OPTIM_ADAM)
-      hipLaunchKernelGGL(wgrad_update27_kernel<0>, grid, dim3(256), 0, s, rsrc, rn, a.Cg, a.Cd, w.CGp, w.CDp, dbws, w.nsl, ps, ua);
-    else if (upd->optim.kind == MMTTA_OPTIM_ADAMW)
-      hipLaunchKernelGGL(wgrad_update27_kernel<1>, grid, dim3(256), 0, s, rsrc, rn, a.Cg, a.Cd, w.CGp, w.CDp, dbws, w.nsl, ps, ua);
-    else
-      hipLaunchKernelGGL(wgrad_update27_kernel<2>, grid, dim3(256), 0, s, rsrc, rn, a.Cg, a.Cd, w.CGp, w.CDp, dbws, w.nsl, ps, ua);
-    st = launch_status("wgrad update");
-    if (st) return st;
-    if (db != nullptr && !w.convt) db = nullptr;       // the bias rows rode in the launch above
-  } else if (w.ntaps == 27)
-    hipLaunchKernelGGL(wgrad_reduce27_kernel, dim3(a.Cg + (db_here ? 1 : 0), (a.Cd + 31) / 32, Q), dim3(256), 0, s, rsrc, dw, rn,
-                       a.Cg, a.Cd, w.CGp, w.CDp, accumulate, dbws, db_here ? db : nullptr, w.nsl, ps);
-  else
-    hipLaunchKernelGGL(wgrad_reduce1_kernel, dim3((a.Cg + 31) / 32, (a.Cd + 31) / 32, Q), dim3(256), 0, s, rsrc, dw, rn,
-                       a.Cg, a.Cd, w.CGp, w.CDp, accumulate, ps);
-  st = launch_status("wgrad reduce");
-  if (st) return st;
-  if (db != nullptr) {
-    if (!w.convt) {
-      if (w.ntaps != 27)
-        hipLaunchKernelGGL(db_reduce_kernel, dim3(a.Cd, Q), dim3(64), 0, s, dbws, db, w.nsl, a.Cd, w.CDp, accumulate, ps, 0);
-    } else {
-      // ConvTranspose3d bias gradient = per-channel sum of dy over the fine grid
-      st = launch_channel_sums(dy, dbws, s);
-      if (st) return st;
-      hipLaunchKernelGGL(db_reduce_kernel, dim3(dy->c, Q), dim3(64), 0, s, dbws, db, (int)w.colsum_blocks, dy->c,
-                         2 * dy->c, accumulate, ps, 0);
+  // bias partials written by the main kernel, [nsl][CDp]: the 27-tap reduce kernels sum them in an extra block column
+  const bool db_rides = db != nullptr && w.bias == WB_MAIN_PARTIALS && route_reduce27(w.route);
+  const int Cg = thin ? w.q->c : w.g->c, Cd = thin ? w.pb->c : w.dn->c;
+  switch (w.route) {
+    case W_TINY: {
+      const int ld = 27 * Cg * Cd;                                // block partials in dw's own layout [cb][cs][27]
+      hipLaunchKernelGGL(db_reduce_kernel, dim3(ld, Q), dim3(64), 0, s, rsrc, dw, w.tiny_blocks, ld, ld, accumulate, ps, 1);
+      break;
     }
-    st = launch_status("bias reduce");
+    case W_SMALL:
+    case W_THIN_TR:
+      hipLaunchKernelGGL(wgrad_small_reduce_kernel, dim3((w.ntaps * Cg * Cd + 255) / 256, Q), dim3(256), 0, s, rsrc, dw, rn, w.ntaps,
+                         Cg, Cd, w.CDp, w.small_is_cd, accumulate, ps);
+      break;
+    case W_F32_1X1:
+    case W_TR_1X1:
+      hipLaunchKernelGGL(wgrad_reduce1_kernel, dim3((Cg + 31) / 32, (Cd + 31) / 32, Q), dim3(256), 0, s, rsrc, dw, rn,
+                         Cg, Cd, w.CGp, w.CDp, accumulate, ps);
+      break;
+    default:                  // the 27-tap routes (route_reduce27)
+      if (upd != nullptr) {
+        static constexpr decltype(&wgrad_update27_kernel<0>) kinds[3] = {      // KIND = mmtta_optim_desc.kind (checked)
+            wgrad_update27_kernel<MMTTA_OPTIM_ADAM>, wgrad_update27_kernel<MMTTA_OPTIM_ADAMW>, wgrad_update27_kernel<MMTTA_OPTIM_SGD>};
+        const auto kern = kinds[upd->optim.kind];
+        hipLaunchKernelGGL(kern, dim3((Cg + UPD_CG - 1) / UPD_CG + (db_rides ? 1 : 0), (Cd + UPD_CD - 1) / UPD_CD, Q),
+                           dim3(256), 0, s, rsrc, rn, Cg, Cd, w.CGp, w.CDp, dbws, w.nsl, ps, ua);
+      } else {
+        hipLaunchKernelGGL(wgrad_reduce27_kernel, dim3(Cg + (db_rides ? 1 : 0), (Cd + 31) / 32, Q), dim3(256), 0, s, rsrc, dw, rn,
+                           Cg, Cd, w.CGp, w.CDp, accumulate, dbws, db_rides ? db : nullptr, w.nsl, ps);
+      }
   }
-  return st;
+  st = launch_status(tiny ? "wgrad tiny reduce" : thin ? "wgrad small reduce" : upd != nullptr ? "wgrad update" : "wgrad reduce");
+  if (st || db == nullptr || db_rides) return st;
+  int rows = w.nsl, ld = w.CDp;
+  if (w.bias == WB_TINY_PARTIALS) { rows = w.tiny_blocks; ld = 4; }
+  if (w.bias == WB_COLSUMS) {
+    // the gathered operand is dy: bias gradient = per-channel sum of dy (rows are n-major: a set's rows are contiguous)
+    st = launch_channel_sums(dy, dbws, s);
+    if (st) return st;
+    rows = (int)w.colsum_blocks; ld = 2 * dy->c;
+  }
+  hipLaunchKernelGGL(db_reduce_kernel, dim3(dy->c, Q), dim3(64), 0, s, dbws, db, rows, dy->c, ld, accumulate, ps, 0);
+  return launch_status(tiny ? "wgrad tiny reduce" : "bias reduce");
+}
+
+// mmtta_conv_wgrad_sets past the checks of its norm-on-load descriptor
+int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                    const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
+                    int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream, const mmtta_update_target* upd) {
+  WGeo w{};
+  int st = wgeometry(d, x, dy, sets, w);
+  if (st) return st;
+  UpdArgs ua;
+  if (upd != nullptr) {
+    st = check_update_target(d, w, upd, ua);
+    if (st) return st;
+    dw = upd->w_p;                       // (not written: the gradient stays in the workspace)
+    db = w.convt ? upd->b_grad : upd->b_p;
+  }
+  MMTTA_CHECK(dw != nullptr, MMTTA_ERR_INVALID, "wgrad: null dw");
+  const int64_t need = (w.slab_floats + w.db_floats + w.pre_floats) * w.nsets * 4;
+  MMTTA_CHECK(workspace != nullptr && workspace_bytes >= need, MMTTA_ERR_WORKSPACE, "wgrad: workspace %lld bytes, need %lld",
+              (long long)workspace_bytes, (long long)need);
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = (float*)workspace;
+  // the main kernel writes bias rows only when they are wanted and are its to write
+  float* dbws = (db != nullptr && w.bias != WB_COLSUMS) ? ws + w.slab_floats * w.nsets : nullptr;
+  if (w.route == W_TINY) st = launch_tiny_family(d, w, x, x_norm, dy, ws, dbws, s);
+  else if (route_thin(w.route)) st = launch_thin_family(d, w, x_norm, ws, dbws, s);
+  else st = launch_main_family(w, x, x_norm, ws, dbws, s);
+  // MMTTA_OPT_PROFILE_MAIN_KERNEL_ONLY stops here; a fused-update call still runs its update
+  if (st || (g_profile_main_only && upd == nullptr)) return st;
+  return reduce_tail(w, dy, ws, dw, db, accumulate, sets, upd, ua, s);
 }
 
 MMTTA_ACT_NS_CLOSE
@@ -2449,7 +2449,7 @@ using namespace mmtta;
 
 extern "C" int64_t mmtta_conv_wgrad_workspace_bytes_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy,
                                                          const mmtta_param_sets* sets) {
-  WGeo w;
+  WGeo w{};
   if (wgeometry(d, x, dy, sets, w)) return -1;
   return (w.slab_floats + w.db_floats + w.pre_floats) * w.nsets * (int64_t)sizeof(float);
 }
@@ -2462,7 +2462,7 @@ extern "C" int64_t mmtta_conv_wgrad_workspace_bytes(const mmtta_conv_desc* d, co
 extern "C" int mmtta_conv_wgrad_plan_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy,
                                           const mmtta_param_sets* sets, int32_t plan[4]) {
   MMTTA_CHECK(plan != nullptr, MMTTA_ERR_INVALID, "wgrad plan: null output");
-  WGeo w;
+  WGeo w{};
   const int st = wgeometry(d, x, dy, sets, w);
   if (st) return st;
   plan[0] = w.nsl; plan[1] = w.pre_chunks; plan[2] = w.CGp; plan[3] = w.CDp;
@@ -2470,15 +2470,10 @@ extern "C" int mmtta_conv_wgrad_plan_sets(const mmtta_conv_desc* d, const mmtta_
 }
 
 extern "C" int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy) {
-  WGeo w;
+  WGeo w{};
   const int st = wgeometry(d, x, dy, nullptr, w);
   if (st) return st < 0 ? st : -st;
-  if (w.tiny) return 6;
-  if (w.small) return w.thin_tr ? 10 : 3;
-  if (w.tr1) return 9;
-  if (w.tr) return w.si == 1 ? 7 : 8;
-  if (w.ntaps == 1) return 2;
-  return w.si == 1 ? 0 : 1;
+  return w.route;
 }
 
 extern "C" int mmtta_conv_wgrad(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
@@ -2500,9 +2495,6 @@ extern "C" int mmtta_conv_wgrad_sets(const mmtta_conv_desc* d, const mmtta_tenso
     return leaky::conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
   return conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
 }
-
-// (A/B switch: MMTTA_FUSED_UPDATE=0 turns the fused weight update off; the host then takes the separate passes)
-static const int g_fused_update = getenv("MMTTA_FUSED_UPDATE") ? atoi(getenv("MMTTA_FUSED_UPDATE")) : 1;
 
 extern "C" int mmtta_fused_update_enabled(void) { return g_fused_update != 0 ? 1 : 0; }
 

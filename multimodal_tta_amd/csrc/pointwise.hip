@@ -845,9 +845,7 @@ static inline int grid_for(long long total, int cap = 8192) {
 // 16-byte access to 4 channels at a time.  C need not be a multiple of 4 when the voxel row is padded to one
 // (sw >= roundup(C,4)): READING the pad lanes is always harmless; WRITING them needs a view that owns its pad.
 static inline bool vec4_rd(const mmtta_tensor* t) {
-  return ((uintptr_t)t->ptr) % (t->dtype == MMTTA_BF16 ? 8 : 16) == 0 && t->sw % 4 == 0 && t->sh % 4 == 0 && t->sd % 4 == 0 &&
-         t->sn % 4 == 0 && t->sc == 1 &&
-         (t->c % 4 == 0 || t->sw >= (t->c + 3) / 4 * 4);
+  return quad_aligned(t, quad_bytes(t)) && t->sc == 1 && (t->c % 4 == 0 || t->sw >= (t->c + 3) / 4 * 4);
 }
 static inline bool vec4_wr(const mmtta_tensor* t) {
   return vec4_rd(t) && (t->c % 4 == 0 || (t->flags & MMTTA_TENSOR_OWNS_PAD));

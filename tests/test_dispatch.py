@@ -5,9 +5,10 @@ parity cases (tests/test_hip_conv.py::CASES / BF16_CASES) - asserted through the
 config ids: csrc/conv_igemm.hip::config_id (0-5 fp32 igemm, 6 direct, 7-12 bf16 igemm, 13 channel kernel, 14 the lean 4x8x8 tile
 of the 32-output-channel bf16 layers: the default, id 7 = the 8x8x8 tile under MMTTA_OPT_IGEMM_LEAN = 0, parity case
 test_lean_tile_matches_the_wide_tile; 15 class-fused);
-weight-gradient ids: mmtta_conv_wgrad_kernel (0 f32 s1, 1 f32 s2, 2 1x1, 3 small-channel, 6 tiny, 7 / 8 transposed-read
-bf16 s1 / s2: the default of bf16 precision, parity cases test_transposed_read_wgrad; 0 / 1 under option 11 = 0; ids 4 / 5
-were round 1's staging-transposed bf16 kernels, removed in round 3;
+weight-gradient ids: mmtta_conv_wgrad_kernel returns the planner's route, the enum csrc/conv_wgrad.hip::WRoute, whose values
+are the ids (0 f32 s1, 1 f32 s2, 2 1x1, 3 small-channel, 6 tiny, 7 / 8 transposed-read bf16 s1 / s2: the default of bf16
+precision, parity cases test_transposed_read_wgrad; 0 / 1 under option 11 = 0; ids 4 / 5 were round 1's staging-transposed
+bf16 kernels, removed in round 3;
 9 the 1x1x1 streaming kernel of bf16 precision, parity cases test_pointwise_conv_weight_gradient_on_transposed_reads;
 10 the thin 27-tap layers of bf16 precision on transposed reads, parity cases test_thin_wgrad_on_transposed_reads).
 VERDICT r1 P1: ids 2 and 9 (igemm <4,4,4,4,8,32>) used to be reachable only by the full-size bench."""

@@ -937,6 +937,53 @@ def test_thin_wgrad_on_transposed_reads(cin, cout, k, stride, transposed, shape,
     close("bias gradient (both kernels)", out[1][1], out[0][1])
 
 
+@pytest.mark.parametrize("precision,shape", [("fp32", (1, 16, 12, 24)), ("bf16", (1, 32, 48, 48))])
+def test_thin_wgrad_with_more_than_32_slabs(precision, shape):
+    """The thin family (wgrad_small_kernel, wgrad_thin_tr_kernel) with more than 32 slabs: slab_prereduce_kernel runs between
+    the main kernel and wgrad_small_reduce_kernel.  3 -> 32, k3 s1, with bias, at the default tuning (4 volumes in flight):
+    fp32 (1, 16, 12, 24) = 4 x 3 x 3 = 36 tiles of 4 x 4 x 8, one slab each; bf16 (1, 32, 48, 48) = 8 x 6 x 6 = 288 tiles of
+    4 x 8 x 8, min(4 * 256, 288 / 8) = 36 slabs; 2 chunks of 32 either way.  The plan is asserted first, so a shape that
+    stops reaching the pre-reduce fails instead of testing the short path."""
+    from multimodal_tta_amd import _lib, ops
+    import ctypes as C
+
+    ops.tune_for_volumes_in_flight(4)
+    cin, cout = 3, 32
+    torch.manual_seed(77)
+    n, d, h, w = shape
+    mod = ref_module(cin, cout, 3, 1, False)
+    x = torch.randn(n, cin, d, h, w)
+    gy = torch.randn(n, cout, d, h, w)
+    if precision == "bf16":
+        x, gy = x.to(torch.bfloat16).float(), gy.to(torch.bfloat16).float()
+    x.requires_grad_(True)
+    mod(x).backward(gy)
+    op = ops.ConvOp(cin, cout, 3, 1, False, "cuda", dtype=ops.BF16 if precision == "bf16" else ops.F32)
+    x_cl, gy_cl = cl(x.detach()), cl(gy)
+    plan = op.wgrad_plan(x_cl, gy_cl)
+    print(f"{precision} {shape}: plan {plan}")
+    assert plan["nsl"] > 32 and plan["pre_chunks"] == (plan["nsl"] + 31) // 32, plan
+    if precision == "bf16":
+        kid = int(_lib.load().mmtta_conv_wgrad_kernel(C.byref(op.d_fwd), C.byref(ops.desc_cl(x_cl)), C.byref(ops.desc_cl(gy_cl))))
+        assert kid == 10, f"weight-gradient kernel {kid}"
+    wt = mod.weight.detach().cuda().contiguous()
+    op.pack(wt)
+    dw = torch.empty_like(wt)
+    db = torch.empty(cout, device="cuda")
+    for step, accumulate in ((1, False), (2, True)):
+        op.wgrad(x_cl, None, gy_cl, dw, db, accumulate=accumulate)
+        torch.cuda.synchronize()
+        what = "accumulate" if accumulate else "plain"
+        if precision == "fp32":
+            close(f"wgrad {what}", dw, step * mod.weight.grad)
+        else:                       # the bf16-operand bound of test_thin_wgrad_on_transposed_reads
+            ref = step * mod.weight.grad
+            err = (dw.cpu() - ref).abs().max().item()
+            print(f"bf16 wgrad {what}: max|err| {err:.3e}, max|ref| {ref.abs().max().item():.3e}")
+            assert err <= 1.5e-2 * ref.abs().max().item() + 1e-5
+        close(f"bgrad {what}", db, step * mod.bias.grad)
+
+
 @pytest.mark.parametrize("cin,cout,k,stride,transposed,shape", [
     (32, 64, 3, 2, False, (2, 16, 16, 32)), (64, 128, 3, 2, False, (1, 9, 11, 13)), (128, 32, 3, 2, True, (2, 6, 8, 8)),
     (256, 64, 3, 2, True, (1, 4, 4, 8)), (64, 64, 3, 1, False, (2, 8, 16, 16)), (128, 128, 3, 1, False, (1, 5, 9, 11)),
