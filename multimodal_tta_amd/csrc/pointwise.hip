@@ -141,6 +141,159 @@ __global__ __launch_bounds__(256) void channel_reduce_kernel(RedArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ the same reduction, streamed
+// channel_reduce_kernel<MODE, 4> for voxel-dense tensors with C <= 1024 and 32-bit element offsets inside a batch item.
+// `part` holds bit for bit what that kernel writes: the rows, cpl / nvl, the voxels of a lane and their order, the order
+// of the lane partials and the expressions per element are its own.  What differs is the schedule:
+//   - a workgroup walks `rows_per_block` consecutive rows of one item and loads its 16 coefficients once;
+//   - a lane's trips are cut into chunks of IT whose loads (clamped addresses, masked adds) are all issued before the
+//     first use, and the next chunk's - the next row's, at a row's end - are in flight under the current one's adds;
+//   - the lane partials of a row are added by one thread per (sum, channel), sequentially in q as before, from an LDS
+//     image [sum][q][channel] that is double-buffered over the rows: one barrier per row, and only the threads that own
+//     a chain stay behind for it.
+struct RedSArgs {
+  const float* x; const float* dout;      // MODE 0: x only
+  long long xsn, dsn;
+  unsigned xsw, dsw;
+  unsigned C, dhw, vox_per_row;
+  unsigned rows_per_n, rows_per_block;
+  const float* mean; const float* rstd; const float* gamma; const float* beta;   // MODE 1
+  act_t relu;
+  int per_item;
+  float* part;
+};
+
+// 4 consecutive channels as loaded (converted when they are used, like Oct8)
+template <bool BF> struct Quad4 { float4 v; };
+template <> struct Quad4<true> { uint2 q; };
+template <bool BF>
+__device__ __forceinline__ Quad4<BF> quad4_ld(const float* base, unsigned eoff) {
+  Quad4<BF> r;
+  if constexpr (BF) r.q = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + eoff);
+  else r.v = *reinterpret_cast<const float4*>(base + eoff);
+  return r;
+}
+__device__ __forceinline__ void quad4_f4(const Quad4<false>& r, float (&v)[4]) { v[0] = r.v.x; v[1] = r.v.y; v[2] = r.v.z; v[3] = r.v.w; }
+__device__ __forceinline__ void quad4_f4(const Quad4<true>& r, float (&v)[4]) {
+  v[0] = bf16_bits_to_f32(r.q.x & 0xffffu); v[1] = __uint_as_float(r.q.x & 0xffff0000u);
+  v[2] = bf16_bits_to_f32(r.q.y & 0xffffu); v[3] = __uint_as_float(r.q.y & 0xffff0000u);
+}
+
+template <int MODE, int IT, bool XBF = false, bool DBF = false>
+__global__ __launch_bounds__(256) void channel_reduce_stream_kernel(RedSArgs a) {
+  __shared__ float red[2][2][1024];                     // [row parity][sum][voxel lane q][4 * cpl channels]
+  const unsigned n = blockIdx.y;
+  const unsigned C = a.C, CV = (C + 3) / 4;
+  unsigned cpl = 1;
+  while (cpl < CV) cpl <<= 1;                           // CV <= 256 (host)
+  const unsigned nvl = 256u / cpl, W = 4 * cpl;
+  const unsigned cl = threadIdx.x & (cpl - 1), vl = threadIdx.x / cpl;
+  const bool live = cl * 4 < C;                         // an idle channel lane sums channel quad 0: nobody reads its partials
+  const unsigned c0 = live ? cl * 4 : 0;
+  const float* xp = item_base<XBF>(a.x, n, a.xsn);
+  const float* dp = MODE == 1 ? item_base<DBF>(a.dout, n, a.dsn) : nullptr;
+  float mu[4], rs[4], g[4], b[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { mu[j] = 0.f; rs[j] = 1.f; g[j] = 1.f; b[j] = 0.f; }
+  if (MODE == 1) {
+    // (the pad lanes of a quad read channel C-1's coefficients: their sums are never written)
+    unsigned pc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pc[j] = min(c0 + j, C - 1);
+    const unsigned ab = a.per_item ? n * C : 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { mu[j] = a.mean[n * C + pc[j]]; rs[j] = a.rstd[n * C + pc[j]]; }
+    if (a.gamma) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] = a.gamma[ab + pc[j]];
+    }
+    if (a.beta) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = a.beta[ab + pc[j]];
+    }
+  }
+  const unsigned row_lo = blockIdx.x * a.rows_per_block;
+  const unsigned row_hi = min(row_lo + a.rows_per_block, a.rows_per_n);
+  const unsigned nchunk = ((a.vox_per_row + nvl - 1) / nvl + IT - 1) / IT;     // chunks of IT trips per row
+  Quad4<XBF> xn[IT];
+  Quad4<DBF> dn[IT];
+  auto issue = [&](unsigned row, unsigned chunk) {
+    const unsigned vb = row * a.vox_per_row + chunk * (IT * nvl) + vl;
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+      const unsigned v = min(vb + i * nvl, a.dhw - 1);
+      xn[i] = quad4_ld<XBF>(xp, v * a.xsw + c0);
+      if (MODE == 1) dn[i] = quad4_ld<DBF>(dp, v * a.dsw + c0);
+    }
+  };
+  float s0[4], s1[4];
+  // one voxel quad into the sums; `ok` false leaves them as they are (skipped, not + 0.f: -0.f stays -0.f)
+  auto add = [&](const Quad4<XBF>& xr, const Quad4<DBF>& dr, bool ok) {
+    float xv[4], dv[4];
+    quad4_f4(xr, xv);
+    if (MODE == 1) quad4_f4(dr, dv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float t0, t1;
+      if (MODE == 0) {
+        t0 = s0[j] + xv[j];
+        t1 = s1[j] + xv[j] * xv[j];
+      } else {
+        const float xhat = (xv[j] - mu[j]) * rs[j];
+        float dz = dv[j];
+        MMTTA_ACT_BWD(dz, a.relu, fmaf(g[j], xhat, b[j]));
+        t0 = s0[j] + dz;
+        t1 = s1[j] + dz * xhat;
+      }
+      s0[j] = ok ? t0 : s0[j];
+      s1[j] = ok ? t1 : s1[j];
+    }
+  };
+  issue(row_lo, 0);
+  for (unsigned row = row_lo; row < row_hi; ++row) {
+    const unsigned v0 = row * a.vox_per_row;
+    const unsigned v1 = min(v0 + a.vox_per_row, a.dhw);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s0[j] = 0.f; s1[j] = 0.f; }
+    for (unsigned chunk = 0; chunk < nchunk; ++chunk) {
+      Quad4<XBF> xq[IT];
+      Quad4<DBF> dq[IT];
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        xq[i] = xn[i];
+        if (MODE == 1) dq[i] = dn[i];
+      }
+      // the next chunk, of the next row behind a row's last; behind the workgroup's last the same chunk once more (cache
+      // hits nobody waits for), so that no branch stands between these loads and the adds below
+      const bool last_c = chunk + 1 == nchunk, last_r = row + 1 == row_hi;
+      issue(last_c && !last_r ? row + 1 : row, last_c ? (last_r ? chunk : 0u) : chunk + 1);
+      const unsigned cb = v0 + chunk * (IT * nvl);
+      if (cb + IT * nvl <= v1) {                          // every lane's IT voxels are inside the row (workgroup-uniform)
+#pragma unroll
+        for (int i = 0; i < IT; ++i) add(xq[i], dq[i], true);
+      } else {
+#pragma unroll
+        for (int i = 0; i < IT; ++i) add(xq[i], dq[i], cb + vl + i * nvl < v1);
+      }
+    }
+    float (&rb)[2][1024] = red[row & 1];
+    *reinterpret_cast<float4*>(&rb[0][vl * W + cl * 4]) = make_float4(s0[0], s0[1], s0[2], s0[3]);
+    *reinterpret_cast<float4*>(&rb[1][vl * W + cl * 4]) = make_float4(s1[0], s1[1], s1[2], s1[3]);
+    __syncthreads();
+    // chain e = (sum, channel).  Its buffer is written again two rows on, behind the next row's barrier, which this
+    // thread reaches only after the chain.
+    for (unsigned e = threadIdx.x; e < 2 * W; e += 256) {
+      const unsigned sm = e / W, c = e & (W - 1);
+      if (c < C) {
+        float t = 0.f;
+#pragma unroll 8
+        for (unsigned q = 0; q < nvl; ++q) t += rb[sm][q * W + c];
+        a.part[(((long long)n * a.rows_per_n + row) * 2 + sm) * C + c] = t;
+      }
+    }
+  }
+}
+
 // stage 2a: one wave per (n,c): fp64 sum over the partial rows -> tot[n*C+c][2]
 __global__ __launch_bounds__(64) void rows_reduce_kernel(const float* part, int rows_per_n, int C, double* tot) {
   const int n = blockIdx.x / C, c = blockIdx.x % C;
@@ -864,6 +1017,51 @@ static void rows_geometry(const mmtta_tensor* t, int& rows_per_n, long long& vox
   vox_per_row = vpr;
 }
 
+// ---- the streamed two-stage reduction (channel_reduce_stream_kernel): which operands take it, and its launch
+static inline bool dense_voxels(const mmtta_tensor* t) { return t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; }
+// `d`: the second tensor of MODE 1 (null for MODE 0).  Voxel-dense 4-channel-vector operands, one pass over the channel
+// lanes (C <= 1024), 32-bit element offsets inside an item; everything else keeps channel_reduce_kernel.
+static bool reduce_stream_ok(const mmtta_tensor* x, const mmtta_tensor* d) {
+  const int64_t pad = (x->c + 3) / 4 * 4;
+  auto ok = [pad](const mmtta_tensor* t) { return vec4_rd(t) && dense_voxels(t) && item_fits_31(t, pad); };
+  const int64_t dhw = (int64_t)x->d * x->h * x->w;
+  return ok(x) && (!d || ok(d)) && x->c >= 1 && x->c <= 1024 && dhw >= 1 && dhw < ((int64_t)1 << 31) && x->n >= 1 && x->n <= 65535;
+}
+
+static RedSArgs reduce_stream_args(const mmtta_tensor* x, const mmtta_tensor* d, const mmtta_norm_on_load* t, float* part) {
+  RedSArgs q;
+  q.x = (const float*)x->ptr; q.dout = d ? (const float*)d->ptr : nullptr;
+  q.xsn = x->sn; q.dsn = d ? d->sn : 0;
+  q.xsw = (unsigned)x->sw; q.dsw = d ? (unsigned)d->sw : 0u;
+  q.C = (unsigned)x->c; q.dhw = (unsigned)((int64_t)x->d * x->h * x->w);
+  int rows; long long vpr;
+  rows_geometry(x, rows, vpr);
+  q.rows_per_n = (unsigned)rows; q.vox_per_row = (unsigned)vpr; q.rows_per_block = 1;
+  q.mean = t ? t->mean : nullptr; q.rstd = t ? t->rstd : nullptr; q.gamma = t ? t->gamma : nullptr; q.beta = t ? t->beta : nullptr;
+  q.relu = act_arg(t); q.per_item = t && t->per_item != 0 ? 1 : 0;
+  q.part = part;
+  return q;
+}
+
+template <int MODE, bool XBF, bool DBF>
+static void launch_reduce_stream(RedSArgs q, int n, hipStream_t s) {
+  unsigned cpl = 1;
+  while (cpl < (q.C + 3) / 4) cpl <<= 1;
+  const unsigned nvl = 256u / cpl, trips = (q.vox_per_row + nvl - 1) / nvl;
+  // Rows per workgroup.  A row of several chunks overlaps its own loads and adds, and one row per workgroup balances best
+  // (measured, groups of 8: 64^3 x 32 and 128^3 x 3 are fastest at 1).  A row of ONE chunk has nothing to overlap with but
+  // the next row: 4 rows per workgroup (32^3 x 64: 23 us at 1, 14 us at 4), fewer where the launch would shrink below
+  // 512 workgroups.
+  const unsigned it = trips >= 4 ? 4 : (trips >= 2 ? 2 : 1), chunks = (trips + it - 1) / it, total = (unsigned)n * q.rows_per_n;
+  unsigned rpb = 1;
+  if (chunks == 1) rpb = total / 512 < 1 ? 1 : (total / 512 > 4 ? 4 : total / 512);
+  q.rows_per_block = rpb;
+  const dim3 grid((q.rows_per_n + rpb - 1) / rpb, (unsigned)n);
+  if (it == 4) hipLaunchKernelGGL((channel_reduce_stream_kernel<MODE, 4, XBF, DBF>), grid, dim3(256), 0, s, q);
+  else if (it == 2) hipLaunchKernelGGL((channel_reduce_stream_kernel<MODE, 2, XBF, DBF>), grid, dim3(256), 0, s, q);
+  else hipLaunchKernelGGL((channel_reduce_stream_kernel<MODE, 1, XBF, DBF>), grid, dim3(256), 0, s, q);
+}
+
 int channel_partial_rows(const mmtta_tensor* t) {
   int r; long long v;
   rows_geometry(t, r, v);
@@ -875,6 +1073,11 @@ int launch_channel_sums(const mmtta_tensor* x, float* part, hipStream_t s) {
   a.x = tv(x); a.dout = tv(x); a.t = nl(nullptr); a.per_item = 0; a.part = part;
   rows_geometry(x, a.rows_per_n, a.vox_per_row);
   const dim3 grid(x->n * a.rows_per_n);
+  if (reduce_stream_ok(x, nullptr)) {
+    const RedSArgs q = reduce_stream_args(x, nullptr, nullptr, part);
+    MMTTA_BF_DISPATCH(is_bf16(x), XBF, { launch_reduce_stream<0, XBF, false>(q, x->n, s); });
+    return launch_status("channel sums");
+  }
   if (is_bf16(x)) {
     if (vec4_rd(x)) hipLaunchKernelGGL((channel_reduce_kernel<0, 4, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((channel_reduce_kernel<0, 1, true>), grid, dim3(256), 0, s, a);
@@ -946,6 +1149,14 @@ int norm_bwd_reduce_body(const mmtta_tensor* dout, const mmtta_tensor* y, const 
   const dim3 grid(y->n * a.rows_per_n);
   hipStream_t s = (hipStream_t)stream;
   const bool v4 = vec4_rd(y) && vec4_rd(dout);
+  if (reduce_stream_ok(y, dout)) {
+    const RedSArgs q = reduce_stream_args(y, dout, t, part);
+    MMTTA_BF_DISPATCH(is_bf16(y), XBF, {
+      if (is_bf16(dout)) launch_reduce_stream<1, XBF, true>(q, y->n, s);
+      else launch_reduce_stream<1, XBF, false>(q, y->n, s);
+    });
+    return launch_status("norm bwd reduce");
+  }
   if (is_bf16(dout) && !is_bf16(y)) {
     if (v4) hipLaunchKernelGGL((channel_reduce_kernel<1, 4, false, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((channel_reduce_kernel<1, 1, false, true>), grid, dim3(256), 0, s, a);
