@@ -205,13 +205,14 @@ int64_t mmtta_conv_pack_table_bytes(int count);
 int mmtta_conv_pack_table_build(const mmtta_pack_item* items, int count, void* table_host, int64_t* total);
 int mmtta_conv_pack_batched(const void* table_dev, int count, int64_t total, void* stream);
 
-/* Launch geometry chosen for a problem; filled by mmtta_conv_plan. */
+/* Launch geometry chosen for a problem; filled by mmtta_conv_plan.  It has no run-time operands, so it plans the route of
+ * the shape: a call that runs as 16 / 17 (mmtta_conv_route) is reported as the implicit GEMM it would otherwise be. */
 typedef struct {
   int32_t tiles;         /* M tiles (over n and space) per launch                           */
-  int32_t launches;      /* 1, or 8 parity classes for stride-2 transposed forms             */
+  int32_t launches;      /* 1 (the 8 parity classes of a stride-2 transposed form share one launch) */
   int32_t ksplit;        /* >1: partial sums go through the workspace                        */
   int32_t stats_rows;    /* rows of the [rows][2][C] partial-statistics slab this op writes  */
-  int32_t config;        /* tile configuration 0..5 (which template instance runs; for profiling) */
+  int32_t config;        /* kernel id 0..15, see mmtta_conv_route (which template instance runs; for profiling) */
   int32_t _pad;
   int64_t workspace_bytes;
 } mmtta_conv_plan_t;
@@ -244,6 +245,16 @@ int mmtta_conv_run(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmt
                    const void* packed, const float* bias, const mmtta_conv_epilogue* epi,
                    const mmtta_tensor* y, int accumulate, float* stats, void* workspace,
                    int64_t workspace_bytes, void* stream);
+
+/* Which kernel mmtta_conv_run would launch for these operands (host-only, launches nothing; the run itself asks the same
+ * planner, csrc/conv_igemm.hip: geometry).  The ids are those of mmtta_conv_plan_t.config, plus the two routes that depend
+ * on the run-time operands:
+ *   0..5 fp32 / 7..12 bf16 implicit GEMM tiles, 14 the lean bf16 tile     6 direct (<= 4 produced channels)
+ *   13 thin-K (<= 4 gathered channels)                                    15 class-fused stride-2 transposed form
+ *   16 small-K 1x1x1 (fp32, nothing fused)                                17 streaming 1x1x1 (bf16, voxel-dense tensors)
+ * or a negative mmtta error code. */
+int mmtta_conv_route(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                     const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
 
 /* ---- per-volume parameter sets: N volumes (or N identical sub-networks) in ONE launch, each with ITS OWN parameters.
  * Episodic adaptation has no cross-volume state: every test volume adapts its own copy of the source weights (SURVEY.md

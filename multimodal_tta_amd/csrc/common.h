@@ -114,6 +114,19 @@ inline bool item_fits_31(const mmtta_tensor* t, int64_t pad) {
   const int64_t last = (int64_t)(t->d - 1) * t->sd + (int64_t)(t->h - 1) * t->sh + (int64_t)(t->w - 1) * t->sw + pad;
   return last < ((int64_t)1 << 31);
 }
+// 32-bit element offsets from 24-bit multiply-adds: the d / h / w strides stay below 2^24
+inline bool strides_fit_24(const mmtta_tensor* t) { return t->sw < (1 << 24) && t->sh < (1 << 24) && t->sd < (1 << 24); }
+// a batch item is one run of voxel rows: no gap between x-rows or between z-slices (the row stride itself may be padded)
+inline bool voxel_dense(const mmtta_tensor* t) { return t->sc == 1 && t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; }
+// ... that the streaming 1x1x1 kernels read 16 bytes at a time behind a 32-bit element offset
+inline bool dense_rows16(const mmtta_tensor* t) {
+  const int q = is_bf16(t) ? 8 : 4;
+  return voxel_dense(t) && ((uintptr_t)t->ptr) % 16 == 0 && t->sw % q == 0 && t->sn % q == 0 &&
+         (int64_t)t->d * t->h * t->w * t->sw < ((int64_t)1 << 31);
+}
+inline bool same_shape(const mmtta_tensor* a, const mmtta_tensor* b) {
+  return a->n == b->n && a->c == b->c && a->d == b->d && a->h == b->h && a->w == b->w;
+}
 
 // ---- storage-type helpers.  In `bf16` precision the forward activations (raw conv outputs, residual-unit outputs,
 // concat buffers) are STORED as bf16 (what torch autocast does); gradients, logits, statistics and weights stay fp32.
@@ -326,6 +339,19 @@ inline NL nl(const mmtta_norm_on_load* t) {
   r.mean = t->mean; r.rstd = t->rstd; r.gamma = t->gamma; r.beta = t->beta; r.relu = act_arg(t);
   r.scale = t->scale; r.shift = t->scale ? t->shift : nullptr;
   return r;
+}
+// The fused `add` of a convolution epilogue into the launch arguments of a kernel family (GArgs, CArgs, DArgs name these
+// fields alike): checked against y, or cleared when the call has none.
+template <class Args>
+inline int epilogue_add(const mmtta_conv_epilogue* epi, const mmtta_tensor* y, Args& a) {
+  a.add = nullptr; a.asn = a.asd = a.ash = a.asw = 0; a.tadd = nl(nullptr);
+  if (!(epi && epi->add)) return MMTTA_OK;
+  const mmtta_tensor* ad = epi->add;
+  MMTTA_CHECK(ad->ptr && is_cl(ad) && same_shape(ad, y), MMTTA_ERR_INVALID,
+              "conv: epilogue `add` must be channels-last with the shape of y");
+  a.add = (const float*)ad->ptr; a.asn = ad->sn; a.asd = ad->sd; a.ash = ad->sh; a.asw = ad->sw;
+  a.tadd = nl(&epi->add_norm);
+  return MMTTA_OK;
 }
 // Per-item affines (mmtta_norm_on_load.per_item): the convolution kernels read a norm-on-load through its precombined
 // scale / shift, which are [N*C] - per item - by construction, so they honour the flag as they are; a per-item descriptor
@@ -603,7 +629,7 @@ long long upconv8_image_bytes(const mmtta_conv_desc* d);
 long long chan_frag_bytes(const mmtta_conv_desc* d);
 int direct_blocks_per_n(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y);
 bool pointwise_small_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y, const float* stats,
-                                const mmtta_conv_epilogue* epi, const mmtta_norm_on_load* x_norm);
+                                const mmtta_tensor* add, const mmtta_norm_on_load* x_norm);
 int pointwise_small_run(const mmtta_tensor* x, const void* packed, int Kp, int Np, const float* bias, const mmtta_tensor* y,
                         int accumulate, const PSets& sets, hipStream_t stream);
 bool chan_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y);

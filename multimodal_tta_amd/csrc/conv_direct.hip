@@ -1216,13 +1216,10 @@ static void launch_chan_k(const CArgs& a, int K, int N, int blocks, hipStream_t 
 
 template <int S, int KI, bool HAS_T>
 static void launch_chan_mfma_n(const CArgs& a, int N, int blocks, hipStream_t s) {
-  if (a.in.bf) {                     // bf16-stored gathered tensor (network input; thin gradients)
-    if (N > 32) hipLaunchKernelGGL((chan_mfma_kernel<S, KI, 2, HAS_T, true>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((chan_mfma_kernel<S, KI, 1, HAS_T, true>), dim3(blocks), dim3(256), 0, s, a);
-    return;
-  }
-  if (N > 32) hipLaunchKernelGGL((chan_mfma_kernel<S, KI, 2, HAS_T>), dim3(blocks), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((chan_mfma_kernel<S, KI, 1, HAS_T>), dim3(blocks), dim3(256), 0, s, a);
+  MMTTA_BF_DISPATCH(a.in.bf, XBF, {      // XBF: bf16-stored gathered tensor (network input; thin gradients)
+    if (N > 32) hipLaunchKernelGGL((chan_mfma_kernel<S, KI, 2, HAS_T, XBF>), dim3(blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((chan_mfma_kernel<S, KI, 1, HAS_T, XBF>), dim3(blocks), dim3(256), 0, s, a);
+  });
 }
 
 template <int S, bool HAS_T>
@@ -1245,16 +1242,11 @@ int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
   MMTTA_CHECK(a.koff == 0 || x->c == 1, MMTTA_ERR_UNSUPPORTED, "thin-K conv: only a one-channel slice may start inside a 16-byte group");
   a.in.p -= a.koff;
   a.w = (const float*)packed; a.Kp = Kp; a.Np = Np; a.bias = bias;
-  a.add = nullptr; a.asn = a.asd = a.ash = a.asw = 0; a.tadd = nl(nullptr); a.add_bf = 0;
-  if (epi && epi->add) {
-    const mmtta_tensor* ad = epi->add;
-    MMTTA_CHECK(ad->ptr && is_cl(ad) && ad->n == y->n && ad->c == y->c && ad->d == y->d && ad->h == y->h && ad->w == y->w,
-                MMTTA_ERR_INVALID, "conv: epilogue `add` must be channels-last with the shape of y");
-    a.add = (const float*)ad->ptr; a.asn = ad->sn; a.asd = ad->sd; a.ash = ad->sh; a.asw = ad->sw;
-    a.tadd = nl(&epi->add_norm);
-    a.add_bf = is_bf16(ad) ? 1 : 0;
-    MMTTA_CHECK((long long)(ad->h + 4) * ad->sh < (1LL << 31), MMTTA_ERR_UNSUPPORTED, "thin-K conv: epilogue `add` slice beyond 2^31 elements");
-  }
+  const int st = epilogue_add(epi, y, a);
+  if (st) return st;
+  a.add_bf = (a.add && is_bf16(epi->add)) ? 1 : 0;
+  MMTTA_CHECK(a.add == nullptr || (long long)(epi->add->h + 4) * a.ash < (1LL << 31), MMTTA_ERR_UNSUPPORTED,
+              "thin-K conv: epilogue `add` slice beyond 2^31 elements");
   // the <= 4-channel gathered tensor is fp32 (gradients, fp32 precision) or - the network input of bf16 precision - bf16
   // with 8-byte voxels, on the matrix-core path; the 32 / 64-channel result may be bf16-stored, on that path only
   // (a bf16-stored result - the deep-fusion stems under method.storage: bf16 - takes the matrix-core kernel for one input
@@ -1271,12 +1263,10 @@ int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
   const int S = d->op == MMTTA_CONV_FWD ? d->stride : 2;       // CONVT_DGRAD: stride-2 gather
   // one input channel (the single-modality stems of the deep-fusion net) is 27 FMAs per output: the VALU kernel wins there
   if (mfma_path) {
-    if (S == 1) { if (has_t) launch_chan_mfma<1, true>(a, x->c, y->c, blocks, stream); else launch_chan_mfma<1, false>(a, x->c, y->c, blocks, stream); }
-    else { if (has_t) launch_chan_mfma<2, true>(a, x->c, y->c, blocks, stream); else launch_chan_mfma<2, false>(a, x->c, y->c, blocks, stream); }
+    MMTTA_BF_DISPATCH(has_t, HT, { if (S == 1) launch_chan_mfma<1, HT>(a, x->c, y->c, blocks, stream); else launch_chan_mfma<2, HT>(a, x->c, y->c, blocks, stream); });
     return launch_status("thin-K conv (bf16 MFMA)");
   }
-  if (S == 1) { if (has_t) launch_chan_k<1, true>(a, x->c, y->c, blocks, stream); else launch_chan_k<1, false>(a, x->c, y->c, blocks, stream); }
-  else { if (has_t) launch_chan_k<2, true>(a, x->c, y->c, blocks, stream); else launch_chan_k<2, false>(a, x->c, y->c, blocks, stream); }
+  MMTTA_BF_DISPATCH(has_t, HT, { if (S == 1) launch_chan_k<1, HT>(a, x->c, y->c, blocks, stream); else launch_chan_k<2, HT>(a, x->c, y->c, blocks, stream); });
   return launch_status("direct conv (lanes along N)");
 }
 
@@ -1380,8 +1370,8 @@ __global__ __launch_bounds__(256) void pointwise_small_k_kernel(PArgs a) {
 }
 
 bool pointwise_small_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y, const float* stats,
-                                const mmtta_conv_epilogue* epi, const mmtta_norm_on_load* x_norm) {
-  if (d->ksize != 1 || d->stride != 1 || stats != nullptr || (epi && epi->add)) return false;
+                                const mmtta_tensor* add, const mmtta_norm_on_load* x_norm) {
+  if (d->ksize != 1 || d->stride != 1 || stats != nullptr || add) return false;
   if (x_norm && (x_norm->mean || x_norm->scale)) return false;
   if (!(d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONV_DGRAD)) return false;
   return x->c <= 4 && is_f32(x) && y->c % 4 == 0 && y->c >= 4 && aligned16(x) && x->sw >= 4 &&
@@ -1419,8 +1409,7 @@ static int direct_variant(const mmtta_conv_desc* d, const mmtta_tensor* x) {
   if ((K == 32 || K == 64) && d->op == MMTTA_CONVT_FWD && d->ksize == 3 && d->stride == 2 &&
       (long long)x->d * x->sd < (1LL << 31)) {               // 32-bit offsets inside a batch item
     // bf16 precision: the 2x2x2 gather GEMM (upconv8_kernel) when the input admits its 8-channel items
-    const int q = is_bf16(x) ? 8 : 4;
-    if (d->dtype == MMTTA_BF16 && x->sw % q == 0 && x->sh % q == 0 && x->sd % q == 0 && x->sn % q == 0) return 5;
+    if (d->dtype == MMTTA_BF16 && quad_aligned(x, 16, is_bf16(x) ? 8 : 4)) return 5;      // (the base: aligned16 above)
     return 3;
   }
   if (K == 32 || K == 64) return 1;
@@ -1458,21 +1447,14 @@ int direct_blocks_per_n(const mmtta_conv_desc* d, const mmtta_tensor* x, const m
 template <int KL, bool HAS_T>
 static void launch_klane(const DArgs& a, int n, size_t lds, hipStream_t stream) {
   const dim3 grid(a.blocks_per_n, n), block(256);
-  if (a.in.bf) {
+  MMTTA_BF_DISPATCH(a.in.bf, XBF, {
     switch (a.N) {
-      case 1: hipLaunchKernelGGL((direct_klane_kernel<KL, 1, HAS_T, true>), grid, block, lds, stream, a); break;
-      case 2: hipLaunchKernelGGL((direct_klane_kernel<KL, 2, HAS_T, true>), grid, block, lds, stream, a); break;
-      case 3: hipLaunchKernelGGL((direct_klane_kernel<KL, 3, HAS_T, true>), grid, block, lds, stream, a); break;
-      default: hipLaunchKernelGGL((direct_klane_kernel<KL, 4, HAS_T, true>), grid, block, lds, stream, a); break;
+      case 1: hipLaunchKernelGGL((direct_klane_kernel<KL, 1, HAS_T, XBF>), grid, block, lds, stream, a); break;
+      case 2: hipLaunchKernelGGL((direct_klane_kernel<KL, 2, HAS_T, XBF>), grid, block, lds, stream, a); break;
+      case 3: hipLaunchKernelGGL((direct_klane_kernel<KL, 3, HAS_T, XBF>), grid, block, lds, stream, a); break;
+      default: hipLaunchKernelGGL((direct_klane_kernel<KL, 4, HAS_T, XBF>), grid, block, lds, stream, a); break;
     }
-    return;
-  }
-  switch (a.N) {
-    case 1: hipLaunchKernelGGL((direct_klane_kernel<KL, 1, HAS_T>), grid, block, lds, stream, a); break;
-    case 2: hipLaunchKernelGGL((direct_klane_kernel<KL, 2, HAS_T>), grid, block, lds, stream, a); break;
-    case 3: hipLaunchKernelGGL((direct_klane_kernel<KL, 3, HAS_T>), grid, block, lds, stream, a); break;
-    default: hipLaunchKernelGGL((direct_klane_kernel<KL, 4, HAS_T>), grid, block, lds, stream, a); break;
-  }
+  });
 }
 
 template <int KI, bool HAS_T>
@@ -1900,19 +1882,12 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   a.ps = sets;
   a.in = tv(x); a.tin = nl(x_norm); a.out = tv(y);
   a.w = (const float*)packed; a.bias = bias;
-  a.add = nullptr; a.asn = a.asd = a.ash = a.asw = 0; a.tadd = nl(nullptr);
-  if (epi && epi->add) {
-    const mmtta_tensor* ad = epi->add;
-    MMTTA_CHECK(ad->ptr && is_cl(ad) && ad->n == y->n && ad->c == y->c && ad->d == y->d && ad->h == y->h && ad->w == y->w,
-                MMTTA_ERR_INVALID, "conv: epilogue `add` must be channels-last with the shape of y");
-    a.add = (const float*)ad->ptr; a.asn = ad->sn; a.asd = ad->sd; a.ash = ad->sh; a.asw = ad->sw;
-    a.tadd = nl(&epi->add_norm);
-  }
+  const int st = epilogue_add(epi, y, a);
+  if (st) return st;
   a.K = x->c; a.N = y->c; a.ksize = d->ksize; a.stride = d->stride;
   a.transposed = (d->op == MMTTA_CONVT_FWD || d->op == MMTTA_CONV_DGRAD) ? 1 : 0;
   a.accumulate = accumulate;
-  a.out_vec4 = (y->flags & MMTTA_TENSOR_OWNS_PAD) && y->sw == 4 && y->sc == 1 && y->sh % 4 == 0 && y->sd % 4 == 0 &&
-               y->sn % 4 == 0 && ((uintptr_t)y->ptr) % 16 == 0;
+  a.out_vec4 = (y->flags & MMTTA_TENSOR_OWNS_PAD) && y->sw == 4 && aligned16(y);
   a.stats = stats; a.blocks_per_n = direct_blocks_per_n(d, x, y);
   const int T = d->ksize * d->ksize * d->ksize;
   const size_t lds = (size_t)T * a.K * 16 + (size_t)a.K * 8 + 32 * sizeof(float);
@@ -1936,80 +1911,61 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   MMTTA_CHECK(thin_bf || (is_f32(y) && !(epi && epi->add && is_bf16(epi->add))), MMTTA_ERR_UNSUPPORTED, "direct conv: outputs are fp32-stored");
   if (variant == 5) {
     const int tz = (x->d + 3) / 4, ty = (x->h + 3) / 4, tx = (x->w + 7) / 8;
-    if (is_bf16(x)) {
-      if (a.K == 64) { if (has_t) launch_upconv8<64, true, true>(a, y->n, tz, ty, tx, stream); else launch_upconv8<64, false, true>(a, y->n, tz, ty, tx, stream); }
-      else { if (has_t) launch_upconv8<32, true, true>(a, y->n, tz, ty, tx, stream); else launch_upconv8<32, false, true>(a, y->n, tz, ty, tx, stream); }
-    } else {
-      if (a.K == 64) { if (has_t) launch_upconv8<64, true, false>(a, y->n, tz, ty, tx, stream); else launch_upconv8<64, false, false>(a, y->n, tz, ty, tx, stream); }
-      else { if (has_t) launch_upconv8<32, true, false>(a, y->n, tz, ty, tx, stream); else launch_upconv8<32, false, false>(a, y->n, tz, ty, tx, stream); }
-    }
+    MMTTA_BF_DISPATCH(has_t, HT, { MMTTA_BF_DISPATCH(is_bf16(x), XBF, {
+      if (a.K == 64) launch_upconv8<64, HT, XBF>(a, y->n, tz, ty, tx, stream);
+      else launch_upconv8<32, HT, XBF>(a, y->n, tz, ty, tx, stream);
+    }); });
     return launch_status("up-convolution (2x2x2 gather GEMM)");
   }
   MMTTA_CHECK(is_f32(x) || (variant == 3 && d->dtype == MMTTA_BF16) || variant == 1 || thin_bf, MMTTA_ERR_UNSUPPORTED,
               "direct conv: a bf16-stored input is supported by the matrix-core up-convolution and the lanes-along-K kernel only");
   {  // 1x1x1 head on voxel-dense tensors, nothing fused: the streaming kernel
-    auto dense = [](const mmtta_tensor* t) { return t->sc == 1 && t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
     const bool head = d->op == MMTTA_CONV_FWD && d->ksize == 1 && (a.K == 32 || a.K == 64) && !has_t && stats == nullptr &&
-                      !(epi && epi->add) && !accumulate && is_f32(y) && dense(x) && dense(y) && y->sw == 4 && a.out_vec4 &&
-                      ((uintptr_t)x->ptr) % 16 == 0 && x->sw % (is_bf16(x) ? 8 : 4) == 0 && x->sn % (is_bf16(x) ? 8 : 4) == 0 &&
-                      (long long)x->d * x->h * x->w * x->sw < (1LL << 31);
+                      !(epi && epi->add) && !accumulate && is_f32(y) && dense_rows16(x) && voxel_dense(y) && y->sw == 4 && a.out_vec4;
     if (head) {
       const long long dhw = (long long)y->d * y->h * y->w;
       long long blocks = (dhw + 255) / 256;
       if (blocks > 2048) blocks = 2048;
       const dim3 grid((unsigned)blocks, y->n), block(256);
-      if (a.K == 32) { if (is_bf16(x)) hipLaunchKernelGGL((pointwise_head_kernel<32, true>), grid, block, 0, stream, a);
-                       else hipLaunchKernelGGL((pointwise_head_kernel<32, false>), grid, block, 0, stream, a); }
-      else { if (is_bf16(x)) hipLaunchKernelGGL((pointwise_head_kernel<64, true>), grid, block, 0, stream, a);
-             else hipLaunchKernelGGL((pointwise_head_kernel<64, false>), grid, block, 0, stream, a); }
+      MMTTA_BF_DISPATCH(is_bf16(x), XBF, {
+        if (a.K == 32) hipLaunchKernelGGL((pointwise_head_kernel<32, XBF>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((pointwise_head_kernel<64, XBF>), grid, block, 0, stream, a);
+      });
       return launch_status("1x1 head (streaming)");
     }
   }
   if (variant == 1) {
     const size_t kl_lds = (size_t)T * a.K * 16 + 32 * sizeof(float);
-    if (a.K == 64) { if (has_t) launch_klane<16, true>(a, y->n, kl_lds, stream); else launch_klane<16, false>(a, y->n, kl_lds, stream); }
-    else { if (has_t) launch_klane<8, true>(a, y->n, kl_lds, stream); else launch_klane<8, false>(a, y->n, kl_lds, stream); }
+    MMTTA_BF_DISPATCH(has_t, HT, {
+      if (a.K == 64) launch_klane<16, HT>(a, y->n, kl_lds, stream);
+      else launch_klane<8, HT>(a, y->n, kl_lds, stream);
+    });
     return launch_status("direct conv (lanes along K)");
   }
   if (variant == 2) {
-    if (has_t) launch_row<true>(a, y->n, stream); else launch_row<false>(a, y->n, stream);
+    MMTTA_BF_DISPATCH(has_t, HT, { launch_row<HT>(a, y->n, stream); });
     return launch_status("direct conv (row)");
   }
   if (variant == 4) {
     const dim3 grid(a.blocks_per_n, y->n), block(256);
-    if (thin_bf) {
-      if (g_thin_mfma == 3) {
-        if (has_t) hipLaunchKernelGGL((conv3_mfma4_kernel<true, 2, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((conv3_mfma4_kernel<false, 2, true>), grid, block, 0, stream, a);
-      } else if (g_thin_mfma == 2) {
-        if (has_t) hipLaunchKernelGGL((conv3_mfma4_kernel<true, 4, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((conv3_mfma4_kernel<false, 4, true>), grid, block, 0, stream, a);
-      } else {
-        if (has_t) hipLaunchKernelGGL((conv3_mfma4_kernel<true, 8, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((conv3_mfma4_kernel<false, 8, true>), grid, block, 0, stream, a);
+    MMTTA_BF_DISPATCH(has_t, HT, { MMTTA_BF_DISPATCH(thin_bf, GBF, {
+      switch (g_thin_mfma) {      // the tile depth TZ (MMTTA_OPT_THIN_MFMA)
+        case 3: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 2, GBF>), grid, block, 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 4, GBF>), grid, block, 0, stream, a); break;
+        default: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 8, GBF>), grid, block, 0, stream, a); break;
       }
-      return launch_status("direct conv (4x4x4 matrix tiles, bf16-stored thin tensors)");
-    }
-    if (g_thin_mfma == 3) {
-      if (has_t) hipLaunchKernelGGL((conv3_mfma4_kernel<true, 2>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((conv3_mfma4_kernel<false, 2>), grid, block, 0, stream, a);
-    } else if (g_thin_mfma == 2) {
-      if (has_t) hipLaunchKernelGGL((conv3_mfma4_kernel<true, 4>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((conv3_mfma4_kernel<false, 4>), grid, block, 0, stream, a);
-    } else {
-      if (has_t) hipLaunchKernelGGL((conv3_mfma4_kernel<true, 8>), grid, block, 0, stream, a);
-      else hipLaunchKernelGGL((conv3_mfma4_kernel<false, 8>), grid, block, 0, stream, a);
-    }
-    return launch_status("direct conv (4x4x4 matrix tiles)");
+    }); });
+    return launch_status(thin_bf ? "direct conv (4x4x4 matrix tiles, bf16-stored thin tensors)" : "direct conv (4x4x4 matrix tiles)");
   }
   if (variant == 3) {
     const bool bf = d->dtype == MMTTA_BF16;
-    if (a.K == 64) { if (has_t) launch_upconv_p<64, true>(a, y->n, bf, stream); else launch_upconv_p<64, false>(a, y->n, bf, stream); }
-    else { if (has_t) launch_upconv_p<32, true>(a, y->n, bf, stream); else launch_upconv_p<32, false>(a, y->n, bf, stream); }
+    MMTTA_BF_DISPATCH(has_t, HT, {
+      if (a.K == 64) launch_upconv_p<64, HT>(a, y->n, bf, stream);
+      else launch_upconv_p<32, HT>(a, y->n, bf, stream);
+    });
     return launch_status("direct up-convolution");
   }
-  if (has_t) hipLaunchKernelGGL(direct_conv_kernel<true>, dim3(a.blocks_per_n, y->n), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL(direct_conv_kernel<false>, dim3(a.blocks_per_n, y->n), dim3(256), lds, stream, a);
+  MMTTA_BF_DISPATCH(has_t, HT, { hipLaunchKernelGGL(direct_conv_kernel<HT>, dim3(a.blocks_per_n, y->n), dim3(256), lds, stream, a); });
   return launch_status("direct conv");
 }
 

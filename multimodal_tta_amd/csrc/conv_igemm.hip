@@ -1708,14 +1708,40 @@ static int validate_desc(const mmtta_conv_desc* d) {
   return MMTTA_OK;
 }
 
+static int config_id(const Config& c) {
+  int id;
+  if (c.bf && c.NB == 1 && c.MB == 2) return 14;     // lean bf16 tile <1,2,4,8,8,16>
+  if (c.NB == 1) id = c.MB == 4 ? 0 : 3;
+  else if (c.NB == 2) id = c.MB == 4 ? 1 : 4;
+  else id = c.KCI == 32 ? 2 : 5;
+  return c.bf ? id + 7 : id;      // 7..12 = bf16 variants
+}
+
+// Which kernel a call runs: the values are the public ids (mmtta_conv_plan_t.config, mmtta_conv_route).  Every other value
+// 0..14 is an implicit GEMM, config_id of its tile.
+enum CRoute : int {
+  C_DIRECT = 6,      // conv_direct.hip: <= 4 produced channels (direct_conv_run picks the variant)
+  C_THIN = 13,       // conv_direct.hip: thin-K kernels, <= 4 gathered channels into 32 / 64 (chan_conv_run)
+  C_CLS_FUSED = 15,  // igemm_cls8_kernel: the 8 parity classes of a stride-2 transposed form in one workgroup
+  C_PW_SMALL = 16,   // pointwise_small_k_kernel: fp32 1x1x1 from <= 4 channels, nothing fused
+  C_PW_MFMA = 17,    // pointwise_mfma_kernel: bf16 1x1x1 streamed over voxel-dense tensors
+};
+
+// What a run knows beyond the shapes.  mmtta_conv_plan has none of it and plans the route of the shape (geometry: rt = null).
+struct RunFacts {
+  const float* stats; const mmtta_tensor* add; const mmtta_norm_on_load* x_norm;      // add: epi->add
+  int accumulate;                      // (no route gate reads it today: the streaming kernels accumulate themselves)
+};
+
 struct Geometry {
+  int route;      // CRoute
   int K, N, Kp, Np, si;
   bool classes;
   Config cfg;
-  int tz, ty, tx, tiles_per_n, tiles, ncls;
+  int tz, ty, tx, tiles_per_n, tiles, ncls;      // (class-fused: its own tiling, coarse 4 x 4 x 8, one statistics row per tile)
   int nstages, ksplit, sps;
-  int launches;
-  bool fused;     // class-fused kernel of the stride-2 transposed forms (its own tiling: coarse 4 x 4 x 8, one row per tile)
+  int stats_rows;              // rows of the partial-statistics slab the call writes
+  int64_t workspace_bytes;     // split-K partial sums
 };
 
 static int expected_out_dim(const mmtta_conv_desc* d, int in) {
@@ -1727,7 +1753,31 @@ static int expected_out_dim(const mmtta_conv_desc* d, int in) {
   }
 }
 
-static int geometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y, Geometry& g) {
+// ---- the gates of the routes (6, 16 and 13: direct_applicable, pointwise_small_applicable, chan_applicable of conv_direct.hip)
+// 17: 1x1x1 over many voxels with bf16 operands, nothing but bias / add / accumulate around it
+static bool pointwise_mfma_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y, const Geometry& g,
+                                      const RunFacts& rt) {
+  static const bool pw_on = !(getenv("MMTTA_POINTWISE_MFMA") && atoi(getenv("MMTTA_POINTWISE_MFMA")) == 0);      // (A/B switch)
+  const int kb = (g.K + 15) / 16;
+  auto rows_ok = [&](const mmtta_tensor* t) { return dense_rows16(t) && is_bf16(t) == is_bf16(x); };
+  return pw_on && d->ksize == 1 && (d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONV_DGRAD) && use_bf16(d, g.K) &&
+         (kb <= 4 || kb == 6 || kb == 8) && g.Np <= 64 && rt.stats == nullptr && !(rt.x_norm && (rt.x_norm->mean || rt.x_norm->scale)) &&
+         (long long)y->d * y->h * y->w >= 4096 && rows_ok(x) && rows_ok(y) && (rt.add == nullptr || (rows_ok(rt.add) && same_shape(rt.add, y)));
+}
+
+// 15: the tensors admit the class-fused kernel's 16-byte accesses behind 32-bit offsets from 24-bit multiply-adds
+static bool cls_fused_operand(const mmtta_tensor* t) {
+  return quad_aligned(t, 16, is_bf16(t) ? 8 : 4) && strides_fit_24(t) && item_fits_31(t, t->c + 16);
+}
+
+// statistics rows written per tile: 1 by the conv epilogue, MT/32 by the split-K finalize
+static int stats_rows_per_tile(const Geometry& g) {
+  if (g.route == C_CLS_FUSED) return 1;
+  return g.ksplit > 1 ? g.cfg.TZ * g.cfg.TY * g.cfg.TX / 32 : 1;
+}
+
+// The planner of a whole call: argument checks, the route, and the numbers mmtta_conv_plan reports for it.
+static int geometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y, const RunFacts* rt, Geometry& g) {
   int st = validate_desc(d);
   if (st) return st;
   MMTTA_CHECK(x && y && x->ptr && y->ptr, MMTTA_ERR_INVALID, "conv: null tensor");
@@ -1764,7 +1814,6 @@ static int geometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   g.ncls = g.classes ? 8 : 1;
   g.tiles = g.tiles_per_n * x->n * g.ncls;     // the parity classes share one launch
   g.nstages = (g.K + g.cfg.KCI - 1) / g.cfg.KCI;
-  g.launches = 1;
   const int ncolgroups = (g.Np + 32 * g.cfg.NB - 1) / (32 * g.cfg.NB);
   const int wgs = g.tiles_per_n * g.ncls * ncolgroups;      // per batch item
   g.ksplit = 1;
@@ -1781,18 +1830,13 @@ static int geometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   }
   // Class-fused kernel (MMTTA_OPT_CLASS_FUSED_MIN_WORKGROUPS): all 8 parity classes of a coarse 4 x 4 x 8 tile in one
   // workgroup, when that still makes enough workgroups (no split-K there) and the tensors admit its 16-byte accesses
-  g.fused = false;
+  g.route = config_id(g.cfg);
   if (g.classes && g.cfg.bf && g_cls_fused_min > 0) {
     const int ftz = (Dg + 3) / 4, fty = (Hg + 3) / 4, ftx = (Wg + 7) / 8;
     const long long fw = (long long)ftz * fty * ftx * (g.Np / 32);      // per batch item
-    auto al = [](const mmtta_tensor* t) {
-      const int64_t q = is_bf16(t) ? 8 : 4, lim24 = (int64_t)1 << 24;
-      const int64_t last = (int64_t)(t->d - 1) * t->sd + (int64_t)(t->h - 1) * t->sh + (int64_t)(t->w - 1) * t->sw + t->c + 16;
-      return ((uintptr_t)t->ptr) % 16 == 0 && t->sw % q == 0 && t->sh % q == 0 && t->sd % q == 0 && t->sn % q == 0 &&
-             t->sw < lim24 && t->sh < lim24 && t->sd < lim24 && last < ((int64_t)1 << 31);
-    };
-    if (fw >= g_cls_fused_min && al(x) && al(y) && y->c % 4 == 0 && is_bf16(x) == is_bf16(y) && g_epilogue_vec) {
-      g.fused = true;
+    if (fw >= g_cls_fused_min && cls_fused_operand(x) && cls_fused_operand(y) && y->c % 4 == 0 && is_bf16(x) == is_bf16(y) &&
+        g_epilogue_vec) {
+      g.route = C_CLS_FUSED;
       g.tz = ftz; g.ty = fty; g.tx = ftx;
       g.tiles_per_n = ftz * fty * ftx;
       g.ncls = 1;                                  // one statistics row per fused tile
@@ -1801,13 +1845,22 @@ static int geometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
       g.ksplit = 1; g.sps = g.nstages;
     }
   }
+  // the kernels outside this file come first; the direct and thin-K plans are one workgroup and one statistics row per tile
+  const bool f32_operands = !use_bf16(d, g.K);
+  if (direct_applicable(d)) {
+    g.route = C_DIRECT; g.ksplit = 1;
+    g.tiles = direct_blocks_per_n(d, x, y) * y->n;
+  } else if (rt && f32_operands && is_f32(x) && pointwise_small_applicable(d, x, y, rt->stats, rt->add, rt->x_norm)) {      // (y: fp32- or bf16-stored)
+    g.route = C_PW_SMALL;
+  } else if (f32_operands && chan_applicable(d, x, y)) {
+    g.route = C_THIN; g.ksplit = 1;
+    g.tiles = chan_tiles_per_n(y) * y->n;
+  } else if (rt && pointwise_mfma_applicable(d, x, y, g, *rt)) {
+    g.route = C_PW_MFMA;
+  }
+  g.stats_rows = g.tiles * stats_rows_per_tile(g);
+  g.workspace_bytes = g.ksplit > 1 ? (int64_t)g.ksplit * g.tiles * g.cfg.TZ * g.cfg.TY * g.cfg.TX * g.Np * (int64_t)sizeof(float) : 0;
   return MMTTA_OK;
-}
-
-// statistics rows written per tile: 1 by the conv epilogue, MT/32 by the split-K finalize
-static int stats_rows_per_tile(const Geometry& g) {
-  if (g.fused) return 1;
-  return g.ksplit > 1 ? g.cfg.TZ * g.cfg.TY * g.cfg.TX / 32 : 1;
 }
 
 static void build_taps(const mmtta_conv_desc* d, int pz, int py, int px, Taps& t) {
@@ -1910,17 +1963,8 @@ static int launch_cfg(const GArgs& a, const Taps* ht, int tiles, hipStream_t s) 
   return launch_cfg_t<NB, MB, TZ, TY, TX, KCI, BF, OCC, false>(a, ht, tiles, s);
 }
 
-static int config_id(const Config& c) {
-  int id;
-  if (c.bf && c.NB == 1 && c.MB == 2) return 14;     // lean bf16 tile <1,2,4,8,8,16>
-  if (c.NB == 1) id = c.MB == 4 ? 0 : 3;
-  else if (c.NB == 2) id = c.MB == 4 ? 1 : 4;
-  else id = c.KCI == 32 ? 2 : 5;
-  return c.bf ? id + 7 : id;      // 6 = direct kernel; 7..12 = bf16 variants
-}
-
-static int launch_any(const Config& c, const GArgs& a, const Taps* ht, int tiles, hipStream_t s) {
-  switch (config_id(c)) {
+static int launch_any(int route, const GArgs& a, const Taps* ht, int tiles, hipStream_t s) {
+  switch (route) {
     case 0: return launch_cfg<1, 4, 8, 8, 8, 8, false>(a, ht, tiles, s);
     case 1: return launch_cfg<2, 4, 4, 8, 8, 16, false>(a, ht, tiles, s);
     case 2: return launch_cfg<4, 4, 4, 4, 8, 32, false>(a, ht, tiles, s);
@@ -1937,106 +1981,45 @@ static int launch_any(const Config& c, const GArgs& a, const Taps* ht, int tiles
   }
 }
 
-// mmtta_conv_run_sets past the checks of its norm-on-load descriptors
-int conv_run_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
-                  const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
-                  void* workspace, int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
-  Geometry g;
-  int st = geometry(d, x, y, g);
-  if (st) return st;
-  MMTTA_CHECK(packed != nullptr, MMTTA_ERR_INVALID, "conv: null packed weights");
-  st = psets_validate(sets, x->n);
-  if (st) return st;
-  const PSets ps = psets(sets);
-  if (direct_applicable(d)) return direct_conv_run(d, x, x_norm, packed, bias, epi, y, accumulate, stats, ps, (hipStream_t)stream);
-  if (pointwise_small_applicable(d, x, y, stats, epi, x_norm) && !use_bf16(d, g.K) && is_f32(x))      // (y: fp32- or bf16-stored)
-    return pointwise_small_run(x, packed, g.Kp, g.Np, bias, y, accumulate, ps, (hipStream_t)stream);
-  if (chan_applicable(d, x, y) && !use_bf16(d, g.K))
-    return chan_conv_run(d, x, x_norm, packed, g.Kp, g.Np, bias, epi, y, accumulate, stats, ps, (hipStream_t)stream);
-  {  // 1x1x1 over many voxels with bf16 operands, nothing but bias / add / accumulate around it: the streaming kernel
-    static const bool pw_on = !(getenv("MMTTA_POINTWISE_MFMA") && atoi(getenv("MMTTA_POINTWISE_MFMA")) == 0);      // (A/B switch)
-    auto dense = [](const mmtta_tensor* t) { return t->sc == 1 && t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
-    const mmtta_tensor* ad = (epi && epi->add) ? epi->add : nullptr;
-    const bool bfs = is_bf16(x);
-    const long long dhw = (long long)y->d * y->h * y->w;
-    const int kb = (g.K + 15) / 16;
-    auto rows_ok = [&](const mmtta_tensor* t) {
-      return dense(t) && is_bf16(t) == bfs && ((uintptr_t)t->ptr) % 16 == 0 && t->sw % (bfs ? 8 : 4) == 0 && t->sn % (bfs ? 8 : 4) == 0 &&
-             dhw * t->sw < (1LL << 31);
-    };
-    const bool pw = pw_on && d->ksize == 1 && (d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONV_DGRAD) && use_bf16(d, g.K) &&
-                    (kb <= 4 || kb == 6 || kb == 8) && g.Np <= 64 && stats == nullptr && !(x_norm && (x_norm->mean || x_norm->scale)) &&
-                    dhw >= 4096 && rows_ok(x) && rows_ok(y) && (ad == nullptr || (rows_ok(ad) && ad->n == y->n && ad->c == y->c && ad->d == y->d && ad->h == y->h && ad->w == y->w));
-    if (pw) {
-      PWArgs q;
-      q.in = (const float*)x->ptr; q.isn = x->sn; q.isw = (unsigned)x->sw; q.Ci = x->c;
-      q.out = (float*)y->ptr; q.osn = y->sn; q.osw = (unsigned)y->sw; q.Co = y->c;
-      q.add = ad ? (const float*)ad->ptr : nullptr; q.asn = ad ? ad->sn : 0; q.asw = ad ? (unsigned)ad->sw : 0u;
-      q.tadd = ad ? nl(&epi->add_norm) : nl(nullptr);
-      q.wp = (const float*)packed; q.bias = bias; q.Np = g.Np; q.ps = ps; q.accumulate = accumulate; q.dhw = dhw;
-      long long blocks = (dhw + 127) / 128;
-      if (blocks > 2048) blocks = 2048;
-      const dim3 grid((unsigned)blocks, y->n);
-      if (bfs) launch_pointwise_mfma<true>(q, kb, g.Np / 32, grid, (hipStream_t)stream);
-      else launch_pointwise_mfma<false>(q, kb, g.Np / 32, grid, (hipStream_t)stream);
-      return launch_status("1x1 conv (streaming MFMA)");
-    }
-  }
-  const int64_t need = g.ksplit > 1 ? (int64_t)g.ksplit * g.tiles * g.cfg.TZ * g.cfg.TY * g.cfg.TX * g.Np * 4 : 0;
-  MMTTA_CHECK(need == 0 || (workspace != nullptr && workspace_bytes >= need), MMTTA_ERR_WORKSPACE,
-              "conv: workspace %lld bytes, need %lld", (long long)workspace_bytes, (long long)need);
-  GArgs a;
+struct ConvCall {      // the operands of a call, as conv_run_body received them
+  const mmtta_conv_desc* d; const mmtta_tensor* x; const mmtta_norm_on_load* x_norm; const void* packed; const float* bias;
+  const mmtta_conv_epilogue* epi; const mmtta_tensor* y; int accumulate; float* stats; void* workspace; int64_t workspace_bytes;
+  PSets ps; hipStream_t stream;
+};
+
+// ---- one launcher per family of this file (direct_conv_run, chan_conv_run, pointwise_small_run: conv_direct.hip)
+// GArgs and the tap tables of a call: what igemm_kernel and igemm_cls8_kernel share
+static int fill_gargs(const ConvCall& c, const Geometry& g, GArgs& a, Taps* ht) {
+  const mmtta_tensor *x = c.x, *y = c.y, *ad = (c.epi && c.epi->add) ? c.epi->add : nullptr;
   a.in = (const float*)x->ptr; a.isn = x->sn; a.isd = x->sd; a.ish = x->sh; a.isw = x->sw;
-  a.Ci = x->c; a.Di = x->d; a.Hi = x->h; a.Wi = x->w;
-  a.tin = nl(x_norm);
+  a.Ci = x->c; a.Di = x->d; a.Hi = x->h; a.Wi = x->w; a.tin = nl(c.x_norm);
   a.out = (float*)y->ptr; a.osn = y->sn; a.osd = y->sd; a.osh = y->sh; a.osw = y->sw;
   a.Co = y->c; a.Do = y->d; a.Ho = y->h; a.Wo = y->w;
-  a.si = g.si;
-  a.wp = (const float*)packed; a.Kp = g.Kp; a.Np = g.Np;
-  a.bias = bias;
-  a.ps = ps;
-  a.add = nullptr; a.asn = a.asd = a.ash = a.asw = 0; a.tadd = nl(nullptr);
-  if (epi && epi->add) {
-    const mmtta_tensor* ad = epi->add;
-    MMTTA_CHECK(ad->ptr && is_cl(ad) && ad->n == y->n && ad->c == y->c && ad->d == y->d && ad->h == y->h && ad->w == y->w,
-                MMTTA_ERR_INVALID, "conv: epilogue `add` must be channels-last with the shape of y");
-    a.add = (const float*)ad->ptr; a.asn = ad->sn; a.asd = ad->sd; a.ash = ad->sh; a.asw = ad->sw;
-    a.tadd = nl(&epi->add_norm);
-  }
-  a.accumulate = accumulate;
-  a.in_bf = is_bf16(x) ? 1 : 0;
-  a.out_bf = is_bf16(y) ? 1 : 0;
-  a.add_bf = (epi && epi->add && is_bf16(epi->add)) ? 1 : 0;
-  {
-    const bool oal = quad_aligned(y, quad_bytes(y)) && y->c % 4 == 0 &&                                    // 4-channel accesses
-                     (!(epi && epi->add) || quad_aligned(epi->add, quad_bytes(epi->add))) &&
-                     (bias == nullptr || ((uintptr_t)bias) % 16 == 0);
-    a.ovec = (oal && g_epilogue_vec) ? 1 : 0;
-  }
-  const int srt = stats_rows_per_tile(g);
-  a.stats = stats; a.stats_rows_per_n = g.ncls * g.tiles_per_n * srt;
-  a.ws = (float*)workspace; a.ksplit = g.ksplit; a.stages_per_split = g.sps; a.nstages = g.nstages;
+  a.si = g.si; a.bias = c.bias; a.ps = c.ps; a.accumulate = c.accumulate;
+  a.wp = (const float*)c.packed; a.Kp = g.Kp; a.Np = g.Np;
+  const int st = epilogue_add(c.epi, y, a);
+  if (st) return st;
+  a.in_bf = is_bf16(x) ? 1 : 0; a.out_bf = is_bf16(y) ? 1 : 0; a.add_bf = (ad && is_bf16(ad)) ? 1 : 0;
+  const bool oal = quad_aligned(y, quad_bytes(y)) && y->c % 4 == 0 &&                                    // 4-channel accesses
+                   (!ad || quad_aligned(ad, quad_bytes(ad))) && (c.bias == nullptr || ((uintptr_t)c.bias) % 16 == 0);
+  a.ovec = (oal && g_epilogue_vec) ? 1 : 0;
+  a.stats = c.stats; a.stats_rows_per_n = g.ncls * g.tiles_per_n * stats_rows_per_tile(g);
+  a.ws = (float*)c.workspace; a.ksplit = g.ksplit; a.stages_per_split = g.sps; a.nstages = g.nstages;
   a.tz = g.tz; a.ty = g.ty; a.tx = g.tx;
   MMTTA_CHECK(g.cfg.bf || (!a.in_bf && !a.out_bf && !a.add_bf), MMTTA_ERR_UNSUPPORTED,
               "conv: bf16-stored tensors need a bf16-operand layer (K >= 16 in bf16 precision)");
   // 8-channel items: 32 bytes of fp32 (two 16-byte loads) or 16 bytes of bf16 (one): strides must keep them aligned
-  const int am = a.in_bf ? 8 : 4;
-  const bool al = (((uintptr_t)x->ptr) % 16 == 0) && x->sw % am == 0 && x->sh % am == 0 && x->sd % am == 0 && x->sn % am == 0;
-  a.vec4 = al ? 1 : 0;
-  a.flip27 = 0;
-  {  // row-structured loader of the 3x3x3 stride-1 stages: 32-bit element offsets from 24-bit multiply-adds
-    const int64_t lim24 = (int64_t)1 << 24;
-    const int64_t last = (int64_t)(x->d - 1) * x->sd + (int64_t)(x->h - 1) * x->sh + (int64_t)(x->w - 1) * x->sw + x->c + 16;
-    a.rowload = (al && x->sd < lim24 && x->sh < lim24 && x->sw < lim24 && x->d < lim24 && x->h < lim24 && x->w < lim24 &&
-                 last < ((int64_t)1 << 31) && g_igemm_pipeline) ? 1 : 0;
-  }
-  Taps ht[8];
-  a.ncls = g.classes ? 8 : 1;
-  a.so = g.classes ? 2 : 1;
+  const bool al = quad_aligned(x, 16, a.in_bf ? 8 : 4);
+  a.vec4 = al ? 1 : 0; a.flip27 = 0;
+  // row-structured loader of the 3x3x3 stride-1 stages: 32-bit element offsets from 24-bit multiply-adds
+  const int64_t lim24 = (int64_t)1 << 24;
+  a.rowload = (al && strides_fit_24(x) && x->d < lim24 && x->h < lim24 && x->w < lim24 && item_fits_31(x, x->c + 16) &&
+               g_igemm_pipeline) ? 1 : 0;
+  a.ncls = g.classes ? 8 : 1; a.so = g.classes ? 2 : 1;
   int tap0 = 0;
   for (int cls = 0; cls < a.ncls; ++cls) {
     const int pz = (cls >> 2) & 1, py = (cls >> 1) & 1, px = cls & 1;
-    build_taps(d, pz, py, px, ht[cls]);
+    build_taps(c.d, pz, py, px, ht[cls]);
     ClassInfo& ci = a.cls[cls];
     ci.tap0 = tap0; ci.ntaps = ht[cls].n; tap0 += ht[cls].n;
     ci.zmin = ht[cls].zmin; ci.ymin = ht[cls].ymin; ci.xmin = ht[cls].xmin;
@@ -2049,14 +2032,72 @@ int conv_run_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
       ci.Dg = y->d; ci.Hg = y->h; ci.Wg = y->w;
     }
   }
-  if (g.fused) {
-    MMTTA_CHECK(a.ovec && a.vec4, MMTTA_ERR_UNSUPPORTED,
-                "conv (class-fused stride-2 form): the epilogue operands must admit 16-byte accesses");
-    MMTTA_CHECK(a.in_bf == a.out_bf && (a.add == nullptr || a.add_bf == a.out_bf), MMTTA_ERR_UNSUPPORTED,
-                "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf, a.add_bf);
-    return a.in_bf ? launch_cls8_t<16, true>(a, g.tiles, (hipStream_t)stream) : launch_cls8_t<16, false>(a, g.tiles, (hipStream_t)stream);
+  return MMTTA_OK;
+}
+
+static int igemm_run(const ConvCall& c, const Geometry& g) {
+  MMTTA_CHECK(g.workspace_bytes == 0 || (c.workspace != nullptr && c.workspace_bytes >= g.workspace_bytes), MMTTA_ERR_WORKSPACE,
+              "conv: workspace %lld bytes, need %lld", (long long)c.workspace_bytes, (long long)g.workspace_bytes);
+  GArgs a; Taps ht[8];
+  const int st = fill_gargs(c, g, a, ht);
+  if (st) return st;
+  return launch_any(g.route, a, ht, g.tiles, c.stream);
+}
+
+static int cls_fused_run(const ConvCall& c, const Geometry& g) {
+  GArgs a; Taps ht[8];
+  const int st = fill_gargs(c, g, a, ht);
+  if (st) return st;
+  MMTTA_CHECK(a.ovec && a.vec4, MMTTA_ERR_UNSUPPORTED,
+              "conv (class-fused stride-2 form): the epilogue operands must admit 16-byte accesses");
+  MMTTA_CHECK(a.in_bf == a.out_bf && (a.add == nullptr || a.add_bf == a.out_bf), MMTTA_ERR_UNSUPPORTED,
+              "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf, a.add_bf);
+  return a.in_bf ? launch_cls8_t<16, true>(a, g.tiles, c.stream) : launch_cls8_t<16, false>(a, g.tiles, c.stream);
+}
+
+static int pointwise_mfma_run(const ConvCall& c, const Geometry& g) {
+  const mmtta_tensor *x = c.x, *y = c.y, *ad = (c.epi && c.epi->add) ? c.epi->add : nullptr;
+  PWArgs q;
+  q.in = (const float*)x->ptr; q.isn = x->sn; q.isw = (unsigned)x->sw; q.Ci = x->c;
+  q.out = (float*)y->ptr; q.osn = y->sn; q.osw = (unsigned)y->sw; q.Co = y->c;
+  q.add = ad ? (const float*)ad->ptr : nullptr; q.asn = ad ? ad->sn : 0; q.asw = ad ? (unsigned)ad->sw : 0u;
+  q.tadd = ad ? nl(&c.epi->add_norm) : nl(nullptr);
+  q.wp = (const float*)c.packed; q.bias = c.bias; q.Np = g.Np; q.ps = c.ps; q.accumulate = c.accumulate;
+  q.dhw = (long long)y->d * y->h * y->w;
+  long long blocks = (q.dhw + 127) / 128;
+  if (blocks > 2048) blocks = 2048;
+  const dim3 grid((unsigned)blocks, y->n);
+  if (is_bf16(x)) launch_pointwise_mfma<true>(q, (g.K + 15) / 16, g.Np / 32, grid, c.stream);
+  else launch_pointwise_mfma<false>(q, (g.K + 15) / 16, g.Np / 32, grid, c.stream);
+  return launch_status("1x1 conv (streaming MFMA)");
+}
+
+// The plan of a run: the one function behind mmtta_conv_route and conv_run_body
+static int plan_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
+                    const mmtta_tensor* y, int accumulate, const float* stats, Geometry& g) {
+  const RunFacts rt{stats, epi ? epi->add : nullptr, x_norm, accumulate};
+  return geometry(d, x, y, &rt, g);
+}
+
+// mmtta_conv_run_sets past the checks of its norm-on-load descriptors: plan, check, switch
+int conv_run_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
+                  const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
+                  void* workspace, int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
+  Geometry g;
+  int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, g);
+  if (st) return st;
+  MMTTA_CHECK(packed != nullptr, MMTTA_ERR_INVALID, "conv: null packed weights");
+  st = psets_validate(sets, x->n);
+  if (st) return st;
+  const ConvCall c{d, x, x_norm, packed, bias, epi, y, accumulate, stats, workspace, workspace_bytes, psets(sets), (hipStream_t)stream};
+  switch (g.route) {
+    case C_DIRECT: return direct_conv_run(d, x, x_norm, packed, bias, epi, y, accumulate, stats, c.ps, c.stream);
+    case C_PW_SMALL: return pointwise_small_run(x, packed, g.Kp, g.Np, bias, y, accumulate, c.ps, c.stream);
+    case C_THIN: return chan_conv_run(d, x, x_norm, packed, g.Kp, g.Np, bias, epi, y, accumulate, stats, c.ps, c.stream);
+    case C_PW_MFMA: return pointwise_mfma_run(c, g);
+    case C_CLS_FUSED: return cls_fused_run(c, g);
+    default: return igemm_run(c, g);
   }
-  return launch_any(g.cfg, a, ht, g.tiles, (hipStream_t)stream);
 }
 
 MMTTA_ACT_NS_CLOSE
@@ -2064,46 +2105,6 @@ MMTTA_ACT_NS_CLOSE
 
 #ifndef MMTTA_ACT_LEAKY_TU
 using namespace mmtta;
-
-extern "C" int64_t mmtta_conv_packed_bytes(const mmtta_conv_desc* d) {
-  if (validate_desc(d)) return -1;
-  int K, N, si; bool cl;
-  op_dims(d, K, N, si, cl);
-  const int T = d->ksize * d->ksize * d->ksize;
-  if (direct_applicable(d)) return (int64_t)T * K * 4 * (int64_t)sizeof(float) + upconv8_image_bytes(d);
-  return (int64_t)T * roundup(K, 32) * roundup(N, 32) * (int64_t)(use_bf16(d, K) ? 2 : sizeof(float)) + chan_frag_bytes(d);
-}
-
-extern "C" int mmtta_conv_pack_weights(const mmtta_conv_desc* d, const float* w, void* packed, void* stream) {
-  int st = validate_desc(d);
-  if (st) return st;
-  MMTTA_CHECK(w && packed, MMTTA_ERR_INVALID, "pack: null pointer");
-  int K, N, si; bool cl;
-  op_dims(d, K, N, si, cl);
-  const int T = d->ksize * d->ksize * d->ksize;
-  const bool convt = d->op == MMTTA_CONVT_FWD || d->op == MMTTA_CONVT_DGRAD;
-  const int A = convt ? d->cin : d->cout, B = convt ? d->cout : d->cin;
-  // K,N in terms of (A,B): CONV_FWD K=cin=B ; CONV_DGRAD K=cout=A ; CONVT_FWD K=cin=A ; CONVT_DGRAD K=cout=B
-  const int kn_is_ba = (d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONVT_DGRAD) ? 1 : 0;
-  const bool direct = direct_applicable(d);
-  const int Kp = direct ? K : roundup(K, 32), Np = direct ? 4 : roundup(N, 32);
-  const long long total = (long long)T * Kp * Np;
-  int blocks = (int)((total + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  if (use_bf16(d, K))
-    hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)packed,
-                       A, B, T, Kp, Np, kn_is_ba);
-  else
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, (float*)packed, A, B, T,
-                       Kp, Np, kn_is_ba);
-  if (direct && upconv8_image_bytes(d) > 0)       // ConvTranspose3d K -> R: + the gather-GEMM image behind the tap image
-    hipLaunchKernelGGL(pack_upconv8_kernel, dim3((K * 4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
-                       (unsigned short*)((char*)packed + (size_t)T * Kp * Np * 4), K, N);
-  if (!direct && chan_frag_bytes(d) > 0)          // thin-K convolution: + its B fragments behind the fp32 tap image
-    hipLaunchKernelGGL(pack_chan_frags_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)packed,
-                       (uint4*)((char*)packed + (size_t)T * Kp * Np * 4), Kp, Np, K, N);
-  return launch_status("pack weights");
-}
 
 // the geometry of an entry (every field but the pointers); up8 / chfr: whether those images follow the tap image
 static int pack_entry_geometry(const mmtta_conv_desc* d, PackEntry& e, bool& up8, bool& chfr) {
@@ -2117,10 +2118,11 @@ static int pack_entry_geometry(const mmtta_conv_desc* d, PackEntry& e, bool& up8
   e.A = convt ? d->cin : d->cout; e.B = convt ? d->cout : d->cin;
   e.T = d->ksize * d->ksize * d->ksize;
   e.Kp = direct ? K : roundup(K, 32); e.Np = direct ? 4 : roundup(N, 32);
+  // K,N in terms of (A,B): CONV_FWD K=cin=B ; CONV_DGRAD K=cout=A ; CONVT_FWD K=cin=A ; CONVT_DGRAD K=cout=B
   e.kn_is_ba = (d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONVT_DGRAD) ? 1 : 0;
   e.bf16 = use_bf16(d, K) ? 1 : 0; e.direct = direct ? 1 : 0;
-  up8 = direct && upconv8_image_bytes(d) > 0;
-  chfr = !direct && chan_frag_bytes(d) > 0;
+  up8 = direct && upconv8_image_bytes(d) > 0;       // ConvTranspose3d K -> R: + the gather-GEMM image behind the tap image
+  chfr = !direct && chan_frag_bytes(d) > 0;         // thin-K convolution: + its B fragments behind the fp32 tap image
   e.KI = K; e.NO = N;
   MMTTA_CHECK(e.T == 1 || e.T == 27, MMTTA_ERR_UNSUPPORTED, "pack: ksize %d", d->ksize);
   e.start = 0;
@@ -2136,6 +2138,34 @@ static int fill_pack_entry(const mmtta_conv_desc* d, const float* w, void* packe
   e.up8 = up8 ? (unsigned short*)((char*)packed + (size_t)e.T * e.Kp * e.Np * 4) : nullptr;
   e.chfr = chfr ? (uint4*)((char*)packed + (size_t)e.T * e.Kp * e.Np * 4) : nullptr;
   return MMTTA_OK;
+}
+
+extern "C" int64_t mmtta_conv_packed_bytes(const mmtta_conv_desc* d) {
+  PackEntry e;
+  bool up8, chfr;
+  if (pack_entry_geometry(d, e, up8, chfr)) return -1;
+  return (int64_t)e.T * e.Kp * e.Np * (int64_t)(e.bf16 ? 2 : sizeof(float)) + (e.direct ? upconv8_image_bytes(d) : chan_frag_bytes(d));
+}
+
+extern "C" int mmtta_conv_pack_weights(const mmtta_conv_desc* d, const float* w, void* packed, void* stream) {
+  PackEntry e;
+  int st = fill_pack_entry(d, w, packed, e);
+  if (st) return st;
+  const long long total = (long long)e.T * e.Kp * e.Np;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  if (e.bf16)
+    hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, (unsigned short*)packed,
+                       e.A, e.B, e.T, e.Kp, e.Np, e.kn_is_ba);
+  else
+    hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, (float*)packed, e.A, e.B, e.T,
+                       e.Kp, e.Np, e.kn_is_ba);
+  if (e.up8)
+    hipLaunchKernelGGL(pack_upconv8_kernel, dim3((e.KI * 4 + 255) / 256), dim3(256), 0, (hipStream_t)stream, w, e.up8, e.KI, e.NO);
+  if (e.chfr)
+    hipLaunchKernelGGL(pack_chan_frags_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)packed, e.chfr, e.Kp,
+                       e.Np, e.KI, e.NO);
+  return launch_status("pack weights");
 }
 
 namespace mmtta {
@@ -2183,37 +2213,18 @@ extern "C" int mmtta_conv_plan(const mmtta_conv_desc* d, const mmtta_tensor* x, 
                                mmtta_conv_plan_t* plan) {
   MMTTA_CHECK(plan != nullptr, MMTTA_ERR_INVALID, "conv plan: null plan");
   Geometry g;
-  int st = geometry(d, x, y, g);
+  int st = geometry(d, x, y, nullptr, g);
   if (st) return st;
-  if (direct_applicable(d)) {
-    plan->tiles = direct_blocks_per_n(d, x, y) * y->n;
-    plan->launches = 1;
-    plan->ksplit = 1;
-    plan->stats_rows = plan->tiles;
-    plan->config = 6;
-    plan->_pad = 0;
-    plan->workspace_bytes = 0;
-    return MMTTA_OK;
-  }
-  if (chan_applicable(d, x, y) && !use_bf16(d, g.K)) {
-    plan->tiles = chan_tiles_per_n(y) * y->n;
-    plan->launches = 1;
-    plan->ksplit = 1;
-    plan->stats_rows = plan->tiles;
-    plan->config = 13;
-    plan->_pad = 0;
-    plan->workspace_bytes = 0;
-    return MMTTA_OK;
-  }
-  plan->tiles = g.tiles;
-  plan->launches = g.launches;
-  plan->ksplit = g.ksplit;
-  plan->stats_rows = g.tiles * stats_rows_per_tile(g);
-  plan->config = g.fused ? 15 : config_id(g.cfg);
-  plan->_pad = 0;
-  plan->workspace_bytes =
-      g.ksplit > 1 ? (int64_t)g.ksplit * g.tiles * g.cfg.TZ * g.cfg.TY * g.cfg.TX * g.Np * (int64_t)sizeof(float) : 0;
+  *plan = mmtta_conv_plan_t{g.tiles, /*launches*/ 1, g.ksplit, g.stats_rows, g.route, 0, g.workspace_bytes};
   return MMTTA_OK;
+}
+
+extern "C" int mmtta_conv_route(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
+  Geometry g;
+  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, g);
+  if (st) return st < 0 ? st : -st;
+  return g.route;
 }
 
 extern "C" int mmtta_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,

@@ -1004,10 +1004,6 @@ static inline bool vec4_wr(const mmtta_tensor* t) {
   return vec4_rd(t) && (t->c % 4 == 0 || (t->flags & MMTTA_TENSOR_OWNS_PAD));
 }
 
-static inline bool same_shape(const mmtta_tensor* a, const mmtta_tensor* b) {
-  return a->n == b->n && a->c == b->c && a->d == b->d && a->h == b->h && a->w == b->w;
-}
-
 static void rows_geometry(const mmtta_tensor* t, int& rows_per_n, long long& vox_per_row) {
   const long long dhw = (long long)t->d * t->h * t->w;
   long long vpr = (dhw + 1023) / 1024;     // at most 1024 rows per batch item

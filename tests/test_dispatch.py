@@ -135,3 +135,118 @@ def test_class_fused_kernel_is_planned_for_large_stride2_forms():
         assert int(plan.config) == want, (cin, cout, transposed, coarse, int(plan.config))
         if want == 15:
             assert plan.ksplit == 1 and plan.stats_rows == (d // 4) * (h // 4) * (w // 8)
+
+
+def _t(base, c, dhw, dtype=0, n=1, row_pad=0, gap=0):
+    """A channels-last descriptor at a synthetic address (the planner never reads tensor memory): voxel rows of c rounded up
+    to 4 elements (8 for a bf16-stored tensor of more than 4 channels) plus `row_pad`, x-rows `gap` elements apart."""
+    from multimodal_tta_amd._lib import Tensor
+    d, h, w = dhw
+    sw = ((c + 3) // 4 * 4 if (dtype == 0 or c <= 4) else (c + 7) // 8 * 8) + row_pad
+    sh = w * sw + gap
+    return Tensor(base, n, c, d, h, w, d * h * sh, 1, h * sh, sh, sw, dtype, 0)
+
+
+def _route(lib, dsc, x, y, stats=None, add=None, norm=None, accumulate=0):
+    from multimodal_tta_amd._lib import ConvEpilogue, NormOnLoadAct
+    epi = ConvEpilogue(C.pointer(add), NormOnLoadAct()) if add is not None else None
+    return int(lib.mmtta_conv_route(C.byref(dsc), C.byref(x), C.byref(norm) if norm is not None else None,
+                                    C.byref(epi) if epi is not None else None, C.byref(y), accumulate, stats))
+
+
+def _config(lib, dsc, x, y):
+    from multimodal_tta_amd._lib import ConvPlan
+    plan = ConvPlan()
+    assert lib.mmtta_conv_plan(C.byref(dsc), C.byref(x), C.byref(y), C.byref(plan)) == 0
+    return int(plan.config)
+
+
+def test_every_route_is_reached_and_run_time_operands_flip_only_the_two_pointwise_routes():
+    """mmtta_conv_route names the kernel a run launches (csrc/conv_igemm.hip::CRoute, the function conv_run_body itself asks).
+    Without run-time operands it is mmtta_conv_plan's config for every parity shape of DISPATCH; the two 1x1x1 routes that
+    mmtta_conv_plan cannot see are expected from the gates of the commit before the planner existed (cb18d86):
+      16  conv_run_body, csrc/conv_igemm.hip:1952 - pointwise_small_applicable (csrc/conv_direct.hip:1382-1389: k1 s1, no
+          statistics, no add, no norm-on-load, <= 4 fp32 channels read from 16-byte-aligned rows, y.c % 4 == 0) and fp32 operands;
+      17  conv_run_body, csrc/conv_igemm.hip:1957-1969 - k1 forward / input gradient with bf16 operands, K / 16 in
+          {1, 2, 3, 4, 6, 8}, Np <= 64, no statistics, no norm-on-load, d * h * w >= 4096, x / y / add voxel-dense with 16-byte
+          rows in one storage type."""
+    from multimodal_tta_amd import _lib, ops
+    from multimodal_tta_amd._lib import BF16, CONV_DGRAD, CONV_FWD, CONVT_DGRAD, CONVT_FWD, F32, ConvDesc, NormOnLoad
+
+    lib = _lib.load()
+    ops.tune_for_volumes_in_flight(4)
+    X, Y, A, STATS = 1 << 30, 1 << 40, 1 << 41, 1 << 20
+    seen = set()
+    for case, want_f32, want_bf16, _ in DISPATCH:
+        cin, cout, k, stride, transposed, (n, d, h, w) = case
+        fine = (2 * d, 2 * h, 2 * w) if transposed else ((d, h, w) if stride == 1 else ((d + 1) // 2, (h + 1) // 2, (w + 1) // 2))
+        tx, ty = _t(X, cin, (d, h, w), n=n), _t(Y, cout, fine, n=n)
+        fo, do = (CONVT_FWD, CONVT_DGRAD) if transposed else (CONV_FWD, CONV_DGRAD)
+        for dtype, want in ((F32, want_f32), (BF16, want_bf16)):
+            for lean in ((1, 0) if dtype == BF16 and 14 in want else (1,)):
+                prev = lib.mmtta_set_option(10, lean)
+                try:
+                    for op, a, b, cfg in ((fo, tx, ty, want[0]), (do, ty, tx, want[1])):
+                        dsc = ConvDesc(op, k, stride, cin, cout, dtype)
+                        r = _route(lib, dsc, a, b)
+                        assert r == _config(lib, dsc, a, b) == (7 if (cfg == 14 and not lean) else cfg), (case, dtype, op, r)
+                        assert r == _route(lib, dsc, a, b, accumulate=1), "no gate reads `accumulate`"
+                        seen.add(r)
+                finally:
+                    lib.mmtta_set_option(10, prev)
+    # 15: test_class_fused_kernel_is_planned_for_large_stride2_forms
+    dsc = ConvDesc(CONVT_FWD, 3, 2, 128, 32, BF16)
+    lo, hi = _t(X, 128, (32, 32, 32)), _t(Y, 32, (64, 64, 64))
+    assert _route(lib, dsc, lo, hi) == _config(lib, dsc, lo, hi) == 15
+    seen.add(15)
+
+    # 16: the input gradient of a 32 -> 3 1x1x1 head; x = dy has 3 channels, y = dx has 32
+    for dtype in (F32, BF16):                      # K = 3 < 16: fp32 operands whatever desc.dtype says
+        dsc = ConvDesc(CONV_DGRAD, 1, 1, 32, 3, dtype)
+        dy, dx = _t(X, 3, (8, 8, 8)), _t(Y, 32, (8, 8, 8))
+        assert _config(lib, dsc, dy, dx) == 0      # the fp32 igemm of the shape, tile <1,4,8,8,8,8>
+        assert _route(lib, dsc, dy, dx) == 16
+        assert _route(lib, dsc, dy, _t(Y, 32, (8, 8, 8), BF16)) == 16, "dx may be a bf16-stored gradient"
+        assert _route(lib, dsc, dy, dx, stats=STATS) == 0
+        assert _route(lib, dsc, dy, dx, add=_t(A, 32, (8, 8, 8))) == 0
+        assert _route(lib, dsc, dy, dx, norm=NormOnLoad(mean=1 << 21, rstd=1 << 22)) == 0
+        assert _route(lib, dsc, _t(X + 4, 3, (8, 8, 8)), dx) == 0, "dy off its 16-byte rows"
+    seen.add(16)
+
+    # 17: a bf16 64 -> 32 1x1x1 forward on voxel-dense tensors at 16^3, bf16- or fp32-stored
+    dsc, e16, e8 = ConvDesc(CONV_FWD, 1, 1, 64, 32, BF16), (16, 16, 16), (8, 8, 8)
+    for st in (BF16, F32):
+        x, y = _t(X, 64, e16, st), _t(Y, 32, e16, st)
+        assert _config(lib, dsc, x, y) == 14       # the lean bf16 igemm of the shape
+        assert _route(lib, dsc, x, y) == 17
+        assert _route(lib, dsc, x, y, add=_t(A, 32, e16, st)) == 17
+        assert _route(lib, dsc, x, y, accumulate=1) == 17
+        assert _route(lib, dsc, _t(X, 64, e8, st), _t(Y, 32, e8, st)) == 14, "d * h * w < 4096"
+        assert _route(lib, dsc, x, y, stats=STATS) == 14
+        assert _route(lib, dsc, x, y, norm=NormOnLoad(scale=1 << 21, shift=1 << 22)) == 14
+        assert _route(lib, dsc, _t(X, 64, e16, st, row_pad=1), y) == 14, "ragged voxel row: no 16-byte items"
+        assert _route(lib, dsc, x, _t(Y, 32, e16, st, gap=32)) == 14, "a gap between x-rows: not voxel-dense"
+        assert _route(lib, dsc, x, y, add=_t(A, 32, e16, BF16 + F32 - st)) == 14, "add in the other storage type"
+        assert _route(lib, dsc, x, _t(Y, 32, e16, BF16 + F32 - st)) == 14, "x and y in different storage types"
+    assert _route(lib, ConvDesc(CONV_FWD, 1, 1, 64, 32, F32), _t(X, 64, e16), _t(Y, 32, e16)) == 0, "fp32 operands"
+    seen.add(17)
+    assert seen == set(range(18)), f"routes never asked for: {sorted(set(range(18)) - seen)}"
+    # argument errors come back as negative status codes, as from mmtta_conv_wgrad_kernel
+    assert _route(lib, ConvDesc(CONV_FWD, 5, 1, 32, 32, F32), _t(X, 32, e8), _t(Y, 32, e8)) == -2
+    assert _route(lib, ConvDesc(CONV_FWD, 3, 1, 32, 32, F32), _t(X, 16, e8), _t(Y, 32, e8)) == -1
+
+
+def test_streaming_pointwise_switch_is_read_from_the_environment():
+    """MMTTA_POINTWISE_MFMA=0 (read once per process: a fresh child) sends route 17's calls to the implicit GEMM."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import ctypes as C\n"
+            "from multimodal_tta_amd import _lib\n"
+            "T = lambda base, c: _lib.Tensor(base, 1, c, 16, 16, 16, 4096 * c, 1, 256 * c, 16 * c, c, _lib.BF16, 0)\n"
+            "d, x, y = _lib.ConvDesc(_lib.CONV_FWD, 1, 1, 64, 32, _lib.BF16), T(1 << 30, 64), T(1 << 40, 32)\n"
+            "print(_lib.load().mmtta_conv_route(C.byref(d), C.byref(x), None, None, C.byref(y), 0, None))\n")
+    env = dict(os.environ, MMTTA_POINTWISE_MFMA="0")          # (unset: 17, asserted in-process by the test above)
+    out = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, check=True)
+    assert out.stdout.split()[-1] == "14", (out.stdout, out.stderr)
