@@ -779,6 +779,29 @@ int mmtta_dice_ce_grad(const mmtta_tensor* logits, const mmtta_tensor* label, co
                        int softmax, int jaccard, int include_background, float lambda_dice, float lambda_ce, float smooth_nr,
                        float smooth_dr, const double* sums, const mmtta_tensor* dlogits, void* stream);
 
+/* Calibration of the evaluation tail: a reliability histogram with Brier and NLL sums per (volume, region), from the
+ * logits and the label in one pass.
+ *   logits  fp32, any strides (the channels-last view of <= 4 channels in 16-byte voxel rows is read 16 bytes wide; its
+ *           pad lanes are never used);  label  fp32, any strides, ground truth = label > 0.5;  bins in [1, 64]
+ *   out     fp64 [N][Rout][3 * bins + 2], written whole by the call: per bin (element count, sum of confidence,
+ *           correct count), then the Brier sum, then the NLL sum.  Counts are exact integers.
+ * softmax == 0 (R <= 256, Rout = R): every (voxel, region) is a Bernoulli element.  prediction = z >= 0, confidence
+ *   c = 1 / (1 + exp(-|z|)), correct = (prediction == ground truth), Brier term (sigmoid(z) - y)^2, NLL term
+ *   max(z, 0) - z y + log1p(exp(-|z|)).
+ * softmax != 0 (2 <= R <= 16, Rout = 1; more classes: MMTTA_ERR_UNSUPPORTED): every voxel is one element.  prediction =
+ *   argmax z, label class = argmax of the label channels (lowest index on ties, both), c = 1 / sum_k exp(z_k - z_max),
+ *   Brier term sum_k (p_k - y_k)^2 with y the one-hot label class, NLL term log-sum-exp(z) - z_label.
+ * Bins are the intervals (k/B, (k+1)/B]: index min(B - 1, max(0, (int)ceilf(c * B) - 1)) in fp32.
+ * scope 0: every element.  scope 1 ("union"): only elements whose prediction or ground truth is foreground (sigmoid head:
+ *   of the pair's own region; softmax head: predicted or labelled class != 0).
+ * Everything is summed as integers (confidence in units of 2^-28, exact; Brier terms of 2^-30; NLL terms of 2^-24, one
+ * term saturating at 255 nats), so the table does not depend on scheduling: two calls agree bit for bit, and a batch
+ * gives the tables of its items computed alone.  At most 2^31 - 1 voxels per volume and 65535 volumes per call.
+ * mmtta_calibration_scratch_bytes: 0 (this build needs none; `scratch` may be NULL then), -1 on bad arguments. */
+int64_t mmtta_calibration_scratch_bytes(const mmtta_tensor* logits, int bins);
+int mmtta_calibration_bins(const mmtta_tensor* logits, const mmtta_tensor* label, int softmax, int bins, int scope,
+                           double* out, void* scratch, void* stream);
+
 /* Surface metrics of the evaluation tail: percentile Hausdorff distance and average surface distance per
  * (volume, region).  Replaces the MONAI calls of reference src/evaluation/seg_eval.py:312-340
  * (`HausdorffDistanceMetric(include_background=True, reduction="none", percentile=95, directed=False)` built at

@@ -56,10 +56,63 @@ def dice_iou_from_counts(counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tens
     return dice, iou, valid
 
 
-class RegionAccumulator:
-    """float64 sums / counts per region, overall and per domain (reference seg_eval.py:250-270,363-378)."""
+CALIBRATION_SCOPES = ("volume", "union")
+CALIBRATION_MAX_BINS = 64
 
-    def __init__(self, region_order: Sequence[str], surface: bool = False):
+
+def calibration_config(config: Any) -> Tuple[bool, int, str]:
+    """``evaluation.calibration: {enable, bins, scope}`` -> (enable, bins, scope); off, 15 bins, ``volume`` when absent.
+    A value the kernel cannot take is a ``ValueError`` that names its key, whether the block is enabled or not."""
+    cal = get_config(config, "evaluation.calibration", {}) or {}
+    enable = get_config(cal, "enable", False)
+    if not isinstance(enable, bool):
+        raise ValueError(f"evaluation.calibration.enable must be true or false, got {enable!r}")
+    bins = get_config(cal, "bins", 15)
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= CALIBRATION_MAX_BINS:
+        raise ValueError(f"evaluation.calibration.bins must be an integer in 1 ... {CALIBRATION_MAX_BINS}, got {bins!r}")
+    scope = get_config(cal, "scope", "volume")
+    if scope not in CALIBRATION_SCOPES:
+        raise ValueError(f"evaluation.calibration.scope must be one of {list(CALIBRATION_SCOPES)}, got {scope!r}")
+    return enable, int(bins), str(scope)
+
+
+def calibration_from_bins(table: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The table of ``ops.calibration_bins`` (float64 [..., 3*bins + 2]: per bin count, sum of confidence, correct count;
+    then the Brier sum, then the NLL sum) -> (ece, brier, nll, valid), float64 / bool of the leading shape.
+
+        ECE = sum_b (n_b / n) |correct_b / n_b - conf_b / n_b|,   Brier = sum / n,   NLL = sum / n,   valid = n > 0
+
+    An entry without elements (``scope: union`` where neither the prediction nor the ground truth has foreground) is
+    invalid and reads 0; it stays out of the means like a Dice with an empty ground truth."""
+    t = table.to(torch.float64)
+    bins = (t.shape[-1] - 2) // 3
+    if bins < 1 or 3 * bins + 2 != t.shape[-1]:
+        raise ValueError(f"calibration table rows must hold 3*bins + 2 entries, got {t.shape[-1]}")
+    per = t[..., :3 * bins].reshape(*t.shape[:-1], bins, 3)
+    cnt, conf, cor = per[..., 0], per[..., 1], per[..., 2]
+    n = cnt.sum(-1)
+    valid = n > 0
+    safe = torch.where(valid, n, torch.ones_like(n))
+    # (n_b / n) |correct_b / n_b - conf_b / n_b| = |correct_b - conf_b| / n: an empty bin adds nothing
+    ece = (cor - conf).abs().sum(-1) / safe
+    brier = t[..., 3 * bins] / safe
+    nll = t[..., 3 * bins + 1] / safe
+    zero = torch.zeros_like(n)
+    return torch.where(valid, ece, zero), torch.where(valid, brier, zero), torch.where(valid, nll, zero), valid
+
+
+def calibration_width(bins: int, rout: int) -> int:
+    """Doubles a volume's calibration adds to its table row."""
+    return int(rout) * (3 * int(bins) + 2) if bins else 0
+
+
+class RegionAccumulator:
+    """float64 sums / counts per region, overall and per domain (reference seg_eval.py:250-270,363-378).  ``bins`` > 0
+    adds the calibration figures: ``calibration_regions`` names their rows (default: the regions; ``["all"]`` for a softmax
+    head), ``reliability`` pools the bins of every row."""
+
+    def __init__(self, region_order: Sequence[str], surface: bool = False, bins: int = 0,
+                 calibration_regions: Optional[Sequence[str]] = None):
         self.regions = list(region_order)
         self.surface = bool(surface)
         R = len(self.regions)
@@ -68,10 +121,39 @@ class RegionAccumulator:
         self.tot = [self._z() for _ in range(8)]
         self.dom: Dict[str, List[torch.Tensor]] = defaultdict(lambda: [self._z() for _ in range(8)])
         self.total_loss, self.n_samples = 0.0, 0
+        self.bins = int(bins)
+        self.cal_regions = list(calibration_regions) if calibration_regions is not None else list(self.regions)
+        Rc = len(self.cal_regions)
+        self._zc = lambda: torch.zeros((4, Rc), dtype=torch.float64)         # sum_ece, sum_brier, sum_nll, count
+        self.cal_tot = self._zc()
+        self.cal_dom: Dict[str, torch.Tensor] = defaultdict(self._zc)
+        self.reliability = torch.zeros((Rc, max(self.bins, 0), 3), dtype=torch.float64)
+
+    def add_calibration(self, raw: torch.Tensor, domain: str) -> None:
+        """One volume's table, float64 [Rout, 3*bins + 2] (or flat)."""
+        raw = raw.to(torch.float64).reshape(len(self.cal_regions), 3 * self.bins + 2)
+        ece, brier, nll, valid = calibration_from_bins(raw)
+        ok = valid.to(torch.float64)
+        for acc in (self.cal_tot, self.cal_dom[domain]):
+            acc[0] += ece * ok
+            acc[1] += brier * ok
+            acc[2] += nll * ok
+            acc[3] += ok
+        self.reliability += raw[:, :3 * self.bins].reshape(-1, self.bins, 3)
+
+    def _calibration_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
+        for row, key in enumerate(("ece", "brier", "nll")):
+            means = self._fin(acc[row], acc[3])
+            for name, v in zip(self.cal_regions, means):
+                out[f"{prefix}{name.lower()}_{key}"] = v
+            out[f"{prefix}avg_{key}"] = self._avg(means, acc[3])
 
     def add_row(self, dice: Sequence[float], iou: Sequence[float], valid: Sequence[bool], domain: str,
-                hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None) -> None:
+                hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None,
+                calibration: Optional[torch.Tensor] = None) -> None:
         d = self.dom[domain]
+        if self.bins:
+            self.add_calibration(calibration, domain)
         for c in range(len(self.regions)):
             if bool(valid[c]):
                 dv, iv = float(dice[c]), float(iou[c])
@@ -112,6 +194,8 @@ class RegionAccumulator:
         out["loss"] = float(self.total_loss / max(1, self.n_samples)) if report_loss else 0.0
         if self.surface:        # reference seg_eval.py:424-440
             self._surface_keys(out, "", self.tot)
+        if self.bins:
+            self._calibration_keys(out, "", self.cal_tot)
         for dom in sorted(self.dom.keys()):
             sd, cd, si, ci = self.dom[dom][:4]
             safe = dom if dom != "" else "unknown"
@@ -122,6 +206,8 @@ class RegionAccumulator:
             out[f"dom/{safe}/miou"] = self._avg(dim_, ci)
             if self.surface:    # reference seg_eval.py:459-476
                 self._surface_keys(out, f"dom/{safe}/", self.dom[dom])
+            if self.bins:
+                self._calibration_keys(out, f"dom/{safe}/", self.cal_dom[dom])
         return out
 
     def _surface_keys(self, out: Dict[str, float], prefix: str, acc: List[torch.Tensor]) -> None:
@@ -209,6 +295,12 @@ class SegmentationEvaluationStrategy:
         self.enable_surface = bool(get_config(surf, "enable", False))
         self.asd_symmetric = bool(get_config(surf, "asd_symmetric", False))
         self.loss_fn = DiceCEReport(get_config(self.config, "training.criterion", {}) or {})
+        # ECE / Brier / NLL from a reliability histogram taken on the GPU, off by default.  The head follows
+        # `training.criterion.softmax` as the plugins do: one table row per region, or the single row "all"
+        self.enable_calibration, self.calibration_bins, self.calibration_scope = calibration_config(self.config)
+        self.calibration_softmax = bool(get_config(self.config, "training.criterion.softmax", False))
+        self.calibration_regions = ["all"] if self.calibration_softmax else list(self.region_order)
+        self.last_reliability: Optional[torch.Tensor] = None
         # input pre-pass on the GPU (raw volumes in, the reference's `_normalize_img` applied here instead of in the
         # dataset worker; reference src/datasets/transforms.py:129-223).  The NIfTI datasets of this package hand over
         # raw intensities, so the pre-pass defaults to on for them and to off for the synthetic source (already
@@ -218,6 +310,11 @@ class SegmentationEvaluationStrategy:
         nod = get_config(tcfg, "normalize_on_device", None)
         self.normalize_on_device = (not synthetic) if nod is None else bool(nod)
         self._tcfg = tcfg
+
+    @property
+    def cal_bins(self) -> int:
+        """The bin count as the table helpers take it: 0 = calibration off."""
+        return self.calibration_bins if self.enable_calibration else 0
 
     def prepare_image(self, x: torch.Tensor) -> torch.Tensor:
         if not self.normalize_on_device:
@@ -259,6 +356,14 @@ class SegmentationEvaluationStrategy:
         ops.mask_dice_counts(logits, y, self.threshold, counts, self._mask, logits_channels_last=channels_last)
         return counts.cpu()
 
+    def calibration_launch(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
+        """Queue the reliability histogram of (logits, y) on the current stream -> device table float64 [B, Rout, 3*bins + 2]."""
+        out = torch.empty((y.shape[0], len(self.calibration_regions), 3 * self.calibration_bins + 2), dtype=torch.float64,
+                          device=y.device)
+        ops.calibration_bins(logits, y, self.calibration_bins, out, softmax=self.calibration_softmax,
+                             scope=self.calibration_scope, logits_channels_last=channels_last)
+        return out
+
     def surface_launch(self, mask: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """Queue HD95 / ASD of (mask, y) on the current stream -> device tensors [B,R] as MONAI would return them."""
         return ops.surface_distances(mask, y, self.spacing, 95.0, self.asd_symmetric)
@@ -296,7 +401,7 @@ class SegmentationEvaluationStrategy:
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         model.eval()
         model.to(device)
-        acc = RegionAccumulator(self.region_order, self.enable_surface)
+        acc = RegionAccumulator(self.region_order, self.enable_surface, self.cal_bins, self.calibration_regions)
         rows: List[torch.Tensor] = []
         domain_names: List[str] = []
         n_local = 0
@@ -306,11 +411,13 @@ class SegmentationEvaluationStrategy:
             counts = self.score(logits.float(), y)
             dice, iou, valid = dice_iou_from_counts(counts)
             hd, asd = self.surface(y, counts) if self.enable_surface else (None, None)
+            cal = self.calibration_launch(logits.float(), y).cpu() if self.enable_calibration else None
             domains = as_list_str(batch.get("domain", None), batch_size=x.size(0))
             if world == 1:
                 for i in range(x.size(0)):
                     acc.add_row(dice[i].tolist(), iou[i].tolist(), valid[i].tolist(), domains[i],
-                                hd[i].tolist() if hd is not None else None, asd[i].tolist() if asd is not None else None)
+                                hd[i].tolist() if hd is not None else None, asd[i].tolist() if asd is not None else None,
+                                cal[i] if cal is not None else None)
                 if self.report_loss:
                     acc.add_loss(self.loss_fn(logits.float(), y), x.size(0))
                 continue
@@ -328,15 +435,28 @@ class SegmentationEvaluationStrategy:
                          dice[i].double(), iou[i].double(), valid[i].double()]
                 if self.enable_surface:
                     parts += [hd[i].double(), asd[i].double()]
+                if cal is not None:
+                    parts.append(cal[i].reshape(-1))
                 rows.append(torch.cat(parts))
                 n_local += 1
         if world == 1:
+            if self.enable_calibration:
+                self.last_reliability = acc.reliability
             return acc.metrics(self.report_loss)
-        R = len(self.region_order)
-        table = torch.stack(rows) if rows else torch.empty((0, table_width(R, self.enable_surface)), dtype=torch.float64)
+        table = torch.stack(rows) if rows else torch.empty((0, self._table_width()), dtype=torch.float64)
         table, domain_names = merge_rank_tables(table, domain_names, device)
         self.last_table = table
-        return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface)
+        return self._metrics_of(table, domain_names)
+
+    def _table_width(self) -> int:
+        return table_width(len(self.region_order), self.enable_surface, self.cal_bins, len(self.calibration_regions))
+
+    def _metrics_of(self, table: torch.Tensor, domain_names: Sequence[str]) -> Dict[str, float]:
+        """Metrics of the whole split from its per-volume table (and ``last_reliability`` with calibration on)."""
+        if self.enable_calibration:
+            self.last_reliability = reliability_from_table(table, self.calibration_bins, len(self.calibration_regions))
+        return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface,
+                                  self.cal_bins, self.calibration_regions)
 
 
 # ----------------------------------------------------------------------------- sharding
@@ -345,8 +465,20 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
     return list(range(rank, n_items, world))
 
 
-def table_width(R: int, surface: bool = False) -> int:
-    return 3 + (5 if surface else 3) * R  # index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R])
+def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None) -> int:
+    """index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R]) (, with ``bins`` > 0 the volume's raw
+    calibration table: ``rout`` rows - default R - of 3*bins + 2 doubles)."""
+    return 3 + (5 if surface else 3) * R + calibration_width(bins, R if rout is None else rout)
+
+
+def reliability_from_table(table: torch.Tensor, bins: int, rout: int) -> torch.Tensor:
+    """The pooled reliability diagram of the gathered rows: float64 [rout, bins, 3] = (count, sum of confidence, correct
+    count), summed over the volumes in row order."""
+    out = torch.zeros((rout, bins, 3), dtype=torch.float64)
+    w = calibration_width(bins, rout)
+    for row in table:
+        out += row[row.numel() - w:].to(torch.float64).reshape(rout, 3 * bins + 2)[:, :3 * bins].reshape(rout, bins, 3)
+    return out
 
 
 def gather_table(rows: torch.Tensor, n_items: int, world: int, group=None) -> torch.Tensor:
@@ -413,11 +545,14 @@ def gather_masks(local: Sequence[Tuple[int, torch.Tensor]], device, group=None) 
 
 
 def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_names: Sequence[str],
-                       report_loss: bool, surface: bool = False) -> Dict[str, float]:
+                       report_loss: bool, surface: bool = False, bins: int = 0,
+                       calibration_regions: Optional[Sequence[str]] = None) -> Dict[str, float]:
     """Replay the reference aggregation over gathered rows in volume-index order: the result is
-    identical to a single-process run (float64 sums, order fixed by index)."""
+    identical to a single-process run (float64 sums, order fixed by index).  ``bins`` > 0: the rows end in the raw
+    calibration table of their volume (``table_width``), one row of it per name in ``calibration_regions``."""
     R = len(region_order)
-    acc = RegionAccumulator(region_order, surface)
+    acc = RegionAccumulator(region_order, surface, bins, calibration_regions)
+    cal_w = calibration_width(bins, len(acc.cal_regions))
     for row in table:
         dom = domain_names[int(row[1].item())] if 0 <= int(row[1].item()) < len(domain_names) else ""
         dice = row[3:3 + R].to(torch.float32).tolist()
@@ -425,7 +560,7 @@ def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_
         valid = (row[3 + 2 * R:3 + 3 * R] > 0.5).tolist()
         hd = row[3 + 3 * R:3 + 4 * R].to(torch.float32).tolist() if surface else None
         asd = row[3 + 4 * R:3 + 5 * R].to(torch.float32).tolist() if surface else None
-        acc.add_row(dice, iou, valid, dom, hd, asd)
+        acc.add_row(dice, iou, valid, dom, hd, asd, row[row.numel() - cal_w:] if bins else None)
         if report_loss:
             acc.add_loss(float(row[2].item()), 1)
     return acc.metrics(report_loss)
@@ -543,6 +678,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
             job["loss"] = self.loss_fn.launch(res["logits_cl"], yb, channels_last=True)
         if self.enable_surface:
             job["surface"] = self.surface_launch(mask, yb)
+        if self.enable_calibration:
+            job["calibration"] = self.calibration_launch(res["logits_cl"], yb, channels_last=True)
         return job
 
     def _finish(self, job: Dict[str, Any]) -> List[torch.Tensor]:
@@ -553,12 +690,15 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         losses = self.loss_fn.values_per_volume(job["loss"]) if self.report_loss else [0.0] * B
         if self.enable_surface:
             hd, asd = self.surface_fix(job["surface"][0], job["surface"][1], counts, job["shape"])
+        cal = job["calibration"].cpu() if self.enable_calibration else None
         rows = []
         for b in range(B):
             parts = [torch.tensor([job["index"][b], job["domain_id"][b], losses[b]], dtype=torch.float64),
                      dice[b].double(), iou[b].double(), valid[b].double()]
             if self.enable_surface:
                 parts += [hd[b].double(), asd[b].double()]
+            if cal is not None:
+                parts.append(cal[b].reshape(-1))
             rows.append(torch.cat(parts))
         if self.gather_masks:
             mk = job["mask"].cpu()
@@ -578,7 +718,6 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
             self._setup_lanes(model, device)
         if getattr(self.plugin, "needs_fisher", False):      # (eata_tta with its regulariser on and no estimate yet)
             data_loader = self._provide_fisher(data_loader, device)
-        R = len(self.region_order)
         done: List[Tuple[int, torch.Tensor]] = []          # (submission order, row)
         pending: List[Optional[Dict[str, Any]]] = [None] * self.lanes
         domain_names: List[str] = []
@@ -639,10 +778,10 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         for lane in range(self.lanes):
             flush(lane)
         rows = [row for _, row in sorted(done, key=lambda t: t[0])]
-        table = torch.stack(rows) if rows else torch.empty((0, table_width(R, self.enable_surface)), dtype=torch.float64)
+        table = torch.stack(rows) if rows else torch.empty((0, self._table_width()), dtype=torch.float64)
         if world > 1:
             table, domain_names = merge_rank_tables(table, domain_names, device)
         self.last_table = table
         if self.gather_masks:
             self.last_masks = gather_masks(self.local_masks, device)
-        return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface)
+        return self._metrics_of(table, domain_names)

@@ -1187,6 +1187,31 @@ def dice_ce_grad(logits: torch.Tensor, label_ncdhw: torch.Tensor, weight: Option
                                          stream_ptr()), "dice_ce_grad")
 
 
+CALIBRATION_SCOPES = {"volume": 0, "union": 1}
+
+
+def calibration_bins(logits: torch.Tensor, label_ncdhw: torch.Tensor, bins: int, out: torch.Tensor, softmax: bool = False,
+                     scope: str = "volume", logits_channels_last: bool = False) -> None:
+    """Reliability histogram + Brier / NLL sums of every (volume, region) -> ``out`` fp64 [N, Rout, 3*bins + 2] on the
+    device (include/mmtta.h: mmtta_calibration_bins), queued on the current stream.  Scratch, where the library asks for
+    any, is the lane's ``Workspace``."""
+    if scope not in CALIBRATION_SCOPES:
+        raise MmttaError(f"calibration_bins: scope {scope!r} (one of {sorted(CALIBRATION_SCOPES)})")
+    tz = _desc_any(logits, logits_channels_last)
+    tl = desc_ncdhw(label_ncdhw)
+    rout = 1 if softmax else int(tz.c)
+    if out.dtype != torch.float64 or not out.is_contiguous() or not out.is_cuda or out.numel() != tz.n * rout * (3 * int(bins) + 2):
+        raise MmttaError(f"calibration_bins: `out` must be a dense CUDA float64 [{tz.n}, {rout}, {3 * int(bins) + 2}] tensor, got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    lib = _lib.load()
+    nbytes = int(lib.mmtta_calibration_scratch_bytes(C.byref(tz), int(bins)))
+    if nbytes < 0:
+        check(-1, "calibration_scratch_bytes")
+    scratch = Workspace.get(nbytes, logits.device) if nbytes > 0 else None
+    check(lib.mmtta_calibration_bins(C.byref(tz), C.byref(tl), 1 if softmax else 0, int(bins), CALIBRATION_SCOPES[scope],
+                                     ptr(out), ptr(scratch), stream_ptr()), "calibration_bins")
+
+
 _SURF_SCRATCH: Dict[Tuple, torch.Tensor] = {}    # working set of surface_distances, per (device, size)
 
 
