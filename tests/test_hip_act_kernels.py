@@ -10,6 +10,15 @@ from test_hip_conv import BF16_CASES, CASES, cl, cl_bf16, close, ncdhw, ref_modu
 
 pytestmark = pytest.mark.gpu
 
+
+@pytest.fixture(autouse=True, scope="module")
+def _default_launch_geometry():
+    """The launch-geometry knobs (options 2 - 5 and 12) are process wide and a plugin test that ran earlier may have tuned
+    them: this module runs at the library defaults (4 volumes in flight) and leaves the knobs as it found them."""
+    import conv_geometry
+    with conv_geometry.pinned(conv_geometry.inflight_values(4)):
+        yield
+
 SLOPES = [0.01, 0.2, -0.3, 1.5]
 
 

@@ -9,6 +9,15 @@ from test_hip_conv import test_conv_bf16_operands, test_conv_bf16_stored_activat
 
 pytestmark = pytest.mark.gpu
 
+
+@pytest.fixture(autouse=True, scope="module")
+def _default_launch_geometry():
+    """The launch-geometry knobs (options 2 - 5 and 12) are process wide and a plugin test that ran earlier may have tuned
+    them: this module runs at the library defaults (4 volumes in flight) and leaves the knobs as it found them."""
+    import conv_geometry
+    with conv_geometry.pinned(conv_geometry.inflight_values(4)):
+        yield
+
 CASE = (128, 136, 3, 1, False, (2, 4, 6, 8))
 
 
