@@ -802,6 +802,33 @@ int64_t mmtta_calibration_scratch_bytes(const mmtta_tensor* logits, int bins);
 int mmtta_calibration_bins(const mmtta_tensor* logits, const mmtta_tensor* label, int softmax, int bins, int scope,
                            double* out, void* scratch, void* stream);
 
+/* Connected-component filtering of the evaluation tail: 3-D labelling of every (volume, region) mask, then a size
+ * filter, an optional keep-the-largest filter and the Dice counts of what is left.  Replaces a host
+ * `scipy.ndimage.label` (with `generate_binary_structure(3, 1 | 2 | 3)`) over a mask copied off the device, the usual
+ * post-processing of BraTS / HECKTOR pipelines; the reference evaluator has no counterpart.
+ *   mask_in, mask_out  uint8 [N,R,D,H,W] dense (the `mask` output of mmtta_mask_dice_counts; non-zero = foreground);
+ *                      may be the same buffer.  mask_out holds 0 / 1.
+ *   label        fp32 any strides, ground truth = label > 0.5, or NULL (then `counts` must be NULL)
+ *   connectivity 6, 18 or 26
+ *   min_voxels   HOST int64 [R], read before return: components of fewer voxels are removed (0 and 1 remove nothing)
+ *   keep_largest HOST int32 [R], read before return: non-zero keeps only the largest component of the region
+ *   counts       int64 [N][R][3] on the device or NULL: inter, psum, gsum of the FILTERED mask against the label, as
+ *                mmtta_mask_dice_counts defines them; zeroed by this call
+ *   stats        int64 [N][R][3] on the device or NULL: components of the raw mask, components kept, voxels removed
+ *   labels       int32 [N,R,D,H,W] dense on the device or NULL: labels of the RAW mask
+ *   scratch      mmtta_components_scratch_bytes(N*R, D, H, W) bytes (negative: unsupported extent)
+ * Label convention: a component's label is 1 + the smallest linear index (z*H*W + y*W + x) of its voxels inside its own
+ * (n, r) volume; 0 is background.  Order: the size filter first, then `keep_largest` among the survivors; equal sizes
+ * go to the smaller label; when nothing survives `min_voxels` the region comes back empty and `kept` is 0.
+ * A fixed sequence of launches on `stream` that depends on the shape alone: no host read, no convergence flag.  All sums
+ * are integers: two calls agree bit for bit and a batch gives what its items give alone.
+ * Limits: every extent >= 1 (no multiple of anything), D*H*W <= 2^31 - 2, R <= 64, N*R <= 65535, and fewer than 2^32 - 256 voxels per
+ * call with every mask rounded up to a multiple of 256 (a larger batch is split by the caller).  Anything else is refused with MMTTA_ERR_INVALID / _UNSUPPORTED before anything is queued. */
+int64_t mmtta_components_scratch_bytes(int64_t n_masks, int64_t d, int64_t h, int64_t w);
+int mmtta_components_filter(const uint8_t* mask_in, uint8_t* mask_out, const mmtta_tensor* label, int n, int r, int d, int h,
+                            int w, int connectivity, const int64_t* min_voxels, const int32_t* keep_largest, int64_t* counts,
+                            int64_t* stats, int32_t* labels, void* scratch, void* stream);
+
 /* Surface metrics of the evaluation tail: percentile Hausdorff distance and average surface distance per
  * (volume, region).  Replaces the MONAI calls of reference src/evaluation/seg_eval.py:312-340
  * (`HausdorffDistanceMetric(include_background=True, reduction="none", percentile=95, directed=False)` built at

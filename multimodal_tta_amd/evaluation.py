@@ -76,6 +76,39 @@ def calibration_config(config: Any) -> Tuple[bool, int, str]:
     return enable, int(bins), str(scope)
 
 
+POSTPROCESS_CONNECTIVITIES = ops.COMPONENT_CONNECTIVITIES
+
+
+def postprocess_config(config: Any) -> Tuple[bool, int, List[int], List[bool]]:
+    """``evaluation.postprocess: {enable, connectivity, min_voxels, keep_largest}`` -> (enable, connectivity, min_voxels,
+    keep_largest), the last two as one entry per region of ``evaluation.seg.region_order``; off, 26, 0 and false when
+    absent.  ``min_voxels`` is an int or a list of ints, ``keep_largest`` a bool or a list of bools; a list has one entry
+    per region.  A value the kernel cannot take is a ``ValueError`` that names its key, whether the block is enabled or not."""
+    pp = get_config(config, "evaluation.postprocess", {}) or {}
+    R = len(list(get_config(config, "evaluation.seg.region_order", ["ET", "TC", "WT"])))
+    enable = get_config(pp, "enable", False)
+    if not isinstance(enable, bool):
+        raise ValueError(f"evaluation.postprocess.enable must be true or false, got {enable!r}")
+    conn = get_config(pp, "connectivity", 26)
+    if isinstance(conn, bool) or conn not in POSTPROCESS_CONNECTIVITIES:
+        raise ValueError(f"evaluation.postprocess.connectivity must be one of {list(POSTPROCESS_CONNECTIVITIES)}, got {conn!r}")
+
+    def per_region(key: str, default, ok, what: str) -> list:
+        v = get_config(pp, key, default)
+        scalar = isinstance(v, (bool, int))
+        vals = [v] * R if scalar else (list(v) if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else None)
+        if vals is None or not all(ok(x) for x in vals):
+            raise ValueError(f"evaluation.postprocess.{key} must be {what} or a list of one per region, got {v!r}")
+        if len(vals) != R:
+            raise ValueError(f"evaluation.postprocess.{key} has {len(vals)} entries for the {R} regions of "
+                             f"evaluation.seg.region_order")
+        return vals
+
+    mv = per_region("min_voxels", 0, lambda x: isinstance(x, int) and not isinstance(x, bool) and x >= 0, "a non-negative integer")
+    kl = per_region("keep_largest", False, lambda x: isinstance(x, bool), "true or false")
+    return enable, int(conn), [int(v) for v in mv], [bool(v) for v in kl]
+
+
 def calibration_from_bins(table: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """The table of ``ops.calibration_bins`` (float64 [..., 3*bins + 2]: per bin count, sum of confidence, correct count;
     then the Brier sum, then the NLL sum) -> (ece, brier, nll, valid), float64 / bool of the leading shape.
@@ -109,10 +142,11 @@ def calibration_width(bins: int, rout: int) -> int:
 class RegionAccumulator:
     """float64 sums / counts per region, overall and per domain (reference seg_eval.py:250-270,363-378).  ``bins`` > 0
     adds the calibration figures: ``calibration_regions`` names their rows (default: the regions; ``["all"]`` for a softmax
-    head), ``reliability`` pools the bins of every row."""
+    head), ``reliability`` pools the bins of every row.  ``components`` adds the connected-component figures of the
+    post-processing: per-volume means over ALL volumes of components found, components kept and voxels removed."""
 
     def __init__(self, region_order: Sequence[str], surface: bool = False, bins: int = 0,
-                 calibration_regions: Optional[Sequence[str]] = None):
+                 calibration_regions: Optional[Sequence[str]] = None, components: bool = False):
         self.regions = list(region_order)
         self.surface = bool(surface)
         R = len(self.regions)
@@ -128,6 +162,25 @@ class RegionAccumulator:
         self.cal_tot = self._zc()
         self.cal_dom: Dict[str, torch.Tensor] = defaultdict(self._zc)
         self.reliability = torch.zeros((Rc, max(self.bins, 0), 3), dtype=torch.float64)
+        self.components = bool(components)
+        self._zp = lambda: torch.zeros((4, R), dtype=torch.float64)          # sum_components, sum_kept, sum_removed, volumes
+        self.pp_tot = self._zp()
+        self.pp_dom: Dict[str, torch.Tensor] = defaultdict(self._zp)
+
+    def add_components(self, stats: Any, domain: str) -> None:
+        """One volume's component figures, [3*R] as the table holds them: components[R], kept[R], removed voxels[R]."""
+        st = torch.as_tensor(stats, dtype=torch.float64).reshape(3, len(self.regions))
+        for acc in (self.pp_tot, self.pp_dom[domain]):
+            acc[:3] += st
+            acc[3] += 1.0
+
+    def _component_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
+        for row, key in enumerate(("components", "kept_components", "removed_voxels")):
+            means = self._fin(acc[row], acc[3])
+            for name, v in zip(self.regions, means):
+                out[f"{prefix}{name.lower()}_{key}"] = v
+            if row == 0:
+                out[f"{prefix}avg_components"] = self._avg(means, acc[3])
 
     def add_calibration(self, raw: torch.Tensor, domain: str) -> None:
         """One volume's table, float64 [Rout, 3*bins + 2] (or flat)."""
@@ -150,8 +203,10 @@ class RegionAccumulator:
 
     def add_row(self, dice: Sequence[float], iou: Sequence[float], valid: Sequence[bool], domain: str,
                 hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None,
-                calibration: Optional[torch.Tensor] = None) -> None:
+                calibration: Optional[torch.Tensor] = None, components: Any = None) -> None:
         d = self.dom[domain]
+        if self.components:
+            self.add_components(components, domain)
         if self.bins:
             self.add_calibration(calibration, domain)
         for c in range(len(self.regions)):
@@ -194,6 +249,8 @@ class RegionAccumulator:
         out["loss"] = float(self.total_loss / max(1, self.n_samples)) if report_loss else 0.0
         if self.surface:        # reference seg_eval.py:424-440
             self._surface_keys(out, "", self.tot)
+        if self.components:
+            self._component_keys(out, "", self.pp_tot)
         if self.bins:
             self._calibration_keys(out, "", self.cal_tot)
         for dom in sorted(self.dom.keys()):
@@ -206,6 +263,8 @@ class RegionAccumulator:
             out[f"dom/{safe}/miou"] = self._avg(dim_, ci)
             if self.surface:    # reference seg_eval.py:459-476
                 self._surface_keys(out, f"dom/{safe}/", self.dom[dom])
+            if self.components:
+                self._component_keys(out, f"dom/{safe}/", self.pp_dom[dom])
             if self.bins:
                 self._calibration_keys(out, f"dom/{safe}/", self.cal_dom[dom])
         return out
@@ -301,6 +360,12 @@ class SegmentationEvaluationStrategy:
         self.calibration_softmax = bool(get_config(self.config, "training.criterion.softmax", False))
         self.calibration_regions = ["all"] if self.calibration_softmax else list(self.region_order)
         self.last_reliability: Optional[torch.Tensor] = None
+        # connected-component filtering of the thresholded mask on the GPU, off by default: small components dropped,
+        # optionally only the largest kept, per region; Dice, the surface distances and the gathered masks then describe
+        # the filtered mask (calibration and the reported loss stay on the logits)
+        (self.enable_postprocess, self.postprocess_connectivity, self.postprocess_min_voxels,
+         self.postprocess_keep_largest) = postprocess_config(self.config)
+        self._stats: Optional[torch.Tensor] = None
         # input pre-pass on the GPU (raw volumes in, the reference's `_normalize_img` applied here instead of in the
         # dataset worker; reference src/datasets/transforms.py:129-223).  The NIfTI datasets of this package hand over
         # raw intensities, so the pre-pass defaults to on for them and to off for the synthetic source (already
@@ -344,16 +409,35 @@ class SegmentationEvaluationStrategy:
             raise ValueError(f"[BratsSegEval] label channels={R} but region_order={len(self.region_order)}")
         return x, y.float()
 
+    def postprocess_launch(self, mask: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Queue the component filter on the current stream, in place on ``mask`` -> device (counts [B,R,3] of the filtered
+        mask, stats [B,R,3] = components, kept, removed voxels), both int64."""
+        res = ops.components_filter(mask, y, self.postprocess_connectivity, self.postprocess_min_voxels,
+                                    self.postprocess_keep_largest, out=mask)
+        return res["counts"], res["stats"]
+
+    @staticmethod
+    def component_columns(stats: torch.Tensor) -> torch.Tensor:
+        """stats int64 [R,3] of one volume -> its table columns float64 [3*R]: components[R], kept[R], removed voxels[R]."""
+        return stats.to(torch.float64).t().reshape(-1)
+
     def score(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
         """logits [B,R,D,H,W] (or channels-last view) + labels -> exact counts int64 [B,R,3] on the host.
-        With ``evaluation.surface.enable`` the prediction mask is kept for :meth:`surface`."""
+        With ``evaluation.surface.enable`` the prediction mask is kept for :meth:`surface`.  With
+        ``evaluation.postprocess.enable`` the mask is filtered in place, the counts are those of the filtered mask and
+        ``self._stats`` holds the component figures int64 [B,R,3] (host)."""
         R = y.shape[1]
         shape_ok = (logits.ndim == 5 and (logits.shape[-1] if channels_last else logits.shape[1]) == R)
         if not shape_ok:
             raise ValueError(f"[BratsSegEval] model logits must be [B,{R},D,H,W], got {tuple(logits.shape)}")
         counts = torch.empty((y.shape[0], R, 3), dtype=torch.int64, device=y.device)
-        self._mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if self.enable_surface else None
+        need_mask = self.enable_surface or self.enable_postprocess
+        self._mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if need_mask else None
         ops.mask_dice_counts(logits, y, self.threshold, counts, self._mask, logits_channels_last=channels_last)
+        self._stats = None
+        if self.enable_postprocess:
+            counts, stats = self.postprocess_launch(self._mask, y)
+            self._stats = stats.cpu()
         return counts.cpu()
 
     def calibration_launch(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
@@ -401,7 +485,8 @@ class SegmentationEvaluationStrategy:
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         model.eval()
         model.to(device)
-        acc = RegionAccumulator(self.region_order, self.enable_surface, self.cal_bins, self.calibration_regions)
+        acc = RegionAccumulator(self.region_order, self.enable_surface, self.cal_bins, self.calibration_regions,
+                                self.enable_postprocess)
         rows: List[torch.Tensor] = []
         domain_names: List[str] = []
         n_local = 0
@@ -412,12 +497,13 @@ class SegmentationEvaluationStrategy:
             dice, iou, valid = dice_iou_from_counts(counts)
             hd, asd = self.surface(y, counts) if self.enable_surface else (None, None)
             cal = self.calibration_launch(logits.float(), y).cpu() if self.enable_calibration else None
+            comp = [self.component_columns(st) for st in self._stats] if self.enable_postprocess else None
             domains = as_list_str(batch.get("domain", None), batch_size=x.size(0))
             if world == 1:
                 for i in range(x.size(0)):
                     acc.add_row(dice[i].tolist(), iou[i].tolist(), valid[i].tolist(), domains[i],
                                 hd[i].tolist() if hd is not None else None, asd[i].tolist() if asd is not None else None,
-                                cal[i] if cal is not None else None)
+                                cal[i] if cal is not None else None, comp[i] if comp is not None else None)
                 if self.report_loss:
                     acc.add_loss(self.loss_fn(logits.float(), y), x.size(0))
                 continue
@@ -435,6 +521,8 @@ class SegmentationEvaluationStrategy:
                          dice[i].double(), iou[i].double(), valid[i].double()]
                 if self.enable_surface:
                     parts += [hd[i].double(), asd[i].double()]
+                if comp is not None:
+                    parts.append(comp[i])
                 if cal is not None:
                     parts.append(cal[i].reshape(-1))
                 rows.append(torch.cat(parts))
@@ -449,14 +537,15 @@ class SegmentationEvaluationStrategy:
         return self._metrics_of(table, domain_names)
 
     def _table_width(self) -> int:
-        return table_width(len(self.region_order), self.enable_surface, self.cal_bins, len(self.calibration_regions))
+        return table_width(len(self.region_order), self.enable_surface, self.cal_bins, len(self.calibration_regions),
+                           components=self.enable_postprocess)
 
     def _metrics_of(self, table: torch.Tensor, domain_names: Sequence[str]) -> Dict[str, float]:
         """Metrics of the whole split from its per-volume table (and ``last_reliability`` with calibration on)."""
         if self.enable_calibration:
             self.last_reliability = reliability_from_table(table, self.calibration_bins, len(self.calibration_regions))
         return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface,
-                                  self.cal_bins, self.calibration_regions)
+                                  self.cal_bins, self.calibration_regions, components=self.enable_postprocess)
 
 
 # ----------------------------------------------------------------------------- sharding
@@ -465,10 +554,11 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
     return list(range(rank, n_items, world))
 
 
-def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None) -> int:
-    """index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R]) (, with ``bins`` > 0 the volume's raw
-    calibration table: ``rout`` rows - default R - of 3*bins + 2 doubles)."""
-    return 3 + (5 if surface else 3) * R + calibration_width(bins, R if rout is None else rout)
+def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None, components: bool = False) -> int:
+    """index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R]) (, with ``components`` the figures of the
+    post-processing: components[R], kept[R], removed voxels[R]) (, with ``bins`` > 0 the volume's raw calibration table:
+    ``rout`` rows - default R - of 3*bins + 2 doubles, always last)."""
+    return 3 + (5 if surface else 3) * R + (3 * R if components else 0) + calibration_width(bins, R if rout is None else rout)
 
 
 def reliability_from_table(table: torch.Tensor, bins: int, rout: int) -> torch.Tensor:
@@ -546,12 +636,14 @@ def gather_masks(local: Sequence[Tuple[int, torch.Tensor]], device, group=None) 
 
 def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_names: Sequence[str],
                        report_loss: bool, surface: bool = False, bins: int = 0,
-                       calibration_regions: Optional[Sequence[str]] = None) -> Dict[str, float]:
+                       calibration_regions: Optional[Sequence[str]] = None, components: bool = False) -> Dict[str, float]:
     """Replay the reference aggregation over gathered rows in volume-index order: the result is
     identical to a single-process run (float64 sums, order fixed by index).  ``bins`` > 0: the rows end in the raw
-    calibration table of their volume (``table_width``), one row of it per name in ``calibration_regions``."""
+    calibration table of their volume (``table_width``), one row of it per name in ``calibration_regions``.
+    ``components``: the 3*R component columns sit behind the surface columns (``table_width``)."""
     R = len(region_order)
-    acc = RegionAccumulator(region_order, surface, bins, calibration_regions)
+    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components)
+    c0 = 3 + (5 if surface else 3) * R
     cal_w = calibration_width(bins, len(acc.cal_regions))
     for row in table:
         dom = domain_names[int(row[1].item())] if 0 <= int(row[1].item()) < len(domain_names) else ""
@@ -560,7 +652,8 @@ def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_
         valid = (row[3 + 2 * R:3 + 3 * R] > 0.5).tolist()
         hd = row[3 + 3 * R:3 + 4 * R].to(torch.float32).tolist() if surface else None
         asd = row[3 + 4 * R:3 + 5 * R].to(torch.float32).tolist() if surface else None
-        acc.add_row(dice, iou, valid, dom, hd, asd, row[row.numel() - cal_w:] if bins else None)
+        acc.add_row(dice, iou, valid, dom, hd, asd, row[row.numel() - cal_w:] if bins else None,
+                    row[c0:c0 + 3 * R] if components else None)
         if report_loss:
             acc.add_loss(float(row[2].item()), 1)
     return acc.metrics(report_loss)
@@ -671,9 +764,15 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         B, R = yb.shape[0], yb.shape[1]
         res = self.plugins[lane].adapt_volume(xb)
         counts = torch.empty((B, R, 3), dtype=torch.int64, device=yb.device)
-        mask = torch.empty(tuple(yb.shape), dtype=torch.uint8, device=yb.device) if (self.enable_surface or self.gather_masks) else None
+        need_mask = self.enable_surface or self.gather_masks or self.enable_postprocess
+        mask = torch.empty(tuple(yb.shape), dtype=torch.uint8, device=yb.device) if need_mask else None
         ops.mask_dice_counts(res["logits_cl"], yb, self.threshold, counts, mask, logits_channels_last=True)
+        stats = None
+        if self.enable_postprocess:      # in place: the surface pass and the gathered masks below take the filtered mask
+            counts, stats = self.postprocess_launch(mask, yb)
         job: Dict[str, Any] = {"counts": counts, "shape": tuple(yb.shape[2:]), "keep": (xb, yb, mask, res), "mask": mask}
+        if stats is not None:
+            job["components"] = stats
         if self.report_loss:
             job["loss"] = self.loss_fn.launch(res["logits_cl"], yb, channels_last=True)
         if self.enable_surface:
@@ -691,12 +790,15 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         if self.enable_surface:
             hd, asd = self.surface_fix(job["surface"][0], job["surface"][1], counts, job["shape"])
         cal = job["calibration"].cpu() if self.enable_calibration else None
+        comp = job["components"].cpu() if self.enable_postprocess else None
         rows = []
         for b in range(B):
             parts = [torch.tensor([job["index"][b], job["domain_id"][b], losses[b]], dtype=torch.float64),
                      dice[b].double(), iou[b].double(), valid[b].double()]
             if self.enable_surface:
                 parts += [hd[b].double(), asd[b].double()]
+            if comp is not None:
+                parts.append(self.component_columns(comp[b]))
             if cal is not None:
                 parts.append(cal[b].reshape(-1))
             rows.append(torch.cat(parts))

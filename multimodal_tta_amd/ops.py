@@ -12,7 +12,7 @@ import ctypes as C
 import os
 import threading
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -1240,3 +1240,68 @@ def surface_distances(pred_mask: torch.Tensor, label_ncdhw: torch.Tensor, spacin
     check(lib.mmtta_surface_distances(ptr(pred_mask), C.byref(tl), sp, float(percentile), 1 if asd_symmetric else 0,
                                       ptr(hd), ptr(asd), ptr(scratch), stream_ptr()), "surface_distances")
     return hd, asd
+
+
+_CC_SCRATCH: Dict[Tuple, torch.Tensor] = {}      # working set of components_filter, per (device, size, stream)
+COMPONENT_CONNECTIVITIES = (6, 18, 26)
+COMPONENTS_MAX_REGIONS = 64
+
+
+def _per_region(value, R: int, what: str) -> List[int]:
+    vals = [value] * R if isinstance(value, (bool, int)) else list(value)
+    if len(vals) != R:
+        raise MmttaError(f"components_filter: {what} has {len(vals)} entries for {R} regions")
+    return [int(v) for v in vals]
+
+
+def components_filter(mask: torch.Tensor, label_ncdhw: Optional[torch.Tensor] = None, connectivity: int = 26, min_voxels=0,
+                      keep_largest=False, out: Optional[torch.Tensor] = None, want_counts: bool = True, want_stats: bool = True,
+                      want_labels: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+    """Connected components of every (volume, region) of ``mask`` (uint8 [B,R,D,H,W], dense; from ``mask_dice_counts``),
+    then the size filter and the keep-largest filter (include/mmtta.h: mmtta_components_filter), queued on the current
+    stream.  ``min_voxels`` / ``keep_largest``: one value, or one per region.  ``out``: where the filtered mask goes
+    (default: a new tensor; pass ``mask`` itself to filter in place).  Returns the device tensors: ``mask`` uint8,
+    ``counts`` int64 [B,R,3] (inter, psum, gsum of the filtered mask; needs a label), ``stats`` int64 [B,R,3]
+    (components, kept, removed voxels), ``labels`` int32 [B,R,D,H,W] of the raw mask (1 + smallest voxel index)."""
+    if mask.dtype != torch.uint8 or mask.dim() != 5 or not mask.is_contiguous() or not mask.is_cuda:
+        raise MmttaError(f"components_filter: mask must be a dense CUDA uint8 [B,R,D,H,W] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    B, R, D, H, W = (int(v) for v in mask.shape)
+    if min(B, R, D, H, W) < 1:
+        raise MmttaError(f"components_filter: empty mask {tuple(mask.shape)}")
+    if R > COMPONENTS_MAX_REGIONS:
+        raise MmttaError(f"components_filter: {R} regions, at most {COMPONENTS_MAX_REGIONS}")
+    if connectivity not in COMPONENT_CONNECTIVITIES:
+        raise MmttaError(f"components_filter: connectivity {connectivity!r} (one of {list(COMPONENT_CONNECTIVITIES)})")
+    if out is None:
+        out = torch.empty_like(mask)
+    elif out.dtype != torch.uint8 or out.shape != mask.shape or not out.is_contiguous() or out.device != mask.device:
+        raise MmttaError(f"components_filter: `out` must be dense uint8 of the mask's shape, got {out.dtype} {tuple(out.shape)}")
+    if label_ncdhw is not None and (tuple(label_ncdhw.shape) != tuple(mask.shape) or label_ncdhw.device != mask.device or
+                                    label_ncdhw.dtype != torch.float32):
+        raise MmttaError(f"components_filter: label must be float32 of the mask's shape on the mask's device, got "
+                         f"{label_ncdhw.dtype} {tuple(label_ncdhw.shape)} on {label_ncdhw.device} vs {tuple(mask.shape)} on "
+                         f"{mask.device}")
+    mv = _per_region(min_voxels, R, "min_voxels")
+    if any(v < 0 for v in mv):
+        raise MmttaError(f"components_filter: min_voxels must not be negative, got {mv}")
+    kl = _per_region(keep_largest, R, "keep_largest")
+    lib = _lib.load()
+    nbytes = int(lib.mmtta_components_scratch_bytes(B * R, D, H, W))
+    if nbytes < 0:
+        raise MmttaError(f"components_filter: extent {(B * R, D, H, W)} unsupported (D*H*W <= 2**31 - 2, B*R <= 65535, "
+                         f"B*R*D*H*W below 2**32: split the batch)")
+    key = (mask.device.index, nbytes, int(torch.cuda.current_stream().cuda_stream))      # per stream: lanes run concurrently
+    scratch = _CC_SCRATCH.get(key)
+    if scratch is None:
+        for k in [k for k in _CC_SCRATCH if k[2] == key[2]]:       # a new shape on this stream replaces its old working set
+            del _CC_SCRATCH[k]
+        scratch = _CC_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+    dev = mask.device
+    counts = torch.empty((B, R, 3), dtype=torch.int64, device=dev) if (want_counts and label_ncdhw is not None) else None
+    stats = torch.empty((B, R, 3), dtype=torch.int64, device=dev) if want_stats else None
+    labels = torch.empty((B, R, D, H, W), dtype=torch.int32, device=dev) if want_labels else None
+    tl = desc_ncdhw(label_ncdhw) if label_ncdhw is not None else None
+    check(lib.mmtta_components_filter(ptr(mask), ptr(out), C.byref(tl) if tl is not None else None, B, R, D, H, W,
+                                      int(connectivity), (C.c_int64 * R)(*mv), (C.c_int32 * R)(*kl), ptr(counts), ptr(stats),
+                                      ptr(labels), ptr(scratch), stream_ptr()), "components_filter")
+    return {"mask": out, "counts": counts, "stats": stats, "labels": labels}
