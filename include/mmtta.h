@@ -456,6 +456,56 @@ int mmtta_upsample2x_bwd(const mmtta_tensor* dy, const mmtta_tensor* dx, int acc
 int mmtta_lincomb(int count, const mmtta_tensor* const* in, const float* w, const mmtta_tensor* out,
                   int accumulate, void* stream);
 
+/* Which kernel of csrc/pointwise.hip an entry point would launch for these operands, and on what launch geometry (host-only:
+ * launches nothing, dereferences no pointer - pointers are read for their alignment only; the entry points themselves ask the
+ * same planners).  `operands` per op:
+ *   CHANNEL_STATS {x}            NORM_BWD_REDUCE {dout, y}      NORM_BWD_APPLY / NORM_BWD_SMALL {dout, y, dy}
+ *   COMBINE {a, out} or {a, b, out}     LINCOMB {in[0], ..., in[k-1], out}     UPSAMPLE_FWD {x, y}     UPSAMPLE_BWD {dy, dx}
+ * `t` is the call's norm-on-load (COMBINE: ta, and `t2` = tb), `m1` / `m2` the coefficient vectors of NORM_BWD_APPLY; NULL
+ * for the ops that take none.  Returns MMTTA_OK or the error the entry point itself would report for these operands. */
+#define MMTTA_PW_OP_CHANNEL_STATS 0
+#define MMTTA_PW_OP_NORM_BWD_REDUCE 1
+#define MMTTA_PW_OP_NORM_BWD_APPLY 2
+#define MMTTA_PW_OP_NORM_BWD_SMALL 3
+#define MMTTA_PW_OP_COMBINE 4
+#define MMTTA_PW_OP_LINCOMB 5
+#define MMTTA_PW_OP_UPSAMPLE_FWD 6
+#define MMTTA_PW_OP_UPSAMPLE_BWD 7
+/* kernel families (mmtta_pointwise_route_t.family) */
+#define MMTTA_PW_REDUCE 0          /* channel_reduce_kernel<mode, vec, bf16_a, bf16_b> */
+#define MMTTA_PW_REDUCE_STREAM 1   /* channel_reduce_stream_kernel<mode, it, bf16_a, bf16_b> */
+#define MMTTA_PW_ELEMENTWISE 2     /* elementwise_kernel<mode, vec, bf16_a, bf16_b, bf16_o> */
+#define MMTTA_PW_COMBINE8 3        /* combine8_kernel<bf16_a, has_b, it> */
+#define MMTTA_PW_NORM_BWD_APPLY8 4 /* norm_bwd_apply8_kernel<bf16_b, it, bf16_a> */
+#define MMTTA_PW_NORM_BWD_SMALL 5  /* norm_bwd_small_kernel<bf16_b, bf16_a> */
+#define MMTTA_PW_LINCOMB 6         /* lincomb_kernel<vec, count, bf16_a, bf16_o> */
+#define MMTTA_PW_UPSAMPLE_FWD 7    /* upsample_fwd_kernel<vec, bf16_a> */
+#define MMTTA_PW_UPSAMPLE_BWD 8    /* upsample_bwd_kernel<vec, bf16_a> */
+typedef struct {
+  int64_t vox_per_row;    /* reductions: voxels per partial row (the last row of an item may be shorter) */
+  int64_t work_items;     /* threads' worth of work: voxels x channel vectors */
+  int64_t grid_x;         /* workgroups of 256 threads */
+  int32_t grid_y;
+  int32_t family;         /* MMTTA_PW_* */
+  int32_t mode;           /* reductions: 0 sums of x and x^2, 1 norm-backward sums; elementwise: 0 combine, 1 norm-backward apply */
+  int32_t vec;            /* channels per thread: 1, 4 or 8 */
+  int32_t it;             /* voxels a thread has in flight (template IT); 0: the kernel has no such parameter */
+  int32_t count;          /* lincomb: number of inputs (template COUNT) */
+  int32_t bf16_a;         /* storage flags of the instantiation: reductions x / y; apply, small: dout; combine: a; lincomb: inputs */
+  int32_t bf16_b;         /*   reductions: dout; apply, small: y; combine: b */
+  int32_t bf16_o;         /*   the tensor written */
+  int32_t has_b;          /* combine: a second source */
+  int32_t rows_per_n;     /* reductions: partial rows per batch item */
+  int32_t rows_per_block; /* reductions: rows a workgroup walks (the last workgroup of an item may have fewer) */
+  int32_t cpl, nvl;       /* channel lanes x voxel lanes of a workgroup (cpl * nvl == 256) */
+  int32_t trips;          /* reductions: voxels a lane adds per row, sequentially */
+  int32_t cb_passes;      /* channel_reduce_kernel: passes of the channel lanes over C */
+  int32_t second_trip;    /* grid-stride kernels: the capped grid makes threads take a second element */
+  int32_t leaky;          /* the LeakyReLU instantiation of the family runs */
+} mmtta_pointwise_route_t;
+int mmtta_pointwise_route(int op, const mmtta_tensor* const* operands, int count, const mmtta_norm_on_load* t,
+                          const mmtta_norm_on_load* t2, const float* m1, const float* m2, mmtta_pointwise_route_t* out);
+
 /* ------------------------------------------------------------------ loss ----------------- */
 /* Entropy-minimisation objective and its gradient in one pass (BUILD-DEFINED: the reference
  * has no TTA loss; it takes the place of DiceCELoss in the step

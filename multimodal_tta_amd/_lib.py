@@ -71,6 +71,20 @@ class ConvPlan(C.Structure):
     ]
 
 
+class PointwiseRoute(C.Structure):     # mmtta_pointwise_route_t
+    _fields_ = [("vox_per_row", C.c_int64), ("work_items", C.c_int64), ("grid_x", C.c_int64), ("grid_y", C.c_int32),
+                ("family", C.c_int32), ("mode", C.c_int32), ("vec", C.c_int32), ("it", C.c_int32), ("count", C.c_int32),
+                ("bf16_a", C.c_int32), ("bf16_b", C.c_int32), ("bf16_o", C.c_int32), ("has_b", C.c_int32),
+                ("rows_per_n", C.c_int32), ("rows_per_block", C.c_int32), ("cpl", C.c_int32), ("nvl", C.c_int32),
+                ("trips", C.c_int32), ("cb_passes", C.c_int32), ("second_trip", C.c_int32), ("leaky", C.c_int32)]
+
+
+PW_OPS = ("channel_stats", "norm_bwd_reduce", "norm_bwd_apply", "norm_bwd_small", "combine", "lincomb", "upsample_fwd",
+          "upsample_bwd")                                      # MMTTA_PW_OP_*: the index is the code
+PW_FAMILIES = ("reduce", "reduce_stream", "elementwise", "combine8", "norm_bwd_apply8", "norm_bwd_small", "lincomb",
+               "upsample_fwd", "upsample_bwd")                 # MMTTA_PW_*: the index is the code
+
+
 class OptimDesc(C.Structure):          # mmtta_optim_desc
     _fields_ = [("kind", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("momentum", C.c_float), ("dampening", C.c_float), ("nesterov", C.c_int32)]
@@ -148,6 +162,8 @@ _SIGNATURES = {
     "mmtta_upsample2x_fwd": (C.c_int, [_P(Tensor), _P(Tensor), C.c_void_p]),
     "mmtta_upsample2x_bwd": (C.c_int, [_P(Tensor), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_lincomb": (C.c_int, [C.c_int, _P(_P(Tensor)), _P(C.c_float), _P(Tensor), C.c_int, C.c_void_p]),
+    "mmtta_pointwise_route": (C.c_int, [C.c_int, _P(_P(Tensor)), C.c_int, _P(NormOnLoad), _P(NormOnLoad), C.c_void_p, C.c_void_p,
+                                        _P(PointwiseRoute)]),
     "mmtta_entropy_partials": (C.c_int64, [_P(Tensor)]),
     "mmtta_entropy_loss": (C.c_int, [_P(Tensor), C.c_int, _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_entropy_partials_items": (C.c_int64, [_P(Tensor)]),

@@ -808,12 +808,9 @@ __global__ __launch_bounds__(256) void combine8_kernel(Cb8Args e) {
 }
 
 template <bool BF, bool HASB>
-static void launch_combine8(const Cb8Args& q, int n, hipStream_t s) {
-  const long long nvl = 256 / (q.C / 8);
-  const bool four = q.dhw / (nvl * 4) >= 1024;
-  const long long per = nvl * (four ? 4 : 2);
-  const dim3 g8((unsigned)((q.dhw + per - 1) / per), (unsigned)n);
-  if (four) hipLaunchKernelGGL((combine8_kernel<BF, HASB, 4>), g8, dim3(256), 0, s, q);
+static void launch_combine8(const Cb8Args& q, const mmtta_pointwise_route_t& r, hipStream_t s) {
+  const dim3 g8((unsigned)r.grid_x, (unsigned)r.grid_y);
+  if (r.it == 4) hipLaunchKernelGGL((combine8_kernel<BF, HASB, 4>), g8, dim3(256), 0, s, q);
   else hipLaunchKernelGGL((combine8_kernel<BF, HASB, 2>), g8, dim3(256), 0, s, q);
 }
 
@@ -1024,6 +1021,161 @@ static bool reduce_stream_ok(const mmtta_tensor* x, const mmtta_tensor* d) {
   return ok(x) && (!d || ok(d)) && x->c >= 1 && x->c <= 1024 && dhw >= 1 && dhw < ((int64_t)1 << 31) && x->n >= 1 && x->n <= 65535;
 }
 
+// ---- host-side planning: which kernel an entry point runs and on what launch geometry.  The launchers below and
+// mmtta_pointwise_route call the same functions, so the answer of the query is the launch (tests assert the route first).
+typedef mmtta_pointwise_route_t PwRoute;
+
+static inline long long vox_count(const mmtta_tensor* t) { return (long long)t->d * t->h * t->w; }
+
+// a grid-stride kernel: `total` work items on at most `cap` workgroups of 256
+static inline void route_grid_stride(PwRoute& r, long long total, int cap = 8192) {
+  r.work_items = total;
+  r.grid_x = grid_for(total, cap);
+  r.grid_y = 1;
+  r.second_trip = total > r.grid_x * 256 ? 1 : 0;
+}
+
+// the octet kernels (combine8 / norm_bwd_apply8 / norm_bwd_small): 16-byte aligned octets of a voxel-dense tensor
+static inline bool oct_aligned(const mmtta_tensor* t) {
+  const int per = is_bf16(t) ? 8 : 4;
+  return ((uintptr_t)t->ptr) % 16 == 0 && t->sw % per == 0 && t->sn % per == 0;
+}
+static inline bool oct_channels(int C) { return C >= 8 && C <= 2048 && (C & (C - 1)) == 0; }
+static inline bool null_or_16(const void* p) { return p == nullptr || ((uintptr_t)p) % 16 == 0; }
+// voxels per thread (IT 4 from 1024 workgroups per item on) and the grid of combine8 / norm_bwd_apply8
+static inline void route_octets(PwRoute& r, int C, long long dhw, int n) {
+  const long long nvl = 256 / (C / 8);
+  const bool four = dhw / (nvl * 4) >= 1024;
+  const long long per = nvl * (four ? 4 : 2);
+  r.vec = 8; r.it = four ? 4 : 2; r.cpl = C / 8; r.nvl = (int)nvl; r.trips = 1;
+  r.grid_x = (dhw + per - 1) / per; r.grid_y = n;
+  r.work_items = dhw * n * (C / 8);
+}
+
+// the streamed reduction's schedule
+struct StreamGeo { unsigned cpl, nvl, trips, it, rpb; };
+static inline StreamGeo stream_geometry(unsigned C, unsigned vox_per_row, unsigned rows_per_n, int n) {
+  StreamGeo g;
+  g.cpl = 1;
+  while (g.cpl < (C + 3) / 4) g.cpl <<= 1;
+  g.nvl = 256u / g.cpl;
+  g.trips = (vox_per_row + g.nvl - 1) / g.nvl;
+  // Rows per workgroup.  A row of several chunks overlaps its own loads and adds, and one row per workgroup balances best
+  // (measured, groups of 8: 64^3 x 32 and 128^3 x 3 are fastest at 1).  A row of ONE chunk has nothing to overlap with but
+  // the next row: 4 rows per workgroup (32^3 x 64: 23 us at 1, 14 us at 4), fewer where the launch would shrink below
+  // 512 workgroups.
+  g.it = g.trips >= 4 ? 4 : (g.trips >= 2 ? 2 : 1);
+  const unsigned chunks = (g.trips + g.it - 1) / g.it, total = (unsigned)n * rows_per_n;
+  g.rpb = 1;
+  if (chunks == 1) g.rpb = total / 512 < 1 ? 1 : (total / 512 > 4 ? 4 : total / 512);
+  return g;
+}
+
+// MODE 0 (`d` null): channel sums of x.  MODE 1: the norm-backward sums of (y = x, dout = d).
+static inline PwRoute reduce_plan(const mmtta_tensor* x, const mmtta_tensor* d) {
+  PwRoute r = {};
+  r.mode = d ? 1 : 0;
+  r.bf16_a = is_bf16(x) ? 1 : 0; r.bf16_b = d && is_bf16(d) ? 1 : 0;
+  int rows; long long vpr;
+  rows_geometry(x, rows, vpr);
+  r.rows_per_n = rows; r.vox_per_row = vpr;
+  if (reduce_stream_ok(x, d)) {
+    const StreamGeo g = stream_geometry((unsigned)x->c, (unsigned)vpr, (unsigned)rows, x->n);
+    r.family = MMTTA_PW_REDUCE_STREAM; r.vec = 4; r.it = (int)g.it;
+    r.cpl = (int)g.cpl; r.nvl = (int)g.nvl; r.trips = (int)g.trips; r.rows_per_block = (int)g.rpb; r.cb_passes = 1;
+    r.grid_x = (rows + g.rpb - 1) / g.rpb; r.grid_y = x->n;
+  } else {
+    const bool v4 = vec4_rd(x) && (!d || vec4_rd(d));
+    r.family = MMTTA_PW_REDUCE; r.vec = v4 ? 4 : 1; r.it = 1;
+    const int cv = (x->c + r.vec - 1) / r.vec;
+    int cpl = 1;
+    while (cpl < cv && cpl < 256) cpl <<= 1;            // channel_reduce_kernel's own block layout
+    r.cpl = cpl; r.nvl = 256 / cpl; r.trips = (int)((vpr + r.nvl - 1) / r.nvl);
+    r.rows_per_block = 1; r.cb_passes = (cv + cpl - 1) / cpl;
+    r.grid_x = (long long)x->n * rows; r.grid_y = 1;
+  }
+  r.work_items = (long long)x->n * vox_count(x) * ((x->c + r.vec - 1) / r.vec);
+  return r;
+}
+
+static inline int combine_check(const mmtta_tensor* a, const mmtta_tensor* b, const mmtta_tensor* out) {
+  MMTTA_CHECK(a && out && a->ptr && out->ptr, MMTTA_ERR_INVALID, "combine: null tensor");
+  MMTTA_CHECK(same_shape(a, out) && (!b || same_shape(b, out)), MMTTA_ERR_INVALID, "combine: shape mismatch");
+  MMTTA_CHECK(is_cl(a) && is_cl(out) && (!b || is_cl(b)), MMTTA_ERR_UNSUPPORTED, "combine: channels-last only");
+  // storage: all fp32, or all bf16 (the wide forward activations of bf16 precision)
+  const bool abf = is_bf16(a), bbf = b ? is_bf16(b) : abf, obf = is_bf16(out);
+  MMTTA_CHECK((abf == bbf && bbf == obf), MMTTA_ERR_UNSUPPORTED, "combine: operands must share one storage type");
+  return MMTTA_OK;
+}
+static inline bool combine_v4(const mmtta_tensor* a, const mmtta_tensor* b, const mmtta_tensor* out) {
+  return vec4_rd(a) && vec4_wr(out) && (!b || vec4_rd(b));
+}
+// octet form: C a power of two in [8, 2048], voxel-dense tensors, 16-byte aligned octets, 32-bit offsets inside an item
+static inline bool combine_ok8(const mmtta_tensor* a, const mmtta_tensor* b, const mmtta_tensor* out) {
+  return combine_v4(a, b, out) && oct_channels(out->c) && dense_voxels(a) && dense_voxels(out) && oct_aligned(a) &&
+         oct_aligned(out) && (!b || (dense_voxels(b) && oct_aligned(b))) &&
+         vox_count(out) * std::max(std::max(a->sw, out->sw), b ? b->sw : (int64_t)0) < (1LL << 31);
+}
+static inline PwRoute combine_plan(const mmtta_tensor* a, const mmtta_tensor* b, const mmtta_tensor* out) {
+  PwRoute r = {};
+  r.mode = 0; r.has_b = b ? 1 : 0;
+  r.bf16_a = r.bf16_b = r.bf16_o = is_bf16(out) ? 1 : 0;
+  if (combine_ok8(a, b, out)) {
+    r.family = MMTTA_PW_COMBINE8;
+    route_octets(r, out->c, vox_count(out), out->n);
+    return r;
+  }
+  const bool v4 = combine_v4(a, b, out);
+  r.family = MMTTA_PW_ELEMENTWISE; r.vec = v4 ? 4 : 1;
+  route_grid_stride(r, (long long)out->n * vox_count(out) * (v4 ? (out->c + 3) / 4 : out->c));
+  return r;
+}
+
+static inline int norm_bwd_reduce_check(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t) {
+  MMTTA_CHECK(dout && y && t && dout->ptr && y->ptr && t->mean && t->rstd, MMTTA_ERR_INVALID, "norm bwd reduce: null argument");
+  // (a bf16-stored gradient sits next to a bf16-stored activation - or, <= 4 channels, next to an fp32-stored one: the thin
+  // full-resolution tensors keep their activations fp32, round 3)
+  MMTTA_CHECK(!is_bf16(dout) || is_bf16(y) || y->c <= 4, MMTTA_ERR_UNSUPPORTED, "norm bwd reduce: a bf16-stored gradient needs a bf16-stored activation");
+  MMTTA_CHECK(same_shape(dout, y) && is_cl(dout) && is_cl(y), MMTTA_ERR_INVALID, "norm bwd reduce: shape/layout mismatch");
+  return MMTTA_OK;
+}
+
+static inline int norm_bwd_apply_check(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
+                                       const float* m1, const float* m2, const mmtta_tensor* dy) {
+  MMTTA_CHECK(dout && y && t && dy && m1 && m2 && t->mean && t->rstd, MMTTA_ERR_INVALID, "norm bwd apply: null argument");
+  MMTTA_CHECK(dout->dtype == dy->dtype && (!is_bf16(dout) || is_bf16(y) || y->c <= 4), MMTTA_ERR_UNSUPPORTED,
+              "norm bwd apply: `dout` and `dy` share one storage type (bf16 only next to a bf16-stored activation)");
+  MMTTA_CHECK(same_shape(dout, y) && same_shape(dy, y), MMTTA_ERR_INVALID, "norm bwd apply: shape mismatch");
+  MMTTA_CHECK(is_cl(dout) && is_cl(y) && is_cl(dy), MMTTA_ERR_UNSUPPORTED, "norm bwd apply: channels-last only");
+  return MMTTA_OK;
+}
+static inline bool norm_bwd_apply_v4(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_tensor* dy) {
+  return vec4_rd(dout) && vec4_rd(y) && vec4_wr(dy);
+}
+// octet form: as combine_ok8, and the [N*C] coefficient vectors on 16 bytes
+static inline bool norm_bwd_apply_ok8(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
+                                      const float* m1, const float* m2, const mmtta_tensor* dy) {
+  return norm_bwd_apply_v4(dout, y, dy) && oct_channels(y->c) && dense_voxels(dout) && dense_voxels(y) && dense_voxels(dy) &&
+         oct_aligned(dout) && oct_aligned(dy) && oct_aligned(y) && ((uintptr_t)t->mean % 16 == 0) &&
+         ((uintptr_t)t->rstd % 16 == 0) && ((uintptr_t)m1 % 16 == 0) && ((uintptr_t)m2 % 16 == 0) && null_or_16(t->gamma) &&
+         null_or_16(t->beta) && vox_count(y) * std::max(std::max(dout->sw, y->sw), dy->sw) < (1LL << 31);
+}
+static inline PwRoute norm_bwd_apply_plan(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
+                                          const float* m1, const float* m2, const mmtta_tensor* dy) {
+  PwRoute r = {};
+  r.mode = 1; r.has_b = 1;
+  r.bf16_a = r.bf16_o = is_bf16(dout) ? 1 : 0; r.bf16_b = is_bf16(y) ? 1 : 0;
+  if (norm_bwd_apply_ok8(dout, y, t, m1, m2, dy)) {
+    r.family = MMTTA_PW_NORM_BWD_APPLY8;
+    route_octets(r, y->c, vox_count(y), y->n);
+    return r;
+  }
+  const bool v4 = norm_bwd_apply_v4(dout, y, dy);
+  r.family = MMTTA_PW_ELEMENTWISE; r.vec = v4 ? 4 : 1;
+  route_grid_stride(r, (long long)y->n * vox_count(y) * (v4 ? (y->c + 3) / 4 : y->c));
+  return r;
+}
+
 static RedSArgs reduce_stream_args(const mmtta_tensor* x, const mmtta_tensor* d, const mmtta_norm_on_load* t, float* part) {
   RedSArgs q;
   q.x = (const float*)x->ptr; q.dout = d ? (const float*)d->ptr : nullptr;
@@ -1040,19 +1192,10 @@ static RedSArgs reduce_stream_args(const mmtta_tensor* x, const mmtta_tensor* d,
 }
 
 template <int MODE, bool XBF, bool DBF>
-static void launch_reduce_stream(RedSArgs q, int n, hipStream_t s) {
-  unsigned cpl = 1;
-  while (cpl < (q.C + 3) / 4) cpl <<= 1;
-  const unsigned nvl = 256u / cpl, trips = (q.vox_per_row + nvl - 1) / nvl;
-  // Rows per workgroup.  A row of several chunks overlaps its own loads and adds, and one row per workgroup balances best
-  // (measured, groups of 8: 64^3 x 32 and 128^3 x 3 are fastest at 1).  A row of ONE chunk has nothing to overlap with but
-  // the next row: 4 rows per workgroup (32^3 x 64: 23 us at 1, 14 us at 4), fewer where the launch would shrink below
-  // 512 workgroups.
-  const unsigned it = trips >= 4 ? 4 : (trips >= 2 ? 2 : 1), chunks = (trips + it - 1) / it, total = (unsigned)n * q.rows_per_n;
-  unsigned rpb = 1;
-  if (chunks == 1) rpb = total / 512 < 1 ? 1 : (total / 512 > 4 ? 4 : total / 512);
-  q.rows_per_block = rpb;
-  const dim3 grid((q.rows_per_n + rpb - 1) / rpb, (unsigned)n);
+static void launch_reduce_stream(RedSArgs q, const PwRoute& r, hipStream_t s) {
+  q.rows_per_block = (unsigned)r.rows_per_block;
+  const dim3 grid((unsigned)r.grid_x, (unsigned)r.grid_y);
+  const int it = r.it;
   if (it == 4) hipLaunchKernelGGL((channel_reduce_stream_kernel<MODE, 4, XBF, DBF>), grid, dim3(256), 0, s, q);
   else if (it == 2) hipLaunchKernelGGL((channel_reduce_stream_kernel<MODE, 2, XBF, DBF>), grid, dim3(256), 0, s, q);
   else hipLaunchKernelGGL((channel_reduce_stream_kernel<MODE, 1, XBF, DBF>), grid, dim3(256), 0, s, q);
@@ -1068,17 +1211,19 @@ int launch_channel_sums(const mmtta_tensor* x, float* part, hipStream_t s) {
   RedArgs a;
   a.x = tv(x); a.dout = tv(x); a.t = nl(nullptr); a.per_item = 0; a.part = part;
   rows_geometry(x, a.rows_per_n, a.vox_per_row);
-  const dim3 grid(x->n * a.rows_per_n);
-  if (reduce_stream_ok(x, nullptr)) {
+  const PwRoute r = reduce_plan(x, nullptr);
+  const dim3 grid((unsigned)r.grid_x);
+  if (r.family == MMTTA_PW_REDUCE_STREAM) {
     const RedSArgs q = reduce_stream_args(x, nullptr, nullptr, part);
-    MMTTA_BF_DISPATCH(is_bf16(x), XBF, { launch_reduce_stream<0, XBF, false>(q, x->n, s); });
+    MMTTA_BF_DISPATCH(is_bf16(x), XBF, { launch_reduce_stream<0, XBF, false>(q, r, s); });
     return launch_status("channel sums");
   }
+  const bool v4 = r.vec == 4;
   if (is_bf16(x)) {
-    if (vec4_rd(x)) hipLaunchKernelGGL((channel_reduce_kernel<0, 4, true>), grid, dim3(256), 0, s, a);
+    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<0, 4, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((channel_reduce_kernel<0, 1, true>), grid, dim3(256), 0, s, a);
   } else {
-    if (vec4_rd(x)) hipLaunchKernelGGL((channel_reduce_kernel<0, 4>), grid, dim3(256), 0, s, a);
+    if (v4) hipLaunchKernelGGL((channel_reduce_kernel<0, 4>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((channel_reduce_kernel<0, 1>), grid, dim3(256), 0, s, a);
   }
   return launch_status("channel sums");
@@ -1087,38 +1232,27 @@ int launch_channel_sums(const mmtta_tensor* x, float* part, hipStream_t s) {
 // ---- entry bodies (the C entry points below check the norm-on-load descriptors and pick the activation instantiation)
 int combine_body(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtta_tensor* b,
                  const mmtta_norm_on_load* tb, const mmtta_tensor* out, void* stream) {
-  MMTTA_CHECK(a && out && a->ptr && out->ptr, MMTTA_ERR_INVALID, "combine: null tensor");
-  MMTTA_CHECK(same_shape(a, out) && (!b || same_shape(b, out)), MMTTA_ERR_INVALID, "combine: shape mismatch");
-  MMTTA_CHECK(is_cl(a) && is_cl(out) && (!b || is_cl(b)), MMTTA_ERR_UNSUPPORTED, "combine: channels-last only");
+  const int st = combine_check(a, b, out);
+  if (st) return st;
   EwArgs e;
   e.a = tv(a); e.b = b ? tv(b) : tv(a); e.o = tv(out); e.ta = nl(ta); e.tb = nl(tb); e.m1 = e.m2 = nullptr; e.hasb = b ? 1 : 0;
   e.pa = ta && ta->per_item ? 1 : 0;
   e.pb = b && tb && tb->per_item ? 1 : 0;
-  const bool v4 = vec4_rd(a) && vec4_wr(out) && (!b || vec4_rd(b));
-  const long long total = (long long)out->n * out->d * out->h * out->w * (v4 ? (out->c + 3) / 4 : out->c);
-  // storage: all fp32, or all bf16 (the wide forward activations of bf16 precision)
-  const bool abf = is_bf16(a), bbf = b ? is_bf16(b) : abf, obf = is_bf16(out);
-  MMTTA_CHECK((abf == bbf && bbf == obf), MMTTA_ERR_UNSUPPORTED, "combine: operands must share one storage type");
-  const dim3 grid(grid_for(total));
+  const PwRoute r = combine_plan(a, b, out);
+  const bool v4 = r.vec == 4, abf = is_bf16(a);
+  const dim3 grid((unsigned)r.grid_x);
   hipStream_t s = (hipStream_t)stream;
   {
-    // octet form: C a power of two in [8, 2048], voxel-dense tensors, 16-byte aligned octets, 32-bit offsets inside an item
-    const int C = out->c;
-    const long long dhw = (long long)out->d * out->h * out->w;
-    auto dense = [](const mmtta_tensor* t) { return t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
-    const int per = abf ? 8 : 4;
-    auto al = [per](const mmtta_tensor* t) { return ((uintptr_t)t->ptr) % 16 == 0 && t->sw % per == 0 && t->sn % per == 0; };
-    const bool pow2 = C >= 8 && C <= 2048 && (C & (C - 1)) == 0;
-    const bool ok8 = v4 && pow2 && dense(a) && dense(out) && al(a) && al(out) && (!b || (dense(b) && al(b))) &&
-                     dhw * std::max(std::max(a->sw, out->sw), b ? b->sw : (int64_t)0) < (1LL << 31);
-    if (ok8) {
+    if (r.family == MMTTA_PW_COMBINE8) {
+      const int C = out->c;
+      const long long dhw = vox_count(out);
       Cb8Args q;
       q.a = (const float*)a->ptr; q.b = b ? (const float*)b->ptr : nullptr; q.o = (float*)out->ptr;
       q.asn = a->sn; q.bsn = b ? b->sn : 0; q.osn = out->sn;
       q.asw = (unsigned)a->sw; q.bsw = b ? (unsigned)b->sw : 0u; q.osw = (unsigned)out->sw;
       q.C = C; q.dhw = (unsigned)dhw; q.ta = e.ta; q.tb = e.tb; q.pa = e.pa; q.pb = e.pb;
-      if (abf) { if (b) launch_combine8<true, true>(q, out->n, s); else launch_combine8<true, false>(q, out->n, s); }
-      else { if (b) launch_combine8<false, true>(q, out->n, s); else launch_combine8<false, false>(q, out->n, s); }
+      if (abf) { if (b) launch_combine8<true, true>(q, r, s); else launch_combine8<true, false>(q, r, s); }
+      else { if (b) launch_combine8<false, true>(q, r, s); else launch_combine8<false, false>(q, r, s); }
       return launch_status("combine");
     }
   }
@@ -1134,22 +1268,21 @@ int combine_body(const mmtta_tensor* a, const mmtta_norm_on_load* ta, const mmtt
 
 int norm_bwd_reduce_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
                          float* part, void* stream) {
-  MMTTA_CHECK(dout && y && t && part && dout->ptr && y->ptr && t->mean && t->rstd, MMTTA_ERR_INVALID, "norm bwd reduce: null argument");
-  // (a bf16-stored gradient sits next to a bf16-stored activation - or, <= 4 channels, next to an fp32-stored one: the thin
-  // full-resolution tensors keep their activations fp32, round 3)
-  MMTTA_CHECK(!is_bf16(dout) || is_bf16(y) || y->c <= 4, MMTTA_ERR_UNSUPPORTED, "norm bwd reduce: a bf16-stored gradient needs a bf16-stored activation");
-  MMTTA_CHECK(same_shape(dout, y) && is_cl(dout) && is_cl(y), MMTTA_ERR_INVALID, "norm bwd reduce: shape/layout mismatch");
+  MMTTA_CHECK(part != nullptr, MMTTA_ERR_INVALID, "norm bwd reduce: null argument");
+  const int st = norm_bwd_reduce_check(dout, y, t);
+  if (st) return st;
   RedArgs a;
   a.x = tv(y); a.dout = tv(dout); a.t = nl(t); a.per_item = t->per_item != 0 ? 1 : 0; a.part = part;
   rows_geometry(y, a.rows_per_n, a.vox_per_row);
-  const dim3 grid(y->n * a.rows_per_n);
+  const PwRoute r = reduce_plan(y, dout);
+  const dim3 grid((unsigned)r.grid_x);
   hipStream_t s = (hipStream_t)stream;
-  const bool v4 = vec4_rd(y) && vec4_rd(dout);
-  if (reduce_stream_ok(y, dout)) {
+  const bool v4 = r.vec == 4;
+  if (r.family == MMTTA_PW_REDUCE_STREAM) {
     const RedSArgs q = reduce_stream_args(y, dout, t, part);
     MMTTA_BF_DISPATCH(is_bf16(y), XBF, {
-      if (is_bf16(dout)) launch_reduce_stream<1, XBF, true>(q, y->n, s);
-      else launch_reduce_stream<1, XBF, false>(q, y->n, s);
+      if (is_bf16(dout)) launch_reduce_stream<1, XBF, true>(q, r, s);
+      else launch_reduce_stream<1, XBF, false>(q, r, s);
     });
     return launch_status("norm bwd reduce");
   }
@@ -1171,34 +1304,20 @@ int norm_bwd_reduce_body(const mmtta_tensor* dout, const mmtta_tensor* y, const 
 
 int norm_bwd_apply_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
                         const float* m1, const float* m2, const mmtta_tensor* dy, void* stream) {
-  MMTTA_CHECK(dout && y && t && dy && m1 && m2 && t->mean && t->rstd, MMTTA_ERR_INVALID, "norm bwd apply: null argument");
-  MMTTA_CHECK(dout->dtype == dy->dtype && (!is_bf16(dout) || is_bf16(y) || y->c <= 4), MMTTA_ERR_UNSUPPORTED,
-              "norm bwd apply: `dout` and `dy` share one storage type (bf16 only next to a bf16-stored activation)");
+  const int st = norm_bwd_apply_check(dout, y, t, m1, m2, dy);
+  if (st) return st;
   const bool dbf = is_bf16(dout);
-  MMTTA_CHECK(same_shape(dout, y) && same_shape(dy, y), MMTTA_ERR_INVALID, "norm bwd apply: shape mismatch");
-  MMTTA_CHECK(is_cl(dout) && is_cl(y) && is_cl(dy), MMTTA_ERR_UNSUPPORTED, "norm bwd apply: channels-last only");
   EwArgs e;
   e.a = tv(dout); e.b = tv(y); e.o = tv(dy); e.ta = nl(t); e.tb = nl(nullptr); e.m1 = m1; e.m2 = m2; e.hasb = 1;
   e.pa = t->per_item ? 1 : 0; e.pb = 0;
-  const bool v4 = vec4_rd(dout) && vec4_rd(y) && vec4_wr(dy);
-  const long long total = (long long)y->n * y->d * y->h * y->w * (v4 ? (y->c + 3) / 4 : y->c);
-  const dim3 grid(grid_for(total));
+  const PwRoute r = norm_bwd_apply_plan(dout, y, t, m1, m2, dy);
+  const bool v4 = r.vec == 4;
+  const dim3 grid((unsigned)r.grid_x);
   hipStream_t s = (hipStream_t)stream;
   {
-    // octet form: C a power of two in [8, 2048], voxel-dense tensors, 16-byte aligned octets, 32-bit offsets inside an item
-    const int C = y->c;
-    const long long dhw = (long long)y->d * y->h * y->w;
-    auto dense = [](const mmtta_tensor* t) { return t->sh == (int64_t)t->w * t->sw && t->sd == (int64_t)t->h * t->sh; };
-    auto al = [](const mmtta_tensor* t, int per) {
-      return ((uintptr_t)t->ptr) % 16 == 0 && t->sw % per == 0 && t->sn % per == 0;
-    };
-    const bool pow2 = C >= 8 && C <= 2048 && (C & (C - 1)) == 0;
-    const bool ok8 = v4 && pow2 && dense(dout) && dense(y) && dense(dy) && al(dout, dbf ? 8 : 4) && al(dy, dbf ? 8 : 4) &&
-                     al(y, is_bf16(y) ? 8 : 4) &&
-                     ((uintptr_t)t->mean % 16 == 0) && ((uintptr_t)t->rstd % 16 == 0) && ((uintptr_t)m1 % 16 == 0) &&
-                     ((uintptr_t)m2 % 16 == 0) && (!t->gamma || (uintptr_t)t->gamma % 16 == 0) &&
-                     (!t->beta || (uintptr_t)t->beta % 16 == 0) && dhw * std::max(std::max(dout->sw, y->sw), dy->sw) < (1LL << 31);
-    if (ok8) {
+    if (r.family == MMTTA_PW_NORM_BWD_APPLY8) {
+      const int C = y->c;
+      const long long dhw = vox_count(y);
       Nb8Args q;
       q.dout = (const float*)dout->ptr; q.y = (const float*)y->ptr; q.o = (float*)dy->ptr;
       q.dsn = dout->sn; q.ysn = y->sn; q.osn = dy->sn;
@@ -1206,10 +1325,8 @@ int norm_bwd_apply_body(const mmtta_tensor* dout, const mmtta_tensor* y, const m
       q.C = C; q.relu = act_arg(t); q.dhw = (unsigned)dhw;
       q.mean = t->mean; q.rstd = t->rstd; q.gamma = t->gamma; q.beta = t->beta; q.m1 = m1; q.m2 = m2;
       q.per_item = t->per_item != 0 ? 1 : 0;
-      const long long nvl = 256 / (C / 8);
-      const bool four = dhw / (nvl * 4) >= 1024;
-      const long long per = nvl * (four ? 4 : 2);
-      const dim3 g8((unsigned)((dhw + per - 1) / per), (unsigned)y->n);
+      const bool four = r.it == 4;
+      const dim3 g8((unsigned)r.grid_x, (unsigned)r.grid_y);
       if (dbf) {
         if (four) hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 4, true>), g8, dim3(256), 0, s, q);
         else hipLaunchKernelGGL((norm_bwd_apply8_kernel<true, 2, true>), g8, dim3(256), 0, s, q);
@@ -1245,12 +1362,23 @@ bool nbs_ok(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on
   if (!dout || !y || !t || !dy || !t->mean || !t->rstd) return false;
   if (dout->dtype != dy->dtype || (is_bf16(dout) && !is_bf16(y))) return false;
   if (!same_shape(dout, y) || !same_shape(dy, y) || !is_cl(dout) || !is_cl(y) || !is_cl(dy)) return false;
-  const long long dhw = (long long)y->d * y->h * y->w;
-  auto dense = [](const mmtta_tensor* x) { return x->sh == (int64_t)x->w * x->sw && x->sd == (int64_t)x->h * x->sh; };
-  auto al = [](const mmtta_tensor* x, int per) { return ((uintptr_t)x->ptr) % 16 == 0 && x->sw % per == 0 && x->sn % per == 0; };
-  auto a16 = [](const void* p) { return p == nullptr || ((uintptr_t)p) % 16 == 0; };
-  return y->c % 32 == 0 && dhw >= 1 && dhw <= 4096 && dense(dout) && dense(y) && dense(dy) && al(dout, is_bf16(dout) ? 8 : 4) &&
-         al(dy, is_bf16(dy) ? 8 : 4) && al(y, is_bf16(y) ? 8 : 4) && a16(t->mean) && a16(t->rstd) && a16(t->gamma) && a16(t->beta);
+  const long long dhw = vox_count(y);
+  return y->c % 32 == 0 && dhw >= 1 && dhw <= 4096 && dense_voxels(dout) && dense_voxels(y) && dense_voxels(dy) &&
+         oct_aligned(dout) && oct_aligned(dy) && oct_aligned(y) && null_or_16(t->mean) && null_or_16(t->rstd) &&
+         null_or_16(t->gamma) && null_or_16(t->beta);
+}
+
+// one workgroup per 32 channels of an item: 4 channel octets x 64 voxel lanes, 2 voxels in flight per lane
+PwRoute norm_bwd_small_plan(const mmtta_tensor* dout, const mmtta_tensor* y) {
+  PwRoute r = {};
+  r.family = MMTTA_PW_NORM_BWD_SMALL; r.mode = 1; r.has_b = 1; r.vec = 8; r.it = 2;
+  r.bf16_a = r.bf16_o = is_bf16(dout) ? 1 : 0; r.bf16_b = is_bf16(y) ? 1 : 0;
+  const long long dhw = vox_count(y);
+  r.cpl = 4; r.nvl = 64; r.trips = (int)((dhw + 127) / 128) * 2;
+  r.rows_per_n = 1; r.rows_per_block = 1; r.vox_per_row = dhw; r.cb_passes = 1;
+  r.grid_x = y->c / 32; r.grid_y = y->n;
+  r.work_items = dhw * y->n * (y->c / 8);
+  return r;
 }
 
 int norm_bwd_small_body(const mmtta_tensor* dout, const mmtta_tensor* y, const mmtta_norm_on_load* t,
@@ -1264,7 +1392,8 @@ int norm_bwd_small_body(const mmtta_tensor* dout, const mmtta_tensor* y, const m
   q.C = y->c; q.relu = act_arg(t); q.dhw = (unsigned)((long long)y->d * y->h * y->w); q.count = (double)count;
   q.mean = t->mean; q.rstd = t->rstd; q.gamma = t->gamma; q.beta = t->beta;
   q.per_item = t->per_item != 0 ? 1 : 0;
-  const dim3 grid((unsigned)(y->c / 32), (unsigned)y->n);
+  const PwRoute r = norm_bwd_small_plan(dout, y);
+  const dim3 grid((unsigned)r.grid_x, (unsigned)r.grid_y);
   if (is_bf16(dout)) hipLaunchKernelGGL((norm_bwd_small_kernel<true, true>), grid, dim3(256), 0, (hipStream_t)stream, q);
   else if (is_bf16(y)) hipLaunchKernelGGL(norm_bwd_small_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, q);
   else hipLaunchKernelGGL(norm_bwd_small_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, q);
@@ -1464,15 +1593,38 @@ extern "C" int mmtta_norm_bwd_small(const mmtta_tensor* dout, const mmtta_tensor
   return nl_leaky(t) ? leaky::norm_bwd_small_body(dout, y, t, count, dy, stream) : norm_bwd_small_body(dout, y, t, count, dy, stream);
 }
 
-extern "C" int mmtta_upsample2x_fwd(const mmtta_tensor* x, const mmtta_tensor* y, void* stream) {
+static int upsample_fwd_check(const mmtta_tensor* x, const mmtta_tensor* y) {
   MMTTA_CHECK(x && y && x->ptr && y->ptr, MMTTA_ERR_INVALID, "upsample: null tensor");
   MMTTA_CHECK(x->dtype == y->dtype, MMTTA_ERR_UNSUPPORTED, "mmtta_upsample2x_fwd: `x` and `y` must share one storage type");
   MMTTA_CHECK(y->n == x->n && y->c == x->c && y->d == 2 * x->d && y->h == 2 * x->h && y->w == 2 * x->w, MMTTA_ERR_INVALID,
               "upsample: y must be exactly 2x of x");
   MMTTA_CHECK(is_cl(x) && is_cl(y), MMTTA_ERR_UNSUPPORTED, "upsample: channels-last only");
-  const bool v4 = vec4_rd(x) && vec4_wr(y);
-  const long long total = (long long)y->n * y->d * y->h * y->w * (v4 ? (y->c + 3) / 4 : y->c);
-  const dim3 ug(grid_for(total, 16384));
+  return MMTTA_OK;
+}
+static int upsample_bwd_check(const mmtta_tensor* dy, const mmtta_tensor* dx) {
+  MMTTA_CHECK(dx && dy && dx->ptr && dy->ptr, MMTTA_ERR_INVALID, "upsample bwd: null tensor");
+  MMTTA_CHECK(dy->dtype == dx->dtype, MMTTA_ERR_UNSUPPORTED, "mmtta_upsample2x_bwd: `dy` and `dx` must share one storage type");
+  MMTTA_CHECK(dy->n == dx->n && dy->c == dx->c && dy->d == 2 * dx->d && dy->h == 2 * dx->h && dy->w == 2 * dx->w,
+              MMTTA_ERR_INVALID, "upsample bwd: dy must be exactly 2x of dx");
+  MMTTA_CHECK(is_cl(dx) && is_cl(dy), MMTTA_ERR_UNSUPPORTED, "upsample bwd: channels-last only");
+  return MMTTA_OK;
+}
+// both directions: one thread per (voxel, channel vector) of the tensor written, `src` the tensor read
+static PwRoute upsample_plan(int family, const mmtta_tensor* src, const mmtta_tensor* dst) {
+  PwRoute r = {};
+  const bool v4 = vec4_rd(src) && vec4_wr(dst);
+  r.family = family; r.vec = v4 ? 4 : 1;
+  r.bf16_a = r.bf16_o = is_bf16(dst) ? 1 : 0;
+  route_grid_stride(r, (long long)dst->n * vox_count(dst) * (v4 ? (dst->c + 3) / 4 : dst->c), 16384);
+  return r;
+}
+
+extern "C" int mmtta_upsample2x_fwd(const mmtta_tensor* x, const mmtta_tensor* y, void* stream) {
+  const int st = upsample_fwd_check(x, y);
+  if (st) return st;
+  const PwRoute r = upsample_plan(MMTTA_PW_UPSAMPLE_FWD, x, y);
+  const bool v4 = r.vec == 4;
+  const dim3 ug((unsigned)r.grid_x);
   if (is_bf16(x)) {
     if (v4) hipLaunchKernelGGL((upsample_fwd_kernel<4, true>), ug, dim3(256), 0, (hipStream_t)stream, tv(x), tv(y));
     else hipLaunchKernelGGL((upsample_fwd_kernel<1, true>), ug, dim3(256), 0, (hipStream_t)stream, tv(x), tv(y));
@@ -1484,14 +1636,11 @@ extern "C" int mmtta_upsample2x_fwd(const mmtta_tensor* x, const mmtta_tensor* y
 }
 
 extern "C" int mmtta_upsample2x_bwd(const mmtta_tensor* dy, const mmtta_tensor* dx, int accumulate, void* stream) {
-  MMTTA_CHECK(dx && dy && dx->ptr && dy->ptr, MMTTA_ERR_INVALID, "upsample bwd: null tensor");
-  MMTTA_CHECK(dy->dtype == dx->dtype, MMTTA_ERR_UNSUPPORTED, "mmtta_upsample2x_bwd: `dy` and `dx` must share one storage type");
-  MMTTA_CHECK(dy->n == dx->n && dy->c == dx->c && dy->d == 2 * dx->d && dy->h == 2 * dx->h && dy->w == 2 * dx->w,
-              MMTTA_ERR_INVALID, "upsample bwd: dy must be exactly 2x of dx");
-  MMTTA_CHECK(is_cl(dx) && is_cl(dy), MMTTA_ERR_UNSUPPORTED, "upsample bwd: channels-last only");
-  const bool v4 = vec4_rd(dy) && vec4_wr(dx);
-  const long long total = (long long)dx->n * dx->d * dx->h * dx->w * (v4 ? (dx->c + 3) / 4 : dx->c);
-  const dim3 ug(grid_for(total, 16384));
+  const int st = upsample_bwd_check(dy, dx);
+  if (st) return st;
+  const PwRoute r = upsample_plan(MMTTA_PW_UPSAMPLE_BWD, dy, dx);
+  const bool v4 = r.vec == 4;
+  const dim3 ug((unsigned)r.grid_x);
   if (is_bf16(dy)) {
     if (v4) hipLaunchKernelGGL((upsample_bwd_kernel<4, true>), ug, dim3(256), 0, (hipStream_t)stream, tv(dy), tv(dx), accumulate);
     else hipLaunchKernelGGL((upsample_bwd_kernel<1, true>), ug, dim3(256), 0, (hipStream_t)stream, tv(dy), tv(dx), accumulate);
@@ -1502,25 +1651,40 @@ extern "C" int mmtta_upsample2x_bwd(const mmtta_tensor* dy, const mmtta_tensor* 
   return launch_status("upsample bwd");
 }
 
-extern "C" int mmtta_lincomb(int count, const mmtta_tensor* const* in, const float* w, const mmtta_tensor* out,
-                             int accumulate, void* stream) {
-  MMTTA_CHECK(count >= 1 && count <= 8 && in && w && out && out->ptr, MMTTA_ERR_INVALID, "lincomb: bad argument");
+static int lincomb_check(int count, const mmtta_tensor* const* in, const mmtta_tensor* out) {
+  MMTTA_CHECK(count >= 1 && count <= 8 && in && out && out->ptr, MMTTA_ERR_INVALID, "lincomb: bad argument");
   for (int i = 0; i < count; ++i)
     MMTTA_CHECK(in[i] != nullptr && in[i]->dtype == in[0]->dtype, MMTTA_ERR_UNSUPPORTED, "lincomb: the inputs must share one storage type");
-  const bool ibf = is_bf16(in[0]), obf = is_bf16(out);
-  LinArgs e;
-  bool v4 = vec4_wr(out);
-  for (int k = 0; k < count; ++k) {
+  for (int k = 0; k < count; ++k)
     MMTTA_CHECK(in[k] && in[k]->ptr && same_shape(in[k], out) && is_cl(in[k]), MMTTA_ERR_INVALID, "lincomb: input %d mismatch", k);
+  MMTTA_CHECK(is_cl(out), MMTTA_ERR_UNSUPPORTED, "lincomb: channels-last only");
+  return MMTTA_OK;
+}
+static PwRoute lincomb_plan(int count, const mmtta_tensor* const* in, const mmtta_tensor* out) {
+  PwRoute r = {};
+  bool v4 = vec4_wr(out);
+  for (int k = 0; k < count; ++k) v4 = v4 && vec4_rd(in[k]);
+  r.family = MMTTA_PW_LINCOMB; r.vec = v4 ? 4 : 1; r.count = count;
+  r.bf16_a = is_bf16(in[0]) ? 1 : 0; r.bf16_o = is_bf16(out) ? 1 : 0;
+  route_grid_stride(r, (long long)out->n * vox_count(out) * (v4 ? (out->c + 3) / 4 : out->c));
+  return r;
+}
+
+extern "C" int mmtta_lincomb(int count, const mmtta_tensor* const* in, const float* w, const mmtta_tensor* out,
+                             int accumulate, void* stream) {
+  MMTTA_CHECK(w != nullptr, MMTTA_ERR_INVALID, "lincomb: bad argument");
+  const int cs = lincomb_check(count, in, out);
+  if (cs) return cs;
+  const PwRoute r = lincomb_plan(count, in, out);
+  const bool ibf = r.bf16_a != 0, obf = r.bf16_o != 0, v4 = r.vec == 4;
+  LinArgs e;
+  for (int k = 0; k < count; ++k) {
     e.in[k] = tv(in[k]);
     e.w[k] = w[k];
-    v4 = v4 && vec4_rd(in[k]);
   }
   for (int k = count; k < 8; ++k) { e.in[k] = e.in[0]; e.w[k] = 0.f; }
-  MMTTA_CHECK(is_cl(out), MMTTA_ERR_UNSUPPORTED, "lincomb: channels-last only");
   e.count = count; e.o = tv(out); e.accumulate = accumulate;
-  const long long total = (long long)out->n * out->d * out->h * out->w * (v4 ? (out->c + 3) / 4 : out->c);
-  const dim3 grid(grid_for(total)), block(256);
+  const dim3 grid((unsigned)r.grid_x), block(256);
   hipStream_t st = (hipStream_t)stream;
 #define MMTTA_LINCOMB_S(N, I, O) \
   do { if (v4) hipLaunchKernelGGL((lincomb_kernel<4, N, I, O>), grid, block, 0, st, e); \
@@ -1535,5 +1699,72 @@ extern "C" int mmtta_lincomb(int count, const mmtta_tensor* const* in, const flo
 #undef MMTTA_LINCOMB
 #undef MMTTA_LINCOMB_S
   return launch_status("lincomb");
+}
+
+extern "C" int mmtta_pointwise_route(int op, const mmtta_tensor* const* operands, int count, const mmtta_norm_on_load* t,
+                                     const mmtta_norm_on_load* t2, const float* m1, const float* m2,
+                                     mmtta_pointwise_route_t* out) {
+  MMTTA_CHECK(operands && out && count >= 1 && count <= 9, MMTTA_ERR_INVALID, "pointwise route: bad argument");
+  for (int i = 0; i < count; ++i) MMTTA_CHECK(operands[i] != nullptr, MMTTA_ERR_INVALID, "pointwise route: null operand %d", i);
+  auto wants = [&](int k) { return count == k; };
+  int st = MMTTA_OK;
+  PwRoute r = {};
+  switch (op) {
+    case MMTTA_PW_OP_CHANNEL_STATS:
+      MMTTA_CHECK(wants(1), MMTTA_ERR_INVALID, "pointwise route: channel stats takes {x}");
+      MMTTA_CHECK(operands[0]->ptr, MMTTA_ERR_INVALID, "channel_stats: null argument");
+      MMTTA_CHECK(is_cl(operands[0]), MMTTA_ERR_UNSUPPORTED, "channel_stats: tensor must be channels-last");
+      r = reduce_plan(operands[0], nullptr);
+      break;
+    case MMTTA_PW_OP_NORM_BWD_REDUCE:
+      MMTTA_CHECK(wants(2), MMTTA_ERR_INVALID, "pointwise route: norm bwd reduce takes {dout, y}");
+      if ((st = nl_act_check(t, "norm bwd reduce")) || (st = norm_bwd_reduce_check(operands[0], operands[1], t))) return st;
+      r = reduce_plan(operands[1], operands[0]);
+      r.leaky = nl_leaky(t) ? 1 : 0;
+      break;
+    case MMTTA_PW_OP_NORM_BWD_APPLY:
+      MMTTA_CHECK(wants(3), MMTTA_ERR_INVALID, "pointwise route: norm bwd apply takes {dout, y, dy}");
+      if ((st = nl_act_check(t, "norm bwd apply")) || (st = norm_bwd_apply_check(operands[0], operands[1], t, m1, m2, operands[2])))
+        return st;
+      r = norm_bwd_apply_plan(operands[0], operands[1], t, m1, m2, operands[2]);
+      r.leaky = nl_leaky(t) ? 1 : 0;
+      break;
+    case MMTTA_PW_OP_NORM_BWD_SMALL:
+      MMTTA_CHECK(wants(3), MMTTA_ERR_INVALID, "pointwise route: norm bwd (one launch) takes {dout, y, dy}");
+      if ((st = nl_act_check(t, "norm bwd (one launch)"))) return st;
+      MMTTA_CHECK(nbs_ok(operands[0], operands[1], t, operands[2]), MMTTA_ERR_UNSUPPORTED,
+                  "norm bwd (one launch): tensors not eligible (mmtta_norm_bwd_small_ok)");
+      r = norm_bwd_small_plan(operands[0], operands[1]);
+      r.leaky = nl_leaky(t) ? 1 : 0;
+      break;
+    case MMTTA_PW_OP_COMBINE: {
+      MMTTA_CHECK(wants(2) || wants(3), MMTTA_ERR_INVALID, "pointwise route: combine takes {a, out} or {a, b, out}");
+      const mmtta_tensor* b = count == 3 ? operands[1] : nullptr;
+      if ((st = nl_act_check(t, "combine (ta)")) || (b && (st = nl_act_check(t2, "combine (tb)")))) return st;
+      if ((st = combine_check(operands[0], b, operands[count - 1]))) return st;
+      r = combine_plan(operands[0], b, operands[count - 1]);
+      r.leaky = nl_leaky(t) || (b && nl_leaky(t2)) ? 1 : 0;
+      break;
+    }
+    case MMTTA_PW_OP_LINCOMB:
+      MMTTA_CHECK(count >= 2, MMTTA_ERR_INVALID, "pointwise route: lincomb takes {in[0..k-1], out}");
+      if ((st = lincomb_check(count - 1, operands, operands[count - 1]))) return st;
+      r = lincomb_plan(count - 1, operands, operands[count - 1]);
+      break;
+    case MMTTA_PW_OP_UPSAMPLE_FWD:
+      MMTTA_CHECK(wants(2), MMTTA_ERR_INVALID, "pointwise route: upsample takes {x, y}");
+      if ((st = upsample_fwd_check(operands[0], operands[1]))) return st;
+      r = upsample_plan(MMTTA_PW_UPSAMPLE_FWD, operands[0], operands[1]);
+      break;
+    case MMTTA_PW_OP_UPSAMPLE_BWD:
+      MMTTA_CHECK(wants(2), MMTTA_ERR_INVALID, "pointwise route: upsample bwd takes {dy, dx}");
+      if ((st = upsample_bwd_check(operands[0], operands[1]))) return st;
+      r = upsample_plan(MMTTA_PW_UPSAMPLE_BWD, operands[0], operands[1]);
+      break;
+    default:
+      MMTTA_CHECK(false, MMTTA_ERR_INVALID, "pointwise route: op %d", op);
+  }
+  *out = r;
+  return MMTTA_OK;
 }
 #endif  // MMTTA_ACT_LEAKY_TU

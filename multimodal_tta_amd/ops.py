@@ -765,6 +765,24 @@ def lincomb(inputs: Sequence[torch.Tensor], weights: Sequence[float], out: torch
     check(_lib.load().mmtta_lincomb(k, arr, w, C.byref(to), 1 if accumulate else 0, stream_ptr()), "lincomb")
 
 
+def pointwise_route(op: str, operands: Sequence, nl=None, nl2=None, m1=None, m2=None) -> Dict[str, object]:
+    """Which kernel of csrc/pointwise.hip the entry point `op` (one of _lib.PW_OPS) launches for these operands, and its launch
+    geometry: mmtta_pointwise_route_t as a dict, `family` by name.  Host-only - nothing is launched.  `operands` in the
+    order of include/mmtta.h: tensors (channels-last views) or ready _lib.Tensor descriptors; `nl` / `nl2` NL objects or
+    _lib.NormOnLoad structs; `m1` / `m2` tensors or addresses (norm_bwd_apply: read for their alignment)."""
+    descs = [t if isinstance(t, _lib.Tensor) else desc_cl(t) for t in operands]
+    arr = (C.POINTER(_lib.Tensor) * len(descs))(*[C.pointer(d) for d in descs])
+    structs = [None if t is None else (t.struct() if isinstance(t, NL) else t) for t in (nl, nl2)]
+    refs = [None if s is None else C.byref(s) for s in structs]
+    addr = [a if a is None or isinstance(a, int) else ptr(a) for a in (m1, m2)]
+    out = _lib.PointwiseRoute()
+    check(_lib.load().mmtta_pointwise_route(_lib.PW_OPS.index(op), arr, len(descs), refs[0], refs[1], addr[0], addr[1],
+                                            C.byref(out)), f"pointwise_route({op})")
+    route = {name: int(getattr(out, name)) for name, _ in _lib.PointwiseRoute._fields_}
+    route["family"] = _lib.PW_FAMILIES[route["family"]]
+    return route
+
+
 # ----------------------------------------------------------------------------- loss / optimizer / metric
 def entropy_partials(logits: torch.Tensor) -> int:
     t = desc_cl(logits)
