@@ -879,6 +879,33 @@ int mmtta_components_filter(const uint8_t* mask_in, uint8_t* mask_out, const mmt
                             int w, int connectivity, const int64_t* min_voxels, const int32_t* keep_largest, int64_t* counts,
                             int64_t* stats, int32_t* labels, void* scratch, void* stream);
 
+/* Lesion-wise scores of the evaluation tail, after the BraTS-2023 lesion-wise evaluation: every ground-truth lesion is
+ * scored on its own, every unmatched predicted component counts against the volume.  Replaces a host
+ * `scipy.ndimage.binary_dilation` and two `scipy.ndimage.label` per (volume, region) over masks copied off the device.
+ * Per (n, r), with P = mask != 0 and G = label > 0.5:
+ *   Gd        G dilated `iterations` (0 ... 8) times with the 6 / 18 / 26 neighbourhood (`dilation_connectivity`), voxels
+ *             outside the volume are background: scipy's binary_dilation(G, generate_binary_structure(3, 1 | 2 | 3), iterations)
+ *   lesions   the 26-connected components of Gd; lesion g's own voxels are G within component g; g is KEPT iff it has at
+ *             least min_lesion_voxels[r] own voxels
+ *   matching  a 26-connected component of P is matched to lesion g iff one of its voxels lies in component g of Gd (it may
+ *             match several lesions and counts for each; lesions that are not kept still match)
+ *   Dice      P_g = union of the whole components matched to g, inter = |P_g & own_g|, den = |P_g| + |own_g|;
+ *             q_g = (2 inter 2^30 + den / 2) / den in unsigned 64-bit integer division, 0 for an unmatched lesion
+ *   mask      uint8 [N,R,D,H,W] dense, not written;  label  fp32, any strides
+ *   min_lesion_voxels  HOST int64 [R], read before return
+ *   stats     int64 [N][R][7] on the device, zeroed by this call: lesions, lesions kept, kept lesions with a match,
+ *             predicted components, matched components, sum of q_g over the kept lesions, voxels of unmatched components
+ *   labels    int32 [N,R,D,H,W] dense on the device or NULL: on the voxels of G the lesion's label (1 + the smallest linear
+ *             index of its Gd component, the convention of mmtta_components_filter), 0 elsewhere
+ *   scratch   mmtta_lesionwise_scratch_bytes(N*R, D, H, W) bytes (negative: unsupported extent)
+ * A fixed sequence of launches on `stream` that depends on the shape alone: no host read, no convergence flag.  Everything
+ * is an integer: two calls agree bit for bit and a batch gives what its items give alone.  Limits: those of
+ * mmtta_components_filter.  Anything else is refused with MMTTA_ERR_INVALID / _UNSUPPORTED before anything is queued. */
+int64_t mmtta_lesionwise_scratch_bytes(int64_t n_masks, int64_t d, int64_t h, int64_t w);
+int mmtta_lesionwise_scores(const uint8_t* mask, const mmtta_tensor* label, int n, int r, int d, int h, int w, int iterations,
+                            int dilation_connectivity, const int64_t* min_lesion_voxels, int64_t* stats, int32_t* labels,
+                            void* scratch, void* stream);
+
 /* Surface metrics of the evaluation tail: percentile Hausdorff distance and average surface distance per
  * (volume, region).  Replaces the MONAI calls of reference src/evaluation/seg_eval.py:312-340
  * (`HausdorffDistanceMetric(include_background=True, reduction="none", percentile=95, directed=False)` built at

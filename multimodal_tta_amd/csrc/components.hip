@@ -19,35 +19,10 @@
 // Only the backward half of the neighbourhood is visited (3 / 9 / 13 neighbours for connectivity 6 / 18 / 26); neighbour
 // tests are on (z, y, x), never on the linear index.  The launch sequence depends on the shape alone; all sums are integers
 // and a root is the smallest index of its component, so results do not depend on scheduling.
-#include "common.h"
+// K1 - K3 are also the labeller of the lesion-wise scores (lesionwise.hip) through cc_label (components.h).
+#include "components.h"
 
 namespace mmtta {
-
-constexpr int CC_TZ = 4, CC_TY = 8, CC_TX = 32;
-constexpr int CC_TILE = CC_TZ * CC_TY * CC_TX;      // 1024 voxels, 4 per thread, 4 KB of LDS
-constexpr int CC_MAX_R = 64;
-constexpr long long CC_MAX_V = 2147483646ll;        // label = index + 1 stays an int32
-constexpr long long CC_MAX_BLOCKS = 16777215ll;     // workgroups of 256 threads in one launch: fewer than 2^32 threads
-
-struct CcArgs {
-  const unsigned char* mask_in;   // [M][V]
-  unsigned char* mask_out;        // [M][V] or the same buffer (read in K1 only, written in K5 only)
-  TV lab;                         // ground truth, used when counts != nullptr
-  int M, R, D, H, W, maxn;        // maxn: largest |dz| + |dy| + |dx| of a neighbour (1, 2, 3)
-  int tz, ty, tx;                 // tiles per axis
-  long long tiles;                // tz * ty * tx
-  long long V;
-  int* L;                         // [M][V] parent / label, 0-based, -1 background
-  unsigned int* size;             // [M][V] voxels of the component, at its root
-  unsigned long long* best;       // [M] (size << 32) | ~label of the largest surviving component, 0 = none
-  unsigned int* ncomp;            // [M]
-  unsigned int* nkept;            // [M]
-  unsigned long long* counts;     // [M][3] or nullptr
-  unsigned long long* stats;      // [M][3] or nullptr
-  int* labels_out;                // [M][V] or nullptr
-  unsigned long long keep_largest;          // bit r
-  unsigned long long min_voxels[CC_MAX_R];  // per region
-};
 
 __device__ __forceinline__ int cc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -244,6 +219,23 @@ __global__ __launch_bounds__(256) void cc_final_kernel(CcArgs a) {
   }
 }
 
+// K1 - K3 on `s`: a.L holds the root of every foreground voxel (-1 background), a.size the voxels of a component at its root
+// (added to what is there: the caller zeroes it), a.ncomp the components per mask (likewise).  Reads a.mask_in, the geometry
+// and a.maxn; shared with lesionwise.hip.
+int cc_label(const CcArgs& a, hipStream_t s) {
+  const long long M = a.M;
+  const long long tblocks = a.tiles < CC_MAX_BLOCKS / M ? a.tiles : CC_MAX_BLOCKS / M;      // >= 1: M <= 65535; further tiles loop
+  const dim3 vox((unsigned)((a.V + 255) / 256), (unsigned)M);
+  hipLaunchKernelGGL(cc_tile_kernel, dim3((unsigned)tblocks, (unsigned)M), dim3(256), 0, s, a);
+  int st = launch_status("components tile");
+  if (st) return st;
+  hipLaunchKernelGGL(cc_merge_kernel, vox, dim3(256), 0, s, a);
+  st = launch_status("components merge");
+  if (st) return st;
+  hipLaunchKernelGGL(cc_flatten_kernel, vox, dim3(256), 0, s, a);
+  return launch_status("components flatten");
+}
+
 static size_t cc_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace mmtta
@@ -301,7 +293,6 @@ extern "C" int mmtta_components_filter(const uint8_t* mask_in, uint8_t* mask_out
   MMTTA_CHECK(M * vblocks <= CC_MAX_BLOCKS, MMTTA_ERR_UNSUPPORTED,
               "components: %lld masks of %lld voxels in one call, at most 2^32 - 256 voxels (rounded up to 256 per mask): split the batch",
               M, V);
-  const long long tblocks = tiles < CC_MAX_BLOCKS / M ? tiles : CC_MAX_BLOCKS / M;      // >= 1: M <= 65535; further tiles loop
   const size_t mv = (size_t)M * (size_t)V;
   char* base = (char*)scratch;
   const size_t head = cc_align((size_t)M * 16);
@@ -324,14 +315,7 @@ extern "C" int mmtta_components_filter(const uint8_t* mask_in, uint8_t* mask_out
     MMTTA_CHECK(e == hipSuccess, MMTTA_ERR_LAUNCH, "components: memset failed: %s", hipGetErrorString(e));
   }
   const dim3 vox((unsigned)((V + 255) / 256), (unsigned)M);
-  hipLaunchKernelGGL(cc_tile_kernel, dim3((unsigned)tblocks, (unsigned)M), dim3(256), 0, s, a);
-  int st = launch_status("components tile");
-  if (st) return st;
-  hipLaunchKernelGGL(cc_merge_kernel, vox, dim3(256), 0, s, a);
-  st = launch_status("components merge");
-  if (st) return st;
-  hipLaunchKernelGGL(cc_flatten_kernel, vox, dim3(256), 0, s, a);
-  st = launch_status("components flatten");
+  int st = cc_label(a, s);
   if (st) return st;
   hipLaunchKernelGGL(cc_select_kernel, vox, dim3(256), 0, s, a);
   st = launch_status("components select");

@@ -109,6 +109,58 @@ def postprocess_config(config: Any) -> Tuple[bool, int, List[int], List[bool]]:
     return enable, int(conn), [int(v) for v in mv], [bool(v) for v in kl]
 
 
+LESIONWISE_CONNECTIVITIES = ops.COMPONENT_CONNECTIVITIES
+LESIONWISE_MAX_DILATION = ops.LESIONWISE_MAX_DILATION
+LESIONWISE_COLUMNS = 7       # table columns per region: lw_dc, valid, lesions kept, found, false-positive, matched, predicted components
+
+
+def lesionwise_config(config: Any) -> Tuple[bool, int, int, List[int]]:
+    """``evaluation.lesionwise: {enable, dilation, dilation_connectivity, min_lesion_voxels}`` -> (enable, dilation,
+    dilation_connectivity, min_lesion_voxels), the last as one entry per region of ``evaluation.seg.region_order``; off, 3,
+    18 and 0 when absent.  ``min_lesion_voxels`` is an int or a list of one int per region.  A value the kernel cannot take
+    is a ``ValueError`` that names its key, whether the block is enabled or not."""
+    lw = get_config(config, "evaluation.lesionwise", {}) or {}
+    R = len(list(get_config(config, "evaluation.seg.region_order", ["ET", "TC", "WT"])))
+    enable = get_config(lw, "enable", False)
+    if not isinstance(enable, bool):
+        raise ValueError(f"evaluation.lesionwise.enable must be true or false, got {enable!r}")
+    dil = get_config(lw, "dilation", 3)
+    if isinstance(dil, bool) or not isinstance(dil, int) or not 0 <= dil <= LESIONWISE_MAX_DILATION:
+        raise ValueError(f"evaluation.lesionwise.dilation must be an integer in 0 ... {LESIONWISE_MAX_DILATION}, got {dil!r}")
+    conn = get_config(lw, "dilation_connectivity", 18)
+    if isinstance(conn, bool) or conn not in LESIONWISE_CONNECTIVITIES:
+        raise ValueError(f"evaluation.lesionwise.dilation_connectivity must be one of {list(LESIONWISE_CONNECTIVITIES)}, "
+                         f"got {conn!r}")
+    v = get_config(lw, "min_lesion_voxels", 0)
+    scalar = isinstance(v, (bool, int))
+    vals = [v] * R if scalar else (list(v) if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else None)
+    if vals is None or not all(isinstance(x, int) and not isinstance(x, bool) and x >= 0 for x in vals):
+        raise ValueError(f"evaluation.lesionwise.min_lesion_voxels must be a non-negative integer or a list of one per region, "
+                         f"got {v!r}")
+    if len(vals) != R:
+        raise ValueError(f"evaluation.lesionwise.min_lesion_voxels has {len(vals)} entries for the {R} regions of "
+                         f"evaluation.seg.region_order")
+    return enable, int(dil), int(conn), [int(x) for x in vals]
+
+
+def lesionwise_columns(stats: torch.Tensor) -> torch.Tensor:
+    """stats int64 [R,7] of one volume (``ops.LESIONWISE_COLUMNS``) -> its table columns float64 [7*R]: lw_dc[R], valid[R],
+    lesions kept[R], lesions found[R], false-positive components[R], matched components[R], predicted components[R].
+
+        lw_dc = dice_q / 2^30 / (lesions kept + false-positive components),   valid = that denominator > 0
+
+    ``dice_q`` is an integer beyond what a double of the table could carry across a sum, so the volume's score is formed
+    here, from the integers, and only small counts travel beside it."""
+    s = stats.to(torch.int64)
+    kept, found, pred, matched = s[:, 1], s[:, 2], s[:, 3], s[:, 4]
+    fp = pred - matched
+    den = kept + fp
+    valid = den > 0
+    safe = torch.where(valid, den, torch.ones_like(den)).to(torch.float64)
+    lw = torch.where(valid, s[:, 5].to(torch.float64) / float(ops.LESIONWISE_Q_ONE) / safe, torch.zeros_like(safe))
+    return torch.cat([lw, valid.to(torch.float64)] + [c.to(torch.float64) for c in (kept, found, fp, matched, pred)])
+
+
 def calibration_from_bins(table: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """The table of ``ops.calibration_bins`` (float64 [..., 3*bins + 2]: per bin count, sum of confidence, correct count;
     then the Brier sum, then the NLL sum) -> (ece, brier, nll, valid), float64 / bool of the leading shape.
@@ -143,10 +195,13 @@ class RegionAccumulator:
     """float64 sums / counts per region, overall and per domain (reference seg_eval.py:250-270,363-378).  ``bins`` > 0
     adds the calibration figures: ``calibration_regions`` names their rows (default: the regions; ``["all"]`` for a softmax
     head), ``reliability`` pools the bins of every row.  ``components`` adds the connected-component figures of the
-    post-processing: per-volume means over ALL volumes of components found, components kept and voxels removed."""
+    post-processing: per-volume means over ALL volumes of components found, components kept and voxels removed.
+    ``lesionwise`` adds the lesion-wise figures: the lesion-wise Dice averaged over the volumes where it is defined (a
+    GT-empty region with false-positive components IS one of them, with 0), per-volume means of kept lesions, found
+    lesions and false-positive components, and recall / precision pooled over all volumes."""
 
     def __init__(self, region_order: Sequence[str], surface: bool = False, bins: int = 0,
-                 calibration_regions: Optional[Sequence[str]] = None, components: bool = False):
+                 calibration_regions: Optional[Sequence[str]] = None, components: bool = False, lesionwise: bool = False):
         self.regions = list(region_order)
         self.surface = bool(surface)
         R = len(self.regions)
@@ -166,6 +221,33 @@ class RegionAccumulator:
         self._zp = lambda: torch.zeros((4, R), dtype=torch.float64)          # sum_components, sum_kept, sum_removed, volumes
         self.pp_tot = self._zp()
         self.pp_dom: Dict[str, torch.Tensor] = defaultdict(self._zp)
+        self.lesionwise = bool(lesionwise)
+        # the 7 table columns summed (lw_dc, valid, kept, found, false-positive, matched, predicted), then the volumes
+        self._zl = lambda: torch.zeros((LESIONWISE_COLUMNS + 1, R), dtype=torch.float64)
+        self.lw_tot = self._zl()
+        self.lw_dom: Dict[str, torch.Tensor] = defaultdict(self._zl)
+
+    def add_lesionwise(self, cols: Any, domain: str) -> None:
+        """One volume's lesion-wise columns, [7*R] as the table holds them (``lesionwise_columns``)."""
+        c = torch.as_tensor(cols, dtype=torch.float64).reshape(LESIONWISE_COLUMNS, len(self.regions))
+        for acc in (self.lw_tot, self.lw_dom[domain]):
+            acc[0] += c[0] * c[1]
+            acc[1:LESIONWISE_COLUMNS] += c[1:]
+            acc[LESIONWISE_COLUMNS] += 1.0
+
+    def _lesionwise_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
+        means = self._fin(acc[0], acc[1])
+        for name, v in zip(self.regions, means):
+            out[f"{prefix}{name.lower()}_lw_dc"] = v
+        out[f"{prefix}avg_lw_dc"] = self._avg(means, acc[1])
+        for row, key in ((2, "lesions"), (3, "lesions_found"), (4, "fp_components")):
+            for name, v in zip(self.regions, self._fin(acc[row], acc[LESIONWISE_COLUMNS])):
+                out[f"{prefix}{name.lower()}_{key}"] = v
+        for k, name in enumerate(self.regions):       # pooled over the volumes; absent where there is nothing to divide by
+            if acc[2][k] > 0:
+                out[f"{prefix}{name.lower()}_lesion_recall"] = float((acc[3][k] / acc[2][k]).item())
+            if acc[6][k] > 0:
+                out[f"{prefix}{name.lower()}_lesion_precision"] = float((acc[5][k] / acc[6][k]).item())
 
     def add_components(self, stats: Any, domain: str) -> None:
         """One volume's component figures, [3*R] as the table holds them: components[R], kept[R], removed voxels[R]."""
@@ -203,10 +285,12 @@ class RegionAccumulator:
 
     def add_row(self, dice: Sequence[float], iou: Sequence[float], valid: Sequence[bool], domain: str,
                 hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None,
-                calibration: Optional[torch.Tensor] = None, components: Any = None) -> None:
+                calibration: Optional[torch.Tensor] = None, components: Any = None, lesionwise: Any = None) -> None:
         d = self.dom[domain]
         if self.components:
             self.add_components(components, domain)
+        if self.lesionwise:
+            self.add_lesionwise(lesionwise, domain)
         if self.bins:
             self.add_calibration(calibration, domain)
         for c in range(len(self.regions)):
@@ -251,6 +335,8 @@ class RegionAccumulator:
             self._surface_keys(out, "", self.tot)
         if self.components:
             self._component_keys(out, "", self.pp_tot)
+        if self.lesionwise:
+            self._lesionwise_keys(out, "", self.lw_tot)
         if self.bins:
             self._calibration_keys(out, "", self.cal_tot)
         for dom in sorted(self.dom.keys()):
@@ -265,6 +351,8 @@ class RegionAccumulator:
                 self._surface_keys(out, f"dom/{safe}/", self.dom[dom])
             if self.components:
                 self._component_keys(out, f"dom/{safe}/", self.pp_dom[dom])
+            if self.lesionwise:
+                self._lesionwise_keys(out, f"dom/{safe}/", self.lw_dom[dom])
             if self.bins:
                 self._calibration_keys(out, f"dom/{safe}/", self.cal_dom[dom])
         return out
@@ -366,6 +454,14 @@ class SegmentationEvaluationStrategy:
         (self.enable_postprocess, self.postprocess_connectivity, self.postprocess_min_voxels,
          self.postprocess_keep_largest) = postprocess_config(self.config)
         self._stats: Optional[torch.Tensor] = None
+        # lesion-wise Dice and detection counts on the GPU, off by default: ground-truth lesions (dilated, 26-connected)
+        # against the predicted components of the mask that is scored (the filtered one with post-processing on)
+        (self.enable_lesionwise, self.lesionwise_dilation, self.lesionwise_connectivity,
+         self.lesionwise_min_voxels) = lesionwise_config(self.config)
+        if self.enable_lesionwise and bool(get_config(self.config, "training.criterion.softmax", False)):
+            raise NotImplementedError("evaluation.lesionwise.enable: lesion-wise scores are defined for the sigmoid-region head "
+                                      "only (training.criterion.softmax is set)")
+        self._lw: Optional[torch.Tensor] = None
         # input pre-pass on the GPU (raw volumes in, the reference's `_normalize_img` applied here instead of in the
         # dataset worker; reference src/datasets/transforms.py:129-223).  The NIfTI datasets of this package hand over
         # raw intensities, so the pre-pass defaults to on for them and to off for the synthetic source (already
@@ -416,6 +512,11 @@ class SegmentationEvaluationStrategy:
                                     self.postprocess_keep_largest, out=mask)
         return res["counts"], res["stats"]
 
+    def lesionwise_launch(self, mask: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """Queue the lesion-wise scores of (mask, y) on the current stream -> device stats int64 [B,R,7]."""
+        return ops.lesionwise_scores(mask, y, self.lesionwise_dilation, self.lesionwise_connectivity,
+                                     self.lesionwise_min_voxels)["stats"]
+
     @staticmethod
     def component_columns(stats: torch.Tensor) -> torch.Tensor:
         """stats int64 [R,3] of one volume -> its table columns float64 [3*R]: components[R], kept[R], removed voxels[R]."""
@@ -431,13 +532,14 @@ class SegmentationEvaluationStrategy:
         if not shape_ok:
             raise ValueError(f"[BratsSegEval] model logits must be [B,{R},D,H,W], got {tuple(logits.shape)}")
         counts = torch.empty((y.shape[0], R, 3), dtype=torch.int64, device=y.device)
-        need_mask = self.enable_surface or self.enable_postprocess
+        need_mask = self.enable_surface or self.enable_postprocess or self.enable_lesionwise
         self._mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if need_mask else None
         ops.mask_dice_counts(logits, y, self.threshold, counts, self._mask, logits_channels_last=channels_last)
         self._stats = None
         if self.enable_postprocess:
             counts, stats = self.postprocess_launch(self._mask, y)
             self._stats = stats.cpu()
+        self._lw = self.lesionwise_launch(self._mask, y).cpu() if self.enable_lesionwise else None
         return counts.cpu()
 
     def calibration_launch(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
@@ -486,7 +588,7 @@ class SegmentationEvaluationStrategy:
         model.eval()
         model.to(device)
         acc = RegionAccumulator(self.region_order, self.enable_surface, self.cal_bins, self.calibration_regions,
-                                self.enable_postprocess)
+                                self.enable_postprocess, self.enable_lesionwise)
         rows: List[torch.Tensor] = []
         domain_names: List[str] = []
         n_local = 0
@@ -498,12 +600,14 @@ class SegmentationEvaluationStrategy:
             hd, asd = self.surface(y, counts) if self.enable_surface else (None, None)
             cal = self.calibration_launch(logits.float(), y).cpu() if self.enable_calibration else None
             comp = [self.component_columns(st) for st in self._stats] if self.enable_postprocess else None
+            lw = [lesionwise_columns(st) for st in self._lw] if self.enable_lesionwise else None
             domains = as_list_str(batch.get("domain", None), batch_size=x.size(0))
             if world == 1:
                 for i in range(x.size(0)):
                     acc.add_row(dice[i].tolist(), iou[i].tolist(), valid[i].tolist(), domains[i],
                                 hd[i].tolist() if hd is not None else None, asd[i].tolist() if asd is not None else None,
-                                cal[i] if cal is not None else None, comp[i] if comp is not None else None)
+                                cal[i] if cal is not None else None, comp[i] if comp is not None else None,
+                                lw[i] if lw is not None else None)
                 if self.report_loss:
                     acc.add_loss(self.loss_fn(logits.float(), y), x.size(0))
                 continue
@@ -523,6 +627,8 @@ class SegmentationEvaluationStrategy:
                     parts += [hd[i].double(), asd[i].double()]
                 if comp is not None:
                     parts.append(comp[i])
+                if lw is not None:
+                    parts.append(lw[i])
                 if cal is not None:
                     parts.append(cal[i].reshape(-1))
                 rows.append(torch.cat(parts))
@@ -538,14 +644,15 @@ class SegmentationEvaluationStrategy:
 
     def _table_width(self) -> int:
         return table_width(len(self.region_order), self.enable_surface, self.cal_bins, len(self.calibration_regions),
-                           components=self.enable_postprocess)
+                           components=self.enable_postprocess, lesionwise=self.enable_lesionwise)
 
     def _metrics_of(self, table: torch.Tensor, domain_names: Sequence[str]) -> Dict[str, float]:
         """Metrics of the whole split from its per-volume table (and ``last_reliability`` with calibration on)."""
         if self.enable_calibration:
             self.last_reliability = reliability_from_table(table, self.calibration_bins, len(self.calibration_regions))
         return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface,
-                                  self.cal_bins, self.calibration_regions, components=self.enable_postprocess)
+                                  self.cal_bins, self.calibration_regions, components=self.enable_postprocess,
+                                  lesionwise=self.enable_lesionwise)
 
 
 # ----------------------------------------------------------------------------- sharding
@@ -554,11 +661,14 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
     return list(range(rank, n_items, world))
 
 
-def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None, components: bool = False) -> int:
+def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None, components: bool = False,
+                lesionwise: bool = False) -> int:
     """index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R]) (, with ``components`` the figures of the
-    post-processing: components[R], kept[R], removed voxels[R]) (, with ``bins`` > 0 the volume's raw calibration table:
-    ``rout`` rows - default R - of 3*bins + 2 doubles, always last)."""
-    return 3 + (5 if surface else 3) * R + (3 * R if components else 0) + calibration_width(bins, R if rout is None else rout)
+    post-processing: components[R], kept[R], removed voxels[R]) (, with ``lesionwise`` the 7*R columns of
+    ``lesionwise_columns``) (, with ``bins`` > 0 the volume's raw calibration table: ``rout`` rows - default R - of
+    3*bins + 2 doubles, always last)."""
+    return (3 + (5 if surface else 3) * R + (3 * R if components else 0) + (LESIONWISE_COLUMNS * R if lesionwise else 0) +
+            calibration_width(bins, R if rout is None else rout))
 
 
 def reliability_from_table(table: torch.Tensor, bins: int, rout: int) -> torch.Tensor:
@@ -636,14 +746,17 @@ def gather_masks(local: Sequence[Tuple[int, torch.Tensor]], device, group=None) 
 
 def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_names: Sequence[str],
                        report_loss: bool, surface: bool = False, bins: int = 0,
-                       calibration_regions: Optional[Sequence[str]] = None, components: bool = False) -> Dict[str, float]:
+                       calibration_regions: Optional[Sequence[str]] = None, components: bool = False,
+                       lesionwise: bool = False) -> Dict[str, float]:
     """Replay the reference aggregation over gathered rows in volume-index order: the result is
     identical to a single-process run (float64 sums, order fixed by index).  ``bins`` > 0: the rows end in the raw
     calibration table of their volume (``table_width``), one row of it per name in ``calibration_regions``.
-    ``components``: the 3*R component columns sit behind the surface columns (``table_width``)."""
+    ``components``: the 3*R component columns sit behind the surface columns (``table_width``); ``lesionwise``: the 7*R
+    lesion-wise columns sit behind those."""
     R = len(region_order)
-    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components)
+    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components, lesionwise)
     c0 = 3 + (5 if surface else 3) * R
+    l0 = c0 + (3 * R if components else 0)
     cal_w = calibration_width(bins, len(acc.cal_regions))
     for row in table:
         dom = domain_names[int(row[1].item())] if 0 <= int(row[1].item()) < len(domain_names) else ""
@@ -653,7 +766,8 @@ def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_
         hd = row[3 + 3 * R:3 + 4 * R].to(torch.float32).tolist() if surface else None
         asd = row[3 + 4 * R:3 + 5 * R].to(torch.float32).tolist() if surface else None
         acc.add_row(dice, iou, valid, dom, hd, asd, row[row.numel() - cal_w:] if bins else None,
-                    row[c0:c0 + 3 * R] if components else None)
+                    row[c0:c0 + 3 * R] if components else None,
+                    row[l0:l0 + LESIONWISE_COLUMNS * R] if lesionwise else None)
         if report_loss:
             acc.add_loss(float(row[2].item()), 1)
     return acc.metrics(report_loss)
@@ -764,7 +878,7 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         B, R = yb.shape[0], yb.shape[1]
         res = self.plugins[lane].adapt_volume(xb)
         counts = torch.empty((B, R, 3), dtype=torch.int64, device=yb.device)
-        need_mask = self.enable_surface or self.gather_masks or self.enable_postprocess
+        need_mask = self.enable_surface or self.gather_masks or self.enable_postprocess or self.enable_lesionwise
         mask = torch.empty(tuple(yb.shape), dtype=torch.uint8, device=yb.device) if need_mask else None
         ops.mask_dice_counts(res["logits_cl"], yb, self.threshold, counts, mask, logits_channels_last=True)
         stats = None
@@ -773,6 +887,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         job: Dict[str, Any] = {"counts": counts, "shape": tuple(yb.shape[2:]), "keep": (xb, yb, mask, res), "mask": mask}
         if stats is not None:
             job["components"] = stats
+        if self.enable_lesionwise:       # right behind the counts, on the mask they describe
+            job["lesionwise"] = self.lesionwise_launch(mask, yb)
         if self.report_loss:
             job["loss"] = self.loss_fn.launch(res["logits_cl"], yb, channels_last=True)
         if self.enable_surface:
@@ -791,6 +907,7 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
             hd, asd = self.surface_fix(job["surface"][0], job["surface"][1], counts, job["shape"])
         cal = job["calibration"].cpu() if self.enable_calibration else None
         comp = job["components"].cpu() if self.enable_postprocess else None
+        lw = job["lesionwise"].cpu() if self.enable_lesionwise else None
         rows = []
         for b in range(B):
             parts = [torch.tensor([job["index"][b], job["domain_id"][b], losses[b]], dtype=torch.float64),
@@ -799,6 +916,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
                 parts += [hd[b].double(), asd[b].double()]
             if comp is not None:
                 parts.append(self.component_columns(comp[b]))
+            if lw is not None:
+                parts.append(lesionwise_columns(lw[b]))
             if cal is not None:
                 parts.append(cal[b].reshape(-1))
             rows.append(torch.cat(parts))

@@ -1323,3 +1323,58 @@ def components_filter(mask: torch.Tensor, label_ncdhw: Optional[torch.Tensor] = 
                                       int(connectivity), (C.c_int64 * R)(*mv), (C.c_int32 * R)(*kl), ptr(counts), ptr(stats),
                                       ptr(labels), ptr(scratch), stream_ptr()), "components_filter")
     return {"mask": out, "counts": counts, "stats": stats, "labels": labels}
+
+
+_LW_SCRATCH: Dict[Tuple, torch.Tensor] = {}      # working set of lesionwise_scores, per (device, size, stream)
+LESIONWISE_MAX_DILATION = 8
+LESIONWISE_COLUMNS = ("lesions", "lesions_kept", "lesions_found", "pred_components", "matched_components", "dice_q", "fp_voxels")
+LESIONWISE_Q_ONE = 1 << 30                       # a lesion's Dice is summed in units of 2^-30
+
+
+def lesionwise_scores(mask: torch.Tensor, label_ncdhw: torch.Tensor, iterations: int = 3, dilation_connectivity: int = 18,
+                      min_lesion_voxels=0, want_labels: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+    """Lesion-wise scores of every (volume, region) of ``mask`` (uint8 [B,R,D,H,W], dense; from ``mask_dice_counts`` or
+    ``components_filter``) against ``label_ncdhw`` (include/mmtta.h: mmtta_lesionwise_scores), queued on the current stream.
+    The ground truth is dilated ``iterations`` times with the ``dilation_connectivity`` neighbourhood; the 26-connected
+    components of that are the lesions, those of the mask the predicted components.  ``min_lesion_voxels``: one value, or
+    one per region.  Returns the device tensors ``stats`` int64 [B,R,7] (``LESIONWISE_COLUMNS``; ``dice_q`` in units of
+    2^-30) and ``labels`` int32 [B,R,D,H,W] (the lesion of every ground-truth voxel, 1 + smallest voxel index of the dilated
+    component; with ``want_labels``)."""
+    if mask.dtype != torch.uint8 or mask.dim() != 5 or not mask.is_contiguous() or not mask.is_cuda:
+        raise MmttaError(f"lesionwise_scores: mask must be a dense CUDA uint8 [B,R,D,H,W] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    B, R, D, H, W = (int(v) for v in mask.shape)
+    if min(B, R, D, H, W) < 1:
+        raise MmttaError(f"lesionwise_scores: empty mask {tuple(mask.shape)}")
+    if R > COMPONENTS_MAX_REGIONS:
+        raise MmttaError(f"lesionwise_scores: {R} regions, at most {COMPONENTS_MAX_REGIONS}")
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= LESIONWISE_MAX_DILATION:
+        raise MmttaError(f"lesionwise_scores: iterations {iterations!r} (an integer in 0 ... {LESIONWISE_MAX_DILATION})")
+    if dilation_connectivity not in COMPONENT_CONNECTIVITIES:
+        raise MmttaError(f"lesionwise_scores: dilation_connectivity {dilation_connectivity!r} (one of {list(COMPONENT_CONNECTIVITIES)})")
+    if (not torch.is_tensor(label_ncdhw) or tuple(label_ncdhw.shape) != tuple(mask.shape) or label_ncdhw.device != mask.device or
+            label_ncdhw.dtype != torch.float32):
+        raise MmttaError(f"lesionwise_scores: label must be float32 of the mask's shape {tuple(mask.shape)} on the mask's device")
+    vals = [min_lesion_voxels] * R if isinstance(min_lesion_voxels, (bool, int)) else list(min_lesion_voxels)
+    if len(vals) != R:
+        raise MmttaError(f"lesionwise_scores: min_lesion_voxels has {len(vals)} entries for {R} regions")
+    mv = [int(v) for v in vals]
+    if any(v < 0 for v in mv):
+        raise MmttaError(f"lesionwise_scores: min_lesion_voxels must not be negative, got {mv}")
+    lib = _lib.load()
+    nbytes = int(lib.mmtta_lesionwise_scratch_bytes(B * R, D, H, W))
+    if nbytes < 0:
+        raise MmttaError(f"lesionwise_scores: extent {(B * R, D, H, W)} unsupported (D*H*W <= 2**31 - 2, B*R <= 65535, "
+                         f"B*R*D*H*W below 2**32: split the batch)")
+    key = (mask.device.index, nbytes, int(torch.cuda.current_stream().cuda_stream))      # per stream: lanes run concurrently
+    scratch = _LW_SCRATCH.get(key)
+    if scratch is None:
+        for k in [k for k in _LW_SCRATCH if k[2] == key[2]]:       # a new shape on this stream replaces its old working set
+            del _LW_SCRATCH[k]
+        scratch = _LW_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+    stats = torch.empty((B, R, 7), dtype=torch.int64, device=mask.device)
+    labels = torch.empty((B, R, D, H, W), dtype=torch.int32, device=mask.device) if want_labels else None
+    tl = desc_ncdhw(label_ncdhw)
+    check(lib.mmtta_lesionwise_scores(ptr(mask), C.byref(tl), B, R, D, H, W, int(iterations), int(dilation_connectivity),
+                                      (C.c_int64 * R)(*mv), ptr(stats), ptr(labels), ptr(scratch), stream_ptr()),
+          "lesionwise_scores")
+    return {"stats": stats, "labels": labels}
