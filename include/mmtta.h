@@ -156,6 +156,15 @@ int mmtta_abi_version(void);
  * workgroup's MFMAs cover a workgroup's staging; same-box A/B 64.1 against 63.7 volumes/s), 3 = 2 x 8 x 64.
  * Changes the statistics rows such a convolution writes: set before planning. */
 #define MMTTA_OPT_THIN_MFMA 13
+/* 1 (default): the 3x3x3 stride-1 32 -> 32 layers of bf16 precision (forward and input gradient) run igemm_reuse_kernel
+ * (route 18 of mmtta_conv_route) when the call does not split K, takes the row-structured loader and the 16-byte epilogue: the lean tile with
+ * the rows of a wave's two blocks split by the parity of x, so that neighbouring kx taps share activation fragments (36
+ * LDS fragment reads per 16-channel stage instead of 54); 0: the lean tile as before (route 14).  The same MFMAs
+ * with the same operands in the same order: outputs and statistics rows equal bit for bit.  A run whose bias is not
+ * 16-byte aligned stays on route 14 (its 4-byte epilogue); mmtta_conv_route, which is shown no bias, cannot tell.
+ * Measured (profiles/igemm64_reuse_ab.md, same machine, parent against change): 132.6 -> 111.9 us per launch of a group
+ * of 8; volumes/s +1.6 % in one alternated series (outside its run-to-run spread), +0.8 % in a second (inside it). */
+#define MMTTA_OPT_IGEMM_FRAGMENT_REUSE 14
 int mmtta_set_option(int key, int value);
 
 /* ------------------------------------------------------------------ layout (boundary) ---- */
@@ -206,7 +215,7 @@ int mmtta_conv_pack_table_build(const mmtta_pack_item* items, int count, void* t
 int mmtta_conv_pack_batched(const void* table_dev, int count, int64_t total, void* stream);
 
 /* Launch geometry chosen for a problem; filled by mmtta_conv_plan.  It has no run-time operands, so it plans the route of
- * the shape: a call that runs as 16 / 17 (mmtta_conv_route) is reported as the implicit GEMM it would otherwise be. */
+ * the shape: a call that runs as 16 / 17 / 18 (mmtta_conv_route) is reported as the implicit GEMM it would otherwise be. */
 typedef struct {
   int32_t tiles;         /* M tiles (over n and space) per launch                           */
   int32_t launches;      /* 1 (the 8 parity classes of a stride-2 transposed form share one launch) */
@@ -247,11 +256,12 @@ int mmtta_conv_run(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmt
                    int64_t workspace_bytes, void* stream);
 
 /* Which kernel mmtta_conv_run would launch for these operands (host-only, launches nothing; the run itself asks the same
- * planner, csrc/conv_igemm.hip: geometry).  The ids are those of mmtta_conv_plan_t.config, plus the two routes that depend
+ * planner, csrc/conv_igemm.hip: geometry).  The ids are those of mmtta_conv_plan_t.config, plus the routes that depend
  * on the run-time operands:
  *   0..5 fp32 / 7..12 bf16 implicit GEMM tiles, 14 the lean bf16 tile     6 direct (<= 4 produced channels)
  *   13 thin-K (<= 4 gathered channels)                                    15 class-fused stride-2 transposed form
  *   16 small-K 1x1x1 (fp32, nothing fused)                                17 streaming 1x1x1 (bf16, voxel-dense tensors)
+ *   18 the lean bf16 tile with activation fragments shared along x (3x3x3 stride-1 32 -> 32, unsplit; mmtta_conv_plan reports 14)
  * or a negative mmtta error code. */
 int mmtta_conv_route(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                      const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);

@@ -14,6 +14,7 @@ int g_profile_main_only = 0;
 int g_igemm_pipeline = 1;
 int g_epilogue_vec = 1;
 int g_igemm_lean = 1;
+int g_igemm_reuse = 1;
 int g_cls_fused_min = 128;
 int g_thin_mfma = 2;
 int g_wgrad_vec = 1;
@@ -46,6 +47,11 @@ extern "C" int mmtta_set_option(int key, int value) {
   if (key == MMTTA_OPT_IGEMM_LEAN) {
     const int prev = mmtta::g_igemm_lean;
     mmtta::g_igemm_lean = value ? 1 : 0;
+    return prev;
+  }
+  if (key == MMTTA_OPT_IGEMM_FRAGMENT_REUSE) {
+    const int prev = mmtta::g_igemm_reuse;
+    mmtta::g_igemm_reuse = value ? 1 : 0;
     return prev;
   }
   if (key == MMTTA_OPT_EPILOGUE_VEC16) {

@@ -35,6 +35,7 @@ extern int g_profile_main_only;     // api.hip: mmtta_set_option(MMTTA_OPT_PROFI
 extern int g_igemm_pipeline;        // api.hip: MMTTA_OPT_IGEMM_PIPELINE
 extern int g_wgrad_vec;             // api.hip: MMTTA_OPT_WGRAD_VECTOR_STAGING
 extern int g_igemm_lean;            // api.hip: MMTTA_OPT_IGEMM_LEAN
+extern int g_igemm_reuse;           // api.hip: MMTTA_OPT_IGEMM_FRAGMENT_REUSE
 extern int g_cls_fused_min;         // api.hip: MMTTA_OPT_CLASS_FUSED_MIN_WORKGROUPS
 extern int g_thin_mfma;             // api.hip: MMTTA_OPT_THIN_MFMA
 extern int g_epilogue_vec;          // api.hip: MMTTA_OPT_EPILOGUE_VEC16
