@@ -916,6 +916,43 @@ int mmtta_lesionwise_scores(const uint8_t* mask, const mmtta_tensor* label, int 
                             int dilation_connectivity, const int64_t* min_lesion_voxels, int64_t* stats, int32_t* labels,
                             void* scratch, void* stream);
 
+/* Hole filling and region nesting of the evaluation tail, the steps that follow the component filter in common BraTS /
+ * HECKTOR post-processing.  Replaces a host `scipy.ndimage.binary_fill_holes` per (volume, region) over a mask copied off
+ * the device and a nesting fix in numpy; the reference evaluator has no counterpart.  Per (n, r), in this order:
+ *   holes     B = voxels where mask == 0.  The components of B are taken at `fill_connectivity` (6, 18 or 26; 6 is scipy's
+ *             default structure and the dual of a 26-connected foreground).  A component is OPEN if one of its voxels lies
+ *             on a face of the volume (z in {0, D-1}, y in {0, H-1} or x in {0, W-1}), otherwise it is a HOLE.  A hole of
+ *             region r is filled iff fill_holes[r] != 0 and (max_hole_voxels[r] == 0 or its size <= max_hole_voxels[r]).
+ *             Without a cap this is binary_fill_holes(mask, generate_binary_structure(3, 1 | 2 | 3)) exactly.  Holes are
+ *             counted for every region, whether or not it fills them.
+ *   nesting   `chain` = c_0 ... c_k, distinct region indices, innermost first; chain_len 0 (then `chain` may be NULL) or >= 2.
+ *             nest_mode 0 (clip): new[c_i] = old[c_i] & old[c_i+1] & ... & old[c_k];
+ *             nest_mode 1 (grow): new[c_i] = old[c_0] | ... | old[c_i];   "old" = after filling.
+ *             Regions outside the chain pass through unchanged.
+ *   mask      uint8 [N,R,D,H,W] dense on the device (non-zero = foreground), rewritten IN PLACE as 0 / 1; nothing else the
+ *             caller owns is written apart from `counts` and `stats`
+ *   label     fp32 any strides, ground truth = label > 0.5, or NULL (then `counts` must be NULL)
+ *   fill_holes       HOST int32 [R], read before return
+ *   max_hole_voxels  HOST int64 [R], read before return, >= 0 (0: no cap)
+ *   chain     HOST int32 [chain_len], read before return
+ *   counts    int64 [N][R][3] on the device or NULL: inter, psum, gsum of the FINAL mask against the label, as
+ *             mmtta_mask_dice_counts defines them; zeroed by this call
+ *   stats     int64 [N][R][4] on the device, zeroed by this call: holes, holes filled, voxels filled, voxels the nesting
+ *             changed
+ *   scratch   mmtta_mask_fill_nest_scratch_bytes(N*R, D, H, W) bytes (negative: unsupported extent)
+ * Five launches on `stream` that depend on the shape alone (a tile pass of its own over the complement, where a tile that is
+ * all background skips the union-find; the merge and flatten passes of mmtta_components_filter; a border pass; a finish
+ * pass): no host read, no convergence flag.  All sums are integers: two calls agree bit for bit and a batch gives what its
+ * items give alone.  MMTTA_FILL_UNIFORM_TILES=0 in the environment (read once) switches the all-background shortcut of the
+ * tile pass off, for measurements; the results are the same.  Limits: those of mmtta_components_filter.  Anything else -
+ * a null argument, a connectivity other than 6 / 18 / 26, a negative cap, a chain of length 1 or longer than R or with a
+ * repeated or out-of-range index, a nest_mode other than 0 / 1, a label of another shape or not fp32 - is refused with
+ * MMTTA_ERR_INVALID / _UNSUPPORTED and a message naming the argument, before anything is queued. */
+int64_t mmtta_mask_fill_nest_scratch_bytes(int64_t n_masks, int64_t d, int64_t h, int64_t w);
+int mmtta_mask_fill_nest(uint8_t* mask, const mmtta_tensor* label, int n, int r, int d, int h, int w, int fill_connectivity,
+                         const int32_t* fill_holes, const int64_t* max_hole_voxels, const int32_t* chain, int chain_len,
+                         int nest_mode, int64_t* counts, int64_t* stats, void* scratch, void* stream);
+
 /* Surface metrics of the evaluation tail: percentile Hausdorff distance and average surface distance per
  * (volume, region).  Replaces the MONAI calls of reference src/evaluation/seg_eval.py:312-340
  * (`HausdorffDistanceMetric(include_background=True, reduction="none", percentile=95, directed=False)` built at

@@ -1,4 +1,4 @@
-// What the component filter (components.hip) and the lesion-wise scores (lesionwise.hip) share: the launch arguments of the
+// What the component filter (components.hip), the lesion-wise scores (lesionwise.hip) and the hole filling (fill_holes.hip) share: the launch arguments of the
 // block-based union-find labeller and its host entry.  The kernels themselves live in components.hip.
 #pragma once
 #include "common.h"
@@ -33,5 +33,10 @@ struct CcArgs {
 
 // components.hip: labelling passes K1 - K3 (tile, merge, flatten) queued on `s`
 int cc_label(const CcArgs& a, hipStream_t s);
+
+// components.hip: K2 and K3 on their own, for a caller that brings its own tile pass (fill_holes.hip labels the complement of
+// a mask).  One thread per voxel, grid ((V + 255) / 256, M); they read L, size, ncomp, the geometry and maxn.
+__global__ __launch_bounds__(256) void cc_merge_kernel(CcArgs a);
+__global__ __launch_bounds__(256) void cc_flatten_kernel(CcArgs a);
 
 }  // namespace mmtta

@@ -109,6 +109,56 @@ def postprocess_config(config: Any) -> Tuple[bool, int, List[int], List[bool]]:
     return enable, int(conn), [int(v) for v in mv], [bool(v) for v in kl]
 
 
+# hole filling and region nesting, the second half of the block: the defaults leave the pass out altogether
+POSTPROCESS_FILL_DEFAULTS = {"fill_holes": False, "fill_connectivity": 6, "max_hole_voxels": 0, "nesting": [],
+                             "nesting_mode": "clip"}
+POSTPROCESS_NESTING_MODES = ops.FILL_NEST_MODES
+FILL_NEST_COLUMNS = len(ops.FILL_NEST_COLUMNS)      # table columns per region: holes, filled holes, filled voxels, nested voxels
+
+
+def fill_nest_config(config: Any) -> Tuple[List[bool], int, List[int], List[int], str]:
+    """``evaluation.postprocess: {fill_holes, fill_connectivity, max_hole_voxels, nesting, nesting_mode}`` -> (fill_holes,
+    fill_connectivity, max_hole_voxels, nesting, nesting_mode); false, 6, 0, [] and ``clip`` when absent
+    (``POSTPROCESS_FILL_DEFAULTS``).  ``fill_holes`` is a bool or a list of bools, ``max_hole_voxels`` an int >= 0 or a list of
+    them (0: no cap), one entry per region of ``evaluation.seg.region_order``; ``nesting`` is a list of region names,
+    innermost first, returned as indices into ``region_order``.  A value the kernel cannot take is a ``ValueError`` that
+    names its key, whether the block is enabled or not."""
+    pp = get_config(config, "evaluation.postprocess", {}) or {}
+    regions = [str(x) for x in get_config(config, "evaluation.seg.region_order", ["ET", "TC", "WT"])]
+    R = len(regions)
+    dflt = POSTPROCESS_FILL_DEFAULTS
+
+    def per_region(key: str, ok, what: str) -> list:
+        v = get_config(pp, key, dflt[key])
+        scalar = isinstance(v, (bool, int))
+        vals = [v] * R if scalar else (list(v) if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else None)
+        if vals is None or not all(ok(x) for x in vals):
+            raise ValueError(f"evaluation.postprocess.{key} must be {what} or a list of one per region, got {v!r}")
+        if len(vals) != R:
+            raise ValueError(f"evaluation.postprocess.{key} has {len(vals)} entries for the {R} regions of "
+                             f"evaluation.seg.region_order")
+        return vals
+
+    fh = per_region("fill_holes", lambda x: isinstance(x, bool), "true or false")
+    conn = get_config(pp, "fill_connectivity", dflt["fill_connectivity"])
+    if isinstance(conn, bool) or conn not in POSTPROCESS_CONNECTIVITIES:
+        raise ValueError(f"evaluation.postprocess.fill_connectivity must be one of {list(POSTPROCESS_CONNECTIVITIES)}, got {conn!r}")
+    cap = per_region("max_hole_voxels", lambda x: isinstance(x, int) and not isinstance(x, bool) and x >= 0, "a non-negative integer")
+    nest = get_config(pp, "nesting", dflt["nesting"])
+    nest = [] if nest is None else nest
+    if isinstance(nest, (str, bytes)) or not hasattr(nest, "__iter__"):
+        raise ValueError(f"evaluation.postprocess.nesting must be a list of region names, innermost first, got {nest!r}")
+    names = list(nest)
+    if not all(isinstance(x, str) and x in regions for x in names):
+        raise ValueError(f"evaluation.postprocess.nesting must name regions of evaluation.seg.region_order {regions}, got {names!r}")
+    if len(names) == 1 or len(set(names)) != len(names):
+        raise ValueError(f"evaluation.postprocess.nesting must be empty or at least two distinct regions, got {names!r}")
+    mode = get_config(pp, "nesting_mode", dflt["nesting_mode"])
+    if mode not in POSTPROCESS_NESTING_MODES:
+        raise ValueError(f"evaluation.postprocess.nesting_mode must be one of {list(POSTPROCESS_NESTING_MODES)}, got {mode!r}")
+    return [bool(v) for v in fh], int(conn), [int(v) for v in cap], [regions.index(x) for x in names], str(mode)
+
+
 LESIONWISE_CONNECTIVITIES = ops.COMPONENT_CONNECTIVITIES
 LESIONWISE_MAX_DILATION = ops.LESIONWISE_MAX_DILATION
 LESIONWISE_COLUMNS = 7       # table columns per region: lw_dc, valid, lesions kept, found, false-positive, matched, predicted components
@@ -198,10 +248,13 @@ class RegionAccumulator:
     post-processing: per-volume means over ALL volumes of components found, components kept and voxels removed.
     ``lesionwise`` adds the lesion-wise figures: the lesion-wise Dice averaged over the volumes where it is defined (a
     GT-empty region with false-positive components IS one of them, with 0), per-volume means of kept lesions, found
-    lesions and false-positive components, and recall / precision pooled over all volumes."""
+    lesions and false-positive components, and recall / precision pooled over all volumes.  ``fill_nest`` adds the figures
+    of the hole filling and nesting pass: per-volume means over all volumes of holes, filled holes, filled voxels and voxels
+    the nesting changed."""
 
     def __init__(self, region_order: Sequence[str], surface: bool = False, bins: int = 0,
-                 calibration_regions: Optional[Sequence[str]] = None, components: bool = False, lesionwise: bool = False):
+                 calibration_regions: Optional[Sequence[str]] = None, components: bool = False, lesionwise: bool = False,
+                 fill_nest: bool = False):
         self.regions = list(region_order)
         self.surface = bool(surface)
         R = len(self.regions)
@@ -226,6 +279,23 @@ class RegionAccumulator:
         self._zl = lambda: torch.zeros((LESIONWISE_COLUMNS + 1, R), dtype=torch.float64)
         self.lw_tot = self._zl()
         self.lw_dom: Dict[str, torch.Tensor] = defaultdict(self._zl)
+        self.fill_nest = bool(fill_nest)
+        self._zf = lambda: torch.zeros((FILL_NEST_COLUMNS + 1, R), dtype=torch.float64)      # the 4 columns summed, then the volumes
+        self.fn_tot = self._zf()
+        self.fn_dom: Dict[str, torch.Tensor] = defaultdict(self._zf)
+
+    def add_fill_nest(self, stats: Any, domain: str) -> None:
+        """One volume's fill / nest figures, [4*R] as the table holds them: holes[R], filled holes[R], filled voxels[R],
+        nested voxels[R]."""
+        st = torch.as_tensor(stats, dtype=torch.float64).reshape(FILL_NEST_COLUMNS, len(self.regions))
+        for acc in (self.fn_tot, self.fn_dom[domain]):
+            acc[:FILL_NEST_COLUMNS] += st
+            acc[FILL_NEST_COLUMNS] += 1.0
+
+    def _fill_nest_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
+        for row, key in enumerate(ops.FILL_NEST_COLUMNS):
+            for name, v in zip(self.regions, self._fin(acc[row], acc[FILL_NEST_COLUMNS])):
+                out[f"{prefix}{name.lower()}_{key}"] = v
 
     def add_lesionwise(self, cols: Any, domain: str) -> None:
         """One volume's lesion-wise columns, [7*R] as the table holds them (``lesionwise_columns``)."""
@@ -285,10 +355,13 @@ class RegionAccumulator:
 
     def add_row(self, dice: Sequence[float], iou: Sequence[float], valid: Sequence[bool], domain: str,
                 hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None,
-                calibration: Optional[torch.Tensor] = None, components: Any = None, lesionwise: Any = None) -> None:
+                calibration: Optional[torch.Tensor] = None, components: Any = None, lesionwise: Any = None,
+                fill_nest: Any = None) -> None:
         d = self.dom[domain]
         if self.components:
             self.add_components(components, domain)
+        if self.fill_nest:
+            self.add_fill_nest(fill_nest, domain)
         if self.lesionwise:
             self.add_lesionwise(lesionwise, domain)
         if self.bins:
@@ -335,6 +408,8 @@ class RegionAccumulator:
             self._surface_keys(out, "", self.tot)
         if self.components:
             self._component_keys(out, "", self.pp_tot)
+        if self.fill_nest:
+            self._fill_nest_keys(out, "", self.fn_tot)
         if self.lesionwise:
             self._lesionwise_keys(out, "", self.lw_tot)
         if self.bins:
@@ -351,6 +426,8 @@ class RegionAccumulator:
                 self._surface_keys(out, f"dom/{safe}/", self.dom[dom])
             if self.components:
                 self._component_keys(out, f"dom/{safe}/", self.pp_dom[dom])
+            if self.fill_nest:
+                self._fill_nest_keys(out, f"dom/{safe}/", self.fn_dom[dom])
             if self.lesionwise:
                 self._lesionwise_keys(out, f"dom/{safe}/", self.lw_dom[dom])
             if self.bins:
@@ -454,6 +531,12 @@ class SegmentationEvaluationStrategy:
         (self.enable_postprocess, self.postprocess_connectivity, self.postprocess_min_voxels,
          self.postprocess_keep_largest) = postprocess_config(self.config)
         self._stats: Optional[torch.Tensor] = None
+        # hole filling and ET < TC < WT nesting of the filtered mask, in place right after the filter; the pass is queued
+        # only when post-processing is on and a region fills or a chain is given, and only then do its keys appear
+        (self.postprocess_fill_holes, self.postprocess_fill_connectivity, self.postprocess_max_hole_voxels,
+         self.postprocess_nesting, self.postprocess_nesting_mode) = fill_nest_config(self.config)
+        self.enable_fill_nest = self.enable_postprocess and (any(self.postprocess_fill_holes) or bool(self.postprocess_nesting))
+        self._fill: Optional[torch.Tensor] = None
         # lesion-wise Dice and detection counts on the GPU, off by default: ground-truth lesions (dilated, 26-connected)
         # against the predicted components of the mask that is scored (the filtered one with post-processing on)
         (self.enable_lesionwise, self.lesionwise_dilation, self.lesionwise_connectivity,
@@ -512,6 +595,18 @@ class SegmentationEvaluationStrategy:
                                     self.postprocess_keep_largest, out=mask)
         return res["counts"], res["stats"]
 
+    def fill_nest_launch(self, mask: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Queue hole filling and nesting on the current stream, in place on ``mask`` -> device (counts [B,R,3] of the final
+        mask, stats [B,R,4] = holes, filled holes, filled voxels, nested voxels), both int64."""
+        res = ops.fill_nest(mask, y, self.postprocess_fill_holes, self.postprocess_fill_connectivity,
+                            self.postprocess_max_hole_voxels, self.postprocess_nesting, self.postprocess_nesting_mode)
+        return res["counts"], res["stats"]
+
+    @staticmethod
+    def fill_nest_columns(stats: torch.Tensor) -> torch.Tensor:
+        """stats int64 [R,4] of one volume -> its table columns float64 [4*R], one column's regions after another."""
+        return stats.to(torch.float64).t().reshape(-1)
+
     def lesionwise_launch(self, mask: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """Queue the lesion-wise scores of (mask, y) on the current stream -> device stats int64 [B,R,7]."""
         return ops.lesionwise_scores(mask, y, self.lesionwise_dilation, self.lesionwise_connectivity,
@@ -526,7 +621,8 @@ class SegmentationEvaluationStrategy:
         """logits [B,R,D,H,W] (or channels-last view) + labels -> exact counts int64 [B,R,3] on the host.
         With ``evaluation.surface.enable`` the prediction mask is kept for :meth:`surface`.  With
         ``evaluation.postprocess.enable`` the mask is filtered in place, the counts are those of the filtered mask and
-        ``self._stats`` holds the component figures int64 [B,R,3] (host)."""
+        ``self._stats`` holds the component figures int64 [B,R,3] (host); with hole filling or nesting on top the counts
+        are those of the final mask and ``self._fill`` holds that pass's figures int64 [B,R,4] (host)."""
         R = y.shape[1]
         shape_ok = (logits.ndim == 5 and (logits.shape[-1] if channels_last else logits.shape[1]) == R)
         if not shape_ok:
@@ -535,9 +631,12 @@ class SegmentationEvaluationStrategy:
         need_mask = self.enable_surface or self.enable_postprocess or self.enable_lesionwise
         self._mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if need_mask else None
         ops.mask_dice_counts(logits, y, self.threshold, counts, self._mask, logits_channels_last=channels_last)
-        self._stats = None
+        self._stats = self._fill = None
         if self.enable_postprocess:
             counts, stats = self.postprocess_launch(self._mask, y)
+            if self.enable_fill_nest:
+                counts, fill = self.fill_nest_launch(self._mask, y)
+                self._fill = fill.cpu()
             self._stats = stats.cpu()
         self._lw = self.lesionwise_launch(self._mask, y).cpu() if self.enable_lesionwise else None
         return counts.cpu()
@@ -588,7 +687,7 @@ class SegmentationEvaluationStrategy:
         model.eval()
         model.to(device)
         acc = RegionAccumulator(self.region_order, self.enable_surface, self.cal_bins, self.calibration_regions,
-                                self.enable_postprocess, self.enable_lesionwise)
+                                self.enable_postprocess, self.enable_lesionwise, self.enable_fill_nest)
         rows: List[torch.Tensor] = []
         domain_names: List[str] = []
         n_local = 0
@@ -601,13 +700,14 @@ class SegmentationEvaluationStrategy:
             cal = self.calibration_launch(logits.float(), y).cpu() if self.enable_calibration else None
             comp = [self.component_columns(st) for st in self._stats] if self.enable_postprocess else None
             lw = [lesionwise_columns(st) for st in self._lw] if self.enable_lesionwise else None
+            fn = [self.fill_nest_columns(st) for st in self._fill] if self.enable_fill_nest else None
             domains = as_list_str(batch.get("domain", None), batch_size=x.size(0))
             if world == 1:
                 for i in range(x.size(0)):
                     acc.add_row(dice[i].tolist(), iou[i].tolist(), valid[i].tolist(), domains[i],
                                 hd[i].tolist() if hd is not None else None, asd[i].tolist() if asd is not None else None,
                                 cal[i] if cal is not None else None, comp[i] if comp is not None else None,
-                                lw[i] if lw is not None else None)
+                                lw[i] if lw is not None else None, fn[i] if fn is not None else None)
                 if self.report_loss:
                     acc.add_loss(self.loss_fn(logits.float(), y), x.size(0))
                 continue
@@ -627,6 +727,8 @@ class SegmentationEvaluationStrategy:
                     parts += [hd[i].double(), asd[i].double()]
                 if comp is not None:
                     parts.append(comp[i])
+                if fn is not None:
+                    parts.append(fn[i])
                 if lw is not None:
                     parts.append(lw[i])
                 if cal is not None:
@@ -644,7 +746,8 @@ class SegmentationEvaluationStrategy:
 
     def _table_width(self) -> int:
         return table_width(len(self.region_order), self.enable_surface, self.cal_bins, len(self.calibration_regions),
-                           components=self.enable_postprocess, lesionwise=self.enable_lesionwise)
+                           components=self.enable_postprocess, lesionwise=self.enable_lesionwise,
+                           fill_nest=self.enable_fill_nest)
 
     def _metrics_of(self, table: torch.Tensor, domain_names: Sequence[str]) -> Dict[str, float]:
         """Metrics of the whole split from its per-volume table (and ``last_reliability`` with calibration on)."""
@@ -652,7 +755,7 @@ class SegmentationEvaluationStrategy:
             self.last_reliability = reliability_from_table(table, self.calibration_bins, len(self.calibration_regions))
         return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface,
                                   self.cal_bins, self.calibration_regions, components=self.enable_postprocess,
-                                  lesionwise=self.enable_lesionwise)
+                                  lesionwise=self.enable_lesionwise, fill_nest=self.enable_fill_nest)
 
 
 # ----------------------------------------------------------------------------- sharding
@@ -662,12 +765,14 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
 
 
 def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None, components: bool = False,
-                lesionwise: bool = False) -> int:
+                lesionwise: bool = False, fill_nest: bool = False) -> int:
     """index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R]) (, with ``components`` the figures of the
-    post-processing: components[R], kept[R], removed voxels[R]) (, with ``lesionwise`` the 7*R columns of
+    post-processing: components[R], kept[R], removed voxels[R]) (, with ``fill_nest`` the figures of the hole filling and
+    nesting: holes[R], filled holes[R], filled voxels[R], nested voxels[R]) (, with ``lesionwise`` the 7*R columns of
     ``lesionwise_columns``) (, with ``bins`` > 0 the volume's raw calibration table: ``rout`` rows - default R - of
     3*bins + 2 doubles, always last)."""
-    return (3 + (5 if surface else 3) * R + (3 * R if components else 0) + (LESIONWISE_COLUMNS * R if lesionwise else 0) +
+    return (3 + (5 if surface else 3) * R + (3 * R if components else 0) + (FILL_NEST_COLUMNS * R if fill_nest else 0) +
+            (LESIONWISE_COLUMNS * R if lesionwise else 0) +
             calibration_width(bins, R if rout is None else rout))
 
 
@@ -747,16 +852,17 @@ def gather_masks(local: Sequence[Tuple[int, torch.Tensor]], device, group=None) 
 def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_names: Sequence[str],
                        report_loss: bool, surface: bool = False, bins: int = 0,
                        calibration_regions: Optional[Sequence[str]] = None, components: bool = False,
-                       lesionwise: bool = False) -> Dict[str, float]:
+                       lesionwise: bool = False, fill_nest: bool = False) -> Dict[str, float]:
     """Replay the reference aggregation over gathered rows in volume-index order: the result is
     identical to a single-process run (float64 sums, order fixed by index).  ``bins`` > 0: the rows end in the raw
     calibration table of their volume (``table_width``), one row of it per name in ``calibration_regions``.
-    ``components``: the 3*R component columns sit behind the surface columns (``table_width``); ``lesionwise``: the 7*R
-    lesion-wise columns sit behind those."""
+    ``components``: the 3*R component columns sit behind the surface columns (``table_width``); ``fill_nest``: the 4*R
+    columns of the hole filling and nesting sit behind those; ``lesionwise``: the 7*R lesion-wise columns sit behind those."""
     R = len(region_order)
-    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components, lesionwise)
+    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components, lesionwise, fill_nest)
     c0 = 3 + (5 if surface else 3) * R
-    l0 = c0 + (3 * R if components else 0)
+    f0 = c0 + (3 * R if components else 0)
+    l0 = f0 + (FILL_NEST_COLUMNS * R if fill_nest else 0)
     cal_w = calibration_width(bins, len(acc.cal_regions))
     for row in table:
         dom = domain_names[int(row[1].item())] if 0 <= int(row[1].item()) < len(domain_names) else ""
@@ -767,7 +873,8 @@ def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_
         asd = row[3 + 4 * R:3 + 5 * R].to(torch.float32).tolist() if surface else None
         acc.add_row(dice, iou, valid, dom, hd, asd, row[row.numel() - cal_w:] if bins else None,
                     row[c0:c0 + 3 * R] if components else None,
-                    row[l0:l0 + LESIONWISE_COLUMNS * R] if lesionwise else None)
+                    row[l0:l0 + LESIONWISE_COLUMNS * R] if lesionwise else None,
+                    row[f0:f0 + FILL_NEST_COLUMNS * R] if fill_nest else None)
         if report_loss:
             acc.add_loss(float(row[2].item()), 1)
     return acc.metrics(report_loss)
@@ -884,9 +991,14 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         stats = None
         if self.enable_postprocess:      # in place: the surface pass and the gathered masks below take the filtered mask
             counts, stats = self.postprocess_launch(mask, yb)
+        fill = None
+        if self.enable_fill_nest:        # likewise in place, right behind the filter: its counts replace the filter's
+            counts, fill = self.fill_nest_launch(mask, yb)
         job: Dict[str, Any] = {"counts": counts, "shape": tuple(yb.shape[2:]), "keep": (xb, yb, mask, res), "mask": mask}
         if stats is not None:
             job["components"] = stats
+        if fill is not None:
+            job["fill_nest"] = fill
         if self.enable_lesionwise:       # right behind the counts, on the mask they describe
             job["lesionwise"] = self.lesionwise_launch(mask, yb)
         if self.report_loss:
@@ -908,6 +1020,7 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         cal = job["calibration"].cpu() if self.enable_calibration else None
         comp = job["components"].cpu() if self.enable_postprocess else None
         lw = job["lesionwise"].cpu() if self.enable_lesionwise else None
+        fn = job["fill_nest"].cpu() if self.enable_fill_nest else None
         rows = []
         for b in range(B):
             parts = [torch.tensor([job["index"][b], job["domain_id"][b], losses[b]], dtype=torch.float64),
@@ -916,6 +1029,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
                 parts += [hd[b].double(), asd[b].double()]
             if comp is not None:
                 parts.append(self.component_columns(comp[b]))
+            if fn is not None:
+                parts.append(self.fill_nest_columns(fn[b]))
             if lw is not None:
                 parts.append(lesionwise_columns(lw[b]))
             if cal is not None:

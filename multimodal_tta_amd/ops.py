@@ -1325,6 +1325,71 @@ def components_filter(mask: torch.Tensor, label_ncdhw: Optional[torch.Tensor] = 
     return {"mask": out, "counts": counts, "stats": stats, "labels": labels}
 
 
+_FN_SCRATCH: Dict[Tuple, torch.Tensor] = {}      # working set of fill_nest, per (device, size, stream)
+FILL_NEST_MODES = ("clip", "grow")
+FILL_NEST_COLUMNS = ("holes", "filled_holes", "filled_voxels", "nested_voxels")
+
+
+def fill_nest(mask: torch.Tensor, label_ncdhw: Optional[torch.Tensor] = None, fill_holes=False, fill_connectivity: int = 6,
+              max_hole_voxels=0, nesting: Sequence[int] = (), nesting_mode: str = "clip",
+              want_counts: bool = True) -> Dict[str, Optional[torch.Tensor]]:
+    """Hole filling, then region nesting, IN PLACE on every (volume, region) of ``mask`` (uint8 [B,R,D,H,W], dense; from
+    ``mask_dice_counts`` or ``components_filter``), queued on the current stream (include/mmtta.h: mmtta_mask_fill_nest).
+    A hole is a component of the background at ``fill_connectivity`` that touches no face of the volume; region r fills
+    its holes where ``fill_holes[r]`` is set and the hole has at most ``max_hole_voxels[r]`` voxels (0: no cap); both take
+    one value, or one per region.  ``nesting``: region indices, innermost first (empty, or at least two distinct ones);
+    ``clip`` cuts every region of the chain to the ones further out, ``grow`` extends it by the ones further in.  Returns
+    the device tensors ``mask`` (the argument, 0 / 1), ``counts`` int64 [B,R,3] (inter, psum, gsum of the final mask; needs a
+    label) and ``stats`` int64 [B,R,4] (``FILL_NEST_COLUMNS``)."""
+    if mask.dtype != torch.uint8 or mask.dim() != 5 or not mask.is_contiguous() or not mask.is_cuda:
+        raise MmttaError(f"fill_nest: mask must be a dense CUDA uint8 [B,R,D,H,W] tensor, got {mask.dtype} {tuple(mask.shape)}")
+    B, R, D, H, W = (int(v) for v in mask.shape)
+    if min(B, R, D, H, W) < 1:
+        raise MmttaError(f"fill_nest: empty mask {tuple(mask.shape)}")
+    if R > COMPONENTS_MAX_REGIONS:
+        raise MmttaError(f"fill_nest: {R} regions, at most {COMPONENTS_MAX_REGIONS}")
+    if isinstance(fill_connectivity, bool) or fill_connectivity not in COMPONENT_CONNECTIVITIES:
+        raise MmttaError(f"fill_nest: fill_connectivity {fill_connectivity!r} (one of {list(COMPONENT_CONNECTIVITIES)})")
+    if nesting_mode not in FILL_NEST_MODES:
+        raise MmttaError(f"fill_nest: nesting_mode {nesting_mode!r} (one of {list(FILL_NEST_MODES)})")
+    if label_ncdhw is not None and (tuple(label_ncdhw.shape) != tuple(mask.shape) or label_ncdhw.device != mask.device or
+                                    label_ncdhw.dtype != torch.float32):
+        raise MmttaError(f"fill_nest: label must be float32 of the mask's shape on the mask's device, got "
+                         f"{label_ncdhw.dtype} {tuple(label_ncdhw.shape)} on {label_ncdhw.device} vs {tuple(mask.shape)} on "
+                         f"{mask.device}")
+    per = []
+    for value, what in ((fill_holes, "fill_holes"), (max_hole_voxels, "max_hole_voxels")):
+        vals = [value] * R if isinstance(value, (bool, int)) else list(value)
+        if len(vals) != R:
+            raise MmttaError(f"fill_nest: {what} has {len(vals)} entries for {R} regions")
+        per.append([int(v) for v in vals])
+    fh, cap = per
+    if any(v < 0 for v in cap):
+        raise MmttaError(f"fill_nest: max_hole_voxels must not be negative, got {cap}")
+    chain = [int(c) for c in nesting]
+    if len(chain) == 1 or len(set(chain)) != len(chain) or any(not 0 <= c < R for c in chain):
+        raise MmttaError(f"fill_nest: nesting {chain} must be empty or at least two distinct region indices in 0 ... {R - 1}")
+    lib = _lib.load()
+    nbytes = int(lib.mmtta_mask_fill_nest_scratch_bytes(B * R, D, H, W))
+    if nbytes < 0:
+        raise MmttaError(f"fill_nest: extent {(B * R, D, H, W)} unsupported (D*H*W <= 2**31 - 2, B*R <= 65535, "
+                         f"B*R*D*H*W below 2**32: split the batch)")
+    key = (mask.device.index, nbytes, int(torch.cuda.current_stream().cuda_stream))      # per stream: lanes run concurrently
+    scratch = _FN_SCRATCH.get(key)
+    if scratch is None:
+        for k in [k for k in _FN_SCRATCH if k[2] == key[2]]:       # a new shape on this stream replaces its old working set
+            del _FN_SCRATCH[k]
+        scratch = _FN_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+    counts = torch.empty((B, R, 3), dtype=torch.int64, device=mask.device) if (want_counts and label_ncdhw is not None) else None
+    stats = torch.empty((B, R, 4), dtype=torch.int64, device=mask.device)
+    tl = desc_ncdhw(label_ncdhw) if label_ncdhw is not None else None
+    check(lib.mmtta_mask_fill_nest(ptr(mask), C.byref(tl) if tl is not None else None, B, R, D, H, W, int(fill_connectivity),
+                                   (C.c_int32 * R)(*fh), (C.c_int64 * R)(*cap), (C.c_int32 * max(1, len(chain)))(*chain),
+                                   len(chain), FILL_NEST_MODES.index(nesting_mode), ptr(counts), ptr(stats), ptr(scratch),
+                                   stream_ptr()), "fill_nest")
+    return {"mask": mask, "counts": counts, "stats": stats}
+
+
 _LW_SCRATCH: Dict[Tuple, torch.Tensor] = {}      # working set of lesionwise_scores, per (device, size, stream)
 LESIONWISE_MAX_DILATION = 8
 LESIONWISE_COLUMNS = ("lesions", "lesions_kept", "lesions_found", "pred_components", "matched_components", "dice_q", "fp_voxels")
