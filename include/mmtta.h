@@ -916,6 +916,49 @@ int mmtta_lesionwise_scores(const uint8_t* mask, const mmtta_tensor* label, int 
                             int dilation_connectivity, const int64_t* min_lesion_voxels, int64_t* stats, int32_t* labels,
                             void* scratch, void* stream);
 
+/* Lesion-wise HD95 of the evaluation tail, the other half of the BraTS-2023 lesion-wise score.  Runs right behind
+ * mmtta_lesionwise_scores and only reads what that call left in its scratch: nothing is labelled twice.  Lesions, own
+ * voxels, kept / found and matching are exactly those of mmtta_lesionwise_scores.  For every lesion g that is kept and has
+ * a match, with A_g = its own voxels and P_g = the union of the whole predicted components matched to it:
+ *   edge(X)   X & ~erode6(X), outside the volume counts as background (the edges of mmtta_surface_distances)
+ *   d(X->Y)   for every voxel of edge(X) the Euclidean distance to the nearest voxel of edge(Y), weighted by `spacing`: the
+ *             squared distance in fp64 as (dz sd)^2 + ((dy sh)^2 + (dx sw)^2), the minimum over every candidate (brute
+ *             force: ties cannot change it), then sqrt to float32
+ *   hd_g      max(quantile_q(d(P_g->A_g)), quantile_q(d(A_g->P_g))), q = percentile / 100, linear interpolation in float32
+ *             like torch.quantile (the quantile of mmtta_surface_distances); always finite
+ * A lesion's distances go to the surface of ITS components only, and a component matched to two lesions is measured
+ * against each of them.
+ *   mask, label, n ... w, min_lesion_voxels   those of the mmtta_lesionwise_scores call
+ *   spacing   HOST, 3 doubles in D, H, W order, read before return;  percentile in [0, 100]
+ *   lesionwise_scratch  the scratch of a mmtta_lesionwise_scores call with the same mask, label, shape and
+ *             min_lesion_voxels, queued on the same stream immediately before; only read
+ *   hd_stats  int64 [N][R][3] on the device, zeroed by this call: hd_q = sum over the scored lesions of
+ *             round(hd_g 2^20) (each rounded once, in fp64), lesions scored (= kept lesions with a match unless the mask
+ *             overflows), overflow
+ *   lesion_hd fp32 [N,R,D,H,W] dense on the device or NULL: filled with NaN, then hd_g at index (lesion label - 1) of every
+ *             scored lesion
+ *   scratch   mmtta_lesionwise_hd95_scratch_bytes(N*R, D, H, W) bytes (negative: unsupported extent), a function of the
+ *             shape alone
+ * The volume's score is host arithmetic on integers:
+ *   lw_hd95 = (hd_q / 2^20 + penalty ((kept - found) + false-positive components)) / (kept + false-positive components),
+ * valid iff that denominator is > 0, with the counts of mmtta_lesionwise_scores.
+ * Overflow: the surface of P_g is gathered into one list per lesion, so a component's edge voxels are held once per lesion
+ * it matches; the pool of those lists has 2 D H W entries per mask.  A mask whose lists (summed over its kept lesions) do
+ * not fit writes nothing beyond its pool: none of its lesions is scored, `overflow` counts them, hd_q and lesions scored
+ * stay 0; the other masks of the batch are unaffected and the call returns normally.
+ * Cost: sum over the pairs of |edge(c)| |edge(A_g)| distance evaluations per direction, spread over the whole device in
+ * work units of (lesion, direction, 128 sources).  A fixed sequence of launches on `stream` that depends on the shape
+ * alone: no host read, no convergence flag.  Segments are handed out by atomic bumps; the results depend on neither their
+ * order nor their placement: two calls agree bit for bit and a batch gives what its items give alone.
+ * Limits: those of mmtta_lesionwise_scores, and every extent <= 1024.  Anything else - a null argument, a spacing that is
+ * not positive and finite, a percentile outside [0, 100], a label of another shape or not fp32 - is refused with
+ * MMTTA_ERR_INVALID / _UNSUPPORTED and a message naming the argument, before anything is queued. */
+int64_t mmtta_lesionwise_hd95_scratch_bytes(int64_t n_masks, int64_t d, int64_t h, int64_t w);
+int mmtta_lesionwise_hd95(const uint8_t* mask, const mmtta_tensor* label, int n, int r, int d, int h, int w,
+                          const double* spacing, double percentile, const int64_t* min_lesion_voxels,
+                          const void* lesionwise_scratch, int64_t* hd_stats, float* lesion_hd,
+                          void* scratch, void* stream);
+
 /* Hole filling and region nesting of the evaluation tail, the steps that follow the component filter in common BraTS /
  * HECKTOR post-processing.  Replaces a host `scipy.ndimage.binary_fill_holes` per (volume, region) over a mask copied off
  * the device and a nesting fix in numpy; the reference evaluator has no counterpart.  Per (n, r), in this order:

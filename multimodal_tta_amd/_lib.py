@@ -223,6 +223,9 @@ _SIGNATURES = {
     "mmtta_lesionwise_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mmtta_lesionwise_scores": (C.c_int, [C.c_void_p, _P(Tensor), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           _P(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_lesionwise_hd95_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mmtta_lesionwise_hd95": (C.c_int, [C.c_void_p, _P(Tensor), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_double,
+                                        _P(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_mask_fill_nest_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mmtta_mask_fill_nest": (C.c_int, [C.c_void_p, _P(Tensor), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_int32),
                                        _P(C.c_int64), _P(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -16,7 +16,7 @@
 // Distances are appended to a per-(mask, direction) list; the order statistics come from a radix select on the float
 // bit patterns and the mean from an integer fixed-point sum, so both are independent of the append order: results are
 // bitwise reproducible.  Integer/byte work, HBM/L2-bound; nothing here is GEMM-shaped.
-#include "common.h"
+#include "surface_quantile.h"
 
 namespace mmtta {
 
@@ -169,56 +169,7 @@ __global__ __launch_bounds__(256) void surf_pass_d_kernel(SurfArgs a) {
   if (threadIdx.x == 0 && s_sum != 0ull) atomicAdd(a.sum + sa, s_sum);
 }
 
-// K4: per mask: the two directional quantiles (radix select, 8 bits per round) -> hd; fixed-point sums -> asd.
-__device__ float surf_quantile(const float* list, unsigned int n, float q, unsigned int* hist, unsigned int* sh) {
-  // torch.quantile(linear) in float32: rank = q * (n - 1); lerp(v[floor], v[ceil], rank - floor)
-  const float rank = q * (float)(n - 1);
-  const unsigned int lo = (unsigned int)rank;
-  const float wgt = rank - (float)lo;
-  const bool need_hi = ceilf(rank) != (float)lo;
-  unsigned int prefix = 0, maskbits = 0, k = lo;
-  for (int pass = 3; pass >= 0; --pass) {
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) hist[i] = 0;
-    __syncthreads();
-    for (unsigned int i = threadIdx.x; i < n; i += blockDim.x) {
-      const unsigned int b = __float_as_uint(list[i]);
-      if ((b & maskbits) == prefix) atomicAdd(&hist[(b >> (8 * pass)) & 255u], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned int cum = 0, bsel = 255;
-      for (unsigned int bkt = 0; bkt < 256; ++bkt) {
-        if (cum + hist[bkt] > k) { bsel = bkt; break; }
-        cum += hist[bkt];
-      }
-      sh[0] = bsel; sh[1] = k - cum;
-    }
-    __syncthreads();
-    prefix |= sh[0] << (8 * pass);
-    k = sh[1];
-    maskbits |= 255u << (8 * pass);
-    __syncthreads();
-  }
-  const float vlo = __uint_as_float(prefix);
-  if (!need_hi) return vlo;
-  // v[lo + 1]: vlo again when enough copies of it exist, else the smallest larger value
-  if (threadIdx.x == 0) { sh[0] = 0; sh[1] = 0xffffffffu; }
-  __syncthreads();
-  unsigned int cle = 0, nmin = 0xffffffffu;
-  for (unsigned int i = threadIdx.x; i < n; i += blockDim.x) {
-    const unsigned int b = __float_as_uint(list[i]);
-    if (b <= prefix) ++cle;
-    else nmin = b < nmin ? b : nmin;
-  }
-  atomicAdd(&sh[0], cle);
-  atomicMin(&sh[1], nmin);
-  __syncthreads();
-  const float vhi = (lo + 1 < sh[0]) ? vlo : __uint_as_float(sh[1]);
-  __syncthreads();
-  const float diff = vhi - vlo;
-  return wgt < 0.5f ? fmaf(wgt, diff, vlo) : fmaf(wgt - 1.0f, diff, vhi);
-}
-
+// K4: per mask: the two directional quantiles (surf_quantile, surface_quantile.h) -> hd; fixed-point sums -> asd.
 __global__ __launch_bounds__(1024) void surf_finish_kernel(SurfArgs a, float q, int use_max, int symmetric, float* hd,
                                                            float* asd) {
   __shared__ unsigned int hist[256];

@@ -211,6 +211,68 @@ def lesionwise_columns(stats: torch.Tensor) -> torch.Tensor:
     return torch.cat([lw, valid.to(torch.float64)] + [c.to(torch.float64) for c in (kept, found, fp, matched, pred)])
 
 
+LESIONWISE_HD95_COLUMNS = 2  # table columns per region: lw_hd95, state (1 valid, 0 undefined, -1 the region's surface lists overflowed)
+
+
+def lesionwise_hd95_config(config: Any) -> Tuple[bool, float, Any]:
+    """``evaluation.lesionwise.hd95: {enable, percentile, penalty}`` -> (enable, percentile, penalty); off, 95.0 and
+    ``"diagonal"`` when absent.  ``penalty`` is what a missed lesion and a false-positive component cost: ``diagonal`` (the
+    volume diagonal in mm, the penalty of ``evaluation.surface``) or a positive number (BraTS-2023 uses 374).  A bad value is
+    a ``ValueError`` that names its key, whether the block is enabled or not; so is ``hd95.enable`` without
+    ``evaluation.lesionwise.enable``."""
+    lw = get_config(config, "evaluation.lesionwise", {}) or {}
+    hd = get_config(lw, "hd95", {}) or {}
+    enable = get_config(hd, "enable", False)
+    if not isinstance(enable, bool):
+        raise ValueError(f"evaluation.lesionwise.hd95.enable must be true or false, got {enable!r}")
+    pct = get_config(hd, "percentile", 95.0)
+    if isinstance(pct, bool) or not isinstance(pct, (int, float)) or not 0.0 <= float(pct) <= 100.0:
+        raise ValueError(f"evaluation.lesionwise.hd95.percentile must be a number in [0, 100], got {pct!r}")
+    pen = get_config(hd, "penalty", "diagonal")
+    if isinstance(pen, str):
+        if pen != "diagonal":
+            raise ValueError(f"evaluation.lesionwise.hd95.penalty must be 'diagonal' or a positive number, got {pen!r}")
+    elif isinstance(pen, bool) or not isinstance(pen, (int, float)) or not (math.isfinite(float(pen)) and float(pen) > 0.0):
+        raise ValueError(f"evaluation.lesionwise.hd95.penalty must be 'diagonal' or a positive number, got {pen!r}")
+    else:
+        pen = float(pen)
+    if enable and get_config(lw, "enable", False) is not True:
+        raise ValueError("evaluation.lesionwise.hd95.enable needs evaluation.lesionwise.enable: the HD95 pass reads what the "
+                         "lesion-wise Dice pass leaves on the device")
+    return enable, float(pct), pen
+
+
+def volume_diagonal_mm(shape: Sequence[int], spacing: Sequence[float]) -> float:
+    """The diagonal of a D x H x W volume in mm, between the centres of its corner voxels (reference
+    src/evaluation/seg_eval.py:89-103): the penalty of the surface metrics."""
+    D, H, W = (int(v) for v in shape)
+    sd, sh, sw = spacing
+    dd, hh, ww = max(D - 1, 0) * sd, max(H - 1, 0) * sh, max(W - 1, 0) * sw
+    return float(math.sqrt(dd * dd + hh * hh + ww * ww))
+
+
+def lesionwise_hd95_columns(stats: torch.Tensor, hd_stats: torch.Tensor, penalty: float) -> torch.Tensor:
+    """stats int64 [R,7] (``ops.LESIONWISE_COLUMNS``) and hd_stats int64 [R,3] (``ops.LESIONWISE_HD_COLUMNS``) of one volume
+    -> its table columns float64 [2*R]: lw_hd95[R], state[R].
+
+        lw_hd95 = (hd_q / 2^20 + penalty ((kept - found) + false-positive components)) / (kept + false-positive components)
+
+    state is 1 where that denominator is > 0 (a GT-empty region with false positives IS scored, with the penalty), 0 where
+    there is nothing to find and nothing predicted, and -1 where the region's surface lists overflowed on the device: then
+    the score reads 0, stays out of the mean and the volume is counted under ``*_lw_hd95_overflow``."""
+    s, h = stats.to(torch.int64), hd_stats.to(torch.int64)
+    kept, found, pred, matched = s[:, 1], s[:, 2], s[:, 3], s[:, 4]
+    fp = pred - matched
+    den = kept + fp
+    over = h[:, 2] > 0
+    valid = (den > 0) & ~over
+    safe = torch.where(den > 0, den, torch.ones_like(den)).to(torch.float64)
+    num = h[:, 0].to(torch.float64) / float(ops.LESIONWISE_HD_Q_ONE) + float(penalty) * ((kept - found) + fp).to(torch.float64)
+    lw = torch.where(valid, num / safe, torch.zeros_like(safe))
+    state = torch.where(over, -torch.ones_like(safe), valid.to(torch.float64))
+    return torch.cat([lw, state])
+
+
 def calibration_from_bins(table: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """The table of ``ops.calibration_bins`` (float64 [..., 3*bins + 2]: per bin count, sum of confidence, correct count;
     then the Brier sum, then the NLL sum) -> (ece, brier, nll, valid), float64 / bool of the leading shape.
@@ -250,11 +312,12 @@ class RegionAccumulator:
     GT-empty region with false-positive components IS one of them, with 0), per-volume means of kept lesions, found
     lesions and false-positive components, and recall / precision pooled over all volumes.  ``fill_nest`` adds the figures
     of the hole filling and nesting pass: per-volume means over all volumes of holes, filled holes, filled voxels and voxels
-    the nesting changed."""
+    the nesting changed.  ``lesionwise_hd95`` adds the lesion-wise HD95 averaged over the volumes where it is defined and did
+    not overflow, and the per-volume mean of overflowed volumes."""
 
     def __init__(self, region_order: Sequence[str], surface: bool = False, bins: int = 0,
                  calibration_regions: Optional[Sequence[str]] = None, components: bool = False, lesionwise: bool = False,
-                 fill_nest: bool = False):
+                 fill_nest: bool = False, lesionwise_hd95: bool = False):
         self.regions = list(region_order)
         self.surface = bool(surface)
         R = len(self.regions)
@@ -279,6 +342,10 @@ class RegionAccumulator:
         self._zl = lambda: torch.zeros((LESIONWISE_COLUMNS + 1, R), dtype=torch.float64)
         self.lw_tot = self._zl()
         self.lw_dom: Dict[str, torch.Tensor] = defaultdict(self._zl)
+        self.lesionwise_hd95 = bool(lesionwise_hd95)
+        self._zh = lambda: torch.zeros((4, R), dtype=torch.float64)          # sum_lw_hd95, valid volumes, overflowed volumes, volumes
+        self.lh_tot = self._zh()
+        self.lh_dom: Dict[str, torch.Tensor] = defaultdict(self._zh)
         self.fill_nest = bool(fill_nest)
         self._zf = lambda: torch.zeros((FILL_NEST_COLUMNS + 1, R), dtype=torch.float64)      # the 4 columns summed, then the volumes
         self.fn_tot = self._zf()
@@ -319,6 +386,24 @@ class RegionAccumulator:
             if acc[6][k] > 0:
                 out[f"{prefix}{name.lower()}_lesion_precision"] = float((acc[5][k] / acc[6][k]).item())
 
+    def add_lesionwise_hd95(self, cols: Any, domain: str) -> None:
+        """One volume's lesion-wise HD95 columns, [2*R] as the table holds them (``lesionwise_hd95_columns``)."""
+        c = torch.as_tensor(cols, dtype=torch.float64).reshape(LESIONWISE_HD95_COLUMNS, len(self.regions))
+        ok, over = (c[1] > 0.5).to(torch.float64), (c[1] < -0.5).to(torch.float64)
+        for acc in (self.lh_tot, self.lh_dom[domain]):
+            acc[0] += c[0] * ok
+            acc[1] += ok
+            acc[2] += over
+            acc[3] += 1.0
+
+    def _lesionwise_hd95_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
+        means = self._fin(acc[0], acc[1])
+        for name, v in zip(self.regions, means):
+            out[f"{prefix}{name.lower()}_lw_hd95"] = v
+        out[f"{prefix}avg_lw_hd95"] = self._avg(means, acc[1])
+        for name, v in zip(self.regions, self._fin(acc[2], acc[3])):
+            out[f"{prefix}{name.lower()}_lw_hd95_overflow"] = v
+
     def add_components(self, stats: Any, domain: str) -> None:
         """One volume's component figures, [3*R] as the table holds them: components[R], kept[R], removed voxels[R]."""
         st = torch.as_tensor(stats, dtype=torch.float64).reshape(3, len(self.regions))
@@ -356,7 +441,7 @@ class RegionAccumulator:
     def add_row(self, dice: Sequence[float], iou: Sequence[float], valid: Sequence[bool], domain: str,
                 hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None,
                 calibration: Optional[torch.Tensor] = None, components: Any = None, lesionwise: Any = None,
-                fill_nest: Any = None) -> None:
+                fill_nest: Any = None, lesionwise_hd95: Any = None) -> None:
         d = self.dom[domain]
         if self.components:
             self.add_components(components, domain)
@@ -364,6 +449,8 @@ class RegionAccumulator:
             self.add_fill_nest(fill_nest, domain)
         if self.lesionwise:
             self.add_lesionwise(lesionwise, domain)
+        if self.lesionwise_hd95:
+            self.add_lesionwise_hd95(lesionwise_hd95, domain)
         if self.bins:
             self.add_calibration(calibration, domain)
         for c in range(len(self.regions)):
@@ -412,6 +499,8 @@ class RegionAccumulator:
             self._fill_nest_keys(out, "", self.fn_tot)
         if self.lesionwise:
             self._lesionwise_keys(out, "", self.lw_tot)
+        if self.lesionwise_hd95:
+            self._lesionwise_hd95_keys(out, "", self.lh_tot)
         if self.bins:
             self._calibration_keys(out, "", self.cal_tot)
         for dom in sorted(self.dom.keys()):
@@ -430,6 +519,8 @@ class RegionAccumulator:
                 self._fill_nest_keys(out, f"dom/{safe}/", self.fn_dom[dom])
             if self.lesionwise:
                 self._lesionwise_keys(out, f"dom/{safe}/", self.lw_dom[dom])
+            if self.lesionwise_hd95:
+                self._lesionwise_hd95_keys(out, f"dom/{safe}/", self.lh_dom[dom])
             if self.bins:
                 self._calibration_keys(out, f"dom/{safe}/", self.cal_dom[dom])
         return out
@@ -545,6 +636,10 @@ class SegmentationEvaluationStrategy:
             raise NotImplementedError("evaluation.lesionwise.enable: lesion-wise scores are defined for the sigmoid-region head "
                                       "only (training.criterion.softmax is set)")
         self._lw: Optional[torch.Tensor] = None
+        # lesion-wise HD95 on top of that, off by default: one more pass behind the lesion-wise scores, on their scratch
+        (self.enable_lesionwise_hd95, self.lesionwise_hd95_percentile,
+         self.lesionwise_hd95_penalty) = lesionwise_hd95_config(self.config)
+        self._lwhd: Optional[torch.Tensor] = None
         # input pre-pass on the GPU (raw volumes in, the reference's `_normalize_img` applied here instead of in the
         # dataset worker; reference src/datasets/transforms.py:129-223).  The NIfTI datasets of this package hand over
         # raw intensities, so the pre-pass defaults to on for them and to off for the synthetic source (already
@@ -612,6 +707,19 @@ class SegmentationEvaluationStrategy:
         return ops.lesionwise_scores(mask, y, self.lesionwise_dilation, self.lesionwise_connectivity,
                                      self.lesionwise_min_voxels)["stats"]
 
+    def lesionwise_hd95_launch(self, mask: torch.Tensor, y: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Queue the lesion-wise scores AND the lesion-wise HD95 of (mask, y) on the current stream -> device (stats int64
+        [B,R,7], hd_stats int64 [B,R,3])."""
+        res = ops.lesionwise_hd95(mask, y, self.lesionwise_dilation, self.lesionwise_connectivity, self.lesionwise_min_voxels,
+                                  self.spacing, self.lesionwise_hd95_percentile)
+        return res["stats"], res["hd_stats"]
+
+    def lesionwise_hd95_penalty_mm(self, shape) -> float:
+        """The penalty of a missed lesion or a false-positive component for a volume of this shape."""
+        if self.lesionwise_hd95_penalty == "diagonal":
+            return volume_diagonal_mm(shape, self.spacing)
+        return float(self.lesionwise_hd95_penalty)
+
     @staticmethod
     def component_columns(stats: torch.Tensor) -> torch.Tensor:
         """stats int64 [R,3] of one volume -> its table columns float64 [3*R]: components[R], kept[R], removed voxels[R]."""
@@ -638,7 +746,12 @@ class SegmentationEvaluationStrategy:
                 counts, fill = self.fill_nest_launch(self._mask, y)
                 self._fill = fill.cpu()
             self._stats = stats.cpu()
-        self._lw = self.lesionwise_launch(self._mask, y).cpu() if self.enable_lesionwise else None
+        self._lw = self._lwhd = None
+        if self.enable_lesionwise_hd95:
+            lw, lwhd = self.lesionwise_hd95_launch(self._mask, y)
+            self._lw, self._lwhd = lw.cpu(), lwhd.cpu()
+        elif self.enable_lesionwise:
+            self._lw = self.lesionwise_launch(self._mask, y).cpu()
         return counts.cpu()
 
     def calibration_launch(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
@@ -656,10 +769,7 @@ class SegmentationEvaluationStrategy:
     def surface_fix(self, hd: torch.Tensor, asd: torch.Tensor, counts: torch.Tensor, shape) -> Tuple[torch.Tensor, torch.Tensor]:
         """The reference's penalty (GT non-empty, prediction empty -> volume diagonal in mm) and sanitising (non-finite ->
         diagonal) on the valid entries (reference src/evaluation/seg_eval.py:342-355); host tensors out."""
-        D, H, W = (int(v) for v in shape)
-        sd, sh, sw = self.spacing
-        dd, hh, ww = max(D - 1, 0) * sd, max(H - 1, 0) * sh, max(W - 1, 0) * sw
-        diag_mm = float(math.sqrt(dd * dd + hh * hh + ww * ww))
+        diag_mm = volume_diagonal_mm(shape, self.spacing)
         hd, asd = hd.cpu(), asd.cpu()
         valid = counts[..., 2] > 0
         pred_empty = counts[..., 1] == 0
@@ -687,7 +797,8 @@ class SegmentationEvaluationStrategy:
         model.eval()
         model.to(device)
         acc = RegionAccumulator(self.region_order, self.enable_surface, self.cal_bins, self.calibration_regions,
-                                self.enable_postprocess, self.enable_lesionwise, self.enable_fill_nest)
+                                self.enable_postprocess, self.enable_lesionwise, self.enable_fill_nest,
+                                self.enable_lesionwise_hd95)
         rows: List[torch.Tensor] = []
         domain_names: List[str] = []
         n_local = 0
@@ -700,6 +811,8 @@ class SegmentationEvaluationStrategy:
             cal = self.calibration_launch(logits.float(), y).cpu() if self.enable_calibration else None
             comp = [self.component_columns(st) for st in self._stats] if self.enable_postprocess else None
             lw = [lesionwise_columns(st) for st in self._lw] if self.enable_lesionwise else None
+            lh = ([lesionwise_hd95_columns(st, hs, self.lesionwise_hd95_penalty_mm(y.shape[2:]))
+                   for st, hs in zip(self._lw, self._lwhd)] if self.enable_lesionwise_hd95 else None)
             fn = [self.fill_nest_columns(st) for st in self._fill] if self.enable_fill_nest else None
             domains = as_list_str(batch.get("domain", None), batch_size=x.size(0))
             if world == 1:
@@ -707,7 +820,8 @@ class SegmentationEvaluationStrategy:
                     acc.add_row(dice[i].tolist(), iou[i].tolist(), valid[i].tolist(), domains[i],
                                 hd[i].tolist() if hd is not None else None, asd[i].tolist() if asd is not None else None,
                                 cal[i] if cal is not None else None, comp[i] if comp is not None else None,
-                                lw[i] if lw is not None else None, fn[i] if fn is not None else None)
+                                lw[i] if lw is not None else None, fn[i] if fn is not None else None,
+                                lh[i] if lh is not None else None)
                 if self.report_loss:
                     acc.add_loss(self.loss_fn(logits.float(), y), x.size(0))
                 continue
@@ -731,6 +845,8 @@ class SegmentationEvaluationStrategy:
                     parts.append(fn[i])
                 if lw is not None:
                     parts.append(lw[i])
+                if lh is not None:
+                    parts.append(lh[i])
                 if cal is not None:
                     parts.append(cal[i].reshape(-1))
                 rows.append(torch.cat(parts))
@@ -747,7 +863,7 @@ class SegmentationEvaluationStrategy:
     def _table_width(self) -> int:
         return table_width(len(self.region_order), self.enable_surface, self.cal_bins, len(self.calibration_regions),
                            components=self.enable_postprocess, lesionwise=self.enable_lesionwise,
-                           fill_nest=self.enable_fill_nest)
+                           fill_nest=self.enable_fill_nest, lesionwise_hd95=self.enable_lesionwise_hd95)
 
     def _metrics_of(self, table: torch.Tensor, domain_names: Sequence[str]) -> Dict[str, float]:
         """Metrics of the whole split from its per-volume table (and ``last_reliability`` with calibration on)."""
@@ -755,7 +871,8 @@ class SegmentationEvaluationStrategy:
             self.last_reliability = reliability_from_table(table, self.calibration_bins, len(self.calibration_regions))
         return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface,
                                   self.cal_bins, self.calibration_regions, components=self.enable_postprocess,
-                                  lesionwise=self.enable_lesionwise, fill_nest=self.enable_fill_nest)
+                                  lesionwise=self.enable_lesionwise, fill_nest=self.enable_fill_nest,
+                                  lesionwise_hd95=self.enable_lesionwise_hd95)
 
 
 # ----------------------------------------------------------------------------- sharding
@@ -765,14 +882,14 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
 
 
 def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None, components: bool = False,
-                lesionwise: bool = False, fill_nest: bool = False) -> int:
+                lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False) -> int:
     """index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R]) (, with ``components`` the figures of the
     post-processing: components[R], kept[R], removed voxels[R]) (, with ``fill_nest`` the figures of the hole filling and
     nesting: holes[R], filled holes[R], filled voxels[R], nested voxels[R]) (, with ``lesionwise`` the 7*R columns of
-    ``lesionwise_columns``) (, with ``bins`` > 0 the volume's raw calibration table: ``rout`` rows - default R - of
+    ``lesionwise_columns``) (, with ``lesionwise_hd95`` the 2*R columns of ``lesionwise_hd95_columns``) (, with ``bins`` > 0 the volume's raw calibration table: ``rout`` rows - default R - of
     3*bins + 2 doubles, always last)."""
     return (3 + (5 if surface else 3) * R + (3 * R if components else 0) + (FILL_NEST_COLUMNS * R if fill_nest else 0) +
-            (LESIONWISE_COLUMNS * R if lesionwise else 0) +
+            (LESIONWISE_COLUMNS * R if lesionwise else 0) + (LESIONWISE_HD95_COLUMNS * R if lesionwise_hd95 else 0) +
             calibration_width(bins, R if rout is None else rout))
 
 
@@ -852,17 +969,19 @@ def gather_masks(local: Sequence[Tuple[int, torch.Tensor]], device, group=None) 
 def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_names: Sequence[str],
                        report_loss: bool, surface: bool = False, bins: int = 0,
                        calibration_regions: Optional[Sequence[str]] = None, components: bool = False,
-                       lesionwise: bool = False, fill_nest: bool = False) -> Dict[str, float]:
+                       lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False) -> Dict[str, float]:
     """Replay the reference aggregation over gathered rows in volume-index order: the result is
     identical to a single-process run (float64 sums, order fixed by index).  ``bins`` > 0: the rows end in the raw
     calibration table of their volume (``table_width``), one row of it per name in ``calibration_regions``.
     ``components``: the 3*R component columns sit behind the surface columns (``table_width``); ``fill_nest``: the 4*R
-    columns of the hole filling and nesting sit behind those; ``lesionwise``: the 7*R lesion-wise columns sit behind those."""
+    columns of the hole filling and nesting sit behind those; ``lesionwise``: the 7*R lesion-wise columns sit behind those;
+    ``lesionwise_hd95``: the 2*R lesion-wise HD95 columns sit directly behind those."""
     R = len(region_order)
-    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components, lesionwise, fill_nest)
+    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components, lesionwise, fill_nest, lesionwise_hd95)
     c0 = 3 + (5 if surface else 3) * R
     f0 = c0 + (3 * R if components else 0)
     l0 = f0 + (FILL_NEST_COLUMNS * R if fill_nest else 0)
+    h0 = l0 + (LESIONWISE_COLUMNS * R if lesionwise else 0)
     cal_w = calibration_width(bins, len(acc.cal_regions))
     for row in table:
         dom = domain_names[int(row[1].item())] if 0 <= int(row[1].item()) < len(domain_names) else ""
@@ -874,7 +993,8 @@ def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_
         acc.add_row(dice, iou, valid, dom, hd, asd, row[row.numel() - cal_w:] if bins else None,
                     row[c0:c0 + 3 * R] if components else None,
                     row[l0:l0 + LESIONWISE_COLUMNS * R] if lesionwise else None,
-                    row[f0:f0 + FILL_NEST_COLUMNS * R] if fill_nest else None)
+                    row[f0:f0 + FILL_NEST_COLUMNS * R] if fill_nest else None,
+                    row[h0:h0 + LESIONWISE_HD95_COLUMNS * R] if lesionwise_hd95 else None)
         if report_loss:
             acc.add_loss(float(row[2].item()), 1)
     return acc.metrics(report_loss)
@@ -999,7 +1119,9 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
             job["components"] = stats
         if fill is not None:
             job["fill_nest"] = fill
-        if self.enable_lesionwise:       # right behind the counts, on the mask they describe
+        if self.enable_lesionwise_hd95:  # right behind the counts, on the mask they describe; the HD95 pass on the same scratch
+            job["lesionwise"], job["lesionwise_hd95"] = self.lesionwise_hd95_launch(mask, yb)
+        elif self.enable_lesionwise:
             job["lesionwise"] = self.lesionwise_launch(mask, yb)
         if self.report_loss:
             job["loss"] = self.loss_fn.launch(res["logits_cl"], yb, channels_last=True)
@@ -1020,6 +1142,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         cal = job["calibration"].cpu() if self.enable_calibration else None
         comp = job["components"].cpu() if self.enable_postprocess else None
         lw = job["lesionwise"].cpu() if self.enable_lesionwise else None
+        lh = job["lesionwise_hd95"].cpu() if self.enable_lesionwise_hd95 else None
+        pen = self.lesionwise_hd95_penalty_mm(job["shape"]) if self.enable_lesionwise_hd95 else 0.0
         fn = job["fill_nest"].cpu() if self.enable_fill_nest else None
         rows = []
         for b in range(B):
@@ -1033,6 +1157,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
                 parts.append(self.fill_nest_columns(fn[b]))
             if lw is not None:
                 parts.append(lesionwise_columns(lw[b]))
+            if lh is not None:
+                parts.append(lesionwise_hd95_columns(lw[b], lh[b], pen))
             if cal is not None:
                 parts.append(cal[b].reshape(-1))
             rows.append(torch.cat(parts))

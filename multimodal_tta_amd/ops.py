@@ -9,6 +9,7 @@ the calls can be captured into a graph.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from dataclasses import dataclass
@@ -1443,3 +1444,55 @@ def lesionwise_scores(mask: torch.Tensor, label_ncdhw: torch.Tensor, iterations:
                                       (C.c_int64 * R)(*mv), ptr(stats), ptr(labels), ptr(scratch), stream_ptr()),
           "lesionwise_scores")
     return {"stats": stats, "labels": labels}
+
+
+_LW_HD_SCRATCH: Dict[Tuple, torch.Tensor] = {}   # working set of lesionwise_hd95 beside the one of lesionwise_scores, likewise
+LESIONWISE_HD_COLUMNS = ("hd_q", "lesions_scored", "overflow")
+LESIONWISE_HD_Q_ONE = 1 << 20                    # a lesion's HD is summed in units of 2^-20
+LESIONWISE_HD_MAX_EXTENT = 1024
+
+
+def lesionwise_hd95(mask: torch.Tensor, label_ncdhw: torch.Tensor, iterations: int = 3, dilation_connectivity: int = 18,
+                    min_lesion_voxels=0, spacing: Sequence[float] = (1.0, 1.0, 1.0), percentile: float = 95.0,
+                    want_lesion_hd: bool = False, want_labels: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+    """Lesion-wise scores AND lesion-wise HD of every (volume, region) of ``mask`` against ``label_ncdhw``: ``lesionwise_scores``
+    followed, on the same scratch and the current stream, by include/mmtta.h: mmtta_lesionwise_hd95.  Every kept lesion with a
+    match gets the ``percentile`` Hausdorff distance between the surface of its own voxels and the surface of the predicted
+    components matched to it, in the units of ``spacing`` (D, H, W order).  Returns the device tensors ``stats`` int64 [B,R,7]
+    (identical to ``lesionwise_scores``' own), ``hd_stats`` int64 [B,R,3] (``LESIONWISE_HD_COLUMNS``; ``hd_q`` in units of
+    2^-20; ``overflow`` > 0: the region's surface lists did not fit and none of its lesions is scored), ``lesion_hd`` float32
+    [B,R,D,H,W] (NaN, and a lesion's HD at index lesion label - 1; with ``want_lesion_hd``) and ``labels`` (with
+    ``want_labels``)."""
+    try:
+        sp = [float(v) for v in spacing]
+    except (TypeError, ValueError):
+        sp = []
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0.0 for v in sp):
+        raise MmttaError(f"lesionwise_hd95: spacing must be three positive finite numbers (D, H, W), got {spacing!r}")
+    if isinstance(percentile, bool) or not isinstance(percentile, (int, float)) or not 0.0 <= float(percentile) <= 100.0:
+        raise MmttaError(f"lesionwise_hd95: percentile {percentile!r} (a number in [0, 100])")
+    if torch.is_tensor(mask) and mask.dim() == 5 and max(int(v) for v in mask.shape[2:]) > LESIONWISE_HD_MAX_EXTENT:
+        raise MmttaError(f"lesionwise_hd95: extent {tuple(mask.shape[2:])} unsupported (at most {LESIONWISE_HD_MAX_EXTENT} per axis)")
+    res = lesionwise_scores(mask, label_ncdhw, iterations, dilation_connectivity, min_lesion_voxels, want_labels=want_labels)
+    B, R, D, H, W = (int(v) for v in mask.shape)
+    vals = [min_lesion_voxels] * R if isinstance(min_lesion_voxels, (bool, int)) else list(min_lesion_voxels)
+    mv = [int(v) for v in vals]
+    lib = _lib.load()
+    stream = int(torch.cuda.current_stream().cuda_stream)
+    lw_scratch = _LW_SCRATCH[(mask.device.index, int(lib.mmtta_lesionwise_scratch_bytes(B * R, D, H, W)), stream)]
+    nbytes = int(lib.mmtta_lesionwise_hd95_scratch_bytes(B * R, D, H, W))
+    if nbytes < 0:
+        raise MmttaError(f"lesionwise_hd95: extent {(B * R, D, H, W)} unsupported")
+    key = (mask.device.index, nbytes, stream)
+    scratch = _LW_HD_SCRATCH.get(key)
+    if scratch is None:
+        for k in [k for k in _LW_HD_SCRATCH if k[2] == key[2]]:
+            del _LW_HD_SCRATCH[k]
+        scratch = _LW_HD_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+    hd_stats = torch.empty((B, R, 3), dtype=torch.int64, device=mask.device)
+    lesion_hd = torch.empty((B, R, D, H, W), dtype=torch.float32, device=mask.device) if want_lesion_hd else None
+    tl = desc_ncdhw(label_ncdhw)
+    check(lib.mmtta_lesionwise_hd95(ptr(mask), C.byref(tl), B, R, D, H, W, (C.c_double * 3)(*sp), float(percentile),
+                                    (C.c_int64 * R)(*mv), ptr(lw_scratch), ptr(hd_stats), ptr(lesion_hd), ptr(scratch),
+                                    stream_ptr()), "lesionwise_hd95")
+    return {"stats": res["stats"], "hd_stats": hd_stats, "lesion_hd": lesion_hd, "labels": res["labels"]}
