@@ -733,6 +733,46 @@ int64_t mmtta_fisher_penalty_partials(int64_t n, int sets);
 int mmtta_fisher_penalty_sets(const float* w, float* g, const float* fisher, const float* source, int64_t n, int sets,
                               int replicas, int64_t set_stride, float lambda, double* partial, float* penalty, void* stream);
 
+/* ------------------------------------------------------------------ DeYO ----------------- */
+/* DeYO (Lee et al., ICLR 2024, "Entropy is not Enough for Test-Time Adaptation") - csrc/deyo.hip.
+ *
+ * The patch grid of both entry points: grid[3] = (gd, gh, gw) patches per axis, every count >= 1 and a divisor of its extent,
+ *   2 <= P = gd gh gw <= 4096; slot j (row-major over the grid) covers the voxels j (+) o, o the offset inside the patch.
+ *   `table` is device int32 [N][2][P]: row 0 of batch item n is its permutation `perm` (slot j of the shuffled volume holds
+ *   patch perm[j]), row 1 the inverse (the content of patch s went to slot inv[s]).  The kernels clamp every entry they read
+ *   to [0, P): whatever the table holds, no access leaves the item (the result is then unspecified).
+ *
+ * mmtta_patch_shuffle: y[n, j (+) o] = x[n, perm_n[j] (+) o].  Channels-last [N,D,H,W,C] of equal shape, row width and
+ *   storage (fp32 or bf16); whole voxel rows are copied, pad lanes included, bit-exact - the contract of mmtta_mirror_views,
+ *   so `y` must own the pad lanes of its rows.  `x` and `y` may not overlap (an in-place call is MMTTA_ERR_INVALID).  A
+ *   gather of contiguous runs of W / gw voxel rows with 16 / 8-byte accesses, one launch, no LDS.
+ *
+ * mmtta_deyo_loss_items: the reliable entropy of N independent items, filtered and weighted by the pseudo-label probability
+ *   difference between `logits` (z) and `logits_shuffled` (z', the logits of the shuffled volume).  Elements, margins (nats),
+ *   mask layout, launch geometry, storages (fp32 logits; fp32 or - on the <= 4-region fast path - bf16 thin gradients) and the
+ *   three launches are those of mmtta_entropy_weighted_items; the entropy arithmetic is that entry point's, so kept_entropy
+ *   equals the `kept` of mmtta_entropy_filtered_items at `margin` bit for bit.  z''(v) = z' at the voxel where the content of
+ *   v went, read from `logits_shuffled` through row 1 of the table (one more voxel row per voxel; no un-shuffled copy is
+ *   written).  Per element, with y^ the hard prediction of z (sigmoid head: 1[z >= 0]; softmax head: the first arg max):
+ *     PLPD  = p(z)[y^] - p(z'')[y^]         (sigmoid head: sigmoid(|z|) - sigmoid(s z''), s = +1 where z >= 0, else -1)
+ *     keep1 = H < margin;  keep = keep1 and PLPD > plpd_threshold
+ *     a     = exp(margin0 - H) + exp(PLPD)  (a constant of the gradient)
+ *   and per item  kept_entropy = |keep1|;  kept = |keep|;  loss = sum_keep a H / kept;  dlogits = keep * a * dH/dz / kept.
+ *   Nothing kept gives loss NaN, kept 0 and a zero gradient.  N items in one call equal N calls bit for bit.
+ *     keep_out  uint8, one byte per element (N*D*H*W*R, softmax head N*D*H*W): keep
+ *     partial   fp64 [mmtta_deyo_partials(logits)] scratch (block partials of the sum and of the two counts)
+ *     loss      fp32 [N];  kept, kept_entropy  int64 [N]
+ *
+ * Bad arguments (null pointers, shape or storage mismatches between x and y, a grid that does not divide the extents, P < 2,
+ * P > 4096, a margin that is not finite and positive, a threshold that is not finite with -1 <= threshold < 1) are
+ * MMTTA_ERR_INVALID, storages without a kernel MMTTA_ERR_UNSUPPORTED, both before anything is launched. */
+int mmtta_patch_shuffle(const mmtta_tensor* x, const mmtta_tensor* y, const int32_t* grid, const int32_t* table, void* stream);
+int64_t mmtta_deyo_partials(const mmtta_tensor* logits);
+int mmtta_deyo_loss_items(const mmtta_tensor* logits, const mmtta_tensor* logits_shuffled, const int32_t* grid,
+                          const int32_t* table, int softmax, float margin, float margin0, float plpd_threshold,
+                          uint8_t* keep_out, const mmtta_tensor* dlogits, double* partial, float* loss, int64_t* kept,
+                          int64_t* kept_entropy, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

@@ -196,6 +196,11 @@ _SIGNATURES = {
     "mmtta_fisher_penalty_partials": (C.c_int64, [C.c_int64, C.c_int]),
     "mmtta_fisher_penalty_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                             C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_patch_shuffle": (C.c_int, [_P(Tensor), _P(Tensor), _P(C.c_int32), C.c_void_p, C.c_void_p]),
+    "mmtta_deyo_partials": (C.c_int64, [_P(Tensor)]),
+    "mmtta_deyo_loss_items": (C.c_int, [_P(Tensor), _P(Tensor), _P(C.c_int32), C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                        C.c_float, C.c_void_p, _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "mmtta_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mmtta_optim_step": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,

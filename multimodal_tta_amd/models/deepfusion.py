@@ -311,6 +311,9 @@ class DeepFusionRuntime(Runtime):
             self.dec.append(build_residual_unit(self, f"decoder_stages.{j}.conv", st.conv))
         self.final = self.make_conv("final_conv", model.final_conv)
         self.nstage = len(self.dec)
+        # the pool buffer the encoders read as their family batch: stage_input / stage_views fill "xm"; a method that forwards
+        # a second staged input (deyo_tta's shuffled volume) fills another with stage_family and switches the key around it
+        self.family_key = "xm"
 
     # ---------------------------------------------------------------- input
     def stage_input(self, x: torch.Tensor) -> torch.Tensor:
@@ -332,6 +335,15 @@ class DeepFusionRuntime(Runtime):
         for m in range(M):
             ops.lincomb([xv[..., m:m + 1]], [1.0], self._member(xm, M, m))
         return xv
+
+    def stage_family(self, x_cl: torch.Tensor, key: str) -> torch.Tensor:
+        """The family batch of a staged channels-last input [n, D, H, W, M] in the pool buffer ``key`` (what ``family_key``
+        then names for a forward of that input): one ``lincomb`` per modality, as ``stage_views`` fills ``xm``."""
+        n, D, H, W, M = x_cl.shape
+        xm = self.pool.cl(key, n * M, D, H, W, 1, ldc=4, zero=True)
+        for m in range(M):
+            ops.lincomb([x_cl[..., m:m + 1]], [1.0], self._member(xm, M, m))
+        return xm
 
     def _member(self, t: torch.Tensor, M: int, m: int) -> torch.Tensor:
         """[n * M, ...] family batch -> the [n, ...] view of member m (batch stride M items).  With views (group 1 only) the
@@ -363,7 +375,7 @@ class DeepFusionRuntime(Runtime):
             dims.append((d // 2, h // 2, w // 2))
         bd = dims[nlev - 1]
         mem = lambda t, m: self._member(t, M, m)
-        xm = pool.cl("xm", n * M, D, H, W, 1, ldc=4, zero=True)          # filled by stage_input
+        xm = pool.cl(self.family_key, n * M, D, H, W, 1, ldc=4, zero=True)          # filled by stage_input
         self.state = dict(n=n, dims=dims, keep=keep, x=x_cl)
         # encoders: every layer ONE launch sequence over the n * M (volume, modality) items -------------------
         skips: List[torch.Tensor] = []

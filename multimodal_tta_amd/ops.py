@@ -1050,6 +1050,76 @@ def fisher_penalty_sets(w: torch.Tensor, g: torch.Tensor, fisher: torch.Tensor, 
           "fisher_penalty_sets")
 
 
+def _patch_grid(grid: Sequence[int]):
+    """The host array (gd, gh, gw) the DeYO entry points read at launch."""
+    if len(grid) != 3:
+        raise MmttaError(f"patch grid {list(grid)!r}: expected three patch counts (gd, gh, gw)")
+    return (C.c_int32 * 3)(*[int(g) for g in grid])
+
+
+def patch_table(perms: Sequence[Sequence[int]]) -> torch.Tensor:
+    """The host table int32 [N, 2, P] of ``patch_shuffle`` / ``deyo_loss_items`` from one permutation of range(P) per batch
+    item: row 0 the permutation (slot j of the shuffled volume holds patch perm[j]), row 1 its inverse.  Raises unless every
+    permutation is a bijection of [0, P) - what is uploaded is checked here, the kernels only clamp."""
+    n = len(perms)
+    p = len(perms[0]) if n else 0
+    table = torch.empty((n, 2, max(p, 1)), dtype=torch.int32)
+    for i, perm in enumerate(perms):
+        row = [int(v) for v in perm]
+        if len(row) != p or p < 1 or sorted(row) != list(range(p)):
+            raise MmttaError(f"patch_table: item {i}: {row!r} is no permutation of range({p})")
+        table[i, 0] = torch.tensor(row, dtype=torch.int32)
+        table[i, 1, torch.tensor(row, dtype=torch.int64)] = torch.arange(p, dtype=torch.int32)
+    return table
+
+
+def _check_patch_table(what: str, table: torch.Tensor, n: int, grid: Sequence[int]) -> None:
+    need = n * 2 * max(int(grid[0]) * int(grid[1]) * int(grid[2]), 0)
+    if table.dtype != torch.int32 or not table.is_contiguous() or not table.is_cuda or table.numel() < need:
+        raise MmttaError(f"{what}: table must be contiguous device int32 of at least {need} elements ([{n}, 2, P])")
+
+
+def patch_shuffle(x: torch.Tensor, y: torch.Tensor, grid: Sequence[int], table: torch.Tensor) -> None:
+    """y[n, slot j (+) o] = x[n, patch perm_n[j] (+) o]: the patches of a (gd, gh, gw) grid of every batch item permuted by
+    row 0 of the item's ``table`` entry (device int32 [N, 2, P], the upload of ``patch_table``).  Channels-last [N,D,H,W,C]
+    of one shape, whole voxel rows (pad lanes included), fp32 or bf16, bit-exact; not in place."""
+    garr = _patch_grid(grid)
+    _check_patch_table("patch_shuffle", table, int(x.shape[0]), grid)
+    tx, ty = desc_cl(x), desc_cl(y)
+    check(_lib.load().mmtta_patch_shuffle(C.byref(tx), C.byref(ty), garr, ptr(table), stream_ptr()), "patch_shuffle")
+
+
+def deyo_partials(logits: torch.Tensor) -> int:
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_deyo_partials(C.byref(t)))
+
+
+def deyo_loss_items(logits: torch.Tensor, logits_shuffled: torch.Tensor, dlogits: torch.Tensor, grid: Sequence[int],
+                    table: torch.Tensor, margin: float, margin0: float, plpd_threshold: float, keep_out: torch.Tensor,
+                    partial: torch.Tensor, loss: torch.Tensor, kept: torch.Tensor, kept_entropy: torch.Tensor,
+                    softmax: bool = False) -> None:
+    """DeYO's objective of every batch item on its own: elements with H < margin (``kept_entropy`` of them) whose pseudo-label
+    probability drops by more than ``plpd_threshold`` from ``logits`` to ``logits_shuffled`` read through the patch
+    permutation (``kept`` of them) enter the loss with the weight a = exp(margin0 - H) + exp(PLPD) (no gradient through a).
+    keep_out: uint8, one byte per element (N*D*H*W*R, or N*D*H*W for softmax heads); loss fp32 [N] = sum a H / kept; kept,
+    kept_entropy int64 [N]; dlogits = keep * a * dH/dz / kept; ``table`` as for ``patch_shuffle``."""
+    n, d, h, w, r = logits.shape
+    elems = n * d * h * w * (1 if softmax else r)
+    garr = _patch_grid(grid)
+    _check_patch_table("deyo_loss_items", table, n, grid)
+    if keep_out.dtype != torch.uint8 or not keep_out.is_contiguous() or keep_out.numel() < elems:
+        raise MmttaError(f"deyo_loss_items: keep_out must be contiguous uint8 of at least {elems} elements")
+    if loss.numel() < n or kept.numel() < n or kept.dtype != torch.int64 or kept_entropy.numel() < n or \
+            kept_entropy.dtype != torch.int64:
+        raise MmttaError("deyo_loss_items: one loss slot and two int64 counts per batch item")
+    if partial.dtype != torch.float64 or partial.numel() < deyo_partials(logits):
+        raise MmttaError("deyo_loss_items: partial must be fp64 of deyo_partials(logits) elements")
+    tz, ts, tg = desc_cl(logits), desc_cl(logits_shuffled), desc_cl(dlogits)
+    check(_lib.load().mmtta_deyo_loss_items(C.byref(tz), C.byref(ts), garr, ptr(table), 1 if softmax else 0, float(margin),
+                                            float(margin0), float(plpd_threshold), ptr(keep_out), C.byref(tg), ptr(partial),
+                                            ptr(loss), ptr(kept), ptr(kept_entropy), stream_ptr()), "deyo_loss_items")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 
