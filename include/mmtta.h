@@ -165,6 +165,9 @@ int mmtta_abi_version(void);
  * Measured (profiles/igemm64_reuse_ab.md, same machine, parent against change): 132.6 -> 111.9 us per launch of a group
  * of 8; volumes/s +1.6 % in one alternated series (outside its run-to-run spread), +0.8 % in a second (inside it). */
 #define MMTTA_OPT_IGEMM_FRAGMENT_REUSE 14
+/* Measurement aid of mmtta_lame_refine: 1 (default) calls that qualify for the tiled kernel take it; 0: every call runs the
+ * generic kernel (how profiles/lame_kernels.md compares the two on one input).  Equal within fp32 summation order. */
+#define MMTTA_OPT_LAME_TILED 15
 int mmtta_set_option(int key, int value);
 
 /* ------------------------------------------------------------------ layout (boundary) ---- */
@@ -772,6 +775,39 @@ int mmtta_deyo_loss_items(const mmtta_tensor* logits, const mmtta_tensor* logits
                           const int32_t* table, int softmax, float margin, float margin0, float plpd_threshold,
                           uint8_t* keep_out, const mmtta_tensor* dlogits, double* partial, float* loss, int64_t* kept,
                           int64_t* kept_entropy, void* stream);
+
+/* ------------------------------------------------------------------ LAME ----------------- */
+/* LAME (Boudiaf et al., CVPR 2022, "Parameter-free Online Test-time Adaptation") - csrc/lame.hip.  The weights stay as they
+ * are; the OUTPUTS are corrected: posteriors that stay close to the model's own (a KL term) while spatial neighbours with
+ * similar inputs agree (a Laplacian term).  The paper's concave-convex iteration z_i <- q_i (.) exp(weight sum_j w_ij z_j),
+ * renormalised, runs in logit space (elements as everywhere: sigmoid head (voxel, region) pairs, softmax head voxels):
+ *     sigmoid head   l_i(t+1)   = l0_i   + weight * sum_j w_ij tanh(l_j(t) / 2)          every region on its own
+ *     softmax head   l_ik(t+1)  = l0_ik  + weight * sum_j w_ij softmax(l_j(t))_k         no re-centring
+ *   l(0) = l0 = `logits0`; `iterations` synchronous (Jacobi) iterations, ping-pong between `work` and `out`, one launch each
+ *   (+ one memset node that clears `flipped`), all queued on `stream` without synchronisation.  The result is in `out`
+ *   whatever the parity of `iterations`; `logits0` is never written; the three buffers are pairwise distinct.
+ *   j: the 6 / 18 / 26 (`connectivity`) spatial neighbours of voxel i inside the same batch item; a neighbour outside the
+ *   volume contributes nothing.  w_ij = a_ij / n with n = connectivity (a constant: w stays symmetric and sum_j w_ij <= 1, so
+ *   `weight` is the largest logit shift of one iteration).
+ *   a_ij = exp(-sum_{c present} (x_ic - x_jc)^2 / (2 sigma^2)) on the staged input `x` [N,D,H,W,C] (fp32 or bf16 as staged,
+ *   converted to fp32; differences and sum in fp32); bit c of `channel_mask` marks channel c present.  sigma == 0: a_ij = 1,
+ *   `x` is not read (it may be null) and the mask is ignored.
+ *   flipped int64 [N]: per item the elements whose hard prediction changed - sigmoid head 1[l(T) >= 0] != 1[l0 >= 0],
+ *   softmax head a different FIRST arg max.  Integer block sums and one atomic per workgroup: the same in every run.
+ *   N items in one call equal N calls bit for bit.
+ * `logits0`, `work`, `out`: channels-last fp32 [N,D,H,W,R] of one shape and row width.  Two routes:
+ *   tiled    R <= 4, C <= 4, dense 16-byte logit rows (and dense 4-element rows of `x`): a workgroup stages a 4 x 8 x 32 tile
+ *            of y = tanh(l / 2) (or the softmax row) and of x with a one-voxel halo in LDS and computes the affinities on the
+ *            fly.  Rows of `out` / `work` are one 16-byte store - pad lanes written as 0 - when R == 4 or the view is
+ *            MMTTA_TENSOR_OWNS_PAD; else R 4-byte stores, pad lanes left as they are.
+ *   generic  everything else up to R <= 16 and C <= 16: one thread per voxel from global memory; pad lanes left as they are.
+ * MMTTA_ERR_INVALID before anything is launched: null pointers, shape or row-width mismatches, aliased buffers, a
+ * connectivity other than 6 / 18 / 26, iterations outside 1 .. 64, a weight that is not finite and in (0, 16], a sigma that
+ * is negative or not finite, sigma > 0 with no bit of channel_mask among the C channels.  R > 16 or C > 16, storages without
+ * a kernel and items of 2^31 elements or more are MMTTA_ERR_UNSUPPORTED. */
+int mmtta_lame_refine(const mmtta_tensor* logits0, const mmtta_tensor* x, uint32_t channel_mask, int softmax, int connectivity,
+                      float weight, float sigma, int iterations, const mmtta_tensor* work, const mmtta_tensor* out,
+                      int64_t* flipped, void* stream);
 
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:

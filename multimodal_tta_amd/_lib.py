@@ -201,6 +201,8 @@ _SIGNATURES = {
     "mmtta_deyo_loss_items": (C.c_int, [_P(Tensor), _P(Tensor), _P(C.c_int32), C.c_void_p, C.c_int, C.c_float, C.c_float,
                                         C.c_float, C.c_void_p, _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
+    "mmtta_lame_refine": (C.c_int, [_P(Tensor), _P(Tensor), C.c_uint32, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
+                                    _P(Tensor), _P(Tensor), C.c_void_p, C.c_void_p]),
     "mmtta_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mmtta_optim_step": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,

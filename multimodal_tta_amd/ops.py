@@ -1120,6 +1120,34 @@ def deyo_loss_items(logits: torch.Tensor, logits_shuffled: torch.Tensor, dlogits
                                             ptr(loss), ptr(kept), ptr(kept_entropy), stream_ptr()), "deyo_loss_items")
 
 
+def lame_refine(logits0: torch.Tensor, x: Optional[torch.Tensor], out: torch.Tensor, work: torch.Tensor, flipped: torch.Tensor, *,
+                connectivity: int, weight: float, sigma: float, iterations: int, present: Optional[Sequence[bool]] = None,
+                softmax: bool = False) -> None:
+    """LAME's output refinement (include/mmtta.h, mmtta_lame_refine): ``iterations`` Jacobi iterations of
+    l <- logits0 + weight * sum_j w_ij y(l_j) over the ``connectivity`` spatial neighbours, y = tanh(l / 2) (or the softmax
+    row), w_ij = exp(-|x_i - x_j|^2 / (2 sigma^2)) / connectivity on the channels of the staged input ``x`` that ``present``
+    marks (default: all; ``sigma`` 0: w_ij = 1 / connectivity and ``x`` may be None).  The result lands in ``out``; ``work``
+    is the second ping-pong buffer; ``flipped`` int64 [N] counts the elements whose hard prediction changed.  Channels-last
+    fp32 [N,D,H,W,R] logits of one shape and row width, three distinct buffers."""
+    n = int(logits0.shape[0])
+    if flipped.dtype != torch.int64 or not flipped.is_cuda or not flipped.is_contiguous() or flipped.numel() < n:
+        raise MmttaError(f"lame_refine: flipped must be contiguous device int64 of at least {n} elements (one per batch item)")
+    mask = 0xFFFFFFFF
+    if present is not None:
+        if x is not None and len(present) != int(x.shape[-1]):
+            raise MmttaError(f"lame_refine: present has {len(present)} entries for the {int(x.shape[-1])} channels of x")
+        if len(present) > 32:
+            raise MmttaError("lame_refine: at most 32 channels in the mask")
+        mask = sum(1 << c for c, p in enumerate(present) if p)
+    if float(sigma) > 0.0 and x is None:
+        raise MmttaError("lame_refine: sigma > 0 needs the staged input x")
+    t0, tw, to = desc_cl(logits0), desc_cl(work), desc_cl(out)
+    tx = desc_cl(x) if (x is not None and float(sigma) > 0.0) else None
+    check(_lib.load().mmtta_lame_refine(C.byref(t0), None if tx is None else C.byref(tx), mask, 1 if softmax else 0,
+                                        int(connectivity), float(weight), float(sigma), int(iterations), C.byref(tw),
+                                        C.byref(to), ptr(flipped), stream_ptr()), "lame_refine")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 
