@@ -529,51 +529,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-// ------------------------------------------------------------------ entropy objectives: what their kernels share
-// (loss_optim_metric.hip: entropy, filtered entropy; eata.hip: weighted entropy.  One definition, so that the filtered and
-// the weighted kernels decide keep = H < margin with the same instructions.)
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  return t;  // valid on thread 0
-}
-
-// One (voxel, region) of the Bernoulli entropy on the <= 4-region fast path: h = H(sigmoid(t)), g = dH/dt.  v_exp_f32,
-// v_rcp_f32, v_log_f32 and a 4-term series of log1p below 2^-6 (the account: entropy_bernoulli_vec_kernel).
-__device__ __forceinline__ void bernoulli_entropy_terms(float t, float& h, float& g) {
-  const float a = fabsf(t);
-  const float e = __builtin_amdgcn_exp2f(-a * 1.4426950408889634f);          // exp(-|t|)
-  const float r = __builtin_amdgcn_rcpf(1.f + e);
-  const float sig = t >= 0.f ? r : e * r;
-  const float series = e * fmaf(e, fmaf(e, fmaf(e, -0.25f, 0.33333334f), -0.5f), 1.f);
-  const float lg = __builtin_amdgcn_logf(1.f + e) * 0.6931471805599453f;     // v_log_f32 is log2
-  const float l1p = e < 0.015625f ? series : lg;
-  h = fmaxf(t, 0.f) + l1p - t * sig;
-  g = -t * (e * r * r);            // sig (1 - sig) = sig(|t|) (1 - sig(|t|)) = r * (e r): even in t
-}
-
-// Pass 1 of a filtered objective: fp64 block partials of the kept sum and of the kept count, partial[item][0 / 1][block].
-__device__ __forceinline__ void fent_store_partials(double acc, int cnt, double* partial, double* sh) {
-  const double s = block_sum_d(acc, sh);
-  __syncthreads();
-  const double c = block_sum_d((double)cnt, sh);
-  if (threadIdx.x == 0) {
-    double* p = partial + (long long)blockIdx.y * 2 * gridDim.x;
-    p[blockIdx.x] = s;
-    p[gridDim.x + blockIdx.x] = c;
-  }
-}
-
-__device__ __forceinline__ float fent_scale(const long long* kept) {
-  const long long k = kept[blockIdx.y];
-  return k > 0 ? (float)(1.0 / (double)k) : 0.f;
-}
-
 // ------------------------------------------------------------------ optimizer arithmetic (one element)
 struct OptimArgs {
   float lr, beta1, beta2, eps, wd, momentum, dampening;

@@ -2,180 +2,51 @@
 // of the student against the teacher's soft target with its gradient, and the pass that follows the student's optimizer
 // step - the teacher's exponential moving average and the stochastic restore of the student - over every parameter set.
 // Both are single-pass HBM-bound streams.  See include/mmtta.h for the contract of the entry points.
-#include "common.h"
+#include "voxel_loss.h"
 
 namespace mmtta {
 
-constexpr int CONS_MAX_BLOCKS = 2048;      // block partials per item (the entropy objective's figure)
-constexpr int CONS_MAX_R = 16;             // classes of the categorical path
-constexpr int CONS_MAX_GRID_Y = 65535;     // gridDim.y carries the item
 constexpr float CONS_CLAMP = 87.33654f;    // -ln(smallest normal fp32): where mmtta_memo_ensemble holds its logit
 constexpr int COTTA_MAX_BLOCKS = 4096;     // workgroups per parameter set (optim_kernel's figure)
 
-__device__ __forceinline__ double cons_block_sum(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  return t;  // valid on thread 0
-}
-
-// One (voxel, region) of the Bernoulli consistency loss: h = -q log sigmoid(z) - (1 - q) log sigmoid(-z), g = sigmoid(z) - q
-// with q = sigmoid(t).  Both sigmoids are taken at the logit held inside +-CONS_CLAMP (the ensemble's own bound) by the
-// same instructions, so t == z gives g == 0 exactly; neither 1 - q nor 1 - sigmoid(z) is formed by subtraction.
-// log sigmoid(z) = min(z, 0) - log1p(exp(-|z|)) with the unclamped z in front: finite for every finite z.  v_exp_f32 /
-// v_rcp_f32 / v_log_f32 as the entropy fast path; log1p(e) is its 4-term series below 2^-6 and log(1 + e) above.
-__device__ __forceinline__ void cons_sigmoid(float t, float& p, float& q) {
-  const float e = __builtin_amdgcn_exp2f(-fabsf(t) * 1.4426950408889634f);   // exp(-|t|)
-  const float r = __builtin_amdgcn_rcpf(1.f + e);
-  const float er = e * r;
-  p = t >= 0.f ? r : er;
-  q = t >= 0.f ? er : r;
-}
-__device__ __forceinline__ void cons_bernoulli_terms(float z, float t, float& h, float& g) {
-  const float zc = fminf(fmaxf(z, -CONS_CLAMP), CONS_CLAMP), tc = fminf(fmaxf(t, -CONS_CLAMP), CONS_CLAMP);
-  float q, qn;
-  cons_sigmoid(tc, q, qn);
-  const float e = __builtin_amdgcn_exp2f(-fabsf(zc) * 1.4426950408889634f);
-  const float r = __builtin_amdgcn_rcpf(1.f + e);
-  const float p = zc >= 0.f ? r : e * r;
-  const float series = e * fmaf(e, fmaf(e, fmaf(e, -0.25f, 0.33333334f), -0.5f), 1.f);
-  const float lg = __builtin_amdgcn_logf(1.f + e) * 0.6931471805599453f;     // v_log_f32 is log2
-  const float l1p = e < 0.015625f ? series : lg;
-  const float lsp = fminf(z, 0.f) - l1p, lsn = fminf(-z, 0.f) - l1p;         // log sigmoid(z), log sigmoid(-z)
-  h = -fmaf(q, lsp, qn * lsn);
-  g = p - q;
-}
-
-// Fast path: <= 4 regions in dense 16-byte voxel rows.  A thread owns a voxel of item blockIdx.y: one 16-byte load of each
-// input, one 16- / 8-byte store (the gradient tensor owns its pad lane), no index arithmetic.  OBF: bf16-stored gradient.
-template <bool OBF>
-__global__ __launch_bounds__(256) void consistency_bernoulli_vec_kernel(const float* __restrict__ z, const float* __restrict__ t,
-                                                                        float* __restrict__ dz, long long zsn, long long tsn,
-                                                                        long long dzsn, int C, unsigned dhw, double* partial,
-                                                                        float inv_count) {
-  __shared__ double sh[4];
-  z += (long long)blockIdx.y * zsn;
-  t += (long long)blockIdx.y * tsn;
-  dz = OBF ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(dz) + (long long)blockIdx.y * dzsn)
-           : dz + (long long)blockIdx.y * dzsn;
-  partial += (long long)blockIdx.y * gridDim.x;
-  double acc = 0.0;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < dhw; i += gridDim.x * 256u) {
-    const float4 z4 = *reinterpret_cast<const float4*>(z + (long long)i * 4);
-    const float4 t4 = *reinterpret_cast<const float4*>(t + (long long)i * 4);
-    const float zs[4] = {z4.x, z4.y, z4.z, z4.w}, ts[4] = {t4.x, t4.y, t4.z, t4.w};
-    float g[4] = {0.f, 0.f, 0.f, 0.f};
-    float h = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c < C) {
-        float hc, gc;
-        cons_bernoulli_terms(zs[c], ts[c], hc, gc);
-        h += hc;
-        g[c] = gc * inv_count;
-      }
-    }
-    acc += (double)h;
-    st4_any(dz, (long long)i * 4, make_float4(g[0], g[1], g[2], g[3]), OBF);
-  }
-  const double s = cons_block_sum(acc, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-// Generic path: any R, any strides, fp32 gradients; a thread owns a (voxel, region) pair of item blockIdx.y.
-__global__ __launch_bounds__(256) void consistency_bernoulli_kernel(TV z, TV t, TV dz, double* partial, float inv_count) {
-  __shared__ double sh[4];
-  const int item = blockIdx.y;
-  partial += (long long)blockIdx.y * gridDim.x;
-  const unsigned C = z.c, H = z.h, W = z.w;
-  const unsigned total = (unsigned)z.d * H * W * C;
-  double acc = 0.0;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned vox = i / C, c = i - vox * C;
-    const unsigned row = vox / W, x = vox - row * W;
-    const unsigned zz = row / H, y = row - zz * H;
-    float h, g;
-    cons_bernoulli_terms(z.p[vox_addr(z, item, zz, y, x) + c], t.p[vox_addr(t, item, zz, y, x) + c], h, g);
-    acc += (double)h;
-    dz.p[vox_addr(dz, item, zz, y, x) + c] = g * inv_count;
-  }
-  const double s = cons_block_sum(acc, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
+// The plain walk of voxel_loss.h over the consistency arithmetic; the second operand is the teacher's target.
+// Bernoulli heads: h = -q log sigmoid(z) - (1 - q) log sigmoid(-z), g = sigmoid(z) - q with q = sigmoid(t).  Both sigmoids
+// are taken at the logit held inside +-CONS_CLAMP (the ensemble's own bound) by the same instructions (sigmoid_pair), so
+// t == z gives g == 0 exactly; neither 1 - q nor 1 - sigmoid(z) is formed by subtraction.  The clamp is this objective's
+// own: the entropy terms take their logit as it is.  log sigmoid(z) = min(z, 0) - log1p(exp(-|z|)) with the unclamped z
+// in front: finite for every finite z.
 // Categorical head: h = -sum_r exp(t_r) log softmax(z)_r, g_r = softmax(z)_r - exp(t_r); t = log pbar as
 // mmtta_memo_ensemble writes it (held at -3e38 from below, as that kernel holds its log softmax).  The log softmax is the
 // ensemble's own form - (z - max) - log(sum) - so that a target made from the same logits gives g == 0 exactly.
-__global__ __launch_bounds__(256) void consistency_categorical_kernel(TV z, TV t, TV dz, double* partial, float inv_count) {
-  __shared__ double sh[4];
-  const int item = blockIdx.y, R = z.c;
-  partial += (long long)blockIdx.y * gridDim.x;
-  const unsigned H = z.h, W = z.w;
-  const unsigned total = (unsigned)z.d * H * W;
-  double acc = 0.0;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned row = i / W, x = i - row * W;
-    const unsigned zz = row / H, y = row - zz * H;
-    const float* zp = z.p + vox_addr(z, item, zz, y, x);
-    const float* tp = t.p + vox_addr(t, item, zz, y, x);
-    float* gp = dz.p + vox_addr(dz, item, zz, y, x);
-    float lp[CONS_MAX_R];
-    float m = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < CONS_MAX_R; ++r)
-      if (r < R) { lp[r] = zp[r]; m = fmaxf(m, lp[r]); }
-    float se = 0.f;
-#pragma unroll
-    for (int r = 0; r < CONS_MAX_R; ++r)
-      if (r < R) se += expf(lp[r] - m);
-    const float lg = logf(se);             // se >= 1: the maximum contributes exp(0)
+struct ConsistencyLoss : SameVoxelOperand {
+  __device__ __forceinline__ void fast(float z, float t, float& h, float& g) const {
+    const float zc = fminf(fmaxf(z, -CONS_CLAMP), CONS_CLAMP), tc = fminf(fmaxf(t, -CONS_CLAMP), CONS_CLAMP);
+    const SigmoidPair q = sigmoid_pair(tc, exp_neg_abs(tc));
+    const float e = exp_neg_abs(zc);
+    const float p = sigmoid_pair(zc, e).p;
+    const float l1p = log1p_unit(e);
+    const float lsp = fminf(z, 0.f) - l1p, lsn = fminf(-z, 0.f) - l1p;         // log sigmoid(z), log sigmoid(-z)
+    h = -fmaf(q.p, lsp, q.q * lsn);
+    g = p - q.p;
+  }
+  __device__ __forceinline__ void generic(float z, float t, float& h, float& g) const { fast(z, t, h, g); }
+  template <class F>
+  __device__ __forceinline__ float categorical(const float* zp, const float* tp, int R, F&& put) const {
+    CategoricalVoxel v;
+    categorical_load(zp, R, v);
+    const float lg = logf(v.se);           // se >= 1: the maximum contributes exp(0)
     float h = 0.f;
 #pragma unroll
-    for (int r = 0; r < CONS_MAX_R; ++r)
+    for (int r = 0; r < LOSS_MAX_R; ++r)
       if (r < R) {
-        const float l = fmaxf((lp[r] - m) - lg, -3e38f);
+        const float l = fmaxf((v.t[r] - v.m) - lg, -3e38f);
         const float q = expf(fmaxf(tp[r], -3e38f));
         h = fmaf(-q, l, h);
-        gp[r] = (expf(l) - q) * inv_count;
+        put(r, expf(l) - q);
       }
-    acc += (double)h;
+    return h;
   }
-  const double s = cons_block_sum(acc, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-__global__ __launch_bounds__(64) void consistency_finish_kernel(const double* partial, int nblocks, double inv_count, float* loss) {
-  partial += (long long)blockIdx.x * nblocks;      // one workgroup per item
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 64) s += partial[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) loss[blockIdx.x] = (float)(s * inv_count);
-}
-
-static int cons_blocks(const mmtta_tensor* z) {
-  // the figure of mmtta_entropy_partials for ONE item, for every head (the kernels that give a thread a whole voxel get up
-  // to c times the workgroups they have voxels for below the cap; those write a zero partial)
-  const long long total = (long long)z->d * z->h * z->w * z->c;
-  long long b = (total + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > CONS_MAX_BLOCKS) b = CONS_MAX_BLOCKS;
-  return (int)b;
-}
-
-static bool cons_dense16(const mmtta_tensor* t) {
-  return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
-         ((uintptr_t)t->ptr) % 16 == 0;
-}
-
-// every offset inside one item fits 31 bits (the kernels index voxels with 32-bit arithmetic)
-static bool cons_small_item(const mmtta_tensor* t) {
-  const long long ld = t->sw > t->c ? t->sw : t->c;
-  return t->d > 0 && t->h > 0 && t->w > 0 && t->c > 0 && (long long)t->d * t->h * t->w * (ld > 4 ? ld : 4) < (1ll << 31);
-}
+};
 
 // ------------------------------------------------------------------ teacher EMA + stochastic restore
 // Philox4x32-10 (Salmon et al., SC 2011; the generator of Random123, curand and hiprand), written out.
@@ -271,7 +142,7 @@ using namespace mmtta;
 
 extern "C" int64_t mmtta_consistency_partials(const mmtta_tensor* logits) {
   if (logits == nullptr || logits->n < 1) return -1;
-  return (int64_t)cons_blocks(logits) * logits->n;
+  return (int64_t)loss_blocks(logits) * logits->n;
 }
 
 extern "C" int mmtta_consistency_loss_items(const mmtta_tensor* logits, const mmtta_tensor* target, int softmax,
@@ -285,42 +156,14 @@ extern "C" int mmtta_consistency_loss_items(const mmtta_tensor* logits, const mm
   MMTTA_CHECK(logits->dtype == MMTTA_F32 && target->dtype == MMTTA_F32, MMTTA_ERR_UNSUPPORTED,
               "consistency loss: `logits` and `target` must be fp32-stored");
   MMTTA_CHECK(is_cl(logits) && is_cl(target) && is_cl(dlogits), MMTTA_ERR_UNSUPPORTED, "consistency loss: channels-last only");
-  MMTTA_CHECK(cons_small_item(logits) && cons_small_item(target) && cons_small_item(dlogits), MMTTA_ERR_UNSUPPORTED,
+  MMTTA_CHECK(loss_small_item(logits) && loss_small_item(target) && loss_small_item(dlogits), MMTTA_ERR_UNSUPPORTED,
               "consistency loss: an item of 2^31 elements or more");
-  MMTTA_CHECK(logits->n <= CONS_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "consistency loss: more than %d items in one call", CONS_MAX_GRID_Y);
-  hipStream_t s = (hipStream_t)stream;
-  const int items = logits->n;
-  const int blocks = cons_blocks(logits);
-  const long long nvox = (long long)logits->d * logits->h * logits->w;
-  const dim3 grid(blocks, items);
-  const double cnt = softmax ? (double)nvox : (double)nvox * logits->c;
-  const float inv = (float)(1.0 / cnt);
-  int st;
-  if (!softmax) {
-    const bool vec = logits->c <= 4 && cons_dense16(logits) && cons_dense16(target) && cons_dense16(dlogits) &&
-                     ((dlogits->flags & MMTTA_TENSOR_OWNS_PAD) || dlogits->c == 4);
-    MMTTA_CHECK(is_f32(dlogits) || vec, MMTTA_ERR_UNSUPPORTED,
-                "consistency loss: a bf16-stored `dlogits` needs dense 4-channel voxel rows that own their pad");
-    if (vec && is_bf16(dlogits))
-      hipLaunchKernelGGL(consistency_bernoulli_vec_kernel<true>, grid, dim3(256), 0, s, (const float*)logits->ptr,
-                         (const float*)target->ptr, (float*)dlogits->ptr, (long long)logits->sn, (long long)target->sn,
-                         (long long)dlogits->sn, (int)logits->c, (unsigned)nvox, partial, inv);
-    else if (vec)
-      hipLaunchKernelGGL(consistency_bernoulli_vec_kernel<false>, grid, dim3(256), 0, s, (const float*)logits->ptr,
-                         (const float*)target->ptr, (float*)dlogits->ptr, (long long)logits->sn, (long long)target->sn,
-                         (long long)dlogits->sn, (int)logits->c, (unsigned)nvox, partial, inv);
-    else
-      hipLaunchKernelGGL(consistency_bernoulli_kernel, grid, dim3(256), 0, s, tv(logits), tv(target), tv(dlogits), partial, inv);
-    st = launch_status("consistency bernoulli");
-  } else {
-    MMTTA_CHECK(logits->c <= CONS_MAX_R, MMTTA_ERR_UNSUPPORTED, "consistency loss softmax: more than %d classes", CONS_MAX_R);
-    MMTTA_CHECK(is_f32(dlogits), MMTTA_ERR_UNSUPPORTED, "consistency loss softmax: `dlogits` must be fp32-stored");
-    hipLaunchKernelGGL(consistency_categorical_kernel, grid, dim3(256), 0, s, tv(logits), tv(target), tv(dlogits), partial, inv);
-    st = launch_status("consistency categorical");
-  }
-  if (st) return st;
-  hipLaunchKernelGGL(consistency_finish_kernel, dim3(items), dim3(64), 0, s, partial, blocks, 1.0 / cnt, loss);
-  return launch_status("consistency finish");
+  MMTTA_CHECK(logits->n <= LOSS_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "consistency loss: more than %d items in one call", LOSS_MAX_GRID_Y);
+  ConsistencyLoss p;
+  p.t = tv(target);
+  return loss_launch<ConsistencyLoss, unsigned>({"consistency loss", "consistency loss", "consistency"}, logits, dlogits,
+                                                softmax, loss_vec(logits, dlogits, target), 1, partial, loss, p,
+                                                (hipStream_t)stream);
 }
 
 extern "C" int64_t mmtta_cotta_update_partials(int64_t n, int sets) {
@@ -334,7 +177,7 @@ extern "C" int mmtta_cotta_update_sets(float* w, float* teacher, const float* so
                                        void* stream) {
   MMTTA_CHECK(w && teacher && source && step && ordinals && partial && restored, MMTTA_ERR_INVALID, "cotta update: null argument");
   MMTTA_CHECK(n >= 0 && n <= (1ll << 34), MMTTA_ERR_INVALID, "cotta update: n = %lld (0 .. 2^34: the counter word is i >> 2)", (long long)n);
-  MMTTA_CHECK(sets >= 1 && sets <= CONS_MAX_GRID_Y, MMTTA_ERR_INVALID, "cotta update: sets = %d (1 .. %d)", sets, CONS_MAX_GRID_Y);
+  MMTTA_CHECK(sets >= 1 && sets <= LOSS_MAX_GRID_Y, MMTTA_ERR_INVALID, "cotta update: sets = %d (1 .. %d)", sets, LOSS_MAX_GRID_Y);
   MMTTA_CHECK(w_stride % 4 == 0 && teacher_stride % 4 == 0 && (sets == 1 || (w_stride >= n && teacher_stride >= n)),
               MMTTA_ERR_INVALID, "cotta update: %d sets with strides %lld / %lld (n = %lld; multiples of 4, >= n)", sets,
               (long long)w_stride, (long long)teacher_stride, (long long)n);

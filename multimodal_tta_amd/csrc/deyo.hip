@@ -2,13 +2,10 @@
 // staged volume and the reliable entropy that is filtered and weighted by the pseudo-label probability difference (PLPD)
 // between the logits of the volume and the logits of its shuffled copy.  Both are HBM-bound streams.  See include/mmtta.h
 // for the contracts.
-#include "common.h"
+#include "voxel_loss.h"
 
 namespace mmtta {
 
-constexpr int DEYO_MAX_BLOCKS = 2048;      // block partials per item (the entropy objective's figure)
-constexpr int DEYO_MAX_R = 16;             // classes of the categorical path
-constexpr int DEYO_MAX_GRID_Y = 65535;     // gridDim.y carries the item
 constexpr int DEYO_MAX_PATCHES = 4096;     // 16 x 16 x 16
 
 // The patch grid of one call: g* patches per axis of p* voxels each, P = gd * gh * gw slots in row-major order.
@@ -55,276 +52,87 @@ __global__ __launch_bounds__(256) void deyo_shuffle_kernel(const T* __restrict__
 }
 
 // ------------------------------------------------------------------ PLPD-weighted reliable entropy
-// The launch geometry, the mask layout and the entropy arithmetic of mmtta_entropy_weighted_items (eata.hip), hence of
-// mmtta_entropy_filtered_items: keep1 = H < margin and its count come out bit for bit as that entry point's.  z'' is read from
-// the shuffled logits at the mapped voxel (the inverse row of the table).  Pass 1 leaves the keep bytes and fp64 block
-// partials of the kept sum of a H, of |keep| and of |keep1|; pass 2 writes dlogits = keep * a * dH/dz / kept[item].
-
-// sigmoid(|t|) with the instructions of bernoulli_entropy_terms (the compiler shares them)
-__device__ __forceinline__ float deyo_sigmoid_abs(float t) {
-  const float e = __builtin_amdgcn_exp2f(-fabsf(t) * 1.4426950408889634f);
-  return __builtin_amdgcn_rcpf(1.f + e);
-}
-// sigmoid(u), without a subtraction
-__device__ __forceinline__ float deyo_sigmoid(float u) {
-  const float e = __builtin_amdgcn_exp2f(-fabsf(u) * 1.4426950408889634f);
-  const float r = __builtin_amdgcn_rcpf(1.f + e);
-  return u >= 0.f ? r : e * r;
-}
-
-// Pass 1: fp64 block partials partial[item][0 / 1 / 2][block] = kept sum, |keep|, |keep1|.
-__device__ __forceinline__ void deyo_store_partials(double acc, int cnt, int cnt1, double* partial, double* sh) {
-  const double s = block_sum_d(acc, sh);
-  __syncthreads();
-  const double c = block_sum_d((double)cnt, sh);
-  __syncthreads();
-  const double c1 = block_sum_d((double)cnt1, sh);
-  if (threadIdx.x == 0) {
-    double* p = partial + (long long)blockIdx.y * 3 * gridDim.x;
-    p[blockIdx.x] = s;
-    p[gridDim.x + blockIdx.x] = c;
-    p[2 * gridDim.x + blockIdx.x] = c1;
-  }
-}
-
-struct DeyoArgs {
+// The filtered walk of voxel_loss.h with three partial rows, hence the launch geometry and the mask layout of
+// mmtta_entropy_weighted_items (eata.hip) and of mmtta_entropy_filtered_items, over the same entropy definitions: keep1 =
+// H < margin and its count are those entry points'.  The second operand z'' is read from the shuffled logits at the mapped
+// voxel (the inverse row of the table).  Pass 1 leaves the keep bytes and fp64 block partials of the kept sum of a H, of
+// |keep| and of |keep1|; pass 2 writes dlogits = keep * a * dH/dz / kept[item].
+struct DeyoLoss {
+  static constexpr int ROWS = 3;
   float margin, margin0, threshold;
-};
-
-__global__ __launch_bounds__(256) void deyo_bernoulli_kernel(TV z, TV zs, TV dz, DeyoGrid pg, const int* __restrict__ table,
-                                                             DeyoArgs a, unsigned char* kout, double* partial,
-                                                             const long long* kept) {
-  __shared__ double sh[4];
-  const unsigned C = z.c, H = z.h, W = z.w;
-  const unsigned total = (unsigned)z.d * H * W * C;
-  const int* inv = table + ((long long)blockIdx.y * 2 + 1) * pg.P;
-  z.p += (long long)blockIdx.y * z.sn;
-  zs.p += (long long)blockIdx.y * zs.sn;
-  kout += (long long)blockIdx.y * total;
-  const bool grad = kept != nullptr;      // pass 2: kout is the mask pass 1 wrote
-  if (grad) dz.p += (long long)blockIdx.y * dz.sn;
-  const float scale = grad ? fent_scale(kept) : 0.f;
-  double acc = 0.0;
-  int cnt = 0, cnt1 = 0;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned vox = i / C, c = i - vox * C;
-    const unsigned r = vox / W, x = vox - r * W;
-    const unsigned zz = r / H, y = r - zz * H;
-    unsigned iz, iy, ix;
-    deyo_image(pg, inv, zz, y, x, iz, iy, ix);
-    const float t = z.p[zz * z.sd + y * z.sh + x * z.sw + c];
-    const float ts = zs.p[iz * zs.sd + iy * zs.sh + ix * zs.sw + c];
-    const float e = expf(-fabsf(t));
-    const float sig = t >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    const float softplus = fmaxf(t, 0.f) + log1pf(e);
-    const float h = softplus - t * sig;
-    const float u = t >= 0.f ? ts : -ts;
-    const float eu = expf(-fabsf(u));
-    const float plpd = 1.f / (1.f + e) - (u >= 0.f ? 1.f / (1.f + eu) : eu / (1.f + eu));
-    const float wgt = expf(a.margin0 - fminf(h, a.margin)) + expf(plpd);
-    if (grad) {
-      dz.p[zz * dz.sd + y * dz.sh + x * dz.sw + c] = kout[i] ? wgt * (-t * sig * (1.f - sig)) * scale : 0.f;
-      continue;
-    }
-    const bool keep1 = h < a.margin;
-    const bool keep = keep1 && plpd > a.threshold;
-    kout[i] = keep ? 1 : 0;
-    cnt1 += keep1 ? 1 : 0;
-    if (keep) { acc += (double)(wgt * h); ++cnt; }
+  TV zs;
+  DeyoGrid pg;
+  const int* inv;      // the call's table; item() moves it to the item's inverse row
+  __device__ __forceinline__ void item(int n, long long) {
+    zs.p += (long long)n * zs.sn;
+    inv += ((long long)n * 2 + 1) * pg.P;
   }
-  if (!grad) deyo_store_partials(acc, cnt, cnt1, partial, sh);
-}
-
-// Fast path: <= 4 regions in dense 16-byte voxel rows of both logit tensors; a thread owns a voxel and reads one more row,
-// the one of the mapped voxel.  OBF: bf16-stored gradient.
-template <bool OBF>
-__global__ __launch_bounds__(256) void deyo_bernoulli_vec_kernel(TV z, TV zs, TV dz, DeyoGrid pg, const int* __restrict__ table,
-                                                                 DeyoArgs a, unsigned char* kout, double* partial,
-                                                                 const long long* kept) {
-  __shared__ double sh[4];
-  const int C = z.c;
-  const unsigned H = z.h, W = z.w;
-  const unsigned total = (unsigned)z.d * H * W;
-  const int* inv = table + ((long long)blockIdx.y * 2 + 1) * pg.P;
-  z.p += (long long)blockIdx.y * z.sn;
-  zs.p += (long long)blockIdx.y * zs.sn;
-  kout += (long long)blockIdx.y * total * C;
-  const bool grad = kept != nullptr;
-  if (grad)
-    dz.p = OBF ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(dz.p) + (long long)blockIdx.y * dz.sn)
-               : dz.p + (long long)blockIdx.y * dz.sn;
-  const float scale = grad ? fent_scale(kept) : 0.f;
-  double acc = 0.0;
-  int cnt = 0, cnt1 = 0;
-  for (unsigned v = blockIdx.x * 256u + threadIdx.x; v < total; v += gridDim.x * 256u) {
+  __device__ __forceinline__ bool allowed(long long) const { return true; }
+  __device__ __forceinline__ long long mapped(unsigned z, unsigned y, unsigned x) const {
+    unsigned iz, iy, ix;
+    deyo_image(pg, inv, z, y, x, iz, iy, ix);
+    return iz * zs.sd + iy * zs.sh + ix * zs.sw;
+  }
+  // dense rows: one more 16-byte load, the row of the mapped voxel
+  __device__ __forceinline__ float4 row(unsigned v) const {
+    const unsigned H = zs.h, W = zs.w;
     const unsigned r = v / W, x = v - r * W;
     const unsigned zz = r / H, y = r - zz * H;
     unsigned iz, iy, ix;
     deyo_image(pg, inv, zz, y, x, iz, iy, ix);
     const unsigned vs = (iz * H + iy) * W + ix;
-    const float4 t4 = *reinterpret_cast<const float4*>(z.p + (long long)v * 4);
-    const float4 s4 = *reinterpret_cast<const float4*>(zs.p + (long long)vs * 4);
-    const float ts[4] = {t4.x, t4.y, t4.z, t4.w};
-    const float ss[4] = {s4.x, s4.y, s4.z, s4.w};
-    unsigned char km[4] = {0, 0, 0, 0};
-    if (grad) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < C) km[c] = kout[(long long)v * C + c];
-    }
-    float g[4] = {0.f, 0.f, 0.f, 0.f};
-    float h = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c < C) {
-        float hc, gc;
-        bernoulli_entropy_terms(ts[c], hc, gc);
-        const float plpd = deyo_sigmoid_abs(ts[c]) - deyo_sigmoid(ts[c] >= 0.f ? ss[c] : -ss[c]);
-        const float wgt = __builtin_amdgcn_exp2f((a.margin0 - fminf(hc, a.margin)) * 1.4426950408889634f) +
-                          __builtin_amdgcn_exp2f(plpd * 1.4426950408889634f);
-        if (grad) {
-          g[c] = km[c] ? wgt * gc * scale : 0.f;
-        } else {
-          const bool keep1 = hc < a.margin;
-          const bool keep = keep1 && plpd > a.threshold;
-          km[c] = keep ? 1 : 0;
-          cnt1 += keep1 ? 1 : 0;
-          if (keep) { h += wgt * hc; ++cnt; }
-        }
-      }
-    }
-    if (grad) {
-      st4_any(dz.p, (long long)v * 4, make_float4(g[0], g[1], g[2], g[3]), OBF);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < C) kout[(long long)v * C + c] = km[c];
-      acc += (double)h;
-    }
+    return *reinterpret_cast<const float4*>(zs.p + (long long)vs * 4);
   }
-  if (!grad) deyo_store_partials(acc, cnt, cnt1, partial, sh);
-}
+  __device__ __forceinline__ float at(const VoxPos& p, int c) const { return zs.p[mapped(p.z, p.y, p.x) + c]; }
+  __device__ __forceinline__ const float* vox(const VoxPos& p) const { return zs.p + mapped(p.z, p.y, p.x); }
 
-// Categorical head: the element is the voxel, y^ the FIRST arg max of z, PLPD = softmax(z)[y^] - softmax(z'')[y^].
-__global__ __launch_bounds__(256) void deyo_categorical_kernel(TV z, TV zs, TV dz, DeyoGrid pg, const int* __restrict__ table,
-                                                               DeyoArgs a, unsigned char* kout, double* partial,
-                                                               const long long* kept) {
-  __shared__ double sh[4];
-  const int R = z.c;
-  const unsigned H = z.h, W = z.w;
-  const unsigned total = (unsigned)z.d * H * W;
-  const int* inv = table + ((long long)blockIdx.y * 2 + 1) * pg.P;
-  z.p += (long long)blockIdx.y * z.sn;
-  zs.p += (long long)blockIdx.y * zs.sn;
-  kout += (long long)blockIdx.y * total;
-  const bool grad = kept != nullptr;
-  if (grad) dz.p += (long long)blockIdx.y * dz.sn;
-  const float scale = grad ? fent_scale(kept) : 0.f;
-  double acc = 0.0;
-  int cnt = 0, cnt1 = 0;
-  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const unsigned rr = i / W, x = i - rr * W;
-    const unsigned zz = rr / H, y = rr - zz * H;
-    unsigned iz, iy, ix;
-    deyo_image(pg, inv, zz, y, x, iz, iy, ix);
-    const float* zp = z.p + zz * z.sd + y * z.sh + x * z.sw;
-    const float* sp = zs.p + iz * zs.sd + iy * zs.sh + ix * zs.sw;
-    float t[DEYO_MAX_R], s[DEYO_MAX_R];
-    float m = -INFINITY, ms = -INFINITY;
-    int arg = 0;
+  __device__ __forceinline__ KeptTerms fast(float t, float s) const {
+    float h, g;
+    bernoulli_entropy_terms(t, h, g);
+    const float u = t >= 0.f ? s : -s;
+    const float plpd = sigmoid_pair(t, exp_neg_abs(t)).r - sigmoid_pair(u, exp_neg_abs(u)).p;      // sigmoid(|t|) - sigmoid(u)
+    const float wgt = exp_fast(margin0 - fminf(h, margin)) + exp_fast(plpd);
+    return {h, wgt * h, wgt * g, plpd > threshold};
+  }
+  __device__ __forceinline__ KeptTerms generic(float t, float s) const {
+    const BernoulliLibm b = bernoulli_entropy_libm(t);
+    const float u = t >= 0.f ? s : -s;
+    const float eu = expf(-fabsf(u));
+    const float plpd = 1.f / (1.f + b.e) - (u >= 0.f ? 1.f / (1.f + eu) : eu / (1.f + eu));
+    const float wgt = expf(margin0 - fminf(b.h, margin)) + expf(plpd);
+    return {b.h, wgt * b.h, wgt * b.g, plpd > threshold};
+  }
+  // Categorical head: the element is the voxel, y^ the FIRST arg max of z, PLPD = softmax(z)[y^] - softmax(z'')[y^].
+  template <class F>
+  __device__ __forceinline__ KeptTerms categorical(const float* zp, const float* sp, int R, F&& put) const {
+    CategoricalVoxel v;
+    categorical_entropy<true>(zp, R, v);
+    const int arg = categorical_argmax(v, R);
+    float s[LOSS_MAX_R];
+    float ms = -INFINITY;
 #pragma unroll
-    for (int r = 0; r < DEYO_MAX_R; ++r)
-      if (r < R) {
-        t[r] = zp[r];
-        s[r] = sp[r];
-        arg = t[r] > m ? r : arg;
-        m = fmaxf(m, t[r]);
-        ms = fmaxf(ms, s[r]);
-      }
-    float se = 0.f, ses = 0.f, sarg = 0.f;
+    for (int r = 0; r < LOSS_MAX_R; ++r)
+      if (r < R) { s[r] = sp[r]; ms = fmaxf(ms, s[r]); }
+    float ses = 0.f, sarg = 0.f;
 #pragma unroll
-    for (int r = 0; r < DEYO_MAX_R; ++r)
+    for (int r = 0; r < LOSS_MAX_R; ++r)
       if (r < R) {
-        se += expf(t[r] - m);
         const float es = expf(s[r] - ms);
         ses += es;
         sarg = r == arg ? es : sarg;
       }
-    const float lse = m + logf(se);
-    float pz = 0.f;
+    const float plpd = 1.f / v.se - sarg / ses;      // softmax(z)[y^] = exp(0) / se
+    const float wgt = expf(margin0 - fminf(v.Hs, margin)) + expf(plpd);
 #pragma unroll
-    for (int r = 0; r < DEYO_MAX_R; ++r)
-      if (r < R) pz += expf(t[r] - lse) * t[r];
-    const float Hf = lse - pz;             // the filtered kernel's H: it decides keep1, bit for bit
-    // loss, weight and gradient use H in the shifted form, as mmtta_entropy_weighted_items does (eata.hip has the account)
-    const float lgs = logf(se);
-    float pu = 0.f;
-#pragma unroll
-    for (int r = 0; r < DEYO_MAX_R; ++r)
-      if (r < R) {
-        const float u = t[r] - m;
-        pu += expf(u - lgs) * u;
-      }
-    const float Hs = lgs - pu;
-    const float plpd = 1.f / se - sarg / ses;      // softmax(z)[y^] = exp(0) / se
-    const float wgt = expf(a.margin0 - fminf(Hs, a.margin)) + expf(plpd);
-    if (grad) {
-      float* gp = dz.p + zz * dz.sd + y * dz.sh + x * dz.sw;
-      const bool keep = kout[i] != 0;
-#pragma unroll
-      for (int r = 0; r < DEYO_MAX_R; ++r)
-        if (r < R) {
-          const float logp = (t[r] - m) - lgs;
-          gp[r] = keep ? wgt * (-expf(logp) * (logp + Hs)) * scale : 0.f;
-        }
-      continue;
-    }
-    const bool keep1 = Hf < a.margin;
-    const bool keep = keep1 && plpd > a.threshold;
-    kout[i] = keep ? 1 : 0;
-    cnt1 += keep1 ? 1 : 0;
-    if (keep) { acc += (double)(wgt * Hs); ++cnt; }
+    for (int r = 0; r < LOSS_MAX_R; ++r)
+      if (r < R) put(r, wgt * categorical_entropy_grad<true>(v, r));
+    return {v.H, wgt * v.Hs, 0.f, plpd > threshold};
   }
-  if (!grad) deyo_store_partials(acc, cnt, cnt1, partial, sh);
-}
+};
 
-__global__ __launch_bounds__(64) void deyo_finish_kernel(const double* partial, int nblocks, float* loss, long long* kept,
-                                                         long long* kept_entropy) {
-  partial += (long long)blockIdx.x * 3 * nblocks;      // one workgroup per item
-  double s = 0.0, c = 0.0, c1 = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 64) {
-    s += partial[i];
-    c += partial[nblocks + i];
-    c1 += partial[2 * nblocks + i];
-  }
-  s = wave_sum_d(s);
-  c = wave_sum_d(c);
-  c1 = wave_sum_d(c1);
-  if (threadIdx.x == 0) {
-    kept[blockIdx.x] = (long long)c;
-    kept_entropy[blockIdx.x] = (long long)c1;
-    loss[blockIdx.x] = c > 0.0 ? (float)(s * (1.0 / c)) : __builtin_nanf("");
-  }
-}
-
-static int deyo_blocks(const mmtta_tensor* z) {      // mmtta_entropy_filtered_partials' figure for ONE item
-  const long long total = (long long)z->d * z->h * z->w * z->c;
-  long long b = (total + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > DEYO_MAX_BLOCKS) b = DEYO_MAX_BLOCKS;
-  return (int)b;
-}
-
-static bool deyo_dense16(const mmtta_tensor* t) {
-  return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
-         ((uintptr_t)t->ptr) % 16 == 0;
-}
-
-// every offset inside one item fits 31 bits (the kernels index voxels with 32-bit arithmetic)
+// every offset inside one item fits 31 bits, the last voxel's included (the patch map reaches any voxel of the item)
 static bool deyo_small_item(const mmtta_tensor* t) {
-  const long long ld = t->sw > t->c ? t->sw : t->c;
-  return t->d > 0 && t->h > 0 && t->w > 0 && t->c > 0 && (long long)t->d * t->h * t->w * (ld > 4 ? ld : 4) < (1ll << 31) &&
-         item_fits_31(t, ld);
+  return loss_small_item(t) && item_fits_31(t, t->sw > t->c ? t->sw : t->c);
 }
 
 // The patch grid of a call against the extents of `t`: counts >= 1 that divide them, 2 <= P <= DEYO_MAX_PATCHES.
@@ -367,7 +175,7 @@ extern "C" int mmtta_patch_shuffle(const mmtta_tensor* x, const mmtta_tensor* y,
   MMTTA_CHECK(y->sw == y->c || (y->flags & MMTTA_TENSOR_OWNS_PAD), MMTTA_ERR_UNSUPPORTED,
               "patch shuffle: `y` must own the pad lanes of its rows");
   MMTTA_CHECK(deyo_small_item(x), MMTTA_ERR_UNSUPPORTED, "patch shuffle: an item of 2^31 elements or more");
-  MMTTA_CHECK(x->n <= DEYO_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "patch shuffle: more than %d items in one call", DEYO_MAX_GRID_Y);
+  MMTTA_CHECK(x->n <= LOSS_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "patch shuffle: more than %d items in one call", LOSS_MAX_GRID_Y);
   const long long esz = x->dtype == MMTTA_BF16 ? 2 : 4;
   {
     // a patch of the output is read from another patch of the input: the two may not share memory
@@ -400,7 +208,7 @@ extern "C" int mmtta_patch_shuffle(const mmtta_tensor* x, const mmtta_tensor* y,
 
 extern "C" int64_t mmtta_deyo_partials(const mmtta_tensor* logits) {
   if (logits == nullptr || logits->n < 1) return -1;
-  return 3 * (int64_t)deyo_blocks(logits) * logits->n;
+  return 3 * (int64_t)loss_blocks(logits) * logits->n;
 }
 
 extern "C" int mmtta_deyo_loss_items(const mmtta_tensor* logits, const mmtta_tensor* logits_shuffled, const int32_t* grid,
@@ -428,51 +236,9 @@ extern "C" int mmtta_deyo_loss_items(const mmtta_tensor* logits, const mmtta_ten
   MMTTA_CHECK(is_cl(logits) && is_cl(logits_shuffled) && is_cl(dlogits), MMTTA_ERR_UNSUPPORTED, "deyo loss: channels-last only");
   MMTTA_CHECK(deyo_small_item(logits) && deyo_small_item(logits_shuffled) && deyo_small_item(dlogits), MMTTA_ERR_UNSUPPORTED,
               "deyo loss: an item of 2^31 elements or more");
-  MMTTA_CHECK(logits->n <= DEYO_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "deyo loss: more than %d items in one call", DEYO_MAX_GRID_Y);
-  hipStream_t s = (hipStream_t)stream;
-  const int items = logits->n;
-  const int blocks = deyo_blocks(logits);
-  const dim3 launch(blocks, items);
-  const long long* kd = (const long long*)kept;
-  const int* tb = (const int*)table;
-  const DeyoArgs a = {margin, margin0, plpd_threshold};
-  if (!softmax) {
-    const bool vec = logits->c <= 4 && deyo_dense16(logits) && deyo_dense16(logits_shuffled) && deyo_dense16(dlogits) &&
-                     ((dlogits->flags & MMTTA_TENSOR_OWNS_PAD) || dlogits->c == 4);
-    MMTTA_CHECK(is_f32(dlogits) || vec, MMTTA_ERR_UNSUPPORTED,
-                "deyo loss: a bf16-stored `dlogits` needs dense 4-channel voxel rows that own their pad");
-    auto run = [&](double* part, const long long* kk) {
-      if (vec && is_bf16(dlogits))
-        hipLaunchKernelGGL(deyo_bernoulli_vec_kernel<true>, launch, dim3(256), 0, s, tv(logits), tv(logits_shuffled), tv(dlogits),
-                           pg, tb, a, keep_out, part, kk);
-      else if (vec)
-        hipLaunchKernelGGL(deyo_bernoulli_vec_kernel<false>, launch, dim3(256), 0, s, tv(logits), tv(logits_shuffled), tv(dlogits),
-                           pg, tb, a, keep_out, part, kk);
-      else
-        hipLaunchKernelGGL(deyo_bernoulli_kernel, launch, dim3(256), 0, s, tv(logits), tv(logits_shuffled), tv(dlogits), pg, tb, a,
-                           keep_out, part, kk);
-    };
-    run(partial, nullptr);
-    st = launch_status("deyo loss bernoulli");
-    if (st) return st;
-    hipLaunchKernelGGL(deyo_finish_kernel, dim3(items), dim3(64), 0, s, (const double*)partial, blocks, loss, (long long*)kept,
-                       (long long*)kept_entropy);
-    st = launch_status("deyo loss finish");
-    if (st) return st;
-    run(nullptr, kd);
-    return launch_status("deyo loss bernoulli gradient");
-  }
-  MMTTA_CHECK(logits->c <= DEYO_MAX_R, MMTTA_ERR_UNSUPPORTED, "deyo loss softmax: more than %d classes", DEYO_MAX_R);
-  MMTTA_CHECK(is_f32(dlogits), MMTTA_ERR_UNSUPPORTED, "deyo loss softmax: `dlogits` must be fp32-stored");
-  hipLaunchKernelGGL(deyo_categorical_kernel, launch, dim3(256), 0, s, tv(logits), tv(logits_shuffled), tv(dlogits), pg, tb, a,
-                     keep_out, partial, (const long long*)nullptr);
-  st = launch_status("deyo loss categorical");
-  if (st) return st;
-  hipLaunchKernelGGL(deyo_finish_kernel, dim3(items), dim3(64), 0, s, (const double*)partial, blocks, loss, (long long*)kept,
-                     (long long*)kept_entropy);
-  st = launch_status("deyo loss finish");
-  if (st) return st;
-  hipLaunchKernelGGL(deyo_categorical_kernel, launch, dim3(256), 0, s, tv(logits), tv(logits_shuffled), tv(dlogits), pg, tb, a,
-                     keep_out, (double*)nullptr, kd);
-  return launch_status("deyo loss categorical gradient");
+  MMTTA_CHECK(logits->n <= LOSS_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "deyo loss: more than %d items in one call", LOSS_MAX_GRID_Y);
+  DeyoLoss p = {margin, margin0, plpd_threshold, tv(logits_shuffled), pg, (const int*)table};
+  return kept_launch<DeyoLoss, unsigned>({"deyo loss", "deyo loss", "deyo loss"}, logits, dlogits, softmax,
+                                         loss_vec(logits, dlogits, logits_shuffled), keep_out, partial, loss, (long long*)kept,
+                                         (long long*)kept_entropy, p, (hipStream_t)stream);
 }

@@ -1,156 +1,33 @@
 // Entropy objective (+gradient), fused Adam over the flat parameter arena, and the
 // sigmoid -> threshold -> Dice counting tail (gfx950).  All three are single-pass HBM-bound
 // kernels; see include/mmtta.h for the reference lines each one stands in for.
-#include "common.h"
+#include "voxel_loss.h"
 
 namespace mmtta {
 
 // ------------------------------------------------------------------ entropy loss
-constexpr int ENT_MAX_BLOCKS = 2048;
-constexpr int ENT_MAX_R = 16;
-
-// block_sum_d: common.h
-
-__global__ __launch_bounds__(256) void entropy_bernoulli_kernel(TV z, TV dz, double* partial, float inv_count, int per_item) {
-  __shared__ double sh[4];
-  if (per_item) {      // N independent volumes: this workgroup column works on batch item blockIdx.y alone
-    z.p += (long long)blockIdx.y * z.sn; dz.p += (long long)blockIdx.y * dz.sn;
-    z.n = 1; dz.n = 1;
-    partial += (long long)blockIdx.y * gridDim.x;
+// The plain walk of voxel_loss.h over the entropy arithmetic.  Its fast path ran at 100 - 120 % vector-ALU busy in libm's
+// expf / log1pf / IEEE division with a double add per logit (profiles/r03d_sq_counters.md: 158 vector instructions per
+// logit) - 203 us per group of 8 volumes at 128^3 against 85 us of HBM time, and vector issue is what the other lanes'
+// kernels run short of.  Now per logit: v_exp_f32, v_rcp_f32, v_log_f32 and ~15 plain instructions
+// (bernoulli_entropy_terms).  Against the libm form: loss within 1e-6 relative, gradient within 2e-6 of its maximum
+// (tests/test_hip_pointwise.py::test_entropy_loss holds both to the torch reference at 2e-5).
+struct EntropyLoss : NoOperand {
+  __device__ __forceinline__ void fast(float z, float, float& h, float& g) const { bernoulli_entropy_terms(z, h, g); }
+  __device__ __forceinline__ void generic(float z, float, float& h, float& g) const {
+    const BernoulliLibm b = bernoulli_entropy_libm(z);
+    h = b.h; g = b.g;
   }
-  const int C = z.c;
-  const long long total = (long long)z.n * z.d * z.h * z.w * C;
-  double acc = 0.0;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    long long v = i / C;
-    const int x = (int)(v % z.w); v /= z.w;
-    const int y = (int)(v % z.h); v /= z.h;
-    const int zz = (int)(v % z.d);
-    const int n = (int)(v / z.d);
-    const float t = z.p[n * z.sn + zz * z.sd + y * z.sh + x * z.sw + c];
-    const float e = expf(-fabsf(t));
-    const float sig = t >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    const float softplus = fmaxf(t, 0.f) + log1pf(e);
-    acc += (double)(softplus - t * sig);
-    dz.p[n * dz.sn + zz * dz.sd + y * dz.sh + x * dz.sw + c] = -t * sig * (1.f - sig) * inv_count;
-  }
-  const double t = block_sum_d(acc, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
-
-// Fast path of the Bernoulli objective: <= 4 regions in 16-byte voxel rows, dense voxel order.  A thread owns a
-// voxel: one 16-byte load, one 16-byte store (the gradient tensor owns its pad lane), no index arithmetic.
-// The kernel ran at 100 - 120 % vector-ALU busy (profiles/r03d_sq_counters.md: 158 vector instructions per logit in
-// libm's expf / log1pf / IEEE division and a double add per logit) - 203 us per group of 8 volumes at 128^3 against 85 us
-// of HBM time, and vector issue is what the other lanes' kernels run short of.  Now per logit: v_exp_f32, v_rcp_f32,
-// v_log_f32 and ~15 plain instructions; log1p(e) of e = exp(-|t|) in (0, 1] is the 4-term series below 2^-6 (relative
-// error < 2e-8) and log(1 + e) above (absolute rounding 6e-8 against a value >= 0.0155); the voxel's <= 4 terms are summed
-// in fp32 and enter the double accumulator once.  Against the libm form: loss within 1e-6 relative, gradient within 2e-6
-// of its maximum (tests/test_hip_pointwise.py::test_entropy_loss holds both to the torch reference at 2e-5).
-// bernoulli_entropy_terms: common.h (shared with csrc/eata.hip, whose masks must equal the filtered kernel's bit for bit)
-// OBF: the gradient is bf16-stored (8-byte voxels; method.grad_storage - its readers round it to bf16 while staging)
-template <bool OBF>
-__global__ __launch_bounds__(256) void entropy_bernoulli_vec_kernel(TV z, TV dz, double* partial, float inv_count, int per_item) {
-  __shared__ double sh[4];
-  if (per_item) {      // N independent volumes: this workgroup column works on batch item blockIdx.y alone
-    z.p += (long long)blockIdx.y * z.sn;
-    dz.p = OBF ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(dz.p) + (long long)blockIdx.y * dz.sn)
-               : dz.p + (long long)blockIdx.y * dz.sn;
-    z.n = 1; dz.n = 1;
-    partial += (long long)blockIdx.y * gridDim.x;
-  }
-  const int C = z.c;
-  const long long dhw = (long long)z.d * z.h * z.w;
-  const long long total = (long long)z.n * dhw;
-  double acc = 0.0;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    // one volume per launch in the adaptation loop: no 64-bit division per voxel then (uniform branch)
-    const long long n = z.n == 1 ? 0 : i / dhw, v = i - n * dhw;
-    const float4 t4 = *reinterpret_cast<const float4*>(z.p + n * z.sn + v * 4);
-    const float ts[4] = {t4.x, t4.y, t4.z, t4.w};
-    float g[4] = {0.f, 0.f, 0.f, 0.f};
-    float h = 0.f;
+  template <class F>
+  __device__ __forceinline__ float categorical(const float* zp, const float*, int R, F&& put) const {
+    CategoricalVoxel v;
+    categorical_entropy<false>(zp, R, v);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c < C) {
-        float hc, gc;
-        bernoulli_entropy_terms(ts[c], hc, gc);
-        h += hc;
-        g[c] = gc * inv_count;
-      }
-    }
-    acc += (double)h;
-    st4_any(dz.p, n * dz.sn + v * 4, make_float4(g[0], g[1], g[2], g[3]), OBF);
+    for (int r = 0; r < LOSS_MAX_R; ++r)
+      if (r < R) put(r, categorical_entropy_grad<false>(v, r));
+    return v.H;
   }
-  const double t = block_sum_d(acc, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
-
-__global__ __launch_bounds__(256) void entropy_categorical_kernel(TV z, TV dz, double* partial, float inv_count, int per_item) {
-  __shared__ double sh[4];
-  if (per_item) {      // N independent volumes: this workgroup column works on batch item blockIdx.y alone
-    z.p += (long long)blockIdx.y * z.sn; dz.p += (long long)blockIdx.y * dz.sn;
-    z.n = 1; dz.n = 1;
-    partial += (long long)blockIdx.y * gridDim.x;
-  }
-  const int R = z.c;
-  const long long total = (long long)z.n * z.d * z.h * z.w;
-  double acc = 0.0;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    long long v = i;
-    const int x = (int)(v % z.w); v /= z.w;
-    const int y = (int)(v % z.h); v /= z.h;
-    const int zz = (int)(v % z.d);
-    const int n = (int)(v / z.d);
-    const float* zp = z.p + n * z.sn + zz * z.sd + y * z.sh + x * z.sw;
-    float* gp = dz.p + n * dz.sn + zz * dz.sd + y * dz.sh + x * dz.sw;
-    float t[ENT_MAX_R];
-    float m = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < ENT_MAX_R; ++r)
-      if (r < R) { t[r] = zp[r]; m = fmaxf(m, t[r]); }
-    float se = 0.f;
-#pragma unroll
-    for (int r = 0; r < ENT_MAX_R; ++r)
-      if (r < R) se += expf(t[r] - m);
-    const float lse = m + logf(se);
-    float pz = 0.f;
-#pragma unroll
-    for (int r = 0; r < ENT_MAX_R; ++r)
-      if (r < R) pz += expf(t[r] - lse) * t[r];
-    const float H = lse - pz;
-    acc += (double)H;
-#pragma unroll
-    for (int r = 0; r < ENT_MAX_R; ++r)
-      if (r < R) {
-        const float logp = t[r] - lse;
-        gp[r] = -expf(logp) * (logp + H) * inv_count;
-      }
-  }
-  const double t = block_sum_d(acc, sh);
-  if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
-
-__global__ __launch_bounds__(64) void entropy_finish_kernel(const double* partial, int nblocks, double inv_count,
-                                                            float* loss) {
-  partial += (long long)blockIdx.x * nblocks;      // one workgroup per independent item (a single one otherwise)
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 64) s += partial[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) loss[blockIdx.x] = (float)(s * inv_count);
-}
-
-static int entropy_blocks(const mmtta_tensor* z) {
-  const long long total = (long long)z->n * z->d * z->h * z->w * z->c;
-  long long b = (total + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > ENT_MAX_BLOCKS) b = ENT_MAX_BLOCKS;
-  return (int)b;
-}
+};
 
 // ------------------------------------------------------------------ fused optimizers over the flat arena
 // KIND 0: torch.optim.Adam (coupled L2), 1: torch.optim.AdamW (decoupled decay), 2: torch.optim.SGD (momentum, dampening,
@@ -456,155 +333,34 @@ __global__ __launch_bounds__(256) void dice_ce_grad_kernel(DceGradArgs a) {
 }
 
 // ------------------------------------------------------------------ filtered entropy (SAR's reliable-entropy loss)
-// Per independent item (gridDim.y), the same launch geometry as entropy_launch(per_item).  Pass 1 computes H per element with
-// the per-logit arithmetic of the three kernels above, writes keep = H < margin (ANDed with an incoming mask) as one byte per
-// element (dense channels-last: (voxel, region) for the Bernoulli heads, voxel for the categorical one) and leaves fp64 block
-// partials of the kept sum of H and of the kept count: partial[item][0][block], partial[item][1][block].  The finish kernel
-// writes loss[item] and kept[item]; pass 2 writes dlogits = keep * dH/dz / kept[item], the scale read on the device.  With
+// The filtered walk of voxel_loss.h over the entropy arithmetic above: keep = H < margin, ANDed with an incoming mask.  With
 // every element kept the block partials, the loss arithmetic and the gradient scale are those of mmtta_entropy_loss_items.
-// fent_store_partials / fent_scale: common.h
-__global__ __launch_bounds__(256) void fent_bernoulli_kernel(TV z, TV dz, float margin, const unsigned char* kin,
-                                                             unsigned char* kout, double* partial, const long long* kept) {
-  __shared__ double sh[4];
-  const int C = z.c;
-  const long long total = (long long)z.d * z.h * z.w * C;
-  z.p += (long long)blockIdx.y * z.sn;
-  kout += (long long)blockIdx.y * total;
-  if (kin) kin += (long long)blockIdx.y * total;
-  const bool grad = kept != nullptr;      // pass 2: kout is the mask pass 1 wrote
-  if (grad) dz.p += (long long)blockIdx.y * dz.sn;
-  const float scale = grad ? fent_scale(kept) : 0.f;
-  double acc = 0.0;
-  int cnt = 0;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    long long v = i / C;
-    const int x = (int)(v % z.w); v /= z.w;
-    const int y = (int)(v % z.h); v /= z.h;
-    const int zz = (int)v;
-    const float t = z.p[zz * z.sd + y * z.sh + x * z.sw + c];
-    const float e = expf(-fabsf(t));
-    const float sig = t >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    if (grad) {
-      dz.p[zz * dz.sd + y * dz.sh + x * dz.sw + c] = kout[i] ? -t * sig * (1.f - sig) * scale : 0.f;
-      continue;
-    }
-    const float softplus = fmaxf(t, 0.f) + log1pf(e);
-    const float h = softplus - t * sig;
-    const bool keep = h < margin && (kin == nullptr || kin[i] != 0);
-    kout[i] = keep ? 1 : 0;
-    if (keep) { acc += (double)h; ++cnt; }
+struct FilteredEntropy : NoOperand {
+  static constexpr int ROWS = 2;
+  float margin;
+  const unsigned char* kin;      // the incoming mask in the layout of the outgoing one, or null
+  __device__ __forceinline__ void item(int n, long long elems) { if (kin) kin += n * elems; }
+  __device__ __forceinline__ bool allowed(long long i) const { return kin == nullptr || kin[i] != 0; }
+  __device__ __forceinline__ KeptTerms fast(float z, float) const {
+    KeptTerms e;
+    bernoulli_entropy_terms(z, e.h, e.g);
+    e.v = e.h; e.pass = true;
+    return e;
   }
-  if (!grad) fent_store_partials(acc, cnt, partial, sh);
-}
-
-template <bool OBF>
-__global__ __launch_bounds__(256) void fent_bernoulli_vec_kernel(TV z, TV dz, float margin, const unsigned char* kin,
-                                                                 unsigned char* kout, double* partial, const long long* kept) {
-  __shared__ double sh[4];
-  const int C = z.c;
-  const long long total = (long long)z.d * z.h * z.w;
-  z.p += (long long)blockIdx.y * z.sn;
-  kout += (long long)blockIdx.y * total * C;
-  if (kin) kin += (long long)blockIdx.y * total * C;
-  const bool grad = kept != nullptr;
-  if (grad)
-    dz.p = OBF ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(dz.p) + (long long)blockIdx.y * dz.sn)
-               : dz.p + (long long)blockIdx.y * dz.sn;
-  const float scale = grad ? fent_scale(kept) : 0.f;
-  double acc = 0.0;
-  int cnt = 0;
-  for (long long v = blockIdx.x * (long long)blockDim.x + threadIdx.x; v < total;
-       v += (long long)gridDim.x * blockDim.x) {
-    const float4 t4 = *reinterpret_cast<const float4*>(z.p + v * 4);
-    const float ts[4] = {t4.x, t4.y, t4.z, t4.w};
-    float g[4] = {0.f, 0.f, 0.f, 0.f};
-    float h = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (c < C) {
-        float hc, gc;
-        bernoulli_entropy_terms(ts[c], hc, gc);
-        if (grad) {
-          g[c] = kout[v * C + c] ? gc * scale : 0.f;
-        } else {
-          const bool keep = hc < margin && (kin == nullptr || kin[v * C + c] != 0);
-          kout[v * C + c] = keep ? 1 : 0;
-          if (keep) { h += hc; ++cnt; }
-        }
-      }
-    }
-    if (grad) st4_any(dz.p, v * 4, make_float4(g[0], g[1], g[2], g[3]), OBF);
-    else acc += (double)h;
+  __device__ __forceinline__ KeptTerms generic(float z, float) const {
+    const BernoulliLibm b = bernoulli_entropy_libm(z);
+    return {b.h, b.h, b.g, true};
   }
-  if (!grad) fent_store_partials(acc, cnt, partial, sh);
-}
-
-__global__ __launch_bounds__(256) void fent_categorical_kernel(TV z, TV dz, float margin, const unsigned char* kin,
-                                                               unsigned char* kout, double* partial, const long long* kept) {
-  __shared__ double sh[4];
-  const int R = z.c;
-  const long long total = (long long)z.d * z.h * z.w;
-  z.p += (long long)blockIdx.y * z.sn;
-  kout += (long long)blockIdx.y * total;
-  if (kin) kin += (long long)blockIdx.y * total;
-  const bool grad = kept != nullptr;
-  if (grad) dz.p += (long long)blockIdx.y * dz.sn;
-  const float scale = grad ? fent_scale(kept) : 0.f;
-  double acc = 0.0;
-  int cnt = 0;
-  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
-       i += (long long)gridDim.x * blockDim.x) {
-    long long v = i;
-    const int x = (int)(v % z.w); v /= z.w;
-    const int y = (int)(v % z.h); v /= z.h;
-    const int zz = (int)v;
-    const float* zp = z.p + zz * z.sd + y * z.sh + x * z.sw;
-    float t[ENT_MAX_R];
-    float m = -INFINITY;
+  template <class F>
+  __device__ __forceinline__ KeptTerms categorical(const float* zp, const float*, int R, F&& put) const {
+    CategoricalVoxel v;
+    categorical_entropy<false>(zp, R, v);
 #pragma unroll
-    for (int r = 0; r < ENT_MAX_R; ++r)
-      if (r < R) { t[r] = zp[r]; m = fmaxf(m, t[r]); }
-    float se = 0.f;
-#pragma unroll
-    for (int r = 0; r < ENT_MAX_R; ++r)
-      if (r < R) se += expf(t[r] - m);
-    const float lse = m + logf(se);
-    float pz = 0.f;
-#pragma unroll
-    for (int r = 0; r < ENT_MAX_R; ++r)
-      if (r < R) pz += expf(t[r] - lse) * t[r];
-    const float H = lse - pz;
-    if (grad) {
-      float* gp = dz.p + zz * dz.sd + y * dz.sh + x * dz.sw;
-      const bool keep = kout[i] != 0;
-#pragma unroll
-      for (int r = 0; r < ENT_MAX_R; ++r)
-        if (r < R) {
-          const float logp = t[r] - lse;
-          gp[r] = keep ? -expf(logp) * (logp + H) * scale : 0.f;
-        }
-      continue;
-    }
-    const bool keep = H < margin && (kin == nullptr || kin[i] != 0);
-    kout[i] = keep ? 1 : 0;
-    if (keep) { acc += (double)H; ++cnt; }
+    for (int r = 0; r < LOSS_MAX_R; ++r)
+      if (r < R) put(r, categorical_entropy_grad<false>(v, r));
+    return {v.H, v.H, 0.f, true};
   }
-  if (!grad) fent_store_partials(acc, cnt, partial, sh);
-}
-
-__global__ __launch_bounds__(64) void fent_finish_kernel(const double* partial, int nblocks, float* loss, long long* kept) {
-  partial += (long long)blockIdx.x * 2 * nblocks;
-  double s = 0.0, c = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 64) { s += partial[i]; c += partial[nblocks + i]; }
-  s = wave_sum_d(s);
-  c = wave_sum_d(c);
-  if (threadIdx.x == 0) {
-    kept[blockIdx.x] = (long long)c;
-    loss[blockIdx.x] = c > 0.0 ? (float)(s * (1.0 / c)) : __builtin_nanf("");
-  }
-}
+};
 
 // ------------------------------------------------------------------ SAM ascent over arena replicas
 // eps = rho * g / (||g||_2 + 1e-12) over [0, n) of each of the first `sets` replicas; w_saved = w, w += eps.  Stage 1: fp64
@@ -660,7 +416,7 @@ using namespace mmtta;
 
 extern "C" int64_t mmtta_entropy_partials(const mmtta_tensor* logits) {
   if (logits == nullptr) return -1;
-  return entropy_blocks(logits);
+  return loss_blocks(logits, logits->n);
 }
 
 static int entropy_launch(const mmtta_tensor* logits, int softmax, const mmtta_tensor* dlogits, double* partial, float* loss,
@@ -670,42 +426,9 @@ static int entropy_launch(const mmtta_tensor* logits, int softmax, const mmtta_t
   MMTTA_CHECK(logits->n == dlogits->n && logits->c == dlogits->c && logits->d == dlogits->d && logits->h == dlogits->h &&
                   logits->w == dlogits->w, MMTTA_ERR_INVALID, "entropy: shape mismatch");
   MMTTA_CHECK(is_cl(logits) && is_cl(dlogits), MMTTA_ERR_UNSUPPORTED, "entropy: channels-last only");
-  hipStream_t s = (hipStream_t)stream;
-  // per_item: every batch item is its own objective - the launch geometry, block partials and scale of ONE item, repeated
-  // along gridDim.y (bit-identical to N separate calls)
-  mmtta_tensor one = *logits;
-  if (per_item) one.n = 1;
-  const int items = per_item ? logits->n : 1;
-  const int blocks = entropy_blocks(&one);
-  const long long nvox = (long long)one.n * logits->d * logits->h * logits->w;
-  const dim3 grid(blocks, items);
-  if (!softmax) {
-    const double cnt = (double)nvox * logits->c;
-    auto dense16 = [](const mmtta_tensor* t) {
-      return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
-             ((uintptr_t)t->ptr) % 16 == 0;
-    };
-    const bool vec = logits->c <= 4 && dense16(logits) && dense16(dlogits) && ((dlogits->flags & MMTTA_TENSOR_OWNS_PAD) || dlogits->c == 4);
-    MMTTA_CHECK(is_f32(dlogits) || vec, MMTTA_ERR_UNSUPPORTED, "mmtta_entropy_loss: a bf16-stored `dlogits` needs dense 4-channel voxel rows that own their pad");
-    if (vec && is_bf16(dlogits))
-      hipLaunchKernelGGL(entropy_bernoulli_vec_kernel<true>, grid, dim3(256), 0, s, tv(logits), tv(dlogits), partial, (float)(1.0 / cnt), per_item);
-    else if (vec)
-      hipLaunchKernelGGL(entropy_bernoulli_vec_kernel<false>, grid, dim3(256), 0, s, tv(logits), tv(dlogits), partial, (float)(1.0 / cnt), per_item);
-    else
-      hipLaunchKernelGGL(entropy_bernoulli_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), partial, (float)(1.0 / cnt), per_item);
-    int st = launch_status("entropy bernoulli");
-    if (st) return st;
-    hipLaunchKernelGGL(entropy_finish_kernel, dim3(items), dim3(64), 0, s, partial, blocks, 1.0 / cnt, loss);
-  } else {
-    MMTTA_CHECK(logits->c <= ENT_MAX_R, MMTTA_ERR_UNSUPPORTED, "entropy softmax: more than %d classes", ENT_MAX_R);
-    MMTTA_CHECK(is_f32(dlogits), MMTTA_ERR_UNSUPPORTED, "entropy softmax: `dlogits` must be fp32-stored");
-    const double cnt = (double)nvox;
-    hipLaunchKernelGGL(entropy_categorical_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), partial, (float)(1.0 / cnt), per_item);
-    int st = launch_status("entropy categorical");
-    if (st) return st;
-    hipLaunchKernelGGL(entropy_finish_kernel, dim3(items), dim3(64), 0, s, partial, blocks, 1.0 / cnt, loss);
-  }
-  return launch_status("entropy finish");
+  return loss_launch<EntropyLoss, long long>({"mmtta_entropy_loss", "entropy", "entropy"}, logits, dlogits, softmax,
+                                             loss_vec(logits, dlogits), per_item, partial, loss, EntropyLoss{},
+                                             (hipStream_t)stream);
 }
 
 extern "C" int mmtta_entropy_loss(const mmtta_tensor* logits, int softmax, const mmtta_tensor* dlogits, double* partial,
@@ -715,9 +438,7 @@ extern "C" int mmtta_entropy_loss(const mmtta_tensor* logits, int softmax, const
 
 extern "C" int64_t mmtta_entropy_partials_items(const mmtta_tensor* logits) {
   if (logits == nullptr) return -1;
-  mmtta_tensor one = *logits;
-  one.n = 1;
-  return (int64_t)entropy_blocks(&one) * logits->n;
+  return (int64_t)loss_blocks(logits) * logits->n;
 }
 
 extern "C" int mmtta_entropy_loss_items(const mmtta_tensor* logits, int softmax, const mmtta_tensor* dlogits, double* partial,
@@ -896,9 +617,7 @@ extern "C" int mmtta_dice_ce_grad(const mmtta_tensor* logits, const mmtta_tensor
 
 extern "C" int64_t mmtta_entropy_filtered_partials(const mmtta_tensor* logits) {
   if (logits == nullptr) return -1;
-  mmtta_tensor one = *logits;
-  one.n = 1;
-  return 2 * (int64_t)entropy_blocks(&one) * logits->n;
+  return 2 * (int64_t)loss_blocks(logits) * logits->n;
 }
 
 extern "C" int mmtta_entropy_filtered_items(const mmtta_tensor* logits, int softmax, float margin, const uint8_t* keep_in,
@@ -914,50 +633,9 @@ extern "C" int mmtta_entropy_filtered_items(const mmtta_tensor* logits, int soft
               MMTTA_ERR_INVALID, "entropy filtered: shape mismatch");
   MMTTA_CHECK(logits->dtype == MMTTA_F32, MMTTA_ERR_UNSUPPORTED, "entropy filtered: `logits` must be fp32-stored");
   MMTTA_CHECK(is_cl(logits) && is_cl(dlogits), MMTTA_ERR_UNSUPPORTED, "entropy filtered: channels-last only");
-  hipStream_t s = (hipStream_t)stream;
-  mmtta_tensor one = *logits;
-  one.n = 1;
-  const int items = logits->n;
-  const int blocks = entropy_blocks(&one);
-  const dim3 grid(blocks, items);
-  const long long* kd = (const long long*)kept;
-  if (!softmax) {
-    auto dense16 = [](const mmtta_tensor* t) {
-      return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
-             ((uintptr_t)t->ptr) % 16 == 0;
-    };
-    const bool vec = logits->c <= 4 && dense16(logits) && dense16(dlogits) && ((dlogits->flags & MMTTA_TENSOR_OWNS_PAD) || dlogits->c == 4);
-    MMTTA_CHECK(is_f32(dlogits) || vec, MMTTA_ERR_UNSUPPORTED,
-                "entropy filtered: a bf16-stored `dlogits` needs dense 4-channel voxel rows that own their pad");
-    auto run = [&](const unsigned char* kin, unsigned char* kout, double* part, const long long* kk) {
-      if (vec && is_bf16(dlogits))
-        hipLaunchKernelGGL(fent_bernoulli_vec_kernel<true>, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin, kin, kout, part, kk);
-      else if (vec)
-        hipLaunchKernelGGL(fent_bernoulli_vec_kernel<false>, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin, kin, kout, part, kk);
-      else
-        hipLaunchKernelGGL(fent_bernoulli_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin, kin, kout, part, kk);
-    };
-    run(keep_in, keep_out, partial, nullptr);
-    int st = launch_status("entropy filtered bernoulli");
-    if (st) return st;
-    hipLaunchKernelGGL(fent_finish_kernel, dim3(items), dim3(64), 0, s, partial, blocks, loss, (long long*)kept);
-    st = launch_status("entropy filtered finish");
-    if (st) return st;
-    run(nullptr, keep_out, nullptr, kd);
-    return launch_status("entropy filtered bernoulli gradient");
-  }
-  MMTTA_CHECK(logits->c <= ENT_MAX_R, MMTTA_ERR_UNSUPPORTED, "entropy filtered softmax: more than %d classes", ENT_MAX_R);
-  MMTTA_CHECK(is_f32(dlogits), MMTTA_ERR_UNSUPPORTED, "entropy filtered softmax: `dlogits` must be fp32-stored");
-  hipLaunchKernelGGL(fent_categorical_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin, keep_in, keep_out, partial,
-                     (const long long*)nullptr);
-  int st = launch_status("entropy filtered categorical");
-  if (st) return st;
-  hipLaunchKernelGGL(fent_finish_kernel, dim3(items), dim3(64), 0, s, partial, blocks, loss, (long long*)kept);
-  st = launch_status("entropy filtered finish");
-  if (st) return st;
-  hipLaunchKernelGGL(fent_categorical_kernel, grid, dim3(256), 0, s, tv(logits), tv(dlogits), margin,
-                     (const unsigned char*)nullptr, keep_out, (double*)nullptr, kd);
-  return launch_status("entropy filtered categorical gradient");
+  return kept_launch<FilteredEntropy, long long>({"entropy filtered", "entropy filtered", "entropy filtered"}, logits, dlogits,
+                                                 softmax, loss_vec(logits, dlogits), keep_out, partial, loss, (long long*)kept,
+                                                 nullptr, FilteredEntropy{{}, margin, keep_in}, (hipStream_t)stream);
 }
 
 static long long sam_blocks(int64_t n) {

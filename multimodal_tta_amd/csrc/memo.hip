@@ -17,32 +17,18 @@
 // land W rows apart in the view, so the per-step kernels of the fast path take a tiled form (memo_bernoulli_tiled_kernel,
 // memo_ensemble_tiled_kernel: the view's tile is loaded along the VIEW's W and turned through LDS); the generic Bernoulli,
 // categorical, generic ensemble and mirror kernels follow the coordinate map alone and are UNCOALESCED for transposed views.
-#include "common.h"
+#include "voxel_loss.h"
 
 namespace mmtta {
 
-constexpr int MEMO_MAX_BLOCKS = 2048;      // block partials per volume (the entropy objective's figure)
-constexpr int MEMO_MAX_R = 16;             // classes of the categorical path (ENT_MAX_R of loss_optim_metric.hip)
 constexpr int MEMO_MAX_V = 8;
 constexpr int MEMO_TURN = 16;              // bit 4 of a view's code: H and W transposed before the mirrors of bits 0-2
-constexpr int MEMO_MAX_GRID_Y = 65535;     // gridDim.y carries the volume (the output item of the view layout)
 constexpr float MEMO_TINY = 1.17549435e-38f;   // smallest normal fp32: v_log_f32 and x log x stay finite from here up
 
 struct MemoViews {
   int v;
   int axes[MEMO_MAX_V];
 };
-
-__device__ __forceinline__ double memo_block_sum(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += sh[w];
-  return t;  // valid on thread 0
-}
 
 // coordinates of linear voxel i (32-bit: the host checks D*H*W*ldc < 2^31) and of its mirror image
 struct MemoVox {
@@ -86,12 +72,10 @@ __device__ __forceinline__ long long memo_addr(const TV& t, long long item, cons
 
 // sigmoid(t), sigmoid(-t) and their product, none formed by subtraction: v_exp_f32 / v_rcp_f32 as the entropy fast path
 __device__ __forceinline__ void memo_sigmoid_terms(float t, float& p, float& q, float& pq) {
-  const float e = __builtin_amdgcn_exp2f(-fabsf(t) * 1.4426950408889634f);   // exp(-|t|)
-  const float r = __builtin_amdgcn_rcpf(1.f + e);
-  const float er = e * r;
-  p = t >= 0.f ? r : er;
-  q = t >= 0.f ? er : r;
-  pq = er * r;
+  const SigmoidPair s = sigmoid_pair(t, exp_neg_abs(t));
+  p = s.p;
+  q = s.q;
+  pq = s.er * s.r;
 }
 __device__ __forceinline__ float memo_ln(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }   // x normal
 // log p and log q of a complementary pair (p + q = 1 up to rounding), finite for p or q = 0: the log of the smaller one is
@@ -162,7 +146,7 @@ __global__ __launch_bounds__(256) void memo_bernoulli_vec_kernel(const float* __
       st4_any(gb, off[v], make_float4(f[0] * pq[v][0], f[1] * pq[v][1], f[2] * pq[v][2], f[3] * pq[v][3]), OBF);
     }
   }
-  const double t = memo_block_sum(acc, sh);
+  const double t = block_sum_d(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -277,7 +261,7 @@ __global__ __launch_bounds__(256) void memo_bernoulli_tiled_kernel(const float* 
       if (tr ? pos.livem : pos.live) st4_any(gb, off[v], g4[v], OBF);
     }
   }
-  const double t = memo_block_sum(acc, sh);
+  const double t = block_sum_d(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -321,25 +305,25 @@ __global__ __launch_bounds__(256) void memo_bernoulli_kernel(TV z, TV dz, MemoVi
       }
     }
   }
-  const double t = memo_block_sum(acc, sh);
+  const double t = block_sum_d(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
 // ------------------------------------------------------------------ marginal entropy, categorical head
 // log softmax of one voxel row into lp[0..R), finite for every finite row (a difference that overflows is held at -3e38)
-__device__ __forceinline__ void memo_log_softmax_row(const float* zp, int R, float (&lp)[MEMO_MAX_R]) {
+__device__ __forceinline__ void memo_log_softmax_row(const float* zp, int R, float (&lp)[LOSS_MAX_R]) {
   float m = -INFINITY;
 #pragma unroll
-  for (int r = 0; r < MEMO_MAX_R; ++r)
+  for (int r = 0; r < LOSS_MAX_R; ++r)
     if (r < R) { lp[r] = zp[r]; m = fmaxf(m, lp[r]); }
   float se = 0.f;
 #pragma unroll
-  for (int r = 0; r < MEMO_MAX_R; ++r)
+  for (int r = 0; r < LOSS_MAX_R; ++r)
     if (r < R) se += expf(lp[r] - m);
   // (t - m) - log(se), not t - (m + log(se)): at logits of 1e4 the sum m + log(se) would round log(se) to 1e-3
   const float lg = logf(se);             // se >= 1: the maximum contributes exp(0)
 #pragma unroll
-  for (int r = 0; r < MEMO_MAX_R; ++r)
+  for (int r = 0; r < LOSS_MAX_R; ++r)
     if (r < R) lp[r] = fmaxf((lp[r] - m) - lg, -3e38f);
 }
 // log pbar_r = logsumexp_v(log softmax_r(u_v)) - log V, accumulated view by view (running maximum mx, scaled sum sm):
@@ -369,16 +353,16 @@ __global__ __launch_bounds__(256) void memo_categorical_kernel(TV z, TV dz, Memo
   double acc = 0.0;
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     const MemoVox pos = memo_vox(i, D, H, W);
-    float lpb[MEMO_MAX_R], sm[MEMO_MAX_R], lp[MEMO_MAX_R];
+    float lpb[LOSS_MAX_R], sm[LOSS_MAX_R], lp[LOSS_MAX_R];
     for (int v = 0; v < V; ++v) {
       memo_log_softmax_row(memo_row<TR>(z, item0 + v, pos, mv.axes[v]), R, lp);
 #pragma unroll
-      for (int r = 0; r < MEMO_MAX_R; ++r)
+      for (int r = 0; r < LOSS_MAX_R; ++r)
         if (r < R) memo_lse_add(lp[r], v == 0, lpb[r], sm[r]);
     }
     float h = 0.f;
 #pragma unroll
-    for (int r = 0; r < MEMO_MAX_R; ++r)
+    for (int r = 0; r < LOSS_MAX_R; ++r)
       if (r < R) {
         lpb[r] = lpb[r] + logf(sm[r]) - log_v;
         h -= expf(lpb[r]) * lpb[r];
@@ -388,24 +372,16 @@ __global__ __launch_bounds__(256) void memo_categorical_kernel(TV z, TV dz, Memo
       memo_log_softmax_row(memo_row<TR>(z, item0 + v, pos, mv.axes[v]), R, lp);
       float s = 0.f;
 #pragma unroll
-      for (int r = 0; r < MEMO_MAX_R; ++r)
+      for (int r = 0; r < LOSS_MAX_R; ++r)
         if (r < R) { lp[r] = expf(lp[r]); s = fmaf(lp[r], lpb[r], s); }
       float* gp = const_cast<float*>(memo_row<TR>(dz, item0 + v, pos, mv.axes[v]));
 #pragma unroll
-      for (int r = 0; r < MEMO_MAX_R; ++r)
+      for (int r = 0; r < LOSS_MAX_R; ++r)
         if (r < R) gp[r] = lp[r] * (s - lpb[r]) * inv_count;
     }
   }
-  const double t = memo_block_sum(acc, sh);
+  const double t = block_sum_d(acc, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
-
-__global__ __launch_bounds__(64) void memo_finish_kernel(const double* partial, int nblocks, double inv_count, float* loss) {
-  partial += (long long)blockIdx.x * nblocks;      // one workgroup per volume
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nblocks; i += 64) s += partial[i];
-  s = wave_sum_d(s);
-  if (threadIdx.x == 0) loss[blockIdx.x] = (float)(s * inv_count);
 }
 
 // ------------------------------------------------------------------ ensemble of the views' predictions
@@ -502,16 +478,16 @@ __global__ __launch_bounds__(256) void memo_ensemble_categorical_kernel(TV z, TV
   const float log_v = logf((float)V);
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     const MemoVox pos = memo_vox(i, D, H, W);
-    float lpb[MEMO_MAX_R], sm[MEMO_MAX_R], lp[MEMO_MAX_R];
+    float lpb[LOSS_MAX_R], sm[LOSS_MAX_R], lp[LOSS_MAX_R];
     for (int v = 0; v < V; ++v) {
       memo_log_softmax_row(memo_row<TR>(z, item0 + v, pos, mv.axes[v]), R, lp);
 #pragma unroll
-      for (int r = 0; r < MEMO_MAX_R; ++r)
+      for (int r = 0; r < LOSS_MAX_R; ++r)
         if (r < R) memo_lse_add(lp[r], v == 0, lpb[r], sm[r]);
     }
     float* op = out.p + vox_addr(out, (int)blockIdx.y, pos.z, pos.y, pos.x);
 #pragma unroll
-    for (int r = 0; r < MEMO_MAX_R; ++r)
+    for (int r = 0; r < LOSS_MAX_R; ++r)
       if (r < R) op[r] = lpb[r] + logf(sm[r]) - log_v;
   }
 }
@@ -538,17 +514,6 @@ __global__ __launch_bounds__(256) void memo_mirror_kernel(const T* __restrict__ 
   }
 }
 
-static int memo_blocks(const mmtta_tensor* z) {
-  // the figure of mmtta_entropy_partials for ONE item, for every head: it counts (voxel, region) pairs, so the kernels that
-  // give a thread a whole voxel get up to c times the workgroups they have voxels for below the cap - those write a zero
-  // partial - and mmtta_memo_partials is one formula
-  const long long total = (long long)z->d * z->h * z->w * z->c;
-  long long b = (total + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > MEMO_MAX_BLOCKS) b = MEMO_MAX_BLOCKS;
-  return (int)b;
-}
-
 // `turned`: a view of the call transposes H and W (bit 4), which needs square (H, W) planes
 static int memo_views_check(const char* what, int views, const int32_t* view_axes, const mmtta_tensor* t, MemoViews& mv, bool& turned) {
   const int n = t->n;
@@ -572,24 +537,13 @@ static int memo_views_check(const char* what, int views, const int32_t* view_axe
   return MMTTA_OK;
 }
 
-static bool memo_dense16(const mmtta_tensor* t) {
-  return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
-         ((uintptr_t)t->ptr) % 16 == 0;
-}
-
-// every offset inside one item fits 31 bits (the kernels index voxels with 32-bit arithmetic)
-static bool memo_small_item(const mmtta_tensor* t) {
-  const long long ld = t->sw > t->c ? t->sw : t->c;
-  return t->d > 0 && t->h > 0 && t->w > 0 && t->c > 0 && (long long)t->d * t->h * t->w * (ld > 4 ? ld : 4) < (1ll << 31);
-}
-
 }  // namespace mmtta
 
 using namespace mmtta;
 
 extern "C" int64_t mmtta_memo_partials(const mmtta_tensor* logits, int views) {
   if (logits == nullptr || !(views == 1 || views == 2 || views == 4 || views == 8) || logits->n < views || logits->n % views) return -1;
-  return (int64_t)memo_blocks(logits) * (logits->n / views);
+  return (int64_t)loss_blocks(logits) * (logits->n / views);
 }
 
 extern "C" int mmtta_memo_loss_items(const mmtta_tensor* logits, int softmax, int views, const int32_t* view_axes,
@@ -606,17 +560,17 @@ extern "C" int mmtta_memo_loss_items(const mmtta_tensor* logits, int softmax, in
   if (views == 1) return mmtta_entropy_loss_items(logits, softmax, dlogits, partial, loss, stream);
   MMTTA_CHECK(logits->dtype == MMTTA_F32, MMTTA_ERR_UNSUPPORTED, "memo loss: `logits` must be fp32-stored");
   MMTTA_CHECK(is_cl(logits) && is_cl(dlogits), MMTTA_ERR_UNSUPPORTED, "memo loss: channels-last only");
-  MMTTA_CHECK(memo_small_item(logits) && memo_small_item(dlogits), MMTTA_ERR_UNSUPPORTED, "memo loss: an item of 2^31 elements or more");
+  MMTTA_CHECK(loss_small_item(logits) && loss_small_item(dlogits), MMTTA_ERR_UNSUPPORTED, "memo loss: an item of 2^31 elements or more");
   hipStream_t s = (hipStream_t)stream;
   const int volumes = logits->n / views;
-  MMTTA_CHECK(volumes <= MEMO_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "memo loss: more than %d volumes in one call", MEMO_MAX_GRID_Y);
-  const int blocks = memo_blocks(logits);
+  MMTTA_CHECK(volumes <= LOSS_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "memo loss: more than %d volumes in one call", LOSS_MAX_GRID_Y);
+  const int blocks = loss_blocks(logits);
   const long long nvox = (long long)logits->d * logits->h * logits->w;
   const dim3 grid(blocks, volumes);
   const double cnt = softmax ? (double)nvox : (double)nvox * logits->c;
   const float inv = (float)(1.0 / (cnt * views));
   if (!softmax) {
-    const bool vec = logits->c <= 4 && memo_dense16(logits) && memo_dense16(dlogits) &&
+    const bool vec = logits->c <= 4 && loss_dense16(logits) && loss_dense16(dlogits) &&
                      ((dlogits->flags & MMTTA_TENSOR_OWNS_PAD) || dlogits->c == 4);
     MMTTA_CHECK(is_f32(dlogits) || vec, MMTTA_ERR_UNSUPPORTED, "memo loss: a bf16-stored `dlogits` needs dense 4-channel voxel rows that own their pad");
     if (vec) {
@@ -662,7 +616,7 @@ extern "C" int mmtta_memo_loss_items(const mmtta_tensor* logits, int softmax, in
     }
     st = launch_status("memo bernoulli");
   } else {
-    MMTTA_CHECK(logits->c <= MEMO_MAX_R, MMTTA_ERR_UNSUPPORTED, "memo loss softmax: more than %d classes", MEMO_MAX_R);
+    MMTTA_CHECK(logits->c <= LOSS_MAX_R, MMTTA_ERR_UNSUPPORTED, "memo loss softmax: more than %d classes", LOSS_MAX_R);
     MMTTA_CHECK(is_f32(dlogits), MMTTA_ERR_UNSUPPORTED, "memo loss softmax: `dlogits` must be fp32-stored");
     if (!turned)
       hipLaunchKernelGGL(memo_categorical_kernel<false>, grid, dim3(256), 0, s, tv(logits), tv(dlogits), mv, partial, inv);
@@ -671,7 +625,7 @@ extern "C" int mmtta_memo_loss_items(const mmtta_tensor* logits, int softmax, in
     st = launch_status("memo categorical");
   }
   if (st) return st;
-  hipLaunchKernelGGL(memo_finish_kernel, dim3(volumes), dim3(64), 0, s, partial, blocks, 1.0 / cnt, loss);
+  hipLaunchKernelGGL(mean_finish_kernel, dim3(volumes), dim3(64), 0, s, partial, blocks, 1.0 / cnt, loss);
   return launch_status("memo finish");
 }
 
@@ -686,11 +640,11 @@ extern "C" int mmtta_memo_ensemble(const mmtta_tensor* logits, int softmax, int 
                   logits->w == out->w, MMTTA_ERR_INVALID, "memo ensemble: shape mismatch");
   MMTTA_CHECK(logits->dtype == MMTTA_F32 && out->dtype == MMTTA_F32, MMTTA_ERR_UNSUPPORTED, "memo ensemble: fp32-stored tensors only");
   MMTTA_CHECK(is_cl(logits) && is_cl(out), MMTTA_ERR_UNSUPPORTED, "memo ensemble: channels-last only");
-  MMTTA_CHECK(memo_small_item(logits) && memo_small_item(out), MMTTA_ERR_UNSUPPORTED, "memo ensemble: an item of 2^31 elements or more");
-  MMTTA_CHECK(!softmax || logits->c <= MEMO_MAX_R, MMTTA_ERR_UNSUPPORTED, "memo ensemble softmax: more than %d classes", MEMO_MAX_R);
-  MMTTA_CHECK(out->n <= MEMO_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "memo ensemble: more than %d volumes in one call", MEMO_MAX_GRID_Y);
+  MMTTA_CHECK(loss_small_item(logits) && loss_small_item(out), MMTTA_ERR_UNSUPPORTED, "memo ensemble: an item of 2^31 elements or more");
+  MMTTA_CHECK(!softmax || logits->c <= LOSS_MAX_R, MMTTA_ERR_UNSUPPORTED, "memo ensemble softmax: more than %d classes", LOSS_MAX_R);
+  MMTTA_CHECK(out->n <= LOSS_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "memo ensemble: more than %d volumes in one call", LOSS_MAX_GRID_Y);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(memo_blocks(logits), out->n);
+  const dim3 grid(loss_blocks(logits), out->n);
   if (!turned) {
     if (softmax)
       hipLaunchKernelGGL(memo_ensemble_categorical_kernel<false>, grid, dim3(256), 0, s, tv(logits), tv(out), mv);
@@ -698,7 +652,7 @@ extern "C" int mmtta_memo_ensemble(const mmtta_tensor* logits, int softmax, int 
       hipLaunchKernelGGL(memo_ensemble_bernoulli_kernel<false>, grid, dim3(256), 0, s, tv(logits), tv(out), mv);
   } else if (softmax) {
     hipLaunchKernelGGL(memo_ensemble_categorical_kernel<true>, grid, dim3(256), 0, s, tv(logits), tv(out), mv);
-  } else if (logits->c <= 4 && memo_dense16(logits) && memo_dense16(out) && ((out->flags & MMTTA_TENSOR_OWNS_PAD) || out->c == 4)) {
+  } else if (logits->c <= 4 && loss_dense16(logits) && loss_dense16(out) && ((out->flags & MMTTA_TENSOR_OWNS_PAD) || out->c == 4)) {
     // the tiled gather (views >= 2 here: view 0 is never transposed)
     const float* zp = (const float*)logits->ptr;
     float* op = (float*)out->ptr;
@@ -729,8 +683,8 @@ extern "C" int mmtta_mirror_views(const mmtta_tensor* x, const mmtta_tensor* y, 
   };
   MMTTA_CHECK(dense(x) && dense(y) && x->sw == y->sw, MMTTA_ERR_UNSUPPORTED, "mirror views: dense channels-last rows of one width");
   MMTTA_CHECK(y->sw == y->c || (y->flags & MMTTA_TENSOR_OWNS_PAD), MMTTA_ERR_UNSUPPORTED, "mirror views: `y` must own the pad lanes of its rows");
-  MMTTA_CHECK(memo_small_item(x), MMTTA_ERR_UNSUPPORTED, "mirror views: an item of 2^31 elements or more");
-  MMTTA_CHECK(y->n <= MEMO_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "mirror views: more than %d output items in one call", MEMO_MAX_GRID_Y);
+  MMTTA_CHECK(loss_small_item(x), MMTTA_ERR_UNSUPPORTED, "mirror views: an item of 2^31 elements or more");
+  MMTTA_CHECK(y->n <= LOSS_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "mirror views: more than %d output items in one call", LOSS_MAX_GRID_Y);
   const long long esz = x->dtype == MMTTA_BF16 ? 2 : 4;
   const long long row = x->sw * esz;
   const uintptr_t both = (uintptr_t)x->ptr | (uintptr_t)y->ptr | (uintptr_t)(x->sn * esz) | (uintptr_t)(y->sn * esz) | (uintptr_t)row;

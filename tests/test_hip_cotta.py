@@ -4,6 +4,7 @@ the oracle networks (deep-copied teacher, flipped views, the same restore mask m
 bitwise properties (graph replay = eager, grouped = one volume at a time, the returned logits = a plain eval forward of
 the adapted replica)."""
 import copy
+import functools
 
 import numpy as np
 import pytest
@@ -11,7 +12,8 @@ import torch
 import torch.nn.functional as F
 
 from test_cotta_host import restore_mask
-from test_hip_memo import BATCH, CLAMP, HEADS, SATURATED, grad_buffer, marginal_log, memo_views, stage
+from test_hip_memo import (BATCH, CLAMP, HEADS, SATURATED, SECOND_TRIP, check_second_trip, grad_buffer, marginal_log, memo_views,
+                           second_trip_logits, stage)
 from test_hip_tta import SMALL, build_pair, root_cfg, volume
 
 pytestmark = pytest.mark.gpu
@@ -80,6 +82,23 @@ def test_consistency_loss_matches_float64(softmax, R, generic, G):
     z = torch.randn((G, R, 5, 6, 7), generator=gen) * 3.0
     t = make_target(torch.randn((G, R, 5, 6, 7), generator=gen) * 3.0, softmax)
     check_loss(z, t, softmax, generic)
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_consistency_reference(softmax):
+    t = make_target(second_trip_logits(83), softmax)
+    return (t,) + loss_reference(second_trip_logits(82), t, softmax)
+
+
+@pytest.mark.parametrize("softmax,generic,dtype", SECOND_TRIP)
+def test_consistency_loss_on_the_second_trip_of_the_walk(softmax, generic, dtype):
+    """test_consistency_loss_matches_float64 at test_hip_memo.SECOND_TRIP_SHAPE: more voxels than one launch has threads, two
+    items."""
+    t, l_ref, g_ref = second_trip_consistency_reference(softmax)
+    z_cl, t_cl = stage(second_trip_logits(82), generic), stage(t, generic)
+    loss, g = run_loss(z_cl, t_cl, softmax, dtype)
+    g32 = run_loss(z_cl, t_cl, softmax, torch.float32)[1] if dtype != torch.float32 else g
+    check_second_trip(loss, g, g32, l_ref, g_ref, dtype)
 
 
 @pytest.mark.parametrize("softmax,R,generic", HEADS)

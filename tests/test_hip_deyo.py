@@ -9,13 +9,14 @@ z = f(x), z''(v) = z' where the content of voxel v went, PLPD = p(z)[y^] - p(z''
 Inputs of the kernel tests are seeded so that no element lies within 1e-5 of either threshold in float64 (the rule DESIGN.md
 section 6 applies to the ReLU threshold): masks and counts must then agree exactly."""
 import copy
+import functools
 import math
 
 import pytest
 import torch
 
 from test_hip_eata import HEADS, SATURATED, masks_of
-from test_hip_sar import BATCH, entropy_elements, grad_buffer, keep_cl, run_filtered, stage
+from test_hip_sar import BATCH, SECOND_TRIP, SECOND_TRIP_SHAPE, entropy_elements, grad_buffer, keep_cl, run_filtered, stage
 from test_hip_tta import SMALL, build_pair, root_cfg, volume
 
 pytestmark = pytest.mark.gpu
@@ -227,6 +228,51 @@ def test_deyo_loss_matches_float64_and_the_filtered_count(softmax, R, generic, N
             want = fp32.to(torch.bfloat16).float()          # the fp32 result rounded, to 1 ulp of bf16 (2^-7 relative)
             assert ((g - want).abs() <= 2.0 ** -7 * want.abs()).all()
         assert torch.all(g[~(m_ref.unsqueeze(1).expand_as(g) if softmax else m_ref)] == 0)
+
+
+SECOND_TRIP_GRID = [3, 1, 1]          # of the 81^3 logits of test_hip_sar.SECOND_TRIP_SHAPE
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_case(softmax):
+    """kernel_case at SECOND_TRIP_SHAPE, and the float64 reference."""
+    gen = torch.Generator().manual_seed(81)
+    lnk = math.log(3 if softmax else 2.0)
+    margin, margin0 = E_MARGIN * lnk, E_MARGIN0 * lnk
+    perms = random_perms(SECOND_TRIP_SHAPE[0], 3, gen)
+    z = torch.randn(SECOND_TRIP_SHAPE, generator=gen) * 3.0
+    zs = torch.randn(SECOND_TRIP_SHAPE, generator=gen) * 3.0
+    z = away_from_thresholds(z, zs, SECOND_TRIP_GRID, perms, margin, THRESHOLD, softmax, gen)
+    return (z, zs, perms, margin, margin0) + deyo_kernel_reference(z, zs, SECOND_TRIP_GRID, perms, margin, margin0, THRESHOLD, softmax)
+
+
+@pytest.mark.parametrize("softmax,generic,dtype", SECOND_TRIP)
+def test_deyo_loss_on_the_second_trip_of_the_walk(softmax, generic, dtype):
+    """test_deyo_loss_matches_float64_and_the_filtered_count at test_hip_sar.SECOND_TRIP_SHAPE: more voxels than one launch has
+    threads, two items, three patches along D."""
+    z, zs, perms, margin, margin0, l_ref, k_ref, k1_ref, m_ref, g_ref = second_trip_case(softmax)
+    elems = float(m_ref.numel())
+    share1, share = sum(k1_ref) / elems, sum(k_ref) / elems
+    print(f"entropy-kept share {share1:.3f}, final share {share:.3f}, removed by PLPD {share1 - share:.3f}")
+    assert 0.2 <= share1 <= 0.8 and share >= 0.2 and share1 - share >= 0.05, "the filters are not exercised"
+    z_cl, zs_cl, table = stage(z, generic), stage(zs, generic), device_table(perms)
+    _, f_kept, f_keep, _ = run_filtered(z_cl, margin, softmax)
+    loss, kept, kept_entropy, keep, g = run_deyo(z_cl, zs_cl, SECOND_TRIP_GRID, table, margin, margin0, THRESHOLD, softmax, dtype=dtype)
+    assert torch.equal(keep, keep_cl(m_ref, softmax)), "keep masks differ from float64"
+    assert kept.tolist() == k_ref and kept_entropy.tolist() == k1_ref
+    assert torch.equal(kept_entropy, f_kept), "kept_entropy differs from mmtta_entropy_filtered_items' kept"
+    assert not torch.any(keep.bool() & ~f_keep.bool()), "an element was kept that the entropy filter drops"
+    for a, b in zip(loss.tolist(), l_ref):
+        print(f"loss {a} vs {b}")
+        assert abs(a - b) <= 1e-5 * abs(b), (a, b)
+    if dtype == torch.float32:
+        err = (g.double() - g_ref).abs().max().item() / g_ref.abs().max().item()
+        print(f"gradient error {err:.2e} of the maximum")
+        assert err <= 2e-5
+    else:
+        want = run_deyo(z_cl, zs_cl, SECOND_TRIP_GRID, table, margin, margin0, THRESHOLD, softmax)[4].to(torch.bfloat16).float()
+        assert ((g - want).abs() <= 2.0 ** -7 * want.abs()).all()
+    assert torch.all(g[~(m_ref.unsqueeze(1).expand_as(g) if softmax else m_ref)] == 0)
 
 
 @pytest.mark.parametrize("softmax,R,generic,dtype", [(False, 3, False, torch.float32), (False, 3, False, torch.bfloat16),

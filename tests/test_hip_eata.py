@@ -6,13 +6,15 @@ eager, lambda = 0, the continual run).
 Inputs of the kernel tests are seeded so that no element's entropy lies within 1e-5 of the margin (the rule DESIGN.md section
 6 applies to the ReLU threshold): the keep masks must then agree exactly."""
 import copy
+import functools
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from test_hip_sar import BATCH, away_from_margin, entropy_elements, grad_buffer, keep_cl, run_filtered, stage
+from test_hip_sar import (BATCH, SECOND_TRIP, away_from_margin, entropy_elements, grad_buffer, keep_cl, run_filtered,
+                          second_trip_logits, stage)
 from test_hip_tta import SMALL, build_pair, root_cfg, volume
 
 pytestmark = pytest.mark.gpu
@@ -96,6 +98,41 @@ def test_weighted_entropy_matches_float64_and_the_filtered_mask(softmax, R, gene
     assert all(a > b for a, b in zip(loss.tolist(), f_loss.tolist()))
 
 
+@functools.lru_cache(maxsize=None)
+def second_trip_weighted_reference(softmax):
+    z, margin = second_trip_logits(softmax)
+    return weighted_reference(z, margin, softmax)
+
+
+@pytest.mark.parametrize("softmax,generic,dtype", SECOND_TRIP)
+def test_weighted_entropy_on_the_second_trip_of_the_walk(softmax, generic, dtype):
+    """test_weighted_entropy_matches_float64_and_the_filtered_mask at test_hip_sar.SECOND_TRIP_SHAPE: more voxels than one
+    launch has threads, two items."""
+    z, margin = second_trip_logits(softmax)
+    l_ref, k_ref, m_ref, g_ref = second_trip_weighted_reference(softmax)
+    share = sum(k_ref) / float(m_ref.numel())
+    print(f"kept share {share:.3f}")
+    assert 0.2 <= share <= 0.8, "the filter is not exercised"
+    z_cl = stage(z, generic)
+    f_loss, f_kept, f_keep, _ = run_filtered(z_cl, margin, softmax)
+    loss, kept, keep, g = run_weighted(z_cl, margin, softmax, dtype=dtype)
+    assert torch.equal(keep, keep_cl(m_ref, softmax)), "keep masks differ from float64"
+    assert kept.tolist() == k_ref
+    assert torch.equal(keep, f_keep) and torch.equal(kept, f_kept), "mask / count differ from mmtta_entropy_filtered_items"
+    for a, b in zip(loss.tolist(), l_ref):
+        print(f"loss {a} vs {b}")
+        assert abs(a - b) <= 1e-5 * abs(b), (a, b)
+    if dtype == torch.float32:
+        err = (g.double() - g_ref).abs().max().item() / g_ref.abs().max().item()
+        print(f"gradient error {err:.2e} of the maximum")
+        assert err <= 2e-5
+    else:
+        want = run_weighted(z_cl, margin, softmax)[3].to(torch.bfloat16).float()          # the fp32 result rounded
+        assert ((g - want).abs() <= 2.0 ** -7 * want.abs()).all()
+    assert torch.all(g[~(m_ref.unsqueeze(1).expand_as(g) if softmax else m_ref)] == 0)
+    assert all(a > b for a, b in zip(loss.tolist(), f_loss.tolist()))
+
+
 @pytest.mark.parametrize("softmax,R,generic,dtype", [(False, 3, False, torch.float32), (False, 3, False, torch.bfloat16),
                                                      (False, 3, True, torch.float32), (True, 4, False, torch.float32)])
 def test_weighted_n_items_equal_n_single_item_calls(softmax, R, generic, dtype):
@@ -173,6 +210,32 @@ def test_pseudo_label_loss_matches_float64(softmax, R, generic, N):
         want = g.to(torch.bfloat16).float()
         assert ((g16 - want).abs() <= 2.0 ** -7 * want.abs()).all()
     for n in range(N):          # N items = N calls, bit for bit
+        l1, g1 = run_pseudo(stage(z[n:n + 1], generic), softmax)
+        assert torch.equal(l1, loss[n:n + 1]) and torch.equal(g1, g[n:n + 1])
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_pseudo_reference(softmax):
+    return pseudo_reference(second_trip_logits(softmax)[0], softmax)
+
+
+@pytest.mark.parametrize("softmax,generic,dtype", SECOND_TRIP)
+def test_pseudo_label_loss_on_the_second_trip_of_the_walk(softmax, generic, dtype):
+    """test_pseudo_label_loss_matches_float64 at test_hip_sar.SECOND_TRIP_SHAPE."""
+    z = second_trip_logits(softmax)[0]
+    l_ref, g_ref = second_trip_pseudo_reference(softmax)
+    z_cl = stage(z, generic)
+    loss, g = run_pseudo(z_cl, softmax)
+    print(f"loss {loss.tolist()} vs {l_ref.tolist()}")
+    assert ((loss.double() - l_ref).abs() <= 1e-5 * l_ref.abs()).all(), (loss, l_ref)
+    err = (g.double() - g_ref).abs().max().item() / g_ref.abs().max().item()
+    print(f"gradient error {err:.2e} of the maximum")
+    assert err <= 2e-5
+    if dtype == torch.bfloat16:
+        l16, g16 = run_pseudo(z_cl, softmax, dtype=dtype)
+        want = g.to(torch.bfloat16).float()
+        assert torch.equal(l16, loss) and ((g16 - want).abs() <= 2.0 ** -7 * want.abs()).all()
+    for n in range(z.shape[0]):          # N items = N calls, bit for bit
         l1, g1 = run_pseudo(stage(z[n:n + 1], generic), softmax)
         assert torch.equal(l1, loss[n:n + 1]) and torch.equal(g1, g[n:n + 1])
 

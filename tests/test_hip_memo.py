@@ -3,6 +3,7 @@ and the ensemble against float64 torch restatements (autograd over flipped views
 MEMO restatement on the oracle networks, and the bitwise properties (no mirror axes = Tent, grouped = one volume at a
 time, graph replay = eager, the returned logits = a plain eval forward of the adapted replica)."""
 import copy
+import functools
 import math
 
 import pytest
@@ -141,6 +142,54 @@ def test_memo_loss_matches_float64(softmax, R, generic, V, G):
     gen = torch.Generator().manual_seed(200 + 7 * R + V + G)
     z = torch.randn((G * V, R, 5, 6, 7), generator=gen) * 3.0          # independent logits per view
     check_loss(z, masks_for(V), softmax, generic)
+
+
+# The second trip of the voxel walk: the loss kernels launch at most 2048 workgroups of 256 threads per volume and walk the
+# rest in a grid-stride loop; 81^3 is the smallest cube (H == W) with more voxels (531 441) than that (524 288), so the
+# thread-per-voxel kernels take a ragged second trip of 7 153 voxels and the generic Bernoulli kernel four trips at R = 3.
+# (softmax, generic, dtype): the Bernoulli fast path with fp32 and bf16 gradients, the generic kernel, the categorical head.
+SECOND_TRIP_SHAPE = (2, 3, 81, 81, 81)
+SECOND_TRIP = [pytest.param(False, False, torch.float32, id="bernoulli-fast-fp32"),
+               pytest.param(False, False, torch.bfloat16, id="bernoulli-fast-bf16"),
+               pytest.param(False, True, torch.float32, id="bernoulli-generic"),
+               pytest.param(True, False, torch.float32, id="categorical")]
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_logits(seed):
+    return torch.randn(SECOND_TRIP_SHAPE, generator=torch.Generator().manual_seed(seed)) * 3.0
+
+
+@functools.lru_cache(maxsize=None)
+def second_trip_memo_reference(softmax):
+    return loss_reference(second_trip_logits(81), masks_for(2), softmax)
+
+
+def check_second_trip(loss, g, g32, l_ref, g_ref, dtype):
+    """check_loss's bounds: loss 1e-5 relative, the fp32 gradient 2e-5 of its maximum, a bf16 gradient the rounded fp32 one."""
+    assert torch.isfinite(loss).all() and torch.isfinite(g).all()
+    for a, b in zip(loss.tolist(), l_ref.tolist()):
+        print(f"{dtype}: loss {a} vs {b}")
+        assert abs(a - b) <= 1e-5 * abs(b), (a, b)
+    if dtype == torch.float32:
+        err = (g.double() - g_ref).abs().max().item() / g_ref.abs().max().item()
+        print(f"gradient error {err:.2e} of the maximum")
+        assert err <= 2e-5
+    else:
+        want = g32.to(torch.bfloat16).float()
+        assert ((g - want).abs() <= want.abs() * 2.0 ** -7).all()
+
+
+@pytest.mark.parametrize("softmax,generic,dtype", SECOND_TRIP)
+def test_memo_loss_on_the_second_trip_of_the_walk(softmax, generic, dtype):
+    """test_memo_loss_matches_float64 at SECOND_TRIP_SHAPE: the two items are the V = 2 views (the second mirrored along D)
+    of one volume."""
+    masks = masks_for(2)
+    l_ref, g_ref = second_trip_memo_reference(softmax)
+    z_cl = stage(second_trip_logits(81), generic)
+    loss, g = run_loss(z_cl, masks, softmax, dtype)
+    g32 = run_loss(z_cl, masks, softmax, torch.float32)[1] if dtype != torch.float32 else g
+    check_second_trip(loss, g, g32, l_ref, g_ref, dtype)
 
 
 @pytest.mark.parametrize("softmax,R,generic", HEADS)
