@@ -650,6 +650,49 @@ int mmtta_cotta_update_sets(float* w, float* teacher, const float* source, int64
                             int64_t teacher_stride, double alpha, float restore_p, uint64_t seed, const int32_t* step,
                             const int32_t* ordinals, int64_t* partial, int64_t* restored, void* stream);
 
+/* ---- PETAL (Brahma & Rai, CVPR 2023): the restore of CoTTA's pass above, ranked by the step's own gradient - csrc/petal.hip.
+ * The magnitude key of a gradient element is key(g) = bits(g) & 0x7fffffff, an unsigned integer: a total order over zeros
+ * (+0 == -0), denormals, infinities and NaNs (above the infinities) that no float comparison mode changes.
+ *
+ * The segment table: a DEVICE int64 array of [count][3] rows (start, length, rank), relative to a parameter set, followed by
+ *   [count + 1] running chunk counts (entry r = the sum of mmtta_magnitude_select_chunks(length) over the rows before r).  Rows
+ *   are ascending and disjoint; start is a multiple of 4, length >= 1 is anything, 0 <= rank < length.  `table_host` is the
+ *   HOST copy of the same array, read at launch for the argument checks.
+ *
+ * mmtta_magnitude_select_sets: gamma_out[s][r] (uint32 [sets][count]) = the rank-th smallest key (0-based, an element's own
+ *   bits) among g[s * set_stride + start .. + length) of row r.  A radix select over the 31 key bits in digits of 11 / 10 /
+ *   10 bits.  Rows of class 0 (mmtta_magnitude_select_class(length) == 0) are selected by one workgroup with their keys in
+ *   LDS; rows of class 1 are cut into chunks, one workgroup each: per digit an LDS histogram, its non-empty bins added to
+ *   the row's global table with integer atomics, and a launch that picks the bin and clears the table.  One launch for a
+ *   table without class-1 rows, seven otherwise - whatever the data and `sets`; no host read-back; integer sums only, so the
+ *   result does not depend on scheduling.  scratch: mmtta_magnitude_select_scratch_bytes(count, sets) bytes, contents
+ *   arbitrary (prepared by the first launch).
+ *
+ * mmtta_petal_update_sets: ONE pass over the first n elements of each of `sets` parameter sets:
+ *     teacher <- a teacher + b w      exactly mmtta_cotta_update_sets' arithmetic (alpha == 1 leaves the teacher's bits)
+ *     w_i <- source_i (the source BITS) where i lies in a row r and key(g_i) < gamma[s][r]; else unchanged
+ *   Elements whose key equals the threshold stay, so a row with an all-zero gradient restores nothing; elements of no row
+ *   (alignment padding) are never restored.  restored[s] (int64) = the number of restored elements of set s, summed from
+ *   int64 block partials in a fixed order.  16-byte accesses, the last elements of a ragged n one by one; a workgroup finds
+ *   the rows of its elements by two searches of the table and keeps them in LDS.
+ *   partial  int64 [mmtta_petal_update_partials(n, sets)] scratch
+ *
+ * Bad arguments (null pointers, sets < 1, strides that are no multiples of 4 or below n - for the select: below the end of the
+ * last row -, rows out of order, overlapping or behind n, a start that is no multiple of 4, length < 1, rank outside [0, length),
+ * chunk counts that do not match the rows, alpha outside [0, 1]) are MMTTA_ERR_INVALID; more than 2^20 rows, 65535 sets, a row
+ * of 2^31 elements or more and misaligned buffers MMTTA_ERR_UNSUPPORTED; both before anything is launched.  Sets beyond
+ * `sets` and elements beyond n are not written. */
+int mmtta_magnitude_select_class(int64_t length);          /* 0: one workgroup, 1: chunked; -1: length < 1 */
+int64_t mmtta_magnitude_select_chunks(int64_t length);     /* chunks of a row (0 for class 0) */
+int64_t mmtta_magnitude_select_scratch_bytes(int count, int sets);
+int mmtta_magnitude_select_sets(const float* g, const int64_t* table, const int64_t* table_host, int count, int sets,
+                                int64_t set_stride, uint32_t* gamma_out, void* scratch, void* stream);
+int64_t mmtta_petal_update_partials(int64_t n, int sets);
+int mmtta_petal_update_sets(float* w, float* teacher, const float* source, const float* g, const uint32_t* gamma,
+                            const int64_t* table, const int64_t* table_host, int count, int64_t n, int sets,
+                            int64_t w_stride, int64_t teacher_stride, int64_t g_stride, double alpha, int64_t* partial,
+                            int64_t* restored, void* stream);
+
 /* ---- Intensity-augmented views of the staged input - csrc/augment.hip.  The views of MEMO and CoTTA above, each with a
  * pointwise intensity transform on top of its mirror: a batch of G volumes x V views is [G * V, D, H, W, C] as for
  * mmtta_mirror_views (`views`, `view_axes` and their rules are that entry point's; masks may repeat and may all be 0).

@@ -182,6 +182,15 @@ _SIGNATURES = {
     "mmtta_cotta_update_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64,
                                           C.c_double, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "mmtta_magnitude_select_class": (C.c_int, [C.c_int64]),
+    "mmtta_magnitude_select_chunks": (C.c_int64, [C.c_int64]),
+    "mmtta_magnitude_select_scratch_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "mmtta_magnitude_select_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "mmtta_petal_update_partials": (C.c_int64, [C.c_int64, C.c_int]),
+    "mmtta_petal_update_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "mmtta_intensity_range_partials": (C.c_int64, [_P(Tensor)]),
     "mmtta_intensity_range": (C.c_int, [_P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_augment_views": (C.c_int, [_P(Tensor), _P(Tensor), C.c_int, _P(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p,

@@ -62,27 +62,29 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
     ``restore_p`` (default 0.01) and ``seed`` (default 0); the optimizer is ``training.optimizer`` exactly as for
     ``entmin_tta``."""
     fused_update = False     # one gradient for the whole span, then the teacher / restore pass over it
+    block = "cotta"          # the ``method.<block>`` mapping the keys are read from (a subclass reads its own)
 
     def __init__(self, config: Any = None):
         super().__init__(config)
         m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "cotta", {}) or {}
-        self.mirror_axes = parse_mirror_axes(get_config(s, "mirror_axes", ["h", "w"]), "method.cotta.mirror_axes")
-        self.rot90 = parse_rot90(get_config(s, "rot90", None), "method.cotta.rot90")
-        self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, "method.cotta.intensity", self.rot90)
+        s = get_config(m, self.block, {}) or {}
+        key = f"method.{self.block}"
+        self.mirror_axes = parse_mirror_axes(get_config(s, "mirror_axes", ["h", "w"]), f"{key}.mirror_axes")
+        self.rot90 = parse_rot90(get_config(s, "rot90", None), f"{key}.rot90")
+        self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, f"{key}.intensity", self.rot90)
         # ({identity} + the quarter turns) x the mirror group, ``intensity.copies`` times over
         self.view_axes = self.intensity.view_axes
         self.views = len(self.view_axes)
         alpha, p, seed = get_config(s, "alpha", 0.999), get_config(s, "restore_p", 0.01), get_config(s, "seed", 0)
         if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not (0.0 <= float(alpha) <= 1.0):
-            raise ValueError(f"method.cotta.alpha = {alpha!r}: expected a teacher momentum with 0 <= alpha <= 1")
+            raise ValueError(f"{key}.alpha = {alpha!r}: expected a teacher momentum with 0 <= alpha <= 1")
         if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0):
-            raise ValueError(f"method.cotta.restore_p = {p!r}: expected a probability with 0 <= p < 1")
+            raise ValueError(f"{key}.restore_p = {p!r}: expected a probability with 0 <= p < 1")
         if isinstance(seed, bool) or not isinstance(seed, int) or not (0 <= seed < 1 << 64):
-            raise ValueError(f"method.cotta.seed = {seed!r}: expected an integer with 0 <= seed < 2^64")
+            raise ValueError(f"{key}.seed = {seed!r}: expected an integer with 0 <= seed < 2^64")
         self.alpha, self.restore_p, self.seed = float(alpha), float(p), int(seed)
         if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
-            raise NotImplementedError("method.moddrop.enabled: true is not supported by cotta_tta (one modality mask per step "
+            raise NotImplementedError(f"method.moddrop.enabled: true is not supported by {self.block}_tta (one modality mask per step "
                                       "for the teacher's views and the student is not defined yet)")
         self.teacher: Optional[torch.Tensor] = None          # [replicas, n_train] fp32
 
@@ -91,7 +93,7 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         rt, ar = self.rt, self.rt.arena
         if rt.buffers:
             raise NotImplementedError(
-                f"cotta_tta: model.norm = {get_config(get_config(self.cfg, 'model', {}) or {}, 'norm', 'BATCH')!r} keeps running "
+                f"{self.block}_tta: model.norm = {get_config(get_config(self.cfg, 'model', {}) or {}, 'norm', 'BATCH')!r} keeps running "
                 "statistics, which the teacher's train-mode forward would move (running_mean, running_var, "
                 "num_batches_tracked belong to the student); use a model.norm without them (INSTANCE, GROUP)")
         self.teacher = torch.empty((ar.replicas, ar.n_train), dtype=torch.float32, device=ar.device)
@@ -138,12 +140,18 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         ops.consistency_loss_items(logits, target, dlogits, partial, loss, softmax=self.softmax)
         restored = rt.pool.flat("cotta_restored", ar.replicas, dtype=torch.int64, zero=True)
         if nt > 0:
-            # 4. - 6. backward, the optimizer (it advances the step counter), teacher EMA + stochastic restore
+            # 4. - 6. backward, the optimizer (it advances the step counter), teacher EMA + restore
             rt.run_backward(dlogits)
             self.optimizer_step(B)
-            upd = rt.pool.flat("cotta_upd_partial", ops.cotta_update_partials(nt, sets), dtype=torch.int64)
-            ops.cotta_update_sets(ar.params_all, self.teacher, ar.source, nt, sets, self.alpha, self.restore_p, self.seed,
-                                  ar.step, self._ordinals, upd, restored)
+            self._after_step(sets, restored)
+
+    def _after_step(self, sets: int, restored: torch.Tensor) -> None:
+        """The pass after the optimizer step over the first ``sets`` replicas: teacher EMA + stochastic restore."""
+        rt, ar = self.rt, self.rt.arena
+        nt = ar.n_train
+        upd = rt.pool.flat("cotta_upd_partial", ops.cotta_update_partials(nt, sets), dtype=torch.int64)
+        ops.cotta_update_sets(ar.params_all, self.teacher, ar.source, nt, sets, self.alpha, self.restore_p, self.seed,
+                              ar.step, self._ordinals, upd, restored)
 
     # ------------------------------------------------------------------ per volume
     def _reset(self) -> None:
@@ -151,7 +159,7 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         self.reset_teacher()
 
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
-        check_square(self.view_axes, int(x_cl.shape[2]), int(x_cl.shape[3]), "method.cotta.rot90")
+        check_square(self.view_axes, int(x_cl.shape[2]), int(x_cl.shape[3]), f"method.{self.block}.rot90")
         self.rt.views = self.views
         if self.intensity.active and self.views > 1:
             present = modality_mask(int(x_cl.shape[-1]), self.missing, 0.0, None)

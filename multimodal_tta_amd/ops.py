@@ -966,6 +966,82 @@ def cotta_update_sets(w: torch.Tensor, teacher: torch.Tensor, source: torch.Tens
                                               ptr(restored), stream_ptr()), "cotta_update_sets")
 
 
+def magnitude_select_class(length: int) -> int:
+    """Which kernel of magnitude_select_sets serves a row of ``length`` elements: 0 one workgroup, 1 chunked."""
+    return int(_lib.load().mmtta_magnitude_select_class(int(length)))
+
+
+@dataclass
+class RankTable:
+    """The segment table of magnitude_select_sets / petal_update_sets: ``rows`` (start, length, rank), its device array
+    ([count][3] then the [count + 1] running chunk counts) and the host copy the argument checks read."""
+    rows: List[Tuple[int, int, int]]
+    device: torch.Tensor
+    host: torch.Tensor
+
+    @property
+    def count(self) -> int:
+        return len(self.rows)
+
+
+def rank_segments_table(rows: Sequence[Tuple[int, int, int]], device) -> RankTable:
+    lib = _lib.load()
+    flat, cum = [], [0]
+    for start, length, rank in rows:
+        flat += [int(start), int(length), int(rank)]
+        cum.append(cum[-1] + max(0, int(lib.mmtta_magnitude_select_chunks(int(length)))))
+    host = torch.tensor(flat + cum, dtype=torch.int64)
+    return RankTable([tuple(int(v) for v in r) for r in rows], host.to(device), host)
+
+
+def magnitude_select_scratch(table: RankTable, sets: int) -> int:
+    """int32 elements of magnitude_select_sets' scratch."""
+    nbytes = int(_lib.load().mmtta_magnitude_select_scratch_bytes(int(table.count), int(sets)))
+    if nbytes < 0:
+        check(-1, "magnitude_select_scratch_bytes")
+    return nbytes // 4
+
+
+def magnitude_select_sets(g: torch.Tensor, table: RankTable, sets: int, gamma: torch.Tensor, scratch: torch.Tensor) -> None:
+    """gamma[s, r] (int32 [>= sets, count]: the uint32 bits) = the rank-th smallest magnitude key (bits & 0x7fffffff) of row
+    r of ``table`` in row s of ``g`` (fp32 [>= sets, width])."""
+    if g.dtype != torch.float32 or not g.is_contiguous() or g.dim() != 2 or g.shape[0] < sets:
+        raise MmttaError(f"magnitude_select_sets: g must be contiguous fp32 [>= {sets}, width], got {tuple(g.shape)}")
+    if gamma.dtype != torch.int32 or not gamma.is_contiguous() or gamma.dim() != 2 or gamma.shape[0] < sets or gamma.shape[1] != table.count:
+        raise MmttaError(f"magnitude_select_sets: gamma must be contiguous int32 [>= {sets}, {table.count}]")
+    if scratch.dtype != torch.int32 or scratch.numel() < magnitude_select_scratch(table, sets):
+        raise MmttaError("magnitude_select_sets: scratch must be int32 of magnitude_select_scratch(table, sets) elements")
+    check(_lib.load().mmtta_magnitude_select_sets(ptr(g), ptr(table.device), ptr(table.host), table.count, int(sets),
+                                                  int(g.shape[1]), ptr(gamma), ptr(scratch), stream_ptr()), "magnitude_select_sets")
+
+
+def petal_update_partials(n: int, sets: int) -> int:
+    return int(_lib.load().mmtta_petal_update_partials(int(n), int(sets)))
+
+
+def petal_update_sets(w: torch.Tensor, teacher: torch.Tensor, source: torch.Tensor, g: torch.Tensor, gamma: torch.Tensor,
+                      table: RankTable, n: int, sets: int, alpha: float, partial: torch.Tensor, restored: torch.Tensor) -> None:
+    """PETAL's pass after the student's optimizer step over the first ``sets`` rows of ``w`` / ``teacher`` / ``g`` ([rows, >= n]
+    fp32) and the shared ``source``: teacher = alpha teacher + (1 - alpha) w (cotta_update_sets' arithmetic), then w[i] =
+    source[i] where i lies in row r of ``table`` and the magnitude key of g[i] is below gamma[s, r].  ``restored``: int64
+    [>= sets], the restored elements per row."""
+    for name, t in (("w", w), ("teacher", teacher), ("g", g)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[0] < sets or t.shape[1] < n:
+            raise MmttaError(f"petal_update_sets: {name} must be contiguous fp32 [>= {sets}, >= {n}], got {tuple(t.shape)}")
+    if source.dtype != torch.float32 or not source.is_contiguous() or source.numel() < n:
+        raise MmttaError(f"petal_update_sets: source must be contiguous fp32 of at least {n} elements")
+    if gamma.dtype != torch.int32 or not gamma.is_contiguous() or gamma.dim() != 2 or gamma.shape[0] < sets or gamma.shape[1] != table.count:
+        raise MmttaError(f"petal_update_sets: gamma must be contiguous int32 [>= {sets}, {table.count}]")
+    if restored.dtype != torch.int64 or restored.numel() < sets:
+        raise MmttaError("petal_update_sets: one int64 count per set")
+    if partial.dtype != torch.int64 or partial.numel() < petal_update_partials(n, sets):
+        raise MmttaError("petal_update_sets: partial must be int64 of petal_update_partials(n, sets) elements")
+    check(_lib.load().mmtta_petal_update_sets(ptr(w), ptr(teacher), ptr(source), ptr(g), ptr(gamma), ptr(table.device),
+                                              ptr(table.host), table.count, int(n), int(sets), int(w.shape[1]),
+                                              int(teacher.shape[1]), int(g.shape[1]), float(alpha), ptr(partial), ptr(restored),
+                                              stream_ptr()), "petal_update_sets")
+
+
 def entropy_weighted_partials(logits: torch.Tensor) -> int:
     t = desc_cl(logits)
     return int(_lib.load().mmtta_entropy_weighted_partials(C.byref(t)))
