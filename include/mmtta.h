@@ -1133,6 +1133,66 @@ int64_t mmtta_surface_scratch_bytes(int64_t n_masks, int64_t d, int64_t h, int64
 int mmtta_surface_distances(const uint8_t* pred_mask, const mmtta_tensor* label, const double* spacing,
                             double percentile, int asd_symmetric, float* hd, float* asd, void* scratch, void* stream);
 
+/* Normalised surface Dice (NSD) of the evaluation tail per (volume, region): the share of each surface that lies within a
+ * tolerance of the other one.  MONAI's SurfaceDiceMetric on the edges of mmtta_surface_distances (voxel counts, not
+ * Nikolov's surface-element areas):
+ *   edge(X)   X & ~erode6(X), outside the volume counts as background
+ *   d(v, u)   (float)sqrt(d2), d2 in fp64 as fma(dz sd, dz sd, fma(dy sh, dy sh, (dx sw)^2)) of the offset (dz, dy, dx)
+ *   hit       a voxel v of edge(A) against B at tolerance tau: some u of edge(B) has d(v, u) <= (float)tau
+ *   NSD_tau   (hits(edge P -> edge G) + hits(edge G -> edge P)) / (|edge P| + |edge G|), host arithmetic on the counts;
+ *             valid iff the ground truth is non-empty, like Dice (then |edge G| >= 1; an empty prediction scores 0)
+ * No distance transform: a bounded search over bit-packed edge masks.  Per axis a the window radius is r_a = the largest
+ * k >= 0 with (float)sqrt((k s_a)^2) <= (float)max(tolerances), found by a loop on the host, so the window holds every
+ * offset that can be a hit; r_a <= 8 on every axis, a larger window is refused (mmtta_surface_distances is the tool for
+ * large distances).  Cost: linear in the volume, independent of the size of the surfaces.
+ *   pred_mask    uint8 [N,R,D,H,W] dense on the device (non-zero = foreground)
+ *   label        fp32 any strides, ground truth = label > 0.5
+ *   spacing      HOST, 3 doubles in D, H, W order, read before return, positive and finite
+ *   tolerances   HOST, n_tolerances doubles (1 ... 4), read before return, each finite and >= 0, in the units of `spacing`
+ *   counts       int64 [N*R][n_tolerances][4] on the device, zeroed by this call: hits edge P -> edge G, |edge P|,
+ *                hits edge G -> edge P, |edge G|
+ *   scratch      mmtta_surface_dice_scratch_bytes(N*R, D, H, W) bytes (negative: an extent above 1024 or more than 65535 masks)
+ * Two launches on `stream` that depend on the shape alone.  Integer counts only: two calls agree bit for bit and a batch
+ * gives what its items give alone.  Anything else - a null argument, 0 or more than 4 tolerances, a negative or non-finite
+ * tolerance, a spacing that is not positive and finite, a window above 8, a label that is not fp32 - is refused with
+ * MMTTA_ERR_INVALID / _UNSUPPORTED and a message naming the argument, before anything is queued. */
+int64_t mmtta_surface_dice_scratch_bytes(int64_t n_masks, int64_t d, int64_t h, int64_t w);
+int mmtta_surface_dice(const uint8_t* pred_mask, const mmtta_tensor* label, const double* spacing, const double* tolerances,
+                       int n_tolerances, int64_t* counts, void* scratch, void* stream);
+
+/* Lesion-wise NSD of the evaluation tail (with lesion-wise Dice the BraTS-2024 pair).  Runs right behind
+ * mmtta_lesionwise_scores on the same stream and only reads what that call left in its scratch: nothing is labelled twice.
+ * Lesions, own voxels, kept / found, matching and false-positive components are exactly those of mmtta_lesionwise_scores.
+ * For every lesion g that is kept and found, with A_g = its own voxels and P_g = the union of the whole predicted components
+ * matched to it (edge, d and hit as in mmtta_surface_dice; edge(A_g) = edge(G) within the lesion, edge(P_g) = edge(P)
+ * within the matched components, a component's edge voxels count once per lesion it matches):
+ *   nsd_{g,tau} = (hits(edge A_g -> edge P_g) + hits(edge P_g -> edge A_g)) / (|edge A_g| + |edge P_g|)
+ * Only voxels of P_g are candidates for A_g and the reverse: the nearer surface of an unmatched component does not count.
+ * A predicted edge voxel within tau of several lesions is a hit for each of them once, exactly, for any number of lesions
+ * in its window.
+ *   mask, n ... w, min_lesion_voxels   those of the mmtta_lesionwise_scores call
+ *   spacing, tolerances, n_tolerances  as in mmtta_surface_dice, with its window limit
+ *   lesionwise_scratch  the scratch of a mmtta_lesionwise_scores call with the same mask, shape and min_lesion_voxels,
+ *               queued on the same stream before; only read
+ *   nsd_stats   int64 [N*R][n_tolerances] on the device, zeroed by this call: sum over the scored lesions of
+ *               floor((hits 2^30 + floor(den / 2)) / den), nsd_{g,tau} in units of 2^-30 rounded once, in integers
+ *   lesion_nsd  fp32 [N*R][n_tolerances][D*H*W] dense on the device or NULL: filled with NaN, then (float)(hits / den) at
+ *               index (lesion label - 1) of every scored lesion
+ *   scratch     mmtta_lesionwise_nsd_scratch_bytes(N*R, D, H, W) bytes (negative: unsupported extent), a function of the
+ *               shape alone
+ * The volume's score is host arithmetic on integers: lw_nsd_tau = (nsd_stats / 2^30) / (kept lesions + false-positive
+ * components), valid iff that denominator is > 0; a kept lesion without a match and a false-positive component add 0.
+ * Six launches on `stream` that depend on the shape alone: no host read, no convergence flag; integer counts only.
+ * Limits: those of mmtta_lesionwise_scores.  Anything else is refused with MMTTA_ERR_INVALID / _UNSUPPORTED and a message
+ * naming the argument, before anything is queued.
+ * mmtta_lesionwise_nsd_list_slots(): how many distinct lesions a thread of the edge P_g -> edge A_g direction keeps in
+ * registers; a window that holds more is walked by the launch for marked voxels (for tests that must reach that launch). */
+int mmtta_lesionwise_nsd_list_slots(void);
+int64_t mmtta_lesionwise_nsd_scratch_bytes(int64_t n_masks, int64_t d, int64_t h, int64_t w);
+int mmtta_lesionwise_nsd(const uint8_t* mask, int n, int r, int d, int h, int w, const double* spacing,
+                         const double* tolerances, int n_tolerances, const int64_t* min_lesion_voxels,
+                         const void* lesionwise_scratch, int64_t* nsd_stats, float* lesion_nsd, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

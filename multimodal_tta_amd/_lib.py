@@ -248,6 +248,13 @@ _SIGNATURES = {
     "mmtta_surface_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "mmtta_surface_distances": (C.c_int, [C.c_void_p, _P(Tensor), _P(C.c_double), C.c_double, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_surface_dice_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mmtta_surface_dice": (C.c_int, [C.c_void_p, _P(Tensor), _P(C.c_double), _P(C.c_double), C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "mmtta_lesionwise_nsd_list_slots": (C.c_int, []),
+    "mmtta_lesionwise_nsd_scratch_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "mmtta_lesionwise_nsd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), _P(C.c_double),
+                                       C.c_int, _P(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -273,6 +273,92 @@ def lesionwise_hd95_columns(stats: torch.Tensor, hd_stats: torch.Tensor, penalty
     return torch.cat([lw, state])
 
 
+NSD_MAX_TOLERANCES = ops.SURFACE_DICE_MAX_TOLERANCES
+
+
+def _nsd_block(config: Any, block: Any, key: str, default: Sequence[float]) -> Tuple[bool, List[float]]:
+    """``{enable, tolerances}`` of an NSD block named ``key`` -> (enable, tolerances in mm).  1 ... 4 distinct tolerances, each
+    finite and >= 0: checked whether the block is enabled or not.  An enabled block's search window at
+    ``evaluation.seg.spacing`` must stay within 8 voxels per axis as well; the window depends on the spacing, so a disabled
+    block - the shipped configs carry one, with the default tolerances - never stands in the way of an evaluation at a fine
+    spacing."""
+    enable = get_config(block, "enable", False)
+    if not isinstance(enable, bool):
+        raise ValueError(f"{key}.enable must be true or false, got {enable!r}")
+    tol = get_config(block, "tolerances", None)
+    tol = list(default) if tol is None else tol
+    vals = list(tol) if hasattr(tol, "__iter__") and not isinstance(tol, (str, bytes)) else None
+    if (vals is None or not 1 <= len(vals) <= NSD_MAX_TOLERANCES or
+            not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(float(v)) and float(v) >= 0.0
+                    for v in vals)):
+        raise ValueError(f"{key}.tolerances must be a list of 1 ... {NSD_MAX_TOLERANCES} finite numbers >= 0 (mm), got {tol!r}")
+    vals = [float(v) for v in vals]
+    names = [nsd_suffix(v) for v in vals]
+    if len(set(names)) != len(names):
+        raise ValueError(f"{key}.tolerances must be distinct (their metric keys {names} collide), got {tol!r}")
+    sp = get_config(config, "evaluation.seg.spacing", [1.0, 1.0, 1.0])
+    sp = [float(v) for v in sp] if sp is not None else [1.0, 1.0, 1.0]
+    if enable and len(sp) == 3 and all(math.isfinite(v) and v > 0.0 for v in sp):
+        rad = ops.surface_dice_radius(sp, max(vals))
+        if max(rad) > ops.SURFACE_DICE_MAX_RADIUS:
+            raise ValueError(f"{key}.tolerances {vals} need a search window of more than {ops.SURFACE_DICE_MAX_RADIUS} voxels at "
+                             f"evaluation.seg.spacing {sp}; evaluation.surface (HD95 / ASD), whose distance transform is exact "
+                             f"at any distance, is the tool for large distances")
+    return enable, vals
+
+
+def nsd_suffix(tolerance: float) -> str:
+    """The tolerance as the metric keys carry it: ``%g`` (0.5 -> ``0.5``, 1.0 -> ``1``)."""
+    return "%g" % float(tolerance)
+
+
+def surface_dice_config(config: Any) -> Tuple[bool, List[float]]:
+    """``evaluation.surface_dice: {enable, tolerances}`` -> (enable, tolerances); off and [1.0] when absent.  A bad value is a
+    ``ValueError`` that names its key, whether the block is enabled or not."""
+    return _nsd_block(config, get_config(config, "evaluation.surface_dice", {}) or {}, "evaluation.surface_dice", [1.0])
+
+
+def lesionwise_nsd_config(config: Any) -> Tuple[bool, List[float]]:
+    """``evaluation.lesionwise.nsd: {enable, tolerances}`` -> (enable, tolerances); off and [0.5, 1.0] (BraTS-2024) when
+    absent.  A bad value is a ``ValueError`` that names its key, whether the block is enabled or not; so is ``nsd.enable``
+    without ``evaluation.lesionwise.enable``."""
+    lw = get_config(config, "evaluation.lesionwise", {}) or {}
+    enable, tol = _nsd_block(config, get_config(lw, "nsd", {}) or {}, "evaluation.lesionwise.nsd", [0.5, 1.0])
+    if enable and get_config(lw, "enable", False) is not True:
+        raise ValueError("evaluation.lesionwise.nsd.enable needs evaluation.lesionwise.enable: the NSD pass reads what the "
+                         "lesion-wise Dice pass leaves on the device")
+    return enable, tol
+
+
+def surface_dice_columns(counts: torch.Tensor) -> torch.Tensor:
+    """counts int64 [R,T,4] of one volume (``ops.SURFACE_DICE_COLUMNS``) -> its table columns float64 [T*R], one tolerance's
+    regions after another:
+
+        NSD = (hits P->G + hits G->P) / (|edge P| + |edge G|),   0 where both surfaces are empty
+
+    A region counts iff its ground truth is non-empty - the ``valid`` column of Dice, which the table already carries."""
+    c = counts.to(torch.int64)
+    num, den = c[..., 0] + c[..., 2], c[..., 1] + c[..., 3]
+    safe = torch.where(den > 0, den, torch.ones_like(den)).to(torch.float64)
+    nsd = torch.where(den > 0, num.to(torch.float64) / safe, torch.zeros_like(safe))
+    return nsd.t().reshape(-1)
+
+
+def lesionwise_nsd_columns(stats: torch.Tensor, nsd_stats: torch.Tensor) -> torch.Tensor:
+    """stats int64 [R,7] (``ops.LESIONWISE_COLUMNS``) and nsd_stats int64 [R,T] of one volume -> its table columns float64
+    [T*R], one tolerance's regions after another:
+
+        lw_nsd = nsd_q / 2^30 / (lesions kept + false-positive components),   0 where that denominator is 0
+
+    valid where the denominator is > 0: the ``valid`` column of ``lesionwise_columns``, which the table already carries."""
+    s, q = stats.to(torch.int64), nsd_stats.to(torch.int64)
+    den = s[:, 1] + (s[:, 3] - s[:, 4])
+    safe = torch.where(den > 0, den, torch.ones_like(den)).to(torch.float64)
+    lw = torch.where((den > 0)[:, None], q.to(torch.float64) / float(ops.LESIONWISE_NSD_Q_ONE) / safe[:, None],
+                     torch.zeros_like(q, dtype=torch.float64))
+    return lw.t().reshape(-1)
+
+
 def calibration_from_bins(table: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """The table of ``ops.calibration_bins`` (float64 [..., 3*bins + 2]: per bin count, sum of confidence, correct count;
     then the Brier sum, then the NLL sum) -> (ece, brier, nll, valid), float64 / bool of the leading shape.
@@ -317,8 +403,19 @@ class RegionAccumulator:
 
     def __init__(self, region_order: Sequence[str], surface: bool = False, bins: int = 0,
                  calibration_regions: Optional[Sequence[str]] = None, components: bool = False, lesionwise: bool = False,
-                 fill_nest: bool = False, lesionwise_hd95: bool = False):
+                 fill_nest: bool = False, lesionwise_hd95: bool = False, surface_dice: Sequence[float] = (),
+                 lesionwise_nsd: Sequence[float] = ()):
         self.regions = list(region_order)
+        # NSD: the tolerances (mm) of the region-wise and of the lesion-wise figure; empty = off.  Sums and counts [2, T, R]
+        self.surface_dice = [float(t) for t in surface_dice]
+        self.lesionwise_nsd = [float(t) for t in lesionwise_nsd]
+        nR = len(self.regions)
+        self._zsd = lambda: torch.zeros((2, len(self.surface_dice), nR), dtype=torch.float64)
+        self.sd_tot = self._zsd()
+        self.sd_dom: Dict[str, torch.Tensor] = defaultdict(self._zsd)
+        self._zln = lambda: torch.zeros((2, len(self.lesionwise_nsd), nR), dtype=torch.float64)
+        self.ln_tot = self._zln()
+        self.ln_dom: Dict[str, torch.Tensor] = defaultdict(self._zln)
         self.surface = bool(surface)
         R = len(self.regions)
         self._z = lambda: torch.zeros(R, dtype=torch.float64)
@@ -404,6 +501,30 @@ class RegionAccumulator:
         for name, v in zip(self.regions, self._fin(acc[2], acc[3])):
             out[f"{prefix}{name.lower()}_lw_hd95_overflow"] = v
 
+    def add_surface_dice(self, cols: Any, valid: Sequence[bool], domain: str) -> None:
+        """One volume's NSD columns, [T*R] as the table holds them (``surface_dice_columns``); ``valid`` is Dice's."""
+        c = torch.as_tensor(cols, dtype=torch.float64).reshape(len(self.surface_dice), len(self.regions))
+        ok = torch.tensor([1.0 if bool(v) else 0.0 for v in valid], dtype=torch.float64)
+        for acc in (self.sd_tot, self.sd_dom[domain]):
+            acc[0] += c * ok
+            acc[1] += ok
+
+    def add_lesionwise_nsd(self, cols: Any, lesionwise: Any, domain: str) -> None:
+        """One volume's lesion-wise NSD columns, [T*R] as the table holds them (``lesionwise_nsd_columns``); defined where the
+        volume's lesion-wise Dice is (the ``valid`` row of its ``lesionwise_columns``)."""
+        c = torch.as_tensor(cols, dtype=torch.float64).reshape(len(self.lesionwise_nsd), len(self.regions))
+        ok = torch.as_tensor(lesionwise, dtype=torch.float64).reshape(LESIONWISE_COLUMNS, len(self.regions))[1]
+        for acc in (self.ln_tot, self.ln_dom[domain]):
+            acc[0] += c * ok
+            acc[1] += ok
+
+    def _nsd_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor, tolerances: Sequence[float], stem: str) -> None:
+        for t, tau in enumerate(tolerances):
+            means = self._fin(acc[0][t], acc[1][t])
+            for name, v in zip(self.regions, means):
+                out[f"{prefix}{name.lower()}_{stem}_{nsd_suffix(tau)}"] = v
+            out[f"{prefix}avg_{stem}_{nsd_suffix(tau)}"] = self._avg(means, acc[1][t])
+
     def add_components(self, stats: Any, domain: str) -> None:
         """One volume's component figures, [3*R] as the table holds them: components[R], kept[R], removed voxels[R]."""
         st = torch.as_tensor(stats, dtype=torch.float64).reshape(3, len(self.regions))
@@ -441,8 +562,13 @@ class RegionAccumulator:
     def add_row(self, dice: Sequence[float], iou: Sequence[float], valid: Sequence[bool], domain: str,
                 hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None,
                 calibration: Optional[torch.Tensor] = None, components: Any = None, lesionwise: Any = None,
-                fill_nest: Any = None, lesionwise_hd95: Any = None) -> None:
+                fill_nest: Any = None, lesionwise_hd95: Any = None, surface_dice: Any = None,
+                lesionwise_nsd: Any = None) -> None:
         d = self.dom[domain]
+        if self.surface_dice:
+            self.add_surface_dice(surface_dice, valid, domain)
+        if self.lesionwise_nsd:
+            self.add_lesionwise_nsd(lesionwise_nsd, lesionwise, domain)
         if self.components:
             self.add_components(components, domain)
         if self.fill_nest:
@@ -501,6 +627,10 @@ class RegionAccumulator:
             self._lesionwise_keys(out, "", self.lw_tot)
         if self.lesionwise_hd95:
             self._lesionwise_hd95_keys(out, "", self.lh_tot)
+        if self.lesionwise_nsd:
+            self._nsd_keys(out, "", self.ln_tot, self.lesionwise_nsd, "lw_nsd")
+        if self.surface_dice:
+            self._nsd_keys(out, "", self.sd_tot, self.surface_dice, "nsd")
         if self.bins:
             self._calibration_keys(out, "", self.cal_tot)
         for dom in sorted(self.dom.keys()):
@@ -521,6 +651,10 @@ class RegionAccumulator:
                 self._lesionwise_keys(out, f"dom/{safe}/", self.lw_dom[dom])
             if self.lesionwise_hd95:
                 self._lesionwise_hd95_keys(out, f"dom/{safe}/", self.lh_dom[dom])
+            if self.lesionwise_nsd:
+                self._nsd_keys(out, f"dom/{safe}/", self.ln_dom[dom], self.lesionwise_nsd, "lw_nsd")
+            if self.surface_dice:
+                self._nsd_keys(out, f"dom/{safe}/", self.sd_dom[dom], self.surface_dice, "nsd")
             if self.bins:
                 self._calibration_keys(out, f"dom/{safe}/", self.cal_dom[dom])
         return out
@@ -640,6 +774,17 @@ class SegmentationEvaluationStrategy:
         (self.enable_lesionwise_hd95, self.lesionwise_hd95_percentile,
          self.lesionwise_hd95_penalty) = lesionwise_hd95_config(self.config)
         self._lwhd: Optional[torch.Tensor] = None
+        # normalised surface Dice at tolerances in mm, off by default: region-wise on the final mask (one bounded search over
+        # bit-packed edge masks, no distance transform), and lesion-wise behind the lesion-wise scores, on their scratch
+        self.enable_surface_dice, self.surface_dice_tolerances = surface_dice_config(self.config)
+        self.enable_lesionwise_nsd, self.lesionwise_nsd_tolerances = lesionwise_nsd_config(self.config)
+        for on, key in ((self.enable_surface_dice, "evaluation.surface_dice.enable"),
+                        (self.enable_lesionwise_nsd, "evaluation.lesionwise.nsd.enable")):
+            if on and bool(get_config(self.config, "training.criterion.softmax", False)):
+                raise NotImplementedError(f"{key}: the normalised surface Dice is defined for the sigmoid-region head only "
+                                          f"(training.criterion.softmax is set)")
+        self._sd: Optional[torch.Tensor] = None
+        self._lwnsd: Optional[torch.Tensor] = None
         # input pre-pass on the GPU (raw volumes in, the reference's `_normalize_img` applied here instead of in the
         # dataset worker; reference src/datasets/transforms.py:129-223).  The NIfTI datasets of this package hand over
         # raw intensities, so the pre-pass defaults to on for them and to off for the synthetic source (already
@@ -714,6 +859,25 @@ class SegmentationEvaluationStrategy:
                                   self.spacing, self.lesionwise_hd95_percentile)
         return res["stats"], res["hd_stats"]
 
+    def lesionwise_nsd_launch(self, mask: torch.Tensor) -> torch.Tensor:
+        """Queue the lesion-wise NSD of ``mask`` on the current stream, behind the lesion-wise scores queued there for it ->
+        device nsd_stats int64 [B,R,T]."""
+        return ops.lesionwise_nsd_after_scores(mask, self.lesionwise_min_voxels, self.spacing,
+                                               self.lesionwise_nsd_tolerances)["nsd_stats"]
+
+    def surface_dice_launch(self, mask: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """Queue the NSD counts of (mask, y) on the current stream -> device counts int64 [B,R,T,4]."""
+        return ops.surface_dice(mask, y, self.spacing, self.surface_dice_tolerances)
+
+    @property
+    def sd_tolerances(self) -> List[float]:
+        """The tolerances as the table helpers take them: empty = region-wise NSD off."""
+        return self.surface_dice_tolerances if self.enable_surface_dice else []
+
+    @property
+    def ln_tolerances(self) -> List[float]:
+        return self.lesionwise_nsd_tolerances if self.enable_lesionwise_nsd else []
+
     def lesionwise_hd95_penalty_mm(self, shape) -> float:
         """The penalty of a missed lesion or a false-positive component for a volume of this shape."""
         if self.lesionwise_hd95_penalty == "diagonal":
@@ -736,7 +900,7 @@ class SegmentationEvaluationStrategy:
         if not shape_ok:
             raise ValueError(f"[BratsSegEval] model logits must be [B,{R},D,H,W], got {tuple(logits.shape)}")
         counts = torch.empty((y.shape[0], R, 3), dtype=torch.int64, device=y.device)
-        need_mask = self.enable_surface or self.enable_postprocess or self.enable_lesionwise
+        need_mask = self.enable_surface or self.enable_postprocess or self.enable_lesionwise or self.enable_surface_dice
         self._mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if need_mask else None
         ops.mask_dice_counts(logits, y, self.threshold, counts, self._mask, logits_channels_last=channels_last)
         self._stats = self._fill = None
@@ -746,12 +910,23 @@ class SegmentationEvaluationStrategy:
                 counts, fill = self.fill_nest_launch(self._mask, y)
                 self._fill = fill.cpu()
             self._stats = stats.cpu()
-        self._lw = self._lwhd = None
+        self._lw = self._lwhd = self._sd = self._lwnsd = None
+        lw = lwhd = None
         if self.enable_lesionwise_hd95:
             lw, lwhd = self.lesionwise_hd95_launch(self._mask, y)
-            self._lw, self._lwhd = lw.cpu(), lwhd.cpu()
         elif self.enable_lesionwise:
-            self._lw = self.lesionwise_launch(self._mask, y).cpu()
+            lw = self.lesionwise_launch(self._mask, y)
+        # the NSD passes are queued behind the lesion-wise ones, before the first host read
+        lwnsd = self.lesionwise_nsd_launch(self._mask) if self.enable_lesionwise_nsd else None
+        sd = self.surface_dice_launch(self._mask, y) if self.enable_surface_dice else None
+        if lw is not None:
+            self._lw = lw.cpu()
+        if lwhd is not None:
+            self._lwhd = lwhd.cpu()
+        if lwnsd is not None:
+            self._lwnsd = lwnsd.cpu()
+        if sd is not None:
+            self._sd = sd.cpu()
         return counts.cpu()
 
     def calibration_launch(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
@@ -798,7 +973,7 @@ class SegmentationEvaluationStrategy:
         model.to(device)
         acc = RegionAccumulator(self.region_order, self.enable_surface, self.cal_bins, self.calibration_regions,
                                 self.enable_postprocess, self.enable_lesionwise, self.enable_fill_nest,
-                                self.enable_lesionwise_hd95)
+                                self.enable_lesionwise_hd95, self.sd_tolerances, self.ln_tolerances)
         rows: List[torch.Tensor] = []
         domain_names: List[str] = []
         n_local = 0
@@ -814,6 +989,9 @@ class SegmentationEvaluationStrategy:
             lh = ([lesionwise_hd95_columns(st, hs, self.lesionwise_hd95_penalty_mm(y.shape[2:]))
                    for st, hs in zip(self._lw, self._lwhd)] if self.enable_lesionwise_hd95 else None)
             fn = [self.fill_nest_columns(st) for st in self._fill] if self.enable_fill_nest else None
+            ln = ([lesionwise_nsd_columns(st, ns) for st, ns in zip(self._lw, self._lwnsd)] if self.enable_lesionwise_nsd
+                  else None)
+            sdc = [surface_dice_columns(c) for c in self._sd] if self.enable_surface_dice else None
             domains = as_list_str(batch.get("domain", None), batch_size=x.size(0))
             if world == 1:
                 for i in range(x.size(0)):
@@ -821,7 +999,8 @@ class SegmentationEvaluationStrategy:
                                 hd[i].tolist() if hd is not None else None, asd[i].tolist() if asd is not None else None,
                                 cal[i] if cal is not None else None, comp[i] if comp is not None else None,
                                 lw[i] if lw is not None else None, fn[i] if fn is not None else None,
-                                lh[i] if lh is not None else None)
+                                lh[i] if lh is not None else None, sdc[i] if sdc is not None else None,
+                                ln[i] if ln is not None else None)
                 if self.report_loss:
                     acc.add_loss(self.loss_fn(logits.float(), y), x.size(0))
                 continue
@@ -847,6 +1026,10 @@ class SegmentationEvaluationStrategy:
                     parts.append(lw[i])
                 if lh is not None:
                     parts.append(lh[i])
+                if ln is not None:
+                    parts.append(ln[i])
+                if sdc is not None:
+                    parts.append(sdc[i])
                 if cal is not None:
                     parts.append(cal[i].reshape(-1))
                 rows.append(torch.cat(parts))
@@ -863,7 +1046,8 @@ class SegmentationEvaluationStrategy:
     def _table_width(self) -> int:
         return table_width(len(self.region_order), self.enable_surface, self.cal_bins, len(self.calibration_regions),
                            components=self.enable_postprocess, lesionwise=self.enable_lesionwise,
-                           fill_nest=self.enable_fill_nest, lesionwise_hd95=self.enable_lesionwise_hd95)
+                           fill_nest=self.enable_fill_nest, lesionwise_hd95=self.enable_lesionwise_hd95,
+                           surface_dice=len(self.sd_tolerances), lesionwise_nsd=len(self.ln_tolerances))
 
     def _metrics_of(self, table: torch.Tensor, domain_names: Sequence[str]) -> Dict[str, float]:
         """Metrics of the whole split from its per-volume table (and ``last_reliability`` with calibration on)."""
@@ -872,7 +1056,8 @@ class SegmentationEvaluationStrategy:
         return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface,
                                   self.cal_bins, self.calibration_regions, components=self.enable_postprocess,
                                   lesionwise=self.enable_lesionwise, fill_nest=self.enable_fill_nest,
-                                  lesionwise_hd95=self.enable_lesionwise_hd95)
+                                  lesionwise_hd95=self.enable_lesionwise_hd95, surface_dice=self.sd_tolerances,
+                                  lesionwise_nsd=self.ln_tolerances)
 
 
 # ----------------------------------------------------------------------------- sharding
@@ -882,15 +1067,17 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
 
 
 def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None, components: bool = False,
-                lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False) -> int:
+                lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False, surface_dice: int = 0,
+                lesionwise_nsd: int = 0) -> int:
     """index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R]) (, with ``components`` the figures of the
     post-processing: components[R], kept[R], removed voxels[R]) (, with ``fill_nest`` the figures of the hole filling and
     nesting: holes[R], filled holes[R], filled voxels[R], nested voxels[R]) (, with ``lesionwise`` the 7*R columns of
-    ``lesionwise_columns``) (, with ``lesionwise_hd95`` the 2*R columns of ``lesionwise_hd95_columns``) (, with ``bins`` > 0 the volume's raw calibration table: ``rout`` rows - default R - of
+    ``lesionwise_columns``) (, with ``lesionwise_hd95`` the 2*R columns of ``lesionwise_hd95_columns``) (, with ``lesionwise_nsd`` = T > 0 tolerances the T*R columns of ``lesionwise_nsd_columns``)
+    (, with ``surface_dice`` = T > 0 tolerances the T*R columns of ``surface_dice_columns``) (, with ``bins`` > 0 the volume's raw calibration table: ``rout`` rows - default R - of
     3*bins + 2 doubles, always last)."""
     return (3 + (5 if surface else 3) * R + (3 * R if components else 0) + (FILL_NEST_COLUMNS * R if fill_nest else 0) +
             (LESIONWISE_COLUMNS * R if lesionwise else 0) + (LESIONWISE_HD95_COLUMNS * R if lesionwise_hd95 else 0) +
-            calibration_width(bins, R if rout is None else rout))
+            (int(lesionwise_nsd) + int(surface_dice)) * R + calibration_width(bins, R if rout is None else rout))
 
 
 def reliability_from_table(table: torch.Tensor, bins: int, rout: int) -> torch.Tensor:
@@ -969,19 +1156,24 @@ def gather_masks(local: Sequence[Tuple[int, torch.Tensor]], device, group=None) 
 def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_names: Sequence[str],
                        report_loss: bool, surface: bool = False, bins: int = 0,
                        calibration_regions: Optional[Sequence[str]] = None, components: bool = False,
-                       lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False) -> Dict[str, float]:
+                       lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False,
+                       surface_dice: Sequence[float] = (), lesionwise_nsd: Sequence[float] = ()) -> Dict[str, float]:
     """Replay the reference aggregation over gathered rows in volume-index order: the result is
     identical to a single-process run (float64 sums, order fixed by index).  ``bins`` > 0: the rows end in the raw
     calibration table of their volume (``table_width``), one row of it per name in ``calibration_regions``.
     ``components``: the 3*R component columns sit behind the surface columns (``table_width``); ``fill_nest``: the 4*R
     columns of the hole filling and nesting sit behind those; ``lesionwise``: the 7*R lesion-wise columns sit behind those;
-    ``lesionwise_hd95``: the 2*R lesion-wise HD95 columns sit directly behind those."""
+    ``lesionwise_hd95``: the 2*R lesion-wise HD95 columns sit directly behind those; ``lesionwise_nsd`` and ``surface_dice``
+    (their tolerances): the T*R lesion-wise NSD columns, then the T*R region-wise NSD columns, behind those."""
     R = len(region_order)
-    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components, lesionwise, fill_nest, lesionwise_hd95)
+    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components, lesionwise, fill_nest, lesionwise_hd95,
+                            surface_dice, lesionwise_nsd)
     c0 = 3 + (5 if surface else 3) * R
     f0 = c0 + (3 * R if components else 0)
     l0 = f0 + (FILL_NEST_COLUMNS * R if fill_nest else 0)
     h0 = l0 + (LESIONWISE_COLUMNS * R if lesionwise else 0)
+    n0 = h0 + (LESIONWISE_HD95_COLUMNS * R if lesionwise_hd95 else 0)
+    s0 = n0 + len(acc.lesionwise_nsd) * R
     cal_w = calibration_width(bins, len(acc.cal_regions))
     for row in table:
         dom = domain_names[int(row[1].item())] if 0 <= int(row[1].item()) < len(domain_names) else ""
@@ -994,7 +1186,9 @@ def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_
                     row[c0:c0 + 3 * R] if components else None,
                     row[l0:l0 + LESIONWISE_COLUMNS * R] if lesionwise else None,
                     row[f0:f0 + FILL_NEST_COLUMNS * R] if fill_nest else None,
-                    row[h0:h0 + LESIONWISE_HD95_COLUMNS * R] if lesionwise_hd95 else None)
+                    row[h0:h0 + LESIONWISE_HD95_COLUMNS * R] if lesionwise_hd95 else None,
+                    row[s0:s0 + len(acc.surface_dice) * R] if acc.surface_dice else None,
+                    row[n0:s0] if acc.lesionwise_nsd else None)
         if report_loss:
             acc.add_loss(float(row[2].item()), 1)
     return acc.metrics(report_loss)
@@ -1105,7 +1299,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         B, R = yb.shape[0], yb.shape[1]
         res = self.plugins[lane].adapt_volume(xb)
         counts = torch.empty((B, R, 3), dtype=torch.int64, device=yb.device)
-        need_mask = self.enable_surface or self.gather_masks or self.enable_postprocess or self.enable_lesionwise
+        need_mask = (self.enable_surface or self.gather_masks or self.enable_postprocess or self.enable_lesionwise or
+                     self.enable_surface_dice)
         mask = torch.empty(tuple(yb.shape), dtype=torch.uint8, device=yb.device) if need_mask else None
         ops.mask_dice_counts(res["logits_cl"], yb, self.threshold, counts, mask, logits_channels_last=True)
         stats = None
@@ -1123,6 +1318,10 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
             job["lesionwise"], job["lesionwise_hd95"] = self.lesionwise_hd95_launch(mask, yb)
         elif self.enable_lesionwise:
             job["lesionwise"] = self.lesionwise_launch(mask, yb)
+        if self.enable_lesionwise_nsd:   # behind the lesion-wise passes, on their scratch
+            job["lesionwise_nsd"] = self.lesionwise_nsd_launch(mask)
+        if self.enable_surface_dice:     # on the final mask, like the surface distances
+            job["surface_dice"] = self.surface_dice_launch(mask, yb)
         if self.report_loss:
             job["loss"] = self.loss_fn.launch(res["logits_cl"], yb, channels_last=True)
         if self.enable_surface:
@@ -1145,6 +1344,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         lh = job["lesionwise_hd95"].cpu() if self.enable_lesionwise_hd95 else None
         pen = self.lesionwise_hd95_penalty_mm(job["shape"]) if self.enable_lesionwise_hd95 else 0.0
         fn = job["fill_nest"].cpu() if self.enable_fill_nest else None
+        ln = job["lesionwise_nsd"].cpu() if self.enable_lesionwise_nsd else None
+        sdc = job["surface_dice"].cpu() if self.enable_surface_dice else None
         rows = []
         for b in range(B):
             parts = [torch.tensor([job["index"][b], job["domain_id"][b], losses[b]], dtype=torch.float64),
@@ -1159,6 +1360,10 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
                 parts.append(lesionwise_columns(lw[b]))
             if lh is not None:
                 parts.append(lesionwise_hd95_columns(lw[b], lh[b], pen))
+            if ln is not None:
+                parts.append(lesionwise_nsd_columns(lw[b], ln[b]))
+            if sdc is not None:
+                parts.append(surface_dice_columns(sdc[b]))
             if cal is not None:
                 parts.append(cal[b].reshape(-1))
             rows.append(torch.cat(parts))

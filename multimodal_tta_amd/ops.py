@@ -1670,3 +1670,148 @@ def lesionwise_hd95(mask: torch.Tensor, label_ncdhw: torch.Tensor, iterations: i
                                     (C.c_int64 * R)(*mv), ptr(lw_scratch), ptr(hd_stats), ptr(lesion_hd), ptr(scratch),
                                     stream_ptr()), "lesionwise_hd95")
     return {"stats": res["stats"], "hd_stats": hd_stats, "lesion_hd": lesion_hd, "labels": res["labels"]}
+
+
+_SD_SCRATCH: Dict[Tuple, torch.Tensor] = {}      # working set of surface_dice, per (device, size, stream)
+SURFACE_DICE_COLUMNS = ("hits_pred", "edge_pred", "hits_gt", "edge_gt")
+SURFACE_DICE_MAX_TOLERANCES = 4
+SURFACE_DICE_MAX_RADIUS = 8                      # search window per axis, in voxels
+
+
+def surface_dice_radius(spacing: Sequence[float], tolerance: float) -> Tuple[int, int, int]:
+    """The search window of the NSD kernels for ``tolerance`` (the largest of a call) at ``spacing`` (D, H, W): per axis the
+    largest k >= 0 with float32(sqrt((k s)^2)) <= float32(tolerance), found by the loop the library runs.  A radius above
+    ``SURFACE_DICE_MAX_RADIUS`` is reported as ``SURFACE_DICE_MAX_RADIUS + 1``."""
+    tau = C.c_float(float(tolerance)).value          # rounded to float32, as the kernel holds it
+    out = []
+    for s in spacing:
+        k = 0
+        while k <= SURFACE_DICE_MAX_RADIUS:
+            f = float(k + 1) * float(s)
+            if not C.c_float(math.sqrt(f * f)).value <= tau:
+                break
+            k += 1
+        out.append(k)
+    return out[0], out[1], out[2]
+
+
+def _nsd_arguments(who: str, spacing, tolerances) -> Tuple[List[float], List[float]]:
+    try:
+        sp = [float(v) for v in spacing]
+    except (TypeError, ValueError):
+        sp = []
+    if len(sp) != 3 or not all(math.isfinite(v) and v > 0.0 for v in sp):
+        raise MmttaError(f"{who}: spacing must be three positive finite numbers (D, H, W), got {spacing!r}")
+    try:
+        tol = [float(v) for v in tolerances]
+        ok = not isinstance(tolerances, (str, bytes)) and all(not isinstance(v, (bool, str, bytes)) for v in tolerances)
+    except (TypeError, ValueError):
+        tol, ok = [], False
+    if not ok or not 1 <= len(tol) <= SURFACE_DICE_MAX_TOLERANCES or not all(math.isfinite(v) and v >= 0.0 for v in tol):
+        raise MmttaError(f"{who}: tolerances must be 1 ... {SURFACE_DICE_MAX_TOLERANCES} finite numbers >= 0, got {tolerances!r}")
+    rad = surface_dice_radius(sp, max(tol))
+    if max(rad) > SURFACE_DICE_MAX_RADIUS:
+        raise MmttaError(f"{who}: tolerances {tol} need a search window of more than {SURFACE_DICE_MAX_RADIUS} voxels at spacing "
+                         f"{sp}; surface_distances (HD95 / ASD) is the tool for large distances")
+    return sp, tol
+
+
+def surface_dice(pred_mask: torch.Tensor, label_ncdhw: torch.Tensor, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                 tolerances: Sequence[float] = (1.0,)) -> torch.Tensor:
+    """The counts behind the normalised surface Dice of every (volume, region) of ``pred_mask`` (uint8 [B,R,D,H,W], dense)
+    against ``label_ncdhw`` at each of ``tolerances`` (1 ... 4, in the units of ``spacing``, D, H, W order), queued on the
+    current stream (include/mmtta.h: mmtta_surface_dice).  Returns int64 [B,R,T,4] on the device (``SURFACE_DICE_COLUMNS``):
+    NSD = (hits_pred + hits_gt) / (edge_pred + edge_gt)."""
+    sp, tol = _nsd_arguments("surface_dice", spacing, tolerances)
+    if (not torch.is_tensor(pred_mask) or pred_mask.dtype != torch.uint8 or pred_mask.dim() != 5 or not pred_mask.is_contiguous()
+            or not pred_mask.is_cuda):
+        raise MmttaError("surface_dice: mask must be a dense CUDA uint8 [B,R,D,H,W] tensor")
+    if (not torch.is_tensor(label_ncdhw) or tuple(label_ncdhw.shape) != tuple(pred_mask.shape) or label_ncdhw.device != pred_mask.device
+            or label_ncdhw.dtype != torch.float32):
+        raise MmttaError(f"surface_dice: label must be float32 of the mask's shape {tuple(pred_mask.shape)} on the mask's device")
+    B, R, D, H, W = (int(v) for v in pred_mask.shape)
+    if min(B, R, D, H, W) < 1:
+        raise MmttaError(f"surface_dice: empty mask {tuple(pred_mask.shape)}")
+    lib = _lib.load()
+    nbytes = int(lib.mmtta_surface_dice_scratch_bytes(B * R, D, H, W))
+    if nbytes < 0:
+        raise MmttaError(f"surface_dice: extent {(B * R, D, H, W)} unsupported (at most 1024 per axis, B*R <= 65535)")
+    key = (pred_mask.device.index, nbytes, int(torch.cuda.current_stream().cuda_stream))     # per stream: lanes run concurrently
+    scratch = _SD_SCRATCH.get(key)
+    if scratch is None:
+        for k in [k for k in _SD_SCRATCH if k[2] == key[2]]:       # a new shape on this stream replaces its old working set
+            del _SD_SCRATCH[k]
+        scratch = _SD_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=pred_mask.device)
+    T = len(tol)
+    counts = torch.empty((B, R, T, 4), dtype=torch.int64, device=pred_mask.device)
+    tl = desc_ncdhw(label_ncdhw)
+    check(lib.mmtta_surface_dice(ptr(pred_mask), C.byref(tl), (C.c_double * 3)(*sp), (C.c_double * T)(*tol), T, ptr(counts),
+                                 ptr(scratch), stream_ptr()), "surface_dice")
+    return counts
+
+
+_LW_NSD_SCRATCH: Dict[Tuple, torch.Tensor] = {}  # working set of lesionwise_nsd beside the one of lesionwise_scores, likewise
+LESIONWISE_NSD_Q_ONE = 1 << 30                   # a lesion's NSD is summed in units of 2^-30
+
+
+def lesionwise_nsd_list_slots() -> int:
+    """Distinct lesions a thread of the P -> A direction of ``mmtta_lesionwise_nsd`` keeps in registers; an edge voxel with more
+    of them in its window is handled by the launch for marked voxels."""
+    return int(_lib.load().mmtta_lesionwise_nsd_list_slots())
+
+
+def lesionwise_nsd_after_scores(mask: torch.Tensor, min_lesion_voxels, spacing: Sequence[float], tolerances: Sequence[float],
+                                want_lesion_nsd: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+    """The lesion-wise NSD pass alone (include/mmtta.h: mmtta_lesionwise_nsd), on the current stream, behind a
+    ``lesionwise_scores`` (or ``lesionwise_hd95``) call with the same mask and ``min_lesion_voxels`` on this stream, whose
+    scratch it reads.  Returns ``nsd_stats`` int64 [B,R,T] (sum over the scored lesions of their NSD in units of 2^-30) and
+    ``lesion_nsd`` float32 [B,R,T,D,H,W] (NaN, and a lesion's NSD at index lesion label - 1; with ``want_lesion_nsd``)."""
+    sp, tol = _nsd_arguments("lesionwise_nsd", spacing, tolerances)
+    if (not torch.is_tensor(mask) or mask.dtype != torch.uint8 or mask.dim() != 5 or not mask.is_contiguous() or not mask.is_cuda):
+        raise MmttaError("lesionwise_nsd: mask must be a dense CUDA uint8 [B,R,D,H,W] tensor, got "
+                         f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+    B, R, D, H, W = (int(v) for v in mask.shape)
+    if min(B, R, D, H, W) < 1:
+        raise MmttaError(f"lesionwise_nsd: empty mask {tuple(mask.shape)}")
+    if R > COMPONENTS_MAX_REGIONS:
+        raise MmttaError(f"lesionwise_nsd: {R} regions, at most {COMPONENTS_MAX_REGIONS}")
+    vals = [min_lesion_voxels] * R if isinstance(min_lesion_voxels, (bool, int)) else list(min_lesion_voxels)
+    if len(vals) != R:
+        raise MmttaError(f"lesionwise_nsd: min_lesion_voxels has {len(vals)} entries for {R} regions")
+    mv = [int(v) for v in vals]
+    if any(v < 0 for v in mv):
+        raise MmttaError(f"lesionwise_nsd: min_lesion_voxels must not be negative, got {mv}")
+    lib = _lib.load()
+    stream = int(torch.cuda.current_stream().cuda_stream)
+    lw_scratch = _LW_SCRATCH.get((mask.device.index, int(lib.mmtta_lesionwise_scratch_bytes(B * R, D, H, W)), stream))
+    if lw_scratch is None:
+        raise MmttaError("lesionwise_nsd: no lesionwise_scores call of this shape on this stream to read from")
+    nbytes = int(lib.mmtta_lesionwise_nsd_scratch_bytes(B * R, D, H, W))
+    if nbytes < 0:
+        raise MmttaError(f"lesionwise_nsd: extent {(B * R, D, H, W)} unsupported")
+    key = (mask.device.index, nbytes, stream)
+    scratch = _LW_NSD_SCRATCH.get(key)
+    if scratch is None:
+        for k in [k for k in _LW_NSD_SCRATCH if k[2] == key[2]]:
+            del _LW_NSD_SCRATCH[k]
+        scratch = _LW_NSD_SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=mask.device)
+    T = len(tol)
+    nsd_stats = torch.empty((B, R, T), dtype=torch.int64, device=mask.device)
+    lesion_nsd = torch.empty((B, R, T, D, H, W), dtype=torch.float32, device=mask.device) if want_lesion_nsd else None
+    check(lib.mmtta_lesionwise_nsd(ptr(mask), B, R, D, H, W, (C.c_double * 3)(*sp), (C.c_double * T)(*tol), T,
+                                   (C.c_int64 * R)(*mv), ptr(lw_scratch), ptr(nsd_stats), ptr(lesion_nsd), ptr(scratch),
+                                   stream_ptr()), "lesionwise_nsd")
+    return {"nsd_stats": nsd_stats, "lesion_nsd": lesion_nsd}
+
+
+def lesionwise_nsd(mask: torch.Tensor, label_ncdhw: torch.Tensor, iterations: int = 3, dilation_connectivity: int = 18,
+                   min_lesion_voxels=0, spacing: Sequence[float] = (1.0, 1.0, 1.0), tolerances: Sequence[float] = (0.5, 1.0),
+                   want_lesion_nsd: bool = False, want_labels: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+    """Lesion-wise scores AND lesion-wise NSD of every (volume, region) of ``mask`` against ``label_ncdhw``:
+    ``lesionwise_scores`` followed, on the same scratch and the current stream, by ``lesionwise_nsd_after_scores``.  Returns
+    the device tensors ``stats`` int64 [B,R,7] (identical to ``lesionwise_scores``' own), ``nsd_stats``, ``lesion_nsd`` and
+    ``labels`` (with ``want_labels``)."""
+    _nsd_arguments("lesionwise_nsd", spacing, tolerances)      # refused before anything is queued
+    res = lesionwise_scores(mask, label_ncdhw, iterations, dilation_connectivity, min_lesion_voxels, want_labels=want_labels)
+    nsd = lesionwise_nsd_after_scores(mask, min_lesion_voxels, spacing, tolerances, want_lesion_nsd)
+    return {"stats": res["stats"], "nsd_stats": nsd["nsd_stats"], "lesion_nsd": nsd["lesion_nsd"], "labels": res["labels"]}
