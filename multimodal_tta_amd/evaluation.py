@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import math
 from collections import defaultdict
-from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import Any, Callable, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -56,6 +56,31 @@ def dice_iou_from_counts(counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tens
     return dice, iou, valid
 
 
+def _enable(block: Any, key: str) -> bool:
+    """``block.enable`` of the config block at ``key``: a bool, false when absent."""
+    enable = get_config(block, "enable", False)
+    if not isinstance(enable, bool):
+        raise ValueError(f"{key}.enable must be true or false, got {enable!r}")
+    return enable
+
+
+def _is_count(x: Any) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool) and x >= 0
+
+
+def _per_region(block: Any, key: str, name: str, default: Any, R: int, ok: Callable[[Any], bool], what: str) -> list:
+    """``block[name]`` of the config block at ``key`` as one value per region: a scalar stands for every region, a list has
+    one entry per region of ``evaluation.seg.region_order``."""
+    v = get_config(block, name, default)
+    scalar = isinstance(v, (bool, int))
+    vals = [v] * R if scalar else (list(v) if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else None)
+    if vals is None or not all(ok(x) for x in vals):
+        raise ValueError(f"{key}.{name} must be {what} or a list of one per region, got {v!r}")
+    if len(vals) != R:
+        raise ValueError(f"{key}.{name} has {len(vals)} entries for the {R} regions of evaluation.seg.region_order")
+    return vals
+
+
 CALIBRATION_SCOPES = ("volume", "union")
 CALIBRATION_MAX_BINS = 64
 
@@ -64,9 +89,7 @@ def calibration_config(config: Any) -> Tuple[bool, int, str]:
     """``evaluation.calibration: {enable, bins, scope}`` -> (enable, bins, scope); off, 15 bins, ``volume`` when absent.
     A value the kernel cannot take is a ``ValueError`` that names its key, whether the block is enabled or not."""
     cal = get_config(config, "evaluation.calibration", {}) or {}
-    enable = get_config(cal, "enable", False)
-    if not isinstance(enable, bool):
-        raise ValueError(f"evaluation.calibration.enable must be true or false, got {enable!r}")
+    enable = _enable(cal, "evaluation.calibration")
     bins = get_config(cal, "bins", 15)
     if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= CALIBRATION_MAX_BINS:
         raise ValueError(f"evaluation.calibration.bins must be an integer in 1 ... {CALIBRATION_MAX_BINS}, got {bins!r}")
@@ -86,26 +109,12 @@ def postprocess_config(config: Any) -> Tuple[bool, int, List[int], List[bool]]:
     per region.  A value the kernel cannot take is a ``ValueError`` that names its key, whether the block is enabled or not."""
     pp = get_config(config, "evaluation.postprocess", {}) or {}
     R = len(list(get_config(config, "evaluation.seg.region_order", ["ET", "TC", "WT"])))
-    enable = get_config(pp, "enable", False)
-    if not isinstance(enable, bool):
-        raise ValueError(f"evaluation.postprocess.enable must be true or false, got {enable!r}")
+    enable = _enable(pp, "evaluation.postprocess")
     conn = get_config(pp, "connectivity", 26)
     if isinstance(conn, bool) or conn not in POSTPROCESS_CONNECTIVITIES:
         raise ValueError(f"evaluation.postprocess.connectivity must be one of {list(POSTPROCESS_CONNECTIVITIES)}, got {conn!r}")
-
-    def per_region(key: str, default, ok, what: str) -> list:
-        v = get_config(pp, key, default)
-        scalar = isinstance(v, (bool, int))
-        vals = [v] * R if scalar else (list(v) if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else None)
-        if vals is None or not all(ok(x) for x in vals):
-            raise ValueError(f"evaluation.postprocess.{key} must be {what} or a list of one per region, got {v!r}")
-        if len(vals) != R:
-            raise ValueError(f"evaluation.postprocess.{key} has {len(vals)} entries for the {R} regions of "
-                             f"evaluation.seg.region_order")
-        return vals
-
-    mv = per_region("min_voxels", 0, lambda x: isinstance(x, int) and not isinstance(x, bool) and x >= 0, "a non-negative integer")
-    kl = per_region("keep_largest", False, lambda x: isinstance(x, bool), "true or false")
+    mv = _per_region(pp, "evaluation.postprocess", "min_voxels", 0, R, _is_count, "a non-negative integer")
+    kl = _per_region(pp, "evaluation.postprocess", "keep_largest", False, R, lambda x: isinstance(x, bool), "true or false")
     return enable, int(conn), [int(v) for v in mv], [bool(v) for v in kl]
 
 
@@ -127,23 +136,13 @@ def fill_nest_config(config: Any) -> Tuple[List[bool], int, List[int], List[int]
     regions = [str(x) for x in get_config(config, "evaluation.seg.region_order", ["ET", "TC", "WT"])]
     R = len(regions)
     dflt = POSTPROCESS_FILL_DEFAULTS
-
-    def per_region(key: str, ok, what: str) -> list:
-        v = get_config(pp, key, dflt[key])
-        scalar = isinstance(v, (bool, int))
-        vals = [v] * R if scalar else (list(v) if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else None)
-        if vals is None or not all(ok(x) for x in vals):
-            raise ValueError(f"evaluation.postprocess.{key} must be {what} or a list of one per region, got {v!r}")
-        if len(vals) != R:
-            raise ValueError(f"evaluation.postprocess.{key} has {len(vals)} entries for the {R} regions of "
-                             f"evaluation.seg.region_order")
-        return vals
-
-    fh = per_region("fill_holes", lambda x: isinstance(x, bool), "true or false")
+    fh = _per_region(pp, "evaluation.postprocess", "fill_holes", dflt["fill_holes"], R, lambda x: isinstance(x, bool),
+                     "true or false")
     conn = get_config(pp, "fill_connectivity", dflt["fill_connectivity"])
     if isinstance(conn, bool) or conn not in POSTPROCESS_CONNECTIVITIES:
         raise ValueError(f"evaluation.postprocess.fill_connectivity must be one of {list(POSTPROCESS_CONNECTIVITIES)}, got {conn!r}")
-    cap = per_region("max_hole_voxels", lambda x: isinstance(x, int) and not isinstance(x, bool) and x >= 0, "a non-negative integer")
+    cap = _per_region(pp, "evaluation.postprocess", "max_hole_voxels", dflt["max_hole_voxels"], R, _is_count,
+                      "a non-negative integer")
     nest = get_config(pp, "nesting", dflt["nesting"])
     nest = [] if nest is None else nest
     if isinstance(nest, (str, bytes)) or not hasattr(nest, "__iter__"):
@@ -171,9 +170,7 @@ def lesionwise_config(config: Any) -> Tuple[bool, int, int, List[int]]:
     is a ``ValueError`` that names its key, whether the block is enabled or not."""
     lw = get_config(config, "evaluation.lesionwise", {}) or {}
     R = len(list(get_config(config, "evaluation.seg.region_order", ["ET", "TC", "WT"])))
-    enable = get_config(lw, "enable", False)
-    if not isinstance(enable, bool):
-        raise ValueError(f"evaluation.lesionwise.enable must be true or false, got {enable!r}")
+    enable = _enable(lw, "evaluation.lesionwise")
     dil = get_config(lw, "dilation", 3)
     if isinstance(dil, bool) or not isinstance(dil, int) or not 0 <= dil <= LESIONWISE_MAX_DILATION:
         raise ValueError(f"evaluation.lesionwise.dilation must be an integer in 0 ... {LESIONWISE_MAX_DILATION}, got {dil!r}")
@@ -181,16 +178,15 @@ def lesionwise_config(config: Any) -> Tuple[bool, int, int, List[int]]:
     if isinstance(conn, bool) or conn not in LESIONWISE_CONNECTIVITIES:
         raise ValueError(f"evaluation.lesionwise.dilation_connectivity must be one of {list(LESIONWISE_CONNECTIVITIES)}, "
                          f"got {conn!r}")
-    v = get_config(lw, "min_lesion_voxels", 0)
-    scalar = isinstance(v, (bool, int))
-    vals = [v] * R if scalar else (list(v) if hasattr(v, "__iter__") and not isinstance(v, (str, bytes)) else None)
-    if vals is None or not all(isinstance(x, int) and not isinstance(x, bool) and x >= 0 for x in vals):
-        raise ValueError(f"evaluation.lesionwise.min_lesion_voxels must be a non-negative integer or a list of one per region, "
-                         f"got {v!r}")
-    if len(vals) != R:
-        raise ValueError(f"evaluation.lesionwise.min_lesion_voxels has {len(vals)} entries for the {R} regions of "
-                         f"evaluation.seg.region_order")
+    vals = _per_region(lw, "evaluation.lesionwise", "min_lesion_voxels", 0, R, _is_count, "a non-negative integer")
     return enable, int(dil), int(conn), [int(x) for x in vals]
+
+
+def stat_columns(stats: torch.Tensor) -> torch.Tensor:
+    """stats int64 [R,C] of one volume, as the component filter (components, kept, removed voxels) and the fill / nest pass
+    (holes, filled holes, filled voxels, nested voxels) leave them -> its table columns float64 [C*R], one column's regions
+    after another."""
+    return stats.to(torch.float64).t().reshape(-1)
 
 
 def lesionwise_columns(stats: torch.Tensor) -> torch.Tensor:
@@ -222,9 +218,7 @@ def lesionwise_hd95_config(config: Any) -> Tuple[bool, float, Any]:
     ``evaluation.lesionwise.enable``."""
     lw = get_config(config, "evaluation.lesionwise", {}) or {}
     hd = get_config(lw, "hd95", {}) or {}
-    enable = get_config(hd, "enable", False)
-    if not isinstance(enable, bool):
-        raise ValueError(f"evaluation.lesionwise.hd95.enable must be true or false, got {enable!r}")
+    enable = _enable(hd, "evaluation.lesionwise.hd95")
     pct = get_config(hd, "percentile", 95.0)
     if isinstance(pct, bool) or not isinstance(pct, (int, float)) or not 0.0 <= float(pct) <= 100.0:
         raise ValueError(f"evaluation.lesionwise.hd95.percentile must be a number in [0, 100], got {pct!r}")
@@ -282,9 +276,7 @@ def _nsd_block(config: Any, block: Any, key: str, default: Sequence[float]) -> T
     ``evaluation.seg.spacing`` must stay within 8 voxels per axis as well; the window depends on the spacing, so a disabled
     block - the shipped configs carry one, with the default tolerances - never stands in the way of an evaluation at a fine
     spacing."""
-    enable = get_config(block, "enable", False)
-    if not isinstance(enable, bool):
-        raise ValueError(f"{key}.enable must be true or false, got {enable!r}")
+    enable = _enable(block, key)
     tol = get_config(block, "tolerances", None)
     tol = list(default) if tol is None else tol
     vals = list(tol) if hasattr(tol, "__iter__") and not isinstance(tol, (str, bytes)) else None
@@ -389,284 +381,287 @@ def calibration_width(bins: int, rout: int) -> int:
     return int(rout) * (3 * int(bins) + 2) if bins else 0
 
 
-class RegionAccumulator:
-    """float64 sums / counts per region, overall and per domain (reference seg_eval.py:250-270,363-378).  ``bins`` > 0
-    adds the calibration figures: ``calibration_regions`` names their rows (default: the regions; ``["all"]`` for a softmax
-    head), ``reliability`` pools the bins of every row.  ``components`` adds the connected-component figures of the
-    post-processing: per-volume means over ALL volumes of components found, components kept and voxels removed.
-    ``lesionwise`` adds the lesion-wise figures: the lesion-wise Dice averaged over the volumes where it is defined (a
-    GT-empty region with false-positive components IS one of them, with 0), per-volume means of kept lesions, found
-    lesions and false-positive components, and recall / precision pooled over all volumes.  ``fill_nest`` adds the figures
-    of the hole filling and nesting pass: per-volume means over all volumes of holes, filled holes, filled voxels and voxels
-    the nesting changed.  ``lesionwise_hd95`` adds the lesion-wise HD95 averaged over the volumes where it is defined and did
-    not overflow, and the per-volume mean of overflowed volumes."""
+# ----------------------------------------------------------------------------- the per-volume table and its blocks
+class Block(NamedTuple):
+    """One optional group of columns of the per-volume table, and what becomes of it.  ``p`` is the block's parameter
+    (``table_layout``): ``True``, the tolerances of an NSD block, (bins, rows) of the calibration."""
+    name: str
+    width: Callable[[int, Any], int]                  # (R, p) -> doubles per row
+    shape: Callable[[int, Any], Tuple[int, ...]]      # (R, p) -> shape of the float64 accumulator
+    columns: Callable[[Dict[str, Any]], torch.Tensor]         # what the passes left of one volume, by pass -> its columns
+    add: Callable[[torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]], None]     # accumulator += columns; the whole row by block
+    keys: Callable[[Dict[str, float], str, torch.Tensor, Sequence[str], Any], None]        # out, prefix, accumulator, regions, p
 
-    def __init__(self, region_order: Sequence[str], surface: bool = False, bins: int = 0,
-                 calibration_regions: Optional[Sequence[str]] = None, components: bool = False, lesionwise: bool = False,
-                 fill_nest: bool = False, lesionwise_hd95: bool = False, surface_dice: Sequence[float] = (),
-                 lesionwise_nsd: Sequence[float] = ()):
-        self.regions = list(region_order)
-        # NSD: the tolerances (mm) of the region-wise and of the lesion-wise figure; empty = off.  Sums and counts [2, T, R]
-        self.surface_dice = [float(t) for t in surface_dice]
-        self.lesionwise_nsd = [float(t) for t in lesionwise_nsd]
-        nR = len(self.regions)
-        self._zsd = lambda: torch.zeros((2, len(self.surface_dice), nR), dtype=torch.float64)
-        self.sd_tot = self._zsd()
-        self.sd_dom: Dict[str, torch.Tensor] = defaultdict(self._zsd)
-        self._zln = lambda: torch.zeros((2, len(self.lesionwise_nsd), nR), dtype=torch.float64)
-        self.ln_tot = self._zln()
-        self.ln_dom: Dict[str, torch.Tensor] = defaultdict(self._zln)
-        self.surface = bool(surface)
-        R = len(self.regions)
-        self._z = lambda: torch.zeros(R, dtype=torch.float64)
-        # sum_dice, cnt_dice, sum_iou, cnt_iou, then (surface) sum_hd95, cnt_hd95, sum_asd, cnt_asd
-        self.tot = [self._z() for _ in range(8)]
-        self.dom: Dict[str, List[torch.Tensor]] = defaultdict(lambda: [self._z() for _ in range(8)])
-        self.total_loss, self.n_samples = 0.0, 0
-        self.bins = int(bins)
-        self.cal_regions = list(calibration_regions) if calibration_regions is not None else list(self.regions)
-        Rc = len(self.cal_regions)
-        self._zc = lambda: torch.zeros((4, Rc), dtype=torch.float64)         # sum_ece, sum_brier, sum_nll, count
-        self.cal_tot = self._zc()
-        self.cal_dom: Dict[str, torch.Tensor] = defaultdict(self._zc)
-        self.reliability = torch.zeros((Rc, max(self.bins, 0), 3), dtype=torch.float64)
-        self.components = bool(components)
-        self._zp = lambda: torch.zeros((4, R), dtype=torch.float64)          # sum_components, sum_kept, sum_removed, volumes
-        self.pp_tot = self._zp()
-        self.pp_dom: Dict[str, torch.Tensor] = defaultdict(self._zp)
-        self.lesionwise = bool(lesionwise)
-        # the 7 table columns summed (lw_dc, valid, kept, found, false-positive, matched, predicted), then the volumes
-        self._zl = lambda: torch.zeros((LESIONWISE_COLUMNS + 1, R), dtype=torch.float64)
-        self.lw_tot = self._zl()
-        self.lw_dom: Dict[str, torch.Tensor] = defaultdict(self._zl)
-        self.lesionwise_hd95 = bool(lesionwise_hd95)
-        self._zh = lambda: torch.zeros((4, R), dtype=torch.float64)          # sum_lw_hd95, valid volumes, overflowed volumes, volumes
-        self.lh_tot = self._zh()
-        self.lh_dom: Dict[str, torch.Tensor] = defaultdict(self._zh)
-        self.fill_nest = bool(fill_nest)
-        self._zf = lambda: torch.zeros((FILL_NEST_COLUMNS + 1, R), dtype=torch.float64)      # the 4 columns summed, then the volumes
-        self.fn_tot = self._zf()
-        self.fn_dom: Dict[str, torch.Tensor] = defaultdict(self._zf)
 
-    def add_fill_nest(self, stats: Any, domain: str) -> None:
-        """One volume's fill / nest figures, [4*R] as the table holds them: holes[R], filled holes[R], filled voxels[R],
-        nested voxels[R]."""
-        st = torch.as_tensor(stats, dtype=torch.float64).reshape(FILL_NEST_COLUMNS, len(self.regions))
-        for acc in (self.fn_tot, self.fn_dom[domain]):
-            acc[:FILL_NEST_COLUMNS] += st
-            acc[FILL_NEST_COLUMNS] += 1.0
+def _n(p: Any) -> int:
+    """A count, or the length of a list."""
+    return p if isinstance(p, int) else len(p)
 
-    def _fill_nest_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
-        for row, key in enumerate(ops.FILL_NEST_COLUMNS):
-            for name, v in zip(self.regions, self._fin(acc[row], acc[FILL_NEST_COLUMNS])):
-                out[f"{prefix}{name.lower()}_{key}"] = v
 
-    def add_lesionwise(self, cols: Any, domain: str) -> None:
-        """One volume's lesion-wise columns, [7*R] as the table holds them (``lesionwise_columns``)."""
-        c = torch.as_tensor(cols, dtype=torch.float64).reshape(LESIONWISE_COLUMNS, len(self.regions))
-        for acc in (self.lw_tot, self.lw_dom[domain]):
-            acc[0] += c[0] * c[1]
-            acc[1:LESIONWISE_COLUMNS] += c[1:]
-            acc[LESIONWISE_COLUMNS] += 1.0
+def _fin(s: torch.Tensor, c: torch.Tensor) -> List[float]:
+    return [float((s[k] / c[k]).item()) if c[k] > 0 else 0.0 for k in range(len(s))]
 
-    def _lesionwise_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
-        means = self._fin(acc[0], acc[1])
-        for name, v in zip(self.regions, means):
-            out[f"{prefix}{name.lower()}_lw_dc"] = v
-        out[f"{prefix}avg_lw_dc"] = self._avg(means, acc[1])
-        for row, key in ((2, "lesions"), (3, "lesions_found"), (4, "fp_components")):
-            for name, v in zip(self.regions, self._fin(acc[row], acc[LESIONWISE_COLUMNS])):
-                out[f"{prefix}{name.lower()}_{key}"] = v
-        for k, name in enumerate(self.regions):       # pooled over the volumes; absent where there is nothing to divide by
-            if acc[2][k] > 0:
-                out[f"{prefix}{name.lower()}_lesion_recall"] = float((acc[3][k] / acc[2][k]).item())
-            if acc[6][k] > 0:
-                out[f"{prefix}{name.lower()}_lesion_precision"] = float((acc[5][k] / acc[6][k]).item())
 
-    def add_lesionwise_hd95(self, cols: Any, domain: str) -> None:
-        """One volume's lesion-wise HD95 columns, [2*R] as the table holds them (``lesionwise_hd95_columns``)."""
-        c = torch.as_tensor(cols, dtype=torch.float64).reshape(LESIONWISE_HD95_COLUMNS, len(self.regions))
-        ok, over = (c[1] > 0.5).to(torch.float64), (c[1] < -0.5).to(torch.float64)
-        for acc in (self.lh_tot, self.lh_dom[domain]):
-            acc[0] += c[0] * ok
-            acc[1] += ok
-            acc[2] += over
-            acc[3] += 1.0
+def _avg(means: List[float], cnt: torch.Tensor) -> float:
+    ok = [k for k in range(len(means)) if cnt[k] > 0]
+    return float(sum(means[k] for k in ok) / max(1, len(ok)))
 
-    def _lesionwise_hd95_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
-        means = self._fin(acc[0], acc[1])
-        for name, v in zip(self.regions, means):
-            out[f"{prefix}{name.lower()}_lw_hd95"] = v
-        out[f"{prefix}avg_lw_hd95"] = self._avg(means, acc[1])
-        for name, v in zip(self.regions, self._fin(acc[2], acc[3])):
-            out[f"{prefix}{name.lower()}_lw_hd95_overflow"] = v
 
-    def add_surface_dice(self, cols: Any, valid: Sequence[bool], domain: str) -> None:
-        """One volume's NSD columns, [T*R] as the table holds them (``surface_dice_columns``); ``valid`` is Dice's."""
-        c = torch.as_tensor(cols, dtype=torch.float64).reshape(len(self.surface_dice), len(self.regions))
-        ok = torch.tensor([1.0 if bool(v) else 0.0 for v in valid], dtype=torch.float64)
-        for acc in (self.sd_tot, self.sd_dom[domain]):
-            acc[0] += c * ok
-            acc[1] += ok
+def _mean_keys(out: Dict[str, float], prefix: str, names: Sequence[str], key: str, s: torch.Tensor, c: torch.Tensor,
+               avg: bool = True) -> None:
+    """``{name}_{key}`` = s / c (0 where c is 0) and, with ``avg``, ``avg_{key}``: their mean over the names with c > 0."""
+    means = _fin(s, c)
+    for name, v in zip(names, means):
+        out[f"{prefix}{name.lower()}_{key}"] = v
+    if avg:
+        out[f"{prefix}avg_{key}"] = _avg(means, c)
 
-    def add_lesionwise_nsd(self, cols: Any, lesionwise: Any, domain: str) -> None:
-        """One volume's lesion-wise NSD columns, [T*R] as the table holds them (``lesionwise_nsd_columns``); defined where the
-        volume's lesion-wise Dice is (the ``valid`` row of its ``lesionwise_columns``)."""
-        c = torch.as_tensor(cols, dtype=torch.float64).reshape(len(self.lesionwise_nsd), len(self.regions))
-        ok = torch.as_tensor(lesionwise, dtype=torch.float64).reshape(LESIONWISE_COLUMNS, len(self.regions))[1]
-        for acc in (self.ln_tot, self.ln_dom[domain]):
-            acc[0] += c * ok
-            acc[1] += ok
 
-    def _nsd_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor, tolerances: Sequence[float], stem: str) -> None:
+def _add_surface(acc: torch.Tensor, c: torch.Tensor, vol: Dict[str, torch.Tensor]) -> None:
+    """sum_hd95, sum_asd, count: over the volumes where Dice is valid (an invalid entry may hold anything)."""
+    acc[:2] += torch.where(vol["valid"] > 0, c.reshape(2, -1), 0.0)
+    acc[2] += vol["valid"]
+
+
+def _surface_keys(out, prefix, acc, regions, p) -> None:      # reference seg_eval.py:424-440, :459-476
+    _mean_keys(out, prefix, regions, "hd95", acc[0], acc[2])
+    _mean_keys(out, prefix, regions, "asd", acc[1], acc[2])
+
+
+def _add_sums(acc: torch.Tensor, c: torch.Tensor, vol: Dict[str, torch.Tensor]) -> None:
+    """The columns summed, then the volumes: per-volume means over ALL volumes."""
+    acc[:-1] += c.reshape(acc.shape[0] - 1, -1)
+    acc[-1] += 1.0
+
+
+def _component_keys(out, prefix, acc, regions, p) -> None:
+    for row, key in enumerate(("components", "kept_components", "removed_voxels")):
+        _mean_keys(out, prefix, regions, key, acc[row], acc[-1], avg=row == 0)
+
+
+def _fill_nest_keys(out, prefix, acc, regions, p) -> None:
+    for row, key in enumerate(ops.FILL_NEST_COLUMNS):
+        _mean_keys(out, prefix, regions, key, acc[row], acc[-1], avg=False)
+
+
+def _add_lesionwise(acc: torch.Tensor, c: torch.Tensor, vol: Dict[str, torch.Tensor]) -> None:
+    """The 7 columns summed (lw_dc where valid, valid, kept, found, false-positive, matched, predicted), then the volumes."""
+    c = c.reshape(LESIONWISE_COLUMNS, -1)
+    acc[0] += c[0] * c[1]
+    acc[1:LESIONWISE_COLUMNS] += c[1:]
+    acc[LESIONWISE_COLUMNS] += 1.0
+
+
+def _lesionwise_keys(out, prefix, acc, regions, p) -> None:
+    """The lesion-wise Dice averaged over the volumes where it is defined (a GT-empty region with false-positive components
+    IS one of them, with 0), per-volume means of kept lesions, found lesions and false-positive components, and recall /
+    precision pooled over all volumes."""
+    _mean_keys(out, prefix, regions, "lw_dc", acc[0], acc[1])
+    for row, key in ((2, "lesions"), (3, "lesions_found"), (4, "fp_components")):
+        _mean_keys(out, prefix, regions, key, acc[row], acc[LESIONWISE_COLUMNS], avg=False)
+    for k, name in enumerate(regions):       # pooled over the volumes; absent where there is nothing to divide by
+        if acc[2][k] > 0:
+            out[f"{prefix}{name.lower()}_lesion_recall"] = float((acc[3][k] / acc[2][k]).item())
+        if acc[6][k] > 0:
+            out[f"{prefix}{name.lower()}_lesion_precision"] = float((acc[5][k] / acc[6][k]).item())
+
+
+def _add_lesionwise_hd95(acc: torch.Tensor, c: torch.Tensor, vol: Dict[str, torch.Tensor]) -> None:
+    """sum_lw_hd95, valid volumes, overflowed volumes, volumes."""
+    c = c.reshape(LESIONWISE_HD95_COLUMNS, -1)
+    ok, over = (c[1] > 0.5).to(torch.float64), (c[1] < -0.5).to(torch.float64)
+    acc[0] += c[0] * ok
+    acc[1] += ok
+    acc[2] += over
+    acc[3] += 1.0
+
+
+def _lesionwise_hd95_keys(out, prefix, acc, regions, p) -> None:
+    """The lesion-wise HD95 averaged over the volumes where it is defined and did not overflow, and the per-volume mean of
+    overflowed volumes."""
+    _mean_keys(out, prefix, regions, "lw_hd95", acc[0], acc[1])
+    _mean_keys(out, prefix, regions, "lw_hd95_overflow", acc[2], acc[3], avg=False)
+
+
+def _add_nsd(acc: torch.Tensor, c: torch.Tensor, ok: torch.Tensor) -> None:
+    """Sums and counts [2, T, R] over the volumes where ``ok`` [R] is 1."""
+    acc[0] += c.reshape(acc.shape[1:]) * ok
+    acc[1] += ok
+
+
+def _nsd_keys(stem: str) -> Callable:
+    def keys(out, prefix, acc, regions, tolerances) -> None:
         for t, tau in enumerate(tolerances):
-            means = self._fin(acc[0][t], acc[1][t])
-            for name, v in zip(self.regions, means):
-                out[f"{prefix}{name.lower()}_{stem}_{nsd_suffix(tau)}"] = v
-            out[f"{prefix}avg_{stem}_{nsd_suffix(tau)}"] = self._avg(means, acc[1][t])
+            _mean_keys(out, prefix, regions, f"{stem}_{nsd_suffix(tau)}", acc[0][t], acc[1][t])
+    return keys
 
-    def add_components(self, stats: Any, domain: str) -> None:
-        """One volume's component figures, [3*R] as the table holds them: components[R], kept[R], removed voxels[R]."""
-        st = torch.as_tensor(stats, dtype=torch.float64).reshape(3, len(self.regions))
-        for acc in (self.pp_tot, self.pp_dom[domain]):
-            acc[:3] += st
-            acc[3] += 1.0
 
-    def _component_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
-        for row, key in enumerate(("components", "kept_components", "removed_voxels")):
-            means = self._fin(acc[row], acc[3])
-            for name, v in zip(self.regions, means):
-                out[f"{prefix}{name.lower()}_{key}"] = v
-            if row == 0:
-                out[f"{prefix}avg_components"] = self._avg(means, acc[3])
+def _add_calibration(acc: torch.Tensor, c: torch.Tensor, vol: Dict[str, torch.Tensor]) -> None:
+    """Per row of the head: sum_ece, sum_brier, sum_nll, count, then its 3*bins reliability entries pooled."""
+    raw = c.reshape(acc.shape[0], -1)
+    ece, brier, nll, valid = calibration_from_bins(raw)
+    ok = valid.to(torch.float64)
+    acc[:, 0] += ece * ok
+    acc[:, 1] += brier * ok
+    acc[:, 2] += nll * ok
+    acc[:, 3] += ok
+    acc[:, 4:] += raw[:, :-2]
 
-    def add_calibration(self, raw: torch.Tensor, domain: str) -> None:
-        """One volume's table, float64 [Rout, 3*bins + 2] (or flat)."""
-        raw = raw.to(torch.float64).reshape(len(self.cal_regions), 3 * self.bins + 2)
-        ece, brier, nll, valid = calibration_from_bins(raw)
-        ok = valid.to(torch.float64)
-        for acc in (self.cal_tot, self.cal_dom[domain]):
-            acc[0] += ece * ok
-            acc[1] += brier * ok
-            acc[2] += nll * ok
-            acc[3] += ok
-        self.reliability += raw[:, :3 * self.bins].reshape(-1, self.bins, 3)
 
-    def _calibration_keys(self, out: Dict[str, float], prefix: str, acc: torch.Tensor) -> None:
-        for row, key in enumerate(("ece", "brier", "nll")):
-            means = self._fin(acc[row], acc[3])
-            for name, v in zip(self.cal_regions, means):
-                out[f"{prefix}{name.lower()}_{key}"] = v
-            out[f"{prefix}avg_{key}"] = self._avg(means, acc[3])
+def _calibration_keys(out, prefix, acc, regions, p) -> None:
+    for col, key in enumerate(("ece", "brier", "nll")):
+        _mean_keys(out, prefix, p[1], key, acc[:, col], acc[:, 3])
+
+
+# The optional blocks of a table row, in column order; the same order governs the metric keys.  A row is
+#     index, domain_id, loss, dice[R], iou[R], valid[R]
+# and then, for every enabled block, what its ``*_columns`` function makes of one volume (one column's or one tolerance's
+# regions after another).  Region-wise NSD is valid where Dice's ``valid`` is, lesion-wise NSD where the ``valid`` row of the
+# volume's lesion-wise columns is.  The calibration, the volume's raw table of ``ops.calibration_bins``, is last, so
+# ``reliability_from_table`` finds it at the row's end.
+BLOCKS: Tuple[Block, ...] = (
+    Block("surface", lambda R, p: 2 * R, lambda R, p: (3, R), lambda v: v["surface"], _add_surface, _surface_keys),
+    Block("components", lambda R, p: 3 * R, lambda R, p: (4, R), lambda v: stat_columns(v["components"]), _add_sums,
+          _component_keys),
+    Block("fill_nest", lambda R, p: FILL_NEST_COLUMNS * R, lambda R, p: (FILL_NEST_COLUMNS + 1, R),
+          lambda v: stat_columns(v["fill_nest"]), _add_sums, _fill_nest_keys),
+    Block("lesionwise", lambda R, p: LESIONWISE_COLUMNS * R, lambda R, p: (LESIONWISE_COLUMNS + 1, R),
+          lambda v: lesionwise_columns(v["lesionwise"]), _add_lesionwise, _lesionwise_keys),
+    Block("lesionwise_hd95", lambda R, p: LESIONWISE_HD95_COLUMNS * R, lambda R, p: (4, R),
+          lambda v: lesionwise_hd95_columns(v["lesionwise"], v["lesionwise_hd95"], v["penalty"]), _add_lesionwise_hd95,
+          _lesionwise_hd95_keys),
+    Block("lesionwise_nsd", lambda R, p: _n(p) * R, lambda R, p: (2, _n(p), R),
+          lambda v: lesionwise_nsd_columns(v["lesionwise"], v["lesionwise_nsd"]),
+          lambda acc, c, vol: _add_nsd(acc, c, vol["lesionwise"].reshape(LESIONWISE_COLUMNS, -1)[1]), _nsd_keys("lw_nsd")),
+    Block("surface_dice", lambda R, p: _n(p) * R, lambda R, p: (2, _n(p), R), lambda v: surface_dice_columns(v["surface_dice"]),
+          lambda acc, c, vol: _add_nsd(acc, c, vol["valid"]), _nsd_keys("nsd")),
+    Block("calibration", lambda R, p: _n(p[1]) * (3 * p[0] + 2), lambda R, p: (_n(p[1]), 4 + 3 * p[0]),
+          lambda v: v["calibration"].reshape(-1), _add_calibration, _calibration_keys),
+)
+
+
+class Layout(NamedTuple):
+    width: int                      # doubles per row
+    slices: Dict[str, slice]        # the enabled blocks' columns, in column order
+    params: Dict[str, Any]          # every block's parameter; false or empty = off
+
+
+def table_layout(regions: Any, surface: bool = False, bins: int = 0, calibration_regions: Any = None,
+                 components: bool = False, lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False,
+                 surface_dice: Any = (), lesionwise_nsd: Any = ()) -> Layout:
+    """Where the enabled blocks sit in a row.  ``regions`` and ``calibration_regions`` are names, or just how many there are;
+    ``bins`` > 0 switches the calibration on, with one row per calibration region (default: the regions; ``["all"]`` for a
+    softmax head); ``surface_dice`` and ``lesionwise_nsd`` are tolerances in mm, or their number."""
+    R = _n(regions)
+    params = {"surface": surface, "components": components, "fill_nest": fill_nest, "lesionwise": lesionwise,
+              "lesionwise_hd95": lesionwise_hd95, "lesionwise_nsd": lesionwise_nsd, "surface_dice": surface_dice,
+              "calibration": (int(bins), regions if calibration_regions is None else calibration_regions) if bins else None}
+    at, slices = 3 + 3 * R, {}
+    for b in BLOCKS:
+        if params[b.name]:
+            slices[b.name] = slice(at, at + b.width(R, params[b.name]))
+            at = slices[b.name].stop
+    return Layout(at, slices, params)
+
+
+def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None, **switches) -> int:
+    """Doubles per table row for the switches of ``table_layout``; ``rout``: the calibration's rows, default R."""
+    return table_layout(R, surface, bins, rout, **switches).width
+
+
+ADD_ROW_POSITIONAL = ("calibration", "components", "lesionwise", "fill_nest", "lesionwise_hd95", "surface_dice", "lesionwise_nsd")
+
+
+class RegionAccumulator:
+    """float64 sums / counts per region, overall and per domain (reference seg_eval.py:250-270,363-378), for Dice / IoU and
+    for every block the switches of ``table_layout`` enable; ``reliability`` pools the calibration bins of every row."""
+
+    def __init__(self, region_order: Sequence[str], *switches, **named):
+        self.regions = list(region_order)
+        self.layout = table_layout(self.regions, *switches, **named)
+        self.blocks = [b for b in BLOCKS if b.name in self.layout.slices]
+        for name, p in self.layout.params.items():       # acc.lesionwise, acc.surface_dice, ...: the switches as given
+            setattr(self, name, p)
+        self.bins, self.cal_regions = self.layout.params["calibration"] or (0, self.regions)
+        R = len(self.regions)
+        shapes = {"dice": (3, R)}            # sum_dice, sum_iou, count
+        shapes.update({b.name: b.shape(R, self.layout.params[b.name]) for b in self.blocks})
+        # one accumulator per block and domain; the key None holds the whole split
+        self.acc = {name: defaultdict(lambda s=s: torch.zeros(s, dtype=torch.float64)) for name, s in shapes.items()}
+        self.total_loss, self.n_samples = 0.0, 0
+
+    @property
+    def reliability(self) -> torch.Tensor:
+        """The pooled reliability diagram, float64 [rows, bins, 3] = (count, sum of confidence, correct count)."""
+        if not self.bins:
+            return torch.zeros((_n(self.cal_regions), 0, 3), dtype=torch.float64)
+        return self.acc["calibration"][None][:, 4:].reshape(-1, self.bins, 3).clone()
 
     def add_row(self, dice: Sequence[float], iou: Sequence[float], valid: Sequence[bool], domain: str,
-                hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None,
-                calibration: Optional[torch.Tensor] = None, components: Any = None, lesionwise: Any = None,
-                fill_nest: Any = None, lesionwise_hd95: Any = None, surface_dice: Any = None,
-                lesionwise_nsd: Any = None) -> None:
-        d = self.dom[domain]
-        if self.surface_dice:
-            self.add_surface_dice(surface_dice, valid, domain)
-        if self.lesionwise_nsd:
-            self.add_lesionwise_nsd(lesionwise_nsd, lesionwise, domain)
-        if self.components:
-            self.add_components(components, domain)
-        if self.fill_nest:
-            self.add_fill_nest(fill_nest, domain)
-        if self.lesionwise:
-            self.add_lesionwise(lesionwise, domain)
-        if self.lesionwise_hd95:
-            self.add_lesionwise_hd95(lesionwise_hd95, domain)
-        if self.bins:
-            self.add_calibration(calibration, domain)
-        for c in range(len(self.regions)):
-            if bool(valid[c]):
-                dv, iv = float(dice[c]), float(iou[c])
-                for acc in (self.tot, d):
-                    acc[0][c] += dv
-                    acc[1][c] += 1.0
-                    acc[2][c] += iv
-                    acc[3][c] += 1.0
-                if self.surface:
-                    hv, av = float(hd95[c]), float(asd[c])
-                    for acc in (self.tot, d):
-                        acc[4][c] += hv
-                        acc[5][c] += 1.0
-                        acc[6][c] += av
-                        acc[7][c] += 1.0
+                hd95: Optional[Sequence[float]] = None, asd: Optional[Sequence[float]] = None, *earlier: Any, **cols: Any) -> None:
+        """One volume.  ``cols``: the columns of every enabled block under the block's name, as the table holds them
+        (``hd95`` and ``asd`` together are the ``surface`` block's).  ``earlier``: callers from before the block list pass
+        some columns by position (``ADD_ROW_POSITIONAL``); that order is frozen, a new block is passed by name only."""
+        if len(earlier) > len(ADD_ROW_POSITIONAL):
+            raise TypeError(f"add_row takes at most {len(ADD_ROW_POSITIONAL)} columns by position, got {len(earlier)}")
+        cols.update(zip(ADD_ROW_POSITIONAL, earlier))
+        unknown = set(cols) - set(self.layout.params)
+        if unknown:
+            raise TypeError(f"add_row: no such block {sorted(unknown)}")
+        vol = {k: torch.as_tensor(v, dtype=torch.float64).reshape(-1) for k, v in cols.items() if v is not None}
+        if hd95 is not None:
+            vol["surface"] = torch.cat([torch.as_tensor(hd95, dtype=torch.float64), torch.as_tensor(asd, dtype=torch.float64)])
+        vol["valid"] = torch.tensor([1.0 if bool(v) else 0.0 for v in valid], dtype=torch.float64)
+        both = torch.stack([torch.as_tensor(dice, dtype=torch.float64), torch.as_tensor(iou, dtype=torch.float64)])
+        for dom in (None, domain):
+            acc = self.acc["dice"][dom]
+            acc[:2] += torch.where(vol["valid"] > 0, both, 0.0)
+            acc[2] += vol["valid"]
+            for b in self.blocks:
+                b.add(self.acc[b.name][dom], vol[b.name], vol)
+
+    def add_table(self, table: torch.Tensor, domain_names: Sequence[str], with_loss: bool) -> None:
+        """The rows of a per-volume table, in their order; ``with_loss``: each row's loss as one sample."""
+        R = len(self.regions)
+        for row in table:
+            d = int(row[1].item())
+            cols = {name: row[s] for name, s in self.layout.slices.items()}
+            if "surface" in cols:               # Dice, IoU, HD95 and ASD are fp32 values, read as such
+                cols["surface"] = cols["surface"].to(torch.float32)
+            self.add_row(row[3:3 + R].to(torch.float32), row[3 + R:3 + 2 * R].to(torch.float32),
+                         (row[3 + 2 * R:3 + 3 * R] > 0.5).tolist(), domain_names[d] if 0 <= d < len(domain_names) else "", **cols)
+            if with_loss:
+                self.add_loss(float(row[2].item()), 1)
 
     def add_loss(self, loss: float, batch: int) -> None:
         self.total_loss += float(loss) * batch
         self.n_samples += batch
 
-    @staticmethod
-    def _fin(s: torch.Tensor, c: torch.Tensor) -> List[float]:
-        return [float((s[k] / c[k]).item()) if c[k] > 0 else 0.0 for k in range(len(s))]
-
-    @staticmethod
-    def _avg(means: List[float], cnt: torch.Tensor) -> float:
-        ok = [k for k in range(len(means)) if cnt[k] > 0]
-        return float(sum(means[k] for k in ok) / max(1, len(ok)))
+    def _keys(self, out: Dict[str, float], prefix: str, dom: Optional[str], loss: Optional[float] = None) -> None:
+        acc = self.acc["dice"][dom]
+        _mean_keys(out, prefix, self.regions, "dc", acc[0], acc[2])
+        out[f"{prefix}miou"] = _avg(_fin(acc[1], acc[2]), acc[2])
+        if loss is not None:
+            out["jc"] = out["miou"]
+            out["loss"] = loss
+        for b in self.blocks:
+            b.keys(out, prefix, self.acc[b.name][dom], self.regions, self.layout.params[b.name])
 
     def metrics(self, report_loss: bool) -> Dict[str, float]:
-        md, mi = self._fin(self.tot[0], self.tot[1]), self._fin(self.tot[2], self.tot[3])
         out: Dict[str, float] = {}
-        for name, v in zip(self.regions, md):
-            out[f"{name.lower()}_dc"] = v
-        out["avg_dc"] = self._avg(md, self.tot[1])
-        out["miou"] = self._avg(mi, self.tot[3])
-        out["jc"] = out["miou"]
-        out["loss"] = float(self.total_loss / max(1, self.n_samples)) if report_loss else 0.0
-        if self.surface:        # reference seg_eval.py:424-440
-            self._surface_keys(out, "", self.tot)
-        if self.components:
-            self._component_keys(out, "", self.pp_tot)
-        if self.fill_nest:
-            self._fill_nest_keys(out, "", self.fn_tot)
-        if self.lesionwise:
-            self._lesionwise_keys(out, "", self.lw_tot)
-        if self.lesionwise_hd95:
-            self._lesionwise_hd95_keys(out, "", self.lh_tot)
-        if self.lesionwise_nsd:
-            self._nsd_keys(out, "", self.ln_tot, self.lesionwise_nsd, "lw_nsd")
-        if self.surface_dice:
-            self._nsd_keys(out, "", self.sd_tot, self.surface_dice, "nsd")
-        if self.bins:
-            self._calibration_keys(out, "", self.cal_tot)
-        for dom in sorted(self.dom.keys()):
-            sd, cd, si, ci = self.dom[dom][:4]
-            safe = dom if dom != "" else "unknown"
-            dm, dim_ = self._fin(sd, cd), self._fin(si, ci)
-            for name, v in zip(self.regions, dm):
-                out[f"dom/{safe}/{name.lower()}_dc"] = v
-            out[f"dom/{safe}/avg_dc"] = self._avg(dm, cd)
-            out[f"dom/{safe}/miou"] = self._avg(dim_, ci)
-            if self.surface:    # reference seg_eval.py:459-476
-                self._surface_keys(out, f"dom/{safe}/", self.dom[dom])
-            if self.components:
-                self._component_keys(out, f"dom/{safe}/", self.pp_dom[dom])
-            if self.fill_nest:
-                self._fill_nest_keys(out, f"dom/{safe}/", self.fn_dom[dom])
-            if self.lesionwise:
-                self._lesionwise_keys(out, f"dom/{safe}/", self.lw_dom[dom])
-            if self.lesionwise_hd95:
-                self._lesionwise_hd95_keys(out, f"dom/{safe}/", self.lh_dom[dom])
-            if self.lesionwise_nsd:
-                self._nsd_keys(out, f"dom/{safe}/", self.ln_dom[dom], self.lesionwise_nsd, "lw_nsd")
-            if self.surface_dice:
-                self._nsd_keys(out, f"dom/{safe}/", self.sd_dom[dom], self.surface_dice, "nsd")
-            if self.bins:
-                self._calibration_keys(out, f"dom/{safe}/", self.cal_dom[dom])
+        self._keys(out, "", None, float(self.total_loss / max(1, self.n_samples)) if report_loss else 0.0)
+        for dom in sorted(d for d in self.acc["dice"] if d is not None):
+            self._keys(out, f"dom/{dom if dom != '' else 'unknown'}/", dom)
         return out
 
-    def _surface_keys(self, out: Dict[str, float], prefix: str, acc: List[torch.Tensor]) -> None:
-        mh, ma = self._fin(acc[4], acc[5]), self._fin(acc[6], acc[7])
-        for name, v in zip(self.regions, mh):
-            out[f"{prefix}{name.lower()}_hd95"] = v
-        out[f"{prefix}avg_hd95"] = self._avg(mh, acc[5])
-        for name, v in zip(self.regions, ma):
-            out[f"{prefix}{name.lower()}_asd"] = v
-        out[f"{prefix}avg_asd"] = self._avg(ma, acc[7])
+
+def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_names: Sequence[str], report_loss: bool,
+                       *switches, **named) -> Dict[str, float]:
+    """Replay the reference aggregation over gathered rows in volume-index order: the result is identical to a
+    single-process run (float64 sums, order fixed by index).  The switches are those of ``table_layout``."""
+    acc = RegionAccumulator(region_order, *switches, **named)
+    acc.add_table(table, domain_names, report_loss)
+    return acc.metrics(report_loss)
 
 
 class DiceCEReport:
@@ -728,6 +723,8 @@ class DiceCEReport:
 # ----------------------------------------------------------------------------- seg_eval
 @register_evaluation_strategy("seg_eval")
 class SegmentationEvaluationStrategy:
+    gather_masks = False         # seg_tta_eval's `evaluation.gather_masks`: keep the scored mask for the second collective
+
     def __init__(self, config: Any = None):
         self.config = as_cfg(config)
         seg = get_config(self.config, "evaluation.seg", {}) or {}
@@ -755,13 +752,11 @@ class SegmentationEvaluationStrategy:
         # the filtered mask (calibration and the reported loss stay on the logits)
         (self.enable_postprocess, self.postprocess_connectivity, self.postprocess_min_voxels,
          self.postprocess_keep_largest) = postprocess_config(self.config)
-        self._stats: Optional[torch.Tensor] = None
         # hole filling and ET < TC < WT nesting of the filtered mask, in place right after the filter; the pass is queued
         # only when post-processing is on and a region fills or a chain is given, and only then do its keys appear
         (self.postprocess_fill_holes, self.postprocess_fill_connectivity, self.postprocess_max_hole_voxels,
          self.postprocess_nesting, self.postprocess_nesting_mode) = fill_nest_config(self.config)
         self.enable_fill_nest = self.enable_postprocess and (any(self.postprocess_fill_holes) or bool(self.postprocess_nesting))
-        self._fill: Optional[torch.Tensor] = None
         # lesion-wise Dice and detection counts on the GPU, off by default: ground-truth lesions (dilated, 26-connected)
         # against the predicted components of the mask that is scored (the filtered one with post-processing on)
         (self.enable_lesionwise, self.lesionwise_dilation, self.lesionwise_connectivity,
@@ -769,11 +764,9 @@ class SegmentationEvaluationStrategy:
         if self.enable_lesionwise and bool(get_config(self.config, "training.criterion.softmax", False)):
             raise NotImplementedError("evaluation.lesionwise.enable: lesion-wise scores are defined for the sigmoid-region head "
                                       "only (training.criterion.softmax is set)")
-        self._lw: Optional[torch.Tensor] = None
         # lesion-wise HD95 on top of that, off by default: one more pass behind the lesion-wise scores, on their scratch
         (self.enable_lesionwise_hd95, self.lesionwise_hd95_percentile,
          self.lesionwise_hd95_penalty) = lesionwise_hd95_config(self.config)
-        self._lwhd: Optional[torch.Tensor] = None
         # normalised surface Dice at tolerances in mm, off by default: region-wise on the final mask (one bounded search over
         # bit-packed edge masks, no distance transform), and lesion-wise behind the lesion-wise scores, on their scratch
         self.enable_surface_dice, self.surface_dice_tolerances = surface_dice_config(self.config)
@@ -783,8 +776,6 @@ class SegmentationEvaluationStrategy:
             if on and bool(get_config(self.config, "training.criterion.softmax", False)):
                 raise NotImplementedError(f"{key}: the normalised surface Dice is defined for the sigmoid-region head only "
                                           f"(training.criterion.softmax is set)")
-        self._sd: Optional[torch.Tensor] = None
-        self._lwnsd: Optional[torch.Tensor] = None
         # input pre-pass on the GPU (raw volumes in, the reference's `_normalize_img` applied here instead of in the
         # dataset worker; reference src/datasets/transforms.py:129-223).  The NIfTI datasets of this package hand over
         # raw intensities, so the pre-pass defaults to on for them and to off for the synthetic source (already
@@ -842,11 +833,6 @@ class SegmentationEvaluationStrategy:
                             self.postprocess_max_hole_voxels, self.postprocess_nesting, self.postprocess_nesting_mode)
         return res["counts"], res["stats"]
 
-    @staticmethod
-    def fill_nest_columns(stats: torch.Tensor) -> torch.Tensor:
-        """stats int64 [R,4] of one volume -> its table columns float64 [4*R], one column's regions after another."""
-        return stats.to(torch.float64).t().reshape(-1)
-
     def lesionwise_launch(self, mask: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """Queue the lesion-wise scores of (mask, y) on the current stream -> device stats int64 [B,R,7]."""
         return ops.lesionwise_scores(mask, y, self.lesionwise_dilation, self.lesionwise_connectivity,
@@ -884,50 +870,76 @@ class SegmentationEvaluationStrategy:
             return volume_diagonal_mm(shape, self.spacing)
         return float(self.lesionwise_hd95_penalty)
 
-    @staticmethod
-    def component_columns(stats: torch.Tensor) -> torch.Tensor:
-        """stats int64 [R,3] of one volume -> its table columns float64 [3*R]: components[R], kept[R], removed voxels[R]."""
-        return stats.to(torch.float64).t().reshape(-1)
+    component_columns = fill_nest_columns = staticmethod(stat_columns)
 
-    def score(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
-        """logits [B,R,D,H,W] (or channels-last view) + labels -> exact counts int64 [B,R,3] on the host.
-        With ``evaluation.surface.enable`` the prediction mask is kept for :meth:`surface`.  With
-        ``evaluation.postprocess.enable`` the mask is filtered in place, the counts are those of the filtered mask and
-        ``self._stats`` holds the component figures int64 [B,R,3] (host); with hole filling or nesting on top the counts
-        are those of the final mask and ``self._fill`` holds that pass's figures int64 [B,R,4] (host)."""
-        R = y.shape[1]
-        shape_ok = (logits.ndim == 5 and (logits.shape[-1] if channels_last else logits.shape[1]) == R)
-        if not shape_ok:
+    def switches(self) -> Dict[str, Any]:
+        """The table's switches as ``table_layout`` takes them, from the ``enable_*`` attributes as they stand now."""
+        return dict(surface=self.enable_surface, bins=self.cal_bins, calibration_regions=self.calibration_regions,
+                    components=self.enable_postprocess, fill_nest=self.enable_fill_nest, lesionwise=self.enable_lesionwise,
+                    lesionwise_hd95=self.enable_lesionwise_hd95, surface_dice=self.sd_tolerances,
+                    lesionwise_nsd=self.ln_tolerances)
+
+    def layout(self) -> Layout:
+        return table_layout(self.region_order, **self.switches())
+
+    def queue_passes(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> Dict[str, Any]:
+        """Queue every enabled pass over logits [B,R,D,H,W] (or their channels-last view) and labels on the current stream ->
+        the job: device tensors, nothing read.  ``counts`` int64 [B,R,3] are those of the mask that is scored - thresholded,
+        then filtered in place with ``evaluation.postprocess.enable``, then filled and nested - and ``raw`` holds what each
+        further pass left, by block; calibration and the reported loss stay on the logits.  ``table_rows`` reads it."""
+        B, R = y.shape[0], y.shape[1]
+        if not (logits.ndim == 5 and (logits.shape[-1] if channels_last else logits.shape[1]) == R):
             raise ValueError(f"[BratsSegEval] model logits must be [B,{R},D,H,W], got {tuple(logits.shape)}")
-        counts = torch.empty((y.shape[0], R, 3), dtype=torch.int64, device=y.device)
-        need_mask = self.enable_surface or self.enable_postprocess or self.enable_lesionwise or self.enable_surface_dice
-        self._mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if need_mask else None
-        ops.mask_dice_counts(logits, y, self.threshold, counts, self._mask, logits_channels_last=channels_last)
-        self._stats = self._fill = None
-        if self.enable_postprocess:
-            counts, stats = self.postprocess_launch(self._mask, y)
-            if self.enable_fill_nest:
-                counts, fill = self.fill_nest_launch(self._mask, y)
-                self._fill = fill.cpu()
-            self._stats = stats.cpu()
-        self._lw = self._lwhd = self._sd = self._lwnsd = None
-        lw = lwhd = None
-        if self.enable_lesionwise_hd95:
-            lw, lwhd = self.lesionwise_hd95_launch(self._mask, y)
-        elif self.enable_lesionwise:
-            lw = self.lesionwise_launch(self._mask, y)
-        # the NSD passes are queued behind the lesion-wise ones, before the first host read
-        lwnsd = self.lesionwise_nsd_launch(self._mask) if self.enable_lesionwise_nsd else None
-        sd = self.surface_dice_launch(self._mask, y) if self.enable_surface_dice else None
-        if lw is not None:
-            self._lw = lw.cpu()
-        if lwhd is not None:
-            self._lwhd = lwhd.cpu()
-        if lwnsd is not None:
-            self._lwnsd = lwnsd.cpu()
-        if sd is not None:
-            self._sd = sd.cpu()
-        return counts.cpu()
+        on = self.layout().slices
+        counts = torch.empty((B, R, 3), dtype=torch.int64, device=y.device)
+        need_mask = self.gather_masks or bool(on.keys() - {"calibration"})       # every other block reads the mask
+        mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if need_mask else None
+        ops.mask_dice_counts(logits, y, self.threshold, counts, mask, logits_channels_last=channels_last)
+        raw: Dict[str, Any] = {}
+        if "components" in on:           # in place: every pass below and the gathered masks take the filtered mask
+            counts, raw["components"] = self.postprocess_launch(mask, y)
+        if "fill_nest" in on:            # likewise in place, right behind the filter: its counts replace the filter's
+            counts, raw["fill_nest"] = self.fill_nest_launch(mask, y)
+        if "lesionwise_hd95" in on:      # right behind the counts, on the mask they describe; the HD95 pass on the same scratch
+            raw["lesionwise"], raw["lesionwise_hd95"] = self.lesionwise_hd95_launch(mask, y)
+        elif "lesionwise" in on:
+            raw["lesionwise"] = self.lesionwise_launch(mask, y)
+        if "lesionwise_nsd" in on:       # directly behind the lesion-wise passes, same stream and mask: it reads their scratch
+            raw["lesionwise_nsd"] = self.lesionwise_nsd_launch(mask)
+        if "surface_dice" in on:         # on the final mask, like the surface distances
+            raw["surface_dice"] = self.surface_dice_launch(mask, y)
+        job: Dict[str, Any] = {"counts": counts, "shape": tuple(y.shape[2:]), "mask": mask, "raw": raw,
+                               "penalty": self.lesionwise_hd95_penalty_mm(y.shape[2:])}
+        if self.report_loss:
+            job["loss"] = self.loss_fn.launch(logits, y, channels_last=channels_last)
+        if "surface" in on:
+            raw["surface"] = self.surface_launch(mask, y)
+        if "calibration" in on:
+            raw["calibration"] = self.calibration_launch(logits, y, channels_last=channels_last)
+        return job
+
+    def table_rows(self, job: Dict[str, Any]) -> List[torch.Tensor]:
+        """First host read of a queued job (with ``index`` and ``domain_id`` per volume added) -> the table rows of its
+        volumes, the blocks in the order of ``BLOCKS``."""
+        counts = job["counts"].cpu()
+        dice, iou, valid = dice_iou_from_counts(counts)
+        B = counts.shape[0]
+        losses = [0.0] * B
+        if "loss" in job:
+            out, *dims = job["loss"]
+            job["loss"] = (out.cpu(), *dims)         # one read serves the per-volume values and the batch's
+            losses = self.loss_fn.values_per_volume(job["loss"])
+        host = {k: v.cpu() for k, v in job["raw"].items() if torch.is_tensor(v)}
+        if "surface" in job["raw"]:
+            hd, asd = self.surface_fix(*job["raw"]["surface"], counts, job["shape"])
+            host["surface"] = torch.cat([hd.double(), asd.double()], dim=1)
+        blocks = [b for b in BLOCKS if b.name in self.layout().slices]
+        rows = []
+        for i in range(B):
+            vol = dict({k: v[i] for k, v in host.items()}, penalty=job.get("penalty"))
+            rows.append(torch.cat([torch.tensor([job["index"][i], job["domain_id"][i], losses[i]], dtype=torch.float64),
+                                   dice[i].double(), iou[i].double(), valid[i].double()] + [b.columns(vol) for b in blocks]))
+        return rows
 
     def calibration_launch(self, logits: torch.Tensor, y: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
         """Queue the reliability histogram of (logits, y) on the current stream -> device table float64 [B, Rout, 3*bins + 2]."""
@@ -955,109 +967,56 @@ class SegmentationEvaluationStrategy:
         asd[(~torch.isfinite(asd)) & valid] = diag_mm
         return hd, asd
 
-    def surface(self, y: torch.Tensor, counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-        """HD95 / ASD [B,R] (host, fp32) of the masks of the last :meth:`score` call (reference seg_eval.py:312-355)."""
-        hd, asd = self.surface_launch(self._mask, y)
-        return self.surface_fix(hd, asd, counts, y.shape[2:])
-
     @torch.no_grad()
     def evaluate_epoch(self, model: torch.nn.Module, data_loader: Iterable, device) -> Dict[str, float]:
-        """Single process: the reference's loop and aggregation (seg_eval.py:276-460).  Under an initialised
-        ``torch.distributed`` group with more than one rank ``data_loader`` is this rank's shard: every volume becomes a
-        row of the per-volume table, the tables are merged (``merge_rank_tables``) and every rank reports the metrics of
-        the WHOLE split - a rank never prints the metrics of its shard as if they were the test set."""
+        """Single process: the reference's loop and aggregation (seg_eval.py:276-460), over the per-volume table rows; the
+        reported loss is the batch's value times the batch size, as the reference forms it.  Under an initialised
+        ``torch.distributed`` group with more than one rank ``data_loader`` is this rank's shard: the tables are merged
+        (``merge_rank_tables``) and every rank reports the metrics of the WHOLE split - a rank never prints the metrics of
+        its shard as if they were the test set."""
         import torch.distributed as dist
 
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         model.eval()
         model.to(device)
-        acc = RegionAccumulator(self.region_order, self.enable_surface, self.cal_bins, self.calibration_regions,
-                                self.enable_postprocess, self.enable_lesionwise, self.enable_fill_nest,
-                                self.enable_lesionwise_hd95, self.sd_tolerances, self.ln_tolerances)
         rows: List[torch.Tensor] = []
         domain_names: List[str] = []
-        n_local = 0
+        batch_losses: List[Tuple[float, int]] = []
         for batch in data_loader:
             x, y = self.check_batch(batch, device)
-            logits = model(x)
-            counts = self.score(logits.float(), y)
-            dice, iou, valid = dice_iou_from_counts(counts)
-            hd, asd = self.surface(y, counts) if self.enable_surface else (None, None)
-            cal = self.calibration_launch(logits.float(), y).cpu() if self.enable_calibration else None
-            comp = [self.component_columns(st) for st in self._stats] if self.enable_postprocess else None
-            lw = [lesionwise_columns(st) for st in self._lw] if self.enable_lesionwise else None
-            lh = ([lesionwise_hd95_columns(st, hs, self.lesionwise_hd95_penalty_mm(y.shape[2:]))
-                   for st, hs in zip(self._lw, self._lwhd)] if self.enable_lesionwise_hd95 else None)
-            fn = [self.fill_nest_columns(st) for st in self._fill] if self.enable_fill_nest else None
-            ln = ([lesionwise_nsd_columns(st, ns) for st, ns in zip(self._lw, self._lwnsd)] if self.enable_lesionwise_nsd
-                  else None)
-            sdc = [surface_dice_columns(c) for c in self._sd] if self.enable_surface_dice else None
+            job = self.queue_passes(model(x).float(), y)
             domains = as_list_str(batch.get("domain", None), batch_size=x.size(0))
-            if world == 1:
-                for i in range(x.size(0)):
-                    acc.add_row(dice[i].tolist(), iou[i].tolist(), valid[i].tolist(), domains[i],
-                                hd[i].tolist() if hd is not None else None, asd[i].tolist() if asd is not None else None,
-                                cal[i] if cal is not None else None, comp[i] if comp is not None else None,
-                                lw[i] if lw is not None else None, fn[i] if fn is not None else None,
-                                lh[i] if lh is not None else None, sdc[i] if sdc is not None else None,
-                                ln[i] if ln is not None else None)
-                if self.report_loss:
-                    acc.add_loss(self.loss_fn(logits.float(), y), x.size(0))
-                continue
-            losses = (self.loss_fn.values_per_volume(self.loss_fn.launch(logits.float(), y)) if self.report_loss
-                      else [0.0] * x.size(0))
             idx = batch.get("index", None)
-            if idx is None:
+            if idx is None and world > 1:
                 raise KeyError("[seg_eval] a sharded evaluation needs batch['index'] (the volume's position in the whole split): "
                                "rank-local counters collide across ranks")
-            for i in range(x.size(0)):
-                if domains[i] not in domain_names:
-                    domain_names.append(domains[i])
-                parts = [torch.tensor([int(idx[i]), domain_names.index(domains[i]),
-                                       losses[i]], dtype=torch.float64),
-                         dice[i].double(), iou[i].double(), valid[i].double()]
-                if self.enable_surface:
-                    parts += [hd[i].double(), asd[i].double()]
-                if comp is not None:
-                    parts.append(comp[i])
-                if fn is not None:
-                    parts.append(fn[i])
-                if lw is not None:
-                    parts.append(lw[i])
-                if lh is not None:
-                    parts.append(lh[i])
-                if ln is not None:
-                    parts.append(ln[i])
-                if sdc is not None:
-                    parts.append(sdc[i])
-                if cal is not None:
-                    parts.append(cal[i].reshape(-1))
-                rows.append(torch.cat(parts))
-                n_local += 1
-        if world == 1:
-            if self.enable_calibration:
-                self.last_reliability = acc.reliability
-            return acc.metrics(self.report_loss)
+            domain_names += [d for d in dict.fromkeys(domains) if d not in domain_names]
+            job.update(index=[int(idx[i]) if idx is not None else len(rows) + i for i in range(x.size(0))],
+                       domain_id=[domain_names.index(d) for d in domains])
+            rows += self.table_rows(job)
+            if world == 1 and self.report_loss:
+                batch_losses.append((self.loss_fn.value(job["loss"]), x.size(0)))
         table = torch.stack(rows) if rows else torch.empty((0, self._table_width()), dtype=torch.float64)
+        if world == 1:
+            return self._metrics_of(table, domain_names, batch_losses)
         table, domain_names = merge_rank_tables(table, domain_names, device)
         self.last_table = table
         return self._metrics_of(table, domain_names)
 
     def _table_width(self) -> int:
-        return table_width(len(self.region_order), self.enable_surface, self.cal_bins, len(self.calibration_regions),
-                           components=self.enable_postprocess, lesionwise=self.enable_lesionwise,
-                           fill_nest=self.enable_fill_nest, lesionwise_hd95=self.enable_lesionwise_hd95,
-                           surface_dice=len(self.sd_tolerances), lesionwise_nsd=len(self.ln_tolerances))
+        return self.layout().width
 
-    def _metrics_of(self, table: torch.Tensor, domain_names: Sequence[str]) -> Dict[str, float]:
-        """Metrics of the whole split from its per-volume table (and ``last_reliability`` with calibration on)."""
+    def _metrics_of(self, table: torch.Tensor, domain_names: Sequence[str],
+                    batch_losses: Optional[List[Tuple[float, int]]] = None) -> Dict[str, float]:
+        """Metrics of the whole split from its per-volume table (and ``last_reliability`` with calibration on); the loss from
+        the rows, or from ``batch_losses`` = (value, batch size) per batch where given."""
+        acc = RegionAccumulator(self.region_order, **self.switches())
+        acc.add_table(table, domain_names, self.report_loss and batch_losses is None)
+        for loss, n in batch_losses or []:
+            acc.add_loss(loss, n)
         if self.enable_calibration:
-            self.last_reliability = reliability_from_table(table, self.calibration_bins, len(self.calibration_regions))
-        return metrics_from_table(table, self.region_order, domain_names, self.report_loss, self.enable_surface,
-                                  self.cal_bins, self.calibration_regions, components=self.enable_postprocess,
-                                  lesionwise=self.enable_lesionwise, fill_nest=self.enable_fill_nest,
-                                  lesionwise_hd95=self.enable_lesionwise_hd95, surface_dice=self.sd_tolerances,
-                                  lesionwise_nsd=self.ln_tolerances)
+            self.last_reliability = acc.reliability
+        return acc.metrics(self.report_loss)
 
 
 # ----------------------------------------------------------------------------- sharding
@@ -1065,19 +1024,6 @@ def shard_indices(n_items: int, rank: int, world: int) -> List[int]:
     """Round-robin, deterministic: volume i -> rank i mod W."""
     return list(range(rank, n_items, world))
 
-
-def table_width(R: int, surface: bool = False, bins: int = 0, rout: Optional[int] = None, components: bool = False,
-                lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False, surface_dice: int = 0,
-                lesionwise_nsd: int = 0) -> int:
-    """index, domain_id, loss, then dice[R], iou[R], valid[R] (, hd95[R], asd[R]) (, with ``components`` the figures of the
-    post-processing: components[R], kept[R], removed voxels[R]) (, with ``fill_nest`` the figures of the hole filling and
-    nesting: holes[R], filled holes[R], filled voxels[R], nested voxels[R]) (, with ``lesionwise`` the 7*R columns of
-    ``lesionwise_columns``) (, with ``lesionwise_hd95`` the 2*R columns of ``lesionwise_hd95_columns``) (, with ``lesionwise_nsd`` = T > 0 tolerances the T*R columns of ``lesionwise_nsd_columns``)
-    (, with ``surface_dice`` = T > 0 tolerances the T*R columns of ``surface_dice_columns``) (, with ``bins`` > 0 the volume's raw calibration table: ``rout`` rows - default R - of
-    3*bins + 2 doubles, always last)."""
-    return (3 + (5 if surface else 3) * R + (3 * R if components else 0) + (FILL_NEST_COLUMNS * R if fill_nest else 0) +
-            (LESIONWISE_COLUMNS * R if lesionwise else 0) + (LESIONWISE_HD95_COLUMNS * R if lesionwise_hd95 else 0) +
-            (int(lesionwise_nsd) + int(surface_dice)) * R + calibration_width(bins, R if rout is None else rout))
 
 
 def reliability_from_table(table: torch.Tensor, bins: int, rout: int) -> torch.Tensor:
@@ -1152,46 +1098,6 @@ def gather_masks(local: Sequence[Tuple[int, torch.Tensor]], device, group=None) 
                 out[i] = bf[k, :r, :d, :h, :w].clone()
     return out
 
-
-def metrics_from_table(table: torch.Tensor, region_order: Sequence[str], domain_names: Sequence[str],
-                       report_loss: bool, surface: bool = False, bins: int = 0,
-                       calibration_regions: Optional[Sequence[str]] = None, components: bool = False,
-                       lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False,
-                       surface_dice: Sequence[float] = (), lesionwise_nsd: Sequence[float] = ()) -> Dict[str, float]:
-    """Replay the reference aggregation over gathered rows in volume-index order: the result is
-    identical to a single-process run (float64 sums, order fixed by index).  ``bins`` > 0: the rows end in the raw
-    calibration table of their volume (``table_width``), one row of it per name in ``calibration_regions``.
-    ``components``: the 3*R component columns sit behind the surface columns (``table_width``); ``fill_nest``: the 4*R
-    columns of the hole filling and nesting sit behind those; ``lesionwise``: the 7*R lesion-wise columns sit behind those;
-    ``lesionwise_hd95``: the 2*R lesion-wise HD95 columns sit directly behind those; ``lesionwise_nsd`` and ``surface_dice``
-    (their tolerances): the T*R lesion-wise NSD columns, then the T*R region-wise NSD columns, behind those."""
-    R = len(region_order)
-    acc = RegionAccumulator(region_order, surface, bins, calibration_regions, components, lesionwise, fill_nest, lesionwise_hd95,
-                            surface_dice, lesionwise_nsd)
-    c0 = 3 + (5 if surface else 3) * R
-    f0 = c0 + (3 * R if components else 0)
-    l0 = f0 + (FILL_NEST_COLUMNS * R if fill_nest else 0)
-    h0 = l0 + (LESIONWISE_COLUMNS * R if lesionwise else 0)
-    n0 = h0 + (LESIONWISE_HD95_COLUMNS * R if lesionwise_hd95 else 0)
-    s0 = n0 + len(acc.lesionwise_nsd) * R
-    cal_w = calibration_width(bins, len(acc.cal_regions))
-    for row in table:
-        dom = domain_names[int(row[1].item())] if 0 <= int(row[1].item()) < len(domain_names) else ""
-        dice = row[3:3 + R].to(torch.float32).tolist()
-        iou = row[3 + R:3 + 2 * R].to(torch.float32).tolist()
-        valid = (row[3 + 2 * R:3 + 3 * R] > 0.5).tolist()
-        hd = row[3 + 3 * R:3 + 4 * R].to(torch.float32).tolist() if surface else None
-        asd = row[3 + 4 * R:3 + 5 * R].to(torch.float32).tolist() if surface else None
-        acc.add_row(dice, iou, valid, dom, hd, asd, row[row.numel() - cal_w:] if bins else None,
-                    row[c0:c0 + 3 * R] if components else None,
-                    row[l0:l0 + LESIONWISE_COLUMNS * R] if lesionwise else None,
-                    row[f0:f0 + FILL_NEST_COLUMNS * R] if fill_nest else None,
-                    row[h0:h0 + LESIONWISE_HD95_COLUMNS * R] if lesionwise_hd95 else None,
-                    row[s0:s0 + len(acc.surface_dice) * R] if acc.surface_dice else None,
-                    row[n0:s0] if acc.lesionwise_nsd else None)
-        if report_loss:
-            acc.add_loss(float(row[2].item()), 1)
-    return acc.metrics(report_loss)
 
 
 def merge_rank_tables(table: torch.Tensor, domain_names: List[str], device) -> Tuple[torch.Tensor, List[str]]:
@@ -1296,80 +1202,17 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
     def _submit(self, lane: int, xb: torch.Tensor, yb: torch.Tensor) -> Dict[str, Any]:
         """Queue adaptation + scoring of one volume - or of one GROUP of volumes (``method.group``, batch items that adapt
         independently) - on the lane's stream; nothing here waits for the GPU."""
-        B, R = yb.shape[0], yb.shape[1]
         res = self.plugins[lane].adapt_volume(xb)
-        counts = torch.empty((B, R, 3), dtype=torch.int64, device=yb.device)
-        need_mask = (self.enable_surface or self.gather_masks or self.enable_postprocess or self.enable_lesionwise or
-                     self.enable_surface_dice)
-        mask = torch.empty(tuple(yb.shape), dtype=torch.uint8, device=yb.device) if need_mask else None
-        ops.mask_dice_counts(res["logits_cl"], yb, self.threshold, counts, mask, logits_channels_last=True)
-        stats = None
-        if self.enable_postprocess:      # in place: the surface pass and the gathered masks below take the filtered mask
-            counts, stats = self.postprocess_launch(mask, yb)
-        fill = None
-        if self.enable_fill_nest:        # likewise in place, right behind the filter: its counts replace the filter's
-            counts, fill = self.fill_nest_launch(mask, yb)
-        job: Dict[str, Any] = {"counts": counts, "shape": tuple(yb.shape[2:]), "keep": (xb, yb, mask, res), "mask": mask}
-        if stats is not None:
-            job["components"] = stats
-        if fill is not None:
-            job["fill_nest"] = fill
-        if self.enable_lesionwise_hd95:  # right behind the counts, on the mask they describe; the HD95 pass on the same scratch
-            job["lesionwise"], job["lesionwise_hd95"] = self.lesionwise_hd95_launch(mask, yb)
-        elif self.enable_lesionwise:
-            job["lesionwise"] = self.lesionwise_launch(mask, yb)
-        if self.enable_lesionwise_nsd:   # behind the lesion-wise passes, on their scratch
-            job["lesionwise_nsd"] = self.lesionwise_nsd_launch(mask)
-        if self.enable_surface_dice:     # on the final mask, like the surface distances
-            job["surface_dice"] = self.surface_dice_launch(mask, yb)
-        if self.report_loss:
-            job["loss"] = self.loss_fn.launch(res["logits_cl"], yb, channels_last=True)
-        if self.enable_surface:
-            job["surface"] = self.surface_launch(mask, yb)
-        if self.enable_calibration:
-            job["calibration"] = self.calibration_launch(res["logits_cl"], yb, channels_last=True)
+        job = self.queue_passes(res["logits_cl"], yb, channels_last=True)
+        job["keep"] = (xb, yb, res)
         return job
 
     def _finish(self, job: Dict[str, Any]) -> List[torch.Tensor]:
         """First host read of a queued group -> the table rows of its volumes."""
-        counts = job["counts"].cpu()
-        dice, iou, valid = dice_iou_from_counts(counts)
-        B = counts.shape[0]
-        losses = self.loss_fn.values_per_volume(job["loss"]) if self.report_loss else [0.0] * B
-        if self.enable_surface:
-            hd, asd = self.surface_fix(job["surface"][0], job["surface"][1], counts, job["shape"])
-        cal = job["calibration"].cpu() if self.enable_calibration else None
-        comp = job["components"].cpu() if self.enable_postprocess else None
-        lw = job["lesionwise"].cpu() if self.enable_lesionwise else None
-        lh = job["lesionwise_hd95"].cpu() if self.enable_lesionwise_hd95 else None
-        pen = self.lesionwise_hd95_penalty_mm(job["shape"]) if self.enable_lesionwise_hd95 else 0.0
-        fn = job["fill_nest"].cpu() if self.enable_fill_nest else None
-        ln = job["lesionwise_nsd"].cpu() if self.enable_lesionwise_nsd else None
-        sdc = job["surface_dice"].cpu() if self.enable_surface_dice else None
-        rows = []
-        for b in range(B):
-            parts = [torch.tensor([job["index"][b], job["domain_id"][b], losses[b]], dtype=torch.float64),
-                     dice[b].double(), iou[b].double(), valid[b].double()]
-            if self.enable_surface:
-                parts += [hd[b].double(), asd[b].double()]
-            if comp is not None:
-                parts.append(self.component_columns(comp[b]))
-            if fn is not None:
-                parts.append(self.fill_nest_columns(fn[b]))
-            if lw is not None:
-                parts.append(lesionwise_columns(lw[b]))
-            if lh is not None:
-                parts.append(lesionwise_hd95_columns(lw[b], lh[b], pen))
-            if ln is not None:
-                parts.append(lesionwise_nsd_columns(lw[b], ln[b]))
-            if sdc is not None:
-                parts.append(surface_dice_columns(sdc[b]))
-            if cal is not None:
-                parts.append(cal[b].reshape(-1))
-            rows.append(torch.cat(parts))
+        rows = self.table_rows(job)
         if self.gather_masks:
             mk = job["mask"].cpu()
-            for b in range(B):
+            for b in range(len(rows)):
                 self.local_masks.append((int(job["index"][b]), mk[b]))
         return rows
 

@@ -192,10 +192,10 @@ def test_ops_wrapper_checks_before_the_library():
 
 # ----------------------------------------------------------------------------- sharded seg_eval with the component columns
 class _CpuFilteredEval:
-    """The strategy's host logic is the product code; the two GPU-only calls behind ``score`` (mmtta_mask_dice_counts,
+    """The strategy's host logic is the product code; the two GPU-only calls behind ``queue_passes`` (mmtta_mask_dice_counts,
     mmtta_components_filter) are replaced by a scipy restatement: 6-connected components below 3 voxels are dropped."""
 
-    def score(self, logits, y, channels_last=False):
+    def queue_passes(self, logits, y, channels_last=False):
         import numpy as np
         from scipy import ndimage
         pred = (torch.sigmoid(logits) >= self.threshold).numpy()
@@ -211,8 +211,7 @@ class _CpuFilteredEval:
                 keep = np.isin(lab, ok)
                 counts[b, r] = torch.tensor([int((keep & gt[b, r]).sum()), int(keep.sum()), int(gt[b, r].sum())])
                 stats[b, r] = torch.tensor([n, len(ok), int(pred[b, r].sum() - keep.sum())])
-        self._stats = stats
-        return counts
+        return {"counts": counts, "shape": tuple(y.shape[2:]), "raw": {"components": stats}}
 
 
 def _pp_setup():

@@ -183,18 +183,17 @@ def test_ops_wrapper_checks_before_the_library():
 
 # ----------------------------------------------------------------------------- sharded seg_eval with the new columns
 class _CpuFillEval:
-    """The strategy's host logic is the product code; the GPU calls behind ``score`` are replaced by a scipy restatement:
+    """The strategy's host logic is the product code; the GPU calls behind ``queue_passes`` are replaced by a scipy restatement:
     no component is dropped (one is counted), then holes are filled and the chain applied as configured."""
 
-    def score(self, logits, y, channels_last=False):
+    def queue_passes(self, logits, y, channels_last=False):
         import numpy as np
         from test_hip_fill_holes import oracle
         pred = (torch.sigmoid(logits) >= self.threshold).numpy().astype(np.uint8)
         final, counts, fstats = oracle(pred, y.numpy(), self.postprocess_fill_connectivity, self.postprocess_fill_holes,
                                        self.postprocess_max_hole_voxels, self.postprocess_nesting, self.postprocess_nesting_mode)
-        self._stats = torch.ones((pred.shape[0], pred.shape[1], 3), dtype=torch.int64)
-        self._fill = torch.from_numpy(fstats)
-        return torch.from_numpy(counts)
+        raw = {"components": torch.ones((pred.shape[0], pred.shape[1], 3), dtype=torch.int64), "fill_nest": torch.from_numpy(fstats)}
+        return {"counts": torch.from_numpy(counts), "shape": tuple(y.shape[2:]), "raw": raw}
 
 
 def _setup():

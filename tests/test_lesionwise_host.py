@@ -238,10 +238,10 @@ def test_ops_wrapper_checks_before_the_library():
 
 # ----------------------------------------------------------------------------- sharded seg_eval with the lesion-wise columns
 class _CpuLesionwiseEval:
-    """The strategy's host logic is the product code; the GPU-only calls behind ``score`` (mmtta_mask_dice_counts,
+    """The strategy's host logic is the product code; the GPU-only calls behind ``queue_passes`` (mmtta_mask_dice_counts,
     mmtta_lesionwise_scores) are replaced by a scipy restatement."""
 
-    def score(self, logits, y, channels_last=False):
+    def queue_passes(self, logits, y, channels_last=False):
         import numpy as np
         from scipy import ndimage
         pred = (torch.sigmoid(logits) >= self.threshold).numpy()
@@ -276,9 +276,7 @@ class _CpuLesionwiseEval:
                         den = int(Pg.sum()) + int(own.sum())
                         q += (2 * int((Pg & own).sum()) * Q1 + den // 2) // den
                 stats[b, r] = torch.tensor([ng, kept, found, npc, int(matched[1:].sum()), q, int(sizes[1:][~matched[1:]].sum())])
-        self._stats = None
-        self._lw = stats
-        return counts
+        return {"counts": counts, "shape": tuple(y.shape[2:]), "raw": {"lesionwise": stats}}
 
 
 def _lw_setup():

@@ -92,13 +92,14 @@ def test_gather_table_two_processes_gloo(tmp_path, surface):
 # ----------------------------------------------------------------------------- seg_eval / merge under a real group
 class _CpuScoredEval:
     """Mixin for the CPU tests: the strategy's host logic is the product code, only the voxel kernel behind
-    ``score`` (mmtta_mask_dice_counts, GPU-only) is replaced by the oracle's restatement of the same counts."""
+    ``queue_passes`` (mmtta_mask_dice_counts, GPU-only) is replaced by the oracle's restatement of the same counts."""
 
-    def score(self, logits, y, channels_last=False):
+    def queue_passes(self, logits, y, channels_last=False):
         import oracle
         pred, gt = oracle.masks_from_logits(logits, y, self.threshold)
         inter = (pred & gt).flatten(2).sum(-1)
-        return torch.stack([inter, pred.flatten(2).sum(-1), gt.flatten(2).sum(-1)], dim=-1).to(torch.int64)
+        counts = torch.stack([inter, pred.flatten(2).sum(-1), gt.flatten(2).sum(-1)], dim=-1).to(torch.int64)
+        return {"counts": counts, "shape": tuple(y.shape[2:]), "raw": {}}
 
 
 def _eval_volumes(n):
