@@ -870,7 +870,8 @@ int mmtta_adam_step(float* p, const float* g, float* m, float* v, int64_t n, int
  *   ADAMW  p *= 1 - lr*weight_decay (decay segment), then the Adam update without the L2 term;
  *   SGD    g += weight_decay*p (decay segment); buf = g on the first step, momentum*buf + (1-dampening)*g after;
  *          g = nesterov ? g + momentum*buf : buf (momentum 0: plain);  p -= lr*g.   `m` is the momentum buffer,
- *          `v` is unused (may be NULL).
+ *          `v` is unused (may be NULL).  With momentum 0 torch keeps no buffer: `m` is neither read nor written (it must
+ *          still be a valid, aligned pointer).
  * All buffers 16-byte aligned, n_decay a multiple of 4 (the arena guarantees both). */
 enum { MMTTA_OPTIM_ADAM = 0, MMTTA_OPTIM_ADAMW = 1, MMTTA_OPTIM_SGD = 2 };
 typedef struct mmtta_optim_desc {

@@ -77,9 +77,11 @@ __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, const
   // ragged tail (n not a multiple of 4: never the case for the arena, kept for arbitrary callers)
   const long long i = (n4 << 2) + blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (i < n) {
-    float pi = p[i], mi = first ? 0.f : m[i], vi = (KIND != 2 && !first) ? v[i] : 0.f;
+    const bool has_m = KIND != 2 || a.momentum != 0.f;      // SGD without momentum keeps no buffer: `m` is neither read nor written
+    float pi = p[i], mi = (has_m && !first) ? m[i] : 0.f, vi = (KIND != 2 && !first) ? v[i] : 0.f;
     optim_update<KIND>(pi, g[i], mi, vi, wd_on && i < n_decay, a, step_size, bc2_sqrt, first);
-    p[i] = pi; m[i] = mi;
+    p[i] = pi;
+    if (has_m) m[i] = mi;
     if (KIND != 2) v[i] = vi;
   }
 }
@@ -204,13 +206,16 @@ __global__ __launch_bounds__(256) void dice_ce_sums_kernel(TV z, TV lab, const f
 #pragma unroll
     for (int r = 0; r < DCE_MAX_R; ++r)
       if (r < R) se += expf(lg[r] - m);
+    // lse rounds at ulp(m): fine for the CE term below (an absolute error of the size of z's own rounding), not for a
+    // probability expf(z - lse), which would inherit it as a relative error (5e-4 at a saturated logit of 1e4)
     const float lse = m + logf(se);
 #pragma unroll
     for (int r = 0; r < DCE_MAX_R; ++r)
       if (r < R) {
         const float e = expf(-fabsf(lg[r]));
-        // Dice probability: sigmoid (multilabel heads) or softmax over the channels (softmax heads with more than one channel)
-        const float p = (softmax && R > 1) ? expf(lg[r] - lse) : (lg[r] >= 0.f ? 1.f / (1.f + e) : e / (1.f + e));
+        // Dice probability: sigmoid (multilabel heads) or softmax over the channels (softmax heads with more than one channel;
+        // the form of dice_ce_grad_kernel)
+        const float p = (softmax && R > 1) ? expf(lg[r] - m) / se : (lg[r] >= 0.f ? 1.f / (1.f + e) : e / (1.f + e));
         acc[r * 3 + 0] += (double)(p * yv[r]);
         acc[r * 3 + 1] += (double)(squared ? p * p : p);
         acc[r * 3 + 2] += (double)(squared ? yv[r] * yv[r] : yv[r]);
