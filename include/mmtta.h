@@ -168,6 +168,24 @@ int mmtta_abi_version(void);
 /* Measurement aid of mmtta_lame_refine: 1 (default) calls that qualify for the tiled kernel take it; 0: every call runs the
  * generic kernel (how profiles/lame_kernels.md compares the two on one input).  Equal within fp32 summation order. */
 #define MMTTA_OPT_LAME_TILED 15
+/* Raw staging of bf16-stored operands that take no transform (a bit mask; default 3; 0: every launch stages through the
+ * transform as before, in the same process).
+ *   bit 0  implicit GEMM (csrc/conv_igemm.hip: igemm_raw_kernel, igemm_reuse_raw_kernel, igemm_cls8_raw_kernel): a call
+ *          whose x is bf16-stored, in whole 8-channel chunks (x.c % 8 == 0) of 16-byte-aligned items, with no norm-on-load
+ *          or one that has neither mean nor scale and no activation, on a bf16-operand tile with y (and the fused add)
+ *          bf16-stored too, copies each 16-byte item of the input box to LDS as loaded, under its halo / channel-chunk
+ *          mask.  The transform of such an input - unpack, x * 1 + 0, max with -inf, round to bf16 - is the identity on
+ *          every finite value and on the infinities, so outputs, statistics rows and split-K sums are equal bit for bit.
+ *          mmtta_conv_stages_raw tells whether a call qualifies; mmtta_conv_route reports the same routes either way.
+ *   bit 1  the transposed-read 27-tap weight gradient of the stride-2 layers, convolutions and transposed convolutions
+ *          (csrc/conv_wgrad.hip: wgrad_tr_raw_kernel; the stride-1 forms measured slower and are not built), with x and
+ *          dy both bf16-stored: dy (dy.c % 8 == 0), which never takes a transform, and - next to a raw dy - an x under the rule
+ *          of bit 0 go to LDS as loaded, under their masks.  With a bias gradient dy is still unpacked for the fp32 sums.
+ *          Slabs, dw and db equal bit for bit; mmtta_conv_wgrad_stages_raw tells which operands qualify.
+ * Two documented differences, neither visible in a finite result: a stored -0.0 reaches the matrix cores as -0.0 (the
+ * transform made it +0.0; sums start at +0, so no output bit depends on it), and a stored NaN stays a NaN, where the
+ * transform's fmaxf(NaN, -inf) turned it into -inf.  Returns the previous value. */
+#define MMTTA_OPT_RAW_STAGING 16
 int mmtta_set_option(int key, int value);
 
 /* ------------------------------------------------------------------ layout (boundary) ---- */
@@ -269,6 +287,11 @@ int mmtta_conv_run(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmt
 int mmtta_conv_route(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                      const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
 
+/* Whether mmtta_conv_run would stage the input box of this call raw (MMTTA_OPT_RAW_STAGING bit 0): 1 / 0, or a negative
+ * mmtta error code.  Host-only, the operands of mmtta_conv_route, the predicate the launchers themselves ask. */
+int mmtta_conv_stages_raw(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                          const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
+
 /* ---- per-volume parameter sets: N volumes (or N identical sub-networks) in ONE launch, each with ITS OWN parameters.
  * Episodic adaptation has no cross-volume state: every test volume adapts its own copy of the source weights (SURVEY.md
  * Appendix C), and the M modality encoders of the deep-fusion network are M identical graphs with different weights run
@@ -316,6 +339,11 @@ int64_t mmtta_conv_wgrad_workspace_bytes(const mmtta_conv_desc* desc, const mmtt
  *   6 tiny (<= 4 channels on both sides, k3 s1: fp32 VALU)
  * or a negative mmtta error code. */
 int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_tensor* dy);
+/* Which operands of this weight gradient the transposed-read kernel would stage raw (MMTTA_OPT_RAW_STAGING bit 1): bit 0
+ * the module input x, bit 1 the gradient dy; 0 for every other kernel, or a negative mmtta error code.  Host-only, the
+ * predicate the launcher itself asks. */
+int mmtta_conv_wgrad_stages_raw(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                const mmtta_tensor* dy);
 int mmtta_conv_wgrad(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                      const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
                      int64_t workspace_bytes, void* stream);

@@ -129,12 +129,14 @@ _SIGNATURES = {
     "mmtta_conv_run_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), C.c_void_p, C.c_void_p, _P(ConvEpilogue),
                                       _P(Tensor), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
     "mmtta_conv_route": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
+    "mmtta_conv_stages_raw": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_wgrad_workspace_bytes": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor)]),
     "mmtta_conv_wgrad_workspace_bytes_sets": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor), _P(ParamSets)]),
     "mmtta_conv_wgrad_plan_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(Tensor), _P(ParamSets), _P(C.c_int32)]),
     "mmtta_conv_wgrad_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(Tensor), C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
     "mmtta_conv_wgrad_kernel": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(Tensor)]),
+    "mmtta_conv_wgrad_stages_raw": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(Tensor)]),
     "mmtta_conv_wgrad": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(Tensor), C.c_void_p, C.c_void_p,
                                    C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "mmtta_norm_stats_finalize": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
@@ -289,6 +291,8 @@ def load() -> C.CDLL:
         lib.mmtta_set_option(12, int(os.environ["MMTTA_CLSFUSE"]))
     if "MMTTA_LEAN" in os.environ:                       # A/B aid: MMTTA_OPT_IGEMM_LEAN
         lib.mmtta_set_option(10, int(os.environ["MMTTA_LEAN"]))
+    if "MMTTA_RAWSTAGE" in os.environ:                   # A/B aid: MMTTA_OPT_RAW_STAGING (same results bit for bit)
+        lib.mmtta_set_option(16, int(os.environ["MMTTA_RAWSTAGE"]))
     _lib = lib
     return lib
 

@@ -40,6 +40,7 @@ extern int g_cls_fused_min;         // api.hip: MMTTA_OPT_CLASS_FUSED_MIN_WORKGR
 extern int g_lame_tiled;            // api.hip: MMTTA_OPT_LAME_TILED
 extern int g_thin_mfma;             // api.hip: MMTTA_OPT_THIN_MFMA
 extern int g_epilogue_vec;          // api.hip: MMTTA_OPT_EPILOGUE_VEC16
+extern int g_raw_staging;           // api.hip: MMTTA_OPT_RAW_STAGING (bit 0: implicit GEMM, bit 1: transposed-read weight gradient)
 extern int g_tune[4];               // api.hip: launch-geometry knobs (MMTTA_OPT_SPLITK_BELOW ... MMTTA_OPT_WGRAD_THIN_SLABS)
 
 // ---- activation of a norm-on-load (mmtta_norm_on_load.relu: MMTTA_ACT_*).

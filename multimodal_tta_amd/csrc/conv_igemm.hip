@@ -313,7 +313,7 @@ constexpr int EPI_TILE_FLOATS = 32 * 36;     // LDS words of one wave's transpos
 // other path of the body is compiled out of it.
 template <int NB, int MB, int TZ, int TY, int TX, int KCI, bool BF, int OCC = 2, bool ABF = false>
 __global__ __launch_bounds__(256, OCC) void igemm_kernel(GArgs a) {
-  constexpr bool REUSE = false;
+  constexpr bool REUSE = false, RAW = false;
 #include "conv_igemm_body.h"
 }
 
@@ -322,7 +322,26 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(GArgs a) {
 template <bool ABF>
 __global__ __launch_bounds__(256, 3) void igemm_reuse_kernel(GArgs a) {
   constexpr int NB = 1, MB = 2, TZ = 4, TY = 8, TX = 8, KCI = 16, OCC = 3;
-  constexpr bool BF = true, REUSE = true;
+  constexpr bool BF = true, REUSE = true, RAW = false;
+#include "conv_igemm_body.h"
+}
+
+// Raw staging (MMTTA_OPT_RAW_STAGING bit 0; host: raw_staging): the bf16 tiles of igemm_kernel and igemm_reuse_kernel for a
+// bf16-stored input without norm-on-load and with whole 8-channel chunks.  For such an input the staging chain - unpack,
+// x * 1 + 0, max with -inf, round back to bf16 - returns the bits it was given (but -0.0 -> +0.0, which no sum that starts
+// at +0 can tell), and it is most of a stage's vector-ALU work (profiles/igemm64_reuse_ab.md: 177 of 207 instructions
+// of a K-loop trip).  These kernels store the loaded item under its mask.  The same body text with one more constant, so
+// the kernels above keep theirs; launched from the plain translation unit only (the form has no activation to vary).
+template <int NB, int MB, int TZ, int TY, int TX, int KCI, int OCC>
+__global__ __launch_bounds__(256, OCC) void igemm_raw_kernel(GArgs a) {
+  constexpr bool BF = true, ABF = true, REUSE = false, RAW = true;
+#include "conv_igemm_body.h"
+}
+
+template <bool ABF>      // (always true: a template, so that the body's discarded branches stay uninstantiated)
+__global__ __launch_bounds__(256, 3) void igemm_reuse_raw_kernel(GArgs a) {
+  constexpr int NB = 1, MB = 2, TZ = 4, TY = 8, TX = 8, KCI = 16, OCC = 3;
+  constexpr bool BF = true, REUSE = true, RAW = true;
 #include "conv_igemm_body.h"
 }
 
@@ -357,164 +376,26 @@ __host__ __device__ constexpr ClsTap cls_tap(int f) {        // f-th (class, tap
 
 template <int KCI, bool ABF>
 __global__ __launch_bounds__(256, 2) void igemm_cls8_kernel(GArgs a) {
-  constexpr int TZ = 4, TY = 4, TX = 8, VS = KCI + 8, LP = LDS_PITCH_BF16, KS = KCI / 16, KC8 = KCI / 8;
-  constexpr int BZ = TZ + 1, BY = TY + 1, BX = TX + 1;
-  constexpr int BOX_HW = BZ * BY * LP * VS;                 // halfwords of the box image
-  constexpr int WIMG = 27 * KC8 * 32;                       // uint4 entries of the stage's weight image
-  extern __shared__ float lds[];
-  unsigned short* lh = reinterpret_cast<unsigned short*>(lds);
-  uint4* wimg = reinterpret_cast<uint4*>(lh + (BOX_HW + 7) / 8 * 8);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, r = lane & 31;
-  int t = blockIdx.x;
-  const int tile_in_n = t % (a.tz * a.ty * a.tx);
-  const int txi = t % a.tx; t /= a.tx;
-  const int tyi = t % a.ty; t /= a.ty;
-  const int tzi = t % a.tz;
-  const int n = t / a.tz;
-  const float* biasn = pset_bias(a.ps, a.bias, n);
-  const int gz0 = tzi * TZ, gy0 = tyi * TY, gx0 = txi * TX;
-  const int colbase = blockIdx.y * 32;
-  const bool colact = colbase < a.Np;
-
-  int zl, yl, xl;
-  row_to_local<TZ, TY, TX, true>(wave * 32 + r, zl, yl, xl);
-  const unsigned short* arow = lh + ((zl * BY + yl) * LP + xl) * VS + 8 * h;
-  const uint4* brow = wimg + h * 32 + r;
-
-  f32x16 acc[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[c][i] = 0.f;
-
-  const uint4* wq = reinterpret_cast<const uint4*>(pset_packed(a.ps, a.wp, n));
-  const long long slabsz8 = (long long)(a.Kp / 8) * a.Np;
-  const unsigned isd = (unsigned)a.isd, ish = (unsigned)a.ish, isw = (unsigned)a.isw;
-  const int cmax = ABF ? ((a.Ci - 1) & ~7) : ((a.Ci - 1) & ~3);
-  constexpr int AIT = (BZ * BY * BX * KC8 + 255) / 256;      // box items per thread
-  constexpr int BIT = (WIMG + 255) / 256;                    // weight entries per thread
-  const float relu_lo = act_lo(a.tin.relu);
-
-  for (int ks = 0; ks < a.nstages; ++ks) {
-    const int c0 = ks * KCI;
-    const float* sb = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.in) + ((long long)n * a.isn + c0) * (ABF ? 2 : 4));
-    // ---- requests first: weights of the stage, norm-on-load coefficients, box items (one round trip for all of them)
-    uint4 wv[BIT];
-#pragma unroll
-    for (int j = 0; j < BIT; ++j) {
-      const int i = min(tid + 256 * j, WIMG - 1);
-      const int tap = i / (KC8 * 32), rem = i - tap * (KC8 * 32), k8l = rem >> 5, col = rem & 31;
-      wv[j] = wq[tap * slabsz8 + (long long)(c0 / 8 + k8l) * a.Np + colbase + col];
-    }
-    Oct8<ABF> av[AIT];
-    unsigned aok = 0u;
-    int alds[AIT];
-#pragma unroll
-    for (int j = 0; j < AIT; ++j) {
-      const int i = min(tid + 256 * j, BZ * BY * BX * KC8 - 1);
-      const int cv = i % KC8, bv = i / KC8;
-      const int bz = bv / (BY * BX), brem = bv - bz * (BY * BX), by = brem / BX, bx = brem - by * BX;
-      const int iz = gz0 + bz, iy = gy0 + by, ix = gx0 + bx;
-      const bool ok = iz < a.Di && iy < a.Hi && ix < a.Wi;
-      aok |= (ok ? 1u : 0u) << j;
-      const unsigned off = __umul24((unsigned)min(iz, a.Di - 1), isd) + __umul24((unsigned)min(iy, a.Hi - 1), ish) +
-                           __umul24((unsigned)min(ix, a.Wi - 1), isw) + cv * 8;
-      const int over = max(c0 + cv * 8 - cmax, 0), over_hi = max(c0 + cv * 8 + 4 - cmax, 0);
-      av[j] = oct8_ld<ABF>(sb, off - over, off + 4 - over_hi);
-      alds[j] = ((bz * BY + by) * LP + bx) * VS + cv * 8;
-    }
-    float sc[AIT][8], sh[AIT][8];
-#pragma unroll
-    for (int j = 0; j < AIT; ++j) {
-      const int i = min(tid + 256 * j, BZ * BY * BX * KC8 - 1);
-      nl_coeff_vec<8>(a.tin, n, a.Ci, c0 + (i % KC8) * 8, sc[j], sh[j]);
-    }
-    // ---- commit
-#pragma unroll
-    for (int j = 0; j < BIT; ++j)
-      if (tid + 256 * j < WIMG) wimg[tid + 256 * j] = wv[j];
-#pragma unroll
-    for (int j = 0; j < AIT; ++j) {
-      float v[8];
-      oct8_f8(av[j], v);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = act_max(fmaf(v[q], sc[j][q], sh[j][q]), relu_lo);
-      const unsigned okm = ((aok >> j) & 1u) ? 0xffffffffu : 0u;
-      uint4 pk;
-      pk.x = pack_bf16x2(v[0], v[1]) & okm; pk.y = pack_bf16x2(v[2], v[3]) & okm;
-      pk.z = pack_bf16x2(v[4], v[5]) & okm; pk.w = pack_bf16x2(v[6], v[7]) & okm;
-      if (tid + 256 * j < BZ * BY * BX * KC8) *reinterpret_cast<uint4*>(lh + alds[j]) = pk;
-    }
-    __syncthreads();
-    // ---- MFMAs: 8 activation fragments per k step (one per tap offset), then the 27 (class, tap) products; weight
-    // fragment f is read LA products ahead through a ring (a fence per MFMA keeps the reads where they are written)
-    if (colact) {
-#pragma unroll
-      for (int k16 = 0; k16 < KS; ++k16) {
-        uint4 af[8];
-#pragma unroll
-        for (int d = 0; d < 8; ++d)
-          af[d] = *reinterpret_cast<const uint4*>(arow + ((((d >> 2) & 1) * BY + ((d >> 1) & 1)) * LP + (d & 1)) * VS + k16 * 16);
-        constexpr int LA = 3;
-        uint4 bring[LA + 1];
-        static_for<0, LA>([&](auto fc) {
-          constexpr int f = decltype(fc)::value;
-          bring[f] = brow[(cls_tap(f).slab * KC8 + k16 * 2) * 32];
-        });
-        __builtin_amdgcn_sched_barrier(0);
-        static_for<0, 27>([&](auto fc) {
-          constexpr int f = decltype(fc)::value;
-          constexpr ClsTap ct = cls_tap(f);
-          if constexpr (f + LA < 27) bring[(f + LA) % (LA + 1)] = brow[(cls_tap(f + LA).slab * KC8 + k16 * 2) * 32];
-          acc[ct.cls] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[ct.d]),
-                                                                __builtin_bit_cast(bf16x8, bring[f % (LA + 1)]), acc[ct.cls], 0, 0, 0);
-          __builtin_amdgcn_sched_barrier(0);
-        });
-      }
-    }
-    __syncthreads();
-  }
-  // ---- epilogue: every class's 32 x 32 block through this wave's LDS transposition tile (the box image is dead)
-  float tsum[4] = {0.f, 0.f, 0.f, 0.f}, tsq[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    float v_sum[4], v_sq[4];
-    epilogue_vec16<TZ, TY, TX, 1, true, ABF>(a, biasn, a.cls[c], *reinterpret_cast<f32x16(*)[1]>(&acc[c]), lds + wave * EPI_TILE_FLOATS,
-                                             lane, wave, colbase, colact, n, gz0, gy0, gx0, v_sum, v_sq);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { tsum[j] += v_sum[j]; tsq[j] += v_sq[j]; }
-  }
-  if (a.stats != nullptr) {
-    float* red = lds + 4 * EPI_TILE_FLOATS;      // [4 waves][2][32], behind the four tiles
-    if (lane < 8) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        red[(wave * 2 + 0) * 32 + lane * 4 + j] = tsum[j];
-        red[(wave * 2 + 1) * 32 + lane * 4 + j] = tsq[j];
-      }
-    }
-    __syncthreads();
-    const int col = colbase + tid;
-    if (tid < 32 && col < a.Co) {
-      float ts = 0.f, tq = 0.f;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) { ts += red[(g * 2 + 0) * 32 + tid]; tq += red[(g * 2 + 1) * 32 + tid]; }
-      const long long row = (long long)n * a.stats_rows_per_n + tile_in_n;
-      a.stats[(row * 2 + 0) * a.Co + col] = ts;
-      a.stats[(row * 2 + 1) * a.Co + col] = tq;
-    }
-  }
+  constexpr bool RAW = false;
+#include "conv_igemm_cls8_body.h"
 }
 
-template <int KCI, bool ABF>
+// ... for a bf16-stored input that takes no norm-on-load (raw staging, igemm_raw_kernel above): no sc / sh[AIT][8] live
+// across the requests of a stage
+template <int KCI, bool ABF>      // (ABF always true: see igemm_reuse_raw_kernel)
+__global__ __launch_bounds__(256, 2) void igemm_cls8_raw_kernel(GArgs a) {
+  constexpr bool RAW = true;
+#include "conv_igemm_cls8_body.h"
+}
+
+template <int KCI, bool ABF, bool RAW = false>
 static int launch_cls8_t(const GArgs& a, int tiles, hipStream_t s) {
   constexpr int VS = KCI + 8;
   size_t lds = ((size_t)(5 * 5 * LDS_PITCH_BF16 * VS + 7) / 8 * 8) * 2 + (size_t)27 * (KCI / 8) * 32 * 16;
   const size_t epi = (4 * EPI_TILE_FLOATS + 4 * 2 * 32) * sizeof(float);
   if (lds < epi) lds = epi;
-  auto kern = igemm_cls8_kernel<KCI, ABF>;
+  void (*kern)(GArgs) = igemm_cls8_kernel<KCI, ABF>;
+  if constexpr (RAW) kern = igemm_cls8_raw_kernel<KCI, ABF>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1099,6 +980,27 @@ struct RunFacts {
   const float* bias;                   // the run's bias (mmtta_conv_route has none to show: null)
 };
 
+// Raw staging of the implicit-GEMM family (MMTTA_OPT_RAW_STAGING bit 0; igemm_raw_kernel, igemm_reuse_raw_kernel,
+// igemm_cls8_raw_kernel): a bf16-stored x whose norm-on-load is the identity - none, or neither mean nor scale and no
+// activation - in whole 8-channel chunks (no lane of a 16-byte item holds row padding or a neighbour's channel) that the
+// kernels can read 16 bytes at a time, on a bf16-operand tile with y and the fused add bf16-stored like x.  The raw kernels
+// are instantiated in the plain translation unit only: a call the LeakyReLU one runs (a LeakyReLU on the fused add) keeps
+// the transform.  The one function behind mmtta_conv_stages_raw and the launchers.
+#ifdef MMTTA_ACT_LEAKY_TU
+constexpr bool RAW_KERNELS = false;
+#else
+constexpr bool RAW_KERNELS = true;
+#endif
+static bool raw_operand(const mmtta_tensor* x, const mmtta_norm_on_load* x_norm) {
+  return is_bf16(x) && x->c % 8 == 0 && quad_aligned(x, 16, 8) &&
+         (x_norm == nullptr || (x_norm->mean == nullptr && x_norm->scale == nullptr && x_norm->relu == MMTTA_ACT_NONE));
+}
+static bool raw_staging(int route, bool bf_tile, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* y,
+                        const mmtta_tensor* add) {
+  const bool igemm = route != 6 && route != 13 && route != 16 && route != 17;      // (C_DIRECT, C_THIN, C_PW_SMALL, C_PW_MFMA)
+  return RAW_KERNELS && (g_raw_staging & 1) && igemm && bf_tile && raw_operand(x, x_norm) && is_bf16(y) && (add == nullptr || is_bf16(add));
+}
+
 struct Geometry {
   int route;      // CRoute
   int K, N, Kp, Np, si;
@@ -1289,7 +1191,7 @@ static void build_taps(const mmtta_conv_desc* d, int pz, int py, int px, Taps& t
   t.zext = zmx - zmn; t.yext = ymx - ymn; t.xext = xmx - xmn;
 }
 
-template <int NB, int MB, int TZ, int TY, int TX, int KCI, bool BF, int OCC, bool ABF, bool REUSE = false>
+template <int NB, int MB, int TZ, int TY, int TX, int KCI, bool BF, int OCC, bool ABF, bool REUSE = false, bool RAW = false>
 static int launch_cfg_t(const GArgs& a_in, const Taps* ht, int tiles, hipStream_t s) {
   GArgs a = a_in;
   size_t lds = 0;
@@ -1319,15 +1221,23 @@ static int launch_cfg_t(const GArgs& a_in, const Taps* ht, int tiles, hipStream_
     // the planner asked for everything the kernel needs but the tap tables, which exist only here: should they ever not be
     // the canonical ones, the plain kernel of the tile computes the same values
     if (!(a.rowload && a.ovec && a.ksplit == 1 && a.Ci == KCI * a.nstages))
-      return launch_cfg_t<NB, MB, TZ, TY, TX, KCI, BF, OCC, ABF, false>(a_in, ht, tiles, s);
+      return launch_cfg_t<NB, MB, TZ, TY, TX, KCI, BF, OCC, ABF, false, RAW>(a_in, ht, tiles, s);
   }
   lds = (lds + 15) / 16 * 16;
   a.coef_off = (int)(lds / sizeof(float));
-  if (BF) lds += (size_t)2 * a.stages_per_split * KCI * sizeof(float);     // scale | shift of the staged channels
+  if (BF && !RAW) lds += (size_t)2 * a.stages_per_split * KCI * sizeof(float);     // scale | shift of the staged channels
   MMTTA_CHECK(lds <= 160 * 1024, MMTTA_ERR_UNSUPPORTED, "conv: LDS box of %zu bytes exceeds 160 KiB", lds);
   int st;
-  void (*kern)(GArgs) = igemm_kernel<NB, MB, TZ, TY, TX, KCI, BF, OCC, ABF>;
-  if constexpr (REUSE) kern = igemm_reuse_kernel<ABF>;
+  void (*kern)(GArgs);
+  if constexpr (RAW) {
+    static_assert(BF && ABF, "raw staging copies bf16-stored items");
+    if constexpr (REUSE) kern = igemm_reuse_raw_kernel<ABF>;
+    else kern = igemm_raw_kernel<NB, MB, TZ, TY, TX, KCI, OCC>;
+  } else if constexpr (REUSE) {
+    kern = igemm_reuse_kernel<ABF>;
+  } else {
+    kern = igemm_kernel<NB, MB, TZ, TY, TX, KCI, BF, OCC, ABF>;
+  }
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1348,34 +1258,37 @@ static int launch_cfg_t(const GArgs& a_in, const Taps* ht, int tiles, hipStream_
 // storage dispatch: bf16-stored activations exist for bf16-operand layers only (forward: input, output and fused add all
 // bf16; everything else all fp32)
 template <int NB, int MB, int TZ, int TY, int TX, int KCI, bool BF, int OCC = 2, bool REUSE = false>
-static int launch_cfg(const GArgs& a, const Taps* ht, int tiles, hipStream_t s) {
+static int launch_cfg(const GArgs& a, const Taps* ht, int tiles, bool raw, hipStream_t s) {
   if constexpr (BF) {
     if (a.in_bf || a.out_bf || a.add_bf) {
       MMTTA_CHECK(a.in_bf && a.out_bf && (a.add == nullptr || a.add_bf), MMTTA_ERR_UNSUPPORTED,
                   "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf,
                   a.add_bf);
+      if constexpr (RAW_KERNELS) {
+        if (raw) return launch_cfg_t<NB, MB, TZ, TY, TX, KCI, BF, OCC, true, REUSE, true>(a, ht, tiles, s);
+      }
       return launch_cfg_t<NB, MB, TZ, TY, TX, KCI, BF, OCC, true, REUSE>(a, ht, tiles, s);
     }
   }
   return launch_cfg_t<NB, MB, TZ, TY, TX, KCI, BF, OCC, false, REUSE>(a, ht, tiles, s);
 }
 
-static int launch_any(int route, const GArgs& a, const Taps* ht, int tiles, hipStream_t s) {
+static int launch_any(int route, const GArgs& a, const Taps* ht, int tiles, bool raw, hipStream_t s) {
   switch (route) {
-    case 0: return launch_cfg<1, 4, 8, 8, 8, 8, false>(a, ht, tiles, s);
-    case 1: return launch_cfg<2, 4, 4, 8, 8, 16, false>(a, ht, tiles, s);
-    case 2: return launch_cfg<4, 4, 4, 4, 8, 32, false>(a, ht, tiles, s);
-    case 3: return launch_cfg<1, 1, 4, 4, 8, 8, false>(a, ht, tiles, s);
-    case 4: return launch_cfg<2, 2, 4, 4, 8, 8, false>(a, ht, tiles, s);
-    case 5: return launch_cfg<4, 4, 4, 4, 8, 8, false>(a, ht, tiles, s);
-    case 14: return launch_cfg<1, 2, 4, 8, 8, 16, true, 3>(a, ht, tiles, s);
-    case C_IGEMM_REUSE: return launch_cfg<1, 2, 4, 8, 8, 16, true, 3, true>(a, ht, tiles, s);
-    case 7: return launch_cfg<1, 4, 8, 8, 8, 16, true>(a, ht, tiles, s);
-    case 8: return launch_cfg<2, 4, 4, 8, 8, 32, true>(a, ht, tiles, s);
-    case 9: return launch_cfg<4, 4, 4, 4, 8, 32, true>(a, ht, tiles, s);
-    case 10: return launch_cfg<1, 1, 4, 4, 8, 16, true>(a, ht, tiles, s);
-    case 11: return launch_cfg<2, 2, 4, 4, 8, 16, true>(a, ht, tiles, s);
-    default: return launch_cfg<4, 4, 4, 4, 8, 16, true>(a, ht, tiles, s);
+    case 0: return launch_cfg<1, 4, 8, 8, 8, 8, false>(a, ht, tiles, raw, s);
+    case 1: return launch_cfg<2, 4, 4, 8, 8, 16, false>(a, ht, tiles, raw, s);
+    case 2: return launch_cfg<4, 4, 4, 4, 8, 32, false>(a, ht, tiles, raw, s);
+    case 3: return launch_cfg<1, 1, 4, 4, 8, 8, false>(a, ht, tiles, raw, s);
+    case 4: return launch_cfg<2, 2, 4, 4, 8, 8, false>(a, ht, tiles, raw, s);
+    case 5: return launch_cfg<4, 4, 4, 4, 8, 8, false>(a, ht, tiles, raw, s);
+    case 14: return launch_cfg<1, 2, 4, 8, 8, 16, true, 3>(a, ht, tiles, raw, s);
+    case C_IGEMM_REUSE: return launch_cfg<1, 2, 4, 8, 8, 16, true, 3, true>(a, ht, tiles, raw, s);
+    case 7: return launch_cfg<1, 4, 8, 8, 8, 16, true>(a, ht, tiles, raw, s);
+    case 8: return launch_cfg<2, 4, 4, 8, 8, 32, true>(a, ht, tiles, raw, s);
+    case 9: return launch_cfg<4, 4, 4, 4, 8, 32, true>(a, ht, tiles, raw, s);
+    case 10: return launch_cfg<1, 1, 4, 4, 8, 16, true>(a, ht, tiles, raw, s);
+    case 11: return launch_cfg<2, 2, 4, 4, 8, 16, true>(a, ht, tiles, raw, s);
+    default: return launch_cfg<4, 4, 4, 4, 8, 16, true>(a, ht, tiles, raw, s);
   }
 }
 
@@ -1437,7 +1350,8 @@ static int igemm_run(const ConvCall& c, const Geometry& g) {
   GArgs a; Taps ht[8];
   const int st = fill_gargs(c, g, a, ht);
   if (st) return st;
-  return launch_any(g.route, a, ht, g.tiles, c.stream);
+  const bool raw = raw_staging(g.route, g.cfg.bf, c.x, c.x_norm, c.y, (c.epi && c.epi->add) ? c.epi->add : nullptr);
+  return launch_any(g.route, a, ht, g.tiles, raw, c.stream);
 }
 
 static int cls_fused_run(const ConvCall& c, const Geometry& g) {
@@ -1448,6 +1362,10 @@ static int cls_fused_run(const ConvCall& c, const Geometry& g) {
               "conv (class-fused stride-2 form): the epilogue operands must admit 16-byte accesses");
   MMTTA_CHECK(a.in_bf == a.out_bf && (a.add == nullptr || a.add_bf == a.out_bf), MMTTA_ERR_UNSUPPORTED,
               "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf, a.add_bf);
+  if constexpr (RAW_KERNELS) {
+    if (raw_staging(g.route, g.cfg.bf, c.x, c.x_norm, c.y, (c.epi && c.epi->add) ? c.epi->add : nullptr))
+      return launch_cls8_t<16, true, true>(a, g.tiles, c.stream);
+  }
   return a.in_bf ? launch_cls8_t<16, true>(a, g.tiles, c.stream) : launch_cls8_t<16, false>(a, g.tiles, c.stream);
 }
 
@@ -1621,6 +1539,16 @@ extern "C" int mmtta_conv_route(const mmtta_conv_desc* d, const mmtta_tensor* x,
   const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
   if (st) return st < 0 ? st : -st;
   return g.route;
+}
+
+extern "C" int mmtta_conv_stages_raw(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                     const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
+  Geometry g;
+  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
+  if (st) return st < 0 ? st : -st;
+  const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
+  // (a LeakyReLU on the fused add sends the run to the LeakyReLU instantiation, which has no raw kernels)
+  return (raw_staging(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
 }
 
 extern "C" int mmtta_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,

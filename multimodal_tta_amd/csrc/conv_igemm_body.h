@@ -1,11 +1,15 @@
 // The body of igemm_kernel and igemm_reuse_kernel (conv_igemm.hip): included inside each kernel, which names the tile
 // (NB, MB, TZ, TY, TX, KCI, BF, OCC, ABF) and REUSE as constants.  One text, so that the two cannot drift apart, and no
 // function in between, so that igemm_kernel compiles to exactly what it was before the second kernel existed.
-// Expects in scope, as compile-time constants: int NB, MB, TZ, TY, TX, KCI, OCC; bool BF, ABF, REUSE; and the kernel
+// Expects in scope, as compile-time constants: int NB, MB, TZ, TY, TX, KCI, OCC; bool BF, ABF, REUSE, RAW; and the kernel
 // argument `GArgs a`.  No include guard on purpose: it is included once per kernel.
+// RAW (igemm_raw_kernel, igemm_reuse_raw_kernel): the input is bf16-stored, takes no norm-on-load and has whole 8-channel
+// chunks only (the host asks: raw_staging), so a 16-byte item goes to LDS as it was loaded, under its halo / chunk mask -
+// no unpack, no coefficients, no fma / max / repack.  Every RAW site is an `if constexpr`: the other kernels keep their text.
   extern __shared__ float lds[];
   static_assert(!REUSE || (NB == 1 && MB == 2 && TZ == 4 && TY == 8 && TX == 8 && KCI == 16 && BF && OCC > 2),
                 "fragment reuse is built for the lean tile");
+  static_assert(!RAW || (BF && ABF), "raw staging copies bf16-stored items");
   // LDS voxel stride: fp32: KCI+1 words (odd: the 32 rows of a fragment hit distinct banks);
   // bf16: KCI+8 halfwords (16-byte slots stay aligned for ds_read_b128)
   constexpr int VS = BF ? (KCI + 8) : (KCI + 1);
@@ -120,11 +124,13 @@
   float* coef = lds + a.coef_off;
   const int cbase = ks0 * KCI, nch = (ks1 - ks0) * KCI;
   if (fast) {
-    for (int cch = tid; cch < nch; cch += 256) {
-      float sc1 = 0.f, sh1 = 0.f;
-      if (cbase + cch < a.Ci) nl_coeff(a.tin, n, a.Ci, cbase + cch, sc1, sh1);     // channels past the last one stage as zeros
-      coef[cch] = sc1;
-      coef[nch + cch] = sh1;
+    if constexpr (!RAW) {
+      for (int cch = tid; cch < nch; cch += 256) {
+        float sc1 = 0.f, sh1 = 0.f;
+        if (cbase + cch < a.Ci) nl_coeff(a.tin, n, a.Ci, cbase + cch, sc1, sh1);     // channels past the last one stage as zeros
+        coef[cch] = sc1;
+        coef[nch + cch] = sh1;
+      }
     }
     if constexpr (RHOIST) geometry();
   }
@@ -146,7 +152,7 @@
   };
   if (fast && ks0 < ks1) {
     if (pipe) issue(ks0);
-    __syncthreads();      // coefficients visible
+    if constexpr (!RAW) __syncthreads();      // coefficients visible
   }
 
   // Weight fragment of (tap t, 16-channel step k2) of the canonical stage: a wave-uniform 64-bit base (scalar registers:
@@ -204,7 +210,7 @@
         if constexpr (!RHOIST) geometry();
         static_for<RPG, R1>([&](auto pc) { load_item(pc, sb, c0); });
         float sc[8], sh[8];
-        {
+        if constexpr (!RAW) {
           const float4* cq = reinterpret_cast<const float4*>(coef + (c0 - cbase) + rcv * 8);
           const float4* hq = reinterpret_cast<const float4*>(coef + nch + (c0 - cbase) + rcv * 8);
           const float4 s0 = cq[0], s1 = cq[1], h0 = hq[0], h1 = hq[1];
@@ -214,14 +220,22 @@
         const float relu_lo = act_lo(a.tin.relu);
         auto commit_item = [&](auto pc) {
           constexpr int P = decltype(pc)::value;
+          uint4 pk;
+          if constexpr (RAW) {
+            // the item as loaded, under the halo bit and - in a partial last stage, where the loader re-read the last valid
+            // chunk - the chunk test, folded into one mask
+            const unsigned okm = (((pok >> P) & 1u) && (REUSE || c0 + rcv * 8 < a.Ci)) ? 0xffffffffu : 0u;
+            pk = gv[P].q;
+            pk.x &= okm; pk.y &= okm; pk.z &= okm; pk.w &= okm;
+          } else {
           float v[8];
           oct8_f8(gv[P], v);
 #pragma unroll
           for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
           const unsigned okm = ((pok >> P) & 1u) ? 0xffffffffu : 0u;
-          uint4 pk;
           pk.x = pack_bf16x2(v[0], v[1]) & okm; pk.y = pack_bf16x2(v[2], v[3]) & okm;
           pk.z = pack_bf16x2(v[4], v[5]) & okm; pk.w = pack_bf16x2(v[6], v[7]) & okm;
+          }
           if (RNROW % RRPP == 0 || P + 1 < RGP || RRPP * P + rrsub < RNROW)       // the last pass may be partial
             *reinterpret_cast<uint4*>(rst + P * (RRPP * LDS_PITCH_BF16 * VS)) = pk;
         };
@@ -231,14 +245,14 @@
           static_for<A, B>([&](auto pc) { load_item(pc, sb, c0); });
           static_for<A, B>(commit_item);
         });
-      } else if (a.vec4) {
+      } else if (RAW || a.vec4) {          // (a raw launch has 16-byte items: the host asked)
         constexpr int CV8 = KCI / 8;
         const int cv = tid % CV8;          // 256 % CV8 == 0
         const int c = c0 + cv * 8;
         float sc[8], sh[8];
         constexpr int STEP = 256 / CV8;
         const int first_item = 0;
-        nl_coeff_vec<8>(a.tin, n, a.Ci, c, sc, sh);
+        if constexpr (!RAW) nl_coeff_vec<8>(a.tin, n, a.Ci, c, sc, sh);
         // U items per trip: all their global loads are issued before the first use (one exposed latency per
         // trip instead of one per item)
         // all of a thread's items in as few trips as the register budget allows: one exposed memory latency per trip
@@ -246,6 +260,7 @@
         const bool tail = (a.Ci & 7) != 0;       // only then can lanes beyond Ci hold uninitialised padding
         for (int bv0 = tid / CV8 + first_item * STEP; bv0 < boxvox; bv0 += U * STEP) {
           float4 x0[U], x1[U];
+          uint4 xq[U];                       // RAW: the item as loaded, zeros outside the tensor and past its last chunk
           bool ok[U];
 #pragma unroll
           for (int u = 0; u < U; ++u) {
@@ -257,9 +272,11 @@
                     (unsigned)ix < (unsigned)a.Wi && c < a.Ci;
             x0[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             x1[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (RAW) xq[u] = make_uint4(0u, 0u, 0u, 0u);
             if (ok[u]) {
               const long long so = inoff + (long long)iz * a.isd + (long long)iy * a.ish + (long long)ix * a.isw + c;
-              if constexpr (ABF) ld8_t<true>(inb, so, x0[u], x1[u]);      // rows of bf16 tensors are padded to 8 channels
+              if constexpr (RAW) xq[u] = *reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(inb) + so);
+              else if constexpr (ABF) ld8_t<true>(inb, so, x0[u], x1[u]);      // rows of bf16 tensors are padded to 8 channels
               else {
                 x0[u] = *reinterpret_cast<const float4*>(inb + so);
                 if (c + 4 < a.Ci) x1[u] = *reinterpret_cast<const float4*>(inb + so + 4);
@@ -271,7 +288,8 @@
             const int bv = bv0 + u * STEP;
             if (bv < boxvox) {
               uint4 pk = make_uint4(0u, 0u, 0u, 0u);
-              if (ok[u]) {
+              if constexpr (RAW) pk = xq[u];
+              else if (ok[u]) {
                 const float xs[8] = {x0[u].x, x0[u].y, x0[u].z, x0[u].w, x1[u].x, x1[u].y, x1[u].z, x1[u].w};
                 float v[8];
 #pragma unroll

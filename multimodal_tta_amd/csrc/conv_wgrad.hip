@@ -724,328 +724,26 @@ typedef __attribute__((address_space(3))) wshort4* wlds4_t;
 // ALU, L2) is their cost, and every dense column block used to repeat it (conv 32->64 at 64^3: 2x, convT 128->32: 4x).
 template <int TZ, int TY, int SI, bool GBF, bool DBF, bool TD, int NB = 1>
 __global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_kernel(WArgs a) {
-  using G = WTGeo<TZ, TY, SI>;
-  static_assert(TY % 2 == 0, "a k step is two rows of one z slice");
-  extern __shared__ float lds[];
-  unsigned char* gl = reinterpret_cast<unsigned char*>(lds);
-  unsigned char* dl = gl + G::G_BYTES;                  // NB dense images back to back
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, r = lane & 31;
-  const int cg0 = blockIdx.y * 32, cd0 = blockIdx.z * 32 * NB;
-
-  // operand addresses: lane part (group row q, 8-byte column chunk, row half) + tap (A only)
-  const int lq = (lane & 15) >> 2, lp = lane & 3, lc = (lane >> 4) & 1;
-  const unsigned char* dread = dl + (h * 8 + lq) * 64 + lc * 32 + lp * 8;
-  const unsigned char* gread[7];
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    const int tap = min(wave + 4 * j, 26);
-    gread[j] = gl + (h * SI * G::BX + lq) * 64 + lc * 32 + lp * 8 + G::tap_off(tap);
-  }
-  f32x16 acc[NB][7];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int j = 0; j < 7; ++j)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[nb][j][i] = 0.f;
-  float dbs[NB][8];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int c = 0; c < 8; ++c) dbs[nb][c] = 0.f;
-  const bool want_db = a.dbpart != nullptr && blockIdx.y == 0;
-
-  // ---- staging roles (per-thread constants)
-  const int rsub = min(tid / G::IPR, G::RPP - 1);                // box row inside a pass
-  const int rem = tid % G::IPR, bx = rem >> 2, c8 = rem & 3;     // box x, 8-channel chunk
-  const int bxm = SI == 1 ? bx : (bx & 1) * G::XH + (bx >> 1);
-  unsigned char* gst = gl + (rsub * G::BX + bxm) * 64 + c8 * 16;  // + pass * RPP * BX * 64
-  const int dvox0 = tid >> 2, d8 = tid & 3;                      // dense item p: voxel dvox0 + 64 p, chunk d8
-  unsigned char* dst = dl + dvox0 * 64 + d8 * 16;                // + p * 4096
-  const int dzl = dvox0 / (TY * 8), dyl = (dvox0 >> 3) % TY, dxl = dvox0 & 7;     // (pass p adds 64 / (TY * 8) to z)
-  const int gcb = cg0 + 8 * c8, dcb = cd0 + 8 * d8;               // (dense column block nb: + 32 nb)
-  // clamped (always valid) load channels; rows of bf16 tensors are padded to 8 channels, of fp32 tensors to 4
-  const unsigned gc_lo = GBF ? min(gcb, (a.Cg - 1) & ~7) : min(gcb, (a.Cg - 1) & ~3), gc_hi = min(gcb + 4, (a.Cg - 1) & ~3);
-  const unsigned dc_lo = DBF ? min(dcb, (a.Cd - 1) & ~7) : min(dcb, (a.Cd - 1) & ~3), dc_hi = min(dcb + 4, (a.Cd - 1) & ~3);
-  // (column block 1 of a pair is whole: the host pairs blocks only when CDp / 32 is even and rows are padded to 8 channels)
-  const unsigned dc_lo1 = DBF ? min(dcb + 32, (a.Cd - 1) & ~7) : min(dcb + 32, (a.Cd - 1) & ~3), dc_hi1 = min(dcb + 36, (a.Cd - 1) & ~3);
-  const bool gtail = (a.Cg & 7) != 0, dtail = (a.Cd & 7) != 0;  // only then can a chunk hold channels past the last one
-  auto pair_mask = [](int c, int C) { return (c < C ? 0xffffu : 0u) | (c + 1 < C ? 0xffff0000u : 0u); };
-  const unsigned gsd = (unsigned)a.gsd, gsh = (unsigned)a.gsh, gsw = (unsigned)a.gsw;
-  const unsigned dsd = (unsigned)a.dsd, dsh = (unsigned)a.dsh, dsw = (unsigned)a.dsw;
-
-  // slab sx = slab (sx % S) of parameter set (sx / S): a set's slabs cover ITS batch items only, in the order a launch of
-  // those items alone would use (the reduce kernels then sum a set's rows in that same order)
-  const int sx = (int)xcd_contiguous_id(blockIdx.x, gridDim.x);
-  const int qset = sx / a.S, sls = sx - qset * a.S;
-  const int t0 = qset * a.tiles_set + sls * a.tiles_per_split;
-  const int t1 = min((qset + 1) * a.tiles_set, t0 + a.tiles_per_split);
-  const int tpn = a.tz * a.ty * a.tx;
-  constexpr int GP = G::GP, DP = G::DP;
-  constexpr int PREF = (GBF || DBF) ? 40 : 32;                         // registers the cross-loop prefetch may hold
-  constexpr int PGmax = (PREF - NB * DP * (DBF ? 4 : 8)) / (GBF ? 4 : 8);
-  constexpr int PG = PGmax < 0 ? 0 : (PGmax < GP ? PGmax : GP);        // box passes prefetched across the MFMA loop
-  Oct8<GBF> gv[GP];
-  Oct8<DBF> dq[NB * DP];
-  unsigned pok = 0u;                             // bit p: box item of pass p lies inside the tensor
-  unsigned dok = 0u;                             // bit p: dense item p lies inside the tensor
-  int pn = -1, poz0 = 0, poy0 = 0, pox0 = 0;     // tile whose loads are in gv[0..PG) / dq
-  int cn = -1;                                   // batch item the transform coefficients belong to
-  float* coefl = reinterpret_cast<float*>(dl + NB * G::D_BYTES);     // [NB][2][32]: scale, shift of the module-input channels
-  const float relu_lo = act_lo(TD ? a.td.relu : a.tg.relu);
-  unsigned gxoff = 0u;                           // per tile: x / channel part of the box offsets, x in bounds
-  bool gxok = false;
-
-  auto tile_x = [&](int ix0) {
-    const int ix = ix0 + bx;
-    gxok = (unsigned)ix < (unsigned)a.Wgg;
-    gxoff = __umul24((unsigned)min(max(ix, 0), a.Wgg - 1), gsw);
-  };
-  auto load_g = [&](auto pc, const float* gbase, int iz0, int iy0) {
-    constexpr int P = decltype(pc)::value;
-    constexpr int row0 = G::RPP * P, bz0 = row0 / G::BY, by0 = row0 % G::BY;
-    constexpr bool can_wrap = by0 + G::RPP > G::BY;
-    int by = by0 + rsub;
-    bool wrap = false;
-    if constexpr (can_wrap) {
-      wrap = by >= G::BY;
-      by = wrap ? by - G::BY : by;
-    }
-    const int izA = iz0 + bz0, izB = izA + 1;                    // wave-uniform candidates
-    const unsigned zoA = __umul24((unsigned)min(max(izA, 0), a.Dgg - 1), gsd), zoB = __umul24((unsigned)min(max(izB, 0), a.Dgg - 1), gsd);
-    const bool zkA = (unsigned)izA < (unsigned)a.Dgg, zkB = (unsigned)izB < (unsigned)a.Dgg;
-    const unsigned zo = (can_wrap && wrap) ? zoB : zoA;
-    const bool zk = (can_wrap && wrap) ? zkB : zkA;
-    const int iy = iy0 + by;
-    const bool ok = zk && gxok && (unsigned)iy < (unsigned)a.Hgg;
-    pok |= (ok ? 1u : 0u) << P;
-    const unsigned off = zo + __umul24((unsigned)min(max(iy, 0), a.Hgg - 1), gsh) + gxoff;
-    gv[P] = oct8_ld<GBF>(gbase, off + gc_lo, off + gc_hi);
-  };
-  auto commit_g = [&](auto pc, const float (&sc)[8], const float (&sh)[8]) {
-    constexpr int P = decltype(pc)::value;
-    float v[8];
-    oct8_f8(gv[P], v);
-    if constexpr (!TD) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
-    }
-    const unsigned okm = ((pok >> P) & 1u) ? 0xffffffffu : 0u;
-    uint4 pk;
-    pk.x = wpack2(v[0], v[1]) & okm; pk.y = wpack2(v[2], v[3]) & okm;
-    pk.z = wpack2(v[4], v[5]) & okm; pk.w = wpack2(v[6], v[7]) & okm;
-    if (gtail) {
-      pk.x &= pair_mask(gcb, a.Cg); pk.y &= pair_mask(gcb + 2, a.Cg); pk.z &= pair_mask(gcb + 4, a.Cg); pk.w &= pair_mask(gcb + 6, a.Cg);
-    }
-    *reinterpret_cast<uint4*>(gst + P * (G::RPP * G::BX * 64)) = pk;
-  };
-  auto issue = [&](int tile) {
-    pn = tile / tpn;
-    int t = tile % tpn;
-    const int txi = t % a.tx; t /= a.tx;
-    const int tyi = t % a.ty;
-    const int tzi = t / a.ty;
-    poz0 = tzi * TZ; poy0 = tyi * TY; pox0 = txi * 8;
-    const float* dbase = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.dn) + (long long)pn * a.dsn * (DBF ? 2 : 4));
-    const int oy = poy0 + dyl, ox = pox0 + dxl;
-    const bool yxok = oy < a.Hd && ox < a.Wd;
-    const unsigned yxoff = __umul24((unsigned)min(oy, a.Hd - 1), dsh) + __umul24((unsigned)min(ox, a.Wd - 1), dsw);
-    dok = 0u;
-#pragma unroll
-    for (int p = 0; p < DP; ++p) {
-      const int oz = poz0 + dzl + p * (64 / (TY * 8));
-      dok |= ((yxok && oz < a.Dd) ? 1u : 0u) << p;
-      const unsigned off = __umul24((unsigned)min(oz, a.Dd - 1), dsd) + yxoff;
-      dq[p] = oct8_ld<DBF>(dbase, off + dc_lo, off + dc_hi);
-      if constexpr (NB == 2) dq[DP + p] = oct8_ld<DBF>(dbase, off + dc_lo1, off + dc_hi1);
-    }
-    pok = 0u;
-    tile_x(pox0 * SI - 1);
-    const float* gbase = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.g) + (long long)pn * a.gsn * (GBF ? 2 : 4));
-    static_for<0, PG>([&](auto pc) { load_g(pc, gbase, poz0 * SI - 1, poy0 * SI - 1); });
-  };
-
-  if (t0 < t1) issue(t0);
-  for (int tile = t0; tile < t1; ++tile) {
-    const int n = pn;
-    // what the prefetch had no registers for comes in rounds of RB passes (all loads of a round in flight together);
-    // the first round is requested before the prefetched part is committed
-    constexpr int RB = GBF ? 12 : 4;
-    constexpr int R1 = PG + RB < GP ? PG + RB : GP;
-    const float* gbase = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.g) + (long long)n * a.gsn * (GBF ? 2 : 4));
-    const int iz0 = poz0 * SI - 1, iy0 = poy0 * SI - 1;
-    static_for<PG, R1>([&](auto pc) { load_g(pc, gbase, iz0, iy0); });
-    if (n != cn) {       // per-(n, channel) transform, once per batch item; kept in LDS (16 registers across the MFMA loop
-                         // cost more than four LDS reads per tile); every thread of a chunk writes the same values
-      if constexpr (NB == 1) {
-        float s8[8], h8[8];
-        if constexpr (TD) nl_coeff_vec<8>(a.td, n, a.Cd, dcb, s8, h8);
-        else nl_coeff_vec<8>(a.tg, n, a.Cg, gcb, s8, h8);
-        const int k8 = TD ? d8 : c8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { coefl[8 * k8 + j] = s8[j]; coefl[32 + 8 * k8 + j] = h8[j]; }
-      } else {
-#pragma unroll
-      for (int nb = 0; nb < (TD ? NB : 1); ++nb) {
-        float s8[8], h8[8];
-        if constexpr (TD) nl_coeff_vec<8>(a.td, n, a.Cd, dcb + 32 * nb, s8, h8);
-        else nl_coeff_vec<8>(a.tg, n, a.Cg, gcb, s8, h8);
-        const int k8 = TD ? d8 : c8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { coefl[64 * nb + 8 * k8 + j] = s8[j]; coefl[64 * nb + 32 + 8 * k8 + j] = h8[j]; }
-      }
-      }
-      cn = n;
-      __syncthreads();
-    }
-    float sc[8], sh[8];
-    // (the one-block form is kept statement for statement: the register allocation of the two-workgroup kernels is at its
-    // limit, and the paired form's loop nest around the same statements cost them 100 bytes more spills, 206 -> 295 us)
-    if constexpr (NB == 1) {
-    {
-      const float4* cq = reinterpret_cast<const float4*>(coefl + 8 * (TD ? d8 : c8));
-      const float4 s0 = cq[0], s1 = cq[1], h0 = cq[8], h1 = cq[9];
-      sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w; sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w;
-      sh[0] = h0.x; sh[1] = h0.y; sh[2] = h0.z; sh[3] = h0.w; sh[4] = h1.x; sh[5] = h1.y; sh[6] = h1.z; sh[7] = h1.w;
-    }
-#pragma unroll
-    for (int p = 0; p < DP; ++p) {
-      float v[8];
-      oct8_f8(dq[p], v);
-      if constexpr (TD) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
-      }
-      const unsigned okm = ((dok >> p) & 1u) ? 0xffffffffu : 0u;
-      if (want_db) {                                                  // bias gradient: fp32 sums of what is staged
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned cm = (dcb + j < a.Cd) ? okm : 0u;
-          dbs[0][j] += __uint_as_float(__float_as_uint(v[j]) & cm);
-        }
-      }
-      uint4 pk;
-      pk.x = wpack2(v[0], v[1]) & okm; pk.y = wpack2(v[2], v[3]) & okm;
-      pk.z = wpack2(v[4], v[5]) & okm; pk.w = wpack2(v[6], v[7]) & okm;
-      if (dtail) {
-        pk.x &= pair_mask(dcb, a.Cd); pk.y &= pair_mask(dcb + 2, a.Cd); pk.z &= pair_mask(dcb + 4, a.Cd); pk.w &= pair_mask(dcb + 6, a.Cd);
-      }
-      *reinterpret_cast<uint4*>(dst + p * 4096) = pk;
-    }
-    } else {
-#define MMTTA_COEF_REGS(nb)                                                                                            \
-    {                                                                                                                  \
-      const float4* cq = reinterpret_cast<const float4*>(coefl + 64 * (nb) + 8 * (TD ? d8 : c8));                      \
-      const float4 s0 = cq[0], s1 = cq[1], h0 = cq[8], h1 = cq[9];                                                     \
-      sc[0] = s0.x; sc[1] = s0.y; sc[2] = s0.z; sc[3] = s0.w; sc[4] = s1.x; sc[5] = s1.y; sc[6] = s1.z; sc[7] = s1.w; \
-      sh[0] = h0.x; sh[1] = h0.y; sh[2] = h0.z; sh[3] = h0.w; sh[4] = h1.x; sh[5] = h1.y; sh[6] = h1.z; sh[7] = h1.w; \
-    }
-    if constexpr (!TD || NB == 1) MMTTA_COEF_REGS(0)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-    if constexpr (TD && NB > 1) MMTTA_COEF_REGS(nb)
-    const int dcn = dcb + 32 * nb;
-#pragma unroll
-    for (int p = 0; p < DP; ++p) {
-      float v[8];
-      oct8_f8(dq[nb * DP + p], v);
-      if constexpr (TD) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = act_max(fmaf(v[j], sc[j], sh[j]), relu_lo);
-      }
-      const unsigned okm = ((dok >> p) & 1u) ? 0xffffffffu : 0u;
-      if (want_db) {                                                  // bias gradient: fp32 sums of what is staged
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const unsigned cm = (dcn + j < a.Cd) ? okm : 0u;
-          dbs[nb][j] += __uint_as_float(__float_as_uint(v[j]) & cm);
-        }
-      }
-      uint4 pk;
-      pk.x = wpack2(v[0], v[1]) & okm; pk.y = wpack2(v[2], v[3]) & okm;
-      pk.z = wpack2(v[4], v[5]) & okm; pk.w = wpack2(v[6], v[7]) & okm;
-      if (dtail) {
-        pk.x &= pair_mask(dcn, a.Cd); pk.y &= pair_mask(dcn + 2, a.Cd); pk.z &= pair_mask(dcn + 4, a.Cd); pk.w &= pair_mask(dcn + 6, a.Cd);
-      }
-      *reinterpret_cast<uint4*>(dst + nb * G::D_BYTES + p * 4096) = pk;
-    }
-    }
-    }
-    static_for<0, R1>([&](auto pc) { commit_g(pc, sc, sh); });
-    if constexpr (R1 < GP) {
-      constexpr int R2 = R1 + RB < GP ? R1 + RB : GP;
-      static_for<R1, R2>([&](auto pc) { load_g(pc, gbase, iz0, iy0); });
-      static_for<R1, R2>([&](auto pc) { commit_g(pc, sc, sh); });
-      if constexpr (R2 < GP) {
-        static_for<R2, GP>([&](auto pc) { load_g(pc, gbase, iz0, iy0); });
-        static_for<R2, GP>([&](auto pc) { commit_g(pc, sc, sh); });
-      }
-    }
-    __syncthreads();
-    if (tile + 1 < t1) issue(tile + 1);                               // lands during the MFMAs below
-    // ---- MFMAs.  Fragment f = (k step, tap slot) is read LA MFMAs before it multiplies (a ring of LA + 1 register sets;
-    // a fence per MFMA, or the scheduler sinks every read to one MFMA ahead and the MFMA waits out the LDS latency)
-    constexpr int LA = 3, NF = G::NK * 7;
-    wbf16x8 ra[LA + 1], fb[2][NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) fb[0][nb] = MMTTA_TR_FRAG(dread, nb * G::D_BYTES);
-#pragma unroll
-    for (int f = 0; f < LA; ++f) ra[f] = MMTTA_TR_FRAG(gread[f % 7], G::row_off(f / 7));
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      const int ks = f / 7, j = f % 7;
-      if (f + LA < NF) ra[(f + LA) % (LA + 1)] = MMTTA_TR_FRAG(gread[(f + LA) % 7], G::row_off((f + LA) / 7));
-      if (j == 2 && ks + 1 < G::NK) {
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) fb[(ks + 1) & 1][nb] = MMTTA_TR_FRAG(dread, nb * G::D_BYTES + (ks + 1) * 1024);
-      }
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-        acc[nb][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ra[f % (LA + 1)], fb[ks & 1][nb], acc[nb][j], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __syncthreads();
-  }
-  const int sl = sx;
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    const int tap = wave + 4 * j;
-    if (tap < 27) {
-      float* sb = a.slab + (((long long)sl * 27 + tap) * a.CGp + cg0) * a.CDp + cd0 + 32 * nb + r;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-        sb[(long long)row * a.CDp] = acc[nb][j][i];
-      }
-    }
-  }
-  if (want_db) {                                    // thread (voxel slot, chunk d8) holds channels 8 d8 .. 8 d8 + 7
-    float* red8 = lds;                              // the images are dead: the loop ended with a barrier
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      if (nb) __syncthreads();
-#pragma unroll
-      for (int c = 0; c < 8; ++c) red8[tid * 8 + c] = dbs[nb][c];
-      __syncthreads();
-      if (tid < 32) {
-        float sacc = 0.f;
-#pragma unroll 8
-        for (int q = 0; q < 64; ++q) sacc += red8[((q << 2) | (tid >> 3)) * 8 + (tid & 7)];
-        a.dbpart[(long long)sl * a.CDp + cd0 + 32 * nb + tid] = sacc;
-      }
-    }
-  }
+  constexpr bool RG = false, RD = false;
+#include "conv_wgrad_tr_body.h"
 }
 
-template <int TZ, int TY, int SI, bool GBF, bool DBF, bool TD, int NB = 1>
+// Raw staging (MMTTA_OPT_RAW_STAGING bit 1; host: wgrad_raw_bits) of the all-bf16 forms: an operand that takes no transform -
+// the gradient side always (it was unpacked and repacked), the module-input side when its norm-on-load is the identity - goes
+// to LDS as loaded.  RG / RD: the gathered / the dense operand.  The same body text with two more constants; launched from
+// the plain translation unit only.
+template <int TZ, int TY, int SI, bool TD, int NB, bool RG, bool RD>
+__global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_raw_kernel(WArgs a) {
+  constexpr bool GBF = true, DBF = true;
+#include "conv_wgrad_tr_body.h"
+}
+
+template <int TZ, int TY, int SI, bool GBF, bool DBF, bool TD, int NB = 1, bool RG = false, bool RD = false>
 static int launch_wgrad_tr_t(const WArgs& a, int S, hipStream_t s) {
   using G = WTGeo<TZ, TY, SI>;
-  auto kern = wgrad_tr_kernel<TZ, TY, SI, GBF, DBF, TD, NB>;
+  void (*kern)(WArgs);
+  if constexpr (RG || RD) kern = wgrad_tr_raw_kernel<TZ, TY, SI, TD, NB, RG, RD>;
+  else kern = wgrad_tr_kernel<TZ, TY, SI, GBF, DBF, TD, NB>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1232,10 +930,31 @@ static int launch_wgrad_tr1(const WArgs& a, int S, hipStream_t s) {
 // the module input (norm-on-load, possibly bf16-stored) is the gathered operand of a convolution and the dense one of a
 // transposed convolution (stride 2 only); the other operand is a gradient: read as is, fp32- or (method.grad_storage: bf16,
 // then next to a bf16-stored module input only) bf16-stored
+#ifdef MMTTA_ACT_LEAKY_TU
+constexpr bool WGRAD_RAW_KERNELS = false;
+#else
+constexpr bool WGRAD_RAW_KERNELS = true;
+#endif
+// the raw instantiations of one (tile, module kind, column blocks): the gradient side is raw in all of them; `both`: the
+// module-input side too
+template <int TZ, int TY, int SI, bool TD, int NB>
+static int launch_wgrad_tr_raw(const WArgs& a, int S, bool both, hipStream_t s) {
+  if (both) return launch_wgrad_tr_t<TZ, TY, SI, true, true, TD, NB, true, true>(a, S, s);
+  return launch_wgrad_tr_t<TZ, TY, SI, true, true, TD, NB, TD, !TD>(a, S, s);
+}
+
+// raw: bit 0 the module input, bit 1 the gradient tensor go to LDS as loaded (wgrad_raw_bits; bit 0 is set with bit 1 only)
 template <int TZ, int TY, int SI>
-static int launch_wgrad_tr(const WArgs& a, int S, hipStream_t s, int ncb = 1) {
+static int launch_wgrad_tr(const WArgs& a, int S, hipStream_t s, int ncb = 1, int raw = 0) {
   MMTTA_CHECK(a.gvec4 && a.dvec4, MMTTA_ERR_INVALID, "wgrad: transposed-read kernel selected for unaligned tensors");
   MMTTA_CHECK(ncb == 1 || (a.g_bf && a.d_bf), MMTTA_ERR_INVALID, "wgrad: paired column blocks exist for the all-bf16 forms");
+  if constexpr (WGRAD_RAW_KERNELS && SI == 2) {      // (stride 1 has no raw instantiation: wgrad_raw_bits)
+    if ((raw & 2) && a.g_bf && a.d_bf) {
+      const bool both = (raw & 1) != 0;
+      if (a.convt) return ncb == 2 ? launch_wgrad_tr_raw<TZ, TY, SI, true, 2>(a, S, both, s) : launch_wgrad_tr_raw<TZ, TY, SI, true, 1>(a, S, both, s);
+      return ncb == 2 ? launch_wgrad_tr_raw<TZ, TY, SI, false, 2>(a, S, both, s) : launch_wgrad_tr_raw<TZ, TY, SI, false, 1>(a, S, both, s);
+    }
+  }
   if (ncb == 2) {
     if constexpr (SI == 2) {
       if (a.convt) return launch_wgrad_tr_t<TZ, TY, SI, true, true, true, 2>(a, S, s);
@@ -2314,6 +2033,21 @@ static int launch_thin_family(const mmtta_conv_desc* d, const WGeo& w, const mmt
   return launch_status("wgrad small");
 }
 
+// Raw staging of wgrad_tr_kernel (MMTTA_OPT_RAW_STAGING bit 1): which operands of the call go to LDS as loaded - bit 0 the
+// module input x, bit 1 the gradient dy.  Both tensors bf16-stored (the all-bf16 forms), each in whole 8-channel chunks;
+// dy takes no transform, x when its norm-on-load is the identity (none, or neither mean nor scale and no activation).  x goes
+// raw next to a raw dy only.  Stride 2 only (convolutions and transposed convolutions: a box of 12x the tile's voxels is
+// staged for 28 MFMAs a wave): the stride-1 instantiations were measured slower than their twins (profiles/raw_staging_ab.md:
+// 134 against 105 us for the one-block form, which also spills two registers more) and are not built.
+// The one function behind mmtta_conv_wgrad_stages_raw and the launcher.
+static int wgrad_raw_bits(const WGeo& w, const mmtta_norm_on_load* x_norm) {
+  if (!WGRAD_RAW_KERNELS || !(g_raw_staging & 2) || w.route != W_TR_S2) return 0;
+  const mmtta_tensor *xin = w.convt ? w.dn : w.g, *grad = w.convt ? w.g : w.dn;
+  if (!is_bf16(xin) || !is_bf16(grad) || grad->c % 8 != 0) return 0;
+  const bool ident = x_norm == nullptr || (x_norm->mean == nullptr && x_norm->scale == nullptr && x_norm->relu == MMTTA_ACT_NONE);
+  return 2 | ((ident && xin->c % 8 == 0) ? 1 : 0);
+}
+
 static int launch_main_family(const WGeo& w, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, float* ws, float* dbws,
                               hipStream_t s) {
   WArgs a;
@@ -2339,8 +2073,8 @@ static int launch_main_family(const WGeo& w, const mmtta_tensor* x, const mmtta_
   const int SQ = w.S * w.nsets;          // slabs of the launch
   switch (w.route) {
     case W_TR_1X1: return launch_wgrad_tr1(a, SQ, s);
-    case W_TR_S1: return launch_wgrad_tr<4, 8, 1>(a, SQ, s, w.ncb);
-    case W_TR_S2: return launch_wgrad_tr<2, 4, 2>(a, SQ, s, w.ncb);
+    case W_TR_S1: return launch_wgrad_tr<4, 8, 1>(a, SQ, s, w.ncb, wgrad_raw_bits(w, x_norm));
+    case W_TR_S2: return launch_wgrad_tr<2, 4, 2>(a, SQ, s, w.ncb, wgrad_raw_bits(w, x_norm));
     case W_F32_1X1: return launch_wgrad<4, 4, 8, 1>(a, SQ, s);
     case W_F32_S1: return launch_wgrad<4, 4, 8, 7>(a, SQ, s);
     default: return launch_wgrad<2, 2, 8, 7>(a, SQ, s);
@@ -2474,6 +2208,14 @@ extern "C" int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* d, const mmtta_ten
   const int st = wgeometry(d, x, dy, nullptr, w);
   if (st) return st < 0 ? st : -st;
   return w.route;
+}
+
+extern "C" int mmtta_conv_wgrad_stages_raw(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                           const mmtta_tensor* dy) {
+  WGeo w{};
+  const int st = wgeometry(d, x, dy, nullptr, w);
+  if (st) return st < 0 ? st : -st;
+  return nl_leaky(x_norm) ? 0 : wgrad_raw_bits(w, x_norm);      // (a LeakyReLU call runs the instantiation without raw kernels)
 }
 
 extern "C" int mmtta_conv_wgrad(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
