@@ -186,6 +186,16 @@ int mmtta_abi_version(void);
  * transform made it +0.0; sums start at +0, so no output bit depends on it), and a stored NaN stays a NaN, where the
  * transform's fmaxf(NaN, -inf) turned it into -inf.  Returns the previous value. */
 #define MMTTA_OPT_RAW_STAGING 16
+/* Two passes over the full-resolution tensors of an entropy-minimisation step that the result does not need (a bit mask;
+ * default 3; 0: the launches as before, in the same process).
+ *   bit 0  mmtta_conv_head_loss_run_sets: the 3x3x3 stride-1 R -> R head convolution (R <= 4) on the 4x4x4 matrix tiles with
+ *          the Bernoulli entropy objective in its epilogue (csrc/conv_direct.hip: conv3_mfma4_loss_kernel).  The logits of a
+ *          step are read by the objective alone: they are not stored, and mmtta_entropy_loss_items' pass over them goes.
+ *          d(logits) equal bit for bit, the loss within the order of its fp64 partial sums.  mmtta_conv_head_loss_eligible
+ *          tells whether a call qualifies; with the bit clear it says no and the entry point refuses.
+ *   bit 1  reserved for the paired thin weight gradients of a stride-2 residual block (not built).
+ * Returns the previous value. */
+#define MMTTA_OPT_HEAD_LOSS_PAIR 17
 int mmtta_set_option(int key, int value);
 
 /* ------------------------------------------------------------------ layout (boundary) ---- */
@@ -322,6 +332,31 @@ int mmtta_conv_run_sets(const mmtta_conv_desc* desc, const mmtta_tensor* x, cons
                         const void* packed, const float* bias, const mmtta_conv_epilogue* epi,
                         const mmtta_tensor* y, int accumulate, float* stats, void* workspace,
                         int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);
+
+/* The head convolution of an entropy-minimisation step with the objective as its tail (MMTTA_OPT_HEAD_LOSS_PAIR bit 0):
+ * mmtta_conv_run_sets(desc, x, x_norm, packed, bias, epi, y, 0, NULL, ...) followed by mmtta_entropy_loss_items(y, softmax,
+ * dlogits, ...) in one launch (plus the finish kernel) that never stores y.  `y` describes the logits the convolution would
+ * have produced (shape, strides and storage decide eligibility and the order of dlogits); its memory is not touched.
+ *   dlogits   fp32- or bf16-stored gradient of the shape of y, equal bit for bit to the two calls' (pad lanes zero)
+ *   partial   mmtta_conv_head_loss_partials doubles: one per workgroup, [item][workgroup of the item]
+ *   loss      [N] (per_item != 0: every batch item its own objective, as mmtta_entropy_loss_items), or [1] for N == 1;
+ *             equal to the two calls' within the summation order of the fp64 partials
+ * A call qualifies when it routes to the 4x4x4 matrix-tile kernel of bf16 precision (mmtta_conv_route 6, desc.op
+ * MMTTA_CONV_FWD, 3x3x3 stride 1, <= 4 channels on both sides, MMTTA_OPT_THIN_MFMA != 0) with x, y and the fused add
+ * fp32-stored and no LeakyReLU on either; softmax == 0; per_item != 0 or N == 1; y and dlogits in dense 16-byte (bf16: 8-byte)
+ * voxel rows, dlogits owning its pad lane (the fast path of mmtta_entropy_loss_items); an item below 2^31 elements and of
+ * at most 2048 workgroups (tiles of MMTTA_OPT_THIN_MFMA's depth x 8 x 64 voxels).  Anything else: _eligible returns 0 and
+ * _run_sets MMTTA_ERR_UNSUPPORTED before anything is launched - the caller keeps the two calls.  _eligible is host-only and
+ * returns 1 / 0 or a negative mmtta error code for descriptors mmtta_conv_run itself would reject; _partials returns -1 for
+ * a call that is not route 6. */
+int mmtta_conv_head_loss_eligible(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                  const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dlogits,
+                                  int softmax, int per_item);
+int64_t mmtta_conv_head_loss_partials(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_tensor* y);
+int mmtta_conv_head_loss_run_sets(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                  const void* packed, const float* bias, const mmtta_conv_epilogue* epi,
+                                  const mmtta_tensor* y, const mmtta_tensor* dlogits, int softmax, int per_item,
+                                  double* partial, float* loss, const mmtta_param_sets* sets, void* stream);
 
 /* Weight (and bias) gradient.
  *   Replaces: autograd's weight-gradient of Conv3d / ConvTranspose3d

@@ -130,6 +130,12 @@ _SIGNATURES = {
                                       _P(Tensor), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
     "mmtta_conv_route": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_stages_raw": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
+    "mmtta_conv_head_loss_eligible": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), _P(Tensor),
+                                                C.c_int, C.c_int]),
+    "mmtta_conv_head_loss_partials": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor)]),
+    "mmtta_conv_head_loss_run_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), C.c_void_p, C.c_void_p, _P(ConvEpilogue),
+                                                _P(Tensor), _P(Tensor), C.c_int, C.c_int, C.c_void_p, C.c_void_p, _P(ParamSets),
+                                                C.c_void_p]),
     "mmtta_conv_wgrad_workspace_bytes": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor)]),
     "mmtta_conv_wgrad_workspace_bytes_sets": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor), _P(ParamSets)]),
     "mmtta_conv_wgrad_plan_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(Tensor), _P(ParamSets), _P(C.c_int32)]),
@@ -293,6 +299,8 @@ def load() -> C.CDLL:
         lib.mmtta_set_option(10, int(os.environ["MMTTA_LEAN"]))
     if "MMTTA_RAWSTAGE" in os.environ:                   # A/B aid: MMTTA_OPT_RAW_STAGING (same results bit for bit)
         lib.mmtta_set_option(16, int(os.environ["MMTTA_RAWSTAGE"]))
+    if "MMTTA_HEADLOSS" in os.environ:                   # A/B aid: MMTTA_OPT_HEAD_LOSS_PAIR (same gradients bit for bit)
+        lib.mmtta_set_option(17, int(os.environ["MMTTA_HEADLOSS"]))
     _lib = lib
     return lib
 

@@ -41,7 +41,8 @@ extern int g_lame_tiled;            // api.hip: MMTTA_OPT_LAME_TILED
 extern int g_thin_mfma;             // api.hip: MMTTA_OPT_THIN_MFMA
 extern int g_epilogue_vec;          // api.hip: MMTTA_OPT_EPILOGUE_VEC16
 extern int g_raw_staging;           // api.hip: MMTTA_OPT_RAW_STAGING (bit 0: implicit GEMM, bit 1: transposed-read weight gradient)
-extern int g_tune[4];               // api.hip: launch-geometry knobs (MMTTA_OPT_SPLITK_BELOW ... MMTTA_OPT_WGRAD_THIN_SLABS)
+extern int g_head_loss_pair;        // api.hip: MMTTA_OPT_HEAD_LOSS_PAIR (bit 0: entropy objective in the head convolution, bit 1: paired thin weight gradients)
+extern int g_tune[4];              // api.hip: launch-geometry knobs (MMTTA_OPT_SPLITK_BELOW ... MMTTA_OPT_WGRAD_THIN_SLABS)
 
 // ---- activation of a norm-on-load (mmtta_norm_on_load.relu: MMTTA_ACT_*).
 // The four sources that read a norm-on-load (conv_igemm, conv_direct, conv_wgrad, pointwise) are compiled TWICE:
@@ -598,6 +599,13 @@ int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
 int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
                     const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
                     const PSets& sets, hipStream_t stream);
+// the head convolution with the entropy objective in its epilogue (conv_direct.hip; the plain translation unit only)
+bool direct_head_loss_eligible(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                               const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz, int softmax,
+                               int per_item);
+int direct_head_loss_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
+                         const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz,
+                         double* partial, float* loss, const PSets& sets, hipStream_t stream);
 
 MMTTA_ACT_NS_CLOSE
 }  // namespace mmtta

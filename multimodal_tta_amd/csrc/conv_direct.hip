@@ -13,6 +13,9 @@
 //   gather      in = out*stride + k - pad                    (Conv3d forward, ConvTranspose3d input gradient)
 //   transposed  t = out + pad - k, in = t/stride if t % stride == 0   (ConvTranspose3d forward, Conv3d input gradient)
 #include "common.h"
+#ifndef MMTTA_ACT_LEAKY_TU
+#include "voxel_loss.h"      // the entropy terms and the finish kernel of conv3_mfma4_loss_kernel
+#endif
 
 namespace mmtta {
 MMTTA_ACT_NS_OPEN
@@ -496,221 +499,27 @@ typedef float cf4v __attribute__((ext_vector_type(4)));
 // when the thin gradients are bf16-stored, round 3: the operands are rounded to bf16 while staging either way)
 template <bool HAS_T, int TZ, bool GBF = false>
 __global__ __launch_bounds__(256) void conv3_mfma4_kernel(DArgs a) {
-  // 8 x 8 x 64 tile: the halo box is 1.6x the tile.  The box rows are padded to 68 voxels so that a staging item is a run
-  // of 4 voxels along x (one decode, one row address, four 16-byte loads): phase timing of the first version showed 26 of
-  // its 44 us in per-voxel index / address arithmetic and in 108 scalar weight loads per lane, not in loads or MFMAs.
-  constexpr int TY = 8, TX = 64, BZ = TZ + 2, BY = TY + 2, BX = 68, RUNS = BX / 4, NRUN = BZ * BY * RUNS;
-  __shared__ uint2 box[BZ * BY * BX];
-  __shared__ uint2 wtab[27 * 4];                // [tap][column] x 4 k values (bf16)
-  __shared__ float red[32];
-  const int n = blockIdx.y;
-  a.w = pset_packed(a.ps, a.w, n); a.bias = pset_bias(a.ps, a.bias, n);      // this batch item's parameter set
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int txn = (a.out.w + TX - 1) / TX, tyn = (a.out.h + TY - 1) / TY;
-  int t = blockIdx.x;
-  const int txi = t % txn; t /= txn;
-  const int tyi = t % tyn;
-  const int tzi = t / tyn;
-  const int oz0 = tzi * TZ, oy0 = tyi * TY, ox0 = txi * TX;
-  // ---- B operand table: column j of tap tp = the 4 k values w[tp][k][j] (fp32 image [tap][K][4], mirrored for the gradient)
-  if (tid < 27 * 4) {
-    const int tp = tid >> 2, j = tid & 3;
-    const float* wt = a.w + (a.transposed ? 26 - tp : tp) * a.K * 4;
-    float wk[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) wk[k] = (k < a.K && j < a.N) ? wt[k * 4 + j] : 0.f;
-    wtab[tid] = make_uint2(f32x2_to_bf16x2(wk[0], wk[1]), f32x2_to_bf16x2(wk[2], wk[3]));
-  }
-  {  // ---- stage the halo box: runs of 4 voxels, two runs (8 loads) in flight per thread
-    constexpr int NIT = (NRUN + 255) / 256, RND = NIT;      // every load of the box in flight at once (RND = 2: two dependent round trips)
-    float sc[4] = {1.f, 1.f, 1.f, 1.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
-    if (HAS_T) nl_coeff_vec<4>(a.tin, n, a.K, 0, sc, sh);          // channels >= K: scale = shift = 0
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k >= a.K) { sc[k] = 0.f; sh[k] = 0.f; }                   // pad lanes of the voxel row may hold anything
-    const float relu_lo = act_lo(HAS_T ? a.tin.relu : MMTTA_ACT_ID);
-    const float* inb = GBF ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(a.in.p) + (long long)n * a.in.sn)
-                           : a.in.p + (long long)n * a.in.sn;
-    const unsigned isw = (unsigned)a.in.sw;
-#pragma unroll 1
-    for (int j0 = 0; j0 < NIT; j0 += RND) {
-      float4 raw[RND][4];
-      unsigned okm = 0u;
-#pragma unroll
-      for (int j = 0; j < RND; ++j) {
-        const int v = min(tid + 256 * (j0 + j), NRUN - 1);
-        const int bz = v / (BY * RUNS), rem = v - bz * (BY * RUNS), by = rem / RUNS, run = rem - by * RUNS;
-        const int iz = oz0 - 1 + bz, iy = oy0 - 1 + by, ix = ox0 - 1 + 4 * run;
-        const bool rok = (unsigned)iz < (unsigned)a.in.d && (unsigned)iy < (unsigned)a.in.h;
-        const long long rowo = (long long)min(max(iz, 0), a.in.d - 1) * a.in.sd + (long long)min(max(iy, 0), a.in.h - 1) * a.in.sh;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          okm |= ((rok && (unsigned)(ix + q) < (unsigned)a.in.w) ? 1u : 0u) << (4 * j + q);
-          const long long eo = rowo + (unsigned)min(max(ix + q, 0), a.in.w - 1) * isw;
-          if constexpr (GBF) {          // the four bf16 channels travel in two dwords of the raw register
-            const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(inb) + eo);
-            raw[j][q].x = __uint_as_float(u.x); raw[j][q].y = __uint_as_float(u.y);
-          } else {
-            raw[j][q] = *reinterpret_cast<const float4*>(inb + eo);
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < RND; ++j) {
-        uint2 pk[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if constexpr (GBF) {
-            const unsigned ux = __float_as_uint(raw[j][q].x), uy = __float_as_uint(raw[j][q].y);
-            raw[j][q] = make_float4(bf16_bits_to_f32(ux & 0xffffu), __uint_as_float(ux & 0xffff0000u),
-                                    bf16_bits_to_f32(uy & 0xffffu), __uint_as_float(uy & 0xffff0000u));
-          }
-          const float xs[4] = {raw[j][q].x, raw[j][q].y, raw[j][q].z, raw[j][q].w};
-          float v4[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) v4[k] = act_max(fmaf(xs[k], sc[k], sh[k]), relu_lo);
-          const unsigned m = ((okm >> (4 * j + q)) & 1u) ? 0xffffffffu : 0u;
-          pk[q].x = f32x2_to_bf16x2(v4[0], v4[1]) & m; pk[q].y = f32x2_to_bf16x2(v4[2], v4[3]) & m;
-        }
-        if (tid + 256 * (j0 + j) < NRUN) {
-          // run v = voxels 4 v .. 4 v + 3 of its box row.  The first 64 voxels of a row are stored PERMUTED, voxel xi at slot
-          // (xi % 16) * 4 + xi / 16: the A operand of lane (blk, arow) is voxel 16 arow + blk (+ tap), and in plain order
-          // arow 0 / 2 and 1 / 3 met in the same banks (SQ_LDS_BANK_CONFLICT: 42 % of the launch's cycles per CU);
-          // permuted, the 64 lanes of a tap read 64 consecutive slots
-          const int v = tid + 256 * (j0 + j), brow = v / RUNS, run = v - brow * RUNS;
-          uint2* drow = box + brow * BX;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) drow[run < 16 ? 16 * (run & 3) + 4 * q + (run >> 2) : 64 + q] = pk[q];
-        }
-      }
-    }
-  }
-  const int jc = lane & 3, blk = lane >> 2;
-  float bias = 0.f, asc = 1.f, ash = 0.f;
-  if (jc < a.N) {
-    if (a.bias) bias = a.bias[jc];
-    if (a.add) nl_coeff(a.tadd, n, a.N, jc, asc, ash);
-  }
-  __syncthreads();
-  cs4 wb[27];
-#pragma unroll
-  for (int tp = 0; tp < 27; ++tp) wb[tp] = __builtin_bit_cast(cs4, wtab[tp * 4 + jc]);
-  float ssum = 0.f, ssq = 0.f;
-  const int arow = lane & 3;                    // A: this lane supplies row `arow` of block `blk`: voxel x = 16 arow + blk
-  const int jl = min(jc, a.N - 1);
-  // element offsets of this lane's four output voxels inside a row (x = ox0 + 16 r + blk), and whether they exist
-  unsigned xoff_o[4], xoff_a[4];
-  unsigned xok = 0u;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int ox = ox0 + 16 * r + blk;
-    xok |= (ox < a.out.w ? 1u : 0u) << r;
-    xoff_o[r] = (unsigned)min(ox, a.out.w - 1) * (unsigned)a.out.sw;
-    xoff_a[r] = (unsigned)min(ox, a.out.w - 1) * (unsigned)a.asw;
-  }
-  // the fused-add / accumulate operands of trip rp + 1 are requested before the MFMAs of trip rp: behind the MFMA loop
-  // every trip waited a full memory latency for them (both 3 -> 3 launches of a step carry the residual add)
-  float addn[2][4], oldn[2][4];
-  auto fetch = [&](int rp) {
-    const int r0 = rp * 8 + wave * 2;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int oz = min(oz0 + (r0 + q) / TY, a.out.d - 1), oy = min(oy0 + (r0 + q) % TY, a.out.h - 1);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { addn[q][r] = 0.f; oldn[q][r] = 0.f; }
-      if (a.add) {
-        const long long ao = (long long)n * a.asn + (long long)oz * a.asd + (long long)oy * a.ash;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) addn[q][r] = ld1_t<GBF>(a.add, ao + xoff_a[r] + jl);
-      }
-      if (a.accumulate) {
-        const long long oo = (long long)n * a.out.sn + (long long)oz * a.out.sd + (long long)oy * a.out.sh;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) oldn[q][r] = ld1_t<GBF>(a.out.p, oo + xoff_o[r] + jl);
-      }
-    }
-  };
-  fetch(0);
-#pragma unroll 1
-  for (int rp = 0; rp < TZ * TY / 8; ++rp) {    // two rows of the tile per wave and trip (independent accumulator chains)
-    const int r0 = rp * 8 + wave * 2;
-    float addc[2][4], oldc[2][4];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { addc[q][r] = addn[q][r]; oldc[q][r] = oldn[q][r]; }
-    if (rp + 1 < TZ * TY / 8) fetch(rp + 1);
-    cf4v acc[2];
-    const uint2* ab[2][3];                        // per x tap: the lane's slot of voxel 16 arow + blk + dx in the permuted row
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int zl = (r0 + q) / TY, yl = (r0 + q) % TY;
-#pragma unroll
-      for (int dx = 0; dx < 3; ++dx) {
-        const int xi = 16 * arow + blk + dx;
-        ab[q][dx] = box + (zl * BY + yl) * BX + (xi < 64 ? ((xi & 15) << 2) | (xi >> 4) : xi);
-      }
-      acc[q] = cf4v{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int tp = 0; tp < 27; ++tp) {
-      const int toff = ((tp / 9) * BY + (tp / 3) % 3) * BX;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const uint2 av = ab[q][tp % 3][toff];
-        acc[q] = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(cs4, av), wb[tp], acc[q], 0, 0, 0);
-      }
-    }
-    // ---- epilogue: register r of lane (blk, jc) = output voxel x = 16 r + blk, channel jc
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int oz = oz0 + (r0 + q) / TY, oy = oy0 + (r0 + q) % TY;
-      const bool rowok = oz < a.out.d && oy < a.out.h;
-      const long long orowo = (long long)n * a.out.sn + (long long)min(oz, a.out.d - 1) * a.out.sd + (long long)min(oy, a.out.h - 1) * a.out.sh;
-      float* orow = a.out.p + orowo;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = acc[q][r] + bias;
-        if (a.add) v += nl_apply(addc[q][r], asc, ash, a.tadd.relu);
-        if (a.accumulate) v += oldc[q][r];
-        if constexpr (GBF) {
-          // 8-byte voxels: channel lanes pair up, the even one stores both as one dword (a 2-byte store per lane is a partial
-          // dword write); channels >= N are stored as zeros (the rows own their pad)
-          v = jc < a.N ? v : 0.f;
-          const float other = __shfl_xor(v, 1, 64);
-          if (rowok && ((xok >> r) & 1u)) {
-            if (!(jc & 1))
-              *reinterpret_cast<unsigned int*>(reinterpret_cast<unsigned short*>(a.out.p) + orowo + xoff_o[r] + jc) = f32x2_to_bf16x2(v, other);
-            if (jc < a.N) { ssum += v; ssq += v * v; }
-          }
-          continue;
-        }
-        if (rowok && ((xok >> r) & 1u)) {
-          if (jc < a.N) {
-            orow[xoff_o[r] + jc] = v;
-            ssum += v; ssq += v * v;
-          } else if (a.out_vec4) {
-            orow[xoff_o[r] + jc] = 0.f;          // the view owns its pad lanes: keep them zero
-          }
-        }
-      }
-    }
-  }
-  if (a.stats != nullptr) {   // lanes with the same l & 3 hold the same channel
-#pragma unroll
-    for (int o = 4; o < 64; o <<= 1) { ssum += __shfl_xor(ssum, o, 64); ssq += __shfl_xor(ssq, o, 64); }
-    if (lane < 4) { red[(0 * 4 + wave) * 4 + lane] = ssum; red[(1 * 4 + wave) * 4 + lane] = ssq; }
-    __syncthreads();
-    if (tid < a.N) {
-      const float s2 = red[0 * 4 + tid] + red[1 * 4 + tid] + red[2 * 4 + tid] + red[3 * 4 + tid];
-      const float q2 = red[16 + 0 * 4 + tid] + red[16 + 1 * 4 + tid] + red[16 + 2 * 4 + tid] + red[16 + 3 * 4 + tid];
-      const long long rrow = (long long)n * a.blocks_per_n + blockIdx.x;
-      a.stats[(rrow * 2 + 0) * a.N + tid] = s2;
-      a.stats[(rrow * 2 + 1) * a.N + tid] = q2;
-    }
-  }
+#include "conv3_mfma4_body.h"
 }
+
+#ifndef MMTTA_ACT_LEAKY_TU
+// The head convolution of an entropy-minimisation step with the objective in its epilogue (MMTTA_OPT_HEAD_LOSS_PAIR bit 0;
+// host: direct_head_loss_eligible): the logits of a step are read by the loss alone, so they are never stored - 16 bytes
+// written and 16 read per voxel - and loss_vec_kernel's launch goes.  The same body text with the loss epilogue switched in;
+// fp32-stored operands only (GBF = false), launched from the plain translation unit only.
+struct HeadLoss {
+  float* dz; long long dsn; int dbf;      // d(logits): dense 4-lane voxel rows, bf16- (8-byte) or fp32-stored (16-byte)
+  float inv_count;                        // 1 / (voxels x regions) of one item
+  double* partial;                        // [item][workgroup]
+};
+template <bool HAS_T, int TZ>
+__global__ __launch_bounds__(256) void conv3_mfma4_loss_kernel(DArgs a, HeadLoss hl) {
+  constexpr bool GBF = false;
+#define MMTTA_HEAD_LOSS_BODY
+#include "conv3_mfma4_body.h"
+#undef MMTTA_HEAD_LOSS_BODY
+}
+#endif
 
 // ------------------------------------------------------------------ stride-2 up-convolution to <= 4 channels
 // ConvTranspose3d K -> R (k3, s2, p1, output_padding 1) with K = 32 / 64: the full-resolution last layer of the U-Net.
@@ -1968,6 +1777,59 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   MMTTA_BF_DISPATCH(has_t, HT, { hipLaunchKernelGGL(direct_conv_kernel<HT>, dim3(a.blocks_per_n, y->n), dim3(256), lds, stream, a); });
   return launch_status("direct conv");
 }
+
+#ifndef MMTTA_ACT_LEAKY_TU
+// ---- the head convolution with the entropy objective in its epilogue (conv3_mfma4_loss_kernel)
+// A call of route 6 qualifies when direct_conv_run would launch conv3_mfma4_kernel<HT, TZ, false> for it - the 4x4x4 matrix
+// tiles on fp32-stored x, y and fused add, nothing accumulated, no statistics rows - and mmtta_entropy_loss_items would run
+// loss_vec_kernel on its result: sigmoid head, logits and gradient in dense 4-lane voxel rows, the gradient owning its pad,
+// every item its own objective (or a batch of one), and no more workgroups per item than an item has partial slots.
+// The one predicate behind mmtta_conv_head_loss_eligible and the entry point.
+bool direct_head_loss_eligible(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                               const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz, int softmax,
+                               int per_item) {
+  const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
+  if (!(g_head_loss_pair & 1) || softmax || !(per_item || y->n == 1)) return false;
+  if (d->op != MMTTA_CONV_FWD || !direct_applicable(d) || direct_variant(d, x) != 4) return false;
+  if (!is_f32(x) || !is_f32(y) || (add && !is_f32(add))) return false;
+  if (nl_leaky(x_norm) || (add && nl_leaky(&epi->add_norm))) return false;      // (the LeakyReLU instantiation has no twin)
+  if (dz == nullptr || dz->ptr == nullptr || !(is_f32(dz) || is_bf16(dz)) || !is_cl(dz) || !same_shape(dz, y)) return false;
+  if (!loss_vec(y, dz) || !loss_small_item(y)) return false;
+  return direct_blocks_per_n(d, x, y) <= LOSS_MAX_BLOCKS;
+}
+
+int direct_head_loss_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
+                         const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz,
+                         double* partial, float* loss, const PSets& sets, hipStream_t stream) {
+  DArgs a;
+  a.ps = sets;
+  a.in = tv(x); a.tin = nl(x_norm); a.out = tv(y);
+  a.w = (const float*)packed; a.bias = bias;
+  const int st = epilogue_add(epi, y, a);
+  if (st) return st;
+  a.K = x->c; a.N = y->c; a.ksize = d->ksize; a.stride = d->stride;
+  a.transposed = 0; a.accumulate = 0; a.out_vec4 = 0;
+  a.stats = nullptr; a.blocks_per_n = direct_blocks_per_n(d, x, y);
+  HeadLoss hl;
+  hl.dz = (float*)dz->ptr; hl.dsn = dz->sn; hl.dbf = is_bf16(dz) ? 1 : 0;
+  const double cnt = (double)y->d * y->h * y->w * y->c;      // one item's (voxel, region) pairs: loss_launch's count
+  hl.inv_count = (float)(1.0 / cnt);
+  hl.partial = partial;
+  const bool has_t = a.tin.mean != nullptr || a.tin.scale != nullptr;
+  const dim3 grid(a.blocks_per_n, y->n), block(256);
+  MMTTA_BF_DISPATCH(has_t, HT, {
+    switch (g_thin_mfma) {      // the tile depth TZ (MMTTA_OPT_THIN_MFMA), as direct_conv_run picks it
+      case 3: hipLaunchKernelGGL((conv3_mfma4_loss_kernel<HT, 2>), grid, block, 0, stream, a, hl); break;
+      case 2: hipLaunchKernelGGL((conv3_mfma4_loss_kernel<HT, 4>), grid, block, 0, stream, a, hl); break;
+      default: hipLaunchKernelGGL((conv3_mfma4_loss_kernel<HT, 8>), grid, block, 0, stream, a, hl); break;
+    }
+  });
+  int ls = launch_status("direct conv (4x4x4 matrix tiles, entropy epilogue)");
+  if (ls || g_profile_main_only) return ls;      // (MMTTA_OPT_PROFILE_MAIN_KERNEL_ONLY stops here)
+  hipLaunchKernelGGL(mean_finish_kernel, dim3(y->n), dim3(64), 0, stream, (const double*)partial, a.blocks_per_n, 1.0 / cnt, loss);
+  return launch_status("direct conv (entropy epilogue) finish");
+}
+#endif
 
 MMTTA_ACT_NS_CLOSE
 }  // namespace mmtta

@@ -1551,6 +1551,56 @@ extern "C" int mmtta_conv_stages_raw(const mmtta_conv_desc* d, const mmtta_tenso
   return (raw_staging(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
 }
 
+// ---- the head convolution with the entropy objective in its epilogue (MMTTA_OPT_HEAD_LOSS_PAIR bit 0)
+static int head_loss_plan(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                          const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz, int softmax, int per_item,
+                          bool& eligible) {
+  Geometry g;
+  const int st = plan_run(d, x, x_norm, epi, y, 0, nullptr, nullptr, g);
+  if (st) return st;
+  eligible = g.route == C_DIRECT && direct_head_loss_eligible(d, x, x_norm, epi, y, dz, softmax, per_item);
+  return MMTTA_OK;
+}
+
+extern "C" int mmtta_conv_head_loss_eligible(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                             const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dlogits,
+                                             int softmax, int per_item) {
+  bool ok = false;
+  const int st = head_loss_plan(d, x, x_norm, epi, y, dlogits, softmax, per_item, ok);
+  if (st) return st < 0 ? st : -st;
+  return ok ? 1 : 0;
+}
+
+extern "C" int64_t mmtta_conv_head_loss_partials(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y) {
+  Geometry g;
+  if (geometry(d, x, y, nullptr, g) || g.route != C_DIRECT) return -1;
+  return (int64_t)direct_blocks_per_n(d, x, y) * y->n;
+}
+
+extern "C" int mmtta_conv_head_loss_run_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                             const void* packed, const float* bias, const mmtta_conv_epilogue* epi,
+                                             const mmtta_tensor* y, const mmtta_tensor* dlogits, int softmax, int per_item,
+                                             double* partial, float* loss, const mmtta_param_sets* sets, void* stream) {
+  int st = nl_act_check(x_norm, "conv_head_loss_run (x_norm)");
+  if (st) return st;
+  st = nl_act_check((epi && epi->add) ? &epi->add_norm : nullptr, "conv_head_loss_run (epilogue add_norm)");
+  if (st) return st;
+  st = nl_per_item_check(x_norm, "conv_head_loss_run (x_norm)");
+  if (st) return st;
+  st = nl_per_item_check(epi ? &epi->add_norm : nullptr, "conv_head_loss_run (epilogue add_norm)");
+  if (st) return st;
+  bool ok = false;
+  st = head_loss_plan(d, x, x_norm, epi, y, dlogits, softmax, per_item, ok);
+  if (st) return st;
+  MMTTA_CHECK(ok, MMTTA_ERR_UNSUPPORTED,
+              "conv_head_loss_run: not a sigmoid head on the 4x4x4 matrix tiles with a dense 4-lane `dlogits` (ask "
+              "mmtta_conv_head_loss_eligible; run mmtta_conv_run and mmtta_entropy_loss_items instead)");
+  MMTTA_CHECK(packed != nullptr && partial != nullptr && loss != nullptr, MMTTA_ERR_INVALID, "conv_head_loss_run: null argument");
+  st = psets_validate(sets, x->n);
+  if (st) return st;
+  return direct_head_loss_run(d, x, x_norm, packed, bias, epi, y, dlogits, partial, loss, psets(sets), (hipStream_t)stream);
+}
+
 extern "C" int mmtta_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                               const void* packed, const float* bias, const mmtta_conv_epilogue* epi,
                               const mmtta_tensor* y, int accumulate, float* stats, void* workspace,

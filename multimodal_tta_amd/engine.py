@@ -381,6 +381,18 @@ class ConvolutionBlock(Block):
             self.conv.op.dgrad(dy, dx, accumulate, add=add)
 
 
+class HeadLossTail:
+    """The plain entropy objective handed to the network's last convolution (``forward_cl(..., tail=)``): when that
+    convolution can take it (``ConvOp.head_loss_eligible``) it leaves d(logits) and the per-item loss and does NOT store the
+    logits - ``done`` says so, and the caller then skips its own objective launch.  ``dlogits_for(logits)`` gives the
+    gradient buffer for the logits tensor the forward would have written."""
+
+    def __init__(self, dlogits_for, loss: torch.Tensor, per_item: bool):
+        self.dlogits_for, self.loss, self.per_item = dlogits_for, loss, bool(per_item)
+        self.dlogits: Optional[torch.Tensor] = None
+        self.done = False
+
+
 class ResidualUnitBlock(Block):
     """monai ResidualUnit: ``conv(x) + residual(x)``, residual = identity | conv k3 (strided) | conv k1."""
 
@@ -393,13 +405,30 @@ class ResidualUnitBlock(Block):
     def out_shape(self, x):
         return self.units[0].conv.op.out_shape(x)[:4] + (self.units[-1].conv.op.cout,)
 
-    def fwd(self, x: torch.Tensor, x_nl: Optional[NL], out: torch.Tensor) -> torch.Tensor:
+    def _fwd_tail(self, unit: ConvolutionBlock, cur, cur_nl, x, x_nl, out, tail: "HeadLossTail") -> bool:
+        """The conv-only last unit with the objective in its epilogue, when the library takes the call."""
+        op = unit.conv.op
+        dlogits = tail.dlogits_for(out)
+        if not op.head_loss_eligible(cur, cur_nl, out, dlogits, add=x, add_nl=x_nl, per_item=tail.per_item):
+            return False
+        partial = self.rt.pool.flat((self.key, "head_loss_partial"), op.head_loss_partials(cur, out), dtype=torch.float64)
+        op.forward_head_loss(cur, cur_nl, unit.conv.bias_data(), out, dlogits, partial, tail.loss, add=x, add_nl=x_nl,
+                             per_item=tail.per_item)
+        tail.dlogits, tail.done = dlogits, True
+        return True
+
+    def fwd(self, x: torch.Tensor, x_nl: Optional[NL], out: torch.Tensor, tail: Optional["HeadLossTail"] = None) -> torch.Tensor:
         cur, cur_nl = x, x_nl
         self.fused_last = False
         for u, unit in enumerate(self.units):
             last = u == len(self.units) - 1
             if last and unit.norm is None and self.residual is None:
                 # conv-only last unit + identity residual: the add is this conv's epilogue
+                if tail is not None and self._fwd_tail(unit, cur, cur_nl, x, x_nl, out, tail):
+                    unit.saved = (cur, cur_nl, out, None)      # (`out` was not written: the backward reads the inputs only)
+                    self.fused_last = True
+                    self.saved = (x, x_nl)
+                    return out
                 unit.conv.op.forward(cur, cur_nl, unit.conv.bias_data(), out, add=x, add_nl=x_nl)
                 unit.saved = (cur, cur_nl, out, None)
                 self.fused_last = True

@@ -124,7 +124,9 @@ class UNetRuntime(Runtime):
         zero = self.pool.flat("in_keep_shift", n * self.in_channels, zero=True)
         return ops.NL(zero, zero, None, None, relu=False, scale=scale, shift=zero)
 
-    def forward_cl(self, x_cl: torch.Tensor, present=None) -> torch.Tensor:
+    supports_head_tail = True      # forward_cl(..., tail=): the objective may ride in the last convolution (engine.HeadLossTail)
+
+    def forward_cl(self, x_cl: torch.Tensor, present=None, tail=None) -> torch.Tensor:
         n, D, H, W, _ = x_cl.shape
         if present is not None and len(present) != self.in_channels:
             raise ValueError(f"modality mask has {len(present)} entries for {self.in_channels} input channels")
@@ -155,7 +157,7 @@ class UNetRuntime(Runtime):
                 logits = out
             if self.upru[i] is not None:
                 yt, nl = self.upconv[i].fwd(cat, None)
-                self.upru[i].fwd(yt, nl, out)
+                self.upru[i].fwd(yt, nl, out, tail=tail if i == 0 else None)
             elif self.upconv[i].norm is not None:
                 yt, nl = self.upconv[i].fwd(cat, None)
                 ops.combine(yt, nl, None, None, out)

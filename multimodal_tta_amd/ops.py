@@ -526,6 +526,64 @@ class ConvOp:
                 add_nl: Optional[NL] = None, accumulate: bool = False) -> None:
         self._run(self.d_fwd, self.packed_fwd, x, x_nl, bias, y, accumulate, stats, add, add_nl)
 
+    # ---- the head convolution with the entropy objective as its tail (MMTTA_OPT_HEAD_LOSS_PAIR bit 0)
+    def _head_loss_args(self, x, x_nl, y, dlogits, add, add_nl):
+        dx, dy, dg = desc_cl(x), desc_cl(y), desc_cl(dlogits)
+        nls, nlr = _nl_ref(x_nl)
+        epi = keep = None
+        if add is not None:
+            keep = desc_cl(add)
+            epi = ConvEpilogue(C.pointer(keep), add_nl.struct() if add_nl is not None else _lib.norm_on_load())
+        return dx, dy, dg, nls, nlr, keep, epi
+
+    def head_loss_eligible(self, x: torch.Tensor, x_nl: Optional[NL], y: torch.Tensor, dlogits: torch.Tensor,
+                           add: Optional[torch.Tensor] = None, add_nl: Optional[NL] = None, softmax: bool = False,
+                           per_item: bool = True) -> bool:
+        """Whether ``forward_head_loss`` takes this call (mmtta_conv_head_loss_eligible; host only, launches nothing)."""
+        dx, dy, dg, nls, nlr, keep, epi = self._head_loss_args(x, x_nl, y, dlogits, add, add_nl)
+        r = int(_lib.load().mmtta_conv_head_loss_eligible(C.byref(self.d_fwd), C.byref(dx), nlr,
+                                                          C.byref(epi) if epi is not None else None, C.byref(dy), C.byref(dg),
+                                                          1 if softmax else 0, 1 if per_item else 0))
+        if r < 0:
+            check(r, "conv_head_loss_eligible")
+        return r == 1
+
+    def head_loss_partials(self, x: torch.Tensor, y: torch.Tensor) -> int:
+        dx, dy = desc_cl(x), desc_cl(y)
+        n = int(_lib.load().mmtta_conv_head_loss_partials(C.byref(self.d_fwd), C.byref(dx), C.byref(dy)))
+        if n < 0:
+            check(-2, "conv_head_loss_partials")
+        return n
+
+    def forward_head_loss(self, x: torch.Tensor, x_nl: Optional[NL], bias: Optional[torch.Tensor], y: torch.Tensor,
+                          dlogits: torch.Tensor, partial: torch.Tensor, loss: torch.Tensor, add: Optional[torch.Tensor] = None,
+                          add_nl: Optional[NL] = None, softmax: bool = False, per_item: bool = True) -> None:
+        """``forward`` followed by ``entropy_loss_items(y, dlogits, ...)`` without the logits: ``y`` is described, not
+        written; ``dlogits`` bit for bit and ``loss`` [N] as the two calls give them (mmtta_conv_head_loss_run_sets).  Refused
+        (MmttaError) for a call ``head_loss_eligible`` says no to."""
+        if loss.numel() < (y.shape[0] if per_item else 1):
+            raise MmttaError("forward_head_loss: one loss slot per batch item")
+        if partial.dtype != torch.float64 or partial.numel() < self.head_loss_partials(x, y):
+            raise MmttaError("forward_head_loss: `partial` holds head_loss_partials(x, y) doubles")
+        dx, dy, dg, nls, nlr, keep, epi = self._head_loss_args(x, x_nl, y, dlogits, add, add_nl)
+        sets = self._sets(self.d_fwd)
+
+        def launch():
+            check(_lib.load().mmtta_conv_head_loss_run_sets(
+                C.byref(self.d_fwd), C.byref(dx), nlr, ptr(self.packed_fwd), ptr(bias), C.byref(epi) if epi is not None else None,
+                C.byref(dy), C.byref(dg), 1 if softmax else 0, 1 if per_item else 0, ptr(partial), ptr(loss),
+                C.byref(sets) if sets is not None else None, stream_ptr()), "conv_head_loss_run")
+
+        launch()
+        if PROFILER is not None:
+            e0 = PROFILER.begin()
+            for _ in range(PROFILER.reps):
+                launch()
+            # what the launch moves: x (and the fused add) in, the gradient out - no logits
+            nbytes = self.io_bytes(x, dlogits, self.packed_fwd) + (add.numel() * add.element_size() if add is not None else 0.0)
+            PROFILER.end("conv3_mfma4_loss_kernel<bf16>", PROFILER.reps, self.flops(x, y, self.d_fwd) * PROFILER.reps, e0,
+                         self._detail(CONV_FWD, x), nbytes * PROFILER.reps)
+
     def dgrad(self, dy: torch.Tensor, dx: torch.Tensor, accumulate: bool = False, add: Optional[torch.Tensor] = None) -> None:
         """dx (+)= conv^T(dy) [+ add]: ``add`` is a second gradient term of the same tensor (the identity branch of a
         ResidualUnit) summed in the epilogue instead of by a separate pass over dx."""

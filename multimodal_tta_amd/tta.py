@@ -23,6 +23,7 @@ import torch
 
 from . import ops
 from .config import as_cfg, get_config
+from .engine import HeadLossTail
 from .models.base import DEFAULT_NO_DECAY_KEYS, HipSegModel
 from .ops import MmttaError
 from .registry import register_plugin
@@ -245,14 +246,24 @@ class EntropyMinimizationTTA:
         (``records``) in its pool buffer, one slot per replica."""
         rt, ar = self.rt, self.rt.arena
         rt.pack_all(fused_current=True)
-        logits = self._forward(x, present)
-        dlogits = self._dlogits(logits)
         loss = rt.pool.flat("ent_loss", rt.group)
-        if rt.group > 1:
+        # the objective may ride in the epilogue of the network's last convolution, which then stores no logits (nothing
+        # else reads a step's logits): every volume its own objective, as below - or the batch of one
+        per_item = rt.group > 1
+        tail = None
+        if getattr(rt, "supports_head_tail", False) and not self.softmax and (per_item or int(x.shape[0]) == 1):
+            tail = HeadLossTail(self._dlogits, loss, per_item)
+        kw = {} if present is None else {"present": present}
+        logits = rt.forward_cl(x, **kw) if tail is None else rt.forward_cl(x, tail=tail, **kw)
+        if tail is not None and tail.done:
+            dlogits = tail.dlogits
+        elif rt.group > 1:
+            dlogits = self._dlogits(logits)
             # every volume of the group is its own objective (own mean, own gradient scale): loss [group]
             partial = rt.pool.flat("ent_partial", ops.entropy_partials_items(logits), dtype=torch.float64)
             ops.entropy_loss_items(logits, dlogits, partial, loss, softmax=self.softmax)
         else:
+            dlogits = self._dlogits(logits)
             partial = rt.pool.flat("ent_partial", ops.entropy_partials(logits), dtype=torch.float64)
             ops.entropy_loss(logits, dlogits, partial, loss, softmax=self.softmax)
         if ar.n_train > 0:
