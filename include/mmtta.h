@@ -196,6 +196,21 @@ int mmtta_abi_version(void);
  *   bit 1  reserved for the paired thin weight gradients of a stride-2 residual block (not built).
  * Returns the previous value. */
 #define MMTTA_OPT_HEAD_LOSS_PAIR 17
+/* Lean stage and epilogue of the thin full-resolution convolutions (a bit mask; default 3; 0: the launches as before, in the
+ * same process).  No route, plan, tile shape, statistics row or workspace size depends on it.
+ *   bit 0  the thin-K convolution on the matrix cores (csrc/conv_direct.hip: chan_mfma_lean_kernel, route 13) at stride 2 from
+ *          a bf16-stored gathered tensor into a bf16-stored y of exactly 32 or 64 channels, y and a fused add in 16-byte-aligned
+ *          rows, without accumulate.  The values of a wave go through a wave-private LDS tile and leave as 16-byte stores (8
+ *          channels of one voxel per lane) instead of one 4-byte store per channel pair from half the lanes behind a
+ *          cross-lane exchange through LDS; the fused add is read in the same 16-byte items; a tile inside the output drops
+ *          its spatial masks; the stage masks the stored voxel instead of unpacking it for any channel count.
+ *   bit 1  the gather-GEMM up-convolution (upconv8_lean_kernel) from a bf16-stored input without a norm-on-load transform:
+ *          each 16-byte item goes to LDS as loaded, under its in-bounds mask, and a tile inside the output skips the bounds
+ *          tests per fine voxel.
+ * Every stored value is the same round-to-nearest-even of the same fp32 value and the statistics rows are summed in the
+ * same order: outputs and rows equal bit for bit.  mmtta_conv_thin_lean tells which form a call takes.  A call with a
+ * LeakyReLU on x or on the fused add keeps the plain kernels.  Returns the previous value. */
+#define MMTTA_OPT_THIN_LEAN 18
 int mmtta_set_option(int key, int value);
 
 /* ------------------------------------------------------------------ layout (boundary) ---- */
@@ -301,6 +316,12 @@ int mmtta_conv_route(const mmtta_conv_desc* desc, const mmtta_tensor* x, const m
  * mmtta error code.  Host-only, the operands of mmtta_conv_route, the predicate the launchers themselves ask. */
 int mmtta_conv_stages_raw(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                           const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
+
+/* Which lean kernel of MMTTA_OPT_THIN_LEAN mmtta_conv_run would take for this call: 1 the thin-K convolution (bit 0), 2 the
+ * gather-GEMM up-convolution (bit 1), 0 neither, or a negative mmtta error code.  Host-only, the operands of mmtta_conv_route,
+ * the predicates the launchers themselves ask. */
+int mmtta_conv_thin_lean(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                         const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
 
 /* ---- per-volume parameter sets: N volumes (or N identical sub-networks) in ONE launch, each with ITS OWN parameters.
  * Episodic adaptation has no cross-volume state: every test volume adapts its own copy of the source weights (SURVEY.md

@@ -130,6 +130,7 @@ _SIGNATURES = {
                                       _P(Tensor), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
     "mmtta_conv_route": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_stages_raw": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
+    "mmtta_conv_thin_lean": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_head_loss_eligible": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), _P(Tensor),
                                                 C.c_int, C.c_int]),
     "mmtta_conv_head_loss_partials": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor)]),
@@ -301,6 +302,8 @@ def load() -> C.CDLL:
         lib.mmtta_set_option(16, int(os.environ["MMTTA_RAWSTAGE"]))
     if "MMTTA_HEADLOSS" in os.environ:                   # A/B aid: MMTTA_OPT_HEAD_LOSS_PAIR (same gradients bit for bit)
         lib.mmtta_set_option(17, int(os.environ["MMTTA_HEADLOSS"]))
+    if "MMTTA_THINLEAN" in os.environ:                   # A/B aid: MMTTA_OPT_THIN_LEAN (same results bit for bit)
+        lib.mmtta_set_option(18, int(os.environ["MMTTA_THINLEAN"]))
     _lib = lib
     return lib
 

@@ -42,6 +42,7 @@ extern int g_thin_mfma;             // api.hip: MMTTA_OPT_THIN_MFMA
 extern int g_epilogue_vec;          // api.hip: MMTTA_OPT_EPILOGUE_VEC16
 extern int g_raw_staging;           // api.hip: MMTTA_OPT_RAW_STAGING (bit 0: implicit GEMM, bit 1: transposed-read weight gradient)
 extern int g_head_loss_pair;        // api.hip: MMTTA_OPT_HEAD_LOSS_PAIR (bit 0: entropy objective in the head convolution, bit 1: paired thin weight gradients)
+extern int g_thin_lean;            // api.hip: MMTTA_OPT_THIN_LEAN (bit 0: thin-K convolution, bit 1: gather-GEMM up-convolution)
 extern int g_tune[4];              // api.hip: launch-geometry knobs (MMTTA_OPT_SPLITK_BELOW ... MMTTA_OPT_WGRAD_THIN_SLABS)
 
 // ---- activation of a norm-on-load (mmtta_norm_on_load.relu: MMTTA_ACT_*).
@@ -593,12 +594,18 @@ int pointwise_small_run(const mmtta_tensor* x, const void* packed, int Kp, int N
                         int accumulate, const PSets& sets, hipStream_t stream);
 bool chan_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y);
 int chan_tiles_per_n(const mmtta_tensor* y);
+// whether chan_conv_run takes the lean kernel for this call (MMTTA_OPT_THIN_LEAN bit 0)
+bool chan_lean_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                          const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate);
 int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed, int Kp,
                   int Np, const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
                   const PSets& sets, hipStream_t stream);
 int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
                     const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
                     const PSets& sets, hipStream_t stream);
+// whether direct_conv_run takes the lean gather-GEMM up-convolution for this call (MMTTA_OPT_THIN_LEAN bit 1)
+bool direct_upconv8_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                         const mmtta_conv_epilogue* epi, const mmtta_tensor* y);
 // the head convolution with the entropy objective in its epilogue (conv_direct.hip; the plain translation unit only)
 bool direct_head_loss_eligible(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz, int softmax,

@@ -802,191 +802,22 @@ __global__ __launch_bounds__(256) void direct_chan_kernel(CArgs a) {
 // kernel and the thin weight gradient round it to bf16 while staging anyway - the same values from half the bytes)
 template <int S, int KI, int NB, bool HAS_T, bool XBF = false>
 __global__ __launch_bounds__(256) void chan_mfma_kernel(CArgs a) {
-  constexpr int TZ = 4, TY = 4, TX = 8;
-  constexpr int BZ = (TZ - 1) * S + 3, BY = (TY - 1) * S + 3, BX = (TX - 1) * S + 3, BOX = BZ * BY * BX;
-  __shared__ uint2 box[BOX];                       // 4 bf16 channels per voxel
-  __shared__ float red[2][4][32 * NB];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, r = lane & 31;
-  int t = blockIdx.x;
-  const int tile_in_n = t % a.tiles_per_n;
-  const int txi = t % a.tx; t /= a.tx;
-  const int tyi = t % a.ty; t /= a.ty;
-  const int tzi = t % a.tz;
-  const int n = t / a.tz;
-  a.w = pset_packed(a.ps, a.w, n); a.bias = pset_bias(a.ps, a.bias, n);      // this batch item's parameter set
-  const int oz0 = tzi * TZ, oy0 = tyi * TY, ox0 = txi * TX;
-  const int iz0 = oz0 * S - 1, iy0 = oy0 * S - 1, ix0 = ox0 * S - 1;
-  const int N = a.out.c;
-  {  // ---- stage the halo box: all loads (clamped) first, then transform / zero-fill / round to bf16.
-     // A thread keeps one box column bx and walks box rows (bz, by): the x clamp and mask are computed once, a row costs one
-     // small decode, offsets are 32-bit elements from the batch item (host-checked), validity travels as a bit mask.
-    constexpr int RPP = 256 / BX, NROW = BZ * BY, NQ = (NROW + RPP - 1) / RPP;
-    float sc[4] = {1.f, 1.f, 1.f, 1.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
-    if (HAS_T) nl_coeff_vec<4>(a.tin, n, KI, 0, sc, sh);
-    const float* inb = XBF ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(a.in.p) + (long long)n * a.in.sn)
-                           : a.in.p + (long long)n * a.in.sn;
-    const int bx = tid % BX, r0 = tid / BX;
-    const int ix = ix0 + bx;
-    const bool xok = (unsigned)ix < (unsigned)a.in.w && r0 < RPP;
-    const unsigned xoff = (unsigned)min(max(ix, 0), a.in.w - 1) * (unsigned)a.in.sw;
-    const unsigned sd = (unsigned)a.in.sd, shh = (unsigned)a.in.sh;
-    float4 raw[NQ];
-    uint2 rawh[NQ];
-    unsigned okm = 0;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int row = min(r0 + q * RPP, NROW - 1);
-      const int by = row % BY, bz = row / BY;
-      const int iz = iz0 + bz, iy = iy0 + by;
-      const bool ok = xok && (unsigned)iz < (unsigned)a.in.d && (unsigned)iy < (unsigned)a.in.h;
-      okm |= (ok ? 1u : 0u) << q;
-      const unsigned off = (unsigned)min(max(iz, 0), a.in.d - 1) * sd + (unsigned)min(max(iy, 0), a.in.h - 1) * shh + xoff;
-      if constexpr (XBF) rawh[q] = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(inb) + off);
-      else raw[q] = *reinterpret_cast<const float4*>(inb + off);
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int row = r0 + q * RPP;
-      if (r0 < RPP && row < NROW) {
-        const bool ok = (okm >> q) & 1u;
-        if constexpr (XBF && !HAS_T && KI == 4) {           // already what the image holds: mask and store
-          const unsigned m = ok ? 0xffffffffu : 0u;
-          box[row * BX + bx] = make_uint2(rawh[q].x & m, rawh[q].y & m);
-          continue;
-        }
-        if constexpr (XBF)
-          raw[q] = make_float4(bf16_bits_to_f32(rawh[q].x & 0xffffu), __uint_as_float(rawh[q].x & 0xffff0000u),
-                               bf16_bits_to_f32(rawh[q].y & 0xffffu), __uint_as_float(rawh[q].y & 0xffff0000u));
-        float r4[4] = {raw[q].x, raw[q].y, raw[q].z, raw[q].w};
-        if (KI == 1) r4[0] = a.koff == 0 ? raw[q].x : a.koff == 1 ? raw[q].y : a.koff == 2 ? raw[q].z : raw[q].w;
-        float v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          v[k] = (ok && k < KI) ? (HAS_T ? nl_apply(r4[k], sc[k], sh[k], a.tin.relu) : r4[k]) : 0.f;
-        uint2 pk;
-        pk.x = __builtin_bit_cast(unsigned int, __builtin_convertvector((float2_t){v[0], v[1]}, bf16x2_t));
-        pk.y = __builtin_bit_cast(unsigned int, __builtin_convertvector((float2_t){v[2], v[3]}, bf16x2_t));
-        box[row * BX + bx] = pk;
-      }
-    }
-  }
-  // ---- B fragments: k = s*16 + h*8 + e  <->  tap = s*4 + h*2 + (e >> 2), channel = e & 3; column = nb*32 + r: the
-  // fragment-ordered bf16 image behind the fp32 tap image of this batch item's packed weights (chan_frag_bytes, written by
-  // the pack kernels): one 16-byte load per fragment and lane, issued before the box is staged
-  uint4 wfrag[7][NB];
-  {
-    const uint4* fr = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.w) + (size_t)27 * a.Kp * a.Np * 4) + lane;
-#pragma unroll
-    for (int s2 = 0; s2 < 7; ++s2)
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) wfrag[s2][nb] = fr[(s2 * NB + nb) * 64];
-  }
-  float bias[NB], asc[NB], ash[NB];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    const int col = min(nb * 32 + r, N - 1);
-    bias[nb] = a.bias ? a.bias[col] : 0.f;
-    asc[nb] = 1.f; ash[nb] = 0.f;
-    if (a.add) nl_coeff(a.tadd, n, N, col, asc[nb], ash[nb]);
-  }
-  __syncthreads();
-  // ---- A fragments: MFMA row m = r  <->  voxel (zl = wave, yl = m / 8, xl = m % 8)
-  ufloat16 acc[NB];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
-  {
-    const int xl = r % TX, yl = r / TX;
-    const uint2* bp = box + ((wave * S) * BY + yl * S) * BX + xl * S;
-    uint2 av[7][2];
-#pragma unroll
-    for (int s2 = 0; s2 < 7; ++s2)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int tap = min(s2 * 4 + h * 2 + j, 26);           // tap 27: any valid address, its weights are zero
-        const int dz = tap / 9, dy = (tap / 3) % 3, dx = tap % 3;
-        av[s2][j] = bp[(dz * BY + dy) * BX + dx];
-      }
-#pragma unroll
-    for (int s2 = 0; s2 < 7; ++s2) {
-      const uint4 a4 = make_uint4(av[s2][0].x, av[s2][0].y, av[s2][1].x, av[s2][1].y);
-      const ubf16x8 af = __builtin_bit_cast(ubf16x8, a4);
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, __builtin_bit_cast(ubf16x8, wfrag[s2][nb]), acc[nb], 0, 0, 0);
-    }
-  }
-  // ---- epilogue: accumulator i of lane (h, r) = voxel m = (i & 3) + 8 * (i >> 2) + 4 * h, channel nb*32 + r
-  float ssum[NB], ssq[NB];
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb) { ssum[nb] = 0.f; ssq[nb] = 0.f; }
-  // voxel m of accumulator i: row oy0 + (i >> 2), column ox0 + (i & 3) + 4 * h; the z-slice (wave) is uniform.  Offsets are
-  // 32-bit elements from the slice (host-checked): four row terms plus four column terms, one add per store.
-  const int oz = oz0 + wave;
-  const bool zok = oz < a.out.d;
-  unsigned oyo[4], oxo[4], ayo[4], axo[4];
-  unsigned okrow = 0, okcol = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int oy = oy0 + j, ox = ox0 + j + 4 * h;
-    okrow |= (zok && oy < a.out.h ? 1u : 0u) << j;
-    okcol |= (ox < a.out.w ? 1u : 0u) << j;
-    oyo[j] = (unsigned)oy * (unsigned)a.out.sh; oxo[j] = (unsigned)ox * (unsigned)a.out.sw;
-    ayo[j] = (unsigned)oy * (unsigned)a.ash; axo[j] = (unsigned)ox * (unsigned)a.asw;
-  }
-  const long long obase = (long long)n * a.out.sn + (long long)oz * a.out.sd;
-  const long long abase = (long long)n * a.asn + (long long)oz * a.asd;
-  MMTTA_BF_DISPATCH(a.out.bf, OBF, {
-    float* const outp = OBF ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(a.out.p) + obase) : a.out.p + obase;
-    const float* const addp = a.add == nullptr ? nullptr
-                              : (OBF ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(a.add) + abase) : a.add + abase);
-_Pragma("unroll")
-    for (int i = 0; i < 16; ++i) {
-      const bool vok = ((okrow >> (i >> 2)) & (okcol >> (i & 3)) & 1u) != 0;
-      const unsigned ooff = oyo[i >> 2] + oxo[i & 3];
-      const unsigned aoff = ayo[i >> 2] + axo[i & 3];
-_Pragma("unroll")
-      for (int nb = 0; nb < NB; ++nb) {
-        const int col = nb * 32 + r;
-        const bool live = vok && col < N;
-        float val = acc[nb][i] + bias[nb];
-        // fused add / accumulate operands share the output's storage type (host-checked)
-        if (a.add) val += nl_apply(live ? ld1_t<OBF>(addp, aoff + col) : 0.f, asc[nb], ash[nb], a.tadd.relu);
-        if (a.accumulate && live) val += ld1_t<OBF>(outp, ooff + col);
-        if constexpr (OBF) {
-          // bf16 rows: neighbouring channel lanes pair up, the even one stores both as one dword (a 2-byte store per
-          // lane is a partial-dword write: ~12x the time per byte of a full store)
-          const float other = __shfl_xor(val, 1, 64);
-          if (live && !(r & 1)) {
-            if (col + 1 < N) reinterpret_cast<unsigned int*>(reinterpret_cast<unsigned short*>(outp) + ooff + col)[0] = f32x2_to_bf16x2(val, other);
-            else st1_t<true>(outp, ooff + col, val);
-          }
-        } else {
-          if (live) outp[ooff + col] = val;
-        }
-        if (live) { ssum[nb] += val; ssq[nb] += val * val; }
-      }
-    }
-  });
-  if (a.stats != nullptr) {
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      const float s0 = ssum[nb] + __shfl_xor(ssum[nb], 32, 64), s1 = ssq[nb] + __shfl_xor(ssq[nb], 32, 64);
-      if (h == 0) { red[0][wave][nb * 32 + r] = s0; red[1][wave][nb * 32 + r] = s1; }
-    }
-    __syncthreads();
-    if (tid < 32 * NB && tid < N) {
-      const float s0 = (red[0][0][tid] + red[0][1][tid]) + (red[0][2][tid] + red[0][3][tid]);
-      const float s1 = (red[1][0][tid] + red[1][1][tid]) + (red[1][2][tid] + red[1][3][tid]);
-      const long long row = (long long)n * a.tiles_per_n + tile_in_n;
-      a.stats[(row * 2 + 0) * N + tid] = s0;
-      a.stats[(row * 2 + 1) * N + tid] = s1;
-    }
-  }
+  constexpr bool LEAN = false;
+#include "chan_mfma_body.h"
 }
+
+#ifndef MMTTA_ACT_LEAKY_TU
+// The lean form (MMTTA_OPT_THIN_LEAN bit 0; host: chan_lean_applicable; chan_mfma_body.h says what it does): the stride-2
+// layers over a bf16-stored gathered tensor with a bf16-stored result - the first block's two convolutions and the input
+// gradient of the last up-convolution.  The same body text with the lean stage and epilogue switched in; launched from the
+// plain translation unit only.
+template <int KI, int NB, bool HAS_T>
+__global__ __launch_bounds__(256) void chan_mfma_lean_kernel(CArgs a) {
+  constexpr int S = 2;
+  constexpr bool XBF = true, LEAN = true;
+#include "chan_mfma_body.h"
+}
+#endif
 
 bool chan_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y) {
   if (!(d->op == MMTTA_CONV_FWD || d->op == MMTTA_CONVT_DGRAD) || d->ksize != 3) return false;
@@ -1041,6 +872,44 @@ static void launch_chan_mfma(const CArgs& a, int K, int N, int blocks, hipStream
   }
 }
 
+// The lean thin-K kernel (MMTTA_OPT_THIN_LEAN bit 0; chan_mfma_lean_kernel) takes a call of route 13 that runs on the matrix
+// cores at stride 2 from a bf16-stored gathered tensor into a bf16-stored y of exactly 32 or 64 channels whose voxel rows -
+// and those of a fused add - are 16-byte items, without accumulate.  The 32-bit offsets are those chan_applicable and
+// chan_conv_run check.  Instantiated in the plain translation unit only: a call with a LeakyReLU on x or on the add keeps
+// chan_mfma_kernel.  The one function behind mmtta_conv_thin_lean and the launcher.
+#ifdef MMTTA_ACT_LEAKY_TU
+constexpr bool LEAN_KERNELS = false;
+#else
+constexpr bool LEAN_KERNELS = true;
+#endif
+static bool rows16(const mmtta_tensor* t) { return is_bf16(t) && t->sc == 1 && quad_aligned(t, 16, 8); }
+bool chan_lean_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                          const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate) {
+  const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
+  const int S = d->op == MMTTA_CONV_FWD ? d->stride : 2;
+  return LEAN_KERNELS && (g_thin_lean & 1) && d->dtype == MMTTA_BF16 && chan_applicable(d, x, y) && S == 2 && is_bf16(x) &&
+         (y->c == 32 || y->c == 64) && rows16(y) && (add == nullptr || (rows16(add) && add->c == y->c)) && accumulate == 0 &&
+         !nl_leaky(x_norm) && !(add && nl_leaky(&epi->add_norm));
+}
+
+#ifndef MMTTA_ACT_LEAKY_TU
+template <bool HAS_T>
+static void launch_chan_lean(const CArgs& a, int K, int N, int blocks, hipStream_t s) {
+#define MMTTA_LEAN_CASE(KI)                                                                                                  \
+  if (N > 32) hipLaunchKernelGGL((chan_mfma_lean_kernel<KI, 2, HAS_T>), dim3(blocks), dim3(256), 0, s, a);                   \
+  else hipLaunchKernelGGL((chan_mfma_lean_kernel<KI, 1, HAS_T>), dim3(blocks), dim3(256), 0, s, a);                          \
+  break
+  switch (K) {
+    // (K = 1 reaches this path with N = 64 only: chan_applicable sends a bf16-stored one-channel x into 32 elsewhere)
+    case 1: hipLaunchKernelGGL((chan_mfma_lean_kernel<1, 2, HAS_T>), dim3(blocks), dim3(256), 0, s, a); break;
+    case 2: MMTTA_LEAN_CASE(2);
+    case 3: MMTTA_LEAN_CASE(3);
+    default: MMTTA_LEAN_CASE(4);
+  }
+#undef MMTTA_LEAN_CASE
+}
+#endif
+
 int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed, int Kp,
                   int Np, const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
                   const PSets& sets, hipStream_t stream) {
@@ -1072,6 +941,12 @@ int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
   const int S = d->op == MMTTA_CONV_FWD ? d->stride : 2;       // CONVT_DGRAD: stride-2 gather
   // one input channel (the single-modality stems of the deep-fusion net) is 27 FMAs per output: the VALU kernel wins there
   if (mfma_path) {
+#ifndef MMTTA_ACT_LEAKY_TU
+    if (chan_lean_applicable(d, x, x_norm, epi, y, accumulate)) {
+      MMTTA_BF_DISPATCH(has_t, HT, { launch_chan_lean<HT>(a, x->c, y->c, blocks, stream); });
+      return launch_status("thin-K conv (bf16 MFMA, lean)");
+    }
+#endif
     MMTTA_BF_DISPATCH(has_t, HT, { if (S == 1) launch_chan_mfma<1, HT>(a, x->c, y->c, blocks, stream); else launch_chan_mfma<2, HT>(a, x->c, y->c, blocks, stream); });
     return launch_status("thin-K conv (bf16 MFMA)");
   }
@@ -1481,152 +1356,24 @@ __device__ __forceinline__ int upconv8_index(int K, int d, int k, int col) {
 
 template <int K, int NO, bool HAS_T, bool INBF>
 __global__ __launch_bounds__(256, 2) void upconv8_kernel(DArgs a, int tiles_per_n, int tz, int ty, int tx) {
-  constexpr int TZ = 4, TY = 4, TX = 8, BZ = TZ + 1, BY = TY + 1, BX = TX + 1;
-  constexpr int VS = K + 8;                           // halfwords per staged voxel: 16 lanes of a ds_read_b128 -> 16 distinct slots
-  constexpr int KS = K / 16, KC8 = K / 8;
-  constexpr int BOXV = BZ * BY * BX;
-  constexpr int NIT = (BOXV * KC8 + 255) / 256;       // 8-channel items per thread
-  constexpr int SLAB_Z = 8 * 72 + 16, SLAB = 2 * SLAB_Z;   // floats of one wave's output slab (padded: conflict-free writes)
-  constexpr int BOX_HW = (BOXV * VS + 7) / 8 * 8;
-  extern __shared__ float lds[];
-  unsigned short* lh = reinterpret_cast<unsigned short*>(lds);                 // box image, later the four output slabs
-  uint4* wl = reinterpret_cast<uint4*>(lh + (BOX_HW > SLAB * 4 * 2 ? BOX_HW : SLAB * 4 * 2));   // W': 8 * KS * 64 fragments
-  float* red = reinterpret_cast<float*>(wl + 8 * KS * 64);                     // 32 floats
-  const int n = blockIdx.y;
-  a.w = pset_packed(a.ps, a.w, n); a.bias = pset_bias(a.ps, a.bias, n);        // this batch item's parameter set
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int h = lane >> 5, r = lane & 31;
-  {  // W' of this batch item's set: behind the fp32 tap image [27][K][4]
-    const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.w) + (size_t)27 * K * 16);
-    for (int i = tid; i < 8 * KS * 64; i += 256) wl[i] = src[i];
-  }
-  // a thread's items i = tid + 256 j all carry the same channel octet (256 % KC8 == 0): one coefficient set per thread
-  static_assert(256 % KC8 == 0, "items of a thread must share their channel octet");
-  float sc[8], sh[8];
-  if (HAS_T) nl_coeff_vec<8>(a.tin, n, K, (tid % KC8) * 8, sc, sh);
-  const float relu_lo = act_lo(HAS_T ? a.tin.relu : MMTTA_ACT_ID);
-  const float* inb = item_base<INBF>(a.in.p, n, a.in.sn);
-  const unsigned isd = (unsigned)a.in.sd, ish = (unsigned)a.in.sh, isw = (unsigned)a.in.sw;
-  long long tfirst, tlast;
-  unit_range(tiles_per_n, xcd_contiguous_id(blockIdx.x, gridDim.x), gridDim.x, tfirst, tlast);
-  // staging roles: a thread's box items are the same for every tile (decoded once); the loads of tile t + 1 are issued
-  // right after tile t's image is complete and land under its MFMAs and epilogue (each tile used to start with a full
-  // memory latency, two workgroups per CU to hide it)
-  int pos[NIT];                                       // box voxel of item j: bz << 16 | by << 8 | bx
-  const int cv = tid % KC8;
-#pragma unroll
-  for (int j = 0; j < NIT; ++j) {
-    const int bv = min(tid + 256 * j, BOXV * KC8 - 1) / KC8;
-    const int bz = bv / (BY * BX), brem = bv - bz * (BY * BX), by = brem / BX, bx = brem - by * BX;
-    pos[j] = (bz << 16) | (by << 8) | bx;
-  }
-  Oct8<INBF> raw[NIT];
-  unsigned okm = 0u;
-  auto issue = [&](long long tile) {
-    int t = (int)tile;
-    const int txi = t % tx; t /= tx;
-    const int tyi = t % ty;
-    const int tzi = t / ty;
-    const int gz0 = tzi * TZ, gy0 = tyi * TY, gx0 = txi * TX;
-    okm = 0u;
-#pragma unroll
-    for (int j = 0; j < NIT; ++j) {
-      const int iz = gz0 + (pos[j] >> 16), iy = gy0 + ((pos[j] >> 8) & 255), ix = gx0 + (pos[j] & 255);
-      okm |= ((iz < a.in.d && iy < a.in.h && ix < a.in.w) ? 1u : 0u) << j;
-      const unsigned off = (unsigned)min(iz, a.in.d - 1) * isd + (unsigned)min(iy, a.in.h - 1) * ish + (unsigned)min(ix, a.in.w - 1) * isw + cv * 8;
-      raw[j] = oct8_ld<INBF>(inb, off, off + 4);
-    }
-  };
-  if (tfirst < tlast) issue(tfirst);
-  for (long long tile = tfirst; tile < tlast; ++tile) {
-    int t = (int)tile;
-    const int txi = t % tx; t /= tx;
-    const int tyi = t % ty;
-    const int tzi = t / ty;
-    const int gz0 = tzi * TZ, gy0 = tyi * TY, gx0 = txi * TX;
-    // ---- the halo box of this tile (requested one tile ago): transform / mask / pack
-#pragma unroll
-    for (int j = 0; j < NIT; ++j) {
-      float v[8];
-      oct8_f8(raw[j], v);
-      if (HAS_T) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = act_max(fmaf(v[q], sc[q], sh[q]), relu_lo);
-      }
-      const unsigned m = ((okm >> j) & 1u) ? 0xffffffffu : 0u;
-      uint4 pk;
-      pk.x = f32x2_to_bf16x2(v[0], v[1]) & m; pk.y = f32x2_to_bf16x2(v[2], v[3]) & m;
-      pk.z = f32x2_to_bf16x2(v[4], v[5]) & m; pk.w = f32x2_to_bf16x2(v[6], v[7]) & m;
-      if (tid + 256 * j < BOXV * KC8)
-        *reinterpret_cast<uint4*>(lh + ((((pos[j] >> 16) * BY + ((pos[j] >> 8) & 255)) * BX + (pos[j] & 255)) * VS + cv * 8)) = pk;
-    }
-    __syncthreads();
-    if (tile + 1 < tlast) issue(tile + 1);
-    // ---- 8 offsets x KS k-steps: one 32 x 32 block per wave (rows = the 4 x 8 coarse voxels of z-slice `wave`)
-    ufloat16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    {
-      const unsigned short* arow = lh + ((wave * BY + (r >> 3)) * BX + (r & 7)) * VS + 8 * h;
-      const uint4* brow = wl + lane;
-#pragma unroll
-      for (int d = 0; d < 8; ++d) {
-        const unsigned short* ad = arow + ((((d >> 2) & 1) * BY + ((d >> 1) & 1)) * BX + (d & 1)) * VS;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          const uint4 af = *reinterpret_cast<const uint4*>(ad + ks * 16);
-          const uint4 bf = brow[(d * KS + ks) * 64];
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ubf16x8, af), __builtin_bit_cast(ubf16x8, bf), acc, 0, 0, 0);
-        }
-      }
-    }
-    __syncthreads();                                   // the box image is dead: its space becomes the output slabs
-    // ---- pixel shuffle through LDS.  Accumulator i of lane (h, r): coarse (y, x) = (i >> 2, (i & 3) + 4 h), column r =
-    // (pz, py, px, co).  Slab address = pz * SLAB_Z + (2 y + py) * 72 + (2 x + px) * 4 + co: for one i the 64 lanes fall on
-    // banks co + 4 px + 8 py + 16 pz + 32 h - all distinct.
-    float* slab = lds + wave * SLAB;
-    {
-      const int pz = r >> 4, py = (r >> 3) & 1, px = (r >> 2) & 1, co = r & 3;
-      float* sp = slab + pz * SLAB_Z + py * 72 + (px + 8 * h) * 4 + co;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sp[(i >> 2) * 144 + (i & 3) * 8] = acc[i];
-    }
-    __syncthreads();
-    float ssum[NO], ssq[NO];
-#pragma unroll
-    for (int c = 0; c < NO; ++c) { ssum[c] = 0.f; ssq[c] = 0.f; }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int v = lane + 64 * q;                     // fine voxel of the slab: (fz, fy, fx) = (v >> 7, (v >> 4) & 7, v & 15)
-      const int fz = v >> 7, fy = (v >> 4) & 7, fx = v & 15;
-      const float4 o4 = *reinterpret_cast<const float4*>(slab + fz * SLAB_Z + fy * 72 + fx * 4);
-      const int oz = 2 * (gz0 + wave) + fz, oy = 2 * gy0 + fy, ox = 2 * gx0 + fx;
-      if (oz < a.out.d && oy < a.out.h && ox < a.out.w) {
-        const float vals[4] = {o4.x, o4.y, o4.z, o4.w};
-        direct_epilogue<NO>(a, n, oz, oy, ox, vals, ssum, ssq);
-      }
-    }
-    // ---- statistics row of this tile (the following norm): lanes -> waves -> one row
-    if (a.stats != nullptr) {
-#pragma unroll
-      for (int c = 0; c < NO; ++c) {
-        const float s = wave_sum(ssum[c]), q2 = wave_sum(ssq[c]);
-        if (lane == 0) { red[(0 * 4 + wave) * 4 + c] = s; red[(1 * 4 + wave) * 4 + c] = q2; }
-      }
-    }
-    __syncthreads();                                   // slabs read, partial sums visible: the next tile may stage
-    if (a.stats != nullptr && tid < NO) {
-      const float s = red[0 * 4 + tid] + red[1 * 4 + tid] + red[2 * 4 + tid] + red[3 * 4 + tid];
-      const float q2 = red[16 + 0 * 4 + tid] + red[16 + 1 * 4 + tid] + red[16 + 2 * 4 + tid] + red[16 + 3 * 4 + tid];
-      const long long rrow = (long long)n * tiles_per_n + tile;
-      a.stats[(rrow * 2 + 0) * a.N + tid] = s;
-      a.stats[(rrow * 2 + 1) * a.N + tid] = q2;
-    }
-  }
+  constexpr bool LEAN = false;
+#include "upconv8_body.h"
 }
 
-template <int K, bool HAS_T, bool INBF>
+// The lean form (MMTTA_OPT_THIN_LEAN bit 1; host: direct_upconv8_lean; upconv8_body.h says what it does): a bf16-stored input
+// without a transform, which is what the last up-convolution of the U-Net reads.
+template <int K, int NO>
+__global__ __launch_bounds__(256, 2) void upconv8_lean_kernel(DArgs a, int tiles_per_n, int tz, int ty, int tx) {
+  constexpr bool HAS_T = false, INBF = true, LEAN = true;
+#include "upconv8_body.h"
+}
+template <int K, int NO, bool HAS_T, bool INBF, bool LEANK>
+static auto upconv8_fn() {
+  if constexpr (LEANK) return &upconv8_lean_kernel<K, NO>;
+  else return &upconv8_kernel<K, NO, HAS_T, INBF>;
+}
+
+template <int K, bool HAS_T, bool INBF, bool LEANK = false>
 static void launch_upconv8(const DArgs& a, int n, int tz, int ty, int tx, hipStream_t stream) {
   constexpr int VS = K + 8, BOX_HW = (225 * VS + 7) / 8 * 8, SLAB = 2 * (8 * 72 + 16);
   constexpr size_t lds = (size_t)(BOX_HW > SLAB * 8 ? BOX_HW : SLAB * 8) * 2 + (size_t)8 * (K / 16) * 64 * 16 + 32 * sizeof(float);
@@ -1635,17 +1382,17 @@ static void launch_upconv8(const DArgs& a, int n, int tz, int ty, int tx, hipStr
   const dim3 grid(tiles_per_n < 128 ? tiles_per_n : 128, n), block(256);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)upconv8_kernel<K, 1, HAS_T, INBF>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)upconv8_kernel<K, 2, HAS_T, INBF>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)upconv8_kernel<K, 3, HAS_T, INBF>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)upconv8_kernel<K, 4, HAS_T, INBF>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    (void)hipFuncSetAttribute((const void*)upconv8_fn<K, 1, HAS_T, INBF, LEANK>(), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    (void)hipFuncSetAttribute((const void*)upconv8_fn<K, 2, HAS_T, INBF, LEANK>(), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    (void)hipFuncSetAttribute((const void*)upconv8_fn<K, 3, HAS_T, INBF, LEANK>(), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    (void)hipFuncSetAttribute((const void*)upconv8_fn<K, 4, HAS_T, INBF, LEANK>(), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     attr_set = true;
   }
   switch (a.N) {
-    case 1: hipLaunchKernelGGL((upconv8_kernel<K, 1, HAS_T, INBF>), grid, block, lds, stream, a, tiles_per_n, tz, ty, tx); break;
-    case 2: hipLaunchKernelGGL((upconv8_kernel<K, 2, HAS_T, INBF>), grid, block, lds, stream, a, tiles_per_n, tz, ty, tx); break;
-    case 3: hipLaunchKernelGGL((upconv8_kernel<K, 3, HAS_T, INBF>), grid, block, lds, stream, a, tiles_per_n, tz, ty, tx); break;
-    default: hipLaunchKernelGGL((upconv8_kernel<K, 4, HAS_T, INBF>), grid, block, lds, stream, a, tiles_per_n, tz, ty, tx); break;
+    case 1: hipLaunchKernelGGL((upconv8_fn<K, 1, HAS_T, INBF, LEANK>()), grid, block, lds, stream, a, tiles_per_n, tz, ty, tx); break;
+    case 2: hipLaunchKernelGGL((upconv8_fn<K, 2, HAS_T, INBF, LEANK>()), grid, block, lds, stream, a, tiles_per_n, tz, ty, tx); break;
+    case 3: hipLaunchKernelGGL((upconv8_fn<K, 3, HAS_T, INBF, LEANK>()), grid, block, lds, stream, a, tiles_per_n, tz, ty, tx); break;
+    default: hipLaunchKernelGGL((upconv8_fn<K, 4, HAS_T, INBF, LEANK>()), grid, block, lds, stream, a, tiles_per_n, tz, ty, tx); break;
   }
 }
 
@@ -1684,6 +1431,17 @@ static void launch_row(const DArgs& a, int n, hipStream_t stream) {
   }
 }
 
+// The lean gather-GEMM up-convolution (MMTTA_OPT_THIN_LEAN bit 1; upconv8_lean_kernel) takes a call of upconv8_kernel whose
+// input is bf16-stored and has no norm-on-load transform (neither mean nor scale: what picks HAS_T = false below).  The plain
+// translation unit only: a call with a LeakyReLU on x or on the add keeps upconv8_kernel.  The one function behind
+// mmtta_conv_thin_lean and the launcher.
+bool direct_upconv8_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                         const mmtta_conv_epilogue* epi, const mmtta_tensor* y) {
+  const bool has_t = x_norm != nullptr && (x_norm->mean != nullptr || x_norm->scale != nullptr);
+  return LEAN_KERNELS && (g_thin_lean & 2) && direct_applicable(d) && direct_variant(d, x) == 5 && is_bf16(x) && !has_t &&
+         !nl_leaky(x_norm) && !(epi && epi->add && nl_leaky(&epi->add_norm));
+}
+
 int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
                     const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
                     const PSets& sets, hipStream_t stream) {
@@ -1720,6 +1478,13 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   MMTTA_CHECK(thin_bf || (is_f32(y) && !(epi && epi->add && is_bf16(epi->add))), MMTTA_ERR_UNSUPPORTED, "direct conv: outputs are fp32-stored");
   if (variant == 5) {
     const int tz = (x->d + 3) / 4, ty = (x->h + 3) / 4, tx = (x->w + 7) / 8;
+#ifndef MMTTA_ACT_LEAKY_TU
+    if (direct_upconv8_lean(d, x, x_norm, epi, y)) {
+      if (a.K == 64) launch_upconv8<64, false, true, true>(a, y->n, tz, ty, tx, stream);
+      else launch_upconv8<32, false, true, true>(a, y->n, tz, ty, tx, stream);
+      return launch_status("up-convolution (2x2x2 gather GEMM, lean)");
+    }
+#endif
     MMTTA_BF_DISPATCH(has_t, HT, { MMTTA_BF_DISPATCH(is_bf16(x), XBF, {
       if (a.K == 64) launch_upconv8<64, HT, XBF>(a, y->n, tz, ty, tx, stream);
       else launch_upconv8<32, HT, XBF>(a, y->n, tz, ty, tx, stream);

@@ -1551,6 +1551,16 @@ extern "C" int mmtta_conv_stages_raw(const mmtta_conv_desc* d, const mmtta_tenso
   return (raw_staging(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
 }
 
+extern "C" int mmtta_conv_thin_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                    const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
+  Geometry g;
+  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
+  if (st) return st < 0 ? st : -st;
+  if (g.route == C_THIN) return chan_lean_applicable(d, x, x_norm, epi, y, accumulate) ? 1 : 0;
+  if (g.route == C_DIRECT) return direct_upconv8_lean(d, x, x_norm, epi, y) ? 2 : 0;
+  return 0;
+}
+
 // ---- the head convolution with the entropy objective in its epilogue (MMTTA_OPT_HEAD_LOSS_PAIR bit 0)
 static int head_loss_plan(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                           const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz, int softmax, int per_item,
