@@ -936,6 +936,48 @@ int mmtta_lame_refine(const mmtta_tensor* logits0, const mmtta_tensor* x, uint32
                       float weight, float sigma, int iterations, const mmtta_tensor* work, const mmtta_tensor* out,
                       int64_t* flipped, void* stream);
 
+/* ------------------------------------------------------------------ CRF-regularised entropy */
+/* The entropy objective plus a pairwise grid-CRF (Potts) regulariser, loss and gradient in one pass - csrc/crf.hip (Tang et
+ * al., ECCV 2018, "On Regularized Losses for Weakly-supervised CNN Segmentation"; the contour term of Hu et al., MICCAI
+ * 2021, "Fully Test-time Adaptation for Image Segmentation").  Where mmtta_lame_refine corrects the outputs, this term sits
+ * inside the step, so the weights learn the spatial prior.  Every batch item is its own objective (elements as everywhere:
+ * sigmoid head (voxel, region) pairs, softmax head voxels; E = D H W R or D H W of ONE item, n = `connectivity`):
+ *     L = H + weight * P                              H: the mean entropy of mmtta_entropy_loss_items
+ *     P = 1 / (2 n E) * sum_i sum_{j in N(i)} a_ij phi(p_i, p_j)         (ordered pairs, hence the 1 / 2)
+ *     phi   form 0, Potts:      sigmoid head  sum_r [p_ir (1 - p_jr) + (1 - p_ir) p_jr];  softmax head  1 - sum_k p_ik p_jk
+ *           form 1, quadratic:  sum_r (p_ir - p_jr)^2  on both heads
+ *     p = sigmoid(l) per region (softmax == 0) or softmax(l) per voxel (softmax != 0)
+ *   N(i): the 6 / 18 / 26 spatial neighbours of voxel i inside the same batch item; a neighbour outside the volume
+ *   contributes nothing.  a_ij = exp(-sum_{c present} (x_ic - x_jc)^2 / (2 sigma^2)) on the staged input `x` [N,D,H,W,C]
+ *   (fp32 or bf16 as staged, converted to fp32; differences and sum in fp32); bit c of `channel_mask` marks channel c
+ *   present.  sigma == 0: a_ij = 1, `x` is not read (it may be null) and the mask is ignored.
+ *   dlogits = dH/dl + weight * dP/dl, a gather (no scatter, no floating-point atomics): with g = dP/dp,
+ *     Potts      sigmoid head  g_ir = 1 / (n E) sum_j a_ij (1 - 2 p_jr);   softmax head  g_ik = 1 / (n E) sum_j a_ij (-p_jk)
+ *     quadratic  g_ik = 1 / (n E) sum_j a_ij 2 (p_ik - p_jk)
+ *     sigmoid head  dP/dl_ir = g_ir p_ir (1 - p_ir);   softmax head  dP/dl_ik = p_ik (g_ik - sum_m p_im g_im)
+ *   loss[n] = L, entropy[n] = H, pairwise[n] = P of item n (fp32 [N] each), from fp64 block partials summed in a fixed
+ *   order: two runs give the same bits, and N items in one call equal N calls bit for bit.
+ *   partial  fp64 [mmtta_crf_partials(logits)] scratch.
+ * Two launches - the main pass and a per-item finish - queued on `stream` without synchronisation or host read (capturable).
+ * `logits` channels-last fp32 [N,D,H,W,R], never written; `dlogits` of the same shape and row width.  Two routes:
+ *   tiled    R <= 4, C <= 4, dense 16-byte logit rows, dense 4-element rows of `dlogits` and of `x`: a workgroup stages a
+ *            4 x 8 x 32 tile of p and of x with a one-voxel halo in LDS and computes the affinities on the fly.  `dlogits`
+ *            fp32, or - sigmoid head - bf16 (8-byte voxels: the thin gradients of method.grad_storage).  A row of `dlogits`
+ *            is one 16- / 8-byte store - pad lanes written as 0 - when R == 4 or the view is MMTTA_TENSOR_OWNS_PAD; else R
+ *            element stores, pad lanes left as they are.
+ *   generic  everything else up to R <= 16 and C <= 16: one thread per voxel from global memory, fp32 `dlogits`, pad lanes
+ *            left as they are.
+ * MMTTA_ERR_INVALID before anything is launched: null pointers, a shape or row-width mismatch between `logits` and
+ * `dlogits`, `x` of another spatial shape, a connectivity other than 6 / 18 / 26, a form other than 0 / 1, a weight that is
+ * not finite and in (0, 16], a sigma that is negative, not finite or so small that 1 / (2 sigma^2) overflows fp32 (below about
+ * 4.6e-20), sigma > 0 with no bit of channel_mask among the C channels, `dlogits` aliasing `logits` or `x`.  R > 16 or C > 16, storages without a kernel (logits that are not fp32, a
+ * bf16 `dlogits` off the sigmoid head's tiled route, views that are not channels-last), items of 2^31 elements or more and
+ * more than 65535 items (gridDim.y carries the item) are MMTTA_ERR_UNSUPPORTED. */
+int64_t mmtta_crf_partials(const mmtta_tensor* logits);
+int mmtta_crf_entropy_items(const mmtta_tensor* logits, const mmtta_tensor* x, uint32_t channel_mask, int softmax,
+                            int connectivity, int form, float weight, float sigma, const mmtta_tensor* dlogits,
+                            double* partial, float* loss, float* entropy, float* pairwise, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

@@ -1282,6 +1282,49 @@ def lame_refine(logits0: torch.Tensor, x: Optional[torch.Tensor], out: torch.Ten
                                         C.byref(to), ptr(flipped), stream_ptr()), "lame_refine")
 
 
+CRF_FORMS = ("potts", "quadratic")
+
+
+def crf_partials(logits: torch.Tensor) -> int:
+    """fp64 elements of the block-partial scratch ``crf_entropy_items`` needs for ``logits``."""
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_crf_partials(C.byref(t)))
+
+
+def crf_entropy_items(logits: torch.Tensor, x: Optional[torch.Tensor], dlogits: torch.Tensor, partial: torch.Tensor,
+                      loss: torch.Tensor, entropy: torch.Tensor, pairwise: torch.Tensor, *, connectivity: int, weight: float,
+                      sigma: float, form: str = "potts", present: Optional[Sequence[bool]] = None, softmax: bool = False) -> None:
+    """CRF-regularised entropy (include/mmtta.h, mmtta_crf_entropy_items): per batch item L = H + weight * P with H the mean
+    entropy and P = 1 / (2 n E) sum_i sum_{j in N(i)} a_ij phi(p_i, p_j) over the ``connectivity`` spatial neighbours, phi the
+    ``potts`` or ``quadratic`` form, a_ij = exp(-|x_i - x_j|^2 / (2 sigma^2)) on the channels of the staged input ``x`` that
+    ``present`` marks (default: all; ``sigma`` 0: a_ij = 1 and ``x`` may be None).  ``dlogits`` receives dL/dlogits; ``loss``,
+    ``entropy`` and ``pairwise`` (fp32, one slot per batch item) L, H and P; ``partial`` is fp64 scratch of
+    ``crf_partials(logits)`` elements."""
+    n = int(logits.shape[0])
+    if form not in CRF_FORMS:
+        raise MmttaError(f"crf_entropy_items: form must be one of {CRF_FORMS}, got {form!r}")
+    for name, t in (("loss", loss), ("entropy", entropy), ("pairwise", pairwise)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+            raise MmttaError(f"crf_entropy_items: {name} must be contiguous fp32 of at least {n} elements (one per batch item)")
+    mask = 0xFFFFFFFF
+    if present is not None:
+        if x is not None and len(present) != int(x.shape[-1]):
+            raise MmttaError(f"crf_entropy_items: present has {len(present)} entries for the {int(x.shape[-1])} channels of x")
+        if len(present) > 32:
+            raise MmttaError("crf_entropy_items: at most 32 channels in the mask")
+        mask = sum(1 << c for c, p in enumerate(present) if p)
+    if float(sigma) > 0.0 and x is None:
+        raise MmttaError("crf_entropy_items: sigma > 0 needs the staged input x")
+    if partial.dtype != torch.float64 or not partial.is_contiguous() or partial.numel() < crf_partials(logits):
+        raise MmttaError("crf_entropy_items: partial must be contiguous fp64 of crf_partials(logits) elements")
+    tz, tg = desc_cl(logits), desc_cl(dlogits)
+    tx = desc_cl(x) if (x is not None and float(sigma) > 0.0) else None
+    check(_lib.load().mmtta_crf_entropy_items(C.byref(tz), None if tx is None else C.byref(tx), mask, 1 if softmax else 0,
+                                              int(connectivity), CRF_FORMS.index(form), float(weight), float(sigma),
+                                              C.byref(tg), ptr(partial), ptr(loss), ptr(entropy), ptr(pairwise), stream_ptr()),
+          "crf_entropy_items")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 
