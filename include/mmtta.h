@@ -978,6 +978,46 @@ int mmtta_crf_entropy_items(const mmtta_tensor* logits, const mmtta_tensor* x, u
                             int connectivity, int form, float weight, float sigma, const mmtta_tensor* dlogits,
                             double* partial, float* loss, float* entropy, float* pairwise, void* stream);
 
+/* ------------------------------------------------------------------ entropy minus a regional nuclear norm */
+/* Batch nuclear-norm maximisation over a grid of boxes - csrc/nuclear.hip (Cui et al., CVPR 2020, "Towards Discriminability
+ * and Diversity: Batch Nuclear-norm Maximization"; the regional nuclear-norm term of Hu et al., MICCAI 2021, "Fully Test-time
+ * Adaptation for Image Segmentation").  Entropy minimisation is content when the minority class collapses; the nuclear norm
+ * of the prediction matrix rewards confidence AND every class staying alive.  Every batch item is its own objective:
+ *     L = entropy_weight * H - weight * N              H: the mean entropy of mmtta_entropy_loss_items (E elements)
+ *     N = 1 / Q * sum_A nu(A),     nu(A) = sum_k sqrt(lambda_k + eps m) / sqrt(m min(m, K))
+ *   The volume is cut into boxes of [bd, bh, bw] voxels that start at multiples of the box size (an entry of 0, or one >= the
+ *   extent: the whole extent; border boxes are smaller, nothing is padded).  A box of m voxels gives
+ *     softmax head  one m x K matrix A with the rows p_i = softmax(l_i), K = R;
+ *     sigmoid head  per region r one m x 2 matrix with the rows (p_ir, 1 - p_ir), p = sigmoid(l);
+ *   Q is the number of matrices of the item, lambda_k >= 0 the eigenvalues of G = A^T A (clamped at 0).  With eps -> 0, nu is
+ *   ||A||_* / sqrt(m min(m, K)) in (0, 1]; the smoothing keeps it differentiable at rank-deficient boxes.
+ *   dN/dA = A M / Q, M = c V diag(1 / sqrt(lambda_k + eps m)) V^T, c = 1 / sqrt(m min(m, K));  with g_i = (A M)_i / Q
+ *     softmax head  dN/dl_ik = p_ik (g_ik - sum_j p_ij g_ij);
+ *     sigmoid head  dN/dl_ir = [(A M)_i0 - (A M)_i1] / Q * p_ir (1 - p_ir);
+ *   dlogits = entropy_weight * dH/dl - weight * dN/dl.
+ *   loss[n] = L, entropy[n] = H, nuclear[n] = N of item n (fp32 [N] each).
+ *   scratch  fp64 [mmtta_nuclear_scratch(logits, softmax, bd, bh, bw)] (-1 on bad arguments).
+ * Four launches whatever the data and the box - the Gram pass (fp64 partials of the boxes' Gram entries and entropy, one
+ * read of the logits), the spectrum pass (per matrix: the partials summed in a fixed order, the eigenproblem in fp64 - closed
+ * form for 2 x 2, cyclic Jacobi up to 16 x 16 -, nu and the coefficients of M), the gradient pass (a second read of the
+ * logits) and a per-item finish - queued on `stream` without synchronisation or host read (capturable).  No floating-point
+ * atomics and no scatter: two runs give the same bits, N items in one call equal N calls bit for bit, and a box's gradient
+ * depends on its own voxels only.  `logits` channels-last fp32 [N,D,H,W,R], never written; `dlogits` of the same shape and
+ * row width.  Two routes:
+ *   fast     R <= 4, dense 16-byte logit rows, dense 4-lane rows of `dlogits` - fp32, or bf16 on the sigmoid head (8-byte
+ *            voxels: the thin gradients of method.grad_storage).  A row of `dlogits` is one store, pad lanes written 0, when
+ *            R == 4 or the view is MMTTA_TENSOR_OWNS_PAD; else R element stores, pad lanes left as they are.
+ *   generic  everything else up to R <= 16: fp32 `dlogits`, pad lanes left as they are.
+ * MMTTA_ERR_INVALID before anything is launched: null pointers, a shape or row-width mismatch, `dlogits` aliasing `logits`
+ * (equal or overlapping), a negative block entry, a weight not finite or outside (0, 16], an entropy_weight not finite or
+ * outside [0, 16], an eps not finite or outside [1e-6, 0.1].  MMTTA_ERR_UNSUPPORTED: R > 16, logits that are not fp32, a bf16
+ * `dlogits` off the sigmoid head's fast route, views that are not channels-last, items of 2^31 elements or more, more than
+ * 65535 items (gridDim.y carries the item), a scratch of 2^31 fp64 elements or more. */
+int64_t mmtta_nuclear_scratch(const mmtta_tensor* logits, int softmax, int bd, int bh, int bw);
+int mmtta_nuclear_entropy_items(const mmtta_tensor* logits, int softmax, int bd, int bh, int bw, float entropy_weight,
+                                float weight, float eps, const mmtta_tensor* dlogits, double* scratch, float* loss,
+                                float* entropy, float* nuclear, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

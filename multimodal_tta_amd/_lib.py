@@ -224,6 +224,9 @@ _SIGNATURES = {
     "mmtta_crf_partials": (C.c_int64, [_P(Tensor)]),
     "mmtta_crf_entropy_items": (C.c_int, [_P(Tensor), _P(Tensor), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                           _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_nuclear_scratch": (C.c_int64, [_P(Tensor), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mmtta_nuclear_entropy_items": (C.c_int, [_P(Tensor), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                              _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mmtta_optim_step": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,

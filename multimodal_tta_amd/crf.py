@@ -17,8 +17,8 @@ enter: the base mask is used, and on a runtime that re-stages the volume with ev
 network) the stencil reads a copy staged once per volume under the base mask.
 
 Where this differs from the papers: the neighbours are those of the voxel grid, not a dense CRF; the affinity is taken on
-the staged intensities, with no distance in mm; the regional nuclear-norm term of Hu et al. is not built; the term sits on
-top of Tent alone (not on SAR / MEMO / CoTTA / EATA / DeYO).
+the staged intensities, with no distance in mm; the regional nuclear-norm term of Hu et al. is a plugin of its own
+(``bnm_tta``, bnm.py), not a second term here; the term sits on top of Tent alone (not on SAR / MEMO / CoTTA / EATA / DeYO).
 
 The class is ``_update`` with the loss call swapped - the stencil needs the logits in memory, so the step gives up the
 head-loss epilogue of the last convolution - and the ``entropy`` / ``pairwise`` records; the per-volume loop - groups, lanes,

@@ -356,27 +356,6 @@ __global__ __launch_bounds__(256) void crf_finish_kernel(const double* partial, 
   }
 }
 
-// 4-element voxel rows with nothing between them: what the tiled kernel addresses with one 32-bit voxel index
-static bool crf_dense4(const mmtta_tensor* t) {
-  const int esz = t->dtype == MMTTA_BF16 ? 2 : 4;
-  return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
-         ((uintptr_t)t->ptr) % (4 * esz) == 0;
-}
-
-static bool crf_overlap(const mmtta_tensor* a, const mmtta_tensor* b) {
-  auto span = [](const mmtta_tensor* t, uintptr_t& lo, uintptr_t& hi) {
-    const long long esz = t->dtype == MMTTA_BF16 ? 2 : 4;
-    const long long last = (long long)(t->n - 1) * t->sn + (long long)(t->d - 1) * t->sd + (long long)(t->h - 1) * t->sh +
-                           (long long)(t->w - 1) * t->sw + t->c;
-    lo = (uintptr_t)t->ptr;
-    hi = lo + (uintptr_t)(last * esz);
-  };
-  uintptr_t alo, ahi, blo, bhi;
-  span(a, alo, ahi);
-  span(b, blo, bhi);
-  return !(ahi <= blo || bhi <= alo);
-}
-
 static long long crf_tiles(const mmtta_tensor* t) {
   return (long long)((t->w + CRF_TW - 1) / CRF_TW) * ((t->h + CRF_TH - 1) / CRF_TH) * ((t->d + CRF_TD - 1) / CRF_TD);
 }
@@ -430,8 +409,8 @@ extern "C" int mmtta_crf_entropy_items(const mmtta_tensor* logits, const mmtta_t
   MMTTA_CHECK(!aff || x->dtype == MMTTA_F32 || x->dtype == MMTTA_BF16, MMTTA_ERR_UNSUPPORTED, "crf entropy: `x` must be fp32 or bf16");
   auto cl = [](const mmtta_tensor* t) { return t->sc == 1 && t->sw >= t->c && t->sh >= 0 && t->sd >= 0 && t->sn >= 0; };
   MMTTA_CHECK(cl(logits) && cl(dlogits) && (!aff || cl(x)), MMTTA_ERR_UNSUPPORTED, "crf entropy: channels-last only");
-  MMTTA_CHECK(!crf_overlap(logits, dlogits), MMTTA_ERR_INVALID, "crf entropy: `dlogits` must not overlap `logits` (aliased)");
-  MMTTA_CHECK(!aff || !crf_overlap(x, dlogits), MMTTA_ERR_INVALID, "crf entropy: `x` is aliased by `dlogits`");
+  MMTTA_CHECK(!loss_overlap(logits, dlogits), MMTTA_ERR_INVALID, "crf entropy: `dlogits` must not overlap `logits` (aliased)");
+  MMTTA_CHECK(!aff || !loss_overlap(x, dlogits), MMTTA_ERR_INVALID, "crf entropy: `x` is aliased by `dlogits`");
   // the kernels index the voxels and the elements of one item with 32-bit arithmetic
   auto small = [](const mmtta_tensor* t) {
     const long long ld = t->sw > 4 ? t->sw : 4;
@@ -441,7 +420,7 @@ extern "C" int mmtta_crf_entropy_items(const mmtta_tensor* logits, const mmtta_t
               "crf entropy: an item of 2^31 elements or more");
   MMTTA_CHECK(logits->n <= CRF_MAX_GRID_Y, MMTTA_ERR_UNSUPPORTED, "crf entropy: more than %d items in one call", CRF_MAX_GRID_Y);
   const int R = logits->c;
-  const bool tiled = R <= 4 && crf_dense4(logits) && crf_dense4(dlogits) && (!aff || (x->c <= 4 && crf_dense4(x)));
+  const bool tiled = R <= 4 && loss_dense4(logits) && loss_dense4(dlogits) && (!aff || (x->c <= 4 && loss_dense4(x)));
   MMTTA_CHECK(is_f32(dlogits) || (tiled && !softmax), MMTTA_ERR_UNSUPPORTED,
               "crf entropy: a bf16-stored `dlogits` needs the sigmoid head on the tiled route (<= 4 regions and channels in "
               "dense 4-element voxel rows)");

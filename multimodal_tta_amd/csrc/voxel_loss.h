@@ -28,6 +28,26 @@ inline bool loss_dense16(const mmtta_tensor* t) {
   return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
          ((uintptr_t)t->ptr) % 16 == 0;
 }
+// 4-element voxel rows with nothing between them, fp32 or bf16: what a kernel addresses with one 32-bit voxel index
+inline bool loss_dense4(const mmtta_tensor* t) {
+  const int esz = t->dtype == MMTTA_BF16 ? 2 : 4;
+  return t->sc == 1 && t->sw == 4 && t->sh == (int64_t)t->w * 4 && t->sd == (int64_t)t->h * t->sh && t->sn % 4 == 0 &&
+         ((uintptr_t)t->ptr) % (4 * esz) == 0;
+}
+// the byte spans of two views meet
+inline bool loss_overlap(const mmtta_tensor* a, const mmtta_tensor* b) {
+  auto span = [](const mmtta_tensor* t, uintptr_t& lo, uintptr_t& hi) {
+    const long long esz = t->dtype == MMTTA_BF16 ? 2 : 4;
+    const long long last = (long long)(t->n - 1) * t->sn + (long long)(t->d - 1) * t->sd + (long long)(t->h - 1) * t->sh +
+                           (long long)(t->w - 1) * t->sw + t->c;
+    lo = (uintptr_t)t->ptr;
+    hi = lo + (uintptr_t)(last * esz);
+  };
+  uintptr_t alo, ahi, blo, bhi;
+  span(a, alo, ahi);
+  span(b, blo, bhi);
+  return !(ahi <= blo || bhi <= alo);
+}
 // every offset inside one item fits 31 bits (the kernels that index voxels with 32-bit arithmetic)
 inline bool loss_small_item(const mmtta_tensor* t) {
   const long long ld = t->sw > t->c ? t->sw : t->c;

@@ -1325,6 +1325,46 @@ def crf_entropy_items(logits: torch.Tensor, x: Optional[torch.Tensor], dlogits: 
           "crf_entropy_items")
 
 
+def _nuclear_block(block: Sequence[int], what: str) -> Tuple[int, int, int]:
+    ok = isinstance(block, (list, tuple)) and len(block) == 3 and all(
+        isinstance(b, int) and not isinstance(b, bool) and b >= 0 for b in block)
+    if not ok:
+        raise MmttaError(f"{what}: block must be three integers >= 0 (0: the whole extent), got {block!r}")
+    return int(block[0]), int(block[1]), int(block[2])
+
+
+def nuclear_scratch(logits: torch.Tensor, block: Sequence[int], softmax: bool = False) -> int:
+    """fp64 elements of the scratch ``nuclear_entropy_items`` needs for ``logits`` cut into boxes of ``block`` voxels."""
+    bd, bh, bw = _nuclear_block(block, "nuclear_scratch")
+    t = desc_cl(logits)
+    n = int(_lib.load().mmtta_nuclear_scratch(C.byref(t), 1 if softmax else 0, bd, bh, bw))
+    if n < 0:
+        raise MmttaError(f"nuclear_scratch: no scratch size for logits {tuple(logits.shape)} and block {list(block)}")
+    return n
+
+
+def nuclear_entropy_items(logits: torch.Tensor, dlogits: torch.Tensor, scratch: torch.Tensor, loss: torch.Tensor,
+                          entropy: torch.Tensor, nuclear: torch.Tensor, *, block: Sequence[int], weight: float,
+                          entropy_weight: float = 1.0, eps: float = 1e-4, softmax: bool = False) -> None:
+    """Entropy minus a regional nuclear norm (include/mmtta.h, mmtta_nuclear_entropy_items): per batch item
+    L = entropy_weight * H - weight * N with H the mean entropy and N the mean over the boxes of ``block`` = [bd, bh, bw] voxels
+    (0: the whole extent) of the smoothed, normalised nuclear norm of the box's prediction matrix - per region the rows
+    (p, 1 - p) on the sigmoid head, the rows softmax(l) on the softmax head.  ``dlogits`` receives dL/dlogits; ``loss``,
+    ``entropy`` and ``nuclear`` (fp32, one slot per batch item) L, H and N; ``scratch`` is fp64 of
+    ``nuclear_scratch(logits, block, softmax)`` elements."""
+    n = int(logits.shape[0])
+    bd, bh, bw = _nuclear_block(block, "nuclear_entropy_items")
+    for name, t in (("loss", loss), ("entropy", entropy), ("nuclear", nuclear)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+            raise MmttaError(f"nuclear_entropy_items: {name} must be contiguous fp32 of at least {n} elements (one per batch item)")
+    if scratch.dtype != torch.float64 or not scratch.is_contiguous() or scratch.numel() < nuclear_scratch(logits, block, softmax):
+        raise MmttaError("nuclear_entropy_items: scratch must be contiguous fp64 of nuclear_scratch(logits, block, softmax) elements")
+    tz, tg = desc_cl(logits), desc_cl(dlogits)
+    check(_lib.load().mmtta_nuclear_entropy_items(C.byref(tz), 1 if softmax else 0, bd, bh, bw, float(entropy_weight),
+                                                  float(weight), float(eps), C.byref(tg), ptr(scratch), ptr(loss), ptr(entropy),
+                                                  ptr(nuclear), stream_ptr()), "nuclear_entropy_items")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 
