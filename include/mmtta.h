@@ -1018,6 +1018,55 @@ int mmtta_nuclear_entropy_items(const mmtta_tensor* logits, int softmax, int bd,
                                 float weight, float eps, const mmtta_tensor* dlogits, double* scratch, float* loss,
                                 float* entropy, float* nuclear, void* stream);
 
+/* ------------------------------------------------------------------ input normaliser */
+/* A per-volume intensity map in front of the network that adapts while the network may stay frozen - csrc/input_norm.hip
+ * (Karani et al., MedIA 2021, "Test-time adaptable neural networks for robust medical image segmentation").  Volume n and
+ * channel c carry theta[n][c] = (s, b, g, 0), fp32 [N][C][4] on the device:
+ *     u  = x                                                  gamma == 0
+ *     u  = ((x - lo) / (hi - lo))^exp(g) (hi - lo) + lo       gamma != 0 (the power as mmtta_augment_views computes it)
+ *     x' = exp(s) u + b                                       (product and sum rounded on their own)
+ *   `range` is what mmtta_intensity_range wrote for the raw volume ([N][C][2]: lo, hi); a channel with hi == lo has u = x.
+ *   Bit c of `keep_mask` says channel c is present: an absent channel is left alone and has no gradient.
+ * mmtta_input_norm_apply: y = x' in one streaming pass.  `x` the raw staged volume, fp32 channels-last rows of 4 lanes
+ *   (<= 4 channels), never written; `y` of the same shape, fp32 or bf16 rows of 4 lanes, owning its pad lanes.  16-byte loads;
+ *   16-byte stores (bf16: one per pair of voxels, an unpaired voxel at either end of an item takes 8 bytes).  A channel
+ *   whose theta row is all zero, an absent channel and the pad lanes pass through: the same bits in fp32, one rounding in bf16.
+ * mmtta_input_norm_grad: the reduced input gradient of the network's first level,
+ *     grad[n][c] = (dL/ds, dL/db, dL/dg, 0) = sum_v dX'[n,c,v] * dx'/dtheta (x[n,c,v]),     fp32 [N][C][4]
+ *     dX'[n,c,i] = keep_c * sum_branches sum_o sum_taps W_r[o,c,t] * dy_r[n,o,(i + 1 - t) / 2]
+ *   over the one or two convolutions that read the input (`branches`: k = 3, stride 2, pad 1, C -> c0 with c0 a multiple of 4
+ *   up to 64; anything else is MMTTA_ERR_UNSUPPORTED).  dy_r is the gradient of branch r's output as the backward left it -
+ *   channels-last [N, ceil(D/2), ceil(H/2), ceil(W/2), c0], fp32 or bf16 (both branches alike), possibly a channel slice of a
+ *   wider tensor -, W_r the fp32 weights in torch layout [c0, C, 3, 3, 3]; item n reads the set `set_stride` * n elements
+ *   behind `weight` (0: one set).  dX never reaches memory: a workgroup gathers it for a tile of 4 x 8 x 64 input voxels
+ *   from the weights in LDS, multiplies by the derivatives and writes 12 fp64 partials; a second launch sums them in a
+ *   fixed order and writes grad.  dL/dg is 0 with gamma == 0 or hi == lo; rounding x' to bf16 counts as the identity.
+ *   With lr > 0 that launch also takes torch.optim.Adam's step on theta (betas 0.9 / 0.999, eps 1e-8, no decay; fp64
+ *   arithmetic, fp32 state `exp_avg` / `exp_avg_sq` [N][C][4]; `step` a device int32 [N] this call advances, a volume whose
+ *   step is 0 starts from zero moments) and clamps (s, b, g) to +- (bound_log_scale, bound_shift, bound_log_gamma); g moves
+ *   only with gamma != 0, an absent channel not at all.  lr == 0: theta is only read, the last three pointers may be null.
+ *   partial  fp64 [mmtta_input_norm_grad_partials(x)] (-1 on a null or empty tensor; host-only).
+ * No floating-point atomics and no scatter: two runs give the same bits and N items in one call equal N calls bit for bit.
+ * Both queue on `stream` without synchronisation or host read (capturable).  MMTTA_ERR_INVALID before anything is launched:
+ * null pointers, a shape mismatch (x / y, or dy against the input's output extents), y == x, n_branches outside {1, 2},
+ * branches that differ in channels or storage, a negative set stride, lr or a bound not finite or out of range.
+ * MMTTA_ERR_UNSUPPORTED: more than 4 input channels, rows that are not dense 4-lane voxel rows, an x that is not fp32,
+ * k != 3 or stride != 2, c0 not a multiple of 4 or above 64, misaligned buffers, items of 2^31 elements or more, more than
+ * 65535 volumes. */
+typedef struct mmtta_input_norm_branch {
+  const mmtta_tensor* dy;
+  const float* weight;
+  int64_t set_stride;
+  int32_t ksize, stride;
+} mmtta_input_norm_branch;
+int mmtta_input_norm_apply(const mmtta_tensor* x, const mmtta_tensor* y, const float* theta, const float* range,
+                           uint32_t keep_mask, int gamma, void* stream);
+int64_t mmtta_input_norm_grad_partials(const mmtta_tensor* x);
+int mmtta_input_norm_grad(const mmtta_tensor* x, const mmtta_input_norm_branch* branches, int n_branches, float* theta,
+                          const float* range, uint32_t keep_mask, int gamma, double* partial, float* grad, float* exp_avg,
+                          float* exp_avg_sq, int32_t* step, double lr, double bound_log_scale, double bound_shift,
+                          double bound_log_gamma, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

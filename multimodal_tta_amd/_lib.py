@@ -110,6 +110,11 @@ class IntensityRule(C.Structure):      # mmtta_intensity_rule
                 ("mean", C.c_float), ("std", C.c_float), ("legacy", C.c_int32), ("_pad", C.c_int32)]
 
 
+class InputNormBranch(C.Structure):    # mmtta_input_norm_branch
+    _fields_ = [("dy", C.POINTER(Tensor)), ("weight", C.c_void_p), ("set_stride", C.c_int64), ("ksize", C.c_int32),
+                ("stride", C.c_int32)]
+
+
 _P = C.POINTER
 _SIGNATURES = {
     "mmtta_last_error": (C.c_char_p, []),
@@ -227,6 +232,11 @@ _SIGNATURES = {
     "mmtta_nuclear_scratch": (C.c_int64, [_P(Tensor), C.c_int, C.c_int, C.c_int, C.c_int]),
     "mmtta_nuclear_entropy_items": (C.c_int, [_P(Tensor), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                               _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_input_norm_apply": (C.c_int, [_P(Tensor), _P(Tensor), C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "mmtta_input_norm_grad_partials": (C.c_int64, [_P(Tensor)]),
+    "mmtta_input_norm_grad": (C.c_int, [_P(Tensor), _P(InputNormBranch), C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                        C.c_double, C.c_double, C.c_void_p]),
     "mmtta_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mmtta_optim_step": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,

@@ -1,0 +1,235 @@
+"""``innorm_tta``: entropy minimisation that adapts the network's INPUT (Karani et al., MedIA 2021, "Test-time adaptable neural
+networks for robust medical image segmentation": the segmentation network is frozen and a shallow image normaliser adapts
+per test volume).  The dominant shift between centres is an intensity shift per modality - scanner gain, SUV scaling, a
+z-score over another mask -, the family the reference normalises by (a per-channel clip and a masked z-score) and augments
+with (``RandScaleIntensity``, ``RandShiftIntensity``); MEMO and CoTTA draw it as random views, this plugin learns it.
+
+Every volume of a group carries theta = (s_c, b_c, g_c) per modality, 0 at the start and reset with the weights:
+
+    u  = x                                                     (innorm.gamma: false)
+    u  = ((x - lo) / (hi - lo))^exp(g_c) (hi - lo) + lo        (innorm.gamma: true; lo, hi: the channel's range over the volume)
+    x' = exp(s_c) u + b_c
+
+One step: x' is written from the raw volume (``ops.input_norm_apply``); the parent's sequence - forward, entropy, backward,
+the optimizer on whatever ``method.params`` selects - runs on x'; theta takes one Adam step on dL/dtheta and is clamped to
+its box (``ops.input_norm_grad``: the first level's input gradient reduced to 3 numbers per modality, never stored as a
+volume; between the backward and the optimizer, so both gradients are taken at the step's weights and the step's theta).
+The returned logits are the eval forward of x' at the final theta.  With ``method.params: []`` the network is the source
+model bit for bit and only theta adapts - Karani's setting.
+
+Where this differs from the paper: the normaliser is 2 - 3 numbers per modality, not a small convolutional network; the
+objective is Tent's entropy, not a denoising-autoencoder prior; the only prior on theta is the box.  It sits on top of Tent
+alone (not on SAR / MEMO / CoTTA / EATA / DeYO / CRF / BNM), on the ``unet`` model (not the deep-fusion network, whose
+family batch and re-staging path would be a second integration), and not together with modality dropout.
+
+``lr: 0`` takes the parent's step untouched - nothing new is launched - and is ``entmin_tta`` bit for bit.
+"""
+from __future__ import annotations
+
+import math
+from typing import Any, Dict, Optional, Sequence, Tuple
+
+import torch
+
+from . import ops
+from .config import as_cfg, get_config
+from .engine import HeadLossTail
+from .models.unet import UNetRuntime
+from .ops import MmttaError
+from .registry import register_plugin
+from .tta import EntropyMinimizationTTA
+
+MAX_LOG_SCALE, MAX_SHIFT, MAX_LOG_GAMMA = 4.0, 16.0, 2.0
+MAX_COUT, MAX_CIN = 64, 4
+
+
+def _number(value: Any) -> bool:
+    return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value)
+
+
+@register_plugin("innorm_tta")
+class InputNormTTA(EntropyMinimizationTTA):
+    """``method.innorm.lr`` (finite, >= 0, default 1e-2; 0: ``entmin_tta``), ``gamma`` (bool, default false: the power form of
+    u), ``bound.log_scale`` ((0, 4], default 0.7), ``bound.shift`` ((0, 16], default 1.0) and ``bound.log_gamma`` ((0, 2],
+    default 0.7): theta is clamped to +- its bound after every step.  theta's optimizer is Adam with torch's default betas
+    and eps and no decay, whatever ``training.optimizer`` is.  Everything else is ``entmin_tta``'s, with one limit: every
+    volume has its own theta, so a call takes at most ``method.group`` volumes."""
+
+    def __init__(self, config: Any = None):
+        super().__init__(config)
+        m = get_config(as_cfg(config), "method", {}) or {}
+        s = get_config(m, "innorm", {}) or {}
+        lr, gm = get_config(s, "lr", 1e-2), get_config(s, "gamma", False)
+        bd = get_config(s, "bound", {}) or {}
+        bs, bb, bg = get_config(bd, "log_scale", 0.7), get_config(bd, "shift", 1.0), get_config(bd, "log_gamma", 0.7)
+        if not _number(lr) or lr < 0.0:
+            raise ValueError(f"method.innorm.lr = {lr!r}: expected a finite number >= 0 (0: entmin_tta)")
+        if not isinstance(gm, bool):
+            raise ValueError(f"method.innorm.gamma = {gm!r}: expected a bool")
+        for key, val, top in (("log_scale", bs, MAX_LOG_SCALE), ("shift", bb, MAX_SHIFT), ("log_gamma", bg, MAX_LOG_GAMMA)):
+            if not _number(val) or not (0.0 < val <= top):
+                raise ValueError(f"method.innorm.bound.{key} = {val!r}: expected a finite number in (0, {top:g}]")
+        if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
+            raise NotImplementedError("method.moddrop.enabled: innorm_tta learns one theta per volume on a fixed set of "
+                                      "modalities; modality dropout redraws them every step")
+        self.lr, self.gamma, self.bounds = float(lr), bool(gm), (float(bs), float(bb), float(bg))
+        self._raw: Optional[torch.Tensor] = None           # the raw fp32 staged volumes of the call
+        self._x_in: Optional[torch.Tensor] = None
+        self._t = 0
+
+    # ------------------------------------------------------------------ setup
+    def setup(self, model, device) -> "InputNormTTA":
+        if self.lr > 0.0 and getattr(model, "runtime_cls", None) is not UNetRuntime:
+            raise NotImplementedError(f"innorm_tta drives the 'unet' model; {type(model).__name__} (the deep-fusion family: "
+                                      "modality encoders in one launch, re-staged inputs) has no reduced input gradient")
+        super().setup(model, device)
+        if self.lr == 0.0:
+            return self
+        rt = self.rt
+        layers = rt.input_layers()
+        for layer in layers:
+            op = layer.op
+            if (op.transposed or op.k != 3 or op.stride != 2 or op.cout % 4 or op.cout > MAX_COUT or op.cin > MAX_CIN
+                    or len(layer.members) != 1):
+                what = f"{'convT' if op.transposed else 'conv'} {op.cin}->{op.cout} k{op.k}s{op.stride}"
+                raise NotImplementedError(f"innorm_tta: the model's first level reads its input through a {what}; the "
+                                          f"reduced input gradient gathers k = 3, stride 2 convolutions of <= {MAX_CIN} "
+                                          f"channels into a multiple of 4 up to {MAX_COUT}")
+        # the gradient reads the arena's weights of the step: no first-level layer may update inside the backward
+        if any(layer in rt.fused_layers for layer in layers):
+            raise MmttaError("innorm_tta: a first-level convolution is in the fused weight update; its weights would move "
+                             "before the input gradient reads them")
+        self._input_layers = layers
+        return self
+
+    # ------------------------------------------------------------------ theta
+    def _tables(self) -> Dict[str, torch.Tensor]:
+        rt, c = self.rt, self.rt.in_channels
+        g = rt.group
+        return {"theta": rt.pool.flat("innorm_theta", g * c * 4, zero=True), "grad": rt.pool.flat("innorm_grad", g * c * 4, zero=True),
+                "exp_avg": rt.pool.flat("innorm_exp_avg", g * c * 4, zero=True),
+                "exp_avg_sq": rt.pool.flat("innorm_exp_avg_sq", g * c * 4, zero=True),
+                "step": rt.pool.flat("innorm_step", g, dtype=torch.int32, zero=True),
+                "range": rt.pool.flat("innorm_range", g * c * 2, zero=True)}
+
+    def _reset(self) -> None:
+        super()._reset()
+        if self.lr > 0.0:
+            t = self._tables()
+            t["theta"].zero_()
+            t["step"].zero_()        # (step 0 starts from zero moments whatever the buffers hold)
+
+    def _apply(self, raw: torch.Tensor, x: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+        t = self._tables()
+        ops.input_norm_apply(raw, x, t["theta"], t["range"], present=present, gamma=self.gamma)
+
+    def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
+        if self.lr == 0.0:
+            return super()._stage(x_cl)
+        rt = self.rt
+        n, d, h, w, c = x_cl.shape
+        if n > rt.group:          # (every volume has its own theta)
+            raise ValueError(f"method.group = {rt.group}: innorm_tta adapts at most {rt.group} volumes per call, got {n}")
+        # the raw volume stays in fp32: a value is rounded once, after the map
+        raw = rt.pool.cl("x_raw", n, d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=torch.float32)
+        ops.to_cl(self._x_in, out=raw)
+        t = self._tables()
+        partial = rt.pool.flat("innorm_range_partial", ops.intensity_range_partials(raw))
+        ops.intensity_range(raw, partial, t["range"])
+        self._raw = raw
+        self._hist = rt.pool.flat("innorm_grad_hist", max(self.steps, self._steps_now, 1) * rt.group * c * 4).view(-1, rt.group, c, 4)
+        self._t = 0
+        return x_cl, (raw,)
+
+    # ------------------------------------------------------------------ one step
+    def _update(self, x: torch.Tensor, present: Optional[Sequence[bool]], *views: torch.Tensor) -> None:
+        """The parent's sequence on x' - the map first, the reduced input gradient between the backward and the optimizer -
+        and the backward runs whether or not a weight trains."""
+        if self.lr == 0.0:
+            super()._update(x, present)
+            return
+        raw, = views
+        rt, ar = self.rt, self.rt.arena
+        self._apply(raw, x, present)
+        rt.pack_all(fused_current=True)
+        loss = rt.pool.flat("ent_loss", rt.group)
+        per_item = rt.group > 1
+        tail = None
+        if getattr(rt, "supports_head_tail", False) and not self.softmax and (per_item or int(x.shape[0]) == 1):
+            tail = HeadLossTail(self._dlogits, loss, per_item)
+        kw = {} if present is None else {"present": present}
+        logits = rt.forward_cl(x, **kw) if tail is None else rt.forward_cl(x, tail=tail, **kw)
+        if tail is not None and tail.done:
+            dlogits = tail.dlogits
+        elif rt.group > 1:
+            dlogits = self._dlogits(logits)
+            partial = rt.pool.flat("ent_partial", ops.entropy_partials_items(logits), dtype=torch.float64)
+            ops.entropy_loss_items(logits, dlogits, partial, loss, softmax=self.softmax)
+        else:
+            dlogits = self._dlogits(logits)
+            partial = rt.pool.flat("ent_partial", ops.entropy_partials(logits), dtype=torch.float64)
+            ops.entropy_loss(logits, dlogits, partial, loss, softmax=self.softmax)
+        fused = bool(rt.fused_layers) and ar.n_train > 0
+        rt.fused_active = fused         # only this backward updates the fused layers in place
+        try:
+            rt.run_backward(dlogits)
+        finally:
+            rt.fused_active = False
+        self._input_step(raw, present)
+        if ar.n_train > 0:
+            self.optimizer_step(int(logits.shape[0]), fused=fused)
+
+    def _input_step(self, raw: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+        """dL/dtheta from what the backward left, Adam's step on theta and the clamp: two launches."""
+        rt, ar = self.rt, self.rt.arena
+        t = self._tables()
+        branches = []
+        for dy, layer, k, stride in rt.input_branches():
+            w = layer.weight
+            shared = layer.frozen or not rt.use_sets or ar.replicas == 1      # (a frozen layer's replicas all hold the source)
+            branches.append((dy, ar.replica_data(w, 0), 0 if shared else ar.total, k, stride))
+        partial = rt.pool.flat("innorm_partial", ops.input_norm_grad_partials(raw), dtype=torch.float64)
+        try:
+            ops.input_norm_grad(raw, branches, t["theta"], t["range"], partial, t["grad"], present=present, gamma=self.gamma,
+                                exp_avg=t["exp_avg"], exp_avg_sq=t["exp_avg_sq"], step=t["step"], lr=self.lr, bounds=self.bounds)
+        except MmttaError as exc:
+            if "status -2" in str(exc):        # MMTTA_ERR_UNSUPPORTED: a first level the kernel does not gather
+                raise NotImplementedError(f"innorm_tta: the model's first level is not supported: {exc}") from exc
+            raise
+
+    def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]], *views: torch.Tensor) -> None:
+        super()._step(x_cl, present, *views)
+        if self.lr > 0.0:
+            self._hist[self._t].copy_(self._tables()["grad"].view(self._hist.shape[1:]))
+            self._t += 1
+
+    def _final_logits(self, x_cl: torch.Tensor, x_step: torch.Tensor, present: Optional[Sequence[bool]]) -> torch.Tensor:
+        """The eval-mode forward of x' at the final theta: the map runs once more, after the last step."""
+        if self.lr > 0.0:
+            self._apply(self._raw, x_cl, present)
+        return self._forward(x_cl, present)
+
+    # ------------------------------------------------------------------ per volume
+    @torch.no_grad()
+    def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
+        """``EntropyMinimizationTTA.adapt_volume`` plus ``input_grad`` [steps, B, C, 3] (dL/d(s, b, g) of every step; the g
+        column is 0 with gamma off) and ``input_scale``, ``input_shift``, ``input_gamma`` [B, C]: exp(s), b, exp(g) at the end."""
+        B, C = int(x.shape[0]), int(x.shape[1])
+        self._steps_now = self.steps if steps is None else int(steps)
+        self._x_in = x.float()
+        try:
+            out = super().adapt_volume(x, steps)
+        finally:
+            self._x_in = None
+        if self.lr == 0.0:
+            out["input_grad"] = torch.zeros((self._steps_now, B, C, 3), dtype=torch.float32, device=x.device)
+            out["input_scale"] = torch.ones((B, C), dtype=torch.float32, device=x.device)
+            out["input_shift"] = torch.zeros((B, C), dtype=torch.float32, device=x.device)
+            out["input_gamma"] = torch.ones((B, C), dtype=torch.float32, device=x.device)
+            return out
+        theta = self._tables()["theta"].view(-1, C, 4)[:B]
+        out["input_grad"] = self._hist[:self._steps_now, :B, :, :3].clone()
+        out["input_scale"] = torch.exp(theta[..., 0])
+        out["input_shift"] = theta[..., 1].clone()
+        out["input_gamma"] = torch.exp(theta[..., 2])
+        return out

@@ -172,6 +172,45 @@ class UNetRuntime(Runtime):
         else:
             blk.bwd(dout, dx, accumulate=True, need_dx=need_dx)
 
+    # ---- the convolutions that read the network input (input-normaliser adaptation: innorm.py)
+    def input_layers(self) -> List[Any]:
+        """The first level's convolutions whose operand is the network input: the first sub-unit's and the residual one of a
+        ResidualUnit, the one convolution of a plain block (``num_res_units: 0``)."""
+        blk = self.down[0]
+        if not isinstance(blk, ResidualUnitBlock):
+            return [blk.conv]
+        if blk.residual is None:
+            raise NotImplementedError("a first level whose residual is the identity (the input itself joins its output)")
+        return [blk.units[0].conv, blk.residual]
+
+    def _kept(self, key, shape, dtype: torch.dtype) -> torch.Tensor:
+        """A gradient buffer the last backward wrote (never a fresh allocation)."""
+        n, d, h, w, c = shape
+        if ("cl", key, n, d, h, w, c, ops.row_pad(c, dtype), dtype) not in self.pool._b:
+            raise ops.MmttaError(f"no backward has left the gradient buffer {key!r} for the shape {tuple(shape)}")
+        return self.pool.cl(key, n, d, h, w, c, dtype=dtype)
+
+    def input_branches(self) -> List[Any]:
+        """(dy, layer, k, stride) per convolution of ``input_layers``, as the last ``backward_cl`` left them: dy is the
+        gradient of that convolution's raw output - behind its norm backward for the first sub-unit, the level's output
+        gradient (a channel slice of the concat gradient) for the residual convolution."""
+        blk = self.down[0]
+        dout = self._cat(0, self.n, self.dims, grad=True)[..., :self.channels[0]]
+        if isinstance(blk, ResidualUnitBlock):
+            d = dout
+            for u in range(len(blk.units) - 1, 0, -1):      # the storage types ResidualUnitBlock.bwd gave its buffers
+                inp = blk.units[u].saved[0]
+                d = self._kept((blk.key, "dprev", u), inp.shape, self.grad_dtype(inp.shape[-1], like=d))
+            first = blk.units[0]
+        else:
+            d, first = dout, blk
+        dy = d if first.norm is None else self._kept((first.key, "dy"), first.saved[2].shape, d.dtype)
+        layers = self.input_layers()
+        out = [(dy, layers[0], layers[0].op.k, layers[0].op.stride)]
+        if len(layers) > 1:
+            out.append((dout, layers[1], layers[1].op.k, layers[1].op.stride))
+        return out
+
     def backward_cl(self, dlogits: torch.Tensor) -> None:
         n, dims, c, L = self.n, self.dims, self.channels, self.L
         d = dlogits

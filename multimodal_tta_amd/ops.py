@@ -1365,6 +1365,75 @@ def nuclear_entropy_items(logits: torch.Tensor, dlogits: torch.Tensor, scratch: 
                                                   ptr(nuclear), stream_ptr()), "nuclear_entropy_items")
 
 
+def _keep_mask(present: Optional[Sequence[bool]], channels: int) -> int:
+    if present is None:
+        return (1 << channels) - 1
+    if len(present) != channels:
+        raise MmttaError(f"input_norm: the modality mask has {len(present)} entries for {channels} input channels")
+    return sum(1 << c for c, p in enumerate(present) if p)
+
+
+def _input_norm_tables(what: str, n: int, c: int, **tables: Optional[torch.Tensor]) -> None:
+    for name, (t, width) in tables.items():
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.numel() < n * c * width:
+            raise MmttaError(f"{what}: {name} must be contiguous device fp32 of at least {n * c * width} elements "
+                             f"([{n}, {c}, {width}])")
+
+
+def input_norm_apply(x: torch.Tensor, y: torch.Tensor, theta: torch.Tensor, value_range: torch.Tensor,
+                     present: Optional[Sequence[bool]] = None, gamma: bool = False) -> None:
+    """The input normaliser's map (include/mmtta.h, mmtta_input_norm_apply): y = exp(s) u + b per volume and channel, from
+    the raw fp32 staged volume ``x`` into ``y`` (fp32 or bf16 rows), with ``theta`` [N, C, 4] = (s, b, g, 0), ``value_range``
+    what ``intensity_range`` wrote for x; the channels ``present`` marks absent, and rows of theta that are zero, pass through."""
+    n, c = int(x.shape[0]), int(x.shape[-1])
+    _input_norm_tables("input_norm_apply", n, c, theta=(theta, 4), value_range=(value_range, 2))
+    tx, ty = desc_cl(x), desc_cl(y)
+    check(_lib.load().mmtta_input_norm_apply(C.byref(tx), C.byref(ty), ptr(theta), ptr(value_range), _keep_mask(present, c),
+                                             1 if gamma else 0, stream_ptr()), "input_norm_apply")
+
+
+def input_norm_grad_partials(x: torch.Tensor) -> int:
+    """fp64 elements of the scratch ``input_norm_grad`` needs for the staged volume ``x``."""
+    t = desc_cl(x)
+    n = int(_lib.load().mmtta_input_norm_grad_partials(C.byref(t)))
+    if n < 0:
+        raise MmttaError(f"input_norm_grad_partials: no scratch size for x {tuple(x.shape)}")
+    return n
+
+
+def input_norm_grad(x: torch.Tensor, branches: Sequence[Tuple[torch.Tensor, torch.Tensor, int, int, int]], theta: torch.Tensor,
+                    value_range: torch.Tensor, partial: torch.Tensor, grad: torch.Tensor, *,
+                    present: Optional[Sequence[bool]] = None, gamma: bool = False, exp_avg: Optional[torch.Tensor] = None,
+                    exp_avg_sq: Optional[torch.Tensor] = None, step: Optional[torch.Tensor] = None, lr: float = 0.0,
+                    bounds: Sequence[float] = (0.0, 0.0, 0.0)) -> None:
+    """The reduced input gradient of the first level (include/mmtta.h, mmtta_input_norm_grad): ``grad`` [N, C, 4] =
+    (dL/ds, dL/db, dL/dg, 0) from the raw volume ``x`` and the ``branches`` that read it - (dy, weight, set_stride, k, stride)
+    each: the output gradient the backward left (channels-last, fp32 or bf16, maybe a channel slice), the fp32 weights
+    [c0, C, 3, 3, 3] of set 0 and the elements between the sets of consecutive items.  With ``lr`` > 0 the same call takes
+    Adam's step on ``theta`` (state ``exp_avg`` / ``exp_avg_sq`` [N, C, 4], device int32 ``step`` [N]) and clamps it to
+    +- ``bounds`` = (log_scale, shift, log_gamma)."""
+    n, c = int(x.shape[0]), int(x.shape[-1])
+    _input_norm_tables("input_norm_grad", n, c, theta=(theta, 4), value_range=(value_range, 2), grad=(grad, 4),
+                       exp_avg=(exp_avg, 4), exp_avg_sq=(exp_avg_sq, 4))
+    if partial.dtype != torch.float64 or not partial.is_contiguous() or partial.numel() < input_norm_grad_partials(x):
+        raise MmttaError("input_norm_grad: partial must be contiguous fp64 of input_norm_grad_partials(x) elements")
+    if step is not None and (step.dtype != torch.int32 or not step.is_contiguous() or step.numel() < n):
+        raise MmttaError(f"input_norm_grad: step must be contiguous device int32 of at least {n} elements")
+    descs = [desc_cl(dy) for dy, *_ in branches]
+    arr = (_lib.InputNormBranch * max(len(branches), 1))()
+    for r, (dy, weight, set_stride, k, stride) in enumerate(branches):
+        if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.numel() != int(dy.shape[-1]) * c * int(k) ** 3:
+            raise MmttaError(f"input_norm_grad: weight of branch {r} must be contiguous fp32 [{int(dy.shape[-1])}, {c}, {k}, {k}, {k}]")
+        arr[r] = _lib.InputNormBranch(C.pointer(descs[r]), ptr(weight), int(set_stride), int(k), int(stride))
+    tx = desc_cl(x)
+    check(_lib.load().mmtta_input_norm_grad(C.byref(tx), arr, len(branches), ptr(theta), ptr(value_range),
+                                            _keep_mask(present, c), 1 if gamma else 0, ptr(partial), ptr(grad), ptr(exp_avg),
+                                            ptr(exp_avg_sq), ptr(step), float(lr), float(bounds[0]), float(bounds[1]),
+                                            float(bounds[2]), stream_ptr()), "input_norm_grad")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 

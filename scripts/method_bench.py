@@ -13,9 +13,10 @@ AXES = {1: [], 2: ["w"], 4: ["h", "w"], 8: ["d", "h", "w"]}          # mirror ax
 class Method:
     """`lanes` plugins (own model replica, stream and graph each) adapting `group` volumes per launch sequence.
     `section`: (key, values) written over that section of the method's config (``method.sar``, ``method.memo``, ...);
-    `plugin`: a registered plugin name to run that config with instead of its own ``method.name``."""
+    `plugin`: a registered plugin name to run that config with instead of its own ``method.name``; `overrides`: further keys
+    of ``method`` itself (``params``, ...)."""
 
-    def __init__(self, method, lanes, group, streams, device, steps, section=None, plugin=None):
+    def __init__(self, method, lanes, group, streams, device, steps, section=None, plugin=None, overrides=None):
         from multimodal_tta_amd.config import compose
         from multimodal_tta_amd.models import UNet
         from multimodal_tta_amd.registry import get_plugin
@@ -28,6 +29,8 @@ class Method:
             cfg["method"][section[0]].update(section[1])
         if plugin is not None:
             cfg["method"]["name"] = plugin
+        if overrides:
+            cfg["method"].update(overrides)
         self.streams = streams[:lanes]
         self.plugs = []
         self.result = None          # lane 0's result of the last round
