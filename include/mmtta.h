@@ -1067,6 +1067,54 @@ int mmtta_input_norm_grad(const mmtta_tensor* x, const mmtta_input_norm_branch* 
                           float* exp_avg_sq, int32_t* step, double lr, double bound_log_scale, double bound_shift,
                           double bound_log_gamma, void* stream);
 
+/* ------------------------------------------------------------------ modality consistency */
+/* The cross-modal objective of modcons_tta - csrc/modcons.hip (in the family of MM-TTA, Shin et al., CVPR 2022): the
+ * prediction from all modalities should agree with the prediction from each subset of them.  A batch of G volumes x V views
+ * is [G * V, D, H, W, C], item g * V + v = view v of volume g; view 0 keeps every present modality, view v >= 1 a subset.
+ *
+ * mmtta_modality_views: y[g * V + v] = x[g] with channel c kept iff bit c of keep_masks[v] is set (`keep_masks`: a HOST
+ *   array of `views` masks, 1 <= views <= 8, read at launch; a bit outside the channels is MMTTA_ERR_INVALID).  x
+ *   [G, D, H, W, C] and y [G * V, D, H, W, C] channels-last, fp32 or bf16 alike, C <= 32.  A kept value keeps its bits; a
+ *   dropped channel is stored as +0, never as x * 0 - a NaN, an infinity or -0 there does not reach the view.  Dense rows of
+ *   4 lanes with C <= 4 (both tensors; y owning its pad lanes or C == 4) take one 16-byte (fp32) or 8-byte (bf16) load per
+ *   voxel and V stores; every other layout a per-element path.  The pad lanes that y owns are written 0.
+ *
+ * mmtta_modcons_loss_items: every volume g is its own objective (as in mmtta_entropy_loss_items).  Elements i are (voxel,
+ *   region) pairs (softmax == 0) or voxels (softmax != 0), n of them per volume; p_v = sigmoid(z_v) resp. softmax(z_v):
+ *     entropy[g]        = H_g   = 1/n sum_i H(p_0,i)
+ *     view_kl[g][v - 1] = K_g,v = 1/n sum_i KL(p_0,i || p_v,i)          v = 1 .. V-1 (Bernoulli per element, categorical per voxel)
+ *     consistency[g]    = C_g   = 1/(V-1) sum_v K_g,v
+ *     loss[g]           = entropy_weight * H_g + weight * C_g
+ *     dlogits of view v >= 1:  weight / ((V-1) n) * (p_v - p_0)
+ *     dlogits of view 0:       entropy_weight / n * dH/dz_0 + (detach ? 0 : weight / ((V-1) n) * sum_v dKL(p_0 || p_v)/dz_0)
+ *                              Bernoulli: dKL/dz_0 = p_0 (1 - p_0) (z_0 - z_v);  categorical: p_0,k [(log p_0,k - log p_v,k) - KL_i]
+ *     disagree[g][v - 1] = #{ i : hard(z_v,i) != hard(z_0,i) },  hard = (z >= 0) resp. the first arg max
+ *   The Bernoulli KL is sigmoid(a) (a - b) + softplus(b) - softplus(a) with the parts of the size of the logits cancelled
+ *   exactly ([a >= 0] (a - b) + max(b, 0) - max(a, 0) is |b| where the signs differ, else 0), held at 0 from below: finite and
+ *   non-negative for every pair of finite logits with a finite difference; views with equal bits give KL = 0, a gradient of 0
+ *   for v >= 1 and disagree = 0 exactly.  View 0's entropy term and its gradient are the bits of mmtta_entropy_loss_items on
+ *   the same path (fast, generic, categorical) - on the categorical head while the voxel's largest |logit| is below 16; from
+ *   there on the shifted form log sum e - sum p (z - max), exact to fp32 rounding at any magnitude.
+ *   One launch over loss_blocks(one item) x G workgroups of 256 threads - a thread owns a
+ *   voxel (fast path, categorical) or a (voxel, region) pair (generic path) of all V views, reads every logit once and writes
+ *   every gradient once - and one finish launch (one workgroup per volume).  No scatter, no floating-point atomics; the fp64
+ *   block partials - rows [entropy | KL per view | disagreement per view] - are summed in a fixed order, so G volumes in one
+ *   call are bit for bit G calls on one volume each.  Storages as mmtta_entropy_loss_items: fp32 logits; fp32 gradients, or -
+ *   softmax == 0, <= 4 channels in dense 4-channel voxel rows that own their pad - bf16; softmax != 0: up to 16 classes.
+ *   partial  fp64 [mmtta_modcons_partials(logits, views)] scratch = (2 V - 1) rows x loss_blocks(one item) x G (host-only;
+ *            -1 on a null tensor, views outside 2 .. 8, a batch that is no multiple of views, an empty extent)
+ *   loss, entropy, consistency  fp32 [G];  view_kl  fp32 [G][V-1];  disagree  int64 [G][V-1]
+ *
+ * MMTTA_ERR_INVALID before anything is launched: null pointers, views outside 2 .. 8 (1 .. 8 for the views' staging), a batch
+ * that is no multiple of views, shape mismatches, `dlogits` overlapping `logits` (`y` overlapping `x`), a weight that is not
+ * finite or negative.  MMTTA_ERR_UNSUPPORTED: storages without a kernel (a bf16 gradient off the fast path included), items
+ * of 2^31 elements or more, more than 65535 volumes. */
+int mmtta_modality_views(const mmtta_tensor* x, const mmtta_tensor* y, int views, const uint32_t* keep_masks, void* stream);
+int64_t mmtta_modcons_partials(const mmtta_tensor* logits, int views);
+int mmtta_modcons_loss_items(const mmtta_tensor* logits, int softmax, int views, float weight, float entropy_weight, int detach,
+                             const mmtta_tensor* dlogits, double* partial, float* loss, float* entropy, float* consistency,
+                             float* view_kl, int64_t* disagree, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

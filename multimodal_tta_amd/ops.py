@@ -1434,6 +1434,46 @@ def input_norm_grad(x: torch.Tensor, branches: Sequence[Tuple[torch.Tensor, torc
                                             float(bounds[2]), stream_ptr()), "input_norm_grad")
 
 
+def modality_views(x: torch.Tensor, y: torch.Tensor, keep_masks: Sequence[int]) -> None:
+    """y[g * V + v] = x[g] with channel c kept iff bit c of keep_masks[v] is set: channels-last [G,D,H,W,C] -> [G*V,D,H,W,C],
+    fp32 or bf16.  Kept values keep their bits; a dropped channel and the pad lanes ``y`` owns are stored as +0."""
+    masks = [int(m) for m in keep_masks]
+    if any(not (0 <= m < 1 << 32) for m in masks):
+        raise MmttaError(f"modality_views: keep_masks = {masks!r} (32-bit channel masks)")
+    tx, ty = desc_cl(x), desc_cl(y)
+    check(_lib.load().mmtta_modality_views(C.byref(tx), C.byref(ty), len(masks), (C.c_uint32 * max(len(masks), 1))(*masks),
+                                           stream_ptr()), "modality_views")
+
+
+def modcons_partials(logits: torch.Tensor, views: int) -> int:
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_modcons_partials(C.byref(t), int(views)))
+
+
+def modcons_loss_items(logits: torch.Tensor, dlogits: torch.Tensor, views: int, partial: torch.Tensor, loss: torch.Tensor,
+                       entropy: torch.Tensor, consistency: torch.Tensor, view_kl: torch.Tensor, disagree: torch.Tensor,
+                       weight: float = 1.0, entropy_weight: float = 1.0, detach: bool = True, softmax: bool = False) -> None:
+    """The modality-consistency objective of every volume on its own: logits / dlogits [G*V,D,H,W,R] (item g*V+v = view v of
+    volume g, view 0 the full one); loss = entropy_weight * entropy + weight * consistency, all three fp32 [G]; view_kl fp32
+    [G, V-1] (the mean KL of view 0's prediction to view v's); disagree int64 [G, V-1] (elements whose hard label differs)."""
+    views = int(views)
+    need = modcons_partials(logits, views)          # -1 for a bad view count: the entry point below says which
+    g = int(logits.shape[0]) // max(views, 1)
+    for name, t in (("loss", loss), ("entropy", entropy), ("consistency", consistency)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < g:
+            raise MmttaError(f"modcons_loss_items: {name} must be contiguous fp32 with one slot per volume")
+    if view_kl.dtype != torch.float32 or not view_kl.is_contiguous() or view_kl.numel() < g * (views - 1):
+        raise MmttaError("modcons_loss_items: view_kl must be contiguous fp32 [volumes, views - 1]")
+    if disagree.dtype != torch.int64 or not disagree.is_contiguous() or disagree.numel() < g * (views - 1):
+        raise MmttaError("modcons_loss_items: disagree must be contiguous int64 [volumes, views - 1]")
+    if partial.dtype != torch.float64 or partial.numel() < need:
+        raise MmttaError("modcons_loss_items: partial must be fp64 of modcons_partials(logits, views) elements")
+    tz, tg = desc_cl(logits), desc_cl(dlogits)
+    check(_lib.load().mmtta_modcons_loss_items(C.byref(tz), 1 if softmax else 0, views, float(weight), float(entropy_weight),
+                                               1 if detach else 0, C.byref(tg), ptr(partial), ptr(loss), ptr(entropy),
+                                               ptr(consistency), ptr(view_kl), ptr(disagree), stream_ptr()), "modcons_loss_items")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 
