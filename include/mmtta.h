@@ -734,6 +734,54 @@ int mmtta_cotta_update_sets(float* w, float* teacher, const float* source, int64
                             int64_t teacher_stride, double alpha, float restore_p, uint64_t seed, const int32_t* step,
                             const int32_t* ordinals, int64_t* partial, int64_t* restored, void* stream);
 
+/* ---- Affine (rotate / scale / shift) teacher views of CoTTA and PETAL - csrc/affine.hip.  The views of a volume are
+ * `first` coded views (mmtta_memo_ensemble's mirror / turn codes, view 0 = the volume itself) followed by `count` affine
+ * views, views = first + count, 2 <= views <= 8, first >= 1, count >= 1; item g * views + v of a batch is view v of volume
+ * g.  The teacher's predictions take no gradient, so both directions are gathers: no adjoint, no scatter, no atomics.
+ *
+ * A matrix is 12 fp32 numbers, row-major 3 x 4.  For the voxel (d, h, w) a thread owns, the sampled coordinate of axis k is
+ *     p_k = fmaf(m[4k], d, fmaf(m[4k + 1], h, fmaf(m[4k + 2], w, m[4k + 3])))          (fp32, this order)
+ * and "trilinear", for both entry points, is: with f = floor(p_k), t = p_k - f per axis, corner f weighs 1 - t and corner
+ * f + 1 weighs t; the value is the sum over the 8 corners f + {0, 1}^3 that lie INSIDE the tensor of (w_d * w_h) * w_w times
+ * the corner's value, accumulated with fmaf in the order 000, 001, .. 111 of (d, h, w); corners outside contribute 0 (and
+ * every corner does once an axis has p_k outside (-1, extent) or not finite); a corner of weight 0 is not read.  Up to
+ * rounding this is torch.nn.functional.grid_sample(mode = "bilinear", padding_mode = "zeros", align_corners = True) on
+ * 5-D input.  The coordinates are VOXEL coordinates: a rotation does not account for anisotropic spacing.
+ *
+ * mmtta_affine_views: x [G, D, H, W, C], y [G * views, D, H, W, C], channels-last dense rows of one width, both fp32 or both
+ *   bf16 (the 8-byte bf16 voxel rows of the network input included).  `matrices` is DEVICE fp32 [G, count, 12], matrix
+ *   (g, j) maps a voxel of view first + j to the coordinate of x[g] it samples; `matrices_host` is its HOST copy, read at
+ *   launch for the argument checks.  Writes items g * views + first + j, j < count, as the trilinear resample of x[g]; the
+ *   other items of y are not touched.  A thread owns one output voxel row (rows wider than 4 lanes: a quad of it; rows no
+ *   16- / 8-byte access fits: a lane): 8 row gathers, fp32 arithmetic, one store; the pad lanes (y must own them) take 0;
+ *   bf16 output is the fp32 result rounded to nearest even.  An identity matrix reproduces x by value, an integer
+ *   translation is the exact shift with zero fill.
+ *
+ * mmtta_affine_ensemble: logits [G * views, D, H, W, R] fp32, every view in its own frame; out [G, D, H, W, R] fp32 in the
+ *   volume's frame.  `view_axes` is a HOST array of `views` codes: views < first carry mirror / turn codes with
+ *   mmtta_memo_ensemble's meaning (view_axes[0] == 0) and are read through the exact coordinate map, views >= first must
+ *   carry 0.  `inv` is DEVICE fp32 [G, count, 12], matrix (g, j) maps a voxel of the volume's frame to the coordinate of
+ *   view first + j that shows it (the inverse of mmtta_affine_views' matrix); `inv_host` is its HOST copy.  Probabilities are
+ *   interpolated, not logits; tri() is the trilinear value above:
+ *     softmax == 0:  P = sum_coded sigmoid(u_v) + sum_affine tri(sigmoid(z_v)),  Q = the same sums of sigmoid(-.),
+ *                    out = log P - log Q held inside +-87.3365; 1 - p is never formed by subtraction, and the common
+ *                    denominator (first + the coverages) cancels
+ *     softmax != 0:  P_r = the same sums of the softmax rows,  Wt = first + sum_affine (sum of the inside corners' weights),
+ *                    out_r = log(P_r / Wt), held at -3e38 from below
+ *   A frame voxel whose image falls outside an affine view is predicted by the remaining views alone (view 0 always
+ *   covers).  Paths: R <= 4 in dense 16-byte rows with `out` owning its pad lanes (they take 0; a thread owns a voxel), any
+ *   R and strides (sigmoid head; a thread owns a (voxel, region) pair), up to 16 classes (softmax head).  G volumes in one
+ *   call are bit for bit G calls on one volume each.
+ *
+ * Bad arguments (null pointers, views outside 2 .. 8, count < 1, first < 1, first + count != views, N no multiple of views,
+ * a code != 0 on an affine view or an invalid code on a coded one, a code with bit 4 at h != w, an extent < 2, a
+ * non-finite matrix entry, shape mismatches) are MMTTA_ERR_INVALID, storages without a kernel (an item of 2^31 elements or
+ * more, more than 65535 items along the grid) MMTTA_ERR_UNSUPPORTED, both before anything is launched. */
+int mmtta_affine_views(const mmtta_tensor* x, const mmtta_tensor* y, int views, int first, int count,
+                       const float* matrices_host, const float* matrices, void* stream);
+int mmtta_affine_ensemble(const mmtta_tensor* logits, int softmax, int views, const int32_t* view_axes, int first, int count,
+                          const float* inv_host, const float* inv, const mmtta_tensor* out, void* stream);
+
 /* ---- PETAL (Brahma & Rai, CVPR 2023): the restore of CoTTA's pass above, ranked by the step's own gradient - csrc/petal.hip.
  * The magnitude key of a gradient element is key(g) = bits(g) & 0x7fffffff, an unsigned integer: a total order over zeros
  * (+0 == -0), denormals, infinities and NaNs (above the infinities) that no float comparison mode changes.

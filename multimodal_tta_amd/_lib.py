@@ -190,6 +190,9 @@ _SIGNATURES = {
     "mmtta_memo_loss_items": (C.c_int, [_P(Tensor), C.c_int, C.c_int, _P(C.c_int32), _P(Tensor), C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     "mmtta_memo_ensemble": (C.c_int, [_P(Tensor), C.c_int, C.c_int, _P(C.c_int32), _P(Tensor), C.c_void_p]),
+    "mmtta_affine_views": (C.c_int, [_P(Tensor), _P(Tensor), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_affine_ensemble": (C.c_int, [_P(Tensor), C.c_int, C.c_int, _P(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        _P(Tensor), C.c_void_p]),
     "mmtta_consistency_partials": (C.c_int64, [_P(Tensor)]),
     "mmtta_consistency_loss_items": (C.c_int, [_P(Tensor), _P(Tensor), C.c_int, _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_cotta_update_partials": (C.c_int64, [C.c_int64, C.c_int]),

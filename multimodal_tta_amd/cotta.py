@@ -30,7 +30,9 @@ same volumes served one at a time.
 
 Where this differs from the paper: the views are the mirror group and quarter turns in the (H, W) plane
 (``method.cotta.mirror_axes``, ``method.cotta.rot90``, ``memo_tta``'s views: the augmentations whose inverse is exact on the
-voxel grid), not colour / affine augmentations; the teacher always averages
+voxel grid) and, with ``method.cotta.affine`` (``affine.py``: off as shipped), small rotations / zooms / shifts that are
+resampled - the teacher's predictions take no gradient, so such a view is a gather forward (``ops.affine_views``) and a
+gather back (``ops.affine_ensemble`` in place of ``ops.memo_ensemble``) - not AugMix or colour jitter; the teacher always averages
 its views (the paper's confidence-gated switch between one and 32 views is not built); the elements are voxels (or voxel x
 region pairs), not images; the restore draw is per element of the flat trainable span, not per tensor.
 
@@ -49,6 +51,7 @@ from typing import Any, Dict, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .affine import check_extents, parse_affine
 from .config import as_cfg, get_config
 from .intensity import parse_intensity
 from .memo import check_square, parse_mirror_axes, parse_rot90
@@ -59,7 +62,7 @@ from .tta import EntropyMinimizationTTA, modality_mask
 @register_plugin("cotta_tta")
 class MeanTeacherTTA(EntropyMinimizationTTA):
     """``method.cotta.mirror_axes`` (default [h, w]: 4 teacher views), ``rot90`` (default {k: []}), ``alpha`` (teacher momentum, default 0.999),
-    ``restore_p`` (default 0.01) and ``seed`` (default 0); the optimizer is ``training.optimizer`` exactly as for
+    ``restore_p`` (default 0.01), ``seed`` (default 0) and ``affine`` (default {views: 0}: ``affine.py``); the optimizer is ``training.optimizer`` exactly as for
     ``entmin_tta``."""
     fused_update = False     # one gradient for the whole span, then the teacher / restore pass over it
     block = "cotta"          # the ``method.<block>`` mapping the keys are read from (a subclass reads its own)
@@ -74,6 +77,11 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, f"{key}.intensity", self.rot90)
         # ({identity} + the quarter turns) x the mirror group, ``intensity.copies`` times over
         self.view_axes = self.intensity.view_axes
+        # ... followed by the affine views of ``affine.views`` (code 0; with the default 0 nothing of affine.py runs)
+        self.affine = parse_affine(get_config(s, "affine", None), len(self.view_axes), f"{key}.affine")
+        self.coded_views = len(self.view_axes)
+        if self.affine.active:
+            self.view_axes = list(self.view_axes) + [0] * self.affine.views
         self.views = len(self.view_axes)
         alpha, p, seed = get_config(s, "alpha", 0.999), get_config(s, "restore_p", 0.01), get_config(s, "seed", 0)
         if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not (0.0 <= float(alpha) <= 1.0):
@@ -96,6 +104,9 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
                 f"{self.block}_tta: model.norm = {get_config(get_config(self.cfg, 'model', {}) or {}, 'norm', 'BATCH')!r} keeps running "
                 "statistics, which the teacher's train-mode forward would move (running_mean, running_var, "
                 "num_batches_tracked belong to the student); use a model.norm without them (INSTANCE, GROUP)")
+        if self.affine.active and hasattr(rt, "stage_family"):
+            raise NotImplementedError(f"method.{self.block}.affine.views = {self.affine.views}: affine views are not built for the "
+                                      "deep-fusion network (its family batch is staged from the views)")
         self.teacher = torch.empty((ar.replicas, ar.n_train), dtype=torch.float32, device=ar.device)
         self._setup_ordinals()          # the restore draw's (and the intensity views') per-volume numbers
         self.reset_teacher()
@@ -126,7 +137,11 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         zv = self._forward(xv, present)
         n, d, h, w, r = zv.shape
         target = rt.pool.cl("cotta_target", B, d, h, w, r, ldc=(r + 3) // 4 * 4)
-        ops.memo_ensemble(zv, target, self.view_axes, softmax=self.softmax)
+        if self.affine.active:
+            inv = rt.pool.flat("affine_inv", B * self.affine.views * 12)          # uploaded by stage_views, per volume
+            ops.affine_ensemble(zv, target, self.view_axes, self.coded_views, rt.affine_inv_host, inv, softmax=self.softmax)
+        else:
+            ops.memo_ensemble(zv, target, self.view_axes, softmax=self.softmax)
         # 2. the student on the volume alone
         if nt > 0:
             ar.params_all[:sets, :nt].copy_(saved[:sets])
@@ -160,12 +175,18 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
 
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
         check_square(self.view_axes, int(x_cl.shape[2]), int(x_cl.shape[3]), f"method.{self.block}.rot90")
+        if self.affine.active:
+            check_extents(x_cl.shape[1:4], f"method.{self.block}.affine")
         self.rt.views = self.views
-        if self.intensity.active and self.views > 1:
+        coded = self.view_axes[:self.coded_views]
+        affine = self.affine if self.affine.active else None
+        if self.intensity.active and self.coded_views > 1:
             present = modality_mask(int(x_cl.shape[-1]), self.missing, 0.0, None)
-            xv = self.rt.stage_views(x_cl, self.view_axes, self.intensity, self._ordinals_host, present)
+            xv = self.rt.stage_views(x_cl, coded, self.intensity, self._ordinals_host, present, affine=affine)
+        elif affine is not None:
+            xv = self.rt.stage_views(x_cl, coded, ordinals=self._ordinals_host, affine=affine)
         else:
-            xv = self.rt.stage_views(x_cl, self.view_axes)
+            xv = self.rt.stage_views(x_cl, coded)
         self.rt.views = 1          # the loop runs on the volumes; the step switches to the views for the teacher
         return x_cl, (xv,)
 

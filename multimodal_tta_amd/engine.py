@@ -806,21 +806,54 @@ class Runtime:
         return x_cl
 
     def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int], intensity=None,
-                    ordinals: Optional[Sequence[int]] = None, present: Optional[Sequence[bool]] = None) -> torch.Tensor:
+                    ordinals: Optional[Sequence[int]] = None, present: Optional[Sequence[bool]] = None,
+                    affine=None) -> torch.Tensor:
         """The staged input [G,D,H,W,C] -> its views as batch items [G * V,D,H,W,C] (item g * V + v = volume g under the
         code view_axes[v]: bit 4 = H and W transposed, then mirrored along the axes of bits 0-2; ops.mirror_views), in the
         storage of the staged input.  A code with bit 4 needs H == W (ValueError before any launch).  ``intensity``
         (an active ``intensity.IntensitySpec``): every view v >= 1 also takes its intensity transform, drawn for the
         per-volume numbers ``ordinals`` (one per volume) with the channels ``present`` marks absent left alone - the
-        channels' ranges, the parameter table's upload, then ops.augment_views in place of the mirror pass."""
+        channels' ranges, the parameter table's upload, then ops.augment_views in place of the mirror pass.
+
+        ``affine`` (an active ``affine.AffineSpec``): V = len(view_axes) + affine.views; items [g * V, g * V + len(view_axes))
+        are, bit for bit, what staging without it gives for volume g (the pass above, once per volume on that slice), the
+        rest the trilinear resamples of ops.affine_views under the matrices drawn for ``ordinals``.  The matrices and their
+        inverses sit in pool buffers (``affine_m`` / ``affine_inv``, fixed addresses: a replayed graph reads the current
+        volume's), uploaded here; ``self.affine_inv_host`` keeps the inverses' host copy for ops.affine_ensemble."""
         n, d, h, w, c = x_cl.shape
         if h != w and any(int(a) & 16 for a in view_axes):
             raise ValueError(f"stage_views: view_axes {list(view_axes)} transpose H and W (bit 4, an odd quarter turn), which "
                              f"needs H == W; the volume has H = {h}, W = {w}")
-        xv = self.pool.cl("x_views", n * len(view_axes), d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=x_cl.dtype)
+        if affine is None or not affine.active:
+            xv = self.pool.cl("x_views", n * len(view_axes), d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=x_cl.dtype)
+            self._fill_views(x_cl, xv, view_axes, intensity, ordinals, present)
+            return xv
+        from .affine import view_matrices
+        if ordinals is None or len(ordinals) != n:
+            raise ValueError(f"stage_views: affine views need one ordinal per volume, got {ordinals!r} for {n} volumes")
+        coded, V = len(view_axes), len(view_axes) + affine.views
+        m_host, inv_host = (torch.from_numpy(a) for a in view_matrices(affine, ordinals, (d, h, w)))
+        xv = self.pool.cl("x_views", n * V, d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=x_cl.dtype)
+        for g in range(n):
+            part = xv[g * V:g * V + coded]
+            part._mmtta_owns_pad = getattr(xv, "_mmtta_owns_pad", False)          # whole rows of whole items: the pad comes along
+            self._fill_views(x_cl[g:g + 1], part, view_axes, intensity, None if ordinals is None else ordinals[g:g + 1], present)
+        m = self.pool.flat("affine_m", m_host.numel())
+        inv = self.pool.flat("affine_inv", inv_host.numel())
+        m.copy_(m_host.reshape(-1))
+        inv.copy_(inv_host.reshape(-1))
+        self.affine_inv_host = inv_host
+        ops.affine_views(x_cl, xv, coded, m_host, m)
+        return xv
+
+    def _fill_views(self, x_cl: torch.Tensor, xv: torch.Tensor, view_axes: Sequence[int], intensity,
+                    ordinals: Optional[Sequence[int]], present: Optional[Sequence[bool]]) -> None:
+        """The coded views of the volumes ``x_cl`` into ``xv`` [len(x_cl) * len(view_axes), ...]: the mirror pass, or with an
+        active ``intensity`` the augment pass (``stage_views``)."""
+        n, c = int(x_cl.shape[0]), int(x_cl.shape[4])
         if intensity is None or not intensity.active:
             ops.mirror_views(x_cl, xv, view_axes)
-            return xv
+            return
         from .intensity import view_parameters
         if ordinals is None or len(ordinals) != n:
             raise ValueError(f"stage_views: intensity views need one ordinal per volume, got {ordinals!r} for {n} volumes")
@@ -835,7 +868,6 @@ class Runtime:
         ords = self.pool.flat("aug_ordinals", n, dtype=torch.int32)
         ords.copy_(torch.from_numpy(np.array([int(o) for o in ordinals], dtype=np.uint32).view(np.int32)))
         ops.augment_views(x_cl, xv, view_axes, table_host, table, value_range, intensity.seed, ords)
-        return xv
 
     def input_dtype(self) -> torch.dtype:
         """Storage of the staged network input.  Runtimes whose every reader of the input rounds it to bf16 while staging

@@ -326,9 +326,13 @@ class DeepFusionRuntime(Runtime):
         return x_cl
 
     def stage_views(self, x_cl: torch.Tensor, view_axes: Sequence[int], intensity=None,
-                    ordinals: Optional[Sequence[int]] = None, present: Optional[Sequence[bool]] = None) -> torch.Tensor:
+                    ordinals: Optional[Sequence[int]] = None, present: Optional[Sequence[bool]] = None,
+                    affine=None) -> torch.Tensor:
         """The mirrored (and, with ``intensity``, intensity-augmented) views of the staged volume, and the family batch
-        [n * V * M, D, H, W, 1] of those views."""
+        [n * V * M, D, H, W, 1] of those views.  Affine views are not built for this network."""
+        if affine is not None and affine.active:
+            raise NotImplementedError("affine.views > 0: affine views are not built for the deep-fusion network (its family "
+                                      "batch is staged from the views)")
         xv = super().stage_views(x_cl, view_axes, intensity, ordinals, present)
         n, D, H, W, M = xv.shape
         xm = self.pool.cl("xm", n * M, D, H, W, 1, ldc=4, zero=True)

@@ -977,6 +977,41 @@ def memo_ensemble(logits: torch.Tensor, out: torch.Tensor, view_axes: Sequence[i
                                           stream_ptr()), "memo_ensemble")
 
 
+def _affine_matrices(what: str, host: torch.Tensor, dev: torch.Tensor, volumes: int, count: int) -> None:
+    n = volumes * count * 12
+    for name, t, cuda in (("the device matrices", dev, True), ("their host copy", host, False)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.is_cuda != cuda:
+            raise MmttaError(f"{what}: {name} must be contiguous fp32 [{volumes}, {count}, 12] on the "
+                             f"{'device' if cuda else 'host'}, got {tuple(t.shape)} {t.dtype} {t.device}")
+
+
+def affine_views(x: torch.Tensor, y: torch.Tensor, first: int, matrices_host: torch.Tensor, matrices: torch.Tensor) -> None:
+    """y[g * V + first + j] = the trilinear resample of x[g] under matrix (g, j) (``affine.py``: a view voxel -> the frame
+    coordinate it samples; corners outside contribute 0): channels-last [G,D,H,W,C] -> [G*V,D,H,W,C], fp32 or bf16 rows, pad
+    lanes 0.  ``matrices`` device fp32 [G, count, 12], ``matrices_host`` its host copy; V = first + count.  The items below
+    ``first`` are not touched."""
+    g, v = int(x.shape[0]), int(y.shape[0]) // max(int(x.shape[0]), 1)
+    count = v - int(first)
+    _affine_matrices("affine_views", matrices_host, matrices, g, max(count, 0))
+    tx, ty = desc_cl(x), desc_cl(y)
+    check(_lib.load().mmtta_affine_views(C.byref(tx), C.byref(ty), v, int(first), count, ptr(matrices_host), ptr(matrices),
+                                         stream_ptr()), "affine_views")
+
+
+def affine_ensemble(logits: torch.Tensor, out: torch.Tensor, view_axes: Sequence[int], first: int, inv_host: torch.Tensor,
+                    inv: torch.Tensor, softmax: bool = False) -> None:
+    """``memo_ensemble`` over ``first`` coded views (``view_axes[:first]``) followed by affine views (code 0): out [G,D,H,W,R]
+    = logit (sigmoid head) or log (softmax head) of the coverage-weighted mean of the predicted probabilities in the volume's
+    frame; an affine view's probabilities come back through the trilinear gather under ``inv`` (device fp32 [G, count, 12]:
+    a frame voxel -> the view coordinate that shows it; ``inv_host`` its host copy)."""
+    v = len(view_axes)
+    count = v - int(first)
+    _affine_matrices("affine_ensemble", inv_host, inv, int(out.shape[0]), max(count, 0))
+    tz, to = desc_cl(logits), desc_cl(out)
+    check(_lib.load().mmtta_affine_ensemble(C.byref(tz), 1 if softmax else 0, v, _view_axes(view_axes), int(first), count,
+                                            ptr(inv_host), ptr(inv), C.byref(to), stream_ptr()), "affine_ensemble")
+
+
 def consistency_partials(logits: torch.Tensor) -> int:
     t = desc_cl(logits)
     return int(_lib.load().mmtta_consistency_partials(C.byref(t)))
