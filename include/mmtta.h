@@ -211,6 +211,19 @@ int mmtta_abi_version(void);
  * same order: outputs and rows equal bit for bit.  mmtta_conv_thin_lean tells which form a call takes.  A call with a
  * LeakyReLU on x or on the fused add keeps the plain kernels.  Returns the previous value. */
 #define MMTTA_OPT_THIN_LEAN 18
+/* 1 (default): a fused weight update (mmtta_conv_wgrad_update_sets) whose weight gradient plans ONE slab per parameter set
+ * steps the optimizer in the epilogue of the transposed-read weight-gradient kernel (csrc/conv_wgrad.hip:
+ * wgrad_tr_upd_kernel): the workgroup that holds the complete gradient of a 27 x 32 x 32 block in its registers runs the
+ * optimizer on p / m / v and writes both bf16 images, so the slab is neither written nor read back and
+ * wgrad_update27_kernel is not launched.  The bias is stepped there too.
+ * Taken by a stride-1 3x3x3 Conv3d of bf16 precision with x and dy bf16-stored, cin and cout multiples of 32, one dense
+ * column block per workgroup (cout > 128, or an odd number of 32-channel blocks), no pre-reduce, p / m / v of every set on
+ * 16 bytes, outside the LeakyReLU instantiation.  The stride-2 forms (Conv3d and ConvTranspose3d) were measured slower than
+ * their two launches (profiles/update_epilogue_ab.md) and are not built.  Everything else, and 0, takes the two launches as
+ * before, in the same process.  The same sums, optimizer arithmetic and rounding: p, m, v, the bias and both images equal
+ * bit for bit.  Workspace sizes and plans do not depend on it.
+ * mmtta_conv_wgrad_updates_in_epilogue tells whether a call qualifies.  Returns the previous value. */
+#define MMTTA_OPT_WGRAD_EPILOGUE_UPDATE 19
 int mmtta_set_option(int key, int value);
 
 /* ------------------------------------------------------------------ layout (boundary) ---- */
@@ -1220,6 +1233,11 @@ int mmtta_fused_update_enabled(void);
 int mmtta_conv_wgrad_update_sets(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                  const mmtta_tensor* dy, const mmtta_update_target* target, void* workspace,
                                  int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);
+/* Whether mmtta_conv_wgrad_update_sets would step the optimizer in the epilogue of this call's weight-gradient kernel
+ * (MMTTA_OPT_WGRAD_EPILOGUE_UPDATE): 1 / 0, or a negative mmtta error code.  Host-only, the predicate the launcher itself
+ * asks; the launcher also needs p / m / v of every set on 16 bytes, which a query without a target cannot see. */
+int mmtta_conv_wgrad_updates_in_epilogue(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                         const mmtta_tensor* dy, const mmtta_param_sets* sets);
 
 /* mmtta_optim_step_sets over a table of segments of every replica (the parameters a fused weight-gradient update does not
  * cover).  `segments` is a DEVICE int64 table: `count` rows (start, length, decay) relative to a replica, start and length

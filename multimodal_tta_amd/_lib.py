@@ -255,6 +255,7 @@ _SIGNATURES = {
     "mmtta_fused_update_enabled": (C.c_int, []),
     "mmtta_conv_wgrad_update_sets": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(Tensor), _P(UpdateTarget),
                                                C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
+    "mmtta_conv_wgrad_updates_in_epilogue": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(Tensor), _P(ParamSets)]),
     "mmtta_sam_ascent_partials": (C.c_int64, [C.c_int64, C.c_int]),
     "mmtta_sam_ascent_sets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                         C.c_int64, C.c_float, C.c_void_p]),
@@ -327,6 +328,8 @@ def load() -> C.CDLL:
         lib.mmtta_set_option(17, int(os.environ["MMTTA_HEADLOSS"]))
     if "MMTTA_THINLEAN" in os.environ:                   # A/B aid: MMTTA_OPT_THIN_LEAN (same results bit for bit)
         lib.mmtta_set_option(18, int(os.environ["MMTTA_THINLEAN"]))
+    if "MMTTA_EPIUPDATE" in os.environ:                  # A/B aid: MMTTA_OPT_WGRAD_EPILOGUE_UPDATE (same results bit for bit)
+        lib.mmtta_set_option(19, int(os.environ["MMTTA_EPIUPDATE"]))
     _lib = lib
     return lib
 

@@ -463,6 +463,35 @@ __device__ __forceinline__ void upd_optim4(const UpdArgs& u, long long ob, long 
   }
 }
 
+// repack phase: one image from the updated tile, pack_tile's index map and rounding (positions outside the weight hold 0,
+// as there).  One text for wgrad_update27_kernel and the transposed-read kernels that update in their epilogue.  (The image
+// by value and the loop over the two at the call site: wgrad_update27_kernel keeps its registers that way.)
+__device__ __forceinline__ void upd_repack(const UpdImage im, const PSets& ps, int q, int cg0, int cd0, const float* tile) {
+  if (im.p == nullptr) return;
+  unsigned short* img = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(im.p) + (ps.inner == 1
+      ? q * im.outer : (q / ps.inner) * im.outer + (q % ps.inner) * im.inner));
+  const long long tslab = (long long)im.Kp * im.Np;
+  if (im.kn_is_ba) {
+    // k = cg (one group of 8), n = cd (32 columns): 27 x 32 runs of 16 bytes
+    for (int o = threadIdx.x; o < 27 * UPD_CD; o += 256) {
+      const int nn = o % UPD_CD, tp = o / UPD_CD;
+      unsigned short h[8];
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) h[kk] = f32_to_bf16_bits(tile[nn * UPD_RS + kk * 27 + tp]);
+      *reinterpret_cast<uint4*>(img + tp * tslab + ((long long)(cg0 >> 3) * im.Np + cd0 + nn) * 8) = bf16x8_pack(h);
+    }
+  } else {
+    // k = cd (four groups of 8), n = cg (8 columns)
+    for (int o = threadIdx.x; o < 27 * 4 * UPD_CG; o += 256) {
+      const int c = o % UPD_CG, k8 = (o / UPD_CG) % 4, tp = o / (UPD_CG * 4);
+      unsigned short h[8];
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) h[kk] = f32_to_bf16_bits(tile[(k8 * 8 + kk) * UPD_RS + c * 27 + tp]);
+      *reinterpret_cast<uint4*>(img + tp * tslab + ((long long)((cd0 >> 3) + k8) * im.Np + cg0 + c) * 8) = bf16x8_pack(h);
+    }
+  }
+}
+
 __device__ __forceinline__ bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <int KIND>
@@ -567,34 +596,9 @@ __global__ __launch_bounds__(256) void wgrad_update27_kernel(const float* __rest
     }
   }
   __syncthreads();
-  // ---- repack: both images, pack_tile's index map and rounding (positions outside the weight hold 0, as there)
+  // ---- repack: both images
 #pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const UpdImage im = u.img[m];
-    if (im.p == nullptr) continue;
-    unsigned short* img = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(im.p) + (ps.inner == 1
-        ? q * im.outer : (q / ps.inner) * im.outer + (q % ps.inner) * im.inner));
-    const long long tslab = (long long)im.Kp * im.Np;
-    if (im.kn_is_ba) {
-      // k = cg (one group of 8), n = cd (32 columns): 27 x 32 runs of 16 bytes
-      for (int o = threadIdx.x; o < 27 * UPD_CD; o += 256) {
-        const int nn = o % UPD_CD, tp = o / UPD_CD;
-        unsigned short h[8];
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) h[kk] = f32_to_bf16_bits(tile[nn * UPD_RS + kk * 27 + tp]);
-        *reinterpret_cast<uint4*>(img + tp * tslab + ((long long)(cg0 >> 3) * im.Np + cd0 + nn) * 8) = bf16x8_pack(h);
-      }
-    } else {
-      // k = cd (four groups of 8), n = cg (8 columns)
-      for (int o = threadIdx.x; o < 27 * 4 * UPD_CG; o += 256) {
-        const int c = o % UPD_CG, k8 = (o / UPD_CG) % 4, tp = o / (UPD_CG * 4);
-        unsigned short h[8];
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) h[kk] = f32_to_bf16_bits(tile[(k8 * 8 + kk) * UPD_RS + c * 27 + tp]);
-        *reinterpret_cast<uint4*>(img + tp * tslab + ((long long)((cd0 >> 3) + k8) * im.Np + cg0 + c) * 8) = bf16x8_pack(h);
-      }
-    }
-  }
+  for (int m = 0; m < 2; ++m) upd_repack(u.img[m], ps, q, cg0, cd0, tile);
 }
 
 __global__ __launch_bounds__(256) void wgrad_reduce1_kernel(const float* __restrict__ slab, float* __restrict__ dw,
@@ -722,9 +726,16 @@ typedef __attribute__((address_space(3))) wshort4* wlds4_t;
 // NB = 2: ONE workgroup multiplies the gathered box with two 32-channel blocks of the dense operand (14 accumulator blocks:
 // one workgroup per CU).  The stride-2 layers stage a box of 12x the tile's voxels for 28 MFMAs a wave - the staging (vector
 // ALU, L2) is their cost, and every dense column block used to repeat it (conv 32->64 at 64^3: 2x, convT 128->32: 4x).
+// (the kernels that write slabs: the body's one UPD site is discarded, and names these only)
+#define MMTTA_TR_NO_UPDATE    \
+  constexpr bool UPD = false; \
+  constexpr int KIND = 0;     \
+  constexpr UpdArgs u{};      \
+  constexpr PSets ps{};
 template <int TZ, int TY, int SI, bool GBF, bool DBF, bool TD, int NB = 1>
 __global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_kernel(WArgs a) {
   constexpr bool RG = false, RD = false;
+  MMTTA_TR_NO_UPDATE
 #include "conv_wgrad_tr_body.h"
 }
 
@@ -735,6 +746,20 @@ __global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_ke
 template <int TZ, int TY, int SI, bool TD, int NB, bool RG, bool RD>
 __global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_raw_kernel(WArgs a) {
   constexpr bool GBF = true, DBF = true;
+  MMTTA_TR_NO_UPDATE
+#include "conv_wgrad_tr_body.h"
+}
+
+// The update in the epilogue (MMTTA_OPT_WGRAD_EPILOGUE_UPDATE; host: wgrad_updates_in_epilogue) of the all-bf16 forms: a
+// launch that plans ONE slab per parameter set has the complete gradient of a 27 x 32 cg x 32 NB cd block in the registers
+// of one workgroup, so the kernel steps the optimizer on p / m / v and writes both bf16 images itself (upd_optim4 and
+// upd_repack on wgrad_update27_kernel's LDS tile, 8 cg at a time) - no slab write, no read-back, no second launch, and the
+// optimizer's streaming of a finished workgroup runs under the MFMA phases of the others.  RG / RD as in wgrad_tr_raw_kernel
+// (both false: the transform form).  The same body text with UPD set; launched from the plain translation unit only, and
+// only as the stride-1 one-block transform form (wgrad_updates_in_epilogue says why).
+template <int TZ, int TY, int SI, bool TD, int NB, bool RG, bool RD, int KIND>
+__global__ __launch_bounds__(256, (NB == 1 && SI == 1) ? 2 : 1) void wgrad_tr_upd_kernel(WArgs a, UpdArgs u, PSets ps) {
+  constexpr bool GBF = true, DBF = true, UPD = true;
 #include "conv_wgrad_tr_body.h"
 }
 
@@ -975,6 +1000,37 @@ static int launch_wgrad_tr(const WArgs& a, int S, hipStream_t s, int ncb = 1, in
   if (a.d_bf) return launch_wgrad_tr_t<TZ, TY, SI, true, true, false>(a, S, s);
   if (a.g_bf) return launch_wgrad_tr_t<TZ, TY, SI, true, false, false>(a, S, s);
   return launch_wgrad_tr_t<TZ, TY, SI, false, false, false>(a, S, s);
+}
+
+// The kernel that updates in its epilogue (wgrad_tr_upd_kernel): only the form wgrad_updates_in_epilogue admits is built -
+// stride 1, one column block, transform staging - for Adam, AdamW and SGD; none in the LeakyReLU translation unit.
+#ifdef MMTTA_ACT_LEAKY_TU
+constexpr bool WGRAD_UPD_KERNELS = false;
+#else
+constexpr bool WGRAD_UPD_KERNELS = true;
+#endif
+template <int TZ, int TY, int SI, bool TD, int NB, bool RG, bool RD>
+static int launch_wgrad_tr_upd_t(const WArgs& a, const UpdArgs& u, const PSets& ps, int kind, int S, hipStream_t s) {
+  using G = WTGeo<TZ, TY, SI>;
+  static_assert(G::lds_bytes(NB) >= (int)((UPD_CD * UPD_RS + 2) * sizeof(float)), "the update tile and its two scalars fit the images");
+  static constexpr void (*kinds[3])(WArgs, UpdArgs, PSets) = {      // KIND = mmtta_optim_desc.kind (checked)
+      wgrad_tr_upd_kernel<TZ, TY, SI, TD, NB, RG, RD, MMTTA_OPTIM_ADAM>, wgrad_tr_upd_kernel<TZ, TY, SI, TD, NB, RG, RD, MMTTA_OPTIM_ADAMW>,
+      wgrad_tr_upd_kernel<TZ, TY, SI, TD, NB, RG, RD, MMTTA_OPTIM_SGD>};
+  static bool attr_set = false;
+  if (!attr_set) {
+    for (int k = 0; k < 3; ++k) (void)hipFuncSetAttribute((const void*)kinds[k], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
+  }
+  dim3 grid(S, a.CGp / 32, a.CDp / 32 / NB);
+  hipLaunchKernelGGL(kinds[kind], grid, dim3(256), G::lds_bytes(NB), s, a, u, ps);
+  return launch_status("conv wgrad bf16 (transposed reads, update in the epilogue)");
+}
+
+template <int TZ, int TY>
+static int launch_wgrad_tr_upd_s1(const WArgs& a, const UpdArgs& u, const PSets& ps, int kind, int S, hipStream_t s) {
+  if constexpr (WGRAD_UPD_KERNELS) return launch_wgrad_tr_upd_t<TZ, TY, 1, false, 1, false, false>(a, u, ps, kind, S, s);
+  set_error("wgrad: no kernel updates in its epilogue in this translation unit");
+  return MMTTA_ERR_UNSUPPORTED;
 }
 
 // ------------------------------------------------------------------ small-channel weight gradient
@@ -2048,8 +2104,34 @@ static int wgrad_raw_bits(const WGeo& w, const mmtta_norm_on_load* x_norm) {
   return 2 | ((ident && xin->c % 8 == 0) ? 1 : 0);
 }
 
+// The update in the epilogue of wgrad_tr_kernel's twins (MMTTA_OPT_WGRAD_EPILOGUE_UPDATE): what a fused-update call must be
+// for one workgroup to hold the complete gradient of its block and for upd_optim4's 16-byte form to apply to every tile of
+// it.  One slab per set and no pre-reduce; both tensors bf16-stored (the all-bf16 forms are the ones built); whole cg groups
+// of 8 in every 32-row block and parameter rows of a multiple of 4 floats (Cg % 32 == 0); dense channels that fill the
+// workgroup's column block; the form that is built: a stride-1 convolution with one column block per workgroup.  The
+// stride-2 forms (paired column blocks, Conv3d and ConvTranspose3d, transform and raw staging) were built and measured
+// slower than their two launches - they run 128 to 384 workgroups of one per CU, and a workgroup's optimizer rounds have
+// nothing to overlap with (profiles/update_epilogue_ab.md) - so they are left out and the query says 0 for them.
+// The one function behind mmtta_conv_wgrad_updates_in_epilogue and the launcher.
+static bool wgrad_updates_in_epilogue(const WGeo& w) {
+  if (!WGRAD_UPD_KERNELS || !g_wgrad_epilogue_update) return false;
+  if (w.route != W_TR_S1 || w.convt || w.ncb != 1) return false;
+  if (w.nsl != 1 || w.pre_chunks != 0) return false;
+  if (!is_bf16(w.g) || !is_bf16(w.dn)) return false;
+  return w.g->c % 32 == 0 && w.dn->c % 32 == 0;
+}
+// ... and of the target: p / m / v of every set start on 16 bytes (the images are checked by check_update_target)
+static bool update_target_vec16(const mmtta_update_target* upd, const PSets& ps, int nsets) {
+  const bool keep_m = upd->optim.kind != MMTTA_OPTIM_SGD || upd->optim.momentum != 0.f;
+  auto al = [](const void* p) { return p != nullptr && ((uintptr_t)p & 15) == 0; };
+  if (!al(upd->w_p) || (keep_m && !al(upd->w_m)) || (upd->optim.kind != MMTTA_OPTIM_SGD && !al(upd->w_v))) return false;
+  if (nsets > 1 && (ps.weight_outer % 4 != 0 || (ps.inner != 1 && ps.weight_inner % 4 != 0))) return false;
+  return true;
+}
+
+// `ua` (with `ps`, `kind`): the call updates in the main kernel's epilogue (wgrad_updates_in_epilogue said so)
 static int launch_main_family(const WGeo& w, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, float* ws, float* dbws,
-                              hipStream_t s) {
+                              hipStream_t s, const UpdArgs* ua = nullptr, const PSets* ps = nullptr, int kind = 0) {
   WArgs a;
   a.g = (const float*)w.g->ptr; a.gsn = w.g->sn; a.gsd = w.g->sd; a.gsh = w.g->sh; a.gsw = w.g->sw;
   a.Cg = w.g->c; a.Dgg = w.g->d; a.Hgg = w.g->h; a.Wgg = w.g->w;
@@ -2071,6 +2153,7 @@ static int launch_main_family(const WGeo& w, const mmtta_tensor* x, const mmtta_
   a.gvec4 = quad_aligned(w.g, quad_bytes(w.g)) ? 1 : 0;
   a.dvec4 = quad_aligned(w.dn, quad_bytes(w.dn)) ? 1 : 0;
   const int SQ = w.S * w.nsets;          // slabs of the launch
+  if (ua != nullptr) return launch_wgrad_tr_upd_s1<4, 8>(a, *ua, *ps, kind, SQ, s);
   switch (w.route) {
     case W_TR_1X1: return launch_wgrad_tr1(a, SQ, s);
     case W_TR_S1: return launch_wgrad_tr<4, 8, 1>(a, SQ, s, w.ncb, wgrad_raw_bits(w, x_norm));
@@ -2082,9 +2165,10 @@ static int launch_main_family(const WGeo& w, const mmtta_tensor* x, const mmtta_
 }
 
 // Everything behind the main kernel: slabs -> (pre-reduce past 32 slabs) -> the route's reduce kernel -> bias gradient.
-// With `upd` the 27-tap reduce is the fused update (optimizer step and both bf16 images in the same pass).
+// With `upd` the 27-tap reduce is the fused update (optimizer step and both bf16 images in the same pass); `updated`: the
+// main kernel has done all of that in its epilogue, a Conv3d's bias included - what is left is a ConvTranspose3d's b_grad.
 static int reduce_tail(const WGeo& w, const mmtta_tensor* dy, float* ws, float* dw, float* db, int accumulate,
-                       const mmtta_param_sets* sets, const mmtta_update_target* upd, const UpdArgs& ua, hipStream_t s) {
+                       const mmtta_param_sets* sets, const mmtta_update_target* upd, const UpdArgs& ua, bool updated, hipStream_t s) {
   const PSets ps = psets(sets);
   const int Q = w.nsets;
   const bool tiny = w.route == W_TINY, thin = route_thin(w.route);
@@ -2120,6 +2204,7 @@ static int reduce_tail(const WGeo& w, const mmtta_tensor* dy, float* ws, float* 
                          Cg, Cd, w.CGp, w.CDp, accumulate, ps);
       break;
     default:                  // the 27-tap routes (route_reduce27)
+      if (updated) break;
       if (upd != nullptr) {
         static constexpr decltype(&wgrad_update27_kernel<0>) kinds[3] = {      // KIND = mmtta_optim_desc.kind (checked)
             wgrad_update27_kernel<MMTTA_OPTIM_ADAM>, wgrad_update27_kernel<MMTTA_OPTIM_ADAMW>, wgrad_update27_kernel<MMTTA_OPTIM_SGD>};
@@ -2165,14 +2250,17 @@ int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
               (long long)workspace_bytes, (long long)need);
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
+  const PSets ps = psets(sets);
+  const bool in_epilogue = upd != nullptr && wgrad_updates_in_epilogue(w) && update_target_vec16(upd, ps, w.nsets);
   // the main kernel writes bias rows only when they are wanted and are its to write
   float* dbws = (db != nullptr && w.bias != WB_COLSUMS) ? ws + w.slab_floats * w.nsets : nullptr;
   if (w.route == W_TINY) st = launch_tiny_family(d, w, x, x_norm, dy, ws, dbws, s);
   else if (route_thin(w.route)) st = launch_thin_family(d, w, x_norm, ws, dbws, s);
+  else if (in_epilogue) st = launch_main_family(w, x, x_norm, ws, dbws, s, &ua, &ps, upd->optim.kind);
   else st = launch_main_family(w, x, x_norm, ws, dbws, s);
   // MMTTA_OPT_PROFILE_MAIN_KERNEL_ONLY stops here; a fused-update call still runs its update
   if (st || (g_profile_main_only && upd == nullptr)) return st;
-  return reduce_tail(w, dy, ws, dw, db, accumulate, sets, upd, ua, s);
+  return reduce_tail(w, dy, ws, dw, db, accumulate, sets, upd, ua, in_epilogue, s);
 }
 
 MMTTA_ACT_NS_CLOSE
@@ -2236,6 +2324,15 @@ extern "C" int mmtta_conv_wgrad_sets(const mmtta_conv_desc* d, const mmtta_tenso
   if (nl_leaky(x_norm))
     return leaky::conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
   return conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
+}
+
+extern "C" int mmtta_conv_wgrad_updates_in_epilogue(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                                    const mmtta_tensor* dy, const mmtta_param_sets* sets) {
+  WGeo w{};
+  const int st = wgeometry(d, x, dy, sets, w);
+  if (st) return st < 0 ? st : -st;
+  if (g_fused_update == 0 || !route_reduce27(w.route)) return 0;      // (mmtta_conv_wgrad_update_sets refuses these)
+  return (!nl_leaky(x_norm) && wgrad_updates_in_epilogue(w)) ? 1 : 0;      // (a LeakyReLU call runs the instantiation without these kernels)
 }
 
 extern "C" int mmtta_fused_update_enabled(void) { return g_fused_update != 0 ? 1 : 0; }

@@ -4,6 +4,8 @@
 // was before the second kernel existed (conv_igemm_body.h does the same).  No include guard on purpose.
 // RG / RD: the gathered / the dense operand is bf16-stored and takes no transform (host: wgrad_raw_bits) - its 16-byte items
 // go to LDS as loaded, under their masks.  Every RG / RD site is an `if constexpr`.
+// UPD (wgrad_tr_upd_kernel; MMTTA_OPT_WGRAD_EPILOGUE_UPDATE): the kernel also has `UpdArgs u`, `PSets ps` and the optimizer
+// KIND, and ends in the fused update of its block instead of the slab stores.  One `if constexpr` at the end of the text.
   using G = WTGeo<TZ, TY, SI>;
   static_assert(TY % 2 == 0, "a k step is two rows of one z slice");
   static_assert((!RG || GBF) && (!RD || DBF), "raw staging copies bf16-stored items");
@@ -314,6 +316,75 @@
     }
     __syncthreads();
   }
+  if constexpr (UPD) {
+    // One slab per set (host: wgrad_updates_in_epilogue): this workgroup holds the complete gradient of its 27 x 32 cg x
+    // 32 NB cd block, so the slab, its read-back and wgrad_update27_kernel's launch are left out - the same optimizer and
+    // image code runs here on the same LDS tile (the images are dead: the loop ended with a barrier), 8 cg at a time.
+    float* tile = lds;                              // [32 cd][UPD_RS], then the two step scalars
+    float* scal = lds + UPD_CD * UPD_RS;
+    const int t0s = *u.step;
+    if (tid == 0) optim_scalars(KIND, u.a, t0s, scal[0], scal[1]);
+    const bool first = t0s == 0;
+    const bool wd_on = u.a.wd != 0.f;
+    const bool keep_m = KIND != 2 || u.a.momentum != 0.f;
+    __syncthreads();
+    const float step_size = scal[0], bc2_sqrt = scal[1];
+    if (want_db) {                                  // the complete bias gradient of these 32 NB channels (see below)
+      float* red8 = lds;
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        if (nb) __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 8; ++c) red8[tid * 8 + c] = dbs[nb][c];
+        __syncthreads();
+        const int cd = cd0 + 32 * nb + tid;
+        if (tid < 32 && cd < a.Cd) {
+          float sacc = 0.f;
+#pragma unroll 8
+          for (int q = 0; q < 64; ++q) sacc += red8[((q << 2) | (tid >> 3)) * 8 + (tid & 7)];
+          // bias_rows_sum over this one row adds zeros to it: sacc is never -0 (it starts at +0), so that is sacc itself
+          const float t = 0.f + sacc;
+          const long long o = pset_bias_elems(ps, qset) + cd;
+          float pi = u.bp[o], mi = 0.f, vi = 0.f;
+          if (!first) {
+            if (keep_m) mi = u.bm[o];
+            if (KIND != 2) vi = u.bv[o];
+          }
+          optim_update<KIND>(pi, t, mi, vi, wd_on && u.b_decay, u.a, step_size, bc2_sqrt, first);
+          u.bp[o] = pi;
+          if (keep_m) u.bm[o] = mi;
+          if (KIND != 2) u.bv[o] = vi;
+        }
+      }
+      __syncthreads();
+    }
+    const bool decay = wd_on && u.w_decay;
+    const long long wo = pset_weight_elems(ps, qset), rowst = (long long)a.Cg * 27;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      // accumulator rows 8 g + (i & 3) + 4 h, i = 4 g .. 4 g + 3, are cg group g of the block; the value is slab_sums4's for
+      // one slab, 0.f + acc (a -0 does not survive there either)
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        const int tap = wave + 4 * j;
+        if (tap < 27) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) tile[r * UPD_RS + (i + 4 * h) * 27 + tap] = 0.f + acc[nb][j][4 * g + i];
+        }
+      }
+      __syncthreads();
+      const int ucg0 = cg0 + 8 * g, ucd0 = cd0 + 32 * nb;
+      const long long ob = wo + ((long long)ucd0 * a.Cg + ucg0) * 27;
+      upd_optim4<KIND, 4>(u, ob, rowst, 0, ucd0, a.Cd, first, keep_m, decay, step_size, bc2_sqrt, tile);
+      upd_optim4<KIND, 3>(u, ob, rowst, 4, ucd0, a.Cd, first, keep_m, decay, step_size, bc2_sqrt, tile);
+      __syncthreads();
+#pragma unroll
+      for (int m = 0; m < 2; ++m) upd_repack(u.img[m], ps, qset, ucg0, ucd0, tile);
+      __syncthreads();
+    }
+  } else {
   const int sl = sx;
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb)
@@ -344,4 +415,5 @@
         a.dbpart[(long long)sl * a.CDp + cd0 + 32 * nb + tid] = sacc;
       }
     }
+  }
   }
