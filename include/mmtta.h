@@ -224,6 +224,16 @@ int mmtta_abi_version(void);
  * bit for bit.  Workspace sizes and plans do not depend on it.
  * mmtta_conv_wgrad_updates_in_epilogue tells whether a call qualifies.  Returns the previous value. */
 #define MMTTA_OPT_WGRAD_EPILOGUE_UPDATE 19
+/* 1 (default): a class-fused stride-2 transposed form (route 15) that stages raw (MMTTA_OPT_RAW_STAGING bit 0) runs
+ * igemm_cls8_pipe_kernel (csrc/conv_igemm.hip): two weight images in LDS, the image of channel stage k+1 fetched by direct
+ * global-to-LDS loads (no registers in between) while the matrix cores work on stage k, and the box items of stage k+1
+ * requested at the same point and committed behind the barrier that closes stage k.  0: igemm_cls8_raw_kernel, request ->
+ * wait -> commit -> barrier -> MFMA -> barrier, in the same process.  The same MFMAs with the same operands in the same
+ * order, the same epilogue: outputs, accumulated / fused-add destinations and statistics rows equal bit for bit.  No route,
+ * plan, statistics row or workspace size depends on it; a call that keeps the transform (norm-on-load, fp32-stored
+ * tensors, the LeakyReLU instantiation) keeps its kernel.  mmtta_conv_cls8_pipelined tells whether a call qualifies.
+ * Returns the previous value. */
+#define MMTTA_OPT_CLS8_PIPELINE 20
 int mmtta_set_option(int key, int value);
 
 /* ------------------------------------------------------------------ layout (boundary) ---- */
@@ -329,6 +339,12 @@ int mmtta_conv_route(const mmtta_conv_desc* desc, const mmtta_tensor* x, const m
  * mmtta error code.  Host-only, the operands of mmtta_conv_route, the predicate the launchers themselves ask. */
 int mmtta_conv_stages_raw(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                           const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
+
+/* Whether mmtta_conv_run would run this call on the pipelined class-fused kernel (MMTTA_OPT_CLS8_PIPELINE): 1 when the call
+ * takes route 15, stages raw and the option is on, else 0, or a negative mmtta error code.  Host-only, the operands of
+ * mmtta_conv_route, the predicate the launcher itself asks. */
+int mmtta_conv_cls8_pipelined(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                              const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
 
 /* Which lean kernel of MMTTA_OPT_THIN_LEAN mmtta_conv_run would take for this call: 1 the thin-K convolution (bit 0), 2 the
  * gather-GEMM up-convolution (bit 1), 0 neither, or a negative mmtta error code.  Host-only, the operands of mmtta_conv_route,

@@ -135,6 +135,7 @@ _SIGNATURES = {
                                       _P(Tensor), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _P(ParamSets), C.c_void_p]),
     "mmtta_conv_route": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_stages_raw": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
+    "mmtta_conv_cls8_pipelined": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_thin_lean": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_head_loss_eligible": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), _P(Tensor),
                                                 C.c_int, C.c_int]),
@@ -330,6 +331,8 @@ def load() -> C.CDLL:
         lib.mmtta_set_option(18, int(os.environ["MMTTA_THINLEAN"]))
     if "MMTTA_EPIUPDATE" in os.environ:                  # A/B aid: MMTTA_OPT_WGRAD_EPILOGUE_UPDATE (same results bit for bit)
         lib.mmtta_set_option(19, int(os.environ["MMTTA_EPIUPDATE"]))
+    if "MMTTA_CLS8PIPE" in os.environ:                   # A/B aid: MMTTA_OPT_CLS8_PIPELINE (same results bit for bit)
+        lib.mmtta_set_option(20, int(os.environ["MMTTA_CLS8PIPE"]))
     _lib = lib
     return lib
 

@@ -23,6 +23,7 @@ int g_raw_staging = 3;
 int g_head_loss_pair = 3;
 int g_thin_lean = 3;
 int g_wgrad_epilogue_update = 1;
+int g_cls8_pipeline = 1;
 // split-K below / target, weight-gradient workgroups, thin-layer slabs.  Swept with the lanes bound to their own hardware
 // queues (profiles/r02_tuning_sweep.txt): four volumes in flight want half the splitting two did (96/128, 128 slabs)
 int g_tune[4] = {96, 128, 128, 256};
@@ -87,6 +88,11 @@ extern "C" int mmtta_set_option(int key, int value) {
   if (key == MMTTA_OPT_WGRAD_EPILOGUE_UPDATE) {
     const int prev = mmtta::g_wgrad_epilogue_update;
     mmtta::g_wgrad_epilogue_update = value ? 1 : 0;
+    return prev;
+  }
+  if (key == MMTTA_OPT_CLS8_PIPELINE) {
+    const int prev = mmtta::g_cls8_pipeline;
+    mmtta::g_cls8_pipeline = value ? 1 : 0;
     return prev;
   }
   if (key == MMTTA_OPT_IGEMM_PIPELINE) {

@@ -44,6 +44,7 @@ extern int g_raw_staging;           // api.hip: MMTTA_OPT_RAW_STAGING (bit 0: im
 extern int g_head_loss_pair;        // api.hip: MMTTA_OPT_HEAD_LOSS_PAIR (bit 0: entropy objective in the head convolution, bit 1: paired thin weight gradients)
 extern int g_thin_lean;            // api.hip: MMTTA_OPT_THIN_LEAN (bit 0: thin-K convolution, bit 1: gather-GEMM up-convolution)
 extern int g_wgrad_epilogue_update; // api.hip: MMTTA_OPT_WGRAD_EPILOGUE_UPDATE
+extern int g_cls8_pipeline;         // api.hip: MMTTA_OPT_CLS8_PIPELINE
 extern int g_tune[4];             // api.hip: launch-geometry knobs (MMTTA_OPT_SPLITK_BELOW ... MMTTA_OPT_WGRAD_THIN_SLABS)
 
 // ---- activation of a norm-on-load (mmtta_norm_on_load.relu: MMTTA_ACT_*).

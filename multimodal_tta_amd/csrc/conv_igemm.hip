@@ -374,9 +374,24 @@ __host__ __device__ constexpr ClsTap cls_tap(int f) {        // f-th (class, tap
   return ClsTap{0, 0, 0};
 }
 
+// A 16-byte operand read from LDS.  TYPED (igemm_cls8_pipe_kernel): as ONE load of a vector type.  The copy of a uint4 is a
+// struct copy, which reaches the back end as a load without type information, and hipcc makes every such LDS read wait for all
+// direct global-to-LDS loads in flight (vmcnt(0) at the head of the MFMA phase, i.e. for the image just requested); the typed
+// load waits only for a load it may alias.  The reads of a stage never touch the image in flight: the barriers order them.
+typedef unsigned cls8_u32x4 __attribute__((ext_vector_type(4)));
+template <bool TYPED>
+__device__ __forceinline__ uint4 cls8_lds_q(const void* p) {
+  if constexpr (TYPED) {
+    const cls8_u32x4 v = *reinterpret_cast<const cls8_u32x4*>(p);
+    return make_uint4(v.x, v.y, v.z, v.w);
+  } else {
+    return *reinterpret_cast<const uint4*>(p);
+  }
+}
+
 template <int KCI, bool ABF>
 __global__ __launch_bounds__(256, 2) void igemm_cls8_kernel(GArgs a) {
-  constexpr bool RAW = false;
+  constexpr bool RAW = false, PIPE = false;
 #include "conv_igemm_cls8_body.h"
 }
 
@@ -384,18 +399,30 @@ __global__ __launch_bounds__(256, 2) void igemm_cls8_kernel(GArgs a) {
 // across the requests of a stage
 template <int KCI, bool ABF>      // (ABF always true: see igemm_reuse_raw_kernel)
 __global__ __launch_bounds__(256, 2) void igemm_cls8_raw_kernel(GArgs a) {
-  constexpr bool RAW = true;
+  constexpr bool RAW = true, PIPE = false;
 #include "conv_igemm_cls8_body.h"
 }
 
-template <int KCI, bool ABF, bool RAW = false>
+// ... and with the K loop pipelined (MMTTA_OPT_CLS8_PIPELINE; host: cls8_pipelined): two weight images in LDS, the image of
+// stage k + 1 fetched by direct global-to-LDS loads while stage k multiplies, the box items of stage k + 1 requested a stage
+// ahead.  No register holds the weights on their way, so the prefetch costs none across the MFMA phase - what the register
+// pipeline of round 3 could not afford beside 8 accumulator blocks.  Same products in the same order, same epilogue.
+template <int KCI, bool ABF>      // (ABF always true)
+__global__ __launch_bounds__(256, 2) void igemm_cls8_pipe_kernel(GArgs a) {
+  constexpr bool RAW = true, PIPE = true;
+#include "conv_igemm_cls8_body.h"
+}
+
+template <int KCI, bool ABF, bool RAW = false, bool PIPE = false>
 static int launch_cls8_t(const GArgs& a, int tiles, hipStream_t s) {
   constexpr int VS = KCI + 8;
-  size_t lds = ((size_t)(5 * 5 * LDS_PITCH_BF16 * VS + 7) / 8 * 8) * 2 + (size_t)27 * (KCI / 8) * 32 * 16;
+  // the box image and the stage's weight image (PIPE: two of them; 69 696 bytes at KCI = 16, two workgroups per CU still)
+  size_t lds = ((size_t)(5 * 5 * LDS_PITCH_BF16 * VS + 7) / 8 * 8) * 2 + (size_t)(PIPE ? 2 : 1) * 27 * (KCI / 8) * 32 * 16;
   const size_t epi = (4 * EPI_TILE_FLOATS + 4 * 2 * 32) * sizeof(float);
   if (lds < epi) lds = epi;
   void (*kern)(GArgs) = igemm_cls8_kernel<KCI, ABF>;
-  if constexpr (RAW) kern = igemm_cls8_raw_kernel<KCI, ABF>;
+  if constexpr (RAW && !PIPE) kern = igemm_cls8_raw_kernel<KCI, ABF>;
+  if constexpr (PIPE) kern = igemm_cls8_pipe_kernel<KCI, ABF>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1001,6 +1028,13 @@ static bool raw_staging(int route, bool bf_tile, const mmtta_tensor* x, const mm
   return RAW_KERNELS && (g_raw_staging & 1) && igemm && bf_tile && raw_operand(x, x_norm) && is_bf16(y) && (add == nullptr || is_bf16(add));
 }
 
+// The pipelined class-fused kernel (MMTTA_OPT_CLS8_PIPELINE; igemm_cls8_pipe_kernel): route 15 on a call that stages raw.  The
+// one function behind mmtta_conv_cls8_pipelined and the launcher.
+static bool cls8_pipelined(int route, bool bf_tile, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* y,
+                           const mmtta_tensor* add) {
+  return g_cls8_pipeline && route == 15 /* C_CLS_FUSED */ && raw_staging(route, bf_tile, x, x_norm, y, add);
+}
+
 struct Geometry {
   int route;      // CRoute
   int K, N, Kp, Np, si;
@@ -1363,8 +1397,9 @@ static int cls_fused_run(const ConvCall& c, const Geometry& g) {
   MMTTA_CHECK(a.in_bf == a.out_bf && (a.add == nullptr || a.add_bf == a.out_bf), MMTTA_ERR_UNSUPPORTED,
               "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf, a.add_bf);
   if constexpr (RAW_KERNELS) {
-    if (raw_staging(g.route, g.cfg.bf, c.x, c.x_norm, c.y, (c.epi && c.epi->add) ? c.epi->add : nullptr))
-      return launch_cls8_t<16, true, true>(a, g.tiles, c.stream);
+    const mmtta_tensor* ad = (c.epi && c.epi->add) ? c.epi->add : nullptr;
+    if (cls8_pipelined(g.route, g.cfg.bf, c.x, c.x_norm, c.y, ad)) return launch_cls8_t<16, true, true, true>(a, g.tiles, c.stream);
+    if (raw_staging(g.route, g.cfg.bf, c.x, c.x_norm, c.y, ad)) return launch_cls8_t<16, true, true>(a, g.tiles, c.stream);
   }
   return a.in_bf ? launch_cls8_t<16, true>(a, g.tiles, c.stream) : launch_cls8_t<16, false>(a, g.tiles, c.stream);
 }
@@ -1549,6 +1584,16 @@ extern "C" int mmtta_conv_stages_raw(const mmtta_conv_desc* d, const mmtta_tenso
   const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
   // (a LeakyReLU on the fused add sends the run to the LeakyReLU instantiation, which has no raw kernels)
   return (raw_staging(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
+}
+
+extern "C" int mmtta_conv_cls8_pipelined(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                         const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
+  Geometry g;
+  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
+  if (st) return st < 0 ? st : -st;
+  const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
+  // (a LeakyReLU on the fused add sends the run to the LeakyReLU instantiation, which has no raw kernels)
+  return (cls8_pipelined(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
 }
 
 extern "C" int mmtta_conv_thin_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,

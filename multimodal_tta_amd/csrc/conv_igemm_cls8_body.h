@@ -1,6 +1,7 @@
-// The body of igemm_cls8_kernel and igemm_cls8_raw_kernel (conv_igemm.hip): included inside each kernel, which names KCI, ABF
-// and RAW as compile-time constants and has the kernel argument `GArgs a`.  One text and no function in between, so that
-// igemm_cls8_kernel compiles to exactly what it was before the second kernel existed (conv_igemm_body.h does the same).
+// The body of igemm_cls8_kernel, igemm_cls8_raw_kernel and igemm_cls8_pipe_kernel (conv_igemm.hip): included inside each
+// kernel, which names KCI, ABF, RAW and PIPE as compile-time constants and has the kernel argument `GArgs a`.  One text and no
+// function in between, so that igemm_cls8_kernel compiles to exactly what it was before the other kernels existed
+// (conv_igemm_body.h does the same).
 // No include guard on purpose: it is included once per kernel.
   constexpr int TZ = 4, TY = 4, TX = 8, VS = KCI + 8, LP = LDS_PITCH_BF16, KS = KCI / 16, KC8 = KCI / 8;
   constexpr int BZ = TZ + 1, BY = TY + 1, BX = TX + 1;
@@ -42,7 +43,76 @@
   constexpr int BIT = (WIMG + 255) / 256;                    // weight entries per thread
   const float relu_lo = act_lo(a.tin.relu);
 
+  // ---- PIPE (igemm_cls8_pipe_kernel; raw staging only): two weight images behind the box, image ks & 1 read by stage ks.
+  // The image of stage ks + 1 comes by direct global-to-LDS loads issued behind the barrier that opens stage ks's MFMA
+  // phase - no register holds it - and the box items of stage ks + 1 are requested there too and committed behind the
+  // barrier that closes stage ks (the single box image is free then).  The plain barriers wait for every outstanding load,
+  // so the closing barrier of stage ks retires the image stage ks + 1 reads one barrier later, and the last stage issues
+  // nothing: the epilogue finds LDS quiet.  Entry i = tid + 256 j of an image is tap i / 64 = 4 j + wave, lane = (k8l, col):
+  // a wave's 64 entries are 1 KiB in lane order, which is what one such load writes; at j = BIT - 1 waves 0-2 have work.
+  // What does not depend on the stage is worked out once: the lane's 32-bit weight offset (the tap and the stage move a
+  // wave-uniform base), its box offsets, LDS addresses and halo bits.  No ordinary load's result may be used between the
+  // issue and the closing barrier (hipcc would wait for every load in flight there, the image included), a spill reload
+  // counts, and the operand reads of the MFMA phase are typed loads (cls8_lds_q) for the same reason.
+  static_assert(!PIPE || (RAW && ABF && KC8 * 32 == 64 && WIMG % 64 == 0), "the pipelined form: raw staging of 16-channel stages");
+  unsigned wlane = 0u;      // the lane's byte offset inside a tap's two rows of the packed image
+  unsigned poff[AIT], phalo = 0u;
+  auto pipe_cv8 = [&](int j) { return (min(tid + 256 * j, BZ * BY * BX * KC8 - 1) % KC8) * 8; };      // item j's chunk in the stage
+  int plds[AIT];
+  Oct8<ABF> pav[AIT];
+  if constexpr (PIPE) {
+    wlane = (unsigned)((lane >> 5) * a.Np + colbase + (lane & 31)) * 16u;
+#pragma unroll
+    for (int j = 0; j < AIT; ++j) {
+      const int i = min(tid + 256 * j, BZ * BY * BX * KC8 - 1);
+      const int cv = i % KC8, bv = i / KC8;
+      const int bz = bv / (BY * BX), brem = bv - bz * (BY * BX), by = brem / BX, bx = brem - by * BX;
+      const int iz = gz0 + bz, iy = gy0 + by, ix = gx0 + bx;
+      phalo |= ((iz < a.Di && iy < a.Hi && ix < a.Wi) ? 1u : 0u) << j;
+      poff[j] = __umul24((unsigned)min(iz, a.Di - 1), isd) + __umul24((unsigned)min(iy, a.Hi - 1), ish) +
+                __umul24((unsigned)min(ix, a.Wi - 1), isw) + cv * 8;
+      plds[j] = ((bz * BY + by) * LP + bx) * VS + cv * 8;
+    }
+  }
+  auto pipe_issue = [&](int ks) {      // the weight image and the box items of stage ks
+    if constexpr (PIPE) {
+    const char* src = reinterpret_cast<const char*>(wq + (long long)ks * KC8 * a.Np);      // wave-uniform; the lane adds 32 bits
+    uint4* dst = wimg + (ks & 1) * WIMG + 64 * wave;
+#pragma unroll
+    for (int j = 0; j < BIT; ++j)
+      if (j < BIT - 1 || 256 * j + 64 * wave < WIMG)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (long long)(4 * j + wave) * slabsz8 * 16 + wlane),
+                                         (__attribute__((address_space(3))) void*)(dst + 256 * j), 16, 0, 0);
+    const int c0 = ks * KCI;
+    const float* sb = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.in) + ((long long)n * a.isn + c0) * 2);
+#pragma unroll
+    for (int j = 0; j < AIT; ++j) {
+      const int over = max(c0 + pipe_cv8(j) - cmax, 0);      // a chunk past Ci re-reads the last valid one; the mask blanks it
+      pav[j] = oct8_ld<ABF>(sb, poff[j] - over, 0u);
+    }
+    }
+  };
+  auto pipe_commit = [&](int ks) {     // the box items of stage ks, as loaded, under halo and chunk mask
+    if constexpr (PIPE) {
+#pragma unroll
+    for (int j = 0; j < AIT; ++j) {
+      const unsigned okm = (((phalo >> j) & 1u) && ks * KCI + pipe_cv8(j) < a.Ci) ? 0xffffffffu : 0u;
+      uint4 pk = pav[j].q;
+      pk.x &= okm; pk.y &= okm; pk.z &= okm; pk.w &= okm;
+      if (tid + 256 * j < BZ * BY * BX * KC8) *reinterpret_cast<uint4*>(lh + plds[j]) = pk;
+    }
+    }
+  };
+  if constexpr (PIPE) {
+    __builtin_assume(a.nstages > 0);      // (K >= 1: no path around the loop; with one the epilogue spills one register more)
+    pipe_issue(0);
+  }
+
   for (int ks = 0; ks < a.nstages; ++ks) {
+    const uint4* const bst = PIPE ? brow + (ks & 1) * WIMG : brow;      // the stage's weight image
+    if constexpr (PIPE) {
+      pipe_commit(ks);
+    } else {
     const int c0 = ks * KCI;
     const float* sb = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.in) + ((long long)n * a.isn + c0) * (ABF ? 2 : 4));
     // ---- requests first: weights of the stage, norm-on-load coefficients, box items (one round trip for all of them)
@@ -101,7 +171,11 @@
       }
       if (tid + 256 * j < BZ * BY * BX * KC8) *reinterpret_cast<uint4*>(lh + alds[j]) = pk;
     }
+    }
     __syncthreads();
+    if constexpr (PIPE) {
+      if (ks + 1 < a.nstages) pipe_issue(ks + 1);
+    }
     // ---- MFMAs: 8 activation fragments per k step (one per tap offset), then the 27 (class, tap) products; weight
     // fragment f is read LA products ahead through a ring (a fence per MFMA keeps the reads where they are written)
     if (colact) {
@@ -110,18 +184,18 @@
         uint4 af[8];
 #pragma unroll
         for (int d = 0; d < 8; ++d)
-          af[d] = *reinterpret_cast<const uint4*>(arow + ((((d >> 2) & 1) * BY + ((d >> 1) & 1)) * LP + (d & 1)) * VS + k16 * 16);
+          af[d] = cls8_lds_q<PIPE>(arow + ((((d >> 2) & 1) * BY + ((d >> 1) & 1)) * LP + (d & 1)) * VS + k16 * 16);
         constexpr int LA = 3;
         uint4 bring[LA + 1];
         static_for<0, LA>([&](auto fc) {
           constexpr int f = decltype(fc)::value;
-          bring[f] = brow[(cls_tap(f).slab * KC8 + k16 * 2) * 32];
+          bring[f] = cls8_lds_q<PIPE>(bst + (cls_tap(f).slab * KC8 + k16 * 2) * 32);
         });
         __builtin_amdgcn_sched_barrier(0);
         static_for<0, 27>([&](auto fc) {
           constexpr int f = decltype(fc)::value;
           constexpr ClsTap ct = cls_tap(f);
-          if constexpr (f + LA < 27) bring[(f + LA) % (LA + 1)] = brow[(cls_tap(f + LA).slab * KC8 + k16 * 2) * 32];
+          if constexpr (f + LA < 27) bring[(f + LA) % (LA + 1)] = cls8_lds_q<PIPE>(bst + (cls_tap(f + LA).slab * KC8 + k16 * 2) * 32);
           acc[ct.cls] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[ct.d]),
                                                                 __builtin_bit_cast(bf16x8, bring[f % (LA + 1)]), acc[ct.cls], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
