@@ -1192,6 +1192,64 @@ int mmtta_modcons_loss_items(const mmtta_tensor* logits, int softmax, int views,
                              const mmtta_tensor* dlogits, double* partial, float* loss, float* entropy, float* consistency,
                              float* view_kl, int64_t* disagree, void* stream);
 
+/* ------------------------------------------------------------------ sliding windows */
+/* Sliding-window adaptation and inference (window_tta) - csrc/window.hip: a volume of any extents is cut into overlapping
+ * windows of the network's own extents (the roi), the network runs on every window as a batch item, and the windows meet
+ * again under an importance weight.  A batch of G volumes x W_n windows is [G * W_n, rd, rh, rw, C], item g * W_n + w = window
+ * w of volume g.  The grid is separable: per axis a list of `count` starts (ascending; a single negative start on an axis the
+ * volume is shorter than the roi along), w = (kd * count_h + kh) * count_w + kw, origin o_w = (start_d[kd], start_h[kh],
+ * start_w[kw]); W_n = count_d * count_h * count_w <= 32.
+ *   origins  int32 [W_n][3], on the device (a replayed graph reads the current volume's) - and for the crop also on the host
+ *   tables   device fp32: A_d [count_d][rd] | A_h [count_h][rh] | A_w [count_w][rw] in one buffer, A_axis[k][i] = the importance
+ *            weight of index i of a window divided by the sum of the weights of all windows over position start_k + i - and 0
+ *            where that position lies outside the volume.  The weight of window w at its voxel (i, j, k) is
+ *            a = (A_d[kd][i] * A_h[kh][j]) * A_w[kw][k], rounded in fp32 in that order by every kernel.  The host builds the
+ *            tables (multimodal_tta_amd/window.py); nothing here checks that they sum to 1.
+ *
+ * mmtta_window_views: y[g * W_n + w] = x[g] cropped at o_w, x [G, D, H, W, C] and y [G * W_n, rd, rh, rw, C] channels-last,
+ *   fp32 or bf16 alike.  A kept value keeps its bits (NaN payloads, infinities, -0); a voxel outside the volume takes
+ *   `pad_value` (rounded to nearest even for bf16 rows) in the C channels; the pad lanes that y owns take +0.  Dense rows of
+ *   4 lanes with C <= 4 (both tensors; y owning its pad lanes or C == 4) take one 16-byte (fp32) or 8-byte (bf16) load and
+ *   store per voxel; every other layout a per-element path.  Every origin must leave its window a voxel of the volume
+ *   (-r < o < extent per axis, checked on `origins_host`): the kernels bound every read by the volume's extents.
+ *
+ * mmtta_window_entropy_items: every volume g is its own objective,
+ *     loss[g]  = 1/(N R) sum_w sum_voxels a_w H_bern(sigmoid z_w)       (softmax != 0: 1/N and the categorical entropy)
+ *     dlogits  = a_w H'(z_w) / (N R)                                     whole rows stored, +0 where a_w == 0
+ *   N = D H W of the volume in `windows` - every voxel of the volume counts once, shared among the windows that see it; the
+ *   voxels outside it count 0.  This is mmtta_entropy_loss_items' walk (voxel_loss.h: fast, any-stride and categorical paths)
+ *   with the window's three table rows in LDS; a launch over loss_blocks(one item) x items workgroups and a finish launch that
+ *   sums the fp64 block partials of a volume's W_n items in ascending order.  The Bernoulli heads use the entropy objective's
+ *   own per-logit arithmetic; the categorical head its shifted form log sum e - sum p (z - max), exact to fp32 rounding at any
+ *   magnitude (the plain form lse - sum p z carries the rounding of lse times the mean logit: 2e-5 of the largest gradient of
+ *   two classes at |z| = 10).  With extents equal to the roi (one window, a == 1 by construction) the call IS
+ *   mmtta_entropy_loss_items, bit for bit, and the tables are not read.  No atomics: G volumes in one call are bit for bit G
+ *   calls on one volume each.  Storages as mmtta_entropy_loss_items; roi <= 512 per axis.
+ *   partial  fp64 [mmtta_window_partials(logits)] scratch = loss_blocks(one item) x items (host-only; -1 on a null tensor or
+ *            an empty extent);  loss  fp32 [G]
+ *
+ * mmtta_window_blend: out[g](v) = sum_w a_w(v) z_w(v - o_w) over the windows that cover voxel v of the volume, a gather: a
+ *   thread owns an output voxel, finds per axis the starts that cover it and accumulates fma(a_w, z_w, acc) from +0 in
+ *   ascending window order, in fp32.  logits [G * W_n, rd, rh, rw, R] and out [G, D, H, W, R] fp32 channels-last; R <= 4 in
+ *   dense 16-byte rows (out owning its pad, which takes +0, or R == 4) takes 16-byte accesses, every other layout a
+ *   per-element path.  Where one window covers a voxel and a == 1 the result is that window's logit bit for bit (a logit
+ *   of -0 comes back as +0: the sum starts from +0).
+ *
+ * MMTTA_ERR_INVALID before anything is launched: null pointers, a count outside 1 .. 32, more than 32 windows, a batch that
+ * is no multiple of W_n, extents that are not the volume tensor's, an origin that misses the volume, overlapping tensors.
+ * MMTTA_ERR_UNSUPPORTED: storages without a kernel, items of 2^31 elements or more, volumes of 2^29 voxels or more. */
+typedef struct mmtta_window_grid {
+  int32_t extent[3]; /* the volume's D, H, W */
+  int32_t count[3];  /* starts per axis */
+} mmtta_window_grid;
+int mmtta_window_views(const mmtta_tensor* x, const mmtta_tensor* y, const mmtta_window_grid* windows,
+                       const int32_t* origins_host, const int32_t* origins, float pad_value, void* stream);
+int64_t mmtta_window_partials(const mmtta_tensor* logits);
+int mmtta_window_entropy_items(const mmtta_tensor* logits, int softmax, const mmtta_window_grid* windows, const float* tables,
+                               const mmtta_tensor* dlogits, double* partial, float* loss, void* stream);
+int mmtta_window_blend(const mmtta_tensor* logits, const mmtta_tensor* out, const mmtta_window_grid* windows,
+                       const int32_t* origins, const float* tables, void* stream);
+
 /* ------------------------------------------------------------------ optimizer ------------ */
 /* torch.optim.Adam (amsgrad=False, coupled L2) over a flat parameter arena, two segments:
  * [0, n_decay) with weight_decay, [n_decay, n) without - the decay / no-decay groups of

@@ -115,6 +115,10 @@ class InputNormBranch(C.Structure):    # mmtta_input_norm_branch
                 ("stride", C.c_int32)]
 
 
+class WindowGrid(C.Structure):         # mmtta_window_grid
+    _fields_ = [("extent", C.c_int32 * 3), ("count", C.c_int32 * 3)]
+
+
 _P = C.POINTER
 _SIGNATURES = {
     "mmtta_last_error": (C.c_char_p, []),
@@ -245,6 +249,11 @@ _SIGNATURES = {
     "mmtta_modcons_partials": (C.c_int64, [_P(Tensor), C.c_int]),
     "mmtta_modcons_loss_items": (C.c_int, [_P(Tensor), C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P(Tensor), C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmtta_window_views": (C.c_int, [_P(Tensor), _P(Tensor), _P(WindowGrid), _P(C.c_int32), C.c_void_p, C.c_float, C.c_void_p]),
+    "mmtta_window_partials": (C.c_int64, [_P(Tensor)]),
+    "mmtta_window_entropy_items": (C.c_int, [_P(Tensor), C.c_int, _P(WindowGrid), C.c_void_p, _P(Tensor), C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "mmtta_window_blend": (C.c_int, [_P(Tensor), _P(Tensor), _P(WindowGrid), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmtta_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "mmtta_optim_step": (C.c_int, [_P(OptimDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,

@@ -846,6 +846,31 @@ class Runtime:
         ops.affine_views(x_cl, xv, coded, m_host, m)
         return xv
 
+    def stage_windows(self, x_cl: torch.Tensor, spec, grid=None) -> torch.Tensor:
+        """The staged input [G,D,H,W,C] -> its sliding windows as batch items [G * W_n, rd, rh, rw, C] (item g * W_n + w = the
+        crop of volume g at window w's origin; ``spec``: a ``window.WindowSpec``, ``grid``: its ``window.window_grid`` for these
+        extents where the caller has built it already), in the storage of the staged input.  The origins and the per-axis
+        weight tables sit in pool buffers (``win_origins`` / ``win_tables``, fixed addresses: a replayed graph reads the
+        current volume's), uploaded here; ``self.window_grid`` keeps the host copy, ``self.win_origins`` / ``self.win_tables``
+        name the device buffers for ops.window_entropy_items and ops.window_blend."""
+        from .window import MAX_WINDOWS, window_grid
+        n, d, h, w, c = x_cl.shape
+        if grid is None:
+            grid = window_grid((d, h, w), spec)
+        elif tuple(grid.extents) != (d, h, w):
+            raise ValueError(f"stage_windows: the grid is that of extents {tuple(grid.extents)}, the volume has {(d, h, w)}")
+        origins_host = torch.tensor(grid.origins, dtype=torch.int32).reshape(-1)
+        tables_host = torch.from_numpy(np.concatenate([t.reshape(-1) for t in grid.tables]).astype(np.float32))
+        origins = self.pool.flat("win_origins", MAX_WINDOWS * 3, dtype=torch.int32, zero=True)
+        tables = self.pool.flat("win_tables", tables_host.numel())
+        origins[:origins_host.numel()].copy_(origins_host)
+        tables.copy_(tables_host)
+        self.window_grid, self.win_origins, self.win_tables = grid, origins, tables
+        rd, rh, rw = grid.roi
+        xv = self.pool.cl("x_views", n * grid.windows, rd, rh, rw, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=x_cl.dtype)
+        ops.window_views(x_cl, xv, grid, origins, spec.pad_value)
+        return xv
+
     def _fill_views(self, x_cl: torch.Tensor, xv: torch.Tensor, view_axes: Sequence[int], intensity,
                     ordinals: Optional[Sequence[int]], present: Optional[Sequence[bool]]) -> None:
         """The coded views of the volumes ``x_cl`` into ``xv`` [len(x_cl) * len(view_axes), ...]: the mirror pass, or with an

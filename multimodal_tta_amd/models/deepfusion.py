@@ -57,11 +57,19 @@ class DecoderStage(Holder):
                                  subunits=num_res_units, act=act, norm=norm, dropout=dropout)
 
 
+def _check_extent(self, D: int, H: int, W: int) -> None:
+    """The extents a forward of either runtime takes (a caller that stages for a forward asks before it stages)."""
+    f = 2 ** (len(self.channels) - 1)
+    if D % f or H % f or W % f:
+        raise ValueError(f"input extent {(D, H, W)} is not divisible by {f}")
+
+
 class DeepFusionLoopRuntime(Runtime):
     """One modality encoder after another, the way the reference runs them (:214-218).  Kept for models whose norm layers
     carry parameters or cross-item statistics (BATCH / GROUP / affine norms): those cannot share one norm object across a
     family of encoders.  The shipped INSTANCE-norm configs run on :class:`DeepFusionRuntime`."""
     supports_present = True
+    check_extent = _check_extent
 
     def __init__(self, model: "MultimodalUNetDeepFusion", device: torch.device):
         super().__init__(device, model.conv_dtype)
@@ -91,9 +99,7 @@ class DeepFusionLoopRuntime(Runtime):
         if M != self.M:
             raise ValueError(f"model has {self.M} modality encoders but the input has {M} channels "
                              "(reference: zip() would silently truncate, unet_multimodal_midfusion.py:214)")
-        f = 2 ** (len(self.channels) - 1)
-        if D % f or H % f or W % f:
-            raise ValueError(f"input extent {(D, H, W)} is not divisible by {f}")
+        self.check_extent(D, H, W)
         keep = [m for m in range(M) if present is None or present[m]]
         if not keep:
             raise ValueError("at least one modality must be present")
@@ -276,6 +282,7 @@ class DeepFusionRuntime(Runtime):
     every mean, feeds the shared mean to ``bottleneck_reduce`` and receives zero gradients, which is exactly what skipping
     it gives (its weight gradients come out as exact zeros)."""
     supports_present = True
+    check_extent = _check_extent
 
     def __init__(self, model: "MultimodalUNetDeepFusion", device: torch.device):
         super().__init__(device, model.conv_dtype, group=getattr(model, "group", 1))
@@ -340,6 +347,15 @@ class DeepFusionRuntime(Runtime):
             ops.lincomb([xv[..., m:m + 1]], [1.0], self._member(xm, M, m))
         return xv
 
+    def stage_windows(self, x_cl: torch.Tensor, spec, grid=None) -> torch.Tensor:
+        """The windows of the staged volume (``Runtime.stage_windows``) and the family batch of those windows."""
+        xv = super().stage_windows(x_cl, spec, grid)
+        n, D, H, W, M = xv.shape
+        xm = self.pool.cl("xm", n * M, D, H, W, 1, ldc=4, zero=True)
+        for m in range(M):
+            ops.lincomb([xv[..., m:m + 1]], [1.0], self._member(xm, M, m))
+        return xv
+
     def stage_family(self, x_cl: torch.Tensor, key: str) -> torch.Tensor:
         """The family batch of a staged channels-last input [n, D, H, W, M] in the pool buffer ``key`` (what ``family_key``
         then names for a forward of that input): one ``lincomb`` per modality, as ``stage_views`` fills ``xm``."""
@@ -364,9 +380,7 @@ class DeepFusionRuntime(Runtime):
         if M != self.M:
             raise ValueError(f"model has {self.M} modality encoders but the input has {M} channels "
                              "(reference: zip() would silently truncate, unet_multimodal_midfusion.py:214)")
-        f = 2 ** (len(self.channels) - 1)
-        if D % f or H % f or W % f:
-            raise ValueError(f"input extent {(D, H, W)} is not divisible by {f}")
+        self.check_extent(D, H, W)
         keep = [m for m in range(M) if present is None or present[m]]
         if not keep:
             raise ValueError("at least one modality must be present")

@@ -126,16 +126,20 @@ class UNetRuntime(Runtime):
 
     supports_head_tail = True      # forward_cl(..., tail=): the objective may ride in the last convolution (engine.HeadLossTail)
 
-    def forward_cl(self, x_cl: torch.Tensor, present=None, tail=None) -> torch.Tensor:
-        n, D, H, W, _ = x_cl.shape
-        if present is not None and len(present) != self.in_channels:
-            raise ValueError(f"modality mask has {len(present)} entries for {self.in_channels} input channels")
-        x_nl = self._input_mask(n, present) if (present is not None and not all(present)) else None
+    def check_extent(self, D: int, H: int, W: int) -> None:
+        """The extents a forward takes (a caller that stages for a forward asks before it stages)."""
         f = 2 ** len(self.strides)
         if D % f or H % f or W % f:
             raise ValueError(
                 f"input extent {(D, H, W)} is not divisible by {f}: the up path could not be concatenated with its "
                 "skip (torch.cat fails in the reference as well)")
+
+    def forward_cl(self, x_cl: torch.Tensor, present=None, tail=None) -> torch.Tensor:
+        n, D, H, W, _ = x_cl.shape
+        if present is not None and len(present) != self.in_channels:
+            raise ValueError(f"modality mask has {len(present)} entries for {self.in_channels} input channels")
+        x_nl = self._input_mask(n, present) if (present is not None and not all(present)) else None
+        self.check_extent(D, H, W)
         dims = self._level_dims(D, H, W)
         c, L = self.channels, self.L
         self.dims, self.n = dims, n

@@ -1509,6 +1509,61 @@ def modcons_loss_items(logits: torch.Tensor, dlogits: torch.Tensor, views: int, 
                                                ptr(consistency), ptr(view_kl), ptr(disagree), stream_ptr()), "modcons_loss_items")
 
 
+def _window_grid(what: str, grid, origins: torch.Tensor, tables: Optional[torch.Tensor], roi: Sequence[int]) -> "_lib.WindowGrid":
+    """The mmtta_window_grid of ``grid`` (``window.WindowGrid``: extents, starts per axis) after the checks that need the device
+    buffers: int32 ``origins`` of at least W_n x 3 elements and fp32 ``tables`` of at least sum(count x roi) elements."""
+    counts = [len(s) for s in grid.starts]
+    windows = counts[0] * counts[1] * counts[2]
+    if origins.dtype != torch.int32 or not origins.is_contiguous() or not origins.is_cuda or origins.numel() < windows * 3:
+        raise MmttaError(f"{what}: origins must be contiguous device int32 of at least {windows * 3} elements ([{windows}, 3])")
+    need = sum(c * int(r) for c, r in zip(counts, roi))
+    if tables is not None and (tables.dtype != torch.float32 or not tables.is_contiguous() or not tables.is_cuda
+                               or tables.numel() < need):
+        raise MmttaError(f"{what}: tables must be contiguous device fp32 of at least {need} elements")
+    return _lib.WindowGrid((C.c_int32 * 3)(*[int(e) for e in grid.extents]), (C.c_int32 * 3)(*counts))
+
+
+def window_views(x: torch.Tensor, y: torch.Tensor, grid, origins: torch.Tensor, pad_value: float = 0.0) -> None:
+    """y[g * W_n + w] = x[g] cropped at window w's origin (include/mmtta.h, mmtta_window_views): channels-last [G,D,H,W,C] ->
+    [G*W_n,rd,rh,rw,C], fp32 or bf16.  Kept values keep their bits; outside the volume the channels take ``pad_value`` and the
+    pad lanes ``y`` owns +0.  ``grid``: the ``window.WindowGrid`` of x's extents; ``origins``: its device copy, int32 [W_n, 3]."""
+    wg = _window_grid("window_views", grid, origins, None, y.shape[1:4])
+    flat = [int(o) for origin in grid.origins for o in origin]
+    tx, ty = desc_cl(x), desc_cl(y)
+    check(_lib.load().mmtta_window_views(C.byref(tx), C.byref(ty), C.byref(wg), (C.c_int32 * max(len(flat), 1))(*flat),
+                                         ptr(origins), float(pad_value), stream_ptr()), "window_views")
+
+
+def window_partials(logits: torch.Tensor) -> int:
+    t = desc_cl(logits)
+    return int(_lib.load().mmtta_window_partials(C.byref(t)))
+
+
+def window_entropy_items(logits: torch.Tensor, dlogits: torch.Tensor, grid, origins: torch.Tensor, tables: torch.Tensor,
+                         partial: torch.Tensor, loss: torch.Tensor, softmax: bool = False) -> None:
+    """The sliding-window entropy of every volume on its own (include/mmtta.h, mmtta_window_entropy_items): logits / dlogits
+    [G*W_n,rd,rh,rw,R] (item g*W_n+w = window w of volume g); loss fp32 [G] = the entropy of the windows' voxels under the
+    weights of ``tables``, over the voxels of the unpadded volume."""
+    wg = _window_grid("window_entropy_items", grid, origins, tables, logits.shape[1:4])
+    windows = len(grid.origins)
+    if loss.dtype != torch.float32 or not loss.is_contiguous() or loss.numel() < int(logits.shape[0]) // max(windows, 1):
+        raise MmttaError("window_entropy_items: loss must be contiguous fp32 with one slot per volume")
+    if partial.dtype != torch.float64 or partial.numel() < window_partials(logits):
+        raise MmttaError("window_entropy_items: partial must be fp64 of window_partials(logits) elements")
+    tz, tg = desc_cl(logits), desc_cl(dlogits)
+    check(_lib.load().mmtta_window_entropy_items(C.byref(tz), 1 if softmax else 0, C.byref(wg), ptr(tables), C.byref(tg),
+                                                 ptr(partial), ptr(loss), stream_ptr()), "window_entropy_items")
+
+
+def window_blend(logits: torch.Tensor, out: torch.Tensor, grid, origins: torch.Tensor, tables: torch.Tensor) -> None:
+    """out[g](v) = sum over the windows w that cover voxel v of a_w(v) * logits[g*W_n+w](v - o_w), fp32, fma in ascending window
+    order (include/mmtta.h, mmtta_window_blend): [G*W_n,rd,rh,rw,R] -> [G,D,H,W,R] at the volume's extents."""
+    wg = _window_grid("window_blend", grid, origins, tables, logits.shape[1:4])
+    tz, to = desc_cl(logits), desc_cl(out)
+    check(_lib.load().mmtta_window_blend(C.byref(tz), C.byref(to), C.byref(wg), ptr(origins), ptr(tables), stream_ptr()),
+          "window_blend")
+
+
 def sam_ascent_partials(n: int, sets: int) -> int:
     return int(_lib.load().mmtta_sam_ascent_partials(int(n), int(sets)))
 
