@@ -1144,6 +1144,50 @@ int mmtta_input_norm_grad(const mmtta_tensor* x, const mmtta_input_norm_branch* 
                           float* exp_avg_sq, int32_t* step, double lr, double bound_log_scale, double bound_shift,
                           double bound_log_gamma, void* stream);
 
+/* ------------------------------------------------------------------ bias field */
+/* A smooth multiplicative field per volume and modality in front of the network - csrc/bias_field.hip: the receive-coil
+ * intensity non-uniformity of MRI, learned in the step as the input normaliser's (s, b, g) are.  Volume n and channel c carry
+ * theta[n][c][k], fp32 [N][C][20] on the device (rows of 20 whatever the order; the first K are read and written):
+ *     F_c(z, y, x) = sum_k theta_ck phi_k(z, y, x)         x'_c = (x_c - a_c) exp(F_c) + a_c
+ *   phi_(a,b,c) = P_a(t_z) P_b(t_y) P_c(t_x), Legendre polynomials of the voxel-centre coordinates t_i = (2 i + 1) / n - 1 (n = 1:
+ *   t = 0), the terms with a + b + c <= `order` in the order (a + b + c, a, b, c) ascending: K = 1, 4, 10, 20 for order 0 .. 3.
+ *   Term 0 is the constant: the global log-gain.  `tables_d`, `tables_h`, `tables_w`: fp32 [4][extent] on the device, T[a][i] =
+ *   P_a(t_i) (the host evaluates them in float64 and rounds once).  a_c is the intensity the field leaves fixed: `anchor` =
+ *   MMTTA_BIAS_ANCHOR_MIN the channel's minimum range[n][c][0] (`range` is what mmtta_intensity_range wrote for the raw
+ *   volume), MMTTA_BIAS_ANCHOR_ZERO 0.  The arithmetic, all fp32 and nothing contracted: phi_k = (T_d[a][z] T_h[b][y]) T_w[c][x]
+ *   rounded in that order; F = fmaf(theta_k, phi_k, F) from 0.f in ascending k; E = expf(F); d = x - a; v = d E; x' = v + a.
+ *   Bit c of `keep_mask` says channel c is present: an absent channel is left alone and has no gradient.
+ * mmtta_bias_field_apply: y = x' in one streaming pass, x and y as mmtta_input_norm_apply takes them (the raw fp32 rows of 4
+ *   lanes, never written; fp32 or bf16 rows that own their pad lanes; 16-byte loads and stores, the bf16 pairs as there).  A
+ *   channel whose K coefficients are all zero, an absent channel and the pad lanes pass through: the same bits in fp32, one
+ *   rounding in bf16.  A workgroup holds the three tables in LDS, 16 (D + H + W) bytes.
+ * mmtta_bias_field_grad: the reduced input gradient of the network's first level against the basis,
+ *     grad[n][c][k] = sum_v dX'[n,c,v] (x[n,c,v] - a_c) exp(F_c(v)) phi_k(v)  +  2 l2 theta_ck (k >= 1),    fp32 [N][C][20]
+ *   (the terms past K are written 0), dX' and `branches` as mmtta_input_norm_grad's - the same gather, one copy in
+ *   csrc/input_gather.h -, F recomputed as the map computes it, every product in fp32 and every sum over voxels in fp64 in a
+ *   fixed order: 4 K fp64 partials per tile of 4 x 8 x 64 input voxels, a second launch (one workgroup per volume) sums
+ *   them.  With lr > 0 that launch also takes torch.optim.Adam's step on theta (as mmtta_input_norm_grad: betas 0.9 / 0.999,
+ *   eps 1e-8, no decay, fp64 arithmetic, fp32 state `exp_avg` / `exp_avg_sq` [N][C][20], `step` a device int32 [N], zero
+ *   moments at step 0) and clamps theta_c0 to +- bound_gain and theta_ck, k >= 1, to +- bound_field.  An absent channel has
+ *   grad = 0 exactly and keeps its theta.  lr == 0: theta is only read, the last three pointers may be null.
+ *   partial  fp64 [mmtta_bias_field_grad_partials(x, order)] = N x tiles x 4 K (-1 on a null or empty tensor or an order
+ *   outside 0 .. 3; host-only).
+ * No floating-point atomics and no scatter: two runs give the same bits and N items in one call equal N calls bit for bit.
+ * Both queue on `stream` without synchronisation or host read (capturable).  MMTTA_ERR_INVALID before anything is launched:
+ * what mmtta_input_norm_apply / _grad refuse so, a null table, a negative order, an anchor that is neither constant, l2 not
+ * finite or negative.  MMTTA_ERR_UNSUPPORTED: what they refuse so, order > 3, an extent above 512 voxels (the LDS budget of
+ * the tables), misaligned theta, range or tables. */
+#define MMTTA_BIAS_ANCHOR_MIN 0
+#define MMTTA_BIAS_ANCHOR_ZERO 1
+int mmtta_bias_field_apply(const mmtta_tensor* x, const mmtta_tensor* y, const float* theta, const float* range,
+                           const float* tables_d, const float* tables_h, const float* tables_w, int order, int anchor,
+                           uint32_t keep_mask, void* stream);
+int64_t mmtta_bias_field_grad_partials(const mmtta_tensor* x, int order);
+int mmtta_bias_field_grad(const mmtta_tensor* x, const mmtta_input_norm_branch* branches, int n_branches, float* theta,
+                          const float* range, const float* tables_d, const float* tables_h, const float* tables_w, int order,
+                          int anchor, uint32_t keep_mask, double* partial, float* grad, float* exp_avg, float* exp_avg_sq,
+                          int32_t* step, double lr, double bound_gain, double bound_field, double l2, void* stream);
+
 /* ------------------------------------------------------------------ modality consistency */
 /* The cross-modal objective of modcons_tta - csrc/modcons.hip (in the family of MM-TTA, Shin et al., CVPR 2022): the
  * prediction from all modalities should agree with the prediction from each subset of them.  A batch of G volumes x V views

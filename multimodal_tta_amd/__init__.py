@@ -4,7 +4,7 @@ Importing the package registers, under the reference's own registry names
 (reference src/registry.py:60-124):
   models                 unet, unet_multimodal_deepfusion, unet_multimodal_midfusion
   evaluation strategies  seg_eval, seg_tta_eval
-  plugins                entmin_tta, sar_tta, memo_tta, cotta_tta, petal_tta, eata_tta, deyo_tta, lame_tta, crf_tta, bnm_tta, innorm_tta, modcons_tta, window_tta, seg_supervised_step
+  plugins                entmin_tta, sar_tta, memo_tta, cotta_tta, petal_tta, eata_tta, deyo_tta, lame_tta, crf_tta, bnm_tta, innorm_tta, biasfield_tta, modcons_tta, window_tta, seg_supervised_step
   dataset builders       brats, hecktor21, default (synthetic volumes)
 All arithmetic runs in csrc/libmmtta.so (HIP, gfx950); there is no CPU or PyTorch fallback.
 """
@@ -48,6 +48,7 @@ from . import lame  # noqa: F401,E402  (plugin lame_tta)
 from . import crf  # noqa: F401,E402  (plugin crf_tta)
 from . import bnm  # noqa: F401,E402  (plugin bnm_tta)
 from . import innorm  # noqa: F401,E402  (plugin innorm_tta)
+from . import biasfield  # noqa: F401,E402  (plugin biasfield_tta)
 from . import modcons  # noqa: F401,E402  (plugin modcons_tta)
 from . import window  # noqa: F401,E402  (plugin window_tta)
 from . import datasets  # noqa: F401,E402

@@ -245,6 +245,12 @@ _SIGNATURES = {
     "mmtta_input_norm_grad": (C.c_int, [_P(Tensor), _P(InputNormBranch), C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                         C.c_double, C.c_double, C.c_void_p]),
+    "mmtta_bias_field_apply": (C.c_int, [_P(Tensor), _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_int, C.c_uint32, C.c_void_p]),
+    "mmtta_bias_field_grad_partials": (C.c_int64, [_P(Tensor), C.c_int]),
+    "mmtta_bias_field_grad": (C.c_int, [_P(Tensor), _P(InputNormBranch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "mmtta_modality_views": (C.c_int, [_P(Tensor), _P(Tensor), C.c_int, _P(C.c_uint32), C.c_void_p]),
     "mmtta_modcons_partials": (C.c_int64, [_P(Tensor), C.c_int]),
     "mmtta_modcons_loss_items": (C.c_int, [_P(Tensor), C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P(Tensor), C.c_void_p,

@@ -47,40 +47,29 @@ def _number(value: Any) -> bool:
     return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value)
 
 
-@register_plugin("innorm_tta")
-class InputNormTTA(EntropyMinimizationTTA):
-    """``method.innorm.lr`` (finite, >= 0, default 1e-2; 0: ``entmin_tta``), ``gamma`` (bool, default false: the power form of
-    u), ``bound.log_scale`` ((0, 4], default 0.7), ``bound.shift`` ((0, 16], default 1.0) and ``bound.log_gamma`` ((0, 2],
-    default 0.7): theta is clamped to +- its bound after every step.  theta's optimizer is Adam with torch's default betas
-    and eps and no decay, whatever ``training.optimizer`` is.  Everything else is ``entmin_tta``'s, with one limit: every
-    volume has its own theta, so a call takes at most ``method.group`` volumes."""
+class InputMapTTA(EntropyMinimizationTTA):
+    """What the plugins that adapt an input map share (``innorm_tta`` here, ``biasfield_tta`` in biasfield.py): a raw fp32 copy
+    of the staged volumes, one step - the map, the parent's forward, loss and backward, the step on the map's theta from the
+    first level's reduced input gradient, the optimizer - and the final logits through the map at the final theta.  A
+    subclass sets ``plugin`` (its name in messages), ``prefix`` (of its pool buffers), ``row`` (floats of a theta / grad row)
+    and ``lr``, and provides ``_apply`` and ``_input_step``."""
+    plugin, prefix, row = "", "", 4
 
     def __init__(self, config: Any = None):
         super().__init__(config)
         m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "innorm", {}) or {}
-        lr, gm = get_config(s, "lr", 1e-2), get_config(s, "gamma", False)
-        bd = get_config(s, "bound", {}) or {}
-        bs, bb, bg = get_config(bd, "log_scale", 0.7), get_config(bd, "shift", 1.0), get_config(bd, "log_gamma", 0.7)
-        if not _number(lr) or lr < 0.0:
-            raise ValueError(f"method.innorm.lr = {lr!r}: expected a finite number >= 0 (0: entmin_tta)")
-        if not isinstance(gm, bool):
-            raise ValueError(f"method.innorm.gamma = {gm!r}: expected a bool")
-        for key, val, top in (("log_scale", bs, MAX_LOG_SCALE), ("shift", bb, MAX_SHIFT), ("log_gamma", bg, MAX_LOG_GAMMA)):
-            if not _number(val) or not (0.0 < val <= top):
-                raise ValueError(f"method.innorm.bound.{key} = {val!r}: expected a finite number in (0, {top:g}]")
         if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
-            raise NotImplementedError("method.moddrop.enabled: innorm_tta learns one theta per volume on a fixed set of "
+            raise NotImplementedError(f"method.moddrop.enabled: {self.plugin} learns one theta per volume on a fixed set of "
                                       "modalities; modality dropout redraws them every step")
-        self.lr, self.gamma, self.bounds = float(lr), bool(gm), (float(bs), float(bb), float(bg))
+        self.lr = 0.0
         self._raw: Optional[torch.Tensor] = None           # the raw fp32 staged volumes of the call
         self._x_in: Optional[torch.Tensor] = None
         self._t = 0
 
     # ------------------------------------------------------------------ setup
-    def setup(self, model, device) -> "InputNormTTA":
+    def setup(self, model, device) -> "InputMapTTA":
         if self.lr > 0.0 and getattr(model, "runtime_cls", None) is not UNetRuntime:
-            raise NotImplementedError(f"innorm_tta drives the 'unet' model; {type(model).__name__} (the deep-fusion family: "
+            raise NotImplementedError(f"{self.plugin} drives the 'unet' model; {type(model).__name__} (the deep-fusion family: "
                                       "modality encoders in one launch, re-staged inputs) has no reduced input gradient")
         super().setup(model, device)
         if self.lr == 0.0:
@@ -92,25 +81,25 @@ class InputNormTTA(EntropyMinimizationTTA):
             if (op.transposed or op.k != 3 or op.stride != 2 or op.cout % 4 or op.cout > MAX_COUT or op.cin > MAX_CIN
                     or len(layer.members) != 1):
                 what = f"{'convT' if op.transposed else 'conv'} {op.cin}->{op.cout} k{op.k}s{op.stride}"
-                raise NotImplementedError(f"innorm_tta: the model's first level reads its input through a {what}; the "
+                raise NotImplementedError(f"{self.plugin}: the model's first level reads its input through a {what}; the "
                                           f"reduced input gradient gathers k = 3, stride 2 convolutions of <= {MAX_CIN} "
                                           f"channels into a multiple of 4 up to {MAX_COUT}")
         # the gradient reads the arena's weights of the step: no first-level layer may update inside the backward
         if any(layer in rt.fused_layers for layer in layers):
-            raise MmttaError("innorm_tta: a first-level convolution is in the fused weight update; its weights would move "
+            raise MmttaError(f"{self.plugin}: a first-level convolution is in the fused weight update; its weights would move "
                              "before the input gradient reads them")
         self._input_layers = layers
         return self
 
     # ------------------------------------------------------------------ theta
     def _tables(self) -> Dict[str, torch.Tensor]:
-        rt, c = self.rt, self.rt.in_channels
+        rt, c, p, w = self.rt, self.rt.in_channels, self.prefix, self.row
         g = rt.group
-        return {"theta": rt.pool.flat("innorm_theta", g * c * 4, zero=True), "grad": rt.pool.flat("innorm_grad", g * c * 4, zero=True),
-                "exp_avg": rt.pool.flat("innorm_exp_avg", g * c * 4, zero=True),
-                "exp_avg_sq": rt.pool.flat("innorm_exp_avg_sq", g * c * 4, zero=True),
-                "step": rt.pool.flat("innorm_step", g, dtype=torch.int32, zero=True),
-                "range": rt.pool.flat("innorm_range", g * c * 2, zero=True)}
+        return {"theta": rt.pool.flat(f"{p}_theta", g * c * w, zero=True), "grad": rt.pool.flat(f"{p}_grad", g * c * w, zero=True),
+                "exp_avg": rt.pool.flat(f"{p}_exp_avg", g * c * w, zero=True),
+                "exp_avg_sq": rt.pool.flat(f"{p}_exp_avg_sq", g * c * w, zero=True),
+                "step": rt.pool.flat(f"{p}_step", g, dtype=torch.int32, zero=True),
+                "range": rt.pool.flat(f"{p}_range", g * c * 2, zero=True)}
 
     def _reset(self) -> None:
         super()._reset()
@@ -120,24 +109,39 @@ class InputNormTTA(EntropyMinimizationTTA):
             t["step"].zero_()        # (step 0 starts from zero moments whatever the buffers hold)
 
     def _apply(self, raw: torch.Tensor, x: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
-        t = self._tables()
-        ops.input_norm_apply(raw, x, t["theta"], t["range"], present=present, gamma=self.gamma)
+        """x = the map of the raw volumes at the current theta."""
+        raise NotImplementedError
+
+    def _input_step(self, raw: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+        """dL/dtheta from what the backward left, Adam's step on theta and the clamp."""
+        raise NotImplementedError
+
+    def _input_branches(self):
+        """The convolutions that read the input, as ``ops.input_norm_grad`` takes them."""
+        rt, ar = self.rt, self.rt.arena
+        branches = []
+        for dy, layer, k, stride in rt.input_branches():
+            w = layer.weight
+            shared = layer.frozen or not rt.use_sets or ar.replicas == 1      # (a frozen layer's replicas all hold the source)
+            branches.append((dy, ar.replica_data(w, 0), 0 if shared else ar.total, k, stride))
+        return branches
 
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
         if self.lr == 0.0:
             return super()._stage(x_cl)
-        rt = self.rt
+        rt, p = self.rt, self.prefix
         n, d, h, w, c = x_cl.shape
         if n > rt.group:          # (every volume has its own theta)
-            raise ValueError(f"method.group = {rt.group}: innorm_tta adapts at most {rt.group} volumes per call, got {n}")
+            raise ValueError(f"method.group = {rt.group}: {self.plugin} adapts at most {rt.group} volumes per call, got {n}")
         # the raw volume stays in fp32: a value is rounded once, after the map
         raw = rt.pool.cl("x_raw", n, d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=torch.float32)
         ops.to_cl(self._x_in, out=raw)
         t = self._tables()
-        partial = rt.pool.flat("innorm_range_partial", ops.intensity_range_partials(raw))
+        partial = rt.pool.flat(f"{p}_range_partial", ops.intensity_range_partials(raw))
         ops.intensity_range(raw, partial, t["range"])
         self._raw = raw
-        self._hist = rt.pool.flat("innorm_grad_hist", max(self.steps, self._steps_now, 1) * rt.group * c * 4).view(-1, rt.group, c, 4)
+        self._hist = rt.pool.flat(f"{p}_grad_hist", max(self.steps, self._steps_now, 1) * rt.group * c * self.row).view(
+            -1, rt.group, c, self.row)
         self._t = 0
         return x_cl, (raw,)
 
@@ -175,27 +179,14 @@ class InputNormTTA(EntropyMinimizationTTA):
             rt.run_backward(dlogits)
         finally:
             rt.fused_active = False
-        self._input_step(raw, present)
-        if ar.n_train > 0:
-            self.optimizer_step(int(logits.shape[0]), fused=fused)
-
-    def _input_step(self, raw: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
-        """dL/dtheta from what the backward left, Adam's step on theta and the clamp: two launches."""
-        rt, ar = self.rt, self.rt.arena
-        t = self._tables()
-        branches = []
-        for dy, layer, k, stride in rt.input_branches():
-            w = layer.weight
-            shared = layer.frozen or not rt.use_sets or ar.replicas == 1      # (a frozen layer's replicas all hold the source)
-            branches.append((dy, ar.replica_data(w, 0), 0 if shared else ar.total, k, stride))
-        partial = rt.pool.flat("innorm_partial", ops.input_norm_grad_partials(raw), dtype=torch.float64)
         try:
-            ops.input_norm_grad(raw, branches, t["theta"], t["range"], partial, t["grad"], present=present, gamma=self.gamma,
-                                exp_avg=t["exp_avg"], exp_avg_sq=t["exp_avg_sq"], step=t["step"], lr=self.lr, bounds=self.bounds)
+            self._input_step(raw, present)
         except MmttaError as exc:
             if "status -2" in str(exc):        # MMTTA_ERR_UNSUPPORTED: a first level the kernel does not gather
-                raise NotImplementedError(f"innorm_tta: the model's first level is not supported: {exc}") from exc
+                raise NotImplementedError(f"{self.plugin}: the model's first level is not supported: {exc}") from exc
             raise
+        if ar.n_train > 0:
+            self.optimizer_step(int(logits.shape[0]), fused=fused)
 
     def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]], *views: torch.Tensor) -> None:
         super()._step(x_cl, present, *views)
@@ -209,18 +200,59 @@ class InputNormTTA(EntropyMinimizationTTA):
             self._apply(self._raw, x_cl, present)
         return self._forward(x_cl, present)
 
+    def _adapt(self, x: torch.Tensor, steps: Optional[int]) -> Dict[str, Any]:
+        """``EntropyMinimizationTTA.adapt_volume`` with the fp32 volumes at hand for ``_stage``."""
+        self._steps_now = self.steps if steps is None else int(steps)
+        self._x_in = x.float()
+        try:
+            return EntropyMinimizationTTA.adapt_volume(self, x, steps)
+        finally:
+            self._x_in = None
+
+
+@register_plugin("innorm_tta")
+class InputNormTTA(InputMapTTA):
+    """``method.innorm.lr`` (finite, >= 0, default 1e-2; 0: ``entmin_tta``), ``gamma`` (bool, default false: the power form of
+    u), ``bound.log_scale`` ((0, 4], default 0.7), ``bound.shift`` ((0, 16], default 1.0) and ``bound.log_gamma`` ((0, 2],
+    default 0.7): theta is clamped to +- its bound after every step.  theta's optimizer is Adam with torch's default betas
+    and eps and no decay, whatever ``training.optimizer`` is.  Everything else is ``entmin_tta``'s, with one limit: every
+    volume has its own theta, so a call takes at most ``method.group`` volumes."""
+    plugin, prefix, row = "innorm_tta", "innorm", 4
+
+    def __init__(self, config: Any = None):
+        super().__init__(config)
+        m = get_config(as_cfg(config), "method", {}) or {}
+        s = get_config(m, "innorm", {}) or {}
+        lr, gm = get_config(s, "lr", 1e-2), get_config(s, "gamma", False)
+        bd = get_config(s, "bound", {}) or {}
+        bs, bb, bg = get_config(bd, "log_scale", 0.7), get_config(bd, "shift", 1.0), get_config(bd, "log_gamma", 0.7)
+        if not _number(lr) or lr < 0.0:
+            raise ValueError(f"method.innorm.lr = {lr!r}: expected a finite number >= 0 (0: entmin_tta)")
+        if not isinstance(gm, bool):
+            raise ValueError(f"method.innorm.gamma = {gm!r}: expected a bool")
+        for key, val, top in (("log_scale", bs, MAX_LOG_SCALE), ("shift", bb, MAX_SHIFT), ("log_gamma", bg, MAX_LOG_GAMMA)):
+            if not _number(val) or not (0.0 < val <= top):
+                raise ValueError(f"method.innorm.bound.{key} = {val!r}: expected a finite number in (0, {top:g}]")
+        self.lr, self.gamma, self.bounds = float(lr), bool(gm), (float(bs), float(bb), float(bg))
+
+    def _apply(self, raw: torch.Tensor, x: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+        t = self._tables()
+        ops.input_norm_apply(raw, x, t["theta"], t["range"], present=present, gamma=self.gamma)
+
+    def _input_step(self, raw: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
+        """dL/dtheta from what the backward left, Adam's step on theta and the clamp: two launches."""
+        t = self._tables()
+        partial = self.rt.pool.flat("innorm_partial", ops.input_norm_grad_partials(raw), dtype=torch.float64)
+        ops.input_norm_grad(raw, self._input_branches(), t["theta"], t["range"], partial, t["grad"], present=present, gamma=self.gamma,
+                            exp_avg=t["exp_avg"], exp_avg_sq=t["exp_avg_sq"], step=t["step"], lr=self.lr, bounds=self.bounds)
+
     # ------------------------------------------------------------------ per volume
     @torch.no_grad()
     def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
         """``EntropyMinimizationTTA.adapt_volume`` plus ``input_grad`` [steps, B, C, 3] (dL/d(s, b, g) of every step; the g
         column is 0 with gamma off) and ``input_scale``, ``input_shift``, ``input_gamma`` [B, C]: exp(s), b, exp(g) at the end."""
         B, C = int(x.shape[0]), int(x.shape[1])
-        self._steps_now = self.steps if steps is None else int(steps)
-        self._x_in = x.float()
-        try:
-            out = super().adapt_volume(x, steps)
-        finally:
-            self._x_in = None
+        out = self._adapt(x, steps)
         if self.lr == 0.0:
             out["input_grad"] = torch.zeros((self._steps_now, B, C, 3), dtype=torch.float32, device=x.device)
             out["input_scale"] = torch.ones((B, C), dtype=torch.float32, device=x.device)

@@ -1417,6 +1417,17 @@ def _input_norm_tables(what: str, n: int, c: int, **tables: Optional[torch.Tenso
                              f"([{n}, {c}, {width}])")
 
 
+def _input_branches(what: str, branches: Sequence[Tuple[torch.Tensor, torch.Tensor, int, int, int]], c: int):
+    """The mmtta_input_norm_branch array of ``branches`` and the descriptors it points to (kept alive by the caller)."""
+    descs = [desc_cl(dy) for dy, *_ in branches]
+    arr = (_lib.InputNormBranch * max(len(branches), 1))()
+    for r, (dy, weight, set_stride, k, stride) in enumerate(branches):
+        if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.numel() != int(dy.shape[-1]) * c * int(k) ** 3:
+            raise MmttaError(f"{what}: weight of branch {r} must be contiguous fp32 [{int(dy.shape[-1])}, {c}, {k}, {k}, {k}]")
+        arr[r] = _lib.InputNormBranch(C.pointer(descs[r]), ptr(weight), int(set_stride), int(k), int(stride))
+    return arr, descs
+
+
 def input_norm_apply(x: torch.Tensor, y: torch.Tensor, theta: torch.Tensor, value_range: torch.Tensor,
                      present: Optional[Sequence[bool]] = None, gamma: bool = False) -> None:
     """The input normaliser's map (include/mmtta.h, mmtta_input_norm_apply): y = exp(s) u + b per volume and channel, from
@@ -1456,17 +1467,81 @@ def input_norm_grad(x: torch.Tensor, branches: Sequence[Tuple[torch.Tensor, torc
         raise MmttaError("input_norm_grad: partial must be contiguous fp64 of input_norm_grad_partials(x) elements")
     if step is not None and (step.dtype != torch.int32 or not step.is_contiguous() or step.numel() < n):
         raise MmttaError(f"input_norm_grad: step must be contiguous device int32 of at least {n} elements")
-    descs = [desc_cl(dy) for dy, *_ in branches]
-    arr = (_lib.InputNormBranch * max(len(branches), 1))()
-    for r, (dy, weight, set_stride, k, stride) in enumerate(branches):
-        if weight.dtype != torch.float32 or not weight.is_contiguous() or weight.numel() != int(dy.shape[-1]) * c * int(k) ** 3:
-            raise MmttaError(f"input_norm_grad: weight of branch {r} must be contiguous fp32 [{int(dy.shape[-1])}, {c}, {k}, {k}, {k}]")
-        arr[r] = _lib.InputNormBranch(C.pointer(descs[r]), ptr(weight), int(set_stride), int(k), int(stride))
+    arr, descs = _input_branches("input_norm_grad", branches, c)
     tx = desc_cl(x)
     check(_lib.load().mmtta_input_norm_grad(C.byref(tx), arr, len(branches), ptr(theta), ptr(value_range),
                                             _keep_mask(present, c), 1 if gamma else 0, ptr(partial), ptr(grad), ptr(exp_avg),
                                             ptr(exp_avg_sq), ptr(step), float(lr), float(bounds[0]), float(bounds[1]),
                                             float(bounds[2]), stream_ptr()), "input_norm_grad")
+
+
+BIAS_ANCHORS = {"min": 0, "zero": 1}      # MMTTA_BIAS_ANCHOR_*
+BIAS_ROW = 20                             # coefficients of a theta / grad row of the bias field, whatever the order
+
+
+def _bias_field_args(what: str, x: torch.Tensor, tables: Sequence[torch.Tensor], order: int, anchor: str) -> int:
+    if anchor not in BIAS_ANCHORS:
+        raise MmttaError(f"{what}: anchor = {anchor!r} (min | zero)")
+    if isinstance(order, bool) or not isinstance(order, int):
+        raise MmttaError(f"{what}: order = {order!r} (an int)")
+    if len(tables) != 3:
+        raise MmttaError(f"{what}: tables must be the three Legendre tables (D, H, W), got {len(tables)}")
+    for t, extent, axis in zip(tables, x.shape[1:4], "DHW"):
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.numel() != 4 * int(extent):
+            raise MmttaError(f"{what}: the table of axis {axis} must be contiguous device fp32 [4, {int(extent)}]")
+    return BIAS_ANCHORS[anchor]
+
+
+def bias_field_apply(x: torch.Tensor, y: torch.Tensor, theta: torch.Tensor, value_range: torch.Tensor,
+                     tables: Sequence[torch.Tensor], order: int, anchor: str = "min",
+                     present: Optional[Sequence[bool]] = None) -> None:
+    """The bias field's map (include/mmtta.h, mmtta_bias_field_apply): y = (x - a) exp(F) + a per volume and channel, from the
+    raw fp32 staged volume ``x`` into ``y`` (fp32 or bf16 rows), with ``theta`` [N, C, 20] the coefficients of F in the
+    Legendre basis of total degree ``order``, ``tables`` the three [4, extent] tables of ``biasfield.legendre_tables`` and
+    ``value_range`` what ``intensity_range`` wrote for x (``anchor`` "min": a = the channel's minimum; "zero": a = 0).  The
+    channels ``present`` marks absent, and channels whose coefficients are all zero, pass through."""
+    n, c = int(x.shape[0]), int(x.shape[-1])
+    _input_norm_tables("bias_field_apply", n, c, theta=(theta, BIAS_ROW), value_range=(value_range, 2))
+    code = _bias_field_args("bias_field_apply", x, tables, order, anchor)
+    tx, ty = desc_cl(x), desc_cl(y)
+    check(_lib.load().mmtta_bias_field_apply(C.byref(tx), C.byref(ty), ptr(theta), ptr(value_range), ptr(tables[0]), ptr(tables[1]),
+                                             ptr(tables[2]), order, code, _keep_mask(present, c), stream_ptr()), "bias_field_apply")
+
+
+def bias_field_grad_partials(x: torch.Tensor, order: int) -> int:
+    """fp64 elements of the scratch ``bias_field_grad`` needs for the staged volume ``x`` at ``order``."""
+    t = desc_cl(x)
+    n = int(_lib.load().mmtta_bias_field_grad_partials(C.byref(t), int(order)))
+    if n < 0:
+        raise MmttaError(f"bias_field_grad_partials: no scratch size for x {tuple(x.shape)} at order {order}")
+    return n
+
+
+def bias_field_grad(x: torch.Tensor, branches: Sequence[Tuple[torch.Tensor, torch.Tensor, int, int, int]], theta: torch.Tensor,
+                    value_range: torch.Tensor, tables: Sequence[torch.Tensor], order: int, partial: torch.Tensor,
+                    grad: torch.Tensor, *, anchor: str = "min", present: Optional[Sequence[bool]] = None,
+                    exp_avg: Optional[torch.Tensor] = None, exp_avg_sq: Optional[torch.Tensor] = None,
+                    step: Optional[torch.Tensor] = None, lr: float = 0.0, bounds: Sequence[float] = (0.0, 0.0),
+                    l2: float = 0.0) -> None:
+    """The reduced input gradient of the first level against the field's basis (include/mmtta.h, mmtta_bias_field_grad):
+    ``grad`` [N, C, 20] = dL/dtheta_ck + 2 ``l2`` theta_ck (k >= 1), the terms past the order's 0; ``x``, ``branches`` and the
+    optimizer state as ``input_norm_grad`` takes them (rows of 20), ``tables`` / ``order`` / ``anchor`` as ``bias_field_apply``.
+    With ``lr`` > 0 the same call takes Adam's step on ``theta`` and clamps the constant coefficient to +- ``bounds[0]`` and
+    every other one to +- ``bounds[1]``."""
+    n, c = int(x.shape[0]), int(x.shape[-1])
+    _input_norm_tables("bias_field_grad", n, c, theta=(theta, BIAS_ROW), value_range=(value_range, 2), grad=(grad, BIAS_ROW),
+                       exp_avg=(exp_avg, BIAS_ROW), exp_avg_sq=(exp_avg_sq, BIAS_ROW))
+    code = _bias_field_args("bias_field_grad", x, tables, order, anchor)
+    if partial.dtype != torch.float64 or not partial.is_contiguous() or partial.numel() < bias_field_grad_partials(x, order):
+        raise MmttaError("bias_field_grad: partial must be contiguous fp64 of bias_field_grad_partials(x, order) elements")
+    if step is not None and (step.dtype != torch.int32 or not step.is_contiguous() or step.numel() < n):
+        raise MmttaError(f"bias_field_grad: step must be contiguous device int32 of at least {n} elements")
+    arr, descs = _input_branches("bias_field_grad", branches, c)
+    tx = desc_cl(x)
+    check(_lib.load().mmtta_bias_field_grad(C.byref(tx), arr, len(branches), ptr(theta), ptr(value_range), ptr(tables[0]),
+                                            ptr(tables[1]), ptr(tables[2]), order, code, _keep_mask(present, c), ptr(partial),
+                                            ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), ptr(step), float(lr), float(bounds[0]),
+                                            float(bounds[1]), float(l2), stream_ptr()), "bias_field_grad")
 
 
 def modality_views(x: torch.Tensor, y: torch.Tensor, keep_masks: Sequence[int]) -> None:
