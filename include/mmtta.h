@@ -352,6 +352,18 @@ int mmtta_conv_cls8_pipelined(const mmtta_conv_desc* desc, const mmtta_tensor* x
 int mmtta_conv_thin_lean(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                          const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
 
+/* Which kernel inside routes 6 and 13 mmtta_conv_run would launch for this call:
+ *    1 direct_conv_kernel (thread per voxel)                2 direct_klane_kernel (lanes along K = 32 / 64)
+ *    3 direct_row_kernel (K <= 4, 3x3x3 stride 1)           4 conv3_mfma4_kernel, fp32-stored thin tensors
+ *    5 conv3_mfma4_kernel, every thin tensor bf16-stored    6 direct_upconv_kernel (LDS-staged up-convolution, fp32)
+ *    7 upconv_mfma_kernel (the same on the matrix cores)    8 upconv8_kernel (2x2x2 gather GEMM)
+ *    9 upconv8_lean_kernel                                  10 pointwise_head_kernel (streaming 1x1x1 head)
+ *   11 direct_chan_kernel (thin-K, VALU)                    12 chan_mfma_kernel     13 chan_mfma_lean_kernel
+ * 0 for a call of any other route, or the negative mmtta error code the run would return before launching.  Host-only, the
+ * operands of mmtta_conv_route; the launchers of the two routes switch on the function this returns. */
+int mmtta_conv_thin_kernel(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                           const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
+
 /* ---- per-volume parameter sets: N volumes (or N identical sub-networks) in ONE launch, each with ITS OWN parameters.
  * Episodic adaptation has no cross-volume state: every test volume adapts its own copy of the source weights (SURVEY.md
  * Appendix C), and the M modality encoders of the deep-fusion network are M identical graphs with different weights run
@@ -420,8 +432,10 @@ int64_t mmtta_conv_wgrad_workspace_bytes(const mmtta_conv_desc* desc, const mmtt
                                          const mmtta_tensor* dy);
 /* Which weight-gradient kernel mmtta_conv_wgrad picks for this problem (profiling / roofline bookkeeping):
  *   0 fp32 MFMA k3 s1   1 fp32 MFMA k3 s2 (and conv_transpose)   2 fp32 MFMA k1
- *   3 small-channel (<= 4 channels on one side, fp32 MFMA)       4 bf16 MFMA k3 s1   5 bf16 MFMA k3 s2
- *   6 tiny (<= 4 channels on both sides, k3 s1: fp32 VALU)
+ *   3 small-channel (wgrad_small_kernel: <= 4 channels on one side)  6 tiny (wgrad_tiny_kernel: <= 4 channels on both sides, fp32 VALU)
+ *   7 bf16 operands, transposed reads (wgrad_tr_kernel), k3 s1   8 the same at stride 2 (and conv_transpose)
+ *   9 the 1x1x1 streaming kernel of bf16 precision (wgrad_tr1_kernel)
+ *   10 the thin 27-tap layers of bf16 precision (wgrad_thin_tr_kernel)          (4 and 5 are retired)
  * or a negative mmtta error code. */
 int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_tensor* dy);
 /* Which operands of this weight gradient the transposed-read kernel would stage raw (MMTTA_OPT_RAW_STAGING bit 1): bit 0

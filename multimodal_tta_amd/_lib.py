@@ -141,6 +141,7 @@ _SIGNATURES = {
     "mmtta_conv_stages_raw": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_cls8_pipelined": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_thin_lean": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
+    "mmtta_conv_thin_kernel": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_head_loss_eligible": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), _P(Tensor),
                                                 C.c_int, C.c_int]),
     "mmtta_conv_head_loss_partials": (C.c_int64, [_P(ConvDesc), _P(Tensor), _P(Tensor)]),

@@ -596,6 +596,16 @@ int pointwise_small_run(const mmtta_tensor* x, const void* packed, int Kp, int N
                         int accumulate, const PSets& sets, hipStream_t stream);
 bool chan_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y);
 int chan_tiles_per_n(const mmtta_tensor* y);
+// the kernels of routes 6 and 13: the ids mmtta_conv_thin_kernel reports (include/mmtta.h) and the launchers switch on
+enum ThinKernel : int {
+  THIN_DIRECT = 1, THIN_KLANE = 2, THIN_ROW = 3, THIN_MFMA4 = 4, THIN_MFMA4_BF = 5, THIN_UPCONV = 6, THIN_UPCONV_MFMA = 7,
+  THIN_UPCONV8 = 8, THIN_UPCONV8_LEAN = 9, THIN_HEAD = 10, THIN_CHAN = 11, THIN_CHAN_MFMA = 12, THIN_CHAN_MFMA_LEAN = 13,
+};
+// which of them chan_conv_run / direct_conv_run launches for this call, or the (negative) error the launcher returns instead
+int chan_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
+                const mmtta_tensor* y, int accumulate);
+int direct_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
+                  const mmtta_tensor* y, int accumulate, const float* stats);
 // whether chan_conv_run takes the lean kernel for this call (MMTTA_OPT_THIN_LEAN bit 0)
 bool chan_lean_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                           const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate);

@@ -910,19 +910,17 @@ static void launch_chan_lean(const CArgs& a, int K, int N, int blocks, hipStream
 }
 #endif
 
-int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed, int Kp,
-                  int Np, const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
-                  const PSets& sets, hipStream_t stream) {
-  CArgs a;
-  a.ps = sets;
-  a.in = tv(x); a.tin = nl(x_norm); a.out = tv(y);
-  a.koff = is_bf16(x) ? 0 : (int)((((uintptr_t)x->ptr) % 16) / 4);
-  MMTTA_CHECK(a.koff == 0 || x->c == 1, MMTTA_ERR_UNSUPPORTED, "thin-K conv: only a one-channel slice may start inside a 16-byte group");
-  a.in.p -= a.koff;
-  a.w = (const float*)packed; a.Kp = Kp; a.Np = Np; a.bias = bias;
+// Which kernel chan_conv_run launches for a call of route 13 (THIN_* of common.h: the ids of mmtta_conv_thin_kernel), or the
+// error it returns instead, every check in the launcher's order.  The one function behind mmtta_conv_thin_kernel and the
+// launcher, which switches on it.
+static int chan_koff(const mmtta_tensor* x) { return is_bf16(x) ? 0 : (int)((((uintptr_t)x->ptr) % 16) / 4); }
+int chan_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
+                const mmtta_tensor* y, int accumulate) {
+  MMTTA_CHECK(chan_koff(x) == 0 || x->c == 1, MMTTA_ERR_UNSUPPORTED, "thin-K conv: only a one-channel slice may start inside a 16-byte group");
+  CArgs a;                                     // (only the fields of the fused add: its checks)
   const int st = epilogue_add(epi, y, a);
   if (st) return st;
-  a.add_bf = (a.add && is_bf16(epi->add)) ? 1 : 0;
+  const bool add_bf = a.add && is_bf16(epi->add);
   MMTTA_CHECK(a.add == nullptr || (long long)(epi->add->h + 4) * a.ash < (1LL << 31), MMTTA_ERR_UNSUPPORTED,
               "thin-K conv: epilogue `add` slice beyond 2^31 elements");
   // the <= 4-channel gathered tensor is fp32 (gradients, fp32 precision) or - the network input of bf16 precision - bf16
@@ -931,27 +929,46 @@ int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
   // channel as well: the VALU kernel writes fp32 only)
   const bool mfma_path = d->dtype == MMTTA_BF16 && (x->c >= 2 || y->c > 32 || is_bf16(y));
   MMTTA_CHECK(is_f32(x) || mfma_path, MMTTA_ERR_UNSUPPORTED, "thin-K conv: a bf16-stored gathered tensor needs the matrix-core path");
-  MMTTA_CHECK(mfma_path || (is_f32(y) && !a.add_bf), MMTTA_ERR_UNSUPPORTED, "thin-K conv (VALU path): fp32-stored tensors only");
-  MMTTA_CHECK(a.add == nullptr || (a.add_bf != 0) == is_bf16(y), MMTTA_ERR_UNSUPPORTED, "thin-K conv: the fused add must share the output's storage type");
+  MMTTA_CHECK(mfma_path || (is_f32(y) && !add_bf), MMTTA_ERR_UNSUPPORTED, "thin-K conv (VALU path): fp32-stored tensors only");
+  MMTTA_CHECK(a.add == nullptr || add_bf == is_bf16(y), MMTTA_ERR_UNSUPPORTED, "thin-K conv: the fused add must share the output's storage type");
+  // one input channel (the single-modality stems of the deep-fusion net) is 27 FMAs per output: the VALU kernel wins there
+  if (!mfma_path) return THIN_CHAN;
+  return chan_lean_applicable(d, x, x_norm, epi, y, accumulate) ? THIN_CHAN_MFMA_LEAN : THIN_CHAN_MFMA;
+}
+
+int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed, int Kp,
+                  int Np, const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
+                  const PSets& sets, hipStream_t stream) {
+  const int kernel = chan_kernel(d, x, x_norm, epi, y, accumulate);
+  if (kernel < 0) return kernel;
+  CArgs a;
+  a.ps = sets;
+  a.in = tv(x); a.tin = nl(x_norm); a.out = tv(y);
+  a.koff = chan_koff(x);
+  a.in.p -= a.koff;
+  a.w = (const float*)packed; a.Kp = Kp; a.Np = Np; a.bias = bias;
+  const int st = epilogue_add(epi, y, a);
+  if (st) return st;
+  a.add_bf = (a.add && is_bf16(epi->add)) ? 1 : 0;
   a.accumulate = accumulate; a.stats = stats;
   a.tz = (y->d + 3) / 4; a.ty = (y->h + 3) / 4; a.tx = (y->w + 7) / 8;
   a.tiles_per_n = a.tz * a.ty * a.tx;
   const int blocks = a.tiles_per_n * y->n;
   const bool has_t = a.tin.mean != nullptr || a.tin.scale != nullptr;
   const int S = d->op == MMTTA_CONV_FWD ? d->stride : 2;       // CONVT_DGRAD: stride-2 gather
-  // one input channel (the single-modality stems of the deep-fusion net) is 27 FMAs per output: the VALU kernel wins there
-  if (mfma_path) {
+  switch (kernel) {
 #ifndef MMTTA_ACT_LEAKY_TU
-    if (chan_lean_applicable(d, x, x_norm, epi, y, accumulate)) {
+    case THIN_CHAN_MFMA_LEAN:
       MMTTA_BF_DISPATCH(has_t, HT, { launch_chan_lean<HT>(a, x->c, y->c, blocks, stream); });
       return launch_status("thin-K conv (bf16 MFMA, lean)");
-    }
 #endif
-    MMTTA_BF_DISPATCH(has_t, HT, { if (S == 1) launch_chan_mfma<1, HT>(a, x->c, y->c, blocks, stream); else launch_chan_mfma<2, HT>(a, x->c, y->c, blocks, stream); });
-    return launch_status("thin-K conv (bf16 MFMA)");
+    case THIN_CHAN_MFMA:
+      MMTTA_BF_DISPATCH(has_t, HT, { if (S == 1) launch_chan_mfma<1, HT>(a, x->c, y->c, blocks, stream); else launch_chan_mfma<2, HT>(a, x->c, y->c, blocks, stream); });
+      return launch_status("thin-K conv (bf16 MFMA)");
+    default:
+      MMTTA_BF_DISPATCH(has_t, HT, { if (S == 1) launch_chan_k<1, HT>(a, x->c, y->c, blocks, stream); else launch_chan_k<2, HT>(a, x->c, y->c, blocks, stream); });
+      return launch_status("direct conv (lanes along N)");
   }
-  MMTTA_BF_DISPATCH(has_t, HT, { if (S == 1) launch_chan_k<1, HT>(a, x->c, y->c, blocks, stream); else launch_chan_k<2, HT>(a, x->c, y->c, blocks, stream); });
-  return launch_status("direct conv (lanes along N)");
 }
 
 // ------------------------------------------------------------------ 1x1x1 head, K = 32 / 64 -> N <= 4, voxel-dense tensors
@@ -1442,6 +1459,41 @@ bool direct_upconv8_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const 
          !nl_leaky(x_norm) && !(epi && epi->add && nl_leaky(&epi->add_norm));
 }
 
+// Which kernel direct_conv_run launches for a call of route 6 (THIN_* of common.h: the ids of mmtta_conv_thin_kernel), or the
+// error it returns instead, every check in the launcher's order.  The one function behind mmtta_conv_thin_kernel and the
+// launcher, which switches on it.
+static bool direct_out_vec4(const mmtta_tensor* y) { return (y->flags & MMTTA_TENSOR_OWNS_PAD) && y->sw == 4 && aligned16(y); }
+int direct_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
+                  const mmtta_tensor* y, int accumulate, const float* stats) {
+  DArgs a;                                     // (only the fields of the fused add: its checks)
+  const int st = epilogue_add(epi, y, a);
+  if (st) return st;
+  const NL tin = nl(x_norm);
+  const bool has_t = tin.mean != nullptr || tin.scale != nullptr;
+  const int K = x->c;
+  const int variant = direct_variant(d, x);
+  // bf16-stored operands: only the INPUT of the matrix-core up-convolution (the 64 / 32-channel concat buffer); the
+  // <= 4-channel results and every other direct variant work on fp32-stored tensors
+  // ... except the 4x4x4 matrix-tile convolution with ALL its thin tensors bf16-stored (8-byte voxels: the input-gradient
+  // launch under bf16-stored thin gradients)
+  const bool thin_bf = variant == 4 && is_bf16(x) && is_bf16(y) && (!(epi && epi->add) || is_bf16(epi->add)) &&
+                       x->sw == 4 && y->sw == 4 && ((y->flags & MMTTA_TENSOR_OWNS_PAD) || y->c == 4) && ((uintptr_t)y->ptr) % 8 == 0 &&
+                       (!(epi && epi->add) || epi->add->sw == 4);
+  MMTTA_CHECK(thin_bf || (is_f32(y) && !(epi && epi->add && is_bf16(epi->add))), MMTTA_ERR_UNSUPPORTED, "direct conv: outputs are fp32-stored");
+  if (variant == 5) return direct_upconv8_lean(d, x, x_norm, epi, y) ? THIN_UPCONV8_LEAN : THIN_UPCONV8;
+  MMTTA_CHECK(is_f32(x) || (variant == 3 && d->dtype == MMTTA_BF16) || variant == 1 || thin_bf, MMTTA_ERR_UNSUPPORTED,
+              "direct conv: a bf16-stored input is supported by the matrix-core up-convolution and the lanes-along-K kernel only");
+  // 1x1x1 head on voxel-dense tensors, nothing fused: the streaming kernel
+  const bool head = d->op == MMTTA_CONV_FWD && d->ksize == 1 && (K == 32 || K == 64) && !has_t && stats == nullptr &&
+                    !(epi && epi->add) && !accumulate && is_f32(y) && dense_rows16(x) && voxel_dense(y) && y->sw == 4 && direct_out_vec4(y);
+  if (head) return THIN_HEAD;
+  if (variant == 1) return THIN_KLANE;
+  if (variant == 2) return THIN_ROW;
+  if (variant == 4) return thin_bf ? THIN_MFMA4_BF : THIN_MFMA4;
+  if (variant == 3) return d->dtype == MMTTA_BF16 ? THIN_UPCONV_MFMA : THIN_UPCONV;
+  return THIN_DIRECT;
+}
+
 int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
                     const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
                     const PSets& sets, hipStream_t stream) {
@@ -1454,7 +1506,7 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
   a.K = x->c; a.N = y->c; a.ksize = d->ksize; a.stride = d->stride;
   a.transposed = (d->op == MMTTA_CONVT_FWD || d->op == MMTTA_CONV_DGRAD) ? 1 : 0;
   a.accumulate = accumulate;
-  a.out_vec4 = (y->flags & MMTTA_TENSOR_OWNS_PAD) && y->sw == 4 && aligned16(y);
+  a.out_vec4 = direct_out_vec4(y);
   a.stats = stats; a.blocks_per_n = direct_blocks_per_n(d, x, y);
   const int T = d->ksize * d->ksize * d->ksize;
   const size_t lds = (size_t)T * a.K * 16 + (size_t)a.K * 8 + 32 * sizeof(float);
@@ -1467,36 +1519,26 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
     attr_set = true;
   }
   const bool has_t = a.tin.mean != nullptr || a.tin.scale != nullptr;
-  const int variant = direct_variant(d, x);
-  // bf16-stored operands: only the INPUT of the matrix-core up-convolution (the 64 / 32-channel concat buffer); the
-  // <= 4-channel results and every other direct variant work on fp32-stored tensors
-  // ... except the 4x4x4 matrix-tile convolution with ALL its thin tensors bf16-stored (8-byte voxels: the input-gradient
-  // launch under bf16-stored thin gradients)
-  const bool thin_bf = variant == 4 && is_bf16(x) && is_bf16(y) && (!(epi && epi->add) || is_bf16(epi->add)) &&
-                       x->sw == 4 && y->sw == 4 && ((y->flags & MMTTA_TENSOR_OWNS_PAD) || y->c == 4) && ((uintptr_t)y->ptr) % 8 == 0 &&
-                       (!(epi && epi->add) || epi->add->sw == 4);
-  MMTTA_CHECK(thin_bf || (is_f32(y) && !(epi && epi->add && is_bf16(epi->add))), MMTTA_ERR_UNSUPPORTED, "direct conv: outputs are fp32-stored");
-  if (variant == 5) {
-    const int tz = (x->d + 3) / 4, ty = (x->h + 3) / 4, tx = (x->w + 7) / 8;
+  const int kernel = direct_kernel(d, x, x_norm, epi, y, accumulate, stats);
+  if (kernel < 0) return kernel;
+  switch (kernel) {
 #ifndef MMTTA_ACT_LEAKY_TU
-    if (direct_upconv8_lean(d, x, x_norm, epi, y)) {
+    case THIN_UPCONV8_LEAN: {
+      const int tz = (x->d + 3) / 4, ty = (x->h + 3) / 4, tx = (x->w + 7) / 8;
       if (a.K == 64) launch_upconv8<64, false, true, true>(a, y->n, tz, ty, tx, stream);
       else launch_upconv8<32, false, true, true>(a, y->n, tz, ty, tx, stream);
       return launch_status("up-convolution (2x2x2 gather GEMM, lean)");
     }
 #endif
-    MMTTA_BF_DISPATCH(has_t, HT, { MMTTA_BF_DISPATCH(is_bf16(x), XBF, {
-      if (a.K == 64) launch_upconv8<64, HT, XBF>(a, y->n, tz, ty, tx, stream);
-      else launch_upconv8<32, HT, XBF>(a, y->n, tz, ty, tx, stream);
-    }); });
-    return launch_status("up-convolution (2x2x2 gather GEMM)");
-  }
-  MMTTA_CHECK(is_f32(x) || (variant == 3 && d->dtype == MMTTA_BF16) || variant == 1 || thin_bf, MMTTA_ERR_UNSUPPORTED,
-              "direct conv: a bf16-stored input is supported by the matrix-core up-convolution and the lanes-along-K kernel only");
-  {  // 1x1x1 head on voxel-dense tensors, nothing fused: the streaming kernel
-    const bool head = d->op == MMTTA_CONV_FWD && d->ksize == 1 && (a.K == 32 || a.K == 64) && !has_t && stats == nullptr &&
-                      !(epi && epi->add) && !accumulate && is_f32(y) && dense_rows16(x) && voxel_dense(y) && y->sw == 4 && a.out_vec4;
-    if (head) {
+    case THIN_UPCONV8: {
+      const int tz = (x->d + 3) / 4, ty = (x->h + 3) / 4, tx = (x->w + 7) / 8;
+      MMTTA_BF_DISPATCH(has_t, HT, { MMTTA_BF_DISPATCH(is_bf16(x), XBF, {
+        if (a.K == 64) launch_upconv8<64, HT, XBF>(a, y->n, tz, ty, tx, stream);
+        else launch_upconv8<32, HT, XBF>(a, y->n, tz, ty, tx, stream);
+      }); });
+      return launch_status("up-convolution (2x2x2 gather GEMM)");
+    }
+    case THIN_HEAD: {      // 1x1x1 head on voxel-dense tensors, nothing fused: the streaming kernel
       const long long dhw = (long long)y->d * y->h * y->w;
       long long blocks = (dhw + 255) / 256;
       if (blocks > 2048) blocks = 2048;
@@ -1507,40 +1549,43 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
       });
       return launch_status("1x1 head (streaming)");
     }
+    case THIN_KLANE: {
+      const size_t kl_lds = (size_t)T * a.K * 16 + 32 * sizeof(float);
+      MMTTA_BF_DISPATCH(has_t, HT, {
+        if (a.K == 64) launch_klane<16, HT>(a, y->n, kl_lds, stream);
+        else launch_klane<8, HT>(a, y->n, kl_lds, stream);
+      });
+      return launch_status("direct conv (lanes along K)");
+    }
+    case THIN_ROW:
+      MMTTA_BF_DISPATCH(has_t, HT, { launch_row<HT>(a, y->n, stream); });
+      return launch_status("direct conv (row)");
+    case THIN_MFMA4:
+    case THIN_MFMA4_BF: {
+      const bool thin_bf = kernel == THIN_MFMA4_BF;
+      const dim3 grid(a.blocks_per_n, y->n), block(256);
+      MMTTA_BF_DISPATCH(has_t, HT, { MMTTA_BF_DISPATCH(thin_bf, GBF, {
+        switch (g_thin_mfma) {      // the tile depth TZ (MMTTA_OPT_THIN_MFMA)
+          case 3: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 2, GBF>), grid, block, 0, stream, a); break;
+          case 2: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 4, GBF>), grid, block, 0, stream, a); break;
+          default: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 8, GBF>), grid, block, 0, stream, a); break;
+        }
+      }); });
+      return launch_status(thin_bf ? "direct conv (4x4x4 matrix tiles, bf16-stored thin tensors)" : "direct conv (4x4x4 matrix tiles)");
+    }
+    case THIN_UPCONV:
+    case THIN_UPCONV_MFMA: {
+      const bool bf = kernel == THIN_UPCONV_MFMA;
+      MMTTA_BF_DISPATCH(has_t, HT, {
+        if (a.K == 64) launch_upconv_p<64, HT>(a, y->n, bf, stream);
+        else launch_upconv_p<32, HT>(a, y->n, bf, stream);
+      });
+      return launch_status("direct up-convolution");
+    }
+    default:
+      MMTTA_BF_DISPATCH(has_t, HT, { hipLaunchKernelGGL(direct_conv_kernel<HT>, dim3(a.blocks_per_n, y->n), dim3(256), lds, stream, a); });
+      return launch_status("direct conv");
   }
-  if (variant == 1) {
-    const size_t kl_lds = (size_t)T * a.K * 16 + 32 * sizeof(float);
-    MMTTA_BF_DISPATCH(has_t, HT, {
-      if (a.K == 64) launch_klane<16, HT>(a, y->n, kl_lds, stream);
-      else launch_klane<8, HT>(a, y->n, kl_lds, stream);
-    });
-    return launch_status("direct conv (lanes along K)");
-  }
-  if (variant == 2) {
-    MMTTA_BF_DISPATCH(has_t, HT, { launch_row<HT>(a, y->n, stream); });
-    return launch_status("direct conv (row)");
-  }
-  if (variant == 4) {
-    const dim3 grid(a.blocks_per_n, y->n), block(256);
-    MMTTA_BF_DISPATCH(has_t, HT, { MMTTA_BF_DISPATCH(thin_bf, GBF, {
-      switch (g_thin_mfma) {      // the tile depth TZ (MMTTA_OPT_THIN_MFMA)
-        case 3: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 2, GBF>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 4, GBF>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((conv3_mfma4_kernel<HT, 8, GBF>), grid, block, 0, stream, a); break;
-      }
-    }); });
-    return launch_status(thin_bf ? "direct conv (4x4x4 matrix tiles, bf16-stored thin tensors)" : "direct conv (4x4x4 matrix tiles)");
-  }
-  if (variant == 3) {
-    const bool bf = d->dtype == MMTTA_BF16;
-    MMTTA_BF_DISPATCH(has_t, HT, {
-      if (a.K == 64) launch_upconv_p<64, HT>(a, y->n, bf, stream);
-      else launch_upconv_p<32, HT>(a, y->n, bf, stream);
-    });
-    return launch_status("direct up-convolution");
-  }
-  MMTTA_BF_DISPATCH(has_t, HT, { hipLaunchKernelGGL(direct_conv_kernel<HT>, dim3(a.blocks_per_n, y->n), dim3(256), lds, stream, a); });
-  return launch_status("direct conv");
 }
 
 #ifndef MMTTA_ACT_LEAKY_TU

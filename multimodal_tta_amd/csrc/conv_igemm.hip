@@ -1606,6 +1606,17 @@ extern "C" int mmtta_conv_thin_lean(const mmtta_conv_desc* d, const mmtta_tensor
   return 0;
 }
 
+extern "C" int mmtta_conv_thin_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                      const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
+  Geometry g;
+  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
+  if (st) return st < 0 ? st : -st;
+  // (a call with a LeakyReLU runs the other instantiation's launcher; it has no lean kernels, and the lean predicates say so)
+  if (g.route == C_THIN) return chan_kernel(d, x, x_norm, epi, y, accumulate);
+  if (g.route == C_DIRECT) return direct_kernel(d, x, x_norm, epi, y, accumulate, stats);
+  return 0;
+}
+
 // ---- the head convolution with the entropy objective in its epilogue (MMTTA_OPT_HEAD_LOSS_PAIR bit 0)
 static int head_loss_plan(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                           const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz, int softmax, int per_item,

@@ -41,3 +41,19 @@ def test_argument_validation_without_a_gpu():
     d = _lib.ConvDesc(0, 3, 1, 4, 32, 0)
     assert lib.mmtta_conv_packed_bytes(ctypes.byref(d)) == 27 * 32 * 32 * 4
     assert lib.mmtta_copy_strided(None, None, None) == -1
+
+
+def test_conv_queries_share_the_operands_of_conv_route():
+    """The host-only queries about a run take what mmtta_conv_route takes, and return its error codes for a bad descriptor."""
+    from multimodal_tta_amd import _lib
+    lib = _lib.load()
+    bad = _lib.ConvDesc(0, 5, 1, 4, 4, 0)       # ksize 5: unsupported
+    t = _lib.Tensor(1 << 30, 1, 4, 4, 4, 8, 512, 1, 128, 32, 4, _lib.F32, 0)
+    for name in ("mmtta_conv_stages_raw", "mmtta_conv_cls8_pipelined", "mmtta_conv_thin_lean", "mmtta_conv_thin_kernel"):
+        assert name in declared_functions()
+        fn = getattr(lib, name)
+        assert fn.argtypes == lib.mmtta_conv_route.argtypes and fn.restype == lib.mmtta_conv_route.restype, name
+        assert fn(ctypes.byref(bad), ctypes.byref(t), None, None, ctypes.byref(t), 0, None) == -2, name
+    ok = _lib.ConvDesc(0, 3, 1, 4, 4, 0)        # 4 -> 4, 3x3x3 stride 1, fp32: the row kernel of route 6
+    assert lib.mmtta_conv_route(ctypes.byref(ok), ctypes.byref(t), None, None, ctypes.byref(t), 0, None) == 6
+    assert lib.mmtta_conv_thin_kernel(ctypes.byref(ok), ctypes.byref(t), None, None, ctypes.byref(t), 0, None) == 3

@@ -154,6 +154,10 @@ def _route(lib, dsc, x, y, stats=None, add=None, norm=None, accumulate=0):
                                     C.byref(epi) if epi is not None else None, C.byref(y), accumulate, stats))
 
 
+def _thin_kernel(lib, dsc, x, y, stats=None, accumulate=0):
+    return int(lib.mmtta_conv_thin_kernel(C.byref(dsc), C.byref(x), None, None, C.byref(y), accumulate, stats))
+
+
 def _config(lib, dsc, x, y):
     from multimodal_tta_amd._lib import ConvPlan
     plan = ConvPlan()
@@ -176,7 +180,7 @@ def test_every_route_is_reached_and_run_time_operands_flip_only_the_two_pointwis
     lib = _lib.load()
     ops.tune_for_volumes_in_flight(4)
     X, Y, A, STATS = 1 << 30, 1 << 40, 1 << 41, 1 << 20
-    seen = set()
+    seen, thin_seen = set(), set()
     for case, want_f32, want_bf16, _ in DISPATCH:
         cin, cout, k, stride, transposed, (n, d, h, w) = case
         fine = (2 * d, 2 * h, 2 * w) if transposed else ((d, h, w) if stride == 1 else ((d + 1) // 2, (h + 1) // 2, (w + 1) // 2))
@@ -192,6 +196,10 @@ def test_every_route_is_reached_and_run_time_operands_flip_only_the_two_pointwis
                         assert r == _config(lib, dsc, a, b) == (7 if (cfg == 14 and not lean) else cfg), (case, dtype, op, r)
                         assert r == _route(lib, dsc, a, b, accumulate=1), "no gate reads `accumulate`"
                         seen.add(r)
+                        # mmtta_conv_thin_kernel names a kernel of route 6 (ids 1 - 10) or 13 (11 - 13), and nothing elsewhere
+                        kern = _thin_kernel(lib, dsc, a, b)
+                        assert (1 <= kern <= 10) if r == 6 else (11 <= kern <= 13) if r == 13 else kern == 0, (case, dtype, op, r, kern)
+                        thin_seen.add(kern)
                 finally:
                     lib.mmtta_set_option(10, prev)
     # 15: test_class_fused_kernel_is_planned_for_large_stride2_forms
@@ -231,6 +239,12 @@ def test_every_route_is_reached_and_run_time_operands_flip_only_the_two_pointwis
     assert _route(lib, ConvDesc(CONV_FWD, 1, 1, 64, 32, F32), _t(X, 64, e16), _t(Y, 32, e16)) == 0, "fp32 operands"
     seen.add(17)
     assert seen == set(range(18)), f"routes never asked for: {sorted(set(range(18)) - seen)}"
+    assert 0 in thin_seen and any(1 <= k <= 10 for k in thin_seen) and any(k >= 11 for k in thin_seen), thin_seen
+    # routes 16 and 17 are none of its kernels; argument errors come back as they do from mmtta_conv_route
+    assert _thin_kernel(lib, ConvDesc(CONV_DGRAD, 1, 1, 32, 3, F32), _t(X, 3, (8, 8, 8)), _t(Y, 32, (8, 8, 8))) == 0
+    assert _thin_kernel(lib, dsc, _t(X, 64, e16, BF16), _t(Y, 32, e16, BF16)) == 0
+    assert _thin_kernel(lib, ConvDesc(CONV_FWD, 5, 1, 32, 32, F32), _t(X, 32, e8), _t(Y, 32, e8)) == -2
+    assert _thin_kernel(lib, ConvDesc(CONV_FWD, 3, 1, 32, 32, F32), _t(X, 16, e8), _t(Y, 32, e8)) == -1
     # argument errors come back as negative status codes, as from mmtta_conv_wgrad_kernel
     assert _route(lib, ConvDesc(CONV_FWD, 5, 1, 32, 32, F32), _t(X, 32, e8), _t(Y, 32, e8)) == -2
     assert _route(lib, ConvDesc(CONV_FWD, 3, 1, 32, 32, F32), _t(X, 16, e8), _t(Y, 32, e8)) == -1
