@@ -234,6 +234,17 @@ int mmtta_abi_version(void);
  * tensors, the LeakyReLU instantiation) keeps its kernel.  mmtta_conv_cls8_pipelined tells whether a call qualifies.
  * Returns the previous value. */
 #define MMTTA_OPT_CLS8_PIPELINE 20
+/* 1 (default): a call that runs the pipelined class-fused kernel (MMTTA_OPT_CLS8_PIPELINE) and whose y - and fused add, if
+ * there is one - has a multiple of 8 channels runs igemm_cls8_lean_kernel (csrc/conv_igemm.hip): the same K loop, and for every
+ * coarse 4 x 4 x 8 tile whose 8 x 8 x 16 output block lies wholly inside y an epilogue of its own (epilogue_cls8_lean): the
+ * row offsets worked out once per tile instead of once per parity class, the fused-add / accumulate operands of the next
+ * classes requested while a class is finished, 16-byte stores through a lane-pair exchange, and no statistics arithmetic
+ * when no statistics rows are asked for.  A tile on the border of y (an odd output extent, a partial tile) takes the
+ * epilogue of igemm_cls8_pipe_kernel inside the same launch.  0: igemm_cls8_pipe_kernel, in the same process.  The same
+ * values through the same operations in the same order: outputs, accumulated / fused-add destinations and statistics rows
+ * equal bit for bit.  No route, plan, statistics row or workspace size depends on it.  Only bit 0 is read; bit 1 is
+ * reserved.  mmtta_conv_cls8_lean_epilogue tells whether a call qualifies.  Returns the previous value. */
+#define MMTTA_OPT_CLS8_LEAN_EPILOGUE 21
 int mmtta_set_option(int key, int value);
 
 /* ------------------------------------------------------------------ layout (boundary) ---- */
@@ -345,6 +356,13 @@ int mmtta_conv_stages_raw(const mmtta_conv_desc* desc, const mmtta_tensor* x, co
  * mmtta_conv_route, the predicate the launcher itself asks. */
 int mmtta_conv_cls8_pipelined(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                               const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
+
+/* Whether mmtta_conv_run would run this call on the class-fused kernel with the lean interior epilogue
+ * (MMTTA_OPT_CLS8_LEAN_EPILOGUE): 1 when mmtta_conv_cls8_pipelined says 1, the option's bit 0 is set and y and the fused add
+ * have multiples of 8 channels, else 0, or a negative mmtta error code.  Host-only, the operands of mmtta_conv_route, the
+ * predicate the launcher itself asks. */
+int mmtta_conv_cls8_lean_epilogue(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                  const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats);
 
 /* Which lean kernel of MMTTA_OPT_THIN_LEAN mmtta_conv_run would take for this call: 1 the thin-K convolution (bit 0), 2 the
  * gather-GEMM up-convolution (bit 1), 0 neither, or a negative mmtta error code.  Host-only, the operands of mmtta_conv_route,

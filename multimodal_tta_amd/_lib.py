@@ -140,6 +140,7 @@ _SIGNATURES = {
     "mmtta_conv_route": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_stages_raw": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_cls8_pipelined": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
+    "mmtta_conv_cls8_lean_epilogue": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_thin_lean": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_thin_kernel": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), C.c_int, C.c_void_p]),
     "mmtta_conv_head_loss_eligible": (C.c_int, [_P(ConvDesc), _P(Tensor), _P(NormOnLoad), _P(ConvEpilogue), _P(Tensor), _P(Tensor),
@@ -349,6 +350,8 @@ def load() -> C.CDLL:
         lib.mmtta_set_option(19, int(os.environ["MMTTA_EPIUPDATE"]))
     if "MMTTA_CLS8PIPE" in os.environ:                   # A/B aid: MMTTA_OPT_CLS8_PIPELINE (same results bit for bit)
         lib.mmtta_set_option(20, int(os.environ["MMTTA_CLS8PIPE"]))
+    if "MMTTA_CLS8LEAN" in os.environ:                   # A/B aid: MMTTA_OPT_CLS8_LEAN_EPILOGUE (same results bit for bit)
+        lib.mmtta_set_option(21, int(os.environ["MMTTA_CLS8LEAN"]))
     _lib = lib
     return lib
 

@@ -24,6 +24,7 @@ int g_head_loss_pair = 3;
 int g_thin_lean = 3;
 int g_wgrad_epilogue_update = 1;
 int g_cls8_pipeline = 1;
+int g_cls8_lean_epilogue = 1;
 // split-K below / target, weight-gradient workgroups, thin-layer slabs.  Swept with the lanes bound to their own hardware
 // queues (profiles/r02_tuning_sweep.txt): four volumes in flight want half the splitting two did (96/128, 128 slabs)
 int g_tune[4] = {96, 128, 128, 256};
@@ -93,6 +94,11 @@ extern "C" int mmtta_set_option(int key, int value) {
   if (key == MMTTA_OPT_CLS8_PIPELINE) {
     const int prev = mmtta::g_cls8_pipeline;
     mmtta::g_cls8_pipeline = value ? 1 : 0;
+    return prev;
+  }
+  if (key == MMTTA_OPT_CLS8_LEAN_EPILOGUE) {
+    const int prev = mmtta::g_cls8_lean_epilogue;
+    mmtta::g_cls8_lean_epilogue = value & 1;      // (bit 1 is reserved: no kernel reads it)
     return prev;
   }
   if (key == MMTTA_OPT_IGEMM_PIPELINE) {

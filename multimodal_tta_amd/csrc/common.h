@@ -45,6 +45,7 @@ extern int g_head_loss_pair;        // api.hip: MMTTA_OPT_HEAD_LOSS_PAIR (bit 0:
 extern int g_thin_lean;            // api.hip: MMTTA_OPT_THIN_LEAN (bit 0: thin-K convolution, bit 1: gather-GEMM up-convolution)
 extern int g_wgrad_epilogue_update; // api.hip: MMTTA_OPT_WGRAD_EPILOGUE_UPDATE
 extern int g_cls8_pipeline;         // api.hip: MMTTA_OPT_CLS8_PIPELINE
+extern int g_cls8_lean_epilogue;    // api.hip: MMTTA_OPT_CLS8_LEAN_EPILOGUE (bit 0: the interior epilogue of the class-fused kernel)
 extern int g_tune[4];             // api.hip: launch-geometry knobs (MMTTA_OPT_SPLITK_BELOW ... MMTTA_OPT_WGRAD_THIN_SLABS)
 
 // ---- activation of a norm-on-load (mmtta_norm_on_load.relu: MMTTA_ACT_*).

@@ -389,9 +389,152 @@ __device__ __forceinline__ uint4 cls8_lds_q(const void* p) {
   }
 }
 
+// The epilogue of a tile of igemm_cls8_lean_kernel whose 8 x 8 x 16 output block lies wholly inside the tensor (the body tests
+// that once per tile): bf16 rows, Co and the add's channels multiples of 8 (host: cls8_lean).  The value path is
+// epilogue_vec16's - accumulator block -> the wave's transposition tile -> float4 of 4 channels x 4 row slots per lane -> bias
+// -> nl_apply of the add -> accumulate, on the same lanes - and so are the statistics sums: k = 0 ... 3 per lane, the xor
+// tree over 8, 16, 32, per class, then tsum += over the classes.  What differs:
+//   * the lane's four row-slot offsets are worked out once per tile: class (pz, py, px) moves a wave-uniform base by
+//     pz osd + py osh + px osw, and the lane term is the interior row_off of epilogue_vec16 at TY = 4 with doubled strides
+//     (x = 4 (k & 1) + (lane >> 3 & 3), y one of two compile-time values by lane bit 5); a second set from the add's strides,
+//     which may be a slice of a wider tensor.  No decode, bound or clamp: every row of every class is inside;
+//   * the fused-add / accumulate operands of class c + AHEAD are requested before class c is finished, raw (converted when
+//     used: a conversion behind the load would wait for it), ADD and ACC compile-time so that a slot holds what the call reads;
+//   * 16-byte stores: each lane rounds its 4 channels x 4 row slots as st4_t<true> does, then lanes l and l ^ 1 - channels
+//     8 m ... 8 m + 3 and 8 m + 4 ... 8 m + 7 of the same rows - swap halves: the even lane ends with all 8 channels of row
+//     slots 0 and 2, the odd one with those of slots 1 and 3.  Two stores per class and lane instead of four.  The column
+//     mask is per 4 channels; with Co % 8 == 0 both lanes of a pair agree, which the host gate guarantees;
+//   * no statistics arithmetic or shuffles when the call asks for no statistics rows (every input gradient).
+// The squares are spelled as the fused multiply-add hipcc's contraction makes of `ssq += v * v` in epilogue_vec16, with
+// implicit contraction off, as in chan_mfma_body.h (tests/test_hip_cls8_lean_epilogue.py compares the rows bit for bit).
+template <bool ADD, bool ACC>
+__device__ __forceinline__ void epilogue_cls8_lean_t(const GArgs& a, const float* biasp, f32x16 (&acc)[8], float* tr, int lane, int wave,
+                                                     int colbase, bool colact, int n, int gz0, int gy0, int gx0, float (&tsum)[4],
+                                                     float (&tsq)[4]) {
+  constexpr int AHEAD = (ADD && ACC) ? 1 : 3;      // classes whose operands are in flight ahead of the one being finished
+  const int osd = (int)a.osd, osh = (int)a.osh, osw = (int)a.osw, asd = (int)a.asd, ash_ = (int)a.ash, asw = (int)a.asw;
+  const int h = lane >> 5, r = lane & 31;
+  const int rsub = lane >> 3, c4 = (lane & 7) * 4;
+  const int colv = colbase + c4;
+  const bool cvok = colact && colv < a.Co;                 // Co % 8 == 0: lanes l and l ^ 1 agree
+  const int colc = min(colv, a.Co - 4);
+  float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float asc[4] = {1.f, 1.f, 1.f, 1.f}, ash[4] = {0.f, 0.f, 0.f, 0.f};
+  if (biasp) bias4 = *reinterpret_cast<const float4*>(biasp + colc);
+  if constexpr (ADD) nl_coeff_vec<4>(a.tadd, n, a.Co, colc, asc, ash);
+  // ---- addresses, once per tile: 32-bit lane offsets in BYTES (an item has < 2^31 elements) beside 64-bit wave-uniform bases:
+  // the loads and stores take the scalar-base + 32-bit-offset form, no 64-bit vector arithmetic
+  const bool lb = (rsub >> 2) != 0, odd = (lane & 1) != 0;
+  constexpr int T = 0xEB14;                                // row_to_local's y table
+  unsigned lo[4], la[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int y0 = (T >> (2 * (2 * k))) & 3, y1 = (T >> (2 * (2 * k + 1))) & 3, x2 = 2 * (4 * (k & 1) + (rsub & 3));
+    lo[k] = (unsigned)((lb ? 2 * y1 : 2 * y0) * osh + x2 * osw + colc) * 2u;
+    la[k] = (unsigned)((lb ? 2 * y1 : 2 * y0) * ash_ + x2 * asw + colc) * 2u;
+  }
+  // the even lane stores row slots 0 and 2 from its own first channel, the odd lane slots 1 and 3 from its neighbour's
+  const unsigned lst[2] = {odd ? lo[1] - 8u : lo[0], odd ? lo[3] - 8u : lo[2]};
+  char* const outh = reinterpret_cast<char*>(reinterpret_cast<unsigned short*>(a.out) + ((long long)n * a.osn + (long long)(2 * (gz0 + wave)) * osd +
+                                                                               (long long)(2 * gy0) * osh + (long long)(2 * gx0) * osw));
+  const char* const addh = reinterpret_cast<const char*>(reinterpret_cast<const unsigned short*>(a.add) + ((long long)n * a.asn + (long long)(2 * (gz0 + wave)) * asd +
+                                                                                           (long long)(2 * gy0) * ash_ + (long long)(2 * gx0) * asw));
+  uint2 qa[AHEAD + 1][4], qo[AHEAD + 1][4];
+  auto request = [&](auto cc) {
+    constexpr int c = decltype(cc)::value, s = c % (AHEAD + 1), pz = (c >> 2) & 1, py = (c >> 1) & 1, px = c & 1;
+    if constexpr (ADD) {
+      const char* const p = addh + 2 * (pz * asd + py * ash_ + px * asw);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) qa[s][k] = *reinterpret_cast<const uint2*>(p + la[k]);
+    }
+    if constexpr (ACC) {
+      const char* const p = outh + 2 * (pz * osd + py * osh + px * osw);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) qo[s][k] = *reinterpret_cast<const uint2*>(p + lo[k]);
+    }
+  };
+  static_for<0, AHEAD>([&](auto cc) { request(cc); });
+  static_for<0, 8>([&](auto cc) {
+    constexpr int c = decltype(cc)::value, s = c % (AHEAD + 1), pz = (c >> 2) & 1, py = (c >> 1) & 1, px = c & 1;
+    if constexpr (c + AHEAD < 8) request(std::integral_constant<int, c + AHEAD>{});
+#pragma unroll
+    for (int i = 0; i < 16; ++i) tr[((i & 3) + 8 * (i >> 2) + 4 * h) * 36 + r] = acc[c][i];
+    float v[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float4 val = *reinterpret_cast<const float4*>(tr + (rsub + 8 * k) * 36 + c4);
+      v[k][0] = val.x + bias4.x; v[k][1] = val.y + bias4.y; v[k][2] = val.z + bias4.z; v[k][3] = val.w + bias4.w;
+    }
+    unsigned pk[4][2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if constexpr (ADD) {
+        const uint2 u = qa[s][k];
+        const float av[4] = {bf16_bits_to_f32(u.x & 0xffffu), bf16_bits_to_f32(u.x >> 16), bf16_bits_to_f32(u.y & 0xffffu),
+                             bf16_bits_to_f32(u.y >> 16)};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[k][j] += nl_apply(av[j], asc[j], ash[j], a.tadd.relu);
+      }
+      if constexpr (ACC) {
+        const uint2 u = qo[s][k];
+        v[k][0] += bf16_bits_to_f32(u.x & 0xffffu); v[k][1] += bf16_bits_to_f32(u.x >> 16);
+        v[k][2] += bf16_bits_to_f32(u.y & 0xffffu); v[k][3] += bf16_bits_to_f32(u.y >> 16);
+      }
+      pk[k][0] = f32x2_to_bf16x2(v[k][0], v[k][1]);
+      pk[k][1] = f32x2_to_bf16x2(v[k][2], v[k][3]);
+    }
+    // rows (k, k + 1): the even lane gives its half of row k + 1 for the odd lane's half of row k
+    char* const po = outh + 2 * (pz * osd + py * osh + px * osw);
+    uint4 q[2];
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const unsigned s0 = odd ? pk[2 * p][0] : pk[2 * p + 1][0], s1 = odd ? pk[2 * p][1] : pk[2 * p + 1][1];
+      const unsigned n0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s0, 0xb1, 0xf, 0xf, true);      // lane ^ 1
+      const unsigned n1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s1, 0xb1, 0xf, 0xf, true);
+      q[p] = odd ? make_uint4(n0, n1, pk[2 * p + 1][0], pk[2 * p + 1][1]) : make_uint4(pk[2 * p][0], pk[2 * p][1], n0, n1);
+    }
+    if (cvok) {
+      *reinterpret_cast<uint4*>(po + lst[0]) = q[0];
+      *reinterpret_cast<uint4*>(po + lst[1]) = q[1];
+    }
+    if (a.stats != nullptr) {
+#pragma clang fp contract(off)
+      float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f};
+      if (cvok) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { ssum[j] += v[k][j]; ssq[j] = fmaf(v[k][j], v[k][j], ssq[j]); }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int o = 8; o < 64; o <<= 1) { ssum[j] += __shfl_xor(ssum[j], o, 64); ssq[j] += __shfl_xor(ssq[j], o, 64); }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { tsum[j] += ssum[j]; tsq[j] += ssq[j]; }
+    }
+  });
+}
+
+template <bool ABF>
+__device__ __forceinline__ void epilogue_cls8_lean(const GArgs& a, const float* biasp, f32x16 (&acc)[8], float* tr, int lane, int wave,
+                                                   int colbase, bool colact, int n, int gz0, int gy0, int gx0, float (&tsum)[4],
+                                                   float (&tsq)[4]) {
+  static_assert(ABF, "bf16 rows: a lane pair holds 16 bytes of one");
+  // one wave-uniform choice per tile: a slot of operands in flight holds what the call reads and nothing else
+  if (a.add != nullptr) {
+    if (a.accumulate) epilogue_cls8_lean_t<true, true>(a, biasp, acc, tr, lane, wave, colbase, colact, n, gz0, gy0, gx0, tsum, tsq);
+    else epilogue_cls8_lean_t<true, false>(a, biasp, acc, tr, lane, wave, colbase, colact, n, gz0, gy0, gx0, tsum, tsq);
+  } else {
+    if (a.accumulate) epilogue_cls8_lean_t<false, true>(a, biasp, acc, tr, lane, wave, colbase, colact, n, gz0, gy0, gx0, tsum, tsq);
+    else epilogue_cls8_lean_t<false, false>(a, biasp, acc, tr, lane, wave, colbase, colact, n, gz0, gy0, gx0, tsum, tsq);
+  }
+}
+
 template <int KCI, bool ABF>
 __global__ __launch_bounds__(256, 2) void igemm_cls8_kernel(GArgs a) {
-  constexpr bool RAW = false, PIPE = false;
+  constexpr bool RAW = false, PIPE = false, LEAN = false;
 #include "conv_igemm_cls8_body.h"
 }
 
@@ -399,7 +542,7 @@ __global__ __launch_bounds__(256, 2) void igemm_cls8_kernel(GArgs a) {
 // across the requests of a stage
 template <int KCI, bool ABF>      // (ABF always true: see igemm_reuse_raw_kernel)
 __global__ __launch_bounds__(256, 2) void igemm_cls8_raw_kernel(GArgs a) {
-  constexpr bool RAW = true, PIPE = false;
+  constexpr bool RAW = true, PIPE = false, LEAN = false;
 #include "conv_igemm_cls8_body.h"
 }
 
@@ -409,12 +552,21 @@ __global__ __launch_bounds__(256, 2) void igemm_cls8_raw_kernel(GArgs a) {
 // pipeline of round 3 could not afford beside 8 accumulator blocks.  Same products in the same order, same epilogue.
 template <int KCI, bool ABF>      // (ABF always true)
 __global__ __launch_bounds__(256, 2) void igemm_cls8_pipe_kernel(GArgs a) {
-  constexpr bool RAW = true, PIPE = true;
+  constexpr bool RAW = true, PIPE = true, LEAN = false;
 #include "conv_igemm_cls8_body.h"
 }
 
-template <int KCI, bool ABF, bool RAW = false, bool PIPE = false>
+// ... and with an epilogue of its own for the tiles inside the tensor (MMTTA_OPT_CLS8_LEAN_EPILOGUE; host: cls8_lean;
+// epilogue_cls8_lean above).  The K loop is the pipelined kernel's, and so is the epilogue of a tile on the border.
+template <int KCI, bool ABF>      // (ABF always true)
+__global__ __launch_bounds__(256, 2) void igemm_cls8_lean_kernel(GArgs a) {
+  constexpr bool RAW = true, PIPE = true, LEAN = true;
+#include "conv_igemm_cls8_body.h"
+}
+
+template <int KCI, bool ABF, bool RAW = false, bool PIPE = false, bool LEAN = false>
 static int launch_cls8_t(const GArgs& a, int tiles, hipStream_t s) {
+  static_assert(!LEAN || PIPE, "the lean epilogue belongs to the pipelined kernel");
   constexpr int VS = KCI + 8;
   // the box image and the stage's weight image (PIPE: two of them; 69 696 bytes at KCI = 16, two workgroups per CU still)
   size_t lds = ((size_t)(5 * 5 * LDS_PITCH_BF16 * VS + 7) / 8 * 8) * 2 + (size_t)(PIPE ? 2 : 1) * 27 * (KCI / 8) * 32 * 16;
@@ -422,7 +574,8 @@ static int launch_cls8_t(const GArgs& a, int tiles, hipStream_t s) {
   if (lds < epi) lds = epi;
   void (*kern)(GArgs) = igemm_cls8_kernel<KCI, ABF>;
   if constexpr (RAW && !PIPE) kern = igemm_cls8_raw_kernel<KCI, ABF>;
-  if constexpr (PIPE) kern = igemm_cls8_pipe_kernel<KCI, ABF>;
+  if constexpr (PIPE && !LEAN) kern = igemm_cls8_pipe_kernel<KCI, ABF>;
+  if constexpr (LEAN) kern = igemm_cls8_lean_kernel<KCI, ABF>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1035,6 +1188,16 @@ static bool cls8_pipelined(int route, bool bf_tile, const mmtta_tensor* x, const
   return g_cls8_pipeline && route == 15 /* C_CLS_FUSED */ && raw_staging(route, bf_tile, x, x_norm, y, add);
 }
 
+// ... with the lean interior epilogue (MMTTA_OPT_CLS8_LEAN_EPILOGUE bit 0; igemm_cls8_lean_kernel): a pipelined call - so x, y
+// and the add are bf16-stored - whose y and add have whole 8-channel groups: a lane pair stores 16 bytes of a row, and both
+// lanes of a pair are live or dead together.  (cls_fused_operand has put y's rows and strides on 16 bytes.)  The one function
+// behind mmtta_conv_cls8_lean_epilogue and the launcher.
+static bool cls8_lean(int route, bool bf_tile, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* y,
+                      const mmtta_tensor* add) {
+  return (g_cls8_lean_epilogue & 1) && cls8_pipelined(route, bf_tile, x, x_norm, y, add) && y->c % 8 == 0 &&
+         (add == nullptr || add->c % 8 == 0);
+}
+
 struct Geometry {
   int route;      // CRoute
   int K, N, Kp, Np, si;
@@ -1398,6 +1561,7 @@ static int cls_fused_run(const ConvCall& c, const Geometry& g) {
               "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf, a.add_bf);
   if constexpr (RAW_KERNELS) {
     const mmtta_tensor* ad = (c.epi && c.epi->add) ? c.epi->add : nullptr;
+    if (cls8_lean(g.route, g.cfg.bf, c.x, c.x_norm, c.y, ad)) return launch_cls8_t<16, true, true, true, true>(a, g.tiles, c.stream);
     if (cls8_pipelined(g.route, g.cfg.bf, c.x, c.x_norm, c.y, ad)) return launch_cls8_t<16, true, true, true>(a, g.tiles, c.stream);
     if (raw_staging(g.route, g.cfg.bf, c.x, c.x_norm, c.y, ad)) return launch_cls8_t<16, true, true>(a, g.tiles, c.stream);
   }
@@ -1594,6 +1758,16 @@ extern "C" int mmtta_conv_cls8_pipelined(const mmtta_conv_desc* d, const mmtta_t
   const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
   // (a LeakyReLU on the fused add sends the run to the LeakyReLU instantiation, which has no raw kernels)
   return (cls8_pipelined(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
+}
+
+extern "C" int mmtta_conv_cls8_lean_epilogue(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                                             const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
+  Geometry g;
+  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
+  if (st) return st < 0 ? st : -st;
+  const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
+  // (a LeakyReLU on the fused add sends the run to the LeakyReLU instantiation, which has no raw kernels)
+  return (cls8_lean(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
 }
 
 extern "C" int mmtta_conv_thin_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,

@@ -1,5 +1,5 @@
-// The body of igemm_cls8_kernel, igemm_cls8_raw_kernel and igemm_cls8_pipe_kernel (conv_igemm.hip): included inside each
-// kernel, which names KCI, ABF, RAW and PIPE as compile-time constants and has the kernel argument `GArgs a`.  One text and no
+// The body of igemm_cls8_kernel, igemm_cls8_raw_kernel, igemm_cls8_pipe_kernel and igemm_cls8_lean_kernel (conv_igemm.hip): included
+// inside each kernel, which names KCI, ABF, RAW, PIPE and LEAN as compile-time constants and has the kernel argument `GArgs a`.  One text and no
 // function in between, so that igemm_cls8_kernel compiles to exactly what it was before the other kernels existed
 // (conv_igemm_body.h does the same).
 // No include guard on purpose: it is included once per kernel.
@@ -206,6 +206,16 @@
   }
   // ---- epilogue: every class's 32 x 32 block through this wave's LDS transposition tile (the box image is dead)
   float tsum[4] = {0.f, 0.f, 0.f, 0.f}, tsq[4] = {0.f, 0.f, 0.f, 0.f};
+  // LEAN (igemm_cls8_lean_kernel): one workgroup-uniform test per tile.  The tile's 8 x 8 x 16 output block lies wholly inside
+  // the tensor when the class of odd parity on every axis - the shortest: it ends one voxel early at an odd extent - has its
+  // last row inside, 2 (g0 + T - 1) + 1 < extent; that is also g0 + T <= Dg of every class.  Such a tile takes
+  // epilogue_cls8_lean, every other one the eight calls below.
+  bool lean_tile = false;
+  if constexpr (LEAN) lean_tile = 2 * (gz0 + TZ) <= a.Do && 2 * (gy0 + TY) <= a.Ho && 2 * (gx0 + TX) <= a.Wo;
+  if (lean_tile) {
+    if constexpr (LEAN)
+      epilogue_cls8_lean<ABF>(a, biasn, acc, lds + wave * EPI_TILE_FLOATS, lane, wave, colbase, colact, n, gz0, gy0, gx0, tsum, tsq);
+  } else {
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
     float v_sum[4], v_sq[4];
@@ -213,6 +223,7 @@
                                              lane, wave, colbase, colact, n, gz0, gy0, gx0, v_sum, v_sq);
 #pragma unroll
     for (int j = 0; j < 4; ++j) { tsum[j] += v_sum[j]; tsq[j] += v_sq[j]; }
+  }
   }
   if (a.stats != nullptr) {
     float* red = lds + 4 * EPI_TILE_FLOATS;      // [4 waves][2][32], behind the four tiles
