@@ -308,6 +308,28 @@ _SIGNATURES = {
                                        C.c_int, _P(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
+# mmtta_set_option keys (include/mmtta.h MMTTA_OPT_*)
+OPT_IGEMM_PIPELINE, OPT_EPILOGUE_VEC16, OPT_IGEMM_LEAN, OPT_WGRAD_VECTOR_STAGING = 6, 9, 10, 11
+OPT_CLASS_FUSED_MIN_WORKGROUPS, OPT_THIN_MFMA, OPT_RAW_STAGING, OPT_HEAD_LOSS_PAIR, OPT_THIN_LEAN = 12, 13, 16, 17, 18
+OPT_WGRAD_EPILOGUE_UPDATE, OPT_CLS8_PIPELINE, OPT_CLS8_LEAN_EPILOGUE = 19, 20, 21
+# A/B aids read once by load(): (environment variable, option, form).  Form True: the value "1" switches the option off;
+# False: the option is set to int(value) whenever the variable is present.  (MMTTA_NO_PIPE and the last six pick between
+# kernels with the same results bit for bit.)
+_ENV_OPTIONS = (
+    ("MMTTA_NO_PIPE", OPT_IGEMM_PIPELINE, True),
+    ("MMTTA_NO_EPIVEC", OPT_EPILOGUE_VEC16, True),
+    ("MMTTA_WGVEC", OPT_WGRAD_VECTOR_STAGING, False),
+    ("MMTTA_THINMFMA", OPT_THIN_MFMA, False),
+    ("MMTTA_CLSFUSE", OPT_CLASS_FUSED_MIN_WORKGROUPS, False),
+    ("MMTTA_LEAN", OPT_IGEMM_LEAN, False),
+    ("MMTTA_RAWSTAGE", OPT_RAW_STAGING, False),
+    ("MMTTA_HEADLOSS", OPT_HEAD_LOSS_PAIR, False),
+    ("MMTTA_THINLEAN", OPT_THIN_LEAN, False),
+    ("MMTTA_EPIUPDATE", OPT_WGRAD_EPILOGUE_UPDATE, False),
+    ("MMTTA_CLS8PIPE", OPT_CLS8_PIPELINE, False),
+    ("MMTTA_CLS8LEAN", OPT_CLS8_LEAN_EPILOGUE, False),
+)
+
 _lib = None
 
 
@@ -328,30 +350,12 @@ def load() -> C.CDLL:
         fn.argtypes = args
     if lib.mmtta_abi_version() != 2:
         raise MmttaError("libmmtta.so ABI version mismatch")
-    if os.environ.get("MMTTA_NO_PIPE", "0") == "1":      # A/B aid: MMTTA_OPT_IGEMM_PIPELINE off (same results bit for bit)
-        lib.mmtta_set_option(6, 0)
-    if os.environ.get("MMTTA_NO_EPIVEC", "0") == "1":    # A/B aid: MMTTA_OPT_EPILOGUE_VEC16 off
-        lib.mmtta_set_option(9, 0)
-    if "MMTTA_WGVEC" in os.environ:                      # A/B aid: MMTTA_OPT_WGRAD_VECTOR_STAGING
-        lib.mmtta_set_option(11, int(os.environ["MMTTA_WGVEC"]))
-    if "MMTTA_THINMFMA" in os.environ:                   # A/B aid: MMTTA_OPT_THIN_MFMA
-        lib.mmtta_set_option(13, int(os.environ["MMTTA_THINMFMA"]))
-    if "MMTTA_CLSFUSE" in os.environ:                    # A/B aid: MMTTA_OPT_CLASS_FUSED_MIN_WORKGROUPS
-        lib.mmtta_set_option(12, int(os.environ["MMTTA_CLSFUSE"]))
-    if "MMTTA_LEAN" in os.environ:                       # A/B aid: MMTTA_OPT_IGEMM_LEAN
-        lib.mmtta_set_option(10, int(os.environ["MMTTA_LEAN"]))
-    if "MMTTA_RAWSTAGE" in os.environ:                   # A/B aid: MMTTA_OPT_RAW_STAGING (same results bit for bit)
-        lib.mmtta_set_option(16, int(os.environ["MMTTA_RAWSTAGE"]))
-    if "MMTTA_HEADLOSS" in os.environ:                   # A/B aid: MMTTA_OPT_HEAD_LOSS_PAIR (same gradients bit for bit)
-        lib.mmtta_set_option(17, int(os.environ["MMTTA_HEADLOSS"]))
-    if "MMTTA_THINLEAN" in os.environ:                   # A/B aid: MMTTA_OPT_THIN_LEAN (same results bit for bit)
-        lib.mmtta_set_option(18, int(os.environ["MMTTA_THINLEAN"]))
-    if "MMTTA_EPIUPDATE" in os.environ:                  # A/B aid: MMTTA_OPT_WGRAD_EPILOGUE_UPDATE (same results bit for bit)
-        lib.mmtta_set_option(19, int(os.environ["MMTTA_EPIUPDATE"]))
-    if "MMTTA_CLS8PIPE" in os.environ:                   # A/B aid: MMTTA_OPT_CLS8_PIPELINE (same results bit for bit)
-        lib.mmtta_set_option(20, int(os.environ["MMTTA_CLS8PIPE"]))
-    if "MMTTA_CLS8LEAN" in os.environ:                   # A/B aid: MMTTA_OPT_CLS8_LEAN_EPILOGUE (same results bit for bit)
-        lib.mmtta_set_option(21, int(os.environ["MMTTA_CLS8LEAN"]))
+    for var, key, off_at_1 in _ENV_OPTIONS:
+        if off_at_1:
+            if os.environ.get(var, "0") == "1":
+                lib.mmtta_set_option(key, 0)
+        elif var in os.environ:
+            lib.mmtta_set_option(key, int(os.environ[var]))
     _lib = lib
     return lib
 

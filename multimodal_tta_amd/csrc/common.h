@@ -602,23 +602,23 @@ enum ThinKernel : int {
   THIN_DIRECT = 1, THIN_KLANE = 2, THIN_ROW = 3, THIN_MFMA4 = 4, THIN_MFMA4_BF = 5, THIN_UPCONV = 6, THIN_UPCONV_MFMA = 7,
   THIN_UPCONV8 = 8, THIN_UPCONV8_LEAN = 9, THIN_HEAD = 10, THIN_CHAN = 11, THIN_CHAN_MFMA = 12, THIN_CHAN_MFMA_LEAN = 13,
 };
-// which of them chan_conv_run / direct_conv_run launches for this call, or the (negative) error the launcher returns instead
-int chan_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
-                const mmtta_tensor* y, int accumulate);
-int direct_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
-                  const mmtta_tensor* y, int accumulate, const float* stats);
-// whether chan_conv_run takes the lean kernel for this call (MMTTA_OPT_THIN_LEAN bit 0)
+// The plan of a run (conv_igemm.hip: plan_run) asks the four functions below, once; the launchers take the answer.
+// whether the call takes the lean thin-K kernel (MMTTA_OPT_THIN_LEAN bit 0) / the lean gather-GEMM up-convolution (bit 1)
 bool chan_lean_applicable(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                           const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate);
-int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed, int Kp,
-                  int Np, const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
-                  const PSets& sets, hipStream_t stream);
-int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
-                    const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
-                    const PSets& sets, hipStream_t stream);
-// whether direct_conv_run takes the lean gather-GEMM up-convolution for this call (MMTTA_OPT_THIN_LEAN bit 1)
 bool direct_upconv8_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                          const mmtta_conv_epilogue* epi, const mmtta_tensor* y);
+// which kernel of route 13 / 6 the call runs (`lean`: the answer above), or the (negative) error its launcher returns instead
+int chan_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, bool lean);
+int direct_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
+                  const mmtta_tensor* y, int accumulate, const float* stats, bool lean);
+// the launchers: `kernel` is the plan's chan_kernel / direct_kernel
+int chan_conv_run(int kernel, const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
+                  int Kp, int Np, const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate,
+                  float* stats, const PSets& sets, hipStream_t stream);
+int direct_conv_run(int kernel, const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
+                    const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
+                    const PSets& sets, hipStream_t stream);
 // the head convolution with the entropy objective in its epilogue (conv_direct.hip; the plain translation unit only)
 bool direct_head_loss_eligible(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz, int softmax,

@@ -875,8 +875,8 @@ static void launch_chan_mfma(const CArgs& a, int K, int N, int blocks, hipStream
 // The lean thin-K kernel (MMTTA_OPT_THIN_LEAN bit 0; chan_mfma_lean_kernel) takes a call of route 13 that runs on the matrix
 // cores at stride 2 from a bf16-stored gathered tensor into a bf16-stored y of exactly 32 or 64 channels whose voxel rows -
 // and those of a fused add - are 16-byte items, without accumulate.  The 32-bit offsets are those chan_applicable and
-// chan_conv_run check.  Instantiated in the plain translation unit only: a call with a LeakyReLU on x or on the add keeps
-// chan_mfma_kernel.  The one function behind mmtta_conv_thin_lean and the launcher.
+// chan_kernel check.  Instantiated in the plain translation unit only: a call with a LeakyReLU on x or on the add keeps
+// chan_mfma_kernel.  The plan of a run asks it (conv_igemm.hip: plan_run); mmtta_conv_thin_lean and chan_kernel take the answer.
 #ifdef MMTTA_ACT_LEAKY_TU
 constexpr bool LEAN_KERNELS = false;
 #else
@@ -911,11 +911,10 @@ static void launch_chan_lean(const CArgs& a, int K, int N, int blocks, hipStream
 #endif
 
 // Which kernel chan_conv_run launches for a call of route 13 (THIN_* of common.h: the ids of mmtta_conv_thin_kernel), or the
-// error it returns instead, every check in the launcher's order.  The one function behind mmtta_conv_thin_kernel and the
-// launcher, which switches on it.
+// error it returns instead, every check of the launch in order.  The plan of a run asks it once (Geometry::thin_kernel);
+// the launcher switches on the answer.  `lean`: chan_lean_applicable.
 static int chan_koff(const mmtta_tensor* x) { return is_bf16(x) ? 0 : (int)((((uintptr_t)x->ptr) % 16) / 4); }
-int chan_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
-                const mmtta_tensor* y, int accumulate) {
+int chan_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, bool lean) {
   MMTTA_CHECK(chan_koff(x) == 0 || x->c == 1, MMTTA_ERR_UNSUPPORTED, "thin-K conv: only a one-channel slice may start inside a 16-byte group");
   CArgs a;                                     // (only the fields of the fused add: its checks)
   const int st = epilogue_add(epi, y, a);
@@ -933,13 +932,12 @@ int chan_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_nor
   MMTTA_CHECK(a.add == nullptr || add_bf == is_bf16(y), MMTTA_ERR_UNSUPPORTED, "thin-K conv: the fused add must share the output's storage type");
   // one input channel (the single-modality stems of the deep-fusion net) is 27 FMAs per output: the VALU kernel wins there
   if (!mfma_path) return THIN_CHAN;
-  return chan_lean_applicable(d, x, x_norm, epi, y, accumulate) ? THIN_CHAN_MFMA_LEAN : THIN_CHAN_MFMA;
+  return lean ? THIN_CHAN_MFMA_LEAN : THIN_CHAN_MFMA;
 }
 
-int chan_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed, int Kp,
-                  int Np, const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
-                  const PSets& sets, hipStream_t stream) {
-  const int kernel = chan_kernel(d, x, x_norm, epi, y, accumulate);
+int chan_conv_run(int kernel, const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
+                  int Kp, int Np, const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate,
+                  float* stats, const PSets& sets, hipStream_t stream) {
   if (kernel < 0) return kernel;
   CArgs a;
   a.ps = sets;
@@ -1450,8 +1448,8 @@ static void launch_row(const DArgs& a, int n, hipStream_t stream) {
 
 // The lean gather-GEMM up-convolution (MMTTA_OPT_THIN_LEAN bit 1; upconv8_lean_kernel) takes a call of upconv8_kernel whose
 // input is bf16-stored and has no norm-on-load transform (neither mean nor scale: what picks HAS_T = false below).  The plain
-// translation unit only: a call with a LeakyReLU on x or on the add keeps upconv8_kernel.  The one function behind
-// mmtta_conv_thin_lean and the launcher.
+// translation unit only: a call with a LeakyReLU on x or on the add keeps upconv8_kernel.  The plan of a run asks it
+// (conv_igemm.hip: plan_run); mmtta_conv_thin_lean and direct_kernel take the answer.
 bool direct_upconv8_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                          const mmtta_conv_epilogue* epi, const mmtta_tensor* y) {
   const bool has_t = x_norm != nullptr && (x_norm->mean != nullptr || x_norm->scale != nullptr);
@@ -1460,11 +1458,11 @@ bool direct_upconv8_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const 
 }
 
 // Which kernel direct_conv_run launches for a call of route 6 (THIN_* of common.h: the ids of mmtta_conv_thin_kernel), or the
-// error it returns instead, every check in the launcher's order.  The one function behind mmtta_conv_thin_kernel and the
-// launcher, which switches on it.
+// error it returns instead, every check of the launch in order.  The plan of a run asks it once (Geometry::thin_kernel);
+// the launcher switches on the answer.  `lean`: direct_upconv8_lean.
 static bool direct_out_vec4(const mmtta_tensor* y) { return (y->flags & MMTTA_TENSOR_OWNS_PAD) && y->sw == 4 && aligned16(y); }
 int direct_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
-                  const mmtta_tensor* y, int accumulate, const float* stats) {
+                  const mmtta_tensor* y, int accumulate, const float* stats, bool lean) {
   DArgs a;                                     // (only the fields of the fused add: its checks)
   const int st = epilogue_add(epi, y, a);
   if (st) return st;
@@ -1480,7 +1478,7 @@ int direct_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
                        x->sw == 4 && y->sw == 4 && ((y->flags & MMTTA_TENSOR_OWNS_PAD) || y->c == 4) && ((uintptr_t)y->ptr) % 8 == 0 &&
                        (!(epi && epi->add) || epi->add->sw == 4);
   MMTTA_CHECK(thin_bf || (is_f32(y) && !(epi && epi->add && is_bf16(epi->add))), MMTTA_ERR_UNSUPPORTED, "direct conv: outputs are fp32-stored");
-  if (variant == 5) return direct_upconv8_lean(d, x, x_norm, epi, y) ? THIN_UPCONV8_LEAN : THIN_UPCONV8;
+  if (variant == 5) return lean ? THIN_UPCONV8_LEAN : THIN_UPCONV8;
   MMTTA_CHECK(is_f32(x) || (variant == 3 && d->dtype == MMTTA_BF16) || variant == 1 || thin_bf, MMTTA_ERR_UNSUPPORTED,
               "direct conv: a bf16-stored input is supported by the matrix-core up-convolution and the lanes-along-K kernel only");
   // 1x1x1 head on voxel-dense tensors, nothing fused: the streaming kernel
@@ -1494,7 +1492,7 @@ int direct_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
   return THIN_DIRECT;
 }
 
-int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
+int direct_conv_run(int kernel, const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const void* packed,
                     const float* bias, const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, float* stats,
                     const PSets& sets, hipStream_t stream) {
   DArgs a;
@@ -1519,7 +1517,6 @@ int direct_conv_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
     attr_set = true;
   }
   const bool has_t = a.tin.mean != nullptr || a.tin.scale != nullptr;
-  const int kernel = direct_kernel(d, x, x_norm, epi, y, accumulate, stats);
   if (kernel < 0) return kernel;
   switch (kernel) {
 #ifndef MMTTA_ACT_LEAKY_TU

@@ -1145,8 +1145,8 @@ static int config_id(const Config& c) {
 // Which kernel a call runs: the values are the public ids (mmtta_conv_plan_t.config, mmtta_conv_route).  Every other value
 // 0..14 is an implicit GEMM, config_id of its tile.
 enum CRoute : int {
-  C_DIRECT = 6,      // conv_direct.hip: <= 4 produced channels (direct_conv_run picks the variant)
-  C_THIN = 13,       // conv_direct.hip: thin-K kernels, <= 4 gathered channels into 32 / 64 (chan_conv_run)
+  C_DIRECT = 6,      // conv_direct.hip: <= 4 produced channels (direct_kernel names the variant, direct_conv_run launches it)
+  C_THIN = 13,       // conv_direct.hip: thin-K kernels, <= 4 gathered channels into 32 / 64 (chan_kernel, chan_conv_run)
   C_CLS_FUSED = 15,  // igemm_cls8_kernel: the 8 parity classes of a stride-2 transposed form in one workgroup
   C_PW_SMALL = 16,   // pointwise_small_k_kernel: fp32 1x1x1 from <= 4 channels, nothing fused
   C_PW_MFMA = 17,    // pointwise_mfma_kernel: bf16 1x1x1 streamed over voxel-dense tensors
@@ -1160,43 +1160,13 @@ struct RunFacts {
   const float* bias;                   // the run's bias (mmtta_conv_route has none to show: null)
 };
 
-// Raw staging of the implicit-GEMM family (MMTTA_OPT_RAW_STAGING bit 0; igemm_raw_kernel, igemm_reuse_raw_kernel,
-// igemm_cls8_raw_kernel): a bf16-stored x whose norm-on-load is the identity - none, or neither mean nor scale and no
-// activation - in whole 8-channel chunks (no lane of a 16-byte item holds row padding or a neighbour's channel) that the
-// kernels can read 16 bytes at a time, on a bf16-operand tile with y and the fused add bf16-stored like x.  The raw kernels
-// are instantiated in the plain translation unit only: a call the LeakyReLU one runs (a LeakyReLU on the fused add) keeps
-// the transform.  The one function behind mmtta_conv_stages_raw and the launchers.
-#ifdef MMTTA_ACT_LEAKY_TU
-constexpr bool RAW_KERNELS = false;
-#else
-constexpr bool RAW_KERNELS = true;
-#endif
-static bool raw_operand(const mmtta_tensor* x, const mmtta_norm_on_load* x_norm) {
-  return is_bf16(x) && x->c % 8 == 0 && quad_aligned(x, 16, 8) &&
-         (x_norm == nullptr || (x_norm->mean == nullptr && x_norm->scale == nullptr && x_norm->relu == MMTTA_ACT_NONE));
-}
-static bool raw_staging(int route, bool bf_tile, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* y,
-                        const mmtta_tensor* add) {
-  const bool igemm = route != 6 && route != 13 && route != 16 && route != 17;      // (C_DIRECT, C_THIN, C_PW_SMALL, C_PW_MFMA)
-  return RAW_KERNELS && (g_raw_staging & 1) && igemm && bf_tile && raw_operand(x, x_norm) && is_bf16(y) && (add == nullptr || is_bf16(add));
-}
-
-// The pipelined class-fused kernel (MMTTA_OPT_CLS8_PIPELINE; igemm_cls8_pipe_kernel): route 15 on a call that stages raw.  The
-// one function behind mmtta_conv_cls8_pipelined and the launcher.
-static bool cls8_pipelined(int route, bool bf_tile, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* y,
-                           const mmtta_tensor* add) {
-  return g_cls8_pipeline && route == 15 /* C_CLS_FUSED */ && raw_staging(route, bf_tile, x, x_norm, y, add);
-}
-
-// ... with the lean interior epilogue (MMTTA_OPT_CLS8_LEAN_EPILOGUE bit 0; igemm_cls8_lean_kernel): a pipelined call - so x, y
-// and the add are bf16-stored - whose y and add have whole 8-channel groups: a lane pair stores 16 bytes of a row, and both
-// lanes of a pair are live or dead together.  (cls_fused_operand has put y's rows and strides on 16 bytes.)  The one function
-// behind mmtta_conv_cls8_lean_epilogue and the launcher.
-static bool cls8_lean(int route, bool bf_tile, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* y,
-                      const mmtta_tensor* add) {
-  return (g_cls8_lean_epilogue & 1) && cls8_pipelined(route, bf_tile, x, x_norm, y, add) && y->c % 8 == 0 &&
-         (add == nullptr || add->c % 8 == 0);
-}
+// The class-fused kernel of a call of route 15: each form is a special case of the one before it
+enum Cls8Form : int {
+  CLS8_TRANSFORM = 0,      // igemm_cls8_kernel: the norm-on-load applied while staging
+  CLS8_RAW = 1,            // igemm_cls8_raw_kernel (raw_staging)
+  CLS8_PIPELINED = 2,      // igemm_cls8_pipe_kernel (cls8_pipelined)
+  CLS8_LEAN = 3,           // igemm_cls8_lean_kernel (cls8_lean)
+};
 
 struct Geometry {
   int route;      // CRoute
@@ -1207,7 +1177,40 @@ struct Geometry {
   int nstages, ksplit, sps;
   int stats_rows;              // rows of the partial-statistics slab the call writes
   int64_t workspace_bytes;     // split-K partial sums
+  // ---- the variant of the route: what picks the kernel of a run.  plan_run fills these and the launchers read them; a plan
+  // of the shapes alone (geometry with rt = null) leaves them cleared.
+  bool leaky;                  // a LeakyReLU on x or on the fused add: the call runs in the leaky:: instantiation, which has
+                               // none of the raw, pipelined, lean or head-loss kernels
+  bool raw;                    // raw_staging
+  int cls8;                    // Cls8Form (route 15)
+  int thin_kernel;             // routes 6 and 13: the THIN_* id, or the negative status the launcher returns; 0 elsewhere
+  int thin_lean;               // what mmtta_conv_thin_lean reports: 1 the thin-K convolution (route 13), 2 the up-convolution (6)
 };
+
+// Raw staging of the implicit-GEMM family (MMTTA_OPT_RAW_STAGING bit 0; igemm_raw_kernel, igemm_reuse_raw_kernel,
+// igemm_cls8_raw_kernel): a bf16-stored x whose norm-on-load is the identity - none, or neither mean nor scale and no
+// activation - in whole 8-channel chunks (no lane of a 16-byte item holds row padding or a neighbour's channel) that the
+// kernels can read 16 bytes at a time, on a bf16-operand tile with y and the fused add bf16-stored like x.  plan_run asks
+// it for the calls of the plain instantiation.
+static bool raw_operand(const mmtta_tensor* x, const mmtta_norm_on_load* x_norm) {
+  return is_bf16(x) && x->c % 8 == 0 && quad_aligned(x, 16, 8) &&
+         (x_norm == nullptr || (x_norm->mean == nullptr && x_norm->scale == nullptr && x_norm->relu == MMTTA_ACT_NONE));
+}
+static bool raw_staging(const Geometry& g, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* y,
+                        const mmtta_tensor* add) {
+  const bool igemm = g.route != C_DIRECT && g.route != C_THIN && g.route != C_PW_SMALL && g.route != C_PW_MFMA;
+  return (g_raw_staging & 1) && igemm && g.cfg.bf && raw_operand(x, x_norm) && is_bf16(y) && (add == nullptr || is_bf16(add));
+}
+
+// The pipelined class-fused kernel (MMTTA_OPT_CLS8_PIPELINE; igemm_cls8_pipe_kernel): route 15 on a call that stages raw.
+static bool cls8_pipelined(const Geometry& g) { return g_cls8_pipeline && g.route == C_CLS_FUSED && g.raw; }
+
+// ... with the lean interior epilogue (MMTTA_OPT_CLS8_LEAN_EPILOGUE bit 0; igemm_cls8_lean_kernel): a pipelined call - so x, y
+// and the add are bf16-stored - whose y and add have whole 8-channel groups: a lane pair stores 16 bytes of a row, and both
+// lanes of a pair are live or dead together.  (cls_fused_operand has put y's rows and strides on 16 bytes.)
+static bool cls8_lean(const mmtta_tensor* y, const mmtta_tensor* add) {
+  return (g_cls8_lean_epilogue & 1) && y->c % 8 == 0 && (add == nullptr || add->c % 8 == 0);
+}
 
 static int expected_out_dim(const mmtta_conv_desc* d, int in) {
   switch (d->op) {
@@ -1266,6 +1269,7 @@ static int stats_rows_per_tile(const Geometry& g) {
 static int geometry(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y, const RunFacts* rt, Geometry& g) {
   int st = validate_desc(d);
   if (st) return st;
+  g.leaky = g.raw = false; g.cls8 = CLS8_TRANSFORM; g.thin_kernel = g.thin_lean = 0;
   MMTTA_CHECK(x && y && x->ptr && y->ptr, MMTTA_ERR_INVALID, "conv: null tensor");
   MMTTA_CHECK(is_cl(x) && is_cl(y), MMTTA_ERR_UNSUPPORTED, "conv: tensors must be channels-last (sc == 1)");
   op_dims(d, g.K, g.N, g.si, g.classes);
@@ -1452,6 +1456,15 @@ static int launch_cfg_t(const GArgs& a_in, const Taps* ht, int tiles, hipStream_
   return st;
 }
 
+// The raw, pipelined and lean kernels are instantiated in the plain translation unit only (their form has no activation to
+// vary).  The guard keeps the LeakyReLU one from instantiating them; which call takes them is the plan's word (Geometry::raw,
+// ::cls8), and the plan of a call that runs there says none.
+#ifdef MMTTA_ACT_LEAKY_TU
+constexpr bool RAW_KERNELS = false;
+#else
+constexpr bool RAW_KERNELS = true;
+#endif
+
 // storage dispatch: bf16-stored activations exist for bf16-operand layers only (forward: input, output and fused add all
 // bf16; everything else all fp32)
 template <int NB, int MB, int TZ, int TY, int TX, int KCI, bool BF, int OCC = 2, bool REUSE = false>
@@ -1547,8 +1560,7 @@ static int igemm_run(const ConvCall& c, const Geometry& g) {
   GArgs a; Taps ht[8];
   const int st = fill_gargs(c, g, a, ht);
   if (st) return st;
-  const bool raw = raw_staging(g.route, g.cfg.bf, c.x, c.x_norm, c.y, (c.epi && c.epi->add) ? c.epi->add : nullptr);
-  return launch_any(g.route, a, ht, g.tiles, raw, c.stream);
+  return launch_any(g.route, a, ht, g.tiles, g.raw, c.stream);
 }
 
 static int cls_fused_run(const ConvCall& c, const Geometry& g) {
@@ -1560,10 +1572,12 @@ static int cls_fused_run(const ConvCall& c, const Geometry& g) {
   MMTTA_CHECK(a.in_bf == a.out_bf && (a.add == nullptr || a.add_bf == a.out_bf), MMTTA_ERR_UNSUPPORTED,
               "conv: input, output and fused add must share one storage type (in %d out %d add %d)", a.in_bf, a.out_bf, a.add_bf);
   if constexpr (RAW_KERNELS) {
-    const mmtta_tensor* ad = (c.epi && c.epi->add) ? c.epi->add : nullptr;
-    if (cls8_lean(g.route, g.cfg.bf, c.x, c.x_norm, c.y, ad)) return launch_cls8_t<16, true, true, true, true>(a, g.tiles, c.stream);
-    if (cls8_pipelined(g.route, g.cfg.bf, c.x, c.x_norm, c.y, ad)) return launch_cls8_t<16, true, true, true>(a, g.tiles, c.stream);
-    if (raw_staging(g.route, g.cfg.bf, c.x, c.x_norm, c.y, ad)) return launch_cls8_t<16, true, true>(a, g.tiles, c.stream);
+    switch (g.cls8) {
+      case CLS8_LEAN: return launch_cls8_t<16, true, true, true, true>(a, g.tiles, c.stream);
+      case CLS8_PIPELINED: return launch_cls8_t<16, true, true, true>(a, g.tiles, c.stream);
+      case CLS8_RAW: return launch_cls8_t<16, true, true>(a, g.tiles, c.stream);
+      default: break;
+    }
   }
   return a.in_bf ? launch_cls8_t<16, true>(a, g.tiles, c.stream) : launch_cls8_t<16, false>(a, g.tiles, c.stream);
 }
@@ -1585,11 +1599,27 @@ static int pointwise_mfma_run(const ConvCall& c, const Geometry& g) {
   return launch_status("1x1 conv (streaming MFMA)");
 }
 
-// The plan of a run: the one function behind mmtta_conv_route and conv_run_body
+// The plan of a run - the route and its variant: the one function behind conv_run_body and every query of a run
+// (mmtta_conv_route ... mmtta_conv_thin_kernel, mmtta_conv_head_loss_eligible).  A thin kernel's refusal is part of the plan
+// (Geometry::thin_kernel < 0), not an error of planning: the launcher returns it from its place in the run.
 static int plan_run(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
                     const mmtta_tensor* y, int accumulate, const float* stats, const float* bias, Geometry& g) {
-  const RunFacts rt{stats, epi ? epi->add : nullptr, x_norm, accumulate, bias};
-  return geometry(d, x, y, &rt, g);
+  const mmtta_tensor* add = epi ? epi->add : nullptr;
+  const RunFacts rt{stats, add, x_norm, accumulate, bias};
+  const int st = geometry(d, x, y, &rt, g);
+  if (st) return st;
+  g.leaky = nl_leaky(x_norm) || (add && nl_leaky(&epi->add_norm));
+  g.raw = !g.leaky && raw_staging(g, x, x_norm, y, add);
+  if (cls8_pipelined(g)) g.cls8 = cls8_lean(y, add) ? CLS8_LEAN : CLS8_PIPELINED;
+  else if (g.route == C_CLS_FUSED && g.raw) g.cls8 = CLS8_RAW;
+  if (g.route == C_THIN) {
+    g.thin_lean = chan_lean_applicable(d, x, x_norm, epi, y, accumulate) ? 1 : 0;
+    g.thin_kernel = chan_kernel(d, x, epi, y, g.thin_lean != 0);
+  } else if (g.route == C_DIRECT) {
+    g.thin_lean = direct_upconv8_lean(d, x, x_norm, epi, y) ? 2 : 0;
+    g.thin_kernel = direct_kernel(d, x, x_norm, epi, y, accumulate, stats, g.thin_lean != 0);
+  }
+  return MMTTA_OK;
 }
 
 // mmtta_conv_run_sets past the checks of its norm-on-load descriptors: plan, check, switch
@@ -1604,9 +1634,9 @@ int conv_run_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_n
   if (st) return st;
   const ConvCall c{d, x, x_norm, packed, bias, epi, y, accumulate, stats, workspace, workspace_bytes, psets(sets), (hipStream_t)stream};
   switch (g.route) {
-    case C_DIRECT: return direct_conv_run(d, x, x_norm, packed, bias, epi, y, accumulate, stats, c.ps, c.stream);
+    case C_DIRECT: return direct_conv_run(g.thin_kernel, d, x, x_norm, packed, bias, epi, y, accumulate, stats, c.ps, c.stream);
     case C_PW_SMALL: return pointwise_small_run(x, packed, g.Kp, g.Np, bias, y, accumulate, c.ps, c.stream);
-    case C_THIN: return chan_conv_run(d, x, x_norm, packed, g.Kp, g.Np, bias, epi, y, accumulate, stats, c.ps, c.stream);
+    case C_THIN: return chan_conv_run(g.thin_kernel, d, x, x_norm, packed, g.Kp, g.Np, bias, epi, y, accumulate, stats, c.ps, c.stream);
     case C_PW_MFMA: return pointwise_mfma_run(c, g);
     case C_CLS_FUSED: return cls_fused_run(c, g);
     default: return igemm_run(c, g);
@@ -1732,71 +1762,34 @@ extern "C" int mmtta_conv_plan(const mmtta_conv_desc* d, const mmtta_tensor* x, 
   return MMTTA_OK;
 }
 
-extern "C" int mmtta_conv_route(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                                const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
-  Geometry g;
+// ---- the queries of a run: each reads one field of the plan mmtta_conv_run would make for these operands (it has no bias
+// to show: null), or reports the plan's error as a negative status
+static int query_plan(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_conv_epilogue* epi,
+                      const mmtta_tensor* y, int accumulate, const float* stats, Geometry& g) {
   const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
-  if (st) return st < 0 ? st : -st;
-  return g.route;
+  return st < 0 ? st : -st;
 }
-
-extern "C" int mmtta_conv_stages_raw(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                                     const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
-  Geometry g;
-  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
-  if (st) return st < 0 ? st : -st;
-  const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
-  // (a LeakyReLU on the fused add sends the run to the LeakyReLU instantiation, which has no raw kernels)
-  return (raw_staging(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
-}
-
-extern "C" int mmtta_conv_cls8_pipelined(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                                         const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
-  Geometry g;
-  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
-  if (st) return st < 0 ? st : -st;
-  const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
-  // (a LeakyReLU on the fused add sends the run to the LeakyReLU instantiation, which has no raw kernels)
-  return (cls8_pipelined(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
-}
-
-extern "C" int mmtta_conv_cls8_lean_epilogue(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                                             const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
-  Geometry g;
-  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
-  if (st) return st < 0 ? st : -st;
-  const mmtta_tensor* add = (epi && epi->add) ? epi->add : nullptr;
-  // (a LeakyReLU on the fused add sends the run to the LeakyReLU instantiation, which has no raw kernels)
-  return (cls8_lean(g.route, g.cfg.bf, x, x_norm, y, add) && !(add && nl_leaky(&epi->add_norm))) ? 1 : 0;
-}
-
-extern "C" int mmtta_conv_thin_lean(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                                    const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
-  Geometry g;
-  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
-  if (st) return st < 0 ? st : -st;
-  if (g.route == C_THIN) return chan_lean_applicable(d, x, x_norm, epi, y, accumulate) ? 1 : 0;
-  if (g.route == C_DIRECT) return direct_upconv8_lean(d, x, x_norm, epi, y) ? 2 : 0;
-  return 0;
-}
-
-extern "C" int mmtta_conv_thin_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                                      const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {
-  Geometry g;
-  const int st = plan_run(d, x, x_norm, epi, y, accumulate, stats, nullptr, g);
-  if (st) return st < 0 ? st : -st;
-  // (a call with a LeakyReLU runs the other instantiation's launcher; it has no lean kernels, and the lean predicates say so)
-  if (g.route == C_THIN) return chan_kernel(d, x, x_norm, epi, y, accumulate);
-  if (g.route == C_DIRECT) return direct_kernel(d, x, x_norm, epi, y, accumulate, stats);
-  return 0;
-}
+#define MMTTA_CONV_QUERY(name, field)                                                                                      \
+  extern "C" int name(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,                  \
+                      const mmtta_conv_epilogue* epi, const mmtta_tensor* y, int accumulate, const float* stats) {         \
+    Geometry g;                                                                                                            \
+    const int st = query_plan(d, x, x_norm, epi, y, accumulate, stats, g);                                                 \
+    return st ? st : (field);                                                                                              \
+  }
+MMTTA_CONV_QUERY(mmtta_conv_route, g.route)
+MMTTA_CONV_QUERY(mmtta_conv_stages_raw, g.raw ? 1 : 0)
+MMTTA_CONV_QUERY(mmtta_conv_cls8_pipelined, g.cls8 >= CLS8_PIPELINED ? 1 : 0)
+MMTTA_CONV_QUERY(mmtta_conv_cls8_lean_epilogue, g.cls8 == CLS8_LEAN ? 1 : 0)
+MMTTA_CONV_QUERY(mmtta_conv_thin_lean, g.thin_lean)
+MMTTA_CONV_QUERY(mmtta_conv_thin_kernel, g.thin_kernel)
+#undef MMTTA_CONV_QUERY
 
 // ---- the head convolution with the entropy objective in its epilogue (MMTTA_OPT_HEAD_LOSS_PAIR bit 0)
 static int head_loss_plan(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                           const mmtta_conv_epilogue* epi, const mmtta_tensor* y, const mmtta_tensor* dz, int softmax, int per_item,
                           bool& eligible) {
   Geometry g;
-  const int st = plan_run(d, x, x_norm, epi, y, 0, nullptr, nullptr, g);
+  const int st = query_plan(d, x, x_norm, epi, y, 0, nullptr, g);
   if (st) return st;
   eligible = g.route == C_DIRECT && direct_head_loss_eligible(d, x, x_norm, epi, y, dz, softmax, per_item);
   return MMTTA_OK;
@@ -1807,8 +1800,7 @@ extern "C" int mmtta_conv_head_loss_eligible(const mmtta_conv_desc* d, const mmt
                                              int softmax, int per_item) {
   bool ok = false;
   const int st = head_loss_plan(d, x, x_norm, epi, y, dlogits, softmax, per_item, ok);
-  if (st) return st < 0 ? st : -st;
-  return ok ? 1 : 0;
+  return st ? st : (ok ? 1 : 0);
 }
 
 extern "C" int64_t mmtta_conv_head_loss_partials(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* y) {

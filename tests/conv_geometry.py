@@ -132,6 +132,23 @@ def _fake_tensor(_lib, base, n, ch, dhw, bf):
     return _lib.Tensor(base, n, ch, d, h, w, d * h * w * sw, 1, h * w * sw, w * sw, sw, _lib.BF16 if bf else _lib.F32, 0)
 
 
+def fake(base, c, dhw, bf=True, n=2):
+    """A channels-last descriptor of dense voxel rows at a made-up address: the planner never reads tensor memory."""
+    from multimodal_tta_amd import _lib
+    return _fake_tensor(_lib, base, n, c, dhw, bf)
+
+
+def query(fn, desc, x, y, x_nl=None, add=None, add_nl=None, accumulate=0, stats=None):
+    """One of the queries of a run (mmtta_conv_route, mmtta_conv_stages_raw, ...: they share a signature) for the call
+    mmtta_conv_run would get; `add` is the fused add's tensor, `add_nl` its norm-on-load (default: none)."""
+    from multimodal_tta_amd import _lib
+    epi = None
+    if add is not None:
+        epi = _lib.ConvEpilogue(C.pointer(add), add_nl if add_nl is not None else _lib.norm_on_load())
+    return int(getattr(_lib.load(), fn)(C.byref(desc), C.byref(x), C.byref(x_nl) if x_nl is not None else None,
+                                        C.byref(epi) if epi is not None else None, C.byref(y), accumulate, stats))
+
+
 def _descs(c, dtype, orientation, stored_bf16):
     from multimodal_tta_amd import _lib
     fo, do = (_lib.CONVT_FWD, _lib.CONVT_DGRAD) if c.transposed else (_lib.CONV_FWD, _lib.CONV_DGRAD)

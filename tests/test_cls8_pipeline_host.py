@@ -14,18 +14,7 @@ X, Y, A, P = 1 << 30, 1 << 40, 1 << 41, 1 << 21
 COARSE, FINE = (8, 8, 8), (16, 16, 16)
 
 
-def _t(base, c, dhw, bf=True, n=2):
-    from multimodal_tta_amd import _lib
-    return cg._fake_tensor(_lib, base, n, c, dhw, bf)
-
-
-def _query(fn, desc, x, y, x_nl=None, add=None, add_nl=None, accumulate=0, stats=None):
-    from multimodal_tta_amd import _lib
-    epi = None
-    if add is not None:
-        epi = _lib.ConvEpilogue(C.pointer(add), add_nl if add_nl is not None else _lib.norm_on_load())
-    return int(getattr(_lib.load(), fn)(C.byref(desc), C.byref(x), C.byref(x_nl) if x_nl is not None else None,
-                                        C.byref(epi) if epi is not None else None, C.byref(y), accumulate, stats))
+_t, _query = cg.fake, cg.query
 
 
 def _pipelined(*a, **k):

@@ -23,8 +23,6 @@ every path of the new code:
   slices     a fused add that is a channel slice of a wider tensor (its strides differ from y's)
 Refused calls - a norm-on-load on x; 36 produced channels (y is then a 36-channel slice of 40-channel rows, which route 15
 admits) - must report 0 from the query and give the same result under both settings."""
-import ctypes as C
-
 import pytest
 import torch
 
@@ -70,11 +68,7 @@ def _case(form, name):
     return cg.case(f"lean_{form}_{name}", N, K, 3, 2, False, (n,) + fine), "dgrad"      # dy = grid
 
 
-def _query(fn, desc, x, y, x_nl=None, add=None, accumulate=0, stats=None):
-    from multimodal_tta_amd import _lib
-    epi = _lib.ConvEpilogue(C.pointer(add), _lib.norm_on_load()) if add is not None else None
-    return int(getattr(_lib.load(), fn)(C.byref(desc), C.byref(x), C.byref(x_nl) if x_nl is not None else None,
-                                        C.byref(epi) if epi is not None else None, C.byref(y), accumulate, stats))
+_query = cg.query
 
 
 def test_shapes_are_small():

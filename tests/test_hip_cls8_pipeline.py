@@ -15,8 +15,6 @@ N = cin), on the coarse grid of the form.  The shapes are the smallest that reac
   batching   batch 1 and 3, one parameter set and one per item (weights and bias)
 Every case runs plain (a forward: bias + statistics rows) and with accumulate plus a fused add.  One refused call - a
 norm-on-load on x - must report 0 from the query and give the same result under both settings."""
-import ctypes as C
-
 import pytest
 import torch
 
@@ -56,11 +54,7 @@ def _case(form, name):
     return cg.case(f"pipe_{form}_{name}", N, K, 3, 2, False, (n,) + tuple(2 * v for v in grid)), "dgrad"      # dy = grid
 
 
-def _query(fn, desc, x, y, x_nl=None, add=None, accumulate=0, stats=None):
-    from multimodal_tta_amd import _lib
-    epi = _lib.ConvEpilogue(C.pointer(add), _lib.norm_on_load()) if add is not None else None
-    return int(getattr(_lib.load(), fn)(C.byref(desc), C.byref(x), C.byref(x_nl) if x_nl is not None else None,
-                                        C.byref(epi) if epi is not None else None, C.byref(y), accumulate, stats))
+_query = cg.query
 
 
 def test_shapes_are_small():

@@ -17,8 +17,6 @@ re-reads the last valid chunk - is made visible: the last valid chunk holds larg
 weight image behind K, zeros in a real image, are set to 1 for both runs, so that whatever is staged there reaches the
 result.  A few inputs are -0.0, the one stored value the transform changes (to +0.0), which no sum that starts at +0 shows.
 """
-import ctypes as C
-
 import pytest
 import torch
 
@@ -75,13 +73,7 @@ def _case(kind, grid, n):
     return cg.case(f"raw_{kind}_{n}x" + "x".join(map(str, grid)), cin, cout, k, stride, transposed, (n,) + tuple(shape))
 
 
-def _query(fn, desc, x, y, x_nl=None, add=None, add_nl=None, accumulate=0, stats=None):
-    from multimodal_tta_amd import _lib
-    epi = None
-    if add is not None:
-        epi = _lib.ConvEpilogue(C.pointer(add), add_nl if add_nl is not None else _lib.norm_on_load())
-    return int(getattr(_lib.load(), fn)(C.byref(desc), C.byref(x), C.byref(x_nl) if x_nl is not None else None,
-                                        C.byref(epi) if epi is not None else None, C.byref(y), accumulate, stats))
+_query = cg.query
 
 
 def _stages_raw(*a, **k):

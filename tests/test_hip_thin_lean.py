@@ -13,8 +13,6 @@ What a stage has to blank by itself is made visible: the planes next to the out-
 them again for the halo), a few inputs are -0.0, and for K < 4 the pad lanes of the 8-byte voxels hold 3 while the weight
 fragments behind K - zeros in a real image - are set to 1 for both runs, so that anything staged there reaches the result.
 """
-import ctypes as C
-
 import pytest
 import torch
 
@@ -31,13 +29,7 @@ GRIDS = {"tile": TILE, "z+1": (5, 4, 8), "y+1": (4, 5, 8), "x+1": (4, 4, 9), "2x
 UPCONV_BIG = (20, 24, 40)      # 5 x 6 x 5 = 150 tiles: a persistent workgroup walks more than one
 
 
-def _query(fn, desc, x, y, x_nl=None, add=None, add_nl=None, accumulate=0, stats=None):
-    from multimodal_tta_amd import _lib
-    epi = None
-    if add is not None:
-        epi = _lib.ConvEpilogue(C.pointer(add), add_nl if add_nl is not None else _lib.norm_on_load())
-    return int(getattr(_lib.load(), fn)(C.byref(desc), C.byref(x), C.byref(x_nl) if x_nl is not None else None,
-                                        C.byref(epi) if epi is not None else None, C.byref(y), accumulate, stats))
+_query = cg.query
 
 
 def _gen(*key):
