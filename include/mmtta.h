@@ -457,8 +457,8 @@ int64_t mmtta_conv_wgrad_workspace_bytes(const mmtta_conv_desc* desc, const mmtt
  * or a negative mmtta error code. */
 int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_tensor* dy);
 /* Which operands of this weight gradient the transposed-read kernel would stage raw (MMTTA_OPT_RAW_STAGING bit 1): bit 0
- * the module input x, bit 1 the gradient dy; 0 for every other kernel, or a negative mmtta error code.  Host-only, the
- * predicate the launcher itself asks. */
+ * the module input x, bit 1 the gradient dy; 0 for every other kernel, or a negative mmtta error code.  Host-only, a
+ * field of the plan the launcher itself reads. */
 int mmtta_conv_wgrad_stages_raw(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                 const mmtta_tensor* dy);
 int mmtta_conv_wgrad(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
@@ -1384,8 +1384,8 @@ int mmtta_conv_wgrad_update_sets(const mmtta_conv_desc* desc, const mmtta_tensor
                                  const mmtta_tensor* dy, const mmtta_update_target* target, void* workspace,
                                  int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream);
 /* Whether mmtta_conv_wgrad_update_sets would step the optimizer in the epilogue of this call's weight-gradient kernel
- * (MMTTA_OPT_WGRAD_EPILOGUE_UPDATE): 1 / 0, or a negative mmtta error code.  Host-only, the predicate the launcher itself
- * asks; the launcher also needs p / m / v of every set on 16 bytes, which a query without a target cannot see. */
+ * (MMTTA_OPT_WGRAD_EPILOGUE_UPDATE): 1 / 0, or a negative mmtta error code.  Host-only, a field of the plan the launcher
+ * itself reads; planned with a target it also needs p / m / v of every set on 16 bytes, which a query cannot see. */
 int mmtta_conv_wgrad_updates_in_epilogue(const mmtta_conv_desc* desc, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                          const mmtta_tensor* dy, const mmtta_param_sets* sets);
 

@@ -38,6 +38,9 @@ struct WArgs {
   int g_bf, d_bf;   // storage of the gathered / dense tensor: 1 = bf16 elements (the forward activation of bf16 precision)
   int convt;        // transposed module: the dense operand is the module input (carries the norm-on-load)
 };
+// An entry of a launch table (a form that is not built: null).  The tables list bf16- before fp32-stored, paired before single
+// and ConvTranspose3d before Conv3d, and are indexed to match: the order the kernels have in the code object.
+using WLaunch = int (*)(const WArgs& a, int S, hipStream_t s);
 
 // NTW = accumulators per wave: 7 for the 27-tap kernel (taps wave, wave+4, ...; slot 27 is a dummy that is
 // never flushed), 1 for a single tap (the four waves then split the voxel pairs instead).
@@ -946,10 +949,10 @@ static int launch_wgrad_tr1_t(const WArgs& a, int S, hipStream_t s) {
 }
 
 static int launch_wgrad_tr1(const WArgs& a, int S, hipStream_t s) {
-  if (a.g_bf && a.d_bf) return launch_wgrad_tr1_t<true, true>(a, S, s);      // bf16-stored gradients (method.grad_storage)
-  if (a.g_bf) return launch_wgrad_tr1_t<true, false>(a, S, s);
-  if (a.d_bf) return launch_wgrad_tr1_t<false, true>(a, S, s);
-  return launch_wgrad_tr1_t<false, false>(a, S, s);
+  static constexpr WLaunch by_storage[2][2] = {      // [g fp32-stored][d fp32-stored] (bf16-stored gradients: method.grad_storage)
+      {launch_wgrad_tr1_t<true, true>, launch_wgrad_tr1_t<true, false>},
+      {launch_wgrad_tr1_t<false, true>, launch_wgrad_tr1_t<false, false>}};
+  return by_storage[!a.g_bf][!a.d_bf](a, S, s);
 }
 
 // the module input (norm-on-load, possibly bf16-stored) is the gathered operand of a convolution and the dense one of a
@@ -960,46 +963,35 @@ constexpr bool WGRAD_RAW_KERNELS = false;
 #else
 constexpr bool WGRAD_RAW_KERNELS = true;
 #endif
-// the raw instantiations of one (tile, module kind, column blocks): the gradient side is raw in all of them; `both`: the
-// module-input side too
-template <int TZ, int TY, int SI, bool TD, int NB>
-static int launch_wgrad_tr_raw(const WArgs& a, int S, bool both, hipStream_t s) {
-  if (both) return launch_wgrad_tr_t<TZ, TY, SI, true, true, TD, NB, true, true>(a, S, s);
-  return launch_wgrad_tr_t<TZ, TY, SI, true, true, TD, NB, TD, !TD>(a, S, s);
+// launch_wgrad_tr_t as a table entry; a form that is not built is null, and not instantiated
+template <bool BUILT, int TZ, int TY, int SI, bool GBF, bool DBF, bool TD, int NB = 1, bool RG = false, bool RD = false>
+static constexpr WLaunch wgrad_tr_form() {
+  if constexpr (BUILT) return launch_wgrad_tr_t<TZ, TY, SI, GBF, DBF, TD, NB, RG, RD>;
+  else return nullptr;
 }
 
-// raw: bit 0 the module input, bit 1 the gradient tensor go to LDS as loaded (wgrad_raw_bits; bit 0 is set with bit 1 only)
+// The forms of one tile: a bf16-stored gradient next to a bf16-stored module input only, paired column blocks for the all-bf16
+// forms only, transposed convolutions at stride 2 only - the planner (wgeometry) produces no other index.  raw (the plan's:
+// all-bf16 forms, stride 2, plain translation unit): bit 1 the gradient goes to LDS as loaded, bit 0 the module input too.
 template <int TZ, int TY, int SI>
-static int launch_wgrad_tr(const WArgs& a, int S, hipStream_t s, int ncb = 1, int raw = 0) {
-  MMTTA_CHECK(a.gvec4 && a.dvec4, MMTTA_ERR_INVALID, "wgrad: transposed-read kernel selected for unaligned tensors");
-  MMTTA_CHECK(ncb == 1 || (a.g_bf && a.d_bf), MMTTA_ERR_INVALID, "wgrad: paired column blocks exist for the all-bf16 forms");
-  if constexpr (WGRAD_RAW_KERNELS && SI == 2) {      // (stride 1 has no raw instantiation: wgrad_raw_bits)
-    if ((raw & 2) && a.g_bf && a.d_bf) {
-      const bool both = (raw & 1) != 0;
-      if (a.convt) return ncb == 2 ? launch_wgrad_tr_raw<TZ, TY, SI, true, 2>(a, S, both, s) : launch_wgrad_tr_raw<TZ, TY, SI, true, 1>(a, S, both, s);
-      return ncb == 2 ? launch_wgrad_tr_raw<TZ, TY, SI, false, 2>(a, S, both, s) : launch_wgrad_tr_raw<TZ, TY, SI, false, 1>(a, S, both, s);
-    }
-  }
-  if (ncb == 2) {
-    if constexpr (SI == 2) {
-      if (a.convt) return launch_wgrad_tr_t<TZ, TY, SI, true, true, true, 2>(a, S, s);
-    }
-    MMTTA_CHECK(!a.convt, MMTTA_ERR_UNSUPPORTED, "wgrad: conv_transpose is stride 2 only");
-    return launch_wgrad_tr_t<TZ, TY, SI, true, true, false, 2>(a, S, s);
-  }
-  if (a.convt) {
-    MMTTA_CHECK(!a.g_bf || a.d_bf, MMTTA_ERR_UNSUPPORTED, "wgrad: a bf16-stored gradient needs a bf16-stored module input");
-    if constexpr (SI == 2) {
-      if (a.g_bf) return launch_wgrad_tr_t<TZ, TY, SI, true, true, true>(a, S, s);
-      if (a.d_bf) return launch_wgrad_tr_t<TZ, TY, SI, false, true, true>(a, S, s);
-      return launch_wgrad_tr_t<TZ, TY, SI, false, false, true>(a, S, s);
-    }
-    return MMTTA_ERR_UNSUPPORTED;
-  }
-  MMTTA_CHECK(!a.d_bf || a.g_bf, MMTTA_ERR_UNSUPPORTED, "wgrad: a bf16-stored gradient needs a bf16-stored module input");
-  if (a.d_bf) return launch_wgrad_tr_t<TZ, TY, SI, true, true, false>(a, S, s);
-  if (a.g_bf) return launch_wgrad_tr_t<TZ, TY, SI, true, false, false>(a, S, s);
-  return launch_wgrad_tr_t<TZ, TY, SI, false, false, false>(a, S, s);
+static int launch_wgrad_tr(const WArgs& a, int S, int ncb, int raw, hipStream_t s) {
+  constexpr bool T = SI == 2, R = WGRAD_RAW_KERNELS && SI == 2;
+#define MMTTA_TR_FORM(built, ...) wgrad_tr_form<built, TZ, TY, SI, __VA_ARGS__>()
+  static constexpr WLaunch staged_raw[2][2][2] = {      // [Conv3d][one column block][the gradient only]
+      {{MMTTA_TR_FORM(R, true, true, true, 2, true, true), MMTTA_TR_FORM(R, true, true, true, 2, true, false)},
+       {MMTTA_TR_FORM(R, true, true, true, 1, true, true), MMTTA_TR_FORM(R, true, true, true, 1, true, false)}},
+      {{MMTTA_TR_FORM(R, true, true, false, 2, true, true), MMTTA_TR_FORM(R, true, true, false, 2, false, true)},
+       {MMTTA_TR_FORM(R, true, true, false, 1, true, true), MMTTA_TR_FORM(R, true, true, false, 1, false, true)}}};
+  static constexpr WLaunch plain[2][2][2][2] = {      // [one column block][Conv3d][g fp32-stored][d fp32-stored]
+      {{{MMTTA_TR_FORM(T, true, true, true, 2), nullptr}, {nullptr, nullptr}},
+       {{MMTTA_TR_FORM(true, true, true, false, 2), nullptr}, {nullptr, nullptr}}},
+      {{{MMTTA_TR_FORM(T, true, true, true), nullptr}, {MMTTA_TR_FORM(T, false, true, true), MMTTA_TR_FORM(T, false, false, true)}},
+       {{MMTTA_TR_FORM(true, true, true, false), MMTTA_TR_FORM(true, true, false, false)}, {nullptr, MMTTA_TR_FORM(true, false, false, false)}}}};
+#undef MMTTA_TR_FORM
+  const WLaunch form = (raw & 2) ? staged_raw[!a.convt][ncb == 1][!(raw & 1)] : plain[ncb == 1][!a.convt][!a.g_bf][!a.d_bf];
+  MMTTA_CHECK(form != nullptr, MMTTA_ERR_UNSUPPORTED, "wgrad: no transposed-read kernel of stride %d for conv_transpose %d, storage %d / %d, "
+              "%d column blocks, raw %d", SI, a.convt, a.g_bf, a.d_bf, ncb, raw);
+  return form(a, S, s);
 }
 
 // The kernel that updates in its epilogue (wgrad_tr_upd_kernel): only the form wgrad_updates_in_epilogue admits is built -
@@ -1553,30 +1545,31 @@ __global__ __launch_bounds__(256, 2) void wgrad_thin_tr_kernel(W2Args a) {
   }
 }
 
-template <int SI, int PM, int NCB>
+template <int SI, int PM, int NCB, bool QBF>
 static void launch_thin_tr_t(const W2Args& a, dim3 grid, hipStream_t s) {
   constexpr int TY = SI == 1 ? 8 : 4;
   constexpr int BZ = 3 * SI + 3, BY = (TY - 1) * SI + 3, BX = 7 * SI + 3;
   constexpr int QBYTES = (BZ * BY * BX * 8 + 63) / 64 * 64;
   size_t lds = QBYTES + (size_t)NCB * (4 * TY * 8) * 64;
   if (lds < 256 * 8 * sizeof(float)) lds = 256 * 8 * sizeof(float);      // the bias-gradient reduction reuses the images
-  if (a.q_bf) {
-    if constexpr (PM < 2) hipLaunchKernelGGL((wgrad_thin_tr_kernel<SI, PM, NCB, true>), grid, dim3(256), lds, s, a);
-  } else {
-    hipLaunchKernelGGL((wgrad_thin_tr_kernel<SI, PM, NCB>), grid, dim3(256), lds, s, a);
-  }
+  hipLaunchKernelGGL((wgrad_thin_tr_kernel<SI, PM, NCB, QBF>), grid, dim3(256), lds, s, a);
 }
 
-static void launch_thin_tr(const W2Args& a, int si, int ncb, dim3 grid, hipStream_t s) {
-  if (a.p_thin) {                                   // both sides thin: stride 1 only (wgeometry)
-    if (a.p_bf) launch_thin_tr_t<1, 3, 1>(a, grid, s); else launch_thin_tr_t<1, 2, 1>(a, grid, s);
-  } else if (si == 1) {
-    if (a.p_bf) { if (ncb == 2) launch_thin_tr_t<1, 1, 2>(a, grid, s); else launch_thin_tr_t<1, 1, 1>(a, grid, s); }
-    else { if (ncb == 2) launch_thin_tr_t<1, 0, 2>(a, grid, s); else launch_thin_tr_t<1, 0, 1>(a, grid, s); }
-  } else {
-    if (a.p_bf) { if (ncb == 2) launch_thin_tr_t<2, 1, 2>(a, grid, s); else launch_thin_tr_t<2, 1, 1>(a, grid, s); }
-    else { if (ncb == 2) launch_thin_tr_t<2, 0, 2>(a, grid, s); else launch_thin_tr_t<2, 0, 1>(a, grid, s); }
-  }
+// pm (the plan's form): bit 0 P is bf16-stored, bit 1 P is thin too (stride 1, one column block, fp32-stored Q: wgeometry)
+static int launch_thin_tr(const W2Args& a, int si, int pm, int ncb, dim3 grid, hipStream_t s) {
+  using Form = void (*)(const W2Args&, dim3, hipStream_t);
+#define MMTTA_THIN_FORMS(SI, PM) \
+  {{launch_thin_tr_t<SI, PM, 2, true>, launch_thin_tr_t<SI, PM, 2, false>}, {launch_thin_tr_t<SI, PM, 1, true>, launch_thin_tr_t<SI, PM, 1, false>}}
+  static constexpr Form forms[2][4][2][2] = {      // [si - 1][3 - pm][one column block][Q fp32-stored]
+      {{{}, {nullptr, launch_thin_tr_t<1, 3, 1, false>}}, {{}, {nullptr, launch_thin_tr_t<1, 2, 1, false>}}, MMTTA_THIN_FORMS(1, 1),
+       MMTTA_THIN_FORMS(1, 0)},
+      {{}, {}, MMTTA_THIN_FORMS(2, 1), MMTTA_THIN_FORMS(2, 0)}};
+#undef MMTTA_THIN_FORMS
+  const Form form = forms[si - 1][3 - pm][ncb == 1][!a.q_bf];
+  MMTTA_CHECK(form != nullptr, MMTTA_ERR_UNSUPPORTED, "wgrad (thin layer): no transposed-read kernel of stride %d, form %d, %d column blocks, "
+              "bf16-stored Q %d", si, pm, ncb, a.q_bf);
+  form(a, grid, s);
+  return launch_status("wgrad small");
 }
 
 // small_is_cd == 0: dw[(cb*Cs + cs)*ntaps + tap]   (Conv3d with tiny Cin, ConvTranspose3d with tiny Cout)
@@ -1595,7 +1588,6 @@ __global__ void wgrad_small_reduce_kernel(const float* __restrict__ slab, float*
     *o = accumulate ? (*o + s) : s;
   }
 }
-
 
 // ------------------------------------------------------------------ tiny x tiny weight gradient (VALU)
 // Conv3d k3 s1 with <= 4 channels on BOTH sides (the full-resolution R->R unit of the top ResidualUnit): 1 GFLOP
@@ -1756,27 +1748,6 @@ __global__ __launch_bounds__(256) void wgrad_tiny_kernel(WTArgs a) {
   }
 }
 
-template <int CS, bool HAS_T>
-static void launch_tiny_cb(const WTArgs& a, int cb, int blocks, hipStream_t s) {
-  const dim3 grid(3 * ((blocks + 7) / 8) * 8), block(256);      // (plane, workgroup) pairs, see the kernel's id decode
-  switch (cb) {
-    case 1: hipLaunchKernelGGL((wgrad_tiny_kernel<CS, 1, HAS_T>), grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((wgrad_tiny_kernel<CS, 2, HAS_T>), grid, block, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((wgrad_tiny_kernel<CS, 3, HAS_T>), grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL((wgrad_tiny_kernel<CS, 4, HAS_T>), grid, block, 0, s, a); break;
-  }
-}
-
-template <bool HAS_T>
-static void launch_tiny(const WTArgs& a, int cs, int cb, int blocks, hipStream_t s) {
-  switch (cs) {
-    case 1: launch_tiny_cb<1, HAS_T>(a, cb, blocks, s); break;
-    case 2: launch_tiny_cb<2, HAS_T>(a, cb, blocks, s); break;
-    case 3: launch_tiny_cb<3, HAS_T>(a, cb, blocks, s); break;
-    default: launch_tiny_cb<4, HAS_T>(a, cb, blocks, s); break;
-  }
-}
-
 // ------------------------------------------------------------------ host side: plan (wgeometry), then launch
 // The transposed-read kernel's loader: 16-byte items of 8 channels (fp32: two quads), 32-bit element offsets built
 // from 24-bit multiply-adds
@@ -1821,6 +1792,14 @@ struct WGeo {
   int ncb = 1;    // 32-column blocks per workgroup (wgrad_tr_kernel NB, wgrad_thin_tr_kernel NCB)
   bool p_thin;    // W_THIN_TR with <= 4 channels on the dense side as well
   int ips, nsets; // batch items per parameter set, sets per launch: tiles / S / nsl / *_floats / colsum_blocks are PER SET
+  // ---- the variant of the route (plan_wgrad): what the launchers and the queries read beyond the geometry
+  bool leaky;               // x_norm is a LeakyReLU: the call runs the instantiation that builds neither raw nor updating kernels
+  int raw;                  // wgrad_raw_bits: bit 0 the module input, bit 1 the gradient go to LDS as loaded (0 under `leaky`)
+  bool upd_in_epilogue;     // the main kernel steps the optimizer (never under `leaky`); without a target: the layer admits it
+  int g_bf, d_bf, gvec4, dvec4;   // storage and 16-byte accesses of the gathered / dense operand (thin family: of Q / P)
+  int form;                 // W_THIN_TR: PM of the kernel; W_SMALL: 0 one tap, 1 27 taps stride 1, 2 stride 2; W_TINY: HAS_T
+  int refuse; char why[96]; // no kernel serves the route: part of the plan (the queries answer), returned before the first launch
+  int64_t workspace_bytes() const { return (slab_floats + db_floats + pre_floats) * nsets * (int64_t)sizeof(float); }
 };
 
 // A/B switches read from the environment once.  MMTTA_WGRAD_PAIR: 0 no paired column blocks, 2: every stride-1 layer too.
@@ -2032,72 +2011,14 @@ static int check_update_target(const mmtta_conv_desc* d, const WGeo& w, const mm
   return MMTTA_OK;
 }
 
-// ---- the main kernel of each family.  Workspace of a launch, Q = w.nsets sets back to back (set-major) in each region:
-// slabs [Q][slab_floats], bias rows [Q][db_floats], pre-reduced slabs [Q][pre_floats]; `dbws` is the second region, or
-// null when the main kernel has no bias rows to write
-static int launch_tiny_family(const mmtta_conv_desc* d, const WGeo& w, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
-                              const mmtta_tensor* dy, float* ws, float* dbws, hipStream_t s) {
-  MMTTA_CHECK(is_f32(x) && is_f32(dy), MMTTA_ERR_UNSUPPORTED, "wgrad (tiny layer): fp32-stored tensors only");
-  WTArgs t;
-  t.x = tv(x); t.tx = nl(x_norm); t.dy = tv(dy);
-  t.part = ws; t.ld = 27 * d->cin * d->cout;
-  t.dbpart = dbws;
-  t.B = w.tiny_blocks; t.ips = w.ips; t.BT = w.tiny_blocks * w.nsets;
-  if (t.tx.mean != nullptr || t.tx.scale != nullptr) launch_tiny<true>(t, d->cin, d->cout, t.BT, s);
-  else launch_tiny<false>(t, d->cin, d->cout, t.BT, s);
-  return launch_status("wgrad tiny");
-}
-
-static int launch_thin_family(const mmtta_conv_desc* d, const WGeo& w, const mmtta_norm_on_load* x_norm, float* ws, float* dbws,
-                              hipStream_t s) {
-  const int Q = w.nsets;
-  const bool thin_tr = w.route == W_THIN_TR;
-  W2Args b;
-  b.q = (const float*)w.q->ptr; b.qsn = w.q->sn; b.qsd = w.q->sd; b.qsh = w.q->sh; b.qsw = w.q->sw;
-  b.Cs = w.q->c; b.Dq = w.q->d; b.Hq = w.q->h; b.Wq = w.q->w;
-  b.p = (const float*)w.pb->ptr; b.psn = w.pb->sn; b.psd = w.pb->sd; b.psh = w.pb->sh; b.psw = w.pb->sw;
-  b.Cb = w.pb->c; b.Dp = w.pb->d; b.Hp = w.pb->h; b.Wp = w.pb->w;
-  b.tq = w.q_is_x ? nl(x_norm) : nl(nullptr);
-  b.tp = w.q_is_x ? nl(nullptr) : nl(x_norm);
-  b.si = w.si; b.ntaps = w.ntaps;
-  b.slab = ws;
-  b.dbpart = dbws;
-  b.tz = w.tz; b.ty = w.ty; b.tx = w.tx; b.tiles = w.tiles * Q; b.tiles_per_split = w.tps; b.CBp = w.CDp;
-  b.S = w.S; b.tiles_set = w.tiles;
-  b.qvec4 = quad_aligned(w.q, 16) ? 1 : 0;
-  b.pvec4 = quad_aligned(w.pb, quad_bytes(w.pb)) ? 1 : 0;
-  MMTTA_CHECK(is_f32(w.q) || thin_tr, MMTTA_ERR_UNSUPPORTED, "wgrad (thin layer): the <= 4-channel tensor must be fp32-stored");
-  b.p_bf = is_bf16(w.pb) ? 1 : 0;
-  b.bf = (d->dtype == MMTTA_BF16 && w.ntaps == 27) ? 1 : 0;
-  b.p_thin = w.p_thin ? 1 : 0;
-  b.q_bf = is_bf16(w.q) ? 1 : 0;
-  MMTTA_CHECK(!b.q_bf || thin_tr, MMTTA_ERR_UNSUPPORTED, "wgrad (thin layer): a bf16-stored <= 4-channel tensor needs the transposed-read kernel");
-  const int ext = w.ntaps == 1 ? 0 : 2;
-  const int BZ = 3 * w.si + ext + 1, BY = 3 * w.si + ext + 1, BX = 7 * w.si + ext + 1;
-  const size_t lds = ((size_t)BZ * BY * BX * 4 + 128 * 32) * sizeof(float);
-  MMTTA_CHECK((w.ntaps == 27 && (w.si == 1 || w.si == 2)) || (w.ntaps == 1 && w.si == 1), MMTTA_ERR_UNSUPPORTED,
-              "wgrad (thin layer): %d taps with stride %d", w.ntaps, w.si);
-  if (thin_tr) {
-    launch_thin_tr(b, w.si, w.ncb, dim3(w.S * Q, w.CDp / 32 / w.ncb), s);
-  } else {
-    static constexpr decltype(&wgrad_small_kernel<false, 1, false>) forms[2][3] = {      // [p_bf][1 tap | 27 taps s1 | 27 taps s2]
-        {wgrad_small_kernel<false, 1, false>, wgrad_small_kernel<false, 1, true>, wgrad_small_kernel<false, 2, true>},
-        {wgrad_small_kernel<true, 1, false>, wgrad_small_kernel<true, 1, true>, wgrad_small_kernel<true, 2, true>}};
-    const auto kern = forms[b.p_bf][w.ntaps == 1 ? 0 : w.si];
-    hipLaunchKernelGGL(kern, dim3(w.S * Q, w.CDp / 32), dim3(256), lds, s, b);
-  }
-  return launch_status("wgrad small");
-}
-
 // Raw staging of wgrad_tr_kernel (MMTTA_OPT_RAW_STAGING bit 1): which operands of the call go to LDS as loaded - bit 0 the
 // module input x, bit 1 the gradient dy.  Both tensors bf16-stored (the all-bf16 forms), each in whole 8-channel chunks;
 // dy takes no transform, x when its norm-on-load is the identity (none, or neither mean nor scale and no activation).  x goes
 // raw next to a raw dy only.  Stride 2 only (convolutions and transposed convolutions: a box of 12x the tile's voxels is
 // staged for 28 MFMAs a wave): the stride-1 instantiations were measured slower than their twins (profiles/raw_staging_ab.md:
 // 134 against 105 us for the one-block form, which also spills two registers more) and are not built.
-// The one function behind mmtta_conv_wgrad_stages_raw and the launcher.
 static int wgrad_raw_bits(const WGeo& w, const mmtta_norm_on_load* x_norm) {
-  if (!WGRAD_RAW_KERNELS || !(g_raw_staging & 2) || w.route != W_TR_S2) return 0;
+  if (!(g_raw_staging & 2) || w.route != W_TR_S2) return 0;
   const mmtta_tensor *xin = w.convt ? w.dn : w.g, *grad = w.convt ? w.g : w.dn;
   if (!is_bf16(xin) || !is_bf16(grad) || grad->c % 8 != 0) return 0;
   const bool ident = x_norm == nullptr || (x_norm->mean == nullptr && x_norm->scale == nullptr && x_norm->relu == MMTTA_ACT_NONE);
@@ -2112,9 +2033,9 @@ static int wgrad_raw_bits(const WGeo& w, const mmtta_norm_on_load* x_norm) {
 // stride-2 forms (paired column blocks, Conv3d and ConvTranspose3d, transform and raw staging) were built and measured
 // slower than their two launches - they run 128 to 384 workgroups of one per CU, and a workgroup's optimizer rounds have
 // nothing to overlap with (profiles/update_epilogue_ab.md) - so they are left out and the query says 0 for them.
-// The one function behind mmtta_conv_wgrad_updates_in_epilogue and the launcher.
+// Never with the fused update switched off (MMTTA_FUSED_UPDATE=0: mmtta_conv_wgrad_update_sets refuses every call).
 static bool wgrad_updates_in_epilogue(const WGeo& w) {
-  if (!WGRAD_UPD_KERNELS || !g_wgrad_epilogue_update) return false;
+  if (!g_fused_update || !g_wgrad_epilogue_update) return false;
   if (w.route != W_TR_S1 || w.convt || w.ncb != 1) return false;
   if (w.nsl != 1 || w.pre_chunks != 0) return false;
   if (!is_bf16(w.g) || !is_bf16(w.dn)) return false;
@@ -2129,7 +2050,87 @@ static bool update_target_vec16(const mmtta_update_target* upd, const PSets& ps,
   return true;
 }
 
-// `ua` (with `ps`, `kind`): the call updates in the main kernel's epilogue (wgrad_updates_in_epilogue said so)
+// The whole decision of a call: the geometry, then the variant of its route (`upd`: the target of a fused update, or null).
+// The one place the family states the LeakyReLU exception and the one caller of the three predicates above.
+static int plan_wgrad(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* dy,
+                      const mmtta_param_sets* sets, const mmtta_update_target* upd, WGeo& w) {
+  const int st = wgeometry(d, x, dy, sets, w);
+  if (st) return st;
+  w.leaky = nl_leaky(x_norm);
+  w.raw = w.leaky ? 0 : wgrad_raw_bits(w, x_norm);
+  w.upd_in_epilogue = !w.leaky && wgrad_updates_in_epilogue(w) && (upd == nullptr || update_target_vec16(upd, psets(sets), w.nsets));
+  const bool thin = route_thin(w.route);
+  const mmtta_tensor *g = thin ? w.q : w.g, *dn = thin ? w.pb : w.dn;
+  w.g_bf = is_bf16(g) ? 1 : 0; w.gvec4 = quad_aligned(g, thin ? 16 : quad_bytes(g)) ? 1 : 0;
+  w.d_bf = is_bf16(dn) ? 1 : 0; w.dvec4 = quad_aligned(dn, quad_bytes(dn)) ? 1 : 0;
+  auto refuse = [&w](const char* fmt, int a = 0, int b = 0) {
+    if (w.refuse == MMTTA_OK) snprintf(w.why, sizeof(w.why), fmt, a, b);
+    w.refuse = MMTTA_ERR_UNSUPPORTED;
+  };
+  if (w.route == W_TINY) {
+    w.form = (x_norm != nullptr && (x_norm->mean != nullptr || x_norm->scale != nullptr)) ? 1 : 0;
+    if (!is_f32(x) || !is_f32(dy)) refuse("wgrad (tiny layer): fp32-stored tensors only");
+  } else if (w.route == W_THIN_TR) {
+    w.form = (w.p_thin ? 2 : 0) | w.d_bf;
+  } else if (w.route == W_SMALL) {
+    w.form = w.ntaps == 1 ? 0 : w.si;
+    if (!is_f32(w.q)) refuse("wgrad (thin layer): the <= 4-channel tensor must be fp32-stored");
+    if (w.ntaps == 1 && w.si != 1) refuse("wgrad (thin layer): %d taps with stride %d", w.ntaps, w.si);
+  }
+  return MMTTA_OK;
+}
+
+// ---- the main kernel of each family.  Workspace of a launch, Q = w.nsets sets back to back (set-major) in each region:
+// slabs [Q][slab_floats], bias rows [Q][db_floats], pre-reduced slabs [Q][pre_floats]; `dbws` is the second region, or
+// null when the main kernel has no bias rows to write
+static int launch_tiny_family(const mmtta_conv_desc* d, const WGeo& w, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                              const mmtta_tensor* dy, float* ws, float* dbws, hipStream_t s) {
+  WTArgs t;
+  t.x = tv(x); t.tx = nl(x_norm); t.dy = tv(dy);
+  t.part = ws; t.dbpart = dbws; t.ld = 27 * d->cin * d->cout;
+  t.B = w.tiny_blocks; t.ips = w.ips; t.BT = w.tiny_blocks * w.nsets;
+#define MMTTA_TINY_ROW(CS, T) \
+  {wgrad_tiny_kernel<CS, 1, T>, wgrad_tiny_kernel<CS, 2, T>, wgrad_tiny_kernel<CS, 3, T>, wgrad_tiny_kernel<CS, 4, T>}
+  static constexpr decltype(&wgrad_tiny_kernel<1, 1, false>) forms[2][4][4] = {      // [no transform on x][cin - 1][cout - 1]
+      {MMTTA_TINY_ROW(1, true), MMTTA_TINY_ROW(2, true), MMTTA_TINY_ROW(3, true), MMTTA_TINY_ROW(4, true)},
+      {MMTTA_TINY_ROW(1, false), MMTTA_TINY_ROW(2, false), MMTTA_TINY_ROW(3, false), MMTTA_TINY_ROW(4, false)}};
+#undef MMTTA_TINY_ROW
+  auto ix = [](int c) { return c >= 1 && c <= 3 ? c - 1 : 3; };
+  const dim3 grid(3 * ((t.BT + 7) / 8) * 8), block(256);      // (plane, workgroup) pairs, see the kernel's id decode
+  hipLaunchKernelGGL(forms[!w.form][ix(d->cin)][ix(d->cout)], grid, block, 0, s, t);
+  return launch_status("wgrad tiny");
+}
+
+static int launch_thin_family(const mmtta_conv_desc* d, const WGeo& w, const mmtta_norm_on_load* x_norm, float* ws, float* dbws,
+                              hipStream_t s) {
+  const int Q = w.nsets;
+  W2Args b;
+  b.q = (const float*)w.q->ptr; b.qsn = w.q->sn; b.qsd = w.q->sd; b.qsh = w.q->sh; b.qsw = w.q->sw;
+  b.Cs = w.q->c; b.Dq = w.q->d; b.Hq = w.q->h; b.Wq = w.q->w;
+  b.p = (const float*)w.pb->ptr; b.psn = w.pb->sn; b.psd = w.pb->sd; b.psh = w.pb->sh; b.psw = w.pb->sw;
+  b.Cb = w.pb->c; b.Dp = w.pb->d; b.Hp = w.pb->h; b.Wp = w.pb->w;
+  b.tq = w.q_is_x ? nl(x_norm) : nl(nullptr);
+  b.tp = w.q_is_x ? nl(nullptr) : nl(x_norm);
+  b.si = w.si; b.ntaps = w.ntaps;
+  b.slab = ws; b.dbpart = dbws;
+  b.tz = w.tz; b.ty = w.ty; b.tx = w.tx; b.tiles = w.tiles * Q; b.tiles_per_split = w.tps; b.CBp = w.CDp;
+  b.S = w.S; b.tiles_set = w.tiles;
+  b.qvec4 = w.gvec4; b.pvec4 = w.dvec4;
+  b.q_bf = w.g_bf; b.p_bf = w.d_bf;
+  b.bf = (d->dtype == MMTTA_BF16 && w.ntaps == 27) ? 1 : 0;
+  b.p_thin = w.p_thin ? 1 : 0;
+  if (w.route == W_THIN_TR) return launch_thin_tr(b, w.si, w.form, w.ncb, dim3(w.S * Q, w.CDp / 32 / w.ncb), s);
+  const int ext = w.ntaps == 1 ? 0 : 2;
+  const int BZ = 3 * w.si + ext + 1, BY = 3 * w.si + ext + 1, BX = 7 * w.si + ext + 1;
+  const size_t lds = ((size_t)BZ * BY * BX * 4 + 128 * 32) * sizeof(float);
+  static constexpr decltype(&wgrad_small_kernel<false, 1, false>) forms[2][3] = {      // [p_bf][1 tap | 27 taps s1 | 27 taps s2]
+      {wgrad_small_kernel<false, 1, false>, wgrad_small_kernel<false, 1, true>, wgrad_small_kernel<false, 2, true>},
+      {wgrad_small_kernel<true, 1, false>, wgrad_small_kernel<true, 1, true>, wgrad_small_kernel<true, 2, true>}};
+  hipLaunchKernelGGL(forms[w.d_bf][w.form], dim3(w.S * Q, w.CDp / 32), dim3(256), lds, s, b);
+  return launch_status("wgrad small");
+}
+
+// `ua` (with `ps`, `kind`): the call updates in the main kernel's epilogue (the plan's upd_in_epilogue)
 static int launch_main_family(const WGeo& w, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, float* ws, float* dbws,
                               hipStream_t s, const UpdArgs* ua = nullptr, const PSets* ps = nullptr, int kind = 0) {
   WArgs a;
@@ -2142,22 +2143,19 @@ static int launch_main_family(const WGeo& w, const mmtta_tensor* x, const mmtta_
   a.td = w.convt ? nl(x_norm) : nl(nullptr);
   a.N = x->n;
   a.si = w.si; a.ntaps = w.ntaps;
-  a.slab = ws;
-  a.dbpart = dbws;
+  a.slab = ws; a.dbpart = dbws;
   a.tz = w.tz; a.ty = w.ty; a.tx = w.tx; a.tiles = w.tiles * w.nsets; a.tiles_per_split = w.tps;
   a.S = w.S; a.tiles_set = w.tiles;
   a.CGp = w.CGp; a.CDp = w.CDp;
-  a.g_bf = is_bf16(w.g) ? 1 : 0;
-  a.d_bf = is_bf16(w.dn) ? 1 : 0;
+  a.g_bf = w.g_bf; a.d_bf = w.d_bf;
   a.convt = w.convt ? 1 : 0;
-  a.gvec4 = quad_aligned(w.g, quad_bytes(w.g)) ? 1 : 0;
-  a.dvec4 = quad_aligned(w.dn, quad_bytes(w.dn)) ? 1 : 0;
+  a.gvec4 = w.gvec4; a.dvec4 = w.dvec4;
   const int SQ = w.S * w.nsets;          // slabs of the launch
   if (ua != nullptr) return launch_wgrad_tr_upd_s1<4, 8>(a, *ua, *ps, kind, SQ, s);
   switch (w.route) {
     case W_TR_1X1: return launch_wgrad_tr1(a, SQ, s);
-    case W_TR_S1: return launch_wgrad_tr<4, 8, 1>(a, SQ, s, w.ncb, wgrad_raw_bits(w, x_norm));
-    case W_TR_S2: return launch_wgrad_tr<2, 4, 2>(a, SQ, s, w.ncb, wgrad_raw_bits(w, x_norm));
+    case W_TR_S1: return launch_wgrad_tr<4, 8, 1>(a, SQ, w.ncb, w.raw, s);
+    case W_TR_S2: return launch_wgrad_tr<2, 4, 2>(a, SQ, w.ncb, w.raw, s);
     case W_F32_1X1: return launch_wgrad<4, 4, 8, 1>(a, SQ, s);
     case W_F32_S1: return launch_wgrad<4, 4, 8, 7>(a, SQ, s);
     default: return launch_wgrad<2, 2, 8, 7>(a, SQ, s);
@@ -2235,7 +2233,7 @@ int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
                     const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
                     int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream, const mmtta_update_target* upd) {
   WGeo w{};
-  int st = wgeometry(d, x, dy, sets, w);
+  int st = plan_wgrad(d, x, x_norm, dy, sets, upd, w);
   if (st) return st;
   UpdArgs ua;
   if (upd != nullptr) {
@@ -2245,13 +2243,14 @@ int conv_wgrad_body(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta
     db = w.convt ? upd->b_grad : upd->b_p;
   }
   MMTTA_CHECK(dw != nullptr, MMTTA_ERR_INVALID, "wgrad: null dw");
-  const int64_t need = (w.slab_floats + w.db_floats + w.pre_floats) * w.nsets * 4;
+  const int64_t need = w.workspace_bytes();
   MMTTA_CHECK(workspace != nullptr && workspace_bytes >= need, MMTTA_ERR_WORKSPACE, "wgrad: workspace %lld bytes, need %lld",
               (long long)workspace_bytes, (long long)need);
+  MMTTA_CHECK(w.refuse == MMTTA_OK, w.refuse, "%s", w.why);
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   const PSets ps = psets(sets);
-  const bool in_epilogue = upd != nullptr && wgrad_updates_in_epilogue(w) && update_target_vec16(upd, ps, w.nsets);
+  const bool in_epilogue = upd != nullptr && w.upd_in_epilogue;
   // the main kernel writes bias rows only when they are wanted and are its to write
   float* dbws = (db != nullptr && w.bias != WB_COLSUMS) ? ws + w.slab_floats * w.nsets : nullptr;
   if (w.route == W_TINY) st = launch_tiny_family(d, w, x, x_norm, dy, ws, dbws, s);
@@ -2269,11 +2268,17 @@ MMTTA_ACT_NS_CLOSE
 #ifndef MMTTA_ACT_LEAKY_TU
 using namespace mmtta;
 
+// The run-time queries: one planning body, then a field of the plan each
+static int query_wgrad(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm, const mmtta_tensor* dy,
+                       const mmtta_param_sets* sets, WGeo& w) {
+  const int st = plan_wgrad(d, x, x_norm, dy, sets, nullptr, w);
+  return st < 0 ? st : -st;
+}
+
 extern "C" int64_t mmtta_conv_wgrad_workspace_bytes_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy,
                                                          const mmtta_param_sets* sets) {
   WGeo w{};
-  if (wgeometry(d, x, dy, sets, w)) return -1;
-  return (w.slab_floats + w.db_floats + w.pre_floats) * w.nsets * (int64_t)sizeof(float);
+  return query_wgrad(d, x, nullptr, dy, sets, w) ? -1 : w.workspace_bytes();
 }
 
 extern "C" int64_t mmtta_conv_wgrad_workspace_bytes(const mmtta_conv_desc* d, const mmtta_tensor* x,
@@ -2285,25 +2290,33 @@ extern "C" int mmtta_conv_wgrad_plan_sets(const mmtta_conv_desc* d, const mmtta_
                                           const mmtta_param_sets* sets, int32_t plan[4]) {
   MMTTA_CHECK(plan != nullptr, MMTTA_ERR_INVALID, "wgrad plan: null output");
   WGeo w{};
-  const int st = wgeometry(d, x, dy, sets, w);
-  if (st) return st;
-  plan[0] = w.nsl; plan[1] = w.pre_chunks; plan[2] = w.CGp; plan[3] = w.CDp;
-  return MMTTA_OK;
+  const int st = query_wgrad(d, x, nullptr, dy, sets, w);
+  if (st == MMTTA_OK) { plan[0] = w.nsl; plan[1] = w.pre_chunks; plan[2] = w.CGp; plan[3] = w.CDp; }
+  return st;
 }
 
 extern "C" int mmtta_conv_wgrad_kernel(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_tensor* dy) {
   WGeo w{};
-  const int st = wgeometry(d, x, dy, nullptr, w);
-  if (st) return st < 0 ? st : -st;
-  return w.route;
+  const int st = query_wgrad(d, x, nullptr, dy, nullptr, w);
+  return st ? st : w.route;
 }
 
 extern "C" int mmtta_conv_wgrad_stages_raw(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                            const mmtta_tensor* dy) {
   WGeo w{};
-  const int st = wgeometry(d, x, dy, nullptr, w);
-  if (st) return st < 0 ? st : -st;
-  return nl_leaky(x_norm) ? 0 : wgrad_raw_bits(w, x_norm);      // (a LeakyReLU call runs the instantiation without raw kernels)
+  const int st = query_wgrad(d, x, x_norm, dy, nullptr, w);
+  return st ? st : w.raw;
+}
+
+// the two launching entry points: the descriptor checks, then the body of the translation unit that builds x_norm's activation
+static int wgrad_entry(const char* what, const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
+                       const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace, int64_t workspace_bytes,
+                       const mmtta_param_sets* sets, void* stream, const mmtta_update_target* upd) {
+  int st = nl_act_check(x_norm, what);
+  if (st == MMTTA_OK) st = nl_per_item_check(x_norm, what);
+  if (st) return st;
+  return (nl_leaky(x_norm) ? leaky::conv_wgrad_body : conv_wgrad_body)(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes,
+                                                                       sets, stream, upd);
 }
 
 extern "C" int mmtta_conv_wgrad(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
@@ -2315,24 +2328,14 @@ extern "C" int mmtta_conv_wgrad(const mmtta_conv_desc* d, const mmtta_tensor* x,
 extern "C" int mmtta_conv_wgrad_sets(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                      const mmtta_tensor* dy, float* dw, float* db, int accumulate, void* workspace,
                                      int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
-  {
-    int st = nl_act_check(x_norm, "conv_wgrad (x_norm)");
-    if (st) return st;
-    st = nl_per_item_check(x_norm, "conv_wgrad (x_norm)");
-    if (st) return st;
-  }
-  if (nl_leaky(x_norm))
-    return leaky::conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
-  return conv_wgrad_body(d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
+  return wgrad_entry("conv_wgrad (x_norm)", d, x, x_norm, dy, dw, db, accumulate, workspace, workspace_bytes, sets, stream, nullptr);
 }
 
 extern "C" int mmtta_conv_wgrad_updates_in_epilogue(const mmtta_conv_desc* d, const mmtta_tensor* x, const mmtta_norm_on_load* x_norm,
                                                     const mmtta_tensor* dy, const mmtta_param_sets* sets) {
   WGeo w{};
-  const int st = wgeometry(d, x, dy, sets, w);
-  if (st) return st < 0 ? st : -st;
-  if (g_fused_update == 0 || !route_reduce27(w.route)) return 0;      // (mmtta_conv_wgrad_update_sets refuses these)
-  return (!nl_leaky(x_norm) && wgrad_updates_in_epilogue(w)) ? 1 : 0;      // (a LeakyReLU call runs the instantiation without these kernels)
+  const int st = query_wgrad(d, x, x_norm, dy, sets, w);
+  return st ? st : (w.upd_in_epilogue ? 1 : 0);      // (0 wherever mmtta_conv_wgrad_update_sets refuses or takes two launches)
 }
 
 extern "C" int mmtta_fused_update_enabled(void) { return g_fused_update != 0 ? 1 : 0; }
@@ -2342,14 +2345,6 @@ extern "C" int mmtta_conv_wgrad_update_sets(const mmtta_conv_desc* d, const mmtt
                                             int64_t workspace_bytes, const mmtta_param_sets* sets, void* stream) {
   MMTTA_CHECK(g_fused_update != 0, MMTTA_ERR_UNSUPPORTED, "wgrad update: switched off (MMTTA_FUSED_UPDATE=0)");
   MMTTA_CHECK(target != nullptr, MMTTA_ERR_INVALID, "wgrad update: null target");
-  {
-    int st = nl_act_check(x_norm, "conv_wgrad_update (x_norm)");
-    if (st) return st;
-    st = nl_per_item_check(x_norm, "conv_wgrad_update (x_norm)");
-    if (st) return st;
-  }
-  if (nl_leaky(x_norm))
-    return leaky::conv_wgrad_body(d, x, x_norm, dy, nullptr, nullptr, 0, workspace, workspace_bytes, sets, stream, target);
-  return conv_wgrad_body(d, x, x_norm, dy, nullptr, nullptr, 0, workspace, workspace_bytes, sets, stream, target);
+  return wgrad_entry("conv_wgrad_update (x_norm)", d, x, x_norm, dy, nullptr, nullptr, 0, workspace, workspace_bytes, sets, stream, target);
 }
 #endif  // MMTTA_ACT_LEAKY_TU

@@ -589,27 +589,33 @@ class ConvOp:
         ResidualUnit) summed in the epilogue instead of by a separate pass over dx."""
         self._run(self.d_dgrad, self.packed_dgrad, dy, None, None, dx, accumulate, None, add, None)
 
-    def wgrad(self, x: torch.Tensor, x_nl: Optional[NL], dy: torch.Tensor, dw: torch.Tensor,
-              db: Optional[torch.Tensor], accumulate: bool = False) -> None:
+    def _wgrad_args(self, x: torch.Tensor, dy: torch.Tensor, workspace: bool = True):
+        """What every weight-gradient call shares: the library, the references (desc, x, dy, sets-or-None; each keeps its
+        structure alive), the sets, and - unless the call launches nothing - the workspace and its size in bytes."""
         lib = _lib.load()
-        tx, tdy = desc_cl(x), desc_cl(dy)
         sets = self._sets(self.d_fwd)
-        sref = C.byref(sets) if sets is not None else None
-        need = lib.mmtta_conv_wgrad_workspace_bytes_sets(C.byref(self.d_fwd), C.byref(tx), C.byref(tdy), sref)
+        refs = (C.byref(self.d_fwd), C.byref(desc_cl(x)), C.byref(desc_cl(dy)), C.byref(sets) if sets is not None else None)
+        if not workspace:
+            return lib, refs, sets, None, 0
+        need = int(lib.mmtta_conv_wgrad_workspace_bytes_sets(*refs))
         if need < 0:
             check(-1, "conv_wgrad_workspace_bytes")
-        ws = Workspace.get(int(need), x.device)
+        return lib, refs, sets, Workspace.get(need, x.device), need
+
+    def wgrad(self, x: torch.Tensor, x_nl: Optional[NL], dy: torch.Tensor, dw: torch.Tensor,
+              db: Optional[torch.Tensor], accumulate: bool = False) -> None:
+        lib, (d, tx, tdy, sref), sets, ws, need = self._wgrad_args(x, dy)
         nls, nlr = _nl_ref(x_nl)
         def launch():
-            check(lib.mmtta_conv_wgrad_sets(C.byref(self.d_fwd), C.byref(tx), nlr, C.byref(tdy), ptr(dw), ptr(db),
-                                            1 if accumulate else 0, ptr(ws), int(need), sref, stream_ptr()), "conv_wgrad")
+            check(lib.mmtta_conv_wgrad_sets(d, tx, nlr, tdy, ptr(dw), ptr(db), 1 if accumulate else 0, ptr(ws), need, sref,
+                                            stream_ptr()), "conv_wgrad")
 
         launch()
         if PROFILER is not None:
             e0 = PROFILER.begin()
             for _ in range(PROFILER.reps):
                 launch()
-            kid = lib.mmtta_conv_wgrad_kernel(C.byref(self.d_fwd), C.byref(tx), C.byref(tdy))
+            kid = lib.mmtta_conv_wgrad_kernel(d, tx, tdy)
             nsets = x.shape[0] // int(sets.items_per_set) if sets is not None else 1
             PROFILER.end(WGRAD_KERNELS[kid], PROFILER.reps, self.flops(x, dy) * PROFILER.reps, e0, self._detail(-1, x),
                          (self.io_bytes(x, dy, dw) + (nsets - 1) * dw.numel() * 4.0) * PROFILER.reps)
@@ -618,12 +624,9 @@ class ConvOp:
     def wgrad_plan(self, x: torch.Tensor, dy: torch.Tensor) -> dict:
         """The weight gradient's reduction plan for this problem (mmtta_conv_wgrad_plan_sets): partial slabs per set, chunks
         of the pre-reduce stage (0: none) and the padded channel counts of a slab.  Launches nothing."""
-        lib = _lib.load()
-        tx, tdy = desc_cl(x), desc_cl(dy)
-        sets = self._sets(self.d_fwd)
+        lib, refs, _, _, _ = self._wgrad_args(x, dy, workspace=False)
         out = (C.c_int32 * 4)()
-        check(lib.mmtta_conv_wgrad_plan_sets(C.byref(self.d_fwd), C.byref(tx), C.byref(tdy),
-                                             C.byref(sets) if sets is not None else None, out), "conv_wgrad_plan")
+        check(lib.mmtta_conv_wgrad_plan_sets(*refs, out), "conv_wgrad_plan")
         return {"nsl": int(out[0]), "pre_chunks": int(out[1]), "CGp": int(out[2]), "CDp": int(out[3])}
 
     def plain_bf16_images(self) -> bool:
@@ -653,17 +656,10 @@ class ConvOp:
     def wgrad_update(self, x: torch.Tensor, x_nl: Optional[NL], dy: torch.Tensor, target: _lib.UpdateTarget) -> None:
         """Weight gradient + optimizer step + repack of both images (mmtta_conv_wgrad_update_sets): the layer's parameters,
         moments and images of every set in the batch are updated in place; the step counter is read, not advanced."""
-        lib = _lib.load()
-        tx, tdy = desc_cl(x), desc_cl(dy)
-        sets = self._sets(self.d_fwd)
-        sref = C.byref(sets) if sets is not None else None
-        need = lib.mmtta_conv_wgrad_workspace_bytes_sets(C.byref(self.d_fwd), C.byref(tx), C.byref(tdy), sref)
-        if need < 0:
-            check(-1, "conv_wgrad_workspace_bytes")
-        ws = Workspace.get(int(need), x.device)
+        lib, (d, tx, tdy, sref), _, ws, need = self._wgrad_args(x, dy)
         nls, nlr = _nl_ref(x_nl)
-        check(lib.mmtta_conv_wgrad_update_sets(C.byref(self.d_fwd), C.byref(tx), nlr, C.byref(tdy), C.byref(target), ptr(ws),
-                                               int(need), sref, stream_ptr()), "conv_wgrad_update")
+        check(lib.mmtta_conv_wgrad_update_sets(d, tx, nlr, tdy, C.byref(target), ptr(ws), need, sref, stream_ptr()),
+              "conv_wgrad_update")
 
 
 def fused_update_enabled() -> bool:

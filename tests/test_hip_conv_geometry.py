@@ -33,6 +33,8 @@ MMTTA_OPT_IGEMM_PIPELINE (6) is crossed with the bf16 stride-1 3x3x3 cases under
 
 Observed worst err / bound on an MI355X (recorded values, not limits): see DESIGN.md, "Parity rules".
 """
+import ctypes as C
+
 import pytest
 import torch
 
@@ -313,6 +315,35 @@ def test_epilogue_store_width_at_unsplit(name, dtype):
             _check_all(c, dtype, "unsplit", res[mode])
     for key in res[0]:
         assert torch.equal(res[0][key][0], res[1][key][0]), f"{name} {dtype}: {key} differs between the store widths"
+
+
+# wgrad_f32_kernel<TZ, TY, TX, NTW, GBF, DBF> reads either operand fp32- or bf16-stored; the cases above launch it next to an
+# fp32-stored dy only.  The storage pairs with a bf16-stored dy, per tile: fp32 precision on bf16-representable
+# operands, so what the kernel unpacks is what the float64 reference multiplies.
+F32_WGRAD_STORAGE = [(cg.case("f32_k1_40_32", 40, 32, 1, 1, False, (2, 6, 10, 12)), False), (cg.case("f32_k1_32_64", 32, 64, 1, 1, False, (2, 6, 10, 12)), True),
+                     (cg.case("f32_s1_32_40", 32, 40, 3, 1, False, (2, 6, 10, 12)), False), (cg.case("f32_s1_40_32", 40, 32, 3, 1, False, (2, 6, 10, 12)), True),
+                     (cg.case("f32_s2_32_64", 32, 64, 3, 2, False, (2, 7, 11, 13)), True)]
+
+
+@GPU
+@pytest.mark.parametrize("c,x_bf16", F32_WGRAD_STORAGE, ids=[f"{c.name}-x_{'bf16' if b else 'fp32'}" for c, b in F32_WGRAD_STORAGE])
+def test_fp32_operand_wgrad_reads_a_bf16_stored_gradient(c, x_bf16):
+    """Weight and bias gradient, plain and accumulating, of the fp32-operand kernel with dy bf16-stored (and x either way),
+    against the float64 reference: the kernel id is asserted before the launch."""
+    from multimodal_tta_amd import _lib, ops
+    o, r = cg.operands(c, "bf16"), cg.reference(c, "bf16")
+    op = _make_op(c, "fp32")
+    x_cl, gy_cl = (cl_bf16 if x_bf16 else cl)(o.x), cl_bf16(o.gy)
+    kid = int(_lib.load().mmtta_conv_wgrad_kernel(C.byref(op.d_fwd), C.byref(ops.desc_cl(x_cl)), C.byref(ops.desc_cl(gy_cl))))
+    assert kid == (2 if c.k == 1 else 0 if c.stride == 1 else 1), f"{c.name}: weight-gradient kernel {kid}"
+    dw, db = torch.full(cg.weight_shape(c), float("nan"), device="cuda"), torch.full((c.cout,), float("nan"), device="cuda")
+    op.wgrad(x_cl, None, gy_cl, dw, db)
+    dwa, dba = o.dw0.cuda(), o.db0.cuda()
+    op.wgrad(x_cl, None, gy_cl, dwa, dba, accumulate=True)
+    torch.cuda.synchronize()
+    for what, got, ref in (("weight gradient", dw, r.dw), ("bias gradient", db, r.db),
+                           ("weight gradient accumulate", dwa, o.dw0.double() + r.dw), ("bias gradient accumulate", dba, o.db0.double() + r.db)):
+        cg.exact_close(f"{c.name} x {'bf16' if x_bf16 else 'fp32'}-stored, dy bf16-stored: {what}", "fp32", got.cpu(), ref)
 
 
 @GPU

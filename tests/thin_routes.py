@@ -177,6 +177,17 @@ LAYERS = [
     # 45 tiles of 4 x 4 x 8 for wgrad_small_kernel; 288 tiles of 4 x 8 x 8, eight to a slab, for wgrad_thin_tr_kernel
     layer("wgrad_small_slabs", 4, 32, 3, 2, False, (1, 17, 33, 33), "fp32", F, F, fwd=(), wgrad=3),
     layer("wgrad_thin_tr_slabs", 4, 2, 3, 1, False, (1, 12, 64, 90), "bf16", F, F, fwd=(), wgrad=10, opts={OPT_THIN_MFMA: 1}),
+    # ---- weight gradients only: the instantiations of the launch tables no layer above reaches.
+    # wgrad_thin_tr_kernel with a bf16-stored thin tensor (QBF): stride 1 next to an fp32-stored P of one and of two column
+    # blocks, stride 1 next to a bf16-stored P of two, stride 2 next to an fp32-stored P of two
+    layer("wgrad_thin_tr_qbf_2_32_s1", 2, 32, 3, 1, False, (2, 6, 10, 12), "bf16", B, F, fwd=(), wgrad=10),
+    layer("wgrad_thin_tr_qbf_3_64_s1", 3, 64, 3, 1, False, (2, 6, 10, 12), "bf16", B, F, fwd=(), wgrad=10),
+    layer("wgrad_thin_tr_qbf_4_64_s1_bf", 4, 64, 3, 1, False, (2, 6, 10, 12), "bf16", B, B, fwd=(), wgrad=10),
+    layer("wgrad_thin_tr_qbf_3_64_s2", 3, 64, 3, 2, False, (2, 7, 11, 13), "bf16", B, F, fwd=(), wgrad=10),
+] + [
+    # wgrad_tiny_kernel<CS, CB, HAS_T>: the (cin, cout) pairs not above; a layer runs without and with a norm-on-load of x
+    layer(f"wgrad_tiny_{ci}_{co}", ci, co, 3, 1, False, (2, 5, 7, 12), "fp32", F, F, fwd=(), wgrad=6)
+    for ci, co in ((1, 2), (1, 3), (2, 1), (2, 2), (2, 3), (2, 4), (3, 1), (3, 2), (3, 4), (4, 1), (4, 3), (4, 4))
 ]
 LAYERS_BY_NAME = {l.case.name: l for l in LAYERS}
 assert len(LAYERS_BY_NAME) == len(LAYERS)
