@@ -30,7 +30,7 @@ from typing import Any, Sequence, Tuple
 
 import numpy as np
 
-from .config import get_config
+from .config import expect, get_config, is_integer, is_number, seed_value
 from .intensity import MAX_VIEWS, philox4x32_10
 
 MAX_ROTATE, MAX_SCALE, MAX_TRANSLATE = 45.0, 0.25, 16.0
@@ -58,7 +58,7 @@ def _triple(value: Any, key: str, limit: float, unit: str) -> Tuple[float, float
         raise ValueError(f"{key} = {value!r}: expected three magnitudes (D, H, W axis), each 0 .. {limit:g} {unit}")
     out = []
     for v in value:
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)) or not (0.0 <= float(v) <= limit):
+        if not (is_number(v) and 0.0 <= v <= limit):
             raise ValueError(f"{key} = {list(value)!r}: {v!r} is no magnitude with 0 <= value <= {limit:g} {unit}")
         out.append(float(v))
     return out[0], out[1], out[2]
@@ -74,16 +74,14 @@ def parse_affine(value: Any, coded_views: int, key: str = "method.cotta.affine")
         if k not in KEYS:
             raise ValueError(f"{key}.{k}: unknown key (expected one of {', '.join(KEYS)})")
     views = get_config(value, "views", 0)
-    if isinstance(views, bool) or not isinstance(views, int) or not (0 <= views < MAX_VIEWS):
-        raise ValueError(f"{key}.views = {views!r}: expected a number of affine views with 0 <= views <= {MAX_VIEWS - 1}")
+    expect(is_integer(views) and 0 <= views < MAX_VIEWS, f"{key}.views", views,
+           f"a number of affine views with 0 <= views <= {MAX_VIEWS - 1}")
     rotate = _triple(get_config(value, "rotate", [0.0, 0.0, 0.0]), f"{key}.rotate", MAX_ROTATE, "degrees")
     translate = _triple(get_config(value, "translate", [0.0, 0.0, 0.0]), f"{key}.translate", MAX_TRANSLATE, "voxels")
-    scale, seed = get_config(value, "scale", 0.0), get_config(value, "seed", 0)
-    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(float(scale)) or not (0.0 <= float(scale) <= MAX_SCALE):
-        raise ValueError(f"{key}.scale = {scale!r}: expected a magnitude with 0 <= scale <= {MAX_SCALE:g}")
-    if isinstance(seed, bool) or not isinstance(seed, int) or not (0 <= seed < 1 << 64):
-        raise ValueError(f"{key}.seed = {seed!r}: expected an integer with 0 <= seed < 2^64")
-    spec = AffineSpec(views=int(views), rotate=rotate, scale=float(scale), translate=translate, seed=int(seed))
+    scale = get_config(value, "scale", 0.0)
+    expect(is_number(scale) and 0.0 <= scale <= MAX_SCALE, f"{key}.scale", scale, f"a magnitude with 0 <= scale <= {MAX_SCALE:g}")
+    seed = seed_value(get_config(value, "seed", 0), f"{key}.seed")
+    spec = AffineSpec(views=int(views), rotate=rotate, scale=float(scale), translate=translate, seed=seed)
     if spec.views > 0 and not (any(rotate) or any(translate) or spec.scale > 0.0):
         raise ValueError(f"{key}.views = {views} with rotate, scale and translate all 0: the affine views would be copies of "
                          "the volume")

@@ -34,8 +34,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
-from .innorm import InputMapTTA, _number
+from .config import expect, get_config, is_integer, is_number, method_block
+from .innorm import InputMapTTA
 from .registry import register_plugin
 
 MAX_ORDER, MAX_EXTENT = 3, 512
@@ -48,8 +48,7 @@ DEFAULTS = {"lr": 1e-2, "order": 2, "anchor": "min", "l2": 0.0, "bound": {"gain"
 def field_terms(order: int) -> List[Tuple[int, int, int]]:
     """The exponents (a, b, c) of phi = P_a(t_z) P_b(t_y) P_c(t_x) with a + b + c <= order, by (a + b + c, a, b, c) ascending:
     (order + 1)(order + 2)(order + 3) / 6 terms, term 0 the constant."""
-    if isinstance(order, bool) or not isinstance(order, int) or not 0 <= order <= MAX_ORDER:
-        raise ValueError(f"order = {order!r}: expected an int in 0 .. {MAX_ORDER}")
+    expect(is_integer(order) and 0 <= order <= MAX_ORDER, "order", order, f"an int in 0 .. {MAX_ORDER}")
     terms = [(a, b, c) for a in range(order + 1) for b in range(order + 1 - a) for c in range(order + 1 - a - b)]
     return sorted(terms, key=lambda t: (sum(t), t))
 
@@ -102,19 +101,14 @@ def parse_config(block: Any) -> Dict[str, Any]:
             raise ValueError(f"method.biasfield.bound.{key} : unknown key (known: {', '.join(DEFAULTS['bound'])})")
     lr, order = get_config(block, "lr", DEFAULTS["lr"]), get_config(block, "order", DEFAULTS["order"])
     anchor, l2 = get_config(block, "anchor", DEFAULTS["anchor"]), get_config(block, "l2", DEFAULTS["l2"])
-    if not _number(lr) or lr < 0.0:
-        raise ValueError(f"method.biasfield.lr = {lr!r}: expected a finite number >= 0 (0: entmin_tta)")
-    if isinstance(order, bool) or not isinstance(order, int) or not 0 <= order <= MAX_ORDER:
-        raise ValueError(f"method.biasfield.order = {order!r}: expected an int in 0 .. {MAX_ORDER}")
-    if not isinstance(anchor, str) or anchor not in ANCHORS:
-        raise ValueError(f"method.biasfield.anchor = {anchor!r}: expected one of {' | '.join(ANCHORS)}")
-    if not _number(l2) or l2 < 0.0:
-        raise ValueError(f"method.biasfield.l2 = {l2!r}: expected a finite number >= 0")
+    expect(is_number(lr) and lr >= 0.0, "method.biasfield.lr", lr, "a finite number >= 0 (0: entmin_tta)")
+    expect(is_integer(order) and 0 <= order <= MAX_ORDER, "method.biasfield.order", order, f"an int in 0 .. {MAX_ORDER}")
+    expect(isinstance(anchor, str) and anchor in ANCHORS, "method.biasfield.anchor", anchor, f"one of {' | '.join(ANCHORS)}")
+    expect(is_number(l2) and l2 >= 0.0, "method.biasfield.l2", l2, "a finite number >= 0")
     out = {"lr": float(lr), "order": order, "anchor": anchor, "l2": float(l2)}
     for key, top in (("gain", MAX_BOUND_GAIN), ("field", MAX_BOUND_FIELD)):
         val = get_config(bound, key, DEFAULTS["bound"][key])
-        if not _number(val) or not (0.0 < val <= top):
-            raise ValueError(f"method.biasfield.bound.{key} = {val!r}: expected a finite number in (0, {top:g}]")
+        expect(is_number(val) and 0.0 < val <= top, f"method.biasfield.bound.{key}", val, f"a finite number in (0, {top:g}]")
         out[f"bound_{key}"] = float(val)
     return out
 
@@ -128,12 +122,11 @@ class BiasFieldTTA(InputMapTTA):
     every other one).  theta's optimizer is Adam with torch's default betas and eps and no decay, whatever
     ``training.optimizer`` is.  Everything else is ``entmin_tta``'s, with one limit: every volume has its own theta, so a call
     takes at most ``method.group`` volumes.  Nobody has measured a Dice with the defaults."""
-    plugin, prefix, row = "biasfield_tta", "biasfield", ops.BIAS_ROW
+    plugin, prefix, row, record = "biasfield_tta", "biasfield", ops.BIAS_ROW, "field_grad"
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        c = parse_config(get_config(m, "biasfield", None))          # (a disabled path still validates its block)
+        c = parse_config(get_config(method_block(config), "biasfield", None))          # (a disabled path still validates its block)
         self.lr, self.order, self.anchor, self.l2 = c["lr"], c["order"], c["anchor"], c["l2"]
         self.bounds = (c["bound_gain"], c["bound_field"])
         self.terms = field_terms(self.order)
@@ -186,12 +179,11 @@ class BiasFieldTTA(InputMapTTA):
         included), ``field_coeff`` [B, C, K] (theta at the end; ``evaluate_field`` turns it into exp(F)) and ``field_terms``, the
         (a, b, c) of the K terms."""
         B, C, K = int(x.shape[0]), int(x.shape[1]), len(self.terms)
-        out = self._adapt(x, steps)
+        out = super().adapt_volume(x, steps)
         out["field_terms"] = list(self.terms)
+        out["field_grad"] = out["field_grad"][..., :K]
         if self.lr == 0.0:
-            out["field_grad"] = torch.zeros((self._steps_now, B, C, K), dtype=torch.float32, device=x.device)
             out["field_coeff"] = torch.zeros((B, C, K), dtype=torch.float32, device=x.device)
             return out
-        out["field_grad"] = self._hist[:self._steps_now, :B, :, :K].clone()
         out["field_coeff"] = self._tables()["theta"].view(-1, C, self.row)[:B, :, :K].clone()
         return out

@@ -27,22 +27,17 @@ untouched and is ``entmin_tta`` bit for bit.
 """
 from __future__ import annotations
 
-import math
 from typing import Any, Optional, Sequence
 
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_integer, is_number, method_block
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA
 
 MAX_WEIGHT = 16.0
 MIN_EPS, MAX_EPS = 1e-6, 0.1
-
-
-def _number(value: Any) -> bool:
-    return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value)
 
 
 @register_plugin("bnm_tta")
@@ -54,24 +49,20 @@ class NuclearNormTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "bnm", {}) or {}
+        s = method_block(config, "bnm")
         wt, ew = get_config(s, "weight", 1.0), get_config(s, "entropy_weight", 1.0)
         bk, ep = get_config(s, "block", [0, 0, 0]), get_config(s, "eps", 1e-4)
-        if not _number(wt) or not (0.0 <= wt <= MAX_WEIGHT):
-            raise ValueError(f"method.bnm.weight = {wt!r}: expected a finite number in [0, {MAX_WEIGHT:g}] (0: entmin_tta)")
-        if not _number(ew) or not (0.0 <= ew <= MAX_WEIGHT):
-            raise ValueError(f"method.bnm.entropy_weight = {ew!r}: expected a finite number in [0, {MAX_WEIGHT:g}] "
-                             "(0: the nuclear norm alone)")
+        expect(is_number(wt) and 0.0 <= wt <= MAX_WEIGHT, "method.bnm.weight", wt,
+               f"a finite number in [0, {MAX_WEIGHT:g}] (0: entmin_tta)")
+        expect(is_number(ew) and 0.0 <= ew <= MAX_WEIGHT, "method.bnm.entropy_weight", ew,
+               f"a finite number in [0, {MAX_WEIGHT:g}] (0: the nuclear norm alone)")
         if wt == 0.0 and ew != 1.0:
             raise ValueError(f"method.bnm.entropy_weight = {ew!r}: with method.bnm.weight = 0 the step is entmin_tta's, "
                              "whose entropy weight is 1")
         bk = list(bk) if not isinstance(bk, (str, bytes)) and hasattr(bk, "__iter__") else bk
-        if not isinstance(bk, list) or len(bk) != 3 or not all(isinstance(b, int) and not isinstance(b, bool) and b >= 0
-                                                                for b in bk):
-            raise ValueError(f"method.bnm.block = {bk!r}: expected three integers >= 0 (0: the whole extent)")
-        if not _number(ep) or not (MIN_EPS <= ep <= MAX_EPS):
-            raise ValueError(f"method.bnm.eps = {ep!r}: expected a finite number in [{MIN_EPS:g}, {MAX_EPS:g}]")
+        expect(isinstance(bk, list) and len(bk) == 3 and all(is_integer(b) and b >= 0 for b in bk), "method.bnm.block", bk,
+               "three integers >= 0 (0: the whole extent)")
+        expect(is_number(ep) and MIN_EPS <= ep <= MAX_EPS, "method.bnm.eps", ep, f"a finite number in [{MIN_EPS:g}, {MAX_EPS:g}]")
         self.weight, self.entropy_weight, self.block, self.eps = float(wt), float(ew), [int(b) for b in bk], float(ep)
         # one slot per replica each.  weight 0 is the parent's step: its loss is the entropy, and nothing writes `nuclear`
         if self.weight > 0.0:
@@ -87,10 +78,8 @@ class NuclearNormTTA(EntropyMinimizationTTA):
         if self.weight == 0.0:
             super()._update(x, present)
             return
-        rt, ar = self.rt, self.rt.arena
-        n = int(x.shape[0])
-        if n > rt.group:          # (every volume is its own objective and has its own record slots)
-            raise ValueError(f"method.group = {rt.group}: bnm_tta adapts at most {rt.group} volumes per call, got {n}")
+        rt = self.rt
+        self._check_volumes(int(x.shape[0]), "bnm_tta adapts ")          # (every volume is its own objective, with own record slots)
         rt.pack_all(fused_current=True)
         loss = rt.pool.flat("bnm_loss", rt.group)
         entropy = rt.pool.flat("bnm_entropy", rt.group)
@@ -100,11 +89,4 @@ class NuclearNormTTA(EntropyMinimizationTTA):
         scratch = rt.pool.flat("bnm_scratch", ops.nuclear_scratch(logits, self.block, self.softmax), dtype=torch.float64)
         ops.nuclear_entropy_items(logits, dlogits, scratch, loss, entropy, nuclear, block=self.block, weight=self.weight,
                                   entropy_weight=self.entropy_weight, eps=self.eps, softmax=self.softmax)
-        if ar.n_train > 0:
-            fused = bool(rt.fused_layers)
-            rt.fused_active = fused         # only this backward updates the fused layers in place
-            try:
-                rt.run_backward(dlogits)
-            finally:
-                rt.fused_active = False
-            self.optimizer_step(int(logits.shape[0]), fused=fused)
+        self._backward_and_step(dlogits, int(logits.shape[0]), fused=True)

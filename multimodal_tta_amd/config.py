@@ -16,6 +16,7 @@ What is reproduced, with the reference file each rule is needed for:
 """
 from __future__ import annotations
 
+import math
 import os
 import re
 import time
@@ -23,7 +24,8 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import yaml
 
-__all__ = ["Cfg", "compose", "get_config", "require_config", "to_container", "as_cfg"]
+__all__ = ["Cfg", "compose", "get_config", "require_config", "to_container", "as_cfg", "method_block", "is_number", "is_integer",
+           "expect", "seed_value"]
 
 
 # ----------------------------------------------------------------------------- container
@@ -133,6 +135,34 @@ def require_config(cfg: Any, path: str, type_: Optional[type] = None) -> Any:
     if type_ is not None and not isinstance(value, type_):
         raise TypeError(f"Config '{path}' must be {type_.__name__}, got {type(value).__name__}")
     return value
+
+
+# ----------------------------------------------------------------------------- what the plugins' constructors share
+def method_block(config: Any, name: Optional[str] = None) -> Any:
+    """The ``method`` mapping of the root config, or its ``method.<name>`` mapping; {} where it is absent or empty."""
+    m = get_config(as_cfg(config), "method", {}) or {}
+    return m if name is None else get_config(m, name, {}) or {}
+
+
+def is_number(value: Any) -> bool:
+    """A finite int or float; a bool is no number."""
+    return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value)
+
+
+def is_integer(value: Any) -> bool:
+    return isinstance(value, int) and not isinstance(value, bool)
+
+
+def expect(ok: bool, key: str, value: Any, expected: str) -> None:
+    """``ValueError`` "<key> = <value>: expected <expected>" unless ``ok``: the caller states the test and its own words."""
+    if not ok:
+        raise ValueError(f"{key} = {value!r}: expected {expected}")
+
+
+def seed_value(value: Any, key: str) -> int:
+    """A Philox seed: the two key words of a draw."""
+    expect(is_integer(value) and 0 <= value < 1 << 64, key, value, "an integer with 0 <= seed < 2^64")
+    return int(value)
 
 
 # ----------------------------------------------------------------------------- YAML loading

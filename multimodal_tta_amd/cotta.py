@@ -52,7 +52,7 @@ import torch
 
 from . import ops
 from .affine import check_extents, parse_affine
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_number, method_block, seed_value
 from .intensity import parse_intensity
 from .memo import check_square, parse_mirror_axes, parse_rot90
 from .registry import register_plugin
@@ -69,8 +69,7 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, self.block, {}) or {}
+        s = method_block(config, self.block)
         key = f"method.{self.block}"
         self.mirror_axes = parse_mirror_axes(get_config(s, "mirror_axes", ["h", "w"]), f"{key}.mirror_axes")
         self.rot90 = parse_rot90(get_config(s, "rot90", None), f"{key}.rot90")
@@ -83,27 +82,18 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         if self.affine.active:
             self.view_axes = list(self.view_axes) + [0] * self.affine.views
         self.views = len(self.view_axes)
-        alpha, p, seed = get_config(s, "alpha", 0.999), get_config(s, "restore_p", 0.01), get_config(s, "seed", 0)
-        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not (0.0 <= float(alpha) <= 1.0):
-            raise ValueError(f"{key}.alpha = {alpha!r}: expected a teacher momentum with 0 <= alpha <= 1")
-        if isinstance(p, bool) or not isinstance(p, (int, float)) or not (0.0 <= float(p) < 1.0):
-            raise ValueError(f"{key}.restore_p = {p!r}: expected a probability with 0 <= p < 1")
-        if isinstance(seed, bool) or not isinstance(seed, int) or not (0 <= seed < 1 << 64):
-            raise ValueError(f"{key}.seed = {seed!r}: expected an integer with 0 <= seed < 2^64")
-        self.alpha, self.restore_p, self.seed = float(alpha), float(p), int(seed)
-        if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
-            raise NotImplementedError(f"method.moddrop.enabled: true is not supported by {self.block}_tta (one modality mask per step "
-                                      "for the teacher's views and the student is not defined yet)")
+        alpha, p = get_config(s, "alpha", 0.999), get_config(s, "restore_p", 0.01)
+        expect(is_number(alpha) and 0.0 <= alpha <= 1.0, f"{key}.alpha", alpha, "a teacher momentum with 0 <= alpha <= 1")
+        expect(is_number(p) and 0.0 <= p < 1.0, f"{key}.restore_p", p, "a probability with 0 <= p < 1")
+        self.alpha, self.restore_p, self.seed = float(alpha), float(p), seed_value(get_config(s, "seed", 0), f"{key}.seed")
+        self._refuse_moddrop(f"true is not supported by {self.block}_tta (one modality mask per step for the teacher's views "
+                             "and the student is not defined yet)")
         self.teacher: Optional[torch.Tensor] = None          # [replicas, n_train] fp32
 
     def setup(self, model, device) -> "MeanTeacherTTA":
         super().setup(model, device)          # (tells the model its views: EntropyMinimizationTTA.setup)
         rt, ar = self.rt, self.rt.arena
-        if rt.buffers:
-            raise NotImplementedError(
-                f"{self.block}_tta: model.norm = {get_config(get_config(self.cfg, 'model', {}) or {}, 'norm', 'BATCH')!r} keeps running "
-                "statistics, which the teacher's train-mode forward would move (running_mean, running_var, "
-                "num_batches_tracked belong to the student); use a model.norm without them (INSTANCE, GROUP)")
+        self._refuse_running_stats(f"{self.block}_tta", "the teacher's train-mode forward", owner="the student")
         if self.affine.active and hasattr(rt, "stage_family"):
             raise NotImplementedError(f"method.{self.block}.affine.views = {self.affine.views}: affine views are not built for the "
                                       "deep-fusion network (its family batch is staged from the views)")
@@ -154,11 +144,8 @@ class MeanTeacherTTA(EntropyMinimizationTTA):
         loss = rt.pool.flat("ent_loss", rt.group)
         ops.consistency_loss_items(logits, target, dlogits, partial, loss, softmax=self.softmax)
         restored = rt.pool.flat("cotta_restored", ar.replicas, dtype=torch.int64, zero=True)
-        if nt > 0:
-            # 4. - 6. backward, the optimizer (it advances the step counter), teacher EMA + restore
-            rt.run_backward(dlogits)
-            self.optimizer_step(B)
-            self._after_step(sets, restored)
+        # 4. - 6. backward, the optimizer (it advances the step counter), teacher EMA + restore
+        self._backward_and_step(dlogits, B, after=lambda: self._after_step(sets, restored))
 
     def _after_step(self, sets: int, restored: torch.Tensor) -> None:
         """The pass after the optimizer step over the first ``sets`` replicas: teacher EMA + stochastic restore."""

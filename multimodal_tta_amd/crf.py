@@ -27,13 +27,12 @@ bit for bit.
 """
 from __future__ import annotations
 
-import math
 from typing import Any, Optional, Sequence
 
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_integer, is_number, method_block
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA, modality_mask
 
@@ -41,10 +40,6 @@ MAX_WEIGHT = 16.0
 MIN_SIGMA = 1e-18          # below about 4.6e-20 the factor 1 / (2 sigma^2) overflows fp32 (mmtta_crf_entropy_items refuses it)
 CONNECTIVITIES = (6, 18, 26)
 FORMS = ops.CRF_FORMS
-
-
-def _number(value: Any) -> bool:
-    return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value)
 
 
 @register_plugin("crf_tta")
@@ -58,18 +53,15 @@ class CrfRegularizedTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "crf", {}) or {}
+        s = method_block(config, "crf")
         wt, sg = get_config(s, "weight", 1.0), get_config(s, "sigma", 1.0)
         cn, fm = get_config(s, "connectivity", 26), get_config(s, "form", "potts")
-        if not _number(wt) or not (0.0 <= wt <= MAX_WEIGHT):
-            raise ValueError(f"method.crf.weight = {wt!r}: expected a finite number in [0, {MAX_WEIGHT:g}] (0: entmin_tta)")
-        if not _number(sg) or sg < 0.0 or 0.0 < sg < MIN_SIGMA:
-            raise ValueError(f"method.crf.sigma = {sg!r}: expected 0 (no affinity) or a finite number >= {MIN_SIGMA:g}")
-        if isinstance(cn, bool) or not isinstance(cn, int) or cn not in CONNECTIVITIES:
-            raise ValueError(f"method.crf.connectivity = {cn!r}: expected 6, 18 or 26")
-        if not isinstance(fm, str) or fm not in FORMS:
-            raise ValueError(f"method.crf.form = {fm!r}: expected one of {', '.join(FORMS)}")
+        expect(is_number(wt) and 0.0 <= wt <= MAX_WEIGHT, "method.crf.weight", wt,
+               f"a finite number in [0, {MAX_WEIGHT:g}] (0: entmin_tta)")
+        expect(is_number(sg) and (sg == 0.0 or sg >= MIN_SIGMA), "method.crf.sigma", sg,
+               f"0 (no affinity) or a finite number >= {MIN_SIGMA:g}")
+        expect(is_integer(cn) and cn in CONNECTIVITIES, "method.crf.connectivity", cn, "6, 18 or 26")
+        expect(isinstance(fm, str) and fm in FORMS, "method.crf.form", fm, f"one of {', '.join(FORMS)}")
         self.weight, self.sigma, self.connectivity, self.form = float(wt), float(sg), int(cn), str(fm)
         # one slot per replica each.  weight 0 is the parent's step: its loss is the entropy, and nothing writes `pairwise`
         if self.weight > 0.0:
@@ -102,10 +94,8 @@ class CrfRegularizedTTA(EntropyMinimizationTTA):
             return
         if x_aff is None:
             x_aff = x
-        rt, ar = self.rt, self.rt.arena
-        n = int(x.shape[0])
-        if n > rt.group:          # (every volume is its own objective and has its own record slots)
-            raise ValueError(f"method.group = {rt.group}: crf_tta adapts at most {rt.group} volumes per call, got {n}")
+        rt = self.rt
+        self._check_volumes(int(x.shape[0]), "crf_tta adapts ")          # (every volume is its own objective, with own record slots)
         rt.pack_all(fused_current=True)
         loss = rt.pool.flat("crf_loss", rt.group)
         entropy = rt.pool.flat("crf_entropy", rt.group)
@@ -119,11 +109,4 @@ class CrfRegularizedTTA(EntropyMinimizationTTA):
         ops.crf_entropy_items(logits, x_aff if self.sigma > 0.0 else None, dlogits, partial, loss, entropy, pairwise,
                               connectivity=self.connectivity, weight=self.weight, sigma=self.sigma, form=self.form,
                               present=base, softmax=self.softmax)
-        if ar.n_train > 0:
-            fused = bool(rt.fused_layers)
-            rt.fused_active = fused         # only this backward updates the fused layers in place
-            try:
-                rt.run_backward(dlogits)
-            finally:
-                rt.fused_active = False
-            self.optimizer_step(int(logits.shape[0]), fused=fused)
+        self._backward_and_step(dlogits, int(logits.shape[0]), fused=True)

@@ -46,7 +46,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_integer, is_number, method_block, seed_value
 from .intensity import philox4x32_10
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA
@@ -60,8 +60,8 @@ def parse_patches(value: Any, key: str = "method.deyo.patches") -> List[int]:
     if isinstance(value, (str, bytes)) or not hasattr(value, "__iter__") or hasattr(value, "keys"):
         raise ValueError(f"{key} = {value!r}: expected three patch counts [gd, gh, gw]")
     grid = list(value)
-    if len(grid) != 3 or any(isinstance(g, bool) or not isinstance(g, int) or not (1 <= g <= MAX_PATCHES_PER_AXIS) for g in grid):
-        raise ValueError(f"{key} = {grid!r}: expected three integers of 1 .. {MAX_PATCHES_PER_AXIS}")
+    expect(len(grid) == 3 and all(is_integer(g) and 1 <= g <= MAX_PATCHES_PER_AXIS for g in grid), key, grid,
+           f"three integers of 1 .. {MAX_PATCHES_PER_AXIS}")
     if grid[0] * grid[1] * grid[2] < 2:
         raise ValueError(f"{key} = {grid!r}: one patch cannot be shuffled (P = gd * gh * gw >= 2)")
     return [int(g) for g in grid]
@@ -82,8 +82,7 @@ def draw_permutation(seed: int, ordinal: int, patches: int) -> List[int]:
 
 
 def _positive(value: Any, key: str) -> float:
-    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (math.isfinite(value) and value > 0.0):
-        raise ValueError(f"{key} = {value!r}: expected a finite positive fraction of ln K")
+    expect(is_number(value) and value > 0.0, key, value, "a finite positive fraction of ln K")
     return float(value)
 
 
@@ -94,21 +93,16 @@ class ShuffleFilteredTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "deyo", {}) or {}
+        s = method_block(config, "deyo")
         self.e_margin = _positive(get_config(s, "e_margin", 0.5), "method.deyo.e_margin")
         self.e_margin0 = _positive(get_config(s, "e_margin0", 0.4), "method.deyo.e_margin0")
-        thr, seed = get_config(s, "plpd_threshold", 0.2), get_config(s, "seed", 0)
-        if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not (math.isfinite(thr) and -1.0 <= thr < 1.0):
-            raise ValueError(f"method.deyo.plpd_threshold = {thr!r}: expected a finite probability difference with "
-                             "-1 <= threshold < 1")
-        if isinstance(seed, bool) or not isinstance(seed, int) or not (0 <= seed < 1 << 64):
-            raise ValueError(f"method.deyo.seed = {seed!r}: expected an integer with 0 <= seed < 2^64")
-        self.plpd_threshold, self.seed = float(thr), int(seed)
+        thr = get_config(s, "plpd_threshold", 0.2)
+        expect(is_number(thr) and -1.0 <= thr < 1.0, "method.deyo.plpd_threshold", thr,
+               "a finite probability difference with -1 <= threshold < 1")
+        self.plpd_threshold, self.seed = float(thr), seed_value(get_config(s, "seed", 0), "method.deyo.seed")
         self.patches = parse_patches(get_config(s, "patches", [4, 4, 4]))
-        if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
-            raise NotImplementedError("method.moddrop.enabled: true is not supported by deyo_tta (the shuffled copy of the "
-                                      "volume is staged once per volume, not once per modality mask)")
+        self._refuse_moddrop("true is not supported by deyo_tta (the shuffled copy of the volume is staged once per volume, "
+                             "not once per modality mask)")
         self._table: Optional[torch.Tensor] = None          # device int32 [B, 2, P] of the volumes being adapted
 
     def margin(self, regions: int, fraction: Optional[float] = None) -> float:
@@ -118,11 +112,7 @@ class ShuffleFilteredTTA(EntropyMinimizationTTA):
 
     def setup(self, model, device) -> "ShuffleFilteredTTA":
         super().setup(model, device)
-        if self.rt.buffers:
-            raise NotImplementedError(
-                f"deyo_tta: model.norm = {get_config(get_config(self.cfg, 'model', {}) or {}, 'norm', 'BATCH')!r} keeps running "
-                "statistics, which the shuffled volume's train-mode forward would move (running_mean, running_var, "
-                "num_batches_tracked belong to the plain forward); use a model.norm without them (INSTANCE, GROUP)")
+        self._refuse_running_stats("deyo_tta", "the shuffled volume's train-mode forward")
         self._setup_ordinals()          # the permutation draw's per-volume numbers
         return self
 
@@ -132,7 +122,7 @@ class ShuffleFilteredTTA(EntropyMinimizationTTA):
                                                 ("kept_entropy", "deyo_kept_entropy", torch.int64))
 
     def _update(self, x: torch.Tensor, present: Optional[Sequence[bool]], x_shuf: torch.Tensor) -> None:
-        rt, ar = self.rt, self.rt.arena
+        rt = self.rt
         rt.pack_all(fused_current=True)          # once, in front of both forwards: the weights do not move in between
         # 1. the shuffled volume; its logits leave the pool's logits buffer, which the second forward writes again
         key = getattr(rt, "family_key", None)
@@ -159,14 +149,7 @@ class ShuffleFilteredTTA(EntropyMinimizationTTA):
         ops.deyo_loss_items(logits, logits_shuf, dlogits, self.patches, self._table, self.margin(r),
                             self.margin(r, self.e_margin0), self.plpd_threshold, keep, partial, loss, kept, kept_entropy,
                             softmax=self.softmax)
-        if ar.n_train > 0:
-            fused = bool(rt.fused_layers)
-            rt.fused_active = fused         # only this backward updates the fused layers in place
-            try:
-                rt.run_backward(dlogits)
-            finally:
-                rt.fused_active = False
-            self.optimizer_step(n, fused=fused)
+        self._backward_and_step(dlogits, n, fused=True)
 
     # ------------------------------------------------------------------ per volume
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:

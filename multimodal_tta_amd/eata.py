@@ -42,7 +42,7 @@ from typing import Any, Dict, Iterable, Optional, Sequence
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_integer, is_number, method_block
 from .ops import MmttaError
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA, drop_modality, modality_mask
@@ -86,15 +86,12 @@ class FisherRegularizedTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        s = get_config(get_config(as_cfg(config), "method", {}) or {}, "eata", {}) or {}
+        s = method_block(config, "eata")
         f = get_config(s, "fisher", {}) or {}
         margin, lam, vols = get_config(s, "e_margin", 0.4), get_config(s, "fisher_alpha", 2000.0), get_config(f, "volumes", 8)
-        if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not (math.isfinite(margin) and margin > 0.0):
-            raise ValueError(f"method.eata.e_margin = {margin!r}: expected a finite positive fraction of ln K")
-        if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not (math.isfinite(lam) and lam >= 0.0):
-            raise ValueError(f"method.eata.fisher_alpha = {lam!r}: expected a finite weight >= 0")
-        if isinstance(vols, bool) or not isinstance(vols, int) or vols < 1:
-            raise ValueError(f"method.eata.fisher.volumes = {vols!r}: expected an integer >= 1")
+        expect(is_number(margin) and margin > 0.0, "method.eata.e_margin", margin, "a finite positive fraction of ln K")
+        expect(is_number(lam) and lam >= 0.0, "method.eata.fisher_alpha", lam, "a finite weight >= 0")
+        expect(is_integer(vols) and vols >= 1, "method.eata.fisher.volumes", vols, "an integer >= 1")
         self.e_margin, self.fisher_alpha, self.fisher_volumes = float(margin), float(lam), int(vols)
         path = get_config(f, "path", None)
         self.fisher_path: Optional[str] = None if path in (None, "", "null") else str(path)
@@ -128,14 +125,15 @@ class FisherRegularizedTTA(EntropyMinimizationTTA):
         keep = rt.pool.flat("eata_keep", elems, dtype=torch.uint8)
         penalty = rt.pool.flat("eata_penalty", slots, zero=True)
         ops.entropy_weighted_items(logits, dlogits, self.margin(r), keep, partial, loss, kept, softmax=self.softmax)
-        if ar.n_train > 0:
-            rt.run_backward(dlogits)
-            if self.fisher_alpha > 0.0:
-                sets = min(n, ar.replicas)
-                pen_partial = rt.pool.flat("eata_pen_partial", ops.fisher_penalty_partials(ar.n_train, sets), dtype=torch.float64)
-                ops.fisher_penalty_sets(ar.params_all, ar.grads_all, self.fisher, ar.source, ar.n_train, sets, self.fisher_alpha,
-                                        pen_partial, penalty)
-            self.optimizer_step(n)
+        self._backward_and_step(dlogits, n, between=lambda: self._fisher_penalty(min(n, ar.replicas), penalty))
+
+    def _fisher_penalty(self, sets: int, penalty: torch.Tensor) -> None:
+        """Between the backward and the optimizer: g += 2 lam F (w - w0) on the first ``sets`` replicas, P into ``penalty``."""
+        rt, ar = self.rt, self.rt.arena
+        if self.fisher_alpha > 0.0:
+            pen_partial = rt.pool.flat("eata_pen_partial", ops.fisher_penalty_partials(ar.n_train, sets), dtype=torch.float64)
+            ops.fisher_penalty_sets(ar.params_all, ar.grads_all, self.fisher, ar.source, ar.n_train, sets, self.fisher_alpha,
+                                    pen_partial, penalty)
 
     def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
         """As ``entmin_tta.adapt_volume``, plus ``kept`` and ``penalty`` per step ([steps], or [steps, B] for a group).  As

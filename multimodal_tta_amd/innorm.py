@@ -26,14 +26,12 @@ family batch and re-staging path would be a second integration), and not togethe
 """
 from __future__ import annotations
 
-import math
 from typing import Any, Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
-from .engine import HeadLossTail
+from .config import expect, get_config, is_number, method_block
 from .models.unet import UNetRuntime
 from .ops import MmttaError
 from .registry import register_plugin
@@ -43,28 +41,21 @@ MAX_LOG_SCALE, MAX_SHIFT, MAX_LOG_GAMMA = 4.0, 16.0, 2.0
 MAX_COUT, MAX_CIN = 64, 4
 
 
-def _number(value: Any) -> bool:
-    return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value)
-
-
 class InputMapTTA(EntropyMinimizationTTA):
     """What the plugins that adapt an input map share (``innorm_tta`` here, ``biasfield_tta`` in biasfield.py): a raw fp32 copy
     of the staged volumes, one step - the map, the parent's forward, loss and backward, the step on the map's theta from the
     first level's reduced input gradient, the optimizer - and the final logits through the map at the final theta.  A
-    subclass sets ``plugin`` (its name in messages), ``prefix`` (of its pool buffers), ``row`` (floats of a theta / grad row)
-    and ``lr``, and provides ``_apply`` and ``_input_step``."""
-    plugin, prefix, row = "", "", 4
+    subclass sets ``plugin`` (its name in messages), ``prefix`` (of its pool buffers), ``row`` (floats of a theta / grad row),
+    ``record`` (the result key of the per-step dL/dtheta) and ``lr``, and provides ``_apply`` and ``_input_step``."""
+    plugin, prefix, row, record = "", "", 4, ""
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
-            raise NotImplementedError(f"method.moddrop.enabled: {self.plugin} learns one theta per volume on a fixed set of "
-                                      "modalities; modality dropout redraws them every step")
+        self._refuse_moddrop(f"{self.plugin} learns one theta per volume on a fixed set of modalities; modality dropout redraws "
+                             "them every step")
         self.lr = 0.0
         self._raw: Optional[torch.Tensor] = None           # the raw fp32 staged volumes of the call
         self._x_in: Optional[torch.Tensor] = None
-        self._t = 0
 
     # ------------------------------------------------------------------ setup
     def setup(self, model, device) -> "InputMapTTA":
@@ -131,8 +122,7 @@ class InputMapTTA(EntropyMinimizationTTA):
             return super()._stage(x_cl)
         rt, p = self.rt, self.prefix
         n, d, h, w, c = x_cl.shape
-        if n > rt.group:          # (every volume has its own theta)
-            raise ValueError(f"method.group = {rt.group}: {self.plugin} adapts at most {rt.group} volumes per call, got {n}")
+        self._check_volumes(n, f"{self.plugin} adapts ")          # (every volume has its own theta)
         # the raw volume stays in fp32: a value is rounded once, after the map
         raw = rt.pool.cl("x_raw", n, d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=torch.float32)
         ops.to_cl(self._x_in, out=raw)
@@ -140,9 +130,6 @@ class InputMapTTA(EntropyMinimizationTTA):
         partial = rt.pool.flat(f"{p}_range_partial", ops.intensity_range_partials(raw))
         ops.intensity_range(raw, partial, t["range"])
         self._raw = raw
-        self._hist = rt.pool.flat(f"{p}_grad_hist", max(self.steps, self._steps_now, 1) * rt.group * c * self.row).view(
-            -1, rt.group, c, self.row)
-        self._t = 0
         return x_cl, (raw,)
 
     # ------------------------------------------------------------------ one step
@@ -153,46 +140,24 @@ class InputMapTTA(EntropyMinimizationTTA):
             super()._update(x, present)
             return
         raw, = views
-        rt, ar = self.rt, self.rt.arena
         self._apply(raw, x, present)
-        rt.pack_all(fused_current=True)
-        loss = rt.pool.flat("ent_loss", rt.group)
-        per_item = rt.group > 1
-        tail = None
-        if getattr(rt, "supports_head_tail", False) and not self.softmax and (per_item or int(x.shape[0]) == 1):
-            tail = HeadLossTail(self._dlogits, loss, per_item)
-        kw = {} if present is None else {"present": present}
-        logits = rt.forward_cl(x, **kw) if tail is None else rt.forward_cl(x, tail=tail, **kw)
-        if tail is not None and tail.done:
-            dlogits = tail.dlogits
-        elif rt.group > 1:
-            dlogits = self._dlogits(logits)
-            partial = rt.pool.flat("ent_partial", ops.entropy_partials_items(logits), dtype=torch.float64)
-            ops.entropy_loss_items(logits, dlogits, partial, loss, softmax=self.softmax)
-        else:
-            dlogits = self._dlogits(logits)
-            partial = rt.pool.flat("ent_partial", ops.entropy_partials(logits), dtype=torch.float64)
-            ops.entropy_loss(logits, dlogits, partial, loss, softmax=self.softmax)
-        fused = bool(rt.fused_layers) and ar.n_train > 0
-        rt.fused_active = fused         # only this backward updates the fused layers in place
-        try:
-            rt.run_backward(dlogits)
-        finally:
-            rt.fused_active = False
-        try:
-            self._input_step(raw, present)
-        except MmttaError as exc:
-            if "status -2" in str(exc):        # MMTTA_ERR_UNSUPPORTED: a first level the kernel does not gather
-                raise NotImplementedError(f"{self.plugin}: the model's first level is not supported: {exc}") from exc
-            raise
-        if ar.n_train > 0:
-            self.optimizer_step(int(logits.shape[0]), fused=fused)
+        self.rt.pack_all(fused_current=True)
+        logits, dlogits = self._entropy_objective(x, present)
 
-    def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]], *views: torch.Tensor) -> None:
-        super()._step(x_cl, present, *views)
-        if self.lr > 0.0:
-            self._hist[self._t].copy_(self._tables()["grad"].view(self._hist.shape[1:]))
-            self._t += 1
+        def input_step():
+            try:
+                self._input_step(raw, present)
+            except MmttaError as exc:
+                if "status -2" in str(exc):        # MMTTA_ERR_UNSUPPORTED: a first level the kernel does not gather
+                    raise NotImplementedError(f"{self.plugin}: the model's first level is not supported: {exc}") from exc
+                raise
+        self._backward_and_step(dlogits, int(logits.shape[0]), fused=True, between=input_step, always_backward=True)
+
+    def _records(self):
+        """The parent's, and dL/dtheta of every step: one [C, row] row per replica (the map's ``grad`` table)."""
+        if self.lr == 0.0:
+            return self.records
+        return self.records + ((self.record, f"{self.prefix}_grad", torch.float32, (self.rt.in_channels, self.row)),)
 
     def _final_logits(self, x_cl: torch.Tensor, x_step: torch.Tensor, present: Optional[Sequence[bool]]) -> torch.Tensor:
         """The eval-mode forward of x' at the final theta: the map runs once more, after the last step."""
@@ -200,14 +165,19 @@ class InputMapTTA(EntropyMinimizationTTA):
             self._apply(self._raw, x_cl, present)
         return self._forward(x_cl, present)
 
-    def _adapt(self, x: torch.Tensor, steps: Optional[int]) -> Dict[str, Any]:
-        """``EntropyMinimizationTTA.adapt_volume`` with the fp32 volumes at hand for ``_stage``."""
-        self._steps_now = self.steps if steps is None else int(steps)
+    @torch.no_grad()
+    def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
+        """``EntropyMinimizationTTA.adapt_volume`` with the fp32 volumes at hand for ``_stage``; at ``lr: 0`` the ``record``
+        is zeros [steps, B, C, row]."""
         self._x_in = x.float()
         try:
-            return EntropyMinimizationTTA.adapt_volume(self, x, steps)
+            out = super().adapt_volume(x, steps)
         finally:
             self._x_in = None
+        if self.lr == 0.0:
+            out[self.record] = torch.zeros((len(out["losses"]), int(x.shape[0]), int(x.shape[1]), self.row), dtype=torch.float32,
+                                           device=x.device)
+        return out
 
 
 @register_plugin("innorm_tta")
@@ -217,22 +187,18 @@ class InputNormTTA(InputMapTTA):
     default 0.7): theta is clamped to +- its bound after every step.  theta's optimizer is Adam with torch's default betas
     and eps and no decay, whatever ``training.optimizer`` is.  Everything else is ``entmin_tta``'s, with one limit: every
     volume has its own theta, so a call takes at most ``method.group`` volumes."""
-    plugin, prefix, row = "innorm_tta", "innorm", 4
+    plugin, prefix, row, record = "innorm_tta", "innorm", 4, "input_grad"
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "innorm", {}) or {}
+        s = method_block(config, "innorm")
         lr, gm = get_config(s, "lr", 1e-2), get_config(s, "gamma", False)
         bd = get_config(s, "bound", {}) or {}
         bs, bb, bg = get_config(bd, "log_scale", 0.7), get_config(bd, "shift", 1.0), get_config(bd, "log_gamma", 0.7)
-        if not _number(lr) or lr < 0.0:
-            raise ValueError(f"method.innorm.lr = {lr!r}: expected a finite number >= 0 (0: entmin_tta)")
-        if not isinstance(gm, bool):
-            raise ValueError(f"method.innorm.gamma = {gm!r}: expected a bool")
+        expect(is_number(lr) and lr >= 0.0, "method.innorm.lr", lr, "a finite number >= 0 (0: entmin_tta)")
+        expect(isinstance(gm, bool), "method.innorm.gamma", gm, "a bool")
         for key, val, top in (("log_scale", bs, MAX_LOG_SCALE), ("shift", bb, MAX_SHIFT), ("log_gamma", bg, MAX_LOG_GAMMA)):
-            if not _number(val) or not (0.0 < val <= top):
-                raise ValueError(f"method.innorm.bound.{key} = {val!r}: expected a finite number in (0, {top:g}]")
+            expect(is_number(val) and 0.0 < val <= top, f"method.innorm.bound.{key}", val, f"a finite number in (0, {top:g}]")
         self.lr, self.gamma, self.bounds = float(lr), bool(gm), (float(bs), float(bb), float(bg))
 
     def _apply(self, raw: torch.Tensor, x: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
@@ -252,15 +218,14 @@ class InputNormTTA(InputMapTTA):
         """``EntropyMinimizationTTA.adapt_volume`` plus ``input_grad`` [steps, B, C, 3] (dL/d(s, b, g) of every step; the g
         column is 0 with gamma off) and ``input_scale``, ``input_shift``, ``input_gamma`` [B, C]: exp(s), b, exp(g) at the end."""
         B, C = int(x.shape[0]), int(x.shape[1])
-        out = self._adapt(x, steps)
+        out = super().adapt_volume(x, steps)
+        out["input_grad"] = out["input_grad"][..., :3]
         if self.lr == 0.0:
-            out["input_grad"] = torch.zeros((self._steps_now, B, C, 3), dtype=torch.float32, device=x.device)
             out["input_scale"] = torch.ones((B, C), dtype=torch.float32, device=x.device)
             out["input_shift"] = torch.zeros((B, C), dtype=torch.float32, device=x.device)
             out["input_gamma"] = torch.ones((B, C), dtype=torch.float32, device=x.device)
             return out
         theta = self._tables()["theta"].view(-1, C, 4)[:B]
-        out["input_grad"] = self._hist[:self._steps_now, :B, :, :3].clone()
         out["input_scale"] = torch.exp(theta[..., 0])
         out["input_shift"] = theta[..., 1].clone()
         out["input_gamma"] = torch.exp(theta[..., 2])

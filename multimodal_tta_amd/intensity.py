@@ -20,13 +20,12 @@ fourth counter word 0: the three never meet.
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass, field
 from typing import Any, List, Optional, Sequence
 
 import numpy as np
 
-from .config import get_config
+from .config import expect, get_config, is_integer, is_number, seed_value
 
 MAX_VIEWS = 8
 COPIES = (1, 2, 4, 8)
@@ -57,8 +56,7 @@ def view_layout(mirror_axes: Sequence[str], copies: int = 1, key: str = "intensi
     over.  A code is a mirror mask (bit 0 = W, 1 = H, 2 = D) plus bit 4 = H and W transposed first."""
     from .memo import ROT90_CODES, rotated_code, view_masks
     base = view_masks(mirror_axes)
-    if isinstance(copies, bool) or not isinstance(copies, int) or copies not in COPIES:
-        raise ValueError(f"{key}.copies = {copies!r}: expected 1, 2, 4 or 8")
+    expect(is_integer(copies) and copies in COPIES, f"{key}.copies", copies, "1, 2, 4 or 8")
     if len(base) * copies > MAX_VIEWS:
         raise ValueError(f"{key}.copies = {copies} with {len(base)} mirrored views: V = {len(base) * copies} views, at most "
                          f"{MAX_VIEWS}")
@@ -120,17 +118,14 @@ def parse_intensity(value: Any, mirror_axes: Sequence[str], key: str = "method.m
     mags = {}
     for k in MAGNITUDES:
         v = get_config(value, k, 0.0)
-        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)) or float(v) < 0.0:
-            raise ValueError(f"{key}.{k} = {v!r}: expected a finite magnitude >= 0")
+        expect(is_number(v) and v >= 0.0, f"{key}.{k}", v, "a finite magnitude >= 0")
         mags[k] = float(v)
     if mags["scale"] >= 1.0:
         raise ValueError(f"{key}.scale = {mags['scale']!r}: expected scale < 1 (the factor 1 + scale * (2u - 1) stays positive)")
-    per_channel, seed = get_config(value, "per_channel", False), get_config(value, "seed", 0)
-    if not isinstance(per_channel, bool):
-        raise ValueError(f"{key}.per_channel = {per_channel!r}: expected true or false")
-    if isinstance(seed, bool) or not isinstance(seed, int) or not (0 <= seed < 1 << 64):
-        raise ValueError(f"{key}.seed = {seed!r}: expected an integer with 0 <= seed < 2^64")
-    spec = IntensitySpec(copies=copies, per_channel=per_channel, seed=int(seed), view_axes=view_axes, **mags)
+    per_channel = get_config(value, "per_channel", False)
+    expect(isinstance(per_channel, bool), f"{key}.per_channel", per_channel, "true or false")
+    seed = seed_value(get_config(value, "seed", 0), f"{key}.seed")
+    spec = IntensitySpec(copies=copies, per_channel=per_channel, seed=seed, view_axes=view_axes, **mags)
     if copies > 1 and not spec.active:
         raise ValueError(f"{key}.copies = {copies} with scale, shift, gamma and noise_std all 0: the copies of a view would be "
                          "identical")

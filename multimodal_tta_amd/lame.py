@@ -28,23 +28,18 @@ and is ``entmin_tta`` bit for bit.
 """
 from __future__ import annotations
 
-import math
 from typing import Any, Dict, Optional, Sequence
 
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_integer, is_number, method_block
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA, modality_mask
 
 MAX_ITERATIONS = 64
 MAX_WEIGHT = 16.0
 CONNECTIVITIES = (6, 18, 26)
-
-
-def _number(value: Any) -> bool:
-    return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value)
 
 
 @register_plugin("lame_tta")
@@ -54,18 +49,13 @@ class LaplacianRefinedTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "lame", {}) or {}
+        s = method_block(config, "lame")
         it, wt = get_config(s, "iterations", 10), get_config(s, "weight", 1.0)
         sg, cn = get_config(s, "sigma", 1.0), get_config(s, "connectivity", 26)
-        if isinstance(it, bool) or not isinstance(it, int) or not (0 <= it <= MAX_ITERATIONS):
-            raise ValueError(f"method.lame.iterations = {it!r}: expected an integer of 0 .. {MAX_ITERATIONS}")
-        if not _number(wt) or not (0.0 < wt <= MAX_WEIGHT):
-            raise ValueError(f"method.lame.weight = {wt!r}: expected a finite number in (0, {MAX_WEIGHT:g}]")
-        if not _number(sg) or sg < 0.0:
-            raise ValueError(f"method.lame.sigma = {sg!r}: expected a finite number >= 0 (0: no affinity)")
-        if isinstance(cn, bool) or not isinstance(cn, int) or cn not in CONNECTIVITIES:
-            raise ValueError(f"method.lame.connectivity = {cn!r}: expected 6, 18 or 26")
+        expect(is_integer(it) and 0 <= it <= MAX_ITERATIONS, "method.lame.iterations", it, f"an integer of 0 .. {MAX_ITERATIONS}")
+        expect(is_number(wt) and 0.0 < wt <= MAX_WEIGHT, "method.lame.weight", wt, f"a finite number in (0, {MAX_WEIGHT:g}]")
+        expect(is_number(sg) and sg >= 0.0, "method.lame.sigma", sg, "a finite number >= 0 (0: no affinity)")
+        expect(is_integer(cn) and cn in CONNECTIVITIES, "method.lame.connectivity", cn, "6, 18 or 26")
         self.iterations, self.weight, self.sigma, self.connectivity = int(it), float(wt), float(sg), int(cn)
         self._flipped: Optional[torch.Tensor] = None
 

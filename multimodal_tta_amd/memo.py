@@ -33,7 +33,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_integer, method_block
 from .intensity import parse_intensity
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA, modality_mask
@@ -74,7 +74,7 @@ def parse_rot90(value: Any, key: str = "method.memo.rot90") -> List[int]:
         raise ValueError(f"{key}.k = {k!r}: expected a list of quarter turns out of 1, 2, 3")
     turns = list(k)
     for t in turns:
-        if isinstance(t, bool) or not isinstance(t, int) or t not in ROT90_CODES:
+        if not is_integer(t) or t not in ROT90_CODES:
             raise ValueError(f"{key}.k = {turns!r}: {t!r} is no quarter-turn count (1, 2 or 3)")
     if len(set(turns)) != len(turns):
         raise ValueError(f"{key}.k = {turns!r}: a turn is repeated")
@@ -106,21 +106,16 @@ class MarginalEntropyTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "memo", {}) or {}
+        s = method_block(config, "memo")
         self.mirror_axes = parse_mirror_axes(get_config(s, "mirror_axes", ["h", "w"]))
-        ens = get_config(s, "ensemble", False)
-        if not isinstance(ens, bool):
-            raise ValueError(f"method.memo.ensemble = {ens!r}: expected true or false")
-        self.ensemble = ens
+        self.ensemble = get_config(s, "ensemble", False)
+        expect(isinstance(self.ensemble, bool), "method.memo.ensemble", self.ensemble, "true or false")
         self.rot90 = parse_rot90(get_config(s, "rot90", None), "method.memo.rot90")
         self.intensity = parse_intensity(get_config(s, "intensity", None), self.mirror_axes, "method.memo.intensity", self.rot90)
         # ({identity} + the quarter turns) x the mirror group, ``intensity.copies`` times over
         self.view_axes = self.intensity.view_axes
         self.views = len(self.view_axes)
-        if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
-            raise NotImplementedError("method.moddrop.enabled: true is not supported by memo_tta (one modality mask per step "
-                                      "for all views is not defined yet)")
+        self._refuse_moddrop("true is not supported by memo_tta (one modality mask per step for all views is not defined yet)")
         # the fused weight update reduces one batch item per parameter set; V views per set take the separate passes
         self.fused_update = self.views == 1
 
@@ -141,9 +136,7 @@ class MarginalEntropyTTA(EntropyMinimizationTTA):
         partial = rt.pool.flat("memo_partial", ops.memo_partials(logits, self.views), dtype=torch.float64)
         loss = rt.pool.flat("ent_loss", rt.group)
         ops.memo_loss_items(logits, dlogits, self.view_axes, partial, loss, softmax=self.softmax)
-        if rt.arena.n_train > 0:
-            rt.run_backward(dlogits)
-            self.optimizer_step(int(logits.shape[0]) // self.views)
+        self._backward_and_step(dlogits, int(logits.shape[0]) // self.views)
 
     # ------------------------------------------------------------------ per volume
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:

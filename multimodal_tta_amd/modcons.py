@@ -31,13 +31,12 @@ V > 1 the fused weight-gradient update is off (its reduction covers one batch it
 """
 from __future__ import annotations
 
-import math
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import as_cfg, expect, get_config, is_integer, is_number, method_block
 from .models.unet import UNetRuntime
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA
@@ -60,7 +59,7 @@ def parse_subsets(value: Any, key: str = KEY) -> Union[str, List[List[int]]]:
         if isinstance(s, (str, bytes)) or not hasattr(s, "__iter__") or hasattr(s, "keys"):
             raise ValueError(f"{key} = {list(value)!r}: {s!r} is no list of channel indices")
         idx = list(s)
-        if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
+        if not all(is_integer(i) for i in idx):
             raise ValueError(f"{key} = {list(value)!r}: {idx!r} is no list of channel indices")
         subsets.append([int(i) for i in idx])
     return subsets
@@ -102,8 +101,7 @@ def keep_masks(subsets: Union[str, Sequence[Sequence[int]]], channels: int, miss
 
 
 def _weight(value: Any, key: str) -> float:
-    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (math.isfinite(value) and value >= 0.0):
-        raise ValueError(f"{key} = {value!r}: expected a finite number >= 0")
+    expect(is_number(value) and value >= 0.0, key, value, "a finite number >= 0")
     return float(value)
 
 
@@ -115,33 +113,26 @@ class ModalityConsistencyTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        s = get_config(m, "modcons", {}) or {}
+        s = method_block(config, "modcons")
         self.subsets = parse_subsets(get_config(s, "subsets", "leave_one_out"))
         self.weight = _weight(get_config(s, "weight", 1.0), "method.modcons.weight")
         self.entropy_weight = _weight(get_config(s, "entropy_weight", 1.0), "method.modcons.entropy_weight")
-        det = get_config(s, "detach", True)
-        if not isinstance(det, bool):
-            raise ValueError(f"method.modcons.detach = {det!r}: expected true or false")
-        self.detach = det
-        if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
-            raise NotImplementedError("method.moddrop.enabled: true is not supported by modcons_tta (the subset views are staged "
-                                      "once per volume, not once per modality mask)")
+        self.detach = get_config(s, "detach", True)
+        expect(isinstance(self.detach, bool), "method.modcons.detach", self.detach, "true or false")
+        self._refuse_moddrop("true is not supported by modcons_tta (the subset views are staged once per volume, not once per "
+                             "modality mask)")
         self.keep_masks: Optional[List[int]] = None
         self.views = 1
         if self.weight > 0.0:
             # the channel count is the model's: known here when the model block says it, else at setup
             mc = get_config(as_cfg(config), "model", {}) or {}
             channels = get_config(mc, "in_channels", None)
-            if isinstance(channels, int) and not isinstance(channels, bool) and channels > 0:
+            if is_integer(channels) and channels > 0:
                 self.resolve(channels)
             elif not isinstance(self.subsets, str):
                 self.views = 1 + len(self.subsets)
         # the fused weight update reduces one batch item per parameter set; V views per set take the separate passes
         self.fused_update = self.views == 1
-        self._kl_hist: Optional[torch.Tensor] = None
-        self._dis_hist: Optional[torch.Tensor] = None
-        self._t = 0
 
     def resolve(self, channels: int) -> List[int]:
         """The views of a model with ``channels`` input channels: ``keep_masks`` and ``views`` (ValueError naming
@@ -162,11 +153,8 @@ class ModalityConsistencyTTA(EntropyMinimizationTTA):
                                           "modality there")
             self.resolve(int(model.in_channels))
         super().setup(model, device)
-        if self.views > 1 and self.rt.buffers:
-            raise NotImplementedError(
-                f"modcons_tta: model.norm = {get_config(get_config(self.cfg, 'model', {}) or {}, 'norm', 'BATCH')!r} keeps running "
-                "statistics, which the train-mode forward of the masked views would move (running_mean, running_var, "
-                "num_batches_tracked belong to the plain forward); use a model.norm without them (INSTANCE, GROUP)")
+        if self.views > 1:
+            self._refuse_running_stats("modcons_tta", "the train-mode forward of the masked views")
         return self
 
     # ------------------------------------------------------------------ one step
@@ -174,10 +162,12 @@ class ModalityConsistencyTTA(EntropyMinimizationTTA):
     records = EntropyMinimizationTTA.records + (("entropy", "modcons_entropy", torch.float32),
                                                 ("consistency", "modcons_consistency", torch.float32))
 
-    def _tables(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        rt, k = self.rt, self.views - 1
-        return (rt.pool.flat("modcons_view_kl", rt.group * k, zero=True),
-                rt.pool.flat("modcons_disagree", rt.group * k, dtype=torch.int64, zero=True))
+    def _records(self):
+        """``records``, and with V > 1 views the K_v and the hard disagreements with view 0: one [V-1] row per replica."""
+        if self.views == 1:
+            return self.records
+        return self.records + (("view_kl", "modcons_view_kl", torch.float32, (self.views - 1,)),
+                               ("disagree", "modcons_disagree", torch.int64, (self.views - 1,)))
 
     def _update(self, xv: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
         if self.views == 1:
@@ -191,31 +181,19 @@ class ModalityConsistencyTTA(EntropyMinimizationTTA):
         loss = rt.pool.flat("ent_loss", rt.group)
         entropy = rt.pool.flat("modcons_entropy", rt.group)
         consistency = rt.pool.flat("modcons_consistency", rt.group)
-        view_kl, disagree = self._tables()
+        k = self.views - 1
+        view_kl = rt.pool.flat("modcons_view_kl", rt.group * k, zero=True)
+        disagree = rt.pool.flat("modcons_disagree", rt.group * k, dtype=torch.int64, zero=True)
         ops.modcons_loss_items(logits, dlogits, self.views, partial, loss, entropy, consistency, view_kl, disagree,
                                weight=self.weight, entropy_weight=self.entropy_weight, detach=self.detach, softmax=self.softmax)
-        if rt.arena.n_train > 0:
-            rt.run_backward(dlogits)
-            self.optimizer_step(int(logits.shape[0]) // self.views)
-
-    def _step(self, x_cl: torch.Tensor, present: Optional[Sequence[bool]], *views: torch.Tensor) -> None:
-        super()._step(x_cl, present, *views)
-        if self.views > 1:
-            view_kl, disagree = self._tables()
-            self._kl_hist[self._t].copy_(view_kl.view(self._kl_hist.shape[1:]))
-            self._dis_hist[self._t].copy_(disagree.view(self._dis_hist.shape[1:]))
-            self._t += 1
+        self._backward_and_step(dlogits, int(logits.shape[0]) // self.views)
 
     # ------------------------------------------------------------------ per volume
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
         if self.views == 1:
             return super()._stage(x_cl)
-        rt, k = self.rt, self.views - 1
+        rt = self.rt
         n, d, h, w, c = x_cl.shape
-        rows = max(self.steps, self._steps_now, 1)
-        self._kl_hist = rt.pool.flat("modcons_view_kl_hist", rows * rt.group * k).view(rows, rt.group, k)
-        self._dis_hist = rt.pool.flat("modcons_disagree_hist", rows * rt.group * k, dtype=torch.int64).view(rows, rt.group, k)
-        self._t = 0
         rt.views = self.views          # every launch of the loop carries V consecutive batch items per volume
         xv = rt.pool.cl("modcons_views", n * self.views, d, h, w, c, ldc=(c + 3) // 4 * 4, zero=True, dtype=x_cl.dtype)
         ops.modality_views(x_cl, xv, self.keep_masks)
@@ -231,18 +209,13 @@ class ModalityConsistencyTTA(EntropyMinimizationTTA):
         fp32 [steps, B, V-1] and ``disagree`` int64 [steps, B, V-1] (``weight: 0``: ``entropy`` = ``losses``, the rest empty or
         zero).  Every volume brings its V views onto its own replica: a call takes at most ``method.group`` volumes."""
         B = int(x.shape[0])
-        group = int(self.rt.group) if self.rt is not None else self.group
-        if self.views > 1 and B > group:
-            raise NotImplementedError(f"method.group = {group}: modcons_tta adapts at most {group} volumes per call (the V views "
-                                      f"of a volume share its parameter replica), got {B}")
-        self._steps_now = self.steps if steps is None else int(steps)
+        if self.views > 1:
+            self._check_volumes(B, "modcons_tta adapts ", " (the V views of a volume share its parameter replica)",
+                                NotImplementedError)
         out = super().adapt_volume(x, steps)
         if self.views == 1:
             out["entropy"] = out["losses"].clone()
             out["consistency"] = torch.zeros_like(out["losses"])
-            out["view_kl"] = torch.zeros((self._steps_now, B, 0), dtype=torch.float32, device=x.device)
-            out["disagree"] = torch.zeros((self._steps_now, B, 0), dtype=torch.int64, device=x.device)
-            return out
-        out["view_kl"] = self._kl_hist[:self._steps_now, :B].clone()
-        out["disagree"] = self._dis_hist[:self._steps_now, :B].clone()
+            out["view_kl"] = torch.zeros((len(out["losses"]), B, 0), dtype=torch.float32, device=x.device)
+            out["disagree"] = torch.zeros((len(out["losses"]), B, 0), dtype=torch.int64, device=x.device)
         return out

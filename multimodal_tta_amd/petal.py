@@ -35,7 +35,7 @@ from typing import Any, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_number, method_block
 from .cotta import MeanTeacherTTA
 from .registry import register_plugin
 
@@ -59,10 +59,8 @@ class FisherRestoreTTA(MeanTeacherTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        s = get_config(get_config(as_cfg(config), "method", {}) or {}, "petal", {}) or {}
-        q = get_config(s, "quantile", 0.03)
-        if isinstance(q, bool) or not isinstance(q, (int, float)) or not (0.0 <= float(q) < 1.0):
-            raise ValueError(f"method.petal.quantile = {q!r}: expected a share with 0 <= quantile < 1")
+        q = get_config(method_block(config, "petal"), "quantile", 0.03)
+        expect(is_number(q) and 0.0 <= q < 1.0, "method.petal.quantile", q, "a share with 0 <= quantile < 1")
         self.quantile = float(q)
         self.restore_p = 0.0          # (no stochastic restore: the keys of method.cotta that method.petal does not carry)
         self.table: Optional[ops.RankTable] = None

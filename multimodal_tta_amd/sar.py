@@ -25,7 +25,7 @@ from typing import Any, Optional, Sequence
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_number, method_block
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA, select_params
 
@@ -38,13 +38,13 @@ class SharpnessAwareReliableTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        s = get_config(get_config(as_cfg(config), "method", {}) or {}, "sar", {}) or {}
+        s = method_block(config, "sar")
+        # (converted before the check: a numeric string or a bool passes, unlike in the later methods)
         self.e_margin = float(get_config(s, "e_margin", 0.4))
         self.rho = float(get_config(s, "rho", 0.05))
-        if not (math.isfinite(self.e_margin) and self.e_margin > 0.0):
-            raise ValueError(f"method.sar.e_margin = {self.e_margin}: expected a finite positive fraction of ln K")
-        if not (math.isfinite(self.rho) and self.rho >= 0.0):
-            raise ValueError(f"method.sar.rho = {self.rho}: expected a finite radius >= 0")
+        expect(is_number(self.e_margin) and self.e_margin > 0.0, "method.sar.e_margin", self.e_margin,
+               "a finite positive fraction of ln K")
+        expect(is_number(self.rho) and self.rho >= 0.0, "method.sar.rho", self.rho, "a finite radius >= 0")
 
     def setup(self, model, device) -> "SharpnessAwareReliableTTA":
         if not select_params(model, self.params_spec):
@@ -86,7 +86,5 @@ class SharpnessAwareReliableTTA(EntropyMinimizationTTA):
         rt.pack_all()
         logits = self._forward(x, present)
         ops.entropy_filtered_items(logits, dlogits, margin, keep1, keep2, partial, loss2, kept2, softmax=self.softmax)
-        rt.run_backward(dlogits)
         # exact restore (SAR's SAM copies old_p back), then the base optimizer with the gradient taken at w + eps
-        ar.params_all[:sets, :ar.n_train].copy_(saved[:sets])
-        self.optimizer_step(n)
+        self._backward_and_step(dlogits, n, between=lambda: ar.params_all[:sets, :ar.n_train].copy_(saved[:sets]))

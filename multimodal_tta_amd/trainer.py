@@ -75,7 +75,7 @@ class SupervisedSegStep(EntropyMinimizationTTA):
         """One supervised step on ``batch = {"image": [B,C,D,H,W], "label": [B,R,D,H,W]}`` (reference :97-145)."""
         if self.rt is None:
             raise MmttaError("call setup(model, device) first")
-        rt, ar = self.rt, self.rt.arena
+        rt = self.rt
         dev = rt.device
         x = batch["image"].to(dev).float()
         y = batch["label"].to(dev).float().contiguous()
@@ -103,7 +103,5 @@ class SupervisedSegStep(EntropyMinimizationTTA):
         dlogits = rt.pool.cl("dlogits", n, d, h, w, r, ldc=(r + 3) // 4 * 4)
         ops.dice_ce_grad(logits, y, self._w_dev, self.squared_pred, self.jaccard, self.include_background,
                          self.lambda_dice, self.lambda_ce, sums, dlogits, logits_channels_last=True, softmax=self.softmax)
-        if ar.n_train > 0:
-            rt.run_backward(dlogits)
-            self.optimizer_step()
+        self._backward_and_step(dlogits, 1)
         return {"loss": self.loss_value(sums, n, r, d * h * w)}

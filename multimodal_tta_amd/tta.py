@@ -15,6 +15,7 @@ returns to the host inside a volume except the final per-region counts (one smal
 """
 from __future__ import annotations
 
+import math
 import warnings
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -22,7 +23,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import as_cfg, get_config, method_block
 from .engine import HeadLossTail
 from .models.base import DEFAULT_NO_DECAY_KEYS, HipSegModel
 from .ops import MmttaError
@@ -79,7 +80,7 @@ class EntropyMinimizationTTA:
     def __init__(self, config: Any = None):
         cfg = as_cfg(config)
         self.cfg = cfg
-        m = get_config(cfg, "method", {}) or {}
+        m = method_block(cfg)
         self.steps = int(get_config(m, "steps", 10))
         self.episodic = bool(get_config(m, "episodic", True))
         self.params_spec = get_config(m, "params", "all")
@@ -206,8 +207,7 @@ class EntropyMinimizationTTA:
         """The ordinals of the ``B`` volumes of one ``adapt_volume`` call, on the host and in ``self._ordinals[:B]``: the
         caller's, or by default the volumes served so far.  The ordinal, never the replica slot, enters a draw - which is
         what keeps a group of volumes equal to the same volumes served one at a time."""
-        if B > self.rt.group:          # (one ordinal per replica)
-            raise ValueError(f"method.group = {self.rt.group}: at most {self.rt.group} volumes per call, got {B}")
+        self._check_volumes(B)          # (one ordinal per replica)
         if ordinals is None:
             ordinals = [self._served + b for b in range(B)]
             self._served += B
@@ -243,9 +243,16 @@ class EntropyMinimizationTTA:
 
     def _update(self, x: torch.Tensor, present: Optional[Sequence[bool]]) -> None:
         """The method's own launch sequence: pack, forward, objective, backward, optimizer.  It leaves every per-step record
-        (``records``) in its pool buffer, one slot per replica."""
-        rt, ar = self.rt, self.rt.arena
-        rt.pack_all(fused_current=True)
+        (``records``) in its pool buffer, one slot per replica.  A method with another objective keeps three parts: the
+        buffers it owns, its loss call, and ``_backward_and_step``."""
+        self.rt.pack_all(fused_current=True)
+        logits, dlogits = self._entropy_objective(x, present)
+        self._backward_and_step(dlogits, int(logits.shape[0]), fused=True)
+
+    def _entropy_objective(self, x: torch.Tensor, present: Optional[Sequence[bool]]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Tent's objective on ``x``: the forward and the mean entropy of its logits, per volume of a group -> (logits,
+        dlogits), the loss in ``ent_loss``."""
+        rt = self.rt
         loss = rt.pool.flat("ent_loss", rt.group)
         # the objective may ride in the epilogue of the network's last convolution, which then stores no logits (nothing
         # else reads a step's logits): every volume its own objective, as below - or the batch of one
@@ -266,14 +273,34 @@ class EntropyMinimizationTTA:
             dlogits = self._dlogits(logits)
             partial = rt.pool.flat("ent_partial", ops.entropy_partials(logits), dtype=torch.float64)
             ops.entropy_loss(logits, dlogits, partial, loss, softmax=self.softmax)
-        if ar.n_train > 0:
-            fused = bool(rt.fused_layers)
-            rt.fused_active = fused         # only this backward updates the fused layers in place
-            try:
-                rt.run_backward(dlogits)
-            finally:
-                rt.fused_active = False
-            self.optimizer_step(int(logits.shape[0]), fused=fused)
+        return logits, dlogits
+
+    def _backward_and_step(self, dlogits: torch.Tensor, volumes: int, fused: bool = False, between=None, after=None,
+                           always_backward: bool = False) -> None:
+        """The tail of every step: the backward of ``dlogits`` and the optimizer over ``volumes`` replicas - nothing at all
+        where no parameter trains, unless ``always_backward`` (a method that reads the input gradients: the backward runs,
+        the optimizer does not).  ``fused``: the step packed with ``fused_current`` and lets the backward update
+        ``rt.fused_layers`` in place.  ``between()`` runs after the backward (the gradients are in the arena, no weight has
+        moved), ``after()`` after the optimizer."""
+        rt = self.rt
+        train = rt.arena.n_train > 0
+        if not (train or always_backward):
+            return
+        fused = fused and train and bool(rt.fused_layers)
+        rt.fused_active = fused         # only this backward updates the fused layers in place
+        try:
+            rt.run_backward(dlogits)
+        finally:
+            rt.fused_active = False
+        if between is not None:
+            between()
+        if train:
+            if fused:
+                self.optimizer_step(volumes, fused=True)
+            else:
+                self.optimizer_step(volumes)
+            if after is not None:
+                after()
 
     def optimizer_step(self, volumes: int = 1, fused: bool = False) -> None:
         """The arena optimizer: ONE launch over [decay | no-decay] of every replica in use (+ the device step counter).
@@ -335,6 +362,32 @@ class EntropyMinimizationTTA:
     # and returns it under the result key, [steps] - or [steps, B] for B > 1 volumes of a group
     records: Tuple[Tuple[str, str, torch.dtype], ...] = (("losses", "ent_loss", torch.float32),)
 
+    def _records(self) -> Tuple[Tuple, ...]:
+        """``records`` as one call reads them (after ``setup``: channels and views are known).  A method adds its wide
+        entries here, (result key, pool buffer, dtype, row shape): the buffer holds one row of that shape per replica, and
+        the history comes back as a copy, [steps, B, *row shape] for any B."""
+        return self.records
+
+    def _check_volumes(self, n: int, who: str = "", why: str = "", exc=ValueError) -> None:
+        """A call takes at most ``method.group`` volumes; ``who`` ("bnm_tta adapts ") and ``why`` (" (the reason)") are the
+        method's own clauses of the message."""
+        group = int(self.rt.group) if self.rt is not None else self.group
+        if n > group:
+            raise exc(f"method.group = {group}: {who}at most {group} volumes per call{why}, got {n}")
+
+    def _refuse_moddrop(self, clause: str) -> None:
+        """For the constructor of a method that stages something once per volume: modality dropout redraws it every step."""
+        if bool(get_config(method_block(self.cfg, "moddrop"), "enabled", False)):
+            raise NotImplementedError(f"method.moddrop.enabled: {clause}")
+
+    def _refuse_running_stats(self, who: str, forward: str, owner: str = "the plain forward") -> None:
+        """For the ``setup`` of a method with an extra train-mode ``forward``: it would move the running statistics."""
+        if self.rt.buffers:
+            norm = get_config(get_config(self.cfg, "model", {}) or {}, "norm", "BATCH")
+            raise NotImplementedError(f"{who}: model.norm = {norm!r} keeps running statistics, which {forward} would move "
+                                      f"(running_mean, running_var, num_batches_tracked belong to {owner}); use a model.norm "
+                                      "without them (INSTANCE, GROUP)")
+
     def _reset(self) -> None:
         """The episodic reset at the start of a volume: weights, optimizer state and running statistics of the source."""
         self.rt.arena.restore_source()
@@ -360,8 +413,8 @@ class EntropyMinimizationTTA:
         steps = self.steps if steps is None else int(steps)
         B = int(x.shape[0])
         # (without a group the batch items share the one weight set: any number of them - unless they are a volume's views)
-        if B > rt.group and (rt.group > 1 or self.views > 1):
-            raise ValueError(f"method.group = {rt.group}: at most {rt.group} volumes per call, got {B}")
+        if rt.group > 1 or self.views > 1:
+            self._check_volumes(B)
         if self.episodic:
             self._reset()
         C = x.shape[1]
@@ -376,8 +429,12 @@ class EntropyMinimizationTTA:
         x_cl = rt.stage_input(drop_modality(x, base_present) if restage else x)
         grouped = rt.group > 1
         rows, width = max(steps, 1), B if grouped else 1
-        recs = [(key, rt.pool.flat(buf, rt.group, dtype=dt, zero=True),
-                 rt.pool.flat(buf + "_hist", rows * width, dtype=dt).view(rows, width)) for key, buf, dt in self.records]
+        recs = []          # (key, wide, the buffer [slots, *row], its history [rows, slots, *row])
+        for key, buf, dt, *row in self._records():
+            row, slots = tuple(row[0]) if row else (), rt.group if row else width
+            numel = math.prod(row)
+            recs.append((key, bool(row), rt.pool.flat(buf, rt.group * numel, dtype=dt, zero=True).view(rt.group, *row)[:slots],
+                         rt.pool.flat(buf + "_hist", rows * slots * numel, dtype=dt).view(rows, slots, *row)))
         try:
             x_step, views = self._stage(x_cl)
             for t in range(steps):
@@ -388,8 +445,8 @@ class EntropyMinimizationTTA:
                         rt.stage_input(drop_modality(x, p))
                     present = p if wants_present else None
                 self._step(x_step, present, *views)
-                for _, buf, hist in recs:
-                    hist[t].copy_(buf[:width])
+                for _, _, buf, hist in recs:          # (outside the captured step)
+                    hist[t].copy_(buf)
             if masked and self.moddrop_p > 0.0 and restage:
                 rt.stage_input(drop_modality(x, base_present))
             rt.training = False
@@ -401,8 +458,8 @@ class EntropyMinimizationTTA:
             rt.use_sets = False
             rt.views = 1
         out = {"logits_cl": logits_cl}
-        for key, _, hist in recs:
-            out[key] = hist[:steps, 0] if width == 1 else hist[:steps]
+        for key, wide, _, hist in recs:
+            out[key] = hist[:steps, :B].clone() if wide else hist[:steps, 0] if width == 1 else hist[:steps]
         return out
 
     def logits(self, result: Dict[str, Any]) -> torch.Tensor:

@@ -36,7 +36,6 @@ forward, bit for bit.  With several windows the fused weight-gradient update and
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
@@ -44,7 +43,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .config import as_cfg, get_config
+from .config import expect, get_config, is_integer, is_number, method_block
 from .models.unet import UNetRuntime
 from .registry import register_plugin
 from .tta import EntropyMinimizationTTA
@@ -79,10 +78,6 @@ class WindowGrid:
         return len(self.origins)
 
 
-def _number(value: Any) -> bool:
-    return not isinstance(value, bool) and isinstance(value, (int, float)) and math.isfinite(value)
-
-
 def parse_window(value: Any, key: str = KEY) -> WindowSpec:
     """The ``window`` block: ``roi`` (three positive extents, required) and the optional ``overlap``, ``mode``, ``sigma_scale``,
     ``floor``, ``pad_value``; ``key``: the config key it came from, for the messages."""
@@ -96,23 +91,19 @@ def parse_window(value: Any, key: str = KEY) -> WindowSpec:
     if roi is None or isinstance(roi, (str, bytes)) or not hasattr(roi, "__iter__") or hasattr(roi, "keys"):
         raise ValueError(f"{key}.roi = {roi!r}: expected three window extents [d, h, w]")
     roi = list(roi)
-    if len(roi) != 3 or any(isinstance(r, bool) or not isinstance(r, int) or r < 1 for r in roi):
-        raise ValueError(f"{key}.roi = {roi!r}: expected three window extents [d, h, w], each an integer >= 1")
+    expect(len(roi) == 3 and all(is_integer(r) and r >= 1 for r in roi), f"{key}.roi", roi,
+           "three window extents [d, h, w], each an integer >= 1")
     overlap = get_config(value, "overlap", 0.5)
-    if not _number(overlap) or not (0.0 <= overlap < 1.0):
-        raise ValueError(f"{key}.overlap = {overlap!r}: expected a number with 0 <= overlap < 1")
+    expect(is_number(overlap) and 0.0 <= overlap < 1.0, f"{key}.overlap", overlap, "a number with 0 <= overlap < 1")
     mode = get_config(value, "mode", "gaussian")
-    if not isinstance(mode, str) or mode.lower() not in MODES:
-        raise ValueError(f"{key}.mode = {mode!r}: expected gaussian or constant")
+    expect(isinstance(mode, str) and mode.lower() in MODES, f"{key}.mode", mode, "gaussian or constant")
     sigma = get_config(value, "sigma_scale", 0.125)
-    if not _number(sigma) or sigma <= 0.0:
-        raise ValueError(f"{key}.sigma_scale = {sigma!r}: expected a finite number > 0")
+    expect(is_number(sigma) and sigma > 0.0, f"{key}.sigma_scale", sigma, "a finite number > 0")
     floor = get_config(value, "floor", 1e-3)
-    if not _number(floor) or not (0.0 < floor <= 1.0):
-        raise ValueError(f"{key}.floor = {floor!r}: expected a number with 0 < floor <= 1 (a weight of 0 has no normaliser)")
+    expect(is_number(floor) and 0.0 < floor <= 1.0, f"{key}.floor", floor,
+           "a number with 0 < floor <= 1 (a weight of 0 has no normaliser)")
     pad = get_config(value, "pad_value", 0.0)
-    if not _number(pad):
-        raise ValueError(f"{key}.pad_value = {pad!r}: expected a finite number")
+    expect(is_number(pad), f"{key}.pad_value", pad, "a finite number")
     return WindowSpec((int(roi[0]), int(roi[1]), int(roi[2])), float(overlap), mode.lower(), float(sigma), float(floor), float(pad))
 
 
@@ -180,12 +171,9 @@ class SlidingWindowTTA(EntropyMinimizationTTA):
 
     def __init__(self, config: Any = None):
         super().__init__(config)
-        m = get_config(as_cfg(config), "method", {}) or {}
-        self.window = parse_window(get_config(m, "window", None))
-        if bool(get_config(get_config(m, "moddrop", {}) or {}, "enabled", False)):
-            raise NotImplementedError("method.moddrop.enabled: true is not supported by window_tta (the windows are cropped once "
-                                      "per volume; a volume re-staged under every step's modality mask would need cropping "
-                                      "again every step)")
+        self.window = parse_window(get_config(method_block(config), "window", None))
+        self._refuse_moddrop("true is not supported by window_tta (the windows are cropped once per volume; a volume re-staged "
+                             "under every step's modality mask would need cropping again every step)")
         self._grid: Optional[WindowGrid] = None          # the current volume's windows; None: the volume is the roi
         self._graph_sets: Dict[Any, Dict[Tuple, Any]] = {}      # a captured step carries its grid: one set of graphs per grid
 
@@ -193,11 +181,7 @@ class SlidingWindowTTA(EntropyMinimizationTTA):
         super().setup(model, device)
         self._graph_sets.clear()
         self.rt.check_extent(*self.window.roi)          # the network runs on the roi: its own error, before anything is staged
-        if self.rt.buffers:
-            raise NotImplementedError(
-                f"window_tta: model.norm = {get_config(get_config(self.cfg, 'model', {}) or {}, 'norm', 'BATCH')!r} keeps running "
-                "statistics, which the train-mode forward of the windows would move (running_mean, running_var, "
-                "num_batches_tracked belong to the plain forward); use a model.norm without them (INSTANCE, GROUP)")
+        self._refuse_running_stats("window_tta", "the train-mode forward of the windows")
         if self.group > 1 and not isinstance(self.rt, UNetRuntime):
             raise NotImplementedError(f"method.group = {self.group}: {type(self.rt).__name__} (the deep-fusion family) takes the "
                                       "windows of a volume at group 1 only (its encoder families spend the set index on the "
@@ -217,9 +201,7 @@ class SlidingWindowTTA(EntropyMinimizationTTA):
         partial = rt.pool.flat("win_partial", ops.window_partials(logits), dtype=torch.float64)
         loss = rt.pool.flat("ent_loss", rt.group)
         ops.window_entropy_items(logits, dlogits, grid, rt.win_origins, rt.win_tables, partial, loss, softmax=self.softmax)
-        if rt.arena.n_train > 0:
-            rt.run_backward(dlogits)
-            self.optimizer_step(int(logits.shape[0]) // grid.windows)
+        self._backward_and_step(dlogits, int(logits.shape[0]) // grid.windows)
 
     # ------------------------------------------------------------------ per volume
     def _stage(self, x_cl: torch.Tensor) -> Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]:
@@ -248,11 +230,7 @@ class SlidingWindowTTA(EntropyMinimizationTTA):
         """``EntropyMinimizationTTA.adapt_volume`` for volumes [B,C,D,H,W] of any extents: the logits come back at the volume's
         extents, ``losses`` as Tent's, plus ``windows`` (W_n).  The windows of a volume share its parameter replica: a call
         takes at most ``method.group`` volumes."""
-        B = int(x.shape[0])
-        group = int(self.rt.group) if self.rt is not None else self.group
-        if B > group:
-            raise ValueError(f"method.group = {group}: window_tta adapts at most {group} volumes per call (the windows of a "
-                             f"volume share its parameter replica), got {B}")
+        self._check_volumes(int(x.shape[0]), "window_tta adapts ", " (the windows of a volume share its parameter replica)")
         extents = tuple(int(e) for e in x.shape[2:])
         # the grid before anything is staged: its refusal names the keys
         self._grid = None if extents == tuple(self.window.roi) else window_grid(extents, self.window)
