@@ -1045,6 +1045,50 @@ int mmtta_lame_refine(const mmtta_tensor* logits0, const mmtta_tensor* x, uint32
                       float weight, float sigma, int iterations, const mmtta_tensor* work, const mmtta_tensor* out,
                       int64_t* flipped, void* stream);
 
+/* ------------------------------------------------------------------ do-no-harm guard ------ */
+/* An output-level check of one adapted volume against the prediction the same method gives before its first step -
+ * csrc/guard.hip.  Where the adapted hard prediction has collapsed or exploded relative to that reference, the reference
+ * logits are put back.  The hard prediction is the evaluator's (mmtta_mask_dice_counts), per channel on either head:
+ * 1 / (1 + expf(-z)) >= threshold in fp32; a NaN logit is background.
+ *
+ * mmtta_guard_counts: counts int64 [N][R][3] = (s, a, i) = |reference mask|, |adapted mask|, |both| per (item, region),
+ *   zeroed by the call (one memset node) and filled by ONE streaming pass that reads both tensors once (32 B per voxel on
+ *   the dense route).  A wave reduces each bit by ballot and population count; a workgroup adds its sums with one integer
+ *   atomic per count.  Integer sums: the same in every run, and N items in one call equal N calls.
+ * mmtta_guard_select: every workgroup reads its item's 3 R counts and evaluates the rule itself (no decision launch, no
+ *   host read); the first workgroup of an item writes fallback int32 [N][R] (1: the region's logits are the reference's).
+ *   With Q = 2^16, A = min_agreement_q16, G = max_growth_q16, H = max_shrink_q16, m = min_voxels, region (n, r) FAILS iff
+ *       A > 0 and max(s, a) >= max(m, 1) and 2 i Q < A (s + a)        the Dice of the two masks is below A / Q
+ *    or G > 0 and a Q > G max(s, m)                                    the region grew more than G / Q times
+ *    or H > 0 and s Q > H max(a, m)                                    the region shrank more than H / Q times
+ *   in unsigned 64-bit arithmetic (no overflow for items below 2^31 voxels); equality passes in every clause; A = G = H = 0
+ *   never fails.  MMTTA_GUARD_SCOPE_VOLUME: an item with a failing region has every channel returned (all its flags are 1);
+ *   MMTTA_GUARD_SCOPE_REGION: the failing channels only.  The workgroups of a passing item exit at once: its `logits`,
+ *   pad lanes included, are not touched.  `counts` need not come from mmtta_guard_counts.
+ * `reference`, `adapted` / `logits`: channels-last fp32 [N,D,H,W,R] of one shape and row width.  Two routes, as
+ * mmtta_lame_refine's: dense 16-byte rows for R <= 4 (one 16-byte load per voxel and tensor; under the volume scope a failing
+ * row is one 16-byte store when R == 4 or `logits` is MMTTA_TENSOR_OWNS_PAD - its pad lanes then take the reference's -
+ * else the failing channels are 4-byte stores and pad lanes stay as they are), and one thread per voxel on any
+ * channels-last rows up to R <= 16 (pad lanes stay as they are).  Vector stores only, no float atomics, no scratch.
+ * MMTTA_ERR_INVALID before anything is launched: null pointers, shape or row-width mismatches between the two tensors,
+ * `reference` aliased by `logits`, a threshold that is not finite and in (0, 1), min_agreement_q16 > Q, max_growth_q16 /
+ * max_shrink_q16 neither 0 nor in [Q, 1024 Q], min_voxels < 0, an unknown scope.  R > 16, storages or strides without a
+ * kernel (bf16, channel stride != 1), more than 65535 items and items of 2^31 voxels or more are MMTTA_ERR_UNSUPPORTED. */
+#define MMTTA_GUARD_SCOPE_VOLUME 0
+#define MMTTA_GUARD_SCOPE_REGION 1
+typedef struct mmtta_guard_rule {
+  uint32_t min_agreement_q16; /* A: 0 (off) .. 65536 */
+  uint32_t max_growth_q16;    /* G: 0 (off) or 65536 .. 1024 * 65536 */
+  uint32_t max_shrink_q16;    /* H: likewise */
+  int32_t min_voxels;         /* m: 0 .. 2^31 - 1 */
+  int32_t scope;              /* MMTTA_GUARD_SCOPE_* */
+  int32_t reserved;           /* 0 */
+} mmtta_guard_rule;
+int mmtta_guard_counts(const mmtta_tensor* reference, const mmtta_tensor* adapted, float threshold, int64_t* counts,
+                       void* stream);
+int mmtta_guard_select(const int64_t* counts, const mmtta_guard_rule* rule, const mmtta_tensor* reference,
+                       const mmtta_tensor* logits, int32_t* fallback, void* stream);
+
 /* ------------------------------------------------------------------ CRF-regularised entropy */
 /* The entropy objective plus a pairwise grid-CRF (Potts) regulariser, loss and gradient in one pass - csrc/crf.hip (Tang et
  * al., ECCV 2018, "On Regularized Losses for Weakly-supervised CNN Segmentation"; the contour term of Hu et al., MICCAI

@@ -119,6 +119,11 @@ class WindowGrid(C.Structure):         # mmtta_window_grid
     _fields_ = [("extent", C.c_int32 * 3), ("count", C.c_int32 * 3)]
 
 
+class GuardRule(C.Structure):          # mmtta_guard_rule
+    _fields_ = [("min_agreement_q16", C.c_uint32), ("max_growth_q16", C.c_uint32), ("max_shrink_q16", C.c_uint32),
+                ("min_voxels", C.c_int32), ("scope", C.c_int32), ("reserved", C.c_int32)]
+
+
 _P = C.POINTER
 _SIGNATURES = {
     "mmtta_last_error": (C.c_char_p, []),
@@ -236,6 +241,8 @@ _SIGNATURES = {
                                         C.c_void_p]),
     "mmtta_lame_refine": (C.c_int, [_P(Tensor), _P(Tensor), C.c_uint32, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int,
                                     _P(Tensor), _P(Tensor), C.c_void_p, C.c_void_p]),
+    "mmtta_guard_counts": (C.c_int, [_P(Tensor), _P(Tensor), C.c_float, C.c_void_p, C.c_void_p]),
+    "mmtta_guard_select": (C.c_int, [C.c_void_p, _P(GuardRule), _P(Tensor), _P(Tensor), C.c_void_p, C.c_void_p]),
     "mmtta_crf_partials": (C.c_int64, [_P(Tensor)]),
     "mmtta_crf_entropy_items": (C.c_int, [_P(Tensor), _P(Tensor), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                           _P(Tensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -18,7 +18,7 @@ LIB = os.path.join(CSRC, "libmmtta.so")
 SOURCES = ["api.hip", "conv_igemm.hip", "conv_direct.hip", "conv_wgrad.hip", "pointwise.hip", "loss_optim_metric.hip", "memo.hip", "cotta.hip",
            "petal.hip", "eata.hip", "deyo.hip", "lame.hip", "augment.hip", "preproc.hip", "surface.hip", "calibration.hip", "components.hip", "lesionwise.hip", "lesionwise_hd95.hip",
            "fill_holes.hip", "surface_dice.hip", "crf.hip", "nuclear.hip", "input_norm.hip", "bias_field.hip", "modcons.hip", "affine.hip",
-           "window.hip"]
+           "window.hip", "guard.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-variable",
          "-Wno-unused-but-set-variable"]
 # Sources that read a norm-on-load are compiled a second time as the LeakyReLU instantiation (common.h: namespace

@@ -22,6 +22,7 @@ import torch
 
 from . import ops
 from .config import as_cfg, get_config
+from .guard import guard_enabled
 from .registry import get_plugin, register_evaluation_strategy
 
 EPS = 1e-7
@@ -508,6 +509,46 @@ def _add_calibration(acc: torch.Tensor, c: torch.Tensor, vol: Dict[str, torch.Te
     acc[:, 4:] += raw[:, :-2]
 
 
+GUARD_COLUMNS = 5          # per region: fallback flag, flips s + a - 2i, agreement numerator 2i and denominator s + a, source Dice
+GUARD_RAW = 7              # what a volume's passes leave per region: fallback, s, a, i, then (inter, pred, gt) of the reference
+
+
+def guard_columns(raw: torch.Tensor) -> torch.Tensor:
+    """raw int64 [R,7] = (fallback, s, a, i, inter, pred, gt of the reference's scored mask) -> float64 [5 R]: one column's
+    regions after another.  The source Dice is formed as ``dice_iou_from_counts`` forms Dice (fp32), so sharded, grouped and
+    single runs agree bit for bit."""
+    raw = raw.to(torch.int64).reshape(-1, GUARD_RAW)
+    s, a, i = raw[:, 1], raw[:, 2], raw[:, 3]
+    src = dice_iou_from_counts(raw[:, 4:7])[0]
+    return torch.cat([raw[:, 0].double(), (s + a - 2 * i).double(), (2 * i).double(), (s + a).double(), src.double()])
+
+
+def _add_guard(acc: torch.Tensor, c: torch.Tensor, vol: Dict[str, torch.Tensor]) -> None:
+    """Rows: fallbacks, flips, sum of agreement and its count (s + a > 0), sum of source Dice, sum of Dice - source Dice,
+    harmed volumes, valid volumes (Dice's own rule: a non-empty ground truth), volumes."""
+    fb, flips, num, den, src = c.reshape(GUARD_COLUMNS, -1)
+    valid, dice = vol["valid"], vol["dice"]
+    ok = (den > 0).to(torch.float64)
+    acc[0] += fb
+    acc[1] += flips
+    acc[2] += torch.where(den > 0, num / torch.where(den > 0, den, 1.0), 0.0)
+    acc[3] += ok
+    acc[4] += torch.where(valid > 0, src, 0.0)
+    acc[5] += torch.where(valid > 0, dice - src, 0.0)
+    acc[6] += ((valid > 0) & (dice < src)).to(torch.float64)
+    acc[7] += valid
+    acc[8] += 1.0
+
+
+def _guard_keys(out, prefix, acc, regions, p) -> None:
+    _mean_keys(out, prefix, regions, "guard_fallback", acc[0], acc[8])
+    _mean_keys(out, prefix, regions, "guard_agreement", acc[2], acc[3], avg=False)
+    _mean_keys(out, prefix, regions, "guard_flips", acc[1], acc[8], avg=False)
+    _mean_keys(out, prefix, regions, "src_dc", acc[4], acc[7])
+    _mean_keys(out, prefix, regions, "dc_gain", acc[5], acc[7], avg=False)
+    _mean_keys(out, prefix, regions, "harmed", acc[6], acc[7], avg=False)
+
+
 def _calibration_keys(out, prefix, acc, regions, p) -> None:
     for col, key in enumerate(("ece", "brier", "nll")):
         _mean_keys(out, prefix, p[1], key, acc[:, col], acc[:, 3])
@@ -518,7 +559,8 @@ def _calibration_keys(out, prefix, acc, regions, p) -> None:
 # and then, for every enabled block, what its ``*_columns`` function makes of one volume (one column's or one tolerance's
 # regions after another).  Region-wise NSD is valid where Dice's ``valid`` is, lesion-wise NSD where the ``valid`` row of the
 # volume's lesion-wise columns is.  The calibration, the volume's raw table of ``ops.calibration_bins``, is last, so
-# ``reliability_from_table`` finds it at the row's end.
+# ``reliability_from_table`` finds it at the row's end; the guard's block (``method.guard``, switched on by ``seg_tta_eval``
+# alone and passed to ``add_row`` by name only) sits right before it.
 BLOCKS: Tuple[Block, ...] = (
     Block("surface", lambda R, p: 2 * R, lambda R, p: (3, R), lambda v: v["surface"], _add_surface, _surface_keys),
     Block("components", lambda R, p: 3 * R, lambda R, p: (4, R), lambda v: stat_columns(v["components"]), _add_sums,
@@ -535,6 +577,8 @@ BLOCKS: Tuple[Block, ...] = (
           lambda acc, c, vol: _add_nsd(acc, c, vol["lesionwise"].reshape(LESIONWISE_COLUMNS, -1)[1]), _nsd_keys("lw_nsd")),
     Block("surface_dice", lambda R, p: _n(p) * R, lambda R, p: (2, _n(p), R), lambda v: surface_dice_columns(v["surface_dice"]),
           lambda acc, c, vol: _add_nsd(acc, c, vol["valid"]), _nsd_keys("nsd")),
+    Block("guard", lambda R, p: GUARD_COLUMNS * R, lambda R, p: (9, R), lambda v: guard_columns(v["guard"]), _add_guard,
+          _guard_keys),
     Block("calibration", lambda R, p: _n(p[1]) * (3 * p[0] + 2), lambda R, p: (_n(p[1]), 4 + 3 * p[0]),
           lambda v: v["calibration"].reshape(-1), _add_calibration, _calibration_keys),
 )
@@ -548,13 +592,15 @@ class Layout(NamedTuple):
 
 def table_layout(regions: Any, surface: bool = False, bins: int = 0, calibration_regions: Any = None,
                  components: bool = False, lesionwise: bool = False, fill_nest: bool = False, lesionwise_hd95: bool = False,
-                 surface_dice: Any = (), lesionwise_nsd: Any = ()) -> Layout:
+                 surface_dice: Any = (), lesionwise_nsd: Any = (), guard: bool = False) -> Layout:
     """Where the enabled blocks sit in a row.  ``regions`` and ``calibration_regions`` are names, or just how many there are;
     ``bins`` > 0 switches the calibration on, with one row per calibration region (default: the regions; ``["all"]`` for a
-    softmax head); ``surface_dice`` and ``lesionwise_nsd`` are tolerances in mm, or their number."""
+    softmax head); ``surface_dice`` and ``lesionwise_nsd`` are tolerances in mm, or their number; ``guard``: the guard's
+    block (fall-backs, agreement with and Dice of the pre-adaptation prediction)."""
     R = _n(regions)
     params = {"surface": surface, "components": components, "fill_nest": fill_nest, "lesionwise": lesionwise,
               "lesionwise_hd95": lesionwise_hd95, "lesionwise_nsd": lesionwise_nsd, "surface_dice": surface_dice,
+              "guard": bool(guard),
               "calibration": (int(bins), regions if calibration_regions is None else calibration_regions) if bins else None}
     at, slices = 3 + 3 * R, {}
     for b in BLOCKS:
@@ -613,6 +659,7 @@ class RegionAccumulator:
             vol["surface"] = torch.cat([torch.as_tensor(hd95, dtype=torch.float64), torch.as_tensor(asd, dtype=torch.float64)])
         vol["valid"] = torch.tensor([1.0 if bool(v) else 0.0 for v in valid], dtype=torch.float64)
         both = torch.stack([torch.as_tensor(dice, dtype=torch.float64), torch.as_tensor(iou, dtype=torch.float64)])
+        vol["dice"] = both[0]
         for dom in (None, domain):
             acc = self.acc["dice"][dom]
             acc[:2] += torch.where(vol["valid"] > 0, both, 0.0)
@@ -785,6 +832,7 @@ class SegmentationEvaluationStrategy:
         nod = get_config(tcfg, "normalize_on_device", None)
         self.normalize_on_device = (not synthetic) if nod is None else bool(nod)
         self._tcfg = tcfg
+        self.enable_guard = False          # seg_tta_eval with ``method.guard.enable``: the guard's block of the table
 
     @property
     def cal_bins(self) -> int:
@@ -877,7 +925,7 @@ class SegmentationEvaluationStrategy:
         return dict(surface=self.enable_surface, bins=self.cal_bins, calibration_regions=self.calibration_regions,
                     components=self.enable_postprocess, fill_nest=self.enable_fill_nest, lesionwise=self.enable_lesionwise,
                     lesionwise_hd95=self.enable_lesionwise_hd95, surface_dice=self.sd_tolerances,
-                    lesionwise_nsd=self.ln_tolerances)
+                    lesionwise_nsd=self.ln_tolerances, guard=self.enable_guard)
 
     def layout(self) -> Layout:
         return table_layout(self.region_order, **self.switches())
@@ -892,7 +940,7 @@ class SegmentationEvaluationStrategy:
             raise ValueError(f"[BratsSegEval] model logits must be [B,{R},D,H,W], got {tuple(logits.shape)}")
         on = self.layout().slices
         counts = torch.empty((B, R, 3), dtype=torch.int64, device=y.device)
-        need_mask = self.gather_masks or bool(on.keys() - {"calibration"})       # every other block reads the mask
+        need_mask = self.gather_masks or bool(on.keys() - {"calibration", "guard"})       # every other block reads the mask
         mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if need_mask else None
         ops.mask_dice_counts(logits, y, self.threshold, counts, mask, logits_channels_last=channels_last)
         raw: Dict[str, Any] = {}
@@ -1147,6 +1195,8 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         # north star: "RCCL ... used only to all-gather final Dice/logits": with `evaluation.gather_masks` the thresholded
         # uint8 masks [R,D,H,W] of every volume are gathered to every rank as well (a second all_gather, off by default)
         self.gather_masks = bool(get_config(self.config, "evaluation.gather_masks", False))
+        # the do-no-harm guard (guard.py): the table takes its block and ``_submit`` scores the reference prediction as well
+        self.enable_guard = guard_enabled(self.config)
         self.local_masks: List[Tuple[int, torch.Tensor]] = []
         self.last_masks: Dict[int, torch.Tensor] = {}
         self.plugin = None
@@ -1204,8 +1254,26 @@ class TTASegmentationEvaluationStrategy(SegmentationEvaluationStrategy):
         independently) - on the lane's stream; nothing here waits for the GPU."""
         res = self.plugins[lane].adapt_volume(xb)
         job = self.queue_passes(res["logits_cl"], yb, channels_last=True)
+        if self.enable_guard:
+            job["raw"]["guard"] = self.guard_launch(res, yb)
         job["keep"] = (xb, yb, res)
         return job
+
+    def guard_launch(self, res: Dict[str, Any], y: torch.Tensor) -> torch.Tensor:
+        """Queue the scoring of the guard's reference prediction on the current stream -> device int64 [B,R,7] = (fallback,
+        s, a, i, then inter, pred, gt of the reference's mask).  That mask is thresholded like the returned one and, with the
+        blocks on, filtered, filled and nested in place like it (its post-processing stats are discarded): the source Dice
+        and ``<region>_dc`` describe masks that went through the same pipeline."""
+        B, R = y.shape[0], y.shape[1]
+        on = self.layout().slices
+        counts = torch.empty((B, R, 3), dtype=torch.int64, device=y.device)
+        mask = torch.empty(tuple(y.shape), dtype=torch.uint8, device=y.device) if "components" in on else None
+        ops.mask_dice_counts(res["guard_reference_cl"], y, self.threshold, counts, mask, logits_channels_last=True)
+        if "components" in on:
+            counts, _ = self.postprocess_launch(mask, y)
+        if "fill_nest" in on:
+            counts, _ = self.fill_nest_launch(mask, y)
+        return torch.cat([res["guard_fallback"].to(torch.int64).unsqueeze(-1), res["guard_counts"], counts], dim=-1)
 
     def _finish(self, job: Dict[str, Any]) -> List[torch.Tensor]:
         """First host read of a queued group -> the table rows of its volumes."""

@@ -13,7 +13,7 @@ import math
 import os
 import threading
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -1311,6 +1311,33 @@ def lame_refine(logits0: torch.Tensor, x: Optional[torch.Tensor], out: torch.Ten
     check(_lib.load().mmtta_lame_refine(C.byref(t0), None if tx is None else C.byref(tx), mask, 1 if softmax else 0,
                                         int(connectivity), float(weight), float(sigma), int(iterations), C.byref(tw),
                                         C.byref(to), ptr(flipped), stream_ptr()), "lame_refine")
+
+
+def guard_counts(reference: torch.Tensor, adapted: torch.Tensor, threshold: float, counts: torch.Tensor) -> None:
+    """The guard's counts (include/mmtta.h, mmtta_guard_counts): ``counts`` int64 [N,R,3] = (s, a, i) = the voxels of the
+    ``reference`` mask, of the ``adapted`` mask and of both, per item and region, under the evaluator's rule
+    sigmoid(z) >= ``threshold``.  Channels-last fp32 [N,D,H,W,R] logits of one shape and row width; zeroed by the call."""
+    n, r = int(reference.shape[0]), int(reference.shape[-1])
+    if counts.dtype != torch.int64 or not counts.is_cuda or not counts.is_contiguous() or counts.numel() < n * r * 3:
+        raise MmttaError(f"guard_counts: counts must be contiguous device int64 of at least {n * r * 3} elements ([N,R,3])")
+    tr, ta = desc_cl(reference), desc_cl(adapted)
+    check(_lib.load().mmtta_guard_counts(C.byref(tr), C.byref(ta), float(threshold), ptr(counts), stream_ptr()), "guard_counts")
+
+
+def guard_select(counts: torch.Tensor, rule: Any, reference: torch.Tensor, logits: torch.Tensor, fallback: torch.Tensor) -> None:
+    """The guard's decision and fall-back (include/mmtta.h, mmtta_guard_select): the integer rule ``rule`` (a
+    ``guard.GuardRule`` or an ``_lib.GuardRule``) on ``counts`` int64 [N,R,3] -> ``fallback`` int32 [N,R], and the
+    ``reference`` logits copied over ``logits`` in place where it fails (the whole item, or the failing channels under the
+    region scope); a passing item's logits are not touched.  Nothing is read on the host."""
+    n, r = int(reference.shape[0]), int(reference.shape[-1])
+    if counts.dtype != torch.int64 or not counts.is_cuda or not counts.is_contiguous() or counts.numel() < n * r * 3:
+        raise MmttaError(f"guard_select: counts must be contiguous device int64 of at least {n * r * 3} elements ([N,R,3])")
+    if fallback.dtype != torch.int32 or not fallback.is_cuda or not fallback.is_contiguous() or fallback.numel() < n * r:
+        raise MmttaError(f"guard_select: fallback must be contiguous device int32 of at least {n * r} elements ([N,R])")
+    rs = rule if isinstance(rule, _lib.GuardRule) else rule.struct()
+    tr, tl = desc_cl(reference), desc_cl(logits)
+    check(_lib.load().mmtta_guard_select(ptr(counts), C.byref(rs), C.byref(tr), C.byref(tl), ptr(fallback), stream_ptr()),
+          "guard_select")
 
 
 CRF_FORMS = ("potts", "quadratic")

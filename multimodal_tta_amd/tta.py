@@ -25,6 +25,7 @@ import torch
 from . import ops
 from .config import as_cfg, get_config, method_block
 from .engine import HeadLossTail
+from .guard import parse_guard
 from .models.base import DEFAULT_NO_DECAY_KEYS, HipSegModel
 from .ops import MmttaError
 from .registry import register_plugin
@@ -138,6 +139,9 @@ class EntropyMinimizationTTA:
         self.softmax = bool(get_config(crit, "softmax", False))
         if self.precision not in ops.PRECISIONS:
             raise ValueError(f"method.precision={self.precision}: expected one of {sorted(ops.PRECISIONS)}")
+        # the do-no-harm guard (guard.py): off unless ``method.guard.enable``; then every volume is checked against what this
+        # plugin returns for it at ``steps = 0``
+        self.guard = parse_guard(cfg)
         self.model: Optional[HipSegModel] = None
         self.rt = None
         self._graphs: Dict[Tuple, torch.cuda.CUDAGraph] = {}
@@ -402,11 +406,58 @@ class EntropyMinimizationTTA:
         """The returned logits: the eval-mode forward of the staged volumes (the images are packed)."""
         return self._forward(x_cl, present)
 
+    @staticmethod
+    def _whole_rows(t: torch.Tensor) -> torch.Tensor:
+        """A channels-last view with its pad lanes, where the view owns them: the rows as one run of memory."""
+        if getattr(t, "_mmtta_owns_pad", False) and int(t.stride(3)) > int(t.shape[4]):
+            return torch.as_strided(t, (*t.shape[:4], int(t.stride(3))), t.stride(), t.storage_offset())
+        return t
+
+    def _guard_reference(self, x_cl: torch.Tensor, x_step: torch.Tensor, present: Optional[Sequence[bool]]) -> torch.Tensor:
+        """What this plugin returns at ``steps = 0``, after the reset and ``_stage`` and before the first step, copied out of
+        the runtime's buffer into a pool buffer of the same row width (the final forward writes the runtime's again).  It
+        leaves no trace: an eval-mode forward moves no running statistics, the images it packs are those the first step
+        packs, and the runtime's switches are put back as ``_stage`` left them."""
+        rt = self.rt
+        training, views = rt.training, rt.views
+        try:
+            rt.training = False
+            ops.Workspace.lane = self.lane
+            rt.use_sets = rt.group > 1
+            rt.pack_all(fused_current=True)
+            z = self._final_logits(x_cl, x_step, present)
+            n, d, h, w, r = z.shape
+            ref = rt.pool.cl("guard_reference", n, d, h, w, r, ldc=max(int(z.stride(3)), r), zero=True)
+            if getattr(z, "_mmtta_owns_pad", False):
+                self._whole_rows(ref).copy_(self._whole_rows(z))          # one run of 16-byte rows
+            else:
+                ref.copy_(z)
+        finally:
+            rt.use_sets = False
+            rt.views = views
+            rt.training = training
+        return ref
+
+    def _guard_apply(self, reference: torch.Tensor, logits_cl: torch.Tensor, out: Dict[str, Any]) -> None:
+        """Queue the counts and the select on the current stream, outside the captured step; nothing is read on the host.
+        ``out`` gets ``guard_counts`` int64 [B,R,3], ``guard_fallback`` int32 [B,R] and ``guard_reference_cl``."""
+        n, r = int(logits_cl.shape[0]), int(logits_cl.shape[-1])
+        pool = self.rt.pool
+        counts = pool.flat("guard_counts", n * r * 3, dtype=torch.int64, zero=True)
+        fallback = pool.flat("guard_fallback", n * r, dtype=torch.int32, zero=True)
+        ops.guard_counts(reference, logits_cl, self.guard.threshold, counts)
+        ops.guard_select(counts, self.guard.rule, reference, logits_cl, fallback)
+        out["guard_counts"] = counts.view(n, r, 3).clone()
+        out["guard_fallback"] = fallback.view(n, r).clone()
+        out["guard_reference_cl"] = reference
+
     @torch.no_grad()
     def adapt_volume(self, x: torch.Tensor, steps: Optional[int] = None) -> Dict[str, Any]:
         """x: [1,C,D,H,W] fp32 on the plugin's device - or, with ``method.group`` = G > 1, up to G volumes [B,C,D,H,W]
         that adapt independently (volume b on parameter replica b).  Returns the final logits (channels-last view
-        [B,D,H,W,R]) and the per-step ``records``: the losses ([steps], or [steps, B] for a group)."""
+        [B,D,H,W,R]) and the per-step ``records``: the losses ([steps], or [steps, B] for a group).  With
+        ``method.guard.enable`` the logits of a volume (or region) that fails the guard's rule are the reference's, and the
+        result also holds ``guard_counts``, ``guard_fallback`` and ``guard_reference_cl`` (``guard.py``)."""
         if self.rt is None:
             raise MmttaError("call setup(model, device) first")
         rt = self.rt
@@ -437,6 +488,9 @@ class EntropyMinimizationTTA:
                          rt.pool.flat(buf + "_hist", rows * slots * numel, dtype=dt).view(rows, slots, *row)))
         try:
             x_step, views = self._stage(x_cl)
+            reference = None
+            if self.guard.enable:
+                reference = self._guard_reference(x_cl, x_step, base_present if wants_present else None)
             for t in range(steps):
                 present = None
                 if masked:
@@ -458,6 +512,8 @@ class EntropyMinimizationTTA:
             rt.use_sets = False
             rt.views = 1
         out = {"logits_cl": logits_cl}
+        if reference is not None:
+            self._guard_apply(reference, logits_cl, out)
         for key, wide, _, hist in recs:
             out[key] = hist[:steps, :B].clone() if wide else hist[:steps, 0] if width == 1 else hist[:steps]
         return out
